@@ -9,6 +9,9 @@ all-gather of counts at the end (RCCL).
 Prints ONE JSON line (rank 0):
   value         descriptors/s with the batch already resident in HBM when the timed region starts and the
                 records left in HBM (hesaff_detect_batch_device) -- the harness contract for `value`;
+                ms_per_step, images_per_s, roofline, roofline_detect and stage_ms_per_step come from the same timed steps.
+A plain run does only that: set-up, warm-up, the --steps timed steps, --dump-outputs if given, the line.  The legs
+below take runs of their own and are measured only with --full (they are null otherwise):
   host_path     the same batch through hesaff_detect_batch: host images in -> H2D -> kernels -> D2H -> host
                 records out, chunks pipelined (SURVEY.md 8d: "H2D -> D2H inclusive"), in the same run;
   end_to_end    hesaff_process_files on EVERY rank at once: PGM files on a RAM disk -> pool threads read them into pinned buffers ->
@@ -19,10 +22,14 @@ Prints ONE JSON line (rank 0):
                 per-device end-to-end rate of an 8-GPU node;
   text_export   the host formatter alone (hesaff_write_sift_batch, the stage API's writer) on a bounded subset;
   photo_density the same device-resident step on mosaics of real photographs (scikit-learn's sample images);
-  roofline      the dominant pyramid kernel (k_blur_hess_march: Gaussian + det-of-Hessian), timed live with HIP
-                events on the library's stream;
+  jpeg_path, fast_modes  colour JPEG files through the file path; the step with hesaff_params.fast = 2;
+  hbm_probe     plain streaming kernels on this device (roofline_detect.frac_of_read_probe is measured against it);
   cpu_baseline  the CPU oracle (a port of the reference, 1 thread) on a bounded sample of the same images;
                 cpu_baseline_multicore: one oracle process per physical core.
+roofline (the dominant pyramid kernel, k_blur_hess_march: Gaussian + det-of-Hessian) is timed live with HIP events on the
+library's stream during the timed steps, in a plain run as well.
+
+--dump-outputs DIR writes what the last timed step returned (dump_outputs below) as .npy files for comparing two builds.
 """
 import argparse
 import json
@@ -503,6 +510,65 @@ def contexts_leg(host_imgs, W, H, n_files, chunk, device, k=4):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_MAX_RECORDS = 65536   # records written by --dump-outputs over all ranks: 137 float32 each, about 36 MB
+DUMP_RUN = 64              # records per contiguous run of the sample when a step returns more than that
+DUMP_SEED = 20261016
+
+
+def dump_runs(total, world):
+    """-> (starts, run): the records --dump-outputs copies out of `total` are rows starts[k] .. starts[k] + run - 1.
+    All of them up to the cap (DUMP_MAX_RECORDS over the ranks); beyond it cap / DUMP_RUN runs of DUMP_RUN rows, one at a
+    seeded offset inside each equal slice of the record array, so that the same total selects the same rows."""
+    cap = max(DUMP_RUN, DUMP_MAX_RECORDS // world)
+    if total <= cap:
+        return np.zeros(1 if total > 0 else 0, np.int64), max(int(total), 0)
+    n_runs = cap // DUMP_RUN
+    stride = total // n_runs           # >= DUMP_RUN because total > n_runs * DUMP_RUN
+    rng = np.random.default_rng(DUMP_SEED)
+    return np.arange(n_runs, dtype=np.int64) * stride + rng.integers(0, stride - DUMP_RUN + 1, n_runs), DUMP_RUN
+
+
+def dump_outputs(out_dir, calls, rank, world):
+    """--dump-outputs: what the last timed step returned to its caller, as .npy files (float64 counts and row indices, float32
+    records).  calls = [(count_hessian, count_desc, d_keys, total)] of the step's library calls.  The per-image counts of every
+    call are written whole.  The records (hesaff_keypoint, left in HBM) are those of the step's last call - a step of more than
+    one call (--scaling strong with more images than --batch) repeats the same images - in full or as the fixed sample of
+    dump_runs.  With several ranks every rank writes its own files (suffix _rank<r>)."""
+    import ctypes
+    import torch
+    import hesaff_amd
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "_rank%d" % rank if world > 1 else ""
+    _, cd_last, d_keys, total = calls[-1]
+    starts, run = dump_runs(total, world)
+    rows = (starts[:, None] + np.arange(run, dtype=np.int64)).ravel()
+    if rows.size and (rows.min() < 0 or rows.max() >= total):
+        raise RuntimeError("record sample outside the %d records" % total)
+    rec = hesaff_amd.KEYPOINT_DTYPE.itemsize
+    keys = np.zeros(0, hesaff_amd.KEYPOINT_DTYPE)
+    if rows.size:
+        buf = torch.empty(rows.size * rec, dtype=torch.uint8, device="cuda")
+        # the HIP runtime torch loaded (a second runtime in the process would not see the GPU); device to device, run by run
+        hip = ctypes.CDLL(os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"))
+        for k, s in enumerate(starts):
+            rc = hip.hipMemcpy(ctypes.c_void_p(buf.data_ptr() + k * run * rec), ctypes.c_void_p(d_keys + int(s) * rec), ctypes.c_size_t(run * rec), 3)
+            if rc != 0:
+                raise RuntimeError("hipMemcpy of the device records failed (%d)" % rc)
+        keys = np.frombuffer(buf.cpu().numpy().tobytes(), dtype=hesaff_amd.KEYPOINT_DTYPE)
+    frame = np.stack([keys[f] for f in ("x", "y", "s", "a11", "a12", "a21", "a22", "response")], axis=1) if rows.size else np.zeros((0, 8), np.float32)
+    out = {
+        "count_hessian": np.concatenate([c[0] for c in calls]).astype(np.float64),
+        "count_desc": np.concatenate([c[1] for c in calls]).astype(np.float64),
+        "keys_row": rows.astype(np.float64),                                                         # row in the last call's ordered records
+        "keys_image": np.searchsorted(np.cumsum(cd_last), rows, side="right").astype(np.float64),   # image of the last call it belongs to
+        "keys_frame": frame.astype(np.float32),                                                      # x y s a11 a12 a21 a22 response
+        "keys_type": keys["type"].astype(np.float32),
+        "keys_desc": keys["desc"].astype(np.float32),
+    }
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), a)
+
+
 def launch_ranks(n):
     """Start n ranks of this script under torch.distributed.run on this node and wait for them.  Nothing in this process
     has initialised the GPU (torch is not even imported yet); the ranks are ordinary child processes."""
@@ -556,7 +622,14 @@ def main():
                     help="weak: every rank owns --batch images per step; strong: --global-images images per step in total, "
                          "split evenly over the ranks (BASELINE.json config 4: 2048 UHD images over 8 GPUs)")
     ap.add_argument("--global-images", type=int, default=2048, help="images per step of the whole job under --scaling strong")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every leg beyond the headline (host path, file paths, JPEG, fast mode, photographs, HBM probe, "
+                         "text export, CPU baselines); without it the run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (per-image counts, a fixed sample of the records) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # `python bench.py --gpus N` without a launcher: this process starts the N ranks itself (one process per GPU under
     # torch.distributed.run) BEFORE anything here touches torch or the GPU, relays rank 0's JSON line and exits with the
@@ -627,13 +700,16 @@ def main():
     bh = {"ms": 0.0, "bytes": 0.0, "launches": 0, "ex_ms": 0.0, "ex_bytes": 0.0, "ex_launches": 0}
     stage = {"pyramid_ms": 0.0, "detect_ms": 0.0, "affine_ms": 0.0, "patch_ms": 0.0, "sift_ms": 0.0, "pack_ms": 0.0, "total_ms": 0.0}
     tot = {"desc": 0, "hess": 0, "imgs": 0, "pyr_bytes": 0.0}
+    last_calls = []   # (count_hessian, count_desc, d_keys, total) of the library calls of the latest step (--dump-outputs)
 
     def step(timed):
         # one pass of the hot path over this rank's images of a step
         done = 0
+        del last_calls[:]
         while done < per_rank:
             nb = min(B, per_rank - done)
-            ch, cd, _, total = ctx.detect_batch_device(imgs.data_ptr(), nb, W, H)
+            ch, cd, dk, total = ctx.detect_batch_device(imgs.data_ptr(), nb, W, H)
+            last_calls.append((ch, cd, dk, total))
             done += nb
             if timed:
                 tot["desc"] += int(cd.sum()); tot["hess"] += int(ch.sum()); tot["imgs"] += nb
@@ -669,6 +745,8 @@ def main():
     counts = gather_counts([n_hess, n_desc, tot["imgs"]], device=coll_dev if grouped else None)
     tot_hess, tot_desc, tot_imgs = [int(v) for v in counts.sum(axis=0)]
     per_rank_images = [int(v) for v in counts[:, 2]]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_calls, rank, world)   # the records of the last call are valid until the context's next call
     ctx.close()
 
     # ---- host-inclusive legs, EVERY rank at the same time: hesaff_detect_batch, then the file path ----
@@ -676,7 +754,7 @@ def main():
     end_to_end = None
     end_to_end_budgeted = None
     host_imgs = None
-    if not args.no_host_path:
+    if args.full and not args.no_host_path:
         hp = hesaff_amd.default_params()
         hp.max_batch = max(1, min(args.host_chunk, B))
         hctx = hesaff_amd.HesaffContext(hp, device=local_rank)
@@ -777,20 +855,20 @@ def main():
         dist.destroy_process_group()
         return
     fast_modes = None
-    if args.fast_steps > 0 and not args.no_host_path:
+    if args.full and args.fast_steps > 0 and not args.no_host_path:
         fast_modes = {"what": "the same device-resident step with hesaff_params.fast = 2 (windows larger than the 41 x 41 patch sampled from the "
                               "scale space instead of warped and blurred, affine.cpp:114-135); NOT bit-exact, not the headline value; "
                               "measured effect on descriptors and matching: DESIGN.md, profiles/",
                       "fast_2": fast_leg(hesaff_amd, torch, imgs, local_rank, B, H, W, 2, args.fast_steps)}
     del imgs
     torch.cuda.empty_cache()
-    probe = hbm_probe(torch, dev)
+    probe = hbm_probe(torch, dev) if args.full else None
     photo = None
-    if args.photo_steps > 0 and args.density == "dense" and not args.no_host_path:
+    if args.full and args.photo_steps > 0 and args.density == "dense" and not args.no_host_path:
         photo = density_leg(hesaff_amd, torch, dev, local_rank, B, H, W, g_lo, args.photo_steps)
     # the host formatter alone (the writer of the stage API; the file path above formats on the device)
     text_export = None
-    if not args.no_host_path and args.export_images > 0:
+    if args.full and not args.no_host_path and args.export_images > 0:
         hp = hesaff_amd.default_params()
         hp.max_batch = max(1, min(args.host_chunk, B))
         ne = min(args.export_images, B)
@@ -813,7 +891,7 @@ def main():
             finally:
                 shutil.rmtree(tmp, ignore_errors=True)
     jpeg_path = None
-    if args.jpeg_images > 0 and not args.no_host_path and args.density == "dense":
+    if args.full and args.jpeg_images > 0 and not args.no_host_path and args.density == "dense":
         jpeg_path = jpeg_path_leg(hesaff_amd, W, H, args.jpeg_images, args.e2e_chunk, local_rank, args.e2e_decode_threads, args.e2e_write_threads)
     cpu_sample = host_imgs
 
@@ -834,6 +912,7 @@ def main():
             "collective_backend": (backend if backend != "nccl" else "nccl (RCCL)") if grouped else None,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": dt / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": args.scaling,
@@ -860,7 +939,7 @@ def main():
             "roofline_detect": {"bound": "hbm", "kernel": "k_extrema_march (the three 3x3x3 extrema scans of an octave in one launch; SURVEY.md 8d: "
                                                           "B_ext = 20 bytes per pixel and octave, five response planes read once)",
                                 "achieved": ex_achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ex_achieved / HBM_PEAK_GBS,
-                                "frac_of_read_probe": ex_achieved / probe["read_only_GBs"] if probe.get("read_only_GBs") else None,
+                                "frac_of_read_probe": ex_achieved / probe["read_only_GBs"] if probe and probe.get("read_only_GBs") else None,
                                 "launches": bh["ex_launches"], "avg_launch_ms": bh["ex_ms"] / max(bh["ex_launches"], 1),
                                 "stage": {"what": "whole detection stage (map clear, extrema, localisation, dedupe, ordering scans) against B_ext",
                                           "achieved": (bh["ex_bytes"] / args.steps / 1e9) / (st["detect_ms"] / 1e3) if st["detect_ms"] > 0 else 0.0}},
@@ -880,7 +959,7 @@ def main():
                                    "achieved": (pyr_bytes_step / 1e9) / (st["pyramid_ms"] / 1e3) if st["pyramid_ms"] > 0 else 0.0,
                                    "frac": ((pyr_bytes_step / 1e9) / (st["pyramid_ms"] / 1e3)) / HBM_PEAK_GBS if st["pyramid_ms"] > 0 else 0.0}},
         }
-        if not args.no_cpu_baseline:   # rank 0 only, also when world > 1 (the other ranks are done)
+        if args.full and not args.no_cpu_baseline:   # rank 0 only, also when world > 1 (the other ranks are done)
             from tests import _oracle
             if cpu_sample is None:
                 cpu_sample = list(band_noise_batch_torch(min(B, 16), H, W, seed=1234 + g_lo, device=dev, bands=bands).cpu().numpy()) \

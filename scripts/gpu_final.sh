@@ -1,13 +1,14 @@
-# usage (through gpurun): bash scripts/gpu_final.sh <tag>
+# usage: bash scripts/gpu_final.sh <tag> <directory of the pass's outputs, relative to the repository: the one the steps below write to>
 # round-end evidence, ONE pass (needs the tuning library: `make -C hesaff_amd/csrc tuning` before the gpurun call): GPU test suite, default bench line,
 # rocprofv3 stats + HBM traffic of the bench command, per-kernel PMC tables (dense and photographs), counters of the overlapped step,
 # per-kernel serial times (parity, fast = 2, photographs), fast-mode reports, config-5 sequence tables (band noise and photograph, fast 0 / 2),
 # the file path inside 2 / 4 / 8 CPUs with per-thread CPU seconds, end-to-end thread sweep, JPEG lists (UHD and 1024x768; pixels on the device / on the host)
 cd $GRAFT_REPO_ROOT
 TAG=$1
+OUT=${2:?usage: bash scripts/gpu_final.sh <tag> <output directory>}
 mkdir -p gpurun_out
 timeout 2400 python -m pytest tests -m gpu -q > gpurun_out/${TAG}_tests.log 2>&1; tail -4 gpurun_out/${TAG}_tests.log
-T0=$(date +%s); timeout 1200 python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err; echo "bench.py wall seconds: $(( $(date +%s) - T0 ))" | tee -a gpurun_out/${TAG}_bench.err
+T0=$(date +%s); timeout 1200 python bench.py --full > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"; echo "bench.py wall seconds: $(( $(date +%s) - T0 ))" | tee -a "$OUT/${TAG}_bench.err"
 bash scripts/gpu_profile_round.sh ${TAG}_prof > gpurun_out/${TAG}_prof.log 2>&1; tail -20 gpurun_out/${TAG}_prof.log | cut -c1-400
 bash scripts/gpu_pmc2.sh ${TAG} 8 > gpurun_out/${TAG}_pmc.md 2>&1; cat gpurun_out/${TAG}_pmc.md
 bash scripts/gpu_pmc_lds.sh ${TAG} 8 > gpurun_out/${TAG}_pmc_lds.md 2>&1; cat gpurun_out/${TAG}_pmc_lds.md

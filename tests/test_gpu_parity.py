@@ -735,7 +735,7 @@ def test_bench_two_ranks_on_one_gpu():
     env = dict(os.environ, BENCH_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "3",
-           "--width", "640", "--height", "480", "--cpu-images", "1", "--cpu-workers", "0"]
+           "--width", "640", "--height", "480", "--cpu-images", "1", "--cpu-workers", "0", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -785,6 +785,42 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     env2 = dict(env, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     r = subprocess.run(cmd, capture_output=True, text=True, env=env2, cwd=ROOT, timeout=120)
     assert r.returncode != 0 and "WORLD_SIZE" in (r.stderr + r.stdout)
+
+
+def test_bench_plain_run_dumps_what_the_step_returned(tmp_path, ctx):
+    """`bench.py` without --full times the steps and prints the line, no other leg; --dump-outputs writes the last step's counts
+    and records, the same from run to run, and they are what the host entry point returns for the same images."""
+    import json
+    import sys
+    from hesaff_amd.synth import band_noise_batch_torch
+    lines, dumps = [], []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "3",
+               "--width", "640", "--height", "480", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+        dumps.append({q.name[:-4]: np.load(q) for q in sorted(d.iterdir())})
+    line = lines[0]
+    assert line["full"] is False and line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    for leg in ("host_path", "end_to_end", "end_to_end_budgeted", "text_export", "photo_density", "jpeg_path", "fast_modes", "hbm_probe"):
+        assert line[leg] is None, leg
+    assert "cpu_baseline" not in line
+    a, b = dumps
+    assert sorted(a) == sorted(b) == ["count_desc", "count_hessian", "keys_desc", "keys_frame", "keys_image", "keys_row", "keys_type"]
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64) and np.array_equal(a[name], b[name]), name
+    assert a["count_desc"].sum() * 2 == line["config"]["descriptors_timed_all_ranks"]
+    host = ctx.detect_batch(list(band_noise_batch_torch(3, 480, 640, seed=1234).cpu().numpy()))
+    assert a["count_hessian"].tolist() == [h[0] for h in host] and a["count_desc"].tolist() == [len(h[1]) for h in host]
+    keys = np.concatenate([h[1] for h in host])
+    assert a["keys_row"].tolist() == list(range(len(keys)))          # three VGA images: under the sample's cap, every record
+    assert a["keys_image"].tolist() == [i for i, h in enumerate(host) for _ in range(len(h[1]))]
+    for j, name in enumerate(["x", "y", "s", "a11", "a12", "a21", "a22", "response"]):
+        assert np.array_equal(a["keys_frame"][:, j].view(np.uint32), keys[name].view(np.uint32)), name
+    assert np.array_equal(a["keys_type"], keys["type"].astype(np.float32))
+    assert np.array_equal(a["keys_desc"], keys["desc"].astype(np.float32))
 
 
 def test_detect_batch_cb_streams_the_same_records(oracle):

@@ -96,3 +96,20 @@ def test_bench_refuses_a_world_size_other_than_gpus():
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8"], capture_output=True, text=True, env=env, timeout=120)
     assert r.returncode != 0 and "--gpus 8" in r.stderr
+
+
+def test_bench_dump_sample_stays_inside_the_records():
+    """bench.py --dump-outputs copies runs of device records: every run lies inside the records, the runs do not overlap,
+    the sample is capped (64 MB of .npy over all ranks) and the same record count selects the same rows."""
+    import bench
+    for world in (1, 2, 8):
+        cap = bench.DUMP_MAX_RECORDS // world
+        for total in (0, 1, 63, cap, cap + 1, 29_000_000, 2 ** 31 - 1):
+            starts, run = bench.dump_runs(total, world)
+            rows = (starts[:, None] + np.arange(run)).ravel()
+            assert rows.size == min(total, cap)
+            assert rows.size == 0 or (rows.min() >= 0 and rows.max() < total)
+            assert np.all(np.diff(rows) > 0)
+            s2, r2 = bench.dump_runs(total, world)
+            assert r2 == run and np.array_equal(s2, starts)
+    assert bench.DUMP_MAX_RECORDS * (8 + 1 + 128) * 4 + bench.DUMP_MAX_RECORDS * 2 * 8 < 64 << 20

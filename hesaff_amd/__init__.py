@@ -9,6 +9,8 @@ from ._binding import (  # noqa: F401
     HesaffContext,
     Params,
     KEYPOINT_DTYPE,
+    REGION_DTYPE,
+    Region,
     default_params,
     format_sift,
     format_sift_mt,

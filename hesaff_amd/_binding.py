@@ -51,11 +51,36 @@ KEYPOINT_DTYPE = np.dtype([
 ])
 assert KEYPOINT_DTYPE.itemsize == 164
 
+
+class Region(C.Structure):
+    """hesaff_region: one onHessianKeypointDetected call (pyramid.h:43-47) and what hesaff.cpp:66-105 made of it, 64 bytes."""
+    _fields_ = [
+        ("x", C.c_float), ("y", C.c_float), ("s", C.c_float), ("pixelDistance", C.c_float), ("response", C.c_float),
+        ("type", C.c_int32), ("octave", C.c_int32), ("level", C.c_int32),
+        ("a11", C.c_float), ("a12", C.c_float), ("a21", C.c_float), ("a22", C.c_float),
+        ("iters", C.c_int32), ("outcome", C.c_int32), ("key", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+# the same record as a numpy structured dtype (field offsets = Region's)
+REGION_DTYPE = np.dtype({
+    "names": [n for n, _ in Region._fields_],
+    "formats": ["<f4" if t is C.c_float else "<i4" for _, t in Region._fields_],
+    "offsets": [getattr(Region, n).offset for n, _ in Region._fields_],
+    "itemsize": C.sizeof(Region),
+})
+assert REGION_DTYPE.itemsize == 64
+REGION_NOT_CONVERGED, REGION_REJECTED, REGION_DESCRIBED = 0, 1, 2   # hesaff_region.outcome
+
+
+class _RegionResult(C.Structure):
+    _fields_ = [("count_hessian", C.c_int32), ("count_desc", C.c_int32), ("regions", C.c_void_p), ("keys", C.c_void_p)]
+
 _f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 _u8p = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
 
-ABI_VERSION = 7   # HESAFF_ABI_VERSION of the include/hesaff_amd.h these ctypes structs mirror
+ABI_VERSION = 8   # HESAFF_ABI_VERSION of the include/hesaff_amd.h these ctypes structs mirror
 
 
 class JpegLayout(C.Structure):
@@ -115,17 +140,24 @@ def load_library():
     L.hesaff_abi_version.argtypes = []
     L.hesaff_sizeof_params.argtypes = []; L.hesaff_sizeof_params.restype = C.c_size_t
     L.hesaff_sizeof_timings.argtypes = []; L.hesaff_sizeof_timings.restype = C.c_size_t
-    if (L.hesaff_abi_version() != ABI_VERSION or L.hesaff_sizeof_params() != C.sizeof(Params)
-            or L.hesaff_sizeof_timings() != C.sizeof(Timings)):
-        raise HesaffError(-2, "%s has ABI version %d (params %d bytes, timings %d bytes); this binding mirrors version %d (%d, %d)"
-                          % (p, L.hesaff_abi_version(), L.hesaff_sizeof_params(), L.hesaff_sizeof_timings(), ABI_VERSION,
-                             C.sizeof(Params), C.sizeof(Timings)))
+    abi = L.hesaff_abi_version()
+    sizeof_region = 0
+    if abi >= 8:   # (older libraries lack the symbol: the version check below reports them)
+        L.hesaff_sizeof_region.argtypes = []; L.hesaff_sizeof_region.restype = C.c_size_t
+        sizeof_region = L.hesaff_sizeof_region()
+    if (abi != ABI_VERSION or L.hesaff_sizeof_params() != C.sizeof(Params)
+            or L.hesaff_sizeof_timings() != C.sizeof(Timings) or sizeof_region != C.sizeof(Region)):
+        raise HesaffError(-2, "%s has ABI version %d (params %d bytes, timings %d bytes, region %d bytes); this binding mirrors version %d (%d, %d, %d)"
+                          % (p, abi, L.hesaff_sizeof_params(), L.hesaff_sizeof_timings(), sizeof_region, ABI_VERSION,
+                             C.sizeof(Params), C.sizeof(Timings), C.sizeof(Region)))
     L.hesaff_default_params.argtypes = [C.POINTER(Params)]
     L.hesaff_create.argtypes = [C.POINTER(vp), C.POINTER(Params), C.c_int]
     L.hesaff_destroy.argtypes = [vp]; L.hesaff_destroy.restype = None
     L.hesaff_last_error.argtypes = [vp]; L.hesaff_last_error.restype = C.c_char_p
     L.hesaff_detect_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                       C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_Result)]
+    L.hesaff_detect_regions.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_RegionResult)]
     L.hesaff_detect_batch_cb.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                          C.POINTER(C.c_int), C.POINTER(C.c_int), CHUNK_SINK, vp]
     L.hesaff_process_files.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(FileStatus)]
@@ -199,7 +231,7 @@ ABI_SYMBOLS = [
     "hesaff_write_sift_rows", "hesaff_write_bin_rows", "hesaff_stage_export", "hesaff_stage_fmt_g", "hesaff_set_resume",
     "hesaff_output_is_complete", "hesaff_read_jpeg_coefficients", "hesaff_read_jpeg_coefficients_alloc", "hesaff_stage_jpeg_pixels",
     "hesaff_read_pnm_alloc", "hesaff_read_image_alloc", "hesaff_set_pinned_read_budget", "hesaff_set_pool_priority",
-    "hesaff_stage_threads_for_pool", "hesaff_read_bmp", "hesaff_read_tiff",
+    "hesaff_stage_threads_for_pool", "hesaff_read_bmp", "hesaff_read_tiff", "hesaff_detect_regions", "hesaff_sizeof_region",
 ]
 
 
@@ -404,6 +436,33 @@ class HesaffContext:
             else:
                 keys = np.zeros(0, KEYPOINT_DTYPE)
             out.append((r.count_hessian, keys))
+        return out
+
+    def detect_regions(self, images):
+        """hesaff_detect_regions: images as for detect_batch.  -> list of (regions[REGION_DTYPE], keys[KEYPOINT_DTYPE]) per image:
+        one record per Hessian keypoint in the reference's callback order (pyramid.h:43-47, affine.h:48-58), and the same keys as
+        detect_batch.  regions[i]["key"] is the row of keys that keypoint became (-1 when it got no descriptor)."""
+        n = len(images)
+        imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+        ptrs = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
+        ws = (C.c_int * n)(*[im.shape[1] for im in imgs])
+        hs = (C.c_int * n)(*[im.shape[0] for im in imgs])
+        chs = (C.c_int * n)(*[1 if im.ndim == 2 else 3 for im in imgs])
+        st = (C.c_int * n)(*[im.shape[1] * (1 if im.ndim == 2 else 3) for im in imgs])
+        res = (_RegionResult * n)()
+        self._check(self.L.hesaff_detect_regions(self.h, n, ptrs, ws, hs, st, chs, res))
+        out = []
+        for r in res:
+            # copies out of the library-owned (pinned) result buffer, valid until the next call
+            if r.count_hessian > 0:
+                regions = np.frombuffer((C.c_char * (r.count_hessian * REGION_DTYPE.itemsize)).from_address(r.regions), dtype=REGION_DTYPE).copy()
+            else:
+                regions = np.zeros(0, REGION_DTYPE)
+            if r.count_desc > 0:
+                keys = np.frombuffer((C.c_char * (r.count_desc * KEYPOINT_DTYPE.itemsize)).from_address(r.keys), dtype=KEYPOINT_DTYPE).copy()
+            else:
+                keys = np.zeros(0, KEYPOINT_DTYPE)
+            out.append((regions, keys))
         return out
 
     def detect_batch_raw(self, images):

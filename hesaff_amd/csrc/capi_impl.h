@@ -53,6 +53,7 @@ const char *hesaff_version(void)
 int hesaff_abi_version(void) { return HESAFF_ABI_VERSION; }
 size_t hesaff_sizeof_params(void) { return sizeof(hesaff_params); }
 size_t hesaff_sizeof_timings(void) { return sizeof(hesaff_timings); }
+size_t hesaff_sizeof_region(void) { return sizeof(hesaff_region); }
 
 int hesaff_device_count(void)
 {
@@ -356,7 +357,9 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
       std::vector<size_t> off;
       std::vector<unsigned long long> toff;   // WANT_TEXT: byte offset of every image's rows
       size_t text_at = 0, bin_at = 0;         // where the text / sidecar rows start inside the result block
+      size_t regions_at = 0;                  // WANT_REGIONS: where the hesaff_region records start
       int total = 0, block = -1, no = 0, largest = 0;
+      bool copied = false;                    // a copy out was enqueued (ev_d2h of its slot is recorded)
    };
    const int wants = io.wants();
    c->ring.reset(ring);
@@ -426,7 +429,7 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
       return s;
    };
    auto deliver = [&](State &s) {
-      if (s.total > 0) hs_wait_event(c->ev_d2h[s.no & 1]);
+      if (s.copied) hs_wait_event(c->ev_d2h[s.no & 1]);
       if (s.total > 0 && c->profiling && (wants & (WANT_TEXT | WANT_BIN))) {
          float ms = 0.0f;   // length pass (with the host's short wait for the byte counts) + write pass
          float ms2 = 0.0f;
@@ -440,6 +443,7 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
       d.keys = (wants & WANT_KEYS) ? (const hesaff_keypoint *)blk : nullptr; d.block = s.block;
       if (wants & WANT_TEXT) { d.text = blk + s.text_at; d.text_off = s.toff.data(); }
       if (wants & WANT_BIN) d.bin = blk + s.bin_at;
+      if (wants & WANT_REGIONS) d.regions = (const hesaff_region *)(blk + s.regions_at);
       io.done(d);
    };
 
@@ -484,12 +488,13 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
             cur->nd[(size_t)b] = ds[b + 1] - ds[b];
             cur->off[(size_t)b] = (size_t)ds[b];
          }
-         // layout of the chunk's result block: [records][text rows][sidecar rows], what the consumer wants of them
-         const size_t n_rows = (size_t)cur->total;
+         // layout of the chunk's result block: [records][regions][text rows][sidecar rows], what the consumer wants of them
+         const size_t n_rows = (size_t)cur->total, n_hess = (size_t)hs[B];
          const KeyRec *d_keys = c->b_out.as<KeyRec>();
          size_t at = 0;
          auto place = [&at](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~(size_t)255; return o; };
          const size_t keys_at = (wants & WANT_KEYS) ? place(n_rows * sizeof(hesaff_keypoint)) : 0;
+         if (wants & WANT_REGIONS) cur->regions_at = place(n_hess * sizeof(hesaff_region));
          unsigned long long text_bytes = 0;
          const bool time_export = c->profiling && (wants & (WANT_TEXT | WANT_BIN)) && n_rows > 0;
          if (time_export) HIP_TRY(hipEventRecord(c->ev_exp[slot][0], c->stream));
@@ -533,11 +538,14 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
          } else {
             c->pin_out[(size_t)cur->block].ensure(std::max<size_t>(bytes, 16));
          }
-         if (cur->total > 0) {
+         cur->copied = cur->total > 0 || ((wants & WANT_REGIONS) && n_hess > 0);
+         if (cur->copied) {
             HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_d2h[slot], 0));      // D2H of chunk k-2 has left this staging slot
             if (bytes > c->b_outstage[slot].bytes) c->b_outstage[slot].ensure(bytes + bytes / 4);
             char *stg = (char *)c->b_outstage[slot].p;
-            if (wants & WANT_KEYS) HIP_TRY(hipMemcpyAsync(stg + keys_at, c->b_out.p, n_rows * sizeof(hesaff_keypoint), hipMemcpyDeviceToDevice, c->stream));
+            if ((wants & WANT_KEYS) && n_rows > 0)
+               HIP_TRY(hipMemcpyAsync(stg + keys_at, c->b_out.p, n_rows * sizeof(hesaff_keypoint), hipMemcpyDeviceToDevice, c->stream));
+            if (wants & WANT_REGIONS) pack_regions(c, (uint32_t)n_hess, B, (hesaff_region *)(stg + cur->regions_at));
             if (time_export) HIP_TRY(hipEventRecord(c->ev_exp[slot][2], c->stream));
             if (wants & WANT_TEXT) export_text_write(c, d_keys, (uint32_t)n_rows, stg + cur->text_at);
             if (wants & WANT_BIN) export_bin_rows(c, d_keys, (uint32_t)n_rows, stg + cur->bin_at);
@@ -605,6 +613,20 @@ int hesaff_detect_batch_cb(hesaff_ctx *c, int n, const uint8_t *const *images, c
    io.sink = sink; io.user = user;
    run_chunks(c, io, 3);
    if (io.sink_rc.load() != 0) throw HsError(HESAFF_ERR_IO, "the result sink reported an error");
+   HS_API_END(c)
+}
+
+// the chunks of hesaff_detect_batch, each with a block of hesaff_region records beside its keys (k_pack_regions, launched in run_chunks'
+// output step into the staging slot: the records leave on the chunk's one copy out)
+int hesaff_detect_regions(hesaff_ctx *c, int n, const uint8_t *const *images, const int *widths, const int *heights,
+                          const int *strides, const int *channels, hesaff_region_result *results)
+{
+   if (!c || n < 0 || (n > 0 && (!images || !widths || !heights || !results))) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   validate_image_list(n, images, widths, heights, strides, channels);
+   ArrayIO io(&c->ring, c->par.max_batch, n, images, widths, heights, strides, channels);
+   io.region_results = results;
+   run_chunks(c, io, 0);
    HS_API_END(c)
 }
 

@@ -79,7 +79,9 @@ inline bool same_jpeg_layout(const hesaff_jpeg_layout &a, const hesaff_jpeg_layo
 // what a consumer wants copied to the host for every chunk
 enum { WANT_KEYS = 1,    // the hesaff_keypoint records (hesaff.cpp:41-48)
        WANT_TEXT = 2,    // the rows of the .hesaff.sift files, formatted on the device (kernels_export.h; hesaff.cpp:124-128)
-       WANT_BIN = 4 };   // the 148-byte rows of the binary sidecar
+       WANT_BIN = 4,     // the 148-byte rows of the binary sidecar
+       WANT_REGIONS = 8  // a hesaff_region per Hessian keypoint (hesaff_detect_regions; pyramid.h:43-47, affine.h:48-58)
+};
 
 struct ChunkDone {
    const HostChunk *chunk;
@@ -90,6 +92,7 @@ struct ChunkDone {
    const char *text = nullptr;                     // WANT_TEXT: the rows of all images of the chunk back to back (no file headers)
    const unsigned long long *text_off = nullptr;   //            image b owns text[text_off[b] .. text_off[b + 1])
    const char *bin = nullptr;                      // WANT_BIN: image b's rows start at bin + key_off[b] * 148
+   const hesaff_region *regions = nullptr;         // WANT_REGIONS: image b's records start at its Hessian offset, the sum of count_hessian[0 .. b)
 };
 
 struct ChunkIO {
@@ -115,6 +118,7 @@ struct ArrayIO : ChunkIO {
    hesaff_result *results = nullptr;             // hesaff_detect_batch: filled in place
    hesaff_chunk_sink sink = nullptr;             // hesaff_detect_batch_cb
    void *user = nullptr;
+   hesaff_region_result *region_results = nullptr;   // hesaff_detect_regions: filled in place (instead of results)
    std::atomic<int> sink_rc{0};                 // written by done() on the caller's thread, read by next() on the staging thread
    ArrayIO(BlockRing *ring_, int max_batch, int n, const uint8_t *const *images, const int *widths, const int *heights, const int *strides,
            const int *channels)
@@ -171,9 +175,20 @@ struct ArrayIO : ChunkIO {
       for (size_t i = pos; i < chunks.size() && chunks[i].W == q.W && chunks[i].H == q.H && chunks[i].ch == q.ch; i++) m = std::max(m, chunks[i].data.size());
       return (int)m;
    }
+   int wants() const override { return region_results ? (WANT_KEYS | WANT_REGIONS) : WANT_KEYS; }
    void done(const ChunkDone &d) override
    {
       const size_t B = d.chunk->index.size();
+      if (region_results) {
+         size_t h_off = 0;
+         for (size_t b = 0; b < B; b++) {
+            hesaff_region_result &r = region_results[d.chunk->index[b]];
+            r.count_hessian = d.count_hessian[b]; r.count_desc = d.count_desc[b]; r.keys = d.keys + d.key_off[b];
+            r.regions = d.count_hessian[b] > 0 ? d.regions + h_off : nullptr;
+            h_off += (size_t)d.count_hessian[b];
+         }
+         return;
+      }
       if (results) {
          for (size_t b = 0; b < B; b++) {
             hesaff_result &r = results[d.chunk->index[b]];

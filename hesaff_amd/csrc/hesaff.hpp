@@ -2,9 +2,17 @@
 // describe path, implemented over the C ABI (include/hesaff_amd.h).  Names, argument
 // meaning and outputs follow hesaff.cpp:21-131: HessianAffineParams (defaults :28-35),
 // Keypoint (:41-48), AffineHessianDetector::{detectPyramidKeypoints, keys,
-// exportKeypoints}.  The reference's per-keypoint virtual callbacks (pyramid.h:43-47,
-// affine.h:48-58) do not exist here: the GPU runs the stages breadth-first and hands
-// back the same `keys` vector, in the same order.
+// exportKeypoints}, and the reference's two per-keypoint virtual callbacks
+// HessianKeypointCallback (pyramid.h:43-47) and AffineShapeCallback (affine.h:48-58) with
+// their setters.  The GPU runs the stages breadth-first and hands back the same `keys`
+// vector, in the same order.  With a callback set, detectPyramidKeypoints replays the
+// records of hesaff_detect_regions depth-first, in the reference's call order
+// (hesaff.cpp:66-105): onHessianKeypointDetected for every Hessian keypoint, followed at
+// once by onAffineShapeFound when findAffineShape converged.  The one difference: the
+// callbacks observe a chain that has already run - a callback cannot suppress or alter
+// the later stages, and `keys` is the same whatever the callbacks do.  The `blur` plane is
+// a light handle (BlurPlane) instead of the cv::Mat; its pixels are those of
+// hesaff_stage_pyramid's plane of that octave and level.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -35,6 +43,25 @@ struct HessianAffineParams {   // hesaff.cpp:21-36
 
 typedef hesaff_keypoint Keypoint;   // hesaff.cpp:41-48, identical layout
 
+// the `const cv::Mat &blur` argument of both callbacks: which plane of the scale space the keypoint was found / shaped on
+// (pixels: hesaff_stage_pyramid's blur plane `level` of octave `octave`), and that octave's pixelDistance (pyramid.cpp:288)
+struct BlurPlane {
+   int octave, level;
+   float pixelDistance;
+};
+
+class HessianKeypointCallback {   // pyramid.h:43-47
+ public:
+   virtual void onHessianKeypointDetected(const BlurPlane &blur, float x, float y, float s, float pixelDistance, int type, float response) = 0;
+   virtual ~HessianKeypointCallback() {}
+};
+
+struct AffineShapeCallback {   // affine.h:48-58; a11..a22 are U as found (not rectified), iters = l at affine.cpp:95
+   virtual void onAffineShapeFound(const BlurPlane &blur, float x, float y, float s, float pixelDistance, float a11, float a12, float a21,
+                                   float a22, int type, float response, int iters) = 0;
+   virtual ~AffineShapeCallback() {}
+};
+
 struct AffineHessianDetector {
    std::vector<Keypoint> keys;      // hesaff.cpp:54
    int g_numberOfPoints = 0;        // hesaff.cpp:38
@@ -44,7 +71,8 @@ struct AffineHessianDetector {
    {
       if (par.patch_size != 41) throw std::invalid_argument("patch_size is fixed at 41 in this build");
       // the structs carry no size field: refuse a library built from another header before passing one across
-      if (hesaff_abi_version() != HESAFF_ABI_VERSION || hesaff_sizeof_params() != sizeof(hesaff_params) || hesaff_sizeof_timings() != sizeof(hesaff_timings))
+      if (hesaff_abi_version() != HESAFF_ABI_VERSION || hesaff_sizeof_params() != sizeof(hesaff_params) || hesaff_sizeof_timings() != sizeof(hesaff_timings) ||
+          hesaff_sizeof_region() != sizeof(hesaff_region))
          throw std::runtime_error("libhesaff_amd.so was built from a different include/hesaff_amd.h (ABI version mismatch)");
       hesaff_default_params(&p_);
       p_.threshold = par.threshold;          // hesaff.cpp:155
@@ -57,17 +85,38 @@ struct AffineHessianDetector {
    AffineHessianDetector(const AffineHessianDetector &) = delete;
    AffineHessianDetector &operator=(const AffineHessianDetector &) = delete;
 
+   // pyramid.h:69, affine.h:87 (nullptr: none).  The callbacks are the caller's; they are called from detectPyramidKeypoints.
+   void setHessianKeypointCallback(HessianKeypointCallback *callback) { hessianKeypointCallback_ = callback; }
+   void setAffineShapeCallback(AffineShapeCallback *callback) { affineShapeCallback_ = callback; }
+
    // == grey conversion hesaff.cpp:138-148 + detectPyramidKeypoints hesaff.cpp:167 with the
    // whole callback chain; image is what cv::imread would deliver (8-bit, 1 or 3 channels).
    void detectPyramidKeypoints(const uint8_t *image, int width, int height, int channels)
    {
-      hesaff_result r;
       const int stride = width * channels;
-      if (hesaff_detect_batch(ctx_, 1, &image, &width, &height, &stride, &channels, &r) != HESAFF_OK)
+      if (!hessianKeypointCallback_ && !affineShapeCallback_) {
+         hesaff_result r;
+         if (hesaff_detect_batch(ctx_, 1, &image, &width, &height, &stride, &channels, &r) != HESAFF_OK)
+            throw std::runtime_error(hesaff_last_error(ctx_));
+         g_numberOfPoints = r.count_hessian;
+         g_numberOfAffinePoints += r.count_desc;   // the reference never resets this counter (hesaff.cpp:166)
+         keys.assign(r.keys, r.keys + r.count_desc);
+         return;
+      }
+      hesaff_region_result r;
+      if (hesaff_detect_regions(ctx_, 1, &image, &width, &height, &stride, &channels, &r) != HESAFF_OK)
          throw std::runtime_error(hesaff_last_error(ctx_));
       g_numberOfPoints = r.count_hessian;
-      g_numberOfAffinePoints += r.count_desc;   // the reference never resets this counter (hesaff.cpp:166)
+      g_numberOfAffinePoints += r.count_desc;
       keys.assign(r.keys, r.keys + r.count_desc);
+      // hesaff.cpp:66-105 depth-first: each Hessian keypoint, then its affine shape when findAffineShape converged
+      for (int i = 0; i < r.count_hessian; i++) {
+         const hesaff_region &g = r.regions[i];
+         const BlurPlane blur = {g.octave, g.level, g.pixelDistance};
+         if (hessianKeypointCallback_) hessianKeypointCallback_->onHessianKeypointDetected(blur, g.x, g.y, g.s, g.pixelDistance, g.type, g.response);
+         if (affineShapeCallback_ && g.outcome >= 1)
+            affineShapeCallback_->onAffineShapeFound(blur, g.x, g.y, g.s, g.pixelDistance, g.a11, g.a12, g.a21, g.a22, g.type, g.response, g.iters);
+      }
    }
 
    // hesaff.cpp:107-130
@@ -85,6 +134,8 @@ struct AffineHessianDetector {
  private:
    hesaff_params p_;
    hesaff_ctx *ctx_ = nullptr;
+   HessianKeypointCallback *hessianKeypointCallback_ = nullptr;
+   AffineShapeCallback *affineShapeCallback_ = nullptr;
 };
 
 } // namespace hesaff_amd

@@ -496,6 +496,41 @@ __global__ __launch_bounds__(256) void k_pack(HessList hl, const uint32_t *__res
    }
 }
 
+// ---------------------------------------------------------------------------------------
+// k_pack_regions: one hesaff_region record (include/hesaff_amd.h, 64 bytes) per Hessian keypoint of the batch, in list
+// order = the reference's onHessianKeypointDetected order (pyramid.h:43-47), with what hesaff.cpp:66-105 made of it:
+// findAffineShape's un-rectified U and iteration count (affine.h:48-58; zero when it did not converge, whatever the
+// affine stage left in those slots), normalizeAffine's verdict, and the row of its keys record (rank[h] from k_pack's scan
+// minus the image's first row).  Only hesaff_detect_regions launches it, straight into the chunk's staging slot.
+// A lane per record: the structure-of-arrays reads are coalesced runs, and the record leaves as four 16-byte stores, so
+// the four stores of a wavefront cover 4 KB back to back.
+// ---------------------------------------------------------------------------------------
+struct RegionTab { float pd[HS_MAX_OCTAVES]; };   // pixelDistance of every octave, the host's octave schedule (pyramid.cpp:264-288)
+#define HS_REGION_DW 16   // dwords per record
+__global__ __launch_bounds__(256) void k_pack_regions(HessList hl, uint32_t n, AffineOut aff, PatchWork pw, const uint32_t *__restrict__ rank,
+                                                      const int32_t *__restrict__ desc_starts, RegionTab tab, uint4 *__restrict__ out)
+{
+   for (uint32_t h = blockIdx.x * blockDim.x + threadIdx.x; h < n; h += gridDim.x * blockDim.x) {
+      const int meta = hl.meta[h];
+      const int b = meta >> 8, octave = (meta >> 4) & 15, level = (meta >> 2) & 3, type = meta & 3;
+      const bool converged = aff.converged[h] != 0;
+      const bool described = converged && pw.alive[h] != 0;
+      uint4 U = make_uint4(0u, 0u, 0u, 0u);
+      uint32_t iters = 0u;
+      if (converged) {
+         U = *reinterpret_cast<const uint4 *>(aff.U + 4 * (size_t)h);
+         iters = (uint32_t)aff.iters[h];
+      }
+      const uint32_t outcome = converged ? (described ? 2u : 1u) : 0u;
+      const uint32_t key = described ? rank[h] - (uint32_t)desc_starts[b] : 0xffffffffu;
+      uint4 *o = out + 4 * (size_t)h;
+      o[0] = make_uint4(__float_as_uint(hl.x[h]), __float_as_uint(hl.y[h]), __float_as_uint(hl.s[h]), __float_as_uint(tab.pd[octave]));
+      o[1] = make_uint4(__float_as_uint(hl.response[h]), (uint32_t)type, (uint32_t)octave, (uint32_t)level);
+      o[2] = U;
+      o[3] = make_uint4(iters, outcome, key, 0u);
+   }
+}
+
 // device check of hmath.h against the host (stage API)
 __global__ void k_math(int n, const float *__restrict__ a, const float *__restrict__ b, float *__restrict__ at, float *__restrict__ pw)
 {

@@ -1449,5 +1449,19 @@ void export_bin_rows(hesaff_ctx *c, const KeyRec *keys, uint32_t n, char *d_bin)
    hipLaunchKernelGGL(k_bin_rows, dim3(std::min<uint32_t>((n + 7) / 8, 4096u)), dim3(256), 0, c->stream, keys, n, c->par.mrSize, (uint32_t *)d_bin);
 }
 
+// hesaff_detect_regions: the n_hess hesaff_region records of the batch run_batch just finished into d_regions, on the main stream
+// (the Hessian list, the affine output, the alive flags, rank[] and the descriptor starts stay valid there until the next batch)
+void pack_regions(hesaff_ctx *c, uint32_t n_hess, int B, hesaff_region *d_regions)
+{
+   static_assert(sizeof(hesaff_region) == 4 * HS_REGION_DW, "hesaff_region layout");
+   if (n_hess == 0) return;
+   if (n_hess > c->cap) throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded; raise hesaff_params.max_kpts_per_mpx");
+   const Lists s = make_lists(c);
+   RegionTab tab;
+   for (int o = 0; o < HS_MAX_OCTAVES; o++) tab.pd[o] = c->consts.pd0 * (float)(1 << o);   // pyramid.cpp:288, as run_detection hands it on
+   hipLaunchKernelGGL(k_pack_regions, dim3(std::min<uint32_t>((n_hess + 255) / 256, 4096u)), dim3(256), 0, c->stream, s.hl, n_hess, s.ao, s.pw,
+                      (const uint32_t *)c->b_rank.p, (const int32_t *)c->b_starts.as<int32_t>() + (B + 1), tab, (uint4 *)d_regions);
+}
+
 } // namespace
 #include "capi_impl.h"

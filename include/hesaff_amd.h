@@ -26,22 +26,24 @@ extern "C" {
 #define HESAFF_ERR_IO (-4)        /* file I/O                                     */
 #define HESAFF_ERR_NOMEM (-5)
 
-/* Layout version of the structs below (hesaff_params, hesaff_timings, hesaff_result, hesaff_file_status).  Neither struct
+/* Layout version of the structs below (hesaff_params, hesaff_timings, hesaff_result, hesaff_file_status, hesaff_region).  Neither struct
  * carries a size field, so a caller built against another header would pass shifted fields without any error: callers
- * compare hesaff_abi_version() (and, if they wish, the two sizeof functions) with the header they were compiled against
+ * compare hesaff_abi_version() (and, if they wish, the sizeof functions) with the header they were compiled against
  * before the first hesaff_create - hesaff.hpp and the Python binding do.  New fields are appended at the END of a
  * struct and bump this number.   1: round 1;  2: + upscaleInputImage, fast, pack_ms (inserted mid-struct);  3: + extrema_*;
  * 4: hesaff_params.fast = 1 withdrawn, HESAFF_FILE_REJECTED, rows formatted on the device;
  * 5: + hesaff_jpeg_layout, hesaff_read_jpeg_coefficients, hesaff_stage_jpeg_pixels (JPEG pixels made on the device);
  * 6: + hesaff_host_plan_for, allocator-owned read buffers (hesaff_read_*_alloc);
- * 7: this header (+ hesaff_set_pinned_read_budget, hesaff_set_pool_priority, hesaff_stage_threads_for_pool, HESAFF_OUT_STRICT; hesaff_set_resume
- *    takes 0 / 1 / 2; no struct changed).
+ * 7: + hesaff_set_pinned_read_budget, hesaff_set_pool_priority, hesaff_stage_threads_for_pool, HESAFF_OUT_STRICT; hesaff_set_resume
+ *    takes 0 / 1 / 2; no struct changed;
+ * 8: this header (+ hesaff_region, hesaff_region_result, hesaff_detect_regions, hesaff_sizeof_region; no existing struct changed).
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
-#define HESAFF_ABI_VERSION 7
+#define HESAFF_ABI_VERSION 8
 int hesaff_abi_version(void);
 size_t hesaff_sizeof_params(void);
 size_t hesaff_sizeof_timings(void);
+size_t hesaff_sizeof_region(void);
 
 typedef struct hesaff_ctx hesaff_ctx;
 
@@ -189,6 +191,38 @@ int hesaff_set_output_format(hesaff_ctx *ctx, int format);
  * under the final name; a target that is not a regular file (/dev/stdout, a FIFO) or whose directory takes no new file is written in
  * place. */
 int hesaff_set_resume(hesaff_ctx *ctx, int on);
+
+/* replaces: the two virtual callbacks the reference chains its stages through - HessianKeypointCallback::onHessianKeypointDetected
+ * (pyramid.h:43-47, installed by setHessianKeypointCallback pyramid.h:69) and AffineShapeCallback::onAffineShapeFound (affine.h:48-58,
+ * installed by setAffineShapeCallback affine.h:87), chained by hesaff.cpp:66-105 - as one record per Hessian keypoint.  Records are
+ * in the reference's call order (the order of onHessianKeypointDetected, = hesaff_stage_hessian_keypoints' order); 64 bytes each. */
+typedef struct hesaff_region {
+   float x, y, s, pixelDistance, response;  /* pyramid.cpp:203, the arguments of onHessianKeypointDetected                         */
+   int32_t type;                            /* HESSIAN_DARK 0 / BRIGHT 1 / SADDLE 2, pyramid.h:51-55                               */
+   int32_t octave, level;                   /* the `blur` plane passed: same indices as hesaff_stage_hessian_keypoints / hesaff_stage_pyramid */
+   float a11, a12, a21, a22;                /* U as passed to onAffineShapeFound (affine.cpp:95), NOT rectified; 0 when not converged */
+   int32_t iters;                           /* `l` at affine.cpp:95; 0 when not converged                                          */
+   int32_t outcome;                         /* 0: findAffineShape returned false; 1: converged, normalizeAffine rejected (hesaff.cpp:82);
+                                               2: described (a row of keys)                                                          */
+   int32_t key;                             /* row of its record in this image's keys, -1 unless outcome == 2                      */
+   int32_t reserved;                        /* 0 */
+} hesaff_region;
+
+/* Per-image result of hesaff_detect_regions: regions[count_hessian] (NULL when count_hessian is 0) and keys[count_desc], the latter
+ * byte-identical to hesaff_detect_batch's keys for the same image.  Both are library-owned, valid until the next call on the context. */
+typedef struct hesaff_region_result {
+   int32_t count_hessian;      /* g_numberOfPoints,       hesaff.cpp:38,68  */
+   int32_t count_desc;         /* g_numberOfAffinePoints, hesaff.cpp:39,103 */
+   const hesaff_region *regions;
+   const hesaff_keypoint *keys;
+} hesaff_region_result;
+
+/* hesaff_detect_batch that also returns every Hessian keypoint with what followed it (hesaff_region): the keypoints that got no
+ * descriptor, the un-rectified U and iteration count of findAffineShape, and which row of keys each one became.  Same inputs, same
+ * chunking and the same lifetime contract as hesaff_detect_batch; the records leave the device with the keys of their chunk.
+ * The callbacks observe a chain that has already run: nothing a caller does with a record changes the later stages. */
+int hesaff_detect_regions(hesaff_ctx *ctx, int n, const uint8_t *const *images, const int *widths, const int *heights,
+                          const int *strides, const int *channels, hesaff_region_result *results);
 
 /* Same path with inputs already resident in device memory (bench / pipelines that decode
  * on the GPU): d_gray = n contiguous height x width 8-bit grey planes (device pointer).

@@ -114,7 +114,7 @@ _lib = None
 
 
 def lib_path():
-    # HESAFF_AMD_LIB: alternative build of the same library (kernel tuning A/B runs)
+    # HESAFF_AMD_LIB: another build of the same library (the tuning build, or another commit's for a comparison)
     return os.environ.get("HESAFF_AMD_LIB") or os.path.join(_HERE, "libhesaff_amd.so")
 
 

@@ -116,58 +116,30 @@ int hesaff_create(hesaff_ctx **out, const hesaff_params *p, int device)
       }
       {
          // The HIP runtime runs the streams of one priority on FOUR hardware queues, and kernels of streams that share a queue do not
-         // overlap.  Which of a context's eight logical streams (main, patch bins 0-3, descriptor, descriptor 2, affine) end up together
-         // moves the step by up to 8 %, and with eight HIP streams it depends on what else the process has created.  So the pairing is
-         // made explicit: four HIP streams, each serving the two logical streams that measured best together
-         // (profiles/r04_notes.md):   main + bin 3 | bin 0 + bin 1 | bin 2 + affine | descriptor + descriptor 2.
-         // Tuning build: HESAFF_MERGE=0 gives every logical stream a HIP stream of its own again, created in HESAFF_ORDER.
-         hipStream_t *slots[8] = {&c->stream, &c->side_streams[0], &c->side_streams[1], &c->side_streams[2], &c->side_streams[3], &c->sift_stream,
-                                  &c->sift_stream2, &c->aff_stream};
-         bool merge = true;
-         int order[8] = {0, 1, 2, 3, 4, 5, 6, 7};
-#ifdef HESAFF_TUNING
-         if (const char *mg = getenv("HESAFF_MERGE")) merge = atoi(mg) != 0;
-         if (const char *od = getenv("HESAFF_ORDER"))
-            if (strlen(od) == 8) for (int i = 0; i < 8; i++) order[i] = (od[i] - '0') & 7;
-#endif
-         if (merge) {
-            // logical stream -> group: 0 main, 1-4 patch bins 0-3, 5 descriptor, 6 descriptor 2, 7 affine
-            int group[8] = {0, 1, 1, 2, 0, 3, 3, 2};
-            bool custom_groups = false;
-#ifdef HESAFF_TUNING
-            if (const char *gr = getenv("HESAFF_GROUPS"))   // e.g. "01120332": eight digits, the group of each logical stream
-               if (strlen(gr) == 8) { for (int i = 0; i < 8; i++) group[i] = (gr[i] - '0') & 7; custom_groups = true; }
-#endif
-            int ctx_prio = 0;   // tuning build, HESAFF_CTX_PRIO: 1 = this context's streams at the high priority (queues apart from a normal context's)
-#ifdef HESAFF_TUNING
-            if (const char *cp = getenv("HESAFF_CTX_PRIO")) ctx_prio = atoi(cp);
-#endif
-            int p_least = 0, p_greatest = 0;
-            HIP_TRY(hipDeviceGetStreamPriorityRange(&p_least, &p_greatest));
-            hipStream_t made[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-            // The HIP streams of a context outlive it: the next context on this device takes the same ones (take_stream_set).  A stream
-            // created later lands on whichever hardware queue has the fewest users at that moment, so the second and third context of
-            // a process used to get another - often worse - sharing of queues than the first (the chunks of bench.py's file leg, third
-            // context of its process: 110-135 ms each against 107-110 in a process of their own).
-            c->pooled_streams = ctx_prio == 0 && !custom_groups;
-            if (c->pooled_streams && take_stream_set(device, c->sset))
-               for (int g = 0; g < 4; g++) made[g] = c->sset.comp[g];
-            for (int i = 0; i < 8; i++) {
-               if (!made[group[i]]) {
-                  if (ctx_prio == 0) HIP_TRY(hipStreamCreateWithFlags(&made[group[i]], hipStreamNonBlocking));
-                  else HIP_TRY(hipStreamCreateWithPriority(&made[group[i]], hipStreamNonBlocking, ctx_prio == 1 ? p_greatest : p_least));
-               }
-               *slots[i] = made[group[i]];
-            }
-            if (c->pooled_streams)
-               for (int g = 0; g < 4; g++) c->sset.comp[g] = made[g];
-         } else {
-            for (int i = 0; i < 8; i++) HIP_TRY(hipStreamCreateWithFlags(slots[order[i]], hipStreamNonBlocking));
+         // overlap.  Which of a context's seven logical streams (main, patch bins 0-3, descriptor, affine) end up together moves the step
+         // by up to 8 %, and with seven HIP streams it depends on what else the process has created.  So the pairing is made explicit:
+         // four HIP streams, each serving the logical streams that measured best together
+         // (profiles/r04_notes.md):   main + bin 3 | bin 0 + bin 1 | bin 2 + affine | descriptor.
+         hipStream_t *slots[7] = {&c->stream, &c->side_streams[0], &c->side_streams[1], &c->side_streams[2], &c->side_streams[3], &c->sift_stream,
+                                  &c->aff_stream};
+         const int group[7] = {0, 1, 1, 2, 0, 3, 2};   // logical stream -> HIP stream: 0 main, 1-4 patch bins 0-3, 5 descriptor, 6 affine
+         hipStream_t made[4] = {nullptr, nullptr, nullptr, nullptr};
+         // The HIP streams of a context outlive it: the next context on this device takes the same ones (take_stream_set).  A stream
+         // created later lands on whichever hardware queue has the fewest users at that moment, so the second and third context of
+         // a process used to get another - often worse - sharing of queues than the first (the chunks of bench.py's file leg, third
+         // context of its process: 110-135 ms each against 107-110 in a process of their own).  New streams are created in the order
+         // of their groups (0, 1, 2, 3).
+         if (take_stream_set(device, c->sset))
+            for (int g = 0; g < 4; g++) made[g] = c->sset.comp[g];
+         for (int i = 0; i < 7; i++) {
+            if (!made[group[i]]) HIP_TRY(hipStreamCreateWithFlags(&made[group[i]], hipStreamNonBlocking));
+            *slots[i] = made[group[i]];
          }
+         for (int g = 0; g < 4; g++) c->sset.comp[g] = made[g];
       }
       for (int i = 0; i < HS_NSIDE; i++) HIP_TRY(hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming));
       HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-      // (the eight compute streams stay on the default priority: every other assignment measured 1.5-6 % slower, profiles/r04_notes.md)
+      // (the four compute streams stay on the default priority: every other assignment measured 1.5-6 % slower, profiles/r04_notes.md)
       HIP_TRY(hipEventCreateWithFlags(&c->ev_detect_done, hipEventDisableTiming | hipEventBlockingSync));
       HIP_TRY(hipEventCreateWithFlags(&c->ev_batch_done, hipEventDisableTiming | hipEventBlockingSync));
       for (int i = 0; i < HS_NSLOT; i++) {
@@ -179,27 +151,9 @@ int hesaff_create(hesaff_ctx **out, const hesaff_params *p, int device)
       refresh_tables_struct(c);
       memset(&c->tm, 0, sizeof c->tm);
 #ifdef HESAFF_TUNING
-      // schedule knobs for A/B measurements (libhesaff_amd_tuning.so only); none of them changes a result
+      // what makes the schedule observable (libhesaff_amd_tuning.so only); neither changes a result
       if (const char *ov = getenv("HESAFF_OVERLAP")) c->no_overlap = atoi(ov) == 0;
-      if (const char *ab = getenv("HESAFF_AFF_BLOCKS")) c->aff_blocks_per_cu = std::max(1, atoi(ab));
-      if (const char *sd = getenv("HESAFF_SIDE")) c->side_mask = atoi(sd);
-      if (const char *gk = getenv("HESAFF_GROUP")) c->sift_group_kpts = (uint32_t)std::max(1000, atoi(gk));
-      if (const char *wv = getenv("HESAFF_BANDS")) c->force_bands = std::max(0, atoi(wv));
-      if (const char *eb = getenv("HESAFF_EXBAND")) c->force_exband = std::max(0, atoi(eb));
       c->debug = getenv("HESAFF_DEBUG") != nullptr;
-      if (const char *sg = getenv("HESAFF_SGRAD_GRID")) c->sgrad_grid = (uint32_t)std::max(0, atoi(sg));
-      if (const char *gm = getenv("HESAFF_GRID_MULT")) {   // the persistent grids of the LDS-window patch kernels and of k_sift_hist x this
-         const uint32_t m = (uint32_t)std::max(1, atoi(gm));
-         c->g_small0 *= m; c->g_small1 *= m; c->g_shist *= m;
-      }
-      if (const char *s2 = getenv("HESAFF_SIFT2")) c->sift2 = atoi(s2) != 0;
-      if (const char *tp = getenv("HESAFF_TAPER")) c->taper_groups = atoi(tp) != 0;
-      if (const char *lst = getenv("HESAFF_LARGE_STREAM")) c->large_stream = atoi(lst) == 1 ? 1 : 0;
-      if (const char *lw = getenv("HESAFF_LARGE_NW")) c->large_nw = std::max(0, std::min(4, atoi(lw)));
-      if (const char *ln = getenv("HESAFF_LARGE_NROW")) c->large_nrow = atoi(ln) == 3 ? 3 : 1;
-      if (const char *ls = getenv("HESAFF_LARGE_SPLIT")) c->large_split = std::max(0, atoi(ls));
-      if (const char *sl = getenv("HESAFF_SIFT_SLICE")) c->sift_slice = (uint32_t)std::max(0, atoi(sl));
-      if (const char *sr = getenv("HESAFF_SLICE_RING")) c->sift_slice_ring = atoi(sr) != 0;
 #endif
    } catch (const HsError &e) {
       hesaff_destroy(c);
@@ -226,12 +180,13 @@ void hesaff_destroy(hesaff_ctx *c)
    for (DevBuf *b : bufs) b->release();
    for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
    {
-      // logical streams may be aliases of one HIP stream (hesaff_create): every HIP stream is destroyed once; c->stream goes last, below
-      hipStream_t all[7] = {c->side_streams[0], c->side_streams[1], c->side_streams[2], c->side_streams[3], c->sift_stream, c->sift_stream2, c->aff_stream};
-      for (int i = 0; i < 7; i++) {
+      // the logical streams are aliases of the context's four HIP streams (hesaff_create), which go back to the device's idle sets
+      // below: each is left idle once; c->stream is synchronised above
+      hipStream_t all[6] = {c->side_streams[0], c->side_streams[1], c->side_streams[2], c->side_streams[3], c->sift_stream, c->aff_stream};
+      for (int i = 0; i < 6; i++) {
          bool seen = all[i] == nullptr || all[i] == c->stream;
          for (int j = 0; j < i; j++) seen = seen || all[j] == all[i];
-         if (!seen) { (void)hipStreamSynchronize(all[i]); if (!c->pooled_streams) (void)hipStreamDestroy(all[i]); }
+         if (!seen) (void)hipStreamSynchronize(all[i]);
       }
       for (int i = 0; i < HS_NSIDE; i++) if (c->ev_join[i]) (void)hipEventDestroy(c->ev_join[i]);
    }
@@ -242,8 +197,9 @@ void hesaff_destroy(hesaff_ctx *c)
    for (int i = 0; i < HS_NSLOT; i++) {
       if (c->ev_extract_done[i]) (void)hipEventDestroy(c->ev_extract_done[i]);
       if (c->ev_sift_done[i]) (void)hipEventDestroy(c->ev_sift_done[i]);
-      c->b_patches2[i].release(); c->b_siftvec2[i].release(); c->b_meanvar2[i].release(); c->b_siftvo2[i].release();
+      c->b_patches2[i].release();
    }
+   c->b_siftvec2.release(); c->b_meanvar2.release(); c->b_siftvo2.release();
    if (c->h2d_stream) (void)hipStreamSynchronize(c->h2d_stream);   // (pin_in is the copy-in stream's source)
    for (int i = 0; i < 2; i++) {
       c->b_in2[i].release(); c->b_outstage[i].release(); c->pin_in[i].release();
@@ -260,13 +216,9 @@ void hesaff_destroy(hesaff_ctx *c)
    for (auto &pb : c->pin_out) pb.release();
    c->pin_read.release();
    c->h_small_end.release(); c->h_small_mid.release(); c->h_small_exp.release();
-   if (c->pooled_streams) {
+   if (c->sset.comp[0]) {   // (a context whose creation failed before its streams were complete has no set)
       c->sset.h2d = c->h2d_stream; c->sset.d2h = c->d2h_stream;
       give_stream_set(c->device, c->sset);   // idle now; the next context of this device runs on them
-   } else {
-      if (c->h2d_stream) (void)hipStreamDestroy(c->h2d_stream);
-      if (c->d2h_stream) (void)hipStreamDestroy(c->d2h_stream);
-      if (c->stream) (void)hipStreamDestroy(c->stream);
    }
    delete c;
 }
@@ -326,12 +278,12 @@ void ensure_copy_streams(hesaff_ctx *c)
 {
    if (c->h2d_stream) return;
    // The copy streams get a priority of their own: the runtime multiplexes the streams of one priority onto a few hardware queues
-   // (four by default; this context has eight compute streams), and a copy command holds its queue until the copy engine is done -
+   // (four by default; this context has four compute streams), and a copy command holds its queue until the copy engine is done -
    // 23 ms for the 1.3 GB of text of a chunk, during which the patch kernels of whatever stream shared that queue did not start
    // (measured: +19 ms on the patch stage of every chunk, profiles/r04_notes.md).  Streams of another priority live on other queues.
    int prio_least = 0, prio_greatest = 0;
    HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-   if (c->pooled_streams && c->sset.h2d && c->sset.d2h) {   // the copy streams of the context that had this set before
+   if (c->sset.h2d && c->sset.d2h) {   // the copy streams of the context that had this set before
       c->h2d_stream = c->sset.h2d; c->d2h_stream = c->sset.d2h;
    } else {
       HIP_TRY(hipStreamCreateWithPriority(&c->h2d_stream, hipStreamNonBlocking, prio_greatest));
@@ -674,18 +626,12 @@ int hesaff_process_files(hesaff_ctx *c, int n, const char *const *paths, const c
    const int dt = std::max(1, std::min(decode_threads > 0 ? decode_threads : hp.decode_threads, 64));
    const int wt = std::max(1, std::min(write_threads > 0 ? write_threads : hp.write_threads, 256));
    // the rows are formatted on the device (kernels_export.h): the writer threads only write()
-   bool device_jpeg = true;
-#ifdef HESAFF_TUNING
-   if (const char *dj = getenv("HESAFF_DEVICE_JPEG")) device_jpeg = atoi(dj) != 0;   // A/B: 0 = whole JPEG decode on the host threads (hesaff_read_jpeg)
-#endif
+   const bool device_jpeg = true;   // JPEG files: entropy decoding on the pool's threads, the pixels made on the device
    PinHooks pin;   // the readers fill page-locked buffers of this context: no malloc'ed image, no staging copy
    c->pin_read.device = c->device;
    pin.alloc = [](size_t bytes, void *user) -> void * { return ((hesaff_ctx *)user)->pin_read.take(bytes); };
    pin.release = [](void *p, size_t bytes, void *user) { ((hesaff_ctx *)user)->pin_read.give(p, bytes); };
    pin.user = c;
-#ifdef HESAFF_TUNING
-   if (const char *pr = getenv("HESAFF_PIN_READ")) { if (atoi(pr) == 0) pin = PinHooks(); }   // A/B: 0 = malloc'ed images + staging copy
-#endif
    // the pool's threads step down (nice 10) only where they would otherwise crowd out the caller's thread: a CPU-starved plan
    const bool nice_pool = c->pool_priority == 1 || (c->pool_priority < 0 && hesaff_host_threads() <= dt + wt + 1);
    FileIO io(&c->ring, c->par.max_batch, c->par.mrSize, c->out_format, n, paths, out_paths, status, dt, wt, true, c->resume, device_jpeg, pin, nice_pool);

@@ -51,10 +51,15 @@ struct DConsts {
       __builtin_amdgcn_wave_barrier();                      \
    } while (0)
 
-// Streaming accesses: data written once and consumed by a later kernel (or read exactly once) is stored / loaded
-// non-temporally so that it does not displace what this kernel and its neighbours re-read from L2 / the memory-side cache
-// (measured: k_sift_grad 21.6 -> 19.9 ms from its 12.8 KB of gradient pairs per keypoint alone).  Each site has a switch
-// (HS_NT_*) for A/B runs of the tuning build.
+// Streaming stores: data written once and consumed by a later kernel is stored non-temporally so that it does not displace what
+// this kernel and its neighbours re-read from L2 / the memory-side cache (measured: k_sift_grad 21.6 -> 19.9 ms from its 12.8 KB of
+// gradient pairs per keypoint alone).  The sites and what each measured:
+//   * non-temporal stores: k_sift_grad's gradient pairs (21.3 -> 19.9 ms; k_sift_hist 14.1 -> 13.3), the patch kernels' 41 x 41 outputs
+//     (the kernels themselves unchanged, k_sift_grad 20.1 -> 18.7 ms), the pyramid planes and response planes (k_blur_hess_march<9 / 13 / 15>:
+//     -16 / -9 / -2 %), the float grey plane written by the initial blur (pyramid stage 18.4-19.6 -> 17.8-18.2 ms at B = 128);
+//   * loads stay plain: k_sift_hist's loads of the gradient pairs (non-temporal: 13.7 -> 17.1 ms), k_extrema_march's reads of the five response
+//     planes, k_sift_grad's reads of the patch (its last reader), k_sift_meanvar's patch reads (non-temporal in the second pass: no change;
+//     in both passes: 9.8 -> 11.8 ms).
 typedef float hs_nt2 __attribute__((ext_vector_type(2)));
 typedef float hs_nt4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void hs_store_nt(float *p, float v) { __builtin_nontemporal_store(v, p); }
@@ -64,39 +69,6 @@ __device__ __forceinline__ void hs_store_nt4(float *p, float a, float b, float c
    hs_nt4 v; v.x = a; v.y = b; v.z = c; v.w = d;
    __builtin_nontemporal_store(v, reinterpret_cast<hs_nt4 *>(p));
 }
-__device__ __forceinline__ float hs_load_nt(const float *p) { return __builtin_nontemporal_load(p); }
-__device__ __forceinline__ float4 hs_load_nt4(const float4 *p)
-{
-   const hs_nt4 v = __builtin_nontemporal_load(reinterpret_cast<const hs_nt4 *>(p));
-   return make_float4(v.x, v.y, v.z, v.w);
-}
-#ifndef HS_NT_VO
-#define HS_NT_VO 1        // k_sift_grad's gradient pairs: stores (21.3 -> 19.9 ms; k_sift_hist 14.1 -> 13.3)
-#endif
-#ifndef HS_NT_VO_LD
-#define HS_NT_VO_LD 0     // ... and k_sift_hist's loads of them (measured: 13.7 -> 17.1 ms, not used)
-#endif
-#ifndef HS_NT_PATCH
-#define HS_NT_PATCH 1     // patch kernels' 41 x 41 outputs (the kernels themselves unchanged, k_sift_grad 20.1 -> 18.7 ms)
-#endif
-#ifndef HS_NT_PYR
-#define HS_NT_PYR 1       // pyramid planes (k_blur_hess_march<9 / 13 / 15>: -16 / -9 / -2 %)
-#endif
-#ifndef HS_NT_PYR_R
-#define HS_NT_PYR_R HS_NT_PYR   // ... the response planes separately (read back by k_extrema_march right after the octave's blurs)
-#endif
-#ifndef HS_NT_GRAY
-#define HS_NT_GRAY 1      // the float grey plane written by the initial blur (pyramid stage 18.4-19.6 -> 17.8-18.2 ms at B = 128)
-#endif
-#ifndef HS_NT_EXT
-#define HS_NT_EXT 0       // k_extrema_march's reads of the five response planes
-#endif
-#ifndef HS_NT_SGRAD_LD
-#define HS_NT_SGRAD_LD 0  // k_sift_grad's reads of the patch (its last reader)
-#endif
-#ifndef HS_NT_MEANVAR
-#define HS_NT_MEANVAR 0   // k_sift_meanvar's patch reads (1: second pass: no change; 2: both passes: 9.8 -> 11.8 ms)
-#endif
 
 // ---- helpers.cpp:227-240 : one bilinear tap; `outside` is OR-ed like `ret` ----
 // (int)floor(w) of the reference is cvttss2si (INT_MIN on NaN/overflow -> "outside");
@@ -118,25 +90,15 @@ __device__ __forceinline__ float hs_bilinear(const float *__restrict__ im, int p
    return in ? v : 0.0f;
 }
 
-#ifndef HS_TAP_FRACT
-#define HS_TAP_FRACT 1
-#endif
 // The tap of a window that lies inside the plane (all four corners tested: hs_window_outside): no bounds test, no selects,
 // a 32-bit element offset.  Same arithmetic as the inside case of hs_bilinear.
 __device__ __forceinline__ float hs_tap_inside_ptr(const float *__restrict__ im, int pitch, float wx, float wy)
 {
-#if HS_TAP_FRACT
    // inside the plane w >= 0: (int)floorf(w) == (int)w (conversion truncates) and w - floorf(w) is v_fract_f32's exact value;
    // two instructions per axis instead of three (helpers.cpp:227-232)
    const uint32_t off = (uint32_t)(int)wy * (uint32_t)pitch + (uint32_t)(int)wx;
    wx = __builtin_amdgcn_fractf(wx);
    wy = __builtin_amdgcn_fractf(wy);
-#else
-   const float fx = floorf(wx), fy = floorf(wy);
-   wx -= fx;
-   wy -= fy;
-   const uint32_t off = (uint32_t)(int)fy * (uint32_t)pitch + (uint32_t)(int)fx;
-#endif
    const float *p = im + off;
    const float p00 = p[0], p01 = p[1], p10 = p[pitch], p11 = p[pitch + 1];
    return (1.0f - wy) * ((1.0f - wx) * p00 + wx * p01) + (wy) * ((1.0f - wx) * p10 + wx * p11);

@@ -26,7 +26,7 @@ struct KpTables {   // device tables built on the host once per context
    // patch, and {output slot r * 40 + c (or -1: row / column 40, no weight), mask value bits}
    const int4 *sgrad_nb;
    const int2 *sgrad_om;
-   // layout of a keypoint's gradient pairs in HBM (kernels_sift.h: HS_VO_COMPACT): per patch row r < 40 {first item of the row in the
+   // layout of a keypoint's gradient pairs in HBM (kernels_sift.h: HS_VO_ITEMS): per patch row r < 40 {first item of the row in the
    // keypoint's block minus f_lo, f_lo, f_hi, 0} in 16-byte items (an empty row: f_lo > f_hi), and per item of the block the item of
    // k_sift_grad's 40 x 20 LDS tile it is a copy of (padding items: tile item 0, which holds no masked pixel)
    const int4 *vo_rows;
@@ -86,20 +86,13 @@ __device__ inline bool hs_window_outside(int imRows, int imCols, float ofsx, flo
 }
 
 #define HS_AFF_NT 23    // ceil(361 / 16)
-// the parity kernel's own grouping (tuning: -DHS_AFFP_G=2 gives each keypoint 32 lanes: half the LDS per wavefront, twice the
-// wavefronts per CU, but the serial sums and the double-precision tail then serve two keypoints instead of four)
-#ifndef HS_AFFP_G
+// the parity kernel's own grouping: four keypoints per wavefront, 16 lanes each (two keypoints of 32 lanes would halve the LDS per
+// wavefront and double the wavefronts per CU, but the serial sums and the double-precision tail would then serve two keypoints instead of four)
 #define HS_AFFP_G 4
-#endif
 #define HS_AFFP_L (64 / HS_AFFP_G)
-#define HS_AFFP_SH (HS_AFFP_G == 4 ? 4 : (HS_AFFP_G == 2 ? 5 : 6))
+#define HS_AFFP_SH 4    // log2(HS_AFFP_L)
 #define HS_AFFP_NT ((HS_SMM_PIX + HS_AFFP_L - 1) / HS_AFFP_L)
-#ifndef HS_AFF_XCD
-#define HS_AFF_XCD 1
-#endif
-#ifndef HS_AFF_BATCHES
 #define HS_AFF_BATCHES 2
-#endif
 #define HS_AFF_ARR 364  // 361 rounded up to a multiple of 4 floats
 
 struct AffKp { const float *blur; int rows, cols, pitch; float x, y, s, pd; };
@@ -120,7 +113,7 @@ __device__ __forceinline__ void hs_affine_groups(uint32_t first, uint32_t n, con
    // are fetched into ONE private L2 instead of eight.  (Grids that are not a multiple of 8 blocks keep the plain stride.)
    uint32_t hstep = gridDim.x * HS_AFFP_G, h_end = n;
    uint32_t h = first + blockIdx.x * HS_AFFP_G + grp;
-   if (HS_AFF_XCD && (gridDim.x & 7u) == 0u && n > first) {
+   if ((gridDim.x & 7u) == 0u && n > first) {
       const uint32_t n_items = (n - first + HS_AFFP_G - 1) / HS_AFFP_G;   // groups of HS_AFFP_G keypoints
       const uint32_t xcd = blockIdx.x & 7u, rank = blockIdx.x >> 3, per_xcd = gridDim.x >> 3;
       const uint32_t it_lo = (uint32_t)(((unsigned long long)n_items * xcd) >> 3), it_hi = (uint32_t)(((unsigned long long)n_items * (xcd + 1)) >> 3);
@@ -288,10 +281,7 @@ __device__ __forceinline__ void hs_affine_groups(uint32_t first, uint32_t n, con
 }
 
 
-#ifndef HS_AFF_WAVES
-#define HS_AFF_WAVES 0   // tuning: wavefronts per SIMD to hold the register allocation to (0: the compiler's choice)
-#endif
-__global__ __launch_bounds__(64, HS_AFF_WAVES) void k_affine(PlaneTab pt, HessList hl, uint32_t h_lo, uint32_t h_hi, const uint32_t *__restrict__ n_ptr,
+__global__ __launch_bounds__(64) void k_affine(PlaneTab pt, HessList hl, uint32_t h_lo, uint32_t h_hi, const uint32_t *__restrict__ n_ptr,
                                                KpTables tb, DConsts k, AffineOut out)
 {
    const uint32_t n = min(min(*n_ptr, hl.cap), h_hi);   // keypoints [h_lo, h_hi) of the list

@@ -51,16 +51,9 @@ struct PatchIO {
 // resource still bounds every load to the plane.)
 __device__ __forceinline__ float hs_tap_inside(const HsPlaneBuf &im, float wx, float wy)
 {
-#if HS_TAP_FRACT
    const uint32_t off = ((uint32_t)(int)wy * im.pitch + (uint32_t)(int)wx) * 4u;   // w >= 0: truncation is floor (see hs_tap_inside_ptr)
    wx = __builtin_amdgcn_fractf(wx);
    wy = __builtin_amdgcn_fractf(wy);
-#else
-   const float fx = floorf(wx), fy = floorf(wy);
-   wx -= fx;
-   wy -= fy;
-   const uint32_t off = ((uint32_t)(int)fy * im.pitch + (uint32_t)(int)fx) * 4u;
-#endif
    const hs_v2u r0 = __builtin_amdgcn_raw_buffer_load_b64(im.rsrc, (int)off, 0, 0);
    const hs_v2u r1 = __builtin_amdgcn_raw_buffer_load_b64(im.rsrc, (int)off, (int)im.pitch_bytes, 0);
    const float p00 = __uint_as_float(r0.x), p01 = __uint_as_float(r0.y), p10 = __uint_as_float(r1.x), p11 = __uint_as_float(r1.y);
@@ -109,16 +102,12 @@ __device__ __forceinline__ int hs_div_small(int idx, float inv)   // floor(idx /
 }
 
 // S: blurred window with row pitch `pitch`
-#ifndef HS_RESAMPLE_COLS
-#define HS_RESAMPLE_COLS 1
-#endif
 template <int PITCH>
 __device__ __forceinline__ void hs_resample_full_tab(const float *S, const int *tab_i, const float *tab_f, float *out)
 {
-#if HS_RESAMPLE_COLS
    // Thread t < 246 owns column ii = t % 41 of the rows jr, jr + 6, ... (jr = t / 41): the column's table entries and
    // 1 - wx are registers, a row's entries are one broadcast read, and output index jj * 41 + ii = t + 246 k needs no
-   // division (the flat form below spends a third of its instructions on idx -> (jj, ii) and the four table reads).
+   // division (a flat loop over idx spends a third of its instructions on idx -> (jj, ii) and the four table reads).
    constexpr int RPP = 256 / HS_PATCH;   // 6 rows per pass
    const int t = threadIdx.x;
    const int jr = hs_div_small(t, 1.0f / (float)HS_PATCH), ii = t - jr * HS_PATCH;
@@ -136,23 +125,10 @@ __device__ __forceinline__ void hs_resample_full_tab(const float *S, const int *
             const float p00 = p[0], p01 = p[1], p10 = p[PITCH], p11 = p[PITCH + 1];
             const float v = (1.0f - wy) * (wx1 * p00 + wx * p01) + (wy) * (wx1 * p10 + wx * p11);
             float *o = out + t + RPP * HS_PATCH * k;
-            if (HS_NT_PATCH) hs_store_nt(o, in ? v : 0.0f); else *o = in ? v : 0.0f;
+            hs_store_nt(o, in ? v : 0.0f);
          }
       }
    }
-#else
-   constexpr int pitch = PITCH;
-   for (int idx = threadIdx.x; idx < HS_PATCH_PIX; idx += 256) {
-      const int jj = hs_div_small(idx, 1.0f / (float)HS_PATCH), ii = idx - jj * HS_PATCH;
-      const int xi = tab_i[ii], yi = tab_i[jj];
-      const float wx = tab_f[ii], wy = tab_f[jj];
-      const bool in = (xi | yi) >= 0;
-      const float *p = S + (in ? yi * pitch + xi : 0);
-      const float p00 = p[0], p01 = p[1], p10 = p[pitch], p11 = p[pitch + 1];
-      const float v = (1.0f - wy) * ((1.0f - wx) * p00 + wx * p01) + (wy) * ((1.0f - wx) * p10 + wx * p11);
-      if (HS_NT_PATCH) hs_store_nt(out + idx, in ? v : 0.0f); else out[idx] = in ? v : 0.0f;
-   }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------
@@ -172,49 +148,19 @@ __device__ __forceinline__ void hs_resample_full_tab(const float *S, const int *
 #define HS_SMALL_RMAX 7
 #define HS_WNIT0 4
 #define HS_WNIT1 6
-#ifndef HS_SMALL_WAVES
 #define HS_SMALL_WAVES 6   // wavefronts per SIMD the register allocation of bin 0 is held to (0: the compiler's choice, 4);
-#endif                     // measured: 17.0 / 15.7 / 14.3 ms per 32 UHD images at 4 / 5 / 6; bin 1 spills at 6 and stays at the compiler's choice
-#ifndef HS_SMALL_BLK_BIN
+                           // measured: 17.0 / 15.7 / 14.3 ms per 32 UHD images at 4 / 5 / 6; bin 1 spills at 6 and stays at the compiler's choice
 #define HS_SMALL_BLK_BIN 1   // first bin whose blur runs register-blocked (measured: bin 1 -7 %, bin 0 +3 %: its windows waste more of a quad)
-#endif
-#ifndef HS_MID_WAVES
-#define HS_MID_WAVES 0
-#endif
-// HS_TAPS_SCALAR: the row pass of the row-streamed windows takes its taps as SCALAR operands.  Everything that selects a window is the same
+// The row pass of the row-streamed windows takes its taps as SCALAR operands (hs_row_taps).  Everything that selects a window is the same
 // for all lanes of a wavefront (the wavefront's task, its keypoint, P, K, the tap table's offset), but the compiler cannot know that of a value
 // derived from threadIdx.x or read from LDS; with the wave index / the claimed item passed through v_readfirstlane the whole chain of per-item
 // parameters lives in scalar registers, and taps[jt] is an s_load from the tap table in global memory (2.4 KB at most, scalar-cache resident)
 // instead of a broadcast ds_read from a staged copy: a third of the row pass's LDS instructions gone, on kernels whose LDS pipe is 45-60 % busy.
 // (The table is read through a pointer to the constant address space: what tells the compiler that the memory does not change during the
 // kernel, without which a uniform load still goes through the vector memory path.)
-#ifndef HS_TAPS_SCALAR
-#define HS_TAPS_SCALAR 1
-#endif
 typedef __attribute__((address_space(4))) const float hs_cfloat;
-#if HS_TAPS_SCALAR
 typedef hs_cfloat *hs_row_taps;
-#define HS_ROW_TAPS(global_table, lds_copy) (reinterpret_cast<hs_cfloat *>(reinterpret_cast<uintptr_t>(global_table)))
-#else
-typedef const float *hs_row_taps;
-#define HS_ROW_TAPS(global_table, lds_copy) (lds_copy)
-#endif
-#ifndef HS_MID_SCALAR
-#define HS_MID_SCALAR 1     // the row pass of the row-streamed windows as scalar sliding-window chains: every sample is read from LDS once (the pair form reads
-                            // it twice) and no register pairs are assembled; k_patch_mid<512> 195.5 -> 178.1, <128> 149.5 -> 144.0 ms per 256 images
-#endif
-#ifndef HS_ABL_MIDCONF
-#define HS_ABL_MIDCONF 0
-#endif
-#ifndef HS_MID_SCALAR_TAIL
-#define HS_MID_SCALAR_TAIL 0   // the same form in the one- and two-row variants (tail rows of a window, k_patch_large_rows): measured slower (182.8 vs 179.4, 33.9 vs 32.2 ms)
-#endif
-#ifndef HS_SMALL_WCOLS
-#define HS_SMALL_WCOLS 0   // tuning: the warp of the LDS-window bins with a fixed window column per thread (below); measured slower (profiles/r05_notes.md)
-#endif
-#ifndef HS_SMALL_SCALAR
-#define HS_SMALL_SCALAR 1   // the plain (pair) form of the LDS-window blur with scalar instead of packed operations: -186 register moves, no scratch; bin 0 156.6 -> 153.7 ms per 256 images
-#endif
+#define HS_ROW_TAPS(global_table) (reinterpret_cast<hs_cfloat *>(reinterpret_cast<uintptr_t>(global_table)))
 
 template <int BIN> struct SmallGeom {
    static constexpr int PMAX = BIN == 0 ? 41 : 63;   // largest window of the bin: the bins are cut on P = P0 + 2 <= 41 | 64, P is odd
@@ -333,17 +279,14 @@ __device__ __forceinline__ void hs_small_blur(float *S, float *T, int P, const f
       else if (K <= 5) {
          t = G(r) * kk[r] + (G(r - 1) + G(r + 1)) * kk[r + 1];
          if (K == 5) t = t + (G(r - 2) + G(r + 2)) * kk[r + 2];
-      } else if (HS_SMALL_SCALAR) {
+      } else {
          // the two chains as scalar operations: the window values are read once each (sp[j + 1] of tap j is sp[j] of tap j + 1),
          // no register pairs have to be assembled for packed operations that issue no faster than two scalar ones
+         // (measured against the packed form: -186 register moves, no scratch; bin 0 156.6 -> 153.7 ms per 256 images)
          float t0 = kk[0] * sp[0], t1 = kk[0] * sp[1];
 #pragma unroll
          for (int j = 1; j < K; j++) { t0 += kk[j] * sp[j]; t1 += kk[j] * sp[j + 1]; }
          t.x = t0; t.y = t1;
-      } else {
-         t = kk[0] * G(0);
-#pragma unroll
-         for (int j = 1; j < K; j++) t += kk[j] * G(j);
       }
       *reinterpret_cast<v2f *>(T + (r + yy) * TPITCH + xx) = t;
       if (yy == 0)
@@ -358,21 +301,15 @@ __device__ __forceinline__ void hs_small_blur(float *S, float *T, int P, const f
       const float *tp = T + (r + yy) * TPITCH + xx;
       auto TT = [&](int j) { return *reinterpret_cast<const v2f *>(tp + j * TPITCH); };
       v2f d;
-      if (HS_SMALL_SCALAR) {
-         const v2f c = TT(0);
-         float d0 = kk[r] * c.x, d1 = kk[r] * c.y;
+      const v2f c = TT(0);
+      float d0 = kk[r] * c.x, d1 = kk[r] * c.y;
 #pragma unroll
-         for (int j = 1; j <= r; j++) {
-            const v2f a = TT(j), b = TT(-j);
-            d0 += kk[r + j] * (a.x + b.x);
-            d1 += kk[r + j] * (a.y + b.y);
-         }
-         d.x = d0; d.y = d1;
-      } else {
-         d = kk[r] * TT(0);
-#pragma unroll
-         for (int j = 1; j <= r; j++) d += kk[r + j] * (TT(j) + TT(-j));
+      for (int j = 1; j <= r; j++) {
+         const v2f a = TT(j), b = TT(-j);
+         d0 += kk[r + j] * (a.x + b.x);
+         d1 += kk[r + j] * (a.y + b.y);
       }
+      d.x = d0; d.y = d1;
       *reinterpret_cast<v2f *>(S + yy * SPITCH + xx) = d;
    }
    __syncthreads();
@@ -454,48 +391,8 @@ __global__ __launch_bounds__(256, (BIN == 0 ? HS_SMALL_WAVES : 0)) void k_patch_
       // The P x P taps are taken in slots of 256 (one per thread), up to WNIT slots per batch with all gathers of a
       // batch issued before the first use.  The batch size is a compile-time constant picked per window (a switch on a
       // block-uniform value): a fixed WNIT would evaluate 1024 taps for a window of 23 x 23 = 529, and a test per slot
-      // inside the batch would serialise the gathers (measured: slower than the waste).
-#if HS_SMALL_WCOLS
-      // Thread t owns window column ii = t % P of the rows jr, jr + rpp, ... (jr = t / P, rpp = 256 / P rows per pass; threads
-      // past rpp * P sample the last row again and store nothing): C[ii] and the LDS store address are per-thread constants, R[jj]
-      // is a broadcast read, and no tap needs idx -> (jj, ii) (twice per tap in the flat form: before the gather and at the store).
-      const int rpp = hs_div_small(256, invP);
-      const int jr = hs_div_small(tid, invP), ii0 = tid - jr * P;
-      const v2f cC = s_C[ii0];
-      float *sdst = S + jr * SPITCH + r + ii0;
-      const bool wact = jr < rpp;
-      auto warp_batch = [&](auto nbc, int kb) {
-         constexpr int NB = decltype(nbc)::value;
-         float wv[NB];
-#pragma unroll
-         for (int it = 0; it < NB; it++) {
-            const v2f w = s_R[min(jr + rpp * (kb + it), P - 1)] + cC;
-            wv[it] = hs_tap_inside(pbuf, w.x, w.y);
-         }
-#pragma unroll
-         for (int it = 0; it < NB; it++) HS_KEEP(wv[it]);
-#pragma unroll
-         for (int it = 0; it < NB; it++)
-            if (wact && jr + rpp * (kb + it) < P) sdst[rpp * (kb + it) * SPITCH] = wv[it];
-      };
-      {
-         int kb = 0;
-         for (int rem = hs_div_small(P + rpp - 1, 1.0f / (float)rpp); rem > 0;) {
-            const int nbatch = (rem + WNIT - 1) / WNIT;   // batches left; this one takes an even share of the passes
-            const int nb = (rem + nbatch - 1) / nbatch;
-            switch (nb) {
-               case 1: warp_batch(std::integral_constant<int, 1>{}, kb); break;
-               case 2: warp_batch(std::integral_constant<int, 2>{}, kb); break;
-               case 3: warp_batch(std::integral_constant<int, 3>{}, kb); break;
-               case 4: warp_batch(std::integral_constant<int, 4>{}, kb); break;
-               case 5: if (WNIT >= 5) warp_batch(std::integral_constant<int, (WNIT >= 5 ? 5 : 1)>{}, kb); break;
-               default: if (WNIT >= 6) warp_batch(std::integral_constant<int, (WNIT >= 6 ? 6 : 1)>{}, kb); break;
-            }
-            kb += nb;
-            rem -= nb;
-         }
-      }
-#else
+      // inside the batch would serialise the gathers (measured: slower than the waste).  A warp with a fixed window column per
+      // thread (no idx -> (jj, ii) per tap) measured slower as well (profiles/r05_notes.md).
       auto warp_batch = [&](auto nbc, int ib) {
          constexpr int NB = decltype(nbc)::value;
          float wv[NB];
@@ -534,7 +431,6 @@ __global__ __launch_bounds__(256, (BIN == 0 ? HS_SMALL_WAVES : 0)) void k_patch_
             rem -= nb;
          }
       }
-#endif
       __syncthreads();
       // 2. blur, affine.cpp:129 (pinned cv::GaussianBlur order, see the file header)
       switch (K) {
@@ -560,8 +456,8 @@ __global__ __launch_bounds__(256, (BIN == 0 ? HS_SMALL_WAVES : 0)) void k_patch_
 // the plane is read through L2 / HBM, where a load per tap step followed by its use is a full round trip per step -
 // and the two columns of a row ride in one packed operation.  CLAMP = false: T points at window row 0 of a plane
 // stored with r replicated rows above and below (k_patch_mid's HBM slot), no index clamps.
-template <int JC, bool CLAMP, class TAPS = const float *>
-__device__ __forceinline__ void hs_colpass4_rows(const float *__restrict__ T, int y0, int q, int pm, TAPS taps, int r,
+template <int JC, bool CLAMP>
+__device__ __forceinline__ void hs_colpass4_rows(const float *__restrict__ T, int y0, int q, int pm, hs_row_taps taps, int r,
                                                  v2f &pa, v2f &pb)
 {
    // row y of the window -> pair at T[row][q]; CLAMP: BORDER_REPLICATE by index clamp (unpadded plane)
@@ -601,8 +497,8 @@ __device__ __forceinline__ void hs_colpass4_rows(const float *__restrict__ T, in
 
 // resample of affine.cpp:131 from the row-pass plane at the 82 needed columns (PADDED: T points at
 // window row 0 of a plane with r replicated rows above and below; otherwise rows are clamped)
-template <bool PADDED, class TAPS = const float *>
-__device__ __forceinline__ void hs_resample_reduced_batched(const float *__restrict__ T, int P, float scale, TAPS taps, int r,
+template <bool PADDED>
+__device__ __forceinline__ void hs_resample_reduced_batched(const float *__restrict__ T, int P, float scale, hs_row_taps taps, int r,
                                                             float *s_patch)
 {
    const float c0 = (float)(P >> 1);
@@ -615,7 +511,7 @@ __device__ __forceinline__ void hs_resample_reduced_batched(const float *__restr
       wx -= fx; wy -= fy;
       const int y0 = min(max((int)fy, 0), P - 2);   // always inside: |j * scale| < P0 / 2
       v2f pa, pb;   // (p00, p01), (p10, p11)
-      hs_colpass4_rows<8, !PADDED, TAPS>(T, y0, 2 * ii, P - 1, taps, r, pa, pb);
+      hs_colpass4_rows<8, !PADDED>(T, y0, 2 * ii, P - 1, taps, r, pa, pb);
       s_patch[idx] = (1.0f - wy) * ((1.0f - wx) * pa.x + wx * pa.y) + (wy) * ((1.0f - wx) * pb.x + wx * pb.y);
    }
 }
@@ -626,8 +522,7 @@ __device__ __forceinline__ void hs_resample_reduced_batched(const float *__restr
 // output, 21 round trips per wavefront and keypoint - 46 % of k_patch_mid<128>, 29 % of <512> in the ablation.  Here as
 // many consecutive output rows as fit are taken per round: their rows of T' come in with one coalesced sweep, and the
 // column pass reads LDS.  Same sums, same order.  T: window row 0 of the padded plane; chunk_rows >= K + 2.
-template <class TAPS = const float *>
-__device__ __forceinline__ void hs_resample_chunked(const float *__restrict__ T, int P, float scale, TAPS taps, int r,
+__device__ __forceinline__ void hs_resample_chunked(const float *__restrict__ T, int P, float scale, hs_row_taps taps, int r,
                                                     float *__restrict__ s_chunk, int chunk_rows, float *s_patch)
 {
    const int tid = threadIdx.x;
@@ -734,13 +629,13 @@ __device__ __forceinline__ void hs_gather_rows(const HsPlaneBuf &img, const v2f 
 // needed columns.  Called by all 64 lanes of a wave.  The LDS row is stored with r replicated
 // border samples on either side (BORDER_REPLICATE), so the tap loop has no index clamps:
 //   srow[r + x] = S[x],  srow[0..r) = S[0],  srow[r+P .. r+P+r) = S[P-1]     (needs P + 2r floats)
-// The image gathers of NIT x 64 window pixels are issued together before any of them is used; taps are read from
-// LDS (`taps`, broadcast reads).  ctab: the window's column table C[ii] = (i*a11, i*a21) in LDS, or nullptr
+// The image gathers of NIT x 64 window pixels are issued together before any of them is used; taps are scalar
+// loads from the tap table (hs_row_taps).  ctab: the window's column table C[ii] = (i*a11, i*a21) in LDS, or nullptr
 // (huge windows: computed per tap).
 // Lane i < 41 owns the output pair (2i, 2i + 1); the two accumulation chains run as one packed chain.
-template <int NIT, class TAPS = const float *>
+template <int NIT>
 __device__ __forceinline__ void hs_row_stream(const HsPlaneBuf &img, float x, float y, float a11, float a12, float a21, float a22, int P, int yy,
-                                              float scale, const v2f *__restrict__ ctab, TAPS taps, int K,
+                                              float scale, const v2f *__restrict__ ctab, hs_row_taps taps, int K,
                                               float *__restrict__ srow, float *__restrict__ out82, int pad_r = 0)
 {
    const int lane = threadIdx.x & 63, half = P >> 1, pm = P - 1, r = K >> 1;
@@ -760,25 +655,11 @@ __device__ __forceinline__ void hs_row_stream(const HsPlaneBuf &img, float x, fl
       const int x0 = min(max((int)floorf(w), 0), pm - 1);
       const float *s = srow + x0;   // s[jt] = S[clamp(x0 - r + jt)],  s[jt + 1] = S[clamp(x0 + 1 - r + jt)]
       auto G = [&](int jt) { v2f g; g.x = s[jt]; g.y = s[jt + 1]; return g; };
-      // RowFilter order; a window of this path has P0 >= 63, i.e. K = odd(int(9 * P0 / 41 + 1)) >= 15 (never the K <= 5 form)
-      v2f t;
-      if (HS_MID_SCALAR_TAIL) {   // scalar sliding-window chains (see hs_row_stream3)
-         float a0 = s[0], a1 = s[1];
-         const float k0 = taps[0];
-         float t0 = k0 * a0, t1 = k0 * a1;
+      // RowFilter order; a window of this path has P0 >= 63, i.e. K = odd(int(9 * P0 / 41 + 1)) >= 15 (never the K <= 5 form).
+      // (The scalar sliding-window chains of hs_row_stream3 measured slower here and in hs_row_stream2: 182.8 vs 179.4, 33.9 vs 32.2 ms.)
+      v2f t = taps[0] * G(0);
 #pragma unroll 8
-         for (int jt = 1; jt < K; jt++) {
-            const float k = taps[jt];
-            a0 = a1;
-            a1 = s[jt + 1];
-            t0 += k * a0; t1 += k * a1;
-         }
-         t.x = t0; t.y = t1;
-      } else {
-         t = taps[0] * G(0);
-#pragma unroll 8
-         for (int jt = 1; jt < K; jt++) t += taps[jt] * G(jt);
-      }
+      for (int jt = 1; jt < K; jt++) t += taps[jt] * G(jt);
       v2f *o = reinterpret_cast<v2f *>(out82) + lane;
       *o = t;
       // padded T' plane: the first / last window row is replicated pad_r times above / below (wave-uniform)
@@ -793,9 +674,9 @@ __device__ __forceinline__ void hs_row_stream(const HsPlaneBuf &img, float x, fl
 // Two window rows at once (rows yyA and yyB of the same window, one LDS row each): the gathers of both rows are in
 // flight together and the two row-pass chains interleave, so that neither the memory round trip nor the dependent
 // accumulation of one row leaves the wavefront without work.  Same operations per row as hs_row_stream.
-template <int NIT, class TAPS = const float *>
+template <int NIT>
 __device__ __forceinline__ void hs_row_stream2(const HsPlaneBuf &img, float x, float y, float a12, float a22, int P, int yyA, int yyB,
-                                               float scale, const v2f *__restrict__ ctab, TAPS taps, int K,
+                                               float scale, const v2f *__restrict__ ctab, hs_row_taps taps, int K,
                                                float *__restrict__ srowA, float *__restrict__ srowB, float *__restrict__ outA, float *__restrict__ outB, int pad_r,
                                                float a11 = 0.0f, float a21 = 0.0f)   // a11, a21: only read when ctab == nullptr
 {
@@ -815,28 +696,12 @@ __device__ __forceinline__ void hs_row_stream2(const HsPlaneBuf &img, float x, f
       const float *sA = srowA + x0, *sB = srowB + x0;
       auto GA = [&](int jt) { v2f g; g.x = sA[jt]; g.y = sA[jt + 1]; return g; };
       auto GB = [&](int jt) { v2f g; g.x = sB[jt]; g.y = sB[jt + 1]; return g; };
-      v2f tA, tB;
-      if (HS_MID_SCALAR_TAIL) {   // scalar sliding-window chains (see hs_row_stream3)
-         float a0 = sA[0], a1 = sA[1], b0 = sB[0], b1 = sB[1];
-         const float k0 = taps[0];
-         float tA0 = k0 * a0, tA1 = k0 * a1, tB0 = k0 * b0, tB1 = k0 * b1;
+      v2f tA = taps[0] * GA(0), tB = taps[0] * GB(0);
 #pragma unroll 4
-         for (int jt = 1; jt < K; jt++) {
-            const float k = taps[jt];
-            a0 = a1; b0 = b1;
-            a1 = sA[jt + 1]; b1 = sB[jt + 1];
-            tA0 += k * a0; tA1 += k * a1;
-            tB0 += k * b0; tB1 += k * b1;
-         }
-         tA.x = tA0; tA.y = tA1; tB.x = tB0; tB.y = tB1;
-      } else {
-         tA = taps[0] * GA(0); tB = taps[0] * GB(0);
-#pragma unroll 4
-         for (int jt = 1; jt < K; jt++) {
-            const float k = taps[jt];
-            tA += k * GA(jt);
-            tB += k * GB(jt);
-         }
+      for (int jt = 1; jt < K; jt++) {
+         const float k = taps[jt];
+         tA += k * GA(jt);
+         tB += k * GB(jt);
       }
       v2f *oA = reinterpret_cast<v2f *>(outA) + lane, *oB = reinterpret_cast<v2f *>(outB) + lane;
       *oA = tA;
@@ -855,9 +720,9 @@ __device__ __forceinline__ void hs_row_stream2(const HsPlaneBuf &img, float x, f
 // (s = 0, 1) is pair t % 41 of row t / 41.  Every task is the same RowFilter chain as before (one lane, ascending taps);
 // only the assignment of chains to lanes changes.  srow: three LDS rows `sstride` floats apart; out[i]: T' row of window
 // row yy[i].
-template <int NIT, class TAPS = const float *>
+template <int NIT>
 __device__ __forceinline__ void hs_row_stream3(const HsPlaneBuf &img, float x, float y, float a12, float a22, int P, int yy0, int yy1, int yy2,
-                                               float scale, const v2f *__restrict__ ctab, TAPS taps, int K,
+                                               float scale, const v2f *__restrict__ ctab, hs_row_taps taps, int K,
                                                float *__restrict__ srow, int sstride, float *__restrict__ out0, float *__restrict__ out1,
                                                float *__restrict__ out2, int pad_r, float a11 = 0.0f, float a21 = 0.0f)   // a11, a21: only read when ctab == nullptr
 {
@@ -883,39 +748,24 @@ __device__ __forceinline__ void hs_row_stream3(const HsPlaneBuf &img, float x, f
       const int colA = tA - HS_PATCH * rowA, colB = tB - HS_PATCH * rowB;
       const float c0 = (float)half;
       const float wA = c0 + (float)(colA - 20) * scale, wB = c0 + (float)(colB - 20) * scale;
-#if HS_ABL_MIDCONF   // ablation only (results invalid): every lane starts at its own column, i.e. consecutive LDS words - what the row pass costs WITHOUT its bank conflicts
-      const int xA = min(colA, pm - 1), xB = min(colB, pm - 1);
-#else
       const int xA = min(max((int)floorf(wA), 0), pm - 1), xB = min(max((int)floorf(wB), 0), pm - 1);
-#endif
       const float *sA = srow + rowA * sstride + xA, *sB = srow + rowB * sstride + xB;
-      auto GA = [&](int jt) { v2f g; g.x = sA[jt]; g.y = sA[jt + 1]; return g; };
-      auto GB = [&](int jt) { v2f g; g.x = sB[jt]; g.y = sB[jt + 1]; return g; };
+      // four scalar chains on a sliding window: every sample of the two rows is read once (the pair form of hs_row_stream2 reads it twice,
+      // as the second element of tap j and the first of tap j + 1) and no register pairs are assembled
+      // (k_patch_mid<512> 195.5 -> 178.1, <128> 149.5 -> 144.0 ms per 256 images against the pair form)
       v2f tA2, tB2;
-      if (HS_MID_SCALAR) {
-         // four scalar chains on a sliding window: every sample of the two rows is read once (the pair form reads it twice, as the
-         // second element of tap j and the first of tap j + 1) and no register pairs are assembled
-         float a0 = sA[0], a1 = sA[1], b0 = sB[0], b1 = sB[1];
-         const float k0 = taps[0];
-         float tA0 = k0 * a0, tA1 = k0 * a1, tB0 = k0 * b0, tB1 = k0 * b1;
+      float a0 = sA[0], a1 = sA[1], b0 = sB[0], b1 = sB[1];
+      const float k0 = taps[0];
+      float tA0 = k0 * a0, tA1 = k0 * a1, tB0 = k0 * b0, tB1 = k0 * b1;
 #pragma unroll 4
-         for (int jt = 1; jt < K; jt++) {
-            const float k = taps[jt];
-            a0 = a1; b0 = b1;
-            a1 = sA[jt + 1]; b1 = sB[jt + 1];
-            tA0 += k * a0; tA1 += k * a1;
-            tB0 += k * b0; tB1 += k * b1;
-         }
-         tA2.x = tA0; tA2.y = tA1; tB2.x = tB0; tB2.y = tB1;
-      } else {
-         tA2 = taps[0] * GA(0); tB2 = taps[0] * GB(0);
-#pragma unroll 4
-         for (int jt = 1; jt < K; jt++) {
-            const float k = taps[jt];
-            tA2 += k * GA(jt);
-            tB2 += k * GB(jt);
-         }
+      for (int jt = 1; jt < K; jt++) {
+         const float k = taps[jt];
+         a0 = a1; b0 = b1;
+         a1 = sA[jt + 1]; b1 = sB[jt + 1];
+         tA0 += k * a0; tA1 += k * a1;
+         tB0 += k * b0; tB1 += k * b1;
       }
+      tA2.x = tA0; tA2.y = tA1; tB2.x = tB0; tB2.y = tB1;
       const int yA = rowA ? yy1 : yy0, yB = rowB == 2 ? yy2 : yy1;
       v2f *oA = reinterpret_cast<v2f *>(rowA ? out1 : out0) + colA;
       v2f *oB = reinterpret_cast<v2f *>(rowB == 2 ? out2 : out1) + colB;
@@ -946,15 +796,9 @@ __device__ __forceinline__ void hs_row_stream3(const HsPlaneBuf &img, float x, f
 #define HS_BIG_TAPS 128   // K <= 113 for P <= 512
 #define HS_MID_RPAD 14    // K / 2 for P <= 128
 #define HS_BIG_RPAD 57    // K / 2 for P <= 512
-#ifndef HS_CHUNK_MIN_ROWS
 #define HS_CHUNK_MIN_ROWS 4   // measured 1 / 4 / 7 / 13: 15.4 / 15.0 / 15.5 / 16.4 ms (bin 3, 32 UHD images)
-#endif
-#ifndef HS_MID_NIT3_BIG
 #define HS_MID_NIT3_BIG 2
-#endif
-#ifndef HS_MID_NIT3_SMALL
 #define HS_MID_NIT3_SMALL 1
-#endif
 #define HS_MID_BLOCKS (256 * 7)   // persistent grids of the row-streamed bins: one T' slot per block
 #define HS_BIG_BLOCKS (256 * 8)
 
@@ -968,11 +812,12 @@ template <int PMAX> struct MidGeom {
    static constexpr int SROWS = 12 * SROW > CHUNK_MIN * HS_NEED ? 12 * SROW : CHUNK_MIN * HS_NEED;
    static constexpr int CHUNK_ROWS = SROWS / HS_NEED;
    // s_patch | taps | C table (float2 x (PMAX + 2)) | 4 waves x 3 rows, later the T' chunk
+   // (the taps area is no longer read - the row pass takes its taps from the table - but it stays: its size sets the occupancy)
    static constexpr int FLOATS = HS_PATCH_ARR + NTAP + 2 * (PMAX + 2) + SROWS;
 };
 
 template <int PMAX>
-__global__ __launch_bounds__(256, HS_MID_WAVES) void k_patch_mid(HessList hl, PatchWork pw, PatchIO io, KpTables tb)
+__global__ __launch_bounds__(256) void k_patch_mid(HessList hl, PatchWork pw, PatchIO io, KpTables tb)
 {
    typedef MidGeom<PMAX> GM;
    constexpr int BIN = GM::BIG ? 3 : 2;
@@ -980,8 +825,7 @@ __global__ __launch_bounds__(256, HS_MID_WAVES) void k_patch_mid(HessList hl, Pa
    constexpr int NIT3 = GM::BIG ? HS_MID_NIT3_BIG : HS_MID_NIT3_SMALL;   // gathers in flight per row of the three-row form
    extern __shared__ __attribute__((aligned(16))) float smem[];
    float *s_patch = smem;
-   float *s_taps = s_patch + HS_PATCH_ARR;
-   v2f *s_C = reinterpret_cast<v2f *>(s_taps + GM::NTAP);
+   v2f *s_C = reinterpret_cast<v2f *>(s_patch + HS_PATCH_ARR + GM::NTAP);
    float *s_srow = reinterpret_cast<float *>(s_C + (PMAX + 2));   // 4 waves x 3 rows x SROW
    float *Tp = io.trows + (size_t)blockIdx.x * ((size_t)(PMAX + 2 * GM::RPAD) * HS_NEED);
 
@@ -996,7 +840,7 @@ __global__ __launch_bounds__(256, HS_MID_WAVES) void k_patch_mid(HessList hl, Pa
    for (;;) {
       if (tid == 0) s_item = atomicAdd(pw.bin_work + BIN, 1u);
       __syncthreads();
-      const uint32_t wi = HS_TAPS_SCALAR ? (uint32_t)__builtin_amdgcn_readfirstlane((int)s_item) : s_item;
+      const uint32_t wi = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_item);
       if (wi >= cnt) break;
       const uint32_t h = pw.bin_items[(size_t)BIN * pw.cap + wi];
       const int b = hl.meta[h] >> 8;
@@ -1007,8 +851,7 @@ __global__ __launch_bounds__(256, HS_MID_WAVES) void k_patch_mid(HessList hl, Pa
       const float scale = (float)P0 / (float)HS_PATCH;
       const int K = tb.patch_tap_k[(P0 - 1) >> 1];
       const float *taps_g = tb.patch_taps + tb.patch_tap_off[(P0 - 1) >> 1];
-      const hs_row_taps ktap = HS_ROW_TAPS(taps_g, s_taps);   // the row pass's taps: scalar loads from the table, or the LDS copy
-      if (!HS_TAPS_SCALAR && tid < K) s_taps[tid] = taps_g[tid];
+      const hs_row_taps ktap = HS_ROW_TAPS(taps_g);   // the row pass's taps: scalar loads from the table
       for (int m = tid; m < P; m += 256) s_C[m] = hs_col_coord(a11, a21, m - half);
       __syncthreads();
       float *srowA = s_srow + wave * 3 * GM::SROW, *srowB = srowA + GM::SROW;
@@ -1017,26 +860,26 @@ __global__ __launch_bounds__(256, HS_MID_WAVES) void k_patch_mid(HessList hl, Pa
          // rows yy, yy + 4 and yy + 8 of this wavefront together; the last one or two rows in the narrower forms
          const int rr = K >> 1;
          if (yy + 8 < P)
-            hs_row_stream3<NIT3, hs_row_taps>(ib, x, y, a12, a22, P, yy, yy + 4, yy + 8, scale, s_C, ktap, K, srowA, GM::SROW,
+            hs_row_stream3<NIT3>(ib, x, y, a12, a22, P, yy, yy + 4, yy + 8, scale, s_C, ktap, K, srowA, GM::SROW,
                                  Tp + (size_t)(yy + rr) * HS_NEED, Tp + (size_t)(yy + 4 + rr) * HS_NEED, Tp + (size_t)(yy + 8 + rr) * HS_NEED, rr);
          else if (yy + 4 < P)
-            hs_row_stream2<NIT, hs_row_taps>(ib, x, y, a12, a22, P, yy, yy + 4, scale, s_C, ktap, K, srowA, srowB,
+            hs_row_stream2<NIT>(ib, x, y, a12, a22, P, yy, yy + 4, scale, s_C, ktap, K, srowA, srowB,
                                 Tp + (size_t)(yy + (K >> 1)) * HS_NEED, Tp + (size_t)(yy + 4 + (K >> 1)) * HS_NEED, K >> 1);
          else
-            hs_row_stream<NIT, hs_row_taps>(ib, x, y, a11, a12, a21, a22, P, yy, scale, s_C, ktap, K, srowA,
+            hs_row_stream<NIT>(ib, x, y, a11, a12, a21, a22, P, yy, scale, s_C, ktap, K, srowA,
                                Tp + (size_t)(yy + (K >> 1)) * HS_NEED, K >> 1);
       }
       __syncthreads();   // workgroup-scope release/acquire: the T' rows of all four waves are visible
       // staged column pass when a round holds at least HS_CHUNK_MIN_ROWS output rows (a round of one or two rows leaves
       // most of the block's threads idle: 41 outputs per row); otherwise straight from the slot
       if ((float)(K + 1) + (float)(HS_CHUNK_MIN_ROWS - 1) * scale <= (float)GM::CHUNK_ROWS)
-         hs_resample_chunked<hs_row_taps>(Tp + (K >> 1) * HS_NEED, P, scale, ktap, K >> 1, s_srow, GM::CHUNK_ROWS, s_patch);
+         hs_resample_chunked(Tp + (K >> 1) * HS_NEED, P, scale, ktap, K >> 1, s_srow, GM::CHUNK_ROWS, s_patch);
       else
-         hs_resample_reduced_batched<true, hs_row_taps>(Tp + (K >> 1) * HS_NEED, P, scale, ktap, K >> 1, s_patch);
+         hs_resample_reduced_batched<true>(Tp + (K >> 1) * HS_NEED, P, scale, ktap, K >> 1, s_patch);
       __syncthreads();
       for (int i = tid; i < HS_PATCH_PIX; i += 256) {
          float *po = io.patches + (size_t)(h - io.h_base) * HS_PATCH_PIX + i;
-         if (HS_NT_PATCH) hs_store_nt(po, s_patch[i]); else *po = s_patch[i];
+         hs_store_nt(po, s_patch[i]);
       }
       __syncthreads();
    }
@@ -1051,16 +894,13 @@ __global__ __launch_bounds__(256, HS_MID_WAVES) void k_patch_mid(HessList hl, Pa
 // The item count and the prefix stay on the device; the host only supplies an upper bound of the rows
 // (k_image_large_rows) to size the T' buffer.
 // ---------------------------------------------------------------------------------------
-#ifndef HS_LARGE_CHUNK
 #define HS_LARGE_CHUNK 18   // consecutive window rows per wavefront task (a multiple of three: the three-row form below)
-#endif
-#ifndef HS_LARGE_NIT3
 #define HS_LARGE_NIT3 2     // gathers in flight per row of the three-row form
-#endif
 
-// dynamic LDS: per wave  nrow x srow_stride floats (window rows + borders)  +  tap_stride floats (taps); blocks of 4, 2 or 1 wavefronts
-// (the host picks the largest count whose rows fit the CU's 160 KB).
-// nrow = 3: three consecutive window rows per step (hs_row_stream3: one tap broadcast and one column coordinate serve three rows, 123 pair
+// dynamic LDS: per wave  nrow x srow_stride floats (window rows + borders)  +  tap_stride floats (a tap area that is no longer read: the
+// taps come from the table; it stays because its size sets the occupancy); blocks of 4, 2 or 1 wavefronts (the host picks the largest
+// count whose rows fit the CU's 160 KB).
+// nrow = 3: three consecutive window rows per step (hs_row_stream3: one tap load and one column coordinate serve three rows, 123 pair
 // chains on 64 lanes instead of 41 - a third fewer vector and two thirds fewer LDS instructions per row than the one-row form); nrow = 1: the
 // one-row form, for windows whose three rows do not fit.  Items with P outside (p_lo, p_hi] are skipped: a batch whose largest window is far
 // above the common ones runs as two launches, so that the 513..1024 windows do not live with the LDS (= occupancy) of one 2800-pixel outlier.
@@ -1068,9 +908,8 @@ __global__ __launch_bounds__(256) void k_patch_large_rows(HessList hl, PatchWork
                                                           int p_lo, int p_hi)
 {
    extern __shared__ __attribute__((aligned(16))) float smem[];
-   const int wave = HS_TAPS_SCALAR ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
+   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
    float *srow = smem + (size_t)wave * (nrow * srow_stride + tap_stride);
-   float *stap = srow + nrow * srow_stride;
    const uint32_t *pre = io.row_prefix;
    const uint32_t n_items = min(pw.bin_count[HS_NBINS - 1], pw.cap);
    if (n_items == 0) return;
@@ -1105,29 +944,24 @@ __global__ __launch_bounds__(256) void k_patch_large_rows(HessList hl, PatchWork
          const float kx = hl.x[h], ky = hl.y[h];
          const float a11 = pw.A[4 * h], a12 = pw.A[4 * h + 1], a21 = pw.A[4 * h + 2], a22 = pw.A[4 * h + 3];
          const uint32_t first = pre[it];
-         // this item's taps -> the wave's LDS tap buffer (broadcast reads in the tap loop); with HS_TAPS_SCALAR they are read from the table itself
-         if (!HS_TAPS_SCALAR) {
-            for (int i = threadIdx.x & 63; i < K; i += 64) stap[i] = taps[i];
-            HS_WAVE_LDS_SYNC();
-         }
-         const hs_row_taps ktap = HS_ROW_TAPS(taps, stap);
+         const hs_row_taps ktap = HS_ROW_TAPS(taps);   // this item's taps, read from the table itself
          float *const out0 = io.trows + (size_t)row * HS_NEED;
          const int yy0 = (int)(row - first), nr = (int)(it_rows_end - row);
          int d = 0;
          if (nrow == 3) {
 #pragma unroll 1
             for (; d + 3 <= nr; d += 3)
-               hs_row_stream3<HS_LARGE_NIT3, hs_row_taps>(ib, kx, ky, a12, a22, P, yy0 + d, yy0 + d + 1, yy0 + d + 2, scale, nullptr, ktap, K, srow, srow_stride,
+               hs_row_stream3<HS_LARGE_NIT3>(ib, kx, ky, a12, a22, P, yy0 + d, yy0 + d + 1, yy0 + d + 2, scale, nullptr, ktap, K, srow, srow_stride,
                                              out0 + (size_t)d * HS_NEED, out0 + (size_t)(d + 1) * HS_NEED, out0 + (size_t)(d + 2) * HS_NEED, 0, a11, a21);
             if (d + 2 <= nr) {
-               hs_row_stream2<HS_LARGE_NIT3, hs_row_taps>(ib, kx, ky, a12, a22, P, yy0 + d, yy0 + d + 1, scale, nullptr, ktap, K, srow, srow + srow_stride,
+               hs_row_stream2<HS_LARGE_NIT3>(ib, kx, ky, a12, a22, P, yy0 + d, yy0 + d + 1, scale, nullptr, ktap, K, srow, srow + srow_stride,
                                              out0 + (size_t)d * HS_NEED, out0 + (size_t)(d + 1) * HS_NEED, 0, a11, a21);
                d += 2;
             }
          }
 #pragma unroll 1
          for (; d < nr; d++)
-            hs_row_stream<8, hs_row_taps>(ib, kx, ky, a11, a12, a21, a22, P, yy0 + d, scale, nullptr, ktap, K, srow, out0 + (size_t)d * HS_NEED);
+            hs_row_stream<8>(ib, kx, ky, a11, a12, a21, a22, P, yy0 + d, scale, nullptr, ktap, K, srow, out0 + (size_t)d * HS_NEED);
          row = it_rows_end;
          it++;
       }
@@ -1146,11 +980,11 @@ __global__ __launch_bounds__(256) void k_patch_large_finish(PatchWork pw, PatchI
       const float scale = (float)P0 / (float)HS_PATCH;
       const int K = tb.patch_tap_k[(P0 - 1) >> 1];
       const float *taps = tb.patch_taps + tb.patch_tap_off[(P0 - 1) >> 1];
-      hs_resample_reduced_batched<false, hs_row_taps>(io.trows + (size_t)pre[it] * HS_NEED, P, scale, HS_ROW_TAPS(taps, taps), K >> 1, s_patch);
+      hs_resample_reduced_batched<false>(io.trows + (size_t)pre[it] * HS_NEED, P, scale, HS_ROW_TAPS(taps), K >> 1, s_patch);
       __syncthreads();
       for (int i = threadIdx.x; i < HS_PATCH_PIX; i += 256) {
          float *po = io.patches + (size_t)(h - io.h_base) * HS_PATCH_PIX + i;
-         if (HS_NT_PATCH) hs_store_nt(po, s_patch[i]); else *po = s_patch[i];
+         hs_store_nt(po, s_patch[i]);
       }
       __syncthreads();
    }

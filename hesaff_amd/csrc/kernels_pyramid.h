@@ -219,12 +219,7 @@ struct CandRec {
    uint32_t pad[3];
 };
 #define HS_CAND_HOLE 0xffffffffu
-#ifndef HS_CAND_PAYLOAD
-#define HS_CAND_PAYLOAD 1   // 0 (A/B only): candidates carry their id alone and k_localize reads every neighbourhood from the planes
-#endif
-#ifndef HS_CAND_BLOCK
 #define HS_CAND_BLOCK 64u   // slots a wavefront reserves at a time (one global atomic per 64 candidates)
-#endif
 struct CandList {
    uint32_t *count;   // device counter (slots handed out, holes included)
    CandRec *items;
@@ -290,11 +285,7 @@ __global__ __launch_bounds__(256) void k_localize(OctaveCtx oc, CandList cl, Rec
       const float4 q0 = rec[0];
       const uint32_t id0 = __float_as_uint(q0.x), id1 = __float_as_uint(q0.y);
       if (id0 == HS_CAND_HOLE) break;
-#if HS_CAND_PAYLOAD
       const float4 q1 = rec[1], q2 = rec[2], q3 = rec[3], q4 = rec[4], q5 = rec[5];
-#else
-      const float4 q1 = q0, q2 = q0, q3 = q0, q4 = q0, q5 = q0;
-#endif
       const int b = (int)(id0 >> 2), level = (int)(id0 & 3u);
       const int r0 = (int)(id1 >> 16), c0 = (int)(id1 & 0xffffu);
       // level = i-2 : low = R[level], cur = R[level+1], high = R[level+2]
@@ -309,7 +300,7 @@ __global__ __launch_bounds__(256) void k_localize(OctaveCtx oc, CandList cl, Rec
       float hc = q4.x, hl = q4.y, hr = q4.z, hu = q4.w, hd = q5.x;
       for (int iter = 0; iter < 5; iter++) {
          r = nr; c = nc;
-         if (iter > 0 || !HS_CAND_PAYLOAD) {   // the centre moved (one candidate in nine): its neighbourhood comes from the planes
+         if (iter > 0) {   // the centre moved (one candidate in nine): its neighbourhood comes from the planes
             const float *pc = cur + (long long)r * pitch + c;
             const float *pl = low + (long long)r * pitch + c;
             const float *ph = high + (long long)r * pitch + c;
@@ -637,23 +628,15 @@ struct GraySrc {
    int row_stride;           // bytes between rows
 };
 
-#ifndef HS_MARCH15_WAVES
-#define HS_MARCH15_WAVES 0   // tuning: wavefronts per SIMD the K = 15 instantiation (144 VGPRs) is held to (0: the compiler's choice, 3)
-#endif
 template <int K, bool WRITE_L, bool WRITE_R, bool WRITE_HALF, bool WRITE_R0 = false, bool SRC8 = false>
-__global__ __launch_bounds__(256, (K == 15 ? HS_MARCH15_WAVES : 0)) void k_blur_hess_march(DPlane in, DPlane outL, DPlane outR, DPlane outHalf,
+__global__ __launch_bounds__(256) void k_blur_hess_march(DPlane in, DPlane outL, DPlane outR, DPlane outHalf,
                                                           const float *__restrict__ taps, float norm2, int band_rows,
                                                           DPlane outR0 = DPlane(), float norm2_in = 0.0f, GraySrc gs = GraySrc(), DPlane outGray = DPlane())
 {
    constexpr int R = K >> 1;
    constexpr int U = K + 1;                      // ring size and unroll factor (even: static prefetch parity)
    constexpr int W0 = 8 - R;                     // row-buffer float of column x-R, relative to 4*lane
-#ifndef HS_R0_LDS3
-#define HS_R0_LDS3 0   // tuning: 1 = the R0 epilogue re-reads its three input rows from LDS instead of carrying two of them in registers
-#endif
-   constexpr bool R0L3 = WRITE_R0 && HS_R0_LDS3;
-   constexpr int NB = R0L3 ? 3 : 2;              // input rows kept in LDS (the row being filtered, the row being staged [, one more])
-   __shared__ __attribute__((aligned(16))) float s_rows[4][NB][BM_ROWBUF];
+   __shared__ __attribute__((aligned(16))) float s_rows[4][2][BM_ROWBUF];   // input rows kept in LDS: the row being filtered, the row being staged
 
    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
    const int strip = blockIdx.x * 4 + wave;
@@ -716,7 +699,7 @@ __global__ __launch_bounds__(256, (K == 15 ? HS_MARCH15_WAVES : 0)) void k_blur_
 #pragma unroll
             for (int m = 0; m < 5; m++) {
                const int f = lane + 64 * m;
-               if (f >= 12 && f < 12 + BM_STRIP && xs - 12 + f < cols) { if (HS_NT_GRAY) hs_store_nt(go + f, dst5[m]); else go[f] = dst5[m]; }
+               if (f >= 12 && f < 12 + BM_STRIP && xs - 12 + f < cols) hs_store_nt(go + f, dst5[m]);
             }
          }
          return;
@@ -754,7 +737,7 @@ __global__ __launch_bounds__(256, (K == 15 ? HS_MARCH15_WAVES : 0)) void k_blur_
             constexpr int QF = (W0 / 4) * 4;                            // first quad, in floats relative to 4 * lane
             constexpr int NQ = (W0 + K + 2) / 4 - W0 / 4 + 1;
             constexpr int O = W0 - QF;                                  // S[O + c + j] = tap j of column c
-            const float4 *qb = reinterpret_cast<const float4 *>(__builtin_assume_aligned(s_rows[wave][R0L3 ? (t % 3) : (u & 1)] + 4 * lane + QF, 16));
+            const float4 *qb = reinterpret_cast<const float4 *>(__builtin_assume_aligned(s_rows[wave][u & 1] + 4 * lane + QF, 16));
             float S[4 * NQ];
 #pragma unroll
             for (int q = 0; q < NQ; q++) {
@@ -800,7 +783,7 @@ __global__ __launch_bounds__(256, (K == 15 ? HS_MARCH15_WAVES : 0)) void k_blur_
             if (row_in && store_lane) {
                if (WRITE_L) {
                   float *o = outL.img(b) + (long long)yl * outL.pitch + xl;
-                  if (full4) { if (HS_NT_PYR) hs_store_nt4(o, la.x, la.y, lb.x, lb.y); else *reinterpret_cast<float4 *>(o) = make_float4(la.x, la.y, lb.x, lb.y); }
+                  if (full4) hs_store_nt4(o, la.x, la.y, lb.x, lb.y);
                   else {
                      const float v[4] = {la.x, la.y, lb.x, lb.y};
                      for (int c = 0; c < 4; c++)
@@ -810,7 +793,7 @@ __global__ __launch_bounds__(256, (K == 15 ? HS_MARCH15_WAVES : 0)) void k_blur_
                if (WRITE_HALF) {
                   if ((yl & 1) == 0 && (yl >> 1) < outHalf.rows) {
                      float *o = outHalf.img(b) + (long long)(yl >> 1) * outHalf.pitch + (xl >> 1);
-                     if ((xl >> 1) + 1 < outHalf.cols) { if (HS_NT_PYR) hs_store_nt2(o, la.x, lb.x); else *reinterpret_cast<float2 *>(o) = make_float2(la.x, lb.x); }
+                     if ((xl >> 1) + 1 < outHalf.cols) hs_store_nt2(o, la.x, lb.x);
                      else if ((xl >> 1) < outHalf.cols) o[0] = la.x;
                   }
                }
@@ -825,7 +808,7 @@ __global__ __launch_bounds__(256, (K == 15 ? HS_MARCH15_WAVES : 0)) void k_blur_
                   const float r0 = (yin && cin0) ? ra.x : 0.0f, r1 = (yin && cin1) ? ra.y : 0.0f;
                   const float r2 = (yin && cin2) ? rbv.x : 0.0f, r3 = (yin && cin3) ? rbv.y : 0.0f;
                   float *o = outR.img(b) + (long long)yh * outR.pitch + xl;
-                  if (full4) { if (HS_NT_PYR_R) hs_store_nt4(o, r0, r1, r2, r3); else *reinterpret_cast<float4 *>(o) = make_float4(r0, r1, r2, r3); }
+                  if (full4) hs_store_nt4(o, r0, r1, r2, r3);
                   else {
                      const float v[4] = {r0, r1, r2, r3};
                      for (int c = 0; c < 4; c++)
@@ -850,8 +833,7 @@ __global__ __launch_bounds__(256, (K == 15 ? HS_MARCH15_WAVES : 0)) void k_blur_
                Q[4].x = m.w; Q[4].y = e5;
             };
             v2f Q2[5];
-            if (R0L3) { row_pairs((t + 1) % 3, Q0); row_pairs((t + 2) % 3, Q1); row_pairs(t % 3, Q2); }
-            else row_pairs(u & 1, Q2);
+            row_pairs(u & 1, Q2);
             const int yr = yh0 - 1 - R + (t - 1);
             if (yr >= yh0 && yr < yh1 && store_lane) {
                const bool yin = yr > 0 && yr < rows - 1;
@@ -860,20 +842,18 @@ __global__ __launch_bounds__(256, (K == 15 ? HS_MARCH15_WAVES : 0)) void k_blur_
                const float r0 = (yin && cin0) ? ra.x : 0.0f, r1 = (yin && cin1) ? ra.y : 0.0f;
                const float r2 = (yin && cin2) ? rbv.x : 0.0f, r3 = (yin && cin3) ? rbv.y : 0.0f;
                float *o = outR0.img(b) + (long long)yr * outR0.pitch + xl;
-               if (full4) { if (HS_NT_PYR_R) hs_store_nt4(o, r0, r1, r2, r3); else *reinterpret_cast<float4 *>(o) = make_float4(r0, r1, r2, r3); }
+               if (full4) hs_store_nt4(o, r0, r1, r2, r3);
                else {
                   const float v[4] = {r0, r1, r2, r3};
                   for (int c = 0; c < 4; c++)
                      if (xl + c < cols) o[c] = v[c];
                }
             }
-            if (!R0L3) {
 #pragma unroll
-               for (int i = 0; i < 5; i++) { Q0[i] = Q1[i]; Q1[i] = Q2[i]; }
-            }
+            for (int i = 0; i < 5; i++) { Q0[i] = Q1[i]; Q1[i] = Q2[i]; }
          }
          // ---- stage row t+1 (loaded during step t-1) for the next step ----
-         stage_row(R0L3 ? ((t + 1) % 3) : ((u + 1) & 1), pre[(u + 1) & 1]);
+         stage_row((u + 1) & 1, pre[(u + 1) & 1]);
       }
    }
 }
@@ -894,13 +874,8 @@ struct FivePlanes { DPlane R[5]; };
 // grid (ceil(cols/248), ceil(rows/band), B), block 64.
 // ---------------------------------------------------------------------------------------
 #define EXM_STRIP 248
-#ifndef EXM_RS
-#define EXM_RS 5      // ring rows: 3 under test + EXM_RS - 3 in flight (tuning; profiles/r05_notes.md)
-#endif
+#define EXM_RS 5      // ring rows: 3 under test + EXM_RS - 3 in flight (measured: profiles/r05_notes.md)
 #define EXM_AHEAD (EXM_RS - 3)
-#ifndef EXM_WAVES
-#define EXM_WAVES 0   // tuning: wavefronts per SIMD the register allocation is held to (0: the compiler's choice, 3)
-#endif
 
 __device__ __forceinline__ float hs_max3(float a, float b, float c)
 {
@@ -915,7 +890,7 @@ __device__ __forceinline__ float hs_min3(float a, float b, float c)
    return r;
 }
 
-__global__ __launch_bounds__(64, EXM_WAVES) void k_extrema_march(FivePlanes fp, float posThr, float negThr, CandList cl, int band)
+__global__ __launch_bounds__(64) void k_extrema_march(FivePlanes fp, float posThr, float negThr, CandList cl, int band)
 {
    const int lane = threadIdx.x, b = blockIdx.z;
    const int rows = fp.R[0].rows, cols = fp.R[0].cols, pitch = fp.R[0].pitch;
@@ -943,8 +918,9 @@ __global__ __launch_bounds__(64, EXM_WAVES) void k_extrema_march(FivePlanes fp, 
 #pragma unroll
    for (int k = 0; k < EXM_AHEAD; k++) {
       const long long off = (long long)min(ya - 1 + k, rows - 1) * pitch;
+      // (the float4 temporaries keep the load order the compiler has always chosen here: a plain assignment reorders the ring's loads)
 #pragma unroll
-      for (int p = 0; p < 5; p++) ring[p][k] = HS_NT_EXT ? hs_load_nt4(reinterpret_cast<const float4 *>(base[p] + off)) : *reinterpret_cast<const float4 *>(base[p] + off);
+      for (int p = 0; p < 5; p++) ring[p][k] = float4(*reinterpret_cast<const float4 *>(base[p] + off));
    }
    for (int k0 = 0; k0 < nsteps; k0 += EXM_RS) {
 #pragma unroll
@@ -954,7 +930,7 @@ __global__ __launch_bounds__(64, EXM_WAVES) void k_extrema_march(FivePlanes fp, 
             // EXM_AHEAD rows ahead, into the slot whose row (k - 3) is no longer needed
             const long long off = (long long)min(ya - 1 + k + EXM_AHEAD, rows - 1) * pitch;
 #pragma unroll
-            for (int p = 0; p < 5; p++) ring[p][(u + EXM_AHEAD) % EXM_RS] = HS_NT_EXT ? hs_load_nt4(reinterpret_cast<const float4 *>(base[p] + off)) : *reinterpret_cast<const float4 *>(base[p] + off);
+            for (int p = 0; p < 5; p++) ring[p][(u + EXM_AHEAD) % EXM_RS] = float4(*reinterpret_cast<const float4 *>(base[p] + off));
          }
          const int y = ya - 2 + k;        // row under test: slots (u-2, u-1, u) = rows y-1, y, y+1
          const int s0 = (u + EXM_RS - 2) % EXM_RS, s1 = (u + EXM_RS - 1) % EXM_RS, s2 = u;
@@ -1001,15 +977,11 @@ __global__ __launch_bounds__(64, EXM_WAVES) void k_extrema_march(FivePlanes fp, 
                if (__ballot(((hits >> (4 * l)) & 15u) != 0u) == 0ull) continue;   // wave-uniform: nothing at this level
                // columns x - 1 and x + 4 belong to the neighbouring lanes: the level's own plane (l + 1) in the three rows, the planes
                // below and above it in the middle row
-#if HS_CAND_PAYLOAD
                const float lowL = hs_from_lane_below(ring[l][s1].w), lowR = hs_from_lane_above(ring[l][s1].x);
                const float highL = hs_from_lane_below(ring[l + 2][s1].w), highR = hs_from_lane_above(ring[l + 2][s1].x);
                const float cL0 = hs_from_lane_below(ring[l + 1][s0].w), cR0 = hs_from_lane_above(ring[l + 1][s0].x);
                const float cL1 = hs_from_lane_below(ring[l + 1][s1].w), cR1 = hs_from_lane_above(ring[l + 1][s1].x);
                const float cL2 = hs_from_lane_below(ring[l + 1][s2].w), cR2 = hs_from_lane_above(ring[l + 1][s2].x);
-#else
-               const float lowL = 0, lowR = 0, highL = 0, highR = 0, cL0 = 0, cR0 = 0, cL1 = 0, cR1 = 0, cL2 = 0, cR2 = 0;
-#endif
                const float cu[3][6] = {
                   {cL0, ring[l + 1][s0].x, ring[l + 1][s0].y, ring[l + 1][s0].z, ring[l + 1][s0].w, cR0},
                   {cL1, ring[l + 1][s1].x, ring[l + 1][s1].y, ring[l + 1][s1].z, ring[l + 1][s1].w, cR1},
@@ -1037,13 +1009,11 @@ __global__ __launch_bounds__(64, EXM_WAVES) void k_extrema_march(FivePlanes fp, 
                      if (slot < cl.cap) {
                         float4 *dst = reinterpret_cast<float4 *>(cl.items + slot);
                         dst[0] = make_float4(__uint_as_float(((uint32_t)b << 2) | (uint32_t)l), __uint_as_float(((uint32_t)y << 16) | (uint32_t)(x + c)), cu[0][c], cu[0][c + 1]);
-#if HS_CAND_PAYLOAD
                         dst[1] = make_float4(cu[0][c + 2], cu[1][c], cu[1][c + 1], cu[1][c + 2]);
                         dst[2] = make_float4(cu[2][c], cu[2][c + 1], cu[2][c + 2], lo1[c + 1]);
                         dst[3] = make_float4(lo1[c], lo1[c + 2], lo0[c], lo2[c]);
                         dst[4] = make_float4(hi1[c + 1], hi1[c], hi1[c + 2], hi0[c]);
                         dst[5] = make_float4(hi2[c], 0.0f, 0.0f, 0.0f);
-#endif
                      }
                   }
                   wused += total;

@@ -34,14 +34,11 @@ struct SiftIO {
 #define HS_VO_DIM 40                          // rows/columns of the patch that carry weight in samplePatch
 #define HS_VO_TILE (HS_VO_DIM * HS_VO_DIM)    // float2 of k_sift_grad's LDS tile (row-major 40 x 40)
 // The gradient pairs of a keypoint in HBM (written once by k_sift_grad, read by k_sift_hist: the largest stream of the descriptor stage, and
-// what both kernels are bound by - profiles/r05_notes.md).  HS_VO_COMPACT: only the 16-byte items (2 pixels) of every row's span inside the
+// what both kernels are bound by - profiles/r05_notes.md).  Compact layout: only the 16-byte items (2 pixels) of every row's span inside the
 // circular mask are stored, row after row (row r: items f_lo(r) .. f_hi(r) of its 20) - 642 items + 6 zero items instead of 800: 10.4 KB
 // instead of 12.8 KB per keypoint.  KpTables::vo_rows / vo_src (host-built from the mask itself) describe the layout to both kernels.
-#ifndef HS_VO_COMPACT
-#define HS_VO_COMPACT 1
-#endif
-#define HS_VO_ITEMS (HS_VO_COMPACT ? 648 : 800)   // 16-byte items per keypoint; the items from HS_VO_ZERO on are zero
-#define HS_VO_ZERO (HS_VO_COMPACT ? 642 : 0)      // an item that is (0, 0, 0, 0) in every keypoint's block (plain layout: row 0 holds no masked pixel)
+#define HS_VO_ITEMS 648   // 16-byte items per keypoint; the items from HS_VO_ZERO on are zero
+#define HS_VO_ZERO 642    // an item that is (0, 0, 0, 0) in every keypoint's block
 #define HS_VO_PITCH (2 * HS_VO_ITEMS)             // float2 per keypoint in the gradient-pair buffer
 #define HS_SIFT_MSK_IT 5   // ceil(1245 / 256): pixels inside the circular mask per thread of a 256-thread block
 #define SM_TILE 64
@@ -53,15 +50,9 @@ struct SiftIO {
 // patches that a CU's resident wavefronts hold between their two passes shrink to about 0.75 MB - 190 MB over the device, inside
 // its 256 MB memory-side cache, which then serves most of the second pass.  Measured per 256 UHD images, kernel alone:
 // SM_KP = 64 / 32 / 16 / 8: 111.5 / 100.8 / 89.0 / 254.9 ms (8: the additions become the bottleneck); step 868 / 862 / 854 / 954 ms.
-#ifndef SM_KP
 #define SM_KP 16
-#endif
-#ifndef SM_PX
 #define SM_PX (64 * 64 / SM_KP)      // masked pixels per tile step (a multiple of 64)
-#endif
-#ifndef SM_UNROLL
 #define SM_UNROLL 8
-#endif
 #define SM_ROW (SM_PX + 1)           // LDS row stride: lane k walking row k is conflict-free
 __global__ __launch_bounds__(64) void k_sift_meanvar(SiftIO io, KpTables tb)
 {
@@ -89,7 +80,7 @@ __global__ __launch_bounds__(64) void k_sift_meanvar(SiftIO io, KpTables tb)
 #pragma unroll
             for (int u = 0; u < SM_PX / 64; u++) {
                const float *q = pp + pix[u];
-               s_tile[k * SM_ROW + lane + 64 * u] = (HS_NT_MEANVAR == 2 || (HS_NT_MEANVAR == 1 && pass == 1)) ? hs_load_nt(q) : *q;
+               s_tile[k * SM_ROW + lane + 64 * u] = *q;
             }
          }
          __syncthreads();
@@ -124,34 +115,24 @@ __global__ __launch_bounds__(64) void k_sift_meanvar(SiftIO io, KpTables tb)
 // neighbour addresses, output offset and mask value in registers; the interval constants of atanf come from an
 // LDS table (hm_atan2f_tab: no select trees, no divergence).  The next keypoint's pixels are requested before
 // the current one is evaluated.
-// grid: min(n, 256 * 8) blocks of 256 threads.
-#ifndef HS_SGRAD_TILE
-#define HS_SGRAD_TILE 1
-#endif
-#ifndef HS_SGRAD_WAVES
-#define HS_SGRAD_WAVES 0   // tuning: wavefronts per SIMD to hold the register allocation to (0: the compiler's choice)
-#endif
-__global__ __launch_bounds__(256, HS_SGRAD_WAVES) void k_sift_grad(SiftIO io, KpTables tb, float2 *__restrict__ vo)
+// grid: min(n, 32 blocks per CU) blocks of 256 threads (hesaff_ctx::sgrad_grid).
+__global__ __launch_bounds__(256) void k_sift_grad(SiftIO io, KpTables tb, float2 *__restrict__ vo)
 {
    __shared__ float s_p[HS_PATCH_PIX];
    __shared__ float s_at[HM_ATAN_TAB_FLOATS];
-#if HS_SGRAD_TILE
    // The keypoint's 40 x 40 pairs are collected here and leave as whole 16-byte items of consecutive addresses (the items of the rows'
    // masked spans; zeros for the pixels of an item outside the mask, which no thread ever writes): 81 full cache lines per keypoint
    // instead of 8-byte pieces that start and end in the middle of lines.  The kernel is bound by this write stream (without the
    // stores it runs in half the time).
    __shared__ __attribute__((aligned(16))) float2 s_vo[HS_VO_TILE];
-#endif
    const int tid = threadIdx.x;
    const uint32_t n = io.h_hi - io.h_lo;
-#if HS_SGRAD_TILE
    for (int i = tid; i < HS_VO_TILE; i += 256) s_vo[i] = make_float2(0.0f, 0.0f);
    // this thread's items of the keypoint's block in HBM: which tile item each of them is (KpTables::vo_src)
    constexpr int VO_NI = (HS_VO_ITEMS + 255) / 256;
    int vsrc[VO_NI];
 #pragma unroll
    for (int i = 0; i < VO_NI; i++) vsrc[i] = tb.vo_src[min(tid + 256 * i, HS_VO_ITEMS - 1)];
-#endif
    {
       const float at_init[HM_ATAN_TAB_FLOATS] = HM_ATAN_TAB_INIT;
       if (tid < HM_ATAN_TAB_FLOATS) s_at[tid] = at_init[tid];
@@ -171,7 +152,7 @@ __global__ __launch_bounds__(256, HS_SGRAD_WAVES) void k_sift_grad(SiftIO io, Kp
    {
       const float *gp = io.patches + (size_t)k * HS_PATCH_PIX;
 #pragma unroll
-      for (int q = 0; q < HS_PATCH_PIX_IT; q++) pv[q] = HS_NT_SGRAD_LD ? hs_load_nt(gp + min(tid + 256 * q, HS_PATCH_PIX - 1)) : gp[min(tid + 256 * q, HS_PATCH_PIX - 1)];
+      for (int q = 0; q < HS_PATCH_PIX_IT; q++) pv[q] = gp[min(tid + 256 * q, HS_PATCH_PIX - 1)];
    }
    for (; k < n; k += gridDim.x) {
       const bool cur_alive = alive != 0;
@@ -197,7 +178,7 @@ __global__ __launch_bounds__(256, HS_SGRAD_WAVES) void k_sift_grad(SiftIO io, Kp
          mean = io.meanvar[2 * (size_t)kn]; var = io.meanvar[2 * (size_t)kn + 1];
          const float *gp = io.patches + (size_t)kn * HS_PATCH_PIX;
 #pragma unroll
-         for (int q = 0; q < HS_PATCH_PIX_IT; q++) pv[q] = HS_NT_SGRAD_LD ? hs_load_nt(gp + min(tid + 256 * q, HS_PATCH_PIX - 1)) : gp[min(tid + 256 * q, HS_PATCH_PIX - 1)];
+         for (int q = 0; q < HS_PATCH_PIX_IT; q++) pv[q] = gp[min(tid + 256 * q, HS_PATCH_PIX - 1)];
       }
       __syncthreads();
       if (cur_alive) {
@@ -217,13 +198,7 @@ __global__ __launch_bounds__(256, HS_SGRAD_WAVES) void k_sift_grad(SiftIO io, Kp
                   const float grad = ND ? hm_sqrt_normal(gx * gx + gy * gy) : sqrtf(gx * gx + gy * gy);
                   const float ori = ND ? hm_atan2f_tab_nd(gy, gx, s_at) : hm_atan2f_tab(gy, gx, s_at);
                   const float o = hm_sift_orient_coord(ori);
-#if HS_SGRAD_TILE
                   s_vo[omq[q].x] = make_float2(__int_as_float(omq[q].y) * grad, o);
-#elif HS_NT_VO
-                  hs_store_nt2(reinterpret_cast<float *>(out + omq[q].x), __int_as_float(omq[q].y) * grad, o);
-#else
-                  out[omq[q].x] = make_float2(__int_as_float(omq[q].y) * grad, o);
-#endif
                }
                // the loop is unrolled only so that the per-pixel constants are registers; do not let the scheduler
                // interleave the iterations (five atan2 bodies in flight cost ~60 VGPRs)
@@ -233,7 +208,6 @@ __global__ __launch_bounds__(256, HS_SGRAD_WAVES) void k_sift_grad(SiftIO io, Kp
          if (cur_norm) pixels(std::true_type{});
          else pixels(std::false_type{});
       }
-#if HS_SGRAD_TILE
       __syncthreads();
       if (cur_alive) {
          float4 *o4 = reinterpret_cast<float4 *>(vo + (size_t)k * HS_VO_PITCH);
@@ -247,7 +221,6 @@ __global__ __launch_bounds__(256, HS_SGRAD_WAVES) void k_sift_grad(SiftIO io, Kp
             }
          }
       }
-#endif
       __syncthreads();
    }
 }
@@ -281,14 +254,8 @@ __global__ void k_math_sift(int n, const float *__restrict__ gy, const float *__
 // The (mask*grad, o) rows of a step are fetched by the whole wave as consecutive 16-byte items and handed
 // out through LDS (see "Row staging" below), the next step's rows in flight while the current ones are consumed.
 // grid-stride over groups of 4 keypoints, block 64.
-#ifndef HS_HIST_TRIM
-#define HS_HIST_TRIM 1
-#endif
 #define HS_HIST_AHEAD 1   // steps the row items are requested ahead (2, with a second set of five registers, measured the same: profiles/r05_notes.md)
-#ifndef HS_HIST_WAVES
-#define HS_HIST_WAVES 0   // tuning: wavefronts per SIMD to hold the register allocation to (0: the compiler's choice)
-#endif
-__global__ __launch_bounds__(64, HS_HIST_WAVES) void k_sift_hist(SiftIO io, KpTables tb, const float2 *__restrict__ vo)
+__global__ __launch_bounds__(64) void k_sift_hist(SiftIO io, KpTables tb, const float2 *__restrict__ vo)
 {
    __shared__ __attribute__((aligned(2048))) float s_acc[8 * 64];
    __shared__ float s_cw[64];   // [spatial bin][offset 0..15]
@@ -351,14 +318,9 @@ __global__ __launch_bounds__(64, HS_HIST_WAVES) void k_sift_hist(SiftIO io, KpTa
 #pragma unroll
       for (int u = 0; u < 5; u++) st_src[u] = min(st_kq[u], kmax) * HS_VO_ITEMS;
       // five named registers, not an array: carried around the loop an array ends up in scratch memory
-#if HS_NT_VO_LD
-#define HS_VO_LD(p) hs_load_nt4(p)
-#else
-#define HS_VO_LD(p) (*(p))
-#endif
       auto item_at = [&](int u, int i) { return st_src[u] + (int)st_tab[u][i * (HS_VO_DIM / 2)]; };   // float4 offset of staged item u at step i
-      float4 st0 = HS_VO_LD(g4 + item_at(0, 0)), st1 = HS_VO_LD(g4 + item_at(1, 0)), st2 = HS_VO_LD(g4 + item_at(2, 0)), st3 = HS_VO_LD(g4 + item_at(3, 0)),
-             st4 = HS_VO_LD(g4 + item_at(4, 0));
+      float4 st0 = g4[item_at(0, 0)], st1 = g4[item_at(1, 0)], st2 = g4[item_at(2, 0)], st3 = g4[item_at(3, 0)],
+             st4 = g4[item_at(4, 0)];
       // One step: park the step's items, request the items of step i + HS_HIST_AHEAD into the registers they came from, consume.
       auto step = [&](int i, float4 &a0, float4 &a1, float4 &a2, float4 &a3, float4 &a4) {
          HS_WAVE_LDS_SYNC();   // every lane has taken the previous step's items
@@ -366,8 +328,8 @@ __global__ __launch_bounds__(64, HS_HIST_WAVES) void k_sift_hist(SiftIO io, KpTa
          HS_WAVE_LDS_SYNC();
          {
             const int in = min(i + HS_HIST_AHEAD, 15);   // (unconditionally: the last rounds re-read row 15's items)
-            a0 = HS_VO_LD(g4 + item_at(0, in)); a1 = HS_VO_LD(g4 + item_at(1, in)); a2 = HS_VO_LD(g4 + item_at(2, in)); a3 = HS_VO_LD(g4 + item_at(3, in));
-            a4 = HS_VO_LD(g4 + item_at(4, in));
+            a0 = g4[item_at(0, in)]; a1 = g4[item_at(1, in)]; a2 = g4[item_at(2, in)]; a3 = g4[item_at(3, in)];
+            a4 = g4[item_at(4, in)];
          }
          if (valid) {
             float4 cur[8];
@@ -380,7 +342,6 @@ __global__ __launch_bounds__(64, HS_HIST_WAVES) void k_sift_hist(SiftIO io, KpTa
                const float qy = (j & 1) ? cur[j >> 1].w : cur[j >> 1].y;
                const float wc = cwc[j] * qx;   // w[c] * (mask*grad)
                const float v = wr * wc;
-#if HS_HIST_TRIM
                // siftdesc.cpp:63-77 in 14 instead of 19 vector instructions.  qy = o lies in [4, 12] (atan2f + 2 pi over 2 pi / 8), so
                // o - (int)o is v_fract_f32 (exact); v is a product of non-negative finite factors (weights, mask, a gradient of
                // finite pixels), i.e. +0 or positive: where the reference skips a term (`v > 0` false) v * wo is +0 and adding it
@@ -395,18 +356,6 @@ __global__ __launch_bounds__(64, HS_HIST_WAVES) void k_sift_hist(SiftIO io, KpTa
                const float a0 = *p0, a1 = *p1;   // bo0 != bo1: both reads in flight together
                *p0 = a0 + t0;
                *p1 = a1 + t1;
-#else
-               const int io0 = (int)qy;
-               const int bo0 = io0 & 7, bo1 = (io0 + 1) & 7;
-               const float wo1 = qy - (float)io0;
-               const float wo0 = 1.0f - wo1;
-               const bool pos = v > 0.0f;
-               const float t0 = pos ? v * wo0 : 0.0f;   // goes to bin bo0
-               const float t1 = pos ? v * wo1 : 0.0f;   // goes to bin bo0 + 1
-               const float a0 = acc[64 * bo0], a1 = acc[64 * bo1];   // bo0 != bo1: both reads in flight together
-               acc[64 * bo0] = a0 + t0;
-               acc[64 * bo1] = a1 + t1;
-#endif
             }
          }
       };

@@ -9,8 +9,9 @@
 // reproduced by ranking survivors through a bitmask laid out in exactly that order.
 //
 // Nothing here reads the environment unless the library is built with -DHESAFF_TUNING
-// (`make tuning`, a second .so for A/B measurements): a drop-in library must not change its
-// schedule, let alone its results, because of an environment variable.
+// (`make tuning`, a second .so that makes the one schedule observable: HESAFF_OVERLAP=0 runs every
+// kernel alone, HESAFF_DEBUG logs the chunks and batches, HESAFF_FAST selects fast mode): a drop-in
+// library must not change its schedule, let alone its results, because of an environment variable.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
@@ -104,12 +105,7 @@ static void hs_wait_event(hipEvent_t ev)
       timespec now;
       clock_gettime(CLOCK_MONOTONIC, &now);
       const long long waited = (long long)(now.tv_sec - t0.tv_sec) * 1000000000ll + (now.tv_nsec - t0.tv_nsec);
-#ifdef HESAFF_TUNING
-      static const long long nap_cap = getenv("HESAFF_NAP_US") ? atoll(getenv("HESAFF_NAP_US")) * 1000ll : 200000ll;
-#else
-      const long long nap_cap = 200000ll;
-#endif
-      const timespec nap = {0, (long)std::min<long long>(std::max<long long>(waited / 8, 20000), nap_cap)};
+      const timespec nap = {0, (long)std::min<long long>(std::max<long long>(waited / 8, 20000), 200000)};
       nanosleep(&nap, nullptr);
    }
 }
@@ -177,31 +173,22 @@ struct OctGeom {
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 #define HS_NSIDE 4   // side streams of the patch stage (one per window-size bin 0..3)
+#define HS_LARGE_NW 2      // wavefronts per block of k_patch_large_rows' three-row form at most: blocks of 40 KB find room beside the other
+                           // stages' kernels where blocks of 80 KB wait (against as many as fit: dense step 786 -> 773 ms, photographs 393 -> 383)
+#define HS_LARGE_SPLIT 1280   // windows up to this side in a launch of their own when the batch holds larger ones (k_patch_large_rows: split at
+                              // 1024 / 1280 / 1536: 7.23 / 7.15 / 7.94 ms per 32 photograph mosaics, profiles/r06_notes.md)
+#define HS_AFF_BLOCKS_PER_CU 8   // persistent k_affine blocks per CU (19 KB of LDS each: 8 resident).  Alone on the device 64 / 128 blocks per CU
+                                 // are 4 % faster (20.7 / 20.6 vs 21.6 ms), beside the other stages' kernels they make the step 3.5 % slower
+                                 // (453 vs 438 ms at B = 128): the queued blocks take every slot that frees up
 // grids of the grid-stride list kernels (blocks of 256 threads)
-#ifndef HS_GRID_LOC
 #define HS_GRID_LOC 1024
-#endif
-#ifndef HS_GRID_DED
 #define HS_GRID_DED 512
-#endif
-#ifndef HS_GRID_SCAT
 #define HS_GRID_SCAT 1024
-#endif
-#ifndef HS_GRID_PACK
 #define HS_GRID_PACK 3584   // 14 blocks per CU: what k_pack's 10.7 KB of LDS per block lets a CU hold
-#endif
-#ifndef HS_MID_CAP
 #define HS_MID_CAP 6   // blocks per CU of the two row-streamed bins (at most; the occupancy query may say fewer)
-#endif
-#ifndef HS_BIG_CAP
 #define HS_BIG_CAP 4
-#endif
-#ifndef HS_OVERSUB
 #define HS_OVERSUB 128u   // oversubscription of the statically strided persistent grids (step at B = 128: x 1 / 32 / 128 / 256 / 2048: 443 / 438 / 433 / 434 / 447 ms)
-#endif
-#ifndef HS_NSLOT
-#define HS_NSLOT 3   // patch / descriptor buffer slots of the group pipeline
-#endif
+#define HS_NSLOT 3   // patch buffer slots of the group pipeline
 // The HIP streams a context runs on (four compute streams, two copy streams).  They are created once per device and handed from a
 // destroyed context to the next one (capi_impl.h): which hardware queues a NEW stream shares depends on everything the process has
 // created before, so only reuse keeps the queue pairing of the first context.  Contexts alive at the same time get sets of their own.
@@ -227,7 +214,6 @@ struct hesaff_ctx {
    hesaff_params par;
    int device = 0;
    StreamSet sset;
-   bool pooled_streams = false;
    hipStream_t stream = nullptr;
    std::string err;
    hesaff::OctaveSchedule sched;
@@ -395,6 +381,7 @@ struct hesaff_ctx {
    // blocks per CU), so that every block takes the same share of a bin's list; queried per device at hesaff_create
    int n_cu = 256;
    uint32_t g_small0 = 256 * 6, g_small1 = 256 * 4, g_mid = HS_MID_BLOCKS, g_big = HS_BIG_BLOCKS, g_lfin = 256 * 4, g_shist = 256 * 32;
+   uint32_t sgrad_grid = 256 * 32;     // persistent grid of k_sift_grad: 32 blocks per CU (set_kernel_attrs)
    uint32_t trows_rows = 4u << 20;     // rows of T' (82 floats each) the large-window buffer holds at least: 1.3 GB
 
    hesaff_timings tm;
@@ -404,33 +391,18 @@ struct hesaff_ctx {
    int pool_priority = -1;             // hesaff_set_pool_priority: -1 lower the pool's priority when the plan is CPU-starved, 0 never, 1 always
    int stage_threads = 4;              // host threads that copy a chunk's pixels into pinned memory (hesaff_process_files: within its thread budget)
    hipStream_t side_streams[HS_NSIDE] = {nullptr, nullptr, nullptr, nullptr};
-   hipStream_t sift_stream = nullptr, sift_stream2 = nullptr;   // descriptor kernels of even / odd groups (sift2: HESAFF_SIFT2)
-   bool sift2 = true;
+   hipStream_t sift_stream = nullptr;     // descriptor kernels of every image group
    hipStream_t aff_stream = nullptr;      // affine shape of image group g+1 runs beside the patch extraction of group g
    hipEvent_t ev_detect_done = nullptr, ev_batch_done = nullptr;   // blocking-sync events: the host sleeps instead of spinning
    std::vector<hipEvent_t> ev_aff;        // one per image group, grown on demand
    hipEvent_t ev_extract_done[HS_NSLOT] = {}, ev_sift_done[HS_NSLOT] = {};
-   DevBuf b_patches2[HS_NSLOT], b_siftvec2[HS_NSLOT], b_meanvar2[HS_NSLOT], b_siftvo2[HS_NSLOT];
+   DevBuf b_patches2[HS_NSLOT];
+   DevBuf b_siftvec2, b_meanvar2, b_siftvo2;   // the descriptor stage's intermediates: one copy (ensure_group_buffers)
    hipEvent_t ev_fork = nullptr, ev_join[HS_NSIDE] = {nullptr, nullptr, nullptr, nullptr};
    bool fast_pyramid = false;      // hesaff_params.fast == 2: windows beyond bin 0 sampled from the scale-space level with the matching blur (not bit-exact)
-   // schedule knobs: fixed in the product build, environment-driven only under -DHESAFF_TUNING
+   // off in the product build; the tuning build (-DHESAFF_TUNING) reads them from the environment, and HESAFF_FAST for fast_pyramid
    bool no_overlap = false;        // HESAFF_OVERLAP=0: every kernel alone on the device (per-kernel profiling)
-   uint32_t sift_group_kpts = 0;   // HESAFF_GROUP: keypoints per image group; 0 = by batch
-   bool taper_groups = false;      // HESAFF_TAPER: small groups at both ends of a batch (pipeline fill / drain)
-   int aff_blocks_per_cu = 8;      // HESAFF_AFF_BLOCKS: persistent k_affine blocks per CU (19 KB of LDS each: 8 resident).  Alone on the device
-                                   // 64 / 128 blocks per CU are 4 % faster (20.7 / 20.6 vs 21.6 ms), beside the other stages' kernels they
-                                   // make the step 3.5 % slower (453 vs 438 ms at B = 128): the queued blocks take every slot that frees up
-   int side_mask = 15;             // HESAFF_SIDE: bit i = window-size bin i runs on its own side stream
-   int force_bands = 0;            // HESAFF_BANDS: force the band count of k_blur_hess_march
-   int force_exband = 0;           // HESAFF_EXBAND: rows per band of k_extrema_march (tuning)
    bool debug = false;             // HESAFF_DEBUG=1: launch geometry on stderr
-   uint32_t sgrad_grid = 0;        // persistent grid of k_sift_grad (set with the device: 32 blocks per CU; HESAFF_SGRAD_GRID; 0: one block per keypoint)
-   int large_stream = 0;           // HESAFF_LARGE_STREAM: 1 = the large-window kernels behind bins 0 and 1 on their stream, 0 = on the main stream (behind bin 3)
-   int large_nw = 2;               // HESAFF_LARGE_NW: wavefronts per block of the three-row form at most (0: as many as fit, up to four).  Two: blocks of 40 KB find room beside the other stages' kernels where blocks of 80 KB wait (dense step 786 -> 773 ms, photographs 393 -> 383)
-   int large_nrow = 3;             // HESAFF_LARGE_NROW: window rows per wavefront step of k_patch_large_rows (3, or 1: the round-5 form)
-   int large_split = 1280;         // HESAFF_LARGE_SPLIT: windows up to this side in a launch of their own when the batch holds larger ones (0: one launch)
-   uint32_t sift_slice = 0;        // HESAFF_SIFT_SLICE: keypoints per slice of the descriptor stage (launch_sift); 0 = a group's kernels each over the whole group
-   bool sift_slice_ring = true;    // HESAFF_SLICE_RING: the slices of a group reuse one slice-sized piece of the intermediates (0: every slice its own piece)
 
    std::vector<hipEvent_t> ev_pool;
    size_t ev_used = 0;
@@ -485,23 +457,21 @@ void build_tables(hesaff_ctx *c)
          memcpy(&om[2 * s + 1], &sm[i], 4);
       }
       upload(c->t_sgrad_nb, nb); upload(c->t_sgrad_om, om);
-      // layout of the gradient pairs in HBM (kernels_sift.h: HS_VO_COMPACT), from the mask itself: per row the span of 16-byte items
-      // (two pixels) that hold a pixel with weight, rows back to back; the plain layout is "every row whole"
+      // layout of the gradient pairs in HBM (kernels_sift.h: HS_VO_ITEMS), from the mask itself: per row the span of 16-byte items
+      // (two pixels) that hold a pixel with weight, rows back to back
       std::vector<int32_t> vrow(4 * HS_VO_DIM, 0);
       std::vector<uint16_t> vsrc(HS_VO_ITEMS, 0);
       int at = 0;
       for (int r = 0; r < HS_VO_DIM; r++) {
          int flo = 1, fhi = 0;
-         if (HS_VO_COMPACT) {
-            for (int cc = 0; cc < HS_VO_DIM; cc++)
-               if (sm[r * HS_PATCH + cc] > 0) { if (fhi < flo) flo = cc / 2; fhi = cc / 2; }
-         } else { flo = 0; fhi = HS_VO_DIM / 2 - 1; }
+         for (int cc = 0; cc < HS_VO_DIM; cc++)
+            if (sm[r * HS_PATCH + cc] > 0) { if (fhi < flo) flo = cc / 2; fhi = cc / 2; }
          vrow[4 * r + 0] = at - flo; vrow[4 * r + 1] = flo; vrow[4 * r + 2] = fhi;
          for (int f = flo; f <= fhi; f++, at++)
             if (at < HS_VO_ITEMS) vsrc[(size_t)at] = (uint16_t)(r * (HS_VO_DIM / 2) + f);
       }
       // the layout constants of kernels_sift.h are those of THIS mask (helpers.cpp:131-147 at patchSize 41)
-      if (at != (HS_VO_COMPACT ? HS_VO_ZERO : HS_VO_ITEMS) || sm[0] > 0) throw HsError(HESAFF_ERR_ARG, "internal: gradient-pair layout does not match the circular mask");
+      if (at != HS_VO_ZERO || sm[0] > 0) throw HsError(HESAFF_ERR_ARG, "internal: gradient-pair layout does not match the circular mask");
       upload(c->t_vo_rows, vrow); upload(c->t_vo_src, vsrc);
    }
    upload(c->t_smm, smm); upload(c->t_sift, sm); upload(c->t_bin0, b0); upload(c->t_bin1, b1); upload(c->t_w0, w0); upload(c->t_w1, w1);
@@ -820,7 +790,6 @@ void launch_march(hesaff_ctx *c, const DPlane &in, const DPlane &outL, const DPl
    const long long blocks_per_band = (long long)((strips + 3) / 4) * B;
    int best_nb = 16 * (int)std::max<long long>(1, std::min<long long>(4, 64 / std::max<long long>(1, blocks_per_band)));
    best_nb = std::max(1, std::min(best_nb, std::max(1, in.rows / 8)));
-   if (c->force_bands > 0) best_nb = std::min(c->force_bands, in.rows);
    const int band = (in.rows + best_nb - 1) / best_nb;
    if (c->debug) fprintf(stderr, "[hesaff] march K=%d %dx%d B=%d bands=%d band=%d blocks=%lld\n", K, in.cols, in.rows, B, best_nb, band, blocks_per_band * best_nb);
    const dim3 grid((strips + 3) / 4, (in.rows + band - 1) / band, B);
@@ -924,10 +893,7 @@ void run_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float *
    if (forked) {
       HIP_TRY(hipEventRecord(c->ev_fork, st));
       for (int i = 0; i < HS_NSIDE; i++) HIP_TRY(hipStreamWaitEvent(c->side_streams[i], c->ev_fork, 0));
-      if (c->side_mask & 1) s0 = c->side_streams[0];
-      if (c->side_mask & 2) s1 = c->side_streams[1];
-      if (c->side_mask & 4) s2 = c->side_streams[2];
-      if (c->side_mask & 8) s3 = c->side_streams[3];
+      s0 = c->side_streams[0]; s1 = c->side_streams[1]; s2 = c->side_streams[2]; s3 = c->side_streams[3];
    }
    {
       PatchIO io2 = io;
@@ -939,46 +905,45 @@ void run_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float *
       hipLaunchKernelGGL(k_patch_mid<HS_MID_PMAX>, dim3(c->g_mid), dim3(256), mid_lds_bytes(), s2, s.hl, s.pw, io2, c->tables);
       hipLaunchKernelGGL(k_patch_mid<HS_BIN3_PMAX>, dim3(c->g_big), dim3(256), big_lds_bytes(), s3, s.hl, s.pw, io3, c->tables);
    }
-   // the rare huge windows (P > 512): row tasks over all of them, then one block per keypoint.  The main stream shares its HIP stream
-   // (= hardware queue) with bin 3, whose kernel is the longest of the bins on photographs: behind it the large-window kernels made that
-   // queue the stage's critical path (8.1 + 8.8 + 1.9 ms per 32 photograph mosaics against 5.3 for the queue of bins 0 and 1).  They go
-   // behind bins 0 and 1 instead (large_stream = 1); k_prepare_patch and the fork event order them after the bin counts either way.
-   hipStream_t sl = (forked && c->large_stream == 1) ? s1 : st;
+   // the rare huge windows (P > 512): row tasks over all of them, then one block per keypoint, on the main stream, which shares its HIP
+   // stream (= hardware queue) with bin 3.  That queue is the stage's longest on photographs (8.1 + 8.8 + 1.9 ms per 32 photograph mosaics
+   // against 5.3 for the queue of bins 0 and 1), but the kernels behind bins 0 and 1 instead measured slower: photographs 397.2 / 394.9 ->
+   // 407.5 / 406.3 ms per step (profiles/r06_notes.md).  k_prepare_patch orders them after the bin counts.
    if (large_rows_bound > 0) {
       const uint32_t rows_cap = std::max(large_rows_bound, c->trows_rows);
       c->b_trows.ensure((size_t)rows_cap * HS_NEED * 4);
       c->b_rowprefix.ensure(((size_t)c->cap + 1) * 4);
       // LDS per wavefront for the largest window that exists in this batch (rounded up so that few distinct launch shapes occur),
       // not for the largest the image could hold.  Three window rows per wavefront step where they fit (k_patch_large_rows); a batch whose
-      // largest window is above 1024 runs as two launches - windows up to 1024 with the LDS, i.e. the occupancy, of a 1024 window, the
-      // rest with that of the batch's largest.
+      // largest window is above HS_LARGE_SPLIT runs as two launches - windows up to HS_LARGE_SPLIT with the LDS, i.e. the occupancy, of
+      // such a window, the rest with that of the batch's largest.
       const int pmax = std::min(c->max_p0 + 2, std::max(HS_BIN3_PMAX + 1, (c->batch_max_p > 0 ? c->batch_max_p : c->max_p0 + 2)));
       io.trows = c->b_trows.as<float>();
       io.row_prefix = c->b_rowprefix.as<uint32_t>();
       io.trows_cap = rows_cap;
       io.overflow = s.counters + 6;
-      hipLaunchKernelGGL(k_large_prefix, dim3(1), dim3(256), 0, sl, s.pw, c->b_rowprefix.as<uint32_t>());
+      hipLaunchKernelGGL(k_large_prefix, dim3(1), dim3(256), 0, st, s.pw, c->b_rowprefix.as<uint32_t>());
       auto launch_rows = [&](int p_lo, int p_hi) {
          const LargeGeom lg = large_geom(std::min(c->max_p0 + 2, (p_hi + 255) / 256 * 256));
          const size_t wave1 = lg.lds / 4;                                        // one row + taps
          const size_t wave3 = wave1 + (size_t)2 * lg.srow_stride * 4;            // three rows + taps
          // the three-row form only where six wavefronts of it fit a CU (windows up to about 1700): below that occupancy the kernel
          // is all exposed gather latency (measured: 3.5x slower at two wavefronts per CU, profiles/r06_notes.md)
-         const int nrow = (c->large_nrow == 3 && wave3 * 6 <= HS_LDS_PER_CU) ? 3 : 1;
+         const int nrow = wave3 * 6 <= HS_LDS_PER_CU ? 3 : 1;
          const size_t per_wave = nrow == 3 ? wave3 : wave1;
          // wavefronts per block: four while their rows fit the CU's LDS (plan_buffers made sure one row fits); blocks of two where two
          // such blocks pack the CU's LDS more tightly than one block of four
          uint32_t nw = 4;
          while (nw > 1 && per_wave * nw > HS_LDS_PER_CU) nw >>= 1;
          if (nw == 4 && (HS_LDS_PER_CU / (per_wave * 2)) * 2 > (HS_LDS_PER_CU / (per_wave * 4)) * 4) nw = 2;
-         if (nrow == 3 && c->large_nw > 0) nw = std::min<uint32_t>(nw, (uint32_t)c->large_nw);
+         if (nrow == 3) nw = std::min<uint32_t>(nw, HS_LARGE_NW);
          const uint32_t gblocks = std::min<uint32_t>((large_rows_bound + nw * HS_LARGE_CHUNK - 1) / (nw * HS_LARGE_CHUNK), 256 * 16 * (4 / nw));
-         hipLaunchKernelGGL(k_patch_large_rows, dim3(gblocks), dim3(64 * nw), per_wave * nw, sl, s.hl, s.pw, io, c->tables, lg.srow_stride, lg.tap_stride, nrow,
+         hipLaunchKernelGGL(k_patch_large_rows, dim3(gblocks), dim3(64 * nw), per_wave * nw, st, s.hl, s.pw, io, c->tables, lg.srow_stride, lg.tap_stride, nrow,
                             p_lo, std::min(p_hi, 0x7ffffff0));
       };
-      if (c->large_split > 0 && pmax > c->large_split) { launch_rows(0, c->large_split); launch_rows(c->large_split, pmax); }
+      if (pmax > HS_LARGE_SPLIT) { launch_rows(0, HS_LARGE_SPLIT); launch_rows(HS_LARGE_SPLIT, pmax); }
       else launch_rows(0, pmax);
-      hipLaunchKernelGGL(k_patch_large_finish, dim3(c->g_lfin), dim3(256), 0, sl, s.pw, io, c->tables);
+      hipLaunchKernelGGL(k_patch_large_finish, dim3(c->g_lfin), dim3(256), 0, st, s.pw, io, c->tables);
    }
    if (forked) {
       for (int i = 0; i < HS_NSIDE; i++) HIP_TRY(hipEventRecord(c->ev_join[i], c->side_streams[i]));
@@ -1106,7 +1071,7 @@ void run_detection(hesaff_ctx *c, const uint8_t *d_src, int channels, long long 
          // 25.0 / 23.4 / 22.2 / 23.5 ms for the detection stage of 256 UHD images); shorter bands when that would leave the chip short of wavefronts
          const int strips = (g.cols + EXM_STRIP - 1) / EXM_STRIP;
          auto waves_at = [&](int rows_per_band) { return (long long)strips * ((g.rows + rows_per_band - 1) / rows_per_band) * B; };
-         const int band = c->force_exband > 0 ? c->force_exband : (waves_at(128) >= 4096 ? 128 : (waves_at(64) >= 4096 ? 64 : 32));
+         const int band = waves_at(128) >= 4096 ? 128 : (waves_at(64) >= 4096 ? 64 : 32);
          const dim3 grid(strips, (g.rows + band - 1) / band, B);
          const int te = tm.begin(T_EXTREMA, 20.0 * (double)B * g.rows * g.cols);
          hipLaunchKernelGGL(k_extrema_march, grid, dim3(64), 0, st, fp, c->consts.positiveThreshold, c->consts.negativeThreshold, s.cl, band);
@@ -1173,56 +1138,31 @@ void collect_timings(hesaff_ctx *c, StageTimer &tm, int B)
    t.export_ms = c->export_ms; t.export_rows = c->export_rows;   // (run_chunks keeps them across the batches of a list)   // (+ the up-sampling pass when upscaleInputImage is set: not counted)
 }
 
-// The descriptor kernels (kernels_sift.h) over n patches in HBM.
-// sift_slice > 0: the group's keypoints in slices of that many, the four kernels back to back per slice, so that what a kernel
-// writes (mean / variance, gradient pairs, histograms) and the patches the slice's first kernel fetched are still in the device's
-// 256 MB memory-side cache when the next kernel of the slice reads them (sweep in profiles/r06_notes.md).
-void launch_sift_range(hesaff_ctx *c, hipStream_t ss, const SiftIO &so, uint32_t n, float2 *vo)
+// The descriptor kernels (kernels_sift.h) over n patches in HBM.  (Slices of a group, each slice's four kernels back to back so that
+// the intermediates stay in the memory-side cache, measured no faster: sweep in profiles/r06_notes.md.)
+void launch_sift(hesaff_ctx *c, hipStream_t ss, const SiftIO &so, uint32_t n, float2 *vo)
 {
    const uint32_t nb64 = (n + 63) / 64;
    hipLaunchKernelGGL(k_sift_meanvar, dim3((n + SM_KP - 1) / SM_KP), dim3(64), 0, ss, so, c->tables);
-   hipLaunchKernelGGL(k_sift_grad, dim3(c->sgrad_grid ? std::min(n, c->sgrad_grid) : n), dim3(256), 0, ss, so, c->tables, vo);
+   hipLaunchKernelGGL(k_sift_grad, dim3(std::min(n, c->sgrad_grid)), dim3(256), 0, ss, so, c->tables, vo);
    hipLaunchKernelGGL(k_sift_hist, dim3(std::min<uint32_t>((n + 3) / 4, c->g_shist)), dim3(64), 0, ss, so, c->tables, (const float2 *)vo);
    hipLaunchKernelGGL(k_sift_quantize, dim3(nb64), dim3(64), 0, ss, so, c->consts);
 }
 
-void launch_sift(hesaff_ctx *c, hipStream_t ss, const SiftIO &so, uint32_t n, float2 *vo)
-{
-   const uint32_t slice = c->sift_slice;
-   if (slice == 0 || slice >= n) { launch_sift_range(c, ss, so, n, vo); return; }
-   for (uint32_t lo = 0; lo < n; lo += slice) {
-      const uint32_t m = std::min(slice, n - lo);
-      SiftIO s = so;
-      s.patches = so.patches + (size_t)lo * HS_PATCH_PIX;
-      s.h_lo = so.h_lo + lo; s.h_hi = s.h_lo + m;
-      // the intermediates are indexed relative to h_lo: in ring mode every slice uses the group buffers' first slice-sized piece
-      // (the kernels of one stream run one after the other; a keypoint's zero items of the pair block are never written)
-      const size_t at = c->sift_slice_ring ? 0 : lo;
-      s.meanvar = so.meanvar + 2 * at;
-      s.vec = so.vec + 128 * at;
-      launch_sift_range(c, ss, s, m, vo + at * HS_VO_PITCH);
-   }
-}
-
-// per-group patch / descriptor buffers (two slots): sized once per batch for the largest group
+// per-group patch / descriptor buffers: sized once per batch for the largest group
 void ensure_group_buffers(hesaff_ctx *c, uint32_t n)
 {
    // The patch buffers rotate over HS_NSLOT slots (the patch stage fills one while the descriptor stage reads the others).  The
    // descriptor stage's own intermediates - gradient pairs (10.4 KB per keypoint), histograms, mean / variance - live and die on its
-   // stream: when both descriptor streams are one HIP stream (the product), one copy of them serves every group.
-   const int dslots = (c->sift_stream == c->sift_stream2 && !c->no_overlap) ? 1 : HS_NSLOT;
-   for (int slot = 0; slot < HS_NSLOT; slot++) {
-      c->b_patches2[slot].ensure_grow((size_t)n * HS_PATCH_PIX * 4);
-      if (slot >= dslots) continue;
-      c->b_siftvec2[slot].ensure_grow((size_t)n * 128 * 4);
-      c->b_meanvar2[slot].ensure_grow((size_t)n * 2 * 4);
-      // the (mask*grad, o) pairs of pixels outside the circular mask stay (0, 0): zero-fill on (re)allocation
-      const void *before = c->b_siftvo2[slot].p;
-      const size_t bytes_before = c->b_siftvo2[slot].bytes;
-      c->b_siftvo2[slot].ensure_grow((size_t)n * HS_VO_PITCH * 8 + 64);
-      if (c->b_siftvo2[slot].p != before || c->b_siftvo2[slot].bytes != bytes_before)
-         HIP_TRY(hipMemsetAsync(c->b_siftvo2[slot].p, 0, c->b_siftvo2[slot].bytes, c->stream));
-   }
+   // one stream (the main stream with HESAFF_OVERLAP=0), so one copy of them serves every group.
+   for (int slot = 0; slot < HS_NSLOT; slot++) c->b_patches2[slot].ensure_grow((size_t)n * HS_PATCH_PIX * 4);
+   c->b_siftvec2.ensure_grow((size_t)n * 128 * 4);
+   c->b_meanvar2.ensure_grow((size_t)n * 2 * 4);
+   // the (mask*grad, o) pairs of pixels outside the circular mask stay (0, 0): zero-fill on (re)allocation
+   const void *before = c->b_siftvo2.p;
+   const size_t bytes_before = c->b_siftvo2.bytes;
+   c->b_siftvo2.ensure_grow((size_t)n * HS_VO_PITCH * 8 + 64);
+   if (c->b_siftvo2.p != before || c->b_siftvo2.bytes != bytes_before) HIP_TRY(hipMemsetAsync(c->b_siftvo2.p, 0, c->b_siftvo2.bytes, c->stream));
 }
 
 // Whole hot path on a device-resident batch.  Leaves ordered KeyRec records in b_out and
@@ -1264,21 +1204,14 @@ void run_batch(hesaff_ctx *c, const uint8_t *d_src, int channels, long long src_
       // the T' rows of a group's huge windows must fit the row buffer (a single image may exceed it: the buffer grows)
       // (the group size itself hardly matters: 0.6 / 0.9 / 1.2 / 1.8 / 2.4 M keypoints per group at B = 256, shuffled: 810 / 823 / 816 /
       //  818 / 816 ms; what matters is that the buffers of a group stay modest: 33 KB per keypoint of a group)
-      const uint32_t group_kpts = c->sift_group_kpts ? c->sift_group_kpts : std::min<uint32_t>(std::max<uint32_t>((uint32_t)hs[B] / 16u, 300000u), 1200000u);
+      const uint32_t group_kpts = std::min<uint32_t>(std::max<uint32_t>((uint32_t)hs[B] / 16u, 300000u), 1200000u);
       struct Group { uint32_t lo, hi, large_rows; };
       std::vector<Group> groups;
       uint32_t max_n = 0;
       for (int g0 = 0; g0 < B;) {
          int g1 = g0 + 1;
          unsigned long long rows = lrows[g0];
-         // tapered schedule: the first groups grow (1/8, 1/8, 1/4, 1/2 of the limit) and the last ones shrink the same way, so that
-         // the pipeline's fill (affine shape of the first group alone on the device) and drain (descriptors of the last) are short
-         uint32_t limit = group_kpts;
-         if (c->taper_groups) {
-            const uint32_t done = (uint32_t)hs[g0], left = (uint32_t)hs[B] - done;
-            limit = std::min(group_kpts, std::max(group_kpts / 8u, std::min(done, left / 2u)));
-         }
-         while (g1 < B && (uint32_t)(hs[g1 + 1] - hs[g0]) <= limit && rows + lrows[g1] <= c->trows_rows) { rows += lrows[g1]; g1++; }
+         while (g1 < B && (uint32_t)(hs[g1 + 1] - hs[g0]) <= group_kpts && rows + lrows[g1] <= c->trows_rows) { rows += lrows[g1]; g1++; }
          if (rows > 0xffffffffull) throw HsError(HESAFF_ERR_NOMEM, "window rows of one image exceed 32 bits");
          if (hs[g1] > hs[g0]) {
             groups.push_back({(uint32_t)hs[g0], (uint32_t)hs[g1], (uint32_t)rows});
@@ -1294,14 +1227,13 @@ void run_batch(hesaff_ctx *c, const uint8_t *d_src, int channels, long long src_
       if (max_n) ensure_group_buffers(c, max_n);
       // Software pipeline over image groups, one stream per stage:
       //   affine shape of group g+1 (aff_stream)  |  patch extraction of group g (main + side
-      //   streams, latency-bound)  |  descriptor kernels of groups g-1 and g-2 (sift_stream, sift_stream2: the
-      //   HBM-bound mean / variance pass of one group beside the gradient and histogram kernels of the other).
-      // Three patch/descriptor buffer slots rotate.
+      //   streams, latency-bound)  |  descriptor kernels of the groups before (sift_stream).
+      // Three patch buffer slots rotate.
       hipStream_t as = c->no_overlap ? st : c->aff_stream;
       if (as != st) HIP_TRY(hipStreamWaitEvent(as, c->ev_detect_done, 0));
       auto launch_affine = [&](size_t gi) {
          const int ta = tm.begin(T_AFF, 0, as);
-         const uint32_t agrid = std::min<uint32_t>((groups[gi].hi - groups[gi].lo + HS_AFFP_G - 1) / HS_AFFP_G, (uint32_t)c->n_cu * c->aff_blocks_per_cu);
+         const uint32_t agrid = std::min<uint32_t>((groups[gi].hi - groups[gi].lo + HS_AFFP_G - 1) / HS_AFFP_G, (uint32_t)c->n_cu * HS_AFF_BLOCKS_PER_CU);
          hipLaunchKernelGGL(k_affine, dim3(agrid), dim3(64), 0, as, pt, s.hl, groups[gi].lo, groups[gi].hi, (const uint32_t *)(cnt + 3), c->tables, c->consts, s.ao);
          tm.end(ta);
          if (as != st) HIP_TRY(hipEventRecord(c->ev_aff[gi], as));
@@ -1323,14 +1255,13 @@ void run_batch(hesaff_ctx *c, const uint8_t *d_src, int channels, long long src_
          run_patch_stage(c, s, c->gray, c->b_patches2[slot].as<float>(), h_lo, groups[gi].large_rows, &pt);
          tm.end(t);
          HIP_TRY(hipEventRecord(c->ev_extract_done[slot], st));
-         hipStream_t ss = c->no_overlap ? st : ((c->sift2 && (gi & 1)) ? c->sift_stream2 : c->sift_stream);
+         hipStream_t ss = c->no_overlap ? st : c->sift_stream;
          if (ss != st) HIP_TRY(hipStreamWaitEvent(ss, c->ev_extract_done[slot], 0));
          SiftIO so;
-         const int dslot = (c->sift_stream == c->sift_stream2 && !c->no_overlap) ? 0 : slot;   // ensure_group_buffers
-         so.patches = c->b_patches2[slot].as<float>(); so.alive = s.pw.alive; so.meanvar = c->b_meanvar2[dslot].as<float>();
-         so.vec = c->b_siftvec2[dslot].as<float>(); so.desc = c->b_desc.as<uint8_t>(); so.h_lo = h_lo; so.h_hi = h_hi;
+         so.patches = c->b_patches2[slot].as<float>(); so.alive = s.pw.alive; so.meanvar = c->b_meanvar2.as<float>();
+         so.vec = c->b_siftvec2.as<float>(); so.desc = c->b_desc.as<uint8_t>(); so.h_lo = h_lo; so.h_hi = h_hi;
          const int ts = tm.begin(T_SIFT, 0, ss);
-         launch_sift(c, ss, so, n, c->b_siftvo2[dslot].as<float2>());
+         launch_sift(c, ss, so, n, c->b_siftvo2.as<float2>());
          tm.end(ts);
          HIP_TRY(hipEventRecord(c->ev_sift_done[slot], ss));
          slot_used[slot] = true;

@@ -2,7 +2,7 @@
 # round-end evidence, ONE pass (needs the tuning library: `make -C hesaff_amd/csrc tuning` before the gpurun call): GPU test suite, default bench line,
 # rocprofv3 stats + HBM traffic of the bench command, per-kernel PMC tables (dense and photographs), counters of the overlapped step,
 # per-kernel serial times (parity, fast = 2, photographs), fast-mode reports, config-5 sequence tables (band noise and photograph, fast 0 / 2),
-# the file path inside 2 / 4 / 8 CPUs with per-thread CPU seconds, end-to-end thread sweep, JPEG lists (UHD and 1024x768; pixels on the device / on the host)
+# the file path inside 2 / 4 / 8 CPUs with per-thread CPU seconds, end-to-end thread sweep, JPEG lists (UHD and 1024x768)
 cd $GRAFT_REPO_ROOT
 TAG=$1
 OUT=${2:?usage: bash scripts/gpu_final.sh <tag> <output directory>}

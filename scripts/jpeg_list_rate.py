@@ -1,7 +1,7 @@
 # usage (through gpurun): python scripts/jpeg_list_rate.py [files=512] [width=3840] [height=2160]
 # hesaff_process_files on a list of colour JPEG photographs (mosaics of the two sample photographs, 4:2:0, quality 90, on a RAM disk)
-# (JPEG_SUBSAMPLING=0|1|2, JPEG_PROGRESSIVE=1 for other encodings) with 2+2, 4+4 and 8+8 host threads: images/s with the pixels made on the device (the product) and - tuning build,
-# HESAFF_DEVICE_JPEG=0 - with the whole decode on the host threads.  One JSON line per case.
+# (JPEG_SUBSAMPLING=0|1|2, JPEG_PROGRESSIVE=1 for other encodings) with 2+2, 4+4 and 8+8 host threads: images/s with the pixels made on the device
+# (the product library).  One JSON line per case.
 import json, os, shutil, subprocess, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -22,7 +22,7 @@ def one_case(paths, dt, wt, fmt):
     ctx.close()
     assert all(s[0] == 0 for s in st), [s for s in st if s[0] != 0][:3]
     return {"images": len(paths), "chunk_images": p.max_batch, "decode_threads": dt, "write_threads": wt, "format": "text" if fmt == 1 else "sidecar",
-            "device_jpeg": os.environ.get("HESAFF_DEVICE_JPEG", "1") != "0", "images_per_s": len(paths) / dt_s,
+            "images_per_s": len(paths) / dt_s,
             "descriptors": int(sum(s[3] for s in st))}
 
 if __name__ == "__main__":
@@ -52,12 +52,8 @@ if __name__ == "__main__":
         print(json.dumps({"files": n, "width": W, "height": H, "bytes_per_file": os.path.getsize(paths[0]),
                           "subsampling": {"0": "4:4:4", "1": "4:2:2", "2": "4:2:0"}[os.environ.get("JPEG_SUBSAMPLING", "2")],
                           "progressive": os.environ.get("JPEG_PROGRESSIVE", "0") == "1"}))
-        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-        tuning = os.path.join(root, "hesaff_amd", "libhesaff_amd_tuning.so")
-        for dev in ("1", "0"):
-            for dt, wt in ((2, 2), (4, 4), (8, 8)):
-                env = dict(os.environ, HESAFF_AMD_LIB=tuning, HESAFF_DEVICE_JPEG=dev)
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", lst, str(dt), str(wt), "2"], env=env, capture_output=True, text=True)
-                print(r.stdout.strip().splitlines()[-1] if r.returncode == 0 and r.stdout.strip() else "FAILED %s" % r.stderr[-400:])
+        for dt, wt in ((2, 2), (4, 4), (8, 8)):
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", lst, str(dt), str(wt), "2"], capture_output=True, text=True)
+            print(r.stdout.strip().splitlines()[-1] if r.returncode == 0 and r.stdout.strip() else "FAILED %s" % r.stderr[-400:])
     finally:
         shutil.rmtree(tmp, ignore_errors=True)

@@ -3,6 +3,10 @@
 Python host mirror over the C ABI (include/hesaff_amd.h -> hesaff_amd/libhesaff_amd.so).
 The library is HIP only: there is no CPU fallback, creating a context without a gfx950
 device raises HesaffError.
+
+Input: 8-bit images (HesaffContext.detect_batch and its kin) or float32 grey planes, the reference's own
+CV_32FC1 detector input (the *_f32 methods: detect_batch_f32, detect_regions_f32, detect_batch_cb_f32,
+pyramid_f32 on numpy arrays, detect_batch_device_f32 on a torch tensor in device memory).
 """
 from ._binding import (  # noqa: F401
     HesaffError,

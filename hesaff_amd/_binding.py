@@ -170,6 +170,16 @@ def load_library():
     L.hesaff_set_pool_priority.argtypes = [vp, C.c_int]
     L.hesaff_stage_threads_for_pool.argtypes = [C.c_int]
     L.hesaff_detect_batch_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, _i32p, _i32p, C.POINTER(vp), C.POINTER(C.c_int64)]
+    # float grey planes (CV_32FC1, pyramid.h:73): the twins above with float images
+    L.hesaff_detect_batch_f32.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                          C.POINTER(_Result)]
+    L.hesaff_detect_regions_f32.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                            C.POINTER(_RegionResult)]
+    L.hesaff_detect_batch_cb_f32.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                             CHUNK_SINK, vp]
+    L.hesaff_detect_batch_device_f32.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int64, _i32p, _i32p, C.POINTER(vp),
+                                                 C.POINTER(C.c_int64)]
+    L.hesaff_stage_pyramid_f32.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
     L.hesaff_set_profiling.argtypes = [vp, C.c_int]
     L.hesaff_get_timings.argtypes = [vp, C.POINTER(Timings)]
     L.hesaff_ellipse.argtypes = [vp, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -232,6 +242,8 @@ ABI_SYMBOLS = [
     "hesaff_output_is_complete", "hesaff_read_jpeg_coefficients", "hesaff_read_jpeg_coefficients_alloc", "hesaff_stage_jpeg_pixels",
     "hesaff_read_pnm_alloc", "hesaff_read_image_alloc", "hesaff_set_pinned_read_budget", "hesaff_set_pool_priority",
     "hesaff_stage_threads_for_pool", "hesaff_read_bmp", "hesaff_read_tiff", "hesaff_detect_regions", "hesaff_sizeof_region",
+    "hesaff_detect_batch_f32", "hesaff_detect_batch_cb_f32", "hesaff_detect_regions_f32", "hesaff_detect_batch_device_f32",
+    "hesaff_stage_pyramid_f32",
 ]
 
 
@@ -394,6 +406,7 @@ class HesaffContext:
     def __init__(self, params=None, device=0):
         self.L = load_library()
         self.params = params if params is not None else default_params()
+        self.device = int(device)   # HIP device ordinal = torch's cuda index (detect_batch_device_f32 checks its tensor against it)
         self.h = C.c_void_p()
         rc = self.L.hesaff_create(C.byref(self.h), C.byref(self.params), device)
         if rc != 0:
@@ -464,6 +477,113 @@ class HesaffContext:
                 keys = np.zeros(0, KEYPOINT_DTYPE)
             out.append((regions, keys))
         return out
+
+    # ---- float grey planes (CV_32FC1, pyramid.h:73) ----
+    @staticmethod
+    def _f32_list(images):
+        """2-D float32 arrays -> (arrays, ptrs, widths, heights, strides); no cast: any other dtype or shape is a TypeError."""
+        for i, im in enumerate(images):
+            if not isinstance(im, np.ndarray) or im.dtype != np.float32 or im.ndim != 2:
+                raise TypeError("image %d: the _f32 methods take 2-D float32 arrays, got %s" % (
+                    i, "%s %s" % (im.dtype, im.shape) if isinstance(im, np.ndarray) else type(im).__name__))
+        imgs = []
+        for im in images:
+            if im.strides[1] != 4 or im.strides[0] < 4 * im.shape[1] or im.strides[0] % 4:
+                im = np.ascontiguousarray(im)   # (same dtype: a layout copy, not a cast)
+            imgs.append(im)
+        n = len(imgs)
+        ptrs = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
+        ws = (C.c_int * n)(*[im.shape[1] for im in imgs])
+        hs = (C.c_int * n)(*[im.shape[0] for im in imgs])
+        st = (C.c_int * n)(*[im.strides[0] for im in imgs])
+        return imgs, ptrs, ws, hs, st
+
+    def detect_batch_f32(self, images):
+        """hesaff_detect_batch_f32: 2-D float32 grey planes (padded rows allowed) -> list of (count_hessian, keys[KEYPOINT_DTYPE])."""
+        imgs, ptrs, ws, hs, st = self._f32_list(images)
+        res = (_Result * len(imgs))()
+        self._check(self.L.hesaff_detect_batch_f32(self.h, len(imgs), ptrs, ws, hs, st, res))
+        return [(r.count_hessian, self._keys_at(r.keys, r.count_desc)) for r in res]
+
+    def detect_regions_f32(self, images):
+        """hesaff_detect_regions_f32: detect_regions for 2-D float32 grey planes."""
+        imgs, ptrs, ws, hs, st = self._f32_list(images)
+        res = (_RegionResult * len(imgs))()
+        self._check(self.L.hesaff_detect_regions_f32(self.h, len(imgs), ptrs, ws, hs, st, res))
+        out = []
+        for r in res:
+            if r.count_hessian > 0:
+                regions = np.frombuffer((C.c_char * (r.count_hessian * REGION_DTYPE.itemsize)).from_address(r.regions), dtype=REGION_DTYPE).copy()
+            else:
+                regions = np.zeros(0, REGION_DTYPE)
+            out.append((regions, self._keys_at(r.keys, r.count_desc)))
+        return out
+
+    def detect_batch_cb_f32(self, images, sink):
+        """hesaff_detect_batch_cb_f32: detect_batch_cb for 2-D float32 grey planes."""
+        imgs, ptrs, ws, hs, st = self._f32_list(images)
+
+        def _sink(_user, m, idx, res):
+            out = [(res[i].count_hessian, self._keys_at(res[i].keys, res[i].count_desc)) for i in range(m)]
+            return 1 if sink([idx[i] for i in range(m)], out) else 0
+        cb = CHUNK_SINK(_sink)
+        self._check(self.L.hesaff_detect_batch_cb_f32(self.h, len(imgs), ptrs, ws, hs, st, cb, None))
+
+    def detect_batch_device_f32(self, t):
+        """hesaff_detect_batch_device_f32 on a torch tensor on this context's device: float32, [n, H, W] or [H, W], unit stride
+        along W, any positive row and image stride.  A tensor that repeats images or rows through a zero stride (expand, broadcast)
+        is made contiguous first: the C entry point reads a stride of 0 as "tightly packed".  torch's current stream on that device
+        is synchronised before the call.  -> (count_hessian[n], count_desc[n], d_keys, total) as detect_batch_device returns them."""
+        import torch
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() not in (2, 3):
+            raise TypeError("detect_batch_device_f32 takes a float32 torch tensor [n, H, W] or [H, W]")
+        if t.dim() == 2:
+            t = t.unsqueeze(0)
+        if t.device.type != "cuda":
+            raise ValueError("detect_batch_device_f32: the tensor is not in device memory")
+        if t.device.index != self.device:
+            raise ValueError("detect_batch_device_f32: the tensor is on %s, this context on cuda:%d" % (t.device, self.device))
+        if t.stride(2) != 1 and t.shape[2] > 1:
+            raise ValueError("detect_batch_device_f32: the tensor needs unit stride along W")
+        n, H, W = t.shape
+        if (n > 1 and t.stride(0) == 0) or (H > 1 and t.stride(1) == 0):
+            t = t.contiguous()   # (on torch's current stream, which is synchronised below)
+        torch.cuda.current_stream(t.device).synchronize()
+        ch = np.zeros(n, np.int32); cd = np.zeros(n, np.int32)
+        dk = C.c_void_p(); tot = C.c_int64()
+        row, img = t.stride(1) * 4, t.stride(0) * 4
+        if H == 1:
+            row = 0   # (the stride of a single row is never used: tightly packed)
+        if n == 1:
+            img = 0
+        self._check(self.L.hesaff_detect_batch_device_f32(self.h, n, C.c_void_p(t.data_ptr()), W, H, row, img, ch, cd, C.byref(dk),
+                                                          C.byref(tot)))
+        return ch, cd, dk.value, tot.value
+
+    def pyramid_f32(self, img):
+        """hesaff_stage_pyramid_f32: pyramid() for a 2-D float32 grey plane."""
+        if not isinstance(img, np.ndarray) or img.dtype != np.float32 or img.ndim != 2:
+            raise TypeError("pyramid_f32 takes a 2-D float32 array")
+        g = np.ascontiguousarray(img)
+        no = C.c_int(); nf = C.c_size_t()
+        self._check(self.L.hesaff_stage_pyramid_f32(self.h, None, g.shape[0], g.shape[1], None, C.byref(no), C.byref(nf)))
+        buf = np.empty(max(nf.value, 1), np.float32)
+        self._check(self.L.hesaff_stage_pyramid_f32(self.h, g.ctypes.data, g.shape[0], g.shape[1], buf.ctypes.data, C.byref(no), C.byref(nf)))
+        out = []; off = 0; r, c = g.shape
+        for _ in range(no.value):
+            n = r * c
+            Ls = buf[off:off + 5 * n].reshape(5, r, c); off += 5 * n
+            Rs = buf[off:off + 5 * n].reshape(5, r, c); off += 5 * n
+            out.append((Ls, Rs))
+            r //= 2; c //= 2
+        return out
+
+    @staticmethod
+    def _keys_at(addr, count):
+        """a copy of `count` records at a library-owned address"""
+        if count <= 0:
+            return np.zeros(0, KEYPOINT_DTYPE)
+        return np.frombuffer((C.c_char * (count * KEYPOINT_DTYPE.itemsize)).from_address(addr), dtype=KEYPOINT_DTYPE).copy()
 
     def detect_batch_raw(self, images):
         """hesaff_detect_batch without copying the records out: -> ctypes array of hesaff_result whose `keys` point into

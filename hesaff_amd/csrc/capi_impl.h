@@ -247,7 +247,7 @@ int hesaff_detect_batch_device(hesaff_ctx *c, int n, const void *d_gray, int wid
    bind_device(c);
    if (n > c->par.max_batch) throw HsError(HESAFF_ERR_ARG, "n exceeds hesaff_params.max_batch for the device-resident entry point");
    plan(c, c->par.max_batch, height, width);
-   run_batch(c, (const uint8_t *)d_gray, 1, (long long)width * height, width, n, height, width);
+   run_batch(c, SrcImages::u8(d_gray, 1, (long long)width * height, width), n, height, width);
    const int32_t *hs = c->h_starts.data(), *ds = c->h_starts.data() + (n + 1);
    for (int b = 0; b < n; b++) {
       if (count_hessian) count_hessian[b] = hs[b + 1] - hs[b];
@@ -273,6 +273,19 @@ int hesaff_detect_batch_device(hesaff_ctx *c, int n, const void *d_gray, int wid
 
 namespace {
 using namespace hesaff_engine;
+
+// the refusal of a float image with a pixel outside the domain (include/hesaff_amd.h): the caller's image index and the first such pixel
+[[noreturn]] void throw_bad_f32(int index, const uint8_t *img, int H, int W, size_t stride)
+{
+   int row = 0, col = 0;
+   float v = 0.0f;
+   char msg[256];
+   if (first_bad_f32(img, H, W, stride, &row, &col, &v))
+      snprintf(msg, sizeof msg, "image %d: pixel (row %d, column %d) is %.9g; float input must be finite with |v| <= 2^20", index, row, col, (double)v);
+   else
+      snprintf(msg, sizeof msg, "image %d: a pixel is not finite or exceeds 2^20 in magnitude", index);
+   throw HsError(HESAFF_ERR_ARG, msg);
+}
 
 void ensure_copy_streams(hesaff_ctx *c)
 {
@@ -331,7 +344,7 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
       if (!io.next(s->q)) return nullptr;
       const HostChunk &q = s->q;
       const int slot = k & 1;
-      const size_t row_bytes = (size_t)q.W * q.ch, img_bytes = row_bytes * q.H;
+      const size_t row_bytes = (size_t)q.W * q.bpp(), img_bytes = row_bytes * q.H;
       // what travels per image: its pixels, or - a JPEG file - its coefficient blob (the pixels are then made in b_in2 by the device)
       const size_t unit = q.blob_bytes ? q.blob_bytes : img_bytes, total = unit * q.data.size();
       hs_wait_event(c->ev_in_free[slot]);   // chunk k-2 no longer reads this input buffer (never recorded: returns at once)
@@ -351,18 +364,25 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
          return s;
       }
       c->pin_in[slot].ensure(unit * (size_t)s->largest);   // sized once, for the large chunks that follow a small first one
-      // pixels into the pinned buffer: a chunk of 64 UHD images is 0.5 GB - on four threads when it is worth it (the first chunk's
-      // copy is the pipeline's fill: nothing runs on the device meanwhile)
+      // pixels into the pinned buffer: a chunk of 64 UHD images is 0.5 GB (2.1 GB as float planes) - on four threads when it is worth
+      // it (the first chunk's copy is the pipeline's fill: nothing runs on the device meanwhile).  Float planes are checked in the same
+      // pass (copy_row_f32): the first image of a share with a pixel outside the domain stops that share and is reported below.
+      const size_t nimg = q.data.size();
+      std::vector<size_t> bad_img(nimg + 1, nimg);   // per share: the first refused image (nimg: none)
       auto copy_images = [&](size_t b0, size_t b1) {
          for (size_t b = b0; b < b1; b++) {
             uint8_t *dst = (uint8_t *)c->pin_in[slot].p + unit * b;
             if (q.blob_bytes) { memcpy(dst, q.data[b], unit); continue; }
             const size_t stride = q.stride[b];
+            if (q.f32) {
+               for (int y = 0; y < q.H; y++)
+                  if (!copy_row_f32(dst + row_bytes * y, q.data[b] + stride * y, q.W)) { bad_img[b0] = b; return; }
+               continue;
+            }
             if (stride == row_bytes) memcpy(dst, q.data[b], img_bytes);
             else for (int y = 0; y < q.H; y++) memcpy(dst + row_bytes * y, q.data[b] + stride * y, row_bytes);
          }
       };
-      const size_t nimg = q.data.size();
       const size_t nthr = (total >= ((size_t)32 << 20) && nimg >= 4) ? (size_t)std::max(1, std::min(4, c->stage_threads)) : 1;
       {
          std::vector<std::thread> th;
@@ -374,6 +394,10 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
          copy_images(0, nimg / nthr);
          if (t < nthr) copy_images(nimg * t / nthr, nimg);
          for (auto &x : th) x.join();
+      }
+      if (q.f32) {
+         const size_t b = *std::min_element(bad_img.begin(), bad_img.end());
+         if (b < nimg) throw_bad_f32(q.index[b], q.data[b], q.H, q.W, q.stride[b]);
       }
       HIP_TRY(hipMemcpyAsync(q.blob_bytes ? c->b_jcoef[slot].p : c->b_in2[slot].p, c->pin_in[slot].p, total, hipMemcpyHostToDevice, c->h2d_stream));
       HIP_TRY(hipEventRecord(c->ev_h2d[slot], c->h2d_stream));
@@ -413,13 +437,15 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
          staged = std::async(std::launch::async, stage, k + 1);
          const HostChunk &q = cur->q;
          const int slot = k & 1, B = (int)q.data.size();
-         const size_t row_bytes = (size_t)q.W * q.ch, img_bytes = row_bytes * q.H;
+         const size_t row_bytes = (size_t)q.W * q.bpp(), img_bytes = row_bytes * q.H;
          HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_h2d[slot], 0));
          try {
             plan(c, std::max(std::min<int>(c->par.max_batch, B), cur->largest), q.H, q.W);
             // a chunk of JPEG files: inverse DCT, up-sampling and colour conversion of all its images (kernels_jpeg.h) into the input slot
             if (q.blob_bytes) jpeg_pixels(c, c->b_jcoef[slot].as<uint8_t>(), make_jpeg_geom(q.jpeg), B, (uint8_t *)c->b_in2[slot].p, img_bytes, c->stream);
-            run_batch(c, (const uint8_t *)c->b_in2[slot].p, q.ch, (long long)img_bytes, (int)row_bytes, B, q.H, q.W);
+            const SrcImages src = q.f32 ? SrcImages::f32(c->b_in2[slot].p, (long long)img_bytes, (int)row_bytes)
+                                        : SrcImages::u8(c->b_in2[slot].p, q.ch, (long long)img_bytes, (int)row_bytes);
+            run_batch(c, src, B, q.H, q.W);
          } catch (const HsError &e) {
             // this chunk's images cannot be planned (geometry) or exceed the planned keypoint capacity: that is about these
             // images, not about the device.  Both are thrown with the main stream idle; the other chunks go on when the
@@ -539,6 +565,42 @@ void validate_image_list(int n, const uint8_t *const *images, const int *widths,
    }
 }
 
+// the same for the float entry points (include/hesaff_amd.h: input layout); -> the image pointers as ArrayIO holds them
+std::vector<const uint8_t *> validate_f32_list(int n, const float *const *images, const int *widths, const int *heights, const int *strides)
+{
+   std::vector<const uint8_t *> bytes((size_t)n);
+   for (int j = 0; j < n; j++) {
+      const int W = widths[j], H = heights[j];
+      if (!images[j] || W < 1 || H < 1) throw HsError(HESAFF_ERR_ARG, "bad image");
+      if ((uintptr_t)images[j] % 4 != 0) throw HsError(HESAFF_ERR_ARG, "float image pointer not 4-byte aligned");
+      if (strides && ((long long)strides[j] < 4LL * W || strides[j] % 4 != 0))
+         throw HsError(HESAFF_ERR_ARG, "row stride of a float image must be at least 4 * width bytes and a multiple of 4");
+      bytes[(size_t)j] = reinterpret_cast<const uint8_t *>(images[j]);
+   }
+   return bytes;
+}
+
+// hesaff_detect_batch_device_f32's check (k_check_f32) of n planes in device memory, before any kernel reads them as an image: one flag
+// per image, read back once; a refused image is copied back to name its first pixel outside the domain
+void check_device_f32(hesaff_ctx *c, int n, const uint8_t *d, long long img_stride, int row_stride, int H, int W)
+{
+   c->b_stage.ensure((size_t)n * 4);
+   int32_t *flags = c->b_stage.as<int32_t>();
+   HIP_TRY(hipMemsetAsync(flags, 0, (size_t)n * 4, c->stream));
+   const int gx = std::max(1, std::min(H, (8 * c->n_cu + n - 1) / n));   // about 8 blocks per CU in all
+   hipLaunchKernelGGL(k_check_f32, dim3(gx, 1, n), dim3(256), 0, c->stream, d, img_stride, row_stride, H, W, flags);
+   std::vector<int32_t> h((size_t)n);
+   HIP_TRY(hipMemcpyAsync(h.data(), flags, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+   HIP_TRY(hipStreamSynchronize(c->stream));
+   HIP_TRY(hipGetLastError());
+   for (int b = 0; b < n; b++) {
+      if (!h[(size_t)b]) continue;
+      std::vector<uint8_t> img((size_t)H * W * 4);
+      HIP_TRY(hipMemcpy2D(img.data(), (size_t)W * 4, d + (long long)b * img_stride, (size_t)row_stride, (size_t)W * 4, (size_t)H, hipMemcpyDeviceToHost));
+      throw_bad_f32(b, img.data(), H, W, (size_t)W * 4);
+   }
+}
+
 } // namespace
 
 extern "C" {
@@ -579,6 +641,71 @@ int hesaff_detect_regions(hesaff_ctx *c, int n, const uint8_t *const *images, co
    ArrayIO io(&c->ring, c->par.max_batch, n, images, widths, heights, strides, channels);
    io.region_results = results;
    run_chunks(c, io, 0);
+   HS_API_END(c)
+}
+
+// ---- float grey planes (CV_32FC1, pyramid.h:73): the same paths with the float source format ----
+int hesaff_detect_batch_f32(hesaff_ctx *c, int n, const float *const *images, const int *widths, const int *heights, const int *strides,
+                            hesaff_result *results)
+{
+   if (!c || n < 0 || (n > 0 && (!images || !widths || !heights || !results))) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   const std::vector<const uint8_t *> bytes = validate_f32_list(n, images, widths, heights, strides);
+   ArrayIO io(&c->ring, c->par.max_batch, n, bytes.data(), widths, heights, strides, nullptr, true);
+   io.results = results;
+   run_chunks(c, io, 0);
+   HS_API_END(c)
+}
+
+int hesaff_detect_batch_cb_f32(hesaff_ctx *c, int n, const float *const *images, const int *widths, const int *heights, const int *strides,
+                               hesaff_chunk_sink sink, void *user)
+{
+   if (!c || n < 0 || !sink || (n > 0 && (!images || !widths || !heights))) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   const std::vector<const uint8_t *> bytes = validate_f32_list(n, images, widths, heights, strides);
+   ArrayIO io(&c->ring, c->par.max_batch, n, bytes.data(), widths, heights, strides, nullptr, true);
+   io.sink = sink; io.user = user;
+   run_chunks(c, io, 3);
+   if (io.sink_rc.load() != 0) throw HsError(HESAFF_ERR_IO, "the result sink reported an error");
+   HS_API_END(c)
+}
+
+int hesaff_detect_regions_f32(hesaff_ctx *c, int n, const float *const *images, const int *widths, const int *heights, const int *strides,
+                              hesaff_region_result *results)
+{
+   if (!c || n < 0 || (n > 0 && (!images || !widths || !heights || !results))) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   const std::vector<const uint8_t *> bytes = validate_f32_list(n, images, widths, heights, strides);
+   ArrayIO io(&c->ring, c->par.max_batch, n, bytes.data(), widths, heights, strides, nullptr, true);
+   io.region_results = results;
+   run_chunks(c, io, 0);
+   HS_API_END(c)
+}
+
+int hesaff_detect_batch_device_f32(hesaff_ctx *c, int n, const void *d_planes, int width, int height, int row_stride, int64_t img_stride,
+                                   int32_t *count_hessian, int32_t *count_desc, const void **d_keys_out, int64_t *total_out)
+{
+   if (!c || n < 1 || !d_planes || width < 1 || height < 1 || row_stride < 0 || img_stride < 0) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   bind_device(c);
+   if (n > c->par.max_batch) throw HsError(HESAFF_ERR_ARG, "n exceeds hesaff_params.max_batch for the device-resident entry point");
+   const long long rs = row_stride ? row_stride : 4LL * width;
+   const long long is = img_stride ? (long long)img_stride : rs * height;
+   if ((uintptr_t)d_planes % 4 != 0) throw HsError(HESAFF_ERR_ARG, "float planes not 4-byte aligned");
+   if (rs < 4LL * width || rs % 4 != 0 || rs > 0x7fffffffLL)
+      throw HsError(HESAFF_ERR_ARG, "row stride of a float plane must be at least 4 * width bytes and a multiple of 4");
+   if (is % 4 != 0 || (n > 1 && is < rs * (height - 1) + 4LL * width))
+      throw HsError(HESAFF_ERR_ARG, "image stride of the float planes must be a multiple of 4 and keep the images apart");
+   plan(c, c->par.max_batch, height, width);
+   check_device_f32(c, n, (const uint8_t *)d_planes, is, (int)rs, height, width);
+   run_batch(c, SrcImages::f32(d_planes, is, (int)rs), n, height, width);
+   const int32_t *hs = c->h_starts.data(), *ds = c->h_starts.data() + (n + 1);
+   for (int b = 0; b < n; b++) {
+      if (count_hessian) count_hessian[b] = hs[b + 1] - hs[b];
+      if (count_desc) count_desc[b] = ds[b + 1] - ds[b];
+   }
+   if (d_keys_out) *d_keys_out = c->b_out.p;
+   if (total_out) *total_out = ds[n];
    HS_API_END(c)
 }
 
@@ -749,7 +876,38 @@ int hesaff_stage_pyramid(hesaff_ctx *c, const uint8_t *gray, int rows, int cols,
       c->ev_used = 0;
       StageTimer tm(c);
       Lists s = make_lists(c);
-      run_detection(c, (const uint8_t *)c->b_input.p, 1, (long long)rows * cols, cols, 1, s, tm, true, planes);
+      run_detection(c, SrcImages::u8(c->b_input.p, 1, (long long)rows * cols, cols), 1, s, tm, true, planes);
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      HIP_TRY(hipGetLastError());
+   }
+   HS_API_END(c)
+}
+
+int hesaff_stage_pyramid_f32(hesaff_ctx *c, const float *plane, int rows, int cols, float *planes, int *n_octaves, size_t *n_floats)
+{
+   if (!c || rows < 1 || cols < 1) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   bind_device(c);
+   plan(c, 1, rows, cols);
+   size_t nf = 0;
+   for (const OctGeom &g : c->oct) nf += (size_t)10 * g.rows * g.cols;
+   if (n_octaves) *n_octaves = (int)c->oct.size();
+   if (n_floats) *n_floats = nf;
+   if (planes) {
+      if (!plane) throw HsError(HESAFF_ERR_ARG, "plane is NULL");
+      if ((uintptr_t)plane % 4 != 0) throw HsError(HESAFF_ERR_ARG, "float plane not 4-byte aligned");
+      const size_t bytes = (size_t)rows * cols * 4;
+      int r = 0, col = 0;
+      float v = 0.0f;
+      if (first_bad_f32((const uint8_t *)plane, rows, cols, (size_t)cols * 4, &r, &col, &v))   // the value domain of the _f32 entry points
+         throw_bad_f32(0, (const uint8_t *)plane, rows, cols, (size_t)cols * 4);
+      c->b_input.ensure(bytes);
+      c->b_stage.ensure((size_t)rows * round_up(cols, 64) * 4);
+      HIP_TRY(hipMemcpyAsync(c->b_input.p, plane, bytes, hipMemcpyHostToDevice, c->stream));
+      c->ev_used = 0;
+      StageTimer tm(c);
+      Lists s = make_lists(c);
+      run_detection(c, SrcImages::f32(c->b_input.p, (long long)bytes, cols * 4), 1, s, tm, true, planes);
       HIP_TRY(hipStreamSynchronize(c->stream));
       HIP_TRY(hipGetLastError());
    }
@@ -767,7 +925,7 @@ int hesaff_stage_hessian_keypoints(hesaff_ctx *c, const uint8_t *gray, int rows,
    c->ev_used = 0;
    StageTimer tm(c);
    Lists s = make_lists(c);
-   run_detection(c, (const uint8_t *)c->b_input.p, 1, (long long)rows * cols, cols, 1, s, tm, false, nullptr);
+   run_detection(c, SrcImages::u8(c->b_input.p, 1, (long long)rows * cols, cols), 1, s, tm, false, nullptr);
    uint32_t cn[8];
    HIP_TRY(hipMemcpyAsync(cn, s.counters, sizeof cn, hipMemcpyDeviceToHost, c->stream));
    HIP_TRY(hipStreamSynchronize(c->stream));

@@ -7,6 +7,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <cstdint>
+#include <cstring>
 #include <deque>
 #include <mutex>
 #include <pthread.h>
@@ -56,6 +57,8 @@ struct BlockRing {
 
 struct HostChunk {                // at most max_batch images of one geometry
    int W = 0, H = 0, ch = 1;
+   bool f32 = false;              // float grey planes (the _f32 entry points, CV_32FC1 as pyramid.h:73 takes it): ch = 1, 4 bytes per pixel
+   size_t bpp() const { return f32 ? 4 : (size_t)ch; }
    std::vector<const uint8_t *> data;
    std::vector<size_t> stride;    // bytes between rows
    std::vector<int> index;        // the caller's image numbers
@@ -109,8 +112,38 @@ struct ChunkIO {
    virtual ~ChunkIO() {}
 };
 
-// hesaff_detect_batch / hesaff_detect_batch_cb: chunks of a caller-supplied image list, images of equal (width, height, channels)
-// grouped in input order.  The arguments are validated by the caller (capi_impl.h: validate_image_list).
+// The value domain of the float entry points (include/hesaff_amd.h): finite, |v| <= 2^20.  On the bit pattern: |v| > 2^20 (0x49800000),
+// +-Inf and NaN are exactly the patterns whose low 31 bits exceed 0x49800000.
+inline bool f32_bits_bad(uint32_t v) { return (int32_t)(v & 0x7fffffffu) > 0x49800000; }
+
+// One row of float pixels into the staging buffer with the value check fused into the copy (one pass over the source):
+// false when the row holds a pixel outside the domain.
+inline bool copy_row_f32(uint8_t *dst, const uint8_t *src, int n)
+{
+   int32_t bad = 0;
+   for (int x = 0; x < n; x++) {
+      uint32_t v;
+      memcpy(&v, src + 4 * (size_t)x, 4);
+      memcpy(dst + 4 * (size_t)x, &v, 4);
+      bad |= (int32_t)f32_bits_bad(v);
+   }
+   return bad == 0;
+}
+
+// The first pixel of an image outside the domain, in raster order: false when there is none.
+inline bool first_bad_f32(const uint8_t *img, int H, int W, size_t stride, int *row, int *col, float *value)
+{
+   for (int y = 0; y < H; y++)
+      for (int x = 0; x < W; x++) {
+         uint32_t v;
+         memcpy(&v, img + stride * y + 4 * (size_t)x, 4);
+         if (f32_bits_bad(v)) { *row = y; *col = x; memcpy(value, &v, 4); return true; }
+      }
+   return false;
+}
+
+// hesaff_detect_batch / hesaff_detect_batch_cb (and their _f32 forms): chunks of a caller-supplied image list, images of equal
+// (width, height, format) grouped in input order.  The arguments are validated by the caller (capi_impl.h: validate_image_list).
 struct ArrayIO : ChunkIO {
    std::vector<HostChunk> chunks;
    size_t pos = 0;
@@ -121,7 +154,7 @@ struct ArrayIO : ChunkIO {
    hesaff_region_result *region_results = nullptr;   // hesaff_detect_regions: filled in place (instead of results)
    std::atomic<int> sink_rc{0};                 // written by done() on the caller's thread, read by next() on the staging thread
    ArrayIO(BlockRing *ring_, int max_batch, int n, const uint8_t *const *images, const int *widths, const int *heights, const int *strides,
-           const int *channels)
+           const int *channels, bool f32 = false)
       : ring(ring_)
    {
       std::vector<char> taken((size_t)n, 0);
@@ -149,12 +182,12 @@ struct ArrayIO : ChunkIO {
          size_t g0 = 0;
          for (size_t sz : sizes) {
             HostChunk k;
-            k.W = W; k.H = H; k.ch = ch;
+            k.W = W; k.H = H; k.ch = ch; k.f32 = f32;
             for (size_t g = g0; g < g0 + sz; g++) {
                const int j = grp[g];
                k.index.push_back(j);
                k.data.push_back(images[j]);
-               k.stride.push_back(strides ? (size_t)strides[j] : (size_t)W * ch);
+               k.stride.push_back(strides ? (size_t)strides[j] : (size_t)W * k.bpp());
             }
             chunks.push_back(std::move(k));
             g0 += sz;
@@ -172,7 +205,7 @@ struct ArrayIO : ChunkIO {
       if (pos == 0 || pos > chunks.size()) return this_chunk;
       const HostChunk &q = chunks[pos - 1];   // the chunk next() handed out last (staging thread, like next())
       size_t m = (size_t)this_chunk;
-      for (size_t i = pos; i < chunks.size() && chunks[i].W == q.W && chunks[i].H == q.H && chunks[i].ch == q.ch; i++) m = std::max(m, chunks[i].data.size());
+      for (size_t i = pos; i < chunks.size() && chunks[i].W == q.W && chunks[i].H == q.H && chunks[i].ch == q.ch && chunks[i].f32 == q.f32; i++) m = std::max(m, chunks[i].data.size());
       return (int)m;
    }
    int wants() const override { return region_results ? (WANT_KEYS | WANT_REGIONS) : WANT_KEYS; }

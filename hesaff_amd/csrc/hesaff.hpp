@@ -12,7 +12,9 @@
 // callbacks observe a chain that has already run - a callback cannot suppress or alter
 // the later stages, and `keys` is the same whatever the callbacks do.  The `blur` plane is
 // a light handle (BlurPlane) instead of the cv::Mat; its pixels are those of
-// hesaff_stage_pyramid's plane of that octave and level.
+// hesaff_stage_pyramid's plane of that octave and level (hesaff_stage_pyramid_f32's for float input).
+// detectPyramidKeypoints takes the reference's own input, a CV_32FC1 plane (pyramid.h:73), or
+// the 8-bit image main() converts to one (hesaff.cpp:138-148).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -44,7 +46,8 @@ struct HessianAffineParams {   // hesaff.cpp:21-36
 typedef hesaff_keypoint Keypoint;   // hesaff.cpp:41-48, identical layout
 
 // the `const cv::Mat &blur` argument of both callbacks: which plane of the scale space the keypoint was found / shaped on
-// (pixels: hesaff_stage_pyramid's blur plane `level` of octave `octave`), and that octave's pixelDistance (pyramid.cpp:288)
+// (pixels: the blur plane `level` of octave `octave` of hesaff_stage_pyramid - of hesaff_stage_pyramid_f32 when the input was a
+// float plane), and that octave's pixelDistance (pyramid.cpp:288)
 struct BlurPlane {
    int octave, level;
    float pixelDistance;
@@ -98,25 +101,31 @@ struct AffineHessianDetector {
          hesaff_result r;
          if (hesaff_detect_batch(ctx_, 1, &image, &width, &height, &stride, &channels, &r) != HESAFF_OK)
             throw std::runtime_error(hesaff_last_error(ctx_));
-         g_numberOfPoints = r.count_hessian;
-         g_numberOfAffinePoints += r.count_desc;   // the reference never resets this counter (hesaff.cpp:166)
-         keys.assign(r.keys, r.keys + r.count_desc);
+         take(r.count_hessian, r.count_desc, r.keys);
          return;
       }
       hesaff_region_result r;
       if (hesaff_detect_regions(ctx_, 1, &image, &width, &height, &stride, &channels, &r) != HESAFF_OK)
          throw std::runtime_error(hesaff_last_error(ctx_));
-      g_numberOfPoints = r.count_hessian;
-      g_numberOfAffinePoints += r.count_desc;
-      keys.assign(r.keys, r.keys + r.count_desc);
-      // hesaff.cpp:66-105 depth-first: each Hessian keypoint, then its affine shape when findAffineShape converged
-      for (int i = 0; i < r.count_hessian; i++) {
-         const hesaff_region &g = r.regions[i];
-         const BlurPlane blur = {g.octave, g.level, g.pixelDistance};
-         if (hessianKeypointCallback_) hessianKeypointCallback_->onHessianKeypointDetected(blur, g.x, g.y, g.s, g.pixelDistance, g.type, g.response);
-         if (affineShapeCallback_ && g.outcome >= 1)
-            affineShapeCallback_->onAffineShapeFound(blur, g.x, g.y, g.s, g.pixelDistance, g.a11, g.a12, g.a21, g.a22, g.type, g.response, g.iters);
+      replay(r);
+   }
+
+   // == detectPyramidKeypoints(const Mat &image) pyramid.h:73 with a CV_32FC1 image, the reference's own detector input:
+   // image.ptr<float>(0), image.cols, image.rows, image.step.  strideBytes = 0: tightly packed rows.  Every pixel must be finite
+   // with |v| <= 2^20 (include/hesaff_amd.h); otherwise std::runtime_error naming the first offending pixel.
+   void detectPyramidKeypoints(const float *image, int width, int height, size_t strideBytes = 0)
+   {
+      if (strideBytes > (size_t)0x7fffffff) throw std::invalid_argument("row stride too large");
+      const int stride = strideBytes ? (int)strideBytes : width * 4;
+      if (!hessianKeypointCallback_ && !affineShapeCallback_) {
+         hesaff_result r;
+         if (hesaff_detect_batch_f32(ctx_, 1, &image, &width, &height, &stride, &r) != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+         take(r.count_hessian, r.count_desc, r.keys);
+         return;
       }
+      hesaff_region_result r;
+      if (hesaff_detect_regions_f32(ctx_, 1, &image, &width, &height, &stride, &r) != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+      replay(r);
    }
 
    // hesaff.cpp:107-130
@@ -132,6 +141,25 @@ struct AffineHessianDetector {
    }
 
  private:
+   void take(int count_hessian, int count_desc, const hesaff_keypoint *k)
+   {
+      g_numberOfPoints = count_hessian;
+      g_numberOfAffinePoints += count_desc;   // the reference never resets this counter (hesaff.cpp:166)
+      keys.assign(k, k + count_desc);
+   }
+   void replay(const hesaff_region_result &r)
+   {
+      take(r.count_hessian, r.count_desc, r.keys);
+      // hesaff.cpp:66-105 depth-first: each Hessian keypoint, then its affine shape when findAffineShape converged
+      for (int i = 0; i < r.count_hessian; i++) {
+         const hesaff_region &g = r.regions[i];
+         const BlurPlane blur = {g.octave, g.level, g.pixelDistance};
+         if (hessianKeypointCallback_) hessianKeypointCallback_->onHessianKeypointDetected(blur, g.x, g.y, g.s, g.pixelDistance, g.type, g.response);
+         if (affineShapeCallback_ && g.outcome >= 1)
+            affineShapeCallback_->onAffineShapeFound(blur, g.x, g.y, g.s, g.pixelDistance, g.a11, g.a12, g.a21, g.a22, g.type, g.response, g.iters);
+      }
+   }
+
    hesaff_params p_;
    hesaff_ctx *ctx_ = nullptr;
    HessianKeypointCallback *hessianKeypointCallback_ = nullptr;

@@ -23,6 +23,32 @@ __global__ __launch_bounds__(256) void k_gray(const uint8_t *__restrict__ src, i
 }
 
 // ---------------------------------------------------------------------------------------
+// k_check_f32: the value check of hesaff_detect_batch_device_f32, run before any kernel reads the caller's float planes
+// as an image: flags[b] = 1 when image b holds a pixel outside the accepted domain (NaN, +-Inf, |v| > 2^20; the header
+// says why).  Read-only over the planes; the flag is a plain vector store (every writer stores the same 1, the host
+// zeroes the flags first).  Planes as GraySrc with SRC_F32 (row_stride a multiple of 4 bytes).
+// grid (row blocks, 1, B), block 256: a block strides over rows, a thread over four columns at a time.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_check_f32(const uint8_t *__restrict__ src, long long img_stride, int row_stride, int rows, int cols,
+                                                   int32_t *__restrict__ flags)
+{
+   const int b = blockIdx.z;
+   const uint8_t *img = src + (long long)b * img_stride;
+   bool bad = false;
+   for (int r = blockIdx.x; r < rows; r += gridDim.x) {
+      const float *rp = reinterpret_cast<const float *>(img + (long long)r * row_stride);
+      for (int c0 = threadIdx.x; c0 < cols; c0 += 1024) {
+         float v[4];
+#pragma unroll
+         for (int m = 0; m < 4; m++) v[m] = rp[min(c0 + 256 * m, cols - 1)];   // (a clamped column re-reads a pixel of the row: all four loads in flight)
+#pragma unroll
+         for (int m = 0; m < 4; m++) bad |= !(fabsf(v[m]) <= 1048576.0f);   // false for NaN as well
+      }
+   }
+   if (bad) flags[b] = 1;
+}
+
+// ---------------------------------------------------------------------------------------
 // k_blur_hess_tile (LDS tile; the fallback for non-default initialSigma, i.e. tap counts K other
 // than 9, 11, 13, 15, which k_blur_hess_march is instantiated for): separable Gaussian (pinned cv::GaussianBlur order, see
 // DESIGN.md) of one 64x16 tile + 1-pixel halo, then the det-of-Hessian response of the
@@ -618,17 +644,19 @@ __device__ __forceinline__ v2f hs_hessian2(v2f ul, v2f uc, v2f ur, v2f ml, v2f m
 // WRITE_R0: additionally emit the response of the INPUT plane (R0 = hessianResponse(L0),
 // pyramid.cpp:230) from the input rows that pass through LDS anyway; used by the first blur
 // of every octave so that L0 is read from HBM once instead of twice.
-// SRC8: the input rows are taken from the 8-bit source images and converted on the fly (hesaff.cpp:145, k_gray's
-// expression); the float grey plane normalizeAffine samples later is written from the same registers.  Used by the
-// initial blur (pyramid.cpp:276-280): the image is read once as bytes instead of once as bytes and once as floats.
+// SRC: where the input rows come from.  SRC_PLANE: the float plane `in`.  SRC_U8: the 8-bit source images, converted on
+// the fly (hesaff.cpp:145, k_gray's expression).  SRC_F32: the caller's CV_32FC1 planes (pyramid.h:73), taken as they are.
+// With either source the float grey plane normalizeAffine samples later is written from the same registers.  Used by the
+// initial blur (pyramid.cpp:276-280): the image is read once instead of once as the source and once as floats.
+enum { SRC_PLANE = 0, SRC_U8 = 1, SRC_F32 = 2 };
 struct GraySrc {
    const uint8_t *p;
-   int channels;             // 1 or 3 interleaved
+   int channels;             // SRC_U8: 1 or 3 interleaved (SRC_F32: unused)
    long long img_stride;     // bytes between images
-   int row_stride;           // bytes between rows
+   int row_stride;           // bytes between rows (SRC_F32: a multiple of 4)
 };
 
-template <int K, bool WRITE_L, bool WRITE_R, bool WRITE_HALF, bool WRITE_R0 = false, bool SRC8 = false>
+template <int K, bool WRITE_L, bool WRITE_R, bool WRITE_HALF, bool WRITE_R0 = false, int SRC = SRC_PLANE>
 __global__ __launch_bounds__(256) void k_blur_hess_march(DPlane in, DPlane outL, DPlane outR, DPlane outHalf,
                                                           const float *__restrict__ taps, float norm2, int band_rows,
                                                           DPlane outR0 = DPlane(), float norm2_in = 0.0f, GraySrc gs = GraySrc(), DPlane outGray = DPlane())
@@ -679,9 +707,14 @@ __global__ __launch_bounds__(256) void k_blur_hess_march(DPlane in, DPlane outL,
    auto load_row = [&](int t, float *dst5) {
       const int yu = yh0 - 1 - R + t;
       const int y = min(max(yu, 0), rows - 1);
-      if (SRC8) {
+      if (SRC == SRC_U8 || SRC == SRC_F32) {
          const uint8_t *rp = gs.p + (long long)b * gs.img_stride + (long long)y * gs.row_stride;
-         if (gs.channels == 1) {
+         if (SRC == SRC_F32) {
+            // the caller's float rows, per-lane clamped columns like the plane path
+            const float *fp = reinterpret_cast<const float *>(rp);
+#pragma unroll
+            for (int m = 0; m < 5; m++) dst5[m] = fp[cx[m]];
+         } else if (gs.channels == 1) {
             // grey input: cv::imread replicates the byte into B, G, R and (float(c) + c + c) / 3.0f == float(c) exactly
             // (3c <= 765 is exact, and so is its quotient by 3): no arithmetic needed
 #pragma unroll

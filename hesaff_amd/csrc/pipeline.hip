@@ -782,7 +782,7 @@ enum { T_PYR = 0, T_DET = 1, T_AFF = 2, T_PATCH = 3, T_SIFT = 4, T_TOTAL = 5, T_
 
 // Band height of k_blur_hess_march: 16 bands per octave is the measured optimum for 16 x 4K at every octave
 // (sweeps in profiles/r01_notes.md); small batches get proportionally more bands to keep ~1000 blocks in flight.
-template <int K, bool WL, bool WR, bool WH, bool WR0 = false, bool SRC8 = false>
+template <int K, bool WL, bool WR, bool WH, bool WR0 = false, int SRC = SRC_PLANE>
 void launch_march(hesaff_ctx *c, const DPlane &in, const DPlane &outL, const DPlane &outR, const DPlane &outHalf, const float *taps,
                   float norm2, int B, const DPlane &outR0 = DPlane(), float norm2_in = 0.0f, const GraySrc &gs = GraySrc(), const DPlane &outGray = DPlane())
 {
@@ -793,7 +793,7 @@ void launch_march(hesaff_ctx *c, const DPlane &in, const DPlane &outL, const DPl
    const int band = (in.rows + best_nb - 1) / best_nb;
    if (c->debug) fprintf(stderr, "[hesaff] march K=%d %dx%d B=%d bands=%d band=%d blocks=%lld\n", K, in.cols, in.rows, B, best_nb, band, blocks_per_band * best_nb);
    const dim3 grid((strips + 3) / 4, (in.rows + band - 1) / band, B);
-   hipLaunchKernelGGL((k_blur_hess_march<K, WL, WR, WH, WR0, SRC8>), grid, dim3(256), 0, c->stream, in, outL, outR, outHalf, taps, norm2, band, outR0, norm2_in, gs, outGray);
+   hipLaunchKernelGGL((k_blur_hess_march<K, WL, WR, WH, WR0, SRC>), grid, dim3(256), 0, c->stream, in, outL, outR, outHalf, taps, norm2, band, outR0, norm2_in, gs, outGray);
 }
 
 template <bool WL, bool WR, bool WH>
@@ -824,6 +824,23 @@ void launch_blur_hess(hesaff_ctx *c, const DPlane &in, const DPlane &outL, const
    if (WR) hipLaunchKernelGGL(k_hess, grid, dim3(256), 0, c->stream, blurred, outR, norm2);
    if (WH) hipLaunchKernelGGL(k_half, dim3((outHalf.cols + 255) / 256, outHalf.rows, B), dim3(256), 0, c->stream, blurred, outHalf);
 }
+
+// The source images of a batch in device memory: B images img_stride bytes apart, rows row_stride bytes apart, in one of three
+// formats - 8-bit grey, 8-bit with three interleaved channels (hesaff.cpp:138-148 converts both), or float planes, the
+// CV_32FC1 image detectPyramidKeypoints takes (pyramid.h:73; row_stride a multiple of 4).
+enum SrcFormat { HS_SRC_U8C1 = 0, HS_SRC_U8C3 = 1, HS_SRC_F32 = 2 };
+struct SrcImages {
+   const uint8_t *p;
+   int format;
+   long long img_stride;
+   int row_stride;
+   int channels() const { return format == HS_SRC_U8C3 ? 3 : 1; }
+   static SrcImages u8(const void *p, int channels, long long img_stride, int row_stride)
+   {
+      return SrcImages{(const uint8_t *)p, channels == 3 ? HS_SRC_U8C3 : HS_SRC_U8C1, img_stride, row_stride};
+   }
+   static SrcImages f32(const void *p, long long img_stride, int row_stride) { return SrcImages{(const uint8_t *)p, HS_SRC_F32, img_stride, row_stride}; }
+};
 
 struct Lists {
    CandList cl;
@@ -952,9 +969,8 @@ void run_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float *
 }
 
 // The scale-space + detection part for the current plan; fills the ordered Hessian list.
-// src: device u8 images ([B][H][row_stride] with `channels` interleaved channels).
-void run_detection(hesaff_ctx *c, const uint8_t *d_src, int channels, long long src_img_stride, int src_row_stride, int B,
-                   const Lists &s, StageTimer &tm, bool keep_all_planes, float *planes_out)
+// src: the B device images of the batch (SrcImages: 8-bit with 1 or 3 interleaved channels, or float planes).
+void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, StageTimer &tm, bool keep_all_planes, float *planes_out)
 {
    const hesaff::OctaveSchedule &sc = c->sched;
    hipStream_t st = c->stream;
@@ -969,19 +985,34 @@ void run_detection(hesaff_ctx *c, const uint8_t *d_src, int channels, long long 
    int t = tm.begin(T_PYR);
    DPlane none = make_plane(nullptr, 0, 0, 0);
    // Default parameters: grey conversion (hesaff.cpp:138-148) fused into the initial blur 0.5 -> 1.6 (pyramid.cpp:276-280,
-   // K = 11): the 8-bit images are read once, the float grey plane (normalizeAffine's input) and L0 are written.
+   // K = 11): the source images are read once, the float grey plane (normalizeAffine's input) and L0 are written.
+   // 8-bit images: 9 B/px (read 1, write 4 + 4); float planes: 12 B/px (read 4, write 4 + 4).
    const bool fused_gray = !c->oct.empty() && c->pyr_K[0] == 11 && !c->up;
    if (fused_gray) {
       GraySrc gs;
-      gs.p = d_src; gs.channels = channels; gs.img_stride = src_img_stride; gs.row_stride = src_row_stride;
+      gs.p = src.p; gs.channels = src.channels(); gs.img_stride = src.img_stride; gs.row_stride = src.row_stride;
       const int tb = tm.begin(T_BLURHESS, 0);   // not one of the 58 B/px launches (bytes 0)
-      launch_march<11, true, false, false, false, true>(c, c->gray, c->L[0], none, none, ptaps + c->pyr_tap_off[0], 0.0f, B, DPlane(), 0.0f, gs, c->gray);
+      if (src.format == HS_SRC_F32)
+         launch_march<11, true, false, false, false, SRC_F32>(c, c->gray, c->L[0], none, none, ptaps + c->pyr_tap_off[0], 0.0f, B, DPlane(), 0.0f, gs, c->gray);
+      else
+         launch_march<11, true, false, false, false, SRC_U8>(c, c->gray, c->L[0], none, none, ptaps + c->pyr_tap_off[0], 0.0f, B, DPlane(), 0.0f, gs, c->gray);
       tm.end(tb);
    } else {
       // grey conversion; without an initial blur (initialSigma <= the input's own blur) it is the first level directly
       const bool direct = c->pyr_K[0] == 0 && !c->oct.empty();
-      const dim3 grid((c->W + 255) / 256, c->H, B);
-      hipLaunchKernelGGL(k_gray, grid, dim3(256), 0, st, d_src, channels, src_img_stride, src_row_stride, c->gray);
+      if (src.format == HS_SRC_F32) {
+         // float planes are the grey plane already (pyramid.h:73): a pitched copy into c->gray
+         const size_t wb = (size_t)c->W * 4, dpitch = (size_t)c->gray.pitch * 4;
+         if (src.img_stride == (long long)src.row_stride * c->H)
+            HIP_TRY(hipMemcpy2DAsync(c->gray.p, dpitch, src.p, (size_t)src.row_stride, wb, (size_t)c->H * B, hipMemcpyDeviceToDevice, st));
+         else
+            for (int b = 0; b < B; b++)
+               HIP_TRY(hipMemcpy2DAsync(c->gray.img(b), dpitch, src.p + (long long)b * src.img_stride, (size_t)src.row_stride, wb, (size_t)c->H,
+                                        hipMemcpyDeviceToDevice, st));
+      } else {
+         const dim3 grid((c->W + 255) / 256, c->H, B);
+         hipLaunchKernelGGL(k_gray, grid, dim3(256), 0, st, src.p, src.channels(), src.img_stride, src.row_stride, c->gray);
+      }
       if (c->up) {
          // pyramid.cpp:267-271: the first level is the 2x up-sampled image (doubleImage, helpers.cpp:297-329)
          const dim3 g2((c->upimg.cols + 255) / 256, c->upimg.rows, B);
@@ -1167,7 +1198,7 @@ void ensure_group_buffers(hesaff_ctx *c, uint32_t n)
 
 // Whole hot path on a device-resident batch.  Leaves ordered KeyRec records in b_out and
 // per-image start offsets (hessian: b_starts[0..B], desc: b_starts[B+1..2B+1]).
-void run_batch(hesaff_ctx *c, const uint8_t *d_src, int channels, long long src_img_stride, int src_row_stride, int B, int H, int W)
+void run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
 {
    plan(c, B, H, W);
    c->ev_used = 0;
@@ -1176,7 +1207,7 @@ void run_batch(hesaff_ctx *c, const uint8_t *d_src, int channels, long long src_
    hipStream_t st = c->stream;
    uint32_t *cnt = s.counters;
    const int tt = tm.begin(T_TOTAL);
-   run_detection(c, d_src, channels, src_img_stride, src_row_stride, B, s, tm, false, nullptr);
+   run_detection(c, src, B, s, tm, false, nullptr);
 
    int t;
    PlaneTab pt;

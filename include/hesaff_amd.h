@@ -37,6 +37,9 @@ extern "C" {
  * 7: + hesaff_set_pinned_read_budget, hesaff_set_pool_priority, hesaff_stage_threads_for_pool, HESAFF_OUT_STRICT; hesaff_set_resume
  *    takes 0 / 1 / 2; no struct changed;
  * 8: this header (+ hesaff_region, hesaff_region_result, hesaff_detect_regions, hesaff_sizeof_region; no existing struct changed).
+ *    Version 8 also carries the float-input entry points (hesaff_detect_batch_f32, hesaff_detect_batch_cb_f32, hesaff_detect_regions_f32,
+ *    hesaff_detect_batch_device_f32, hesaff_stage_pyramid_f32): they add no struct and change none, so the version stays; a caller that
+ *    needs them finds them by symbol (dlsym) in the library it loaded.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -224,6 +227,45 @@ typedef struct hesaff_region_result {
 int hesaff_detect_regions(hesaff_ctx *ctx, int n, const uint8_t *const *images, const int *widths, const int *heights,
                           const int *strides, const int *channels, hesaff_region_result *results);
 
+/* ---- float grey planes: the reference's own detector input ----
+ * replaces: detectPyramidKeypoints(const Mat &image) with a CV_32FC1 image (pyramid.h:73, pyramid.cpp:261-292) and the callback chain
+ * hesaff.cpp:66-105 - what main() hands the detector after its grey conversion (hesaff.cpp:138-148), and what a caller that uses the
+ * reference as a library passes when it made the plane itself (linearised or gamma-corrected images, 16-bit sources scaled to float,
+ * planes normalised to [0, 1]).  Each _f32 entry point is its 8-bit twin with float planes in place of bytes: the same chunking, mixed
+ * sizes, size limits and lifetime contract; from the grey plane on, the arithmetic is the one the twin runs.
+ *
+ * Input layout: images[i] is H x W float32, one channel, rows strides[i] BYTES apart (at least 4 * width and a multiple of 4; strides
+ * NULL: tightly packed rows); every pointer 4-byte aligned.  Anything else: HESAFF_ERR_ARG.
+ *
+ * Accepted values: every pixel finite with |v| <= 2^20 (1048576) - [0, 1], [0, 255] and [0, 65535] inputs with room to spare.  An image
+ * with a NaN, an infinity or a larger magnitude makes the whole call return HESAFF_ERR_ARG; hesaff_last_error names the caller's image
+ * index and the first offending pixel in raster order (row, column, value).  The context stays usable.  (The reference takes any float;
+ * this bound is a deliberate difference, INTEGRATION.md.)  Where the check runs: the host entry points check each image while the
+ * staging thread copies it into pinned memory (no extra pass over the caller's list); hesaff_detect_batch_device_f32 runs a read-only
+ * check kernel over the planes first.  Either way no refused value reaches a keypoint kernel.
+ * Why 2^20 is enough: no pixel value ever forms an address (every index comes from the image geometry, or from keypoint positions
+ * clamped to the plane), and no intermediate overflows float: a blur is a convex combination (|L| <= 2^20); the Hessian terms of
+ * pyramid.cpp:95-100 stay below 2^22 and the response below 2^45 sigma^4 (2^53 at the default sigmas, sigma <= 4.1); localisation's
+ * second differences stay below 2^56, its edge score below 2^113, and solveLinear3x3 (helpers.cpp:46-90) pivots, so its multipliers
+ * are at most 1; the affine stage's second-moment sums of squared gradients (19 x 19 window) stay below 2^52 and its eigenvalue terms
+ * below 2^105; normalizeAffine interpolates (|v| <= 2^20), and the SIFT stage's mean / variance sums stay below 2^52 before the patch is
+ * normalised.  Every one is far below 2^128.
+ *
+ * hesaff_detect_batch_cb_f32: chunks before a refused image may already have gone to the sink when the call returns HESAFF_ERR_ARG. */
+int hesaff_detect_batch_f32(hesaff_ctx *ctx, int n, const float *const *images, const int *widths, const int *heights, const int *strides,
+                            hesaff_result *results);
+int hesaff_detect_batch_cb_f32(hesaff_ctx *ctx, int n, const float *const *images, const int *widths, const int *heights,
+                               const int *strides, hesaff_chunk_sink sink, void *user);
+/* records and keys as hesaff_detect_regions returns them */
+int hesaff_detect_regions_f32(hesaff_ctx *ctx, int n, const float *const *images, const int *widths, const int *heights,
+                              const int *strides, hesaff_region_result *results);
+/* hesaff_detect_batch_device with float planes already in device memory: plane b starts img_stride bytes after plane b-1, its rows are
+ * row_stride bytes apart (0 = tightly packed: row_stride = 4 * width, img_stride = row_stride * height); n <= max_batch.  A check kernel
+ * reads the planes first and the call returns HESAFF_ERR_ARG (naming the image, 0-based in this call) before any detection kernel runs. */
+int hesaff_detect_batch_device_f32(hesaff_ctx *ctx, int n, const void *d_planes, int width, int height, int row_stride,
+                                   int64_t img_stride, int32_t *count_hessian, int32_t *count_desc, const void **d_keys_out,
+                                   int64_t *total_out);
+
 /* Same path with inputs already resident in device memory (bench / pipelines that decode
  * on the GPU): d_gray = n contiguous height x width 8-bit grey planes (device pointer).
  * Results stay on the device; per-image counts are copied to the two host arrays.
@@ -368,6 +410,9 @@ int hesaff_stage_half_image(hesaff_ctx *ctx, const float *in, int rows, int cols
  * *n_octaves.  Call with planes == NULL to get n_octaves and the float count in *n_floats. */
 int hesaff_stage_pyramid(hesaff_ctx *ctx, const uint8_t *gray, int rows, int cols, float *planes,
                          int *n_octaves, size_t *n_floats);
+/* the same for a float grey plane (tightly packed rows x cols, the accepted values of the _f32 entry points): the pixels of the BlurPlane
+ * a callback receives when the input was float (hesaff.hpp) */
+int hesaff_stage_pyramid_f32(hesaff_ctx *ctx, const float *plane, int rows, int cols, float *planes, int *n_octaves, size_t *n_floats);
 /* detectPyramidKeypoints pyramid.cpp:261-292 up to the onHessianKeypointDetected callback
  * pyramid.h:46: fills f[n][5] = x,y,s,pixelDistance,response and i[n][5] =
  * type,octave,level,r0,c0 in reference order; returns n in *count (cap = array capacity). */

@@ -432,29 +432,25 @@ class HesaffContext:
     # ---- whole path ----
     def detect_batch(self, images):
         """images: list of uint8 arrays HxW (grey) or HxWx3.  -> list of (count_hessian, keys[KEYPOINT_DTYPE])."""
-        n = len(images)
-        imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
-        ptrs = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
-        ws = (C.c_int * n)(*[im.shape[1] for im in imgs])
-        hs = (C.c_int * n)(*[im.shape[0] for im in imgs])
-        chs = (C.c_int * n)(*[1 if im.ndim == 2 else 3 for im in imgs])
-        st = (C.c_int * n)(*[im.shape[1] * (1 if im.ndim == 2 else 3) for im in imgs])
+        imgs, n, ptrs, ws, hs, st, chs = self._u8_list(images)
         res = (_Result * n)()
         self._check(self.L.hesaff_detect_batch(self.h, n, ptrs, ws, hs, st, chs, res))
-        out = []
-        for r in res:
-            if r.count_desc > 0:
-                # one copy out of the library-owned (pinned) result buffer, valid until the next call
-                keys = np.frombuffer((C.c_char * (r.count_desc * 164)).from_address(r.keys), dtype=KEYPOINT_DTYPE).copy()
-            else:
-                keys = np.zeros(0, KEYPOINT_DTYPE)
-            out.append((r.count_hessian, keys))
-        return out
+        # one copy out of the library-owned (pinned) result buffer, valid until the next call
+        return [(r.count_hessian, self._keys_at(r.keys, r.count_desc)) for r in res]
 
     def detect_regions(self, images):
         """hesaff_detect_regions: images as for detect_batch.  -> list of (regions[REGION_DTYPE], keys[KEYPOINT_DTYPE]) per image:
         one record per Hessian keypoint in the reference's callback order (pyramid.h:43-47, affine.h:48-58), and the same keys as
         detect_batch.  regions[i]["key"] is the row of keys that keypoint became (-1 when it got no descriptor)."""
+        imgs, n, ptrs, ws, hs, st, chs = self._u8_list(images)
+        res = (_RegionResult * n)()
+        self._check(self.L.hesaff_detect_regions(self.h, n, ptrs, ws, hs, st, chs, res))
+        # copies out of the library-owned (pinned) result buffer, valid until the next call
+        return [(self._regions_at(r.regions, r.count_hessian), self._keys_at(r.keys, r.count_desc)) for r in res]
+
+    @staticmethod
+    def _u8_list(images):
+        """arrays HxW (grey) or HxWx3, cast to uint8 -> (arrays, n, ptrs, widths, heights, strides, channels)"""
         n = len(images)
         imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
         ptrs = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
@@ -462,21 +458,7 @@ class HesaffContext:
         hs = (C.c_int * n)(*[im.shape[0] for im in imgs])
         chs = (C.c_int * n)(*[1 if im.ndim == 2 else 3 for im in imgs])
         st = (C.c_int * n)(*[im.shape[1] * (1 if im.ndim == 2 else 3) for im in imgs])
-        res = (_RegionResult * n)()
-        self._check(self.L.hesaff_detect_regions(self.h, n, ptrs, ws, hs, st, chs, res))
-        out = []
-        for r in res:
-            # copies out of the library-owned (pinned) result buffer, valid until the next call
-            if r.count_hessian > 0:
-                regions = np.frombuffer((C.c_char * (r.count_hessian * REGION_DTYPE.itemsize)).from_address(r.regions), dtype=REGION_DTYPE).copy()
-            else:
-                regions = np.zeros(0, REGION_DTYPE)
-            if r.count_desc > 0:
-                keys = np.frombuffer((C.c_char * (r.count_desc * KEYPOINT_DTYPE.itemsize)).from_address(r.keys), dtype=KEYPOINT_DTYPE).copy()
-            else:
-                keys = np.zeros(0, KEYPOINT_DTYPE)
-            out.append((regions, keys))
-        return out
+        return imgs, n, ptrs, ws, hs, st, chs
 
     # ---- float grey planes (CV_32FC1, pyramid.h:73) ----
     @staticmethod
@@ -510,24 +492,13 @@ class HesaffContext:
         imgs, ptrs, ws, hs, st = self._f32_list(images)
         res = (_RegionResult * len(imgs))()
         self._check(self.L.hesaff_detect_regions_f32(self.h, len(imgs), ptrs, ws, hs, st, res))
-        out = []
-        for r in res:
-            if r.count_hessian > 0:
-                regions = np.frombuffer((C.c_char * (r.count_hessian * REGION_DTYPE.itemsize)).from_address(r.regions), dtype=REGION_DTYPE).copy()
-            else:
-                regions = np.zeros(0, REGION_DTYPE)
-            out.append((regions, self._keys_at(r.keys, r.count_desc)))
-        return out
+        return [(self._regions_at(r.regions, r.count_hessian), self._keys_at(r.keys, r.count_desc)) for r in res]
 
     def detect_batch_cb_f32(self, images, sink):
         """hesaff_detect_batch_cb_f32: detect_batch_cb for 2-D float32 grey planes."""
         imgs, ptrs, ws, hs, st = self._f32_list(images)
 
-        def _sink(_user, m, idx, res):
-            out = [(res[i].count_hessian, self._keys_at(res[i].keys, res[i].count_desc)) for i in range(m)]
-            return 1 if sink([idx[i] for i in range(m)], out) else 0
-        cb = CHUNK_SINK(_sink)
-        self._check(self.L.hesaff_detect_batch_cb_f32(self.h, len(imgs), ptrs, ws, hs, st, cb, None))
+        self._check(self.L.hesaff_detect_batch_cb_f32(self.h, len(imgs), ptrs, ws, hs, st, self._chunk_sink(sink), None))
 
     def detect_batch_device_f32(self, t):
         """hesaff_detect_batch_device_f32 on a torch tensor on this context's device: float32, [n, H, W] or [H, W], unit stride
@@ -565,36 +536,34 @@ class HesaffContext:
         if not isinstance(img, np.ndarray) or img.dtype != np.float32 or img.ndim != 2:
             raise TypeError("pyramid_f32 takes a 2-D float32 array")
         g = np.ascontiguousarray(img)
-        no = C.c_int(); nf = C.c_size_t()
-        self._check(self.L.hesaff_stage_pyramid_f32(self.h, None, g.shape[0], g.shape[1], None, C.byref(no), C.byref(nf)))
-        buf = np.empty(max(nf.value, 1), np.float32)
-        self._check(self.L.hesaff_stage_pyramid_f32(self.h, g.ctypes.data, g.shape[0], g.shape[1], buf.ctypes.data, C.byref(no), C.byref(nf)))
-        out = []; off = 0; r, c = g.shape
-        for _ in range(no.value):
-            n = r * c
-            Ls = buf[off:off + 5 * n].reshape(5, r, c); off += 5 * n
-            Rs = buf[off:off + 5 * n].reshape(5, r, c); off += 5 * n
-            out.append((Ls, Rs))
-            r //= 2; c //= 2
-        return out
+        return self._pyramid(self.L.hesaff_stage_pyramid_f32, g)
 
     @staticmethod
-    def _keys_at(addr, count):
+    def _records_at(addr, count, dtype):
         """a copy of `count` records at a library-owned address"""
         if count <= 0:
-            return np.zeros(0, KEYPOINT_DTYPE)
-        return np.frombuffer((C.c_char * (count * KEYPOINT_DTYPE.itemsize)).from_address(addr), dtype=KEYPOINT_DTYPE).copy()
+            return np.zeros(0, dtype)
+        return np.frombuffer((C.c_char * (count * dtype.itemsize)).from_address(addr), dtype=dtype).copy()
+
+    @classmethod
+    def _keys_at(cls, addr, count):
+        return cls._records_at(addr, count, KEYPOINT_DTYPE)
+
+    @classmethod
+    def _regions_at(cls, addr, count):
+        return cls._records_at(addr, count, REGION_DTYPE)
+
+    def _chunk_sink(self, sink):
+        """the hesaff_chunk_sink that hands a chunk's image indices and copies of its records to sink(indices, [(count_hessian, keys), ...])"""
+        def _sink(_user, m, idx, res):
+            out = [(res[i].count_hessian, self._keys_at(res[i].keys, res[i].count_desc)) for i in range(m)]
+            return 1 if sink([idx[i] for i in range(m)], out) else 0
+        return CHUNK_SINK(_sink)
 
     def detect_batch_raw(self, images):
         """hesaff_detect_batch without copying the records out: -> ctypes array of hesaff_result whose `keys` point into
         library-owned pinned memory (valid until the next call on this context)."""
-        n = len(images)
-        imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
-        ptrs = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
-        ws = (C.c_int * n)(*[im.shape[1] for im in imgs])
-        hs = (C.c_int * n)(*[im.shape[0] for im in imgs])
-        chs = (C.c_int * n)(*[1 if im.ndim == 2 else 3 for im in imgs])
-        st = (C.c_int * n)(*[im.shape[1] * (1 if im.ndim == 2 else 3) for im in imgs])
+        imgs, n, ptrs, ws, hs, st, chs = self._u8_list(images)
         res = (_Result * n)()
         self._check(self.L.hesaff_detect_batch(self.h, n, ptrs, ws, hs, st, chs, res))
         return res
@@ -602,27 +571,8 @@ class HesaffContext:
     def detect_batch_cb(self, images, sink):
         """hesaff_detect_batch_cb: sink(image_indices, [(count_hessian, keys copy), ...]) is called once per chunk with
         records that are valid only during the call (bounded pinned memory); a truthy return value stops the run."""
-        n = len(images)
-        imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
-        ptrs = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
-        ws = (C.c_int * n)(*[im.shape[1] for im in imgs])
-        hs = (C.c_int * n)(*[im.shape[0] for im in imgs])
-        chs = (C.c_int * n)(*[1 if im.ndim == 2 else 3 for im in imgs])
-        st = (C.c_int * n)(*[im.shape[1] * (1 if im.ndim == 2 else 3) for im in imgs])
-
-        def _sink(_user, m, idx, res):
-            out = []
-            for i in range(m):
-                r = res[i]
-                if r.count_desc > 0:
-                    buf = (C.c_char * (r.count_desc * KEYPOINT_DTYPE.itemsize)).from_address(r.keys)
-                    keys = np.frombuffer(buf, dtype=KEYPOINT_DTYPE).copy()
-                else:
-                    keys = np.zeros(0, KEYPOINT_DTYPE)
-                out.append((r.count_hessian, keys))
-            return 1 if sink([idx[i] for i in range(m)], out) else 0
-        cb = CHUNK_SINK(_sink)
-        self._check(self.L.hesaff_detect_batch_cb(self.h, n, ptrs, ws, hs, st, chs, cb, None))
+        imgs, n, ptrs, ws, hs, st, chs = self._u8_list(images)
+        self._check(self.L.hesaff_detect_batch_cb(self.h, n, ptrs, ws, hs, st, chs, self._chunk_sink(sink), None))
 
     def set_output_format(self, fmt):
         """1 = text (.hesaff.sift, default), 2 = binary sidecar (.hesaff.bin), 3 = both."""
@@ -693,13 +643,12 @@ class HesaffContext:
         self._check(self.L.hesaff_stage_half_image(self.h, img, img.shape[0], img.shape[1], out))
         return out
 
-    def pyramid(self, gray_u8):
-        """-> list over octaves of (L[5,rows,cols], R[5,rows,cols])."""
-        g = np.ascontiguousarray(gray_u8, np.uint8)
+    def _pyramid(self, entry, g):
+        """hesaff_stage_pyramid or its float twin on the contiguous image g: sizes first, then the planes, cut into octaves"""
         no = C.c_int(); nf = C.c_size_t()
-        self._check(self.L.hesaff_stage_pyramid(self.h, None, g.shape[0], g.shape[1], None, C.byref(no), C.byref(nf)))
+        self._check(entry(self.h, None, g.shape[0], g.shape[1], None, C.byref(no), C.byref(nf)))
         buf = np.empty(max(nf.value, 1), np.float32)
-        self._check(self.L.hesaff_stage_pyramid(self.h, g.ctypes.data, g.shape[0], g.shape[1], buf.ctypes.data, C.byref(no), C.byref(nf)))
+        self._check(entry(self.h, g.ctypes.data, g.shape[0], g.shape[1], buf.ctypes.data, C.byref(no), C.byref(nf)))
         out = []; off = 0; r, c = g.shape
         for _ in range(no.value):
             n = r * c
@@ -708,6 +657,11 @@ class HesaffContext:
             out.append((Ls, Rs))
             r //= 2; c //= 2
         return out
+
+    def pyramid(self, gray_u8):
+        """-> list over octaves of (L[5,rows,cols], R[5,rows,cols])."""
+        g = np.ascontiguousarray(gray_u8, np.uint8)
+        return self._pyramid(self.L.hesaff_stage_pyramid, g)
 
     def hessian_keypoints(self, gray_u8, cap=None):
         """-> f[n,5] = x,y,s,pd,response ; i[n,5] = type,octave,level,r0,c0 (reference order)."""

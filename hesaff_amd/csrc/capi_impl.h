@@ -21,6 +21,13 @@ int fail(hesaff_ctx *c, const HsError &e)
 
 void bind_device(hesaff_ctx *c) { HIP_TRY(hipSetDevice(c->device)); }
 
+// the end of a stage entry point: everything it enqueued on the main stream has run, and without an error
+void finish_stream(hesaff_ctx *c)
+{
+   HIP_TRY(hipStreamSynchronize(c->stream));
+   HIP_TRY(hipGetLastError());
+}
+
 bool finite_f(float v) { return v == v && v - v == 0.0f; }
 
 void validate_params(const hesaff_params &p)
@@ -35,6 +42,31 @@ void validate_params(const hesaff_params &p)
    if (p.fast == 1)
       throw HsError(HESAFF_ERR_ARG, "hesaff_params.fast = 1 was withdrawn in ABI version 4 (it bought 1.02x); use 0 (parity mode) or 2");
    if (p.fast != 0 && p.fast != 2) throw HsError(HESAFF_ERR_ARG, "fast must be 0 (parity mode) or 2");
+}
+
+// What the two device-resident entry points share: the device and the batch size first, then (detect_device) the plan for a full
+// batch, the batch itself and the counts read back.  check_source runs between plan and batch: the float planes' value check fires
+// after the plan's own refusals.
+void begin_device_batch(hesaff_ctx *c, int n)
+{
+   bind_device(c);
+   if (n > c->par.max_batch) throw HsError(HESAFF_ERR_ARG, "n exceeds hesaff_params.max_batch for the device-resident entry point");
+}
+
+template <class CHECK>
+void detect_device(hesaff_ctx *c, int n, const SrcImages &src, int height, int width, int32_t *count_hessian, int32_t *count_desc,
+                   const void **d_keys_out, int64_t *total_out, CHECK check_source)
+{
+   plan(c, c->par.max_batch, height, width);
+   check_source();
+   run_batch(c, src, n, height, width);
+   const int32_t *hs = c->h_starts, *ds = c->h_starts + (n + 1);
+   for (int b = 0; b < n; b++) {
+      if (count_hessian) count_hessian[b] = hs[b + 1] - hs[b];
+      if (count_desc) count_desc[b] = ds[b + 1] - ds[b];
+   }
+   if (d_keys_out) *d_keys_out = c->geo.b_out.p;
+   if (total_out) *total_out = ds[n];
 }
 
 } // namespace
@@ -137,14 +169,14 @@ int hesaff_create(hesaff_ctx **out, const hesaff_params *p, int device)
          }
          for (int g = 0; g < 4; g++) c->sset.comp[g] = made[g];
       }
-      for (int i = 0; i < HS_NSIDE; i++) HIP_TRY(hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+      for (int i = 0; i < HS_NSIDE; i++) c->ev_join[i] = DevEvent(hipEventDisableTiming);
+      c->ev_fork = DevEvent(hipEventDisableTiming);
       // (the four compute streams stay on the default priority: every other assignment measured 1.5-6 % slower, profiles/r04_notes.md)
-      HIP_TRY(hipEventCreateWithFlags(&c->ev_detect_done, hipEventDisableTiming | hipEventBlockingSync));
-      HIP_TRY(hipEventCreateWithFlags(&c->ev_batch_done, hipEventDisableTiming | hipEventBlockingSync));
+      c->ev_detect_done = DevEvent(hipEventDisableTiming | hipEventBlockingSync);
+      c->ev_batch_done = DevEvent(hipEventDisableTiming | hipEventBlockingSync);
       for (int i = 0; i < HS_NSLOT; i++) {
-         HIP_TRY(hipEventCreateWithFlags(&c->ev_extract_done[i], hipEventDisableTiming));
-         HIP_TRY(hipEventCreateWithFlags(&c->ev_sift_done[i], hipEventDisableTiming));
+         c->ev_extract_done[i] = DevEvent(hipEventDisableTiming);
+         c->ev_sift_done[i] = DevEvent(hipEventDisableTiming);
       }
       set_kernel_attrs(c);
       build_tables(c);
@@ -169,58 +201,17 @@ int hesaff_create(hesaff_ctx **out, const hesaff_params *p, int device)
 void hesaff_destroy(hesaff_ctx *c)
 {
    if (!c) return;
-   (void)hipSetDevice(c->device);
-   if (c->stream) { (void)hipStreamSynchronize(c->stream); }
-   DevBuf *bufs[] = {&c->t_smm, &c->t_sift, &c->t_bin0, &c->t_bin1, &c->t_w0, &c->t_w1, &c->t_pyr_taps, &c->t_patch_taps,
-                     &c->t_patch_off, &c->t_patch_k, &c->b_gray, &c->b_up, &c->b_L, &c->b_L3, &c->b_R, &c->b_map, &c->b_bitmask, &c->b_prefix,
-                     &c->b_blocksums, &c->b_generic, &c->b_counters, &c->b_cand, &c->b_rec_f, &c->b_rec_i, &c->b_rec_w, &c->b_hess_f, &c->b_hess_i,
-                     &c->b_aff, &c->b_pw, &c->b_bins, &c->b_rank, &c->b_desc, &c->b_out, &c->b_starts, &c->b_patches,
-                     &c->b_stage, &c->b_input, &c->t_mask_idx, &c->t_sgrad_nb, &c->t_sgrad_om, &c->t_vo_rows, &c->t_vo_src, &c->b_rowprefix, &c->b_trows, &c->b_trows2, &c->b_trows3,
-                     &c->b_ex_len, &c->b_ex_sums, &c->b_ex_off, &c->b_ex_imgoff, &c->b_ex_starts, &c->b_jcoef[0], &c->b_jcoef[1], &c->b_jplane};
-   for (DevBuf *b : bufs) b->release();
-   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-   {
-      // the logical streams are aliases of the context's four HIP streams (hesaff_create), which go back to the device's idle sets
-      // below: each is left idle once; c->stream is synchronised above
-      hipStream_t all[6] = {c->side_streams[0], c->side_streams[1], c->side_streams[2], c->side_streams[3], c->sift_stream, c->aff_stream};
-      for (int i = 0; i < 6; i++) {
-         bool seen = all[i] == nullptr || all[i] == c->stream;
-         for (int j = 0; j < i; j++) seen = seen || all[j] == all[i];
-         if (!seen) (void)hipStreamSynchronize(all[i]);
-      }
-      for (int i = 0; i < HS_NSIDE; i++) if (c->ev_join[i]) (void)hipEventDestroy(c->ev_join[i]);
-   }
-   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-   if (c->ev_detect_done) (void)hipEventDestroy(c->ev_detect_done);
-   if (c->ev_batch_done) (void)hipEventDestroy(c->ev_batch_done);
-   for (hipEvent_t e : c->ev_aff) (void)hipEventDestroy(e);
-   for (int i = 0; i < HS_NSLOT; i++) {
-      if (c->ev_extract_done[i]) (void)hipEventDestroy(c->ev_extract_done[i]);
-      if (c->ev_sift_done[i]) (void)hipEventDestroy(c->ev_sift_done[i]);
-      c->b_patches2[i].release();
-   }
-   c->b_siftvec2.release(); c->b_meanvar2.release(); c->b_siftvo2.release();
-   if (c->h2d_stream) (void)hipStreamSynchronize(c->h2d_stream);   // (pin_in is the copy-in stream's source)
-   for (int i = 0; i < 2; i++) {
-      c->b_in2[i].release(); c->b_outstage[i].release(); c->pin_in[i].release();
-      if (c->ev_h2d[i]) (void)hipEventDestroy(c->ev_h2d[i]);
-      if (c->ev_h2d_blk[i]) (void)hipEventDestroy(c->ev_h2d_blk[i]);
-      if (c->ev_in_free[i]) (void)hipEventDestroy(c->ev_in_free[i]);
-      if (c->ev_out_ready[i]) (void)hipEventDestroy(c->ev_out_ready[i]);
-      if (c->ev_d2h[i]) (void)hipEventDestroy(c->ev_d2h[i]);
-      for (int q = 0; q < 4; q++) if (c->ev_exp[i][q]) (void)hipEventDestroy(c->ev_exp[i][q]);
-   }
-   // the copy streams are idle before any page-locked block they may still read or write goes back
-   if (c->h2d_stream) (void)hipStreamSynchronize(c->h2d_stream);
-   if (c->d2h_stream) (void)hipStreamSynchronize(c->d2h_stream);
-   for (auto &pb : c->pin_out) pb.release();
-   c->pin_read.release();
-   c->h_small_end.release(); c->h_small_mid.release(); c->h_small_exp.release();
-   if (c->sset.comp[0]) {   // (a context whose creation failed before its streams were complete has no set)
-      c->sset.h2d = c->h2d_stream; c->sset.d2h = c->d2h_stream;
-      give_stream_set(c->device, c->sset);   // idle now; the next context of this device runs on them
-   }
+   const int device = c->device;
+   (void)hipSetDevice(device);
+   // Every HIP stream of the context (its logical streams are aliases of the set's four, hesaff_create) is idle before anything goes
+   // back: no kernel still uses a buffer, no copy engine a page-locked block.  The members then free themselves; the streams outlive
+   // the context and serve the next one on this device.
+   StreamSet set = c->sset;
+   set.h2d = c->h2d_stream; set.d2h = c->d2h_stream;
+   for (hipStream_t st : {c->stream, set.comp[0], set.comp[1], set.comp[2], set.comp[3], set.h2d, set.d2h})
+      if (st) (void)hipStreamSynchronize(st);
    delete c;
+   if (set.comp[0]) give_stream_set(device, set);   // (a context whose creation failed before its streams were complete has no set)
 }
 
 const char *hesaff_last_error(const hesaff_ctx *c) { return c ? c->err.c_str() : g_create_error.c_str(); }
@@ -244,17 +235,8 @@ int hesaff_detect_batch_device(hesaff_ctx *c, int n, const void *d_gray, int wid
 {
    if (!c || n < 1 || !d_gray) return HESAFF_ERR_ARG;
    HS_API_BEGIN
-   bind_device(c);
-   if (n > c->par.max_batch) throw HsError(HESAFF_ERR_ARG, "n exceeds hesaff_params.max_batch for the device-resident entry point");
-   plan(c, c->par.max_batch, height, width);
-   run_batch(c, SrcImages::u8(d_gray, 1, (long long)width * height, width), n, height, width);
-   const int32_t *hs = c->h_starts.data(), *ds = c->h_starts.data() + (n + 1);
-   for (int b = 0; b < n; b++) {
-      if (count_hessian) count_hessian[b] = hs[b + 1] - hs[b];
-      if (count_desc) count_desc[b] = ds[b + 1] - ds[b];
-   }
-   if (d_keys_out) *d_keys_out = c->b_out.p;
-   if (total_out) *total_out = ds[n];
+   begin_device_batch(c, n);
+   detect_device(c, n, SrcImages::u8(d_gray, 1, (long long)width * height, width), height, width, count_hessian, count_desc, d_keys_out, total_out, [] {});
    HS_API_END(c)
 }
 
@@ -303,12 +285,12 @@ void ensure_copy_streams(hesaff_ctx *c)
       HIP_TRY(hipStreamCreateWithPriority(&c->d2h_stream, hipStreamNonBlocking, prio_greatest));
    }
    for (int i = 0; i < 2; i++) {
-      HIP_TRY(hipEventCreateWithFlags(&c->ev_h2d[i], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&c->ev_h2d_blk[i], hipEventDisableTiming | hipEventBlockingSync));
-      HIP_TRY(hipEventCreateWithFlags(&c->ev_in_free[i], hipEventDisableTiming | hipEventBlockingSync));
-      HIP_TRY(hipEventCreateWithFlags(&c->ev_out_ready[i], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&c->ev_d2h[i], hipEventDisableTiming | hipEventBlockingSync));
-      for (int q = 0; q < 4; q++) HIP_TRY(hipEventCreate(&c->ev_exp[i][q]));
+      c->ev_h2d[i] = DevEvent(hipEventDisableTiming);
+      c->ev_h2d_blk[i] = DevEvent(hipEventDisableTiming | hipEventBlockingSync);
+      c->ev_in_free[i] = DevEvent(hipEventDisableTiming | hipEventBlockingSync);
+      c->ev_out_ready[i] = DevEvent(hipEventDisableTiming);
+      c->ev_d2h[i] = DevEvent(hipEventDisableTiming | hipEventBlockingSync);
+      for (int q = 0; q < 4; q++) c->ev_exp[i][q] = DevEvent(hipEventDefault);
    }
 }
 
@@ -458,7 +440,7 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
          HIP_TRY(hipEventRecord(c->ev_in_free[slot], c->stream));
          const auto dbg_t2 = std::chrono::steady_clock::now();
          const double dbg_c2 = c->debug ? thread_cpu_ms() : 0.0;
-         const int32_t *hs = c->h_starts.data(), *ds = c->h_starts.data() + (B + 1);
+         const int32_t *hs = c->h_starts, *ds = c->h_starts + (B + 1);
          cur->total = ds[B];
          cur->nh.resize((size_t)B); cur->nd.resize((size_t)B); cur->off.resize((size_t)B);
          for (int b = 0; b < B; b++) {
@@ -468,7 +450,7 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
          }
          // layout of the chunk's result block: [records][regions][text rows][sidecar rows], what the consumer wants of them
          const size_t n_rows = (size_t)cur->total, n_hess = (size_t)hs[B];
-         const KeyRec *d_keys = c->b_out.as<KeyRec>();
+         const KeyRec *d_keys = c->geo.b_out.as<KeyRec>();
          size_t at = 0;
          auto place = [&at](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~(size_t)255; return o; };
          const size_t keys_at = (wants & WANT_KEYS) ? place(n_rows * sizeof(hesaff_keypoint)) : 0;
@@ -477,7 +459,7 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
          const bool time_export = c->profiling && (wants & (WANT_TEXT | WANT_BIN)) && n_rows > 0;
          if (time_export) HIP_TRY(hipEventRecord(c->ev_exp[slot][0], c->stream));
          if (wants & WANT_TEXT) {   // row lengths and offsets first: the host needs the byte count (a short wait on the main stream)
-            text_bytes = export_text_prepare(c, d_keys, (uint32_t)n_rows, c->b_starts.as<int32_t>() + (B + 1), B, cur->toff);
+            text_bytes = export_text_prepare(c, d_keys, (uint32_t)n_rows, c->geo.b_starts.as<int32_t>() + (B + 1), B, cur->toff);
             cur->text_at = place((size_t)text_bytes);
          }
          if (wants & WANT_BIN) cur->bin_at = place(n_rows * EX_BIN_ROW);
@@ -502,7 +484,7 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
             const int follow = std::max(cur->largest, B);   // images of the largest chunk that is known to follow (ChunkIO::largest_chunk)
             const size_t full = (bytes * (size_t)follow + (size_t)B - 1) / (size_t)B;
             if (presize[(size_t)cur->block].valid()) presize[(size_t)cur->block].get();
-            hesaff_ctx::Pinned &pb = c->pin_out[(size_t)cur->block];
+            PinBuf &pb = c->pin_out[(size_t)cur->block];
             if (bytes > pb.bytes) pb.ensure_grow(std::max<size_t>(full, 16));
             if (!presized && follow > B) {   // a list that starts small is a long one: its other blocks will be needed
                presized = true;
@@ -522,7 +504,7 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
             if (bytes > c->b_outstage[slot].bytes) c->b_outstage[slot].ensure(bytes + bytes / 4);
             char *stg = (char *)c->b_outstage[slot].p;
             if ((wants & WANT_KEYS) && n_rows > 0)
-               HIP_TRY(hipMemcpyAsync(stg + keys_at, c->b_out.p, n_rows * sizeof(hesaff_keypoint), hipMemcpyDeviceToDevice, c->stream));
+               HIP_TRY(hipMemcpyAsync(stg + keys_at, c->geo.b_out.p, n_rows * sizeof(hesaff_keypoint), hipMemcpyDeviceToDevice, c->stream));
             if (wants & WANT_REGIONS) pack_regions(c, (uint32_t)n_hess, B, (hesaff_region *)(stg + cur->regions_at));
             if (time_export) HIP_TRY(hipEventRecord(c->ev_exp[slot][2], c->stream));
             if (wants & WANT_TEXT) export_text_write(c, d_keys, (uint32_t)n_rows, stg + cur->text_at);
@@ -591,14 +573,29 @@ void check_device_f32(hesaff_ctx *c, int n, const uint8_t *d, long long img_stri
    hipLaunchKernelGGL(k_check_f32, dim3(gx, 1, n), dim3(256), 0, c->stream, d, img_stride, row_stride, H, W, flags);
    std::vector<int32_t> h((size_t)n);
    HIP_TRY(hipMemcpyAsync(h.data(), flags, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-   HIP_TRY(hipStreamSynchronize(c->stream));
-   HIP_TRY(hipGetLastError());
+   finish_stream(c);
    for (int b = 0; b < n; b++) {
       if (!h[(size_t)b]) continue;
       std::vector<uint8_t> img((size_t)H * W * 4);
       HIP_TRY(hipMemcpy2D(img.data(), (size_t)W * 4, d + (long long)b * img_stride, (size_t)row_stride, (size_t)W * 4, (size_t)H, hipMemcpyDeviceToHost));
       throw_bad_f32(b, img.data(), H, W, (size_t)W * 4);
    }
+}
+
+// The body of the six host-image entry points: the list is validated, cut into chunks (ArrayIO), given its consumer - set_consumer
+// fills in `results`, `region_results` or `sink` + `user` - and run through the chunk engine with `ring` result blocks.
+// images: n pointers to 8-bit images (const uint8_t *const *, with `channels`) or, f32, to float planes (const float *const *).
+template <class CONSUMER>
+void detect_images(hesaff_ctx *c, int n, const void *images, bool f32, const int *widths, const int *heights, const int *strides, const int *channels,
+                   int ring, CONSUMER set_consumer)
+{
+   std::vector<const uint8_t *> planes;
+   if (f32) planes = validate_f32_list(n, (const float *const *)images, widths, heights, strides);
+   else validate_image_list(n, (const uint8_t *const *)images, widths, heights, strides, channels);
+   ArrayIO io(&c->ring, c->par.max_batch, n, f32 ? planes.data() : (const uint8_t *const *)images, widths, heights, strides, channels, f32);
+   set_consumer(io);
+   run_chunks(c, io, ring);
+   if (io.sink_rc.load() != 0) throw HsError(HESAFF_ERR_IO, "the result sink reported an error");
 }
 
 } // namespace
@@ -610,10 +607,7 @@ int hesaff_detect_batch(hesaff_ctx *c, int n, const uint8_t *const *images, cons
 {
    if (!c || n < 0 || (n > 0 && (!images || !widths || !heights || !results))) return HESAFF_ERR_ARG;
    HS_API_BEGIN
-   validate_image_list(n, images, widths, heights, strides, channels);
-   ArrayIO io(&c->ring, c->par.max_batch, n, images, widths, heights, strides, channels);
-   io.results = results;
-   run_chunks(c, io, 0);
+   detect_images(c, n, images, false, widths, heights, strides, channels, 0, [&](ArrayIO &io) { io.results = results; });
    HS_API_END(c)
 }
 
@@ -622,11 +616,7 @@ int hesaff_detect_batch_cb(hesaff_ctx *c, int n, const uint8_t *const *images, c
 {
    if (!c || n < 0 || !sink || (n > 0 && (!images || !widths || !heights))) return HESAFF_ERR_ARG;
    HS_API_BEGIN
-   validate_image_list(n, images, widths, heights, strides, channels);
-   ArrayIO io(&c->ring, c->par.max_batch, n, images, widths, heights, strides, channels);
-   io.sink = sink; io.user = user;
-   run_chunks(c, io, 3);
-   if (io.sink_rc.load() != 0) throw HsError(HESAFF_ERR_IO, "the result sink reported an error");
+   detect_images(c, n, images, false, widths, heights, strides, channels, 3, [&](ArrayIO &io) { io.sink = sink; io.user = user; });
    HS_API_END(c)
 }
 
@@ -637,10 +627,7 @@ int hesaff_detect_regions(hesaff_ctx *c, int n, const uint8_t *const *images, co
 {
    if (!c || n < 0 || (n > 0 && (!images || !widths || !heights || !results))) return HESAFF_ERR_ARG;
    HS_API_BEGIN
-   validate_image_list(n, images, widths, heights, strides, channels);
-   ArrayIO io(&c->ring, c->par.max_batch, n, images, widths, heights, strides, channels);
-   io.region_results = results;
-   run_chunks(c, io, 0);
+   detect_images(c, n, images, false, widths, heights, strides, channels, 0, [&](ArrayIO &io) { io.region_results = results; });
    HS_API_END(c)
 }
 
@@ -650,10 +637,7 @@ int hesaff_detect_batch_f32(hesaff_ctx *c, int n, const float *const *images, co
 {
    if (!c || n < 0 || (n > 0 && (!images || !widths || !heights || !results))) return HESAFF_ERR_ARG;
    HS_API_BEGIN
-   const std::vector<const uint8_t *> bytes = validate_f32_list(n, images, widths, heights, strides);
-   ArrayIO io(&c->ring, c->par.max_batch, n, bytes.data(), widths, heights, strides, nullptr, true);
-   io.results = results;
-   run_chunks(c, io, 0);
+   detect_images(c, n, images, true, widths, heights, strides, nullptr, 0, [&](ArrayIO &io) { io.results = results; });
    HS_API_END(c)
 }
 
@@ -662,11 +646,7 @@ int hesaff_detect_batch_cb_f32(hesaff_ctx *c, int n, const float *const *images,
 {
    if (!c || n < 0 || !sink || (n > 0 && (!images || !widths || !heights))) return HESAFF_ERR_ARG;
    HS_API_BEGIN
-   const std::vector<const uint8_t *> bytes = validate_f32_list(n, images, widths, heights, strides);
-   ArrayIO io(&c->ring, c->par.max_batch, n, bytes.data(), widths, heights, strides, nullptr, true);
-   io.sink = sink; io.user = user;
-   run_chunks(c, io, 3);
-   if (io.sink_rc.load() != 0) throw HsError(HESAFF_ERR_IO, "the result sink reported an error");
+   detect_images(c, n, images, true, widths, heights, strides, nullptr, 3, [&](ArrayIO &io) { io.sink = sink; io.user = user; });
    HS_API_END(c)
 }
 
@@ -675,10 +655,7 @@ int hesaff_detect_regions_f32(hesaff_ctx *c, int n, const float *const *images, 
 {
    if (!c || n < 0 || (n > 0 && (!images || !widths || !heights || !results))) return HESAFF_ERR_ARG;
    HS_API_BEGIN
-   const std::vector<const uint8_t *> bytes = validate_f32_list(n, images, widths, heights, strides);
-   ArrayIO io(&c->ring, c->par.max_batch, n, bytes.data(), widths, heights, strides, nullptr, true);
-   io.region_results = results;
-   run_chunks(c, io, 0);
+   detect_images(c, n, images, true, widths, heights, strides, nullptr, 0, [&](ArrayIO &io) { io.region_results = results; });
    HS_API_END(c)
 }
 
@@ -687,8 +664,7 @@ int hesaff_detect_batch_device_f32(hesaff_ctx *c, int n, const void *d_planes, i
 {
    if (!c || n < 1 || !d_planes || width < 1 || height < 1 || row_stride < 0 || img_stride < 0) return HESAFF_ERR_ARG;
    HS_API_BEGIN
-   bind_device(c);
-   if (n > c->par.max_batch) throw HsError(HESAFF_ERR_ARG, "n exceeds hesaff_params.max_batch for the device-resident entry point");
+   begin_device_batch(c, n);
    const long long rs = row_stride ? row_stride : 4LL * width;
    const long long is = img_stride ? (long long)img_stride : rs * height;
    if ((uintptr_t)d_planes % 4 != 0) throw HsError(HESAFF_ERR_ARG, "float planes not 4-byte aligned");
@@ -696,16 +672,8 @@ int hesaff_detect_batch_device_f32(hesaff_ctx *c, int n, const void *d_planes, i
       throw HsError(HESAFF_ERR_ARG, "row stride of a float plane must be at least 4 * width bytes and a multiple of 4");
    if (is % 4 != 0 || (n > 1 && is < rs * (height - 1) + 4LL * width))
       throw HsError(HESAFF_ERR_ARG, "image stride of the float planes must be a multiple of 4 and keep the images apart");
-   plan(c, c->par.max_batch, height, width);
-   check_device_f32(c, n, (const uint8_t *)d_planes, is, (int)rs, height, width);
-   run_batch(c, SrcImages::f32(d_planes, is, (int)rs), n, height, width);
-   const int32_t *hs = c->h_starts.data(), *ds = c->h_starts.data() + (n + 1);
-   for (int b = 0; b < n; b++) {
-      if (count_hessian) count_hessian[b] = hs[b + 1] - hs[b];
-      if (count_desc) count_desc[b] = ds[b + 1] - ds[b];
-   }
-   if (d_keys_out) *d_keys_out = c->b_out.p;
-   if (total_out) *total_out = ds[n];
+   detect_device(c, n, SrcImages::f32(d_planes, is, (int)rs), height, width, count_hessian, count_desc, d_keys_out, total_out,
+                 [&] { check_device_f32(c, n, (const uint8_t *)d_planes, is, (int)rs, height, width); });
    HS_API_END(c)
 }
 
@@ -812,8 +780,7 @@ int hesaff_stage_gaussian_blur(hesaff_ctx *c, const float *in, int rows, int col
       hipLaunchKernelGGL(k_blur_cols_generic, grid, dim3(256), 0, c->stream, pt, po, (const float *)d_taps, K);
    }
    HIP_TRY(hipMemcpy2DAsync(out, (size_t)cols * 4, d_out, (size_t)pitch * 4, (size_t)cols * 4, rows, hipMemcpyDeviceToHost, c->stream));
-   HIP_TRY(hipStreamSynchronize(c->stream));
-   HIP_TRY(hipGetLastError());
+   finish_stream(c);
    HS_API_END(c)
 }
 
@@ -835,8 +802,7 @@ int hesaff_stage_hessian_response(hesaff_ctx *c, const float *in, int rows, int 
    launch_march<9, true, true, false, true>(c, pi, make_plane(d_l, rows, cols, pitch), make_plane(d_r, rows, cols, pitch), make_plane(nullptr, 0, 0, 0),
                                             d_taps, 1.0f, 1, po, norm * norm);
    HIP_TRY(hipMemcpy2DAsync(out, (size_t)cols * 4, d_out, (size_t)pitch * 4, (size_t)cols * 4, rows, hipMemcpyDeviceToHost, c->stream));
-   HIP_TRY(hipStreamSynchronize(c->stream));
-   HIP_TRY(hipGetLastError());
+   finish_stream(c);
    HS_API_END(c)
 }
 
@@ -853,65 +819,52 @@ int hesaff_stage_half_image(hesaff_ctx *c, const float *in, int rows, int cols, 
    DPlane pi = make_plane(d_in, rows, cols, cols), po = make_plane(d_out, r2, c2, c2);
    hipLaunchKernelGGL(k_half, dim3((c2 + 255) / 256, r2, 1), dim3(256), 0, c->stream, pi, po);
    HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)r2 * c2 * 4, hipMemcpyDeviceToHost, c->stream));
-   HIP_TRY(hipStreamSynchronize(c->stream));
-   HIP_TRY(hipGetLastError());
+   finish_stream(c);
+   HS_API_END(c)
+}
+
+// hesaff_stage_pyramid and its float twin: `image` is rows x cols pixels of 1 byte or, f32, of 4, tightly packed
+static int stage_pyramid(hesaff_ctx *c, const void *image, bool f32, int rows, int cols, float *planes, int *n_octaves, size_t *n_floats)
+{
+   if (!c || rows < 1 || cols < 1) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   bind_device(c);
+   plan(c, 1, rows, cols);
+   size_t nf = 0;
+   for (const OctGeom &g : c->oct) nf += (size_t)10 * g.rows * g.cols;
+   if (n_octaves) *n_octaves = (int)c->oct.size();
+   if (n_floats) *n_floats = nf;
+   if (planes) {
+      if (!image) throw HsError(HESAFF_ERR_ARG, f32 ? "plane is NULL" : "gray is NULL");
+      const size_t row_bytes = (size_t)cols * (f32 ? 4 : 1), bytes = row_bytes * rows;
+      if (f32) {
+         if ((uintptr_t)image % 4 != 0) throw HsError(HESAFF_ERR_ARG, "float plane not 4-byte aligned");
+         int r = 0, col = 0;
+         float v = 0.0f;
+         if (first_bad_f32((const uint8_t *)image, rows, cols, row_bytes, &r, &col, &v))   // the value domain of the _f32 entry points
+            throw_bad_f32(0, (const uint8_t *)image, rows, cols, row_bytes);
+      }
+      c->b_input.ensure(bytes);
+      c->b_stage.ensure((size_t)rows * round_up(cols, 64) * 4);
+      HIP_TRY(hipMemcpyAsync(c->b_input.p, image, bytes, hipMemcpyHostToDevice, c->stream));
+      c->ev_used = 0;
+      StageTimer tm(c);
+      Lists s = make_lists(c);
+      const SrcImages src = f32 ? SrcImages::f32(c->b_input.p, (long long)bytes, (int)row_bytes) : SrcImages::u8(c->b_input.p, 1, (long long)bytes, (int)row_bytes);
+      run_detection(c, src, 1, s, tm, true, planes);
+      finish_stream(c);
+   }
    HS_API_END(c)
 }
 
 int hesaff_stage_pyramid(hesaff_ctx *c, const uint8_t *gray, int rows, int cols, float *planes, int *n_octaves, size_t *n_floats)
 {
-   if (!c || rows < 1 || cols < 1) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   plan(c, 1, rows, cols);
-   size_t nf = 0;
-   for (const OctGeom &g : c->oct) nf += (size_t)10 * g.rows * g.cols;
-   if (n_octaves) *n_octaves = (int)c->oct.size();
-   if (n_floats) *n_floats = nf;
-   if (planes) {
-      if (!gray) throw HsError(HESAFF_ERR_ARG, "gray is NULL");
-      c->b_input.ensure((size_t)rows * cols);
-      c->b_stage.ensure((size_t)rows * round_up(cols, 64) * 4);
-      HIP_TRY(hipMemcpyAsync(c->b_input.p, gray, (size_t)rows * cols, hipMemcpyHostToDevice, c->stream));
-      c->ev_used = 0;
-      StageTimer tm(c);
-      Lists s = make_lists(c);
-      run_detection(c, SrcImages::u8(c->b_input.p, 1, (long long)rows * cols, cols), 1, s, tm, true, planes);
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      HIP_TRY(hipGetLastError());
-   }
-   HS_API_END(c)
+   return stage_pyramid(c, gray, false, rows, cols, planes, n_octaves, n_floats);
 }
 
 int hesaff_stage_pyramid_f32(hesaff_ctx *c, const float *plane, int rows, int cols, float *planes, int *n_octaves, size_t *n_floats)
 {
-   if (!c || rows < 1 || cols < 1) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   plan(c, 1, rows, cols);
-   size_t nf = 0;
-   for (const OctGeom &g : c->oct) nf += (size_t)10 * g.rows * g.cols;
-   if (n_octaves) *n_octaves = (int)c->oct.size();
-   if (n_floats) *n_floats = nf;
-   if (planes) {
-      if (!plane) throw HsError(HESAFF_ERR_ARG, "plane is NULL");
-      if ((uintptr_t)plane % 4 != 0) throw HsError(HESAFF_ERR_ARG, "float plane not 4-byte aligned");
-      const size_t bytes = (size_t)rows * cols * 4;
-      int r = 0, col = 0;
-      float v = 0.0f;
-      if (first_bad_f32((const uint8_t *)plane, rows, cols, (size_t)cols * 4, &r, &col, &v))   // the value domain of the _f32 entry points
-         throw_bad_f32(0, (const uint8_t *)plane, rows, cols, (size_t)cols * 4);
-      c->b_input.ensure(bytes);
-      c->b_stage.ensure((size_t)rows * round_up(cols, 64) * 4);
-      HIP_TRY(hipMemcpyAsync(c->b_input.p, plane, bytes, hipMemcpyHostToDevice, c->stream));
-      c->ev_used = 0;
-      StageTimer tm(c);
-      Lists s = make_lists(c);
-      run_detection(c, SrcImages::f32(c->b_input.p, (long long)bytes, cols * 4), 1, s, tm, true, planes);
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      HIP_TRY(hipGetLastError());
-   }
-   HS_API_END(c)
+   return stage_pyramid(c, plane, true, rows, cols, planes, n_octaves, n_floats);
 }
 
 int hesaff_stage_hessian_keypoints(hesaff_ctx *c, const uint8_t *gray, int rows, int cols, int cap, float *f, int32_t *iv, int *count)
@@ -928,8 +881,7 @@ int hesaff_stage_hessian_keypoints(hesaff_ctx *c, const uint8_t *gray, int rows,
    run_detection(c, SrcImages::u8(c->b_input.p, 1, (long long)rows * cols, cols), 1, s, tm, false, nullptr);
    uint32_t cn[8];
    HIP_TRY(hipMemcpyAsync(cn, s.counters, sizeof cn, hipMemcpyDeviceToHost, c->stream));
-   HIP_TRY(hipStreamSynchronize(c->stream));
-   HIP_TRY(hipGetLastError());
+   finish_stream(c);
    if (cn[2] != 0 || cn[1] > c->cap) throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded");
    const int n = (int)cn[3];
    *count = n;
@@ -975,8 +927,7 @@ int hesaff_stage_find_affine_shape(hesaff_ctx *c, const float *blur, int rows, i
    if (converged) HIP_TRY(hipMemcpyAsync(converged, d_conv, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
    if (iters) HIP_TRY(hipMemcpyAsync(iters, d_iters, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
    if (U) HIP_TRY(hipMemcpyAsync(U, d_U, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
-   HIP_TRY(hipStreamSynchronize(c->stream));
-   HIP_TRY(hipGetLastError());
+   finish_stream(c);
    HS_API_END(c)
 }
 
@@ -990,8 +941,7 @@ int hesaff_stage_rectify(hesaff_ctx *c, int n, float *A)
    HIP_TRY(hipMemcpyAsync(c->b_stage.p, A, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
    hipLaunchKernelGGL(k_rectify_stage, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->b_stage.as<float>());
    HIP_TRY(hipMemcpyAsync(A, c->b_stage.p, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
-   HIP_TRY(hipStreamSynchronize(c->stream));
-   HIP_TRY(hipGetLastError());
+   finish_stream(c);
    HS_API_END(c)
 }
 
@@ -1040,8 +990,7 @@ int hesaff_stage_normalize_affine(hesaff_ctx *c, const float *img, int rows, int
    HIP_TRY(hipMemcpyAsync(&ovf, s.counters + 6, 4, hipMemcpyDeviceToHost, st));
    HIP_TRY(hipMemcpyAsync(alive.data(), s.pw.alive, (size_t)n * 4, hipMemcpyDeviceToHost, st));
    if (patches) HIP_TRY(hipMemcpyAsync(patches, c->b_patches.p, (size_t)n * HS_PATCH_PIX * 4, hipMemcpyDeviceToHost, st));
-   HIP_TRY(hipStreamSynchronize(st));
-   HIP_TRY(hipGetLastError());
+   finish_stream(c);
    if (ovf) throw HsError(HESAFF_ERR_NOMEM, "large-window row buffer exceeded (internal bound violated)");
    if (rejected) for (int i = 0; i < n; i++) rejected[i] = alive[i] ? 0 : 1;
    HS_API_END(c)
@@ -1068,8 +1017,7 @@ int hesaff_stage_sift(hesaff_ctx *c, int n, const float *patches, uint8_t *desc)
    so.vec = (float *)(base + off_vec); so.desc = (uint8_t *)(base + off_desc); so.h_lo = 0; so.h_hi = (uint32_t)n;
    launch_sift(c, c->stream, so, (uint32_t)n, (float2 *)(base + off_vo));
    HIP_TRY(hipMemcpyAsync(desc, base + off_desc, N * 128, hipMemcpyDeviceToHost, c->stream));
-   HIP_TRY(hipStreamSynchronize(c->stream));
-   HIP_TRY(hipGetLastError());
+   finish_stream(c);
    HS_API_END(c)
 }
 
@@ -1112,8 +1060,7 @@ int hesaff_stage_export(hesaff_ctx *c, const hesaff_keypoint *keys, int n, float
          else export_bin_rows(c, d_keys, (uint32_t)n, (char *)c->b_generic.p);
          HIP_TRY(hipMemcpyAsync(buf + hl, c->b_generic.p, body, hipMemcpyDeviceToHost, c->stream));
       }
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      HIP_TRY(hipGetLastError());
+      finish_stream(c);
       *out = buf;
       *len = hl + body;
    } catch (...) {
@@ -1141,8 +1088,7 @@ int hesaff_stage_fmt_g(hesaff_ctx *c, int n, const float *v, char *text, int32_t
    hipLaunchKernelGGL(k_fmt_g_test, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, (const float *)d_v, d_text, d_len);
    HIP_TRY(hipMemcpyAsync(text, d_text, N * 16, hipMemcpyDeviceToHost, c->stream));
    HIP_TRY(hipMemcpyAsync(lens, d_len, N * 4, hipMemcpyDeviceToHost, c->stream));
-   HIP_TRY(hipStreamSynchronize(c->stream));
-   HIP_TRY(hipGetLastError());
+   finish_stream(c);
    HS_API_END(c)
 }
 
@@ -1160,8 +1106,7 @@ int hesaff_stage_jpeg_pixels(hesaff_ctx *c, const hesaff_jpeg_layout *layout, in
    HIP_TRY(hipMemcpyAsync(c->b_jcoef[0].p, blobs, blob_bytes * (size_t)n, hipMemcpyHostToDevice, c->stream));
    jpeg_pixels(c, c->b_jcoef[0].as<uint8_t>(), g, n, c->b_stage.as<uint8_t>(), img, c->stream);
    HIP_TRY(hipMemcpyAsync(pixels, c->b_stage.p, img * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-   HIP_TRY(hipStreamSynchronize(c->stream));
-   HIP_TRY(hipGetLastError());
+   finish_stream(c);
    HS_API_END(c)
 }
 
@@ -1178,8 +1123,7 @@ int hesaff_stage_math(hesaff_ctx *c, int n, const float *a, const float *b, floa
    hipLaunchKernelGGL(k_math, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, (const float *)d_a, (const float *)d_b, d_at, d_pw);
    if (atan2_out) HIP_TRY(hipMemcpyAsync(atan2_out, d_at, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
    if (pow2_out) HIP_TRY(hipMemcpyAsync(pow2_out, d_pw, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-   HIP_TRY(hipStreamSynchronize(c->stream));
-   HIP_TRY(hipGetLastError());
+   finish_stream(c);
    HS_API_END(c)
 }
 
@@ -1198,8 +1142,7 @@ int hesaff_stage_math_sift(hesaff_ctx *c, int n, const float *gy, const float *g
                       d + 2 * (size_t)n, d + 3 * (size_t)n, d + 4 * (size_t)n, d + 5 * (size_t)n);
    float *outs[4] = {ori_general, ori_nd, grad_general, grad_nd};
    for (int q = 0; q < 4; q++) HIP_TRY(hipMemcpyAsync(outs[q], d + (2 + q) * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-   HIP_TRY(hipStreamSynchronize(c->stream));
-   HIP_TRY(hipGetLastError());
+   finish_stream(c);
    HS_API_END(c)
 }
 

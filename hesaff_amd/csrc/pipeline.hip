@@ -120,10 +120,20 @@ static double thread_cpu_ms()   // CPU time of the calling thread (debug lines: 
 // A device buffer that only grows.  ensure() never leaves a dangling pointer behind: the new block
 // is allocated before the old one is released (when the device cannot hold both, the old block
 // is released first and the allocation retried); on failure the buffer is empty (p == nullptr,
-// bytes == 0) and HESAFF_ERR_NOMEM is thrown.
+// bytes == 0) and HESAFF_ERR_NOMEM is thrown.  The buffer owns its block: move-only, released with it.
 struct DevBuf {
    void *p = nullptr;
    size_t bytes = 0;
+   DevBuf() = default;
+   DevBuf(const DevBuf &) = delete;
+   DevBuf &operator=(const DevBuf &) = delete;
+   DevBuf(DevBuf &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+   DevBuf &operator=(DevBuf &&o) noexcept
+   {
+      if (this != &o) { release(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; }
+      return *this;
+   }
+   ~DevBuf() { release(); }
    void ensure(size_t need)
    {
       if (need <= bytes) return;
@@ -162,6 +172,73 @@ struct DevBuf {
       bytes = 0;
    }
    template <class T> T *as() const { return (T *)p; }
+};
+
+// A page-locked host block that only grows, owned like a DevBuf.  The three ways to ask differ in what a block that has to be
+// replaced is sized to - pinning costs 0.1 ms per MB and synchronises the device, so that is part of the schedule.
+struct PinBuf {
+   void *p = nullptr;
+   size_t bytes = 0;
+   PinBuf() = default;
+   PinBuf(const PinBuf &) = delete;
+   PinBuf &operator=(const PinBuf &) = delete;
+   PinBuf(PinBuf &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+   PinBuf &operator=(PinBuf &&o) noexcept
+   {
+      if (this != &o) { release(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; }
+      return *this;
+   }
+   ~PinBuf() { release(); }
+   void release() { if (p) (void)hipHostFree(p); p = nullptr; bytes = 0; }
+   hipError_t replace(size_t cap)   // the old block goes first; on failure the block is empty
+   {
+      release();
+      const hipError_t e = hipHostMalloc(&p, cap, hipHostMallocDefault);
+      if (e != hipSuccess) p = nullptr; else bytes = cap;
+      return e;
+   }
+   // exactly `need` bytes
+   void ensure(size_t need)
+   {
+      if (need <= bytes) return;
+      const hipError_t e = replace(need);
+      if (e != hipSuccess) throw HsError(HESAFF_ERR_NOMEM, std::string("hipHostMalloc failed: ") + hipGetErrorString(e));
+   }
+   // a block that is asked for a little more every other chunk (result blocks: the chunks' keypoint counts differ) grows with
+   // head-room, so that hipHostFree + hipHostMalloc (hundreds of MB, device-synchronising) stop after the first chunks
+   void ensure_grow(size_t need)
+   {
+      if (need <= bytes) return;
+      ensure((need + need / 4 + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1));
+   }
+   // Small results the host reads every batch (per-image counts, counters, byte offsets of the text rows) arrive in PAGE-LOCKED memory:
+   // a hipMemcpyAsync into pageable memory is not asynchronous - the calling thread waits inside the runtime, spinning, until everything
+   // before it in the stream has run (a whole batch of kernels: one busy core per context, measured in round 5) - whereas a copy into
+   // pinned memory is enqueued and the host sleeps on a blocking-sync event.  Twice the need, 4 KB at least.
+   void *ensure_small(size_t need)
+   {
+      if (need > bytes && replace(std::max<size_t>(need * 2, 4096)) != hipSuccess)
+         throw HsError(HESAFF_ERR_NOMEM, "hipHostMalloc failed (small result block)");
+      return p;
+   }
+};
+
+// A HIP event, created with its flags and destroyed with its owner (move-only); passes for the hipEvent_t wherever HIP wants one.
+struct DevEvent {
+   hipEvent_t e = nullptr;
+   DevEvent() = default;
+   explicit DevEvent(unsigned flags) { HIP_TRY(hipEventCreateWithFlags(&e, flags)); }
+   DevEvent(const DevEvent &) = delete;
+   DevEvent &operator=(const DevEvent &) = delete;
+   DevEvent(DevEvent &&o) noexcept : e(o.e) { o.e = nullptr; }
+   DevEvent &operator=(DevEvent &&o) noexcept
+   {
+      if (this != &o) { reset(); e = o.e; o.e = nullptr; }
+      return *this;
+   }
+   ~DevEvent() { reset(); }
+   void reset() { if (e) (void)hipEventDestroy(e); e = nullptr; }
+   operator hipEvent_t() const { return e; }
 };
 
 struct OctGeom {
@@ -240,40 +317,25 @@ struct hesaff_ctx {
    int map_kbits = 32;       // bits of an order key (3 x pixels of the first pyramid level)
    uint32_t map_epoch = 0;   // the last epoch handed out; 0: the next pass refills the map first
 
-   // planes
-   DevBuf b_gray, b_up, b_L, b_L3, b_R, b_map, b_bitmask, b_prefix, b_blocksums, b_generic;
+   // the buffers whose size follows the plan's geometry (B x H x W and the keypoint capacity): a plan the device cannot hold gives
+   // all of them back at once (plan())
+   struct GeomBufs {
+      DevBuf b_gray, b_up, b_L, b_L3, b_R, b_map, b_bitmask, b_prefix, b_blocksums;   // planes
+      DevBuf b_cand, b_rec_f, b_rec_i, b_rec_w, b_hess_f, b_hess_i, b_aff, b_pw, b_bins, b_rank, b_desc, b_out, b_starts;   // lists
+   } geo;
+   DevBuf b_generic;
    std::vector<DPlane> L;   // [octave*3 + level]
    DPlane gray, upimg, L3, R[5];
    // lists
    DevBuf b_counters;       // uint32: [0] cand_count [1] rec_count [2] overflow [3] hess_total [4] desc_total [5] group end
                             //         [6] T' row overflow, [8..12] bin_count, [24..28] bin work counters,
                             //         [32..32+HS_MAX_OCTAVES) octave rec starts
-   DevBuf b_cand, b_rec_f, b_rec_i, b_rec_w, b_hess_f, b_hess_i, b_aff, b_pw, b_bins, b_rank, b_desc, b_out, b_starts, b_patches, b_stage;
+   DevBuf b_patches, b_stage;
    DevBuf b_input;          // staging for host images (stage API)
    // hesaff_detect_batch, host entry point: chunks of max_batch images are pipelined -- pinned
    // staging + H2D of chunk i+1 and D2H of chunk i-1 run beside the kernels of chunk i
    DevBuf b_in2[2], b_outstage[2];
-   struct Pinned {
-      void *p = nullptr;
-      size_t bytes = 0;
-      void ensure(size_t need)
-      {
-         if (need <= bytes) return;
-         if (p) { (void)hipHostFree(p); p = nullptr; bytes = 0; }
-         hipError_t e = hipHostMalloc(&p, need, hipHostMallocDefault);
-         if (e != hipSuccess) { p = nullptr; throw HsError(HESAFF_ERR_NOMEM, std::string("hipHostMalloc failed: ") + hipGetErrorString(e)); }
-         bytes = need;
-      }
-      // a block that is asked for a little more every other chunk (result blocks: the chunks' keypoint counts differ) grows with
-      // head-room, so that hipHostFree + hipHostMalloc (hundreds of MB, device-synchronising) stop after the first chunks
-      void ensure_grow(size_t need)
-      {
-         if (need <= bytes) return;
-         ensure((need + need / 4 + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1));
-      }
-      void release() { if (p) (void)hipHostFree(p); p = nullptr; bytes = 0; }
-   };
-   Pinned pin_in[2];
+   PinBuf pin_in[2];
    // Page-locked buffers the readers of hesaff_process_files fill directly (chunk_engine.h: PinHooks): handed out by size, taken back
    // when their image is on the device, kept pinned from one list to the next (pinning costs 0.1 ms per MB), released with the context.
    // At most kPinReadBytes are out or parked; a request beyond that gets nullptr (the image then takes the staging copy).
@@ -336,43 +398,17 @@ struct hesaff_ctx {
          }
          for (auto &b : out) (void)hipHostFree(b.first);
       }
-      void release()
-      {
-         trim(0);
-         std::lock_guard<std::mutex> lk(mu);
-         bytes_total = 0;
-      }
+      ~PinReadCache() { trim(0); }
    } pin_read;
-   hipEvent_t ev_h2d_blk[2] = {nullptr, nullptr};   // blocking-sync: the staging thread sleeps until a chunk's direct copies have left the readers' buffers
-   std::vector<Pinned> pin_out;       // result blocks: one per chunk of the current call (hesaff_detect_batch), or a ring of three
+   DevEvent ev_h2d_blk[2];   // blocking-sync: the staging thread sleeps until a chunk's direct copies have left the readers' buffers
+   std::vector<PinBuf> pin_out;       // result blocks: one per chunk of the current call (hesaff_detect_batch), or a ring of three
    hesaff_engine::BlockRing ring;     // (hesaff_detect_batch_cb, hesaff_process_files: a block returns to the ring when its consumer is done with it)
    hipStream_t h2d_stream = nullptr, d2h_stream = nullptr;
-   hipEvent_t ev_exp[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};   // profiling, per staging slot: brackets of a chunk's length pass and of its write pass (the host's waits between them - a free pinned block - are not the export's)
+   DevEvent ev_exp[2][4];   // profiling, per staging slot: brackets of a chunk's length pass and of its write pass (the host's waits between them - a free pinned block - are not the export's)
    float export_ms = 0.0f; int32_t export_rows = 0;
-   hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_in_free[2] = {nullptr, nullptr}, ev_out_ready[2] = {nullptr, nullptr}, ev_d2h[2] = {nullptr, nullptr};
-   // Small results the host reads every batch (per-image counts, counters, byte offsets of the text rows) arrive in PAGE-LOCKED memory:
-   // a hipMemcpyAsync into pageable memory is not asynchronous - the calling thread waits inside the runtime, spinning, until everything
-   // before it in the stream has run (a whole batch of kernels: one busy core per context, measured in round 5) - whereas a copy into
-   // pinned memory is enqueued and the host sleeps on a blocking-sync event.
-   struct HostSmall {
-      void *p = nullptr; size_t bytes = 0;
-      void *ensure(size_t need)
-      {
-         if (need > bytes) {
-            if (p) (void)hipHostFree(p);
-            p = nullptr; bytes = 0;
-            const size_t cap = std::max<size_t>(need * 2, 4096);
-            if (hipHostMalloc(&p, cap, hipHostMallocDefault) != hipSuccess) { p = nullptr; throw HsError(HESAFF_ERR_NOMEM, "hipHostMalloc failed (small result block)"); }
-            bytes = cap;
-         }
-         return p;
-      }
-      void release() { if (p) (void)hipHostFree(p); p = nullptr; bytes = 0; }
-   } h_small_end, h_small_mid, h_small_exp;
-   struct HStarts {   // view of h_small_end with std::vector's two members in use
-      int32_t *q = nullptr;
-      int32_t *data() const { return q; }
-   } h_starts;
+   DevEvent ev_h2d[2], ev_in_free[2], ev_out_ready[2], ev_d2h[2];
+   PinBuf h_small_end, h_small_mid, h_small_exp;   // small results the host reads every batch (PinBuf::ensure_small)
+   int32_t *h_starts = nullptr;   // in h_small_end: the last batch's Hessian starts [B + 1], descriptor starts [B + 1], counters [8] (run_batch)
    DevBuf t_mask_idx, t_sgrad_nb, t_sgrad_om, t_vo_rows, t_vo_src, b_rowprefix, b_trows, b_trows2, b_trows3;
    DevBuf b_jcoef[2], b_jplane;   // JPEG chunks: the images' coefficient blobs per input slot, the component planes after the inverse DCT (kernels_jpeg.h)
    DevBuf b_ex_len, b_ex_sums, b_ex_off, b_ex_imgoff, b_ex_starts;   // device export (kernels_export.h): row lengths, sums / offsets per 64 rows, offsets per image
@@ -393,18 +429,18 @@ struct hesaff_ctx {
    hipStream_t side_streams[HS_NSIDE] = {nullptr, nullptr, nullptr, nullptr};
    hipStream_t sift_stream = nullptr;     // descriptor kernels of every image group
    hipStream_t aff_stream = nullptr;      // affine shape of image group g+1 runs beside the patch extraction of group g
-   hipEvent_t ev_detect_done = nullptr, ev_batch_done = nullptr;   // blocking-sync events: the host sleeps instead of spinning
-   std::vector<hipEvent_t> ev_aff;        // one per image group, grown on demand
-   hipEvent_t ev_extract_done[HS_NSLOT] = {}, ev_sift_done[HS_NSLOT] = {};
+   DevEvent ev_detect_done, ev_batch_done;   // blocking-sync events: the host sleeps instead of spinning
+   std::vector<DevEvent> ev_aff;             // one per image group, grown on demand
+   DevEvent ev_extract_done[HS_NSLOT], ev_sift_done[HS_NSLOT];
    DevBuf b_patches2[HS_NSLOT];
    DevBuf b_siftvec2, b_meanvar2, b_siftvo2;   // the descriptor stage's intermediates: one copy (ensure_group_buffers)
-   hipEvent_t ev_fork = nullptr, ev_join[HS_NSIDE] = {nullptr, nullptr, nullptr, nullptr};
+   DevEvent ev_fork, ev_join[HS_NSIDE];
    bool fast_pyramid = false;      // hesaff_params.fast == 2: windows beyond bin 0 sampled from the scale-space level with the matching blur (not bit-exact)
    // off in the product build; the tuning build (-DHESAFF_TUNING) reads them from the environment, and HESAFF_FAST for fast_pyramid
    bool no_overlap = false;        // HESAFF_OVERLAP=0: every kernel alone on the device (per-kernel profiling)
    bool debug = false;             // HESAFF_DEBUG=1: launch geometry on stderr
 
-   std::vector<hipEvent_t> ev_pool;
+   std::vector<DevEvent> ev_pool;   // timing events of the stage timers (get_event)
    size_t ev_used = 0;
 };
 
@@ -414,11 +450,7 @@ struct EvPair { hipEvent_t a, b; int kind; double bytes; };
 
 hipEvent_t get_event(hesaff_ctx *c)
 {
-   if (c->ev_used == c->ev_pool.size()) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreate(&e));
-      c->ev_pool.push_back(e);
-   }
+   if (c->ev_used == c->ev_pool.size()) c->ev_pool.emplace_back(hipEventDefault);
    return c->ev_pool[c->ev_used++];
 }
 
@@ -619,11 +651,8 @@ void plan(hesaff_ctx *c, int B, int H, int W)
       if (e.code == HESAFF_ERR_NOMEM) {
          // a plan the device cannot hold must not keep what it managed to allocate on the way (hundreds of GB for an absurd
          // capacity request): every geometry-sized buffer goes back, the next plan starts from nothing
-         DevBuf *bufs[] = {&c->b_gray, &c->b_up, &c->b_L, &c->b_L3, &c->b_R, &c->b_map, &c->b_bitmask, &c->b_prefix, &c->b_blocksums, &c->b_cand,
-                           &c->b_rec_f, &c->b_rec_i, &c->b_rec_w, &c->b_hess_f, &c->b_hess_i, &c->b_aff, &c->b_pw, &c->b_bins, &c->b_rank, &c->b_desc,
-                           &c->b_out, &c->b_starts};
          (void)hipStreamSynchronize(c->stream);
-         for (DevBuf *b : bufs) b->release();
+         c->geo = hesaff_ctx::GeomBufs();
          c->map_clean = false;
       }
       throw;
@@ -659,11 +688,11 @@ void plan_buffers(hesaff_ctx *c, int B, int H, int W)
    c->words_per_image = words;
    const int pitch0 = round_up(W, 64);
    const size_t plane0 = (size_t)B * H * pitch0;
-   c->b_gray.ensure(plane0 * 4);
-   c->gray = make_plane(c->b_gray.as<float>(), H, W, pitch0);
-   c->b_L.ensure(std::max<size_t>(L_floats * 4, 16));
+   c->geo.b_gray.ensure(plane0 * 4);
+   c->gray = make_plane(c->geo.b_gray.as<float>(), H, W, pitch0);
+   c->geo.b_L.ensure(std::max<size_t>(L_floats * 4, 16));
    {
-      float *p = c->b_L.as<float>();
+      float *p = c->geo.b_L.as<float>();
       for (const OctGeom &g : c->oct)
          for (int l = 0; l < 3; l++) {
             c->L.push_back(make_plane(p, g.rows, g.cols, g.pitch));
@@ -673,25 +702,25 @@ void plan_buffers(hesaff_ctx *c, int B, int H, int W)
    const int ppitch0 = round_up(PW, 64);
    const size_t pplane0 = (size_t)B * PH * ppitch0;
    if (c->up) {
-      c->b_up.ensure(pplane0 * 4);
-      c->upimg = make_plane(c->b_up.as<float>(), PH, PW, ppitch0);
+      c->geo.b_up.ensure(pplane0 * 4);
+      c->upimg = make_plane(c->geo.b_up.as<float>(), PH, PW, ppitch0);
    }
-   c->b_L3.ensure(pplane0 * 4);
-   c->b_R.ensure(pplane0 * 4 * 5);
+   c->geo.b_L3.ensure(pplane0 * 4);
+   c->geo.b_R.ensure(pplane0 * 4 * 5);
    {
-      const void *before = c->b_map.p;
-      const size_t before_bytes = c->b_map.bytes;
-      c->b_map.ensure(std::max<size_t>((size_t)B * PH * PW * 4, 16));
+      const void *before = c->geo.b_map.p;
+      const size_t before_bytes = c->geo.b_map.bytes;
+      c->geo.b_map.ensure(std::max<size_t>((size_t)B * PH * PW * 4, 16));
       // a new block is filled once before its first use (run_detection).  Pointer AND size: ensure()'s out-of-memory path frees the old
       // block first, and the larger one may come back at the same address with a tail that was never filled
-      if (c->b_map.p != before || c->b_map.bytes != before_bytes) c->map_clean = false;
+      if (c->geo.b_map.p != before || c->geo.b_map.bytes != before_bytes) c->map_clean = false;
       int kb = 1;
       while (kb < 32 && (3ull * (unsigned long long)PH * PW) > (1ull << kb)) kb++;
       if (kb != c->map_kbits) { c->map_kbits = kb; c->map_clean = false; }   // (another key width: epochs of the old one mean nothing)
    }
    const long long total_words = (long long)B * words;
-   c->b_bitmask.ensure(std::max<size_t>((size_t)total_words * 8, 16));
-   c->b_prefix.ensure(std::max<size_t>((size_t)(total_words + 1) * 4, 16));
+   c->geo.b_bitmask.ensure(std::max<size_t>((size_t)total_words * 8, 16));
+   c->geo.b_prefix.ensure(std::max<size_t>((size_t)(total_words + 1) * 4, 16));
    double mpx = (double)B * PH * PW / 1.0e6;   // capacity per megapixel of the first pyramid level
    double capd = mpx * (double)c->par.max_kpts_per_mpx;
    if (capd < 4096) capd = 4096;
@@ -699,7 +728,7 @@ void plan_buffers(hesaff_ctx *c, int B, int H, int W)
    c->cap = ((uint32_t)capd + 63u) & ~63u;   // a multiple of 64: the arrays carved out of one buffer (cap entries each) stay 16-byte aligned
    const size_t cap = c->cap;
    const long long scan_items = std::max<long long>(total_words, (long long)cap);
-   c->b_blocksums.ensure((size_t)((scan_items + SCAN_BLOCK - 1) / SCAN_BLOCK + 1) * 4);
+   c->geo.b_blocksums.ensure((size_t)((scan_items + SCAN_BLOCK - 1) / SCAN_BLOCK + 1) * 4);
    c->b_counters.ensure(64 * 4);
    {
       // candidate slots: the keypoint capacity + what the wavefronts of k_extrema_march may leave unused of their blocks of 64
@@ -710,20 +739,20 @@ void plan_buffers(hesaff_ctx *c, int B, int H, int W)
       const unsigned long long cc = (unsigned long long)cap + (unsigned long long)cap / 8 + HS_CAND_BLOCK * waves0;
       if (cc > 0xfffffff0ull) throw HsError(HESAFF_ERR_ARG, "batch too large for 32-bit candidate indices");
       c->cand_cap = (uint32_t)cc;
-      c->b_cand.ensure((size_t)cc * sizeof(CandRec));
+      c->geo.b_cand.ensure((size_t)cc * sizeof(CandRec));
    }
-   c->b_rec_f.ensure(cap * 4 * 4);
-   c->b_rec_i.ensure(cap * 4 * 4);
-   c->b_rec_w.ensure(cap * 8);
-   c->b_hess_f.ensure(cap * 4 * 4);
-   c->b_hess_i.ensure(cap * 2 * 4);
-   c->b_aff.ensure(cap * 6 * 4);
-   c->b_pw.ensure(cap * 6 * 4);
-   c->b_bins.ensure(cap * HS_NBINS * 4);
-   c->b_rank.ensure((cap + 1) * 4);
-   c->b_desc.ensure(cap * 128);
-   c->b_out.ensure(cap * sizeof(KeyRec));
-   c->b_starts.ensure(((size_t)(B + 1) * 3 + 2) * 4);   // hessian starts | descriptor starts | huge-window rows per image, + their largest side
+   c->geo.b_rec_f.ensure(cap * 4 * 4);
+   c->geo.b_rec_i.ensure(cap * 4 * 4);
+   c->geo.b_rec_w.ensure(cap * 8);
+   c->geo.b_hess_f.ensure(cap * 4 * 4);
+   c->geo.b_hess_i.ensure(cap * 2 * 4);
+   c->geo.b_aff.ensure(cap * 6 * 4);
+   c->geo.b_pw.ensure(cap * 6 * 4);
+   c->geo.b_bins.ensure(cap * HS_NBINS * 4);
+   c->geo.b_rank.ensure((cap + 1) * 4);
+   c->geo.b_desc.ensure(cap * 128);
+   c->geo.b_out.ensure(cap * sizeof(KeyRec));
+   c->geo.b_starts.ensure(((size_t)(B + 1) * 3 + 2) * 4);   // hessian starts | descriptor starts | huge-window rows per image, + their largest side
    // patch taps: P <= sqrt(W*H) + small (the det-1 window must fit)
    const int max_p0 = (int)std::floor(std::sqrt((double)W * (double)H)) + 3;
    ensure_patch_taps(c, max_p0);
@@ -752,7 +781,7 @@ template <class LOAD> void exclusive_scan(hesaff_ctx *c, LOAD load, long long n,
    // out[0..n) exclusive prefix, *total = sum (device pointers)
    if (n <= 0) { HIP_TRY(hipMemsetAsync(total, 0, 4, c->stream)); return; }
    const int nb = (int)((n + SCAN_BLOCK - 1) / SCAN_BLOCK);
-   uint32_t *bs = c->b_blocksums.as<uint32_t>();
+   uint32_t *bs = c->geo.b_blocksums.as<uint32_t>();
    hipLaunchKernelGGL(k_scan_reduce<LOAD>, dim3(nb), dim3(256), 0, c->stream, load, n, bs);
    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, c->stream, bs, nb, total);
    hipLaunchKernelGGL(k_scan_down<LOAD>, dim3(nb), dim3(256), 0, c->stream, load, n, bs, out);
@@ -857,22 +886,22 @@ Lists make_lists(hesaff_ctx *c)
    uint32_t *cnt = c->b_counters.as<uint32_t>();
    const size_t cap = c->cap;
    s.counters = cnt;
-   s.cl.count = cnt + 0; s.cl.items = c->b_cand.as<CandRec>(); s.cl.cap = c->cand_cap; s.cl.overflow = cnt + 2;
+   s.cl.count = cnt + 0; s.cl.items = c->geo.b_cand.as<CandRec>(); s.cl.cap = c->cand_cap; s.cl.overflow = cnt + 2;
    s.rl.count = cnt + 1; s.rl.cap = c->cap;
-   float *rf = c->b_rec_f.as<float>();
+   float *rf = c->geo.b_rec_f.as<float>();
    s.rl.x = rf; s.rl.y = rf + cap; s.rl.s = rf + 2 * cap; s.rl.response = rf + 3 * cap;
-   uint32_t *ri = c->b_rec_i.as<uint32_t>();
+   uint32_t *ri = c->geo.b_rec_i.as<uint32_t>();
    s.rl.meta = (int32_t *)ri; s.rl.cell = ri + cap; s.rl.key = ri + 2 * cap; s.rl.bit = ri + 3 * cap;
-   s.rl.word = c->b_rec_w.as<long long>();
-   float *hf = c->b_hess_f.as<float>();
+   s.rl.word = c->geo.b_rec_w.as<long long>();
+   float *hf = c->geo.b_hess_f.as<float>();
    s.hl.x = hf; s.hl.y = hf + cap; s.hl.s = hf + 2 * cap; s.hl.response = hf + 3 * cap;
-   int32_t *hi = c->b_hess_i.as<int32_t>();
+   int32_t *hi = c->geo.b_hess_i.as<int32_t>();
    s.hl.meta = hi; s.hl.r0c0 = hi + cap; s.hl.cap = c->cap;
-   int32_t *ai = c->b_aff.as<int32_t>();
+   int32_t *ai = c->geo.b_aff.as<int32_t>();
    s.ao.converged = ai; s.ao.iters = ai + cap; s.ao.U = (float *)(ai + 2 * cap);
-   int32_t *pi = c->b_pw.as<int32_t>();
+   int32_t *pi = c->geo.b_pw.as<int32_t>();
    s.pw.P0 = pi; s.pw.alive = pi + cap; s.pw.A = (float *)(pi + 2 * cap);
-   s.pw.bin_count = cnt + 8; s.pw.bin_work = cnt + 24; s.pw.bin_items = c->b_bins.as<uint32_t>(); s.pw.cap = c->cap;
+   s.pw.bin_count = cnt + 8; s.pw.bin_work = cnt + 24; s.pw.bin_items = c->geo.b_bins.as<uint32_t>(); s.pw.cap = c->cap;
    return s;
 }
 
@@ -977,10 +1006,10 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
    uint32_t *cnt = s.counters;
    const float *ptaps = c->t_pyr_taps.as<float>();
    HIP_TRY(hipMemsetAsync(cnt, 0, 64 * 4, st));
-   HIP_TRY(hipMemsetAsync(c->b_bitmask.p, 0, std::max<size_t>((size_t)B * c->words_per_image * 8, 8), st));
+   HIP_TRY(hipMemsetAsync(c->geo.b_bitmask.p, 0, std::max<size_t>((size_t)B * c->words_per_image * 8, 8), st));
    // octaveMap (pyramid.cpp:226: zeroed per octave): the order-key map is filled with "free" when it is new; every pass over an octave then bids
    // with keys of a fresh, smaller epoch (OctaveCtx::map_epoch), so what earlier passes left behind never wins - no fill and no reset per octave
-   if (!c->map_clean) { HIP_TRY(hipMemsetAsync(c->b_map.p, 0xFF, c->b_map.bytes, st)); c->map_epoch = c->map_kbits < 32 ? (0xffffffffu >> c->map_kbits) : 0u; c->map_clean = true; }
+   if (!c->map_clean) { HIP_TRY(hipMemsetAsync(c->geo.b_map.p, 0xFF, c->geo.b_map.bytes, st)); c->map_epoch = c->map_kbits < 32 ? (0xffffffffu >> c->map_kbits) : 0u; c->map_clean = true; }
 
    int t = tm.begin(T_PYR);
    DPlane none = make_plane(nullptr, 0, 0, 0);
@@ -1034,10 +1063,10 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
       const size_t planeF = (size_t)B * g.rows * g.pitch;
       DPlane Lo[5], Ro[5];
       for (int l = 0; l < 3; l++) Lo[l] = c->L[o * 3 + l];
-      Lo[3] = make_plane(c->b_L3.as<float>(), g.rows, g.cols, g.pitch);
+      Lo[3] = make_plane(c->geo.b_L3.as<float>(), g.rows, g.cols, g.pitch);
       Lo[4] = none;
       if (keep_all_planes) Lo[4] = make_plane(c->b_stage.as<float>(), g.rows, g.cols, g.pitch);
-      for (int l = 0; l < 5; l++) Ro[l] = make_plane(c->b_R.as<float>() + l * planeF, g.rows, g.cols, g.pitch);
+      for (int l = 0; l < 5; l++) Ro[l] = make_plane(c->geo.b_R.as<float>() + l * planeF, g.rows, g.cols, g.pitch);
       t = tm.begin(T_PYR);
       // R0 = hessianResponse(L0) (pyramid.cpp:230) is fused into the first blur launch when the
       // marching kernel handles it (default sigmas: K = 9); otherwise a separate pass.
@@ -1087,9 +1116,9 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
       for (int l = 0; l < 5; l++) { oc.R[l] = Ro[l]; oc.L[l] = Lo[l]; oc.sigma[l] = sc.level_sigma[l]; }
       oc.pixelDistance = c->consts.pd0 * (float)(1 << o);   // pyramid.cpp:288: doubles per octave
       oc.octave = (int)o;
-      oc.map = c->b_map.as<uint32_t>();
+      oc.map = c->geo.b_map.as<uint32_t>();
       // a fresh epoch for this pass (counting down; the all-ones epoch is the fill value): refill when they have run out
-      if (c->map_epoch == 0) { HIP_TRY(hipMemsetAsync(c->b_map.p, 0xFF, c->b_map.bytes, st)); c->map_epoch = c->map_kbits < 32 ? (0xffffffffu >> c->map_kbits) : 0u; }
+      if (c->map_epoch == 0) { HIP_TRY(hipMemsetAsync(c->geo.b_map.p, 0xFF, c->geo.b_map.bytes, st)); c->map_epoch = c->map_kbits < 32 ? (0xffffffffu >> c->map_kbits) : 0u; }
       if (c->map_epoch > 0) c->map_epoch--;
       oc.map_epoch = c->map_kbits < 32 ? (c->map_epoch << c->map_kbits) : 0u;
       oc.word_base = g.word_base;
@@ -1109,27 +1138,27 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
          tm.end(te);
          hipLaunchKernelGGL(k_localize, dim3(HS_GRID_LOC), dim3(256), 0, st, oc, s.cl, s.rl, c->consts);
          hipLaunchKernelGGL(k_dedupe, dim3(HS_GRID_DED), dim3(256), 0, st, oc, s.rl, (const uint32_t *)(cnt + 32 + o),
-                            c->b_bitmask.as<unsigned long long>());
+                            c->geo.b_bitmask.as<unsigned long long>());
       }
       tm.end(t);
    }
    // ---- ordering ----
    t = tm.begin(T_DET);
    const long long total_words = (long long)B * c->words_per_image;
-   LoadPopc lp; lp.p = c->b_bitmask.as<unsigned long long>();
-   exclusive_scan(c, lp, total_words, c->b_prefix.as<uint32_t>(), cnt + 3);
+   LoadPopc lp; lp.p = c->geo.b_bitmask.as<unsigned long long>();
+   exclusive_scan(c, lp, total_words, c->geo.b_prefix.as<uint32_t>(), cnt + 3);
    // the records at their ranks as 32-byte items (in the candidate buffer: its last reader, the last octave's k_localize, is done), then dealt out
-   HessItem *items = reinterpret_cast<HessItem *>(c->b_cand.p);
+   HessItem *items = reinterpret_cast<HessItem *>(c->geo.b_cand.p);
    static_assert(sizeof(HessItem) == 32 && sizeof(CandRec) >= sizeof(HessItem), "the items fit the candidate slots (cand_cap >= cap)");
-   hipLaunchKernelGGL(k_scatter_ordered, dim3(HS_GRID_SCAT), dim3(256), 0, st, s.rl, (const unsigned long long *)c->b_bitmask.p,
-                      (const uint32_t *)c->b_prefix.p, items, s.hl.cap);
+   hipLaunchKernelGGL(k_scatter_ordered, dim3(HS_GRID_SCAT), dim3(256), 0, st, s.rl, (const unsigned long long *)c->geo.b_bitmask.p,
+                      (const uint32_t *)c->geo.b_prefix.p, items, s.hl.cap);
    hipLaunchKernelGGL(k_hess_deal, dim3(HS_GRID_SCAT), dim3(256), 0, st, (const HessItem *)items, (const uint32_t *)(cnt + 3), s.hl);
-   hipLaunchKernelGGL(k_image_counts, dim3((B + 1 + 63) / 64), dim3(64), 0, st, (const uint32_t *)c->b_prefix.p,
-                      c->words_per_image, B, (const uint32_t *)(cnt + 3), c->b_starts.as<int32_t>());
+   hipLaunchKernelGGL(k_image_counts, dim3((B + 1 + 63) / 64), dim3(64), 0, st, (const uint32_t *)c->geo.b_prefix.p,
+                      c->words_per_image, B, (const uint32_t *)(cnt + 3), c->geo.b_starts.as<int32_t>());
    // per image: upper bound of the T' rows its huge windows (P > 512) need, known from the scales alone
-   HIP_TRY(hipMemsetAsync(c->b_starts.as<int32_t>() + 2 * (B + 1), 0, (size_t)(B + 2) * 4, st));
+   HIP_TRY(hipMemsetAsync(c->geo.b_starts.as<int32_t>() + 2 * (B + 1), 0, (size_t)(B + 2) * 4, st));
    hipLaunchKernelGGL(k_image_large_rows, dim3(512), dim3(256), 0, st, s.hl, (const uint32_t *)(cnt + 3), c->consts.mrSize,
-                      c->b_starts.as<uint32_t>() + 2 * (B + 1), B);
+                      c->geo.b_starts.as<uint32_t>() + 2 * (B + 1), B);
    tm.end(t);
 }
 
@@ -1219,16 +1248,15 @@ void run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
       // The one host round trip of a batch: per-image Hessian counts + large-window row bounds.  The bin kernels
       // only extract the 41x41 patches (to HBM); the descriptor runs as four kernels with the parallel axis each
       // part wants (kernels_sift.h).  Images are processed in groups so that the patch buffers stay bounded.
-      int32_t *hs_p = (int32_t *)c->h_small_mid.ensure(((size_t)3 * (B + 1) + 1) * 4);   // pinned: see hesaff_ctx::HostSmall
-      struct { int32_t *q; int32_t *data() const { return q; } int32_t &operator[](size_t i) const { return q[i]; } } hs{hs_p};
-      HIP_TRY(hipMemcpyAsync(hs.data(), c->b_starts.p, ((size_t)3 * (B + 1) + 1) * 4, hipMemcpyDeviceToHost, st));
+      int32_t *hs = (int32_t *)c->h_small_mid.ensure_small(((size_t)3 * (B + 1) + 1) * 4);
+      HIP_TRY(hipMemcpyAsync(hs, c->geo.b_starts.p, ((size_t)3 * (B + 1) + 1) * 4, hipMemcpyDeviceToHost, st));
       HIP_TRY(hipEventRecord(c->ev_detect_done, st));
       const double dbg_ca = c->debug ? thread_cpu_ms() : 0.0;
       hs_wait_event(c->ev_detect_done);   // sleeps: no core spins while the detection stage runs
       if (c->debug) fprintf(stderr, "[hesaff] run_batch: caller's CPU inside the wait for the detection stage %.2f ms\n", thread_cpu_ms() - dbg_ca);
       if ((uint32_t)hs[B] > c->cap) throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded; raise hesaff_params.max_kpts_per_mpx");
       n_hess_host = (uint32_t)hs[B];
-      const uint32_t *lrows = (const uint32_t *)hs.data() + 2 * (B + 1);
+      const uint32_t *lrows = (const uint32_t *)hs + 2 * (B + 1);
       c->batch_max_p = (int)lrows[B + 1];   // largest huge window of the batch (0: none)
       // image groups [h_lo, h_hi) of at most group_kpts keypoints: about 16 groups per batch keep the
       // three-stage pipeline full, between 300 k (launch overheads) and 1.2 M keypoints (buffer size);
@@ -1250,11 +1278,7 @@ void run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
          }
          g0 = g1;
       }
-      while (c->ev_aff.size() < groups.size()) {
-         hipEvent_t e;
-         HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-         c->ev_aff.push_back(e);
-      }
+      while (c->ev_aff.size() < groups.size()) c->ev_aff.emplace_back(hipEventDisableTiming);
       if (max_n) ensure_group_buffers(c, max_n);
       // Software pipeline over image groups, one stream per stage:
       //   affine shape of group g+1 (aff_stream)  |  patch extraction of group g (main + side
@@ -1290,7 +1314,7 @@ void run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
          if (ss != st) HIP_TRY(hipStreamWaitEvent(ss, c->ev_extract_done[slot], 0));
          SiftIO so;
          so.patches = c->b_patches2[slot].as<float>(); so.alive = s.pw.alive; so.meanvar = c->b_meanvar2.as<float>();
-         so.vec = c->b_siftvec2.as<float>(); so.desc = c->b_desc.as<uint8_t>(); so.h_lo = h_lo; so.h_hi = h_hi;
+         so.vec = c->b_siftvec2.as<float>(); so.desc = c->geo.b_desc.as<uint8_t>(); so.h_lo = h_lo; so.h_hi = h_hi;
          const int ts = tm.begin(T_SIFT, 0, ss);
          launch_sift(c, ss, so, n, c->b_siftvo2.as<float2>());
          tm.end(ts);
@@ -1305,24 +1329,24 @@ void run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
    // Hessian keypoints (alive[] is rewritten for h < n_hess each batch; the host knows n_hess since the round trip after detection -
    // the scan used to run over the whole capacity, 85 M flags for 31 M keypoints, behind a kernel that cleared the tail)
    LoadFlagI32 lf; lf.p = s.pw.alive;
-   exclusive_scan(c, lf, (long long)n_hess_host, c->b_rank.as<uint32_t>(), cnt + 4);
-   hipLaunchKernelGGL(k_pack, dim3(HS_GRID_PACK), dim3(256), 0, st, s.hl, (const uint32_t *)(cnt + 3), s.pw, (const uint32_t *)c->b_rank.p,
-                      (const uint8_t *)c->b_desc.p, c->b_out.as<KeyRec>());
-   hipLaunchKernelGGL(k_desc_starts, dim3((B + 1 + 63) / 64), dim3(64), 0, st, (const int32_t *)c->b_starts.p, B,
-                      (const uint32_t *)c->b_rank.p, (const uint32_t *)(cnt + 3), (const uint32_t *)(cnt + 4),
-                      c->b_starts.as<int32_t>() + (B + 1));
+   exclusive_scan(c, lf, (long long)n_hess_host, c->geo.b_rank.as<uint32_t>(), cnt + 4);
+   hipLaunchKernelGGL(k_pack, dim3(HS_GRID_PACK), dim3(256), 0, st, s.hl, (const uint32_t *)(cnt + 3), s.pw, (const uint32_t *)c->geo.b_rank.p,
+                      (const uint8_t *)c->geo.b_desc.p, c->geo.b_out.as<KeyRec>());
+   hipLaunchKernelGGL(k_desc_starts, dim3((B + 1 + 63) / 64), dim3(64), 0, st, (const int32_t *)c->geo.b_starts.p, B,
+                      (const uint32_t *)c->geo.b_rank.p, (const uint32_t *)(cnt + 3), (const uint32_t *)(cnt + 4),
+                      c->geo.b_starts.as<int32_t>() + (B + 1));
    tm.end(t);
    tm.end(tt);
-   c->h_starts.q = (int32_t *)c->h_small_end.ensure(((size_t)2 * (B + 1) + 8) * 4);
-   HIP_TRY(hipMemcpyAsync(c->h_starts.data(), c->b_starts.p, (size_t)2 * (B + 1) * 4, hipMemcpyDeviceToHost, st));
-   HIP_TRY(hipMemcpyAsync(c->h_starts.data() + 2 * (B + 1), cnt, 8 * 4, hipMemcpyDeviceToHost, st));
+   c->h_starts = (int32_t *)c->h_small_end.ensure_small(((size_t)2 * (B + 1) + 8) * 4);
+   HIP_TRY(hipMemcpyAsync(c->h_starts, c->geo.b_starts.p, (size_t)2 * (B + 1) * 4, hipMemcpyDeviceToHost, st));
+   HIP_TRY(hipMemcpyAsync(c->h_starts + 2 * (B + 1), cnt, 8 * 4, hipMemcpyDeviceToHost, st));
    HIP_TRY(hipEventRecord(c->ev_batch_done, st));
    const double dbg_cb = c->debug ? thread_cpu_ms() : 0.0;
    hs_wait_event(c->ev_batch_done);
    if (c->debug) fprintf(stderr, "[hesaff] run_batch: caller's CPU inside the wait for the end of the batch %.2f ms\n", thread_cpu_ms() - dbg_cb);
    HIP_TRY(hipGetLastError());
    if (c->profiling) collect_timings(c, tm, B);
-   const int32_t *cn = c->h_starts.data() + 2 * (B + 1);
+   const int32_t *cn = c->h_starts + 2 * (B + 1);
    if (cn[2] != 0 || (uint32_t)cn[1] > c->cap)
       throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded; raise hesaff_params.max_kpts_per_mpx");
    if (cn[6] != 0) throw HsError(HESAFF_ERR_NOMEM, "large-window row buffer exceeded (internal bound violated)");
@@ -1347,7 +1371,7 @@ unsigned long long export_text_prepare(hesaff_ctx *c, const KeyRec *keys, uint32
    hipLaunchKernelGGL(k_text_imgoff, dim3((B + 1 + 63) / 64), dim3(64), 0, st, d_starts, B, (const uint16_t *)c->b_ex_len.p,
                       (const unsigned long long *)c->b_ex_off.p, c->b_ex_imgoff.as<unsigned long long>());
    // into pinned memory, then a sleep on the blocking-sync event (a copy into the pageable vector would spin in the runtime)
-   unsigned long long *ho = (unsigned long long *)c->h_small_exp.ensure(((size_t)B + 1) * 8);
+   unsigned long long *ho = (unsigned long long *)c->h_small_exp.ensure_small(((size_t)B + 1) * 8);
    HIP_TRY(hipMemcpyAsync(ho, c->b_ex_imgoff.p, ((size_t)B + 1) * 8, hipMemcpyDeviceToHost, st));
    HIP_TRY(hipEventRecord(c->ev_batch_done, st));      // (run_batch has returned: the event is free)
    hs_wait_event(c->ev_batch_done);
@@ -1422,7 +1446,7 @@ void pack_regions(hesaff_ctx *c, uint32_t n_hess, int B, hesaff_region *d_region
    RegionTab tab;
    for (int o = 0; o < HS_MAX_OCTAVES; o++) tab.pd[o] = c->consts.pd0 * (float)(1 << o);   // pyramid.cpp:288, as run_detection hands it on
    hipLaunchKernelGGL(k_pack_regions, dim3(std::min<uint32_t>((n_hess + 255) / 256, 4096u)), dim3(256), 0, c->stream, s.hl, n_hess, s.ao, s.pw,
-                      (const uint32_t *)c->b_rank.p, (const int32_t *)c->b_starts.as<int32_t>() + (B + 1), tab, (uint4 *)d_regions);
+                      (const uint32_t *)c->geo.b_rank.p, (const int32_t *)c->geo.b_starts.as<int32_t>() + (B + 1), tab, (uint4 *)d_regions);
 }
 
 } // namespace

@@ -7,6 +7,10 @@ device raises HesaffError.
 Input: 8-bit images (HesaffContext.detect_batch and its kin) or float32 grey planes, the reference's own
 CV_32FC1 detector input (the *_f32 methods: detect_batch_f32, detect_regions_f32, detect_batch_cb_f32,
 pyramid_f32 on numpy arrays, detect_batch_device_f32 on a torch tensor in device memory).
+
+Detect, choose, describe the chosen: HesaffContext.detect_regions returns every Hessian keypoint as a record, and
+HesaffContext.describe_regions (describe_regions_f32) runs the rest of the chain on the records the caller hands back,
+or on keypoints of the caller's own, entering at findAffineShape (FROM_POINTS) or at the affine shape (FROM_SHAPES).
 """
 from ._binding import (  # noqa: F401
     HesaffError,
@@ -15,6 +19,8 @@ from ._binding import (  # noqa: F401
     KEYPOINT_DTYPE,
     REGION_DTYPE,
     Region,
+    FROM_POINTS,
+    FROM_SHAPES,
     default_params,
     format_sift,
     format_sift_mt,

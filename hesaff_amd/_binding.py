@@ -180,6 +180,12 @@ def load_library():
     L.hesaff_detect_batch_device_f32.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int64, _i32p, _i32p, C.POINTER(vp),
                                                  C.POINTER(C.c_int64)]
     L.hesaff_stage_pyramid_f32.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
+    # describe caller-supplied keypoints (found by name: a library of ABI version 8 built before them lacks the two symbols)
+    if hasattr(L, "hesaff_describe_regions"):
+        L.hesaff_describe_regions.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                              C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.POINTER(_RegionResult)]
+        L.hesaff_describe_regions_f32.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.POINTER(_RegionResult)]
     L.hesaff_set_profiling.argtypes = [vp, C.c_int]
     L.hesaff_get_timings.argtypes = [vp, C.POINTER(Timings)]
     L.hesaff_ellipse.argtypes = [vp, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -243,8 +249,12 @@ ABI_SYMBOLS = [
     "hesaff_read_pnm_alloc", "hesaff_read_image_alloc", "hesaff_set_pinned_read_budget", "hesaff_set_pool_priority",
     "hesaff_stage_threads_for_pool", "hesaff_read_bmp", "hesaff_read_tiff", "hesaff_detect_regions", "hesaff_sizeof_region",
     "hesaff_detect_batch_f32", "hesaff_detect_batch_cb_f32", "hesaff_detect_regions_f32", "hesaff_detect_batch_device_f32",
-    "hesaff_stage_pyramid_f32",
+    "hesaff_stage_pyramid_f32", "hesaff_describe_regions", "hesaff_describe_regions_f32",
 ]
+
+# hesaff_describe_regions' `from`: which of the reference's two public callback members each record enters the chain through
+FROM_POINTS = 1   # onHessianKeypointDetected (hesaff.cpp:66-71): findAffineShape, then the rest when it converges
+FROM_SHAPES = 2   # onAffineShapeFound (hesaff.cpp:73-105): rectify, normalizeAffine, SIFT
 
 
 def default_params():
@@ -446,6 +456,35 @@ class HesaffContext:
         res = (_RegionResult * n)()
         self._check(self.L.hesaff_detect_regions(self.h, n, ptrs, ws, hs, st, chs, res))
         # copies out of the library-owned (pinned) result buffer, valid until the next call
+        return [(self._regions_at(r.regions, r.count_hessian), self._keys_at(r.keys, r.count_desc)) for r in res]
+
+    @staticmethod
+    def _region_lists(regions, n):
+        """one REGION_DTYPE array per image -> (arrays, pointers, counts)"""
+        if len(regions) != n:
+            raise ValueError("describe_regions takes one record array per image (%d images, %d arrays)" % (n, len(regions)))
+        recs = [np.ascontiguousarray(r, dtype=REGION_DTYPE).reshape(-1) for r in regions]
+        ptrs = (C.c_void_p * n)(*[r.ctypes.data if r.size else None for r in recs])
+        counts = (C.c_int * n)(*[r.size for r in recs])
+        return recs, ptrs, counts
+
+    def describe_regions(self, images, regions, from_):
+        """hesaff_describe_regions: the rest of the chain for the caller's records.  images as for detect_batch; regions: one
+        REGION_DTYPE array per image (what detect_regions returned, whole, filtered or reordered, or keypoints of the caller's own);
+        from_: FROM_POINTS (findAffineShape on the plane (octave, level), then rectify / normalizeAffine / SIFT) or FROM_SHAPES
+        (a11..a22 given: rectify / normalizeAffine / SIFT only).  -> what detect_regions returns, records and keys in the caller's order."""
+        imgs, n, ptrs, ws, hs, st, chs = self._u8_list(images)
+        recs, rptrs, counts = self._region_lists(regions, n)
+        res = (_RegionResult * n)()
+        self._check(self.L.hesaff_describe_regions(self.h, n, ptrs, ws, hs, st, chs, rptrs, counts, int(from_), res))
+        return [(self._regions_at(r.regions, r.count_hessian), self._keys_at(r.keys, r.count_desc)) for r in res]
+
+    def describe_regions_f32(self, images, regions, from_):
+        """hesaff_describe_regions_f32: describe_regions for 2-D float32 grey planes."""
+        imgs, ptrs, ws, hs, st = self._f32_list(images)
+        recs, rptrs, counts = self._region_lists(regions, len(imgs))
+        res = (_RegionResult * len(imgs))()
+        self._check(self.L.hesaff_describe_regions_f32(self.h, len(imgs), ptrs, ws, hs, st, rptrs, counts, int(from_), res))
         return [(self._regions_at(r.regions, r.count_hessian), self._keys_at(r.keys, r.count_desc)) for r in res]
 
     @staticmethod

@@ -269,6 +269,40 @@ using namespace hesaff_engine;
    throw HsError(HESAFF_ERR_ARG, msg);
 }
 
+// hesaff_describe_regions: why a caller's record is refused (include/hesaff_amd.h lists the rules), nullptr when it is accepted.
+// n_oct: the octaves of this image's pyramid.  Runs on the staging thread while the records are copied into pinned memory, so no
+// refused value reaches a kernel.
+const char *describe_bad_record(const hesaff_region &r, int from, int n_oct)
+{
+   const float lim = 1048576.0f;   // 2^20
+   if (r.type < 0 || r.type > 2) return "type is not 0, 1 or 2";
+   if (!finite_f(r.x) || !finite_f(r.y) || !finite_f(r.s) || !finite_f(r.response)) return "x, y, s or response is not finite";
+   if (fabsf(r.x) > lim || fabsf(r.y) > lim) return "|x| or |y| exceeds 2^20";
+   if (!(r.s > 0.0f && r.s <= lim)) return "s is not in (0, 2^20]";
+   if (from == HESAFF_FROM_POINTS) {
+      if (r.octave < 0 || r.octave >= n_oct) return "octave is outside this image's pyramid";
+      if (r.level < 0 || r.level >= HS_NSCALES) return "level is not one the detector finds keypoints on (0..2)";
+      return nullptr;
+   }
+   const float a[4] = {r.a11, r.a12, r.a21, r.a22};
+   for (float v : a) {
+      if (!finite_f(v)) return "a11..a22 is not finite";
+      if (fabsf(v) > lim) return "|a_ij| exceeds 2^20";
+   }
+   // rectifyAffineTransformationUpIsUp divides by both (helpers.cpp:90-97), in double
+   if ((double)r.a11 * (double)r.a22 - (double)r.a12 * (double)r.a21 == 0.0) return "a11 * a22 - a12 * a21 is zero";
+   if ((double)r.a11 * (double)r.a11 + (double)r.a12 * (double)r.a12 == 0.0) return "a11^2 + a12^2 is zero";
+   return nullptr;
+}
+
+// octaves of the pyramid of an H x W image (plan_buffers builds the same sequence: pyramid.cpp:283-291)
+int pyramid_octaves(int H, int W, int up)
+{
+   int n = 0;
+   for (int r = H << up, cc = W << up; r > 2 * HS_BORDER + 2 && cc > 2 * HS_BORDER + 2 && n < HS_MAX_OCTAVES; r /= 2, cc /= 2) n++;
+   return n;
+}
+
 void ensure_copy_streams(hesaff_ctx *c)
 {
    if (c->h2d_stream) return;
@@ -306,6 +340,7 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
       size_t text_at = 0, bin_at = 0;         // where the text / sidecar rows start inside the result block
       size_t regions_at = 0;                  // WANT_REGIONS: where the hesaff_region records start
       int total = 0, block = -1, no = 0, largest = 0;
+      uint32_t n_rec = 0;                     // hesaff_describe_regions: records of the chunk
       bool copied = false;                    // a copy out was enqueued (ev_d2h of its slot is recorded)
    };
    const int wants = io.wants();
@@ -381,6 +416,35 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
          const size_t b = *std::min_element(bad_img.begin(), bad_img.end());
          if (b < nimg) throw_bad_f32(q.index[b], q.data[b], q.H, q.W, q.stride[b]);
       }
+      if (q.from) {
+         // the chunk's records travel with it: [B + 1 starts][records] into pinned memory, each record checked on the way, one copy in
+         const int n_oct = pyramid_octaves(q.H, q.W, c->up);
+         unsigned long long n_rec = 0;
+         for (int cnt : q.region_count) n_rec += (unsigned long long)cnt;
+         if (n_rec > 0x7fffffffull) throw HsError(HESAFF_ERR_CAPACITY, "more records in a chunk than 32-bit indices hold");
+         const size_t rec_at = describe_records_offset((int)nimg), bytes = rec_at + (size_t)n_rec * sizeof(hesaff_region);
+         c->pin_reg[slot].ensure_grow(bytes);
+         c->b_reg[slot].ensure_grow(bytes);
+         int32_t *starts = (int32_t *)c->pin_reg[slot].p;
+         hesaff_region *dst = (hesaff_region *)((char *)c->pin_reg[slot].p + rec_at);
+         size_t at = 0;
+         for (size_t b = 0; b < nimg; b++) {
+            starts[b] = (int32_t)at;
+            const hesaff_region *src = q.regions[b];
+            for (int i = 0; i < q.region_count[b]; i++) {
+               if (const char *why = describe_bad_record(src[i], q.from, n_oct)) {
+                  char msg[256];
+                  snprintf(msg, sizeof msg, "image %d: record %d: %s", q.index[b], i, why);
+                  throw HsError(HESAFF_ERR_ARG, msg);
+               }
+               dst[at + (size_t)i] = src[i];
+            }
+            at += (size_t)q.region_count[b];
+         }
+         starts[nimg] = (int32_t)at;
+         s->n_rec = (uint32_t)at;
+         HIP_TRY(hipMemcpyAsync(c->b_reg[slot].p, c->pin_reg[slot].p, bytes, hipMemcpyHostToDevice, c->h2d_stream));
+      }
       HIP_TRY(hipMemcpyAsync(q.blob_bytes ? c->b_jcoef[slot].p : c->b_in2[slot].p, c->pin_in[slot].p, total, hipMemcpyHostToDevice, c->h2d_stream));
       HIP_TRY(hipEventRecord(c->ev_h2d[slot], c->h2d_stream));
       io.staged(q);
@@ -427,7 +491,8 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
             if (q.blob_bytes) jpeg_pixels(c, c->b_jcoef[slot].as<uint8_t>(), make_jpeg_geom(q.jpeg), B, (uint8_t *)c->b_in2[slot].p, img_bytes, c->stream);
             const SrcImages src = q.f32 ? SrcImages::f32(c->b_in2[slot].p, (long long)img_bytes, (int)row_bytes)
                                         : SrcImages::u8(c->b_in2[slot].p, q.ch, (long long)img_bytes, (int)row_bytes);
-            run_batch(c, src, B, q.H, q.W);
+            if (q.from) run_describe(c, src, B, q.H, q.W, (const uint8_t *)c->b_reg[slot].p, cur->n_rec, q.from);
+            else run_batch(c, src, B, q.H, q.W);
          } catch (const HsError &e) {
             // this chunk's images cannot be planned (geometry) or exceed the planned keypoint capacity: that is about these
             // images, not about the device.  Both are thrown with the main stream idle; the other chunks go on when the
@@ -585,14 +650,16 @@ void check_device_f32(hesaff_ctx *c, int n, const uint8_t *d, long long img_stri
 // The body of the six host-image entry points: the list is validated, cut into chunks (ArrayIO), given its consumer - set_consumer
 // fills in `results`, `region_results` or `sink` + `user` - and run through the chunk engine with `ring` result blocks.
 // images: n pointers to 8-bit images (const uint8_t *const *, with `channels`) or, f32, to float planes (const float *const *).
+struct DescribeInput { const hesaff_region *const *regions = nullptr; const int *counts = nullptr; int from = 0; };
 template <class CONSUMER>
 void detect_images(hesaff_ctx *c, int n, const void *images, bool f32, const int *widths, const int *heights, const int *strides, const int *channels,
-                   int ring, CONSUMER set_consumer)
+                   int ring, CONSUMER set_consumer, const DescribeInput &di = DescribeInput())
 {
    std::vector<const uint8_t *> planes;
    if (f32) planes = validate_f32_list(n, (const float *const *)images, widths, heights, strides);
    else validate_image_list(n, (const uint8_t *const *)images, widths, heights, strides, channels);
-   ArrayIO io(&c->ring, c->par.max_batch, n, f32 ? planes.data() : (const uint8_t *const *)images, widths, heights, strides, channels, f32);
+   ArrayIO io(&c->ring, c->par.max_batch, n, f32 ? planes.data() : (const uint8_t *const *)images, widths, heights, strides, channels, f32,
+              di.regions, di.counts, di.from);
    set_consumer(io);
    run_chunks(c, io, ring);
    if (io.sink_rc.load() != 0) throw HsError(HESAFF_ERR_IO, "the result sink reported an error");
@@ -656,6 +723,44 @@ int hesaff_detect_regions_f32(hesaff_ctx *c, int n, const float *const *images, 
    if (!c || n < 0 || (n > 0 && (!images || !widths || !heights || !results))) return HESAFF_ERR_ARG;
    HS_API_BEGIN
    detect_images(c, n, images, true, widths, heights, strides, nullptr, 0, [&](ArrayIO &io) { io.region_results = results; });
+   HS_API_END(c)
+}
+
+// ---- hesaff_describe_regions: the chunks of hesaff_detect_regions with the caller's records in the place of detection's ----
+} // extern "C"
+namespace {
+DescribeInput describe_input(int n, const hesaff_region *const *regions, const int *counts, int from)
+{
+   if (from != HESAFF_FROM_POINTS && from != HESAFF_FROM_SHAPES) throw HsError(HESAFF_ERR_ARG, "from must be HESAFF_FROM_POINTS (1) or HESAFF_FROM_SHAPES (2)");
+   for (int j = 0; j < n; j++) {
+      char msg[128];
+      if (counts[j] < 0) { snprintf(msg, sizeof msg, "image %d: negative record count", j); throw HsError(HESAFF_ERR_ARG, msg); }
+      if (counts[j] > 0 && !regions[j]) { snprintf(msg, sizeof msg, "image %d: %d records but no record pointer", j, counts[j]); throw HsError(HESAFF_ERR_ARG, msg); }
+   }
+   DescribeInput di;
+   di.regions = regions; di.counts = counts; di.from = from;
+   return di;
+}
+} // namespace
+extern "C" {
+
+int hesaff_describe_regions(hesaff_ctx *c, int n, const uint8_t *const *images, const int *widths, const int *heights, const int *strides,
+                            const int *channels, const hesaff_region *const *regions, const int *counts, int from, hesaff_region_result *results)
+{
+   if (!c || n < 0 || (n > 0 && (!images || !widths || !heights || !regions || !counts || !results))) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   const DescribeInput di = describe_input(n, regions, counts, from);
+   detect_images(c, n, images, false, widths, heights, strides, channels, 0, [&](ArrayIO &io) { io.region_results = results; }, di);
+   HS_API_END(c)
+}
+
+int hesaff_describe_regions_f32(hesaff_ctx *c, int n, const float *const *images, const int *widths, const int *heights, const int *strides,
+                                const hesaff_region *const *regions, const int *counts, int from, hesaff_region_result *results)
+{
+   if (!c || n < 0 || (n > 0 && (!images || !widths || !heights || !regions || !counts || !results))) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   const DescribeInput di = describe_input(n, regions, counts, from);
+   detect_images(c, n, images, true, widths, heights, strides, nullptr, 0, [&](ArrayIO &io) { io.region_results = results; }, di);
    HS_API_END(c)
 }
 

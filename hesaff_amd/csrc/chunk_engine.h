@@ -67,6 +67,11 @@ struct HostChunk {                // at most max_batch images of one geometry
    size_t blob_bytes = 0;         // 0: data[b] are pixels
    hesaff_jpeg_layout jpeg = {};
    bool pinned = false;           // every data[b] is page-locked memory of the context (PinHooks): copied to the device from where it is
+   // hesaff_describe_regions: the caller's records travel with their images (from = HESAFF_FROM_POINTS / HESAFF_FROM_SHAPES; 0: a
+   // chunk to detect on).  regions[b] may be null when region_count[b] is 0.
+   int from = 0;
+   std::vector<const hesaff_region *> regions;
+   std::vector<int> region_count;
 };
 
 // Page-locked host buffers for the images a FileIO reads (the context's hipHostMalloc behind two plain function pointers: nothing here
@@ -154,7 +159,7 @@ struct ArrayIO : ChunkIO {
    hesaff_region_result *region_results = nullptr;   // hesaff_detect_regions: filled in place (instead of results)
    std::atomic<int> sink_rc{0};                 // written by done() on the caller's thread, read by next() on the staging thread
    ArrayIO(BlockRing *ring_, int max_batch, int n, const uint8_t *const *images, const int *widths, const int *heights, const int *strides,
-           const int *channels, bool f32 = false)
+           const int *channels, bool f32 = false, const hesaff_region *const *regions = nullptr, const int *counts = nullptr, int from = 0)
       : ring(ring_)
    {
       std::vector<char> taken((size_t)n, 0);
@@ -182,12 +187,13 @@ struct ArrayIO : ChunkIO {
          size_t g0 = 0;
          for (size_t sz : sizes) {
             HostChunk k;
-            k.W = W; k.H = H; k.ch = ch; k.f32 = f32;
+            k.W = W; k.H = H; k.ch = ch; k.f32 = f32; k.from = from;
             for (size_t g = g0; g < g0 + sz; g++) {
                const int j = grp[g];
                k.index.push_back(j);
                k.data.push_back(images[j]);
                k.stride.push_back(strides ? (size_t)strides[j] : (size_t)W * k.bpp());
+               if (from) { k.regions.push_back(regions[j]); k.region_count.push_back(counts[j]); }
             }
             chunks.push_back(std::move(k));
             g0 += sz;

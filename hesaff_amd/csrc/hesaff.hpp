@@ -10,7 +10,15 @@
 // (hesaff.cpp:66-105): onHessianKeypointDetected for every Hessian keypoint, followed at
 // once by onAffineShapeFound when findAffineShape converged.  The one difference: the
 // callbacks observe a chain that has already run - a callback cannot suppress or alter
-// the later stages, and `keys` is the same whatever the callbacks do.  The `blur` plane is
+// the later stages of THAT run, and its `keys` is the same whatever the callbacks do.  What
+// the reference lets a caller do by overriding or calling the two public callback members
+// of AffineHessianDetector (hesaff.cpp:66-105) - keep the strongest N keypoints and only
+// then find their shapes, describe the keypoints of another detector - is done here in two
+// steps: collect the records in the callbacks (or bring your own), choose, and hand what
+// was kept to onHessianKeypointsDetected (findAffineShape + the rest, hesaff.cpp:66-105) or
+// onAffineShapesFound (rectify, normalizeAffine, SIFT, hesaff.cpp:73-105), the batch forms
+// of those two members: they run the rest of the chain on the device for exactly the
+// records given and fill `keys` and the counters from them.  The `blur` plane is
 // a light handle (BlurPlane) instead of the cv::Mat; its pixels are those of
 // hesaff_stage_pyramid's plane of that octave and level (hesaff_stage_pyramid_f32's for float input).
 // detectPyramidKeypoints takes the reference's own input, a CV_32FC1 plane (pyramid.h:73), or
@@ -128,6 +136,47 @@ struct AffineHessianDetector {
       replay(r);
    }
 
+   // The batch forms of the reference's two public callback members (hesaff.cpp:66-71 and :73-105) for one image: the rest of the
+   // chain for the caller's records (hesaff_describe_regions).  image: the image the keypoints belong to, as detectPyramidKeypoints
+   // takes it.  records: hesaff_region, e.g. region() of what a callback received, or rows of hesaff_detect_regions; which fields are
+   // read, and which values are refused (std::runtime_error naming the record), is in include/hesaff_amd.h.  keys is replaced by the
+   // descriptors of these records, in their order; g_numberOfPoints = records.size(), g_numberOfAffinePoints grows by keys.size() -
+   // as detectPyramidKeypoints leaves them.  described (optional) receives the records with a11..a22, iters, outcome and key
+   // filled in.  The callbacks set on this detector are not called: the caller made these calls itself.
+   // == onHessianKeypointDetected(blur, x, y, s, pixelDistance, type, response) per record, blur = the plane (octave, level)
+   void onHessianKeypointsDetected(const uint8_t *image, int width, int height, int channels, const std::vector<hesaff_region> &records,
+                                   std::vector<hesaff_region> *described = nullptr)
+   {
+      describe(image, width, height, channels, records, HESAFF_FROM_POINTS, described);
+   }
+   void onHessianKeypointsDetected(const float *image, int width, int height, size_t strideBytes, const std::vector<hesaff_region> &records,
+                                   std::vector<hesaff_region> *described = nullptr)
+   {
+      describe_f32(image, width, height, strideBytes, records, HESAFF_FROM_POINTS, described);
+   }
+   // == onAffineShapeFound(blur, x, y, s, pixelDistance, a11, a12, a21, a22, type, response, iters) per record (U not rectified)
+   void onAffineShapesFound(const uint8_t *image, int width, int height, int channels, const std::vector<hesaff_region> &records,
+                            std::vector<hesaff_region> *described = nullptr)
+   {
+      describe(image, width, height, channels, records, HESAFF_FROM_SHAPES, described);
+   }
+   void onAffineShapesFound(const float *image, int width, int height, size_t strideBytes, const std::vector<hesaff_region> &records,
+                            std::vector<hesaff_region> *described = nullptr)
+   {
+      describe_f32(image, width, height, strideBytes, records, HESAFF_FROM_SHAPES, described);
+   }
+   // the record of a keypoint as the callbacks received it (a11..a22 / iters: leave at 0 for onHessianKeypointsDetected)
+   static hesaff_region region(const BlurPlane &blur, float x, float y, float s, int type, float response, float a11 = 0.0f, float a12 = 0.0f,
+                               float a21 = 0.0f, float a22 = 0.0f, int iters = 0)
+   {
+      hesaff_region g = {};
+      g.x = x; g.y = y; g.s = s; g.pixelDistance = blur.pixelDistance; g.response = response;
+      g.type = type; g.octave = blur.octave; g.level = blur.level;
+      g.a11 = a11; g.a12 = a12; g.a21 = a21; g.a22 = a22; g.iters = iters;
+      g.key = -1;
+      return g;
+   }
+
    // hesaff.cpp:107-130
    void exportKeypoints(std::ostream &out)
    {
@@ -146,6 +195,32 @@ struct AffineHessianDetector {
       g_numberOfPoints = count_hessian;
       g_numberOfAffinePoints += count_desc;   // the reference never resets this counter (hesaff.cpp:166)
       keys.assign(k, k + count_desc);
+   }
+   void taken(const hesaff_region_result &r, std::vector<hesaff_region> *described)
+   {
+      take(r.count_hessian, r.count_desc, r.keys);
+      if (described) described->assign(r.regions, r.regions + r.count_hessian);   // (count 0: regions is null, the range empty)
+   }
+   void describe(const uint8_t *image, int width, int height, int channels, const std::vector<hesaff_region> &records, int from,
+                 std::vector<hesaff_region> *described)
+   {
+      const int stride = width * channels, count = (int)records.size();
+      const hesaff_region *recs = records.data();
+      hesaff_region_result r;
+      if (hesaff_describe_regions(ctx_, 1, &image, &width, &height, &stride, &channels, &recs, &count, from, &r) != HESAFF_OK)
+         throw std::runtime_error(hesaff_last_error(ctx_));
+      taken(r, described);
+   }
+   void describe_f32(const float *image, int width, int height, size_t strideBytes, const std::vector<hesaff_region> &records, int from,
+                     std::vector<hesaff_region> *described)
+   {
+      if (strideBytes > (size_t)0x7fffffff) throw std::invalid_argument("row stride too large");
+      const int stride = strideBytes ? (int)strideBytes : width * 4, count = (int)records.size();
+      const hesaff_region *recs = records.data();
+      hesaff_region_result r;
+      if (hesaff_describe_regions_f32(ctx_, 1, &image, &width, &height, &stride, &recs, &count, from, &r) != HESAFF_OK)
+         throw std::runtime_error(hesaff_last_error(ctx_));
+      taken(r, described);
    }
    void replay(const hesaff_region_result &r)
    {

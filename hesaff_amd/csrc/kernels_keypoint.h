@@ -343,7 +343,9 @@ __device__ __forceinline__ int hs_window_p0(float s, float mrSize)
 // affine iteration.  rows[b] += P for every Hessian keypoint whose window falls into the last bin.
 // rows[nimg + 1] (one past the per-image sums) receives the largest such P of the batch: the row kernel's LDS is sized for the
 // windows that exist, not for the largest the image could hold.
-__global__ __launch_bounds__(256) void k_image_large_rows(HessList hl, const uint32_t *__restrict__ n_ptr, float mrSize, uint32_t *__restrict__ rows, int nimg);
+// A window wider than the tabulated taps (max_p0) is never extracted (k_prepare_patch rejects it): it adds no rows.
+__global__ __launch_bounds__(256) void k_image_large_rows(HessList hl, const uint32_t *__restrict__ n_ptr, float mrSize, uint32_t *__restrict__ rows, int nimg,
+                                                          int max_p0);
 
 template <bool RECTIFY>
 __device__ __forceinline__ void hs_prepare_patch_body(const HessList &hl, uint32_t h_lo, uint32_t n, const AffineOut &aff, int imRows, int imCols,
@@ -396,14 +398,15 @@ __device__ __forceinline__ void hs_prepare_patch_body(const HessList &hl, uint32
    }
 }
 
-__global__ __launch_bounds__(256) void k_image_large_rows(HessList hl, const uint32_t *__restrict__ n_ptr, float mrSize, uint32_t *__restrict__ rows, int nimg)
+__global__ __launch_bounds__(256) void k_image_large_rows(HessList hl, const uint32_t *__restrict__ n_ptr, float mrSize, uint32_t *__restrict__ rows, int nimg,
+                                                          int max_p0)
 {
    const uint32_t n = min(*n_ptr, hl.cap);
    for (uint32_t h = blockIdx.x * blockDim.x + threadIdx.x; h < n; h += gridDim.x * blockDim.x) {
       const int P0 = hs_window_p0(hl.s[h], mrSize);
       const float scale = (float)P0 / (float)HS_PATCH;
       const int P = ((double)scale > 0.4) ? P0 + 2 : 0;
-      if (hs_patch_bin(P) == HS_NBINS - 1 && P0 < (1 << 20)) {
+      if (hs_patch_bin(P) == HS_NBINS - 1 && P0 < (1 << 20) && P0 <= max_p0) {
          atomicAdd(rows + (hl.meta[h] >> 8), (uint32_t)P);
          atomicMax(rows + nimg + 1, (uint32_t)P);
       }
@@ -518,6 +521,47 @@ __global__ __launch_bounds__(256) void k_pack_regions(HessList hl, uint32_t n, A
       o[1] = make_uint4(__float_as_uint(hl.response[h]), (uint32_t)type, (uint32_t)octave, (uint32_t)level);
       o[2] = U;
       o[3] = make_uint4(iters, outcome, key, 0u);
+   }
+}
+
+// ---------------------------------------------------------------------------------------
+// k_ingest_regions: the other direction (hesaff_describe_regions).  The caller's hesaff_region records of a chunk - image
+// after image, starts[b] .. starts[b + 1] those of image b - become the Hessian list the detector would have left:
+// x, y, s, response and meta = image << 8 | octave << 4 | level << 2 | type.  With `shapes` (HESAFF_FROM_SHAPES) the
+// affine stage's output is written as well, as if findAffineShape had converged on the caller's U (hesaff.cpp:73-105
+// entered directly).  Also sets what run_detection's ordering step leaves behind: the list's length and the per-image starts.
+// The host has checked every record (describe_bad_record): what arrives here is finite and in range.  Octave and level
+// are not used for addressing after a HESAFF_FROM_SHAPES ingest; fields the record format cannot hold are taken as 0.
+// A lane per record: four 16-byte loads cover its 64 bytes (a wavefront reads 4 KB back to back), and every store is a
+// coalesced run of one structure-of-arrays column.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_ingest_regions(const uint4 *__restrict__ recs, uint32_t n, const int32_t *__restrict__ starts, int nimg,
+                                                        int shapes, HessList hl, AffineOut aff, uint32_t *__restrict__ n_hess,
+                                                        int32_t *__restrict__ hess_starts)
+{
+   const uint32_t t0 = blockIdx.x * blockDim.x + threadIdx.x;
+   if (t0 <= (uint32_t)nimg) hess_starts[t0] = starts[t0];
+   if (t0 == 0) *n_hess = n;
+   for (uint32_t h = t0; h < n; h += gridDim.x * blockDim.x) {
+      const uint4 *r = recs + 4 * (size_t)h;
+      const uint4 q0 = r[0], q1 = r[1];
+      // the image of record h: the last b with starts[b] <= h (empty images share a start with their successor)
+      int lo = 0, hi = nimg;
+      while (hi - lo > 1) {
+         const int mid = (lo + hi) >> 1;
+         if ((uint32_t)starts[mid] <= h) lo = mid; else hi = mid;
+      }
+      const uint32_t octave = q1.z < (uint32_t)HS_MAX_OCTAVES ? q1.z : 0u, level = q1.w < 4u ? q1.w : 0u, type = q1.y & 3u;
+      hl.x[h] = __uint_as_float(q0.x); hl.y[h] = __uint_as_float(q0.y); hl.s[h] = __uint_as_float(q0.z);
+      hl.response[h] = __uint_as_float(q1.x);
+      hl.meta[h] = (int32_t)(((uint32_t)lo << 8) | (octave << 4) | (level << 2) | type);
+      hl.r0c0[h] = 0;
+      if (shapes) {
+         const uint4 q2 = r[2], q3 = r[3];
+         *reinterpret_cast<uint4 *>(aff.U + 4 * (size_t)h) = q2;
+         aff.converged[h] = 1;
+         aff.iters[h] = (int32_t)q3.x;
+      }
    }
 }
 

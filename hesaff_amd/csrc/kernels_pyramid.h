@@ -23,6 +23,57 @@ __global__ __launch_bounds__(256) void k_gray(const uint8_t *__restrict__ src, i
 }
 
 // ---------------------------------------------------------------------------------------
+// k_gray_plane: the float grey plane alone, for a batch that needs no scale space (hesaff_describe_regions with
+// HESAFF_FROM_SHAPES: normalizeAffine samples the image, nothing else).  The same values the fused initial blur
+// (k_blur_hess_march with SRC_U8 / SRC_F32) writes into the grey plane: hesaff.cpp:145 for bytes, the caller's floats as
+// they are.  FORMAT: 0 one byte per pixel, 1 three interleaved bytes, 2 float.
+// A thread takes four neighbouring pixels: one 4-, 12- or 16-byte read when the source address allows it (a packed row of
+// an odd width does not start aligned: such rows are read element by element), one 16-byte store (plane rows are 256-byte aligned).
+// grid (ceil(cols / 1024), rows, B), block 256.
+// ---------------------------------------------------------------------------------------
+template <int FORMAT>
+__global__ __launch_bounds__(256) void k_gray_plane(const uint8_t *__restrict__ src, long long src_img_stride, int src_row_stride, DPlane dst)
+{
+   const int c0 = (blockIdx.x * 256 + threadIdx.x) * 4;
+   const int r = blockIdx.y, b = blockIdx.z;
+   if (c0 >= dst.cols) return;
+   constexpr int BPP = FORMAT == 0 ? 1 : (FORMAT == 1 ? 3 : 4);
+   const uint8_t *p = src + (long long)b * src_img_stride + (long long)r * src_row_stride + (long long)c0 * BPP;
+   float *o = dst.img(b) + (long long)r * dst.pitch + c0;
+   const bool whole = c0 + 3 < dst.cols;
+   float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+   if (whole && (reinterpret_cast<uintptr_t>(p) & (FORMAT == 2 ? 15u : 3u)) == 0u) {
+      if (FORMAT == 0) {
+         const uint32_t q = *reinterpret_cast<const uint32_t *>(p);
+#pragma unroll
+         for (int m = 0; m < 4; m++) v[m] = (float)((q >> (8 * m)) & 255u);   // (float(c) + c + c) / 3.0f == float(c) exactly
+      } else if (FORMAT == 1) {
+         const uint32_t q0 = reinterpret_cast<const uint32_t *>(p)[0], q1 = reinterpret_cast<const uint32_t *>(p)[1],
+                        q2 = reinterpret_cast<const uint32_t *>(p)[2];
+         const uint32_t by[12] = {q0 & 255u, (q0 >> 8) & 255u, (q0 >> 16) & 255u, q0 >> 24, q1 & 255u, (q1 >> 8) & 255u,
+                                  (q1 >> 16) & 255u, q1 >> 24, q2 & 255u, (q2 >> 8) & 255u, (q2 >> 16) & 255u, q2 >> 24};
+#pragma unroll
+         for (int m = 0; m < 4; m++) v[m] = ((float)by[3 * m] + (float)by[3 * m + 1] + (float)by[3 * m + 2]) / 3.0f;   // hesaff.cpp:145
+      } else {
+         const float4 q = *reinterpret_cast<const float4 *>(p);
+         v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+      }
+   } else {
+#pragma unroll
+      for (int m = 0; m < 4; m++) {
+         if (c0 + m >= dst.cols) break;
+         const uint8_t *e = p + m * BPP;
+         if (FORMAT == 0) v[m] = (float)e[0];
+         else if (FORMAT == 1) v[m] = ((float)e[0] + (float)e[1] + (float)e[2]) / 3.0f;
+         else v[m] = *reinterpret_cast<const float *>(e);   // (rows of float planes are 4-byte aligned: the entry points check it)
+      }
+   }
+   if (whole) *reinterpret_cast<float4 *>(o) = make_float4(v[0], v[1], v[2], v[3]);
+   else
+      for (int m = 0; m < 4 && c0 + m < dst.cols; m++) o[m] = v[m];
+}
+
+// ---------------------------------------------------------------------------------------
 // k_check_f32: the value check of hesaff_detect_batch_device_f32, run before any kernel reads the caller's float planes
 // as an image: flags[b] = 1 when image b holds a pixel outside the accepted domain (NaN, +-Inf, |v| > 2^20; the header
 // says why).  Read-only over the planes; the flag is a plain vector store (every writer stores the same 1, the host

@@ -336,6 +336,8 @@ struct hesaff_ctx {
    // staging + H2D of chunk i+1 and D2H of chunk i-1 run beside the kernels of chunk i
    DevBuf b_in2[2], b_outstage[2];
    PinBuf pin_in[2];
+   PinBuf pin_reg[2];       // hesaff_describe_regions: a chunk's record starts + records, staged per input slot ...
+   DevBuf b_reg[2];         // ... and on the device (run_describe's d_block)
    // Page-locked buffers the readers of hesaff_process_files fill directly (chunk_engine.h: PinHooks): handed out by size, taken back
    // when their image is on the device, kept pinned from one list to the next (pinning costs 0.1 ms per MB), released with the context.
    // At most kPinReadBytes are out or parked; a request beyond that gets nullptr (the image then takes the staging copy).
@@ -999,17 +1001,23 @@ void run_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float *
 
 // The scale-space + detection part for the current plan; fills the ordered Hessian list.
 // src: the B device images of the batch (SrcImages: 8-bit with 1 or 3 interleaved channels, or float planes).
-void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, StageTimer &tm, bool keep_all_planes, float *planes_out)
+// detect = false (hesaff_describe_regions): the scale space alone - the grey plane and every level findAffineShape can be asked to run
+// on (L0..L2 of each octave; L3 only as the source of the next octave) - with no response plane, no extrema scan, no localisation and
+// no ordering; the counters and the Hessian list are then the caller's business (ingest_regions).
+void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, StageTimer &tm, bool keep_all_planes, float *planes_out,
+                   bool detect = true)
 {
    const hesaff::OctaveSchedule &sc = c->sched;
    hipStream_t st = c->stream;
    uint32_t *cnt = s.counters;
    const float *ptaps = c->t_pyr_taps.as<float>();
-   HIP_TRY(hipMemsetAsync(cnt, 0, 64 * 4, st));
-   HIP_TRY(hipMemsetAsync(c->geo.b_bitmask.p, 0, std::max<size_t>((size_t)B * c->words_per_image * 8, 8), st));
-   // octaveMap (pyramid.cpp:226: zeroed per octave): the order-key map is filled with "free" when it is new; every pass over an octave then bids
-   // with keys of a fresh, smaller epoch (OctaveCtx::map_epoch), so what earlier passes left behind never wins - no fill and no reset per octave
-   if (!c->map_clean) { HIP_TRY(hipMemsetAsync(c->geo.b_map.p, 0xFF, c->geo.b_map.bytes, st)); c->map_epoch = c->map_kbits < 32 ? (0xffffffffu >> c->map_kbits) : 0u; c->map_clean = true; }
+   if (detect) {
+      HIP_TRY(hipMemsetAsync(cnt, 0, 64 * 4, st));
+      HIP_TRY(hipMemsetAsync(c->geo.b_bitmask.p, 0, std::max<size_t>((size_t)B * c->words_per_image * 8, 8), st));
+      // octaveMap (pyramid.cpp:226: zeroed per octave): the order-key map is filled with "free" when it is new; every pass over an octave then bids
+      // with keys of a fresh, smaller epoch (OctaveCtx::map_epoch), so what earlier passes left behind never wins - no fill and no reset per octave
+      if (!c->map_clean) { HIP_TRY(hipMemsetAsync(c->geo.b_map.p, 0xFF, c->geo.b_map.bytes, st)); c->map_epoch = c->map_kbits < 32 ? (0xffffffffu >> c->map_kbits) : 0u; c->map_clean = true; }
+   }
 
    int t = tm.begin(T_PYR);
    DPlane none = make_plane(nullptr, 0, 0, 0);
@@ -1071,12 +1079,21 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
       // R0 = hessianResponse(L0) (pyramid.cpp:230) is fused into the first blur launch when the
       // marching kernel handles it (default sigmas: K = 9); otherwise a separate pass.
       const bool fuse_r0 = c->pyr_march;
-      if (!fuse_r0) {
+      if (!fuse_r0 && detect) {
          const dim3 grid((g.cols + 255) / 256, g.rows, B);
          hipLaunchKernelGGL(k_hess, grid, dim3(256), 0, st, Lo[0], Ro[0], sc.norm2[0]);
       }
       const bool has_next = o + 1 < c->oct.size();
-      for (int i = 1; i <= 4; i++) {
+      for (int i = 1; i <= 4 && !detect; i++) {
+         // the blurs alone: L1, L2, and - when an octave follows - its first level, the decimated L3 (which itself is not kept)
+         if (i == 4 || (i == 3 && !has_next)) break;
+         const float *taps = ptaps + c->pyr_tap_off[i];
+         const int tb = tm.begin(T_BLURHESS, (i == 3 ? 5.0 : 8.0) * (double)B * g.rows * g.cols);
+         if (i < 3) launch_blur_hess<true, false, false>(c, Lo[i - 1], Lo[i], none, none, taps, c->pyr_K[i], 0.0f, B);
+         else launch_blur_hess<false, false, true>(c, Lo[2], none, none, c->L[(o + 1) * 3], taps, c->pyr_K[i], 0.0f, B);
+         tm.end(tb);
+      }
+      for (int i = 1; i <= 4 && detect; i++) {
          // algorithmic bytes of this launch: 12 N, + 8 N when it also produces R0
          // (read L0 + write R0 of the stand-alone pass), + 2 N for the fused decimation
          double bytes = 12.0 * (double)B * g.rows * g.cols;
@@ -1108,6 +1125,7 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
             pout += (size_t)g.rows * g.cols;
          }
       }
+      if (!detect) continue;
       // ---- detection on this octave ----
       t = tm.begin(T_DET);
       HIP_TRY(hipMemsetAsync(cnt + 0, 0, 4, st));
@@ -1142,6 +1160,7 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
       }
       tm.end(t);
    }
+   if (!detect) return;
    // ---- ordering ----
    t = tm.begin(T_DET);
    const long long total_words = (long long)B * c->words_per_image;
@@ -1158,7 +1177,7 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
    // per image: upper bound of the T' rows its huge windows (P > 512) need, known from the scales alone
    HIP_TRY(hipMemsetAsync(c->geo.b_starts.as<int32_t>() + 2 * (B + 1), 0, (size_t)(B + 2) * 4, st));
    hipLaunchKernelGGL(k_image_large_rows, dim3(512), dim3(256), 0, st, s.hl, (const uint32_t *)(cnt + 3), c->consts.mrSize,
-                      c->geo.b_starts.as<uint32_t>() + 2 * (B + 1), B);
+                      c->geo.b_starts.as<uint32_t>() + 2 * (B + 1), B, c->max_p0);
    tm.end(t);
 }
 
@@ -1225,35 +1244,38 @@ void ensure_group_buffers(hesaff_ctx *c, uint32_t n)
    if (c->b_siftvo2.p != before || c->b_siftvo2.bytes != bytes_before) HIP_TRY(hipMemsetAsync(c->b_siftvo2.p, 0, c->b_siftvo2.bytes, c->stream));
 }
 
-// Whole hot path on a device-resident batch.  Leaves ordered KeyRec records in b_out and
-// per-image start offsets (hessian: b_starts[0..B], desc: b_starts[B+1..2B+1]).
-void run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
+// The host round trip of a batch: the per-image Hessian starts and the large-window row bounds (b_starts, 3 (B + 1) + 1 words)
+// into pinned memory; the caller's thread sleeps until everything before it on the main stream has run.
+const int32_t *fetch_hessian_starts(hesaff_ctx *c, int B)
 {
-   plan(c, B, H, W);
-   c->ev_used = 0;
-   StageTimer tm(c);
-   Lists s = make_lists(c);
+   hipStream_t st = c->stream;
+   int32_t *hs = (int32_t *)c->h_small_mid.ensure_small(((size_t)3 * (B + 1) + 1) * 4);
+   HIP_TRY(hipMemcpyAsync(hs, c->geo.b_starts.p, ((size_t)3 * (B + 1) + 1) * 4, hipMemcpyDeviceToHost, st));
+   HIP_TRY(hipEventRecord(c->ev_detect_done, st));
+   const double dbg_ca = c->debug ? thread_cpu_ms() : 0.0;
+   hs_wait_event(c->ev_detect_done);   // sleeps: no core spins while the detection stage runs
+   if (c->debug) fprintf(stderr, "[hesaff] run_batch: caller's CPU inside the wait for the detection stage %.2f ms\n", thread_cpu_ms() - dbg_ca);
+   return hs;
+}
+
+// Everything after the Hessian list of a batch is complete - by detection (run_batch) or from the caller's records (run_describe):
+// affine shape, patches and descriptors over image groups on three streams, the stable compaction into KeyRec records, the
+// descriptor starts, and the wait for the end of the batch.  hs: fetch_hessian_starts' block.  with_affine = false: the affine
+// output is already in place (HESAFF_FROM_SHAPES), k_affine is not launched.  The affine stream starts behind ev_detect_done,
+// which the caller has recorded after the last kernel that writes a plane k_affine reads.
+void run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, int tt, int B, int H, int W, const int32_t *hs, bool with_affine)
+{
    hipStream_t st = c->stream;
    uint32_t *cnt = s.counters;
-   const int tt = tm.begin(T_TOTAL);
-   run_detection(c, src, B, s, tm, false, nullptr);
-
    int t;
    PlaneTab pt;
    memset(&pt, 0, sizeof pt);
-   uint32_t n_hess_host = 0;   // Hessian keypoints of the batch (known after the host round trip below)
+   uint32_t n_hess_host = 0;   // Hessian keypoints of the batch
    for (size_t o = 0; o < c->oct.size(); o++)
       for (int l = 0; l < 3; l++) pt.L[o][l] = c->L[o * 3 + l];
    {
-      // The one host round trip of a batch: per-image Hessian counts + large-window row bounds.  The bin kernels
-      // only extract the 41x41 patches (to HBM); the descriptor runs as four kernels with the parallel axis each
+      // The bin kernels only extract the 41x41 patches (to HBM); the descriptor runs as four kernels with the parallel axis each
       // part wants (kernels_sift.h).  Images are processed in groups so that the patch buffers stay bounded.
-      int32_t *hs = (int32_t *)c->h_small_mid.ensure_small(((size_t)3 * (B + 1) + 1) * 4);
-      HIP_TRY(hipMemcpyAsync(hs, c->geo.b_starts.p, ((size_t)3 * (B + 1) + 1) * 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipEventRecord(c->ev_detect_done, st));
-      const double dbg_ca = c->debug ? thread_cpu_ms() : 0.0;
-      hs_wait_event(c->ev_detect_done);   // sleeps: no core spins while the detection stage runs
-      if (c->debug) fprintf(stderr, "[hesaff] run_batch: caller's CPU inside the wait for the detection stage %.2f ms\n", thread_cpu_ms() - dbg_ca);
       if ((uint32_t)hs[B] > c->cap) throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded; raise hesaff_params.max_kpts_per_mpx");
       n_hess_host = (uint32_t)hs[B];
       const uint32_t *lrows = (const uint32_t *)hs + 2 * (B + 1);
@@ -1285,8 +1307,9 @@ void run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
       //   streams, latency-bound)  |  descriptor kernels of the groups before (sift_stream).
       // Three patch buffer slots rotate.
       hipStream_t as = c->no_overlap ? st : c->aff_stream;
-      if (as != st) HIP_TRY(hipStreamWaitEvent(as, c->ev_detect_done, 0));
+      if (as != st && with_affine) HIP_TRY(hipStreamWaitEvent(as, c->ev_detect_done, 0));
       auto launch_affine = [&](size_t gi) {
+         if (!with_affine) return;
          const int ta = tm.begin(T_AFF, 0, as);
          const uint32_t agrid = std::min<uint32_t>((groups[gi].hi - groups[gi].lo + HS_AFFP_G - 1) / HS_AFFP_G, (uint32_t)c->n_cu * HS_AFF_BLOCKS_PER_CU);
          hipLaunchKernelGGL(k_affine, dim3(agrid), dim3(64), 0, as, pt, s.hl, groups[gi].lo, groups[gi].hi, (const uint32_t *)(cnt + 3), c->tables, c->consts, s.ao);
@@ -1298,7 +1321,7 @@ void run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
       for (size_t gi = 0; gi < groups.size(); gi++) {
          const uint32_t h_lo = groups[gi].lo, h_hi = groups[gi].hi, n = h_hi - h_lo;
          if (gi + 1 < groups.size()) launch_affine(gi + 1);
-         if (as != st) HIP_TRY(hipStreamWaitEvent(st, c->ev_aff[gi], 0));
+         if (as != st && with_affine) HIP_TRY(hipStreamWaitEvent(st, c->ev_aff[gi], 0));
          const int slot = (int)(gi % HS_NSLOT);
          if (slot_used[slot]) HIP_TRY(hipStreamWaitEvent(st, c->ev_sift_done[slot], 0));   // the slot's previous descriptors are finished
          t = tm.begin(T_PATCH);
@@ -1350,6 +1373,61 @@ void run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
    if (cn[2] != 0 || (uint32_t)cn[1] > c->cap)
       throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded; raise hesaff_params.max_kpts_per_mpx");
    if (cn[6] != 0) throw HsError(HESAFF_ERR_NOMEM, "large-window row buffer exceeded (internal bound violated)");
+}
+
+// Whole hot path on a device-resident batch.  Leaves ordered KeyRec records in b_out and
+// per-image start offsets (hessian: b_starts[0..B], desc: b_starts[B+1..2B+1]).
+void run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
+{
+   plan(c, B, H, W);
+   c->ev_used = 0;
+   StageTimer tm(c);
+   Lists s = make_lists(c);
+   const int tt = tm.begin(T_TOTAL);
+   run_detection(c, src, B, s, tm, false, nullptr);
+   // the one host round trip of a batch
+   run_keypoint_stages(c, s, tm, tt, B, H, W, fetch_hessian_starts(c, B), true);
+}
+
+// hesaff_describe_regions on a device-resident chunk: the caller's records take the place of detection's list.  d_block (device,
+// 256-byte aligned): B + 1 record starts (int32, image b owns records starts[b] .. starts[b + 1]), then - describe_records_offset(B)
+// bytes in - the chunk's hesaff_region records, already checked by the host (describe_bad_record).  n_rec = starts[B].
+// from = HESAFF_FROM_POINTS: the scale space as detection builds it (which also yields the grey plane), then k_affine over the list.
+// from = HESAFF_FROM_SHAPES: the grey plane alone (parity mode) - fast mode 2 builds the scale space too, k_patch_pyramid samples it -
+// and the affine output from the records.  Leaves what run_batch leaves.
+inline size_t describe_records_offset(int B) { return (((size_t)B + 1) * 4 + 255) & ~(size_t)255; }
+void run_describe(hesaff_ctx *c, const SrcImages &src, int B, int H, int W, const uint8_t *d_block, uint32_t n_rec, int from)
+{
+   plan(c, B, H, W);
+   if (n_rec > c->cap) throw HsError(HESAFF_ERR_CAPACITY, "more records than the keypoint capacity; raise hesaff_params.max_kpts_per_mpx");
+   c->ev_used = 0;
+   StageTimer tm(c);
+   Lists s = make_lists(c);
+   hipStream_t st = c->stream;
+   uint32_t *cnt = s.counters;
+   const bool shapes = from == HESAFF_FROM_SHAPES;
+   const int tt = tm.begin(T_TOTAL);
+   HIP_TRY(hipMemsetAsync(cnt, 0, 64 * 4, st));
+   hipLaunchKernelGGL(k_ingest_regions, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((std::max<uint32_t>(n_rec, (uint32_t)B + 1) + 255) / 256, 4096u))), dim3(256), 0, st,
+                      (const uint4 *)(d_block + describe_records_offset(B)), n_rec, (const int32_t *)d_block, B, shapes ? 1 : 0, s.hl, s.ao,
+                      cnt + 3, c->geo.b_starts.as<int32_t>());
+   // per image: upper bound of the T' rows its huge windows (P > 512) need, from the scales alone
+   HIP_TRY(hipMemsetAsync(c->geo.b_starts.as<int32_t>() + 2 * (B + 1), 0, (size_t)(B + 2) * 4, st));
+   hipLaunchKernelGGL(k_image_large_rows, dim3(512), dim3(256), 0, st, s.hl, (const uint32_t *)(cnt + 3), c->consts.mrSize,
+                      c->geo.b_starts.as<uint32_t>() + 2 * (B + 1), B, c->max_p0);
+   // (the per-image counts are the caller's, but the row bounds are the device's: the round trip stays, behind two short kernels;
+   //  the planes below are enqueued after it and run while the groups are formed)
+   const int32_t *hs = fetch_hessian_starts(c, B);
+   if (!shapes || c->fast_pyramid) {
+      run_detection(c, src, B, s, tm, false, nullptr, false);
+   } else {
+      const dim3 grid((W + 1023) / 1024, H, B);
+      if (src.format == HS_SRC_F32) hipLaunchKernelGGL(k_gray_plane<2>, grid, dim3(256), 0, st, src.p, src.img_stride, src.row_stride, c->gray);
+      else if (src.format == HS_SRC_U8C3) hipLaunchKernelGGL(k_gray_plane<1>, grid, dim3(256), 0, st, src.p, src.img_stride, src.row_stride, c->gray);
+      else hipLaunchKernelGGL(k_gray_plane<0>, grid, dim3(256), 0, st, src.p, src.img_stride, src.row_stride, c->gray);
+   }
+   HIP_TRY(hipEventRecord(c->ev_detect_done, st));   // the affine stream starts behind the planes
+   run_keypoint_stages(c, s, tm, tt, B, H, W, hs, !shapes);
 }
 
 // ---- exportKeypoints on the device (kernels_export.h) ----

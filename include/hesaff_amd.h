@@ -39,7 +39,8 @@ extern "C" {
  * 8: this header (+ hesaff_region, hesaff_region_result, hesaff_detect_regions, hesaff_sizeof_region; no existing struct changed).
  *    Version 8 also carries the float-input entry points (hesaff_detect_batch_f32, hesaff_detect_batch_cb_f32, hesaff_detect_regions_f32,
  *    hesaff_detect_batch_device_f32, hesaff_stage_pyramid_f32): they add no struct and change none, so the version stays; a caller that
- *    needs them finds them by symbol (dlsym) in the library it loaded.
+ *    needs them finds them by symbol (dlsym) in the library it loaded.  The same holds for hesaff_describe_regions and
+ *    hesaff_describe_regions_f32 (HESAFF_FROM_POINTS / HESAFF_FROM_SHAPES): new symbols over the structs of version 8.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -223,7 +224,8 @@ typedef struct hesaff_region_result {
 /* hesaff_detect_batch that also returns every Hessian keypoint with what followed it (hesaff_region): the keypoints that got no
  * descriptor, the un-rectified U and iteration count of findAffineShape, and which row of keys each one became.  Same inputs, same
  * chunking and the same lifetime contract as hesaff_detect_batch; the records leave the device with the keys of their chunk.
- * The callbacks observe a chain that has already run: nothing a caller does with a record changes the later stages. */
+ * The callbacks observe a chain that has already run: nothing a caller does with a record changes the later stages.  What a
+ * caller kept of the records - or keypoints of its own - goes through the rest of the chain with hesaff_describe_regions below. */
 int hesaff_detect_regions(hesaff_ctx *ctx, int n, const uint8_t *const *images, const int *widths, const int *heights,
                           const int *strides, const int *channels, hesaff_region_result *results);
 
@@ -265,6 +267,58 @@ int hesaff_detect_regions_f32(hesaff_ctx *ctx, int n, const float *const *images
 int hesaff_detect_batch_device_f32(hesaff_ctx *ctx, int n, const void *d_planes, int width, int height, int row_stride,
                                    int64_t img_stride, int32_t *count_hessian, int32_t *count_desc, const void **d_keys_out,
                                    int64_t *total_out);
+
+/* ---- describe caller-supplied keypoints: the second half of the chain, entered where the reference's callbacks enter it ----
+ * replaces: a caller's own calls of the two public callback members of AffineHessianDetector - onHessianKeypointDetected
+ * (hesaff.cpp:66-71: findAffineShape on the blur plane, then hesaff.cpp:73-105 when it converges) and onAffineShapeFound
+ * (hesaff.cpp:73-105: rectify, normalizeAffine, SIFT) - for counts[i] records of image i, n images at once: what a subclass that keeps
+ * the strongest N keypoints (or those inside a mask) before findAffineShape does, and what a caller with a detector of its own does.
+ *   from = HESAFF_FROM_POINTS: as calling onHessianKeypointDetected(blur, x, y, s, pixelDistance, type, response) per record, with
+ *          blur = the scale-space plane (octave, level) of image i and pixelDistance that octave's own;
+ *   from = HESAFF_FROM_SHAPES: as calling onAffineShapeFound(blur, x, y, s, pixelDistance, a11, a12, a21, a22, type, response, iters)
+ *          per record (blur and pixelDistance are not used by hesaff.cpp:73-105).  No scale space is built in parity mode (fast = 0):
+ *          the grey plane is all normalizeAffine needs; fast = 2 builds it, because its larger windows are sampled from it.
+ * The input record is hesaff_region itself: what hesaff_detect_regions returned, whole or any subset in any order (a record given
+ * twice is described twice), goes straight back in.  Fields read: x, y, s, response, type always; octave, level with
+ * HESAFF_FROM_POINTS only (the indices hesaff_detect_regions reports; only planes the detector finds keypoints on: octave below the
+ * image's octave count, level 0..2); a11..a22 (U as onAffineShapeFound receives it, NOT rectified) and iters (echoed) with
+ * HESAFF_FROM_SHAPES only.  pixelDistance, outcome, key and reserved are ignored on input, and so are a11..a22 and iters with
+ * HESAFF_FROM_POINTS.  With HESAFF_FROM_SHAPES octave and level are echoed (taken as 0 when outside what a record can name, octave
+ * 0..15 and level 0..3).  Records that hesaff_detect_regions returned with outcome == 0 carry a zero U: drop them before
+ * HESAFF_FROM_SHAPES, which refuses them (below).
+ * Output: results[i] as hesaff_detect_regions fills it, same lifetime contract: count_hessian = counts[i]; regions[counts[i]] in the
+ * caller's order with pixelDistance = the octave's own value (pd0 * 2^octave, pd0 = 0.5 with upscaleInputImage, else 1), a11..a22,
+ * iters, outcome and key as hesaff_detect_regions defines them (HESAFF_FROM_SHAPES: U and iters echoed, outcome 1 or 2, never 0);
+ * keys[count_desc] in the caller's record order (keys.push_back in call order, hesaff.cpp:87).  counts[i] == 0: an empty result
+ * (regions[i] may then be NULL; results[i].regions is NULL).  Mixed image sizes and chunks of max_batch images as in
+ * hesaff_detect_regions; a chunk's records travel with its images (staged into pinned memory, one copy in).
+ * Refused (HESAFF_ERR_ARG; hesaff_last_error names the caller's image index and the first offending record of that image; the context
+ * stays usable): from not 1 or 2; counts[i] < 0, or regions[i] NULL with counts[i] > 0; type not in 0..2; octave or level outside
+ * the image's pyramid (HESAFF_FROM_POINTS); x, y, s or response not finite; |x| or |y| above 2^20; s not in (0, 2^20]; with
+ * HESAFF_FROM_SHAPES also an a_ij that is not finite or exceeds 2^20 in magnitude, and - evaluated in double -
+ * a11 * a22 - a12 * a21 == 0 or a11^2 + a12^2 == 0, the two divisors of rectifyAffineTransformationUpIsUp (helpers.cpp:90-97).
+ * More records in a chunk than the context's keypoint capacity for it (max_kpts_per_mpx): HESAFF_ERR_CAPACITY.
+ * The records are checked on the host while the staging thread copies them into pinned memory: no refused value reaches a kernel.
+ * Why the accepted ranges are safe: a position never forms an address unchecked - findAffineShape's taps (k_affine) and normalizeAffine's
+ * (the patch kernels) are either proven inside the plane by the four corners of their window (hs_window_outside, interpolateCheckBorders)
+ * or individually tested, an outside tap reading pixel (0, 0) and contributing 0 (helpers.cpp:227-240), and the tests are written so
+ * that a NaN or infinite coordinate counts as outside.  With |x|, |y|, s <= 2^20 and pixelDistance >= 0.5 the window coordinates of
+ * the first iteration stay below 2^45; later iterations may overflow U to infinity or NaN for absurd keypoints, which the tests above
+ * classify as outside, after which the iteration ends unconverged (as it does in the reference).  The window side 2 * int(ceil(s *
+ * mrSize)) + 1 is formed through a guard that saturates at 10^6 (hs_window_p0) and a window wider than the tabulated taps (about
+ * sqrt(width * height)) is rejected, not tabulated, so no scale sizes a buffer.  With HESAFF_FROM_SHAPES the rectified matrix
+ * (helpers.cpp:90-97) is finite or has infinite entries of a definite sign - never NaN, since both divisors are non-zero and every
+ * term is below 2^41 in double - and an infinite corner fails interpolateCheckBorders' comparisons, so such a record is rejected
+ * (outcome 1) like any window that leaves the image. */
+#define HESAFF_FROM_POINTS 1   /* = calling onHessianKeypointDetected per record: hesaff.cpp:66-71, then :73-105 when findAffineShape converges */
+#define HESAFF_FROM_SHAPES 2   /* = calling onAffineShapeFound per record: hesaff.cpp:73-105 (rectify, normalizeAffine, SIFT) */
+int hesaff_describe_regions(hesaff_ctx *ctx, int n, const uint8_t *const *images, const int *widths, const int *heights,
+                            const int *strides, const int *channels, const hesaff_region *const *regions, const int *counts, int from,
+                            hesaff_region_result *results);
+/* the same with float grey planes: input layout, accepted pixel values and their check as the other _f32 entry points */
+int hesaff_describe_regions_f32(hesaff_ctx *ctx, int n, const float *const *images, const int *widths, const int *heights,
+                                const int *strides, const hesaff_region *const *regions, const int *counts, int from,
+                                hesaff_region_result *results);
 
 /* Same path with inputs already resident in device memory (bench / pipelines that decode
  * on the GPU): d_gray = n contiguous height x width 8-bit grey planes (device pointer).

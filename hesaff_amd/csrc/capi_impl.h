@@ -59,8 +59,8 @@ void detect_device(hesaff_ctx *c, int n, const SrcImages &src, int height, int w
 {
    plan(c, c->par.max_batch, height, width);
    check_source();
-   run_batch(c, src, n, height, width);
-   const int32_t *hs = c->h_starts, *ds = c->h_starts + (n + 1);
+   const BatchResult r = run_batch(c, src, n, height, width);
+   const int32_t *hs = r.hessian_starts, *ds = r.desc_starts;
    for (int b = 0; b < n; b++) {
       if (count_hessian) count_hessian[b] = hs[b + 1] - hs[b];
       if (count_desc) count_desc[b] = ds[b + 1] - ds[b];
@@ -241,15 +241,10 @@ int hesaff_detect_batch_device(hesaff_ctx *c, int n, const void *d_gray, int wid
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Chunk engine: the host side of every entry point that takes host images (hesaff_detect_batch, hesaff_detect_batch_cb,
-// hesaff_process_files).  A ChunkIO hands over chunks of equally sized images one after the other and receives each
-// chunk's records when they are in host memory:
-//    staging thread :  io.next(chunk k+1) -> pixels into pinned memory -> H2D on its own stream -> io.staged()
-//    caller's thread:  kernels of chunk k (run_batch) ; io.done(chunk k-1) ; D2D + D2H of chunk k on a third stream
-// so the copy in of chunk k+1 and the copy out of chunk k-1 run beside the kernels of chunk k.  Pinned result memory:
-// ring == 0 keeps one block per chunk until the next call (hesaff_detect_batch's contract: every results[i].keys stays
-// valid); ring == N > 0 cycles through N blocks, and the consumer gives a block back (BlockRing::release) when it
-// has finished with the chunk (bounded host memory however long the list is).
+// Chunk engine: the device side of every entry point that takes host images or files (hesaff_detect_batch, _cb, _regions,
+// hesaff_describe_regions, hesaff_process_files).  The loop - which thread does what, in which order, and what happens
+// to a chunk that is refused - is run_chunk_loop (chunk_engine.h); ChunkDevice is what that loop drives: every HIP call
+// of a chunk, on the stream and the thread the loop's order puts it.
 // ------------------------------------------------------------------------------------------------------------------
 } // extern "C"
 
@@ -318,69 +313,67 @@ void ensure_copy_streams(hesaff_ctx *c)
       HIP_TRY(hipStreamCreateWithPriority(&c->h2d_stream, hipStreamNonBlocking, prio_greatest));
       HIP_TRY(hipStreamCreateWithPriority(&c->d2h_stream, hipStreamNonBlocking, prio_greatest));
    }
-   for (int i = 0; i < 2; i++) {
-      c->ev_h2d[i] = DevEvent(hipEventDisableTiming);
-      c->ev_h2d_blk[i] = DevEvent(hipEventDisableTiming | hipEventBlockingSync);
-      c->ev_in_free[i] = DevEvent(hipEventDisableTiming | hipEventBlockingSync);
-      c->ev_out_ready[i] = DevEvent(hipEventDisableTiming);
-      c->ev_d2h[i] = DevEvent(hipEventDisableTiming | hipEventBlockingSync);
-      for (int q = 0; q < 4; q++) c->ev_exp[i][q] = DevEvent(hipEventDefault);
+   for (hesaff_ctx::ChunkSlot &sl : c->slot) {
+      sl.ev_h2d = DevEvent(hipEventDisableTiming);
+      sl.ev_h2d_blk = DevEvent(hipEventDisableTiming | hipEventBlockingSync);
+      sl.ev_in_free = DevEvent(hipEventDisableTiming | hipEventBlockingSync);
+      sl.ev_out_ready = DevEvent(hipEventDisableTiming);
+      sl.ev_d2h = DevEvent(hipEventDisableTiming | hipEventBlockingSync);
+      for (DevEvent &e : sl.ev_exp) e = DevEvent(hipEventDefault);
    }
 }
 
-void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
-{
-   bind_device(c);
-   ensure_copy_streams(c);
-   struct State {
-      HostChunk q;
-      std::vector<int32_t> nh, nd;
-      std::vector<size_t> off;
-      std::vector<unsigned long long> toff;   // WANT_TEXT: byte offset of every image's rows
-      size_t text_at = 0, bin_at = 0;         // where the text / sidecar rows start inside the result block
-      size_t regions_at = 0;                  // WANT_REGIONS: where the hesaff_region records start
-      int total = 0, block = -1, no = 0, largest = 0;
-      uint32_t n_rec = 0;                     // hesaff_describe_regions: records of the chunk
-      bool copied = false;                    // a copy out was enqueued (ev_d2h of its slot is recorded)
-   };
-   const int wants = io.wants();
-   c->ring.reset(ring);
-   if (ring > 0 && (int)c->pin_out.size() < ring) c->pin_out.resize((size_t)ring);
-   std::vector<std::future<void>> presize((size_t)std::max(ring, 0));   // ring blocks being pinned on a helper thread
+// The device of run_chunk_loop (chunk_engine.h) for one call.  stage runs on the staging thread, everything else on the caller's.
+struct ChunkDevice {
+   using State = ChunkState;
+   using Slot = hesaff_ctx::ChunkSlot;
+   using Clock = std::chrono::steady_clock;
+   hesaff_ctx *c;
+   const int wants, ring;
+   std::vector<std::future<void>> presize;   // ring blocks being pinned on a helper thread
    bool presized = false;
-   struct JoinPresize {   // no helper outlives this call
-      std::vector<std::future<void>> &f;
-      ~JoinPresize() { for (auto &x : f) if (x.valid()) x.wait(); }
-   } join_presize{presize};
+   // the tuning build's per-chunk lines (HESAFF_DEBUG): when the caller's thread began to wait for the chunk, got it, had run its
+   // batch and had laid out its block, and the thread's CPU time at the first three
+   Clock::time_point dbg_t0, dbg_t1, dbg_t2, dbg_t3;
+   double dbg_c0 = 0.0, dbg_c1 = 0.0, dbg_c2 = 0.0;
 
-   // stage(k): chunk k -> pinned buffer -> device input buffer (k & 1) on the H2D stream; runs while chunk k-1 computes
-   auto stage = [&](int k) -> std::unique_ptr<State> {
-      (void)pthread_setname_np(pthread_self(), "hs-stage");
+   ChunkDevice(hesaff_ctx *c_, int wants_, int ring_) : c(c_), wants(wants_), ring(ring_), presize((size_t)std::max(ring_, 0))
+   {
+      bind_device(c);
+      ensure_copy_streams(c);
+      if (ring > 0 && (int)c->pin_out.size() < ring) c->pin_out.resize((size_t)ring);
+      dbg_next_chunk();
+   }
+   ~ChunkDevice() { for (auto &x : presize) if (x.valid()) x.wait(); }   // no helper outlives the call
+   void dbg_next_chunk() { dbg_t0 = Clock::now(); dbg_c0 = c->debug ? thread_cpu_ms() : 0.0; }
+   bool times_export(const State &s) const { return c->profiling && (wants & (WANT_TEXT | WANT_BIN)) && s.total > 0; }
+
+   // chunk -> pinned buffer -> the slot's device input buffer on the H2D stream; runs while the chunk before computes
+   void stage(State &s)
+   {
       HIP_TRY(hipSetDevice(c->device));
-      std::unique_ptr<State> s(new State());
-      if (!io.next(s->q)) return nullptr;
-      const HostChunk &q = s->q;
-      const int slot = k & 1;
+      const HostChunk &q = s.q;
+      Slot &sl = c->slot[s.no & 1];
       const size_t row_bytes = (size_t)q.W * q.bpp(), img_bytes = row_bytes * q.H;
       // what travels per image: its pixels, or - a JPEG file - its coefficient blob (the pixels are then made in b_in2 by the device)
       const size_t unit = q.blob_bytes ? q.blob_bytes : img_bytes, total = unit * q.data.size();
-      hs_wait_event(c->ev_in_free[slot]);   // chunk k-2 no longer reads this input buffer (never recorded: returns at once)
-      s->largest = std::max<int>((int)q.data.size(), std::min(io.largest_chunk((int)q.data.size()), c->par.max_batch));
-      c->b_in2[slot].ensure(img_bytes * (size_t)s->largest);
-      if (q.blob_bytes) c->b_jcoef[slot].ensure(unit * (size_t)s->largest);
+      hs_wait_event(sl.ev_in_free);   // the chunk two before no longer reads this input buffer (never recorded: returns at once)
+      s.largest = std::max<int>((int)q.data.size(), std::min(s.largest, c->par.max_batch));
+      sl.b_in2.ensure(img_bytes * (size_t)s.largest);
+      if (q.blob_bytes) sl.b_jcoef.ensure(unit * (size_t)s.largest);
       if (q.pinned) {
          // the readers filled page-locked buffers of this context (PinHooks): every image goes to the device from where it is, and its
-         // buffer is given back to the readers when the copy engine has read it (this thread sleeps on a blocking event meanwhile)
-         uint8_t *dst = (uint8_t *)(q.blob_bytes ? c->b_jcoef[slot].p : c->b_in2[slot].p);
+         // buffer is given back to the readers (ChunkIO::staged) when the copy engine has read it (this thread sleeps on a blocking
+         // event meanwhile)
+         uint8_t *dst = (uint8_t *)(q.blob_bytes ? sl.b_jcoef.p : sl.b_in2.p);
          for (size_t b = 0; b < q.data.size(); b++)
             HIP_TRY(hipMemcpyAsync(dst + unit * b, q.data[b], unit, hipMemcpyHostToDevice, c->h2d_stream));
-         HIP_TRY(hipEventRecord(c->ev_h2d[slot], c->h2d_stream));
-         HIP_TRY(hipEventRecord(c->ev_h2d_blk[slot], c->h2d_stream));
-         hs_wait_event(c->ev_h2d_blk[slot]);
-         io.staged(q);
-         return s;
+         HIP_TRY(hipEventRecord(sl.ev_h2d, c->h2d_stream));
+         HIP_TRY(hipEventRecord(sl.ev_h2d_blk, c->h2d_stream));
+         hs_wait_event(sl.ev_h2d_blk);
+         return;
       }
-      c->pin_in[slot].ensure(unit * (size_t)s->largest);   // sized once, for the large chunks that follow a small first one
+      sl.pin_in.ensure(unit * (size_t)s.largest);   // sized once, for the large chunks that follow a small first one
       // pixels into the pinned buffer: a chunk of 64 UHD images is 0.5 GB (2.1 GB as float planes) - on four threads when it is worth
       // it (the first chunk's copy is the pipeline's fill: nothing runs on the device meanwhile).  Float planes are checked in the same
       // pass (copy_row_f32): the first image of a share with a pixel outside the domain stops that share and is reported below.
@@ -388,7 +381,7 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
       std::vector<size_t> bad_img(nimg + 1, nimg);   // per share: the first refused image (nimg: none)
       auto copy_images = [&](size_t b0, size_t b1) {
          for (size_t b = b0; b < b1; b++) {
-            uint8_t *dst = (uint8_t *)c->pin_in[slot].p + unit * b;
+            uint8_t *dst = (uint8_t *)sl.pin_in.p + unit * b;
             if (q.blob_bytes) { memcpy(dst, q.data[b], unit); continue; }
             const size_t stride = q.stride[b];
             if (q.f32) {
@@ -423,10 +416,10 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
          for (int cnt : q.region_count) n_rec += (unsigned long long)cnt;
          if (n_rec > 0x7fffffffull) throw HsError(HESAFF_ERR_CAPACITY, "more records in a chunk than 32-bit indices hold");
          const size_t rec_at = describe_records_offset((int)nimg), bytes = rec_at + (size_t)n_rec * sizeof(hesaff_region);
-         c->pin_reg[slot].ensure_grow(bytes);
-         c->b_reg[slot].ensure_grow(bytes);
-         int32_t *starts = (int32_t *)c->pin_reg[slot].p;
-         hesaff_region *dst = (hesaff_region *)((char *)c->pin_reg[slot].p + rec_at);
+         sl.pin_reg.ensure_grow(bytes);
+         sl.b_reg.ensure_grow(bytes);
+         int32_t *starts = (int32_t *)sl.pin_reg.p;
+         hesaff_region *dst = (hesaff_region *)((char *)sl.pin_reg.p + rec_at);
          size_t at = 0;
          for (size_t b = 0; b < nimg; b++) {
             starts[b] = (int32_t)at;
@@ -442,163 +435,156 @@ void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
             at += (size_t)q.region_count[b];
          }
          starts[nimg] = (int32_t)at;
-         s->n_rec = (uint32_t)at;
-         HIP_TRY(hipMemcpyAsync(c->b_reg[slot].p, c->pin_reg[slot].p, bytes, hipMemcpyHostToDevice, c->h2d_stream));
+         s.n_rec = (uint32_t)at;
+         HIP_TRY(hipMemcpyAsync(sl.b_reg.p, sl.pin_reg.p, bytes, hipMemcpyHostToDevice, c->h2d_stream));
       }
-      HIP_TRY(hipMemcpyAsync(q.blob_bytes ? c->b_jcoef[slot].p : c->b_in2[slot].p, c->pin_in[slot].p, total, hipMemcpyHostToDevice, c->h2d_stream));
-      HIP_TRY(hipEventRecord(c->ev_h2d[slot], c->h2d_stream));
-      io.staged(q);
-      return s;
-   };
-   auto deliver = [&](State &s) {
-      if (s.copied) hs_wait_event(c->ev_d2h[s.no & 1]);
-      if (s.total > 0 && c->profiling && (wants & (WANT_TEXT | WANT_BIN))) {
+      HIP_TRY(hipMemcpyAsync(q.blob_bytes ? sl.b_jcoef.p : sl.b_in2.p, sl.pin_in.p, total, hipMemcpyHostToDevice, c->h2d_stream));
+      HIP_TRY(hipEventRecord(sl.ev_h2d, c->h2d_stream));
+   }
+
+   // the chunk's batch, its per-image counts and the layout of its result block.  ev_in_free of the slot is recorded when the batch has
+   // run and when the chunk is refused (HESAFF_ERR_ARG, HESAFF_ERR_CAPACITY: both are thrown with the main stream idle), not on other errors
+   void compute(State &s)
+   {
+      dbg_t1 = Clock::now();
+      dbg_c1 = c->debug ? thread_cpu_ms() : 0.0;
+      const HostChunk &q = s.q;
+      Slot &sl = c->slot[s.no & 1];
+      const int B = (int)q.data.size();
+      const size_t row_bytes = (size_t)q.W * q.bpp(), img_bytes = row_bytes * q.H;
+      HIP_TRY(hipStreamWaitEvent(c->stream, sl.ev_h2d, 0));
+      BatchResult res = {};
+      try {
+         plan(c, std::max(std::min<int>(c->par.max_batch, B), s.largest), q.H, q.W);
+         // a chunk of JPEG files: inverse DCT, up-sampling and colour conversion of all its images (kernels_jpeg.h) into the input slot
+         if (q.blob_bytes) jpeg_pixels(c, sl.b_jcoef.as<uint8_t>(), make_jpeg_geom(q.jpeg), B, (uint8_t *)sl.b_in2.p, img_bytes, c->stream);
+         const SrcImages src = q.f32 ? SrcImages::f32(sl.b_in2.p, (long long)img_bytes, (int)row_bytes)
+                                     : SrcImages::u8(sl.b_in2.p, q.ch, (long long)img_bytes, (int)row_bytes);
+         res = q.from ? run_describe(c, src, B, q.H, q.W, (const uint8_t *)sl.b_reg.p, s.n_rec, q.from) : run_batch(c, src, B, q.H, q.W);
+      } catch (const HsError &e) {
+         if (e.code == HESAFF_ERR_ARG || e.code == HESAFF_ERR_CAPACITY) {
+            HIP_TRY(hipEventRecord(sl.ev_in_free, c->stream));
+            dbg_next_chunk();
+         }
+         throw;
+      }
+      HIP_TRY(hipEventRecord(sl.ev_in_free, c->stream));
+      dbg_t2 = Clock::now();
+      dbg_c2 = c->debug ? thread_cpu_ms() : 0.0;
+      const int32_t *hs = res.hessian_starts, *ds = res.desc_starts;
+      s.total = ds[B];
+      s.n_hess = (size_t)hs[B];
+      s.nh.resize((size_t)B); s.nd.resize((size_t)B); s.off.resize((size_t)B);
+      for (int b = 0; b < B; b++) {
+         s.nh[(size_t)b] = hs[b + 1] - hs[b];
+         s.nd[(size_t)b] = ds[b + 1] - ds[b];
+         s.off[(size_t)b] = (size_t)ds[b];
+      }
+      const size_t n_rows = (size_t)s.total;
+      size_t at = 0;
+      auto place = [&at](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~(size_t)255; return o; };
+      if (wants & WANT_KEYS) s.keys_at = place(n_rows * sizeof(hesaff_keypoint));
+      if (wants & WANT_REGIONS) s.regions_at = place(s.n_hess * sizeof(hesaff_region));
+      if (times_export(s)) HIP_TRY(hipEventRecord(sl.ev_exp[0], c->stream));
+      if (wants & WANT_TEXT) {   // row lengths and offsets first: the host needs the byte count (a short wait on the main stream)
+         const unsigned long long text_bytes = export_text_prepare(c, c->geo.b_out.as<KeyRec>(), (uint32_t)n_rows, res.d_desc_starts, B, s.toff);
+         s.text_at = place((size_t)text_bytes);
+      }
+      if (wants & WANT_BIN) s.bin_at = place(n_rows * EX_BIN_ROW);
+      if (times_export(s)) HIP_TRY(hipEventRecord(sl.ev_exp[1], c->stream));
+      s.bytes = at;
+      dbg_t3 = Clock::now();
+   }
+
+   // s.block is chosen: the block is sized, then the device copy / formatting into the staging slot (frees b_out for the next chunk)
+   // and the D2H beside the next chunk
+   void copy_out(State &s)
+   {
+      Slot &sl = c->slot[s.no & 1];
+      const int B = (int)s.q.data.size();
+      const size_t bytes = s.bytes, n_rows = (size_t)s.total;
+      if (ring > 0) {
+         // A list that starts with small chunks (a long one): every block of the ring is sized for a FULL chunk of this density the
+         // first time one is needed, the other blocks on a helper thread beside the next chunk's kernels: pinning 1.5 GB takes
+         // 150 ms, and a block that is sized - or grown - when its chunk is already waiting leaves the device idle for that long.
+         const int follow = std::max(s.largest, B);   // images of the largest chunk that is known to follow (ChunkIO::largest_chunk)
+         const size_t full = (bytes * (size_t)follow + (size_t)B - 1) / (size_t)B;
+         if (presize[(size_t)s.block].valid()) presize[(size_t)s.block].get();
+         PinBuf &pb = c->pin_out[(size_t)s.block];
+         if (bytes > pb.bytes) pb.ensure_grow(std::max<size_t>(full, 16));
+         if (!presized && follow > B) {   // a list that starts small is a long one: its other blocks will be needed
+            presized = true;
+            for (int r = 0; r < ring; r++)
+               if (r != s.block && c->pin_out[(size_t)r].bytes == 0)
+                  presize[(size_t)r] = std::async(std::launch::async, [c = c, r, full] {
+                     if (hipSetDevice(c->device) != hipSuccess) return;
+                     try { c->pin_out[(size_t)r].ensure_grow(std::max<size_t>(full, 16)); } catch (const HsError &) {}   // asked for again, and reported, when the block is needed
+                  });
+         }
+      } else {   // a block per chunk, kept until the next call
+         if ((int)c->pin_out.size() <= s.block) c->pin_out.resize((size_t)s.block + 1);
+         c->pin_out[(size_t)s.block].ensure(std::max<size_t>(bytes, 16));
+      }
+      s.copied = s.total > 0 || ((wants & WANT_REGIONS) && s.n_hess > 0);
+      if (s.copied) {
+         const KeyRec *d_keys = c->geo.b_out.as<KeyRec>();
+         HIP_TRY(hipStreamWaitEvent(c->stream, sl.ev_d2h, 0));      // the D2H of the chunk two before has left this staging slot
+         if (bytes > sl.b_outstage.bytes) sl.b_outstage.ensure(bytes + bytes / 4);
+         char *stg = (char *)sl.b_outstage.p;
+         if ((wants & WANT_KEYS) && n_rows > 0)
+            HIP_TRY(hipMemcpyAsync(stg + s.keys_at, c->geo.b_out.p, n_rows * sizeof(hesaff_keypoint), hipMemcpyDeviceToDevice, c->stream));
+         if (wants & WANT_REGIONS) pack_regions(c, (uint32_t)s.n_hess, B, (hesaff_region *)(stg + s.regions_at));
+         if (times_export(s)) HIP_TRY(hipEventRecord(sl.ev_exp[2], c->stream));
+         if (wants & WANT_TEXT) export_text_write(c, d_keys, (uint32_t)n_rows, stg + s.text_at);
+         if (wants & WANT_BIN) export_bin_rows(c, d_keys, (uint32_t)n_rows, stg + s.bin_at);
+         if (times_export(s)) HIP_TRY(hipEventRecord(sl.ev_exp[3], c->stream));
+         HIP_TRY(hipEventRecord(sl.ev_out_ready, c->stream));
+         HIP_TRY(hipStreamWaitEvent(c->d2h_stream, sl.ev_out_ready, 0));
+         HIP_TRY(hipMemcpyAsync(c->pin_out[(size_t)s.block].p, stg, bytes, hipMemcpyDeviceToHost, c->d2h_stream));
+         HIP_TRY(hipEventRecord(sl.ev_d2h, c->d2h_stream));
+      }
+      if (c->debug) {
+         auto ms = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+         const auto dbg_t5 = Clock::now();
+         fprintf(stderr, "[hesaff] chunk %d: caller's CPU: wait staged %.1f run_batch %.1f rest %.1f ms\n", s.no, dbg_c1 - dbg_c0, dbg_c2 - dbg_c1, thread_cpu_ms() - dbg_c2);
+         fprintf(stderr, "[hesaff] chunk %d: wait staged %.1f  run_batch %.1f  export prepare %.1f  deliver prev %.1f  acquire+enqueue %.1f ms | device: pyramid %.1f detect %.1f affine %.1f patch %.1f sift %.1f pack %.1f total %.1f\n", s.no, ms(dbg_t0, dbg_t1),
+                 ms(dbg_t1, dbg_t2), ms(dbg_t2, dbg_t3), ms(dbg_t3, s.delivered), ms(s.delivered, dbg_t5), c->tm.pyramid_ms, c->tm.detect_ms, c->tm.affine_ms, c->tm.patch_ms, c->tm.sift_ms, c->tm.pack_ms, c->tm.total_ms);
+      }
+      dbg_next_chunk();
+   }
+
+   // the chunk's copy out has landed: the base of its result block (and, when profiling, what its export passes took)
+   const char *wait_out(State &s)
+   {
+      Slot &sl = c->slot[s.no & 1];
+      if (s.copied) hs_wait_event(sl.ev_d2h);
+      if (times_export(s)) {
          float ms = 0.0f;   // length pass (with the host's short wait for the byte counts) + write pass
          float ms2 = 0.0f;
-         if (hipEventElapsedTime(&ms, c->ev_exp[s.no & 1][0], c->ev_exp[s.no & 1][1]) == hipSuccess && hipEventElapsedTime(&ms2, c->ev_exp[s.no & 1][2], c->ev_exp[s.no & 1][3]) == hipSuccess) {
+         if (hipEventElapsedTime(&ms, sl.ev_exp[0], sl.ev_exp[1]) == hipSuccess && hipEventElapsedTime(&ms2, sl.ev_exp[2], sl.ev_exp[3]) == hipSuccess) {
             ms += ms2; c->export_ms = ms; c->export_rows = s.total; c->tm.export_ms = ms; c->tm.export_rows = s.total; }
          else (void)hipGetLastError();
       }
-      ChunkDone d;
-      const char *blk = (const char *)c->pin_out[(size_t)s.block].p;
-      d.chunk = &s.q; d.count_hessian = s.nh.data(); d.count_desc = s.nd.data(); d.key_off = s.off.data();
-      d.keys = (wants & WANT_KEYS) ? (const hesaff_keypoint *)blk : nullptr; d.block = s.block;
-      if (wants & WANT_TEXT) { d.text = blk + s.text_at; d.text_off = s.toff.data(); }
-      if (wants & WANT_BIN) d.bin = blk + s.bin_at;
-      if (wants & WANT_REGIONS) d.regions = (const hesaff_region *)(blk + s.regions_at);
-      io.done(d);
-   };
+      return (const char *)c->pin_out[(size_t)s.block].p;
+   }
 
-   std::future<std::unique_ptr<State>> staged = std::async(std::launch::async, stage, 0);
-   std::unique_ptr<State> prev;
-   try {
-      for (int k = 0;; k++) {
-         const auto dbg_t0 = std::chrono::steady_clock::now();
-         const double dbg_c0 = c->debug ? thread_cpu_ms() : 0.0;
-         std::unique_ptr<State> cur = staged.get();           // H2D of chunk k is enqueued
-         if (!cur) break;
-         const auto dbg_t1 = std::chrono::steady_clock::now();
-         const double dbg_c1 = c->debug ? thread_cpu_ms() : 0.0;
-         cur->no = k;
-         staged = std::async(std::launch::async, stage, k + 1);
-         const HostChunk &q = cur->q;
-         const int slot = k & 1, B = (int)q.data.size();
-         const size_t row_bytes = (size_t)q.W * q.bpp(), img_bytes = row_bytes * q.H;
-         HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_h2d[slot], 0));
-         try {
-            plan(c, std::max(std::min<int>(c->par.max_batch, B), cur->largest), q.H, q.W);
-            // a chunk of JPEG files: inverse DCT, up-sampling and colour conversion of all its images (kernels_jpeg.h) into the input slot
-            if (q.blob_bytes) jpeg_pixels(c, c->b_jcoef[slot].as<uint8_t>(), make_jpeg_geom(q.jpeg), B, (uint8_t *)c->b_in2[slot].p, img_bytes, c->stream);
-            const SrcImages src = q.f32 ? SrcImages::f32(c->b_in2[slot].p, (long long)img_bytes, (int)row_bytes)
-                                        : SrcImages::u8(c->b_in2[slot].p, q.ch, (long long)img_bytes, (int)row_bytes);
-            if (q.from) run_describe(c, src, B, q.H, q.W, (const uint8_t *)c->b_reg[slot].p, cur->n_rec, q.from);
-            else run_batch(c, src, B, q.H, q.W);
-         } catch (const HsError &e) {
-            // this chunk's images cannot be planned (geometry) or exceed the planned keypoint capacity: that is about these
-            // images, not about the device.  Both are thrown with the main stream idle; the other chunks go on when the
-            // consumer can note the failure per image (hesaff_process_files), otherwise the call fails as a whole.
-            if (e.code != HESAFF_ERR_ARG && e.code != HESAFF_ERR_CAPACITY) throw;
-            HIP_TRY(hipEventRecord(c->ev_in_free[slot], c->stream));
-            if (!io.failed(q, e.code)) throw;
-            continue;
-         }
-         HIP_TRY(hipEventRecord(c->ev_in_free[slot], c->stream));
-         const auto dbg_t2 = std::chrono::steady_clock::now();
-         const double dbg_c2 = c->debug ? thread_cpu_ms() : 0.0;
-         const int32_t *hs = c->h_starts, *ds = c->h_starts + (B + 1);
-         cur->total = ds[B];
-         cur->nh.resize((size_t)B); cur->nd.resize((size_t)B); cur->off.resize((size_t)B);
-         for (int b = 0; b < B; b++) {
-            cur->nh[(size_t)b] = hs[b + 1] - hs[b];
-            cur->nd[(size_t)b] = ds[b + 1] - ds[b];
-            cur->off[(size_t)b] = (size_t)ds[b];
-         }
-         // layout of the chunk's result block: [records][regions][text rows][sidecar rows], what the consumer wants of them
-         const size_t n_rows = (size_t)cur->total, n_hess = (size_t)hs[B];
-         const KeyRec *d_keys = c->geo.b_out.as<KeyRec>();
-         size_t at = 0;
-         auto place = [&at](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~(size_t)255; return o; };
-         const size_t keys_at = (wants & WANT_KEYS) ? place(n_rows * sizeof(hesaff_keypoint)) : 0;
-         if (wants & WANT_REGIONS) cur->regions_at = place(n_hess * sizeof(hesaff_region));
-         unsigned long long text_bytes = 0;
-         const bool time_export = c->profiling && (wants & (WANT_TEXT | WANT_BIN)) && n_rows > 0;
-         if (time_export) HIP_TRY(hipEventRecord(c->ev_exp[slot][0], c->stream));
-         if (wants & WANT_TEXT) {   // row lengths and offsets first: the host needs the byte count (a short wait on the main stream)
-            text_bytes = export_text_prepare(c, d_keys, (uint32_t)n_rows, c->geo.b_starts.as<int32_t>() + (B + 1), B, cur->toff);
-            cur->text_at = place((size_t)text_bytes);
-         }
-         if (wants & WANT_BIN) cur->bin_at = place(n_rows * EX_BIN_ROW);
-         if (time_export) HIP_TRY(hipEventRecord(c->ev_exp[slot][1], c->stream));
-         const size_t bytes = at;
-         const auto dbg_t3 = std::chrono::steady_clock::now();
-         // chunk k-1: its copy out was enqueued before the kernels of chunk k and has long finished
-         if (prev) { deliver(*prev); prev.reset(); }
-         const auto dbg_t4 = std::chrono::steady_clock::now();
-         // a pinned block for chunk k
-         if (ring > 0) {
-            cur->block = c->ring.acquire();
-         } else {
-            if ((int)c->pin_out.size() <= k) c->pin_out.resize((size_t)k + 1);
-            cur->block = k;
-         }
-         // device copy / formatting into the staging slot (frees b_out for the next chunk), then D2H beside the next chunk
-         if (ring > 0) {
-            // A list that starts with small chunks (a long one): every block of the ring is sized for a FULL chunk of this density the
-            // first time one is needed, the other blocks on a helper thread beside the next chunk's kernels: pinning 1.5 GB takes
-            // 150 ms, and a block that is sized - or grown - when its chunk is already waiting leaves the device idle for that long.
-            const int follow = std::max(cur->largest, B);   // images of the largest chunk that is known to follow (ChunkIO::largest_chunk)
-            const size_t full = (bytes * (size_t)follow + (size_t)B - 1) / (size_t)B;
-            if (presize[(size_t)cur->block].valid()) presize[(size_t)cur->block].get();
-            PinBuf &pb = c->pin_out[(size_t)cur->block];
-            if (bytes > pb.bytes) pb.ensure_grow(std::max<size_t>(full, 16));
-            if (!presized && follow > B) {   // a list that starts small is a long one: its other blocks will be needed
-               presized = true;
-               for (int r = 0; r < ring; r++)
-                  if (r != cur->block && c->pin_out[(size_t)r].bytes == 0)
-                     presize[(size_t)r] = std::async(std::launch::async, [c, r, full] {
-                        if (hipSetDevice(c->device) != hipSuccess) return;
-                        try { c->pin_out[(size_t)r].ensure_grow(std::max<size_t>(full, 16)); } catch (const HsError &) {}   // asked for again, and reported, when the block is needed
-                     });
-            }
-         } else {
-            c->pin_out[(size_t)cur->block].ensure(std::max<size_t>(bytes, 16));
-         }
-         cur->copied = cur->total > 0 || ((wants & WANT_REGIONS) && n_hess > 0);
-         if (cur->copied) {
-            HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_d2h[slot], 0));      // D2H of chunk k-2 has left this staging slot
-            if (bytes > c->b_outstage[slot].bytes) c->b_outstage[slot].ensure(bytes + bytes / 4);
-            char *stg = (char *)c->b_outstage[slot].p;
-            if ((wants & WANT_KEYS) && n_rows > 0)
-               HIP_TRY(hipMemcpyAsync(stg + keys_at, c->geo.b_out.p, n_rows * sizeof(hesaff_keypoint), hipMemcpyDeviceToDevice, c->stream));
-            if (wants & WANT_REGIONS) pack_regions(c, (uint32_t)n_hess, B, (hesaff_region *)(stg + cur->regions_at));
-            if (time_export) HIP_TRY(hipEventRecord(c->ev_exp[slot][2], c->stream));
-            if (wants & WANT_TEXT) export_text_write(c, d_keys, (uint32_t)n_rows, stg + cur->text_at);
-            if (wants & WANT_BIN) export_bin_rows(c, d_keys, (uint32_t)n_rows, stg + cur->bin_at);
-            if (time_export) HIP_TRY(hipEventRecord(c->ev_exp[slot][3], c->stream));
-            HIP_TRY(hipEventRecord(c->ev_out_ready[slot], c->stream));
-            HIP_TRY(hipStreamWaitEvent(c->d2h_stream, c->ev_out_ready[slot], 0));
-            HIP_TRY(hipMemcpyAsync(c->pin_out[(size_t)cur->block].p, stg, bytes, hipMemcpyDeviceToHost, c->d2h_stream));
-            HIP_TRY(hipEventRecord(c->ev_d2h[slot], c->d2h_stream));
-         }
-         if (c->debug) {
-            auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-            const auto dbg_t5 = std::chrono::steady_clock::now();
-            fprintf(stderr, "[hesaff] chunk %d: caller's CPU: wait staged %.1f run_batch %.1f rest %.1f ms\n", k, dbg_c1 - dbg_c0, dbg_c2 - dbg_c1, thread_cpu_ms() - dbg_c2);
-            fprintf(stderr, "[hesaff] chunk %d: wait staged %.1f  run_batch %.1f  export prepare %.1f  deliver prev %.1f  acquire+enqueue %.1f ms | device: pyramid %.1f detect %.1f affine %.1f patch %.1f sift %.1f pack %.1f total %.1f\n", k, ms(dbg_t0, dbg_t1),
-                    ms(dbg_t1, dbg_t2), ms(dbg_t2, dbg_t3), ms(dbg_t3, dbg_t4), ms(dbg_t4, dbg_t5), c->tm.pyramid_ms, c->tm.detect_ms, c->tm.affine_ms, c->tm.patch_ms, c->tm.sift_ms, c->tm.pack_ms, c->tm.total_ms);
-         }
-         prev = std::move(cur);
-      }
-      if (prev) { deliver(*prev); prev.reset(); }
-   } catch (...) {
-      if (staged.valid()) { try { staged.get(); } catch (...) {} }
+   void drain()
+   {
       (void)hipStreamSynchronize(c->h2d_stream);
       (void)hipStreamSynchronize(c->d2h_stream);
       (void)hipStreamSynchronize(c->stream);
-      throw;
    }
-   HIP_TRY(hipStreamSynchronize(c->d2h_stream));
-   HIP_TRY(hipStreamSynchronize(c->stream));
+   void finish()
+   {
+      HIP_TRY(hipStreamSynchronize(c->d2h_stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+   }
+};
+
+void run_chunks(hesaff_ctx *c, ChunkIO &io, int ring)
+{
+   ChunkDevice dev(c, io.wants(), ring);
+   run_chunk_loop(io, c->ring, ring, dev);
 }
 
 // what ArrayIO (chunk_engine.h) takes for granted
@@ -687,8 +673,8 @@ int hesaff_detect_batch_cb(hesaff_ctx *c, int n, const uint8_t *const *images, c
    HS_API_END(c)
 }
 
-// the chunks of hesaff_detect_batch, each with a block of hesaff_region records beside its keys (k_pack_regions, launched in run_chunks'
-// output step into the staging slot: the records leave on the chunk's one copy out)
+// the chunks of hesaff_detect_batch, each with a block of hesaff_region records beside its keys (k_pack_regions, launched in ChunkDevice's
+// copy_out into the staging slot: the records leave on the chunk's one copy out)
 int hesaff_detect_regions(hesaff_ctx *c, int n, const uint8_t *const *images, const int *widths, const int *heights,
                           const int *strides, const int *channels, hesaff_region_result *results)
 {
@@ -1206,10 +1192,11 @@ int hesaff_stage_jpeg_pixels(hesaff_ctx *c, const hesaff_jpeg_layout *layout, in
    const JpegGeom g = make_jpeg_geom(*layout);
    if ((size_t)g.blob_bytes != blob_bytes) throw HsError(HESAFF_ERR_ARG, "blob size does not match the layout");
    const size_t img = (size_t)g.W * g.H * g.nc;
-   c->b_jcoef[0].ensure(blob_bytes * (size_t)n);
+   DevBuf &b_jcoef = c->slot[0].b_jcoef;   // (no chunk is on its way during a stage call)
+   b_jcoef.ensure(blob_bytes * (size_t)n);
    c->b_stage.ensure(img * (size_t)n);
-   HIP_TRY(hipMemcpyAsync(c->b_jcoef[0].p, blobs, blob_bytes * (size_t)n, hipMemcpyHostToDevice, c->stream));
-   jpeg_pixels(c, c->b_jcoef[0].as<uint8_t>(), g, n, c->b_stage.as<uint8_t>(), img, c->stream);
+   HIP_TRY(hipMemcpyAsync(b_jcoef.p, blobs, blob_bytes * (size_t)n, hipMemcpyHostToDevice, c->stream));
+   jpeg_pixels(c, b_jcoef.as<uint8_t>(), g, n, c->b_stage.as<uint8_t>(), img, c->stream);
    HIP_TRY(hipMemcpyAsync(pixels, c->b_stage.p, img * (size_t)n, hipMemcpyDeviceToHost, c->stream));
    finish_stream(c);
    HS_API_END(c)

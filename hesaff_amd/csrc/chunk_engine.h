@@ -1,14 +1,19 @@
-// chunk_engine.h -- the host-only half of the chunk engine (capi_impl.h): the chunk types, the ring of pinned result blocks
-// and FileIO, the decoder / writer thread pools of hesaff_process_files.  Nothing here touches HIP, so that this code - every
-// mutex, condition variable and hand-over between threads of the file pipeline - also runs under ThreadSanitizer and
-// AddressSanitizer on a CPU with a mock device loop (tests/native/engine_sanitize.cpp, tests/test_host_sanitize.py).
+// chunk_engine.h -- the host-only half of the chunk engine: the chunk types, the ring of pinned result blocks, the chunk loop
+// (run_chunk_loop: the staging thread one chunk ahead, the order compute / deliver / copy out, the refusal rule and the error
+// path of every host entry point) and FileIO, the decoder / writer thread pools of hesaff_process_files.  Nothing here touches
+// HIP: the loop drives the device through an object that capi_impl.h implements with HIP (ChunkDevice).  So this code - every
+// mutex, condition variable and hand-over between threads of the pipeline - also runs as it is under ThreadSanitizer and
+// AddressSanitizer on a CPU, with a mock of that object alone (tests/native/engine_sanitize.cpp, tests/test_host_sanitize.py).
 #pragma once
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <cstdint>
 #include <cstring>
 #include <deque>
+#include <future>
+#include <memory>
 #include <mutex>
 #include <pthread.h>
 #include <sys/resource.h>
@@ -22,6 +27,13 @@
 #include "../../include/hesaff_amd.h"
 
 namespace hesaff_engine {
+
+// What the library throws: a return code of include/hesaff_amd.h and the text hesaff_last_error() hands out.
+struct HsError {
+   int code;
+   std::string msg;
+   HsError(int c, const std::string &m) : code(c), msg(m) {}
+};
 
 // Pinned result blocks in rotation: a block is busy from the copy out of a chunk until its consumer gives it back.
 struct BlockRing {
@@ -116,6 +128,101 @@ struct ChunkIO {
    virtual bool failed(const HostChunk &, int /*rc*/) { return false; }
    virtual ~ChunkIO() {}
 };
+
+// One chunk on its way through run_chunk_loop.  Three chunks are alive at once - k-1 waits to be delivered, k computes, k+1 is
+// staged on the other thread - over two device slots (k & 1): whatever belongs to a chunk lives here, never in its slot.
+struct ChunkState {
+   HostChunk q;
+   int no = 0;                             // the chunk's number in the call (refused chunks count); its device slot is no & 1
+   int largest = 0;                        // ChunkIO::largest_chunk when the chunk was staged
+   std::vector<int32_t> nh, nd;            // per image: Hessian keypoints, descriptors
+   std::vector<size_t> off;                // per image: its first record
+   std::vector<unsigned long long> toff;   // WANT_TEXT: byte offset of every image's rows
+   int total = 0;                          // records of the chunk
+   size_t n_hess = 0;                      // Hessian keypoints of the chunk
+   // layout of the chunk's result block: [records][regions][text rows][sidecar rows], what the consumer wants of them, `bytes` in all
+   size_t keys_at = 0, regions_at = 0, text_at = 0, bin_at = 0, bytes = 0;
+   int block = -1;                         // the result block the loop chose: one of the ring, or `no` without a ring
+   uint32_t n_rec = 0;                     // hesaff_describe_regions: records of the chunk
+   bool copied = false;                    // a copy out was enqueued
+   std::chrono::steady_clock::time_point delivered;   // when chunk no-1 had been handed on (the tuning build's per-chunk line)
+};
+
+// The chunk loop of every entry point that takes host images or files.  A ChunkIO hands over chunks of equally sized images one
+// after the other and receives each chunk's records when they are in host memory:
+//    staging thread :  io.next(chunk k+1) -> dev.stage (pixels into pinned memory, H2D on its own stream) -> io.staged()
+//    caller's thread:  dev.compute(chunk k) ; io.done(chunk k-1) ; a result block ; dev.copy_out(chunk k) (D2H on a third stream)
+// so the copy in of chunk k+1 and the copy out of chunk k-1 run beside the kernels of chunk k.  Result blocks: ring_blocks == 0
+// gives every chunk the block of its own number, kept until the next call (hesaff_detect_batch's contract: every
+// results[i].keys stays valid); ring_blocks == N > 0 cycles through N blocks, and the consumer gives a block back
+// (BlockRing::release) when it has finished with the chunk (bounded host memory however long the list is).
+// Device, with State = ChunkState or a struct derived from it:
+//    stage(State &)      staging thread: the chunk's images on their way into device slot no & 1
+//    compute(State &)    everything up to the layout of the result block (nh .. bytes); throws HsError
+//    copy_out(State &)   `block` is chosen: the block sized, the copy out enqueued
+//    wait_out(State &)   the copy out has landed -> the block's base address
+//    drain()             error path: the device idle, nothing thrown;  finish(): the same at the end of a list, errors thrown
+template <class Device>
+void run_chunk_loop(ChunkIO &io, BlockRing &ring, int ring_blocks, Device &dev)
+{
+   using State = typename Device::State;
+   const int wants = io.wants();
+   ring.reset(ring_blocks);
+   auto stage = [&](int k) {   // chunk k on a thread of its own: nullptr when the list has ended
+      return std::async(std::launch::async, [&io, &dev, k]() -> std::unique_ptr<State> {
+         (void)pthread_setname_np(pthread_self(), "hs-stage");
+         std::unique_ptr<State> s(new State());
+         if (!io.next(s->q)) return nullptr;
+         s->no = k;
+         s->largest = io.largest_chunk((int)s->q.data.size());
+         dev.stage(*s);
+         io.staged(s->q);
+         return s;
+      });
+   };
+   auto deliver = [&](State &s) {
+      const char *blk = dev.wait_out(s);
+      ChunkDone d;
+      d.chunk = &s.q; d.count_hessian = s.nh.data(); d.count_desc = s.nd.data(); d.key_off = s.off.data();
+      d.keys = (wants & WANT_KEYS) ? (const hesaff_keypoint *)(blk + s.keys_at) : nullptr; d.block = s.block;
+      if (wants & WANT_TEXT) { d.text = blk + s.text_at; d.text_off = s.toff.data(); }
+      if (wants & WANT_BIN) d.bin = blk + s.bin_at;
+      if (wants & WANT_REGIONS) d.regions = (const hesaff_region *)(blk + s.regions_at);
+      io.done(d);
+   };
+
+   std::future<std::unique_ptr<State>> staged = stage(0);
+   std::unique_ptr<State> prev;
+   try {
+      for (int k = 0;; k++) {
+         std::unique_ptr<State> cur = staged.get();           // the copy in of chunk k is enqueued
+         if (!cur) break;
+         staged = stage(k + 1);
+         try {
+            dev.compute(*cur);
+         } catch (const HsError &e) {
+            // this chunk's images cannot be planned (geometry) or exceed the planned keypoint capacity: that is about these
+            // images, not about the device.  The other chunks go on when the consumer can note the failure per image
+            // (hesaff_process_files), otherwise the call fails as a whole.
+            if ((e.code != HESAFF_ERR_ARG && e.code != HESAFF_ERR_CAPACITY) || !io.failed(cur->q, e.code)) throw;
+            continue;
+         }
+         // chunk k-1: its copy out was enqueued before the kernels of chunk k and has long finished
+         if (prev) { deliver(*prev); prev.reset(); }
+         cur->delivered = std::chrono::steady_clock::now();
+         cur->block = ring_blocks > 0 ? ring.acquire() : k;
+         dev.copy_out(*cur);
+         prev = std::move(cur);
+      }
+      if (prev) { deliver(*prev); prev.reset(); }
+   } catch (...) {
+      // the staging thread holds references to io and dev: it ends before either goes away (what it threw is not this call's error)
+      if (staged.valid()) { try { staged.get(); } catch (...) {} }
+      dev.drain();
+      throw;
+   }
+   dev.finish();
+}
 
 // The value domain of the float entry points (include/hesaff_amd.h): finite, |v| <= 2^20.  On the bit pattern: |v| > 2^20 (0x49800000),
 // +-Inf and NaN are exactly the patterns whose low 31 bits exceed 0x49800000.

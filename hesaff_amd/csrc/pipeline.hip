@@ -81,11 +81,7 @@ static thread_local std::string g_create_error;
       }                                                                                       \
    } while (0)
 
-struct HsError {
-   int code;
-   std::string msg;
-   HsError(int c, const std::string &m) : code(c), msg(m) {}
-};
+using hesaff_engine::HsError;
 
 // Host wait for a HIP event WITHOUT a spinning core.  hipEventSynchronize spins in this runtime even on events created with
 // hipEventBlockingSync (measured in round 5 with CLOCK_THREAD_CPUTIME_ID around the call: 96 ms of CPU for a 96 ms wait, one busy core per
@@ -332,12 +328,22 @@ struct hesaff_ctx {
                             //         [32..32+HS_MAX_OCTAVES) octave rec starts
    DevBuf b_patches, b_stage;
    DevBuf b_input;          // staging for host images (stage API)
-   // hesaff_detect_batch, host entry point: chunks of max_batch images are pipelined -- pinned
-   // staging + H2D of chunk i+1 and D2H of chunk i-1 run beside the kernels of chunk i
-   DevBuf b_in2[2], b_outstage[2];
-   PinBuf pin_in[2];
-   PinBuf pin_reg[2];       // hesaff_describe_regions: a chunk's record starts + records, staged per input slot ...
-   DevBuf b_reg[2];         // ... and on the device (run_describe's d_block)
+   // The host entry points: chunks of max_batch images are pipelined -- pinned staging + H2D of chunk k+1 and D2H of chunk k-1 run
+   // beside the kernels of chunk k (chunk_engine.h: run_chunk_loop).  Chunk k has slot k & 1: what it is copied into, computed from and
+   // copied out of on the device, and the events between those steps (made by ensure_copy_streams, capi_impl.h).
+   struct ChunkSlot {
+      PinBuf pin_in;        // the chunk's pixels (or JPEG coefficient blobs) on their way in, unless the readers filled pinned memory ...
+      DevBuf b_in2;         // ... and on the device: the input of run_batch
+      DevBuf b_jcoef;       // JPEG chunks: the images' coefficient blobs (kernels_jpeg.h makes the pixels in b_in2)
+      PinBuf pin_reg;       // hesaff_describe_regions: the chunk's record starts + records ...
+      DevBuf b_reg;         // ... and on the device (run_describe's d_block)
+      DevBuf b_outstage;    // what leaves for the host, in the layout of the result block
+      DevEvent ev_h2d;      // the copy in has landed
+      DevEvent ev_h2d_blk;  // blocking-sync: the staging thread sleeps until a chunk's direct copies have left the readers' buffers
+      DevEvent ev_in_free;  // the kernels have read the input: the slot may be refilled
+      DevEvent ev_out_ready, ev_d2h;   // b_outstage is complete; the copy out has left it
+      DevEvent ev_exp[4];   // profiling: brackets of the chunk's length pass and of its write pass (the host's waits between them - a free pinned block - are not the export's)
+   } slot[2];
    // Page-locked buffers the readers of hesaff_process_files fill directly (chunk_engine.h: PinHooks): handed out by size, taken back
    // when their image is on the device, kept pinned from one list to the next (pinning costs 0.1 ms per MB), released with the context.
    // At most kPinReadBytes are out or parked; a request beyond that gets nullptr (the image then takes the staging copy).
@@ -402,17 +408,13 @@ struct hesaff_ctx {
       }
       ~PinReadCache() { trim(0); }
    } pin_read;
-   DevEvent ev_h2d_blk[2];   // blocking-sync: the staging thread sleeps until a chunk's direct copies have left the readers' buffers
    std::vector<PinBuf> pin_out;       // result blocks: one per chunk of the current call (hesaff_detect_batch), or a ring of three
    hesaff_engine::BlockRing ring;     // (hesaff_detect_batch_cb, hesaff_process_files: a block returns to the ring when its consumer is done with it)
    hipStream_t h2d_stream = nullptr, d2h_stream = nullptr;
-   DevEvent ev_exp[2][4];   // profiling, per staging slot: brackets of a chunk's length pass and of its write pass (the host's waits between them - a free pinned block - are not the export's)
    float export_ms = 0.0f; int32_t export_rows = 0;
-   DevEvent ev_h2d[2], ev_in_free[2], ev_out_ready[2], ev_d2h[2];
    PinBuf h_small_end, h_small_mid, h_small_exp;   // small results the host reads every batch (PinBuf::ensure_small)
-   int32_t *h_starts = nullptr;   // in h_small_end: the last batch's Hessian starts [B + 1], descriptor starts [B + 1], counters [8] (run_batch)
    DevBuf t_mask_idx, t_sgrad_nb, t_sgrad_om, t_vo_rows, t_vo_src, b_rowprefix, b_trows, b_trows2, b_trows3;
-   DevBuf b_jcoef[2], b_jplane;   // JPEG chunks: the images' coefficient blobs per input slot, the component planes after the inverse DCT (kernels_jpeg.h)
+   DevBuf b_jplane;   // JPEG chunks: the component planes after the inverse DCT (kernels_jpeg.h)
    DevBuf b_ex_len, b_ex_sums, b_ex_off, b_ex_imgoff, b_ex_starts;   // device export (kernels_export.h): row lengths, sums / offsets per 64 rows, offsets per image
    size_t rows_lds_set = 0;            // dynamic LDS opt-in of k_patch_large_rows on THIS device
    // persistent grids of the LDS-window kernels: exactly as many blocks as the device holds at once (CUs x resident
@@ -1258,12 +1260,19 @@ const int32_t *fetch_hessian_starts(hesaff_ctx *c, int B)
    return hs;
 }
 
+// What a batch produced besides the KeyRec records in b_out: B + 1 Hessian starts and B + 1 descriptor starts (image b owns
+// [starts[b], starts[b + 1])) in pinned host memory, and the descriptor starts on the device.  Valid until the next batch.
+struct BatchResult {
+   const int32_t *hessian_starts, *desc_starts;
+   const int32_t *d_desc_starts;
+};
+
 // Everything after the Hessian list of a batch is complete - by detection (run_batch) or from the caller's records (run_describe):
 // affine shape, patches and descriptors over image groups on three streams, the stable compaction into KeyRec records, the
 // descriptor starts, and the wait for the end of the batch.  hs: fetch_hessian_starts' block.  with_affine = false: the affine
 // output is already in place (HESAFF_FROM_SHAPES), k_affine is not launched.  The affine stream starts behind ev_detect_done,
 // which the caller has recorded after the last kernel that writes a plane k_affine reads.
-void run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, int tt, int B, int H, int W, const int32_t *hs, bool with_affine)
+BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, int tt, int B, int H, int W, const int32_t *hs, bool with_affine)
 {
    hipStream_t st = c->stream;
    uint32_t *cnt = s.counters;
@@ -1360,24 +1369,26 @@ void run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, int tt, 
                       c->geo.b_starts.as<int32_t>() + (B + 1));
    tm.end(t);
    tm.end(tt);
-   c->h_starts = (int32_t *)c->h_small_end.ensure_small(((size_t)2 * (B + 1) + 8) * 4);
-   HIP_TRY(hipMemcpyAsync(c->h_starts, c->geo.b_starts.p, (size_t)2 * (B + 1) * 4, hipMemcpyDeviceToHost, st));
-   HIP_TRY(hipMemcpyAsync(c->h_starts + 2 * (B + 1), cnt, 8 * 4, hipMemcpyDeviceToHost, st));
+   // Hessian starts [B + 1], descriptor starts [B + 1], counters [8]
+   int32_t *h_starts = (int32_t *)c->h_small_end.ensure_small(((size_t)2 * (B + 1) + 8) * 4);
+   HIP_TRY(hipMemcpyAsync(h_starts, c->geo.b_starts.p, (size_t)2 * (B + 1) * 4, hipMemcpyDeviceToHost, st));
+   HIP_TRY(hipMemcpyAsync(h_starts + 2 * (B + 1), cnt, 8 * 4, hipMemcpyDeviceToHost, st));
    HIP_TRY(hipEventRecord(c->ev_batch_done, st));
    const double dbg_cb = c->debug ? thread_cpu_ms() : 0.0;
    hs_wait_event(c->ev_batch_done);
    if (c->debug) fprintf(stderr, "[hesaff] run_batch: caller's CPU inside the wait for the end of the batch %.2f ms\n", thread_cpu_ms() - dbg_cb);
    HIP_TRY(hipGetLastError());
    if (c->profiling) collect_timings(c, tm, B);
-   const int32_t *cn = c->h_starts + 2 * (B + 1);
+   const int32_t *cn = h_starts + 2 * (B + 1);
    if (cn[2] != 0 || (uint32_t)cn[1] > c->cap)
       throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded; raise hesaff_params.max_kpts_per_mpx");
    if (cn[6] != 0) throw HsError(HESAFF_ERR_NOMEM, "large-window row buffer exceeded (internal bound violated)");
+   return {h_starts, h_starts + (B + 1), c->geo.b_starts.as<int32_t>() + (B + 1)};
 }
 
 // Whole hot path on a device-resident batch.  Leaves ordered KeyRec records in b_out and
-// per-image start offsets (hessian: b_starts[0..B], desc: b_starts[B+1..2B+1]).
-void run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
+// per-image start offsets (hessian: b_starts[0..B], desc: b_starts[B+1..2B+1]; BatchResult: their host copies).
+BatchResult run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
 {
    plan(c, B, H, W);
    c->ev_used = 0;
@@ -1386,7 +1397,7 @@ void run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
    const int tt = tm.begin(T_TOTAL);
    run_detection(c, src, B, s, tm, false, nullptr);
    // the one host round trip of a batch
-   run_keypoint_stages(c, s, tm, tt, B, H, W, fetch_hessian_starts(c, B), true);
+   return run_keypoint_stages(c, s, tm, tt, B, H, W, fetch_hessian_starts(c, B), true);
 }
 
 // hesaff_describe_regions on a device-resident chunk: the caller's records take the place of detection's list.  d_block (device,
@@ -1396,7 +1407,7 @@ void run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
 // from = HESAFF_FROM_SHAPES: the grey plane alone (parity mode) - fast mode 2 builds the scale space too, k_patch_pyramid samples it -
 // and the affine output from the records.  Leaves what run_batch leaves.
 inline size_t describe_records_offset(int B) { return (((size_t)B + 1) * 4 + 255) & ~(size_t)255; }
-void run_describe(hesaff_ctx *c, const SrcImages &src, int B, int H, int W, const uint8_t *d_block, uint32_t n_rec, int from)
+BatchResult run_describe(hesaff_ctx *c, const SrcImages &src, int B, int H, int W, const uint8_t *d_block, uint32_t n_rec, int from)
 {
    plan(c, B, H, W);
    if (n_rec > c->cap) throw HsError(HESAFF_ERR_CAPACITY, "more records than the keypoint capacity; raise hesaff_params.max_kpts_per_mpx");
@@ -1427,7 +1438,7 @@ void run_describe(hesaff_ctx *c, const SrcImages &src, int B, int H, int W, cons
       else hipLaunchKernelGGL(k_gray_plane<0>, grid, dim3(256), 0, st, src.p, src.img_stride, src.row_stride, c->gray);
    }
    HIP_TRY(hipEventRecord(c->ev_detect_done, st));   // the affine stream starts behind the planes
-   run_keypoint_stages(c, s, tm, tt, B, H, W, hs, !shapes);
+   return run_keypoint_stages(c, s, tm, tt, B, H, W, hs, !shapes);
 }
 
 // ---- exportKeypoints on the device (kernels_export.h) ----

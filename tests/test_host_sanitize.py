@@ -228,10 +228,11 @@ ENGINE_SRC = [os.path.join(ROOT, "hesaff_amd", "csrc", "hostio.cpp"), os.path.jo
 
 @pytest.mark.parametrize("san", ["thread", "address,undefined"])
 def test_file_pipeline_threads_under_sanitizers(san, tmp_path):
-    """The host-only half of hesaff_process_files (hesaff_amd/csrc/chunk_engine.h: decoder threads, the bounded look-ahead window,
-    chunk formation, the ring of three result blocks, writer threads, per-file status) under ThreadSanitizer and under
-    AddressSanitizer + UBSan, with the device replaced by a mock loop of the same threading shape (tests/native/
-    engine_sanitize.cpp).  The GPU suite runs the same code for its results; this run is for its races and lifetimes."""
+    """The host-only half of the chunk engine (hesaff_amd/csrc/chunk_engine.h: the chunk loop of every host entry point with its
+    staging thread, refusal rule and error path; decoder threads, the bounded look-ahead window, chunk formation, the ring of three
+    result blocks, writer threads, per-file status) under ThreadSanitizer and under AddressSanitizer + UBSan.  The loop is the
+    product's own (run_chunk_loop); only the object it drives, which makes the HIP calls in the library, is a mock (MockDevice,
+    tests/native/engine_sanitize.cpp).  The GPU suite runs the same code for its results; this run is for its races and lifetimes."""
     import numpy as np
     if shutil.which("g++") is None:
         pytest.skip("g++ not available")
@@ -249,12 +250,15 @@ def test_file_pipeline_threads_under_sanitizers(san, tmp_path):
     bad = tmp_path / "bad.pgm"; bad.write_bytes(b"P5\n9 9\n255\nxx")
     names.insert(7, str(bad)); names.append(str(bad))
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1:exitcode=66", ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1")
-    # fmt + 4: the mock device hands the writers finished rows (ChunkDone::text / bin) like the GPU formatter does
-    for max_batch, dt, wt, fmt in ((1, 1, 1, 1), (4, 3, 3, 3), (64, 8, 2, 2), (3, 2, 8, 1), (4, 2, 3, 7), (2, 1, 2, 5), (8, 2, 2, 6), (4, 3, 2, 16 + 7), (2, 2, 2, 16 + 2)):
+
+    def remove_outputs():
         for n_ in names:
             for ext in (".hesaff.sift", ".hesaff.bin"):
                 if os.path.exists(n_ + ext):
                     os.remove(n_ + ext)
+    # fmt + 4: the mock device hands the writers finished rows (ChunkDone::text / bin) like the GPU formatter does
+    for max_batch, dt, wt, fmt in ((1, 1, 1, 1), (4, 3, 3, 3), (64, 8, 2, 2), (3, 2, 8, 1), (4, 2, 3, 7), (2, 1, 2, 5), (8, 2, 2, 6), (4, 3, 2, 16 + 7), (2, 2, 2, 16 + 2)):
+        remove_outputs()
         r = subprocess.run([exe, str(max_batch), str(dt), str(wt), str(fmt)] + names, capture_output=True, text=True, env=env, timeout=600)
         assert r.returncode == 0, (max_batch, dt, wt, fmt, r.stdout[-500:], r.stderr[-4000:])
         assert "files=47 written=45 unreadable=2 other=0" in r.stdout, r.stdout
@@ -299,3 +303,26 @@ def test_file_pipeline_threads_under_sanitizers(san, tmp_path):
     for max_batch, n_img in ((1, 7), (4, 45), (8, 64)):
         r = subprocess.run([exe, "array", str(max_batch), str(n_img)], capture_output=True, text=True, env=env, timeout=600)
         assert r.returncode == 0, (max_batch, n_img, r.stdout[-500:], r.stderr[-4000:])
+    # The device refuses (HESAFF_ERR_CAPACITY) every chunk with an image whose index i has i % 11 == 3 (fmt + 32).  A file list notes
+    # the refusal per image and goes on: every file ends up written, unreadable or rejected with that code (the driver's exit code),
+    # at least the images 3, 14, 25 and 36 and at most their 4 chunks of 4 images are rejected, and the rows of the written files
+    # are the rows of the chunks that were not refused.
+    remove_outputs()
+    r = subprocess.run([exe, "4", "3", "3", str(32 + 7)] + names, capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, (r.stdout[-500:], r.stderr[-4000:])
+    rejected = int(r.stdout.split("rejected=", 1)[1].split()[0])
+    assert 4 <= rejected <= 16, r.stdout
+    assert "files=47 written=%d unreadable=2 other=0" % (45 - rejected) in r.stdout, r.stdout
+    rows = int(r.stdout.strip().rsplit("rows=", 1)[1])
+    outputs = [n_ + ".hesaff.sift" for n_ in names if os.path.exists(n_ + ".hesaff.sift")]
+    assert len(outputs) == 45 - rejected
+    assert sum(int(open(o, "rb").read().split(b"\n", 2)[1]) for o in outputs) == rows
+    # ... an array call fails as a whole with that code (ArrayIO::failed is false): the staging thread is joined, nothing leaks
+    r = subprocess.run([exe, "array", "4", "45", "refuse"], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, (r.stdout[-500:], r.stderr[-4000:])
+    # A device error on the third chunk (fmt + 64), while the staging thread holds the fourth: the loop joins that thread, idles the
+    # device and lets the error through with its message; the driver then shuts the pools down as hesaff_process_files does
+    remove_outputs()
+    r = subprocess.run([exe, "4", "3", "3", str(64 + 7)] + names, capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, (r.stdout[-500:], r.stderr[-4000:])
+    assert "device_error came_through=1" in r.stdout, r.stdout

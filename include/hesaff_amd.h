@@ -59,7 +59,9 @@ typedef struct hesaff_ctx hesaff_ctx;
 typedef struct hesaff_params {
    float threshold;            /* 16/3  pyramid.h:37, hesaff.cpp:30   */
    float edgeEigenValueRatio;  /* 10    pyramid.h:38                  */
-   float initialSigma;         /* 1.6   pyramid.h:36 (also affine.h:40) */
+   float initialSigma;         /* 1.6   pyramid.h:36 only: PyramidParams::initialSigma.  AffineShapeParams::initialSigma
+                                *       (affine.h:40, read at affine.cpp:40) stays 1.6 whatever this is, as in the reference's
+                                *       main, which sets neither (tests/test_reference.py pins this reading) */
    int maxIterations;          /* 16    affine.h:39, hesaff.cpp:31    */
    float convergenceThreshold; /* 0.05  affine.h:41                   */
    float mrSize;               /* 3*sqrt(3) affine.h:44, hesaff.cpp:32 */

@@ -8,13 +8,15 @@
 // cpu_baseline leg can check / time the HIP path against it; nothing under hesaff_amd/
 // may include, link or call it.
 //
-// PARITY STATUS: *parity unpinned*.  The reference ships no tests, fixtures or golden
-// vectors (14 files, none of them data), and it cannot be built in this image: all five
-// sources include <cv.h>/<highgui.h> of OpenCV >= 2.3.1 (README:17, Makefile:2), which is
-// not installed and is not vendored in /root/reference.  The separable Gaussian
-// (cv::GaussianBlur, called at helpers.cpp:287,294) is therefore restated here from
-// OpenCV 2.4's published algorithm (imgproc/src/smooth.cpp getGaussianKernel +
-// filter.cpp RowFilter / SymmRowSmallFilter / SymmColumnFilter, scalar == SSE order).
+// PARITY STATUS: pinned to the compiled reference, up to OpenCV.  The reference ships no
+// tests, fixtures or golden vectors, but its five sources compile unmodified against the
+// OpenCV stand-in in oracle/cvshim/ (`make ref`), and tests/test_reference.py compares this
+// file with that build bit for bit.  What stays unpinned is OpenCV itself: the separable
+// Gaussian (cv::GaussianBlur, called at helpers.cpp:287,294) is restated, here and in the
+// stand-in alike, from OpenCV 2.4's published algorithm (imgproc/src/smooth.cpp
+// getGaussianKernel + filter.cpp RowFilter / SymmRowSmallFilter / SymmColumnFilter, scalar
+// == SSE order); and doubleImage (helpers.cpp:297-329), which reads outside its buffer in
+// the reference, is restated as its evident intent and compared with nothing.
 // libm calls (expf, powf, atan2f, sqrt) go to the host glibc exactly as the reference's
 // do.  Build with -ffp-contract=off (the reference's own Makefile targets baseline x86-64,
 // which has no FMA).

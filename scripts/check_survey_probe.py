@@ -4,8 +4,9 @@
 The survey compiled the five reference sources unmodified against a throw-away OpenCV shim and
 wrote down, for reproducible inputs (App. C.3), the md5 of every input PGM and the candidate /
 Hessian-keypoint / descriptor counts of the reference's run (App. C.4, C.6, C.9).  Nothing of
-that harness was kept and the reference cannot be rebuilt here without stand-in headers, so
-those recorded numbers are the only trace of the real reference's behaviour in this repo.
+that harness was kept; those recorded numbers are the survey's own trace of the reference's
+behaviour.  (The reference is rebuilt against oracle/cvshim/ since, and tests/test_reference.py
+compares the oracle with that build directly; this script stays as the check against the record.)
 This script regenerates the inputs (the md5 prefixes must match App. C.3), runs
 oracle/libhesaff_oracle.so on them and compares the counts.  FMA contraction alone moves these
 counts (App. C.5: 4763 -> 4760 at VGA), so equal counts at three sizes are strong evidence that

@@ -2,16 +2,19 @@
 """Regenerates tests/golden/*.  Run from the repo root:  python tests/golden/make_golden.py
 
 WHAT THESE FIXTURES ARE: regression vectors produced by the repo's own CPU oracle
-(oracle/hesaff_oracle.cpp) on small deterministic images.  They are NOT outputs of the
-reference binary: perdoch/hesaff cannot be built in this image (all sources include
-OpenCV's <cv.h>, which is neither installed nor vendored) and it ships no golden vectors
-of its own.  The fixtures pin the oracle against accidental change and give the GPU tests
-byte-exact files to reproduce.
+(oracle/hesaff_oracle.cpp) on small deterministic images.  The reference ships no golden
+vectors of its own.  The fixtures pin the oracle against accidental change and give the GPU
+tests byte-exact files to reproduce.  The *.hesaff.sift files among them are, byte for byte,
+what the compiled reference (oracle/_ref/hesaff_ref: its sources, unmodified, against the
+OpenCV stand-in oracle/cvshim/) writes for the same PGM: tests/test_reference.py::test_whole_files
+checks that wherever that build exists.  The fixtures the compiled reference itself wrote are
+ref_*.npz and the "reference" block of manifest.json (make_ref_golden.py); this script keeps
+that block as it finds it.
 
-The one fixture that ties the oracle to the COMPILED reference is probe_vga.pgm: the 640x480
-input of SURVEY.md Appendix C.3 (md5 74f828b5...), for which the survey recorded the md5 of the
-reference's own output file (e004ba88..., App. C.4) and its call counts (App. C.6).  The oracle
-reproduces both (tests/test_oracle.py::test_survey_probe_*, scripts/check_survey_probe.py).
+probe_vga.pgm is the 640x480 input of SURVEY.md Appendix C.3 (md5 74f828b5...), for which the
+survey recorded the md5 of the reference's own output file (e004ba88..., App. C.4) and its call
+counts (App. C.6).  The oracle reproduces both (tests/test_oracle.py::test_survey_probe_*,
+scripts/check_survey_probe.py), and so does oracle/_ref/hesaff_ref.
 """
 import hashlib
 import json
@@ -73,7 +76,13 @@ def main():
                              "sift_md5": hashlib.md5(o.export_text()).hexdigest(),
                              "survey_recorded": {"pgm_md5_prefix": "74f828b5", "sift_md5_prefix": "e004ba88",
                                                  "candidates": 5281, "hessian": 4763, "descriptors": 4183}}
-    with open(os.path.join(HERE, "manifest.json"), "w") as f:
+    path = os.path.join(HERE, "manifest.json")
+    if os.path.exists(path):   # the compiled reference's block belongs to make_ref_golden.py
+        with open(path) as f:
+            old = json.load(f)
+        if "reference" in old:
+            manifest["reference"] = old["reference"]
+    with open(path, "w") as f:
         json.dump(manifest, f, indent=1, sort_keys=True)
     print(json.dumps(manifest, indent=1, sort_keys=True))
 

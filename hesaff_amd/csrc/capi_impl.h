@@ -290,14 +290,6 @@ const char *describe_bad_record(const hesaff_region &r, int from, int n_oct)
    return nullptr;
 }
 
-// octaves of the pyramid of an H x W image (plan_buffers builds the same sequence: pyramid.cpp:283-291)
-int pyramid_octaves(int H, int W, int up)
-{
-   int n = 0;
-   for (int r = H << up, cc = W << up; r > 2 * HS_BORDER + 2 && cc > 2 * HS_BORDER + 2 && n < HS_MAX_OCTAVES; r /= 2, cc /= 2) n++;
-   return n;
-}
-
 void ensure_copy_streams(hesaff_ctx *c)
 {
    if (c->h2d_stream) return;
@@ -411,7 +403,7 @@ struct ChunkDevice {
       }
       if (q.from) {
          // the chunk's records travel with it: [B + 1 starts][records] into pinned memory, each record checked on the way, one copy in
-         const int n_oct = pyramid_octaves(q.H, q.W, c->up);
+         const int n_oct = (int)pyramid_geometry(q.H, q.W, c->up).oct.size();
          unsigned long long n_rec = 0;
          for (int cnt : q.region_count) n_rec += (unsigned long long)cnt;
          if (n_rec > 0x7fffffffull) throw HsError(HESAFF_ERR_CAPACITY, "more records in a chunk than 32-bit indices hold");
@@ -970,11 +962,11 @@ int hesaff_stage_hessian_keypoints(hesaff_ctx *c, const uint8_t *gray, int rows,
    StageTimer tm(c);
    Lists s = make_lists(c);
    run_detection(c, SrcImages::u8(c->b_input.p, 1, (long long)rows * cols, cols), 1, s, tm, false, nullptr);
-   uint32_t cn[8];
-   HIP_TRY(hipMemcpyAsync(cn, s.counters, sizeof cn, hipMemcpyDeviceToHost, c->stream));
+   CounterHead cn;
+   HIP_TRY(hipMemcpyAsync(&cn, &s.counters->head, sizeof cn, hipMemcpyDeviceToHost, c->stream));
    finish_stream(c);
-   if (cn[2] != 0 || cn[1] > c->cap) throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded");
-   const int n = (int)cn[3];
+   if (cn.overflow != 0 || cn.rec > c->cap) throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded");
+   const int n = (int)cn.hess_total;
    *count = n;
    const int m = std::min(n, cap);
    if (m > 0 && f && iv) {
@@ -1060,25 +1052,19 @@ int hesaff_stage_normalize_affine(hesaff_ctx *c, const float *img, int rows, int
    // feed A through the affine-output slot as an already rectified matrix: k_prepare_patch
    // would rectify again, so do its arithmetic (mrScale, P0, border test) via a dedicated kernel
    HIP_TRY(hipMemcpyAsync(s.pw.A, A, (size_t)n * 16, hipMemcpyHostToDevice, st));
-   HIP_TRY(hipMemsetAsync(s.counters, 0, 64 * 4, st));
+   HIP_TRY(hipMemsetAsync(s.counters, 0, sizeof(CounterBlock), st));
    uint32_t nn = (uint32_t)n;
-   HIP_TRY(hipMemcpyAsync(s.counters + 3, &nn, 4, hipMemcpyHostToDevice, st));
-   hipLaunchKernelGGL(k_prepare_patch_given_A, dim3((n + 255) / 256), dim3(256), 0, st, s.hl, (const uint32_t *)(s.counters + 3), rows, cols,
+   HIP_TRY(hipMemcpyAsync(&s.counters->head.hess_total, &nn, 4, hipMemcpyHostToDevice, st));
+   hipLaunchKernelGGL(k_prepare_patch_given_A, dim3((n + 255) / 256), dim3(256), 0, st, s.hl, (const uint32_t *)&s.counters->head.hess_total, rows, cols,
                       c->consts, c->tables, s.pw);
    c->b_patches.ensure((size_t)n * HS_PATCH_PIX * 4);
    HIP_TRY(hipMemsetAsync(c->b_patches.p, 0, (size_t)n * HS_PATCH_PIX * 4, st));
    // T' rows of the huge windows: bounded by the sum of their sides
-   unsigned long long large_rows = 0;
-   c->batch_max_p = 0;
-   for (int i = 0; i < n; i++) {
-      const float mrScale = ceilf(sc[i] * c->consts.mrSize);
-      const long long P = (mrScale < 1.0e6f) ? 2 * (long long)mrScale + 3 : 0;
-      if (P > HS_BIN3_PMAX && P <= c->max_p0 + 2) { large_rows += (unsigned long long)P; c->batch_max_p = std::max(c->batch_max_p, (int)P); }
-   }
-   if (large_rows > 0xffffffffull) throw HsError(HESAFF_ERR_NOMEM, "too many huge windows in one call");
-   run_patch_stage(c, s, c->gray, c->b_patches.as<float>(), 0, (uint32_t)large_rows);
+   const LargeRows lr = host_large_rows(sc.data(), n, c->consts.mrSize, c->max_p0);
+   c->batch_max_p = lr.max_p;
+   run_patch_stage(c, s, c->gray, c->b_patches.as<float>(), 0, lr.rows);
    uint32_t ovf = 0;
-   HIP_TRY(hipMemcpyAsync(&ovf, s.counters + 6, 4, hipMemcpyDeviceToHost, st));
+   HIP_TRY(hipMemcpyAsync(&ovf, &s.counters->head.row_overflow, 4, hipMemcpyDeviceToHost, st));
    HIP_TRY(hipMemcpyAsync(alive.data(), s.pw.alive, (size_t)n * 4, hipMemcpyDeviceToHost, st));
    if (patches) HIP_TRY(hipMemcpyAsync(patches, c->b_patches.p, (size_t)n * HS_PATCH_PIX * 4, hipMemcpyDeviceToHost, st));
    finish_stream(c);

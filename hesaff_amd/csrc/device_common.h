@@ -8,14 +8,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hmath.h"
+#include "plan_consts.h"   // HS_PATCH, HS_BORDER, HS_NSCALES, HS_MAX_OCTAVES and the other constants the host plan shares
 
-#define HS_PATCH 41                 // patchSize, affine.h:42 / siftdesc.h:30
 #define HS_PATCH_PIX (41 * 41)
 #define HS_SMM 19                   // smmWindowSize, affine.h:43
 #define HS_SMM_PIX (19 * 19)
-#define HS_BORDER 5                 // PyramidParams::border, pyramid.h:39
-#define HS_NSCALES 3                // numberOfScales, pyramid.h:35
-#define HS_MAX_OCTAVES 16
 
 // A batch of equally sized float planes: [img][rows][pitch]
 struct DPlane {

@@ -315,8 +315,7 @@ __global__ __launch_bounds__(64) void k_affine_stage(DPlane P, const float *__re
 // interpolateCheckBorders.  Thread per keypoint.  Survivors are binned by window size P so
 // that each patch kernel launch has a uniform LDS footprint.
 // ---------------------------------------------------------------------------------------
-#define HS_NBINS 5   // window size P: 0: <=41, 1: <=64 (full blur in LDS); 2: <=128 (row-streamed, LDS); 3: <=512, 4: larger (row-streamed, HBM)
-#define HS_BIN3_PMAX 512
+// (HS_NBINS bins with HS_BIN3_PMAX as the last bound: plan_consts.h)
 __host__ __device__ inline int hs_patch_bin(int P) { return P <= 41 ? 0 : (P <= 64 ? 1 : (P <= 128 ? 2 : (P <= HS_BIN3_PMAX ? 3 : 4))); }
 
 struct PatchWork {
@@ -341,7 +340,8 @@ __device__ __forceinline__ int hs_window_p0(float s, float mrSize)
 // Upper bound, per image, of the T' rows the huge windows (last bin) of its keypoints need: depends on the scales
 // only, so it is known right after detection and the host can size / group the patch stage without waiting for the
 // affine iteration.  rows[b] += P for every Hessian keypoint whose window falls into the last bin.
-// rows[nimg + 1] (one past the per-image sums) receives the largest such P of the batch: the row kernel's LDS is sized for the
+// rows[nimg + 1] (one past the per-image sums: StartsBlock::largest_window() of batch_plan.h, rows being its large_rows()) receives the
+// largest such P of the batch: the row kernel's LDS is sized for the
 // windows that exist, not for the largest the image could hold.
 // A window wider than the tabulated taps (max_p0) is never extracted (k_prepare_patch rejects it): it adds no rows.
 __global__ __launch_bounds__(256) void k_image_large_rows(HessList hl, const uint32_t *__restrict__ n_ptr, float mrSize, uint32_t *__restrict__ rows, int nimg,

@@ -34,7 +34,7 @@
 
 #define HS_PATCH_ARR 1684  // 1681 rounded up to a multiple of 4 floats
 #define HS_PATCH_PIX_IT 7  // ceil(1681 / 256)
-#define HS_NEED 82         // blurred columns (and rows) the 41x41 resample reads: 2 per output
+// (HS_NEED, the 82 blurred columns and rows the 41x41 resample reads: plan_consts.h)
 
 struct PatchIO {
    DPlane image;         // original float image batch (normalizeAffine samples the ORIGINAL image, hesaff.cpp:82)
@@ -894,7 +894,7 @@ __global__ __launch_bounds__(256) void k_patch_mid(HessList hl, PatchWork pw, Pa
 // The item count and the prefix stay on the device; the host only supplies an upper bound of the rows
 // (k_image_large_rows) to size the T' buffer.
 // ---------------------------------------------------------------------------------------
-#define HS_LARGE_CHUNK 18   // consecutive window rows per wavefront task (a multiple of three: the three-row form below)
+// (HS_LARGE_CHUNK, the window rows per wavefront task - a multiple of three for the three-row form below: plan_consts.h)
 #define HS_LARGE_NIT3 2     // gathers in flight per row of the three-row form
 
 // dynamic LDS: per wave  nrow x srow_stride floats (window rows + borders)  +  tap_stride floats (a tap area that is no longer read: the

@@ -296,7 +296,7 @@ struct CandRec {
    uint32_t pad[3];
 };
 #define HS_CAND_HOLE 0xffffffffu
-#define HS_CAND_BLOCK 64u   // slots a wavefront reserves at a time (one global atomic per 64 candidates)
+// (HS_CAND_BLOCK, the slots a wavefront reserves at a time: plan_consts.h)
 struct CandList {
    uint32_t *count;   // device counter (slots handed out, holes included)
    CandRec *items;
@@ -678,7 +678,7 @@ __global__ void k_image_counts(const uint32_t *__restrict__ prefix, long long st
 // byte about once.  No block-level synchronisation: the 4 waves of a block are independent.
 // grid (ceil(strips/4), bands, B), block 256.
 // ---------------------------------------------------------------------------------------
-#define BM_STRIP 248
+// (BM_STRIP: plan_consts.h)
 #define BM_ROWBUF 272   // floats: 8 + 256 + 8
 
 typedef float v2f __attribute__((ext_vector_type(2)));
@@ -957,7 +957,7 @@ struct FivePlanes { DPlane R[5]; };
 // levels instead of ~400.  Candidates are collected in LDS and flushed with one global atomic.
 // grid (ceil(cols/248), ceil(rows/band), B), block 64.
 // ---------------------------------------------------------------------------------------
-#define EXM_STRIP 248
+// (EXM_STRIP: plan_consts.h)
 #define EXM_RS 5      // ring rows: 3 under test + EXM_RS - 3 in flight (measured: profiles/r05_notes.md)
 #define EXM_AHEAD (EXM_RS - 3)
 

@@ -39,6 +39,7 @@
 #include "kernels_export.h"
 #include "kernels_jpeg.h"
 #include "chunk_engine.h"
+#include "batch_plan.h"
 
 namespace hesaff {
 OctaveSchedule make_schedule(float initialSigma, bool upscale)
@@ -82,6 +83,7 @@ static thread_local std::string g_create_error;
    } while (0)
 
 using hesaff_engine::HsError;
+using namespace hesaff_plan;   // batch_plan.h: the layouts and the launch arithmetic of a batch
 
 // Host wait for a HIP event WITHOUT a spinning core.  hipEventSynchronize spins in this runtime even on events created with
 // hipEventBlockingSync (measured in round 5 with CLOCK_THREAD_CPUTIME_ID around the call: 96 ms of CPU for a 96 ms wait, one busy core per
@@ -237,19 +239,7 @@ struct DevEvent {
    operator hipEvent_t() const { return e; }
 };
 
-struct OctGeom {
-   int rows, cols, pitch;
-   long long word_base;   // first bitmask word of this octave inside one image
-   int words_per_row;
-};
-
-static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
 #define HS_NSIDE 4   // side streams of the patch stage (one per window-size bin 0..3)
-#define HS_LARGE_NW 2      // wavefronts per block of k_patch_large_rows' three-row form at most: blocks of 40 KB find room beside the other
-                           // stages' kernels where blocks of 80 KB wait (against as many as fit: dense step 786 -> 773 ms, photographs 393 -> 383)
-#define HS_LARGE_SPLIT 1280   // windows up to this side in a launch of their own when the batch holds larger ones (k_patch_large_rows: split at
-                              // 1024 / 1280 / 1536: 7.23 / 7.15 / 7.94 ms per 32 photograph mosaics, profiles/r06_notes.md)
 #define HS_AFF_BLOCKS_PER_CU 8   // persistent k_affine blocks per CU (19 KB of LDS each: 8 resident).  Alone on the device 64 / 128 blocks per CU
                                  // are 4 % faster (20.7 / 20.6 vs 21.6 ms), beside the other stages' kernels they make the step 3.5 % slower
                                  // (453 vs 438 ms at B = 128): the queued blocks take every slot that frees up
@@ -323,9 +313,7 @@ struct hesaff_ctx {
    std::vector<DPlane> L;   // [octave*3 + level]
    DPlane gray, upimg, L3, R[5];
    // lists
-   DevBuf b_counters;       // uint32: [0] cand_count [1] rec_count [2] overflow [3] hess_total [4] desc_total [5] group end
-                            //         [6] T' row overflow, [8..12] bin_count, [24..28] bin work counters,
-                            //         [32..32+HS_MAX_OCTAVES) octave rec starts
+   DevBuf b_counters;       // one CounterBlock (batch_plan.h)
    DevBuf b_patches, b_stage;
    DevBuf b_input;          // staging for host images (stage API)
    // The host entry points: chunks of max_batch images are pipelined -- pinned staging + H2D of chunk k+1 and D2H of chunk k-1 run
@@ -593,19 +581,6 @@ size_t small_extract_lds_bytes(int bin) { return (size_t)(bin == 0 ? SmallGeom<0
 size_t mid_lds_bytes() { return (size_t)MidGeom<HS_MID_PMAX>::FLOATS * 4; }
 size_t big_lds_bytes() { return (size_t)MidGeom<HS_BIN3_PMAX>::FLOATS * 4; }
 
-// geometry of the large-window row kernel for windows up to pmax: LDS per wave = window row + replicated borders + taps
-constexpr size_t HS_LDS_PER_CU = 160 * 1024;
-struct LargeGeom { int srow_stride, tap_stride; size_t lds; };   // lds: bytes for a block of FOUR wavefronts
-LargeGeom large_geom(int pmax)
-{
-   LargeGeom g;
-   // window row + r replicated border samples on each side, r = K/2 <= (6 * 1.5 * P0/41 + 2) / 2
-   g.srow_stride = round_up((int)(pmax * 1.23) + 16, 64);
-   g.tap_stride = round_up((int)(pmax * 0.22) + 8, 64);   // K = odd(int(6 * 1.5 * P0/41 + 1))
-   g.lds = (size_t)4 * (g.srow_stride + g.tap_stride) * 4;
-   return g;
-}
-
 // Dynamic-LDS opt-ins are per device: applied when a context is created on its device (hesaff_create) and, for the
 // large-window kernel whose need depends on the image size, in plan().
 template <class KERNEL> uint32_t resident_grid(hesaff_ctx *c, KERNEL kern, int threads, size_t dyn_lds, uint32_t fallback_per_cu)
@@ -670,26 +645,15 @@ void plan_buffers(hesaff_ctx *c, int B, int H, int W)
    const int PH = H << c->up, PW = W << c->up;   // first pyramid level
    // the cached geometry describes buffers that are about to be replaced: a failure below must not leave it valid
    c->B = c->H = c->W = 0;
-   c->oct.clear();
    c->L.clear();
-   long long words = 0;
-   size_t L_floats = 0;
    {
-      int r = PH, cc = PW;
-      const int minSize = 2 * HS_BORDER + 2;   // pyramid.cpp:283
-      while (r > minSize && cc > minSize) {
-         OctGeom g;
-         g.rows = r; g.cols = cc; g.pitch = round_up(cc, 64);
-         g.words_per_row = (cc + 63) / 64;
-         g.word_base = words;
-         words += (long long)HS_NSCALES * r * g.words_per_row;
-         L_floats += (size_t)3 * B * r * g.pitch;
-         c->oct.push_back(g);
-         r /= 2; cc /= 2;
-         if ((int)c->oct.size() >= HS_MAX_OCTAVES) break;
-      }
+      PyramidGeom pg = pyramid_geometry(H, W, c->up);
+      c->oct = std::move(pg.oct);
+      c->words_per_image = pg.words_per_image;
    }
-   c->words_per_image = words;
+   const long long words = c->words_per_image;
+   size_t L_floats = 0;
+   for (const OctGeom &g : c->oct) L_floats += (size_t)3 * B * g.rows * g.pitch;
    const int pitch0 = round_up(W, 64);
    const size_t plane0 = (size_t)B * H * pitch0;
    c->geo.b_gray.ensure(plane0 * 4);
@@ -718,33 +682,19 @@ void plan_buffers(hesaff_ctx *c, int B, int H, int W)
       // a new block is filled once before its first use (run_detection).  Pointer AND size: ensure()'s out-of-memory path frees the old
       // block first, and the larger one may come back at the same address with a tail that was never filled
       if (c->geo.b_map.p != before || c->geo.b_map.bytes != before_bytes) c->map_clean = false;
-      int kb = 1;
-      while (kb < 32 && (3ull * (unsigned long long)PH * PW) > (1ull << kb)) kb++;
+      const int kb = order_key_bits(PH, PW);
       if (kb != c->map_kbits) { c->map_kbits = kb; c->map_clean = false; }   // (another key width: epochs of the old one mean nothing)
    }
    const long long total_words = (long long)B * words;
    c->geo.b_bitmask.ensure(std::max<size_t>((size_t)total_words * 8, 16));
    c->geo.b_prefix.ensure(std::max<size_t>((size_t)(total_words + 1) * 4, 16));
-   double mpx = (double)B * PH * PW / 1.0e6;   // capacity per megapixel of the first pyramid level
-   double capd = mpx * (double)c->par.max_kpts_per_mpx;
-   if (capd < 4096) capd = 4096;
-   if (capd > 2.0e9) throw HsError(HESAFF_ERR_ARG, "batch too large for 32-bit keypoint indices");
-   c->cap = ((uint32_t)capd + 63u) & ~63u;   // a multiple of 64: the arrays carved out of one buffer (cap entries each) stay 16-byte aligned
+   c->cap = keypoint_capacity(B, PH, PW, (double)c->par.max_kpts_per_mpx);
    const size_t cap = c->cap;
    const long long scan_items = std::max<long long>(total_words, (long long)cap);
    c->geo.b_blocksums.ensure((size_t)((scan_items + SCAN_BLOCK - 1) / SCAN_BLOCK + 1) * 4);
-   c->b_counters.ensure(64 * 4);
-   {
-      // candidate slots: the keypoint capacity + what the wavefronts of k_extrema_march may leave unused of their blocks of 64
-      // (octave 0 has the most wavefronts: one per 248-column strip and 32-row band at least)
-      const unsigned long long waves0 = (unsigned long long)((PW + EXM_STRIP - 1) / EXM_STRIP) * (unsigned long long)(PH / 32 + 1) * (unsigned long long)B;
-      // + cap / 8: a wavefront also abandons the rest of its block whenever a ballot group does not fit (holes grow with the number of
-      // blocks, not only with the number of wavefronts).  96 bytes per slot: 11 GB per 256 UHD images at the default max_kpts_per_mpx
-      const unsigned long long cc = (unsigned long long)cap + (unsigned long long)cap / 8 + HS_CAND_BLOCK * waves0;
-      if (cc > 0xfffffff0ull) throw HsError(HESAFF_ERR_ARG, "batch too large for 32-bit candidate indices");
-      c->cand_cap = (uint32_t)cc;
-      c->geo.b_cand.ensure((size_t)cc * sizeof(CandRec));
-   }
+   c->b_counters.ensure(sizeof(CounterBlock));
+   c->cand_cap = candidate_capacity(c->cap, B, PH, PW);
+   c->geo.b_cand.ensure((size_t)c->cand_cap * sizeof(CandRec));
    c->geo.b_rec_f.ensure(cap * 4 * 4);
    c->geo.b_rec_i.ensure(cap * 4 * 4);
    c->geo.b_rec_w.ensure(cap * 8);
@@ -756,7 +706,7 @@ void plan_buffers(hesaff_ctx *c, int B, int H, int W)
    c->geo.b_rank.ensure((cap + 1) * 4);
    c->geo.b_desc.ensure(cap * 128);
    c->geo.b_out.ensure(cap * sizeof(KeyRec));
-   c->geo.b_starts.ensure(((size_t)(B + 1) * 3 + 2) * 4);   // hessian starts | descriptor starts | huge-window rows per image, + their largest side
+   c->geo.b_starts.ensure(starts_block((int32_t *)nullptr, B).words_allocated() * 4);   // StartsBlock, batch_plan.h
    // patch taps: P <= sqrt(W*H) + small (the det-1 window must fit)
    const int max_p0 = (int)std::floor(std::sqrt((double)W * (double)H)) + 3;
    ensure_patch_taps(c, max_p0);
@@ -764,18 +714,10 @@ void plan_buffers(hesaff_ctx *c, int B, int H, int W)
    // per-block T' slots of the row-streamed bins (persistent grids of fixed size)
    c->b_trows2.ensure((size_t)HS_MID_BLOCKS * (HS_MID_PMAX + 2 * HS_MID_RPAD) * HS_NEED * 4);
    c->b_trows3.ensure((size_t)HS_BIG_BLOCKS * (HS_BIN3_PMAX + 2 * HS_BIG_RPAD) * HS_NEED * 4);
-   {
-      // k_patch_large_rows keeps one window row (+ borders, + taps) per wavefront in LDS: blocks of four wavefronts while four rows of the
-      // batch's largest window fit the CU's 160 KB, of two or one beyond that (run_patch_stage); a row that does not fit alone - a window
-      // above ~27 900 pixels a side, i.e. an image of more than 780 Mpx - is refused here
-      const LargeGeom lg = large_geom(c->max_p0 + 2);
-      if (lg.lds / 4 > HS_LDS_PER_CU) throw HsError(HESAFF_ERR_ARG, "image too large for the large-window row kernel (sqrt(width x height) above about 27900)");
-      // (three rows per wavefront where they fit: the launches ask for up to the whole LDS of a CU)
-      const size_t want = std::min<size_t>(lg.lds + (size_t)8 * lg.srow_stride * 4, HS_LDS_PER_CU);
-      if (want > c->rows_lds_set) {
-         set_dyn_lds(k_patch_large_rows, want);
-         c->rows_lds_set = want;
-      }
+   const size_t want = large_rows_lds_optin(c->max_p0);   // (refuses an image whose largest window row does not fit the LDS)
+   if (want > c->rows_lds_set) {
+      set_dyn_lds(k_patch_large_rows, want);
+      c->rows_lds_set = want;
    }
    c->B = B; c->H = H; c->W = W;
 }
@@ -813,19 +755,15 @@ struct StageTimer {
 
 enum { T_PYR = 0, T_DET = 1, T_AFF = 2, T_PATCH = 3, T_SIFT = 4, T_TOTAL = 5, T_PACK = 6, T_BLURHESS = 100, T_EXTREMA = 101 };
 
-// Band height of k_blur_hess_march: 16 bands per octave is the measured optimum for 16 x 4K at every octave
-// (sweeps in profiles/r01_notes.md); small batches get proportionally more bands to keep ~1000 blocks in flight.
+// Band height of k_blur_hess_march: march_bands (batch_plan.h).
 template <int K, bool WL, bool WR, bool WH, bool WR0 = false, int SRC = SRC_PLANE>
 void launch_march(hesaff_ctx *c, const DPlane &in, const DPlane &outL, const DPlane &outR, const DPlane &outHalf, const float *taps,
                   float norm2, int B, const DPlane &outR0 = DPlane(), float norm2_in = 0.0f, const GraySrc &gs = GraySrc(), const DPlane &outGray = DPlane())
 {
-   const int strips = (in.cols + BM_STRIP - 1) / BM_STRIP;
-   const long long blocks_per_band = (long long)((strips + 3) / 4) * B;
-   int best_nb = 16 * (int)std::max<long long>(1, std::min<long long>(4, 64 / std::max<long long>(1, blocks_per_band)));
-   best_nb = std::max(1, std::min(best_nb, std::max(1, in.rows / 8)));
-   const int band = (in.rows + best_nb - 1) / best_nb;
-   if (c->debug) fprintf(stderr, "[hesaff] march K=%d %dx%d B=%d bands=%d band=%d blocks=%lld\n", K, in.cols, in.rows, B, best_nb, band, blocks_per_band * best_nb);
-   const dim3 grid((strips + 3) / 4, (in.rows + band - 1) / band, B);
+   const MarchBands mb = march_bands(in.rows, in.cols, B);
+   const int band = mb.band;
+   if (c->debug) fprintf(stderr, "[hesaff] march K=%d %dx%d B=%d bands=%d band=%d blocks=%lld\n", K, in.cols, in.rows, B, mb.bands, band, (long long)mb.strip_blocks * B * mb.bands);
+   const dim3 grid(mb.strip_blocks, (in.rows + band - 1) / band, B);
    hipLaunchKernelGGL((k_blur_hess_march<K, WL, WR, WH, WR0, SRC>), grid, dim3(256), 0, c->stream, in, outL, outR, outHalf, taps, norm2, band, outR0, norm2_in, gs, outGray);
 }
 
@@ -881,17 +819,17 @@ struct Lists {
    HessList hl;
    AffineOut ao;
    PatchWork pw;
-   uint32_t *counters;
+   CounterBlock *counters;
 };
 
 Lists make_lists(hesaff_ctx *c)
 {
    Lists s;
-   uint32_t *cnt = c->b_counters.as<uint32_t>();
+   CounterBlock *cnt = c->b_counters.as<CounterBlock>();
    const size_t cap = c->cap;
    s.counters = cnt;
-   s.cl.count = cnt + 0; s.cl.items = c->geo.b_cand.as<CandRec>(); s.cl.cap = c->cand_cap; s.cl.overflow = cnt + 2;
-   s.rl.count = cnt + 1; s.rl.cap = c->cap;
+   s.cl.count = &cnt->head.cand; s.cl.items = c->geo.b_cand.as<CandRec>(); s.cl.cap = c->cand_cap; s.cl.overflow = &cnt->head.overflow;
+   s.rl.count = &cnt->head.rec; s.rl.cap = c->cap;
    float *rf = c->geo.b_rec_f.as<float>();
    s.rl.x = rf; s.rl.y = rf + cap; s.rl.s = rf + 2 * cap; s.rl.response = rf + 3 * cap;
    uint32_t *ri = c->geo.b_rec_i.as<uint32_t>();
@@ -905,7 +843,7 @@ Lists make_lists(hesaff_ctx *c)
    s.ao.converged = ai; s.ao.iters = ai + cap; s.ao.U = (float *)(ai + 2 * cap);
    int32_t *pi = c->geo.b_pw.as<int32_t>();
    s.pw.P0 = pi; s.pw.alive = pi + cap; s.pw.A = (float *)(pi + 2 * cap);
-   s.pw.bin_count = cnt + 8; s.pw.bin_work = cnt + 24; s.pw.bin_items = c->geo.b_bins.as<uint32_t>(); s.pw.cap = c->cap;
+   s.pw.bin_count = cnt->bin_count; s.pw.bin_work = cnt->bin_work; s.pw.bin_items = c->geo.b_bins.as<uint32_t>(); s.pw.cap = c->cap;
    return s;
 }
 
@@ -963,42 +901,33 @@ void run_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float *
       const uint32_t rows_cap = std::max(large_rows_bound, c->trows_rows);
       c->b_trows.ensure((size_t)rows_cap * HS_NEED * 4);
       c->b_rowprefix.ensure(((size_t)c->cap + 1) * 4);
-      // LDS per wavefront for the largest window that exists in this batch (rounded up so that few distinct launch shapes occur),
-      // not for the largest the image could hold.  Three window rows per wavefront step where they fit (k_patch_large_rows); a batch whose
-      // largest window is above HS_LARGE_SPLIT runs as two launches - windows up to HS_LARGE_SPLIT with the LDS, i.e. the occupancy, of
-      // such a window, the rest with that of the batch's largest.
-      const int pmax = std::min(c->max_p0 + 2, std::max(HS_BIN3_PMAX + 1, (c->batch_max_p > 0 ? c->batch_max_p : c->max_p0 + 2)));
       io.trows = c->b_trows.as<float>();
       io.row_prefix = c->b_rowprefix.as<uint32_t>();
       io.trows_cap = rows_cap;
-      io.overflow = s.counters + 6;
+      io.overflow = &s.counters->head.row_overflow;
       hipLaunchKernelGGL(k_large_prefix, dim3(1), dim3(256), 0, st, s.pw, c->b_rowprefix.as<uint32_t>());
-      auto launch_rows = [&](int p_lo, int p_hi) {
-         const LargeGeom lg = large_geom(std::min(c->max_p0 + 2, (p_hi + 255) / 256 * 256));
-         const size_t wave1 = lg.lds / 4;                                        // one row + taps
-         const size_t wave3 = wave1 + (size_t)2 * lg.srow_stride * 4;            // three rows + taps
-         // the three-row form only where six wavefronts of it fit a CU (windows up to about 1700): below that occupancy the kernel
-         // is all exposed gather latency (measured: 3.5x slower at two wavefronts per CU, profiles/r06_notes.md)
-         const int nrow = wave3 * 6 <= HS_LDS_PER_CU ? 3 : 1;
-         const size_t per_wave = nrow == 3 ? wave3 : wave1;
-         // wavefronts per block: four while their rows fit the CU's LDS (plan_buffers made sure one row fits); blocks of two where two
-         // such blocks pack the CU's LDS more tightly than one block of four
-         uint32_t nw = 4;
-         while (nw > 1 && per_wave * nw > HS_LDS_PER_CU) nw >>= 1;
-         if (nw == 4 && (HS_LDS_PER_CU / (per_wave * 2)) * 2 > (HS_LDS_PER_CU / (per_wave * 4)) * 4) nw = 2;
-         if (nrow == 3) nw = std::min<uint32_t>(nw, HS_LARGE_NW);
-         const uint32_t gblocks = std::min<uint32_t>((large_rows_bound + nw * HS_LARGE_CHUNK - 1) / (nw * HS_LARGE_CHUNK), 256 * 16 * (4 / nw));
-         hipLaunchKernelGGL(k_patch_large_rows, dim3(gblocks), dim3(64 * nw), per_wave * nw, st, s.hl, s.pw, io, c->tables, lg.srow_stride, lg.tap_stride, nrow,
-                            p_lo, std::min(p_hi, 0x7ffffff0));
-      };
-      if (pmax > HS_LARGE_SPLIT) { launch_rows(0, HS_LARGE_SPLIT); launch_rows(HS_LARGE_SPLIT, pmax); }
-      else launch_rows(0, pmax);
+      // one launch, or two when the batch's largest window is far above the common ones (large_rows_split, large_rows_launch: batch_plan.h)
+      const LargeSplit sp = large_rows_split(c->max_p0, c->batch_max_p);
+      for (int i = 0; i < sp.n; i++) {
+         const LargeLaunch ll = large_rows_launch(sp.p_hi[i], c->max_p0, large_rows_bound);
+         hipLaunchKernelGGL(k_patch_large_rows, dim3(ll.grid_blocks), dim3(64 * ll.wavefronts), ll.lds_bytes, st, s.hl, s.pw, io, c->tables, ll.srow_stride,
+                            ll.tap_stride, ll.nrow, sp.p_lo[i], std::min(sp.p_hi[i], 0x7ffffff0));
+      }
       hipLaunchKernelGGL(k_patch_large_finish, dim3(c->g_lfin), dim3(256), 0, st, s.pw, io, c->tables);
    }
    if (forked) {
       for (int i = 0; i < HS_NSIDE; i++) HIP_TRY(hipEventRecord(c->ev_join[i], c->side_streams[i]));
       for (int i = 0; i < HS_NSIDE; i++) HIP_TRY(hipStreamWaitEvent(st, c->ev_join[i], 0));
    }
+}
+
+// per image: upper bound of the T' rows its huge windows (P > 512) need, known from the scales alone
+void launch_image_large_rows(hesaff_ctx *c, const Lists &s, int B)
+{
+   const StartsBlock<uint32_t> sb = starts_block(c->geo.b_starts.as<uint32_t>(), B);
+   HIP_TRY(hipMemsetAsync(sb.large_rows(), 0, sb.words_to_clear() * 4, c->stream));
+   hipLaunchKernelGGL(k_image_large_rows, dim3(512), dim3(256), 0, c->stream, s.hl, (const uint32_t *)&s.counters->head.hess_total, c->consts.mrSize,
+                      sb.large_rows(), B, c->max_p0);
 }
 
 // The scale-space + detection part for the current plan; fills the ordered Hessian list.
@@ -1011,10 +940,10 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
 {
    const hesaff::OctaveSchedule &sc = c->sched;
    hipStream_t st = c->stream;
-   uint32_t *cnt = s.counters;
+   CounterBlock *cnt = s.counters;
    const float *ptaps = c->t_pyr_taps.as<float>();
    if (detect) {
-      HIP_TRY(hipMemsetAsync(cnt, 0, 64 * 4, st));
+      HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(CounterBlock), st));
       HIP_TRY(hipMemsetAsync(c->geo.b_bitmask.p, 0, std::max<size_t>((size_t)B * c->words_per_image * 8, 8), st));
       // octaveMap (pyramid.cpp:226: zeroed per octave): the order-key map is filled with "free" when it is new; every pass over an octave then bids
       // with keys of a fresh, smaller epoch (OctaveCtx::map_epoch), so what earlier passes left behind never wins - no fill and no reset per octave
@@ -1130,8 +1059,8 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
       if (!detect) continue;
       // ---- detection on this octave ----
       t = tm.begin(T_DET);
-      HIP_TRY(hipMemsetAsync(cnt + 0, 0, 4, st));
-      HIP_TRY(hipMemcpyAsync(cnt + 32 + o, cnt + 1, 4, hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipMemsetAsync(&cnt->head.cand, 0, 4, st));
+      HIP_TRY(hipMemcpyAsync(&cnt->oct_rec_start[o], &cnt->head.rec, 4, hipMemcpyDeviceToDevice, st));
       OctaveCtx oc;
       for (int l = 0; l < 5; l++) { oc.R[l] = Ro[l]; oc.L[l] = Lo[l]; oc.sigma[l] = sc.level_sigma[l]; }
       oc.pixelDistance = c->consts.pd0 * (float)(1 << o);   // pyramid.cpp:288: doubles per octave
@@ -1147,17 +1076,14 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
       if (g.rows > 2 * HS_BORDER && g.cols > 2 * HS_BORDER) {
          FivePlanes fp;
          for (int l = 0; l < 5; l++) fp.R[l] = Ro[l];
-         // bands of 128 rows (a band re-reads 4 rows of halo and starts with two row loads nothing overlaps: 32 / 64 / 128 / 256 rows measured
-         // 25.0 / 23.4 / 22.2 / 23.5 ms for the detection stage of 256 UHD images); shorter bands when that would leave the chip short of wavefronts
          const int strips = (g.cols + EXM_STRIP - 1) / EXM_STRIP;
-         auto waves_at = [&](int rows_per_band) { return (long long)strips * ((g.rows + rows_per_band - 1) / rows_per_band) * B; };
-         const int band = waves_at(128) >= 4096 ? 128 : (waves_at(64) >= 4096 ? 64 : 32);
+         const int band = extrema_band(g.rows, g.cols, B);
          const dim3 grid(strips, (g.rows + band - 1) / band, B);
          const int te = tm.begin(T_EXTREMA, 20.0 * (double)B * g.rows * g.cols);
          hipLaunchKernelGGL(k_extrema_march, grid, dim3(64), 0, st, fp, c->consts.positiveThreshold, c->consts.negativeThreshold, s.cl, band);
          tm.end(te);
          hipLaunchKernelGGL(k_localize, dim3(HS_GRID_LOC), dim3(256), 0, st, oc, s.cl, s.rl, c->consts);
-         hipLaunchKernelGGL(k_dedupe, dim3(HS_GRID_DED), dim3(256), 0, st, oc, s.rl, (const uint32_t *)(cnt + 32 + o),
+         hipLaunchKernelGGL(k_dedupe, dim3(HS_GRID_DED), dim3(256), 0, st, oc, s.rl, (const uint32_t *)&cnt->oct_rec_start[o],
                             c->geo.b_bitmask.as<unsigned long long>());
       }
       tm.end(t);
@@ -1167,19 +1093,16 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
    t = tm.begin(T_DET);
    const long long total_words = (long long)B * c->words_per_image;
    LoadPopc lp; lp.p = c->geo.b_bitmask.as<unsigned long long>();
-   exclusive_scan(c, lp, total_words, c->geo.b_prefix.as<uint32_t>(), cnt + 3);
+   exclusive_scan(c, lp, total_words, c->geo.b_prefix.as<uint32_t>(), &cnt->head.hess_total);
    // the records at their ranks as 32-byte items (in the candidate buffer: its last reader, the last octave's k_localize, is done), then dealt out
    HessItem *items = reinterpret_cast<HessItem *>(c->geo.b_cand.p);
    static_assert(sizeof(HessItem) == 32 && sizeof(CandRec) >= sizeof(HessItem), "the items fit the candidate slots (cand_cap >= cap)");
    hipLaunchKernelGGL(k_scatter_ordered, dim3(HS_GRID_SCAT), dim3(256), 0, st, s.rl, (const unsigned long long *)c->geo.b_bitmask.p,
                       (const uint32_t *)c->geo.b_prefix.p, items, s.hl.cap);
-   hipLaunchKernelGGL(k_hess_deal, dim3(HS_GRID_SCAT), dim3(256), 0, st, (const HessItem *)items, (const uint32_t *)(cnt + 3), s.hl);
+   hipLaunchKernelGGL(k_hess_deal, dim3(HS_GRID_SCAT), dim3(256), 0, st, (const HessItem *)items, (const uint32_t *)&cnt->head.hess_total, s.hl);
    hipLaunchKernelGGL(k_image_counts, dim3((B + 1 + 63) / 64), dim3(64), 0, st, (const uint32_t *)c->geo.b_prefix.p,
-                      c->words_per_image, B, (const uint32_t *)(cnt + 3), c->geo.b_starts.as<int32_t>());
-   // per image: upper bound of the T' rows its huge windows (P > 512) need, known from the scales alone
-   HIP_TRY(hipMemsetAsync(c->geo.b_starts.as<int32_t>() + 2 * (B + 1), 0, (size_t)(B + 2) * 4, st));
-   hipLaunchKernelGGL(k_image_large_rows, dim3(512), dim3(256), 0, st, s.hl, (const uint32_t *)(cnt + 3), c->consts.mrSize,
-                      c->geo.b_starts.as<uint32_t>() + 2 * (B + 1), B, c->max_p0);
+                      c->words_per_image, B, (const uint32_t *)&cnt->head.hess_total, c->geo.b_starts.as<int32_t>());
+   launch_image_large_rows(c, s, B);
    tm.end(t);
 }
 
@@ -1246,13 +1169,14 @@ void ensure_group_buffers(hesaff_ctx *c, uint32_t n)
    if (c->b_siftvo2.p != before || c->b_siftvo2.bytes != bytes_before) HIP_TRY(hipMemsetAsync(c->b_siftvo2.p, 0, c->b_siftvo2.bytes, c->stream));
 }
 
-// The host round trip of a batch: the per-image Hessian starts and the large-window row bounds (b_starts, 3 (B + 1) + 1 words)
+// The host round trip of a batch: the per-image Hessian starts and the large-window row bounds (all of b_starts: StartsBlock::words_to_copy)
 // into pinned memory; the caller's thread sleeps until everything before it on the main stream has run.
 const int32_t *fetch_hessian_starts(hesaff_ctx *c, int B)
 {
    hipStream_t st = c->stream;
-   int32_t *hs = (int32_t *)c->h_small_mid.ensure_small(((size_t)3 * (B + 1) + 1) * 4);
-   HIP_TRY(hipMemcpyAsync(hs, c->geo.b_starts.p, ((size_t)3 * (B + 1) + 1) * 4, hipMemcpyDeviceToHost, st));
+   const size_t bytes = starts_block(c->geo.b_starts.as<int32_t>(), B).words_to_copy() * 4;
+   int32_t *hs = (int32_t *)c->h_small_mid.ensure_small(bytes);
+   HIP_TRY(hipMemcpyAsync(hs, c->geo.b_starts.p, bytes, hipMemcpyDeviceToHost, st));
    HIP_TRY(hipEventRecord(c->ev_detect_done, st));
    const double dbg_ca = c->debug ? thread_cpu_ms() : 0.0;
    hs_wait_event(c->ev_detect_done);   // sleeps: no core spins while the detection stage runs
@@ -1275,7 +1199,7 @@ struct BatchResult {
 BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, int tt, int B, int H, int W, const int32_t *hs, bool with_affine)
 {
    hipStream_t st = c->stream;
-   uint32_t *cnt = s.counters;
+   CounterBlock *cnt = s.counters;
    int t;
    PlaneTab pt;
    memset(&pt, 0, sizeof pt);
@@ -1287,30 +1211,13 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
       // part wants (kernels_sift.h).  Images are processed in groups so that the patch buffers stay bounded.
       if ((uint32_t)hs[B] > c->cap) throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded; raise hesaff_params.max_kpts_per_mpx");
       n_hess_host = (uint32_t)hs[B];
-      const uint32_t *lrows = (const uint32_t *)hs + 2 * (B + 1);
-      c->batch_max_p = (int)lrows[B + 1];   // largest huge window of the batch (0: none)
-      // image groups [h_lo, h_hi) of at most group_kpts keypoints: about 16 groups per batch keep the
-      // three-stage pipeline full, between 300 k (launch overheads) and 1.2 M keypoints (buffer size);
-      // the T' rows of a group's huge windows must fit the row buffer (a single image may exceed it: the buffer grows)
-      // (the group size itself hardly matters: 0.6 / 0.9 / 1.2 / 1.8 / 2.4 M keypoints per group at B = 256, shuffled: 810 / 823 / 816 /
-      //  818 / 816 ms; what matters is that the buffers of a group stay modest: 33 KB per keypoint of a group)
-      const uint32_t group_kpts = std::min<uint32_t>(std::max<uint32_t>((uint32_t)hs[B] / 16u, 300000u), 1200000u);
-      struct Group { uint32_t lo, hi, large_rows; };
-      std::vector<Group> groups;
-      uint32_t max_n = 0;
-      for (int g0 = 0; g0 < B;) {
-         int g1 = g0 + 1;
-         unsigned long long rows = lrows[g0];
-         while (g1 < B && (uint32_t)(hs[g1 + 1] - hs[g0]) <= group_kpts && rows + lrows[g1] <= c->trows_rows) { rows += lrows[g1]; g1++; }
-         if (rows > 0xffffffffull) throw HsError(HESAFF_ERR_NOMEM, "window rows of one image exceed 32 bits");
-         if (hs[g1] > hs[g0]) {
-            groups.push_back({(uint32_t)hs[g0], (uint32_t)hs[g1], (uint32_t)rows});
-            max_n = std::max(max_n, (uint32_t)(hs[g1] - hs[g0]));
-         }
-         g0 = g1;
-      }
+      const StartsBlock<const uint32_t> hb = starts_block((const uint32_t *)hs, B);
+      c->batch_max_p = (int)*hb.largest_window();   // largest huge window of the batch (0: none)
+      // image groups [lo, hi) of keypoints; the T' rows of a group's huge windows fit the row buffer (form_groups, batch_plan.h)
+      const GroupPlan gp = form_groups(hs, hb.large_rows(), B, c->trows_rows);
+      const std::vector<ImageGroup> &groups = gp.groups;
       while (c->ev_aff.size() < groups.size()) c->ev_aff.emplace_back(hipEventDisableTiming);
-      if (max_n) ensure_group_buffers(c, max_n);
+      if (gp.max_n) ensure_group_buffers(c, gp.max_n);
       // Software pipeline over image groups, one stream per stage:
       //   affine shape of group g+1 (aff_stream)  |  patch extraction of group g (main + side
       //   streams, latency-bound)  |  descriptor kernels of the groups before (sift_stream).
@@ -1321,7 +1228,7 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
          if (!with_affine) return;
          const int ta = tm.begin(T_AFF, 0, as);
          const uint32_t agrid = std::min<uint32_t>((groups[gi].hi - groups[gi].lo + HS_AFFP_G - 1) / HS_AFFP_G, (uint32_t)c->n_cu * HS_AFF_BLOCKS_PER_CU);
-         hipLaunchKernelGGL(k_affine, dim3(agrid), dim3(64), 0, as, pt, s.hl, groups[gi].lo, groups[gi].hi, (const uint32_t *)(cnt + 3), c->tables, c->consts, s.ao);
+         hipLaunchKernelGGL(k_affine, dim3(agrid), dim3(64), 0, as, pt, s.hl, groups[gi].lo, groups[gi].hi, (const uint32_t *)&cnt->head.hess_total, c->tables, c->consts, s.ao);
          tm.end(ta);
          if (as != st) HIP_TRY(hipEventRecord(c->ev_aff[gi], as));
       };
@@ -1334,10 +1241,10 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
          const int slot = (int)(gi % HS_NSLOT);
          if (slot_used[slot]) HIP_TRY(hipStreamWaitEvent(st, c->ev_sift_done[slot], 0));   // the slot's previous descriptors are finished
          t = tm.begin(T_PATCH);
-         HIP_TRY(hipMemsetAsync(cnt + 8, 0, 24 * 4, st));   // bin counts [8..13) and work counters [24..29)
+         HIP_TRY(hipMemsetAsync(cnt->bin_count, 0, CounterBlock::bins_bytes(), st));   // bin counts and work counters
          // (the group's end travels as a kernel argument: a 4-byte copy from pageable memory would make the host wait
          //  here until the stream has drained, once per group)
-         hipLaunchKernelGGL(k_prepare_patch, dim3(1024), dim3(256), 0, st, s.hl, h_lo, h_hi, (const uint32_t *)(cnt + 3), s.ao, H, W, c->consts,
+         hipLaunchKernelGGL(k_prepare_patch, dim3(1024), dim3(256), 0, st, s.hl, h_lo, h_hi, (const uint32_t *)&cnt->head.hess_total, s.ao, H, W, c->consts,
                             c->tables, s.pw);
          run_patch_stage(c, s, c->gray, c->b_patches2[slot].as<float>(), h_lo, groups[gi].large_rows, &pt);
          tm.end(t);
@@ -1361,33 +1268,36 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
    // Hessian keypoints (alive[] is rewritten for h < n_hess each batch; the host knows n_hess since the round trip after detection -
    // the scan used to run over the whole capacity, 85 M flags for 31 M keypoints, behind a kernel that cleared the tail)
    LoadFlagI32 lf; lf.p = s.pw.alive;
-   exclusive_scan(c, lf, (long long)n_hess_host, c->geo.b_rank.as<uint32_t>(), cnt + 4);
-   hipLaunchKernelGGL(k_pack, dim3(HS_GRID_PACK), dim3(256), 0, st, s.hl, (const uint32_t *)(cnt + 3), s.pw, (const uint32_t *)c->geo.b_rank.p,
+   exclusive_scan(c, lf, (long long)n_hess_host, c->geo.b_rank.as<uint32_t>(), &cnt->head.desc_total);
+   hipLaunchKernelGGL(k_pack, dim3(HS_GRID_PACK), dim3(256), 0, st, s.hl, (const uint32_t *)&cnt->head.hess_total, s.pw, (const uint32_t *)c->geo.b_rank.p,
                       (const uint8_t *)c->geo.b_desc.p, c->geo.b_out.as<KeyRec>());
-   hipLaunchKernelGGL(k_desc_starts, dim3((B + 1 + 63) / 64), dim3(64), 0, st, (const int32_t *)c->geo.b_starts.p, B,
-                      (const uint32_t *)c->geo.b_rank.p, (const uint32_t *)(cnt + 3), (const uint32_t *)(cnt + 4),
-                      c->geo.b_starts.as<int32_t>() + (B + 1));
+   const StartsBlock<int32_t> d_starts = starts_block(c->geo.b_starts.as<int32_t>(), B);
+   hipLaunchKernelGGL(k_desc_starts, dim3((B + 1 + 63) / 64), dim3(64), 0, st, (const int32_t *)d_starts.hess(), B,
+                      (const uint32_t *)c->geo.b_rank.p, (const uint32_t *)&cnt->head.hess_total, (const uint32_t *)&cnt->head.desc_total,
+                      d_starts.desc());
    tm.end(t);
    tm.end(tt);
-   // Hessian starts [B + 1], descriptor starts [B + 1], counters [8]
-   int32_t *h_starts = (int32_t *)c->h_small_end.ensure_small(((size_t)2 * (B + 1) + 8) * 4);
-   HIP_TRY(hipMemcpyAsync(h_starts, c->geo.b_starts.p, (size_t)2 * (B + 1) * 4, hipMemcpyDeviceToHost, st));
-   HIP_TRY(hipMemcpyAsync(h_starts + 2 * (B + 1), cnt, 8 * 4, hipMemcpyDeviceToHost, st));
+   // Hessian starts [B + 1], descriptor starts [B + 1], and behind them the head of the counter block
+   const size_t final_words = d_starts.words_final();
+   int32_t *h_starts = (int32_t *)c->h_small_end.ensure_small(final_words * 4 + sizeof(CounterHead));
+   HIP_TRY(hipMemcpyAsync(h_starts, c->geo.b_starts.p, final_words * 4, hipMemcpyDeviceToHost, st));
+   HIP_TRY(hipMemcpyAsync(h_starts + final_words, &cnt->head, sizeof(CounterHead), hipMemcpyDeviceToHost, st));
    HIP_TRY(hipEventRecord(c->ev_batch_done, st));
    const double dbg_cb = c->debug ? thread_cpu_ms() : 0.0;
    hs_wait_event(c->ev_batch_done);
    if (c->debug) fprintf(stderr, "[hesaff] run_batch: caller's CPU inside the wait for the end of the batch %.2f ms\n", thread_cpu_ms() - dbg_cb);
    HIP_TRY(hipGetLastError());
    if (c->profiling) collect_timings(c, tm, B);
-   const int32_t *cn = h_starts + 2 * (B + 1);
-   if (cn[2] != 0 || (uint32_t)cn[1] > c->cap)
+   const CounterHead *cn = (const CounterHead *)(h_starts + final_words);
+   if (cn->overflow != 0 || cn->rec > c->cap)
       throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded; raise hesaff_params.max_kpts_per_mpx");
-   if (cn[6] != 0) throw HsError(HESAFF_ERR_NOMEM, "large-window row buffer exceeded (internal bound violated)");
-   return {h_starts, h_starts + (B + 1), c->geo.b_starts.as<int32_t>() + (B + 1)};
+   if (cn->row_overflow != 0) throw HsError(HESAFF_ERR_NOMEM, "large-window row buffer exceeded (internal bound violated)");
+   const StartsBlock<const int32_t> h = starts_block((const int32_t *)h_starts, B);
+   return {h.hess(), h.desc(), d_starts.desc()};
 }
 
 // Whole hot path on a device-resident batch.  Leaves ordered KeyRec records in b_out and
-// per-image start offsets (hessian: b_starts[0..B], desc: b_starts[B+1..2B+1]; BatchResult: their host copies).
+// per-image start offsets (b_starts: StartsBlock::hess() and desc(); BatchResult: their host copies).
 BatchResult run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
 {
    plan(c, B, H, W);
@@ -1406,7 +1316,6 @@ BatchResult run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
 // from = HESAFF_FROM_POINTS: the scale space as detection builds it (which also yields the grey plane), then k_affine over the list.
 // from = HESAFF_FROM_SHAPES: the grey plane alone (parity mode) - fast mode 2 builds the scale space too, k_patch_pyramid samples it -
 // and the affine output from the records.  Leaves what run_batch leaves.
-inline size_t describe_records_offset(int B) { return (((size_t)B + 1) * 4 + 255) & ~(size_t)255; }
 BatchResult run_describe(hesaff_ctx *c, const SrcImages &src, int B, int H, int W, const uint8_t *d_block, uint32_t n_rec, int from)
 {
    plan(c, B, H, W);
@@ -1415,17 +1324,14 @@ BatchResult run_describe(hesaff_ctx *c, const SrcImages &src, int B, int H, int 
    StageTimer tm(c);
    Lists s = make_lists(c);
    hipStream_t st = c->stream;
-   uint32_t *cnt = s.counters;
+   CounterBlock *cnt = s.counters;
    const bool shapes = from == HESAFF_FROM_SHAPES;
    const int tt = tm.begin(T_TOTAL);
-   HIP_TRY(hipMemsetAsync(cnt, 0, 64 * 4, st));
+   HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(CounterBlock), st));
    hipLaunchKernelGGL(k_ingest_regions, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((std::max<uint32_t>(n_rec, (uint32_t)B + 1) + 255) / 256, 4096u))), dim3(256), 0, st,
                       (const uint4 *)(d_block + describe_records_offset(B)), n_rec, (const int32_t *)d_block, B, shapes ? 1 : 0, s.hl, s.ao,
-                      cnt + 3, c->geo.b_starts.as<int32_t>());
-   // per image: upper bound of the T' rows its huge windows (P > 512) need, from the scales alone
-   HIP_TRY(hipMemsetAsync(c->geo.b_starts.as<int32_t>() + 2 * (B + 1), 0, (size_t)(B + 2) * 4, st));
-   hipLaunchKernelGGL(k_image_large_rows, dim3(512), dim3(256), 0, st, s.hl, (const uint32_t *)(cnt + 3), c->consts.mrSize,
-                      c->geo.b_starts.as<uint32_t>() + 2 * (B + 1), B, c->max_p0);
+                      &cnt->head.hess_total, c->geo.b_starts.as<int32_t>());
+   launch_image_large_rows(c, s, B);
    // (the per-image counts are the caller's, but the row bounds are the device's: the round trip stays, behind two short kernels;
    //  the planes below are enqueued after it and run while the groups are formed)
    const int32_t *hs = fetch_hessian_starts(c, B);
@@ -1535,7 +1441,7 @@ void pack_regions(hesaff_ctx *c, uint32_t n_hess, int B, hesaff_region *d_region
    RegionTab tab;
    for (int o = 0; o < HS_MAX_OCTAVES; o++) tab.pd[o] = c->consts.pd0 * (float)(1 << o);   // pyramid.cpp:288, as run_detection hands it on
    hipLaunchKernelGGL(k_pack_regions, dim3(std::min<uint32_t>((n_hess + 255) / 256, 4096u)), dim3(256), 0, c->stream, s.hl, n_hess, s.ao, s.pw,
-                      (const uint32_t *)c->geo.b_rank.p, (const int32_t *)c->geo.b_starts.as<int32_t>() + (B + 1), tab, (uint4 *)d_regions);
+                      (const uint32_t *)c->geo.b_rank.p, (const int32_t *)starts_block(c->geo.b_starts.as<int32_t>(), B).desc(), tab, (uint4 *)d_regions);
 }
 
 } // namespace

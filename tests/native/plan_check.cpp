@@ -1,0 +1,260 @@
+// CPU check of the batch plan's host arithmetic (hesaff_amd/csrc/batch_plan.h; built and run by tests/test_batch_plan.py with
+// g++ -fsanitize=address,undefined).  Two kinds of checks: properties that pin the behaviour without reference to the code under test
+// (what the kernels read and write, taken from kernels_patch.h / kernels_keypoint.h and stated at each check), and a few values worked
+// out by hand.  Prints "plan_check ok"; the first failed check prints a message and ends the program with exit code 1.
+#include <cstdio>
+#include <cstdlib>
+#include <random>
+#include "../../hesaff_amd/csrc/batch_plan.h"
+#include "../../hesaff_amd/csrc/host_tables.h"
+
+using namespace hesaff_plan;
+
+#define CHECK(cond, ...)                                                     \
+   do {                                                                      \
+      if (!(cond)) {                                                         \
+         fprintf(stderr, "plan_check: %s:%d: %s failed: ", __FILE__, __LINE__, #cond); \
+         fprintf(stderr, __VA_ARGS__);                                       \
+         fprintf(stderr, "\n");                                              \
+         exit(1);                                                            \
+      }                                                                      \
+   } while (0)
+
+static void check_octaves()
+{
+   {
+      const PyramidGeom p = pyramid_geometry(120, 160, 0);
+      const int rows[4] = {120, 60, 30, 15}, cols[4] = {160, 80, 40, 20}, pitch[4] = {192, 128, 64, 64}, wpr[4] = {3, 2, 1, 1};
+      CHECK(p.oct.size() == 4, "160x120: %zu octaves", p.oct.size());
+      long long base = 0;
+      for (int o = 0; o < 4; o++) {
+         const OctGeom &g = p.oct[o];
+         CHECK(g.rows == rows[o] && g.cols == cols[o] && g.pitch == pitch[o] && g.words_per_row == wpr[o] && g.word_base == base,
+               "octave %d: %dx%d pitch %d words %d base %lld", o, g.rows, g.cols, g.pitch, g.words_per_row, g.word_base);
+         base += 3ll * rows[o] * wpr[o];
+      }
+      CHECK(p.words_per_image == 1575, "words_per_image %lld", p.words_per_image);   // 3 * (120*3 + 60*2 + 30 + 15)
+   }
+   CHECK(pyramid_geometry(120, 160, 1).oct.size() == 5, "160x120 upscaled");
+   {
+      const PyramidGeom p = pyramid_geometry(2160, 3840, 0);
+      CHECK(p.oct.size() == 8 && p.oct.back().rows == 16 && p.oct.back().cols == 30, "UHD: %zu octaves", p.oct.size());
+   }
+   CHECK(pyramid_geometry(12, 12, 0).oct.empty() && pyramid_geometry(12, 13, 0).oct.empty() && pyramid_geometry(13, 12, 0).oct.empty(), "12x12, 13x12");
+   CHECK(pyramid_geometry(13, 13, 0).oct.size() == 1, "13x13");
+}
+
+static void check_capacity()
+{
+   const uint32_t cap = keypoint_capacity(1, 120, 160, 40000.0);
+   CHECK(cap == 4096, "cap %u", cap);
+   CHECK(candidate_capacity(cap, 1, 120, 160) == 4864, "cand_cap %u", candidate_capacity(cap, 1, 120, 160));   // 4096 + 512 + 64 * (1 strip * 4 bands)
+   CHECK(order_key_bits(120, 160) == 16, "key bits %d", order_key_bits(120, 160));                              // 3 * 19200 = 57600 <= 2^16
+   const int Bs[3] = {1, 64, 256}, Hs[3] = {120, 1080, 2160}, Ws[3] = {160, 1920, 3840};
+   for (int B : Bs)
+      for (int i = 0; i < 3; i++) {
+         const uint32_t c = keypoint_capacity(B, Hs[i], Ws[i], 40000.0);
+         CHECK(c % 64 == 0 && candidate_capacity(c, B, Hs[i], Ws[i]) >= c, "B %d %dx%d cap %u", B, Ws[i], Hs[i], c);
+      }
+   int code = 0;
+   try { (void)keypoint_capacity(256, 2160, 3840, 1.0e6); }   // 2.1e9 keypoints
+   catch (const HsError &e) { code = e.code; }
+   CHECK(code == HESAFF_ERR_ARG, "a request above 2e9 keypoints: code %d", code);
+}
+
+static void check_layouts()
+{
+   const int Bs[4] = {1, 2, 64, 256};
+   for (int B : Bs) {
+      std::vector<uint32_t> mem(starts_block((uint32_t *)nullptr, B).words_allocated());
+      const StartsBlock<uint32_t> sb = starts_block(mem.data(), B);
+      // the four regions and their sizes: B + 1 starts twice, B row sums and the word behind them, one word
+      const size_t at[4] = {(size_t)(sb.hess() - mem.data()), (size_t)(sb.desc() - mem.data()), (size_t)(sb.large_rows() - mem.data()),
+                            (size_t)(sb.largest_window() - mem.data())};
+      const size_t len[4] = {(size_t)B + 1, (size_t)B + 1, (size_t)B + 1, 1};
+      for (int i = 0; i < 4; i++) {
+         for (int j = i + 1; j < 4; j++) CHECK(at[i] + len[i] <= at[j] || at[j] + len[j] <= at[i], "B %d: regions %d and %d overlap", B, i, j);
+         CHECK(at[i] + len[i] <= sb.words_to_copy(), "B %d: region %d lies outside the copied prefix", B, i);
+      }
+      CHECK(sb.largest_window() == sb.large_rows() + B + 1, "B %d: largest_window", B);
+      CHECK(sb.words_to_copy() <= sb.words_allocated(), "B %d: the copy reads past the allocation", B);
+      CHECK(sb.words_final() == at[2], "B %d: the end-of-batch copy is hess() and desc()", B);
+      CHECK(at[2] + sb.words_to_clear() == at[3] + 1, "B %d: the clear ends with largest_window()", B);
+   }
+   // (the counter block's words are pinned by the static_asserts of batch_plan.h)
+   CHECK(describe_records_offset(1) == 256 && describe_records_offset(63) == 256 && describe_records_offset(64) == 512, "describe_records_offset");
+}
+
+// the properties of form_groups' result; they determine the greedy result
+static void check_groups_of(const char *what, const std::vector<int32_t> &hs, const std::vector<uint32_t> &lrows, uint32_t trows_rows, size_t min_groups,
+                            uint32_t kpts_lo, uint32_t kpts_hi)
+{
+   const int B = (int)lrows.size();
+   const GroupPlan p = form_groups(hs.data(), lrows.data(), B, trows_rows);
+   const uint32_t total = (uint32_t)hs[B];
+   const uint32_t kpts = total / 16u < 300000u ? 300000u : (total / 16u > 1200000u ? 1200000u : total / 16u);
+   CHECK(kpts >= kpts_lo && kpts <= kpts_hi, "%s: the case is meant for a keypoint limit in [%u, %u], not %u", what, kpts_lo, kpts_hi, kpts);
+   std::vector<int> ne;   // images with keypoints
+   for (int b = 0; b < B; b++)
+      if (hs[b + 1] > hs[b]) ne.push_back(b);
+   size_t k = 0;
+   uint32_t max_n = 0;
+   for (size_t gi = 0; gi < p.groups.size(); gi++) {
+      const ImageGroup &g = p.groups[gi];
+      CHECK(k < ne.size() && g.lo == (uint32_t)hs[ne[k]], "%s: group %zu does not start where the one before ended", what, gi);
+      unsigned long long rows = 0;
+      int count = 0;
+      while (k < ne.size() && (uint32_t)hs[ne[k] + 1] <= g.hi) { rows += lrows[ne[k]]; count++; k++; }
+      CHECK(count >= 1 && (uint32_t)hs[ne[k - 1] + 1] == g.hi, "%s: group %zu does not end at an image boundary", what, gi);
+      CHECK(g.large_rows == rows, "%s: group %zu large_rows %u, its images' %llu", what, gi, g.large_rows, rows);
+      CHECK(count == 1 || (g.hi - g.lo <= kpts && rows <= trows_rows), "%s: group %zu of %d images exceeds a limit", what, gi, count);
+      if (k < ne.size())
+         CHECK((uint32_t)hs[ne[k] + 1] - g.lo > kpts || rows + lrows[ne[k]] > trows_rows, "%s: group %zu could have taken the next image", what, gi);
+      max_n = std::max(max_n, g.hi - g.lo);
+   }
+   CHECK(k == ne.size(), "%s: the groups end before the last image with keypoints", what);
+   CHECK(p.max_n == max_n, "%s: max_n %u, largest group %u", what, p.max_n, max_n);
+   CHECK(p.groups.size() >= min_groups, "%s: %zu groups, the case is meant to make %zu at least", what, p.groups.size(), min_groups);
+}
+
+static void check_groups()
+{
+   // counts[b] keypoints and rows[b] window rows per image (an image without keypoints has no rows)
+   auto run = [](const char *what, const std::vector<uint32_t> &counts, std::vector<uint32_t> rows, uint32_t trows_rows, size_t min_groups,
+                 uint32_t kpts_lo = 300000, uint32_t kpts_hi = 1200000) {
+      std::vector<int32_t> hs(counts.size() + 1, 0);
+      for (size_t b = 0; b < counts.size(); b++) {
+         hs[b + 1] = hs[b] + (int32_t)counts[b];
+         if (counts[b] == 0) rows[b] = 0;
+      }
+      check_groups_of(what, hs, rows, trows_rows, min_groups, kpts_lo, kpts_hi);
+   };
+   const uint32_t trows = 4u << 20;
+   std::mt19937 rng(20261017);
+   auto uni = [&](uint32_t lo, uint32_t hi) { return lo + (uint32_t)(rng() % (hi - lo + 1)); };
+   for (int round = 0; round < 20; round++) {
+      {
+         // 256 images, about 7 M keypoints (the limit is total / 16, between its clamps), images without keypoints at the front, in the middle, at the end
+         std::vector<uint32_t> c(256), r(256);
+         for (int b = 0; b < 256; b++) { c[b] = uni(0, 60000); r[b] = uni(0, 600000); }
+         c[0] = c[1] = c[100] = c[101] = c[102] = c[254] = c[255] = 0;
+         for (int z = 0; z < 10; z++) c[uni(0, 255)] = 0;
+         run("empty images", c, r, trows, 8, 300001, 1199999);
+      }
+      {
+         // one image above the limit's lower clamp (300 000) among small ones
+         std::vector<uint32_t> c(64), r(64);
+         for (int b = 0; b < 64; b++) { c[b] = uni(0, 20000); r[b] = uni(0, 2000); }
+         c[uni(0, 63)] = 300001 + uni(0, 400000);
+         run("one image above group_kpts", c, r, trows, 2, 300000, 300000);
+      }
+      {
+         // one image whose rows alone exceed the row buffer
+         std::vector<uint32_t> c(32), r(32);
+         for (int b = 0; b < 32; b++) { c[b] = uni(1, 5000); r[b] = uni(0, 300000); }
+         r[uni(0, 31)] = trows + 1 + uni(0, 1000000);
+         run("one image above trows_rows", c, r, trows, 2);
+      }
+      {
+         // above 19.2 M keypoints the limit is its upper clamp (1 200 000)
+         std::vector<uint32_t> c(256), r(256);
+         for (int b = 0; b < 256; b++) { c[b] = uni(60000, 140000); r[b] = uni(0, 100000); }
+         run("upper clamp", c, r, trows, 16, 1200000, 1200000);
+      }
+   }
+   // both limits are inclusive: three images with exactly 300 000 keypoints and exactly trows_rows rows are one group
+   run("limits met exactly", {100000, 100000, 100000, 1}, {trows / 2, trows / 2, 0, 0}, trows, 2, 300000, 300000);
+   run("no keypoints at all", std::vector<uint32_t>(7, 0), std::vector<uint32_t>(7, 0), trows, 0);
+   run("one image", std::vector<uint32_t>(1, 123), std::vector<uint32_t>(1, 4000), trows, 1);
+   run("one image, rows near 2^32", std::vector<uint32_t>(3, 10), std::vector<uint32_t>(3, 0xfffffff0u), trows, 3);
+}
+
+// What k_patch_large_rows needs of a launch that serves a window of side P (kernels_patch.h):
+//  * each wavefront owns nrow * srow_stride + tap_stride floats of the dynamic LDS, its rows srow_stride apart;
+//  * hs_row_stream / 2 / 3 store the P samples of a row at srow[r .. r + P), r = K / 2 replicated samples on either side
+//    (srow[0 .. r) and srow[r + P .. r + P + r)), and read srow[x0 + jt + 1] for x0 <= P - 2, jt < K, i.e. up to index P + 2 r - 1:
+//    a row needs P + 2 (K / 2) floats;
+//  * K = tb.patch_tap_k[(P0 - 1) / 2], P0 = P - 2: gauss_ksize(1.5f * P0 / 41) (ensure_patch_taps); the tap area holds K floats at most.
+static void check_large_launch(int max_p0, int P, int batch_max_p, size_t optin)
+{
+   const LargeSplit sp = large_rows_split(max_p0, batch_max_p);
+   int serves = -1;
+   for (int i = 0; i < sp.n; i++)
+      if (P > sp.p_lo[i] && P <= sp.p_hi[i]) { CHECK(serves < 0, "max_p0 %d P %d: two launches serve the window", max_p0, P); serves = i; }
+   CHECK(serves >= 0, "max_p0 %d batch_max_p %d: no launch serves P %d", max_p0, batch_max_p, P);
+   const LargeLaunch ll = large_rows_launch(sp.p_hi[serves], max_p0, (uint32_t)P);
+   const int K = hesaff::gauss_ksize(1.5f * ((float)(P - 2) / (float)HS_PATCH));
+   CHECK(ll.srow_stride >= P + 2 * (K / 2), "max_p0 %d P %d (launch up to %d): srow_stride %d < %d", max_p0, P, sp.p_hi[serves], ll.srow_stride, P + 2 * (K / 2));
+   CHECK(ll.tap_stride >= K, "max_p0 %d P %d: tap_stride %d < K %d", max_p0, P, ll.tap_stride, K);
+   CHECK(ll.lds_bytes <= 160 * 1024 && ll.lds_bytes <= optin, "max_p0 %d P %d: %zu bytes of LDS, opt-in %zu", max_p0, P, ll.lds_bytes, optin);
+   CHECK(ll.wavefronts == 1 || ll.wavefronts == 2 || ll.wavefronts == 4, "max_p0 %d P %d: %u wavefronts", max_p0, P, ll.wavefronts);
+   CHECK(ll.nrow == 1 || ll.nrow == 3, "max_p0 %d P %d: nrow %d", max_p0, P, ll.nrow);
+   const size_t per_wave = ((size_t)ll.nrow * ll.srow_stride + ll.tap_stride) * 4;
+   if (ll.nrow == 3) CHECK(ll.wavefronts <= HS_LARGE_NW && 6 * per_wave <= 160 * 1024, "max_p0 %d P %d: three-row form with %u wavefronts of %zu bytes", max_p0, P, ll.wavefronts, per_wave);
+   CHECK(ll.lds_bytes == ll.wavefronts * per_wave, "max_p0 %d P %d: %zu bytes for %u wavefronts of %zu", max_p0, P, ll.lds_bytes, ll.wavefronts, per_wave);
+   CHECK(ll.grid_blocks >= 1, "max_p0 %d P %d: empty grid", max_p0, P);
+}
+
+static void check_large()
+{
+   // the plan's refusal: exactly where one row of the largest window no longer fits the 160 KB of a CU
+   int largest = 0;
+   for (int max_p0 = 515; max_p0 <= 40000; max_p0++) {
+      int code = 0;
+      try { (void)large_rows_lds_optin(max_p0); }
+      catch (const HsError &e) { code = e.code; }
+      const LargeLaunch one = large_rows_launch(max_p0 + 2, max_p0, 1);   // of the largest window: one wavefront with one row at the least
+      if (code == 0) {
+         CHECK(largest == max_p0 - 1 || max_p0 == 515, "max_p0 %d accepted above a refused one", max_p0);
+         CHECK(one.lds_bytes <= 160 * 1024, "max_p0 %d accepted, a row needs %zu bytes", max_p0, one.lds_bytes);
+         largest = max_p0;
+      } else {
+         CHECK(code == HESAFF_ERR_ARG, "max_p0 %d: code %d", max_p0, code);
+         CHECK(one.wavefronts == 1 && one.nrow == 1 && one.lds_bytes > 160 * 1024, "max_p0 %d refused, yet a row fits (%zu bytes)", max_p0, one.lds_bytes);
+      }
+   }
+   CHECK(largest > 20000 && largest < 40000, "largest accepted max_p0 %d", largest);
+   // every tap-table bound up to 3000, every 37th above, the largest; every window side each
+   for (int max_p0 = 515; max_p0 <= largest; max_p0 += (max_p0 < 3000 || max_p0 + 37 > largest) ? 1 : 37) {
+      const size_t optin = large_rows_lds_optin(max_p0);
+      for (int P = HS_BIN3_PMAX + 1; P <= max_p0 + 2; P++) {
+         check_large_launch(max_p0, P, P, optin);             // the window is the batch's largest
+         check_large_launch(max_p0, P, max_p0 + 2, optin);    // the batch holds the largest the image allows
+         check_large_launch(max_p0, P, 0, optin);             // the stage entry point before it knows
+      }
+   }
+   // the host's row bound (hesaff_stage_normalize_affine): P = 2 ceil(s * mrSize) + 3 for windows above 512 whose taps are tabulated
+   const float s[5] = {10.0f, 255.0f, 255.5f, 1000.0f, 3.0e6f};
+   const LargeRows lr = host_large_rows(s, 5, 1.0f, 2001);   // P = 23, 513, 515, 2003, none
+   CHECK(lr.rows == 513 + 515 + 2003 && lr.max_p == 2003, "host_large_rows: %u rows, largest %d", lr.rows, lr.max_p);
+   CHECK(host_large_rows(s, 5, 1.0f, 2000).rows == 513 + 515, "host_large_rows: a window beyond the tap table counts");
+}
+
+static void check_bands()
+{
+   const int Bs[5] = {1, 2, 16, 64, 256};
+   for (int rows = 1; rows <= 4400; rows += (rows < 300 ? 1 : 41))
+      for (int cols = 1; cols <= 7700; cols += (cols < 300 ? 7 : 247))
+         for (int B : Bs) {
+            const MarchBands m = march_bands(rows, cols, B);
+            CHECK(m.bands >= 1 && m.bands <= std::max(1, rows / 8) && (long long)m.band * m.bands >= rows, "march %dx%d B %d: %d bands of %d", cols, rows, B, m.bands, m.band);
+            CHECK(m.strip_blocks == (cols + 4 * BM_STRIP - 1) / (4 * BM_STRIP), "march %d columns: %d blocks across", cols, m.strip_blocks);
+         }
+   // the 4096-wavefront rule: 128 rows per band where that leaves 4096 wavefronts (one per 248-column strip, band and image), else 64, else 32
+   CHECK(extrema_band(15, 20, 1) == 32, "extrema 20x15");                 // 1 wavefront whatever the band
+   CHECK(extrema_band(2160, 3840, 1) == 32, "extrema UHD B = 1");         // 16 strips x 17 / 34 bands = 272 / 544
+   CHECK(extrema_band(2160, 3840, 256) == 128, "extrema UHD B = 256");    // 16 x 17 x 256 = 69632
+   CHECK(extrema_band(2160, 3840, 8) == 64, "extrema UHD B = 8");         // 16 x 17 x 8 = 2176, 16 x 34 x 8 = 4352
+}
+
+int main()
+{
+   check_octaves();
+   check_capacity();
+   check_layouts();
+   check_groups();
+   check_large();
+   check_bands();
+   printf("plan_check ok\n");
+   return 0;
+}

@@ -77,6 +77,37 @@ inline int order_key_bits(int PH, int PW)
    return kb;
 }
 
+// ---- the epochs of the order-key map (b_map; OctaveCtx::map_epoch, kernels_pyramid.h) ----
+// The map is filled with "free" (all ones) when it is new; every pass over an octave then bids with keys of a fresh, smaller epoch in the
+// bits above the key, so what earlier passes left behind never wins - no fill and no reset per octave.  This is the bookkeeping: when
+// the map must be filled, and which epoch a pass bids with.  run_detection issues the fills exactly when told to.
+struct OrderMapEpochs {
+   int kbits = 32;       // bits of an order key (order_key_bits)
+   uint32_t epoch = 0;   // the last epoch handed out; 0: the next pass refills the map first
+   bool clean = false;   // the map holds nothing but all-ones words and bids of epochs above `epoch`
+   // the all-ones epoch, which the fill value carries and no pass gets (none at all when the key takes the whole word)
+   uint32_t fill_epoch() const { return kbits < 32 ? (0xffffffffu >> kbits) : 0u; }
+   // the block is new or resized, or a plan failed half-way: nothing is known of its contents
+   void invalidate() { clean = false; }
+   void set_key_bits(int kb) { if (kb != kbits) { kbits = kb; clean = false; } }   // (another key width: epochs of the old one mean nothing)
+   // before the first pass of a batch: true when the map must be filled now
+   bool begin_batch()
+   {
+      if (clean) return false;
+      epoch = fill_epoch(); clean = true;
+      return true;
+   }
+   // a fresh epoch for a pass (counting down): refill_first when they have run out - the map is then filled before the pass
+   struct Pass { bool refill_first; uint32_t epoch_bits; };
+   Pass next_pass()
+   {
+      const bool refill = epoch == 0;
+      if (refill) epoch = fill_epoch();
+      if (epoch > 0) epoch--;
+      return {refill, kbits < 32 ? (epoch << kbits) : 0u};
+   }
+};
+
 // ---- the counter block: 64 words of device memory (b_counters) ----
 // The kernels take pointers to single words; the host names them here.  CounterHead is what the host reads back at the end of a batch.
 struct CounterHead {

@@ -24,7 +24,7 @@ void bind_device(hesaff_ctx *c) { HIP_TRY(hipSetDevice(c->device)); }
 // the end of a stage entry point: everything it enqueued on the main stream has run, and without an error
 void finish_stream(hesaff_ctx *c)
 {
-   HIP_TRY(hipStreamSynchronize(c->stream));
+   HIP_TRY(hipStreamSynchronize(c->stream()));
    HIP_TRY(hipGetLastError());
 }
 
@@ -146,29 +146,13 @@ int hesaff_create(hesaff_ctx **out, const hesaff_params *p, int device)
          std::string m = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
          throw HsError(HESAFF_ERR_DEVICE, m);
       }
-      {
-         // The HIP runtime runs the streams of one priority on FOUR hardware queues, and kernels of streams that share a queue do not
-         // overlap.  Which of a context's seven logical streams (main, patch bins 0-3, descriptor, affine) end up together moves the step
-         // by up to 8 %, and with seven HIP streams it depends on what else the process has created.  So the pairing is made explicit:
-         // four HIP streams, each serving the logical streams that measured best together
-         // (profiles/r04_notes.md):   main + bin 3 | bin 0 + bin 1 | bin 2 + affine | descriptor.
-         hipStream_t *slots[7] = {&c->stream, &c->side_streams[0], &c->side_streams[1], &c->side_streams[2], &c->side_streams[3], &c->sift_stream,
-                                  &c->aff_stream};
-         const int group[7] = {0, 1, 1, 2, 0, 3, 2};   // logical stream -> HIP stream: 0 main, 1-4 patch bins 0-3, 5 descriptor, 6 affine
-         hipStream_t made[4] = {nullptr, nullptr, nullptr, nullptr};
-         // The HIP streams of a context outlive it: the next context on this device takes the same ones (take_stream_set).  A stream
-         // created later lands on whichever hardware queue has the fewest users at that moment, so the second and third context of
-         // a process used to get another - often worse - sharing of queues than the first (the chunks of bench.py's file leg, third
-         // context of its process: 110-135 ms each against 107-110 in a process of their own).  New streams are created in the order
-         // of their groups (0, 1, 2, 3).
-         if (take_stream_set(device, c->sset))
-            for (int g = 0; g < 4; g++) made[g] = c->sset.comp[g];
-         for (int i = 0; i < 7; i++) {
-            if (!made[group[i]]) HIP_TRY(hipStreamCreateWithFlags(&made[group[i]], hipStreamNonBlocking));
-            *slots[i] = made[group[i]];
-         }
-         for (int g = 0; g < 4; g++) c->sset.comp[g] = made[g];
-      }
+      // The HIP streams of a context outlive it: the next context on this device takes the same ones, whole (take_stream_set).  A stream
+      // created later lands on whichever hardware queue has the fewest users at that moment, so the second and third context of
+      // a process used to get another - often worse - sharing of queues than the first (the chunks of bench.py's file leg, third
+      // context of its process: 110-135 ms each against 107-110 in a process of their own).  New streams are created in the order
+      // of their groups (0, 1, 2, 3; StreamSet has the pairing).
+      if (!take_stream_set(device, c->sset))
+         for (hipStream_t &st : c->sset.comp) HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
       for (int i = 0; i < HS_NSIDE; i++) c->ev_join[i] = DevEvent(hipEventDisableTiming);
       c->ev_fork = DevEvent(hipEventDisableTiming);
       // (the four compute streams stay on the default priority: every other assignment measured 1.5-6 % slower, profiles/r04_notes.md)
@@ -179,8 +163,11 @@ int hesaff_create(hesaff_ctx **out, const hesaff_params *p, int device)
          c->ev_sift_done[i] = DevEvent(hipEventDisableTiming);
       }
       set_kernel_attrs(c);
-      build_tables(c);
-      refresh_tables_struct(c);
+      {
+         const ContextTables t = build_context_tables(c->par);
+         c->tables.upload(t);
+         c->ct = t;   // (the scalars; the vectors end here)
+      }
       memset(&c->tm, 0, sizeof c->tm);
 #ifdef HESAFF_TUNING
       // what makes the schedule observable (libhesaff_amd_tuning.so only); neither changes a result
@@ -203,15 +190,13 @@ void hesaff_destroy(hesaff_ctx *c)
    if (!c) return;
    const int device = c->device;
    (void)hipSetDevice(device);
-   // Every HIP stream of the context (its logical streams are aliases of the set's four, hesaff_create) is idle before anything goes
-   // back: no kernel still uses a buffer, no copy engine a page-locked block.  The members then free themselves; the streams outlive
-   // the context and serve the next one on this device.
-   StreamSet set = c->sset;
-   set.h2d = c->h2d_stream; set.d2h = c->d2h_stream;
-   for (hipStream_t st : {c->stream, set.comp[0], set.comp[1], set.comp[2], set.comp[3], set.h2d, set.d2h})
+   // Every HIP stream of the context is idle before anything goes back: no kernel still uses a buffer, no copy engine a page-locked
+   // block.  The members then free themselves; the streams outlive the context and serve the next one on this device.
+   const StreamSet set = c->sset;
+   for (hipStream_t st : {set.comp[0], set.comp[1], set.comp[2], set.comp[3], set.h2d, set.d2h})
       if (st) (void)hipStreamSynchronize(st);
    delete c;
-   if (set.comp[0]) give_stream_set(device, set);   // (a context whose creation failed before its streams were complete has no set)
+   if (set.comp[3]) give_stream_set(device, set);   // (a context whose creation failed before its streams were complete has no set)
 }
 
 const char *hesaff_last_error(const hesaff_ctx *c) { return c ? c->err.c_str() : g_create_error.c_str(); }
@@ -292,18 +277,16 @@ const char *describe_bad_record(const hesaff_region &r, int from, int n_oct)
 
 void ensure_copy_streams(hesaff_ctx *c)
 {
-   if (c->h2d_stream) return;
+   if (c->slot[1].ev_exp[3]) return;   // (the last thing made below)
    // The copy streams get a priority of their own: the runtime multiplexes the streams of one priority onto a few hardware queues
    // (four by default; this context has four compute streams), and a copy command holds its queue until the copy engine is done -
    // 23 ms for the 1.3 GB of text of a chunk, during which the patch kernels of whatever stream shared that queue did not start
    // (measured: +19 ms on the patch stage of every chunk, profiles/r04_notes.md).  Streams of another priority live on other queues.
    int prio_least = 0, prio_greatest = 0;
    HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-   if (c->sset.h2d && c->sset.d2h) {   // the copy streams of the context that had this set before
-      c->h2d_stream = c->sset.h2d; c->d2h_stream = c->sset.d2h;
-   } else {
-      HIP_TRY(hipStreamCreateWithPriority(&c->h2d_stream, hipStreamNonBlocking, prio_greatest));
-      HIP_TRY(hipStreamCreateWithPriority(&c->d2h_stream, hipStreamNonBlocking, prio_greatest));
+   if (!(c->sset.h2d && c->sset.d2h)) {   // (else: the copy streams of the context that had this set before)
+      HIP_TRY(hipStreamCreateWithPriority(&c->sset.h2d, hipStreamNonBlocking, prio_greatest));
+      HIP_TRY(hipStreamCreateWithPriority(&c->sset.d2h, hipStreamNonBlocking, prio_greatest));
    }
    for (hesaff_ctx::ChunkSlot &sl : c->slot) {
       sl.ev_h2d = DevEvent(hipEventDisableTiming);
@@ -359,9 +342,9 @@ struct ChunkDevice {
          // event meanwhile)
          uint8_t *dst = (uint8_t *)(q.blob_bytes ? sl.b_jcoef.p : sl.b_in2.p);
          for (size_t b = 0; b < q.data.size(); b++)
-            HIP_TRY(hipMemcpyAsync(dst + unit * b, q.data[b], unit, hipMemcpyHostToDevice, c->h2d_stream));
-         HIP_TRY(hipEventRecord(sl.ev_h2d, c->h2d_stream));
-         HIP_TRY(hipEventRecord(sl.ev_h2d_blk, c->h2d_stream));
+            HIP_TRY(hipMemcpyAsync(dst + unit * b, q.data[b], unit, hipMemcpyHostToDevice, c->sset.h2d));
+         HIP_TRY(hipEventRecord(sl.ev_h2d, c->sset.h2d));
+         HIP_TRY(hipEventRecord(sl.ev_h2d_blk, c->sset.h2d));
          hs_wait_event(sl.ev_h2d_blk);
          return;
       }
@@ -403,7 +386,7 @@ struct ChunkDevice {
       }
       if (q.from) {
          // the chunk's records travel with it: [B + 1 starts][records] into pinned memory, each record checked on the way, one copy in
-         const int n_oct = (int)pyramid_geometry(q.H, q.W, c->up).oct.size();
+         const int n_oct = (int)pyramid_geometry(q.H, q.W, c->ct.up).oct.size();
          unsigned long long n_rec = 0;
          for (int cnt : q.region_count) n_rec += (unsigned long long)cnt;
          if (n_rec > 0x7fffffffull) throw HsError(HESAFF_ERR_CAPACITY, "more records in a chunk than 32-bit indices hold");
@@ -428,10 +411,10 @@ struct ChunkDevice {
          }
          starts[nimg] = (int32_t)at;
          s.n_rec = (uint32_t)at;
-         HIP_TRY(hipMemcpyAsync(sl.b_reg.p, sl.pin_reg.p, bytes, hipMemcpyHostToDevice, c->h2d_stream));
+         HIP_TRY(hipMemcpyAsync(sl.b_reg.p, sl.pin_reg.p, bytes, hipMemcpyHostToDevice, c->sset.h2d));
       }
-      HIP_TRY(hipMemcpyAsync(q.blob_bytes ? sl.b_jcoef.p : sl.b_in2.p, sl.pin_in.p, total, hipMemcpyHostToDevice, c->h2d_stream));
-      HIP_TRY(hipEventRecord(sl.ev_h2d, c->h2d_stream));
+      HIP_TRY(hipMemcpyAsync(q.blob_bytes ? sl.b_jcoef.p : sl.b_in2.p, sl.pin_in.p, total, hipMemcpyHostToDevice, c->sset.h2d));
+      HIP_TRY(hipEventRecord(sl.ev_h2d, c->sset.h2d));
    }
 
    // the chunk's batch, its per-image counts and the layout of its result block.  ev_in_free of the slot is recorded when the batch has
@@ -444,23 +427,23 @@ struct ChunkDevice {
       Slot &sl = c->slot[s.no & 1];
       const int B = (int)q.data.size();
       const size_t row_bytes = (size_t)q.W * q.bpp(), img_bytes = row_bytes * q.H;
-      HIP_TRY(hipStreamWaitEvent(c->stream, sl.ev_h2d, 0));
+      HIP_TRY(hipStreamWaitEvent(c->stream(), sl.ev_h2d, 0));
       BatchResult res = {};
       try {
          plan(c, std::max(std::min<int>(c->par.max_batch, B), s.largest), q.H, q.W);
          // a chunk of JPEG files: inverse DCT, up-sampling and colour conversion of all its images (kernels_jpeg.h) into the input slot
-         if (q.blob_bytes) jpeg_pixels(c, sl.b_jcoef.as<uint8_t>(), make_jpeg_geom(q.jpeg), B, (uint8_t *)sl.b_in2.p, img_bytes, c->stream);
+         if (q.blob_bytes) jpeg_pixels(c, sl.b_jcoef.as<uint8_t>(), make_jpeg_geom(q.jpeg), B, (uint8_t *)sl.b_in2.p, img_bytes, c->stream());
          const SrcImages src = q.f32 ? SrcImages::f32(sl.b_in2.p, (long long)img_bytes, (int)row_bytes)
                                      : SrcImages::u8(sl.b_in2.p, q.ch, (long long)img_bytes, (int)row_bytes);
          res = q.from ? run_describe(c, src, B, q.H, q.W, (const uint8_t *)sl.b_reg.p, s.n_rec, q.from) : run_batch(c, src, B, q.H, q.W);
       } catch (const HsError &e) {
          if (e.code == HESAFF_ERR_ARG || e.code == HESAFF_ERR_CAPACITY) {
-            HIP_TRY(hipEventRecord(sl.ev_in_free, c->stream));
+            HIP_TRY(hipEventRecord(sl.ev_in_free, c->stream()));
             dbg_next_chunk();
          }
          throw;
       }
-      HIP_TRY(hipEventRecord(sl.ev_in_free, c->stream));
+      HIP_TRY(hipEventRecord(sl.ev_in_free, c->stream()));
       dbg_t2 = Clock::now();
       dbg_c2 = c->debug ? thread_cpu_ms() : 0.0;
       const int32_t *hs = res.hessian_starts, *ds = res.desc_starts;
@@ -477,13 +460,13 @@ struct ChunkDevice {
       auto place = [&at](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~(size_t)255; return o; };
       if (wants & WANT_KEYS) s.keys_at = place(n_rows * sizeof(hesaff_keypoint));
       if (wants & WANT_REGIONS) s.regions_at = place(s.n_hess * sizeof(hesaff_region));
-      if (times_export(s)) HIP_TRY(hipEventRecord(sl.ev_exp[0], c->stream));
+      if (times_export(s)) HIP_TRY(hipEventRecord(sl.ev_exp[0], c->stream()));
       if (wants & WANT_TEXT) {   // row lengths and offsets first: the host needs the byte count (a short wait on the main stream)
          const unsigned long long text_bytes = export_text_prepare(c, c->geo.b_out.as<KeyRec>(), (uint32_t)n_rows, res.d_desc_starts, B, s.toff);
          s.text_at = place((size_t)text_bytes);
       }
       if (wants & WANT_BIN) s.bin_at = place(n_rows * EX_BIN_ROW);
-      if (times_export(s)) HIP_TRY(hipEventRecord(sl.ev_exp[1], c->stream));
+      if (times_export(s)) HIP_TRY(hipEventRecord(sl.ev_exp[1], c->stream()));
       s.bytes = at;
       dbg_t3 = Clock::now();
    }
@@ -520,20 +503,20 @@ struct ChunkDevice {
       s.copied = s.total > 0 || ((wants & WANT_REGIONS) && s.n_hess > 0);
       if (s.copied) {
          const KeyRec *d_keys = c->geo.b_out.as<KeyRec>();
-         HIP_TRY(hipStreamWaitEvent(c->stream, sl.ev_d2h, 0));      // the D2H of the chunk two before has left this staging slot
+         HIP_TRY(hipStreamWaitEvent(c->stream(), sl.ev_d2h, 0));      // the D2H of the chunk two before has left this staging slot
          if (bytes > sl.b_outstage.bytes) sl.b_outstage.ensure(bytes + bytes / 4);
          char *stg = (char *)sl.b_outstage.p;
          if ((wants & WANT_KEYS) && n_rows > 0)
-            HIP_TRY(hipMemcpyAsync(stg + s.keys_at, c->geo.b_out.p, n_rows * sizeof(hesaff_keypoint), hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(stg + s.keys_at, c->geo.b_out.p, n_rows * sizeof(hesaff_keypoint), hipMemcpyDeviceToDevice, c->stream()));
          if (wants & WANT_REGIONS) pack_regions(c, (uint32_t)s.n_hess, B, (hesaff_region *)(stg + s.regions_at));
-         if (times_export(s)) HIP_TRY(hipEventRecord(sl.ev_exp[2], c->stream));
+         if (times_export(s)) HIP_TRY(hipEventRecord(sl.ev_exp[2], c->stream()));
          if (wants & WANT_TEXT) export_text_write(c, d_keys, (uint32_t)n_rows, stg + s.text_at);
          if (wants & WANT_BIN) export_bin_rows(c, d_keys, (uint32_t)n_rows, stg + s.bin_at);
-         if (times_export(s)) HIP_TRY(hipEventRecord(sl.ev_exp[3], c->stream));
-         HIP_TRY(hipEventRecord(sl.ev_out_ready, c->stream));
-         HIP_TRY(hipStreamWaitEvent(c->d2h_stream, sl.ev_out_ready, 0));
-         HIP_TRY(hipMemcpyAsync(c->pin_out[(size_t)s.block].p, stg, bytes, hipMemcpyDeviceToHost, c->d2h_stream));
-         HIP_TRY(hipEventRecord(sl.ev_d2h, c->d2h_stream));
+         if (times_export(s)) HIP_TRY(hipEventRecord(sl.ev_exp[3], c->stream()));
+         HIP_TRY(hipEventRecord(sl.ev_out_ready, c->stream()));
+         HIP_TRY(hipStreamWaitEvent(c->sset.d2h, sl.ev_out_ready, 0));
+         HIP_TRY(hipMemcpyAsync(c->pin_out[(size_t)s.block].p, stg, bytes, hipMemcpyDeviceToHost, c->sset.d2h));
+         HIP_TRY(hipEventRecord(sl.ev_d2h, c->sset.d2h));
       }
       if (c->debug) {
          auto ms = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -562,14 +545,14 @@ struct ChunkDevice {
 
    void drain()
    {
-      (void)hipStreamSynchronize(c->h2d_stream);
-      (void)hipStreamSynchronize(c->d2h_stream);
-      (void)hipStreamSynchronize(c->stream);
+      (void)hipStreamSynchronize(c->sset.h2d);
+      (void)hipStreamSynchronize(c->sset.d2h);
+      (void)hipStreamSynchronize(c->stream());
    }
    void finish()
    {
-      HIP_TRY(hipStreamSynchronize(c->d2h_stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
+      HIP_TRY(hipStreamSynchronize(c->sset.d2h));
+      HIP_TRY(hipStreamSynchronize(c->stream()));
    }
 };
 
@@ -611,11 +594,11 @@ void check_device_f32(hesaff_ctx *c, int n, const uint8_t *d, long long img_stri
 {
    c->b_stage.ensure((size_t)n * 4);
    int32_t *flags = c->b_stage.as<int32_t>();
-   HIP_TRY(hipMemsetAsync(flags, 0, (size_t)n * 4, c->stream));
+   HIP_TRY(hipMemsetAsync(flags, 0, (size_t)n * 4, c->stream()));
    const int gx = std::max(1, std::min(H, (8 * c->n_cu + n - 1) / n));   // about 8 blocks per CU in all
-   hipLaunchKernelGGL(k_check_f32, dim3(gx, 1, n), dim3(256), 0, c->stream, d, img_stride, row_stride, H, W, flags);
+   hipLaunchKernelGGL(k_check_f32, dim3(gx, 1, n), dim3(256), 0, c->stream(), d, img_stride, row_stride, H, W, flags);
    std::vector<int32_t> h((size_t)n);
-   HIP_TRY(hipMemcpyAsync(h.data(), flags, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+   HIP_TRY(hipMemcpyAsync(h.data(), flags, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream()));
    finish_stream(c);
    for (int b = 0; b < n; b++) {
       if (!h[(size_t)b]) continue;
@@ -847,22 +830,22 @@ int hesaff_stage_gaussian_blur(hesaff_ctx *c, const float *in, int rows, int col
    const size_t n = (size_t)rows * pitch;
    c->b_stage.ensure(n * 4 * 3 + (size_t)(K + 16) * 4);
    float *d_in = c->b_stage.as<float>(), *d_tmp = d_in + n, *d_out = d_tmp + n, *d_taps = d_out + n;
-   std::vector<float> taps(K, 1.0f);
-   if (K > 1) hesaff::gauss_taps(K, sigma, taps.data());
-   HIP_TRY(hipMemcpy2DAsync(d_in, (size_t)pitch * 4, in, (size_t)cols * 4, (size_t)cols * 4, rows, hipMemcpyHostToDevice, c->stream));
-   HIP_TRY(hipMemcpyAsync(d_taps, taps.data(), (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
+   std::vector<float> taps(K);
+   hesaff::blur_taps(K, sigma, taps.data());
+   HIP_TRY(hipMemcpy2DAsync(d_in, (size_t)pitch * 4, in, (size_t)cols * 4, (size_t)cols * 4, rows, hipMemcpyHostToDevice, c->stream()));
+   HIP_TRY(hipMemcpyAsync(d_taps, taps.data(), (size_t)K * 4, hipMemcpyHostToDevice, c->stream()));
    DPlane pi = make_plane(d_in, rows, cols, pitch), pt = make_plane(d_tmp, rows, cols, pitch), po = make_plane(d_out, rows, cols, pitch);
    const DPlane none = make_plane(nullptr, 0, 0, 0);
    if (K == 1) {
-      HIP_TRY(hipMemcpyAsync(d_out, d_in, n * 4, hipMemcpyDeviceToDevice, c->stream));
+      HIP_TRY(hipMemcpyAsync(d_out, d_in, n * 4, hipMemcpyDeviceToDevice, c->stream()));
    } else if (K == 9 || K == 11 || K == 13 || K == 15) {
       launch_blur_hess<true, false, false>(c, pi, po, none, none, d_taps, K, 0.0f, 1);
    } else {
       const dim3 grid((cols + 255) / 256, rows, 1);
-      hipLaunchKernelGGL(k_blur_rows_generic, grid, dim3(256), 0, c->stream, pi, pt, (const float *)d_taps, K);
-      hipLaunchKernelGGL(k_blur_cols_generic, grid, dim3(256), 0, c->stream, pt, po, (const float *)d_taps, K);
+      hipLaunchKernelGGL(k_blur_rows_generic, grid, dim3(256), 0, c->stream(), pi, pt, (const float *)d_taps, K);
+      hipLaunchKernelGGL(k_blur_cols_generic, grid, dim3(256), 0, c->stream(), pt, po, (const float *)d_taps, K);
    }
-   HIP_TRY(hipMemcpy2DAsync(out, (size_t)cols * 4, d_out, (size_t)pitch * 4, (size_t)cols * 4, rows, hipMemcpyDeviceToHost, c->stream));
+   HIP_TRY(hipMemcpy2DAsync(out, (size_t)cols * 4, d_out, (size_t)pitch * 4, (size_t)cols * 4, rows, hipMemcpyDeviceToHost, c->stream()));
    finish_stream(c);
    HS_API_END(c)
 }
@@ -876,15 +859,15 @@ int hesaff_stage_hessian_response(hesaff_ctx *c, const float *in, int rows, int 
    const size_t n = (size_t)rows * pitch;
    c->b_stage.ensure(n * 4 * 4 + 64);
    float *d_in = c->b_stage.as<float>(), *d_out = d_in + n, *d_l = d_out + n, *d_r = d_l + n, *d_taps = d_r + n;
-   HIP_TRY(hipMemcpy2DAsync(d_in, (size_t)pitch * 4, in, (size_t)cols * 4, (size_t)cols * 4, rows, hipMemcpyHostToDevice, c->stream));
+   HIP_TRY(hipMemcpy2DAsync(d_in, (size_t)pitch * 4, in, (size_t)cols * 4, (size_t)cols * 4, rows, hipMemcpyHostToDevice, c->stream()));
    DPlane pi = make_plane(d_in, rows, cols, pitch), po = make_plane(d_out, rows, cols, pitch);
    // the batch path computes R0 in the epilogue of the first blur launch of an octave (K = 9 at the default sigmas)
    std::vector<float> taps(9);
-   hesaff::gauss_taps(9, 1.2262737f, taps.data());
-   HIP_TRY(hipMemcpyAsync(d_taps, taps.data(), 9 * 4, hipMemcpyHostToDevice, c->stream));
+   hesaff::blur_taps(9, hesaff::make_schedule(1.6f, false).blur_sigma[1], taps.data());
+   HIP_TRY(hipMemcpyAsync(d_taps, taps.data(), 9 * 4, hipMemcpyHostToDevice, c->stream()));
    launch_march<9, true, true, false, true>(c, pi, make_plane(d_l, rows, cols, pitch), make_plane(d_r, rows, cols, pitch), make_plane(nullptr, 0, 0, 0),
                                             d_taps, 1.0f, 1, po, norm * norm);
-   HIP_TRY(hipMemcpy2DAsync(out, (size_t)cols * 4, d_out, (size_t)pitch * 4, (size_t)cols * 4, rows, hipMemcpyDeviceToHost, c->stream));
+   HIP_TRY(hipMemcpy2DAsync(out, (size_t)cols * 4, d_out, (size_t)pitch * 4, (size_t)cols * 4, rows, hipMemcpyDeviceToHost, c->stream()));
    finish_stream(c);
    HS_API_END(c)
 }
@@ -898,10 +881,10 @@ int hesaff_stage_half_image(hesaff_ctx *c, const float *in, int rows, int cols, 
    const int r2 = rows / 2, c2 = cols / 2;
    c->b_stage.ensure(n * 4 * 2);
    float *d_in = c->b_stage.as<float>(), *d_out = d_in + n;
-   HIP_TRY(hipMemcpyAsync(d_in, in, n * 4, hipMemcpyHostToDevice, c->stream));
+   HIP_TRY(hipMemcpyAsync(d_in, in, n * 4, hipMemcpyHostToDevice, c->stream()));
    DPlane pi = make_plane(d_in, rows, cols, cols), po = make_plane(d_out, r2, c2, c2);
-   hipLaunchKernelGGL(k_half, dim3((c2 + 255) / 256, r2, 1), dim3(256), 0, c->stream, pi, po);
-   HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)r2 * c2 * 4, hipMemcpyDeviceToHost, c->stream));
+   hipLaunchKernelGGL(k_half, dim3((c2 + 255) / 256, r2, 1), dim3(256), 0, c->stream(), pi, po);
+   HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)r2 * c2 * 4, hipMemcpyDeviceToHost, c->stream()));
    finish_stream(c);
    HS_API_END(c)
 }
@@ -929,7 +912,7 @@ static int stage_pyramid(hesaff_ctx *c, const void *image, bool f32, int rows, i
       }
       c->b_input.ensure(bytes);
       c->b_stage.ensure((size_t)rows * round_up(cols, 64) * 4);
-      HIP_TRY(hipMemcpyAsync(c->b_input.p, image, bytes, hipMemcpyHostToDevice, c->stream));
+      HIP_TRY(hipMemcpyAsync(c->b_input.p, image, bytes, hipMemcpyHostToDevice, c->stream()));
       c->ev_used = 0;
       StageTimer tm(c);
       Lists s = make_lists(c);
@@ -957,13 +940,13 @@ int hesaff_stage_hessian_keypoints(hesaff_ctx *c, const uint8_t *gray, int rows,
    bind_device(c);
    plan(c, 1, rows, cols);
    c->b_input.ensure((size_t)rows * cols);
-   HIP_TRY(hipMemcpyAsync(c->b_input.p, gray, (size_t)rows * cols, hipMemcpyHostToDevice, c->stream));
+   HIP_TRY(hipMemcpyAsync(c->b_input.p, gray, (size_t)rows * cols, hipMemcpyHostToDevice, c->stream()));
    c->ev_used = 0;
    StageTimer tm(c);
    Lists s = make_lists(c);
    run_detection(c, SrcImages::u8(c->b_input.p, 1, (long long)rows * cols, cols), 1, s, tm, false, nullptr);
    CounterHead cn;
-   HIP_TRY(hipMemcpyAsync(&cn, &s.counters->head, sizeof cn, hipMemcpyDeviceToHost, c->stream));
+   HIP_TRY(hipMemcpyAsync(&cn, &s.counters->head, sizeof cn, hipMemcpyDeviceToHost, c->stream()));
    finish_stream(c);
    if (cn.overflow != 0 || cn.rec > c->cap) throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded");
    const int n = (int)cn.hess_total;
@@ -982,7 +965,7 @@ int hesaff_stage_hessian_keypoints(hesaff_ctx *c, const uint8_t *gray, int rows,
          const int octave = (meta[i] >> 4) & 15, level = (meta[i] >> 2) & 3, type = meta[i] & 3;
          const OctGeom &g = c->oct[octave];
          const uint32_t pix = (uint32_t)key[i] % (uint32_t)(g.rows * g.cols);
-         f[5 * i] = x[i]; f[5 * i + 1] = y[i]; f[5 * i + 2] = sc[i]; f[5 * i + 3] = c->consts.pd0 * (float)(1 << octave); f[5 * i + 4] = resp[i];
+         f[5 * i] = x[i]; f[5 * i + 1] = y[i]; f[5 * i + 2] = sc[i]; f[5 * i + 3] = c->ct.consts.pd0 * (float)(1 << octave); f[5 * i + 4] = resp[i];
          iv[5 * i] = type; iv[5 * i + 1] = octave; iv[5 * i + 2] = level; iv[5 * i + 3] = (int32_t)(pix / g.cols); iv[5 * i + 4] = (int32_t)(pix % g.cols);
       }
    }
@@ -1002,14 +985,14 @@ int hesaff_stage_find_affine_shape(hesaff_ctx *c, const float *blur, int rows, i
    float *d_kp = d_plane + np;
    int32_t *d_conv = (int32_t *)(d_kp + (size_t)4 * n), *d_iters = d_conv + n;
    float *d_U = (float *)(d_iters + n);
-   HIP_TRY(hipMemcpyAsync(d_plane, blur, np * 4, hipMemcpyHostToDevice, c->stream));
-   HIP_TRY(hipMemcpyAsync(d_kp, kp, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+   HIP_TRY(hipMemcpyAsync(d_plane, blur, np * 4, hipMemcpyHostToDevice, c->stream()));
+   HIP_TRY(hipMemcpyAsync(d_kp, kp, (size_t)n * 16, hipMemcpyHostToDevice, c->stream()));
    AffineOut ao; ao.converged = d_conv; ao.iters = d_iters; ao.U = d_U;
    DPlane P = make_plane(d_plane, rows, cols, cols);
-   hipLaunchKernelGGL(k_affine_stage, dim3(std::min((n + HS_AFFP_G - 1) / HS_AFFP_G, 256 * 6)), dim3(64), 0, c->stream, P, (const float *)d_kp, n, c->tables, c->consts, ao);
-   if (converged) HIP_TRY(hipMemcpyAsync(converged, d_conv, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-   if (iters) HIP_TRY(hipMemcpyAsync(iters, d_iters, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-   if (U) HIP_TRY(hipMemcpyAsync(U, d_U, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
+   hipLaunchKernelGGL(k_affine_stage, dim3(std::min((n + HS_AFFP_G - 1) / HS_AFFP_G, 256 * 6)), dim3(64), 0, c->stream(), P, (const float *)d_kp, n, c->tables.view, c->ct.consts, ao);
+   if (converged) HIP_TRY(hipMemcpyAsync(converged, d_conv, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream()));
+   if (iters) HIP_TRY(hipMemcpyAsync(iters, d_iters, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream()));
+   if (U) HIP_TRY(hipMemcpyAsync(U, d_U, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream()));
    finish_stream(c);
    HS_API_END(c)
 }
@@ -1021,9 +1004,9 @@ int hesaff_stage_rectify(hesaff_ctx *c, int n, float *A)
    bind_device(c);
    if (n == 0) return HESAFF_OK;
    c->b_stage.ensure((size_t)n * 16);
-   HIP_TRY(hipMemcpyAsync(c->b_stage.p, A, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-   hipLaunchKernelGGL(k_rectify_stage, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, c->b_stage.as<float>());
-   HIP_TRY(hipMemcpyAsync(A, c->b_stage.p, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
+   HIP_TRY(hipMemcpyAsync(c->b_stage.p, A, (size_t)n * 16, hipMemcpyHostToDevice, c->stream()));
+   hipLaunchKernelGGL(k_rectify_stage, dim3((n + 255) / 256), dim3(256), 0, c->stream(), n, c->b_stage.as<float>());
+   HIP_TRY(hipMemcpyAsync(A, c->b_stage.p, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream()));
    finish_stream(c);
    HS_API_END(c)
 }
@@ -1040,7 +1023,7 @@ int hesaff_stage_normalize_affine(hesaff_ctx *c, const float *img, int rows, int
    plan(c, 1, rows, cols);
    if ((uint32_t)n > c->cap) throw HsError(HESAFF_ERR_CAPACITY, "too many keypoints for this image size");
    Lists s = make_lists(c);
-   hipStream_t st = c->stream;
+   hipStream_t st = c->stream();
    HIP_TRY(hipMemcpy2DAsync(c->gray.p, (size_t)c->gray.pitch * 4, img, (size_t)cols * 4, (size_t)cols * 4, rows, hipMemcpyHostToDevice, st));
    std::vector<float> x(n), y(n), sc(n);
    std::vector<int32_t> meta(n, 0), P0(n), alive(n);
@@ -1056,11 +1039,11 @@ int hesaff_stage_normalize_affine(hesaff_ctx *c, const float *img, int rows, int
    uint32_t nn = (uint32_t)n;
    HIP_TRY(hipMemcpyAsync(&s.counters->head.hess_total, &nn, 4, hipMemcpyHostToDevice, st));
    hipLaunchKernelGGL(k_prepare_patch_given_A, dim3((n + 255) / 256), dim3(256), 0, st, s.hl, (const uint32_t *)&s.counters->head.hess_total, rows, cols,
-                      c->consts, c->tables, s.pw);
+                      c->ct.consts, c->tables.view, s.pw);
    c->b_patches.ensure((size_t)n * HS_PATCH_PIX * 4);
    HIP_TRY(hipMemsetAsync(c->b_patches.p, 0, (size_t)n * HS_PATCH_PIX * 4, st));
    // T' rows of the huge windows: bounded by the sum of their sides
-   const LargeRows lr = host_large_rows(sc.data(), n, c->consts.mrSize, c->max_p0);
+   const LargeRows lr = host_large_rows(sc.data(), n, c->ct.consts.mrSize, c->tables.view.max_p0);
    c->batch_max_p = lr.max_p;
    run_patch_stage(c, s, c->gray, c->b_patches.as<float>(), 0, lr.rows);
    uint32_t ovf = 0;
@@ -1086,14 +1069,14 @@ int hesaff_stage_sift(hesaff_ctx *c, int n, const float *patches, uint8_t *desc)
    c->b_stage.ensure(total);
    char *base = (char *)c->b_stage.p;
    std::vector<int32_t> ones(N, 1);
-   HIP_TRY(hipMemcpyAsync(base, patches, N * HS_PATCH_PIX * 4, hipMemcpyHostToDevice, c->stream));
-   HIP_TRY(hipMemcpyAsync(base + off_alive, ones.data(), N * 4, hipMemcpyHostToDevice, c->stream));
-   HIP_TRY(hipMemsetAsync(base + off_vo, 0, N * HS_VO_PITCH * 8 + 64, c->stream));   // pairs outside the circular mask stay (0, 0)
+   HIP_TRY(hipMemcpyAsync(base, patches, N * HS_PATCH_PIX * 4, hipMemcpyHostToDevice, c->stream()));
+   HIP_TRY(hipMemcpyAsync(base + off_alive, ones.data(), N * 4, hipMemcpyHostToDevice, c->stream()));
+   HIP_TRY(hipMemsetAsync(base + off_vo, 0, N * HS_VO_PITCH * 8 + 64, c->stream()));   // pairs outside the circular mask stay (0, 0)
    SiftIO so;
    so.patches = (const float *)base; so.alive = (const int32_t *)(base + off_alive); so.meanvar = (float *)(base + off_mv);
    so.vec = (float *)(base + off_vec); so.desc = (uint8_t *)(base + off_desc); so.h_lo = 0; so.h_hi = (uint32_t)n;
-   launch_sift(c, c->stream, so, (uint32_t)n, (float2 *)(base + off_vo));
-   HIP_TRY(hipMemcpyAsync(desc, base + off_desc, N * 128, hipMemcpyDeviceToHost, c->stream));
+   launch_sift(c, c->stream(), so, (uint32_t)n, (float2 *)(base + off_vo));
+   HIP_TRY(hipMemcpyAsync(desc, base + off_desc, N * 128, hipMemcpyDeviceToHost, c->stream()));
    finish_stream(c);
    HS_API_END(c)
 }
@@ -1110,14 +1093,14 @@ int hesaff_stage_export(hesaff_ctx *c, const hesaff_keypoint *keys, int n, float
    try {
       const size_t N = (size_t)n;
       c->b_stage.ensure(std::max<size_t>(N * sizeof(KeyRec), 16));
-      if (n > 0) HIP_TRY(hipMemcpyAsync(c->b_stage.p, keys, N * sizeof(KeyRec), hipMemcpyHostToDevice, c->stream));
+      if (n > 0) HIP_TRY(hipMemcpyAsync(c->b_stage.p, keys, N * sizeof(KeyRec), hipMemcpyHostToDevice, c->stream()));
       const KeyRec *d_keys = c->b_stage.as<KeyRec>();
       char head[64];
       size_t hl, body;
       if (format == HESAFF_OUT_TEXT) {
          const int32_t starts[2] = {0, n};
          c->b_ex_starts.ensure(16);
-         HIP_TRY(hipMemcpyAsync(c->b_ex_starts.p, starts, sizeof starts, hipMemcpyHostToDevice, c->stream));
+         HIP_TRY(hipMemcpyAsync(c->b_ex_starts.p, starts, sizeof starts, hipMemcpyHostToDevice, c->stream()));
          std::vector<unsigned long long> off;
          body = (size_t)export_text_prepare(c, d_keys, (uint32_t)n, c->b_ex_starts.as<int32_t>(), 1, off);
          hl = (size_t)snprintf(head, sizeof head, "%d\n%d\n", 128, n);
@@ -1135,7 +1118,7 @@ int hesaff_stage_export(hesaff_ctx *c, const hesaff_keypoint *keys, int n, float
          c->b_generic.ensure(body + 16);
          if (format == HESAFF_OUT_TEXT) export_text_write(c, d_keys, (uint32_t)n, (char *)c->b_generic.p);
          else export_bin_rows(c, d_keys, (uint32_t)n, (char *)c->b_generic.p);
-         HIP_TRY(hipMemcpyAsync(buf + hl, c->b_generic.p, body, hipMemcpyDeviceToHost, c->stream));
+         HIP_TRY(hipMemcpyAsync(buf + hl, c->b_generic.p, body, hipMemcpyDeviceToHost, c->stream()));
       }
       finish_stream(c);
       *out = buf;
@@ -1160,11 +1143,11 @@ int hesaff_stage_fmt_g(hesaff_ctx *c, int n, const float *v, char *text, int32_t
    float *d_v = c->b_stage.as<float>();
    int32_t *d_len = (int32_t *)(d_v + N);
    char *d_text = (char *)(d_len + N);
-   HIP_TRY(hipMemcpyAsync(d_v, v, N * 4, hipMemcpyHostToDevice, c->stream));
-   HIP_TRY(hipMemsetAsync(d_text, 0, N * 16, c->stream));
-   hipLaunchKernelGGL(k_fmt_g_test, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, (const float *)d_v, d_text, d_len);
-   HIP_TRY(hipMemcpyAsync(text, d_text, N * 16, hipMemcpyDeviceToHost, c->stream));
-   HIP_TRY(hipMemcpyAsync(lens, d_len, N * 4, hipMemcpyDeviceToHost, c->stream));
+   HIP_TRY(hipMemcpyAsync(d_v, v, N * 4, hipMemcpyHostToDevice, c->stream()));
+   HIP_TRY(hipMemsetAsync(d_text, 0, N * 16, c->stream()));
+   hipLaunchKernelGGL(k_fmt_g_test, dim3((n + 255) / 256), dim3(256), 0, c->stream(), n, (const float *)d_v, d_text, d_len);
+   HIP_TRY(hipMemcpyAsync(text, d_text, N * 16, hipMemcpyDeviceToHost, c->stream()));
+   HIP_TRY(hipMemcpyAsync(lens, d_len, N * 4, hipMemcpyDeviceToHost, c->stream()));
    finish_stream(c);
    HS_API_END(c)
 }
@@ -1181,9 +1164,9 @@ int hesaff_stage_jpeg_pixels(hesaff_ctx *c, const hesaff_jpeg_layout *layout, in
    DevBuf &b_jcoef = c->slot[0].b_jcoef;   // (no chunk is on its way during a stage call)
    b_jcoef.ensure(blob_bytes * (size_t)n);
    c->b_stage.ensure(img * (size_t)n);
-   HIP_TRY(hipMemcpyAsync(b_jcoef.p, blobs, blob_bytes * (size_t)n, hipMemcpyHostToDevice, c->stream));
-   jpeg_pixels(c, b_jcoef.as<uint8_t>(), g, n, c->b_stage.as<uint8_t>(), img, c->stream);
-   HIP_TRY(hipMemcpyAsync(pixels, c->b_stage.p, img * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+   HIP_TRY(hipMemcpyAsync(b_jcoef.p, blobs, blob_bytes * (size_t)n, hipMemcpyHostToDevice, c->stream()));
+   jpeg_pixels(c, b_jcoef.as<uint8_t>(), g, n, c->b_stage.as<uint8_t>(), img, c->stream());
+   HIP_TRY(hipMemcpyAsync(pixels, c->b_stage.p, img * (size_t)n, hipMemcpyDeviceToHost, c->stream()));
    finish_stream(c);
    HS_API_END(c)
 }
@@ -1196,11 +1179,11 @@ int hesaff_stage_math(hesaff_ctx *c, int n, const float *a, const float *b, floa
    if (n == 0) return HESAFF_OK;
    c->b_stage.ensure((size_t)n * 16);
    float *d_a = c->b_stage.as<float>(), *d_b = d_a + n, *d_at = d_b + n, *d_pw = d_at + n;
-   HIP_TRY(hipMemcpyAsync(d_a, a, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-   HIP_TRY(hipMemcpyAsync(d_b, b, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-   hipLaunchKernelGGL(k_math, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, (const float *)d_a, (const float *)d_b, d_at, d_pw);
-   if (atan2_out) HIP_TRY(hipMemcpyAsync(atan2_out, d_at, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-   if (pow2_out) HIP_TRY(hipMemcpyAsync(pow2_out, d_pw, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+   HIP_TRY(hipMemcpyAsync(d_a, a, (size_t)n * 4, hipMemcpyHostToDevice, c->stream()));
+   HIP_TRY(hipMemcpyAsync(d_b, b, (size_t)n * 4, hipMemcpyHostToDevice, c->stream()));
+   hipLaunchKernelGGL(k_math, dim3((n + 255) / 256), dim3(256), 0, c->stream(), n, (const float *)d_a, (const float *)d_b, d_at, d_pw);
+   if (atan2_out) HIP_TRY(hipMemcpyAsync(atan2_out, d_at, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream()));
+   if (pow2_out) HIP_TRY(hipMemcpyAsync(pow2_out, d_pw, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream()));
    finish_stream(c);
    HS_API_END(c)
 }
@@ -1214,12 +1197,12 @@ int hesaff_stage_math_sift(hesaff_ctx *c, int n, const float *gy, const float *g
    if (n == 0) return HESAFF_OK;
    c->b_stage.ensure((size_t)n * 24);
    float *d = c->b_stage.as<float>();
-   HIP_TRY(hipMemcpyAsync(d, gy, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-   HIP_TRY(hipMemcpyAsync(d + n, gx, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-   hipLaunchKernelGGL(k_math_sift, dim3(std::min(4096, (n + 255) / 256)), dim3(256), 0, c->stream, n, (const float *)d, (const float *)(d + n),
+   HIP_TRY(hipMemcpyAsync(d, gy, (size_t)n * 4, hipMemcpyHostToDevice, c->stream()));
+   HIP_TRY(hipMemcpyAsync(d + n, gx, (size_t)n * 4, hipMemcpyHostToDevice, c->stream()));
+   hipLaunchKernelGGL(k_math_sift, dim3(std::min(4096, (n + 255) / 256)), dim3(256), 0, c->stream(), n, (const float *)d, (const float *)(d + n),
                       d + 2 * (size_t)n, d + 3 * (size_t)n, d + 4 * (size_t)n, d + 5 * (size_t)n);
    float *outs[4] = {ori_general, ori_nd, grad_general, grad_nd};
-   for (int q = 0; q < 4; q++) HIP_TRY(hipMemcpyAsync(outs[q], d + (2 + q) * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+   for (int q = 0; q < 4; q++) HIP_TRY(hipMemcpyAsync(outs[q], d + (2 + q) * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream()));
    finish_stream(c);
    HS_API_END(c)
 }
@@ -1251,7 +1234,7 @@ int hesaff_table_gauss_kernel(float sigma, int cap, float *taps, int *ksize)
    *ksize = K;
    if (taps) {
       if (cap < K) return HESAFF_ERR_ARG;
-      if (K == 1) taps[0] = 1.0f; else hesaff::gauss_taps(K, sigma, taps);
+      hesaff::blur_taps(K, sigma, taps);
    }
    return HESAFF_OK;
 }

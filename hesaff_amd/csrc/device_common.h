@@ -8,11 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hmath.h"
-#include "plan_consts.h"   // HS_PATCH, HS_BORDER, HS_NSCALES, HS_MAX_OCTAVES and the other constants the host plan shares
-
-#define HS_PATCH_PIX (41 * 41)
-#define HS_SMM 19                   // smmWindowSize, affine.h:43
-#define HS_SMM_PIX (19 * 19)
+#include "plan_consts.h"   // HS_PATCH, HS_BORDER, HS_NSCALES, HS_MAX_OCTAVES, DConsts and the other constants the host plans share
 
 // A batch of equally sized float planes: [img][rows][pitch]
 struct DPlane {
@@ -20,17 +16,6 @@ struct DPlane {
    int rows, cols, pitch;
    long long img_stride;   // floats between consecutive images
    __host__ __device__ float *img(int b) const { return p + (long long)b * img_stride; }
-};
-
-// constants of one context, uploaded once (tables) / per call (thresholds)
-struct DConsts {
-   float edgeScoreThreshold, finalThreshold, positiveThreshold, negativeThreshold;  // pyramid.h:60-64
-   float convergenceThreshold;  // affine.h:41
-   float affInitialSigma;       // affine.h:40
-   float mrSize;                // affine.h:44
-   float maxBinValue;           // siftdesc.h:29
-   int maxIterations;           // affine.h:39
-   float pd0;                   // pixelDistance of octave 0: 1, or 0.5 with upscaleInputImage (pyramid.cpp:264,270)
 };
 
 // Pins a value: everything it depends on (in particular its global loads) is issued before this

@@ -87,7 +87,6 @@ struct OctaveSchedule {
    float blur_sigma[5];     // [i], i = 1..4 : curSigma * sqrt(step^2 - 1)
    float level_sigma[5];    // [0] = initialSigma, [i] = curSigma * step
    float norm2[5];          // (sigma*sigma)^2 handed to hessianResponse (pyramid.cpp:76)
-};
-OctaveSchedule make_schedule(float initialSigma, bool upscale);
+};   // (make_schedule: context_tables.h)
 
 } // namespace hesaff

@@ -31,15 +31,8 @@ struct SiftIO {
    uint32_t h_lo, h_hi;
 };
 
-#define HS_VO_DIM 40                          // rows/columns of the patch that carry weight in samplePatch
+// (HS_VO_DIM and the layout of a keypoint's gradient pairs in HBM - HS_VO_ITEMS, HS_VO_ZERO, HS_VO_PITCH: plan_consts.h)
 #define HS_VO_TILE (HS_VO_DIM * HS_VO_DIM)    // float2 of k_sift_grad's LDS tile (row-major 40 x 40)
-// The gradient pairs of a keypoint in HBM (written once by k_sift_grad, read by k_sift_hist: the largest stream of the descriptor stage, and
-// what both kernels are bound by - profiles/r05_notes.md).  Compact layout: only the 16-byte items (2 pixels) of every row's span inside the
-// circular mask are stored, row after row (row r: items f_lo(r) .. f_hi(r) of its 20) - 642 items + 6 zero items instead of 800: 10.4 KB
-// instead of 12.8 KB per keypoint.  KpTables::vo_rows / vo_src (host-built from the mask itself) describe the layout to both kernels.
-#define HS_VO_ITEMS 648   // 16-byte items per keypoint; the items from HS_VO_ZERO on are zero
-#define HS_VO_ZERO 642    // an item that is (0, 0, 0, 0) in every keypoint's block
-#define HS_VO_PITCH (2 * HS_VO_ITEMS)             // float2 per keypoint in the gradient-pair buffer
 #define HS_SIFT_MSK_IT 5   // ceil(1245 / 256): pixels inside the circular mask per thread of a 256-thread block
 #define SM_TILE 64
 

@@ -40,35 +40,7 @@
 #include "kernels_jpeg.h"
 #include "chunk_engine.h"
 #include "batch_plan.h"
-
-namespace hesaff {
-OctaveSchedule make_schedule(float initialSigma, bool upscale)
-{
-   OctaveSchedule s;
-   // pyramid.cpp:227 : powf(2, 1/numberOfScales) ; hm_pow2f == glibc powf(2,.) bit for bit
-   const float sigmaStep = hm_pow2f(1.0f / (float)HS_NSCALES);
-   float curSigma = initialSigma;
-   // pyramid.cpp:263-280: the input is taken to be blurred by 0.5 already (1.0 after the 2x up-sampling);
-   // no initial blur when initialSigma does not exceed that
-   const float inputSigma = upscale ? 0.5f * 2.0f : 0.5f;
-   s.init_sigma = initialSigma > inputSigma ? sqrtf(initialSigma * initialSigma - inputSigma * inputSigma) : 0.0f;
-   s.level_sigma[0] = curSigma;
-   s.blur_sigma[0] = 0.0f;
-   {
-      const float n = curSigma * curSigma;
-      s.norm2[0] = n * n;
-   }
-   for (int i = 1; i < HS_NSCALES + 2; i++) {
-      s.blur_sigma[i] = curSigma * sqrtf(sigmaStep * sigmaStep - 1.0f);
-      const float sigma = curSigma * sigmaStep;
-      s.level_sigma[i] = sigma;
-      const float n = sigma * sigma;
-      s.norm2[i] = n * n;
-      curSigma *= sigmaStep;
-   }
-   return s;
-}
-} // namespace hesaff
+#include "context_tables.h"
 
 static thread_local std::string g_create_error;
 
@@ -83,7 +55,7 @@ static thread_local std::string g_create_error;
    } while (0)
 
 using hesaff_engine::HsError;
-using namespace hesaff_plan;   // batch_plan.h: the layouts and the launch arithmetic of a batch
+using namespace hesaff_plan;   // batch_plan.h, context_tables.h: the layouts, the launch arithmetic and the tables of a batch
 
 // Host wait for a HIP event WITHOUT a spinning core.  hipEventSynchronize spins in this runtime even on events created with
 // hipEventBlockingSync (measured in round 5 with CLOCK_THREAD_CPUTIME_ID around the call: 96 ms of CPU for a 96 ms wait, one busy core per
@@ -255,7 +227,21 @@ struct DevEvent {
 // The HIP streams a context runs on (four compute streams, two copy streams).  They are created once per device and handed from a
 // destroyed context to the next one (capi_impl.h): which hardware queues a NEW stream shares depends on everything the process has
 // created before, so only reuse keeps the queue pairing of the first context.  Contexts alive at the same time get sets of their own.
-struct StreamSet { hipStream_t comp[4] = {nullptr, nullptr, nullptr, nullptr}; hipStream_t h2d = nullptr, d2h = nullptr; };
+//
+// The HIP runtime runs the streams of one priority on FOUR hardware queues, and kernels of streams that share a queue do not
+// overlap.  Which of a context's seven logical streams (main, patch bins 0-3, descriptor, affine) end up together moves the step
+// by up to 8 %, and with seven HIP streams it depends on what else the process has created.  So the pairing is made explicit:
+// four HIP streams, each serving the logical streams that measured best together
+// (profiles/r04_notes.md):   main + bin 3 | bin 0 + bin 1 | bin 2 + affine | descriptor.
+struct StreamSet {
+   hipStream_t comp[4] = {nullptr, nullptr, nullptr, nullptr};
+   hipStream_t h2d = nullptr, d2h = nullptr;   // made when the first chunk needs them (ensure_copy_streams, capi_impl.h)
+   static constexpr int group[7] = {0, 1, 1, 2, 0, 3, 2};   // logical stream -> HIP stream: 0 main, 1-4 patch bins 0-3, 5 descriptor, 6 affine
+   hipStream_t main() const { return comp[group[0]]; }
+   hipStream_t bin(int i) const { return comp[group[1 + i]]; }   // side stream of the patch stage's window-size bin i (0..3)
+   hipStream_t sift() const { return comp[group[5]]; }           // descriptor kernels of every image group
+   hipStream_t affine() const { return comp[group[6]]; }         // affine shape of image group g+1 runs beside the patch extraction of group g
+};
 static std::mutex g_sets_mu;
 static std::map<int, std::vector<StreamSet>> g_idle_sets;   // per device: the sets no context is using
 static bool take_stream_set(int device, StreamSet &out)
@@ -273,35 +259,52 @@ static void give_stream_set(int device, const StreamSet &s)
    g_idle_sets[device].push_back(s);
 }
 
+// The tables of a context on the device (context_tables.h makes them), and the view of them the kernels take.  Either method
+// leaves the view current.
+struct DeviceTables {
+   DevBuf smm, sift_mask, bin0, bin1, w0, w1, mask_idx, sgrad_nb, sgrad_om, vo_rows, vo_src, pyr_taps, patch_taps, patch_off, patch_k;
+   KpTables view = {};   // (view.max_p0: the patch tap table covers odd P0 <= max_p0)
+   template <class T> static const T *put(DevBuf &b, const std::vector<T> &v)
+   {
+      b.ensure(std::max<size_t>(v.size() * sizeof(T), 16));
+      HIP_TRY(hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+      return b.as<T>();
+   }
+   void upload(const ContextTables &t)
+   {
+      view.smm_mask = put(smm, t.smm); view.sift_mask = put(sift_mask, t.sift_mask);
+      view.mask_idx = put(mask_idx, t.mask_idx); view.n_masked = t.n_masked;
+      view.sgrad_nb = (const int4 *)put(sgrad_nb, t.sgrad_nb); view.sgrad_om = (const int2 *)put(sgrad_om, t.sgrad_om);
+      view.vo_rows = (const int4 *)put(vo_rows, t.vo_rows); view.vo_src = put(vo_src, t.vo_src);
+      view.bin0 = put(bin0, t.bin0); view.bin1 = put(bin1, t.bin1); view.w0 = put(w0, t.w0); view.w1 = put(w1, t.w1);
+      put(pyr_taps, t.pyr_taps);
+   }
+   void grow_patch_taps(int max_p0)
+   {
+      if (max_p0 <= view.max_p0) return;
+      const PatchTaps t = build_patch_taps(max_p0);
+      view.patch_taps = put(patch_taps, t.taps); view.patch_tap_off = put(patch_off, t.off); view.patch_tap_k = put(patch_k, t.k);
+      view.max_p0 = t.max_p0;
+   }
+};
+
 struct hesaff_ctx {
    hesaff_params par;
    int device = 0;
-   StreamSet sset;
-   hipStream_t stream = nullptr;
+   StreamSet sset;   // every HIP stream of the context
+   hipStream_t stream() const { return sset.main(); }
    std::string err;
-   hesaff::OctaveSchedule sched;
-   DConsts consts;
-
-   // tables
-   DevBuf t_smm, t_sift, t_bin0, t_bin1, t_w0, t_w1, t_pyr_taps, t_patch_taps, t_patch_off, t_patch_k;
-   int pyr_K[5];          // [0] initial blur (0 = none), [1..4] octave blurs
-   int pyr_tap_off[5];
-   bool pyr_march = false;   // the four octave blurs have K = 9, 11, 13, 15 (default initialSigma): marching kernel
-   int max_p0 = 0;        // tap table covers odd P0 <= max_p0
+   ContextScalars ct;     // the schedule, DConsts and the pyramid blurs' tap counts (build_context_tables)
+   DeviceTables tables;
    int batch_max_p = 0;   // largest window side P of the current batch's huge windows (known after detection)
-   int n_masked = 0;
-   KpTables tables;
 
-   // geometry of the current buffer plan (H x W: the images; the pyramid starts at (H << up) x (W << up))
-   int up = 0;            // upscaleInputImage, pyramid.h:34
+   // geometry of the current buffer plan (H x W: the images; the pyramid starts at (H << ct.up) x (W << ct.up))
    int B = 0, H = 0, W = 0;
    std::vector<OctGeom> oct;
    long long words_per_image = 0;
    uint32_t cap = 0;      // keypoint capacity of a batch
    uint32_t cand_cap = 0; // candidate slots of one octave (k_extrema_march -> k_localize)
-   bool map_clean = false;   // b_map holds nothing but 0xFFFFFFFF and bids of epochs above map_epoch (OctaveCtx::map_epoch, kernels_pyramid.h)
-   int map_kbits = 32;       // bits of an order key (3 x pixels of the first pyramid level)
-   uint32_t map_epoch = 0;   // the last epoch handed out; 0: the next pass refills the map first
+   OrderMapEpochs map_epochs;   // of b_map (batch_plan.h)
 
    // the buffers whose size follows the plan's geometry (B x H x W and the keypoint capacity): a plan the device cannot hold gives
    // all of them back at once (plan())
@@ -398,10 +401,9 @@ struct hesaff_ctx {
    } pin_read;
    std::vector<PinBuf> pin_out;       // result blocks: one per chunk of the current call (hesaff_detect_batch), or a ring of three
    hesaff_engine::BlockRing ring;     // (hesaff_detect_batch_cb, hesaff_process_files: a block returns to the ring when its consumer is done with it)
-   hipStream_t h2d_stream = nullptr, d2h_stream = nullptr;
    float export_ms = 0.0f; int32_t export_rows = 0;
    PinBuf h_small_end, h_small_mid, h_small_exp;   // small results the host reads every batch (PinBuf::ensure_small)
-   DevBuf t_mask_idx, t_sgrad_nb, t_sgrad_om, t_vo_rows, t_vo_src, b_rowprefix, b_trows, b_trows2, b_trows3;
+   DevBuf b_rowprefix, b_trows, b_trows2, b_trows3;
    DevBuf b_jplane;   // JPEG chunks: the component planes after the inverse DCT (kernels_jpeg.h)
    DevBuf b_ex_len, b_ex_sums, b_ex_off, b_ex_imgoff, b_ex_starts;   // device export (kernels_export.h): row lengths, sums / offsets per 64 rows, offsets per image
    size_t rows_lds_set = 0;            // dynamic LDS opt-in of k_patch_large_rows on THIS device
@@ -418,9 +420,6 @@ struct hesaff_ctx {
    int resume = 0;                     // hesaff_set_resume: 0 off, 1 skip complete outputs (O(1) test), 2 strict (rows counted)
    int pool_priority = -1;             // hesaff_set_pool_priority: -1 lower the pool's priority when the plan is CPU-starved, 0 never, 1 always
    int stage_threads = 4;              // host threads that copy a chunk's pixels into pinned memory (hesaff_process_files: within its thread budget)
-   hipStream_t side_streams[HS_NSIDE] = {nullptr, nullptr, nullptr, nullptr};
-   hipStream_t sift_stream = nullptr;     // descriptor kernels of every image group
-   hipStream_t aff_stream = nullptr;      // affine shape of image group g+1 runs beside the patch extraction of group g
    DevEvent ev_detect_done, ev_batch_done;   // blocking-sync events: the host sleeps instead of spinning
    std::vector<DevEvent> ev_aff;             // one per image group, grown on demand
    DevEvent ev_extract_done[HS_NSLOT], ev_sift_done[HS_NSLOT];
@@ -444,125 +443,6 @@ hipEvent_t get_event(hesaff_ctx *c)
 {
    if (c->ev_used == c->ev_pool.size()) c->ev_pool.emplace_back(hipEventDefault);
    return c->ev_pool[c->ev_used++];
-}
-
-template <class T> void upload(DevBuf &b, const std::vector<T> &v)
-{
-   b.ensure(std::max<size_t>(v.size() * sizeof(T), 16));
-   HIP_TRY(hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-}
-
-void build_tables(hesaff_ctx *c)
-{
-   std::vector<float> smm(HS_SMM_PIX), sm(HS_PATCH_PIX), w0(HS_PATCH), w1(HS_PATCH);
-   std::vector<int32_t> b0(HS_PATCH), b1(HS_PATCH);
-   hesaff::gauss_mask(HS_SMM, smm.data());
-   hesaff::circ_gauss_mask(HS_PATCH, sm.data());
-   hesaff::sift_bins(b0.data(), b1.data(), w0.data(), w1.data());
-   {
-      std::vector<int32_t> midx;
-      for (int i = 0; i < HS_PATCH_PIX; i++)
-         if (sm[i] > 0) midx.push_back(i);
-      c->n_masked = (int)midx.size();
-      upload(c->t_mask_idx, midx);
-      // k_sift_grad's per-pixel constants (affine.cpp:14-33 stencil convention: one-sided differences at the patch border)
-      std::vector<int32_t> nb(4 * 1280, 0), om(2 * 1280, 0);
-      for (size_t s = 0; s < 1280; s++) {
-         const bool used = s < midx.size();
-         const int i = used ? midx[s] : 0, r = i / HS_PATCH, cc = i - r * HS_PATCH;
-         const bool valid = used && r < HS_PATCH - 1 && cc < HS_PATCH - 1;   // row / column 40 carry no weight in samplePatch
-         if (valid) {
-            nb[4 * s + 0] = 4 * (cc == 0 ? i : i - 1);
-            nb[4 * s + 1] = 4 * (i + 1);
-            nb[4 * s + 2] = 4 * (r == 0 ? i : i - HS_PATCH);
-            nb[4 * s + 3] = 4 * (i + HS_PATCH);
-         }
-         om[2 * s + 0] = valid ? r * (HS_PATCH - 1) + cc : -1;
-         memcpy(&om[2 * s + 1], &sm[i], 4);
-      }
-      upload(c->t_sgrad_nb, nb); upload(c->t_sgrad_om, om);
-      // layout of the gradient pairs in HBM (kernels_sift.h: HS_VO_ITEMS), from the mask itself: per row the span of 16-byte items
-      // (two pixels) that hold a pixel with weight, rows back to back
-      std::vector<int32_t> vrow(4 * HS_VO_DIM, 0);
-      std::vector<uint16_t> vsrc(HS_VO_ITEMS, 0);
-      int at = 0;
-      for (int r = 0; r < HS_VO_DIM; r++) {
-         int flo = 1, fhi = 0;
-         for (int cc = 0; cc < HS_VO_DIM; cc++)
-            if (sm[r * HS_PATCH + cc] > 0) { if (fhi < flo) flo = cc / 2; fhi = cc / 2; }
-         vrow[4 * r + 0] = at - flo; vrow[4 * r + 1] = flo; vrow[4 * r + 2] = fhi;
-         for (int f = flo; f <= fhi; f++, at++)
-            if (at < HS_VO_ITEMS) vsrc[(size_t)at] = (uint16_t)(r * (HS_VO_DIM / 2) + f);
-      }
-      // the layout constants of kernels_sift.h are those of THIS mask (helpers.cpp:131-147 at patchSize 41)
-      if (at != HS_VO_ZERO || sm[0] > 0) throw HsError(HESAFF_ERR_ARG, "internal: gradient-pair layout does not match the circular mask");
-      upload(c->t_vo_rows, vrow); upload(c->t_vo_src, vsrc);
-   }
-   upload(c->t_smm, smm); upload(c->t_sift, sm); upload(c->t_bin0, b0); upload(c->t_bin1, b1); upload(c->t_w0, w0); upload(c->t_w1, w1);
-   c->up = c->par.upscaleInputImage > 0 ? 1 : 0;
-   c->sched = hesaff::make_schedule(c->par.initialSigma, c->up != 0);
-   std::vector<float> taps;
-   for (int i = 0; i < 5; i++) {
-      const float sigma = i == 0 ? c->sched.init_sigma : c->sched.blur_sigma[i];
-      c->pyr_tap_off[i] = (int)taps.size();
-      taps.resize(taps.size() + 256, 0.0f);
-      if (i == 0 && !(c->sched.init_sigma > 0.0f)) { c->pyr_K[0] = 0; continue; }   // pyramid.cpp:276: no initial blur
-      const int K = hesaff::gauss_ksize(sigma);
-      if (K > 255) throw HsError(HESAFF_ERR_ARG, "initialSigma too large (a pyramid blur would need more than 255 taps)");
-      c->pyr_K[i] = K;
-      if (K == 1) taps[c->pyr_tap_off[i]] = 1.0f;
-      else hesaff::gauss_taps(K, sigma, taps.data() + c->pyr_tap_off[i]);
-   }
-   c->pyr_march = c->pyr_K[1] == 9 && c->pyr_K[2] == 11 && c->pyr_K[3] == 13 && c->pyr_K[4] == 15;
-   upload(c->t_pyr_taps, taps);
-   const hesaff_params &p = c->par;
-   DConsts &k = c->consts;
-   // pyramid.h:59-64
-   k.edgeScoreThreshold = (p.edgeEigenValueRatio + 1.0f) * (p.edgeEigenValueRatio + 1.0f) / p.edgeEigenValueRatio;
-   k.finalThreshold = p.threshold * p.threshold;
-   k.positiveThreshold = (float)(0.8 * k.finalThreshold);
-   k.negativeThreshold = -k.positiveThreshold;
-   k.convergenceThreshold = p.convergenceThreshold;
-   k.affInitialSigma = 1.6f;   // AffineShapeParams::initialSigma affine.h:40 (not overridden by hesaff.cpp)
-   k.mrSize = p.mrSize;
-   k.maxBinValue = p.maxBinValue;
-   k.maxIterations = p.maxIterations;
-   k.pd0 = c->up ? 0.5f : 1.0f;   // pixelDistance of octave 0, pyramid.cpp:264,270
-}
-
-// taps of the per-keypoint patch blur (affine.cpp:129: sigma = 1.5f * P0/41) for odd P0
-void ensure_patch_taps(hesaff_ctx *c, int max_p0)
-{
-   if (max_p0 <= c->max_p0) return;
-   if ((max_p0 & 1) == 0) max_p0++;
-   std::vector<float> taps;
-   std::vector<int32_t> off((max_p0 + 1) / 2), kk((max_p0 + 1) / 2);
-   for (int P0 = 1; P0 <= max_p0; P0 += 2) {
-      const float scale = (float)P0 / (float)HS_PATCH;
-      const float sigma = 1.5f * scale;
-      const int K = hesaff::gauss_ksize(sigma);
-      off[(P0 - 1) / 2] = (int32_t)taps.size();
-      kk[(P0 - 1) / 2] = K;
-      taps.resize(taps.size() + K);
-      if (K == 1) taps[taps.size() - 1] = 1.0f;
-      else hesaff::gauss_taps(K, sigma, taps.data() + off[(P0 - 1) / 2]);
-   }
-   upload(c->t_patch_taps, taps); upload(c->t_patch_off, off); upload(c->t_patch_k, kk);
-   c->max_p0 = max_p0;
-}
-
-void refresh_tables_struct(hesaff_ctx *c)
-{
-   KpTables &t = c->tables;
-   t.smm_mask = c->t_smm.as<float>(); t.sift_mask = c->t_sift.as<float>();
-   t.bin0 = c->t_bin0.as<int32_t>(); t.bin1 = c->t_bin1.as<int32_t>();
-   t.w0 = c->t_w0.as<float>(); t.w1 = c->t_w1.as<float>();
-   t.patch_taps = c->t_patch_taps.as<float>(); t.patch_tap_off = c->t_patch_off.as<int32_t>(); t.patch_tap_k = c->t_patch_k.as<int32_t>();
-   t.max_p0 = c->max_p0;
-   t.mask_idx = c->t_mask_idx.as<int32_t>();
-   t.sgrad_nb = c->t_sgrad_nb.as<int4>(); t.sgrad_om = c->t_sgrad_om.as<int2>();
-   t.vo_rows = c->t_vo_rows.as<int4>(); t.vo_src = c->t_vo_src.as<uint16_t>();
-   t.n_masked = c->n_masked;
 }
 
 DPlane make_plane(float *p, int rows, int cols, int pitch)
@@ -630,9 +510,9 @@ void plan(hesaff_ctx *c, int B, int H, int W)
       if (e.code == HESAFF_ERR_NOMEM) {
          // a plan the device cannot hold must not keep what it managed to allocate on the way (hundreds of GB for an absurd
          // capacity request): every geometry-sized buffer goes back, the next plan starts from nothing
-         (void)hipStreamSynchronize(c->stream);
+         (void)hipStreamSynchronize(c->stream());
          c->geo = hesaff_ctx::GeomBufs();
-         c->map_clean = false;
+         c->map_epochs.invalidate();
       }
       throw;
    }
@@ -641,13 +521,13 @@ void plan(hesaff_ctx *c, int B, int H, int W)
 void plan_buffers(hesaff_ctx *c, int B, int H, int W)
 {
    if (B <= c->B && H == c->H && W == c->W) return;
-   if (H < 1 || W < 1 || (H << c->up) > 65535 || (W << c->up) > 65535) throw HsError(HESAFF_ERR_ARG, "image size out of range (1..65535 at the first pyramid level)");
-   const int PH = H << c->up, PW = W << c->up;   // first pyramid level
+   if (H < 1 || W < 1 || (H << c->ct.up) > 65535 || (W << c->ct.up) > 65535) throw HsError(HESAFF_ERR_ARG, "image size out of range (1..65535 at the first pyramid level)");
+   const int PH = H << c->ct.up, PW = W << c->ct.up;   // first pyramid level
    // the cached geometry describes buffers that are about to be replaced: a failure below must not leave it valid
    c->B = c->H = c->W = 0;
    c->L.clear();
    {
-      PyramidGeom pg = pyramid_geometry(H, W, c->up);
+      PyramidGeom pg = pyramid_geometry(H, W, c->ct.up);
       c->oct = std::move(pg.oct);
       c->words_per_image = pg.words_per_image;
    }
@@ -669,7 +549,7 @@ void plan_buffers(hesaff_ctx *c, int B, int H, int W)
    }
    const int ppitch0 = round_up(PW, 64);
    const size_t pplane0 = (size_t)B * PH * ppitch0;
-   if (c->up) {
+   if (c->ct.up) {
       c->geo.b_up.ensure(pplane0 * 4);
       c->upimg = make_plane(c->geo.b_up.as<float>(), PH, PW, ppitch0);
    }
@@ -681,9 +561,8 @@ void plan_buffers(hesaff_ctx *c, int B, int H, int W)
       c->geo.b_map.ensure(std::max<size_t>((size_t)B * PH * PW * 4, 16));
       // a new block is filled once before its first use (run_detection).  Pointer AND size: ensure()'s out-of-memory path frees the old
       // block first, and the larger one may come back at the same address with a tail that was never filled
-      if (c->geo.b_map.p != before || c->geo.b_map.bytes != before_bytes) c->map_clean = false;
-      const int kb = order_key_bits(PH, PW);
-      if (kb != c->map_kbits) { c->map_kbits = kb; c->map_clean = false; }   // (another key width: epochs of the old one mean nothing)
+      if (c->geo.b_map.p != before || c->geo.b_map.bytes != before_bytes) c->map_epochs.invalidate();
+      c->map_epochs.set_key_bits(order_key_bits(PH, PW));
    }
    const long long total_words = (long long)B * words;
    c->geo.b_bitmask.ensure(std::max<size_t>((size_t)total_words * 8, 16));
@@ -709,12 +588,11 @@ void plan_buffers(hesaff_ctx *c, int B, int H, int W)
    c->geo.b_starts.ensure(starts_block((int32_t *)nullptr, B).words_allocated() * 4);   // StartsBlock, batch_plan.h
    // patch taps: P <= sqrt(W*H) + small (the det-1 window must fit)
    const int max_p0 = (int)std::floor(std::sqrt((double)W * (double)H)) + 3;
-   ensure_patch_taps(c, max_p0);
-   refresh_tables_struct(c);
+   c->tables.grow_patch_taps(max_p0);
    // per-block T' slots of the row-streamed bins (persistent grids of fixed size)
    c->b_trows2.ensure((size_t)HS_MID_BLOCKS * (HS_MID_PMAX + 2 * HS_MID_RPAD) * HS_NEED * 4);
    c->b_trows3.ensure((size_t)HS_BIG_BLOCKS * (HS_BIN3_PMAX + 2 * HS_BIG_RPAD) * HS_NEED * 4);
-   const size_t want = large_rows_lds_optin(c->max_p0);   // (refuses an image whose largest window row does not fit the LDS)
+   const size_t want = large_rows_lds_optin(c->tables.view.max_p0);   // (refuses an image whose largest window row does not fit the LDS)
    if (want > c->rows_lds_set) {
       set_dyn_lds(k_patch_large_rows, want);
       c->rows_lds_set = want;
@@ -725,12 +603,12 @@ void plan_buffers(hesaff_ctx *c, int B, int H, int W)
 template <class LOAD> void exclusive_scan(hesaff_ctx *c, LOAD load, long long n, uint32_t *out, uint32_t *total)
 {
    // out[0..n) exclusive prefix, *total = sum (device pointers)
-   if (n <= 0) { HIP_TRY(hipMemsetAsync(total, 0, 4, c->stream)); return; }
+   if (n <= 0) { HIP_TRY(hipMemsetAsync(total, 0, 4, c->stream())); return; }
    const int nb = (int)((n + SCAN_BLOCK - 1) / SCAN_BLOCK);
    uint32_t *bs = c->geo.b_blocksums.as<uint32_t>();
-   hipLaunchKernelGGL(k_scan_reduce<LOAD>, dim3(nb), dim3(256), 0, c->stream, load, n, bs);
-   hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, c->stream, bs, nb, total);
-   hipLaunchKernelGGL(k_scan_down<LOAD>, dim3(nb), dim3(256), 0, c->stream, load, n, bs, out);
+   hipLaunchKernelGGL(k_scan_reduce<LOAD>, dim3(nb), dim3(256), 0, c->stream(), load, n, bs);
+   hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, c->stream(), bs, nb, total);
+   hipLaunchKernelGGL(k_scan_down<LOAD>, dim3(nb), dim3(256), 0, c->stream(), load, n, bs, out);
 }
 
 // Stage timers: one HIP event pair per bracket, recorded on the stream the bracketed work is launched on.
@@ -743,7 +621,7 @@ struct StageTimer {
    {
       if (!c->profiling) return -1;
       if (kind >= 100 && c->profiling < 2) return -1;
-      if (!st) st = c->stream;
+      if (!st) st = c->stream();
       EvPair p; p.a = get_event(c); p.b = get_event(c); p.kind = kind; p.bytes = bytes;
       (void)hipEventRecord(p.a, st);
       pairs.push_back(p);
@@ -764,7 +642,7 @@ void launch_march(hesaff_ctx *c, const DPlane &in, const DPlane &outL, const DPl
    const int band = mb.band;
    if (c->debug) fprintf(stderr, "[hesaff] march K=%d %dx%d B=%d bands=%d band=%d blocks=%lld\n", K, in.cols, in.rows, B, mb.bands, band, (long long)mb.strip_blocks * B * mb.bands);
    const dim3 grid(mb.strip_blocks, (in.rows + band - 1) / band, B);
-   hipLaunchKernelGGL((k_blur_hess_march<K, WL, WR, WH, WR0, SRC>), grid, dim3(256), 0, c->stream, in, outL, outR, outHalf, taps, norm2, band, outR0, norm2_in, gs, outGray);
+   hipLaunchKernelGGL((k_blur_hess_march<K, WL, WR, WH, WR0, SRC>), grid, dim3(256), 0, c->stream(), in, outL, outR, outHalf, taps, norm2, band, outR0, norm2_in, gs, outGray);
 }
 
 template <bool WL, bool WR, bool WH>
@@ -781,7 +659,7 @@ void launch_blur_hess(hesaff_ctx *c, const DPlane &in, const DPlane &outL, const
    if (K <= 2 * BH_RMAX + 1) {
       // LDS-tile kernel: any tap count up to 15
       const dim3 grid((in.cols + BH_TW - 1) / BH_TW, (in.rows + BH_TH - 1) / BH_TH, B);
-      hipLaunchKernelGGL((k_blur_hess_tile<WL, WR, WH>), grid, dim3(256), 0, c->stream, in, outL, outR, outHalf, taps, K, norm2);
+      hipLaunchKernelGGL((k_blur_hess_tile<WL, WR, WH>), grid, dim3(256), 0, c->stream(), in, outL, outR, outHalf, taps, K, norm2);
       return;
    }
    // any larger tap count (initialSigma above ~1.9): plain two-pass blur + stand-alone response / decimation kernels
@@ -790,10 +668,10 @@ void launch_blur_hess(hesaff_ctx *c, const DPlane &in, const DPlane &outL, const
    const DPlane tmp = make_plane(c->b_generic.as<float>(), in.rows, in.cols, in.pitch);
    const DPlane blurred = WL ? outL : make_plane(c->b_generic.as<float>() + planeF, in.rows, in.cols, in.pitch);
    const dim3 grid((in.cols + 255) / 256, in.rows, B);
-   hipLaunchKernelGGL(k_blur_rows_generic, grid, dim3(256), 0, c->stream, in, tmp, taps, K);
-   hipLaunchKernelGGL(k_blur_cols_generic, grid, dim3(256), 0, c->stream, tmp, blurred, taps, K);
-   if (WR) hipLaunchKernelGGL(k_hess, grid, dim3(256), 0, c->stream, blurred, outR, norm2);
-   if (WH) hipLaunchKernelGGL(k_half, dim3((outHalf.cols + 255) / 256, outHalf.rows, B), dim3(256), 0, c->stream, blurred, outHalf);
+   hipLaunchKernelGGL(k_blur_rows_generic, grid, dim3(256), 0, c->stream(), in, tmp, taps, K);
+   hipLaunchKernelGGL(k_blur_cols_generic, grid, dim3(256), 0, c->stream(), tmp, blurred, taps, K);
+   if (WR) hipLaunchKernelGGL(k_hess, grid, dim3(256), 0, c->stream(), blurred, outR, norm2);
+   if (WH) hipLaunchKernelGGL(k_half, dim3((outHalf.cols + 255) / 256, outHalf.rows, B), dim3(256), 0, c->stream(), blurred, outHalf);
 }
 
 // The source images of a batch in device memory: B images img_stride bytes apart, rows row_stride bytes apart, in one of three
@@ -853,7 +731,7 @@ Lists make_lists(hesaff_ctx *c)
 void run_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float *patches_out, uint32_t h_base, uint32_t large_rows_bound,
                      const PlaneTab *pt = nullptr)
 {
-   hipStream_t st = c->stream;
+   hipStream_t st = c->stream();
    PatchIO io;
    memset(&io, 0, sizeof io);
    io.image = image;
@@ -862,36 +740,36 @@ void run_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float *
    if (c->fast_pyramid && pt) {
       // hesaff_params.fast = 2: bin 0 (P <= 41) on the parity kernel, every larger window from the pyramid (k_patch_pyramid)
       hipStream_t s0 = st;
-      const bool forked = c->side_streams[0] && !c->no_overlap;
+      const bool forked = !c->no_overlap;
       if (forked) {
          HIP_TRY(hipEventRecord(c->ev_fork, st));
-         HIP_TRY(hipStreamWaitEvent(c->side_streams[0], c->ev_fork, 0));
-         s0 = c->side_streams[0];
+         HIP_TRY(hipStreamWaitEvent(c->sset.bin(0), c->ev_fork, 0));
+         s0 = c->sset.bin(0);
       }
-      hipLaunchKernelGGL(k_patch_extract_small<0>, dim3(c->g_small0), dim3(256), small_extract_lds_bytes(0), s0, s.hl, s.pw, io, c->tables);
+      hipLaunchKernelGGL(k_patch_extract_small<0>, dim3(c->g_small0), dim3(256), small_extract_lds_bytes(0), s0, s.hl, s.pw, io, c->tables.view);
       if (forked) HIP_TRY(hipEventRecord(c->ev_join[0], s0));
-      hipLaunchKernelGGL(k_patch_pyramid, dim3((uint32_t)c->n_cu * 32u), dim3(256), 0, st, s.hl, s.pw, io, *pt, (int)c->oct.size(), c->consts.pd0, 1);
+      hipLaunchKernelGGL(k_patch_pyramid, dim3((uint32_t)c->n_cu * 32u), dim3(256), 0, st, s.hl, s.pw, io, *pt, (int)c->oct.size(), c->ct.consts.pd0, 1);
       if (forked) HIP_TRY(hipStreamWaitEvent(st, c->ev_join[0], 0));
       return;
    }
    // The bins are independent (disjoint keypoints) and each kernel leaves CU resources idle
    // (LDS- or latency-bound), so they run concurrently on side streams.
    hipStream_t s0 = st, s1 = st, s2 = st, s3 = st;
-   const bool forked = c->side_streams[0] && !c->no_overlap;
+   const bool forked = !c->no_overlap;
    if (forked) {
       HIP_TRY(hipEventRecord(c->ev_fork, st));
-      for (int i = 0; i < HS_NSIDE; i++) HIP_TRY(hipStreamWaitEvent(c->side_streams[i], c->ev_fork, 0));
-      s0 = c->side_streams[0]; s1 = c->side_streams[1]; s2 = c->side_streams[2]; s3 = c->side_streams[3];
+      for (int i = 0; i < HS_NSIDE; i++) HIP_TRY(hipStreamWaitEvent(c->sset.bin(i), c->ev_fork, 0));
+      s0 = c->sset.bin(0); s1 = c->sset.bin(1); s2 = c->sset.bin(2); s3 = c->sset.bin(3);
    }
    {
       PatchIO io2 = io;
       io2.trows = c->b_trows2.as<float>();
       PatchIO io3 = io;
       io3.trows = c->b_trows3.as<float>();
-      hipLaunchKernelGGL(k_patch_extract_small<0>, dim3(c->g_small0), dim3(256), small_extract_lds_bytes(0), s0, s.hl, s.pw, io, c->tables);
-      hipLaunchKernelGGL(k_patch_extract_small<1>, dim3(c->g_small1), dim3(256), small_extract_lds_bytes(1), s1, s.hl, s.pw, io, c->tables);
-      hipLaunchKernelGGL(k_patch_mid<HS_MID_PMAX>, dim3(c->g_mid), dim3(256), mid_lds_bytes(), s2, s.hl, s.pw, io2, c->tables);
-      hipLaunchKernelGGL(k_patch_mid<HS_BIN3_PMAX>, dim3(c->g_big), dim3(256), big_lds_bytes(), s3, s.hl, s.pw, io3, c->tables);
+      hipLaunchKernelGGL(k_patch_extract_small<0>, dim3(c->g_small0), dim3(256), small_extract_lds_bytes(0), s0, s.hl, s.pw, io, c->tables.view);
+      hipLaunchKernelGGL(k_patch_extract_small<1>, dim3(c->g_small1), dim3(256), small_extract_lds_bytes(1), s1, s.hl, s.pw, io, c->tables.view);
+      hipLaunchKernelGGL(k_patch_mid<HS_MID_PMAX>, dim3(c->g_mid), dim3(256), mid_lds_bytes(), s2, s.hl, s.pw, io2, c->tables.view);
+      hipLaunchKernelGGL(k_patch_mid<HS_BIN3_PMAX>, dim3(c->g_big), dim3(256), big_lds_bytes(), s3, s.hl, s.pw, io3, c->tables.view);
    }
    // the rare huge windows (P > 512): row tasks over all of them, then one block per keypoint, on the main stream, which shares its HIP
    // stream (= hardware queue) with bin 3.  That queue is the stage's longest on photographs (8.1 + 8.8 + 1.9 ms per 32 photograph mosaics
@@ -907,16 +785,16 @@ void run_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float *
       io.overflow = &s.counters->head.row_overflow;
       hipLaunchKernelGGL(k_large_prefix, dim3(1), dim3(256), 0, st, s.pw, c->b_rowprefix.as<uint32_t>());
       // one launch, or two when the batch's largest window is far above the common ones (large_rows_split, large_rows_launch: batch_plan.h)
-      const LargeSplit sp = large_rows_split(c->max_p0, c->batch_max_p);
+      const LargeSplit sp = large_rows_split(c->tables.view.max_p0, c->batch_max_p);
       for (int i = 0; i < sp.n; i++) {
-         const LargeLaunch ll = large_rows_launch(sp.p_hi[i], c->max_p0, large_rows_bound);
-         hipLaunchKernelGGL(k_patch_large_rows, dim3(ll.grid_blocks), dim3(64 * ll.wavefronts), ll.lds_bytes, st, s.hl, s.pw, io, c->tables, ll.srow_stride,
+         const LargeLaunch ll = large_rows_launch(sp.p_hi[i], c->tables.view.max_p0, large_rows_bound);
+         hipLaunchKernelGGL(k_patch_large_rows, dim3(ll.grid_blocks), dim3(64 * ll.wavefronts), ll.lds_bytes, st, s.hl, s.pw, io, c->tables.view, ll.srow_stride,
                             ll.tap_stride, ll.nrow, sp.p_lo[i], std::min(sp.p_hi[i], 0x7ffffff0));
       }
-      hipLaunchKernelGGL(k_patch_large_finish, dim3(c->g_lfin), dim3(256), 0, st, s.pw, io, c->tables);
+      hipLaunchKernelGGL(k_patch_large_finish, dim3(c->g_lfin), dim3(256), 0, st, s.pw, io, c->tables.view);
    }
    if (forked) {
-      for (int i = 0; i < HS_NSIDE; i++) HIP_TRY(hipEventRecord(c->ev_join[i], c->side_streams[i]));
+      for (int i = 0; i < HS_NSIDE; i++) HIP_TRY(hipEventRecord(c->ev_join[i], c->sset.bin(i)));
       for (int i = 0; i < HS_NSIDE; i++) HIP_TRY(hipStreamWaitEvent(st, c->ev_join[i], 0));
    }
 }
@@ -925,9 +803,9 @@ void run_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float *
 void launch_image_large_rows(hesaff_ctx *c, const Lists &s, int B)
 {
    const StartsBlock<uint32_t> sb = starts_block(c->geo.b_starts.as<uint32_t>(), B);
-   HIP_TRY(hipMemsetAsync(sb.large_rows(), 0, sb.words_to_clear() * 4, c->stream));
-   hipLaunchKernelGGL(k_image_large_rows, dim3(512), dim3(256), 0, c->stream, s.hl, (const uint32_t *)&s.counters->head.hess_total, c->consts.mrSize,
-                      sb.large_rows(), B, c->max_p0);
+   HIP_TRY(hipMemsetAsync(sb.large_rows(), 0, sb.words_to_clear() * 4, c->stream()));
+   hipLaunchKernelGGL(k_image_large_rows, dim3(512), dim3(256), 0, c->stream(), s.hl, (const uint32_t *)&s.counters->head.hess_total, c->ct.consts.mrSize,
+                      sb.large_rows(), B, c->tables.view.max_p0);
 }
 
 // The scale-space + detection part for the current plan; fills the ordered Hessian list.
@@ -938,16 +816,16 @@ void launch_image_large_rows(hesaff_ctx *c, const Lists &s, int B)
 void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, StageTimer &tm, bool keep_all_planes, float *planes_out,
                    bool detect = true)
 {
-   const hesaff::OctaveSchedule &sc = c->sched;
-   hipStream_t st = c->stream;
+   const hesaff::OctaveSchedule &sc = c->ct.sched;
+   hipStream_t st = c->stream();
    CounterBlock *cnt = s.counters;
-   const float *ptaps = c->t_pyr_taps.as<float>();
+   const float *ptaps = c->tables.pyr_taps.as<float>();
    if (detect) {
       HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(CounterBlock), st));
       HIP_TRY(hipMemsetAsync(c->geo.b_bitmask.p, 0, std::max<size_t>((size_t)B * c->words_per_image * 8, 8), st));
       // octaveMap (pyramid.cpp:226: zeroed per octave): the order-key map is filled with "free" when it is new; every pass over an octave then bids
       // with keys of a fresh, smaller epoch (OctaveCtx::map_epoch), so what earlier passes left behind never wins - no fill and no reset per octave
-      if (!c->map_clean) { HIP_TRY(hipMemsetAsync(c->geo.b_map.p, 0xFF, c->geo.b_map.bytes, st)); c->map_epoch = c->map_kbits < 32 ? (0xffffffffu >> c->map_kbits) : 0u; c->map_clean = true; }
+      if (c->map_epochs.begin_batch()) HIP_TRY(hipMemsetAsync(c->geo.b_map.p, 0xFF, c->geo.b_map.bytes, st));
    }
 
    int t = tm.begin(T_PYR);
@@ -955,19 +833,19 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
    // Default parameters: grey conversion (hesaff.cpp:138-148) fused into the initial blur 0.5 -> 1.6 (pyramid.cpp:276-280,
    // K = 11): the source images are read once, the float grey plane (normalizeAffine's input) and L0 are written.
    // 8-bit images: 9 B/px (read 1, write 4 + 4); float planes: 12 B/px (read 4, write 4 + 4).
-   const bool fused_gray = !c->oct.empty() && c->pyr_K[0] == 11 && !c->up;
+   const bool fused_gray = !c->oct.empty() && c->ct.pyr_K[0] == 11 && !c->ct.up;
    if (fused_gray) {
       GraySrc gs;
       gs.p = src.p; gs.channels = src.channels(); gs.img_stride = src.img_stride; gs.row_stride = src.row_stride;
       const int tb = tm.begin(T_BLURHESS, 0);   // not one of the 58 B/px launches (bytes 0)
       if (src.format == HS_SRC_F32)
-         launch_march<11, true, false, false, false, SRC_F32>(c, c->gray, c->L[0], none, none, ptaps + c->pyr_tap_off[0], 0.0f, B, DPlane(), 0.0f, gs, c->gray);
+         launch_march<11, true, false, false, false, SRC_F32>(c, c->gray, c->L[0], none, none, ptaps + c->ct.pyr_tap_off[0], 0.0f, B, DPlane(), 0.0f, gs, c->gray);
       else
-         launch_march<11, true, false, false, false, SRC_U8>(c, c->gray, c->L[0], none, none, ptaps + c->pyr_tap_off[0], 0.0f, B, DPlane(), 0.0f, gs, c->gray);
+         launch_march<11, true, false, false, false, SRC_U8>(c, c->gray, c->L[0], none, none, ptaps + c->ct.pyr_tap_off[0], 0.0f, B, DPlane(), 0.0f, gs, c->gray);
       tm.end(tb);
    } else {
       // grey conversion; without an initial blur (initialSigma <= the input's own blur) it is the first level directly
-      const bool direct = c->pyr_K[0] == 0 && !c->oct.empty();
+      const bool direct = c->ct.pyr_K[0] == 0 && !c->oct.empty();
       if (src.format == HS_SRC_F32) {
          // float planes are the grey plane already (pyramid.h:73): a pitched copy into c->gray
          const size_t wb = (size_t)c->W * 4, dpitch = (size_t)c->gray.pitch * 4;
@@ -981,17 +859,17 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
          const dim3 grid((c->W + 255) / 256, c->H, B);
          hipLaunchKernelGGL(k_gray, grid, dim3(256), 0, st, src.p, src.channels(), src.img_stride, src.row_stride, c->gray);
       }
-      if (c->up) {
+      if (c->ct.up) {
          // pyramid.cpp:267-271: the first level is the 2x up-sampled image (doubleImage, helpers.cpp:297-329)
          const dim3 g2((c->upimg.cols + 255) / 256, c->upimg.rows, B);
          hipLaunchKernelGGL(k_double, g2, dim3(256), 0, st, c->gray, c->upimg);
       }
-      const DPlane &first = c->up ? c->upimg : c->gray;
+      const DPlane &first = c->ct.up ? c->upimg : c->gray;
       if (direct) HIP_TRY(hipMemcpyAsync(c->L[0].p, first.p, (size_t)B * first.img_stride * 4, hipMemcpyDeviceToDevice, st));
-      if (!c->oct.empty() && c->pyr_K[0] > 0) {
+      if (!c->oct.empty() && c->ct.pyr_K[0] > 0) {
          // pyramid.cpp:276-280 initial blur 0.5 -> initialSigma
          const int tb = tm.begin(T_BLURHESS, 0);   // initial blur: not counted in the 12N launches (bytes 0)
-         launch_blur_hess<true, false, false>(c, first, c->L[0], none, none, ptaps + c->pyr_tap_off[0], c->pyr_K[0], 0.0f, B);
+         launch_blur_hess<true, false, false>(c, first, c->L[0], none, none, ptaps + c->ct.pyr_tap_off[0], c->ct.pyr_K[0], 0.0f, B);
          tm.end(tb);
       }
    }
@@ -1009,7 +887,7 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
       t = tm.begin(T_PYR);
       // R0 = hessianResponse(L0) (pyramid.cpp:230) is fused into the first blur launch when the
       // marching kernel handles it (default sigmas: K = 9); otherwise a separate pass.
-      const bool fuse_r0 = c->pyr_march;
+      const bool fuse_r0 = c->ct.pyr_march;
       if (!fuse_r0 && detect) {
          const dim3 grid((g.cols + 255) / 256, g.rows, B);
          hipLaunchKernelGGL(k_hess, grid, dim3(256), 0, st, Lo[0], Ro[0], sc.norm2[0]);
@@ -1018,10 +896,10 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
       for (int i = 1; i <= 4 && !detect; i++) {
          // the blurs alone: L1, L2, and - when an octave follows - its first level, the decimated L3 (which itself is not kept)
          if (i == 4 || (i == 3 && !has_next)) break;
-         const float *taps = ptaps + c->pyr_tap_off[i];
+         const float *taps = ptaps + c->ct.pyr_tap_off[i];
          const int tb = tm.begin(T_BLURHESS, (i == 3 ? 5.0 : 8.0) * (double)B * g.rows * g.cols);
-         if (i < 3) launch_blur_hess<true, false, false>(c, Lo[i - 1], Lo[i], none, none, taps, c->pyr_K[i], 0.0f, B);
-         else launch_blur_hess<false, false, true>(c, Lo[2], none, none, c->L[(o + 1) * 3], taps, c->pyr_K[i], 0.0f, B);
+         if (i < 3) launch_blur_hess<true, false, false>(c, Lo[i - 1], Lo[i], none, none, taps, c->ct.pyr_K[i], 0.0f, B);
+         else launch_blur_hess<false, false, true>(c, Lo[2], none, none, c->L[(o + 1) * 3], taps, c->ct.pyr_K[i], 0.0f, B);
          tm.end(tb);
       }
       for (int i = 1; i <= 4 && detect; i++) {
@@ -1030,8 +908,8 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
          double bytes = 12.0 * (double)B * g.rows * g.cols;
          if (i == 1 && fuse_r0) bytes += 8.0 * (double)B * g.rows * g.cols;
          if (i == 3 && has_next) bytes += 2.0 * (double)B * g.rows * g.cols;
-         const float *taps = ptaps + c->pyr_tap_off[i];
-         const int K = c->pyr_K[i];
+         const float *taps = ptaps + c->ct.pyr_tap_off[i];
+         const int K = c->ct.pyr_K[i];
          const int tb = tm.begin(T_BLURHESS, bytes);
          if (i == 1 && fuse_r0) launch_march<9, true, true, false, true>(c, Lo[0], Lo[1], Ro[1], none, taps, sc.norm2[1], B, Ro[0], sc.norm2[0]);
          else if (i < 3) launch_blur_hess<true, true, false>(c, Lo[i - 1], Lo[i], Ro[i], none, taps, K, sc.norm2[i], B);
@@ -1063,13 +941,13 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
       HIP_TRY(hipMemcpyAsync(&cnt->oct_rec_start[o], &cnt->head.rec, 4, hipMemcpyDeviceToDevice, st));
       OctaveCtx oc;
       for (int l = 0; l < 5; l++) { oc.R[l] = Ro[l]; oc.L[l] = Lo[l]; oc.sigma[l] = sc.level_sigma[l]; }
-      oc.pixelDistance = c->consts.pd0 * (float)(1 << o);   // pyramid.cpp:288: doubles per octave
+      oc.pixelDistance = c->ct.consts.pd0 * (float)(1 << o);   // pyramid.cpp:288: doubles per octave
       oc.octave = (int)o;
       oc.map = c->geo.b_map.as<uint32_t>();
       // a fresh epoch for this pass (counting down; the all-ones epoch is the fill value): refill when they have run out
-      if (c->map_epoch == 0) { HIP_TRY(hipMemsetAsync(c->geo.b_map.p, 0xFF, c->geo.b_map.bytes, st)); c->map_epoch = c->map_kbits < 32 ? (0xffffffffu >> c->map_kbits) : 0u; }
-      if (c->map_epoch > 0) c->map_epoch--;
-      oc.map_epoch = c->map_kbits < 32 ? (c->map_epoch << c->map_kbits) : 0u;
+      const OrderMapEpochs::Pass pass = c->map_epochs.next_pass();
+      if (pass.refill_first) HIP_TRY(hipMemsetAsync(c->geo.b_map.p, 0xFF, c->geo.b_map.bytes, st));
+      oc.map_epoch = pass.epoch_bits;
       oc.word_base = g.word_base;
       oc.words_per_image = c->words_per_image;
       oc.words_per_row = g.words_per_row;
@@ -1080,9 +958,9 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
          const int band = extrema_band(g.rows, g.cols, B);
          const dim3 grid(strips, (g.rows + band - 1) / band, B);
          const int te = tm.begin(T_EXTREMA, 20.0 * (double)B * g.rows * g.cols);
-         hipLaunchKernelGGL(k_extrema_march, grid, dim3(64), 0, st, fp, c->consts.positiveThreshold, c->consts.negativeThreshold, s.cl, band);
+         hipLaunchKernelGGL(k_extrema_march, grid, dim3(64), 0, st, fp, c->ct.consts.positiveThreshold, c->ct.consts.negativeThreshold, s.cl, band);
          tm.end(te);
-         hipLaunchKernelGGL(k_localize, dim3(HS_GRID_LOC), dim3(256), 0, st, oc, s.cl, s.rl, c->consts);
+         hipLaunchKernelGGL(k_localize, dim3(HS_GRID_LOC), dim3(256), 0, st, oc, s.cl, s.rl, c->ct.consts);
          hipLaunchKernelGGL(k_dedupe, dim3(HS_GRID_DED), dim3(256), 0, st, oc, s.rl, (const uint32_t *)&cnt->oct_rec_start[o],
                             c->geo.b_bitmask.as<unsigned long long>());
       }
@@ -1147,10 +1025,10 @@ void collect_timings(hesaff_ctx *c, StageTimer &tm, int B)
 void launch_sift(hesaff_ctx *c, hipStream_t ss, const SiftIO &so, uint32_t n, float2 *vo)
 {
    const uint32_t nb64 = (n + 63) / 64;
-   hipLaunchKernelGGL(k_sift_meanvar, dim3((n + SM_KP - 1) / SM_KP), dim3(64), 0, ss, so, c->tables);
-   hipLaunchKernelGGL(k_sift_grad, dim3(std::min(n, c->sgrad_grid)), dim3(256), 0, ss, so, c->tables, vo);
-   hipLaunchKernelGGL(k_sift_hist, dim3(std::min<uint32_t>((n + 3) / 4, c->g_shist)), dim3(64), 0, ss, so, c->tables, (const float2 *)vo);
-   hipLaunchKernelGGL(k_sift_quantize, dim3(nb64), dim3(64), 0, ss, so, c->consts);
+   hipLaunchKernelGGL(k_sift_meanvar, dim3((n + SM_KP - 1) / SM_KP), dim3(64), 0, ss, so, c->tables.view);
+   hipLaunchKernelGGL(k_sift_grad, dim3(std::min(n, c->sgrad_grid)), dim3(256), 0, ss, so, c->tables.view, vo);
+   hipLaunchKernelGGL(k_sift_hist, dim3(std::min<uint32_t>((n + 3) / 4, c->g_shist)), dim3(64), 0, ss, so, c->tables.view, (const float2 *)vo);
+   hipLaunchKernelGGL(k_sift_quantize, dim3(nb64), dim3(64), 0, ss, so, c->ct.consts);
 }
 
 // per-group patch / descriptor buffers: sized once per batch for the largest group
@@ -1166,14 +1044,14 @@ void ensure_group_buffers(hesaff_ctx *c, uint32_t n)
    const void *before = c->b_siftvo2.p;
    const size_t bytes_before = c->b_siftvo2.bytes;
    c->b_siftvo2.ensure_grow((size_t)n * HS_VO_PITCH * 8 + 64);
-   if (c->b_siftvo2.p != before || c->b_siftvo2.bytes != bytes_before) HIP_TRY(hipMemsetAsync(c->b_siftvo2.p, 0, c->b_siftvo2.bytes, c->stream));
+   if (c->b_siftvo2.p != before || c->b_siftvo2.bytes != bytes_before) HIP_TRY(hipMemsetAsync(c->b_siftvo2.p, 0, c->b_siftvo2.bytes, c->stream()));
 }
 
 // The host round trip of a batch: the per-image Hessian starts and the large-window row bounds (all of b_starts: StartsBlock::words_to_copy)
 // into pinned memory; the caller's thread sleeps until everything before it on the main stream has run.
 const int32_t *fetch_hessian_starts(hesaff_ctx *c, int B)
 {
-   hipStream_t st = c->stream;
+   hipStream_t st = c->stream();
    const size_t bytes = starts_block(c->geo.b_starts.as<int32_t>(), B).words_to_copy() * 4;
    int32_t *hs = (int32_t *)c->h_small_mid.ensure_small(bytes);
    HIP_TRY(hipMemcpyAsync(hs, c->geo.b_starts.p, bytes, hipMemcpyDeviceToHost, st));
@@ -1198,7 +1076,7 @@ struct BatchResult {
 // which the caller has recorded after the last kernel that writes a plane k_affine reads.
 BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, int tt, int B, int H, int W, const int32_t *hs, bool with_affine)
 {
-   hipStream_t st = c->stream;
+   hipStream_t st = c->stream();
    CounterBlock *cnt = s.counters;
    int t;
    PlaneTab pt;
@@ -1219,16 +1097,16 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
       while (c->ev_aff.size() < groups.size()) c->ev_aff.emplace_back(hipEventDisableTiming);
       if (gp.max_n) ensure_group_buffers(c, gp.max_n);
       // Software pipeline over image groups, one stream per stage:
-      //   affine shape of group g+1 (aff_stream)  |  patch extraction of group g (main + side
-      //   streams, latency-bound)  |  descriptor kernels of the groups before (sift_stream).
+      //   affine shape of group g+1 (sset.affine())  |  patch extraction of group g (main + side
+      //   streams, latency-bound)  |  descriptor kernels of the groups before (sset.sift()).
       // Three patch buffer slots rotate.
-      hipStream_t as = c->no_overlap ? st : c->aff_stream;
+      hipStream_t as = c->no_overlap ? st : c->sset.affine();
       if (as != st && with_affine) HIP_TRY(hipStreamWaitEvent(as, c->ev_detect_done, 0));
       auto launch_affine = [&](size_t gi) {
          if (!with_affine) return;
          const int ta = tm.begin(T_AFF, 0, as);
          const uint32_t agrid = std::min<uint32_t>((groups[gi].hi - groups[gi].lo + HS_AFFP_G - 1) / HS_AFFP_G, (uint32_t)c->n_cu * HS_AFF_BLOCKS_PER_CU);
-         hipLaunchKernelGGL(k_affine, dim3(agrid), dim3(64), 0, as, pt, s.hl, groups[gi].lo, groups[gi].hi, (const uint32_t *)&cnt->head.hess_total, c->tables, c->consts, s.ao);
+         hipLaunchKernelGGL(k_affine, dim3(agrid), dim3(64), 0, as, pt, s.hl, groups[gi].lo, groups[gi].hi, (const uint32_t *)&cnt->head.hess_total, c->tables.view, c->ct.consts, s.ao);
          tm.end(ta);
          if (as != st) HIP_TRY(hipEventRecord(c->ev_aff[gi], as));
       };
@@ -1244,12 +1122,12 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
          HIP_TRY(hipMemsetAsync(cnt->bin_count, 0, CounterBlock::bins_bytes(), st));   // bin counts and work counters
          // (the group's end travels as a kernel argument: a 4-byte copy from pageable memory would make the host wait
          //  here until the stream has drained, once per group)
-         hipLaunchKernelGGL(k_prepare_patch, dim3(1024), dim3(256), 0, st, s.hl, h_lo, h_hi, (const uint32_t *)&cnt->head.hess_total, s.ao, H, W, c->consts,
-                            c->tables, s.pw);
+         hipLaunchKernelGGL(k_prepare_patch, dim3(1024), dim3(256), 0, st, s.hl, h_lo, h_hi, (const uint32_t *)&cnt->head.hess_total, s.ao, H, W, c->ct.consts,
+                            c->tables.view, s.pw);
          run_patch_stage(c, s, c->gray, c->b_patches2[slot].as<float>(), h_lo, groups[gi].large_rows, &pt);
          tm.end(t);
          HIP_TRY(hipEventRecord(c->ev_extract_done[slot], st));
-         hipStream_t ss = c->no_overlap ? st : c->sift_stream;
+         hipStream_t ss = c->no_overlap ? st : c->sset.sift();
          if (ss != st) HIP_TRY(hipStreamWaitEvent(ss, c->ev_extract_done[slot], 0));
          SiftIO so;
          so.patches = c->b_patches2[slot].as<float>(); so.alive = s.pw.alive; so.meanvar = c->b_meanvar2.as<float>();
@@ -1323,7 +1201,7 @@ BatchResult run_describe(hesaff_ctx *c, const SrcImages &src, int B, int H, int 
    c->ev_used = 0;
    StageTimer tm(c);
    Lists s = make_lists(c);
-   hipStream_t st = c->stream;
+   hipStream_t st = c->stream();
    CounterBlock *cnt = s.counters;
    const bool shapes = from == HESAFF_FROM_SHAPES;
    const int tt = tm.begin(T_TOTAL);
@@ -1355,7 +1233,7 @@ unsigned long long export_text_prepare(hesaff_ctx *c, const KeyRec *keys, uint32
 {
    img_off.assign((size_t)B + 1, 0ull);
    if (n == 0) return 0ull;
-   hipStream_t st = c->stream;
+   hipStream_t st = c->stream();
    const uint32_t nblk = (n + EX_ROWS - 1) / EX_ROWS;
    c->b_ex_len.ensure_grow(((size_t)n + 64) * 2);
    c->b_ex_sums.ensure_grow((size_t)nblk * 4);
@@ -1379,7 +1257,7 @@ unsigned long long export_text_prepare(hesaff_ctx *c, const KeyRec *keys, uint32
 void export_text_write(hesaff_ctx *c, const KeyRec *keys, uint32_t n, char *d_text)
 {
    if (n == 0) return;
-   hipLaunchKernelGGL(k_text_write, dim3((n + EX_ROWS - 1) / EX_ROWS), dim3(EX_ROWS), 0, c->stream, keys, n, c->par.mrSize, (const uint16_t *)c->b_ex_len.p,
+   hipLaunchKernelGGL(k_text_write, dim3((n + EX_ROWS - 1) / EX_ROWS), dim3(EX_ROWS), 0, c->stream(), keys, n, c->par.mrSize, (const uint16_t *)c->b_ex_len.p,
                       (const unsigned long long *)c->b_ex_off.p, d_text);
 }
 
@@ -1427,7 +1305,7 @@ void jpeg_pixels(hesaff_ctx *c, const uint8_t *d_blobs, const JpegGeom &g, int B
 void export_bin_rows(hesaff_ctx *c, const KeyRec *keys, uint32_t n, char *d_bin)
 {
    if (n == 0) return;
-   hipLaunchKernelGGL(k_bin_rows, dim3(std::min<uint32_t>((n + 7) / 8, 4096u)), dim3(256), 0, c->stream, keys, n, c->par.mrSize, (uint32_t *)d_bin);
+   hipLaunchKernelGGL(k_bin_rows, dim3(std::min<uint32_t>((n + 7) / 8, 4096u)), dim3(256), 0, c->stream(), keys, n, c->par.mrSize, (uint32_t *)d_bin);
 }
 
 // hesaff_detect_regions: the n_hess hesaff_region records of the batch run_batch just finished into d_regions, on the main stream
@@ -1439,8 +1317,8 @@ void pack_regions(hesaff_ctx *c, uint32_t n_hess, int B, hesaff_region *d_region
    if (n_hess > c->cap) throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded; raise hesaff_params.max_kpts_per_mpx");
    const Lists s = make_lists(c);
    RegionTab tab;
-   for (int o = 0; o < HS_MAX_OCTAVES; o++) tab.pd[o] = c->consts.pd0 * (float)(1 << o);   // pyramid.cpp:288, as run_detection hands it on
-   hipLaunchKernelGGL(k_pack_regions, dim3(std::min<uint32_t>((n_hess + 255) / 256, 4096u)), dim3(256), 0, c->stream, s.hl, n_hess, s.ao, s.pw,
+   for (int o = 0; o < HS_MAX_OCTAVES; o++) tab.pd[o] = c->ct.consts.pd0 * (float)(1 << o);   // pyramid.cpp:288, as run_detection hands it on
+   hipLaunchKernelGGL(k_pack_regions, dim3(std::min<uint32_t>((n_hess + 255) / 256, 4096u)), dim3(256), 0, c->stream(), s.hl, n_hess, s.ao, s.pw,
                       (const uint32_t *)c->geo.b_rank.p, (const int32_t *)starts_block(c->geo.b_starts.as<int32_t>(), B).desc(), tab, (uint4 *)d_regions);
 }
 

@@ -174,7 +174,7 @@ static void check_groups()
 //  * hs_row_stream / 2 / 3 store the P samples of a row at srow[r .. r + P), r = K / 2 replicated samples on either side
 //    (srow[0 .. r) and srow[r + P .. r + P + r)), and read srow[x0 + jt + 1] for x0 <= P - 2, jt < K, i.e. up to index P + 2 r - 1:
 //    a row needs P + 2 (K / 2) floats;
-//  * K = tb.patch_tap_k[(P0 - 1) / 2], P0 = P - 2: gauss_ksize(1.5f * P0 / 41) (ensure_patch_taps); the tap area holds K floats at most.
+//  * K = tb.patch_tap_k[(P0 - 1) / 2], P0 = P - 2: gauss_ksize(1.5f * P0 / 41) (build_patch_taps, context_tables.h); the tap area holds K floats at most.
 static void check_large_launch(int max_p0, int P, int batch_max_p, size_t optin)
 {
    const LargeSplit sp = large_rows_split(max_p0, batch_max_p);

@@ -1056,7 +1056,9 @@ int hesaff_stage_normalize_affine(hesaff_ctx *c, const float *img, int rows, int
    HS_API_END(c)
 }
 
-int hesaff_stage_sift(hesaff_ctx *c, int n, const float *patches, uint8_t *desc)
+// hesaff_stage_sift and hesaff_stage_sift_parts: the production descriptor kernels on caller-supplied patches; meanvar / hist
+// (either may be null) additionally receive what k_sift_meanvar and k_sift_hist left in the stage buffer
+static int stage_sift(hesaff_ctx *c, int n, const float *patches, float *meanvar, float *hist, uint8_t *desc)
 {
    if (!c || !patches || !desc || n < 0) return HESAFF_ERR_ARG;
    HS_API_BEGIN
@@ -1076,9 +1078,19 @@ int hesaff_stage_sift(hesaff_ctx *c, int n, const float *patches, uint8_t *desc)
    so.patches = (const float *)base; so.alive = (const int32_t *)(base + off_alive); so.meanvar = (float *)(base + off_mv);
    so.vec = (float *)(base + off_vec); so.desc = (uint8_t *)(base + off_desc); so.h_lo = 0; so.h_hi = (uint32_t)n;
    launch_sift(c, c->stream(), so, (uint32_t)n, (float2 *)(base + off_vo));
+   if (meanvar) HIP_TRY(hipMemcpyAsync(meanvar, base + off_mv, N * 8, hipMemcpyDeviceToHost, c->stream()));
+   if (hist) HIP_TRY(hipMemcpyAsync(hist, base + off_vec, N * 128 * 4, hipMemcpyDeviceToHost, c->stream()));
    HIP_TRY(hipMemcpyAsync(desc, base + off_desc, N * 128, hipMemcpyDeviceToHost, c->stream()));
    finish_stream(c);
    HS_API_END(c)
+}
+
+int hesaff_stage_sift(hesaff_ctx *c, int n, const float *patches, uint8_t *desc) { return stage_sift(c, n, patches, nullptr, nullptr, desc); }
+
+int hesaff_stage_sift_parts(hesaff_ctx *c, int n, const float *patches, float *meanvar, float *hist, uint8_t *desc)
+{
+   if (!meanvar || !hist) return HESAFF_ERR_ARG;
+   return stage_sift(c, n, patches, meanvar, hist, desc);
 }
 
 // exportKeypoints on the device for caller-supplied records: the kernels hesaff_process_files runs per chunk
@@ -1203,6 +1215,24 @@ int hesaff_stage_math_sift(hesaff_ctx *c, int n, const float *gy, const float *g
                       d + 2 * (size_t)n, d + 3 * (size_t)n, d + 4 * (size_t)n, d + 5 * (size_t)n);
    float *outs[4] = {ori_general, ori_nd, grad_general, grad_nd};
    for (int q = 0; q < 4; q++) HIP_TRY(hipMemcpyAsync(outs[q], d + (2 + q) * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream()));
+   finish_stream(c);
+   HS_API_END(c)
+}
+
+int hesaff_stage_math_sift_general(hesaff_ctx *c, int n, const float *gy, const float *gx, float *ori, float *grad, float *coord)
+{
+   if (!c || !gy || !gx || !ori || !grad || !coord || n < 0) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   bind_device(c);
+   if (n == 0) return HESAFF_OK;
+   c->b_stage.ensure((size_t)n * 20);
+   float *d = c->b_stage.as<float>();
+   HIP_TRY(hipMemcpyAsync(d, gy, (size_t)n * 4, hipMemcpyHostToDevice, c->stream()));
+   HIP_TRY(hipMemcpyAsync(d + n, gx, (size_t)n * 4, hipMemcpyHostToDevice, c->stream()));
+   hipLaunchKernelGGL(k_math_sift_general, dim3(std::min(4096, (n + 255) / 256)), dim3(256), 0, c->stream(), n, (const float *)d,
+                      (const float *)(d + n), d + 2 * (size_t)n, d + 3 * (size_t)n, d + 4 * (size_t)n);
+   float *outs[3] = {ori, grad, coord};
+   for (int q = 0; q < 3; q++) HIP_TRY(hipMemcpyAsync(outs[q], d + (2 + q) * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream()));
    finish_stream(c);
    HS_API_END(c)
 }

@@ -238,6 +238,26 @@ __global__ void k_math_sift(int n, const float *__restrict__ gy, const float *__
    }
 }
 
+// device check (stage API): the forms k_sift_grad takes for a FLAT patch (variance below 1e-4: raw pixels, operands of any finite
+// magnitude, denormals included), as it calls them: hm_atan2f_tab on the LDS table, sqrtf, hm_sift_orient_coord of the orientation
+__global__ void k_math_sift_general(int n, const float *__restrict__ gy, const float *__restrict__ gx, float *__restrict__ ori,
+                                    float *__restrict__ grad, float *__restrict__ coord)
+{
+   __shared__ float s_at[HM_ATAN_TAB_FLOATS];
+   {
+      const float at_init[HM_ATAN_TAB_FLOATS] = HM_ATAN_TAB_INIT;
+      if (threadIdx.x < HM_ATAN_TAB_FLOATS) s_at[threadIdx.x] = at_init[threadIdx.x];
+   }
+   __syncthreads();
+   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+      const float y = gy[i], x = gx[i];
+      const float o = hm_atan2f_tab(y, x, s_at);
+      ori[i] = o;
+      grad[i] = sqrtf(x * x + y * y);
+      coord[i] = hm_sift_orient_coord(o);
+   }
+}
+
 // k_sift_hist: samplePatch (siftdesc.cpp:51-81).  A wavefront takes FOUR keypoints; lane =
 // (keypoint, spatial cell) owns the cell's 8 orientation bins as 8 LDS words laid out
 // [bin][lane] (a lane only ever touches its own bank) and walks the cell's 16x16 pixel support

@@ -489,6 +489,13 @@ int hesaff_stage_normalize_affine(hesaff_ctx *ctx, const float *img, int rows, i
 /* SIFTDescriptor::computeSiftDescriptor siftdesc.cpp:115-140 for n 41x41 patches;
  * desc[n][128] = the values of `vec` cast as at hesaff.cpp:91. */
 int hesaff_stage_sift(hesaff_ctx *ctx, int n, const float *patches, uint8_t *desc);
+/* the same launch, additionally returning what the descriptor kernels hand to each other: meanvar[n][2] = the mean and `var` of
+ * photometricallyNormalize (helpers.cpp:253-268), hist[n][128] = `vec` before the first normalizeVec (siftdesc.cpp:98).  A one-ulp
+ * error in either almost never moves a descriptor byte; tests compare them as bits.
+ * Patch domain of the descriptor kernels (both entry points): every value finite with |v| <= 2^20, the bound of the _f32 entry points'
+ * pixels, which normalizeAffine's interpolation and smoothing do not exceed.  Within it a patch may be flat (var < 1e-4: it keeps its raw
+ * pixels, gradients down to denormals and 0) or constant.  Infinities, NaN and larger magnitudes are outside the domain. */
+int hesaff_stage_sift_parts(hesaff_ctx *ctx, int n, const float *patches, float *meanvar, float *hist, uint8_t *desc);
 /* exportKeypoints hesaff.cpp:107-130 on the device for n records in host memory (what hesaff_process_files runs per chunk):
  * format = HESAFF_OUT_TEXT: the bytes of the .hesaff.sift file, == hesaff_format_sift; HESAFF_OUT_BIN: the bytes of the sidecar,
  * == hesaff_write_bin's file.  *out is malloc'ed (hesaff_free). */
@@ -506,6 +513,10 @@ int hesaff_stage_math(hesaff_ctx *ctx, int n, const float *a, const float *b, fl
  * photometrically normalised patches (operands zero or normal); for testing that the two agree bit for bit */
 int hesaff_stage_math_sift(hesaff_ctx *ctx, int n, const float *gy, const float *gx, float *ori_general, float *ori_nd,
                            float *grad_general, float *grad_nd);
+/* the forms the descriptor's gradient kernel takes for a flat patch (raw pixels: finite operands of any magnitude, denormals and zeros
+ * included; no infinities or NaN), as the kernel calls them: ori = atan2f(gy, gx) in the table-driven general form, grad =
+ * sqrt(gx^2 + gy^2), coord = the orientation coordinate 8 (ori + 2 pi) / (2 pi) of siftdesc.cpp:65 */
+int hesaff_stage_math_sift_general(hesaff_ctx *ctx, int n, const float *gy, const float *gx, float *ori, float *grad, float *coord);
 
 /* Host-side tables the kernels use (for known-answer tests): computeGaussMask
  * helpers.cpp:104, computeCircularGaussMask helpers.cpp:131, precomputeBinsAndWeights

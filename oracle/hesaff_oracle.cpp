@@ -549,6 +549,67 @@ struct Oracle {
          vec[i] = float(b);
       }
    }
+   // The intermediate values of computeSiftDescriptor for one patch (test hook; computeSiftDescriptor above is left as
+   // it is and tests/test_stage_edges.py holds the two to the same final vector): meanvar = the `sum` (mean) and `var` of
+   // photometricallyNormalize (helpers.cpp:253-268), hist = vec before the first normalizeVec (siftdesc.cpp:98), vec =
+   // the final values.  The patch is modified in place like the reference's.
+   void siftParts(float *patch, float *meanvar /*2*/, float *hist /*128*/, float *vec /*128*/)
+   {
+      const int ps = par.patchSize, n = ps * ps;
+      {
+         float sum = 0, gsum = 0;
+         for (int i = 0; i < n; i++)
+            if (siftMask[i] > 0) { sum += patch[i]; gsum++; }
+         sum = sum / gsum;
+         float var = 0;
+         for (int i = 0; i < n; i++)
+            if (siftMask[i] > 0) var += (sum - patch[i]) * (sum - patch[i]);
+         var = sqrtf(var / gsum);
+         meanvar[0] = sum; meanvar[1] = var;
+      }
+      photometricallyNormalize(patch, siftMask.data(), ps);
+      std::vector<float> grad(n), ori(n);
+      for (int r = 0; r < ps; ++r)
+         for (int c = 0; c < ps; ++c) {
+            float gx, gy;
+            gradAt(patch, ps, r, c, gx, gy);
+            grad[r * ps + c] = sqrtf(gx * gx + gy * gy);
+            ori[r * ps + c] = atan2f(gy, gx);
+         }
+      const int nv = par.spatialBins * par.spatialBins * par.orientationBins;
+      for (int i = 0; i < nv; i++) vec[i] = 0;
+      for (int r = 0; r < ps; ++r) {
+         const int br0 = par.spatialBins * bin0[r]; const float wr0 = w0[r];
+         const int br1 = par.spatialBins * bin1[r]; const float wr1 = w1[r];
+         for (int c = 0; c < ps; ++c) {
+            float val = siftMask[r * ps + c] * grad[r * ps + c];
+            const int bc0 = bin0[c]; const float wc0 = w0[c] * val;
+            const int bc1 = bin1[c]; const float wc1 = w1[c] * val;
+            const float o = float(par.orientationBins) * (ori[r * ps + c] + 2 * M_PI) / (2 * M_PI);
+            int bo0 = (int)o;
+            const float wo1 = o - bo0;
+            bo0 %= par.orientationBins;
+            const int bo1 = (bo0 + 1) % par.orientationBins;
+            const float wo0 = 1.0f - wo1;
+            val = wr0 * wc0; if (val > 0) { vec[br0 + bc0 + bo0] += val * wo0; vec[br0 + bc0 + bo1] += val * wo1; }
+            val = wr0 * wc1; if (val > 0) { vec[br0 + bc1 + bo0] += val * wo0; vec[br0 + bc1 + bo1] += val * wo1; }
+            val = wr1 * wc0; if (val > 0) { vec[br1 + bc0 + bo0] += val * wo0; vec[br1 + bc0 + bo1] += val * wo1; }
+            val = wr1 * wc1; if (val > 0) { vec[br1 + bc1 + bo0] += val * wo0; vec[br1 + bc1 + bo1] += val * wo1; }
+         }
+      }
+      for (int i = 0; i < nv; i++) hist[i] = vec[i];
+      normalizeVec(vec, nv);
+      bool changed = false;
+      for (int i = 0; i < nv; i++)
+         if (vec[i] > par.maxBinValue) { vec[i] = par.maxBinValue; changed = true; }
+      if (changed) normalizeVec(vec, nv);
+      for (int i = 0; i < nv; i++) {
+         const float q = 512.0f * vec[i];
+         int b = (q == q) ? (int)q : 0;
+         if (b > 255) b = 255;
+         vec[i] = float(b);
+      }
+   }
    // siftdesc.cpp:83-96
    static void normalizeVec(float *vec, int n)
    {
@@ -939,6 +1000,7 @@ int ho_h_normalize_affine(void *h, const float *img, int rows, int cols, float x
    return ((Oracle *)h)->normalizeAffine(p, x, y, s, A[0], A[1], A[2], A[3], patch) ? 1 : 0;
 }
 void ho_h_sift(void *h, float *patch, float *vec) { ((Oracle *)h)->computeSiftDescriptor(patch, vec); }
+void ho_h_sift_parts(void *h, float *patch, float *meanvar, float *hist, float *vec) { ((Oracle *)h)->siftParts(patch, meanvar, hist, vec); }
 void ho_destroy(void *h) { delete (Oracle *)h; }
 void ho_set_keep_planes(void *h, int keep) { ((Oracle *)h)->keepPlanes = keep != 0; }
 void ho_set_detect_only(void *h, int v) { ((Oracle *)h)->detectOnly = v != 0; }

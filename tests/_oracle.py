@@ -67,6 +67,7 @@ def lib():
     L.ho_h_normalize_affine.argtypes = [C.c_void_p, f32p, C.c_int, C.c_int] + [C.c_float] * 3 + [f32p, f32p]
     L.ho_h_normalize_affine.restype = C.c_int
     L.ho_h_sift.argtypes = [C.c_void_p, f32p, f32p]
+    L.ho_h_sift_parts.argtypes = [C.c_void_p, f32p, f32p, f32p, f32p]
     for n in ("ho_num_hessian", "ho_num_keys", "ho_num_octaves"):
         getattr(L, n).argtypes = [C.c_void_p]; getattr(L, n).restype = C.c_int
     L.ho_num_candidates.argtypes = [C.c_void_p]; L.ho_num_candidates.restype = C.c_long
@@ -127,6 +128,13 @@ class OracleHandle:
         vec = np.zeros(128, np.float32)
         lib().ho_h_sift(self.h, p, vec)
         return vec.astype(np.uint8)
+
+    def sift_parts(self, patch):
+        """-> meanvar[2] (mean and `var` of photometricallyNormalize), hist[128] (before normalizeVec), desc[128] u8."""
+        p = np.ascontiguousarray(patch, np.float32).reshape(-1).copy()
+        mv = np.zeros(2, np.float32); hist = np.zeros(128, np.float32); vec = np.zeros(128, np.float32)
+        lib().ho_h_sift_parts(self.h, p, mv, hist, vec)
+        return mv, hist, vec.astype(np.uint8)
 
 
 class OracleRun:

@@ -168,6 +168,8 @@ def load_library():
     L.hesaff_output_is_complete.argtypes = [C.c_char_p, C.c_int]
     L.hesaff_set_pinned_read_budget.argtypes = [vp, C.c_size_t, C.c_size_t]
     L.hesaff_set_pool_priority.argtypes = [vp, C.c_int]
+    L.hesaff_set_keypoint_limit.argtypes = [vp, C.c_int]
+    L.hesaff_get_keypoint_limit.argtypes = [vp, C.POINTER(C.c_int)]
     L.hesaff_stage_threads_for_pool.argtypes = [C.c_int]
     L.hesaff_detect_batch_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, _i32p, _i32p, C.POINTER(vp), C.POINTER(C.c_int64)]
     # float grey planes (CV_32FC1, pyramid.h:73): the twins above with float images
@@ -252,6 +254,7 @@ ABI_SYMBOLS = [
     "hesaff_stage_threads_for_pool", "hesaff_read_bmp", "hesaff_read_tiff", "hesaff_detect_regions", "hesaff_sizeof_region",
     "hesaff_detect_batch_f32", "hesaff_detect_batch_cb_f32", "hesaff_detect_regions_f32", "hesaff_detect_batch_device_f32",
     "hesaff_stage_pyramid_f32", "hesaff_describe_regions", "hesaff_describe_regions_f32",
+    "hesaff_set_keypoint_limit", "hesaff_get_keypoint_limit",
 ]
 
 # hesaff_describe_regions' `from`: which of the reference's two public callback members each record enters the chain through
@@ -630,6 +633,22 @@ class HesaffContext:
     def set_pool_priority(self, mode):
         """-1: the pool of process_files steps down (nice 10) when the host plan is CPU-starved (default); 0 never; 1 always"""
         self._check(self.L.hesaff_set_pool_priority(self.h, mode))
+
+    def set_keypoint_limit(self, n):
+        """hesaff_set_keypoint_limit: every detecting call keeps, per image, the n Hessian keypoints of greatest |response| (ties at
+        the cut to the earlier one), in the reference's order; 0 = no limit (default).  n bounds Hessian keypoints, not descriptors.
+        describe_regions* and the stage operators are not limited."""
+        self._check(self.L.hesaff_set_keypoint_limit(self.h, int(n)))
+
+    @property
+    def keypoint_limit(self):
+        n = C.c_int()
+        self._check(self.L.hesaff_get_keypoint_limit(self.h, C.byref(n)))
+        return n.value
+
+    @keypoint_limit.setter
+    def keypoint_limit(self, n):
+        self.set_keypoint_limit(n)
 
     def process_files(self, paths, out_paths=None, decode_threads=0, write_threads=0):
         """hesaff_process_files: image files -> <name>.hesaff.sift through the decode / device / write pipeline.

@@ -116,7 +116,7 @@ struct CounterHead {
    uint32_t overflow;       // a candidate or a record did not fit
    uint32_t hess_total;     // Hessian keypoints of the batch
    uint32_t desc_total;     // descriptors of the batch
-   uint32_t pad5;           // unused (once the end of the current image group, which now travels as a kernel argument)
+   uint32_t hess_detected;  // with a keypoint limit: the Hessian keypoints detection found, hess_total being those kept (0 otherwise)
    uint32_t row_overflow;   // the T' rows of the large windows exceeded their buffer (k_patch_large_rows)
    uint32_t pad7;
 };

@@ -776,6 +776,20 @@ int hesaff_set_pool_priority(hesaff_ctx *c, int mode)
    return HESAFF_OK;
 }
 
+int hesaff_set_keypoint_limit(hesaff_ctx *c, int n)
+{
+   if (!c || n < 0) return HESAFF_ERR_ARG;
+   c->keypoint_limit = n;
+   return HESAFF_OK;
+}
+
+int hesaff_get_keypoint_limit(const hesaff_ctx *c, int *n)
+{
+   if (!c || !n) return HESAFF_ERR_ARG;
+   *n = c->keypoint_limit;
+   return HESAFF_OK;
+}
+
 int hesaff_process_files(hesaff_ctx *c, int n, const char *const *paths, const char *const *out_paths, int decode_threads,
                          int write_threads, hesaff_file_status *status)
 {

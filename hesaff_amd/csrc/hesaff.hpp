@@ -100,6 +100,16 @@ struct AffineHessianDetector {
    void setHessianKeypointCallback(HessianKeypointCallback *callback) { hessianKeypointCallback_ = callback; }
    void setAffineShapeCallback(AffineShapeCallback *callback) { affineShapeCallback_ = callback; }
 
+   // No counterpart in the reference (hesaff_set_keypoint_limit, include/hesaff_amd.h): detectPyramidKeypoints keeps the n Hessian
+   // keypoints of greatest |response| (ties at the cut to the earlier one) and drops the rest on the device before findAffineShape;
+   // `keys`, the counters and the replayed callbacks then see only the kept keypoints, in the reference's order, each as the
+   // unlimited run produces it.  n bounds Hessian keypoints, not descriptors; 0 (default): no limit.  The batch forms below
+   // (onHessianKeypointsDetected, onAffineShapesFound) are not limited: their records are the caller's.
+   void setKeypointLimit(int n)
+   {
+      if (hesaff_set_keypoint_limit(ctx_, n) != HESAFF_OK) throw std::invalid_argument("keypoint limit must be 0 (off) or positive");
+   }
+
    // == grey conversion hesaff.cpp:138-148 + detectPyramidKeypoints hesaff.cpp:167 with the
    // whole callback chain; image is what cv::imread would deliver (8-bit, 1 or 3 channels).
    void detectPyramidKeypoints(const uint8_t *image, int width, int height, int channels)

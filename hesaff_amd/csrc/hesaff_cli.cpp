@@ -23,6 +23,9 @@
 //       the text path then writes 217 instead of 181 images/s (profiles/r06_notes.md).  --runtime-nice 0 leaves them alone, --runtime-nice 1 forces it.
 //       --output text | bin | both    what every image gets: <image>.hesaff.sift (default), the binary sidecar
 //       <image>.hesaff.bin (the same rows unprinted, include/hesaff_amd.h: hesaff_write_bin), or both.
+//       --max-keypoints N             a keypoint budget per image (hesaff_set_keypoint_limit): the N Hessian keypoints of greatest |response|
+//                                     are kept, in the reference's order, the rest dropped on the device before findAffineShape; N bounds the
+//                                     "keypoints" count, the "affine shapes" are fewer.  Default 0 = no limit.  Batch form only.
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -95,7 +98,8 @@ bool parse_devices(const char *spec, std::vector<int> &out)
 
 // hesaff --batch: the list is cut into contiguous shards, one per device context (hesaff_shard_range); every shard runs
 // through hesaff_process_files - decode threads -> device -> writer threads, bounded memory - on its own host thread.
-int run_batch_mode(const char *list_path, const char *devices_spec, int out_format, bool dynamic, int fast, int resume, int host_share, int runtime_nice)
+int run_batch_mode(const char *list_path, const char *devices_spec, int out_format, bool dynamic, int fast, int resume, int host_share, int runtime_nice,
+                   int max_keypoints)
 {
    std::ifstream lf(list_path);
    if (!lf) { fprintf(stderr, "hesaff: cannot read list '%s'\n", list_path); return 1; }
@@ -145,6 +149,7 @@ int run_batch_mode(const char *list_path, const char *devices_spec, int out_form
       if (hesaff_create(&ctx, &par, devices[(size_t)rank]) != HESAFF_OK) { errs[(size_t)rank] = hesaff_last_error(nullptr); return; }
       hesaff_set_output_format(ctx, out_format);
       hesaff_set_resume(ctx, resume);
+      hesaff_set_keypoint_limit(ctx, max_keypoints);
       hesaff_host_plan hp;   // this device's share of the host: the library's one rule (include/hesaff_amd.h)
       hesaff_host_plan_for(world * host_share, &hp);
       const int wt = hp.write_threads, dt = hp.decode_threads;
@@ -222,7 +227,7 @@ int main(int argc, char **argv)
    for (int i = 1; i < argc; i++) batch = batch || strcmp(argv[i], "--batch") == 0;
    if (batch) {
       const char *devices = nullptr, *list = nullptr;
-      int out_format = HESAFF_OUT_TEXT, fast = 0, host_share = 1, runtime_nice = -1;
+      int out_format = HESAFF_OUT_TEXT, fast = 0, host_share = 1, runtime_nice = -1, max_keypoints = 0;
       bool bad = false, dynamic = false;
       int resume = 0;
       for (int i = 1; i < argc && !bad; i += 2) {
@@ -233,7 +238,13 @@ int main(int argc, char **argv)
          else if (strcmp(argv[i], "--devices") == 0) devices = argv[i + 1];
          else if (strcmp(argv[i], "--host-share") == 0) { host_share = atoi(argv[i + 1]); bad = host_share < 1 || host_share > 1024; }
          else if (strcmp(argv[i], "--runtime-nice") == 0) { runtime_nice = atoi(argv[i + 1]); bad = runtime_nice < 0 || runtime_nice > 1; }
-         else if (strcmp(argv[i], "--fast") == 0) {
+         else if (strcmp(argv[i], "--max-keypoints") == 0) {
+            // digits only: "-1", "x", "" and "12x" are refused, as is anything beyond int
+            char *end = nullptr;
+            const long v = strtol(argv[i + 1], &end, 10);
+            if (argv[i + 1][0] < '0' || argv[i + 1][0] > '9' || *end != 0 || v > 0x7fffffffL) bad = true;
+            else max_keypoints = (int)v;
+         } else if (strcmp(argv[i], "--fast") == 0) {
             if (strcmp(argv[i + 1], "0") == 0 || strcmp(argv[i + 1], "2") == 0) fast = atoi(argv[i + 1]);
             else bad = true;
          } else if (strcmp(argv[i], "--schedule") == 0) {
@@ -246,8 +257,8 @@ int main(int argc, char **argv)
             else bad = true;
          } else bad = true;
       }
-      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1]\n"); return 1; }
-      return run_batch_mode(list, devices, out_format, dynamic, fast, resume, host_share, runtime_nice);
+      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1] [--max-keypoints N]\n"); return 1; }
+      return run_batch_mode(list, devices, out_format, dynamic, fast, resume, host_share, runtime_nice, max_keypoints);
    }
    if (argc > 1) {
       uint8_t *data = nullptr;

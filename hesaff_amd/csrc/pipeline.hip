@@ -33,6 +33,7 @@
 #include "../../include/hesaff_amd.h"
 #include "host_tables.h"
 #include "kernels_keypoint.h"
+#include "kernels_select.h"
 #include "kernels_patch.h"
 #include "kernels_sift.h"
 #include "kernels_pyramid.h"
@@ -419,6 +420,7 @@ struct hesaff_ctx {
    int out_format = HESAFF_OUT_TEXT;   // hesaff_set_output_format
    int resume = 0;                     // hesaff_set_resume: 0 off, 1 skip complete outputs (O(1) test), 2 strict (rows counted)
    int pool_priority = -1;             // hesaff_set_pool_priority: -1 lower the pool's priority when the plan is CPU-starved, 0 never, 1 always
+   int keypoint_limit = 0;             // hesaff_set_keypoint_limit: 0 no limit, N >= 1 the N strongest Hessian keypoints of every image (run_batch)
    int stage_threads = 4;              // host threads that copy a chunk's pixels into pinned memory (hesaff_process_files: within its thread budget)
    DevEvent ev_detect_done, ev_batch_done;   // blocking-sync events: the host sleeps instead of spinning
    std::vector<DevEvent> ev_aff;             // one per image group, grown on demand
@@ -1174,6 +1176,28 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
    return {h.hess(), h.desc(), d_starts.desc()};
 }
 
+// hesaff_set_keypoint_limit (kernels_select.h): of the ordered Hessian list run_detection left, every image keeps its keypoint_limit
+// strongest keypoints, in their order, and the list, its length, the per-image starts and the large-window row bounds become those of
+// the kept keypoints - everything behind sees a shorter list.  Only run_batch calls it: the stage operators and run_describe, which
+// share run_detection, are not limited.  The ranks live in b_rank (free until the pack stage's scan), the ordered items are still in
+// b_cand, the length detection found stays in the counter block: no buffer of its own, nothing allocated.
+void select_strongest(hesaff_ctx *c, const Lists &s, StageTimer &tm, int B)
+{
+   hipStream_t st = c->stream();
+   CounterBlock *cnt = s.counters;
+   const uint32_t limit = (uint32_t)c->keypoint_limit;
+   int32_t *starts = starts_block(c->geo.b_starts.as<int32_t>(), B).hess();
+   uint32_t *keep_rank = c->geo.b_rank.as<uint32_t>();
+   const int t = tm.begin(T_DET);
+   hipLaunchKernelGGL(k_select_image, dim3(B), dim3(HS_SEL_THREADS), 0, st, (const float *)s.hl.response, (const int32_t *)starts,
+                      (const uint32_t *)&cnt->head.hess_total, s.hl.cap, limit, keep_rank);
+   hipLaunchKernelGGL(k_select_starts, dim3(1), dim3(256), 0, st, starts, B, limit, s.hl.cap, &cnt->head.hess_total, &cnt->head.hess_detected);
+   hipLaunchKernelGGL(k_hess_deal_kept, dim3(HS_GRID_SCAT), dim3(256), 0, st, (const HessItem *)c->geo.b_cand.p, (const uint32_t *)&cnt->head.hess_detected,
+                      (const uint32_t *)keep_rank, (const int32_t *)starts, s.hl);
+   launch_image_large_rows(c, s, B);   // the bounds form_groups reads describe the kept keypoints
+   tm.end(t);
+}
+
 // Whole hot path on a device-resident batch.  Leaves ordered KeyRec records in b_out and
 // per-image start offsets (b_starts: StartsBlock::hess() and desc(); BatchResult: their host copies).
 BatchResult run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
@@ -1184,6 +1208,7 @@ BatchResult run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
    Lists s = make_lists(c);
    const int tt = tm.begin(T_TOTAL);
    run_detection(c, src, B, s, tm, false, nullptr);
+   if (c->keypoint_limit > 0) select_strongest(c, s, tm, B);
    // the one host round trip of a batch
    return run_keypoint_stages(c, s, tm, tt, B, H, W, fetch_hessian_starts(c, B), true);
 }

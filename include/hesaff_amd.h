@@ -40,7 +40,8 @@ extern "C" {
  *    Version 8 also carries the float-input entry points (hesaff_detect_batch_f32, hesaff_detect_batch_cb_f32, hesaff_detect_regions_f32,
  *    hesaff_detect_batch_device_f32, hesaff_stage_pyramid_f32): they add no struct and change none, so the version stays; a caller that
  *    needs them finds them by symbol (dlsym) in the library it loaded.  The same holds for hesaff_describe_regions and
- *    hesaff_describe_regions_f32 (HESAFF_FROM_POINTS / HESAFF_FROM_SHAPES): new symbols over the structs of version 8.
+ *    hesaff_describe_regions_f32 (HESAFF_FROM_POINTS / HESAFF_FROM_SHAPES): new symbols over the structs of version 8.  And for
+ *    hesaff_set_keypoint_limit / hesaff_get_keypoint_limit: two more symbols, no struct touched, the version stays 8.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -321,6 +322,31 @@ int hesaff_describe_regions(hesaff_ctx *ctx, int n, const uint8_t *const *images
 int hesaff_describe_regions_f32(hesaff_ctx *ctx, int n, const float *const *images, const int *widths, const int *heights,
                                 const int *strides, const hesaff_region *const *regions, const int *counts, int from,
                                 hesaff_region_result *results);
+
+/* ---- a keypoint budget per image: the N strongest Hessian keypoints, chosen on the device ----
+ * No counterpart in the reference, whose caller would filter inside HessianKeypointCallback::onHessianKeypointDetected (pyramid.h:43-47)
+ * - once the whole list is known, so in a second pass - before findAffineShape.  Here the context holds keypoint_limit, an int:
+ * 0, the default, means no limit, and everything is bit for bit what it is without this call.  With limit N >= 1, for each image the N
+ * Hessian keypoints of greatest strength are kept; the rest are discarded before findAffineShape and cost nothing after detection.
+ * Strength of keypoint i is |response_i|, the float `response` of onHessianKeypointDetected (saddles and dark blobs have negative
+ * responses; responses are finite and non-zero because they passed the threshold, so comparing the strengths as floats and comparing
+ * the uint32 bit patterns of fabsf(response) is the same order).  With i the keypoint's position in the reference's detection order
+ * within its image, keypoint i is kept iff
+ *    #{j : |r_j| > |r_i|} + #{j < i : |r_j| == |r_i|} < N:
+ * ties at the cut go to the earlier keypoint; the result does not depend on launch geometry and is the same from run to run.
+ * The kept keypoints stay in the reference's order, and everything downstream (regions, keys, text rows, the callbacks hesaff.hpp
+ * replays) is what the unlimited run produces for those keypoints, bit for bit, in that order: a keypoint's chain does not depend on
+ * the other keypoints, so a kept keypoint's hesaff_region record equals its unlimited record except for `key`, which is renumbered
+ * over the image's kept, described keypoints, and its hesaff_keypoint bytes equal its unlimited key.
+ * count_hessian is the number kept, min(N, detected); count_desc <= count_hessian.  N bounds the Hessian keypoints, NOT the descriptors:
+ * the strongest keypoints are often saddles on which findAffineShape does not converge, so expect fewer than N keys.
+ * The limit applies to every entry point that detects - hesaff_detect_batch, _cb, _f32, _cb_f32, hesaff_detect_regions, _f32,
+ * hesaff_detect_batch_device, _device_f32, hesaff_process_files - with any parameter set (fast = 2, upscaleInputImage = 1: the
+ * selection comes before either matters).  It does not apply to hesaff_describe_regions* (the records are the caller's) or to the
+ * hesaff_stage_* operators.  max_kpts_per_mpx still has to hold every DETECTED keypoint: the selection runs after the ordering step.
+ * n: 0 = off.  n < 0 or ctx NULL: HESAFF_ERR_ARG (hesaff_get_keypoint_limit: ctx or n NULL). */
+int hesaff_set_keypoint_limit(hesaff_ctx *ctx, int n);
+int hesaff_get_keypoint_limit(const hesaff_ctx *ctx, int *n);
 
 /* Same path with inputs already resident in device memory (bench / pipelines that decode
  * on the GPU): d_gray = n contiguous height x width 8-bit grey planes (device pointer).

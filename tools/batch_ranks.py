@@ -23,7 +23,11 @@ def main():
     ap.add_argument("list")
     ap.add_argument("--one-device", action="store_true")
     ap.add_argument("--chunk", type=int, default=32, help="images per device chunk (hesaff_params.max_batch)")
+    ap.add_argument("--max-keypoints", type=int, default=0,
+                    help="keep the N Hessian keypoints of greatest |response| per image (hesaff_set_keypoint_limit; 0: no limit)")
     args = ap.parse_args()
+    if args.max_keypoints < 0:
+        ap.error("--max-keypoints must be 0 (no limit) or positive")
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1")); local = int(os.environ.get("LOCAL_RANK", "0"))
     backend = None
     if world > 1:
@@ -38,6 +42,7 @@ def main():
     p = hesaff_amd.default_params()
     p.max_batch = max(1, args.chunk)
     ctx = hesaff_amd.HesaffContext(p, device=0 if args.one_device else local)
+    ctx.set_keypoint_limit(args.max_keypoints)
     # the rank's shard through hesaff_process_files (what `hesaff --batch` runs per device): decode ahead, device, rows formatted
     # on the device, write behind - with this rank's share of the host threads
     hp = hesaff_amd.host_plan(max(world, 1))   # the library's one rule (hesaff_host_plan_for): this rank's share of the host

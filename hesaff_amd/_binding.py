@@ -218,6 +218,8 @@ def load_library():
     L.hesaff_stage_normalize_affine.argtypes = [vp, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _i32p, _f32p]
     L.hesaff_stage_sift.argtypes = [vp, C.c_int, _f32p, _u8p]
     L.hesaff_stage_sift_parts.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _u8p]
+    if hasattr(L, "hesaff_stage_sift_alive"):   # (absent from an older build loaded through HESAFF_AMD_LIB for a comparison)
+        L.hesaff_stage_sift_alive.argtypes = [vp, C.c_int, _f32p, _i32p, _u8p]
     L.hesaff_stage_math_sift_general.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math_sift.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]
@@ -243,7 +245,7 @@ ABI_SYMBOLS = [
     "hesaff_write_sift", "hesaff_format_sift", "hesaff_free", "hesaff_read_pnm", "hesaff_stage_gaussian_blur",
     "hesaff_stage_hessian_response", "hesaff_stage_half_image", "hesaff_stage_pyramid", "hesaff_stage_hessian_keypoints",
     "hesaff_stage_find_affine_shape", "hesaff_stage_rectify", "hesaff_stage_normalize_affine", "hesaff_stage_sift",
-    "hesaff_stage_math", "hesaff_stage_math_sift", "hesaff_stage_sift_parts", "hesaff_stage_math_sift_general", "hesaff_table_gauss_mask", "hesaff_table_circ_gauss_mask", "hesaff_table_sift_bins",
+    "hesaff_stage_math", "hesaff_stage_math_sift", "hesaff_stage_sift_parts", "hesaff_stage_sift_alive", "hesaff_stage_math_sift_general", "hesaff_table_gauss_mask", "hesaff_table_circ_gauss_mask", "hesaff_table_sift_bins",
     "hesaff_table_gauss_kernel", "hesaff_format_sift_mt", "hesaff_write_sift_batch", "hesaff_test_fmt_g",
     "hesaff_read_png", "hesaff_read_image", "hesaff_device_count", "hesaff_shard_range", "hesaff_read_jpeg",
     "hesaff_host_threads", "hesaff_host_plan_for", "hesaff_abi_version", "hesaff_sizeof_params", "hesaff_sizeof_timings", "hesaff_detect_batch_cb",
@@ -766,6 +768,15 @@ class HesaffContext:
         mv = np.zeros((n, 2), np.float32); hist = np.zeros((n, 128), np.float32); d = np.zeros((n, 128), np.uint8)
         self._check(self.L.hesaff_stage_sift_parts(self.h, n, p, mv, hist, d))
         return mv, hist, d
+
+    def sift_alive(self, patches, alive, fill=0):
+        """-> desc [n, 128] u8, every byte `fill` before the call: rows of keypoints with alive == 0 keep it (hesaff_stage_sift_alive)."""
+        p = np.ascontiguousarray(patches, np.float32).reshape(-1, 41 * 41)
+        a = np.ascontiguousarray(alive, np.int32).reshape(-1)
+        assert len(a) == len(p)
+        d = np.full((len(p), 128), fill, np.uint8)
+        self._check(self.L.hesaff_stage_sift_alive(self.h, len(p), p, a, d))
+        return d
 
     def export(self, keys, mr_size=None, fmt=1):
         """exportKeypoints on the device (hesaff_stage_export): bytes of the .hesaff.sift file (fmt 1) or of the sidecar (fmt 2)."""

@@ -173,6 +173,7 @@ int hesaff_create(hesaff_ctx **out, const hesaff_params *p, int device)
       // what makes the schedule observable (libhesaff_amd_tuning.so only); neither changes a result
       if (const char *ov = getenv("HESAFF_OVERLAP")) c->no_overlap = atoi(ov) == 0;
       c->debug = getenv("HESAFF_DEBUG") != nullptr;
+      if (const char *sf = getenv("HESAFF_SIFT_INSIDE")) c->sift_inside = atoi(sf) == 1;
 #endif
    } catch (const HsError &e) {
       hesaff_destroy(c);
@@ -829,7 +830,7 @@ int hesaff_process_files(hesaff_ctx *c, int n, const char *const *paths, const c
 // The stage entry points run the PRODUCTION kernels wherever the batch path has one for the operator:
 //   gaussianBlur     -> k_blur_hess_march<K> (K = 9, 11, 13, 15: every blur of the default pyramid), else the generic two-pass kernels
 //   hessianResponse  -> the fused R0 epilogue of k_blur_hess_march<9, .., WRITE_R0> (pyramid.cpp:230 on the batch path)
-//   SIFT             -> k_sift_meanvar / _grad / _hist / _quantize
+//   SIFT             -> k_sift_meanvar / _grad / _hist (histogram, then normalise / clip / quantise)
 //   normalizeAffine  -> k_prepare_patch + the five window-size bin kernels
 //   findAffineShape  -> hs_affine_groups (k_affine's body)
 // halfImage has no stand-alone production kernel (the decimation is an epilogue of the K = 13 blur launch, checked
@@ -1071,8 +1072,10 @@ int hesaff_stage_normalize_affine(hesaff_ctx *c, const float *img, int rows, int
 }
 
 // hesaff_stage_sift and hesaff_stage_sift_parts: the production descriptor kernels on caller-supplied patches; meanvar / hist
-// (either may be null) additionally receive what k_sift_meanvar and k_sift_hist left in the stage buffer
-static int stage_sift(hesaff_ctx *c, int n, const float *patches, float *meanvar, float *hist, uint8_t *desc)
+// (either may be null) additionally receive what k_sift_meanvar left in the stage buffer and the histogram k_sift_hist writes out
+// when it is given a place for it (SiftIO::vec; the pipeline passes none)
+// alive (may be null: every keypoint alive): the pipeline's flags; desc then goes to the device first (dead keypoints' rows stay)
+static int stage_sift(hesaff_ctx *c, int n, const float *patches, float *meanvar, float *hist, uint8_t *desc, const int32_t *alive = nullptr)
 {
    if (!c || !patches || !desc || n < 0) return HESAFF_ERR_ARG;
    HS_API_BEGIN
@@ -1086,11 +1089,12 @@ static int stage_sift(hesaff_ctx *c, int n, const float *patches, float *meanvar
    char *base = (char *)c->b_stage.p;
    std::vector<int32_t> ones(N, 1);
    HIP_TRY(hipMemcpyAsync(base, patches, N * HS_PATCH_PIX * 4, hipMemcpyHostToDevice, c->stream()));
-   HIP_TRY(hipMemcpyAsync(base + off_alive, ones.data(), N * 4, hipMemcpyHostToDevice, c->stream()));
+   HIP_TRY(hipMemcpyAsync(base + off_alive, alive ? alive : ones.data(), N * 4, hipMemcpyHostToDevice, c->stream()));
+   if (alive) HIP_TRY(hipMemcpyAsync(base + off_desc, desc, N * 128, hipMemcpyHostToDevice, c->stream()));
    HIP_TRY(hipMemsetAsync(base + off_vo, 0, N * HS_VO_PITCH * 8 + 64, c->stream()));   // pairs outside the circular mask stay (0, 0)
    SiftIO so;
    so.patches = (const float *)base; so.alive = (const int32_t *)(base + off_alive); so.meanvar = (float *)(base + off_mv);
-   so.vec = (float *)(base + off_vec); so.desc = (uint8_t *)(base + off_desc); so.h_lo = 0; so.h_hi = (uint32_t)n;
+   so.vec = hist ? (float *)(base + off_vec) : nullptr; so.desc = (uint8_t *)(base + off_desc); so.h_lo = 0; so.h_hi = (uint32_t)n;
    launch_sift(c, c->stream(), so, (uint32_t)n, (float2 *)(base + off_vo));
    if (meanvar) HIP_TRY(hipMemcpyAsync(meanvar, base + off_mv, N * 8, hipMemcpyDeviceToHost, c->stream()));
    if (hist) HIP_TRY(hipMemcpyAsync(hist, base + off_vec, N * 128 * 4, hipMemcpyDeviceToHost, c->stream()));
@@ -1105,6 +1109,12 @@ int hesaff_stage_sift_parts(hesaff_ctx *c, int n, const float *patches, float *m
 {
    if (!meanvar || !hist) return HESAFF_ERR_ARG;
    return stage_sift(c, n, patches, meanvar, hist, desc);
+}
+
+int hesaff_stage_sift_alive(hesaff_ctx *c, int n, const float *patches, const int32_t *alive, uint8_t *desc)
+{
+   if (!alive) return HESAFF_ERR_ARG;
+   return stage_sift(c, n, patches, nullptr, nullptr, desc, alive);
 }
 
 // exportKeypoints on the device for caller-supplied records: the kernels hesaff_process_files runs per chunk

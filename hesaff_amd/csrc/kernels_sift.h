@@ -1,5 +1,5 @@
 // kernels_sift.h -- SIFT descriptor (siftdesc.cpp:115-140, helpers.cpp:246-281) over patches
-// held in HBM, as four kernels whose parallel axis matches the structure of the reference's
+// held in HBM, as three kernels whose parallel axis matches the structure of the reference's
 // arithmetic instead of fighting it:
 //
 //  k_sift_meanvar   the photometric mean / variance are long SEQUENTIAL float sums
@@ -14,9 +14,10 @@
 //  k_sift_hist      FOUR keypoints per wavefront, lane = (keypoint, spatial cell): the cell's 8
 //                   orientation bins live in LDS ([bin][lane], conflict-free) and the lane walks
 //                   its 16x16 support in raster order (siftdesc.cpp:51-81); the wave fetches each step's
-//                   rows coalesced and hands them out through LDS.
-//  k_sift_quantize  normalize / clip / renormalize / quantise (siftdesc.cpp:83-113): the two
-//                   128-term sequential sums again run one thread per keypoint.
+//                   rows coalesced and hands them out through LDS.  The four histograms are then still in LDS:
+//                   normalize / clip / renormalize / quantise (siftdesc.cpp:83-113) follow in place - the two
+//                   128-term sequential sums on one lane per keypoint, everything else on all 64 - and the
+//                   128 bytes go straight to the descriptor.
 //
 // All sums are accumulated in the reference's order; nothing is re-associated.
 #pragma once
@@ -26,7 +27,7 @@ struct SiftIO {
    const float *patches;     // [n][1681] (index = h - h_lo)
    const int32_t *alive;     // [n] flags, indexed by h
    float *meanvar;           // [n][2]
-   float *vec;               // [n][128] un-normalised histogram
+   float *vec;               // [n][128] un-normalised histogram: the stage API's test hook, null in the pipeline (not written)
    uint8_t *desc;            // [n][128] (index = h, absolute)
    uint32_t h_lo, h_hi;
 };
@@ -34,7 +35,6 @@ struct SiftIO {
 // (HS_VO_DIM and the layout of a keypoint's gradient pairs in HBM - HS_VO_ITEMS, HS_VO_ZERO, HS_VO_PITCH: plan_consts.h)
 #define HS_VO_TILE (HS_VO_DIM * HS_VO_DIM)    // float2 of k_sift_grad's LDS tile (row-major 40 x 40)
 #define HS_SIFT_MSK_IT 5   // ceil(1245 / 256): pixels inside the circular mask per thread of a 256-thread block
-#define SM_TILE 64
 
 // grid: ceil(n / SM_KP) blocks of 64 threads.
 // SM_KP = keypoints per wavefront.  64 (every lane owns a keypoint) is the form with the fewest instructions, but a wavefront
@@ -266,9 +266,11 @@ __global__ void k_math_sift_general(int n, const float *__restrict__ gy, const f
 // LDS and not registers).  Where the reference adds nothing (val <= 0) this adds +0.0f.
 // The (mask*grad, o) rows of a step are fetched by the whole wave as consecutive 16-byte items and handed
 // out through LDS (see "Row staging" below), the next step's rows in flight while the current ones are consumed.
+// Behind the 16 steps the wave turns its four histograms into descriptor bytes (max_bin = DConsts::maxBinValue).
 // grid-stride over groups of 4 keypoints, block 64.
+#define HS_SQ_PITCH 132   // floats between the keypoints' squared vectors in LDS (k_sift_hist): 128 + one 16-byte item
 #define HS_HIST_AHEAD 1   // steps the row items are requested ahead (2, with a second set of five registers, measured the same: profiles/r05_notes.md)
-__global__ __launch_bounds__(64) void k_sift_hist(SiftIO io, KpTables tb, const float2 *__restrict__ vo)
+__global__ __launch_bounds__(64) void k_sift_hist(SiftIO io, KpTables tb, const float2 *__restrict__ vo, float max_bin)
 {
    __shared__ __attribute__((aligned(2048))) float s_acc[8 * 64];
    __shared__ float s_cw[64];   // [spatial bin][offset 0..15]
@@ -374,65 +376,62 @@ __global__ __launch_bounds__(64) void k_sift_hist(SiftIO io, KpTables tb, const 
       };
 #pragma unroll 1
       for (int i = 0; i < 16; i++) step(i, st0, st1, st2, st3, st4);
-      if (k < n) {
+      // sample() behind samplePatch (siftdesc.cpp:98-113): normalizeVec, clip at maxBinValue, normalizeVec again where a bin was clipped,
+      // quantise.  The vector's index is i = 8 * cell + bin, so this lane holds items 8 cell .. 8 cell + 7 of its keypoint.  The two
+      // 128-term sums of squares run in the reference's order on the keypoint's first lane: every lane squares its own eight items
+      // into LDS in vector order (the staging rows are free now; keypoints HS_SQ_PITCH floats apart, so that the four summing lanes
+      // read 16-byte items from disjoint banks), the sum itself is 32 reads and 128 additions.  (A keypoint past the list or a dead
+      // one carries zeros: 0 * inf = NaN all the way, nothing is stored.)
+      HS_WAVE_LDS_SYNC();   // (this lane's bins: its own writes, but the compiler must not move the reads above them)
+      float vb[8];
+#pragma unroll
+      for (int b = 0; b < 8; b++) vb[b] = acc[64 * b];
+      if (io.vec != nullptr && k < n) {   // stage API only (hesaff_stage_sift_parts): the un-normalised histogram
          float4 *dst = reinterpret_cast<float4 *>(io.vec + (size_t)k * 128 + cell * 8);
-         dst[0] = make_float4(acc[0], acc[64], acc[128], acc[192]);
-         dst[1] = make_float4(acc[256], acc[320], acc[384], acc[448]);
+         dst[0] = make_float4(vb[0], vb[1], vb[2], vb[3]);
+         dst[1] = make_float4(vb[4], vb[5], vb[6], vb[7]);
       }
-   }
-}
-
-// sample() siftdesc.cpp:98-113 after samplePatch: one thread per keypoint for the serial norms.
-// grid: ceil(n / 64) blocks of 64 threads; LDS tile 64 keypoints x 128 bins.
-__global__ __launch_bounds__(64) void k_sift_quantize(SiftIO io, DConsts kc)
-{
-   __shared__ float s_t[SM_TILE * 129];
-   const int lane = threadIdx.x;
-   const uint32_t n = io.h_hi - io.h_lo;
-   const uint32_t k0 = blockIdx.x * SM_TILE;
-   // coalesced load: row k = keypoint, 128 consecutive floats
-   for (int k = 0; k < SM_TILE; k++) {
-      const uint32_t kp = min(k0 + k, n - 1);
-      s_t[k * 129 + lane] = io.vec[(size_t)kp * 128 + lane];
-      s_t[k * 129 + 64 + lane] = io.vec[(size_t)kp * 128 + 64 + lane];
-   }
-   __syncthreads();
-   float *v = s_t + lane * 129;
-   {
-      float vectlen = 0.0f;
-      for (int i = 0; i < 128; i++) { const float x = v[i]; vectlen += x * x; }   // siftdesc.cpp:86-90
-      vectlen = sqrtf(vectlen);
-      const float fac = 1.0f / vectlen;
+      float *s_sq = reinterpret_cast<float *>(s_rows);
+      auto norm_factor = [&]() {   // 1 / sqrt(sum of vb^2 over the keypoint's 128 items), siftdesc.cpp:86-92
+         float4 *mine = reinterpret_cast<float4 *>(s_sq + HS_SQ_PITCH * kq + 8 * cell);
+         mine[0] = make_float4(vb[0] * vb[0], vb[1] * vb[1], vb[2] * vb[2], vb[3] * vb[3]);
+         mine[1] = make_float4(vb[4] * vb[4], vb[5] * vb[5], vb[6] * vb[6], vb[7] * vb[7]);
+         HS_WAVE_LDS_SYNC();
+         float len = 0.0f;
+         if (cell == 0) {
+            const float4 *r = reinterpret_cast<const float4 *>(s_sq + HS_SQ_PITCH * kq);
+#pragma unroll 8
+            for (int j = 0; j < 32; j++) { const float4 q = r[j]; len += q.x; len += q.y; len += q.z; len += q.w; }
+         }
+         len = sqrtf(__shfl(len, tid & 48));
+         HS_WAVE_LDS_SYNC();   // the sums are read before anything is parked here again
+         return 1.0f / len;
+      };
+      const float fac = norm_factor();
       bool changed = false;
-      for (int i = 0; i < 128; i++) {
-         float x = v[i] * fac;
-         if (x > kc.maxBinValue) { x = kc.maxBinValue; changed = true; }
-         v[i] = x;
+#pragma unroll
+      for (int b = 0; b < 8; b++) {
+         float x = vb[b] * fac;
+         if (x > max_bin) { x = max_bin; changed = true; }
+         vb[b] = x;
       }
-      if (changed) {
-         float l2 = 0.0f;
-         for (int i = 0; i < 128; i++) { const float x = v[i]; l2 += x * x; }
-         l2 = sqrtf(l2);
-         const float f2 = 1.0f / l2;
-         for (int i = 0; i < 128; i++) v[i] *= f2;
+      const unsigned long long clipped = __ballot(changed);   // bit = lane; a keypoint's 16 lanes are 16 consecutive bits
+      if (clipped != 0ull) {   // (wave-uniform; the sums of the wave's unclipped keypoints are computed and dropped)
+         const float f2 = norm_factor();
+         if ((clipped >> (16 * kq)) & 0xffffull) {
+#pragma unroll
+            for (int b = 0; b < 8; b++) vb[b] *= f2;
+         }
       }
-      for (int i = 0; i < 128; i++) {
-         const float q = 512.0f * v[i];
-         int bq = (q == q) ? (int)q : 0;
-         v[i] = (float)min(bq, 255);
-      }
-   }
-   __syncthreads();
-   // coalesced byte store: 4 bytes per lane, two keypoints per iteration
-   for (int k = 0; k < SM_TILE; k++) {
-      const uint32_t kp = k0 + k;
-      if (kp >= n) break;
-      const uint32_t h = io.h_lo + kp;
-      if (!io.alive[h]) continue;
-      if (lane < 32) {
-         const float *r = s_t + k * 129 + 4 * lane;
-         const uint32_t w = (uint32_t)r[0] | ((uint32_t)r[1] << 8) | ((uint32_t)r[2] << 16) | ((uint32_t)r[3] << 24);
-         *reinterpret_cast<uint32_t *>(io.desc + (size_t)h * 128 + 4 * lane) = w;
+      if (valid) {
+         uint32_t w[2] = {0u, 0u};
+#pragma unroll
+         for (int b = 0; b < 8; b++) {
+            const float q = 512.0f * vb[b];
+            const int bq = (q == q) ? (int)q : 0;
+            w[b >> 2] |= (uint32_t)(float)min(bq, 255) << (8 * (b & 3));
+         }
+         *reinterpret_cast<uint2 *>(io.desc + (size_t)(io.h_lo + k) * 128 + 8 * cell) = make_uint2(w[0], w[1]);
       }
    }
 }

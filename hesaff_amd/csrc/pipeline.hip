@@ -426,12 +426,13 @@ struct hesaff_ctx {
    std::vector<DevEvent> ev_aff;             // one per image group, grown on demand
    DevEvent ev_extract_done[HS_NSLOT], ev_sift_done[HS_NSLOT];
    DevBuf b_patches2[HS_NSLOT];
-   DevBuf b_siftvec2, b_meanvar2, b_siftvo2;   // the descriptor stage's intermediates: one copy (ensure_group_buffers)
+   DevBuf b_meanvar2, b_siftvo2;   // the descriptor stage's intermediates: one copy (ensure_group_buffers)
    DevEvent ev_fork, ev_join[HS_NSIDE];
    bool fast_pyramid = false;      // hesaff_params.fast == 2: windows beyond bin 0 sampled from the scale-space level with the matching blur (not bit-exact)
    // off in the product build; the tuning build (-DHESAFF_TUNING) reads them from the environment, and HESAFF_FAST for fast_pyramid
    bool no_overlap = false;        // HESAFF_OVERLAP=0: every kernel alone on the device (per-kernel profiling)
    bool debug = false;             // HESAFF_DEBUG=1: launch geometry on stderr
+   bool sift_inside = false;       // HESAFF_SIFT_INSIDE=1: a group's descriptor kernels submitted inside the next group's patch stage (run_keypoint_stages)
 
    std::vector<DevEvent> ev_pool;   // timing events of the stage timers (get_event)
    size_t ev_used = 0;
@@ -730,8 +731,11 @@ Lists make_lists(hesaff_ctx *c)
 // normalizeAffine for every keypoint k_prepare_patch left alive and binned.  Every launch is a persistent grid of
 // fixed size that reads its work-list length from the device-side bin counters: the host never waits for them.
 // large_rows_bound: upper bound of the large bin's T' rows in this group (from k_image_large_rows).
-void run_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float *patches_out, uint32_t h_base, uint32_t large_rows_bound,
-                     const PlaneTab *pt = nullptr)
+// Two halves: launch_patch_stage enqueues every kernel and returns how many side streams the main stream has to take back
+// (0: none were used); join_patch_stage records their ends and makes the main stream wait for them.  What a caller enqueues between
+// the two halves stands, on a hardware queue the main stream shares, in front of that wait and not behind it (run_keypoint_stages).
+int launch_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float *patches_out, uint32_t h_base, uint32_t large_rows_bound,
+                       const PlaneTab *pt = nullptr)
 {
    hipStream_t st = c->stream();
    PatchIO io;
@@ -749,10 +753,8 @@ void run_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float *
          s0 = c->sset.bin(0);
       }
       hipLaunchKernelGGL(k_patch_extract_small<0>, dim3(c->g_small0), dim3(256), small_extract_lds_bytes(0), s0, s.hl, s.pw, io, c->tables.view);
-      if (forked) HIP_TRY(hipEventRecord(c->ev_join[0], s0));
       hipLaunchKernelGGL(k_patch_pyramid, dim3((uint32_t)c->n_cu * 32u), dim3(256), 0, st, s.hl, s.pw, io, *pt, (int)c->oct.size(), c->ct.consts.pd0, 1);
-      if (forked) HIP_TRY(hipStreamWaitEvent(st, c->ev_join[0], 0));
-      return;
+      return forked ? 1 : 0;
    }
    // The bins are independent (disjoint keypoints) and each kernel leaves CU resources idle
    // (LDS- or latency-bound), so they run concurrently on side streams.
@@ -795,10 +797,19 @@ void run_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float *
       }
       hipLaunchKernelGGL(k_patch_large_finish, dim3(c->g_lfin), dim3(256), 0, st, s.pw, io, c->tables.view);
    }
-   if (forked) {
-      for (int i = 0; i < HS_NSIDE; i++) HIP_TRY(hipEventRecord(c->ev_join[i], c->sset.bin(i)));
-      for (int i = 0; i < HS_NSIDE; i++) HIP_TRY(hipStreamWaitEvent(st, c->ev_join[i], 0));
-   }
+   return forked ? HS_NSIDE : 0;
+}
+
+void join_patch_stage(hesaff_ctx *c, int n_side)
+{
+   for (int i = 0; i < n_side; i++) HIP_TRY(hipEventRecord(c->ev_join[i], c->sset.bin(i)));
+   for (int i = 0; i < n_side; i++) HIP_TRY(hipStreamWaitEvent(c->stream(), c->ev_join[i], 0));
+}
+
+void run_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float *patches_out, uint32_t h_base, uint32_t large_rows_bound,
+                     const PlaneTab *pt = nullptr)
+{
+   join_patch_stage(c, launch_patch_stage(c, s, image, patches_out, h_base, large_rows_bound, pt));
 }
 
 // per image: upper bound of the T' rows its huge windows (P > 512) need, known from the scales alone
@@ -1022,25 +1033,23 @@ void collect_timings(hesaff_ctx *c, StageTimer &tm, int B)
    t.export_ms = c->export_ms; t.export_rows = c->export_rows;   // (run_chunks keeps them across the batches of a list)   // (+ the up-sampling pass when upscaleInputImage is set: not counted)
 }
 
-// The descriptor kernels (kernels_sift.h) over n patches in HBM.  (Slices of a group, each slice's four kernels back to back so that
+// The descriptor kernels (kernels_sift.h) over n patches in HBM.  (Slices of a group, each slice's kernels back to back so that
 // the intermediates stay in the memory-side cache, measured no faster: sweep in profiles/r06_notes.md.)
 void launch_sift(hesaff_ctx *c, hipStream_t ss, const SiftIO &so, uint32_t n, float2 *vo)
 {
-   const uint32_t nb64 = (n + 63) / 64;
    hipLaunchKernelGGL(k_sift_meanvar, dim3((n + SM_KP - 1) / SM_KP), dim3(64), 0, ss, so, c->tables.view);
    hipLaunchKernelGGL(k_sift_grad, dim3(std::min(n, c->sgrad_grid)), dim3(256), 0, ss, so, c->tables.view, vo);
-   hipLaunchKernelGGL(k_sift_hist, dim3(std::min<uint32_t>((n + 3) / 4, c->g_shist)), dim3(64), 0, ss, so, c->tables.view, (const float2 *)vo);
-   hipLaunchKernelGGL(k_sift_quantize, dim3(nb64), dim3(64), 0, ss, so, c->ct.consts);
+   hipLaunchKernelGGL(k_sift_hist, dim3(std::min<uint32_t>((n + 3) / 4, c->g_shist)), dim3(64), 0, ss, so, c->tables.view, (const float2 *)vo,
+                      c->ct.consts.maxBinValue);
 }
 
 // per-group patch / descriptor buffers: sized once per batch for the largest group
 void ensure_group_buffers(hesaff_ctx *c, uint32_t n)
 {
    // The patch buffers rotate over HS_NSLOT slots (the patch stage fills one while the descriptor stage reads the others).  The
-   // descriptor stage's own intermediates - gradient pairs (10.4 KB per keypoint), histograms, mean / variance - live and die on its
+   // descriptor stage's own intermediates - gradient pairs (10.4 KB per keypoint), mean / variance - live and die on its
    // one stream (the main stream with HESAFF_OVERLAP=0), so one copy of them serves every group.
    for (int slot = 0; slot < HS_NSLOT; slot++) c->b_patches2[slot].ensure_grow((size_t)n * HS_PATCH_PIX * 4);
-   c->b_siftvec2.ensure_grow((size_t)n * 128 * 4);
    c->b_meanvar2.ensure_grow((size_t)n * 2 * 4);
    // the (mask*grad, o) pairs of pixels outside the circular mask stay (0, 0): zero-fill on (re)allocation
    const void *before = c->b_siftvo2.p;
@@ -1087,7 +1096,7 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
    for (size_t o = 0; o < c->oct.size(); o++)
       for (int l = 0; l < 3; l++) pt.L[o][l] = c->L[o * 3 + l];
    {
-      // The bin kernels only extract the 41x41 patches (to HBM); the descriptor runs as four kernels with the parallel axis each
+      // The bin kernels only extract the 41x41 patches (to HBM); the descriptor runs as three kernels with the parallel axis each
       // part wants (kernels_sift.h).  Images are processed in groups so that the patch buffers stay bounded.
       if ((uint32_t)hs[B] > c->cap) throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded; raise hesaff_params.max_kpts_per_mpx");
       n_hess_host = (uint32_t)hs[B];
@@ -1101,7 +1110,7 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
       // Software pipeline over image groups, one stream per stage:
       //   affine shape of group g+1 (sset.affine())  |  patch extraction of group g (main + side
       //   streams, latency-bound)  |  descriptor kernels of the groups before (sset.sift()).
-      // Three patch buffer slots rotate.
+      // Three patch buffer slots rotate: a slot is written again only when the descriptors of the group three back are finished.
       hipStream_t as = c->no_overlap ? st : c->sset.affine();
       if (as != st && with_affine) HIP_TRY(hipStreamWaitEvent(as, c->ev_detect_done, 0));
       auto launch_affine = [&](size_t gi) {
@@ -1114,8 +1123,29 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
       };
       if (!groups.empty()) launch_affine(0);
       bool slot_used[HS_NSLOT] = {};
+      hipStream_t ss = c->no_overlap ? st : c->sset.sift();
+      // the descriptor kernels of group gi, behind its patches
+      auto launch_descriptors = [&](size_t gi) {
+         const int slot = (int)(gi % HS_NSLOT);
+         if (ss != st) HIP_TRY(hipStreamWaitEvent(ss, c->ev_extract_done[slot], 0));
+         SiftIO so;
+         so.patches = c->b_patches2[slot].as<float>(); so.alive = s.pw.alive; so.meanvar = c->b_meanvar2.as<float>();
+         so.vec = nullptr; so.desc = c->geo.b_desc.as<uint8_t>(); so.h_lo = groups[gi].lo; so.h_hi = groups[gi].hi;
+         const int ts = tm.begin(T_SIFT, 0, ss);
+         launch_sift(c, ss, so, groups[gi].hi - groups[gi].lo, c->b_siftvo2.as<float2>());
+         tm.end(ts);
+         HIP_TRY(hipEventRecord(c->ev_sift_done[slot], ss));
+      };
+      // Order of submission.  The runtime multiplexes the HIP streams of one priority onto its few hardware queues, and a process that
+      // has streams of its own (under PyTorch: two of the four queues) leaves this context's four streams two queues, the descriptor
+      // stream on the one the main stream uses.  A hardware queue runs its packets in the order they were submitted, whichever stream
+      // they came through, so a group's descriptor kernels, submitted behind its patch stage, stand in front of the next group's
+      // k_prepare_patch: there the two stages take turns (profiles/r07_notes.md).  sift_inside (tuning build) submits the descriptor
+      // kernels of group g - 1 in the MIDDLE of group g's patch stage instead - behind its kernels and in front of the main stream's
+      // wait for the side streams - so that the other queue's bins run beside the descriptor chain.  They do, and each runs that much
+      // slower: the dense step measured 0.8 % slower that way, the photograph step 2 % faster, so the order stays.
       for (size_t gi = 0; gi < groups.size(); gi++) {
-         const uint32_t h_lo = groups[gi].lo, h_hi = groups[gi].hi, n = h_hi - h_lo;
+         const uint32_t h_lo = groups[gi].lo, h_hi = groups[gi].hi;
          if (gi + 1 < groups.size()) launch_affine(gi + 1);
          if (as != st && with_affine) HIP_TRY(hipStreamWaitEvent(st, c->ev_aff[gi], 0));
          const int slot = (int)(gi % HS_NSLOT);
@@ -1126,20 +1156,15 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
          //  here until the stream has drained, once per group)
          hipLaunchKernelGGL(k_prepare_patch, dim3(1024), dim3(256), 0, st, s.hl, h_lo, h_hi, (const uint32_t *)&cnt->head.hess_total, s.ao, H, W, c->ct.consts,
                             c->tables.view, s.pw);
-         run_patch_stage(c, s, c->gray, c->b_patches2[slot].as<float>(), h_lo, groups[gi].large_rows, &pt);
+         const int n_side = launch_patch_stage(c, s, c->gray, c->b_patches2[slot].as<float>(), h_lo, groups[gi].large_rows, &pt);
+         if (gi > 0 && c->sift_inside) launch_descriptors(gi - 1);
+         join_patch_stage(c, n_side);
          tm.end(t);
          HIP_TRY(hipEventRecord(c->ev_extract_done[slot], st));
-         hipStream_t ss = c->no_overlap ? st : c->sset.sift();
-         if (ss != st) HIP_TRY(hipStreamWaitEvent(ss, c->ev_extract_done[slot], 0));
-         SiftIO so;
-         so.patches = c->b_patches2[slot].as<float>(); so.alive = s.pw.alive; so.meanvar = c->b_meanvar2.as<float>();
-         so.vec = c->b_siftvec2.as<float>(); so.desc = c->geo.b_desc.as<uint8_t>(); so.h_lo = h_lo; so.h_hi = h_hi;
-         const int ts = tm.begin(T_SIFT, 0, ss);
-         launch_sift(c, ss, so, n, c->b_siftvo2.as<float2>());
-         tm.end(ts);
-         HIP_TRY(hipEventRecord(c->ev_sift_done[slot], ss));
          slot_used[slot] = true;
+         if (!c->sift_inside) launch_descriptors(gi);
       }
+      if (!groups.empty() && c->sift_inside) launch_descriptors(groups.size() - 1);
       for (int sl = 0; sl < HS_NSLOT; sl++)
          if (slot_used[sl]) HIP_TRY(hipStreamWaitEvent(st, c->ev_sift_done[sl], 0));
    }

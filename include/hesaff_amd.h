@@ -42,6 +42,7 @@ extern "C" {
  *    needs them finds them by symbol (dlsym) in the library it loaded.  The same holds for hesaff_describe_regions and
  *    hesaff_describe_regions_f32 (HESAFF_FROM_POINTS / HESAFF_FROM_SHAPES): new symbols over the structs of version 8.  And for
  *    hesaff_set_keypoint_limit / hesaff_get_keypoint_limit: two more symbols, no struct touched, the version stays 8.
+ *    And for the test hook hesaff_stage_sift_alive.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -522,6 +523,10 @@ int hesaff_stage_sift(hesaff_ctx *ctx, int n, const float *patches, uint8_t *des
  * pixels, which normalizeAffine's interpolation and smoothing do not exceed.  Within it a patch may be flat (var < 1e-4: it keeps its raw
  * pixels, gradients down to denormals and 0) or constant.  Infinities, NaN and larger magnitudes are outside the domain. */
 int hesaff_stage_sift_parts(hesaff_ctx *ctx, int n, const float *patches, float *meanvar, float *hist, uint8_t *desc);
+/* hesaff_stage_sift with the pipeline's per-keypoint flags: alive[n], 0 = a keypoint normalizeAffine rejected.  The descriptor kernels
+ * write nothing for such a keypoint: desc[n][128] goes to the device as the caller filled it and comes back, the rows of dead
+ * keypoints unchanged. */
+int hesaff_stage_sift_alive(hesaff_ctx *ctx, int n, const float *patches, const int32_t *alive, uint8_t *desc);
 /* exportKeypoints hesaff.cpp:107-130 on the device for n records in host memory (what hesaff_process_files runs per chunk):
  * format = HESAFF_OUT_TEXT: the bytes of the .hesaff.sift file, == hesaff_format_sift; HESAFF_OUT_BIN: the bytes of the sidecar,
  * == hesaff_write_bin's file.  *out is malloc'ed (hesaff_free). */

@@ -1,0 +1,122 @@
+// group_schedule.h -- the stream / event order of the keypoint stages: which logical stream runs which stage of which image group,
+// which stream waits for which event, and when a patch slot may be written again.  No HIP here: run_group_schedule is a template over
+// a device object, as run_chunk_loop (chunk_engine.h) is.  pipeline.hip follows it with an adapter that is launches and lookups;
+// tests/native/schedule_check.cpp runs the same template over a recording device and checks the happens-before relation of every trace.
+#pragma once
+#include "plan_consts.h"
+
+namespace hesaff_sched {
+
+// The logical streams of a context, numbered as StreamSet (pipeline.hip) pairs them onto its four HIP streams.
+enum Stream { S_MAIN = 0, S_BIN0 = 1, S_DESC = 1 + HS_NSIDE, S_AFFINE = 2 + HS_NSIDE, S_COUNT = 3 + HS_NSIDE };
+inline Stream bin_stream(int i) { return (Stream)(S_BIN0 + i); }   // side stream of the patch stage's window-size bin i
+// the stream bin i's patch kernel runs on when the stage forks n_side side streams: bins beyond them stay on the main stream
+inline Stream patch_stream(int i, int n_side) { return i < n_side ? bin_stream(i) : S_MAIN; }
+
+// The events of the pipeline.  (kind, index) names the event object; an event of a slot or a bin is recorded again for every group,
+// and a wait sees whichever record was issued last before it.  `group` says which group's record this record is, or this wait is
+// meant to see: the device never needs it, the checker holds every wait to it.
+struct Event {
+   enum Kind { DETECT_DONE, AFFINE_DONE, EXTRACT_DONE, SIFT_DONE, FORK, JOIN } kind;
+   int index;   // AFFINE_DONE: the group; EXTRACT_DONE, SIFT_DONE: the slot; JOIN: the bin; otherwise 0
+   int group;   // -1: none (DETECT_DONE, which the caller records before the schedule starts)
+};
+inline Event ev_detect_done() { return {Event::DETECT_DONE, 0, -1}; }
+inline Event ev_affine_done(int g) { return {Event::AFFINE_DONE, g, g}; }
+inline Event ev_extract_done(int slot, int g) { return {Event::EXTRACT_DONE, slot, g}; }
+inline Event ev_sift_done(int slot, int g) { return {Event::SIFT_DONE, slot, g}; }
+inline Event ev_fork(int g) { return {Event::FORK, 0, g}; }
+inline Event ev_join(int bin, int g) { return {Event::JOIN, bin, g}; }
+
+// The patch stage's fork onto n_side side streams and the main stream's taking them back (group g; 0: nothing to do).  What is
+// enqueued between the patch kernels and the join stands, on a hardware queue the main stream shares, in front of the main stream's
+// waits and not behind them.
+template <class Device> void fork_side_streams(Device &dev, int g, int n_side)
+{
+   if (n_side > 0) dev.record(ev_fork(g), S_MAIN);
+   for (int i = 0; i < n_side; i++) dev.wait(bin_stream(i), ev_fork(g));
+}
+template <class Device> void join_side_streams(Device &dev, int g, int n_side)
+{
+   for (int i = 0; i < n_side; i++) dev.record(ev_join(i, g), bin_stream(i));
+   for (int i = 0; i < n_side; i++) dev.wait(S_MAIN, ev_join(i, g));
+}
+
+struct ScheduleOptions {
+   bool overlap;       // false (HESAFF_OVERLAP=0, tuning build): every logical stream is the main stream, every kernel alone on the device
+   bool sift_inside;   // HESAFF_SIFT_INSIDE=1 (tuning build): the other order of submission, below
+   bool with_affine;   // false: the affine output is in place already, no affine stage
+   int n_side;         // side streams the patch stage forks: 0, 1 (fast mode 2) or HS_NSIDE
+};
+
+// Software pipeline over n_groups image groups, one stream per stage:
+//   affine shape of group g+1 (S_AFFINE)  |  patch extraction of group g (main + side streams, latency-bound)  |  descriptor
+//   kernels of the groups before (S_DESC).
+// HS_NSLOT patch buffer slots rotate, group g in slot g % HS_NSLOT.  What the order has to guarantee (schedule_check.cpp asserts
+// each of them for every trace):
+//   - the patch stage of g, k_prepare_patch included, reads the affine output of g: behind affine(g), and affine(0) behind the
+//     caller's detect-done;
+//   - a slot is written again only when the descriptors of the group HS_NSLOT back have read it;
+//   - the descriptors of g read every patch of g, whichever stream wrote it;
+//   - the one copy of the descriptor stage's intermediates (b_meanvar2, b_siftvo2) serves one group at a time: the descriptor
+//     chains stand on one stream, one behind the other;
+//   - patch_prepare(g) clears the bin counters: behind every patch kernel of g-1 on every stream, which still reads them, and
+//     in front of every patch kernel of g, which reads what it counted;
+//   - what follows the schedule on the main stream (the pack stage) is behind every descriptor chain, patch kernel and affine.
+// Device:
+//   wait(stream, event), record(event, stream)   every hipStreamWaitEvent / hipEventRecord of the pipeline, and no other
+//   affine(g, stream)                    k_affine of group g
+//   patch_prepare(g)                     main stream: the bin counters cleared, k_prepare_patch
+//   patch_kernels(g, slot, n_side)       bin i's kernel on patch_stream(i, n_side), the rest (huge windows, or fast mode 2's pyramid
+//                                        kernel) on the main stream; patches into `slot`
+//   patch_done(g)                        main stream, behind the join: the end of the patch stage's timer bracket
+//   descriptors(g, slot, stream)         the descriptor kernels of group g over the patches in `slot`
+//
+// Order of submission.  The runtime multiplexes the HIP streams of one priority onto its few hardware queues, and a process that
+// has streams of its own (under PyTorch: two of the four queues) leaves a context's four streams two queues, the descriptor
+// stream on the one the main stream uses.  A hardware queue runs its packets in the order they were submitted, whichever stream
+// they came through, so a group's descriptor kernels, submitted behind its patch stage, stand in front of the next group's
+// k_prepare_patch: there the two stages take turns (profiles/r07_notes.md).  sift_inside submits the descriptor kernels of group
+// g - 1 in the MIDDLE of group g's patch stage instead - behind its kernels and in front of the main stream's wait for the side
+// streams - so that the other queue's bins run beside the descriptor chain.  They do, and each runs that much slower: the dense step
+// measured 0.8 % slower that way, the photograph step 2 % faster, so the order stays.
+template <class Device> void run_group_schedule(Device &dev, int n_groups, const ScheduleOptions &o)
+{
+   const Stream as = o.overlap ? S_AFFINE : S_MAIN, ss = o.overlap ? S_DESC : S_MAIN;
+   const bool affine_events = o.overlap && o.with_affine;
+   if (affine_events) dev.wait(as, ev_detect_done());
+   auto affine = [&](int g) {
+      if (!o.with_affine) return;
+      dev.affine(g, as);
+      if (o.overlap) dev.record(ev_affine_done(g), as);
+   };
+   // the descriptor kernels of group g, behind its patches
+   auto descriptors = [&](int g) {
+      const int slot = g % HS_NSLOT;
+      if (o.overlap) dev.wait(ss, ev_extract_done(slot, g));
+      dev.descriptors(g, slot, ss);
+      dev.record(ev_sift_done(slot, g), ss);
+   };
+   if (n_groups > 0) affine(0);
+   bool slot_used[HS_NSLOT] = {};
+   for (int g = 0; g < n_groups; g++) {
+      if (g + 1 < n_groups) affine(g + 1);
+      if (affine_events) dev.wait(S_MAIN, ev_affine_done(g));
+      const int slot = g % HS_NSLOT;
+      if (slot_used[slot]) dev.wait(S_MAIN, ev_sift_done(slot, g - HS_NSLOT));   // the slot's previous descriptors are finished
+      dev.patch_prepare(g);
+      fork_side_streams(dev, g, o.n_side);
+      dev.patch_kernels(g, slot, o.n_side);
+      if (g > 0 && o.sift_inside) descriptors(g - 1);
+      join_side_streams(dev, g, o.n_side);
+      dev.patch_done(g);
+      dev.record(ev_extract_done(slot, g), S_MAIN);
+      slot_used[slot] = true;
+      if (!o.sift_inside) descriptors(g);
+   }
+   if (n_groups > 0 && o.sift_inside) descriptors(n_groups - 1);
+   for (int sl = 0; sl < HS_NSLOT; sl++)
+      if (slot_used[sl]) dev.wait(S_MAIN, ev_sift_done(sl, (n_groups - 1 - sl) / HS_NSLOT * HS_NSLOT + sl));   // the slot's last group
+}
+
+}   // namespace hesaff_sched

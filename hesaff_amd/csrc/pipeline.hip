@@ -42,6 +42,7 @@
 #include "chunk_engine.h"
 #include "batch_plan.h"
 #include "context_tables.h"
+#include "group_schedule.h"
 
 static thread_local std::string g_create_error;
 
@@ -57,6 +58,7 @@ static thread_local std::string g_create_error;
 
 using hesaff_engine::HsError;
 using namespace hesaff_plan;   // batch_plan.h, context_tables.h: the layouts, the launch arithmetic and the tables of a batch
+namespace sched = hesaff_sched;   // group_schedule.h: the stream / event order of the keypoint stages
 
 // Host wait for a HIP event WITHOUT a spinning core.  hipEventSynchronize spins in this runtime even on events created with
 // hipEventBlockingSync (measured in round 5 with CLOCK_THREAD_CPUTIME_ID around the call: 96 ms of CPU for a 96 ms wait, one busy core per
@@ -212,7 +214,6 @@ struct DevEvent {
    operator hipEvent_t() const { return e; }
 };
 
-#define HS_NSIDE 4   // side streams of the patch stage (one per window-size bin 0..3)
 #define HS_AFF_BLOCKS_PER_CU 8   // persistent k_affine blocks per CU (19 KB of LDS each: 8 resident).  Alone on the device 64 / 128 blocks per CU
                                  // are 4 % faster (20.7 / 20.6 vs 21.6 ms), beside the other stages' kernels they make the step 3.5 % slower
                                  // (453 vs 438 ms at B = 128): the queued blocks take every slot that frees up
@@ -224,7 +225,6 @@ struct DevEvent {
 #define HS_MID_CAP 6   // blocks per CU of the two row-streamed bins (at most; the occupancy query may say fewer)
 #define HS_BIG_CAP 4
 #define HS_OVERSUB 128u   // oversubscription of the statically strided persistent grids (step at B = 128: x 1 / 32 / 128 / 256 / 2048: 443 / 438 / 433 / 434 / 447 ms)
-#define HS_NSLOT 3   // patch buffer slots of the group pipeline
 // The HIP streams a context runs on (four compute streams, two copy streams).  They are created once per device and handed from a
 // destroyed context to the next one (capi_impl.h): which hardware queues a NEW stream shares depends on everything the process has
 // created before, so only reuse keeps the queue pairing of the first context.  Contexts alive at the same time get sets of their own.
@@ -238,10 +238,11 @@ struct StreamSet {
    hipStream_t comp[4] = {nullptr, nullptr, nullptr, nullptr};
    hipStream_t h2d = nullptr, d2h = nullptr;   // made when the first chunk needs them (ensure_copy_streams, capi_impl.h)
    static constexpr int group[7] = {0, 1, 1, 2, 0, 3, 2};   // logical stream -> HIP stream: 0 main, 1-4 patch bins 0-3, 5 descriptor, 6 affine
-   hipStream_t main() const { return comp[group[0]]; }
-   hipStream_t bin(int i) const { return comp[group[1 + i]]; }   // side stream of the patch stage's window-size bin i (0..3)
-   hipStream_t sift() const { return comp[group[5]]; }           // descriptor kernels of every image group
-   hipStream_t affine() const { return comp[group[6]]; }         // affine shape of image group g+1 runs beside the patch extraction of group g
+   hipStream_t of(int logical) const { return comp[group[logical]]; }   // (the numbers are sched::Stream's, group_schedule.h)
+   hipStream_t main() const { return of(0); }
+   hipStream_t bin(int i) const { return of(1 + i); }   // side stream of the patch stage's window-size bin i (0..3)
+   hipStream_t sift() const { return of(5); }           // descriptor kernels of every image group
+   hipStream_t affine() const { return of(6); }         // affine shape of image group g+1 runs beside the patch extraction of group g
 };
 static std::mutex g_sets_mu;
 static std::map<int, std::vector<StreamSet>> g_idle_sets;   // per device: the sets no context is using
@@ -423,7 +424,7 @@ struct hesaff_ctx {
    int keypoint_limit = 0;             // hesaff_set_keypoint_limit: 0 no limit, N >= 1 the N strongest Hessian keypoints of every image (run_batch)
    int stage_threads = 4;              // host threads that copy a chunk's pixels into pinned memory (hesaff_process_files: within its thread budget)
    DevEvent ev_detect_done, ev_batch_done;   // blocking-sync events: the host sleeps instead of spinning
-   std::vector<DevEvent> ev_aff;             // one per image group, grown on demand
+   std::vector<DevEvent> ev_aff;             // one per image group, grown on demand (GroupDevice)
    DevEvent ev_extract_done[HS_NSLOT], ev_sift_done[HS_NSLOT];
    DevBuf b_patches2[HS_NSLOT];
    DevBuf b_meanvar2, b_siftvo2;   // the descriptor stage's intermediates: one copy (ensure_group_buffers)
@@ -432,7 +433,7 @@ struct hesaff_ctx {
    // off in the product build; the tuning build (-DHESAFF_TUNING) reads them from the environment, and HESAFF_FAST for fast_pyramid
    bool no_overlap = false;        // HESAFF_OVERLAP=0: every kernel alone on the device (per-kernel profiling)
    bool debug = false;             // HESAFF_DEBUG=1: launch geometry on stderr
-   bool sift_inside = false;       // HESAFF_SIFT_INSIDE=1: a group's descriptor kernels submitted inside the next group's patch stage (run_keypoint_stages)
+   bool sift_inside = false;       // HESAFF_SIFT_INSIDE=1: a group's descriptor kernels submitted inside the next group's patch stage (group_schedule.h)
 
    std::vector<DevEvent> ev_pool;   // timing events of the stage timers (get_event)
    size_t ev_used = 0;
@@ -728,14 +729,36 @@ Lists make_lists(hesaff_ctx *c)
    return s;
 }
 
+// group_schedule.h's wait / record on a context: the logical streams through the pairing table, the events by name.  Every
+// hipStreamWaitEvent and hipEventRecord of the keypoint stages is issued here (the stage timers' and the host round trips' apart).
+struct ScheduleDevice {
+   hesaff_ctx *c;
+   hipStream_t stream(sched::Stream s) const { return c->sset.of(s); }
+   hipEvent_t event(const sched::Event &e) const
+   {
+      switch (e.kind) {
+         case sched::Event::DETECT_DONE: return c->ev_detect_done;
+         case sched::Event::AFFINE_DONE: return c->ev_aff[e.index];
+         case sched::Event::EXTRACT_DONE: return c->ev_extract_done[e.index];
+         case sched::Event::SIFT_DONE: return c->ev_sift_done[e.index];
+         case sched::Event::FORK: return c->ev_fork;
+         case sched::Event::JOIN: return c->ev_join[e.index];
+      }
+      return nullptr;
+   }
+   void wait(sched::Stream s, const sched::Event &e) { HIP_TRY(hipStreamWaitEvent(stream(s), event(e), 0)); }
+   void record(const sched::Event &e, sched::Stream s) { HIP_TRY(hipEventRecord(event(e), stream(s))); }
+};
+
 // normalizeAffine for every keypoint k_prepare_patch left alive and binned.  Every launch is a persistent grid of
 // fixed size that reads its work-list length from the device-side bin counters: the host never waits for them.
 // large_rows_bound: upper bound of the large bin's T' rows in this group (from k_image_large_rows).
-// Two halves: launch_patch_stage enqueues every kernel and returns how many side streams the main stream has to take back
-// (0: none were used); join_patch_stage records their ends and makes the main stream wait for them.  What a caller enqueues between
-// the two halves stands, on a hardware queue the main stream shares, in front of that wait and not behind it (run_keypoint_stages).
-int launch_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float *patches_out, uint32_t h_base, uint32_t large_rows_bound,
-                       const PlaneTab *pt = nullptr)
+// n_side: the side streams the caller has forked (fork_side_streams / join_side_streams, group_schedule.h; patch_side_streams says
+// how many a context uses); bin i's kernel runs on patch_stream(i, n_side).
+int patch_side_streams(const hesaff_ctx *c, const PlaneTab *pt) { return c->no_overlap ? 0 : (c->fast_pyramid && pt) ? 1 : HS_NSIDE; }
+
+void launch_patch_kernels(hesaff_ctx *c, const Lists &s, const DPlane &image, float *patches_out, uint32_t h_base, uint32_t large_rows_bound,
+                          const PlaneTab *pt, int n_side)
 {
    hipStream_t st = c->stream();
    PatchIO io;
@@ -743,37 +766,25 @@ int launch_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float
    io.image = image;
    io.patches = patches_out;
    io.h_base = h_base;
-   if (c->fast_pyramid && pt) {
-      // hesaff_params.fast = 2: bin 0 (P <= 41) on the parity kernel, every larger window from the pyramid (k_patch_pyramid)
-      hipStream_t s0 = st;
-      const bool forked = !c->no_overlap;
-      if (forked) {
-         HIP_TRY(hipEventRecord(c->ev_fork, st));
-         HIP_TRY(hipStreamWaitEvent(c->sset.bin(0), c->ev_fork, 0));
-         s0 = c->sset.bin(0);
-      }
-      hipLaunchKernelGGL(k_patch_extract_small<0>, dim3(c->g_small0), dim3(256), small_extract_lds_bytes(0), s0, s.hl, s.pw, io, c->tables.view);
-      hipLaunchKernelGGL(k_patch_pyramid, dim3((uint32_t)c->n_cu * 32u), dim3(256), 0, st, s.hl, s.pw, io, *pt, (int)c->oct.size(), c->ct.consts.pd0, 1);
-      return forked ? 1 : 0;
-   }
    // The bins are independent (disjoint keypoints) and each kernel leaves CU resources idle
    // (LDS- or latency-bound), so they run concurrently on side streams.
-   hipStream_t s0 = st, s1 = st, s2 = st, s3 = st;
-   const bool forked = !c->no_overlap;
-   if (forked) {
-      HIP_TRY(hipEventRecord(c->ev_fork, st));
-      for (int i = 0; i < HS_NSIDE; i++) HIP_TRY(hipStreamWaitEvent(c->sset.bin(i), c->ev_fork, 0));
-      s0 = c->sset.bin(0); s1 = c->sset.bin(1); s2 = c->sset.bin(2); s3 = c->sset.bin(3);
+   hipStream_t sb[HS_NSIDE];
+   for (int i = 0; i < HS_NSIDE; i++) sb[i] = c->sset.of(sched::patch_stream(i, n_side));
+   if (c->fast_pyramid && pt) {
+      // hesaff_params.fast = 2: bin 0 (P <= 41) on the parity kernel, every larger window from the pyramid (k_patch_pyramid)
+      hipLaunchKernelGGL(k_patch_extract_small<0>, dim3(c->g_small0), dim3(256), small_extract_lds_bytes(0), sb[0], s.hl, s.pw, io, c->tables.view);
+      hipLaunchKernelGGL(k_patch_pyramid, dim3((uint32_t)c->n_cu * 32u), dim3(256), 0, st, s.hl, s.pw, io, *pt, (int)c->oct.size(), c->ct.consts.pd0, 1);
+      return;
    }
    {
       PatchIO io2 = io;
       io2.trows = c->b_trows2.as<float>();
       PatchIO io3 = io;
       io3.trows = c->b_trows3.as<float>();
-      hipLaunchKernelGGL(k_patch_extract_small<0>, dim3(c->g_small0), dim3(256), small_extract_lds_bytes(0), s0, s.hl, s.pw, io, c->tables.view);
-      hipLaunchKernelGGL(k_patch_extract_small<1>, dim3(c->g_small1), dim3(256), small_extract_lds_bytes(1), s1, s.hl, s.pw, io, c->tables.view);
-      hipLaunchKernelGGL(k_patch_mid<HS_MID_PMAX>, dim3(c->g_mid), dim3(256), mid_lds_bytes(), s2, s.hl, s.pw, io2, c->tables.view);
-      hipLaunchKernelGGL(k_patch_mid<HS_BIN3_PMAX>, dim3(c->g_big), dim3(256), big_lds_bytes(), s3, s.hl, s.pw, io3, c->tables.view);
+      hipLaunchKernelGGL(k_patch_extract_small<0>, dim3(c->g_small0), dim3(256), small_extract_lds_bytes(0), sb[0], s.hl, s.pw, io, c->tables.view);
+      hipLaunchKernelGGL(k_patch_extract_small<1>, dim3(c->g_small1), dim3(256), small_extract_lds_bytes(1), sb[1], s.hl, s.pw, io, c->tables.view);
+      hipLaunchKernelGGL(k_patch_mid<HS_MID_PMAX>, dim3(c->g_mid), dim3(256), mid_lds_bytes(), sb[2], s.hl, s.pw, io2, c->tables.view);
+      hipLaunchKernelGGL(k_patch_mid<HS_BIN3_PMAX>, dim3(c->g_big), dim3(256), big_lds_bytes(), sb[3], s.hl, s.pw, io3, c->tables.view);
    }
    // the rare huge windows (P > 512): row tasks over all of them, then one block per keypoint, on the main stream, which shares its HIP
    // stream (= hardware queue) with bin 3.  That queue is the stage's longest on photographs (8.1 + 8.8 + 1.9 ms per 32 photograph mosaics
@@ -797,19 +808,16 @@ int launch_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float
       }
       hipLaunchKernelGGL(k_patch_large_finish, dim3(c->g_lfin), dim3(256), 0, st, s.pw, io, c->tables.view);
    }
-   return forked ? HS_NSIDE : 0;
 }
 
-void join_patch_stage(hesaff_ctx *c, int n_side)
+// the patch stage on its own (hesaff_stage_normalize_affine): no plane table, so never fast mode 2's kernels
+void run_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float *patches_out, uint32_t h_base, uint32_t large_rows_bound)
 {
-   for (int i = 0; i < n_side; i++) HIP_TRY(hipEventRecord(c->ev_join[i], c->sset.bin(i)));
-   for (int i = 0; i < n_side; i++) HIP_TRY(hipStreamWaitEvent(c->stream(), c->ev_join[i], 0));
-}
-
-void run_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float *patches_out, uint32_t h_base, uint32_t large_rows_bound,
-                     const PlaneTab *pt = nullptr)
-{
-   join_patch_stage(c, launch_patch_stage(c, s, image, patches_out, h_base, large_rows_bound, pt));
+   ScheduleDevice dev{c};
+   const int n_side = patch_side_streams(c, nullptr);
+   sched::fork_side_streams(dev, 0, n_side);
+   launch_patch_kernels(c, s, image, patches_out, h_base, large_rows_bound, nullptr, n_side);
+   sched::join_side_streams(dev, 0, n_side);
 }
 
 // per image: upper bound of the T' rows its huge windows (P > 512) need, known from the scales alone
@@ -1080,9 +1088,57 @@ struct BatchResult {
    const int32_t *d_desc_starts;
 };
 
+// run_group_schedule's device (group_schedule.h): the launches of the keypoint stages of one batch, each with its timer bracket, on
+// the stream the schedule names.  The order, the waits and the slots are the schedule's; nothing here decides any of them.
+struct GroupDevice : ScheduleDevice {
+   const Lists &s;
+   StageTimer &tm;
+   const std::vector<ImageGroup> &groups;
+   const PlaneTab &pt;
+   int H, W;
+   int t_patch = -1;
+   GroupDevice(hesaff_ctx *ctx, const Lists &s_, StageTimer &tm_, const std::vector<ImageGroup> &groups_, const PlaneTab &pt_, int H_, int W_)
+      : ScheduleDevice{ctx}, s(s_), tm(tm_), groups(groups_), pt(pt_), H(H_), W(W_)
+   {
+      while (c->ev_aff.size() < groups.size()) c->ev_aff.emplace_back(hipEventDisableTiming);
+   }
+   void affine(int g, sched::Stream as)
+   {
+      const int ta = tm.begin(T_AFF, 0, stream(as));
+      const uint32_t agrid = std::min<uint32_t>((groups[g].hi - groups[g].lo + HS_AFFP_G - 1) / HS_AFFP_G, (uint32_t)c->n_cu * HS_AFF_BLOCKS_PER_CU);
+      hipLaunchKernelGGL(k_affine, dim3(agrid), dim3(64), 0, stream(as), pt, s.hl, groups[g].lo, groups[g].hi, (const uint32_t *)&s.counters->head.hess_total,
+                         c->tables.view, c->ct.consts, s.ao);
+      tm.end(ta);
+   }
+   void patch_prepare(int g)
+   {
+      hipStream_t st = c->stream();
+      t_patch = tm.begin(T_PATCH);
+      HIP_TRY(hipMemsetAsync(s.counters->bin_count, 0, CounterBlock::bins_bytes(), st));   // bin counts and work counters
+      // (the group's end travels as a kernel argument: a 4-byte copy from pageable memory would make the host wait
+      //  here until the stream has drained, once per group)
+      hipLaunchKernelGGL(k_prepare_patch, dim3(1024), dim3(256), 0, st, s.hl, groups[g].lo, groups[g].hi, (const uint32_t *)&s.counters->head.hess_total, s.ao, H, W,
+                         c->ct.consts, c->tables.view, s.pw);
+   }
+   void patch_kernels(int g, int slot, int n_side)
+   {
+      launch_patch_kernels(c, s, c->gray, c->b_patches2[slot].as<float>(), groups[g].lo, groups[g].large_rows, &pt, n_side);
+   }
+   void patch_done(int) { tm.end(t_patch); }
+   void descriptors(int g, int slot, sched::Stream ss)
+   {
+      SiftIO so;
+      so.patches = c->b_patches2[slot].as<float>(); so.alive = s.pw.alive; so.meanvar = c->b_meanvar2.as<float>();
+      so.vec = nullptr; so.desc = c->geo.b_desc.as<uint8_t>(); so.h_lo = groups[g].lo; so.h_hi = groups[g].hi;
+      const int ts = tm.begin(T_SIFT, 0, stream(ss));
+      launch_sift(c, stream(ss), so, groups[g].hi - groups[g].lo, c->b_siftvo2.as<float2>());
+      tm.end(ts);
+   }
+};
+
 // Everything after the Hessian list of a batch is complete - by detection (run_batch) or from the caller's records (run_describe):
-// affine shape, patches and descriptors over image groups on three streams, the stable compaction into KeyRec records, the
-// descriptor starts, and the wait for the end of the batch.  hs: fetch_hessian_starts' block.  with_affine = false: the affine
+// affine shape, patches and descriptors over image groups in the order of group_schedule.h, the stable compaction into KeyRec records,
+// the descriptor starts, and the wait for the end of the batch.  hs: fetch_hessian_starts' block.  with_affine = false: the affine
 // output is already in place (HESAFF_FROM_SHAPES), k_affine is not launched.  The affine stream starts behind ev_detect_done,
 // which the caller has recorded after the last kernel that writes a plane k_affine reads.
 BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, int tt, int B, int H, int W, const int32_t *hs, bool with_affine)
@@ -1104,69 +1160,9 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
       c->batch_max_p = (int)*hb.largest_window();   // largest huge window of the batch (0: none)
       // image groups [lo, hi) of keypoints; the T' rows of a group's huge windows fit the row buffer (form_groups, batch_plan.h)
       const GroupPlan gp = form_groups(hs, hb.large_rows(), B, c->trows_rows);
-      const std::vector<ImageGroup> &groups = gp.groups;
-      while (c->ev_aff.size() < groups.size()) c->ev_aff.emplace_back(hipEventDisableTiming);
+      GroupDevice dev(c, s, tm, gp.groups, pt, H, W);
       if (gp.max_n) ensure_group_buffers(c, gp.max_n);
-      // Software pipeline over image groups, one stream per stage:
-      //   affine shape of group g+1 (sset.affine())  |  patch extraction of group g (main + side
-      //   streams, latency-bound)  |  descriptor kernels of the groups before (sset.sift()).
-      // Three patch buffer slots rotate: a slot is written again only when the descriptors of the group three back are finished.
-      hipStream_t as = c->no_overlap ? st : c->sset.affine();
-      if (as != st && with_affine) HIP_TRY(hipStreamWaitEvent(as, c->ev_detect_done, 0));
-      auto launch_affine = [&](size_t gi) {
-         if (!with_affine) return;
-         const int ta = tm.begin(T_AFF, 0, as);
-         const uint32_t agrid = std::min<uint32_t>((groups[gi].hi - groups[gi].lo + HS_AFFP_G - 1) / HS_AFFP_G, (uint32_t)c->n_cu * HS_AFF_BLOCKS_PER_CU);
-         hipLaunchKernelGGL(k_affine, dim3(agrid), dim3(64), 0, as, pt, s.hl, groups[gi].lo, groups[gi].hi, (const uint32_t *)&cnt->head.hess_total, c->tables.view, c->ct.consts, s.ao);
-         tm.end(ta);
-         if (as != st) HIP_TRY(hipEventRecord(c->ev_aff[gi], as));
-      };
-      if (!groups.empty()) launch_affine(0);
-      bool slot_used[HS_NSLOT] = {};
-      hipStream_t ss = c->no_overlap ? st : c->sset.sift();
-      // the descriptor kernels of group gi, behind its patches
-      auto launch_descriptors = [&](size_t gi) {
-         const int slot = (int)(gi % HS_NSLOT);
-         if (ss != st) HIP_TRY(hipStreamWaitEvent(ss, c->ev_extract_done[slot], 0));
-         SiftIO so;
-         so.patches = c->b_patches2[slot].as<float>(); so.alive = s.pw.alive; so.meanvar = c->b_meanvar2.as<float>();
-         so.vec = nullptr; so.desc = c->geo.b_desc.as<uint8_t>(); so.h_lo = groups[gi].lo; so.h_hi = groups[gi].hi;
-         const int ts = tm.begin(T_SIFT, 0, ss);
-         launch_sift(c, ss, so, groups[gi].hi - groups[gi].lo, c->b_siftvo2.as<float2>());
-         tm.end(ts);
-         HIP_TRY(hipEventRecord(c->ev_sift_done[slot], ss));
-      };
-      // Order of submission.  The runtime multiplexes the HIP streams of one priority onto its few hardware queues, and a process that
-      // has streams of its own (under PyTorch: two of the four queues) leaves this context's four streams two queues, the descriptor
-      // stream on the one the main stream uses.  A hardware queue runs its packets in the order they were submitted, whichever stream
-      // they came through, so a group's descriptor kernels, submitted behind its patch stage, stand in front of the next group's
-      // k_prepare_patch: there the two stages take turns (profiles/r07_notes.md).  sift_inside (tuning build) submits the descriptor
-      // kernels of group g - 1 in the MIDDLE of group g's patch stage instead - behind its kernels and in front of the main stream's
-      // wait for the side streams - so that the other queue's bins run beside the descriptor chain.  They do, and each runs that much
-      // slower: the dense step measured 0.8 % slower that way, the photograph step 2 % faster, so the order stays.
-      for (size_t gi = 0; gi < groups.size(); gi++) {
-         const uint32_t h_lo = groups[gi].lo, h_hi = groups[gi].hi;
-         if (gi + 1 < groups.size()) launch_affine(gi + 1);
-         if (as != st && with_affine) HIP_TRY(hipStreamWaitEvent(st, c->ev_aff[gi], 0));
-         const int slot = (int)(gi % HS_NSLOT);
-         if (slot_used[slot]) HIP_TRY(hipStreamWaitEvent(st, c->ev_sift_done[slot], 0));   // the slot's previous descriptors are finished
-         t = tm.begin(T_PATCH);
-         HIP_TRY(hipMemsetAsync(cnt->bin_count, 0, CounterBlock::bins_bytes(), st));   // bin counts and work counters
-         // (the group's end travels as a kernel argument: a 4-byte copy from pageable memory would make the host wait
-         //  here until the stream has drained, once per group)
-         hipLaunchKernelGGL(k_prepare_patch, dim3(1024), dim3(256), 0, st, s.hl, h_lo, h_hi, (const uint32_t *)&cnt->head.hess_total, s.ao, H, W, c->ct.consts,
-                            c->tables.view, s.pw);
-         const int n_side = launch_patch_stage(c, s, c->gray, c->b_patches2[slot].as<float>(), h_lo, groups[gi].large_rows, &pt);
-         if (gi > 0 && c->sift_inside) launch_descriptors(gi - 1);
-         join_patch_stage(c, n_side);
-         tm.end(t);
-         HIP_TRY(hipEventRecord(c->ev_extract_done[slot], st));
-         slot_used[slot] = true;
-         if (!c->sift_inside) launch_descriptors(gi);
-      }
-      if (!groups.empty() && c->sift_inside) launch_descriptors(groups.size() - 1);
-      for (int sl = 0; sl < HS_NSLOT; sl++)
-         if (slot_used[sl]) HIP_TRY(hipStreamWaitEvent(st, c->ev_sift_done[sl], 0));
+      sched::run_group_schedule(dev, (int)gp.groups.size(), {!c->no_overlap, c->sift_inside, with_affine, patch_side_streams(c, &pt)});
    }
    t = tm.begin(T_PACK);
    // final stable compaction (hesaff.cpp:87: keys.push_back in detection order): exclusive scan of the alive flags of the batch's

@@ -17,6 +17,8 @@
 #define HS_NBINS 5   // window size P: 0: <=41, 1: <=64 (full blur in LDS); 2: <=128 (row-streamed, LDS); 3: <=512, 4: larger (row-streamed, HBM)
 #define HS_BIN3_PMAX 512
 #define HS_NEED 82          // blurred columns (and rows) the 41x41 resample reads: 2 per output
+#define HS_NSIDE 4          // side streams of the patch stage (one per window-size bin 0..3)
+#define HS_NSLOT 3          // patch buffer slots of the group pipeline (group_schedule.h)
 #define HS_LARGE_CHUNK 18   // consecutive window rows per wavefront task of k_patch_large_rows (a multiple of three: its three-row form)
 
 // The gradient pairs of a keypoint in HBM (written once by k_sift_grad, read by k_sift_hist: the largest stream of the descriptor stage, and

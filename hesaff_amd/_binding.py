@@ -170,6 +170,10 @@ def load_library():
     L.hesaff_set_pool_priority.argtypes = [vp, C.c_int]
     L.hesaff_set_keypoint_limit.argtypes = [vp, C.c_int]
     L.hesaff_get_keypoint_limit.argtypes = [vp, C.POINTER(C.c_int)]
+    # per-image detection masks for the next detecting call (found by name, like hesaff_describe_regions)
+    if hasattr(L, "hesaff_set_next_masks"):
+        L.hesaff_set_next_masks.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+        L.hesaff_set_next_masks_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64]
     L.hesaff_stage_threads_for_pool.argtypes = [C.c_int]
     L.hesaff_detect_batch_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, _i32p, _i32p, C.POINTER(vp), C.POINTER(C.c_int64)]
     # float grey planes (CV_32FC1, pyramid.h:73): the twins above with float images
@@ -256,7 +260,7 @@ ABI_SYMBOLS = [
     "hesaff_stage_threads_for_pool", "hesaff_read_bmp", "hesaff_read_tiff", "hesaff_detect_regions", "hesaff_sizeof_region",
     "hesaff_detect_batch_f32", "hesaff_detect_batch_cb_f32", "hesaff_detect_regions_f32", "hesaff_detect_batch_device_f32",
     "hesaff_stage_pyramid_f32", "hesaff_describe_regions", "hesaff_describe_regions_f32",
-    "hesaff_set_keypoint_limit", "hesaff_get_keypoint_limit",
+    "hesaff_set_keypoint_limit", "hesaff_get_keypoint_limit", "hesaff_set_next_masks", "hesaff_set_next_masks_device",
 ]
 
 # hesaff_describe_regions' `from`: which of the reference's two public callback members each record enters the chain through
@@ -447,19 +451,51 @@ class HesaffContext:
             raise HesaffError(rc, self.L.hesaff_last_error(self.h).decode())
 
     # ---- whole path ----
-    def detect_batch(self, images):
-        """images: list of uint8 arrays HxW (grey) or HxWx3.  -> list of (count_hessian, keys[KEYPOINT_DTYPE])."""
+    def _arm_masks(self, masks, imgs):
+        """hesaff_set_next_masks for the call that follows: masks is None (nothing armed) or a list with, per image, None or an H x W
+        uint8 / bool array (non-zero: detect here; any positive row stride with unit pixel stride is passed as it is).  -> the arrays,
+        which the caller keeps alive across the detecting call: the library copies the pointers, not the pixels."""
+        if masks is None:
+            return None
+        if len(masks) != len(imgs):
+            raise ValueError("masks: one entry (an array or None) per image (%d images, %d masks)" % (len(imgs), len(masks)))
+        keep = []
+        for i, (m, im) in enumerate(zip(masks, imgs)):
+            if m is None:
+                keep.append(None)
+                continue
+            m = np.asarray(m)
+            if m.dtype == np.bool_:
+                m = m.view(np.uint8)
+            if m.dtype != np.uint8 or m.ndim != 2 or m.shape != tuple(im.shape[:2]):
+                raise ValueError("mask %d: an H x W uint8 or bool array of the image's size %s is expected, got %s %s"
+                                 % (i, tuple(im.shape[:2]), m.dtype, m.shape))
+            if (m.shape[1] > 1 and m.strides[1] != 1) or (m.shape[0] > 1 and m.strides[0] < m.shape[1]):
+                m = np.ascontiguousarray(m)
+            keep.append(m)
+        n = len(keep)
+        ptrs = (C.c_void_p * n)(*[None if m is None else m.ctypes.data for m in keep])
+        st = (C.c_int * n)(*[0 if m is None else (m.strides[0] if m.shape[0] > 1 else m.shape[1]) for m in keep])
+        self._check(self.L.hesaff_set_next_masks(self.h, n, ptrs, st))
+        return keep
+
+    def detect_batch(self, images, masks=None):
+        """images: list of uint8 arrays HxW (grey) or HxWx3.  -> list of (count_hessian, keys[KEYPOINT_DTYPE]).
+        masks (here and in the other detect_* methods): per-image detection masks for this call (hesaff_set_next_masks): a list
+        with, per image, None or an H x W uint8 / bool array; keypoints whose pixel is zero are dropped on the device."""
         imgs, n, ptrs, ws, hs, st, chs = self._u8_list(images)
+        keep = self._arm_masks(masks, imgs)  # noqa: F841  (alive until the call has returned)
         res = (_Result * n)()
         self._check(self.L.hesaff_detect_batch(self.h, n, ptrs, ws, hs, st, chs, res))
         # one copy out of the library-owned (pinned) result buffer, valid until the next call
         return [(r.count_hessian, self._keys_at(r.keys, r.count_desc)) for r in res]
 
-    def detect_regions(self, images):
+    def detect_regions(self, images, masks=None):
         """hesaff_detect_regions: images as for detect_batch.  -> list of (regions[REGION_DTYPE], keys[KEYPOINT_DTYPE]) per image:
         one record per Hessian keypoint in the reference's callback order (pyramid.h:43-47, affine.h:48-58), and the same keys as
         detect_batch.  regions[i]["key"] is the row of keys that keypoint became (-1 when it got no descriptor)."""
         imgs, n, ptrs, ws, hs, st, chs = self._u8_list(images)
+        keep = self._arm_masks(masks, imgs)  # noqa: F841
         res = (_RegionResult * n)()
         self._check(self.L.hesaff_detect_regions(self.h, n, ptrs, ws, hs, st, chs, res))
         # copies out of the library-owned (pinned) result buffer, valid until the next call
@@ -526,31 +562,42 @@ class HesaffContext:
         st = (C.c_int * n)(*[im.strides[0] for im in imgs])
         return imgs, ptrs, ws, hs, st
 
-    def detect_batch_f32(self, images):
+    def detect_batch_f32(self, images, masks=None):
         """hesaff_detect_batch_f32: 2-D float32 grey planes (padded rows allowed) -> list of (count_hessian, keys[KEYPOINT_DTYPE])."""
         imgs, ptrs, ws, hs, st = self._f32_list(images)
+        keep = self._arm_masks(masks, imgs)  # noqa: F841
         res = (_Result * len(imgs))()
         self._check(self.L.hesaff_detect_batch_f32(self.h, len(imgs), ptrs, ws, hs, st, res))
         return [(r.count_hessian, self._keys_at(r.keys, r.count_desc)) for r in res]
 
-    def detect_regions_f32(self, images):
+    def detect_regions_f32(self, images, masks=None):
         """hesaff_detect_regions_f32: detect_regions for 2-D float32 grey planes."""
         imgs, ptrs, ws, hs, st = self._f32_list(images)
+        keep = self._arm_masks(masks, imgs)  # noqa: F841
         res = (_RegionResult * len(imgs))()
         self._check(self.L.hesaff_detect_regions_f32(self.h, len(imgs), ptrs, ws, hs, st, res))
         return [(self._regions_at(r.regions, r.count_hessian), self._keys_at(r.keys, r.count_desc)) for r in res]
 
-    def detect_batch_cb_f32(self, images, sink):
+    def detect_batch_cb_f32(self, images, sink, masks=None):
         """hesaff_detect_batch_cb_f32: detect_batch_cb for 2-D float32 grey planes."""
         imgs, ptrs, ws, hs, st = self._f32_list(images)
-
+        keep = self._arm_masks(masks, imgs)  # noqa: F841
         self._check(self.L.hesaff_detect_batch_cb_f32(self.h, len(imgs), ptrs, ws, hs, st, self._chunk_sink(sink), None))
 
-    def detect_batch_device_f32(self, t):
+    def set_next_masks_device(self, masks_ptr, n, row_stride=0, img_stride=0):
+        """hesaff_set_next_masks_device: n mask planes in device memory (raw device pointer) for the next device-resident call;
+        strides in bytes, 0 = tightly packed.  masks_ptr None or n = 0 disarms."""
+        if masks_ptr is None:
+            n = 0
+        self._check(self.L.hesaff_set_next_masks_device(self.h, int(n), C.c_void_p(masks_ptr), int(row_stride), int(img_stride)))
+
+    def detect_batch_device_f32(self, t, masks_ptr=None, mask_row_stride=0, mask_img_stride=0):
         """hesaff_detect_batch_device_f32 on a torch tensor on this context's device: float32, [n, H, W] or [H, W], unit stride
         along W, any positive row and image stride.  A tensor that repeats images or rows through a zero stride (expand, broadcast)
         is made contiguous first: the C entry point reads a stride of 0 as "tightly packed".  torch's current stream on that device
-        is synchronised before the call.  -> (count_hessian[n], count_desc[n], d_keys, total) as detect_batch_device returns them."""
+        is synchronised before the call.  masks_ptr: n uint8 mask planes [n, H, W] in device memory (raw device pointer, complete
+        before the call; strides in bytes, 0 = tightly packed), armed for this call.
+        -> (count_hessian[n], count_desc[n], d_keys, total) as detect_batch_device returns them."""
         import torch
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() not in (2, 3):
             raise TypeError("detect_batch_device_f32 takes a float32 torch tensor [n, H, W] or [H, W]")
@@ -573,6 +620,8 @@ class HesaffContext:
             row = 0   # (the stride of a single row is never used: tightly packed)
         if n == 1:
             img = 0
+        if masks_ptr is not None:
+            self.set_next_masks_device(masks_ptr, n, mask_row_stride, mask_img_stride)
         self._check(self.L.hesaff_detect_batch_device_f32(self.h, n, C.c_void_p(t.data_ptr()), W, H, row, img, ch, cd, C.byref(dk),
                                                           C.byref(tot)))
         return ch, cd, dk.value, tot.value
@@ -614,10 +663,11 @@ class HesaffContext:
         self._check(self.L.hesaff_detect_batch(self.h, n, ptrs, ws, hs, st, chs, res))
         return res
 
-    def detect_batch_cb(self, images, sink):
+    def detect_batch_cb(self, images, sink, masks=None):
         """hesaff_detect_batch_cb: sink(image_indices, [(count_hessian, keys copy), ...]) is called once per chunk with
         records that are valid only during the call (bounded pinned memory); a truthy return value stops the run."""
         imgs, n, ptrs, ws, hs, st, chs = self._u8_list(images)
+        keep = self._arm_masks(masks, imgs)  # noqa: F841
         self._check(self.L.hesaff_detect_batch_cb(self.h, n, ptrs, ws, hs, st, chs, self._chunk_sink(sink), None))
 
     def set_output_format(self, fmt):
@@ -673,8 +723,11 @@ class HesaffContext:
         if rc != 0:
             raise HesaffError(rc, "hesaff_write_sift_batch")
 
-    def detect_batch_device(self, d_ptr, n, width, height):
-        """Inputs resident in HBM (uint8 [n,H,W], raw device pointer).  -> (count_hessian[n], count_desc[n], d_keys, total)."""
+    def detect_batch_device(self, d_ptr, n, width, height, masks_ptr=None, mask_row_stride=0, mask_img_stride=0):
+        """Inputs resident in HBM (uint8 [n,H,W], raw device pointer).  -> (count_hessian[n], count_desc[n], d_keys, total).
+        masks_ptr: n uint8 mask planes in device memory (raw device pointer; strides in bytes, 0 = tightly packed) for this call."""
+        if masks_ptr is not None:
+            self.set_next_masks_device(masks_ptr, n, mask_row_stride, mask_img_stride)
         ch = np.zeros(n, np.int32); cd = np.zeros(n, np.int32)
         dk = C.c_void_p(); tot = C.c_int64()
         self._check(self.L.hesaff_detect_batch_device(self.h, n, C.c_void_p(d_ptr), width, height, ch, cd, C.byref(dk), C.byref(tot)))

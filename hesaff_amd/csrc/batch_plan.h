@@ -158,6 +158,10 @@ template <class T> inline StartsBlock<T> starts_block(T *base, int B) { return S
 // hesaff_describe_regions: a chunk's block is B + 1 record starts, then - this many bytes in - its hesaff_region records
 inline size_t describe_records_offset(int B) { return (((size_t)B + 1) * 4 + 255) & ~(size_t)255; }
 
+// hesaff_set_next_masks: a chunk's block is B "present" bytes (0: image b has no mask), then - this many bytes in - B tight H x W planes
+inline size_t mask_planes_offset(int B) { return ((size_t)B + 255) & ~(size_t)255; }
+inline size_t mask_block_bytes(int B, int H, int W) { return mask_planes_offset(B) + (size_t)B * (size_t)H * (size_t)W; }
+
 // ---- image groups ----
 // Images are processed in groups [lo, hi) of Hessian keypoints so that the patch buffers stay bounded: about 16 groups per batch keep
 // the three-stage pipeline full, between 300 k (launch overheads) and 1.2 M keypoints (buffer size).

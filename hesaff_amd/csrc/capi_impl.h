@@ -53,13 +53,47 @@ void begin_device_batch(hesaff_ctx *c, int n)
    if (n > c->par.max_batch) throw HsError(HESAFF_ERR_ARG, "n exceeds hesaff_params.max_batch for the device-resident entry point");
 }
 
+// hesaff_set_next_masks*: what is armed leaves the context with the call that meets it, whatever that call then returns
+ArmedMasks take_masks(hesaff_ctx *c)
+{
+   ArmedMasks am;
+   if (c) std::swap(am, c->next_masks);
+   return am;
+}
+
+// a call that takes no masks met armed ones
+void refuse_masks(const ArmedMasks &am, const char *why)
+{
+   if (am.kind != ArmedMasks::NONE) throw HsError(HESAFF_ERR_ARG, std::string("detection masks are armed (hesaff_set_next_masks), but ") + why + "; the masks are cleared");
+}
+
+// the masks of a device-resident call: n planes of height x width bytes in device memory
+SelMasks device_masks(const ArmedMasks &am, int n, int height, int width)
+{
+   SelMasks mk;
+   if (am.kind == ArmedMasks::NONE) return mk;
+   if (am.kind != ArmedMasks::DEVICE) throw HsError(HESAFF_ERR_ARG, "masks armed with hesaff_set_next_masks (host memory) met a device-resident call; the masks are cleared");
+   char msg[160];
+   if (am.n != n) {
+      snprintf(msg, sizeof msg, "%d masks armed for a call with %d images; the masks are cleared", am.n, n);
+      throw HsError(HESAFF_ERR_ARG, msg);
+   }
+   const long long rs = am.row_stride ? am.row_stride : width;
+   const long long is = am.img_stride ? (long long)am.img_stride : rs * height;
+   if (rs < width) throw HsError(HESAFF_ERR_ARG, "row stride of the device masks smaller than the width; the masks are cleared");
+   if (n > 1 && is < rs * (height - 1) + width) throw HsError(HESAFF_ERR_ARG, "image stride of the device masks does not keep the planes apart; the masks are cleared");
+   mk.base = (const uint8_t *)am.d_masks; mk.img_stride = is; mk.row_stride = (int)rs; mk.W = width; mk.H = height;
+   return mk;
+}
+
 template <class CHECK>
 void detect_device(hesaff_ctx *c, int n, const SrcImages &src, int height, int width, int32_t *count_hessian, int32_t *count_desc,
-                   const void **d_keys_out, int64_t *total_out, CHECK check_source)
+                   const void **d_keys_out, int64_t *total_out, CHECK check_source, const ArmedMasks &am)
 {
+   const SelMasks mk = device_masks(am, n, height, width);
    plan(c, c->par.max_batch, height, width);
    check_source();
-   const BatchResult r = run_batch(c, src, n, height, width);
+   const BatchResult r = run_batch(c, src, n, height, width, mk);
    const int32_t *hs = r.hessian_starts, *ds = r.desc_starts;
    for (int b = 0; b < n; b++) {
       if (count_hessian) count_hessian[b] = hs[b + 1] - hs[b];
@@ -219,10 +253,11 @@ int hesaff_get_timings(const hesaff_ctx *c, hesaff_timings *t)
 int hesaff_detect_batch_device(hesaff_ctx *c, int n, const void *d_gray, int width, int height, int32_t *count_hessian,
                                int32_t *count_desc, const void **d_keys_out, int64_t *total_out)
 {
+   const ArmedMasks am = take_masks(c);
    if (!c || n < 1 || !d_gray) return HESAFF_ERR_ARG;
    HS_API_BEGIN
    begin_device_batch(c, n);
-   detect_device(c, n, SrcImages::u8(d_gray, 1, (long long)width * height, width), height, width, count_hessian, count_desc, d_keys_out, total_out, [] {});
+   detect_device(c, n, SrcImages::u8(d_gray, 1, (long long)width * height, width), height, width, count_hessian, count_desc, d_keys_out, total_out, [] {}, am);
    HS_API_END(c)
 }
 
@@ -414,6 +449,14 @@ struct ChunkDevice {
          s.n_rec = (uint32_t)at;
          HIP_TRY(hipMemcpyAsync(sl.b_reg.p, sl.pin_reg.p, bytes, hipMemcpyHostToDevice, c->sset.h2d));
       }
+      if (!q.masks.empty()) {
+         // the chunk's masks travel with it: [present bytes][tight planes] into pinned memory, one copy in beside the pixels
+         const size_t bytes = mask_block_bytes((int)nimg, q.H, q.W);
+         sl.pin_mask.ensure_grow(bytes);
+         sl.b_mask.ensure_grow(bytes);
+         fill_mask_block((uint8_t *)sl.pin_mask.p, mask_planes_offset((int)nimg), q);
+         HIP_TRY(hipMemcpyAsync(sl.b_mask.p, sl.pin_mask.p, bytes, hipMemcpyHostToDevice, c->sset.h2d));
+      }
       HIP_TRY(hipMemcpyAsync(q.blob_bytes ? sl.b_jcoef.p : sl.b_in2.p, sl.pin_in.p, total, hipMemcpyHostToDevice, c->sset.h2d));
       HIP_TRY(hipEventRecord(sl.ev_h2d, c->sset.h2d));
    }
@@ -436,7 +479,12 @@ struct ChunkDevice {
          if (q.blob_bytes) jpeg_pixels(c, sl.b_jcoef.as<uint8_t>(), make_jpeg_geom(q.jpeg), B, (uint8_t *)sl.b_in2.p, img_bytes, c->stream());
          const SrcImages src = q.f32 ? SrcImages::f32(sl.b_in2.p, (long long)img_bytes, (int)row_bytes)
                                      : SrcImages::u8(sl.b_in2.p, q.ch, (long long)img_bytes, (int)row_bytes);
-         res = q.from ? run_describe(c, src, B, q.H, q.W, (const uint8_t *)sl.b_reg.p, s.n_rec, q.from) : run_batch(c, src, B, q.H, q.W);
+         SelMasks mk;
+         if (!q.masks.empty()) {
+            mk.present = (const uint8_t *)sl.b_mask.p; mk.base = mk.present + mask_planes_offset(B);
+            mk.img_stride = (long long)q.H * q.W; mk.row_stride = q.W; mk.W = q.W; mk.H = q.H;
+         }
+         res = q.from ? run_describe(c, src, B, q.H, q.W, (const uint8_t *)sl.b_reg.p, s.n_rec, q.from) : run_batch(c, src, B, q.H, q.W, mk);
       } catch (const HsError &e) {
          if (e.code == HESAFF_ERR_ARG || e.code == HESAFF_ERR_CAPACITY) {
             HIP_TRY(hipEventRecord(sl.ev_in_free, c->stream()));
@@ -613,15 +661,39 @@ void check_device_f32(hesaff_ctx *c, int n, const uint8_t *d, long long img_stri
 // fills in `results`, `region_results` or `sink` + `user` - and run through the chunk engine with `ring` result blocks.
 // images: n pointers to 8-bit images (const uint8_t *const *, with `channels`) or, f32, to float planes (const float *const *).
 struct DescribeInput { const hesaff_region *const *regions = nullptr; const int *counts = nullptr; int from = 0; };
+
+// the armed masks against the images of the host call that takes them -> what ArrayIO deals out with the images
+MaskInput host_masks(const ArmedMasks &am, int n, const int *widths)
+{
+   MaskInput mi;
+   if (am.kind == ArmedMasks::NONE) return mi;
+   if (am.kind != ArmedMasks::HOST) throw HsError(HESAFF_ERR_ARG, "masks armed with hesaff_set_next_masks_device met a host-image call; the masks are cleared");
+   char msg[160];
+   if (am.n != n) {
+      snprintf(msg, sizeof msg, "%d masks armed for a call with %d images; the masks are cleared", am.n, n);
+      throw HsError(HESAFF_ERR_ARG, msg);
+   }
+   if (!am.strides.empty())
+      for (int j = 0; j < n; j++)
+         if (am.masks[(size_t)j] && am.strides[(size_t)j] < widths[j]) {
+            snprintf(msg, sizeof msg, "image %d: row stride of its mask (%d) smaller than the width (%d); the masks are cleared", j, am.strides[(size_t)j], widths[j]);
+            throw HsError(HESAFF_ERR_ARG, msg);
+         }
+   mi.masks = am.masks.data();
+   mi.strides = am.strides.empty() ? nullptr : am.strides.data();
+   return mi;
+}
+
 template <class CONSUMER>
 void detect_images(hesaff_ctx *c, int n, const void *images, bool f32, const int *widths, const int *heights, const int *strides, const int *channels,
-                   int ring, CONSUMER set_consumer, const DescribeInput &di = DescribeInput())
+                   int ring, CONSUMER set_consumer, const ArmedMasks &am, const DescribeInput &di = DescribeInput())
 {
    std::vector<const uint8_t *> planes;
    if (f32) planes = validate_f32_list(n, (const float *const *)images, widths, heights, strides);
    else validate_image_list(n, (const uint8_t *const *)images, widths, heights, strides, channels);
+   const MaskInput mi = host_masks(am, n, widths);
    ArrayIO io(&c->ring, c->par.max_batch, n, f32 ? planes.data() : (const uint8_t *const *)images, widths, heights, strides, channels, f32,
-              di.regions, di.counts, di.from);
+              di.regions, di.counts, di.from, mi);
    set_consumer(io);
    run_chunks(c, io, ring);
    if (io.sink_rc.load() != 0) throw HsError(HESAFF_ERR_IO, "the result sink reported an error");
@@ -634,18 +706,20 @@ extern "C" {
 int hesaff_detect_batch(hesaff_ctx *c, int n, const uint8_t *const *images, const int *widths, const int *heights,
                         const int *strides, const int *channels, hesaff_result *results)
 {
+   const ArmedMasks am = take_masks(c);
    if (!c || n < 0 || (n > 0 && (!images || !widths || !heights || !results))) return HESAFF_ERR_ARG;
    HS_API_BEGIN
-   detect_images(c, n, images, false, widths, heights, strides, channels, 0, [&](ArrayIO &io) { io.results = results; });
+   detect_images(c, n, images, false, widths, heights, strides, channels, 0, [&](ArrayIO &io) { io.results = results; }, am);
    HS_API_END(c)
 }
 
 int hesaff_detect_batch_cb(hesaff_ctx *c, int n, const uint8_t *const *images, const int *widths, const int *heights,
                            const int *strides, const int *channels, hesaff_chunk_sink sink, void *user)
 {
+   const ArmedMasks am = take_masks(c);
    if (!c || n < 0 || !sink || (n > 0 && (!images || !widths || !heights))) return HESAFF_ERR_ARG;
    HS_API_BEGIN
-   detect_images(c, n, images, false, widths, heights, strides, channels, 3, [&](ArrayIO &io) { io.sink = sink; io.user = user; });
+   detect_images(c, n, images, false, widths, heights, strides, channels, 3, [&](ArrayIO &io) { io.sink = sink; io.user = user; }, am);
    HS_API_END(c)
 }
 
@@ -654,9 +728,10 @@ int hesaff_detect_batch_cb(hesaff_ctx *c, int n, const uint8_t *const *images, c
 int hesaff_detect_regions(hesaff_ctx *c, int n, const uint8_t *const *images, const int *widths, const int *heights,
                           const int *strides, const int *channels, hesaff_region_result *results)
 {
+   const ArmedMasks am = take_masks(c);
    if (!c || n < 0 || (n > 0 && (!images || !widths || !heights || !results))) return HESAFF_ERR_ARG;
    HS_API_BEGIN
-   detect_images(c, n, images, false, widths, heights, strides, channels, 0, [&](ArrayIO &io) { io.region_results = results; });
+   detect_images(c, n, images, false, widths, heights, strides, channels, 0, [&](ArrayIO &io) { io.region_results = results; }, am);
    HS_API_END(c)
 }
 
@@ -664,27 +739,30 @@ int hesaff_detect_regions(hesaff_ctx *c, int n, const uint8_t *const *images, co
 int hesaff_detect_batch_f32(hesaff_ctx *c, int n, const float *const *images, const int *widths, const int *heights, const int *strides,
                             hesaff_result *results)
 {
+   const ArmedMasks am = take_masks(c);
    if (!c || n < 0 || (n > 0 && (!images || !widths || !heights || !results))) return HESAFF_ERR_ARG;
    HS_API_BEGIN
-   detect_images(c, n, images, true, widths, heights, strides, nullptr, 0, [&](ArrayIO &io) { io.results = results; });
+   detect_images(c, n, images, true, widths, heights, strides, nullptr, 0, [&](ArrayIO &io) { io.results = results; }, am);
    HS_API_END(c)
 }
 
 int hesaff_detect_batch_cb_f32(hesaff_ctx *c, int n, const float *const *images, const int *widths, const int *heights, const int *strides,
                                hesaff_chunk_sink sink, void *user)
 {
+   const ArmedMasks am = take_masks(c);
    if (!c || n < 0 || !sink || (n > 0 && (!images || !widths || !heights))) return HESAFF_ERR_ARG;
    HS_API_BEGIN
-   detect_images(c, n, images, true, widths, heights, strides, nullptr, 3, [&](ArrayIO &io) { io.sink = sink; io.user = user; });
+   detect_images(c, n, images, true, widths, heights, strides, nullptr, 3, [&](ArrayIO &io) { io.sink = sink; io.user = user; }, am);
    HS_API_END(c)
 }
 
 int hesaff_detect_regions_f32(hesaff_ctx *c, int n, const float *const *images, const int *widths, const int *heights, const int *strides,
                               hesaff_region_result *results)
 {
+   const ArmedMasks am = take_masks(c);
    if (!c || n < 0 || (n > 0 && (!images || !widths || !heights || !results))) return HESAFF_ERR_ARG;
    HS_API_BEGIN
-   detect_images(c, n, images, true, widths, heights, strides, nullptr, 0, [&](ArrayIO &io) { io.region_results = results; });
+   detect_images(c, n, images, true, widths, heights, strides, nullptr, 0, [&](ArrayIO &io) { io.region_results = results; }, am);
    HS_API_END(c)
 }
 
@@ -709,26 +787,31 @@ extern "C" {
 int hesaff_describe_regions(hesaff_ctx *c, int n, const uint8_t *const *images, const int *widths, const int *heights, const int *strides,
                             const int *channels, const hesaff_region *const *regions, const int *counts, int from, hesaff_region_result *results)
 {
+   const ArmedMasks am = take_masks(c);
    if (!c || n < 0 || (n > 0 && (!images || !widths || !heights || !regions || !counts || !results))) return HESAFF_ERR_ARG;
    HS_API_BEGIN
+   refuse_masks(am, "hesaff_describe_regions takes none: its records are the caller's");
    const DescribeInput di = describe_input(n, regions, counts, from);
-   detect_images(c, n, images, false, widths, heights, strides, channels, 0, [&](ArrayIO &io) { io.region_results = results; }, di);
+   detect_images(c, n, images, false, widths, heights, strides, channels, 0, [&](ArrayIO &io) { io.region_results = results; }, am, di);
    HS_API_END(c)
 }
 
 int hesaff_describe_regions_f32(hesaff_ctx *c, int n, const float *const *images, const int *widths, const int *heights, const int *strides,
                                 const hesaff_region *const *regions, const int *counts, int from, hesaff_region_result *results)
 {
+   const ArmedMasks am = take_masks(c);
    if (!c || n < 0 || (n > 0 && (!images || !widths || !heights || !regions || !counts || !results))) return HESAFF_ERR_ARG;
    HS_API_BEGIN
+   refuse_masks(am, "hesaff_describe_regions takes none: its records are the caller's");
    const DescribeInput di = describe_input(n, regions, counts, from);
-   detect_images(c, n, images, true, widths, heights, strides, nullptr, 0, [&](ArrayIO &io) { io.region_results = results; }, di);
+   detect_images(c, n, images, true, widths, heights, strides, nullptr, 0, [&](ArrayIO &io) { io.region_results = results; }, am, di);
    HS_API_END(c)
 }
 
 int hesaff_detect_batch_device_f32(hesaff_ctx *c, int n, const void *d_planes, int width, int height, int row_stride, int64_t img_stride,
                                    int32_t *count_hessian, int32_t *count_desc, const void **d_keys_out, int64_t *total_out)
 {
+   const ArmedMasks am = take_masks(c);
    if (!c || n < 1 || !d_planes || width < 1 || height < 1 || row_stride < 0 || img_stride < 0) return HESAFF_ERR_ARG;
    HS_API_BEGIN
    begin_device_batch(c, n);
@@ -740,7 +823,7 @@ int hesaff_detect_batch_device_f32(hesaff_ctx *c, int n, const void *d_planes, i
    if (is % 4 != 0 || (n > 1 && is < rs * (height - 1) + 4LL * width))
       throw HsError(HESAFF_ERR_ARG, "image stride of the float planes must be a multiple of 4 and keep the images apart");
    detect_device(c, n, SrcImages::f32(d_planes, is, (int)rs), height, width, count_hessian, count_desc, d_keys_out, total_out,
-                 [&] { check_device_f32(c, n, (const uint8_t *)d_planes, is, (int)rs, height, width); });
+                 [&] { check_device_f32(c, n, (const uint8_t *)d_planes, is, (int)rs, height, width); }, am);
    HS_API_END(c)
 }
 
@@ -791,11 +874,36 @@ int hesaff_get_keypoint_limit(const hesaff_ctx *c, int *n)
    return HESAFF_OK;
 }
 
+int hesaff_set_next_masks(hesaff_ctx *c, int n, const uint8_t *const *masks, const int *strides)
+{
+   if (!c || n < 0 || (n > 0 && !masks)) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   ArmedMasks am;
+   if (n > 0 && masks) {
+      am.kind = ArmedMasks::HOST; am.n = n;
+      am.masks.assign(masks, masks + n);
+      if (strides) am.strides.assign(strides, strides + n);
+   }
+   c->next_masks = std::move(am);
+   HS_API_END(c)
+}
+
+int hesaff_set_next_masks_device(hesaff_ctx *c, int n, const void *d_masks, int row_stride, int64_t img_stride)
+{
+   if (!c || n < 0 || (n > 0 && !d_masks) || row_stride < 0 || img_stride < 0) return HESAFF_ERR_ARG;
+   ArmedMasks am;
+   if (n > 0) { am.kind = ArmedMasks::DEVICE; am.n = n; am.d_masks = d_masks; am.row_stride = row_stride; am.img_stride = img_stride; }
+   c->next_masks = am;
+   return HESAFF_OK;
+}
+
 int hesaff_process_files(hesaff_ctx *c, int n, const char *const *paths, const char *const *out_paths, int decode_threads,
                          int write_threads, hesaff_file_status *status)
 {
+   const ArmedMasks am = take_masks(c);
    if (!c || n < 0 || (n > 0 && (!paths || !status))) return HESAFF_ERR_ARG;
    HS_API_BEGIN
+   refuse_masks(am, "hesaff_process_files takes none: no masks travel with a file list");
    for (int i = 0; i < n; i++) { status[i].rc = HESAFF_ERR_IO; status[i].stage = HESAFF_FILE_PENDING; status[i].count_hessian = 0; status[i].count_desc = 0; }
    hesaff_host_plan hp;
    (void)hesaff_host_plan_for(1, &hp);   // "0 = auto": this context has the host to itself (callers that share it pass the counts of their own plan)

@@ -84,7 +84,43 @@ struct HostChunk {                // at most max_batch images of one geometry
    int from = 0;
    std::vector<const hesaff_region *> regions;
    std::vector<int> region_count;
+   // hesaff_set_next_masks: the caller's detection masks travel with their images.  Empty: no image of the chunk has one; otherwise
+   // masks[b] (null: image b is unmasked) is an H x W plane of 8-bit pixels whose rows are mask_stride[b] bytes apart.
+   std::vector<const uint8_t *> masks;
+   std::vector<size_t> mask_stride;
 };
+
+// What hesaff_set_next_masks / hesaff_set_next_masks_device armed for the next detecting call of a context: the caller's two lists
+// (copied: the planes they point to are not), or n planes in device memory.
+struct ArmedMasks {
+   enum { NONE = 0, HOST = 1, DEVICE = 2 };
+   int kind = NONE, n = 0;
+   std::vector<const uint8_t *> masks;   // HOST
+   std::vector<int> strides;             // HOST: empty = tightly packed
+   const void *d_masks = nullptr;        // DEVICE
+   int row_stride = 0;
+   int64_t img_stride = 0;
+};
+
+// The host masks as detect_images hands them to ArrayIO: the caller's lists, already checked against the call's images (strides null:
+// tightly packed; masks null: the call has none).
+struct MaskInput { const uint8_t *const *masks = nullptr; const int *strides = nullptr; };
+
+// A chunk's masks in the layout the device reads (batch_plan.h: mask_planes_offset): one "present" byte per image, then - planes_at
+// bytes in - one tight H x W plane per image (left alone where the image has no mask).  Row by row: the padding of a caller's rows
+// is never read.
+inline void fill_mask_block(uint8_t *blk, size_t planes_at, const HostChunk &q)
+{
+   const size_t W = (size_t)q.W, H = (size_t)q.H;
+   for (size_t b = 0; b < q.masks.size(); b++) {
+      blk[b] = q.masks[b] ? 1 : 0;
+      if (!q.masks[b]) continue;
+      uint8_t *dst = blk + planes_at + b * H * W;
+      const size_t stride = q.mask_stride[b];
+      if (stride == W) memcpy(dst, q.masks[b], H * W);
+      else for (size_t y = 0; y < H; y++) memcpy(dst + W * y, q.masks[b] + stride * y, W);
+   }
+}
 
 // Page-locked host buffers for the images a FileIO reads (the context's hipHostMalloc behind two plain function pointers: nothing here
 // touches HIP).  alloc may return nullptr (no room, or the caller pins nothing): the image then lives in ordinary memory and travels
@@ -266,7 +302,8 @@ struct ArrayIO : ChunkIO {
    hesaff_region_result *region_results = nullptr;   // hesaff_detect_regions: filled in place (instead of results)
    std::atomic<int> sink_rc{0};                 // written by done() on the caller's thread, read by next() on the staging thread
    ArrayIO(BlockRing *ring_, int max_batch, int n, const uint8_t *const *images, const int *widths, const int *heights, const int *strides,
-           const int *channels, bool f32 = false, const hesaff_region *const *regions = nullptr, const int *counts = nullptr, int from = 0)
+           const int *channels, bool f32 = false, const hesaff_region *const *regions = nullptr, const int *counts = nullptr, int from = 0,
+           const MaskInput &mi = MaskInput())
       : ring(ring_)
    {
       std::vector<char> taken((size_t)n, 0);
@@ -301,7 +338,10 @@ struct ArrayIO : ChunkIO {
                k.data.push_back(images[j]);
                k.stride.push_back(strides ? (size_t)strides[j] : (size_t)W * k.bpp());
                if (from) { k.regions.push_back(regions[j]); k.region_count.push_back(counts[j]); }
+               // (the regrouping is by geometry, not by position: image b of the chunk is the caller's image j, and so is its mask)
+               if (mi.masks) { k.masks.push_back(mi.masks[j]); k.mask_stride.push_back(mi.strides ? (size_t)mi.strides[j] : (size_t)W); }
             }
+            if (std::all_of(k.masks.begin(), k.masks.end(), [](const uint8_t *m) { return m == nullptr; })) { k.masks.clear(); k.mask_stride.clear(); }
             chunks.push_back(std::move(k));
             g0 += sz;
          }

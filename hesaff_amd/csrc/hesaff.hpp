@@ -110,11 +110,26 @@ struct AffineHessianDetector {
       if (hesaff_set_keypoint_limit(ctx_, n) != HESAFF_OK) throw std::invalid_argument("keypoint limit must be 0 (off) or positive");
    }
 
+   // No counterpart in the reference (hesaff_set_next_masks, include/hesaff_amd.h; OpenCV's detect(image, keypoints, mask)): the NEXT
+   // detectPyramidKeypoints keeps only the Hessian keypoints on a non-zero pixel of `mask` - height x width 8-bit pixels at the size of
+   // the image as passed, rows strideBytes apart (0: tightly packed), pixel (row, col) = (clamp((int)(y + 0.5f)), clamp((int)(x +
+   // 0.5f))) - and drops the rest on the device before findAffineShape; `keys`, the counters and the replayed callbacks see only the
+   // kept keypoints, each as the unmasked run produces it.  One-shot: that call consumes the mask whatever it returns (nullptr:
+   // disarm).  The pixels are not copied: they stay valid until that call has returned.  With a keypoint limit, the mask acts first.
+   // The batch forms below take no mask: their records are the caller's.
+   void setMask(const uint8_t *mask, size_t strideBytes = 0)
+   {
+      if (strideBytes > (size_t)0x7fffffff) throw std::invalid_argument("row stride too large");
+      mask_ = mask;
+      maskStride_ = (int)strideBytes;
+   }
+
    // == grey conversion hesaff.cpp:138-148 + detectPyramidKeypoints hesaff.cpp:167 with the
    // whole callback chain; image is what cv::imread would deliver (8-bit, 1 or 3 channels).
    void detectPyramidKeypoints(const uint8_t *image, int width, int height, int channels)
    {
       const int stride = width * channels;
+      armMask(width);
       if (!hessianKeypointCallback_ && !affineShapeCallback_) {
          hesaff_result r;
          if (hesaff_detect_batch(ctx_, 1, &image, &width, &height, &stride, &channels, &r) != HESAFF_OK)
@@ -135,6 +150,7 @@ struct AffineHessianDetector {
    {
       if (strideBytes > (size_t)0x7fffffff) throw std::invalid_argument("row stride too large");
       const int stride = strideBytes ? (int)strideBytes : width * 4;
+      armMask(width);
       if (!hessianKeypointCallback_ && !affineShapeCallback_) {
          hesaff_result r;
          if (hesaff_detect_batch_f32(ctx_, 1, &image, &width, &height, &stride, &r) != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
@@ -200,6 +216,15 @@ struct AffineHessianDetector {
    }
 
  private:
+   // setMask's mask goes to the context for the call that follows, and leaves this object
+   void armMask(int width)
+   {
+      const uint8_t *mask = mask_;
+      const int stride = maskStride_ ? maskStride_ : width;
+      mask_ = nullptr;
+      maskStride_ = 0;
+      if (mask && hesaff_set_next_masks(ctx_, 1, &mask, &stride) != HESAFF_OK) throw std::runtime_error("hesaff_set_next_masks failed");
+   }
    void take(int count_hessian, int count_desc, const hesaff_keypoint *k)
    {
       g_numberOfPoints = count_hessian;
@@ -249,6 +274,8 @@ struct AffineHessianDetector {
    hesaff_ctx *ctx_ = nullptr;
    HessianKeypointCallback *hessianKeypointCallback_ = nullptr;
    AffineShapeCallback *affineShapeCallback_ = nullptr;
+   const uint8_t *mask_ = nullptr;   // setMask
+   int maskStride_ = 0;
 };
 
 } // namespace hesaff_amd

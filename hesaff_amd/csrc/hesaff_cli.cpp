@@ -3,6 +3,10 @@
 // libhesaff_amd.so.  Input: binary PGM/PPM (P5/P6), PNG or JPEG.
 //
 // Extensions (the reference has no flags; it would try to open a file called "--batch"):
+//   hesaff <image> --mask <mask file>
+//       a detection mask for the single-image form (hesaff_set_next_masks): an image file of ONE channel and the image's size; keypoints
+//       whose pixel (x and y rounded to nearest) is zero in it are dropped on the device before findAffineShape, and the stdout line
+//       and the output file hold what is left, each row as the unmasked run writes it.  Not available with --batch.
 //   hesaff --batch <list file> [--devices <spec>]
 //       one image path per line; every image gets the `<image>.hesaff.sift` the single-image form writes.
 //       --devices 0-7 | 0,2,5 | all   shards the list over several GPUs of the node: one context per device, each on
@@ -267,9 +271,31 @@ int main(int argc, char **argv)
          fprintf(stderr, "hesaff: cannot read '%s' (PBM / PGM / PPM, PNG, JPEG, BMP or baseline TIFF expected)\n", argv[1]);
          return 1;
       }
+      // --mask <file> behind the image: refused here, before a device is touched, when it cannot serve as this image's mask
+      uint8_t *mask = nullptr;
+      for (int i = 2; i < argc; i++) {
+         if (strcmp(argv[i], "--mask") != 0) continue;
+         if (mask) { hesaff_free(mask); mask = nullptr; }   // (the last --mask counts)
+         int mw = 0, mh = 0, mch = 0;
+         const char *why = nullptr;
+         if (i + 1 >= argc) { fprintf(stderr, "hesaff: --mask needs a mask file\n"); hesaff_free(data); return 1; }
+         const char *mname = argv[++i];
+         if (hesaff_read_image(mname, &mask, &mw, &mh, &mch) != HESAFF_OK) { why = "cannot be read"; mask = nullptr; }
+         else if (mch != 1) why = "has three channels: a mask has one";
+         else if (mw != w || mh != h) why = "is not of the image's size";
+         if (why) {
+            fprintf(stderr, "hesaff: mask '%s' %s", mname, why);
+            if (mask && mch == 1) fprintf(stderr, " (%d x %d, the image is %d x %d)", mw, mh, w, h);
+            fprintf(stderr, "\n");
+            if (mask) hesaff_free(mask);
+            hesaff_free(data);
+            return 1;
+         }
+      }
       try {
          hesaff_amd::HessianAffineParams par;
          hesaff_amd::AffineHessianDetector detector(par);
+         if (mask) detector.setMask(mask);
          const auto t1 = std::chrono::steady_clock::now();
          detector.detectPyramidKeypoints(data, w, h, ch);
          const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
@@ -277,14 +303,16 @@ int main(int argc, char **argv)
                    << " affine shapes in " << dt << " sec." << std::endl;
          const std::string name = std::string(argv[1]) + ".hesaff.sift";
          std::ofstream out(name.c_str());
-         if (!out) { fprintf(stderr, "hesaff: cannot write '%s'\n", name.c_str()); hesaff_free(data); return 1; }
+         if (!out) { fprintf(stderr, "hesaff: cannot write '%s'\n", name.c_str()); hesaff_free(data); if (mask) hesaff_free(mask); return 1; }
          detector.exportKeypoints(out);
       } catch (const std::exception &e) {
          fprintf(stderr, "hesaff: %s\n", e.what());
          hesaff_free(data);
+         if (mask) hesaff_free(mask);
          return 1;
       }
       hesaff_free(data);
+      if (mask) hesaff_free(mask);
    } else {
       printf("\nUsage: hesaff image_name.ppm\nDetects Hessian Affine points and describes them using SIFT descriptor.\nThe detector assumes that the vertical orientation is preserved.\n\n");
    }

@@ -57,6 +57,7 @@ static thread_local std::string g_create_error;
    } while (0)
 
 using hesaff_engine::HsError;
+using hesaff_engine::ArmedMasks;
 using namespace hesaff_plan;   // batch_plan.h, context_tables.h: the layouts, the launch arithmetic and the tables of a batch
 namespace sched = hesaff_sched;   // group_schedule.h: the stream / event order of the keypoint stages
 
@@ -330,6 +331,8 @@ struct hesaff_ctx {
       DevBuf b_jcoef;       // JPEG chunks: the images' coefficient blobs (kernels_jpeg.h makes the pixels in b_in2)
       PinBuf pin_reg;       // hesaff_describe_regions: the chunk's record starts + records ...
       DevBuf b_reg;         // ... and on the device (run_describe's d_block)
+      PinBuf pin_mask;      // hesaff_set_next_masks: the chunk's "present" bytes + mask planes (batch_plan.h: mask_planes_offset) ...
+      DevBuf b_mask;        // ... and on the device (run_batch's SelMasks); neither exists before a mask was armed
       DevBuf b_outstage;    // what leaves for the host, in the layout of the result block
       DevEvent ev_h2d;      // the copy in has landed
       DevEvent ev_h2d_blk;  // blocking-sync: the staging thread sleeps until a chunk's direct copies have left the readers' buffers
@@ -422,6 +425,7 @@ struct hesaff_ctx {
    int resume = 0;                     // hesaff_set_resume: 0 off, 1 skip complete outputs (O(1) test), 2 strict (rows counted)
    int pool_priority = -1;             // hesaff_set_pool_priority: -1 lower the pool's priority when the plan is CPU-starved, 0 never, 1 always
    int keypoint_limit = 0;             // hesaff_set_keypoint_limit: 0 no limit, N >= 1 the N strongest Hessian keypoints of every image (run_batch)
+   ArmedMasks next_masks;              // hesaff_set_next_masks / _device: the masks of the next detecting call (taken, so cleared, by take_masks)
    int stage_threads = 4;              // host threads that copy a chunk's pixels into pinned memory (hesaff_process_files: within its thread budget)
    DevEvent ev_detect_done, ev_batch_done;   // blocking-sync events: the host sleeps instead of spinning
    std::vector<DevEvent> ev_aff;             // one per image group, grown on demand (GroupDevice)
@@ -1197,22 +1201,26 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
    return {h.hess(), h.desc(), d_starts.desc()};
 }
 
-// hesaff_set_keypoint_limit (kernels_select.h): of the ordered Hessian list run_detection left, every image keeps its keypoint_limit
-// strongest keypoints, in their order, and the list, its length, the per-image starts and the large-window row bounds become those of
-// the kept keypoints - everything behind sees a shorter list.  Only run_batch calls it: the stage operators and run_describe, which
-// share run_detection, are not limited.  The ranks live in b_rank (free until the pack stage's scan), the ordered items are still in
-// b_cand, the length detection found stays in the counter block: no buffer of its own, nothing allocated.
-void select_strongest(hesaff_ctx *c, const Lists &s, StageTimer &tm, int B)
+// hesaff_set_keypoint_limit and hesaff_set_next_masks (kernels_select.h): of the ordered Hessian list run_detection left, every image
+// keeps its eligible keypoints - those on a non-zero pixel of its mask, all without one - or the keypoint_limit strongest of them, in
+// their order, and the list, its length, the per-image starts and the large-window row bounds become those of the kept keypoints -
+// everything behind sees a shorter list.  Only run_batch calls it: the stage operators and run_describe, which share run_detection,
+// neither limit nor mask.  The ranks live in b_rank (free until the pack stage's scan), the kept counts in the descriptor starts
+// (written at the end of the batch), the ordered items are still in b_cand, the length detection found stays in the counter block:
+// no buffer of its own, nothing allocated.
+void select_keypoints(hesaff_ctx *c, const Lists &s, StageTimer &tm, int B, const SelMasks &mk)
 {
    hipStream_t st = c->stream();
    CounterBlock *cnt = s.counters;
-   const uint32_t limit = (uint32_t)c->keypoint_limit;
-   int32_t *starts = starts_block(c->geo.b_starts.as<int32_t>(), B).hess();
+   const uint32_t limit = c->keypoint_limit > 0 ? (uint32_t)c->keypoint_limit : HS_SEL_NO_LIMIT;
+   const StartsBlock<int32_t> sb = starts_block(c->geo.b_starts.as<int32_t>(), B);
+   int32_t *starts = sb.hess();
+   uint32_t *kept = (uint32_t *)sb.desc();
    uint32_t *keep_rank = c->geo.b_rank.as<uint32_t>();
    const int t = tm.begin(T_DET);
-   hipLaunchKernelGGL(k_select_image, dim3(B), dim3(HS_SEL_THREADS), 0, st, (const float *)s.hl.response, (const int32_t *)starts,
-                      (const uint32_t *)&cnt->head.hess_total, s.hl.cap, limit, keep_rank);
-   hipLaunchKernelGGL(k_select_starts, dim3(1), dim3(256), 0, st, starts, B, limit, s.hl.cap, &cnt->head.hess_total, &cnt->head.hess_detected);
+   hipLaunchKernelGGL(k_select_image, dim3(B), dim3(HS_SEL_THREADS), 0, st, (const float *)s.hl.response, (const float *)s.hl.x, (const float *)s.hl.y,
+                      (const int32_t *)starts, (const uint32_t *)&cnt->head.hess_total, s.hl.cap, limit, mk, keep_rank, kept);
+   hipLaunchKernelGGL(k_select_starts, dim3(1), dim3(256), 0, st, starts, B, (const uint32_t *)kept, s.hl.cap, &cnt->head.hess_total, &cnt->head.hess_detected);
    hipLaunchKernelGGL(k_hess_deal_kept, dim3(HS_GRID_SCAT), dim3(256), 0, st, (const HessItem *)c->geo.b_cand.p, (const uint32_t *)&cnt->head.hess_detected,
                       (const uint32_t *)keep_rank, (const int32_t *)starts, s.hl);
    launch_image_large_rows(c, s, B);   // the bounds form_groups reads describe the kept keypoints
@@ -1221,7 +1229,8 @@ void select_strongest(hesaff_ctx *c, const Lists &s, StageTimer &tm, int B)
 
 // Whole hot path on a device-resident batch.  Leaves ordered KeyRec records in b_out and
 // per-image start offsets (b_starts: StartsBlock::hess() and desc(); BatchResult: their host copies).
-BatchResult run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
+// mk: the batch's detection masks (base null: none), H x W like the images.
+BatchResult run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W, const SelMasks &mk = SelMasks())
 {
    plan(c, B, H, W);
    c->ev_used = 0;
@@ -1229,7 +1238,7 @@ BatchResult run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W)
    Lists s = make_lists(c);
    const int tt = tm.begin(T_TOTAL);
    run_detection(c, src, B, s, tm, false, nullptr);
-   if (c->keypoint_limit > 0) select_strongest(c, s, tm, B);
+   if (c->keypoint_limit > 0 || mk.base) select_keypoints(c, s, tm, B, mk);
    // the one host round trip of a batch
    return run_keypoint_stages(c, s, tm, tt, B, H, W, fetch_hessian_starts(c, B), true);
 }

@@ -42,6 +42,7 @@ extern "C" {
  *    needs them finds them by symbol (dlsym) in the library it loaded.  The same holds for hesaff_describe_regions and
  *    hesaff_describe_regions_f32 (HESAFF_FROM_POINTS / HESAFF_FROM_SHAPES): new symbols over the structs of version 8.  And for
  *    hesaff_set_keypoint_limit / hesaff_get_keypoint_limit: two more symbols, no struct touched, the version stays 8.
+ *    Likewise hesaff_set_next_masks / hesaff_set_next_masks_device (per-image detection masks): symbols only, version 8.
  *    And for the test hook hesaff_stage_sift_alive.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
@@ -348,6 +349,40 @@ int hesaff_describe_regions_f32(hesaff_ctx *ctx, int n, const float *const *imag
  * n: 0 = off.  n < 0 or ctx NULL: HESAFF_ERR_ARG (hesaff_get_keypoint_limit: ctx or n NULL). */
 int hesaff_set_keypoint_limit(hesaff_ctx *ctx, int n);
 int hesaff_get_keypoint_limit(const hesaff_ctx *ctx, int *n);
+
+/* ---- per-image detection masks: keypoints off the mask are dropped on the device (OpenCV's detect(image, keypoints, mask)) ----
+ * The other half of the sentence above hesaff_describe_regions: a caller of the reference who wants keypoints only inside a mask
+ * filters inside onHessianKeypointDetected (pyramid.h:43-47).  Here the masks are armed for the NEXT detecting call on the context
+ * and consumed (cleared) by that call whatever it returns; the selection runs where the keypoint limit runs, between detection's
+ * ordering step and findAffineShape.
+ * Each image may have a mask: height x width 8-bit pixels, one channel, at the size of the image as passed - also with
+ * upscaleInputImage = 1, since keypoint coordinates are in the caller's pixels.  Non-zero means "detect here".  Hessian keypoint i of
+ * an image with a mask is eligible iff mask[row][col] != 0 with
+ *    col = clamp((int)(x + 0.5f), 0, width - 1),  row = clamp((int)(y + 0.5f), 0, height - 1)
+ * - the add in binary32, the conversion truncating (OpenCV's runByPixelsMask rounding, clamped); x, y are the floats
+ * onHessianKeypointDetected receives.  In numpy: np.clip((x + np.float32(0.5)).astype(np.int32), 0, W - 1).  An image without a mask
+ * has every keypoint eligible.  Ineligible keypoints are discarded before findAffineShape and cost nothing after detection.
+ * With a keypoint limit N >= 1 the rule of hesaff_set_keypoint_limit applies over the eligible keypoints only (counts and ties among
+ * eligible j; ties at the cut to the earlier one): mask first, then the N strongest of what is left.  With limit 0 every eligible
+ * keypoint is kept.  Kept keypoints stay in the reference's order; count_hessian is the number kept; each hesaff_region record equals
+ * its unmasked record except `key`, which is renumbered, and each hesaff_keypoint has the bytes of its unmasked key; text rows, sidecar
+ * rows and the callbacks hesaff.hpp replays follow from these records.  max_kpts_per_mpx must still hold every DETECTED keypoint: the
+ * mask acts after the ordering step.  The result does not depend on launch geometry and is the same from run to run.
+ *
+ * hesaff_set_next_masks (host memory) serves hesaff_detect_batch, _cb, _f32, _cb_f32, hesaff_detect_regions and _f32.  masks[i]
+ * belongs to image i of that call, NULL = image i is unmasked; strides[i] = bytes between the rows of mask i, >= width (strides NULL:
+ * tightly packed).  The two lists are copied here, the planes are not: they must stay valid until the detecting call returns.
+ * n = 0 (or masks NULL with n = 0) disarms.  ctx NULL, n < 0, or n > 0 with masks NULL: HESAFF_ERR_ARG.  At the call: n differing
+ * from the call's n, or a stride below the image's width: HESAFF_ERR_ARG (hesaff_last_error names both counts / the image), and the
+ * masks are cleared.
+ * hesaff_set_next_masks_device serves hesaff_detect_batch_device and _device_f32: n planes in device memory, row_stride / img_stride
+ * in bytes, 0 = tight (row_stride = width, img_stride = row_stride * height).  A negative stride: HESAFF_ERR_ARG.
+ * Masks armed in host memory that meet a device-resident call, or the reverse: HESAFF_ERR_ARG, masks cleared.
+ * While masks are armed, hesaff_describe_regions* (the records are the caller's) and hesaff_process_files (no masks travel with a
+ * file list) return HESAFF_ERR_ARG and clear them; the hesaff_stage_* operators neither read nor clear them.  The context stays
+ * usable after every refusal. */
+int hesaff_set_next_masks(hesaff_ctx *ctx, int n, const uint8_t *const *masks, const int *strides);
+int hesaff_set_next_masks_device(hesaff_ctx *ctx, int n, const void *d_masks, int row_stride, int64_t img_stride);
 
 /* Same path with inputs already resident in device memory (bench / pipelines that decode
  * on the GPU): d_gray = n contiguous height x width 8-bit grey planes (device pointer).

@@ -21,6 +21,8 @@ from ._binding import (  # noqa: F401
     Region,
     FROM_POINTS,
     FROM_SHAPES,
+    ORI_UP,
+    ORI_DOMINANT,
     default_params,
     format_sift,
     format_sift_mt,

@@ -224,6 +224,10 @@ def load_library():
     L.hesaff_stage_sift_parts.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _u8p]
     if hasattr(L, "hesaff_stage_sift_alive"):   # (absent from an older build loaded through HESAFF_AMD_LIB for a comparison)
         L.hesaff_stage_sift_alive.argtypes = [vp, C.c_int, _f32p, _i32p, _u8p]
+    if hasattr(L, "hesaff_set_orientation"):   # (likewise)
+        L.hesaff_set_orientation.argtypes = [vp, C.c_int]
+        L.hesaff_get_orientation.argtypes = [vp, C.POINTER(C.c_int)]
+        L.hesaff_stage_orientation.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math_sift_general.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math_sift.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]
@@ -261,7 +265,31 @@ ABI_SYMBOLS = [
     "hesaff_detect_batch_f32", "hesaff_detect_batch_cb_f32", "hesaff_detect_regions_f32", "hesaff_detect_batch_device_f32",
     "hesaff_stage_pyramid_f32", "hesaff_describe_regions", "hesaff_describe_regions_f32",
     "hesaff_set_keypoint_limit", "hesaff_get_keypoint_limit", "hesaff_set_next_masks", "hesaff_set_next_masks_device",
+    "hesaff_set_orientation", "hesaff_get_orientation", "hesaff_stage_orientation",
 ]
+
+# hesaff_set_orientation's modes
+ORI_UP = 0         # the reference's "up is up" frame (default)
+ORI_DOMINANT = 1   # the frame turned by the dominant gradient angle of the keypoint's own patch
+_ORI_NAMES = {"up": ORI_UP, "dominant": ORI_DOMINANT}
+
+class _OrientationMode(int):
+    """What HesaffContext.orientation returns: the mode, an int.  It is a subclass only so that the spelling
+    ctx.orientation(patches) works beside the property; the operator itself is HesaffContext.orientation_of, which is what new
+    code should call.  The object keeps a reference to its context, and compares, hashes and pickles as the plain int."""
+
+    def __reduce__(self):
+        return (int, (int(self),))
+
+
+    def __new__(cls, value, ctx):
+        self = super().__new__(cls, value)
+        self._ctx = ctx
+        return self
+
+    def __call__(self, patches, parts=False):
+        return self._ctx.orientation_of(patches, parts)
+
 
 # hesaff_describe_regions' `from`: which of the reference's two public callback members each record enters the chain through
 FROM_POINTS = 1   # onHessianKeypointDetected (hesaff.cpp:66-71): findAffineShape, then the rest when it converges
@@ -702,6 +730,29 @@ class HesaffContext:
     def keypoint_limit(self, n):
         self.set_keypoint_limit(n)
 
+    def set_orientation(self, mode):
+        """hesaff_set_orientation: ORI_UP / "up" (default: the reference's upright frame, bit for bit) or ORI_DOMINANT / "dominant":
+        every keypoint's frame is turned by the dominant gradient angle of its patch before it is described, so descriptors follow
+        an in-plane rotation of the image (one orientation per keypoint; definition in include/hesaff_amd.h).  Applies to every
+        detecting call, process_files and describe_regions*; not to the stage operators."""
+        if isinstance(mode, str):
+            if mode not in _ORI_NAMES:
+                raise ValueError("orientation is 'up' or 'dominant', not %r" % (mode,))
+            mode = _ORI_NAMES[mode]
+        self._check(self.L.hesaff_set_orientation(self.h, int(mode)))
+
+    @property
+    def orientation(self):
+        """The mode, an int (ORI_UP / ORI_DOMINANT) - and, called with patches, the stage operator: ctx.orientation(patches) is
+        ctx.orientation_of(patches)."""
+        m = C.c_int()
+        self._check(self.L.hesaff_get_orientation(self.h, C.byref(m)))
+        return _OrientationMode(m.value, self)
+
+    @orientation.setter
+    def orientation(self, mode):
+        self.set_orientation(mode)
+
     def process_files(self, paths, out_paths=None, decode_threads=0, write_threads=0):
         """hesaff_process_files: image files -> <name>.hesaff.sift through the decode / device / write pipeline.
         -> list of (rc, stage, count_hessian, count_desc) per file."""
@@ -821,6 +872,15 @@ class HesaffContext:
         mv = np.zeros((n, 2), np.float32); hist = np.zeros((n, 128), np.float32); d = np.zeros((n, 128), np.uint8)
         self._check(self.L.hesaff_stage_sift_parts(self.h, n, p, mv, hist, d))
         return mv, hist, d
+
+    def orientation_of(self, patches, parts=False):
+        """hesaff_stage_orientation on [n, 41, 41] patches -> theta [n]; parts=True: (theta, hist [n, 36] after smoothing,
+        cs [n, 2] = (cos theta, sin theta))."""
+        p = np.ascontiguousarray(patches, np.float32).reshape(-1, 41 * 41)
+        n = len(p)
+        theta = np.zeros(n, np.float32); hist = np.zeros((n, 36), np.float32); cs = np.zeros((n, 2), np.float32)
+        self._check(self.L.hesaff_stage_orientation(self.h, n, p, theta, hist, cs))
+        return (theta, hist, cs) if parts else theta
 
     def sift_alive(self, patches, alive, fill=0):
         """-> desc [n, 128] u8, every byte `fill` before the call: rows of keypoints with alive == 0 keep it (hesaff_stage_sift_alive)."""

@@ -874,6 +874,20 @@ int hesaff_get_keypoint_limit(const hesaff_ctx *c, int *n)
    return HESAFF_OK;
 }
 
+int hesaff_set_orientation(hesaff_ctx *c, int mode)
+{
+   if (!c || (mode != HESAFF_ORI_UP && mode != HESAFF_ORI_DOMINANT)) return HESAFF_ERR_ARG;
+   c->orientation = mode;
+   return HESAFF_OK;
+}
+
+int hesaff_get_orientation(const hesaff_ctx *c, int *mode)
+{
+   if (!c || !mode) return HESAFF_ERR_ARG;
+   *mode = c->orientation;
+   return HESAFF_OK;
+}
+
 int hesaff_set_next_masks(hesaff_ctx *c, int n, const uint8_t *const *masks, const int *strides)
 {
    if (!c || n < 0 || (n > 0 && !masks)) return HESAFF_ERR_ARG;
@@ -1223,6 +1237,31 @@ int hesaff_stage_sift_alive(hesaff_ctx *c, int n, const float *patches, const in
 {
    if (!alive) return HESAFF_ERR_ARG;
    return stage_sift(c, n, patches, nullptr, nullptr, desc, alive);
+}
+
+// k_orientation (kernels_orient.h) on caller-supplied patches: every keypoint alive, no affine frame to turn
+int hesaff_stage_orientation(hesaff_ctx *c, int n, const float *patches, float *theta, float *hist, float *cs)
+{
+   if (!c || !patches || !theta || n < 0) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   bind_device(c);
+   if (n == 0) return HESAFF_OK;
+   const size_t N = (size_t)n;
+   // patches | theta | hist | (cos, sin)
+   const size_t off_theta = N * HS_PATCH_PIX * 4, off_hist = off_theta + N * 4, off_cs = off_hist + N * HS_ORI_BINS * 4, total = off_cs + N * 8;
+   c->b_stage.ensure(total);
+   char *base = (char *)c->b_stage.p;
+   HIP_TRY(hipMemcpyAsync(base, patches, N * HS_PATCH_PIX * 4, hipMemcpyHostToDevice, c->stream()));
+   OrientIO oi;
+   memset(&oi, 0, sizeof oi);
+   oi.patches = (const float *)base; oi.h_lo = 0; oi.h_hi = (uint32_t)n;
+   oi.theta = (float *)(base + off_theta); oi.hist = (float *)(base + off_hist); oi.cs = (float *)(base + off_cs);
+   hipLaunchKernelGGL(k_orientation, dim3(orientation_grid(c, (uint32_t)n)), dim3(64), 0, c->stream(), oi, c->tables.view);
+   HIP_TRY(hipMemcpyAsync(theta, base + off_theta, N * 4, hipMemcpyDeviceToHost, c->stream()));
+   if (hist) HIP_TRY(hipMemcpyAsync(hist, base + off_hist, N * HS_ORI_BINS * 4, hipMemcpyDeviceToHost, c->stream()));
+   if (cs) HIP_TRY(hipMemcpyAsync(cs, base + off_cs, N * 8, hipMemcpyDeviceToHost, c->stream()));
+   finish_stream(c);
+   HS_API_END(c)
 }
 
 // exportKeypoints on the device for caller-supplied records: the kernels hesaff_process_files runs per chunk

@@ -80,7 +80,18 @@ struct ScheduleOptions {
 // g - 1 in the MIDDLE of group g's patch stage instead - behind its kernels and in front of the main stream's wait for the side
 // streams - so that the other queue's bins run beside the descriptor chain.  They do, and each runs that much slower: the dense step
 // measured 0.8 % slower that way, the photograph step 2 % faster, so the order stays.
-template <class Device> void run_group_schedule(Device &dev, int n_groups, const ScheduleOptions &o)
+//
+// The oriented order (ORIENTED, hesaff_set_orientation: run_group_schedule_oriented below) runs the patch stage of a group twice, and
+// asks two more launches of the device, both on the main stream:
+//   orientation(g, slot)                 k_orientation over the first pass's patches in `slot`: the affine frames of g turned in place
+//   patch_rebin(g)                       the bin counters cleared again, k_prepare_patch_second over the turned frames
+// between the first pass's join and a second fork / patch_kernels / join into the same slot.  What it adds to the guarantees:
+//   - orientation(g) reads every first-pass patch of g and stands in front of the counter clear those kernels still read: behind
+//     every first-pass patch kernel on every stream (the join);
+//   - every second-pass patch kernel reads the turned frames and what patch_rebin(g) counted: behind both;
+//   - the descriptors of g read the second pass's patches: extract-done is recorded behind the second join.
+// With ORIENTED false nothing of this is instantiated: the device needs neither member, and the sequence is the one above.
+template <bool ORIENTED, class Device> void run_group_schedule_as(Device &dev, int n_groups, const ScheduleOptions &o)
 {
    const Stream as = o.overlap ? S_AFFINE : S_MAIN, ss = o.overlap ? S_DESC : S_MAIN;
    const bool affine_events = o.overlap && o.with_affine;
@@ -109,6 +120,13 @@ template <class Device> void run_group_schedule(Device &dev, int n_groups, const
       dev.patch_kernels(g, slot, o.n_side);
       if (g > 0 && o.sift_inside) descriptors(g - 1);
       join_side_streams(dev, g, o.n_side);
+      if constexpr (ORIENTED) {
+         dev.orientation(g, slot);
+         dev.patch_rebin(g);
+         fork_side_streams(dev, g, o.n_side);
+         dev.patch_kernels(g, slot, o.n_side);
+         join_side_streams(dev, g, o.n_side);
+      }
       dev.patch_done(g);
       dev.record(ev_extract_done(slot, g), S_MAIN);
       slot_used[slot] = true;
@@ -118,5 +136,7 @@ template <class Device> void run_group_schedule(Device &dev, int n_groups, const
    for (int sl = 0; sl < HS_NSLOT; sl++)
       if (slot_used[sl]) dev.wait(S_MAIN, ev_sift_done(sl, (n_groups - 1 - sl) / HS_NSLOT * HS_NSLOT + sl));   // the slot's last group
 }
+template <class Device> void run_group_schedule(Device &dev, int n_groups, const ScheduleOptions &o) { run_group_schedule_as<false>(dev, n_groups, o); }
+template <class Device> void run_group_schedule_oriented(Device &dev, int n_groups, const ScheduleOptions &o) { run_group_schedule_as<true>(dev, n_groups, o); }
 
 }   // namespace hesaff_sched

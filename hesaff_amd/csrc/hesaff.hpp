@@ -110,6 +110,17 @@ struct AffineHessianDetector {
       if (hesaff_set_keypoint_limit(ctx_, n) != HESAFF_OK) throw std::invalid_argument("keypoint limit must be 0 (off) or positive");
    }
 
+   // No counterpart in the reference (hesaff_set_orientation, include/hesaff_amd.h), whose descriptors live in the "up is up" frame of
+   // rectifyAffineTransformationUpIsUp (hesaff.cpp:79).  HESAFF_ORI_DOMINANT: every region's frame is turned by the dominant gradient
+   // angle of its own patch before normalizeAffine runs a second time and SIFT describes it; `keys` then holds A' = A R(theta) (theta =
+   // atan2(-a12, a11)), descriptors follow an in-plane rotation of the image, and a region normalizeAffine rejects in either run has
+   // no key.  The callbacks replay what they replay in mode 0: U stays un-rectified and un-turned.  One orientation per region.
+   // HESAFF_ORI_UP (default): the reference's behaviour, bit for bit.  Applies to detectPyramidKeypoints and to the batch forms below.
+   void setOrientation(int mode)
+   {
+      if (hesaff_set_orientation(ctx_, mode) != HESAFF_OK) throw std::invalid_argument("orientation is HESAFF_ORI_UP or HESAFF_ORI_DOMINANT");
+   }
+
    // No counterpart in the reference (hesaff_set_next_masks, include/hesaff_amd.h; OpenCV's detect(image, keypoints, mask)): the NEXT
    // detectPyramidKeypoints keeps only the Hessian keypoints on a non-zero pixel of `mask` - height x width 8-bit pixels at the size of
    // the image as passed, rows strideBytes apart (0: tightly packed), pixel (row, col) = (clamp((int)(y + 0.5f)), clamp((int)(x +

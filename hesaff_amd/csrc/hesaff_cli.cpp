@@ -30,6 +30,9 @@
 //       --max-keypoints N             a keypoint budget per image (hesaff_set_keypoint_limit): the N Hessian keypoints of greatest |response|
 //                                     are kept, in the reference's order, the rest dropped on the device before findAffineShape; N bounds the
 //                                     "keypoints" count, the "affine shapes" are fewer.  Default 0 = no limit.  Batch form only.
+//       --orientation up | dominant   the frame every region is described in (hesaff_set_orientation): the reference's "up is up" frame
+//                                     (default), or that frame turned by the dominant gradient angle of the region's own patch, which makes
+//                                     the descriptors follow an in-plane rotation of the image.  Batch form, and behind a single image.
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -103,7 +106,7 @@ bool parse_devices(const char *spec, std::vector<int> &out)
 // hesaff --batch: the list is cut into contiguous shards, one per device context (hesaff_shard_range); every shard runs
 // through hesaff_process_files - decode threads -> device -> writer threads, bounded memory - on its own host thread.
 int run_batch_mode(const char *list_path, const char *devices_spec, int out_format, bool dynamic, int fast, int resume, int host_share, int runtime_nice,
-                   int max_keypoints)
+                   int max_keypoints, int orientation)
 {
    std::ifstream lf(list_path);
    if (!lf) { fprintf(stderr, "hesaff: cannot read list '%s'\n", list_path); return 1; }
@@ -154,6 +157,7 @@ int run_batch_mode(const char *list_path, const char *devices_spec, int out_form
       hesaff_set_output_format(ctx, out_format);
       hesaff_set_resume(ctx, resume);
       hesaff_set_keypoint_limit(ctx, max_keypoints);
+      hesaff_set_orientation(ctx, orientation);
       hesaff_host_plan hp;   // this device's share of the host: the library's one rule (include/hesaff_amd.h)
       hesaff_host_plan_for(world * host_share, &hp);
       const int wt = hp.write_threads, dt = hp.decode_threads;
@@ -231,7 +235,7 @@ int main(int argc, char **argv)
    for (int i = 1; i < argc; i++) batch = batch || strcmp(argv[i], "--batch") == 0;
    if (batch) {
       const char *devices = nullptr, *list = nullptr;
-      int out_format = HESAFF_OUT_TEXT, fast = 0, host_share = 1, runtime_nice = -1, max_keypoints = 0;
+      int out_format = HESAFF_OUT_TEXT, fast = 0, host_share = 1, runtime_nice = -1, max_keypoints = 0, orientation = HESAFF_ORI_UP;
       bool bad = false, dynamic = false;
       int resume = 0;
       for (int i = 1; i < argc && !bad; i += 2) {
@@ -248,6 +252,10 @@ int main(int argc, char **argv)
             const long v = strtol(argv[i + 1], &end, 10);
             if (argv[i + 1][0] < '0' || argv[i + 1][0] > '9' || *end != 0 || v > 0x7fffffffL) bad = true;
             else max_keypoints = (int)v;
+         } else if (strcmp(argv[i], "--orientation") == 0) {
+            if (strcmp(argv[i + 1], "up") == 0) orientation = HESAFF_ORI_UP;
+            else if (strcmp(argv[i + 1], "dominant") == 0) orientation = HESAFF_ORI_DOMINANT;
+            else bad = true;
          } else if (strcmp(argv[i], "--fast") == 0) {
             if (strcmp(argv[i + 1], "0") == 0 || strcmp(argv[i + 1], "2") == 0) fast = atoi(argv[i + 1]);
             else bad = true;
@@ -261,8 +269,8 @@ int main(int argc, char **argv)
             else bad = true;
          } else bad = true;
       }
-      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1] [--max-keypoints N]\n"); return 1; }
-      return run_batch_mode(list, devices, out_format, dynamic, fast, resume, host_share, runtime_nice, max_keypoints);
+      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1] [--max-keypoints N] [--orientation up|dominant]\n"); return 1; }
+      return run_batch_mode(list, devices, out_format, dynamic, fast, resume, host_share, runtime_nice, max_keypoints, orientation);
    }
    if (argc > 1) {
       uint8_t *data = nullptr;
@@ -292,10 +300,25 @@ int main(int argc, char **argv)
             return 1;
          }
       }
+      // --orientation up | dominant behind the image (the last one counts)
+      int orientation = HESAFF_ORI_UP;
+      for (int i = 2; i < argc; i++) {
+         if (strcmp(argv[i], "--orientation") != 0) continue;
+         const char *v = i + 1 < argc ? argv[++i] : "";
+         if (strcmp(v, "up") == 0) orientation = HESAFF_ORI_UP;
+         else if (strcmp(v, "dominant") == 0) orientation = HESAFF_ORI_DOMINANT;
+         else {
+            fprintf(stderr, "hesaff: --orientation takes up or dominant\n");
+            hesaff_free(data);
+            if (mask) hesaff_free(mask);
+            return 1;
+         }
+      }
       try {
          hesaff_amd::HessianAffineParams par;
          hesaff_amd::AffineHessianDetector detector(par);
          if (mask) detector.setMask(mask);
+         detector.setOrientation(orientation);
          const auto t1 = std::chrono::steady_clock::now();
          detector.detectPyramidKeypoints(data, w, h, ch);
          const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();

@@ -333,3 +333,40 @@ HM_HD float hm_sift_orient_coord(float ori)
    return (float)q2;
 }
 
+
+// ---- sin and cos of a binary32 angle, |theta| <= pi (a little beyond is harmless), each rounded once to binary32 ----
+// The dominant-orientation stage (kernels_orient.h) rotates the affine frame by the estimated angle, and the key stores the
+// product: one ulp in c or s is one ulp in A'.  Explicit binary64 operations only: the quadrant k = RN(theta * 2/pi) in -2 .. 2,
+// r = (theta - k*pio2_hi) - k*pio2_lo in [-pi/4, pi/4] (k*pio2_hi is exact for |k| <= 2), then fdlibm's __kernel_sin /
+// __kernel_cos coefficients (fdlibm k_sin.c / k_cos.c: "Copyright (C) 1993 by Sun Microsystems, Inc. All rights reserved.  Developed
+// at SunPro, a Sun Microsystems, Inc. business.  Permission to use, copy, modify, and distribute this software is freely granted,
+// provided that this notice is preserved."), swapped and negated by quadrant, and one conversion to binary32.  The cosine is
+// evaluated as 1 - (z/2 - z*pc), without fdlibm's qx split for |r| > 0.3: the binary64 value is then within 2 ulp of a double
+// (2.3e-16 absolute near |r| = pi/4, where cos is 0.7; the sine within 1.2e-16), against a binary32 half-ulp of 3e-8 there.  So the
+// result differs from the correctly rounded one only where the true value lies within 2.3e-16 of a binary32 rounding boundary
+// (about one angle in 1e8); tests/test_orientation_host.py holds it to (float)sin((double)theta) of libm on 10^6 angles.
+HM_HD void hm_sincosf(float theta, float *s, float *c)
+{
+   const double inv_pio2 = hm_u2d(0x3fe45f306dc9c883ull);   // RN(2 / pi)
+   const double pio2_hi = hm_u2d(0x3ff921fb54442d18ull);    // RN(pi / 2)
+   const double pio2_lo = hm_u2d(0x3c91a62633145c07ull);    // RN(pi / 2 - pio2_hi)
+   const double SHIFT = hm_u2d(0x4338000000000000ull);      // 0x1.8p+52
+   const double S1 = hm_u2d(0xbfc5555555555549ull), S2 = hm_u2d(0x3f8111111110f8a6ull), S3 = hm_u2d(0xbf2a01a019c161d5ull),
+                S4 = hm_u2d(0x3ec71de357b1fe7dull), S5 = hm_u2d(0xbe5ae5e68a2b9cebull), S6 = hm_u2d(0x3de5d93a5acfd57cull);
+   const double C1 = hm_u2d(0x3fa555555555554cull), C2 = hm_u2d(0xbf56c16c16c15177ull), C3 = hm_u2d(0x3efa01a019cb1590ull),
+                C4 = hm_u2d(0xbe927e4f809c52adull), C5 = hm_u2d(0x3e21ee9ebdb4b1c4ull), C6 = hm_u2d(0xbda8fae9be8838d4ull);
+   const double x = (double)theta;
+   double kd = x * inv_pio2 + SHIFT;
+   const int q = (int)(uint32_t)hm_d2u(kd) & 3;   // k mod 4 (two's complement low bits of the shifted sum)
+   kd -= SHIFT;
+   const double r = (x - kd * pio2_hi) - kd * pio2_lo;
+   const double z = r * r;
+   const double ps = S2 + z * (S3 + z * (S4 + z * (S5 + z * S6)));
+   const double ts = (z * r) * (S1 + z * ps);
+   const double sn = (ts == 0.0) ? r : r + ts;   // (-0 + +0 would lose the sign of sin(-0))
+   const double pc = z * (C1 + z * (C2 + z * (C3 + z * (C4 + z * (C5 + z * C6)))));
+   const double cs = 1.0 - (0.5 * z - z * pc);
+   const double sv = (q & 1) ? cs : sn, cv = (q & 1) ? sn : cs;
+   *s = (float)((q & 2) ? -sv : sv);
+   *c = (float)(((q + 1) & 2) ? -cv : cv);
+}

@@ -347,7 +347,8 @@ __device__ __forceinline__ int hs_window_p0(float s, float mrSize)
 __global__ __launch_bounds__(256) void k_image_large_rows(HessList hl, const uint32_t *__restrict__ n_ptr, float mrSize, uint32_t *__restrict__ rows, int nimg,
                                                           int max_p0);
 
-template <bool RECTIFY>
+// ONLY_ALIVE (k_prepare_patch_second, kernels_orient.h): a keypoint whose alive flag is already 0 stays rejected.
+template <bool RECTIFY, bool ONLY_ALIVE = false>
 __device__ __forceinline__ void hs_prepare_patch_body(const HessList &hl, uint32_t h_lo, uint32_t n, const AffineOut &aff, int imRows, int imCols,
                                                       const DConsts &k, const KpTables &tb, const PatchWork &pw)
 {
@@ -355,7 +356,7 @@ __device__ __forceinline__ void hs_prepare_patch_body(const HessList &hl, uint32
       const uint32_t h = h0 + threadIdx.x;
       const bool valid = h < n;
       int alive = 0, P0 = 0;
-      if (valid && (!RECTIFY || aff.converged[h])) {
+      if (valid && (!RECTIFY || aff.converged[h]) && (!ONLY_ALIVE || pw.alive[h])) {
          float a11, a12, a21, a22;
          if (RECTIFY) {
             a11 = aff.U[4 * h]; a12 = aff.U[4 * h + 1]; a21 = aff.U[4 * h + 2]; a22 = aff.U[4 * h + 3];

@@ -36,6 +36,7 @@
 #include "kernels_select.h"
 #include "kernels_patch.h"
 #include "kernels_sift.h"
+#include "kernels_orient.h"
 #include "kernels_pyramid.h"
 #include "kernels_export.h"
 #include "kernels_jpeg.h"
@@ -425,6 +426,7 @@ struct hesaff_ctx {
    int resume = 0;                     // hesaff_set_resume: 0 off, 1 skip complete outputs (O(1) test), 2 strict (rows counted)
    int pool_priority = -1;             // hesaff_set_pool_priority: -1 lower the pool's priority when the plan is CPU-starved, 0 never, 1 always
    int keypoint_limit = 0;             // hesaff_set_keypoint_limit: 0 no limit, N >= 1 the N strongest Hessian keypoints of every image (run_batch)
+   int orientation = HESAFF_ORI_UP;    // hesaff_set_orientation: HESAFF_ORI_DOMINANT runs the oriented order of group_schedule.h (run_keypoint_stages)
    ArmedMasks next_masks;              // hesaff_set_next_masks / _device: the masks of the next detecting call (taken, so cleared, by take_masks)
    int stage_threads = 4;              // host threads that copy a chunk's pixels into pinned memory (hesaff_process_files: within its thread budget)
    DevEvent ev_detect_done, ev_batch_done;   // blocking-sync events: the host sleeps instead of spinning
@@ -824,6 +826,9 @@ void run_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float *
    sched::join_side_streams(dev, 0, n_side);
 }
 
+// k_orientation's grid over n keypoints: one wavefront each, at most the 8 blocks per CU its 19536 B (19.1 KiB) of LDS admit
+uint32_t orientation_grid(const hesaff_ctx *c, uint32_t n) { return std::max<uint32_t>(1u, std::min<uint32_t>(n, (uint32_t)c->n_cu * 8u)); }
+
 // per image: upper bound of the T' rows its huge windows (P > 512) need, known from the scales alone
 void launch_image_large_rows(hesaff_ctx *c, const Lists &s, int B)
 {
@@ -1128,6 +1133,22 @@ struct GroupDevice : ScheduleDevice {
    {
       launch_patch_kernels(c, s, c->gray, c->b_patches2[slot].as<float>(), groups[g].lo, groups[g].large_rows, &pt, n_side);
    }
+   // the oriented order only (hesaff_set_orientation): inside the patch stage's timer bracket, like the second pass behind them
+   void orientation(int g, int slot)
+   {
+      OrientIO oi;
+      memset(&oi, 0, sizeof oi);
+      oi.patches = c->b_patches2[slot].as<float>(); oi.h_lo = groups[g].lo; oi.h_hi = groups[g].hi;
+      oi.n_ptr = &s.counters->head.hess_total; oi.cap = s.hl.cap; oi.alive = s.pw.alive; oi.A = s.pw.A;
+      hipLaunchKernelGGL(k_orientation, dim3(orientation_grid(c, groups[g].hi - groups[g].lo)), dim3(64), 0, c->stream(), oi, c->tables.view);
+   }
+   void patch_rebin(int g)
+   {
+      hipStream_t st = c->stream();
+      HIP_TRY(hipMemsetAsync(s.counters->bin_count, 0, CounterBlock::bins_bytes(), st));
+      hipLaunchKernelGGL(k_prepare_patch_second, dim3(1024), dim3(256), 0, st, s.hl, groups[g].lo, groups[g].hi, (const uint32_t *)&s.counters->head.hess_total, H, W,
+                         c->ct.consts, c->tables.view, s.pw);
+   }
    void patch_done(int) { tm.end(t_patch); }
    void descriptors(int g, int slot, sched::Stream ss)
    {
@@ -1166,7 +1187,9 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
       const GroupPlan gp = form_groups(hs, hb.large_rows(), B, c->trows_rows);
       GroupDevice dev(c, s, tm, gp.groups, pt, H, W);
       if (gp.max_n) ensure_group_buffers(c, gp.max_n);
-      sched::run_group_schedule(dev, (int)gp.groups.size(), {!c->no_overlap, c->sift_inside, with_affine, patch_side_streams(c, &pt)});
+      const sched::ScheduleOptions so = {!c->no_overlap, c->sift_inside, with_affine, patch_side_streams(c, &pt)};
+      if (c->orientation == HESAFF_ORI_DOMINANT) sched::run_group_schedule_oriented(dev, (int)gp.groups.size(), so);
+      else sched::run_group_schedule(dev, (int)gp.groups.size(), so);
    }
    t = tm.begin(T_PACK);
    // final stable compaction (hesaff.cpp:87: keys.push_back in detection order): exclusive scan of the alive flags of the batch's

@@ -44,6 +44,7 @@ extern "C" {
  *    hesaff_set_keypoint_limit / hesaff_get_keypoint_limit: two more symbols, no struct touched, the version stays 8.
  *    Likewise hesaff_set_next_masks / hesaff_set_next_masks_device (per-image detection masks): symbols only, version 8.
  *    And for the test hook hesaff_stage_sift_alive.
+ *    And for hesaff_set_orientation / hesaff_get_orientation / hesaff_stage_orientation (dominant-orientation mode): symbols only, version 8.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -384,6 +385,44 @@ int hesaff_get_keypoint_limit(const hesaff_ctx *ctx, int *n);
 int hesaff_set_next_masks(hesaff_ctx *ctx, int n, const uint8_t *const *masks, const int *strides);
 int hesaff_set_next_masks_device(hesaff_ctx *ctx, int n, const void *d_masks, int row_stride, int64_t img_stride);
 
+/* ---- dominant-orientation mode: rotation-invariant descriptors ----
+ * Replaces nothing: the reference describes every region in the "up is up" frame of rectifyAffineTransformationUpIsUp (hesaff.cpp:79,
+ * helpers.cpp:90-97) and has no other.  The detector and the affine shapes follow an in-plane rotation of the image, the descriptors
+ * of that frame do not.  With HESAFF_ORI_DOMINANT the frame of every keypoint is turned by the dominant gradient angle of its own
+ * patch, on the device, between two runs of normalizeAffine.  The definition is this library's; everything is binary32 unless stated,
+ * no FMA contraction, operations evaluated left to right as written, sqrt and / IEEE-exact.  For one keypoint, p is the 41 x 41 patch
+ * normalizeAffine produced for the up-is-up matrix A (the raw values, before photometric normalisation), M is
+ * computeCircularGaussMask(41) (hesaff_table_circ_gauss_mask), PI = (float)M_PI, atan2f as hesaff_stage_math computes it (glibc's):
+ *  1. for r, c in 1..39:  gx = p[r][c+1] - p[r][c-1],  gy = p[r+1][c] - p[r-1][c],  w = M[r][c] * sqrtf(gx*gx + gy*gy),
+ *     t = (atan2f(gy, gx) + PI) * (36.0f / (2.0f * PI)),  b = (int)t truncating, b >= 36: b -= 36;
+ *  2. row[r][b] accumulates w over c = 1..39 in increasing c, starting from +0;
+ *  3. h[b] = ((row[1][b] + row[2][b]) + ...) + row[39][b], in increasing r, starting from +0;
+ *  4. six times, circularly, every h' from the previous h:  h'[b] = ((h[b-1] + h[b]) + h[b+1]) / 3.0f;
+ *  5. m = the lowest index of the maximum of h.  h[m] == 0: theta = 0 and A' = A bit for bit.  Otherwise, with l = h[m-1], q = h[m],
+ *     r = h[m+1] (circular):  den = (l + r) - (q + q),  off = den == 0 ? 0 : (0.5f * (l - r)) / den,
+ *     theta = (((float)m + 0.5f) + off) * ((2.0f * PI) / 36.0f) - PI;
+ *  6. c, s = cos theta, sin theta of that binary32 theta, each computed in binary64 and rounded once to binary32 (the correctly
+ *     rounded value but for an angle in 3e8);  A' = A * R(theta):  a11' = a11*c + a12*s,  a12' = a12*c - a11*s,
+ *     a21' = a21*c + a22*s,  a22' = a22*c - a21*s;  normalizeAffine(image, x, y, s, A') runs again, its patch goes to the SIFT
+ *     descriptor, and A' is what the hesaff_keypoint stores.
+ * What follows:  a keypoint is described iff normalizeAffine accepts it in BOTH runs, otherwise its hesaff_region has outcome 1 and no
+ * key.  hesaff_region is unchanged: U stays un-rectified and un-turned, x, y, s, response, type, iters as in mode 0.  The ellipse and
+ * the text row are unchanged up to rounding (A' * A'^T = A * A^T); the file formats carry no orientation; theta is recoverable from
+ * a key as atan2(-a12', a11'), because the rectified a12 is 0 and a11 > 0.  One orientation per keypoint: Lowe's secondary peaks,
+ * which would make several keys of one region, are not produced.
+ * The mode is context state, like the keypoint limit.  HESAFF_ORI_UP, the default, is today's behaviour bit for bit: nothing is
+ * launched, allocated or copied for the mode.  HESAFF_ORI_DOMINANT applies to every detecting entry point (hesaff_detect_batch*,
+ * hesaff_detect_regions*, hesaff_detect_batch_device*), to hesaff_process_files and to hesaff_describe_regions* in both `from` modes
+ * (HESAFF_FROM_SHAPES rectifies the caller's U, then orients), with any parameter set - with fast = 2 the first run's patch, however
+ * it was sampled, feeds the estimator - and composes with the keypoint limit and the masks, which act before the affine stage.  It
+ * does not apply to the hesaff_stage_* operators.  The second run doubles patch_ms and, the patch stage being the longest stream, the step
+ * (measured: DESIGN.md section 7).
+ * ctx NULL or mode not 0 / 1: HESAFF_ERR_ARG (hesaff_get_orientation: ctx or mode NULL). */
+#define HESAFF_ORI_UP 0
+#define HESAFF_ORI_DOMINANT 1
+int hesaff_set_orientation(hesaff_ctx *ctx, int mode);
+int hesaff_get_orientation(const hesaff_ctx *ctx, int *mode);
+
 /* Same path with inputs already resident in device memory (bench / pipelines that decode
  * on the GPU): d_gray = n contiguous height x width 8-bit grey planes (device pointer).
  * Results stay on the device; per-image counts are copied to the two host arrays.
@@ -562,6 +601,9 @@ int hesaff_stage_sift_parts(hesaff_ctx *ctx, int n, const float *patches, float 
  * write nothing for such a keypoint: desc[n][128] goes to the device as the caller filled it and comes back, the rows of dead
  * keypoints unchanged. */
 int hesaff_stage_sift_alive(hesaff_ctx *ctx, int n, const float *patches, const int32_t *alive, uint8_t *desc);
+/* steps 1-6 of hesaff_set_orientation's definition (the production kernel, k_orientation) on n caller-supplied 41 x 41 patches:
+ * theta[n]; optionally (NULL: not wanted) hist[n][36], the histogram after smoothing, and cs[n][2] = (cos theta, sin theta) */
+int hesaff_stage_orientation(hesaff_ctx *ctx, int n, const float *patches, float *theta, float *hist, float *cs);
 /* exportKeypoints hesaff.cpp:107-130 on the device for n records in host memory (what hesaff_process_files runs per chunk):
  * format = HESAFF_OUT_TEXT: the bytes of the .hesaff.sift file, == hesaff_format_sift; HESAFF_OUT_BIN: the bytes of the sidecar,
  * == hesaff_write_bin's file.  *out is malloc'ed (hesaff_free). */

@@ -170,6 +170,9 @@ def load_library():
     L.hesaff_set_pool_priority.argtypes = [vp, C.c_int]
     L.hesaff_set_keypoint_limit.argtypes = [vp, C.c_int]
     L.hesaff_get_keypoint_limit.argtypes = [vp, C.POINTER(C.c_int)]
+    if hasattr(L, "hesaff_set_keypoint_grid"):   # (absent from an older build loaded through HESAFF_AMD_LIB for a comparison)
+        L.hesaff_set_keypoint_grid.argtypes = [vp, C.c_int, C.c_int]
+        L.hesaff_get_keypoint_grid.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     # per-image detection masks for the next detecting call (found by name, like hesaff_describe_regions)
     if hasattr(L, "hesaff_set_next_masks"):
         L.hesaff_set_next_masks.argtypes = [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
@@ -266,6 +269,7 @@ ABI_SYMBOLS = [
     "hesaff_stage_pyramid_f32", "hesaff_describe_regions", "hesaff_describe_regions_f32",
     "hesaff_set_keypoint_limit", "hesaff_get_keypoint_limit", "hesaff_set_next_masks", "hesaff_set_next_masks_device",
     "hesaff_set_orientation", "hesaff_get_orientation", "hesaff_stage_orientation",
+    "hesaff_set_keypoint_grid", "hesaff_get_keypoint_grid",
 ]
 
 # hesaff_set_orientation's modes
@@ -729,6 +733,23 @@ class HesaffContext:
     @keypoint_limit.setter
     def keypoint_limit(self, n):
         self.set_keypoint_limit(n)
+
+    def set_keypoint_grid(self, rows, cols):
+        """hesaff_set_keypoint_grid: with a keypoint limit n, every detecting call keeps the n // (rows * cols) strongest Hessian
+        keypoints of every cell of a rows x cols grid over the image (OpenCV's GridAdaptedFeatureDetector; the rule in
+        include/hesaff_amd.h), in the reference's order; (1, 1) = no grid (default).  rows * cols <= 64, and not more cells than a
+        set limit."""
+        self._check(self.L.hesaff_set_keypoint_grid(self.h, int(rows), int(cols)))
+
+    @property
+    def keypoint_grid(self):
+        r, c = C.c_int(), C.c_int()
+        self._check(self.L.hesaff_get_keypoint_grid(self.h, C.byref(r), C.byref(c)))
+        return r.value, c.value
+
+    @keypoint_grid.setter
+    def keypoint_grid(self, rows_cols):
+        self.set_keypoint_grid(*rows_cols)
 
     def set_orientation(self, mode):
         """hesaff_set_orientation: ORI_UP / "up" (default: the reference's upright frame, bit for bit) or ORI_DOMINANT / "dominant":

@@ -863,6 +863,7 @@ int hesaff_set_pool_priority(hesaff_ctx *c, int mode)
 int hesaff_set_keypoint_limit(hesaff_ctx *c, int n)
 {
    if (!c || n < 0) return HESAFF_ERR_ARG;
+   if (n > 0 && n < c->grid_rows * c->grid_cols) return HESAFF_ERR_ARG;   // a quota of 0 per cell
    c->keypoint_limit = n;
    return HESAFF_OK;
 }
@@ -871,6 +872,23 @@ int hesaff_get_keypoint_limit(const hesaff_ctx *c, int *n)
 {
    if (!c || !n) return HESAFF_ERR_ARG;
    *n = c->keypoint_limit;
+   return HESAFF_OK;
+}
+
+int hesaff_set_keypoint_grid(hesaff_ctx *c, int rows, int cols)
+{
+   if (!c || rows < 1 || cols < 1 || rows > HS_GRID_MAX_CELLS || cols > HS_GRID_MAX_CELLS || rows * cols > HS_GRID_MAX_CELLS) return HESAFF_ERR_ARG;
+   if (c->keypoint_limit > 0 && c->keypoint_limit < rows * cols) return HESAFF_ERR_ARG;   // a quota of 0 per cell
+   c->grid_rows = rows;
+   c->grid_cols = cols;
+   return HESAFF_OK;
+}
+
+int hesaff_get_keypoint_grid(const hesaff_ctx *c, int *rows, int *cols)
+{
+   if (!c || !rows || !cols) return HESAFF_ERR_ARG;
+   *rows = c->grid_rows;
+   *cols = c->grid_cols;
    return HESAFF_OK;
 }
 

@@ -107,7 +107,18 @@ struct AffineHessianDetector {
    // (onHessianKeypointsDetected, onAffineShapesFound) are not limited: their records are the caller's.
    void setKeypointLimit(int n)
    {
-      if (hesaff_set_keypoint_limit(ctx_, n) != HESAFF_OK) throw std::invalid_argument("keypoint limit must be 0 (off) or positive");
+      if (hesaff_set_keypoint_limit(ctx_, n) != HESAFF_OK)
+         throw std::invalid_argument("keypoint limit must be 0 (off) or positive, and not below the cells of a set keypoint grid");
+   }
+
+   // No counterpart in the reference (hesaff_set_keypoint_grid, include/hesaff_amd.h; OpenCV's GridAdaptedFeatureDetector): with a
+   // keypoint limit n, detectPyramidKeypoints keeps the n / (rows * cols) strongest Hessian keypoints of every cell of a rows x cols
+   // grid over the image - a budget spread over the image - in the reference's order; 1 x 1 (default): no grid.  rows * cols <= 64,
+   // and no more cells than a set limit.
+   void setKeypointGrid(int rows, int cols)
+   {
+      if (hesaff_set_keypoint_grid(ctx_, rows, cols) != HESAFF_OK)
+         throw std::invalid_argument("keypoint grid needs rows, cols >= 1, rows * cols <= 64 and at most as many cells as a set keypoint limit");
    }
 
    // No counterpart in the reference (hesaff_set_orientation, include/hesaff_amd.h), whose descriptors live in the "up is up" frame of

@@ -30,6 +30,8 @@
 //       --max-keypoints N             a keypoint budget per image (hesaff_set_keypoint_limit): the N Hessian keypoints of greatest |response|
 //                                     are kept, in the reference's order, the rest dropped on the device before findAffineShape; N bounds the
 //                                     "keypoints" count, the "affine shapes" are fewer.  Default 0 = no limit.  Batch form only.
+//       --grid RxC                    with --max-keypoints N: the N / (R * C) strongest keypoints of every cell of an R x C grid over the image
+//                                     (hesaff_set_keypoint_grid: a spatially uniform budget), R * C <= 64 and <= N.  Default 1x1 = no grid.
 //       --orientation up | dominant   the frame every region is described in (hesaff_set_orientation): the reference's "up is up" frame
 //                                     (default), or that frame turned by the dominant gradient angle of the region's own patch, which makes
 //                                     the descriptors follow an in-plane rotation of the image.  Batch form, and behind a single image.
@@ -106,7 +108,7 @@ bool parse_devices(const char *spec, std::vector<int> &out)
 // hesaff --batch: the list is cut into contiguous shards, one per device context (hesaff_shard_range); every shard runs
 // through hesaff_process_files - decode threads -> device -> writer threads, bounded memory - on its own host thread.
 int run_batch_mode(const char *list_path, const char *devices_spec, int out_format, bool dynamic, int fast, int resume, int host_share, int runtime_nice,
-                   int max_keypoints, int orientation)
+                   int max_keypoints, int orientation, int grid_rows, int grid_cols)
 {
    std::ifstream lf(list_path);
    if (!lf) { fprintf(stderr, "hesaff: cannot read list '%s'\n", list_path); return 1; }
@@ -157,6 +159,7 @@ int run_batch_mode(const char *list_path, const char *devices_spec, int out_form
       hesaff_set_output_format(ctx, out_format);
       hesaff_set_resume(ctx, resume);
       hesaff_set_keypoint_limit(ctx, max_keypoints);
+      hesaff_set_keypoint_grid(ctx, grid_rows, grid_cols);   // (main checked it against the limit)
       hesaff_set_orientation(ctx, orientation);
       hesaff_host_plan hp;   // this device's share of the host: the library's one rule (include/hesaff_amd.h)
       hesaff_host_plan_for(world * host_share, &hp);
@@ -235,8 +238,8 @@ int main(int argc, char **argv)
    for (int i = 1; i < argc; i++) batch = batch || strcmp(argv[i], "--batch") == 0;
    if (batch) {
       const char *devices = nullptr, *list = nullptr;
-      int out_format = HESAFF_OUT_TEXT, fast = 0, host_share = 1, runtime_nice = -1, max_keypoints = 0, orientation = HESAFF_ORI_UP;
-      bool bad = false, dynamic = false;
+      int out_format = HESAFF_OUT_TEXT, fast = 0, host_share = 1, runtime_nice = -1, max_keypoints = 0, orientation = HESAFF_ORI_UP, grid_rows = 1, grid_cols = 1;
+      bool bad = false, grid = false, dynamic = false;
       int resume = 0;
       for (int i = 1; i < argc && !bad; i += 2) {
          if (strcmp(argv[i], "--resume") == 0) { resume = 1; i--; continue; }
@@ -252,6 +255,14 @@ int main(int argc, char **argv)
             const long v = strtol(argv[i + 1], &end, 10);
             if (argv[i + 1][0] < '0' || argv[i + 1][0] > '9' || *end != 0 || v > 0x7fffffffL) bad = true;
             else max_keypoints = (int)v;
+         } else if (strcmp(argv[i], "--grid") == 0) {
+            // <digits>x<digits>, both at least 1, at most 64 cells
+            const char *a = argv[i + 1];
+            char *end = nullptr, *end2 = nullptr;
+            const long r = (a[0] >= '0' && a[0] <= '9') ? strtol(a, &end, 10) : 0;
+            const long cc = (end && *end == 'x' && end[1] >= '0' && end[1] <= '9') ? strtol(end + 1, &end2, 10) : 0;
+            if (r < 1 || cc < 1 || r > 64 || cc > 64 || r * cc > 64 || !end2 || *end2 != 0) bad = true;
+            else { grid_rows = (int)r; grid_cols = (int)cc; grid = true; }
          } else if (strcmp(argv[i], "--orientation") == 0) {
             if (strcmp(argv[i + 1], "up") == 0) orientation = HESAFF_ORI_UP;
             else if (strcmp(argv[i + 1], "dominant") == 0) orientation = HESAFF_ORI_DOMINANT;
@@ -269,8 +280,10 @@ int main(int argc, char **argv)
             else bad = true;
          } else bad = true;
       }
-      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1] [--max-keypoints N] [--orientation up|dominant]\n"); return 1; }
-      return run_batch_mode(list, devices, out_format, dynamic, fast, resume, host_share, runtime_nice, max_keypoints, orientation);
+      // a grid divides a budget: without --max-keypoints, or with more cells than keypoints, there is nothing to divide
+      if (grid && (max_keypoints < 1 || grid_rows * grid_cols > max_keypoints)) bad = true;
+      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1] [--max-keypoints N] [--orientation up|dominant] [--grid RxC]\n"); return 1; }
+      return run_batch_mode(list, devices, out_format, dynamic, fast, resume, host_share, runtime_nice, max_keypoints, orientation, grid_rows, grid_cols);
    }
    if (argc > 1) {
       uint8_t *data = nullptr;

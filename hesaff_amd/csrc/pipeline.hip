@@ -426,6 +426,7 @@ struct hesaff_ctx {
    int resume = 0;                     // hesaff_set_resume: 0 off, 1 skip complete outputs (O(1) test), 2 strict (rows counted)
    int pool_priority = -1;             // hesaff_set_pool_priority: -1 lower the pool's priority when the plan is CPU-starved, 0 never, 1 always
    int keypoint_limit = 0;             // hesaff_set_keypoint_limit: 0 no limit, N >= 1 the N strongest Hessian keypoints of every image (run_batch)
+   int grid_rows = 1, grid_cols = 1;   // hesaff_set_keypoint_grid: with a limit N and more than one cell, the N / cells strongest of every cell
    int orientation = HESAFF_ORI_UP;    // hesaff_set_orientation: HESAFF_ORI_DOMINANT runs the oriented order of group_schedule.h (run_keypoint_stages)
    ArmedMasks next_masks;              // hesaff_set_next_masks / _device: the masks of the next detecting call (taken, so cleared, by take_masks)
    int stage_threads = 4;              // host threads that copy a chunk's pixels into pinned memory (hesaff_process_files: within its thread budget)
@@ -1231,7 +1232,9 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
 // neither limit nor mask.  The ranks live in b_rank (free until the pack stage's scan), the kept counts in the descriptor starts
 // (written at the end of the batch), the ordered items are still in b_cand, the length detection found stays in the counter block:
 // no buffer of its own, nothing allocated.
-void select_keypoints(hesaff_ctx *c, const Lists &s, StageTimer &tm, int B, const SelMasks &mk)
+// With hesaff_set_keypoint_grid (more than one cell, and a limit) k_select_image_grid takes k_select_image's place: the limit's N /
+// cells strongest eligible keypoints of every cell of the grid over the H x W image as the caller passed it.
+void select_keypoints(hesaff_ctx *c, const Lists &s, StageTimer &tm, int B, int H, int W, const SelMasks &mk)
 {
    hipStream_t st = c->stream();
    CounterBlock *cnt = s.counters;
@@ -1241,8 +1244,14 @@ void select_keypoints(hesaff_ctx *c, const Lists &s, StageTimer &tm, int B, cons
    uint32_t *kept = (uint32_t *)sb.desc();
    uint32_t *keep_rank = c->geo.b_rank.as<uint32_t>();
    const int t = tm.begin(T_DET);
-   hipLaunchKernelGGL(k_select_image, dim3(B), dim3(HS_SEL_THREADS), 0, st, (const float *)s.hl.response, (const float *)s.hl.x, (const float *)s.hl.y,
-                      (const int32_t *)starts, (const uint32_t *)&cnt->head.hess_total, s.hl.cap, limit, mk, keep_rank, kept);
+   const int cells = c->grid_rows * c->grid_cols;
+   if (c->keypoint_limit > 0 && cells > 1)   // (the setters keep keypoint_limit >= cells: the quota is at least 1)
+      hipLaunchKernelGGL(k_select_image_grid, dim3(B), dim3(HS_SEL_THREADS), 0, st, (const float *)s.hl.response, (const float *)s.hl.x,
+                         (const float *)s.hl.y, (const int32_t *)starts, (const uint32_t *)&cnt->head.hess_total, s.hl.cap, limit / (uint32_t)cells,
+                         c->grid_rows, c->grid_cols, W, H, mk, keep_rank, kept);
+   else
+      hipLaunchKernelGGL(k_select_image, dim3(B), dim3(HS_SEL_THREADS), 0, st, (const float *)s.hl.response, (const float *)s.hl.x, (const float *)s.hl.y,
+                         (const int32_t *)starts, (const uint32_t *)&cnt->head.hess_total, s.hl.cap, limit, mk, keep_rank, kept);
    hipLaunchKernelGGL(k_select_starts, dim3(1), dim3(256), 0, st, starts, B, (const uint32_t *)kept, s.hl.cap, &cnt->head.hess_total, &cnt->head.hess_detected);
    hipLaunchKernelGGL(k_hess_deal_kept, dim3(HS_GRID_SCAT), dim3(256), 0, st, (const HessItem *)c->geo.b_cand.p, (const uint32_t *)&cnt->head.hess_detected,
                       (const uint32_t *)keep_rank, (const int32_t *)starts, s.hl);
@@ -1261,7 +1270,7 @@ BatchResult run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W, 
    Lists s = make_lists(c);
    const int tt = tm.begin(T_TOTAL);
    run_detection(c, src, B, s, tm, false, nullptr);
-   if (c->keypoint_limit > 0 || mk.base) select_keypoints(c, s, tm, B, mk);
+   if (c->keypoint_limit > 0 || mk.base) select_keypoints(c, s, tm, B, H, W, mk);
    // the one host round trip of a batch
    return run_keypoint_stages(c, s, tm, tt, B, H, W, fetch_hessian_starts(c, B), true);
 }

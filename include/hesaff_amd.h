@@ -42,6 +42,7 @@ extern "C" {
  *    needs them finds them by symbol (dlsym) in the library it loaded.  The same holds for hesaff_describe_regions and
  *    hesaff_describe_regions_f32 (HESAFF_FROM_POINTS / HESAFF_FROM_SHAPES): new symbols over the structs of version 8.  And for
  *    hesaff_set_keypoint_limit / hesaff_get_keypoint_limit: two more symbols, no struct touched, the version stays 8.
+ *    hesaff_set_keypoint_grid / hesaff_get_keypoint_grid: two more symbols, no struct touched, the version stays 8.
  *    Likewise hesaff_set_next_masks / hesaff_set_next_masks_device (per-image detection masks): symbols only, version 8.
  *    And for the test hook hesaff_stage_sift_alive.
  *    And for hesaff_set_orientation / hesaff_get_orientation / hesaff_stage_orientation (dominant-orientation mode): symbols only, version 8.
@@ -384,6 +385,35 @@ int hesaff_get_keypoint_limit(const hesaff_ctx *ctx, int *n);
  * usable after every refusal. */
 int hesaff_set_next_masks(hesaff_ctx *ctx, int n, const uint8_t *const *masks, const int *strides);
 int hesaff_set_next_masks_device(hesaff_ctx *ctx, int n, const void *d_masks, int row_stride, int64_t img_stride);
+
+/* ---- a spatially uniform keypoint budget: the N / (rows * cols) strongest Hessian keypoints of every cell of a grid ----
+ * OpenCV 2.4's GridAdaptedFeatureDetector(detector, maxTotalKeypoints, gridRows, gridCols), with one stated difference: OpenCV runs the
+ * detector on every sub-image, here the selection is taken from the full image's detection, so there are no border effects at the
+ * seams of the cells.  The context holds a grid R x C, default 1 x 1 (no grid).  With keypoint limit N >= 1 and R * C > 1 let
+ * Q = N / (R * C) in integer division.  For an image of W x H pixels as the caller passed it (also with upscaleInputImage = 1, as for
+ * the masks):
+ *  - keypoint i has the pixel col = clamp((int)(x + 0.5f), 0, W - 1), row = clamp((int)(y + 0.5f), 0, H - 1) - the add in binary32, the
+ *    conversion truncating: the masks' rule, the same code;
+ *  - its cell is cr * C + cc with cr = ((row + 1) * R - 1) / H and cc = ((col + 1) * C - 1) / W in integer division: the closed form
+ *    of OpenCV's cell ranges, row in [cr * H / R, (cr + 1) * H / R) and columns likewise.  It is NOT row * R / H: the two differ wherever
+ *    H is no multiple of R;
+ *  - a keypoint is eligible under the masks' rule (an image without a mask: every keypoint);
+ *  - an eligible keypoint i of cell k is kept iff
+ *       #{j eligible in cell k : |r_j| > |r_i|} + #{j < i, eligible in cell k : |r_j| == |r_i|} < Q:
+ *    mask first, then the Q strongest of every cell; ties at a cell's cut go to the earlier keypoint of the reference's order;
+ *  - the unused quota of a sparse cell is not handed to other cells (OpenCV's adapter does not do that either).
+ * count_hessian is the number kept, at most Q * R * C <= N.  Kept keypoints stay in the reference's order; each hesaff_region equals its
+ * unlimited record except `key`, which is renumbered, and each hesaff_keypoint has the bytes of its unlimited key.  The result does not
+ * depend on launch geometry and is the same from run to run.
+ * Limit 0 with a grid set: the grid is inert.  A 1 x 1 grid: hesaff_set_keypoint_limit's rule, and its code path.
+ * Scope: the limit's - every detecting entry point and hesaff_process_files, with any parameter set and orientation mode; not
+ * hesaff_describe_regions* nor the hesaff_stage_* operators.
+ * rows, cols >= 1 and rows * cols <= 64.  HESAFF_ERR_ARG: ctx NULL; a getter pointer NULL; a value out of range; a grid that would leave
+ * Q = 0 under the current limit (0 < N < rows * cols).  hesaff_set_keypoint_limit likewise refuses 0 < n < R * C under the current grid
+ * (with the default grid it accepts what it always did).  A refused call changes no state, so the two setters never leave a context that
+ * a detecting call would have to refuse: to go from (N, R x C) to a smaller N and a smaller grid, set the grid first. */
+int hesaff_set_keypoint_grid(hesaff_ctx *ctx, int rows, int cols);
+int hesaff_get_keypoint_grid(const hesaff_ctx *ctx, int *rows, int *cols);
 
 /* ---- dominant-orientation mode: rotation-invariant descriptors ----
  * Replaces nothing: the reference describes every region in the "up is up" frame of rectifyAffineTransformationUpIsUp (hesaff.cpp:79,

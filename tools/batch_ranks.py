@@ -11,6 +11,7 @@ Rank 0 prints one JSON line with the totals."""
 import argparse
 import json
 import os
+import re
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -25,9 +26,18 @@ def main():
     ap.add_argument("--chunk", type=int, default=32, help="images per device chunk (hesaff_params.max_batch)")
     ap.add_argument("--max-keypoints", type=int, default=0,
                     help="keep the N Hessian keypoints of greatest |response| per image (hesaff_set_keypoint_limit; 0: no limit)")
+    ap.add_argument("--grid", default="1x1", metavar="RxC",
+                    help="with --max-keypoints N: the N // (R * C) strongest keypoints of every cell of an R x C grid over the image "
+                         "(hesaff_set_keypoint_grid; R * C <= 64 and <= N; 1x1: no grid)")
     args = ap.parse_args()
     if args.max_keypoints < 0:
         ap.error("--max-keypoints must be 0 (no limit) or positive")
+    m = re.fullmatch(r"([0-9]+)x([0-9]+)", args.grid)
+    grid = (int(m.group(1)), int(m.group(2))) if m else (0, 0)
+    if min(grid) < 1 or grid[0] * grid[1] > 64:
+        ap.error("--grid is RxC with R, C >= 1 and R * C <= 64")
+    if grid != (1, 1) and grid[0] * grid[1] > args.max_keypoints:
+        ap.error("--grid needs --max-keypoints N with N >= R * C")
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1")); local = int(os.environ.get("LOCAL_RANK", "0"))
     backend = None
     if world > 1:
@@ -43,6 +53,7 @@ def main():
     p.max_batch = max(1, args.chunk)
     ctx = hesaff_amd.HesaffContext(p, device=0 if args.one_device else local)
     ctx.set_keypoint_limit(args.max_keypoints)
+    ctx.set_keypoint_grid(*grid)
     # the rank's shard through hesaff_process_files (what `hesaff --batch` runs per device): decode ahead, device, rows formatted
     # on the device, write behind - with this rank's share of the host threads
     hp = hesaff_amd.host_plan(max(world, 1))   # the library's one rule (hesaff_host_plan_for): this rank's share of the host

@@ -220,6 +220,7 @@ def load_library():
     L.hesaff_stage_half_image.argtypes = [vp, _f32p, C.c_int, C.c_int, _f32p]
     L.hesaff_stage_pyramid.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
     L.hesaff_stage_hessian_keypoints.argtypes = [vp, _u8p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, C.POINTER(C.c_int)]
+    L.hesaff_stage_detect_planes.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
     L.hesaff_stage_find_affine_shape.argtypes = [vp, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _f32p, _i32p]
     L.hesaff_stage_rectify.argtypes = [vp, C.c_int, _f32p]
     L.hesaff_stage_normalize_affine.argtypes = [vp, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _i32p, _f32p]
@@ -269,7 +270,7 @@ ABI_SYMBOLS = [
     "hesaff_stage_pyramid_f32", "hesaff_describe_regions", "hesaff_describe_regions_f32",
     "hesaff_set_keypoint_limit", "hesaff_get_keypoint_limit", "hesaff_set_next_masks", "hesaff_set_next_masks_device",
     "hesaff_set_orientation", "hesaff_get_orientation", "hesaff_stage_orientation",
-    "hesaff_set_keypoint_grid", "hesaff_get_keypoint_grid",
+    "hesaff_set_keypoint_grid", "hesaff_get_keypoint_grid", "hesaff_stage_detect_planes",
 ]
 
 # hesaff_set_orientation's modes
@@ -859,6 +860,24 @@ class HesaffContext:
         self._check(self.L.hesaff_stage_hessian_keypoints(self.h, g, g.shape[0], g.shape[1], cap, f, i, C.byref(cnt)))
         n = min(cnt.value, cap)
         return f[:n].copy(), i[:n].copy(), cnt.value
+
+    def detect_planes(self, L, R, band=0, cap=None):
+        """hesaff_stage_detect_planes: the detection chain on the blur planes L and response planes R of one octave, [5, rows, cols] or
+        [n_images, 5, rows, cols] (finite values).  band: 0 = the batch path's choice, or 32, 64, 128.
+        -> f[n,5], i[n,5] as hessian_keypoints (octave 0), image[n], count."""
+        L = np.ascontiguousarray(L, np.float32); R = np.ascontiguousarray(R, np.float32)
+        if L.ndim == 3:
+            L = L[None]; R = R[None]
+        if L.ndim != 4 or L.shape[1] != 5 or R.shape != L.shape:
+            raise ValueError("L and R must both be [n_images, 5, rows, cols]")
+        nimg, _, rows, cols = L.shape
+        if cap is None:
+            cap = max(4096, int(nimg * rows * cols * 0.05))
+        f = np.zeros((cap, 5), np.float32); i = np.zeros((cap, 5), np.int32); im = np.zeros(cap, np.int32); cnt = C.c_int()
+        self._check(self.L.hesaff_stage_detect_planes(self.h, nimg, rows, cols, L.ctypes.data, R.ctypes.data, int(band), cap,
+                                                      f.ctypes.data, i.ctypes.data, im.ctypes.data, C.byref(cnt)))
+        n = min(cnt.value, cap)
+        return f[:n].copy(), i[:n].copy(), im[:n].copy(), cnt.value
 
     def find_affine_shape(self, blur, kp):
         blur = np.ascontiguousarray(blur, np.float32); kp = np.ascontiguousarray(kp, np.float32).reshape(-1, 4)

@@ -1088,6 +1088,27 @@ int hesaff_stage_pyramid_f32(hesaff_ctx *c, const float *plane, int rows, int co
    return stage_pyramid(c, plane, true, rows, cols, planes, n_octaves, n_floats);
 }
 
+// the first m entries of the ordered Hessian list as the stage entry points return them (image: optional)
+static void fetch_hessian_list(hesaff_ctx *c, const Lists &s, int m, float *f, int32_t *iv, int32_t *image)
+{
+   std::vector<float> x(m), y(m), sc(m), resp(m);
+   std::vector<int32_t> meta(m), key(m);
+   HIP_TRY(hipMemcpy(x.data(), s.hl.x, (size_t)m * 4, hipMemcpyDeviceToHost));
+   HIP_TRY(hipMemcpy(y.data(), s.hl.y, (size_t)m * 4, hipMemcpyDeviceToHost));
+   HIP_TRY(hipMemcpy(sc.data(), s.hl.s, (size_t)m * 4, hipMemcpyDeviceToHost));
+   HIP_TRY(hipMemcpy(resp.data(), s.hl.response, (size_t)m * 4, hipMemcpyDeviceToHost));
+   HIP_TRY(hipMemcpy(meta.data(), s.hl.meta, (size_t)m * 4, hipMemcpyDeviceToHost));
+   HIP_TRY(hipMemcpy(key.data(), s.hl.r0c0, (size_t)m * 4, hipMemcpyDeviceToHost));
+   for (int i = 0; i < m; i++) {
+      const int octave = (meta[i] >> 4) & 15, level = (meta[i] >> 2) & 3, type = meta[i] & 3;
+      const OctGeom &g = c->oct[octave];
+      const uint32_t pix = (uint32_t)key[i] % (uint32_t)(g.rows * g.cols);
+      f[5 * i] = x[i]; f[5 * i + 1] = y[i]; f[5 * i + 2] = sc[i]; f[5 * i + 3] = c->ct.consts.pd0 * (float)(1 << octave); f[5 * i + 4] = resp[i];
+      iv[5 * i] = type; iv[5 * i + 1] = octave; iv[5 * i + 2] = level; iv[5 * i + 3] = (int32_t)(pix / g.cols); iv[5 * i + 4] = (int32_t)(pix % g.cols);
+      if (image) image[i] = meta[i] >> 8;
+   }
+}
+
 int hesaff_stage_hessian_keypoints(hesaff_ctx *c, const uint8_t *gray, int rows, int cols, int cap, float *f, int32_t *iv, int *count)
 {
    if (!c || !gray || rows < 1 || cols < 1 || !count) return HESAFF_ERR_ARG;
@@ -1107,23 +1128,52 @@ int hesaff_stage_hessian_keypoints(hesaff_ctx *c, const uint8_t *gray, int rows,
    const int n = (int)cn.hess_total;
    *count = n;
    const int m = std::min(n, cap);
-   if (m > 0 && f && iv) {
-      std::vector<float> x(m), y(m), sc(m), resp(m);
-      std::vector<int32_t> meta(m), key(m);
-      HIP_TRY(hipMemcpy(x.data(), s.hl.x, (size_t)m * 4, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(y.data(), s.hl.y, (size_t)m * 4, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(sc.data(), s.hl.s, (size_t)m * 4, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(resp.data(), s.hl.response, (size_t)m * 4, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(meta.data(), s.hl.meta, (size_t)m * 4, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(key.data(), s.hl.r0c0, (size_t)m * 4, hipMemcpyDeviceToHost));
-      for (int i = 0; i < m; i++) {
-         const int octave = (meta[i] >> 4) & 15, level = (meta[i] >> 2) & 3, type = meta[i] & 3;
-         const OctGeom &g = c->oct[octave];
-         const uint32_t pix = (uint32_t)key[i] % (uint32_t)(g.rows * g.cols);
-         f[5 * i] = x[i]; f[5 * i + 1] = y[i]; f[5 * i + 2] = sc[i]; f[5 * i + 3] = c->ct.consts.pd0 * (float)(1 << octave); f[5 * i + 4] = resp[i];
-         iv[5 * i] = type; iv[5 * i + 1] = octave; iv[5 * i + 2] = level; iv[5 * i + 3] = (int32_t)(pix / g.cols); iv[5 * i + 4] = (int32_t)(pix % g.cols);
+   if (m > 0 && f && iv) fetch_hessian_list(c, s, m, f, iv, nullptr);
+   HS_API_END(c)
+}
+
+// The detection chain on the caller's planes: what run_detection does with an octave's planes once it has made them (begin_detection,
+// detect_octave, order_hessian_list: pipeline.hip), on octave 0 of a plan for n_images x rows x cols.
+int hesaff_stage_detect_planes(hesaff_ctx *c, int n_images, int rows, int cols, const float *L, const float *R, int band, int cap, float *f,
+                               int32_t *iv, int32_t *image, int *count)
+{
+   const int min_size = 2 * HS_BORDER + 2;   // pyramid.cpp:283: the smallest plane that is an octave
+   if (!c || !L || !R || !count || n_images < 1 || rows <= min_size || cols <= min_size) return HESAFF_ERR_ARG;
+   if (band != 0 && band != 32 && band != 64 && band != 128) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   bind_device(c);
+   if (c->ct.up) throw HsError(HESAFF_ERR_ARG, "hesaff_stage_detect_planes: the planes are the first pyramid level as given; not with upscaleInputImage");
+   plan(c, n_images, rows, cols);
+   const OctGeom &g = c->oct[0];
+   hipStream_t st = c->stream();
+   const size_t planeF = (size_t)n_images * g.rows * g.pitch, tight = (size_t)rows * cols;
+   DPlane Lo[5], Ro[5];
+   for (int l = 0; l < 3; l++) Lo[l] = c->L[l];
+   Lo[3] = make_plane(c->geo.b_L3.as<float>(), g.rows, g.cols, g.pitch);
+   Lo[4] = make_plane(nullptr, 0, 0, 0);   // L4 is never read by detection (getHessianPointType reads L1..L3)
+   for (int l = 0; l < 5; l++) Ro[l] = make_plane(c->geo.b_R.as<float>() + l * planeF, g.rows, g.cols, g.pitch);
+   // cols floats per row: the pitch padding behind them keeps what it held.  k_extrema_march's clamped 16-byte loads read it, as they do on
+   // the batch path (the blur kernels store cols floats too); it can only reach columns that are not scanned
+   for (int b = 0; b < n_images; b++)
+      for (int l = 0; l < 5; l++) {
+         const size_t off = ((size_t)b * 5 + l) * tight;
+         HIP_TRY(hipMemcpy2DAsync(Ro[l].img(b), (size_t)g.pitch * 4, R + off, (size_t)cols * 4, (size_t)cols * 4, rows, hipMemcpyHostToDevice, st));
+         if (l < 4) HIP_TRY(hipMemcpy2DAsync(Lo[l].img(b), (size_t)g.pitch * 4, L + off, (size_t)cols * 4, (size_t)cols * 4, rows, hipMemcpyHostToDevice, st));
       }
-   }
+   c->ev_used = 0;
+   StageTimer tm(c);
+   Lists s = make_lists(c);
+   begin_detection(c, s, n_images);
+   detect_octave(c, s, tm, n_images, 0, Lo, Ro, band);
+   order_hessian_list(c, s, tm, n_images);
+   CounterHead cn;
+   HIP_TRY(hipMemcpyAsync(&cn, &s.counters->head, sizeof cn, hipMemcpyDeviceToHost, st));
+   finish_stream(c);
+   if (cn.overflow != 0 || cn.rec > c->cap) throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded");
+   const int n = (int)cn.hess_total;
+   *count = n;
+   const int m = std::min(n, cap);
+   if (m > 0 && f && iv) fetch_hessian_list(c, s, m, f, iv, image);
    HS_API_END(c)
 }
 

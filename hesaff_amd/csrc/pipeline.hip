@@ -839,6 +839,79 @@ void launch_image_large_rows(hesaff_ctx *c, const Lists &s, int B)
                       sb.large_rows(), B, c->tables.view.max_p0);
 }
 
+// The three steps of detection that follow the response planes.  run_detection calls them on the planes it has just made,
+// hesaff_stage_detect_planes (capi_impl.h) on the planes of its caller: one set of launches for both.
+// begin_detection: the counters, the bitmask and the order-key map before the first octave of a batch
+void begin_detection(hesaff_ctx *c, const Lists &s, int B)
+{
+   hipStream_t st = c->stream();
+   HIP_TRY(hipMemsetAsync(s.counters, 0, sizeof(CounterBlock), st));
+   HIP_TRY(hipMemsetAsync(c->geo.b_bitmask.p, 0, std::max<size_t>((size_t)B * c->words_per_image * 8, 8), st));
+   // octaveMap (pyramid.cpp:226: zeroed per octave): the order-key map is filled with "free" when it is new; every pass over an octave then bids
+   // with keys of a fresh, smaller epoch (OctaveCtx::map_epoch), so what earlier passes left behind never wins - no fill and no reset per octave
+   if (c->map_epochs.begin_batch()) HIP_TRY(hipMemsetAsync(c->geo.b_map.p, 0xFF, c->geo.b_map.bytes, st));
+}
+
+// detect_octave: extrema scan, localisation and the octaveMap rule on octave o, whose blur planes are Lo[0..3] and response planes Ro[0..4].
+// band_override: the band height of k_extrema_march (0: extrema_band's choice; only the stage entry point passes anything else).
+void detect_octave(hesaff_ctx *c, const Lists &s, StageTimer &tm, int B, size_t o, const DPlane *Lo, const DPlane *Ro, int band_override = 0)
+{
+   const hesaff::OctaveSchedule &sc = c->ct.sched;
+   hipStream_t st = c->stream();
+   CounterBlock *cnt = s.counters;
+   const OctGeom &g = c->oct[o];
+   const int t = tm.begin(T_DET);
+   HIP_TRY(hipMemsetAsync(&cnt->head.cand, 0, 4, st));
+   HIP_TRY(hipMemcpyAsync(&cnt->oct_rec_start[o], &cnt->head.rec, 4, hipMemcpyDeviceToDevice, st));
+   OctaveCtx oc;
+   for (int l = 0; l < 5; l++) { oc.R[l] = Ro[l]; oc.L[l] = Lo[l]; oc.sigma[l] = sc.level_sigma[l]; }
+   oc.pixelDistance = c->ct.consts.pd0 * (float)(1 << o);   // pyramid.cpp:288: doubles per octave
+   oc.octave = (int)o;
+   oc.map = c->geo.b_map.as<uint32_t>();
+   // a fresh epoch for this pass (counting down; the all-ones epoch is the fill value): refill when they have run out
+   const OrderMapEpochs::Pass pass = c->map_epochs.next_pass();
+   if (pass.refill_first) HIP_TRY(hipMemsetAsync(c->geo.b_map.p, 0xFF, c->geo.b_map.bytes, st));
+   oc.map_epoch = pass.epoch_bits;
+   oc.word_base = g.word_base;
+   oc.words_per_image = c->words_per_image;
+   oc.words_per_row = g.words_per_row;
+   if (g.rows > 2 * HS_BORDER && g.cols > 2 * HS_BORDER) {
+      FivePlanes fp;
+      for (int l = 0; l < 5; l++) fp.R[l] = Ro[l];
+      const int strips = (g.cols + EXM_STRIP - 1) / EXM_STRIP;
+      const int band = band_override > 0 ? band_override : extrema_band(g.rows, g.cols, B);
+      const dim3 grid(strips, (g.rows + band - 1) / band, B);
+      const int te = tm.begin(T_EXTREMA, 20.0 * (double)B * g.rows * g.cols);
+      hipLaunchKernelGGL(k_extrema_march, grid, dim3(64), 0, st, fp, c->ct.consts.positiveThreshold, c->ct.consts.negativeThreshold, s.cl, band);
+      tm.end(te);
+      hipLaunchKernelGGL(k_localize, dim3(HS_GRID_LOC), dim3(256), 0, st, oc, s.cl, s.rl, c->ct.consts);
+      hipLaunchKernelGGL(k_dedupe, dim3(HS_GRID_DED), dim3(256), 0, st, oc, s.rl, (const uint32_t *)&cnt->oct_rec_start[o],
+                         c->geo.b_bitmask.as<unsigned long long>());
+   }
+   tm.end(t);
+}
+
+// order_hessian_list: the surviving records of all octaves at their ranks in the reference's detection order, and the per-image starts
+void order_hessian_list(hesaff_ctx *c, const Lists &s, StageTimer &tm, int B)
+{
+   hipStream_t st = c->stream();
+   CounterBlock *cnt = s.counters;
+   const int t = tm.begin(T_DET);
+   const long long total_words = (long long)B * c->words_per_image;
+   LoadPopc lp; lp.p = c->geo.b_bitmask.as<unsigned long long>();
+   exclusive_scan(c, lp, total_words, c->geo.b_prefix.as<uint32_t>(), &cnt->head.hess_total);
+   // the records at their ranks as 32-byte items (in the candidate buffer: its last reader, the last octave's k_localize, is done), then dealt out
+   HessItem *items = reinterpret_cast<HessItem *>(c->geo.b_cand.p);
+   static_assert(sizeof(HessItem) == 32 && sizeof(CandRec) >= sizeof(HessItem), "the items fit the candidate slots (cand_cap >= cap)");
+   hipLaunchKernelGGL(k_scatter_ordered, dim3(HS_GRID_SCAT), dim3(256), 0, st, s.rl, (const unsigned long long *)c->geo.b_bitmask.p,
+                      (const uint32_t *)c->geo.b_prefix.p, items, s.hl.cap);
+   hipLaunchKernelGGL(k_hess_deal, dim3(HS_GRID_SCAT), dim3(256), 0, st, (const HessItem *)items, (const uint32_t *)&cnt->head.hess_total, s.hl);
+   hipLaunchKernelGGL(k_image_counts, dim3((B + 1 + 63) / 64), dim3(64), 0, st, (const uint32_t *)c->geo.b_prefix.p,
+                      c->words_per_image, B, (const uint32_t *)&cnt->head.hess_total, c->geo.b_starts.as<int32_t>());
+   launch_image_large_rows(c, s, B);
+   tm.end(t);
+}
+
 // The scale-space + detection part for the current plan; fills the ordered Hessian list.
 // src: the B device images of the batch (SrcImages: 8-bit with 1 or 3 interleaved channels, or float planes).
 // detect = false (hesaff_describe_regions): the scale space alone - the grey plane and every level findAffineShape can be asked to run
@@ -849,15 +922,8 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
 {
    const hesaff::OctaveSchedule &sc = c->ct.sched;
    hipStream_t st = c->stream();
-   CounterBlock *cnt = s.counters;
    const float *ptaps = c->tables.pyr_taps.as<float>();
-   if (detect) {
-      HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(CounterBlock), st));
-      HIP_TRY(hipMemsetAsync(c->geo.b_bitmask.p, 0, std::max<size_t>((size_t)B * c->words_per_image * 8, 8), st));
-      // octaveMap (pyramid.cpp:226: zeroed per octave): the order-key map is filled with "free" when it is new; every pass over an octave then bids
-      // with keys of a fresh, smaller epoch (OctaveCtx::map_epoch), so what earlier passes left behind never wins - no fill and no reset per octave
-      if (c->map_epochs.begin_batch()) HIP_TRY(hipMemsetAsync(c->geo.b_map.p, 0xFF, c->geo.b_map.bytes, st));
-   }
+   if (detect) begin_detection(c, s, B);
 
    int t = tm.begin(T_PYR);
    DPlane none = make_plane(nullptr, 0, 0, 0);
@@ -966,53 +1032,10 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
          }
       }
       if (!detect) continue;
-      // ---- detection on this octave ----
-      t = tm.begin(T_DET);
-      HIP_TRY(hipMemsetAsync(&cnt->head.cand, 0, 4, st));
-      HIP_TRY(hipMemcpyAsync(&cnt->oct_rec_start[o], &cnt->head.rec, 4, hipMemcpyDeviceToDevice, st));
-      OctaveCtx oc;
-      for (int l = 0; l < 5; l++) { oc.R[l] = Ro[l]; oc.L[l] = Lo[l]; oc.sigma[l] = sc.level_sigma[l]; }
-      oc.pixelDistance = c->ct.consts.pd0 * (float)(1 << o);   // pyramid.cpp:288: doubles per octave
-      oc.octave = (int)o;
-      oc.map = c->geo.b_map.as<uint32_t>();
-      // a fresh epoch for this pass (counting down; the all-ones epoch is the fill value): refill when they have run out
-      const OrderMapEpochs::Pass pass = c->map_epochs.next_pass();
-      if (pass.refill_first) HIP_TRY(hipMemsetAsync(c->geo.b_map.p, 0xFF, c->geo.b_map.bytes, st));
-      oc.map_epoch = pass.epoch_bits;
-      oc.word_base = g.word_base;
-      oc.words_per_image = c->words_per_image;
-      oc.words_per_row = g.words_per_row;
-      if (g.rows > 2 * HS_BORDER && g.cols > 2 * HS_BORDER) {
-         FivePlanes fp;
-         for (int l = 0; l < 5; l++) fp.R[l] = Ro[l];
-         const int strips = (g.cols + EXM_STRIP - 1) / EXM_STRIP;
-         const int band = extrema_band(g.rows, g.cols, B);
-         const dim3 grid(strips, (g.rows + band - 1) / band, B);
-         const int te = tm.begin(T_EXTREMA, 20.0 * (double)B * g.rows * g.cols);
-         hipLaunchKernelGGL(k_extrema_march, grid, dim3(64), 0, st, fp, c->ct.consts.positiveThreshold, c->ct.consts.negativeThreshold, s.cl, band);
-         tm.end(te);
-         hipLaunchKernelGGL(k_localize, dim3(HS_GRID_LOC), dim3(256), 0, st, oc, s.cl, s.rl, c->ct.consts);
-         hipLaunchKernelGGL(k_dedupe, dim3(HS_GRID_DED), dim3(256), 0, st, oc, s.rl, (const uint32_t *)&cnt->oct_rec_start[o],
-                            c->geo.b_bitmask.as<unsigned long long>());
-      }
-      tm.end(t);
+      detect_octave(c, s, tm, B, o, Lo, Ro);
    }
    if (!detect) return;
-   // ---- ordering ----
-   t = tm.begin(T_DET);
-   const long long total_words = (long long)B * c->words_per_image;
-   LoadPopc lp; lp.p = c->geo.b_bitmask.as<unsigned long long>();
-   exclusive_scan(c, lp, total_words, c->geo.b_prefix.as<uint32_t>(), &cnt->head.hess_total);
-   // the records at their ranks as 32-byte items (in the candidate buffer: its last reader, the last octave's k_localize, is done), then dealt out
-   HessItem *items = reinterpret_cast<HessItem *>(c->geo.b_cand.p);
-   static_assert(sizeof(HessItem) == 32 && sizeof(CandRec) >= sizeof(HessItem), "the items fit the candidate slots (cand_cap >= cap)");
-   hipLaunchKernelGGL(k_scatter_ordered, dim3(HS_GRID_SCAT), dim3(256), 0, st, s.rl, (const unsigned long long *)c->geo.b_bitmask.p,
-                      (const uint32_t *)c->geo.b_prefix.p, items, s.hl.cap);
-   hipLaunchKernelGGL(k_hess_deal, dim3(HS_GRID_SCAT), dim3(256), 0, st, (const HessItem *)items, (const uint32_t *)&cnt->head.hess_total, s.hl);
-   hipLaunchKernelGGL(k_image_counts, dim3((B + 1 + 63) / 64), dim3(64), 0, st, (const uint32_t *)c->geo.b_prefix.p,
-                      c->words_per_image, B, (const uint32_t *)&cnt->head.hess_total, c->geo.b_starts.as<int32_t>());
-   launch_image_large_rows(c, s, B);
-   tm.end(t);
+   order_hessian_list(c, s, tm, B);
 }
 
 __global__ void k_desc_starts(const int32_t *__restrict__ hess_starts, int nimg, const uint32_t *__restrict__ rank,

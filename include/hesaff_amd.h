@@ -46,6 +46,7 @@ extern "C" {
  *    Likewise hesaff_set_next_masks / hesaff_set_next_masks_device (per-image detection masks): symbols only, version 8.
  *    And for the test hook hesaff_stage_sift_alive.
  *    And for hesaff_set_orientation / hesaff_get_orientation / hesaff_stage_orientation (dominant-orientation mode): symbols only, version 8.
+ *    And for the stage entry point hesaff_stage_detect_planes.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -605,6 +606,18 @@ int hesaff_stage_pyramid_f32(hesaff_ctx *ctx, const float *plane, int rows, int 
  * type,octave,level,r0,c0 in reference order; returns n in *count (cap = array capacity). */
 int hesaff_stage_hessian_keypoints(hesaff_ctx *ctx, const uint8_t *gray, int rows, int cols, int cap,
                                    float *f, int32_t *i, int *count);
+/* The same chain - extrema scan (pyramid.cpp:206-222), localizeKeypoint (:122-204) with the octaveMap rule, getHessianPointType
+ * (:24-37) and the ordering - on planes of the caller's instead of an image's: L and R are [n_images][5][rows][cols] floats each, tightly
+ * packed, the blur planes L0..L4 and the response planes R0..R4 of ONE octave (L4 is not read).  They are taken as octave 0: the octave
+ * index returned is 0 and pixelDistance is that of the first level.  f and i as above, image[n] = the index of the image; the order is the
+ * reference's (image, level, r0, c0).  band: the rows one wavefront of the extrema scan marches down - 0 for the height the batch
+ * path would choose for this size, or 32, 64 or 128 (every height gives the same list).
+ * Domain: every value of L and R is finite.  NaN and infinities are outside it - the response of a finite blur plane is finite - and
+ * what the chain makes of them is not specified.
+ * HESAFF_ERR_ARG: rows or cols <= 2 * 5 + 2 (no octave, pyramid.cpp:283), another band, a NULL plane, a context with upscaleInputImage.
+ * HESAFF_ERR_CAPACITY: more candidates or keypoints than the plan for this size holds, as for an image. */
+int hesaff_stage_detect_planes(hesaff_ctx *ctx, int n_images, int rows, int cols, const float *L, const float *R, int band, int cap,
+                               float *f, int32_t *i, int32_t *image, int *count);
 /* AffineShape::findAffineShape affine.cpp:35-100 for n keypoints on one blur plane.
  * kp[n][4] = x,y,s,pixelDistance; out: converged[n], U[n][4] (a11,a12,a21,a22 as passed to
  * onAffineShapeFound affine.h:50-57), iters[n]. */

@@ -428,6 +428,24 @@ struct HessKp {   // arguments of onHessianKeypointDetected (pyramid.h:46) + pro
    int r0, c0;          // initial extremum pixel
 };
 
+// One record per candidate of the extrema scan when Oracle::tracing is set: which way localizeKeypoint left, and what it had computed
+// by then.  Test infrastructure (tests/test_detect_edges.py): it proves that a constructed input takes the branch it was built for.
+enum TraceExit {
+   TX_KEPT = 0, TX_EDGE_HIGH = 1 /* edgeScore >= threshold */, TX_EDGE_NEG = 2 /* edgeScore < 0 */, TX_NAN = 3 /* NaN after the solve */,
+   TX_OUT_RIGHT = 4 /* c < cols - 3 failed */, TX_OUT_DOWN = 5 /* r < rows - 3 */, TX_OUT_LEFT = 6 /* c > 3 */, TX_OUT_UP = 7 /* r > 3 */,
+   TX_SHIFT = 8 /* |b| > 1.5 */, TX_WEAK = 9 /* |val| < finalThreshold */, TX_TAKEN = 10 /* octaveMap cell already taken */
+};
+struct TraceRec {
+   int level, r0, c0;
+   int iters;           // iterations of the loop that were entered
+   int rf, cf;          // the centre of the last iteration
+   int path[5][2];      // the centre (r, c) of every iteration that was entered, -1 beyond
+   int exit;            // TraceExit
+   uint32_t b[3], val;  // bits of b[0..2] and val as they were at the exit
+   uint32_t edge;       // bits of the first iteration's edgeScore
+};
+inline uint32_t bitsOf(float v) { uint32_t u; memcpy(&u, &v, 4); return u; }
+
 struct AffRes {   // result of findAffineShape (affine.cpp:35-100)
    int converged;
    float a11, a12, a21, a22;
@@ -460,6 +478,8 @@ struct Oracle {
    bool keepPlanes = false;
    bool detectOnly = false;                       // stop after Hessian keypoints
    long nCandidates = 0;
+   bool tracing = false;                          // keep a TraceRec per candidate (off by default)
+   std::vector<TraceRec> trace;
 
    Oracle() { configure(); }
 
@@ -715,15 +735,28 @@ struct Oracle {
       float b[3] = {0, 0, 0};
       float val = 0;
       int nr = r, nc = c;
+      // (the recorder: no part of the arithmetic)
+      int iters = 0;
+      int path[5][2] = {{-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}};
+      uint32_t edgeBits = 0;
+      auto leave = [&](int exit) {
+         if (!tracing) return;
+         TraceRec t{level, r0, c0, iters, r, c, {}, exit, {bitsOf(b[0]), bitsOf(b[1]), bitsOf(b[2])}, bitsOf(val), edgeBits};
+         memcpy(t.path, path, sizeof path);
+         trace.push_back(t);
+      };
       for (int iter = 0; iter < 5; iter++) {
          r = nr; c = nc;
+         iters = iter + 1;
+         path[iter][0] = r; path[iter][1] = c;
          const float dxx = cur.at(r, c - 1) - 2.0f * cur.at(r, c) + cur.at(r, c + 1);
          const float dyy = cur.at(r - 1, c) - 2.0f * cur.at(r, c) + cur.at(r + 1, c);
          const float dss = low.at(r, c) - 2.0f * cur.at(r, c) + high.at(r, c);
          const float dxy = 0.25f * (cur.at(r + 1, c + 1) - cur.at(r + 1, c - 1) - cur.at(r - 1, c + 1) + cur.at(r - 1, c - 1));
          if (0 == iter) {
             const float edgeScore = (dxx + dyy) * (dxx + dyy) / (dxx * dyy - dxy * dxy);
-            if (edgeScore >= edgeScoreThreshold || edgeScore < 0) return;
+            edgeBits = bitsOf(edgeScore);
+            if (edgeScore >= edgeScoreThreshold || edgeScore < 0) { leave(edgeScore >= edgeScoreThreshold ? TX_EDGE_HIGH : TX_EDGE_NEG); return; }
          }
          const float dxs = 0.25f * (high.at(r, c + 1) - high.at(r, c - 1) - low.at(r, c + 1) + low.at(r, c - 1));
          const float dys = 0.25f * (high.at(r + 1, c) - high.at(r - 1, c) - low.at(r + 1, c) + low.at(r - 1, c));
@@ -733,17 +766,20 @@ struct Oracle {
          const float ds = 0.5f * (high.at(r, c) - low.at(r, c));
          b[0] = -dx; b[1] = -dy; b[2] = -ds;
          solveLinear3x3(A, b);
-         if (std::isnan(b[0]) || std::isnan(b[1]) || std::isnan(b[2])) return;
+         if (std::isnan(b[0]) || std::isnan(b[1]) || std::isnan(b[2])) { leave(TX_NAN); return; }
          val = cur.at(r, c) + 0.5f * (dx * b[0] + dy * b[1] + ds * b[2]);
-         if (b[0] > 0.6) { if (c < cols - 3) nc++; else return; }
-         if (b[1] > 0.6) { if (r < rows - 3) nr++; else return; }
-         if (b[0] < -0.6) { if (c > 3) nc--; else return; }
-         if (b[1] < -0.6) { if (r > 3) nr--; else return; }
+         if (b[0] > 0.6) { if (c < cols - 3) nc++; else { leave(TX_OUT_RIGHT); return; } }
+         if (b[1] > 0.6) { if (r < rows - 3) nr++; else { leave(TX_OUT_DOWN); return; } }
+         if (b[0] < -0.6) { if (c > 3) nc--; else { leave(TX_OUT_LEFT); return; } }
+         if (b[1] < -0.6) { if (r > 3) nr--; else { leave(TX_OUT_UP); return; } }
          if (nr == r && nc == c) break;
       }
       if (fabsf(b[0]) > 1.5 || fabsf(b[1]) > 1.5 || fabsf(b[2]) > 1.5 || fabsf(val) < finalThreshold ||
-          octaveMap.at(r, c) > 0)
+          octaveMap.at(r, c) > 0) {
+         leave((fabsf(b[0]) > 1.5 || fabsf(b[1]) > 1.5 || fabsf(b[2]) > 1.5) ? TX_SHIFT : fabsf(val) < finalThreshold ? TX_WEAK : TX_TAKEN);
          return;
+      }
+      leave(TX_KEPT);
       octaveMap.at(r, c) = 1;
       const float scale = curScale * powf(2.0f, b[2] / par.numberOfScales);
       // pyramid.cpp:24-37
@@ -781,6 +817,42 @@ struct Oracle {
       return true;
    }
 
+   // pyramid.cpp:206-222 as pyramid.cpp:247-249 calls it: level i - 2 of an octave whose planes L[0..i] and R[0..i] exist
+   void scanLevel(int i, float curSigma, float pixelDistance, const std::vector<Plane> &L, const std::vector<Plane> &R, Plane &octaveMap,
+                  const Plane &image, int octave)
+   {
+      const Plane &low = R[i - 2], &cur = R[i - 1], &high = R[i];
+      const int rows = cur.rows, cols = cur.cols;
+      for (int r = par.border; r < rows - par.border; r++)
+         for (int c = par.border; c < cols - par.border; c++) {
+            const float val = cur.at(r, c);
+            if ((val > positiveThreshold && (isMax(val, cur, r, c) && isMax(val, low, r, c) && isMax(val, high, r, c))) ||
+                (val < negativeThreshold && (isMin(val, cur, r, c) && isMin(val, low, r, c) && isMin(val, high, r, c)))) {
+               nCandidates++;
+               localizeKeypoint(r, c, curSigma, pixelDistance, low, cur, high, L[i - 1], L[i - 2], octaveMap,
+                                image, octave, i - 2);
+            }
+         }
+   }
+
+   // detectOctave's scans on planes of the caller's (one image, octave 0, detectOnly): the sigma of every level advances as in detectOctave,
+   // nothing is blurred and no response is computed
+   void detectPlanes(const std::vector<Plane> &L, const std::vector<Plane> &R)
+   {
+      hess.clear(); aff.clear(); keys.clear(); keySrc.clear(); blurs.clear(); resps.clear(); trace.clear(); nCandidates = 0;
+      const bool was = detectOnly;
+      detectOnly = true;
+      Plane octaveMap(R[0].rows, R[0].cols);
+      const float sigmaStep = powf(2.0f, 1.0f / (float)par.numberOfScales);
+      float curSigma = par.initialSigma;
+      const int nl = par.numberOfScales + 2;
+      for (int i = 1; i < nl; i++) {
+         if (i >= 2) scanLevel(i, curSigma, 1.0f, L, R, octaveMap, L[0], 0);
+         curSigma *= sigmaStep;
+      }
+      detectOnly = was;
+   }
+
    // pyramid.cpp:224-259 (+ :206-222 scan)
    void detectOctave(const Plane &firstLevel, float pixelDistance, Plane &nextFirst, const Plane &image, int octave)
    {
@@ -796,20 +868,7 @@ struct Oracle {
          gaussianBlur(L[i - 1], sigma, L[i]);
          sigma = curSigma * sigmaStep;
          hessianResponse(L[i], sigma * sigma, R[i]);
-         if (i >= 2) {
-            const Plane &low = R[i - 2], &cur = R[i - 1], &high = R[i];
-            const int rows = cur.rows, cols = cur.cols;
-            for (int r = par.border; r < rows - par.border; r++)
-               for (int c = par.border; c < cols - par.border; c++) {
-                  const float val = cur.at(r, c);
-                  if ((val > positiveThreshold && (isMax(val, cur, r, c) && isMax(val, low, r, c) && isMax(val, high, r, c))) ||
-                      (val < negativeThreshold && (isMin(val, cur, r, c) && isMin(val, low, r, c) && isMin(val, high, r, c)))) {
-                     nCandidates++;
-                     localizeKeypoint(r, c, curSigma, pixelDistance, low, cur, high, L[i - 1], L[i - 2], octaveMap,
-                                      image, octave, i - 2);
-                  }
-               }
-         }
+         if (i >= 2) scanLevel(i, curSigma, pixelDistance, L, R, octaveMap, image, octave);
          if (i == par.numberOfScales) halfImage(L[i], nextFirst);
          curSigma *= sigmaStep;
       }
@@ -819,7 +878,7 @@ struct Oracle {
    // pyramid.cpp:261-292 (upscaleInputImage = 0 path)
    void detect(const Plane &image)
    {
-      hess.clear(); aff.clear(); keys.clear(); keySrc.clear(); blurs.clear(); resps.clear(); nCandidates = 0;
+      hess.clear(); aff.clear(); keys.clear(); keySrc.clear(); blurs.clear(); resps.clear(); trace.clear(); nCandidates = 0;
       float curSigma = 0.5f;
       float pixelDistance = 1.0f;
       Plane firstLevel = image;
@@ -1027,6 +1086,39 @@ void ho_detect(void *h, const float *gray, int rows, int cols)
    Plane p(rows, cols);
    memcpy(p.d.data(), gray, sizeof(float) * rows * cols);
    ((Oracle *)h)->detect(p);
+}
+// the scans of one octave on caller-supplied planes: L, R = [5][rows][cols] each (blur L0..L4, response R0..R4), one image, detectOnly
+void ho_h_detect_planes(void *h, const float *L, const float *R, int rows, int cols)
+{
+   std::vector<Plane> Lp(5), Rp(5);
+   for (int l = 0; l < 5; l++) {
+      Lp[l] = Plane(rows, cols); Rp[l] = Plane(rows, cols);
+      memcpy(Lp[l].d.data(), L + (size_t)l * rows * cols, sizeof(float) * rows * cols);
+      memcpy(Rp[l].d.data(), R + (size_t)l * rows * cols, sizeof(float) * rows * cols);
+   }
+   ((Oracle *)h)->detectPlanes(Lp, Rp);
+}
+// the recorder of localizeKeypoint's exits (off by default), one record per candidate in scan order
+void ho_set_trace(void *h, int on) { ((Oracle *)h)->tracing = on != 0; }
+int ho_num_trace(void *h) { return (int)((Oracle *)h)->trace.size(); }
+// i[n][17] = level, r0, c0, iterations, final r, final c, exit (TraceExit), then the (r, c) of the five iterations' centres (-1: not entered) ;
+// u[n][5] = bits of b[0], b[1], b[2], val, first edgeScore
+void ho_get_trace(void *h, int *i, unsigned *u)
+{
+   const Oracle *o = (Oracle *)h;
+   for (size_t n = 0; n < o->trace.size(); n++) {
+      const TraceRec &t = o->trace[n];
+      int *ii = i + 17 * n; unsigned *uu = u + 5 * n;
+      ii[0] = t.level; ii[1] = t.r0; ii[2] = t.c0; ii[3] = t.iters; ii[4] = t.rf; ii[5] = t.cf; ii[6] = t.exit;
+      for (int k = 0; k < 5; k++) { ii[7 + 2 * k] = t.path[k][0]; ii[8 + 2 * k] = t.path[k][1]; }
+      uu[0] = t.b[0]; uu[1] = t.b[1]; uu[2] = t.b[2]; uu[3] = t.val; uu[4] = t.edge;
+   }
+}
+// t[3] = positiveThreshold, finalThreshold, edgeScoreThreshold (pyramid.h:59-64) of the handle's parameters
+void ho_get_thresholds(void *h, float *t)
+{
+   const Oracle *o = (Oracle *)h;
+   t[0] = o->positiveThreshold; t[1] = o->finalThreshold; t[2] = o->edgeScoreThreshold;
 }
 int ho_num_hessian(void *h) { return (int)((Oracle *)h)->hess.size(); }
 int ho_num_keys(void *h) { return (int)((Oracle *)h)->keys.size(); }

@@ -14,6 +14,7 @@ _SO = os.path.join(_ROOT, "oracle", "libhesaff_oracle.so")
 
 f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
+u32p = np.ctypeslib.ndpointer(dtype=np.uint32, flags="C_CONTIGUOUS")
 u8p = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
 
 
@@ -79,6 +80,11 @@ def lib():
     L.ho_get_plane.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, f32p]
     L.ho_export.argtypes = [C.c_void_p, C.c_char_p, C.c_long]; L.ho_export.restype = C.c_long
     L.ho_ellipse.argtypes = [f32p, C.c_float, f32p]
+    L.ho_h_detect_planes.argtypes = [C.c_void_p, f32p, f32p, C.c_int, C.c_int]
+    L.ho_set_trace.argtypes = [C.c_void_p, C.c_int]
+    L.ho_num_trace.argtypes = [C.c_void_p]; L.ho_num_trace.restype = C.c_int
+    L.ho_get_trace.argtypes = [C.c_void_p, i32p, u32p]
+    L.ho_get_thresholds.argtypes = [C.c_void_p, f32p]
     _lib = L
     return L
 
@@ -135,6 +141,48 @@ class OracleHandle:
         mv = np.zeros(2, np.float32); hist = np.zeros(128, np.float32); vec = np.zeros(128, np.float32)
         lib().ho_h_sift_parts(self.h, p, mv, hist, vec)
         return mv, hist, vec.astype(np.uint8)
+
+
+# exits of localizeKeypoint in a trace record (TraceExit, oracle/hesaff_oracle.cpp)
+TX_KEPT, TX_EDGE_HIGH, TX_EDGE_NEG, TX_NAN, TX_OUT_RIGHT, TX_OUT_DOWN, TX_OUT_LEFT, TX_OUT_UP, TX_SHIFT, TX_WEAK, TX_TAKEN = range(11)
+TX_NAMES = ["kept", "edge>=threshold", "edge<0", "nan", "out-right", "out-down", "out-left", "out-up", "|b|>1.5", "<finalThreshold", "taken"]
+
+
+def thresholds(params=None):
+    """-> (positiveThreshold, finalThreshold, edgeScoreThreshold) as float32, of the oracle with these parameters"""
+    o = OracleHandle(params)
+    t = np.zeros(3, np.float32)
+    lib().ho_get_thresholds(o.h, t)
+    return t[0], t[1], t[2]
+
+
+class PlanesRun:
+    """The extrema scans and localizeKeypoint on caller-supplied planes of one octave (L, R: [5, rows, cols] float32), with the trace."""
+
+    def __init__(self, L, R, params=None):
+        lb = lib()
+        L = np.ascontiguousarray(L, np.float32); R = np.ascontiguousarray(R, np.float32)
+        assert L.shape == R.shape and L.ndim == 3 and L.shape[0] == 5
+        o = OracleHandle(params)
+        lb.ho_set_trace(o.h, 1)
+        lb.ho_h_detect_planes(o.h, L.reshape(-1), R.reshape(-1), L.shape[1], L.shape[2])
+        n = lb.ho_num_hessian(o.h)
+        self.f = np.zeros((n, 6), np.float32); self.i = np.zeros((n, 5), np.int32)
+        for k in range(n):
+            lb.ho_get_hessian(o.h, k, self.f[k], self.i[k])
+        nt = lb.ho_num_trace(o.h)
+        self.trace_i = np.zeros((nt, 17), np.int32); self.trace_u = np.zeros((nt, 5), np.uint32)
+        if nt:
+            lb.ho_get_trace(o.h, self.trace_i.reshape(-1), self.trace_u.reshape(-1))
+        self.n_candidates = lb.ho_num_candidates(o.h)
+
+    def trace_at(self, level, r0, c0):
+        """the trace record of candidate (level, r0, c0) as (ints[17], bits[5]), or None when it was no candidate.
+        ints = level, r0, c0, iterations, final r, final c, exit (TX_*), then (r, c) of each iteration's centre (-1: not entered)"""
+        t = self.trace_i
+        m = np.flatnonzero((t[:, 0] == level) & (t[:, 1] == r0) & (t[:, 2] == c0))
+        assert len(m) <= 1
+        return (self.trace_i[m[0]], self.trace_u[m[0]]) if len(m) else None
 
 
 class OracleRun:

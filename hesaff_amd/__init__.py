@@ -23,6 +23,8 @@ from ._binding import (  # noqa: F401
     FROM_SHAPES,
     ORI_UP,
     ORI_DOMINANT,
+    DESC_SIFT,
+    DESC_ROOTSIFT,
     default_params,
     format_sift,
     format_sift_mt,

@@ -232,6 +232,10 @@ def load_library():
         L.hesaff_set_orientation.argtypes = [vp, C.c_int]
         L.hesaff_get_orientation.argtypes = [vp, C.POINTER(C.c_int)]
         L.hesaff_stage_orientation.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p]
+    if hasattr(L, "hesaff_set_descriptor"):   # (likewise)
+        L.hesaff_set_descriptor.argtypes = [vp, C.c_int]
+        L.hesaff_get_descriptor.argtypes = [vp, C.POINTER(C.c_int)]
+        L.hesaff_stage_sift_mode.argtypes = [vp, C.c_int, _f32p, C.c_void_p, C.c_int, _u8p]
     L.hesaff_stage_math_sift_general.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math_sift.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]
@@ -271,7 +275,13 @@ ABI_SYMBOLS = [
     "hesaff_set_keypoint_limit", "hesaff_get_keypoint_limit", "hesaff_set_next_masks", "hesaff_set_next_masks_device",
     "hesaff_set_orientation", "hesaff_get_orientation", "hesaff_stage_orientation",
     "hesaff_set_keypoint_grid", "hesaff_get_keypoint_grid", "hesaff_stage_detect_planes",
+    "hesaff_set_descriptor", "hesaff_get_descriptor", "hesaff_stage_sift_mode",
 ]
+
+# hesaff_set_descriptor's modes
+DESC_SIFT = 0       # the reference's SIFT bytes (default)
+DESC_ROOTSIFT = 1   # the vector L1-normalised and square-rooted before it is quantised
+_DESC_NAMES = {"sift": DESC_SIFT, "rootsift": DESC_ROOTSIFT}
 
 # hesaff_set_orientation's modes
 ORI_UP = 0         # the reference's "up is up" frame (default)
@@ -775,6 +785,27 @@ class HesaffContext:
     def orientation(self, mode):
         self.set_orientation(mode)
 
+    def set_descriptor(self, mode):
+        """hesaff_set_descriptor: DESC_SIFT / "sift" (default: the reference's bytes, bit for bit) or DESC_ROOTSIFT / "rootsift": the
+        descriptor vector is L1-normalised and square-rooted on the device before it is quantised (definition in
+        include/hesaff_amd.h); only `desc` of the keys changes.  Applies to every detecting call, process_files and
+        describe_regions*; not to the stage operators."""
+        if isinstance(mode, str):
+            if mode not in _DESC_NAMES:
+                raise ValueError("descriptor is 'sift' or 'rootsift', not %r" % (mode,))
+            mode = _DESC_NAMES[mode]
+        self._check(self.L.hesaff_set_descriptor(self.h, int(mode)))
+
+    @property
+    def descriptor(self):
+        m = C.c_int()
+        self._check(self.L.hesaff_get_descriptor(self.h, C.byref(m)))
+        return m.value
+
+    @descriptor.setter
+    def descriptor(self, mode):
+        self.set_descriptor(mode)
+
     def process_files(self, paths, out_paths=None, decode_threads=0, write_threads=0):
         """hesaff_process_files: image files -> <name>.hesaff.sift through the decode / device / write pipeline.
         -> list of (rc, stage, count_hessian, count_desc) per file."""
@@ -929,6 +960,18 @@ class HesaffContext:
         assert len(a) == len(p)
         d = np.full((len(p), 128), fill, np.uint8)
         self._check(self.L.hesaff_stage_sift_alive(self.h, len(p), p, a, d))
+        return d
+
+    def sift_mode(self, patches, mode, alive=None, fill=0):
+        """-> desc [n, 128] u8 in descriptor mode `mode` (DESC_SIFT / DESC_ROOTSIFT), whatever the context's mode is
+        (hesaff_stage_sift_mode).  alive=None: every keypoint; otherwise rows of keypoints with alive == 0 keep `fill`."""
+        p = np.ascontiguousarray(patches, np.float32).reshape(-1, 41 * 41)
+        d = np.full((len(p), 128), fill, np.uint8)
+        a = None
+        if alive is not None:
+            a = np.ascontiguousarray(alive, np.int32).reshape(-1)
+            assert len(a) == len(p)
+        self._check(self.L.hesaff_stage_sift_mode(self.h, len(p), p, None if a is None else a.ctypes.data, int(mode), d))
         return d
 
     def export(self, keys, mr_size=None, fmt=1):

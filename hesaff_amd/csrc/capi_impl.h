@@ -906,6 +906,20 @@ int hesaff_get_orientation(const hesaff_ctx *c, int *mode)
    return HESAFF_OK;
 }
 
+int hesaff_set_descriptor(hesaff_ctx *c, int mode)
+{
+   if (!c || (mode != HESAFF_DESC_SIFT && mode != HESAFF_DESC_ROOTSIFT)) return HESAFF_ERR_ARG;
+   c->descriptor = mode;
+   return HESAFF_OK;
+}
+
+int hesaff_get_descriptor(const hesaff_ctx *c, int *mode)
+{
+   if (!c || !mode) return HESAFF_ERR_ARG;
+   *mode = c->descriptor;
+   return HESAFF_OK;
+}
+
 int hesaff_set_next_masks(hesaff_ctx *c, int n, const uint8_t *const *masks, const int *strides)
 {
    if (!c || n < 0 || (n > 0 && !masks)) return HESAFF_ERR_ARG;
@@ -1265,7 +1279,9 @@ int hesaff_stage_normalize_affine(hesaff_ctx *c, const float *img, int rows, int
 // (either may be null) additionally receive what k_sift_meanvar left in the stage buffer and the histogram k_sift_hist writes out
 // when it is given a place for it (SiftIO::vec; the pipeline passes none)
 // alive (may be null: every keypoint alive): the pipeline's flags; desc then goes to the device first (dead keypoints' rows stay)
-static int stage_sift(hesaff_ctx *c, int n, const float *patches, float *meanvar, float *hist, uint8_t *desc, const int32_t *alive = nullptr)
+// desc_mode: the operator's own (stage operators do not read the context's modes)
+static int stage_sift(hesaff_ctx *c, int n, const float *patches, float *meanvar, float *hist, uint8_t *desc, const int32_t *alive = nullptr,
+                      int desc_mode = HESAFF_DESC_SIFT)
 {
    if (!c || !patches || !desc || n < 0) return HESAFF_ERR_ARG;
    HS_API_BEGIN
@@ -1285,7 +1301,7 @@ static int stage_sift(hesaff_ctx *c, int n, const float *patches, float *meanvar
    SiftIO so;
    so.patches = (const float *)base; so.alive = (const int32_t *)(base + off_alive); so.meanvar = (float *)(base + off_mv);
    so.vec = hist ? (float *)(base + off_vec) : nullptr; so.desc = (uint8_t *)(base + off_desc); so.h_lo = 0; so.h_hi = (uint32_t)n;
-   launch_sift(c, c->stream(), so, (uint32_t)n, (float2 *)(base + off_vo));
+   launch_sift(c, c->stream(), so, (uint32_t)n, (float2 *)(base + off_vo), desc_mode);
    if (meanvar) HIP_TRY(hipMemcpyAsync(meanvar, base + off_mv, N * 8, hipMemcpyDeviceToHost, c->stream()));
    if (hist) HIP_TRY(hipMemcpyAsync(hist, base + off_vec, N * 128 * 4, hipMemcpyDeviceToHost, c->stream()));
    HIP_TRY(hipMemcpyAsync(desc, base + off_desc, N * 128, hipMemcpyDeviceToHost, c->stream()));
@@ -1305,6 +1321,12 @@ int hesaff_stage_sift_alive(hesaff_ctx *c, int n, const float *patches, const in
 {
    if (!alive) return HESAFF_ERR_ARG;
    return stage_sift(c, n, patches, nullptr, nullptr, desc, alive);
+}
+
+int hesaff_stage_sift_mode(hesaff_ctx *c, int n, const float *patches, const int32_t *alive, int mode, uint8_t *desc)
+{
+   if (mode != HESAFF_DESC_SIFT && mode != HESAFF_DESC_ROOTSIFT) return HESAFF_ERR_ARG;
+   return stage_sift(c, n, patches, nullptr, nullptr, desc, alive, mode);
 }
 
 // k_orientation (kernels_orient.h) on caller-supplied patches: every keypoint alive, no affine frame to turn

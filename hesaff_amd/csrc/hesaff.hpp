@@ -132,6 +132,14 @@ struct AffineHessianDetector {
       if (hesaff_set_orientation(ctx_, mode) != HESAFF_OK) throw std::invalid_argument("orientation is HESAFF_ORI_UP or HESAFF_ORI_DOMINANT");
    }
 
+   // No counterpart in the reference (hesaff_set_descriptor, include/hesaff_amd.h), whose descriptors are SIFT bytes.
+   // HESAFF_DESC_ROOTSIFT: the vector is L1-normalised and square-rooted on the device before it is quantised (RootSIFT); only
+   // `desc` of the keys changes.  HESAFF_DESC_SIFT (default): the reference's bytes, bit for bit.
+   void setDescriptor(int mode)
+   {
+      if (hesaff_set_descriptor(ctx_, mode) != HESAFF_OK) throw std::invalid_argument("descriptor is HESAFF_DESC_SIFT or HESAFF_DESC_ROOTSIFT");
+   }
+
    // No counterpart in the reference (hesaff_set_next_masks, include/hesaff_amd.h; OpenCV's detect(image, keypoints, mask)): the NEXT
    // detectPyramidKeypoints keeps only the Hessian keypoints on a non-zero pixel of `mask` - height x width 8-bit pixels at the size of
    // the image as passed, rows strideBytes apart (0: tightly packed), pixel (row, col) = (clamp((int)(y + 0.5f)), clamp((int)(x +

@@ -267,10 +267,13 @@ __global__ void k_math_sift_general(int n, const float *__restrict__ gy, const f
 // The (mask*grad, o) rows of a step are fetched by the whole wave as consecutive 16-byte items and handed
 // out through LDS (see "Row staging" below), the next step's rows in flight while the current ones are consumed.
 // Behind the 16 steps the wave turns its four histograms into descriptor bytes (max_bin = DConsts::maxBinValue).
+// DESC (hesaff_set_descriptor, chosen by launch_sift): HESAFF_DESC_SIFT quantises that vector; HESAFF_DESC_ROOTSIFT first divides it by
+// its L1 norm - one more 128-term sequential sum, parked and added like the sums of squares - and takes the square roots.  The mode is a
+// template parameter: the SIFT instantiation carries no trace of the other.
 // grid-stride over groups of 4 keypoints, block 64.
 #define HS_SQ_PITCH 132   // floats between the keypoints' squared vectors in LDS (k_sift_hist): 128 + one 16-byte item
 #define HS_HIST_AHEAD 1   // steps the row items are requested ahead (2, with a second set of five registers, measured the same: profiles/r05_notes.md)
-__global__ __launch_bounds__(64) void k_sift_hist(SiftIO io, KpTables tb, const float2 *__restrict__ vo, float max_bin)
+template <int DESC> __global__ __launch_bounds__(64) void k_sift_hist(SiftIO io, KpTables tb, const float2 *__restrict__ vo, float max_bin)
 {
    __shared__ __attribute__((aligned(2048))) float s_acc[8 * 64];
    __shared__ float s_cw[64];   // [spatial bin][offset 0..15]
@@ -422,6 +425,25 @@ __global__ __launch_bounds__(64) void k_sift_hist(SiftIO io, KpTables tb, const 
 #pragma unroll
             for (int b = 0; b < 8; b++) vb[b] *= f2;
          }
+      }
+      if constexpr (DESC == HESAFF_DESC_ROOTSIFT) {
+         // RootSIFT (include/hesaff_amd.h): s = the sum of the 128 items in index order, u = sqrtf(v / s).  The items are +0 or positive
+         // (or all NaN: zero histogram, dead keypoint, keypoint past the list - NaN all the way, byte 0 or nothing stored), so s is the
+         // L1 norm.  Unconditional, hence wave-uniform in its LDS synchronisation whatever mix of keypoints the wave holds.
+         float4 *mine = reinterpret_cast<float4 *>(s_sq + HS_SQ_PITCH * kq + 8 * cell);
+         mine[0] = make_float4(vb[0], vb[1], vb[2], vb[3]);
+         mine[1] = make_float4(vb[4], vb[5], vb[6], vb[7]);
+         HS_WAVE_LDS_SYNC();
+         float l1 = 0.0f;
+         if (cell == 0) {
+            const float4 *r = reinterpret_cast<const float4 *>(s_sq + HS_SQ_PITCH * kq);
+#pragma unroll 8
+            for (int j = 0; j < 32; j++) { const float4 q = r[j]; l1 += q.x; l1 += q.y; l1 += q.z; l1 += q.w; }
+         }
+         l1 = __shfl(l1, tid & 48);
+         HS_WAVE_LDS_SYNC();   // the sums are read before the next group's rows are parked here
+#pragma unroll
+         for (int b = 0; b < 8; b++) vb[b] = sqrtf(vb[b] / l1);
       }
       if (valid) {
          uint32_t w[2] = {0u, 0u};

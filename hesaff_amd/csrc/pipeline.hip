@@ -427,6 +427,7 @@ struct hesaff_ctx {
    int pool_priority = -1;             // hesaff_set_pool_priority: -1 lower the pool's priority when the plan is CPU-starved, 0 never, 1 always
    int keypoint_limit = 0;             // hesaff_set_keypoint_limit: 0 no limit, N >= 1 the N strongest Hessian keypoints of every image (run_batch)
    int grid_rows = 1, grid_cols = 1;   // hesaff_set_keypoint_grid: with a limit N and more than one cell, the N / cells strongest of every cell
+   int descriptor = HESAFF_DESC_SIFT;  // hesaff_set_descriptor: which instantiation of k_sift_hist the pipeline's launch_sift takes
    int orientation = HESAFF_ORI_UP;    // hesaff_set_orientation: HESAFF_ORI_DOMINANT runs the oriented order of group_schedule.h (run_keypoint_stages)
    ArmedMasks next_masks;              // hesaff_set_next_masks / _device: the masks of the next detecting call (taken, so cleared, by take_masks)
    int stage_threads = 4;              // host threads that copy a chunk's pixels into pinned memory (hesaff_process_files: within its thread budget)
@@ -499,7 +500,7 @@ void set_kernel_attrs(hesaff_ctx *c)
    c->g_mid = std::min<uint32_t>(resident_grid(c, k_patch_mid<HS_MID_PMAX>, 256, mid_lds_bytes(), HS_MID_CAP), HS_MID_BLOCKS);
    c->g_big = std::min<uint32_t>(resident_grid(c, k_patch_mid<HS_BIN3_PMAX>, 256, big_lds_bytes(), HS_BIG_CAP), HS_BIG_BLOCKS);
    c->g_lfin = resident_grid(c, k_patch_large_finish, 256, 0, 4);
-   c->g_shist = resident_grid(c, k_sift_hist, 64, 0, 32);
+   c->g_shist = resident_grid(c, k_sift_hist<HESAFF_DESC_SIFT>, 64, 0, 32);   // (the RootSIFT instantiation strides over the same grid)
    // k_sift_grad: a block keeps its per-pixel tables and requests the next patch while it works on the current one; well
    // over the resident count so that the tail of a launch is short (measured: one block per keypoint 18.5 ms per 32 UHD
    // images, 6 / 16 / 32 / 64 blocks per CU 15.2 / 13.8 / 13.3 / 13.4)
@@ -1076,12 +1077,16 @@ void collect_timings(hesaff_ctx *c, StageTimer &tm, int B)
 
 // The descriptor kernels (kernels_sift.h) over n patches in HBM.  (Slices of a group, each slice's kernels back to back so that
 // the intermediates stay in the memory-side cache, measured no faster: sweep in profiles/r06_notes.md.)
-void launch_sift(hesaff_ctx *c, hipStream_t ss, const SiftIO &so, uint32_t n, float2 *vo)
+// desc_mode: HESAFF_DESC_SIFT / HESAFF_DESC_ROOTSIFT - the pipeline passes the context's mode, a stage operator its own.
+void launch_sift(hesaff_ctx *c, hipStream_t ss, const SiftIO &so, uint32_t n, float2 *vo, int desc_mode)
 {
    hipLaunchKernelGGL(k_sift_meanvar, dim3((n + SM_KP - 1) / SM_KP), dim3(64), 0, ss, so, c->tables.view);
    hipLaunchKernelGGL(k_sift_grad, dim3(std::min(n, c->sgrad_grid)), dim3(256), 0, ss, so, c->tables.view, vo);
-   hipLaunchKernelGGL(k_sift_hist, dim3(std::min<uint32_t>((n + 3) / 4, c->g_shist)), dim3(64), 0, ss, so, c->tables.view, (const float2 *)vo,
-                      c->ct.consts.maxBinValue);
+   const dim3 hg(std::min<uint32_t>((n + 3) / 4, c->g_shist));
+   if (desc_mode == HESAFF_DESC_ROOTSIFT)
+      hipLaunchKernelGGL(k_sift_hist<HESAFF_DESC_ROOTSIFT>, hg, dim3(64), 0, ss, so, c->tables.view, (const float2 *)vo, c->ct.consts.maxBinValue);
+   else
+      hipLaunchKernelGGL(k_sift_hist<HESAFF_DESC_SIFT>, hg, dim3(64), 0, ss, so, c->tables.view, (const float2 *)vo, c->ct.consts.maxBinValue);
 }
 
 // per-group patch / descriptor buffers: sized once per batch for the largest group
@@ -1180,7 +1185,7 @@ struct GroupDevice : ScheduleDevice {
       so.patches = c->b_patches2[slot].as<float>(); so.alive = s.pw.alive; so.meanvar = c->b_meanvar2.as<float>();
       so.vec = nullptr; so.desc = c->geo.b_desc.as<uint8_t>(); so.h_lo = groups[g].lo; so.h_hi = groups[g].hi;
       const int ts = tm.begin(T_SIFT, 0, stream(ss));
-      launch_sift(c, stream(ss), so, groups[g].hi - groups[g].lo, c->b_siftvo2.as<float2>());
+      launch_sift(c, stream(ss), so, groups[g].hi - groups[g].lo, c->b_siftvo2.as<float2>(), c->descriptor);
       tm.end(ts);
    }
 };

@@ -47,6 +47,7 @@ extern "C" {
  *    And for the test hook hesaff_stage_sift_alive.
  *    And for hesaff_set_orientation / hesaff_get_orientation / hesaff_stage_orientation (dominant-orientation mode): symbols only, version 8.
  *    And for the stage entry point hesaff_stage_detect_planes.
+ *    And for hesaff_set_descriptor / hesaff_get_descriptor / hesaff_stage_sift_mode (RootSIFT descriptor mode): symbols only, version 8.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -454,6 +455,35 @@ int hesaff_get_keypoint_grid(const hesaff_ctx *ctx, int *rows, int *cols);
 int hesaff_set_orientation(hesaff_ctx *ctx, int mode);
 int hesaff_get_orientation(const hesaff_ctx *ctx, int *mode);
 
+/* ---- descriptor mode: SIFT or RootSIFT bytes ----
+ * Replaces nothing: the reference has the L2-normalised, clipped, 512-scaled SIFT byte vector only (siftdesc.cpp:98-113).  RootSIFT
+ * (Arandjelovic and Zisserman 2012) L1-normalises the vector and takes element-wise square roots, so that the Euclidean distance of
+ * two results is the Hellinger kernel of the histograms.  A caller cannot do that well from the 0..255 bytes, which are truncated
+ * already; the float vector is in registers at the end of the descriptor kernel, where the mode costs one more 128-term sum, eight
+ * divisions and eight square roots per lane.  The definition is this library's; everything is binary32, no FMA contraction, / and
+ * sqrtf IEEE-exact.  Let v[0..127] be `vec` as it stands after siftdesc.cpp:102-106: normalize, clip at maxBinValue, normalize again
+ * only if a bin was clipped.
+ *  HESAFF_DESC_SIFT (0, the default):  byte[i] = min((int)(512.0f * v[i]), 255) - today's bytes, bit for bit; nothing is launched,
+ *     allocated or copied for the mode.
+ *  HESAFF_DESC_ROOTSIFT (1):
+ *   1. s = ((v[0] + v[1]) + ...) + v[127], in increasing i, starting from +0 (every v[i] is +0 or positive: the L1 norm);
+ *   2. u[i] = sqrtf(v[i] / s);
+ *   3. byte[i] = min((int)(512.0f * u[i]), 255), truncating; byte[i] = 0 where 512.0f * u[i] is NaN (the existing guard: only the
+ *      all-zero histogram gets there, whose v is NaN in both modes).
+ * u has unit L2 norm, so the scale 512 and the saturation at 255 keep the meaning they have for SIFT.  Every other field of
+ * hesaff_keypoint and hesaff_region, the set and order of the described keypoints, the counts and the file formats (which carry no
+ * flag for the mode) are those of mode 0.
+ * The mode is context state, like the orientation.  It applies to every entry point that produces descriptors: hesaff_detect_batch*,
+ * hesaff_detect_regions*, hesaff_detect_batch_device*, hesaff_process_files (text and sidecar rows) and hesaff_describe_regions* in
+ * both `from` modes, with any parameter set (fast = 2, upscaleInputImage), and composes with the dominant orientation, the keypoint
+ * limit, the grid and the masks.  It does not apply to the hesaff_stage_* operators: hesaff_stage_sift, _parts and _alive stay SIFT
+ * whatever the context holds, hesaff_stage_sift_mode takes the mode as an argument.
+ * ctx NULL or mode not 0 / 1: HESAFF_ERR_ARG, nothing changed (hesaff_get_descriptor: ctx or mode NULL). */
+#define HESAFF_DESC_SIFT 0
+#define HESAFF_DESC_ROOTSIFT 1
+int hesaff_set_descriptor(hesaff_ctx *ctx, int mode);
+int hesaff_get_descriptor(const hesaff_ctx *ctx, int *mode);
+
 /* Same path with inputs already resident in device memory (bench / pipelines that decode
  * on the GPU): d_gray = n contiguous height x width 8-bit grey planes (device pointer).
  * Results stay on the device; per-image counts are copied to the two host arrays.
@@ -644,6 +674,9 @@ int hesaff_stage_sift_parts(hesaff_ctx *ctx, int n, const float *patches, float 
  * write nothing for such a keypoint: desc[n][128] goes to the device as the caller filled it and comes back, the rows of dead
  * keypoints unchanged. */
 int hesaff_stage_sift_alive(hesaff_ctx *ctx, int n, const float *patches, const int32_t *alive, uint8_t *desc);
+/* the same launch with an explicit descriptor mode (hesaff_set_descriptor's definition; HESAFF_DESC_SIFT / HESAFF_DESC_ROOTSIFT, anything
+ * else HESAFF_ERR_ARG).  alive NULL: every keypoint alive; otherwise as hesaff_stage_sift_alive. */
+int hesaff_stage_sift_mode(hesaff_ctx *ctx, int n, const float *patches, const int32_t *alive, int mode, uint8_t *desc);
 /* steps 1-6 of hesaff_set_orientation's definition (the production kernel, k_orientation) on n caller-supplied 41 x 41 patches:
  * theta[n]; optionally (NULL: not wanted) hist[n][36], the histogram after smoothing, and cs[n][2] = (cos theta, sin theta) */
 int hesaff_stage_orientation(hesaff_ctx *ctx, int n, const float *patches, float *theta, float *hist, float *cs);

@@ -868,7 +868,8 @@ class HesaffContext:
         self._check(entry(self.h, None, g.shape[0], g.shape[1], None, C.byref(no), C.byref(nf)))
         buf = np.empty(max(nf.value, 1), np.float32)
         self._check(entry(self.h, g.ctypes.data, g.shape[0], g.shape[1], buf.ctypes.data, C.byref(no), C.byref(nf)))
-        out = []; off = 0; r, c = g.shape
+        up = 1 if self.params.upscaleInputImage > 0 else 0   # (the first octave is the 2x up-sampled image: pyramid.cpp:267-271)
+        out = []; off = 0; r, c = g.shape[0] << up, g.shape[1] << up
         for _ in range(no.value):
             n = r * c
             Ls = buf[off:off + 5 * n].reshape(5, r, c); off += 5 * n

@@ -48,6 +48,31 @@ inline PyramidGeom pyramid_geometry(int H, int W, int up)
    return p;
 }
 
+// ---- the blur launches of an octave (pyramid.cpp:224-259) ----
+// What a caller wants of an octave whose first level L0 exists: the planes detection reads (L0..L3, R0..R4), those and L4 (the stage
+// operator that returns every plane), or the blurs alone (describe_regions: L1, L2 and the next octave's first level, no response plane).
+enum class OctaveWant { Detect, DetectKeepL4, BlursOnly };
+// Step i = 1..4 blurs level `in` into level i: write_L keeps the blurred level, write_R its response plane R[i], write_half its 2x decimation,
+// the next octave's first level, write_R0 the response of the input level as well.  bytes_per_px: the algorithmic bytes the stage timer is
+// told: 12, + 8 with R0 (read L0 + write R0 of the stand-alone pass), + 2 with the decimation; the blurs alone 8 and 5.
+struct BlurStep { bool launch; int in; bool write_L, write_R, write_half, write_R0; double bytes_per_px; };
+// hess_first: R0 = hessianResponse(L0) (pyramid.cpp:230) as a pass of its own before step 1.  step[1..4]; step[0] is never launched.
+struct OctaveSteps { bool hess_first; BlurStep step[5]; };
+// has_next: an octave follows.  pyr_march: the marching kernel serves the octave's tap counts (default sigmas) and fuses R0 into step 1.
+inline OctaveSteps octave_steps(OctaveWant want, bool has_next, bool pyr_march)
+{
+   const bool detect = want != OctaveWant::BlursOnly;
+   OctaveSteps s = {detect && !pyr_march, {}};
+   for (int i = 1; i <= 4; i++) {
+      const bool half = i == 3 && has_next, r0 = i == 1 && pyr_march;
+      // L4 is never read by detection (getHessianPointType reads L1..L3); without detection L3 is only the source of the next octave
+      if (detect) s.step[i] = {true, i - 1, i < 4 || want == OctaveWant::DetectKeepL4, true, half, r0, 12.0 + (r0 ? 8.0 : 0.0) + (half ? 2.0 : 0.0)};
+      else if (i < 3) s.step[i] = {true, i - 1, true, false, false, false, 8.0};
+      else if (half) s.step[i] = {true, 2, false, false, true, false, 5.0};
+   }
+   return s;
+}
+
 // ---- capacities of a batch of B images whose first pyramid level is PH x PW ----
 // keypoints: max_kpts_per_mpx per megapixel of the first pyramid level, 4096 at least
 inline uint32_t keypoint_capacity(int B, int PH, int PW, double max_kpts_per_mpx)

@@ -1058,7 +1058,8 @@ int hesaff_stage_half_image(hesaff_ctx *c, const float *in, int rows, int cols, 
    HS_API_END(c)
 }
 
-// hesaff_stage_pyramid and its float twin: `image` is rows x cols pixels of 1 byte or, f32, of 4, tightly packed
+// hesaff_stage_pyramid and its float twin: `image` is rows x cols pixels of 1 byte or, f32, of 4, tightly packed.  Out come all
+// planes of every octave, L0..L4 then R0..R4, without pitch padding: the builder's, with L4 kept in a scratch plane sized here
 static int stage_pyramid(hesaff_ctx *c, const void *image, bool f32, int rows, int cols, float *planes, int *n_octaves, size_t *n_floats)
 {
    if (!c || rows < 1 || cols < 1) return HESAFF_ERR_ARG;
@@ -1080,13 +1081,23 @@ static int stage_pyramid(hesaff_ctx *c, const void *image, bool f32, int rows, i
             throw_bad_f32(0, (const uint8_t *)image, rows, cols, row_bytes);
       }
       c->b_input.ensure(bytes);
-      c->b_stage.ensure((size_t)rows * round_up(cols, 64) * 4);
+      if (!c->oct.empty()) c->b_stage.ensure((size_t)c->oct[0].rows * c->oct[0].pitch * 4);   // L4 of the largest octave, the plan's first
       HIP_TRY(hipMemcpyAsync(c->b_input.p, image, bytes, hipMemcpyHostToDevice, c->stream()));
       c->ev_used = 0;
       StageTimer tm(c);
-      Lists s = make_lists(c);
       const SrcImages src = f32 ? SrcImages::f32(c->b_input.p, (long long)bytes, (int)row_bytes) : SrcImages::u8(c->b_input.p, 1, (long long)bytes, (int)row_bytes);
-      run_detection(c, src, 1, s, tm, true, planes);
+      build_first_level(c, src, 1, tm);
+      float *pout = planes;
+      for (size_t o = 0; o < c->oct.size(); o++) {
+         const OctGeom &g = c->oct[o];
+         OctavePlanes P = octave_planes(c, o, 1);
+         P.L[4] = make_plane(c->b_stage.as<float>(), g.rows, g.cols, g.pitch);
+         build_octave(c, o, 1, P, OctaveWant::DetectKeepL4, tm);
+         // (before the next octave overwrites L3 and the response planes: the copies are in stream order)
+         for (int l = 0; l < 10; l++, pout += (size_t)g.rows * g.cols)
+            HIP_TRY(hipMemcpy2DAsync(pout, (size_t)g.cols * 4, (l < 5 ? P.L[l] : P.R[l - 5]).p, (size_t)g.pitch * 4, (size_t)g.cols * 4, g.rows, hipMemcpyDeviceToHost,
+                                     c->stream()));
+      }
       finish_stream(c);
    }
    HS_API_END(c)
@@ -1123,6 +1134,18 @@ static void fetch_hessian_list(hesaff_ctx *c, const Lists &s, int m, float *f, i
    }
 }
 
+// the end of a stage operator that has enqueued detection: waits, refuses a list that did not fit, returns its length and first `cap` entries
+static void finish_hessian_list(hesaff_ctx *c, const Lists &s, int cap, float *f, int32_t *iv, int32_t *image, int *count)
+{
+   CounterHead cn;
+   HIP_TRY(hipMemcpyAsync(&cn, &s.counters->head, sizeof cn, hipMemcpyDeviceToHost, c->stream()));
+   finish_stream(c);
+   if (cn.overflow != 0 || cn.rec > c->cap) throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded");
+   *count = (int)cn.hess_total;
+   const int m = std::min(*count, cap);
+   if (m > 0 && f && iv) fetch_hessian_list(c, s, m, f, iv, image);
+}
+
 int hesaff_stage_hessian_keypoints(hesaff_ctx *c, const uint8_t *gray, int rows, int cols, int cap, float *f, int32_t *iv, int *count)
 {
    if (!c || !gray || rows < 1 || cols < 1 || !count) return HESAFF_ERR_ARG;
@@ -1134,15 +1157,8 @@ int hesaff_stage_hessian_keypoints(hesaff_ctx *c, const uint8_t *gray, int rows,
    c->ev_used = 0;
    StageTimer tm(c);
    Lists s = make_lists(c);
-   run_detection(c, SrcImages::u8(c->b_input.p, 1, (long long)rows * cols, cols), 1, s, tm, false, nullptr);
-   CounterHead cn;
-   HIP_TRY(hipMemcpyAsync(&cn, &s.counters->head, sizeof cn, hipMemcpyDeviceToHost, c->stream()));
-   finish_stream(c);
-   if (cn.overflow != 0 || cn.rec > c->cap) throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded");
-   const int n = (int)cn.hess_total;
-   *count = n;
-   const int m = std::min(n, cap);
-   if (m > 0 && f && iv) fetch_hessian_list(c, s, m, f, iv, nullptr);
+   run_detection(c, SrcImages::u8(c->b_input.p, 1, (long long)rows * cols, cols), 1, s, tm);
+   finish_hessian_list(c, s, cap, f, iv, nullptr, count);
    HS_API_END(c)
 }
 
@@ -1160,34 +1176,23 @@ int hesaff_stage_detect_planes(hesaff_ctx *c, int n_images, int rows, int cols, 
    plan(c, n_images, rows, cols);
    const OctGeom &g = c->oct[0];
    hipStream_t st = c->stream();
-   const size_t planeF = (size_t)n_images * g.rows * g.pitch, tight = (size_t)rows * cols;
-   DPlane Lo[5], Ro[5];
-   for (int l = 0; l < 3; l++) Lo[l] = c->L[l];
-   Lo[3] = make_plane(c->geo.b_L3.as<float>(), g.rows, g.cols, g.pitch);
-   Lo[4] = make_plane(nullptr, 0, 0, 0);   // L4 is never read by detection (getHessianPointType reads L1..L3)
-   for (int l = 0; l < 5; l++) Ro[l] = make_plane(c->geo.b_R.as<float>() + l * planeF, g.rows, g.cols, g.pitch);
+   const size_t tight = (size_t)rows * cols;
+   const OctavePlanes P = octave_planes(c, 0, n_images);
    // cols floats per row: the pitch padding behind them keeps what it held.  k_extrema_march's clamped 16-byte loads read it, as they do on
    // the batch path (the blur kernels store cols floats too); it can only reach columns that are not scanned
    for (int b = 0; b < n_images; b++)
       for (int l = 0; l < 5; l++) {
          const size_t off = ((size_t)b * 5 + l) * tight;
-         HIP_TRY(hipMemcpy2DAsync(Ro[l].img(b), (size_t)g.pitch * 4, R + off, (size_t)cols * 4, (size_t)cols * 4, rows, hipMemcpyHostToDevice, st));
-         if (l < 4) HIP_TRY(hipMemcpy2DAsync(Lo[l].img(b), (size_t)g.pitch * 4, L + off, (size_t)cols * 4, (size_t)cols * 4, rows, hipMemcpyHostToDevice, st));
+         HIP_TRY(hipMemcpy2DAsync(P.R[l].img(b), (size_t)g.pitch * 4, R + off, (size_t)cols * 4, (size_t)cols * 4, rows, hipMemcpyHostToDevice, st));
+         if (l < 4) HIP_TRY(hipMemcpy2DAsync(P.L[l].img(b), (size_t)g.pitch * 4, L + off, (size_t)cols * 4, (size_t)cols * 4, rows, hipMemcpyHostToDevice, st));
       }
    c->ev_used = 0;
    StageTimer tm(c);
    Lists s = make_lists(c);
    begin_detection(c, s, n_images);
-   detect_octave(c, s, tm, n_images, 0, Lo, Ro, band);
+   detect_octave(c, s, tm, n_images, 0, P.L, P.R, band);
    order_hessian_list(c, s, tm, n_images);
-   CounterHead cn;
-   HIP_TRY(hipMemcpyAsync(&cn, &s.counters->head, sizeof cn, hipMemcpyDeviceToHost, st));
-   finish_stream(c);
-   if (cn.overflow != 0 || cn.rec > c->cap) throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded");
-   const int n = (int)cn.hess_total;
-   *count = n;
-   const int m = std::min(n, cap);
-   if (m > 0 && f && iv) fetch_hessian_list(c, s, m, f, iv, image);
+   finish_hessian_list(c, s, cap, f, iv, image, count);
    HS_API_END(c)
 }
 

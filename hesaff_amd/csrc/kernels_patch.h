@@ -903,7 +903,7 @@ __global__ __launch_bounds__(256) void k_patch_mid(HessList hl, PatchWork pw, Pa
 // nrow = 3: three consecutive window rows per step (hs_row_stream3: one tap load and one column coordinate serve three rows, 123 pair
 // chains on 64 lanes instead of 41 - a third fewer vector and two thirds fewer LDS instructions per row than the one-row form); nrow = 1: the
 // one-row form, for windows whose three rows do not fit.  Items with P outside (p_lo, p_hi] are skipped: a batch whose largest window is far
-// above the common ones runs as two launches, so that the 513..1024 windows do not live with the LDS (= occupancy) of one 2800-pixel outlier.
+// above the common ones runs as two launches, so that the windows up to HS_LARGE_SPLIT do not live with the LDS (= occupancy) of one 2800-pixel outlier.
 __global__ __launch_bounds__(256) void k_patch_large_rows(HessList hl, PatchWork pw, PatchIO io, KpTables tb, int srow_stride, int tap_stride, int nrow,
                                                           int p_lo, int p_hi)
 {

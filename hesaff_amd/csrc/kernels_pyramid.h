@@ -5,28 +5,12 @@
 #include "device_common.h"
 
 // ---------------------------------------------------------------------------------------
-// k_gray: 8-bit (1 or 3 interleaved channels) -> float32 grey, hesaff.cpp:145
-//   out = ((float(c0) + c1) + c2) / 3.0f   (channels == 1: c0 = c1 = c2, like cv::imread)
-// grid (ceil(cols/256), rows, B)
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_gray(const uint8_t *__restrict__ src, int channels, long long src_img_stride,
-                                              int src_row_stride, DPlane dst)
-{
-   const int c = blockIdx.x * 256 + threadIdx.x;
-   const int r = blockIdx.y, b = blockIdx.z;
-   if (c >= dst.cols) return;
-   const uint8_t *p = src + (long long)b * src_img_stride + (long long)r * src_row_stride + (long long)c * channels;
-   const float c0 = (float)p[0];
-   const float c1 = (float)(channels == 3 ? p[1] : p[0]);
-   const float c2 = (float)(channels == 3 ? p[2] : p[0]);
-   dst.img(b)[(long long)r * dst.pitch + c] = (c0 + c1 + c2) / 3.0f;
-}
-
-// ---------------------------------------------------------------------------------------
-// k_gray_plane: the float grey plane alone, for a batch that needs no scale space (hesaff_describe_regions with
-// HESAFF_FROM_SHAPES: normalizeAffine samples the image, nothing else).  The same values the fused initial blur
-// (k_blur_hess_march with SRC_U8 / SRC_F32) writes into the grey plane: hesaff.cpp:145 for bytes, the caller's floats as
-// they are.  FORMAT: 0 one byte per pixel, 1 three interleaved bytes, 2 float.
+// k_gray_plane: the float grey plane alone - wherever the initial blur does not make it on the way (upscaleInputImage, a
+// non-default initialSigma), and for a batch that needs no scale space (hesaff_describe_regions with HESAFF_FROM_SHAPES:
+// normalizeAffine samples the image, nothing else).  The same values the fused initial blur (k_blur_hess_march with SRC_U8 /
+// SRC_F32) writes into the grey plane: hesaff.cpp:145 for bytes,
+//   out = ((float(c0) + c1) + c2) / 3.0f   (one channel: c0 = c1 = c2, like cv::imread),
+// the caller's floats (the CV_32FC1 image of pyramid.h:73) as they are.  FORMAT: 0 one byte per pixel, 1 three interleaved bytes, 2 float.
 // A thread takes four neighbouring pixels: one 4-, 12- or 16-byte read when the source address allows it (a packed row of
 // an odd width does not start aligned: such rows are read element by element), one 16-byte store (plane rows are 256-byte aligned).
 // grid (ceil(cols / 1024), rows, B), block 256.
@@ -696,7 +680,7 @@ __device__ __forceinline__ v2f hs_hessian2(v2f ul, v2f uc, v2f ur, v2f ml, v2f m
 // pyramid.cpp:230) from the input rows that pass through LDS anyway; used by the first blur
 // of every octave so that L0 is read from HBM once instead of twice.
 // SRC: where the input rows come from.  SRC_PLANE: the float plane `in`.  SRC_U8: the 8-bit source images, converted on
-// the fly (hesaff.cpp:145, k_gray's expression).  SRC_F32: the caller's CV_32FC1 planes (pyramid.h:73), taken as they are.
+// the fly (hesaff.cpp:145, k_gray_plane's expression).  SRC_F32: the caller's CV_32FC1 planes (pyramid.h:73), taken as they are.
 // With either source the float grey plane normalizeAffine samples later is written from the same registers.  Used by the
 // initial blur (pyramid.cpp:276-280): the image is read once instead of once as the source and once as floats.
 enum { SRC_PLANE = 0, SRC_U8 = 1, SRC_F32 = 2 };

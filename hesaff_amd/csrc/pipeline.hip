@@ -913,23 +913,40 @@ void order_hessian_list(hesaff_ctx *c, const Lists &s, StageTimer &tm, int B)
    tm.end(t);
 }
 
-// The scale-space + detection part for the current plan; fills the ordered Hessian list.
-// src: the B device images of the batch (SrcImages: 8-bit with 1 or 3 interleaved channels, or float planes).
-// detect = false (hesaff_describe_regions): the scale space alone - the grey plane and every level findAffineShape can be asked to run
-// on (L0..L2 of each octave; L3 only as the source of the next octave) - with no response plane, no extrema scan, no localisation and
-// no ordering; the counters and the Hessian list are then the caller's business (ingest_regions).
-void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, StageTimer &tm, bool keep_all_planes, float *planes_out,
-                   bool detect = true)
+// ---- the pyramid builder: the first level, then octave by octave the launches of batch_plan.h's step table ----
+void launch_gray_plane(hesaff_ctx *c, const SrcImages &src, int B)
 {
-   const hesaff::OctaveSchedule &sc = c->ct.sched;
-   hipStream_t st = c->stream();
-   const float *ptaps = c->tables.pyr_taps.as<float>();
-   if (detect) begin_detection(c, s, B);
+   const dim3 grid((c->W + 1023) / 1024, c->H, B);
+   if (src.format == HS_SRC_F32) hipLaunchKernelGGL(k_gray_plane<2>, grid, dim3(256), 0, c->stream(), src.p, src.img_stride, src.row_stride, c->gray);
+   else if (src.format == HS_SRC_U8C3) hipLaunchKernelGGL(k_gray_plane<1>, grid, dim3(256), 0, c->stream(), src.p, src.img_stride, src.row_stride, c->gray);
+   else hipLaunchKernelGGL(k_gray_plane<0>, grid, dim3(256), 0, c->stream(), src.p, src.img_stride, src.row_stride, c->gray);
+}
 
-   int t = tm.begin(T_PYR);
-   DPlane none = make_plane(nullptr, 0, 0, 0);
+// The planes of octave o of a batch of B images: L[0..2] the kept levels, L[3] and R[0..4] one octave's worth of b_L3 / b_R, which every
+// octave overwrites.  L[4] is empty: detection never reads it (getHessianPointType reads L1..L3); who wants it supplies a plane.
+struct OctavePlanes { DPlane L[5], R[5]; };
+OctavePlanes octave_planes(hesaff_ctx *c, size_t o, int B)
+{
+   const OctGeom &g = c->oct[o];
+   const size_t planeF = (size_t)B * g.rows * g.pitch;
+   OctavePlanes P;
+   for (int l = 0; l < 3; l++) P.L[l] = c->L[o * 3 + l];
+   P.L[3] = make_plane(c->geo.b_L3.as<float>(), g.rows, g.cols, g.pitch);
+   P.L[4] = make_plane(nullptr, 0, 0, 0);
+   for (int l = 0; l < 5; l++) P.R[l] = make_plane(c->geo.b_R.as<float>() + l * planeF, g.rows, g.cols, g.pitch);
+   return P;
+}
+
+// The grey plane (normalizeAffine's input) and the first level L0 of octave 0, of the B device images src (SrcImages: 8-bit with 1 or
+// 3 interleaved channels, or float planes).
+void build_first_level(hesaff_ctx *c, const SrcImages &src, int B, StageTimer &tm)
+{
+   hipStream_t st = c->stream();
+   const float *taps = c->tables.pyr_taps.as<float>() + c->ct.pyr_tap_off[0];
+   const int t = tm.begin(T_PYR);
+   const DPlane none = make_plane(nullptr, 0, 0, 0);
    // Default parameters: grey conversion (hesaff.cpp:138-148) fused into the initial blur 0.5 -> 1.6 (pyramid.cpp:276-280,
-   // K = 11): the source images are read once, the float grey plane (normalizeAffine's input) and L0 are written.
+   // K = 11): the source images are read once, the float grey plane and L0 are written.
    // 8-bit images: 9 B/px (read 1, write 4 + 4); float planes: 12 B/px (read 4, write 4 + 4).
    const bool fused_gray = !c->oct.empty() && c->ct.pyr_K[0] == 11 && !c->ct.up;
    if (fused_gray) {
@@ -937,105 +954,74 @@ void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, S
       gs.p = src.p; gs.channels = src.channels(); gs.img_stride = src.img_stride; gs.row_stride = src.row_stride;
       const int tb = tm.begin(T_BLURHESS, 0);   // not one of the 58 B/px launches (bytes 0)
       if (src.format == HS_SRC_F32)
-         launch_march<11, true, false, false, false, SRC_F32>(c, c->gray, c->L[0], none, none, ptaps + c->ct.pyr_tap_off[0], 0.0f, B, DPlane(), 0.0f, gs, c->gray);
+         launch_march<11, true, false, false, false, SRC_F32>(c, c->gray, c->L[0], none, none, taps, 0.0f, B, DPlane(), 0.0f, gs, c->gray);
       else
-         launch_march<11, true, false, false, false, SRC_U8>(c, c->gray, c->L[0], none, none, ptaps + c->ct.pyr_tap_off[0], 0.0f, B, DPlane(), 0.0f, gs, c->gray);
+         launch_march<11, true, false, false, false, SRC_U8>(c, c->gray, c->L[0], none, none, taps, 0.0f, B, DPlane(), 0.0f, gs, c->gray);
       tm.end(tb);
    } else {
       // grey conversion; without an initial blur (initialSigma <= the input's own blur) it is the first level directly
-      const bool direct = c->ct.pyr_K[0] == 0 && !c->oct.empty();
-      if (src.format == HS_SRC_F32) {
-         // float planes are the grey plane already (pyramid.h:73): a pitched copy into c->gray
-         const size_t wb = (size_t)c->W * 4, dpitch = (size_t)c->gray.pitch * 4;
-         if (src.img_stride == (long long)src.row_stride * c->H)
-            HIP_TRY(hipMemcpy2DAsync(c->gray.p, dpitch, src.p, (size_t)src.row_stride, wb, (size_t)c->H * B, hipMemcpyDeviceToDevice, st));
-         else
-            for (int b = 0; b < B; b++)
-               HIP_TRY(hipMemcpy2DAsync(c->gray.img(b), dpitch, src.p + (long long)b * src.img_stride, (size_t)src.row_stride, wb, (size_t)c->H,
-                                        hipMemcpyDeviceToDevice, st));
-      } else {
-         const dim3 grid((c->W + 255) / 256, c->H, B);
-         hipLaunchKernelGGL(k_gray, grid, dim3(256), 0, st, src.p, src.channels(), src.img_stride, src.row_stride, c->gray);
-      }
+      launch_gray_plane(c, src, B);
       if (c->ct.up) {
          // pyramid.cpp:267-271: the first level is the 2x up-sampled image (doubleImage, helpers.cpp:297-329)
          const dim3 g2((c->upimg.cols + 255) / 256, c->upimg.rows, B);
          hipLaunchKernelGGL(k_double, g2, dim3(256), 0, st, c->gray, c->upimg);
       }
       const DPlane &first = c->ct.up ? c->upimg : c->gray;
-      if (direct) HIP_TRY(hipMemcpyAsync(c->L[0].p, first.p, (size_t)B * first.img_stride * 4, hipMemcpyDeviceToDevice, st));
+      if (c->ct.pyr_K[0] == 0 && !c->oct.empty()) HIP_TRY(hipMemcpyAsync(c->L[0].p, first.p, (size_t)B * first.img_stride * 4, hipMemcpyDeviceToDevice, st));
       if (!c->oct.empty() && c->ct.pyr_K[0] > 0) {
          // pyramid.cpp:276-280 initial blur 0.5 -> initialSigma
          const int tb = tm.begin(T_BLURHESS, 0);   // initial blur: not counted in the 12N launches (bytes 0)
-         launch_blur_hess<true, false, false>(c, first, c->L[0], none, none, ptaps + c->ct.pyr_tap_off[0], c->ct.pyr_K[0], 0.0f, B);
+         launch_blur_hess<true, false, false>(c, first, c->L[0], none, none, taps, c->ct.pyr_K[0], 0.0f, B);
          tm.end(tb);
       }
    }
    tm.end(t);
-   float *pout = planes_out;
-   for (size_t o = 0; o < c->oct.size(); o++) {
-      const OctGeom &g = c->oct[o];
-      const size_t planeF = (size_t)B * g.rows * g.pitch;
-      DPlane Lo[5], Ro[5];
-      for (int l = 0; l < 3; l++) Lo[l] = c->L[o * 3 + l];
-      Lo[3] = make_plane(c->geo.b_L3.as<float>(), g.rows, g.cols, g.pitch);
-      Lo[4] = none;
-      if (keep_all_planes) Lo[4] = make_plane(c->b_stage.as<float>(), g.rows, g.cols, g.pitch);
-      for (int l = 0; l < 5; l++) Ro[l] = make_plane(c->geo.b_R.as<float>() + l * planeF, g.rows, g.cols, g.pitch);
-      t = tm.begin(T_PYR);
-      // R0 = hessianResponse(L0) (pyramid.cpp:230) is fused into the first blur launch when the
-      // marching kernel handles it (default sigmas: K = 9); otherwise a separate pass.
-      const bool fuse_r0 = c->ct.pyr_march;
-      if (!fuse_r0 && detect) {
-         const dim3 grid((g.cols + 255) / 256, g.rows, B);
-         hipLaunchKernelGGL(k_hess, grid, dim3(256), 0, st, Lo[0], Ro[0], sc.norm2[0]);
-      }
-      const bool has_next = o + 1 < c->oct.size();
-      for (int i = 1; i <= 4 && !detect; i++) {
-         // the blurs alone: L1, L2, and - when an octave follows - its first level, the decimated L3 (which itself is not kept)
-         if (i == 4 || (i == 3 && !has_next)) break;
-         const float *taps = ptaps + c->ct.pyr_tap_off[i];
-         const int tb = tm.begin(T_BLURHESS, (i == 3 ? 5.0 : 8.0) * (double)B * g.rows * g.cols);
-         if (i < 3) launch_blur_hess<true, false, false>(c, Lo[i - 1], Lo[i], none, none, taps, c->ct.pyr_K[i], 0.0f, B);
-         else launch_blur_hess<false, false, true>(c, Lo[2], none, none, c->L[(o + 1) * 3], taps, c->ct.pyr_K[i], 0.0f, B);
-         tm.end(tb);
-      }
-      for (int i = 1; i <= 4 && detect; i++) {
-         // algorithmic bytes of this launch: 12 N, + 8 N when it also produces R0
-         // (read L0 + write R0 of the stand-alone pass), + 2 N for the fused decimation
-         double bytes = 12.0 * (double)B * g.rows * g.cols;
-         if (i == 1 && fuse_r0) bytes += 8.0 * (double)B * g.rows * g.cols;
-         if (i == 3 && has_next) bytes += 2.0 * (double)B * g.rows * g.cols;
-         const float *taps = ptaps + c->ct.pyr_tap_off[i];
-         const int K = c->ct.pyr_K[i];
-         const int tb = tm.begin(T_BLURHESS, bytes);
-         if (i == 1 && fuse_r0) launch_march<9, true, true, false, true>(c, Lo[0], Lo[1], Ro[1], none, taps, sc.norm2[1], B, Ro[0], sc.norm2[0]);
-         else if (i < 3) launch_blur_hess<true, true, false>(c, Lo[i - 1], Lo[i], Ro[i], none, taps, K, sc.norm2[i], B);
-         else if (i == 3) {
-            if (has_next) launch_blur_hess<true, true, true>(c, Lo[2], Lo[3], Ro[3], c->L[(o + 1) * 3], taps, K, sc.norm2[3], B);
-            else launch_blur_hess<true, true, false>(c, Lo[2], Lo[3], Ro[3], none, taps, K, sc.norm2[3], B);
-         } else {
-            if (keep_all_planes) launch_blur_hess<true, true, false>(c, Lo[3], Lo[4], Ro[4], none, taps, K, sc.norm2[4], B);
-            else launch_blur_hess<false, true, false>(c, Lo[3], none, Ro[4], none, taps, K, sc.norm2[4], B);
-         }
-         tm.end(tb);
-      }
-      tm.end(t);
-      if (planes_out) {
-         // stage API (B == 1): copy L0..L4, R0..R4 tightly packed
-         for (int l = 0; l < 5; l++) {
-            HIP_TRY(hipMemcpy2DAsync(pout, (size_t)g.cols * 4, Lo[l].p, (size_t)g.pitch * 4, (size_t)g.cols * 4, g.rows, hipMemcpyDeviceToHost, st));
-            pout += (size_t)g.rows * g.cols;
-         }
-         for (int l = 0; l < 5; l++) {
-            HIP_TRY(hipMemcpy2DAsync(pout, (size_t)g.cols * 4, Ro[l].p, (size_t)g.pitch * 4, (size_t)g.cols * 4, g.rows, hipMemcpyDeviceToHost, st));
-            pout += (size_t)g.rows * g.cols;
-         }
-      }
-      if (!detect) continue;
-      detect_octave(c, s, tm, B, o, Lo, Ro);
+}
+
+// What `want` asks of octave o, whose first level P.L[0] exists: octave_steps (batch_plan.h) says which blur launches that takes and what
+// each writes.  DetectKeepL4: P.L[4] is the caller's plane.  BlursOnly touches the blur planes and nothing else.
+void build_octave(hesaff_ctx *c, size_t o, int B, const OctavePlanes &P, OctaveWant want, StageTimer &tm)
+{
+   const hesaff::OctaveSchedule &sc = c->ct.sched;
+   const OctGeom &g = c->oct[o];
+   const OctaveSteps steps = octave_steps(want, o + 1 < c->oct.size(), c->ct.pyr_march);
+   const DPlane none = make_plane(nullptr, 0, 0, 0);
+   const int t = tm.begin(T_PYR);
+   if (steps.hess_first) {
+      const dim3 grid((g.cols + 255) / 256, g.rows, B);
+      hipLaunchKernelGGL(k_hess, grid, dim3(256), 0, c->stream(), P.L[0], P.R[0], sc.norm2[0]);
    }
-   if (!detect) return;
+   for (int i = 1; i <= 4; i++) {
+      const BlurStep &b = steps.step[i];
+      if (!b.launch) continue;
+      const DPlane &in = P.L[b.in], &outL = b.write_L ? P.L[i] : none, &outR = b.write_R ? P.R[i] : none;
+      const DPlane &half = b.write_half ? c->L[(o + 1) * 3] : none;
+      const float *taps = c->tables.pyr_taps.as<float>() + c->ct.pyr_tap_off[i];
+      const int K = c->ct.pyr_K[i];
+      const float norm2 = b.write_R ? sc.norm2[i] : 0.0f;
+      const int tb = tm.begin(T_BLURHESS, b.bytes_per_px * (double)B * g.rows * g.cols);
+      // the five output sets the table can ask for (tests/native/plan_check.cpp enumerates it), each its own instantiation
+      if (b.write_R0) launch_march<9, true, true, false, true>(c, in, outL, outR, none, taps, norm2, B, P.R[0], sc.norm2[0]);
+      else if (b.write_L && b.write_R && b.write_half) launch_blur_hess<true, true, true>(c, in, outL, outR, half, taps, K, norm2, B);
+      else if (b.write_L && b.write_R) launch_blur_hess<true, true, false>(c, in, outL, outR, none, taps, K, norm2, B);
+      else if (b.write_L) launch_blur_hess<true, false, false>(c, in, outL, none, none, taps, K, norm2, B);
+      else if (b.write_R) launch_blur_hess<false, true, false>(c, in, none, outR, none, taps, K, norm2, B);
+      else launch_blur_hess<false, false, true>(c, in, none, none, half, taps, K, norm2, B);
+      tm.end(tb);
+   }
+   tm.end(t);
+}
+
+// The scale-space + detection part for the current plan; fills the ordered Hessian list.
+void run_detection(hesaff_ctx *c, const SrcImages &src, int B, const Lists &s, StageTimer &tm)
+{
+   begin_detection(c, s, B);
+   build_first_level(c, src, B, tm);
+   for (size_t o = 0; o < c->oct.size(); o++) {
+      const OctavePlanes P = octave_planes(c, o, B);
+      build_octave(c, o, B, P, OctaveWant::Detect, tm);
+      detect_octave(c, s, tm, B, o, P.L, P.R);
+   }
    order_hessian_list(c, s, tm, B);
 }
 
@@ -1256,7 +1242,7 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
 // hesaff_set_keypoint_limit and hesaff_set_next_masks (kernels_select.h): of the ordered Hessian list run_detection left, every image
 // keeps its eligible keypoints - those on a non-zero pixel of its mask, all without one - or the keypoint_limit strongest of them, in
 // their order, and the list, its length, the per-image starts and the large-window row bounds become those of the kept keypoints -
-// everything behind sees a shorter list.  Only run_batch calls it: the stage operators and run_describe, which share run_detection,
+// everything behind sees a shorter list.  Only run_batch calls it: the stage operators and run_describe
 // neither limit nor mask.  The ranks live in b_rank (free until the pack stage's scan), the kept counts in the descriptor starts
 // (written at the end of the batch), the ordered items are still in b_cand, the length detection found stays in the counter block:
 // no buffer of its own, nothing allocated.
@@ -1297,7 +1283,7 @@ BatchResult run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W, 
    StageTimer tm(c);
    Lists s = make_lists(c);
    const int tt = tm.begin(T_TOTAL);
-   run_detection(c, src, B, s, tm, false, nullptr);
+   run_detection(c, src, B, s, tm);
    if (c->keypoint_limit > 0 || mk.base) select_keypoints(c, s, tm, B, H, W, mk);
    // the one host round trip of a batch
    return run_keypoint_stages(c, s, tm, tt, B, H, W, fetch_hessian_starts(c, B), true);
@@ -1306,7 +1292,7 @@ BatchResult run_batch(hesaff_ctx *c, const SrcImages &src, int B, int H, int W, 
 // hesaff_describe_regions on a device-resident chunk: the caller's records take the place of detection's list.  d_block (device,
 // 256-byte aligned): B + 1 record starts (int32, image b owns records starts[b] .. starts[b + 1]), then - describe_records_offset(B)
 // bytes in - the chunk's hesaff_region records, already checked by the host (describe_bad_record).  n_rec = starts[B].
-// from = HESAFF_FROM_POINTS: the scale space as detection builds it (which also yields the grey plane), then k_affine over the list.
+// from = HESAFF_FROM_POINTS: the blur planes as detection builds them (which also yields the grey plane), then k_affine over the list.
 // from = HESAFF_FROM_SHAPES: the grey plane alone (parity mode) - fast mode 2 builds the scale space too, k_patch_pyramid samples it -
 // and the affine output from the records.  Leaves what run_batch leaves.
 BatchResult run_describe(hesaff_ctx *c, const SrcImages &src, int B, int H, int W, const uint8_t *d_block, uint32_t n_rec, int from)
@@ -1329,12 +1315,11 @@ BatchResult run_describe(hesaff_ctx *c, const SrcImages &src, int B, int H, int 
    //  the planes below are enqueued after it and run while the groups are formed)
    const int32_t *hs = fetch_hessian_starts(c, B);
    if (!shapes || c->fast_pyramid) {
-      run_detection(c, src, B, s, tm, false, nullptr, false);
+      // the grey plane and every level findAffineShape can be asked to run on (L0..L2 of each octave): no response plane, no detection
+      build_first_level(c, src, B, tm);
+      for (size_t o = 0; o < c->oct.size(); o++) build_octave(c, o, B, octave_planes(c, o, B), OctaveWant::BlursOnly, tm);
    } else {
-      const dim3 grid((W + 1023) / 1024, H, B);
-      if (src.format == HS_SRC_F32) hipLaunchKernelGGL(k_gray_plane<2>, grid, dim3(256), 0, st, src.p, src.img_stride, src.row_stride, c->gray);
-      else if (src.format == HS_SRC_U8C3) hipLaunchKernelGGL(k_gray_plane<1>, grid, dim3(256), 0, st, src.p, src.img_stride, src.row_stride, c->gray);
-      else hipLaunchKernelGGL(k_gray_plane<0>, grid, dim3(256), 0, st, src.p, src.img_stride, src.row_stride, c->gray);
+      launch_gray_plane(c, src, B);
    }
    HIP_TRY(hipEventRecord(c->ev_detect_done, st));   // the affine stream starts behind the planes
    return run_keypoint_stages(c, s, tm, tt, B, H, W, hs, !shapes);

@@ -5,7 +5,7 @@ rows = list(csv.DictReader(open(sys.argv[1])))
 ks = [(int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name'].split('(')[0].replace('void ', ''), r.get('Queue_Id', '')) for r in rows]
 ks.sort()
 # the last step starts at its first pyramid launch: the initial blur that also converts the source (the only k_blur_hess_march
-# instantiation whose last template argument, SRC, is not 0), or k_gray on the non-default paths
+# instantiation whose last template argument, SRC, is not 0), or k_gray_plane on the non-default paths
 starts = [s for s, e, n, q in ks if n.startswith('k_gray') or (n.startswith('k_blur_hess_march') and not n.rstrip().endswith(', 0>'))]
 t0 = max(starts)
 ks = [k for k in ks if k[0] >= t0]

@@ -1,7 +1,7 @@
 // CPU check of the batch plan's host arithmetic (hesaff_amd/csrc/batch_plan.h; built and run by tests/test_batch_plan.py with
-// g++ -fsanitize=address,undefined).  Two kinds of checks: properties that pin the behaviour without reference to the code under test
-// (what the kernels read and write, taken from kernels_patch.h / kernels_keypoint.h and stated at each check), and a few values worked
-// out by hand.  Prints "plan_check ok"; the first failed check prints a message and ends the program with exit code 1.
+// g++ -fsanitize=address,undefined).  Three kinds of checks: properties that pin the behaviour without reference to the code under test
+// (what the kernels read and write, taken from kernels_patch.h / kernels_keypoint.h and stated at each check), a few values worked
+// out by hand, and the blur steps of an octave against the loops the step table replaced.  Prints "plan_check ok"; the first failed check prints a message and ends the program with exit code 1.
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -247,9 +247,66 @@ static void check_bands()
    CHECK(extrema_band(2160, 3840, 8) == 64, "extrema UHD B = 8");         // 16 x 17 x 8 = 2176, 16 x 34 x 8 = 4352
 }
 
+// octave_steps against the two blur loops run_detection had before the table, restated literally: which steps they launched, from which
+// level, with which outputs, and the bytes they told the stage timer (N pixels: B * rows * cols of a batch of 256 UHD images and of one small one)
+struct Launched {
+   int i, in;
+   bool wl, wr, wh, wr0;
+   double bytes;
+};
+static void check_octave_steps()
+{
+   const OctaveWant wants[3] = {OctaveWant::Detect, OctaveWant::DetectKeepL4, OctaveWant::BlursOnly};
+   const double Ns[2] = {256.0 * 2160 * 3840, 1.0 * 131 * 77};
+   for (int w = 0; w < 3; w++)
+      for (int hn = 0; hn < 2; hn++)
+         for (int pm = 0; pm < 2; pm++)
+            for (double N : Ns) {
+               const bool detect = wants[w] != OctaveWant::BlursOnly, keep_l4 = wants[w] == OctaveWant::DetectKeepL4;
+               const bool has_next = hn != 0, fuse_r0 = pm != 0;
+               std::vector<Launched> old;
+               const bool old_hess_first = !fuse_r0 && detect;
+               for (int i = 1; i <= 4 && !detect; i++) {
+                  if (i == 4 || (i == 3 && !has_next)) break;
+                  const double bytes = (i == 3 ? 5.0 : 8.0) * N;
+                  if (i < 3) old.push_back({i, i - 1, true, false, false, false, bytes});
+                  else old.push_back({i, 2, false, false, true, false, bytes});
+               }
+               for (int i = 1; i <= 4 && detect; i++) {
+                  double bytes = 12.0 * N;
+                  if (i == 1 && fuse_r0) bytes += 8.0 * N;
+                  if (i == 3 && has_next) bytes += 2.0 * N;
+                  if (i == 1 && fuse_r0) old.push_back({1, 0, true, true, false, true, bytes});
+                  else if (i < 3) old.push_back({i, i - 1, true, true, false, false, bytes});
+                  else if (i == 3) {
+                     if (has_next) old.push_back({3, 2, true, true, true, false, bytes});
+                     else old.push_back({3, 2, true, true, false, false, bytes});
+                  } else {
+                     if (keep_l4) old.push_back({4, 3, true, true, false, false, bytes});
+                     else old.push_back({4, 3, false, true, false, false, bytes});
+                  }
+               }
+               const OctaveSteps s = octave_steps(wants[w], has_next, fuse_r0);
+               CHECK(s.hess_first == old_hess_first, "want %d next %d march %d: hess_first %d", w, hn, pm, (int)s.hess_first);
+               CHECK(!s.step[0].launch, "want %d: step 0 is launched", w);
+               size_t k = 0;
+               for (int i = 1; i <= 4; i++) {
+                  const BlurStep &b = s.step[i];
+                  if (!b.launch) continue;
+                  CHECK(k < old.size() && old[k].i == i, "want %d next %d march %d: step %d is launched, the loops did not", w, hn, pm, i);
+                  const Launched &q = old[k++];
+                  CHECK(b.in == q.in && b.write_L == q.wl && b.write_R == q.wr && b.write_half == q.wh && b.write_R0 == q.wr0,
+                        "want %d next %d march %d step %d: L%d -> (%d, %d, %d, %d)", w, hn, pm, i, b.in, (int)b.write_L, (int)b.write_R, (int)b.write_half, (int)b.write_R0);
+                  CHECK(b.bytes_per_px * N == q.bytes, "want %d next %d march %d step %d: %g bytes, the loops %g", w, hn, pm, i, b.bytes_per_px * N, q.bytes);
+               }
+               CHECK(k == old.size(), "want %d next %d march %d: %zu launches, the loops %zu", w, hn, pm, k, old.size());
+            }
+}
+
 int main()
 {
    check_octaves();
+   check_octave_steps();
    check_capacity();
    check_layouts();
    check_groups();

@@ -355,12 +355,14 @@ def test_chunks_and_mixed_sizes(ctx, from_):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("kw", [dict(upscaleInputImage=1), dict(maxIterations=2), dict(mrSize=4.0), dict(fast=2)],
+@pytest.mark.parametrize("kw", [dict(upscaleInputImage=1), dict(maxIterations=2), dict(mrSize=4.0), dict(fast=2),
+                                dict(initialSigma=1.0), dict(initialSigma=2.0)],
                          ids=lambda kw: ",".join("%s=%g" % kv for kv in kw.items()))
 def test_parameter_variants(oracle, kw):
     """T7: on a context with other parameters both modes round-trip to that context's own detect_regions (fast = 2 included: its
-    FROM_SHAPES builds the pyramid its larger windows are sampled from); the parity-mode variants also describe foreign keypoints
-    as the oracle does with those parameters."""
+    FROM_SHAPES builds the pyramid its larger windows are sampled from; initialSigma 1.0 / 2.0: FROM_POINTS builds its blur planes with
+    the LDS-tile / the two-pass kernels, the launch that only decimates included); the parity-mode variants also describe foreign
+    keypoints as the oracle does with those parameters."""
     p = _params(**kw)
     imgs = [band_noise_image(300, 420, 91), band_noise_image(200, 260, 92, SMALL_BANDS)]
     with hesaff_amd.HesaffContext(p, device=0) as c2:

@@ -105,13 +105,45 @@ def test_hessian_and_half(ctx, oracle):
 def test_pyramid_planes(ctx, oracle, hw, seed):
     img = band_noise_image(hw[0], hw[1], seed, SMALL_BANDS if hw[0] < 400 else None or SMALL_BANDS)
     o = oracle.OracleRun(oracle.gray_from_u8(img), keep_planes=True, detect_only=True)
-    pyr = ctx.pyramid(img)
+    _assert_pyramid_equals_oracle(ctx.pyramid(img), o)
+
+
+# The pyramid's non-default branches: initialSigma 1.0 the LDS-tile kernel, 2.0 the two-pass kernels with stand-alone k_hess / k_half,
+# 0.45 no initial blur (the grey plane is the first level), upscaleInputImage k_double (and, at 0.9, no initial blur behind it).
+PYRAMID_VARIANTS = [dict(initialSigma=1.0), dict(initialSigma=2.0), dict(initialSigma=0.45), dict(upscaleInputImage=1),
+                    dict(upscaleInputImage=1, initialSigma=0.9)]
+
+
+def _assert_pyramid_equals_oracle(pyr, o):
     assert len(pyr) == o.n_octaves()
     for oi, (Ls, Rs) in enumerate(pyr):
         for l in range(5):
             assert_bit_equal(Ls[l], o.plane(oi, 0, l), "octave %d L%d" % (oi, l))
             ref = o.plane(oi, 1, l)
             assert_bit_equal(Rs[l][1:-1, 1:-1], ref[1:-1, 1:-1], "octave %d R%d" % (oi, l))
+
+
+@pytest.mark.parametrize("kw", PYRAMID_VARIANTS, ids=lambda kw: ",".join("%s=%g" % kv for kv in kw.items()))
+def test_pyramid_planes_non_default(oracle, kw):
+    """131 x 77: three octaves (four when up-sampled), so an octave with and without a successor, and a partial 64-column strip."""
+    import hesaff_amd
+    p = _params(**kw)
+    img = band_noise_image(131, 77, 7, SMALL_BANDS)
+    o = oracle.OracleRun(oracle.gray_from_u8(img), keep_planes=True, detect_only=True, params=p)
+    assert o.n_octaves() >= 3
+    with hesaff_amd.HesaffContext(p, device=0) as c2:
+        _assert_pyramid_equals_oracle(c2.pyramid(img), o)
+
+
+@pytest.mark.parametrize("kw", [dict(initialSigma=1.0), dict(upscaleInputImage=1)], ids=lambda kw: ",".join("%s=%g" % kv for kv in kw.items()))
+def test_pyramid_planes_non_default_f32(oracle, kw):
+    """The float twin: the grey plane of the same image as a float plane, which k_gray_plane<2> copies."""
+    import hesaff_amd
+    p = _params(**kw)
+    gray = oracle.gray_from_u8(band_noise_image(131, 77, 7, SMALL_BANDS))
+    o = oracle.OracleRun(gray, keep_planes=True, detect_only=True, params=p)
+    with hesaff_amd.HesaffContext(p, device=0) as c2:
+        _assert_pyramid_equals_oracle(c2.pyramid_f32(gray), o)
 
 
 @pytest.mark.parametrize("hw,seed", [((131, 77), 7), ((96, 96), 8), ((240, 320), 10), ((480, 640), 1234)])
@@ -490,6 +522,21 @@ def test_non_default_parameters(oracle, kw):
             assert hesaff_amd.format_sift(keys, p.mrSize) == o.export_text()
             total += len(keys)
         assert total > 30, "parameter set leaves too few keypoints for a meaningful comparison"
+
+
+def test_non_fused_grey_path_three_channels(oracle):
+    """initialSigma = 1.0 takes the grey conversion out of the initial blur (k_gray_plane<1>); rows of 131 x 3 bytes do not start
+    4-byte aligned, so the element-wise branch runs beside the 12-byte reads."""
+    import hesaff_amd
+    p = _params(initialSigma=1.0)
+    rng = np.random.default_rng(4)
+    base = band_noise_image(97, 131, 33, SMALL_BANDS).astype(np.int32)
+    bgr = np.stack([np.clip(base + rng.integers(-20, 20, base.shape), 0, 255) for _ in range(3)], axis=-1).astype(np.uint8)
+    o = oracle.OracleRun(oracle.gray_from_u8(bgr), params=p)
+    assert o.n_keys >= 30
+    with hesaff_amd.HesaffContext(p, device=0) as c2:
+        (n_hess, keys), = c2.detect_batch([bgr])
+    _assert_keys_equal_oracle(keys, n_hess, o, "97x131x3, initialSigma=1")
 
 
 def test_direct_branch_is_taken_with_small_mr_size(oracle):

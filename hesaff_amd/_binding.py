@@ -232,6 +232,10 @@ def load_library():
         L.hesaff_set_orientation.argtypes = [vp, C.c_int]
         L.hesaff_get_orientation.argtypes = [vp, C.POINTER(C.c_int)]
         L.hesaff_stage_orientation.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p]
+    if hasattr(L, "hesaff_set_orientation_count"):   # (likewise)
+        L.hesaff_set_orientation_count.argtypes = [vp, C.c_int]
+        L.hesaff_get_orientation_count.argtypes = [vp, C.POINTER(C.c_int)]
+        L.hesaff_stage_orientation_peaks.argtypes = [vp, C.c_int, _f32p, C.c_int, _i32p, _i32p, _f32p]
     if hasattr(L, "hesaff_set_descriptor"):   # (likewise)
         L.hesaff_set_descriptor.argtypes = [vp, C.c_int]
         L.hesaff_get_descriptor.argtypes = [vp, C.POINTER(C.c_int)]
@@ -276,6 +280,7 @@ ABI_SYMBOLS = [
     "hesaff_set_orientation", "hesaff_get_orientation", "hesaff_stage_orientation",
     "hesaff_set_keypoint_grid", "hesaff_get_keypoint_grid", "hesaff_stage_detect_planes",
     "hesaff_set_descriptor", "hesaff_get_descriptor", "hesaff_stage_sift_mode",
+    "hesaff_set_orientation_count", "hesaff_get_orientation_count", "hesaff_stage_orientation_peaks",
 ]
 
 # hesaff_set_descriptor's modes
@@ -785,6 +790,23 @@ class HesaffContext:
     def orientation(self, mode):
         self.set_orientation(mode)
 
+    def set_orientation_count(self, k):
+        """hesaff_set_orientation_count: up to k keys per region, k in 1..4 (default 1), one per peak of the orientation histogram
+        within 80 % of the highest (definition in include/hesaff_amd.h).  Read in ORI_DOMINANT only; inert in ORI_UP.  With k > 1 a
+        region's keys are adjacent rows in ascending rank, REGION_DTYPE's `key` is the first and `reserved` their number, and an image
+        may have more keys than Hessian keypoints."""
+        self._check(self.L.hesaff_set_orientation_count(self.h, int(k)))
+
+    @property
+    def orientation_count(self):
+        k = C.c_int(0)
+        self._check(self.L.hesaff_get_orientation_count(self.h, C.byref(k)))
+        return k.value
+
+    @orientation_count.setter
+    def orientation_count(self, k):
+        self.set_orientation_count(k)
+
     def set_descriptor(self, mode):
         """hesaff_set_descriptor: DESC_SIFT / "sift" (default: the reference's bytes, bit for bit) or DESC_ROOTSIFT / "rootsift": the
         descriptor vector is L1-normalised and square-rooted on the device before it is quantised (definition in
@@ -953,6 +975,15 @@ class HesaffContext:
         theta = np.zeros(n, np.float32); hist = np.zeros((n, 36), np.float32); cs = np.zeros((n, 2), np.float32)
         self._check(self.L.hesaff_stage_orientation(self.h, n, p, theta, hist, cs))
         return (theta, hist, cs) if parts else theta
+
+    def orientation_peaks_of(self, patches, k=4):
+        """hesaff_stage_orientation_peaks on [n, 41, 41] patches with orientation count k -> (n_ori [n] int32, bins [n, 4] int32,
+        theta [n, 4] float32); beyond n_ori a bin is -1 and an angle 0."""
+        p = np.ascontiguousarray(patches, np.float32).reshape(-1, 41 * 41)
+        n = len(p)
+        n_ori = np.zeros(n, np.int32); bins = np.zeros((n, 4), np.int32); theta = np.zeros((n, 4), np.float32)
+        self._check(self.L.hesaff_stage_orientation_peaks(self.h, n, p, int(k), n_ori, bins, theta))
+        return n_ori, bins, theta
 
     def sift_alive(self, patches, alive, fill=0):
         """-> desc [n, 128] u8, every byte `fill` before the call: rows of keypoints with alive == 0 keep it (hesaff_stage_sift_alive)."""

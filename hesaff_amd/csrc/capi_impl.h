@@ -899,6 +899,20 @@ int hesaff_set_orientation(hesaff_ctx *c, int mode)
    return HESAFF_OK;
 }
 
+int hesaff_set_orientation_count(hesaff_ctx *c, int k)
+{
+   if (!c || k < 1 || k > HS_ORI_MAX_COUNT) return HESAFF_ERR_ARG;
+   c->orientation_count = k;
+   return HESAFF_OK;
+}
+
+int hesaff_get_orientation_count(const hesaff_ctx *c, int *k)
+{
+   if (!c || !k) return HESAFF_ERR_ARG;
+   *k = c->orientation_count;
+   return HESAFF_OK;
+}
+
 int hesaff_get_orientation(const hesaff_ctx *c, int *mode)
 {
    if (!c || !mode) return HESAFF_ERR_ARG;
@@ -1356,6 +1370,37 @@ int hesaff_stage_orientation(hesaff_ctx *c, int n, const float *patches, float *
    if (hist) HIP_TRY(hipMemcpyAsync(hist, base + off_hist, N * HS_ORI_BINS * 4, hipMemcpyDeviceToHost, c->stream()));
    if (cs) HIP_TRY(hipMemcpyAsync(cs, base + off_cs, N * 8, hipMemcpyDeviceToHost, c->stream()));
    finish_stream(c);
+   HS_API_END(c)
+}
+
+// k_orientation_peaks on caller-supplied patches: every keypoint alive, no frame to turn, no rank arrays
+int hesaff_stage_orientation_peaks(hesaff_ctx *c, int n, const float *patches, int k, int32_t *n_ori, int32_t *bins, float *theta)
+{
+   if (!c || !patches || !n_ori || !bins || !theta || n < 0 || k < 1 || k > HS_ORI_MAX_COUNT) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   bind_device(c);
+   if (n == 0) return HESAFF_OK;
+   const size_t N = (size_t)n;
+   // patches | n_ori | bins | theta
+   const size_t off_n = N * HS_PATCH_PIX * 4, off_bins = off_n + N * 4, off_theta = off_bins + N * HS_ORI_MAX_COUNT * 4, total = off_theta + N * HS_ORI_MAX_COUNT * 4;
+   c->b_stage.ensure(total);
+   char *base = (char *)c->b_stage.p;
+   HIP_TRY(hipMemcpyAsync(base, patches, N * HS_PATCH_PIX * 4, hipMemcpyHostToDevice, c->stream()));
+   HIP_TRY(hipMemsetAsync(base + off_n, 0, total - off_n, c->stream()));
+   OrientIO oi;
+   memset(&oi, 0, sizeof oi);
+   oi.patches = (const float *)base; oi.h_lo = 0; oi.h_hi = (uint32_t)n;
+   OrientRanks mr;
+   memset(&mr, 0, sizeof mr);
+   mr.K = k; mr.n_ori = (int32_t *)(base + off_n); mr.bins = (int32_t *)(base + off_bins); mr.thetas = (float *)(base + off_theta);
+   hipLaunchKernelGGL(k_orientation_peaks, dim3(orientation_grid(c, (uint32_t)n)), dim3(64), 0, c->stream(), oi, c->tables.view, mr);
+   // (an orientation count below 4 leaves the ranks beyond it to the host: bin -1, angle 0)
+   HIP_TRY(hipMemcpyAsync(n_ori, base + off_n, N * 4, hipMemcpyDeviceToHost, c->stream()));
+   HIP_TRY(hipMemcpyAsync(bins, base + off_bins, N * HS_ORI_MAX_COUNT * 4, hipMemcpyDeviceToHost, c->stream()));
+   HIP_TRY(hipMemcpyAsync(theta, base + off_theta, N * HS_ORI_MAX_COUNT * 4, hipMemcpyDeviceToHost, c->stream()));
+   finish_stream(c);
+   for (size_t i = 0; i < N; i++)
+      for (int j = k; j < HS_ORI_MAX_COUNT; j++) { bins[i * HS_ORI_MAX_COUNT + j] = -1; theta[i * HS_ORI_MAX_COUNT + j] = 0.0f; }
    HS_API_END(c)
 }
 

@@ -90,53 +90,92 @@ struct ScheduleOptions {
 //     every first-pass patch kernel on every stream (the join);
 //   - every second-pass patch kernel reads the turned frames and what patch_rebin(g) counted: behind both;
 //   - the descriptors of g read the second pass's patches: extract-done is recorded behind the second join.
-// With ORIENTED false nothing of this is instantiated: the device needs neither member, and the sequence is the one above.
-template <bool ORIENTED, class Device> void run_group_schedule_as(Device &dev, int n_groups, const ScheduleOptions &o)
+// With the form PLAIN nothing of this is instantiated: the device needs neither member, and the sequence is the one above.
+//
+// The peaks order (PEAKS, hesaff_set_orientation_count K > 1: run_group_schedule_peaks below) gives a group K rank passes.  The unit
+// of the pipeline is the (group, rank) pair, virtual index v = g * K + r, in slot v % HS_NSLOT; the events of a slot carry v where the
+// other orders carry g.  Rank 0 of a group is the oriented order's patch stage - pass one, the orientation kernel and rank 0's pass in one
+// slot - and each rank r >= 1 is one more patch pass into the next slot and one more descriptor chain.  It asks of the device, besides the
+// oriented order's members (orientation(g, slot) being the multi form, which also writes the frames and flags of every rank >= 1):
+//   rank_prepare(g, r)                      main stream: the bin counters cleared, k_prepare_patch_second over rank r's frames, restricted
+//                                           to the keypoints that have a rank r; the start of the pass's timer bracket
+//   rank_patch_kernels(g, r, slot, n_side)  patch_kernels over rank r's frames and bins, patches into `slot`
+//   rank_descriptors(g, r, slot, stream)    the descriptor kernels over `slot` into rank r's descriptor rows (r = 0: descriptors(g, ..))
+// What it adds to the guarantees (tests/native/schedule_peaks_check.cpp):
+//   - rank_prepare(g, r) reads the frames and flags orientation(g) wrote, and clears the counters the pass before still reads: behind
+//     orientation(g) and behind every patch kernel of the pair before on every stream;
+//   - the patch kernels of (g, r) read what rank_prepare(g, r) counted, and write a slot the descriptors of the pair HS_NSLOT back
+//     have finished with;
+//   - the descriptors of (g, r) read every patch of (g, r); the chains stand on one stream in ascending v, so a region's ranks are
+//     described in order and the one copy of the intermediates serves one pair at a time;
+//   - the main stream ends behind the last chain of every slot.
+// A pass with no live keypoint costs its launches: the host does not know the counts.
+enum Form { PLAIN = 0, ORIENTED = 1, PEAKS = 2 };
+template <int FORM, class Device> void run_group_schedule_as(Device &dev, int n_groups, const ScheduleOptions &o, int K = 1)
 {
    const Stream as = o.overlap ? S_AFFINE : S_MAIN, ss = o.overlap ? S_DESC : S_MAIN;
    const bool affine_events = o.overlap && o.with_affine;
+   if constexpr (FORM != PEAKS) K = 1;
+   const int n_units = n_groups * K;
    if (affine_events) dev.wait(as, ev_detect_done());
    auto affine = [&](int g) {
       if (!o.with_affine) return;
       dev.affine(g, as);
       if (o.overlap) dev.record(ev_affine_done(g), as);
    };
-   // the descriptor kernels of group g, behind its patches
-   auto descriptors = [&](int g) {
-      const int slot = g % HS_NSLOT;
-      if (o.overlap) dev.wait(ss, ev_extract_done(slot, g));
-      dev.descriptors(g, slot, ss);
-      dev.record(ev_sift_done(slot, g), ss);
+   // the descriptor kernels of unit v (group v / K, rank v % K), behind its patches
+   auto descriptors = [&](int v) {
+      const int slot = v % HS_NSLOT;
+      if (o.overlap) dev.wait(ss, ev_extract_done(slot, v));
+      if constexpr (FORM == PEAKS) {
+         if (v % K) dev.rank_descriptors(v / K, v % K, slot, ss);
+         else dev.descriptors(v / K, slot, ss);
+      } else {
+         dev.descriptors(v, slot, ss);
+      }
+      dev.record(ev_sift_done(slot, v), ss);
    };
    if (n_groups > 0) affine(0);
    bool slot_used[HS_NSLOT] = {};
-   for (int g = 0; g < n_groups; g++) {
-      if (g + 1 < n_groups) affine(g + 1);
-      if (affine_events) dev.wait(S_MAIN, ev_affine_done(g));
-      const int slot = g % HS_NSLOT;
-      if (slot_used[slot]) dev.wait(S_MAIN, ev_sift_done(slot, g - HS_NSLOT));   // the slot's previous descriptors are finished
-      dev.patch_prepare(g);
-      fork_side_streams(dev, g, o.n_side);
-      dev.patch_kernels(g, slot, o.n_side);
-      if (g > 0 && o.sift_inside) descriptors(g - 1);
-      join_side_streams(dev, g, o.n_side);
-      if constexpr (ORIENTED) {
-         dev.orientation(g, slot);
-         dev.patch_rebin(g);
-         fork_side_streams(dev, g, o.n_side);
+   for (int v = 0; v < n_units; v++) {
+      const int g = v / K, r = v % K;
+      if (r == 0) {
+         if (g + 1 < n_groups) affine(g + 1);
+         if (affine_events) dev.wait(S_MAIN, ev_affine_done(g));
+      }
+      const int slot = v % HS_NSLOT;
+      if (slot_used[slot]) dev.wait(S_MAIN, ev_sift_done(slot, v - HS_NSLOT));   // the slot's previous descriptors are finished
+      if (r == 0) {
+         dev.patch_prepare(g);
+         fork_side_streams(dev, v, o.n_side);
          dev.patch_kernels(g, slot, o.n_side);
-         join_side_streams(dev, g, o.n_side);
+         if (v > 0 && o.sift_inside) descriptors(v - 1);
+         join_side_streams(dev, v, o.n_side);
+         if constexpr (FORM != PLAIN) {
+            dev.orientation(g, slot);
+            dev.patch_rebin(g);
+            fork_side_streams(dev, v, o.n_side);
+            dev.patch_kernels(g, slot, o.n_side);
+            join_side_streams(dev, v, o.n_side);
+         }
+      } else if constexpr (FORM == PEAKS) {
+         dev.rank_prepare(g, r);
+         fork_side_streams(dev, v, o.n_side);
+         dev.rank_patch_kernels(g, r, slot, o.n_side);
+         if (o.sift_inside) descriptors(v - 1);
+         join_side_streams(dev, v, o.n_side);
       }
       dev.patch_done(g);
-      dev.record(ev_extract_done(slot, g), S_MAIN);
+      dev.record(ev_extract_done(slot, v), S_MAIN);
       slot_used[slot] = true;
-      if (!o.sift_inside) descriptors(g);
+      if (!o.sift_inside) descriptors(v);
    }
-   if (n_groups > 0 && o.sift_inside) descriptors(n_groups - 1);
+   if (n_units > 0 && o.sift_inside) descriptors(n_units - 1);
    for (int sl = 0; sl < HS_NSLOT; sl++)
-      if (slot_used[sl]) dev.wait(S_MAIN, ev_sift_done(sl, (n_groups - 1 - sl) / HS_NSLOT * HS_NSLOT + sl));   // the slot's last group
+      if (slot_used[sl]) dev.wait(S_MAIN, ev_sift_done(sl, (n_units - 1 - sl) / HS_NSLOT * HS_NSLOT + sl));   // the slot's last unit
 }
-template <class Device> void run_group_schedule(Device &dev, int n_groups, const ScheduleOptions &o) { run_group_schedule_as<false>(dev, n_groups, o); }
-template <class Device> void run_group_schedule_oriented(Device &dev, int n_groups, const ScheduleOptions &o) { run_group_schedule_as<true>(dev, n_groups, o); }
+template <class Device> void run_group_schedule(Device &dev, int n_groups, const ScheduleOptions &o) { run_group_schedule_as<PLAIN>(dev, n_groups, o); }
+template <class Device> void run_group_schedule_oriented(Device &dev, int n_groups, const ScheduleOptions &o) { run_group_schedule_as<ORIENTED>(dev, n_groups, o); }
+template <class Device> void run_group_schedule_peaks(Device &dev, int n_groups, int K, const ScheduleOptions &o) { run_group_schedule_as<PEAKS>(dev, n_groups, o, K); }
 
 }   // namespace hesaff_sched

@@ -125,11 +125,20 @@ struct AffineHessianDetector {
    // rectifyAffineTransformationUpIsUp (hesaff.cpp:79).  HESAFF_ORI_DOMINANT: every region's frame is turned by the dominant gradient
    // angle of its own patch before normalizeAffine runs a second time and SIFT describes it; `keys` then holds A' = A R(theta) (theta =
    // atan2(-a12, a11)), descriptors follow an in-plane rotation of the image, and a region normalizeAffine rejects in either run has
-   // no key.  The callbacks replay what they replay in mode 0: U stays un-rectified and un-turned.  One orientation per region.
+   // no key.  The callbacks replay what they replay in mode 0: U stays un-rectified and un-turned.  One orientation per region
+   // unless setOrientationCount says otherwise.
    // HESAFF_ORI_UP (default): the reference's behaviour, bit for bit.  Applies to detectPyramidKeypoints and to the batch forms below.
    void setOrientation(int mode)
    {
       if (hesaff_set_orientation(ctx_, mode) != HESAFF_OK) throw std::invalid_argument("orientation is HESAFF_ORI_UP or HESAFF_ORI_DOMINANT");
+   }
+
+   // Secondary orientation peaks (hesaff_set_orientation_count, include/hesaff_amd.h): with HESAFF_ORI_DOMINANT a region gets up to k
+   // keys, k in 1..4, one per peak of its orientation histogram within 80 % of the highest, adjacent in `keys` in ascending rank - `keys`
+   // may then be longer than the number of regions.  The callbacks still replay once per region.  1 (default): one key per region.
+   void setOrientationCount(int k)
+   {
+      if (hesaff_set_orientation_count(ctx_, k) != HESAFF_OK) throw std::invalid_argument("orientation count is 1..4");
    }
 
    // No counterpart in the reference (hesaff_set_descriptor, include/hesaff_amd.h), whose descriptors are SIFT bytes.

@@ -35,6 +35,9 @@
 //       --orientation up | dominant   the frame every region is described in (hesaff_set_orientation): the reference's "up is up" frame
 //                                     (default), or that frame turned by the dominant gradient angle of the region's own patch, which makes
 //                                     the descriptors follow an in-plane rotation of the image.  Batch form, and behind a single image.
+//       --orientations K              with --orientation dominant: up to K rows per region, K in 1..4 (default 1), one per peak of the region's
+//                                     orientation histogram within 80 % of the highest (hesaff_set_orientation_count).  Batch form, and behind a
+//                                     single image.
 //       --descriptor sift | rootsift  what the 128 bytes of a row hold (hesaff_set_descriptor): the reference's SIFT bytes (default), or RootSIFT -
 //                                     the vector L1-normalised and square-rooted on the device before it is quantised, for retrieval and matching
 //                                     under the Hellinger kernel.  The file formats are unchanged.  Batch form, and behind a single image.
@@ -111,7 +114,7 @@ bool parse_devices(const char *spec, std::vector<int> &out)
 // hesaff --batch: the list is cut into contiguous shards, one per device context (hesaff_shard_range); every shard runs
 // through hesaff_process_files - decode threads -> device -> writer threads, bounded memory - on its own host thread.
 int run_batch_mode(const char *list_path, const char *devices_spec, int out_format, bool dynamic, int fast, int resume, int host_share, int runtime_nice,
-                   int max_keypoints, int orientation, int grid_rows, int grid_cols, int descriptor)
+                   int max_keypoints, int orientation, int grid_rows, int grid_cols, int descriptor, int orientations)
 {
    std::ifstream lf(list_path);
    if (!lf) { fprintf(stderr, "hesaff: cannot read list '%s'\n", list_path); return 1; }
@@ -164,6 +167,7 @@ int run_batch_mode(const char *list_path, const char *devices_spec, int out_form
       hesaff_set_keypoint_limit(ctx, max_keypoints);
       hesaff_set_keypoint_grid(ctx, grid_rows, grid_cols);   // (main checked it against the limit)
       hesaff_set_orientation(ctx, orientation);
+      hesaff_set_orientation_count(ctx, orientations);
       hesaff_set_descriptor(ctx, descriptor);
       hesaff_host_plan hp;   // this device's share of the host: the library's one rule (include/hesaff_amd.h)
       hesaff_host_plan_for(world * host_share, &hp);
@@ -242,7 +246,7 @@ int main(int argc, char **argv)
    for (int i = 1; i < argc; i++) batch = batch || strcmp(argv[i], "--batch") == 0;
    if (batch) {
       const char *devices = nullptr, *list = nullptr;
-      int out_format = HESAFF_OUT_TEXT, fast = 0, host_share = 1, runtime_nice = -1, max_keypoints = 0, orientation = HESAFF_ORI_UP, grid_rows = 1, grid_cols = 1, descriptor = HESAFF_DESC_SIFT;
+      int out_format = HESAFF_OUT_TEXT, fast = 0, host_share = 1, runtime_nice = -1, max_keypoints = 0, orientation = HESAFF_ORI_UP, grid_rows = 1, grid_cols = 1, descriptor = HESAFF_DESC_SIFT, orientations = 1;
       bool bad = false, grid = false, dynamic = false;
       int resume = 0;
       for (int i = 1; i < argc && !bad; i += 2) {
@@ -271,6 +275,10 @@ int main(int argc, char **argv)
             if (strcmp(argv[i + 1], "up") == 0) orientation = HESAFF_ORI_UP;
             else if (strcmp(argv[i + 1], "dominant") == 0) orientation = HESAFF_ORI_DOMINANT;
             else bad = true;
+         } else if (strcmp(argv[i], "--orientations") == 0) {
+            // one digit, 1..4 (hesaff_set_orientation_count; read with --orientation dominant only)
+            if (argv[i + 1][0] < '1' || argv[i + 1][0] > '4' || argv[i + 1][1] != 0) bad = true;
+            else orientations = argv[i + 1][0] - '0';
          } else if (strcmp(argv[i], "--descriptor") == 0) {
             if (strcmp(argv[i + 1], "sift") == 0) descriptor = HESAFF_DESC_SIFT;
             else if (strcmp(argv[i + 1], "rootsift") == 0) descriptor = HESAFF_DESC_ROOTSIFT;
@@ -290,8 +298,8 @@ int main(int argc, char **argv)
       }
       // a grid divides a budget: without --max-keypoints, or with more cells than keypoints, there is nothing to divide
       if (grid && (max_keypoints < 1 || grid_rows * grid_cols > max_keypoints)) bad = true;
-      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1] [--max-keypoints N] [--descriptor sift|rootsift] [--orientation up|dominant] [--grid RxC]\n"); return 1; }
-      return run_batch_mode(list, devices, out_format, dynamic, fast, resume, host_share, runtime_nice, max_keypoints, orientation, grid_rows, grid_cols, descriptor);
+      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1] [--max-keypoints N] [--orientations 1..4] [--descriptor sift|rootsift] [--orientation up|dominant] [--grid RxC]\n"); return 1; }
+      return run_batch_mode(list, devices, out_format, dynamic, fast, resume, host_share, runtime_nice, max_keypoints, orientation, grid_rows, grid_cols, descriptor, orientations);
    }
    if (argc > 1) {
       uint8_t *data = nullptr;
@@ -335,6 +343,19 @@ int main(int argc, char **argv)
             return 1;
          }
       }
+      // --orientations 1..4 behind the image (the last one counts; read with --orientation dominant only)
+      int orientations = 1;
+      for (int i = 2; i < argc; i++) {
+         if (strcmp(argv[i], "--orientations") != 0) continue;
+         const char *v = i + 1 < argc ? argv[++i] : "";
+         if (v[0] >= '1' && v[0] <= '4' && v[1] == 0) orientations = v[0] - '0';
+         else {
+            fprintf(stderr, "hesaff: --orientations takes 1, 2, 3 or 4\n");
+            hesaff_free(data);
+            if (mask) hesaff_free(mask);
+            return 1;
+         }
+      }
       // --descriptor sift | rootsift behind the image (the last one counts)
       int descriptor = HESAFF_DESC_SIFT;
       for (int i = 2; i < argc; i++) {
@@ -343,7 +364,7 @@ int main(int argc, char **argv)
          if (strcmp(v, "sift") == 0) descriptor = HESAFF_DESC_SIFT;
          else if (strcmp(v, "rootsift") == 0) descriptor = HESAFF_DESC_ROOTSIFT;
          else {
-            fprintf(stderr, "hesaff: usage: hesaff <image> [--mask <mask file>] [--orientation up|dominant] [--descriptor sift|rootsift]\n");
+            fprintf(stderr, "hesaff: usage: hesaff <image> [--mask <mask file>] [--orientation up|dominant] [--orientations 1..4] [--descriptor sift|rootsift]\n");
             hesaff_free(data);
             if (mask) hesaff_free(mask);
             return 1;
@@ -354,6 +375,7 @@ int main(int argc, char **argv)
          hesaff_amd::AffineHessianDetector detector(par);
          if (mask) detector.setMask(mask);
          detector.setOrientation(orientation);
+         detector.setOrientationCount(orientations);
          detector.setDescriptor(descriptor);
          const auto t1 = std::chrono::steady_clock::now();
          detector.detectPyramidKeypoints(data, w, h, ch);

@@ -429,6 +429,8 @@ struct hesaff_ctx {
    int grid_rows = 1, grid_cols = 1;   // hesaff_set_keypoint_grid: with a limit N and more than one cell, the N / cells strongest of every cell
    int descriptor = HESAFF_DESC_SIFT;  // hesaff_set_descriptor: which instantiation of k_sift_hist the pipeline's launch_sift takes
    int orientation = HESAFF_ORI_UP;    // hesaff_set_orientation: HESAFF_ORI_DOMINANT runs the oriented order of group_schedule.h (run_keypoint_stages)
+   int orientation_count = 1;          // hesaff_set_orientation_count: keys per region at most (read in HESAFF_ORI_DOMINANT only: ori_count)
+   DevBuf b_ori_ranks;                 // the rank arrays of an orientation count K > 1 (OrientRanks, kernels_orient.h): allocated by the first such call
    ArmedMasks next_masks;              // hesaff_set_next_masks / _device: the masks of the next detecting call (taken, so cleared, by take_masks)
    int stage_threads = 4;              // host threads that copy a chunk's pixels into pinned memory (hesaff_process_files: within its thread budget)
    DevEvent ev_detect_done, ev_batch_done;   // blocking-sync events: the host sleeps instead of spinning
@@ -831,6 +833,23 @@ void run_patch_stage(hesaff_ctx *c, const Lists &s, const DPlane &image, float *
 // k_orientation's grid over n keypoints: one wavefront each, at most the 8 blocks per CU its 19536 B (19.1 KiB) of LDS admit
 uint32_t orientation_grid(const hesaff_ctx *c, uint32_t n) { return std::max<uint32_t>(1u, std::min<uint32_t>(n, (uint32_t)c->n_cu * 8u)); }
 
+// The orientation count in force: hesaff_set_orientation_count's K in HESAFF_ORI_DOMINANT, 1 - the feature inert - in HESAFF_ORI_UP.
+int ori_count(const hesaff_ctx *c) { return c->orientation == HESAFF_ORI_DOMINANT ? c->orientation_count : 1; }
+
+// The rank arrays of K > 1 over the current keypoint capacity: frames, window sides, flags and descriptor rows of the ranks 1 .. K - 1,
+// 152 bytes per keypoint and rank.  ensure_rank_arrays allocates them (HESAFF_ERR_NOMEM when the device cannot hold them).
+OrientRanks rank_arrays(const hesaff_ctx *c, int K)
+{
+   OrientRanks r;
+   memset(&r, 0, sizeof r);
+   const size_t n = (size_t)(K - 1) * c->cap;
+   char *base = (char *)c->b_ori_ranks.p;
+   r.K = K; r.cap = c->cap;
+   r.A = (float *)base; r.P0 = (int32_t *)(base + n * 16); r.alive = (int32_t *)(base + n * 20); r.desc = (uint8_t *)(base + n * 24);
+   return r;
+}
+void ensure_rank_arrays(hesaff_ctx *c, int K) { c->b_ori_ranks.ensure(std::max<size_t>((size_t)(K - 1) * c->cap * 152, 16)); }
+
 // per image: upper bound of the T' rows its huge windows (P > 512) need, known from the scales alone
 void launch_image_large_rows(hesaff_ctx *c, const Lists &s, int B)
 {
@@ -1165,15 +1184,51 @@ struct GroupDevice : ScheduleDevice {
                          c->ct.consts, c->tables.view, s.pw);
    }
    void patch_done(int) { tm.end(t_patch); }
-   void descriptors(int g, int slot, sched::Stream ss)
+   void descriptors(int g, int slot, sched::Stream ss) { describe(g, slot, ss, s.pw.alive, c->geo.b_desc.as<uint8_t>()); }
+   void describe(int g, int slot, sched::Stream ss, const int32_t *alive, uint8_t *desc)
    {
       SiftIO so;
-      so.patches = c->b_patches2[slot].as<float>(); so.alive = s.pw.alive; so.meanvar = c->b_meanvar2.as<float>();
-      so.vec = nullptr; so.desc = c->geo.b_desc.as<uint8_t>(); so.h_lo = groups[g].lo; so.h_hi = groups[g].hi;
+      so.patches = c->b_patches2[slot].as<float>(); so.alive = alive; so.meanvar = c->b_meanvar2.as<float>();
+      so.vec = nullptr; so.desc = desc; so.h_lo = groups[g].lo; so.h_hi = groups[g].hi;
       const int ts = tm.begin(T_SIFT, 0, stream(ss));
       launch_sift(c, stream(ss), so, groups[g].hi - groups[g].lo, c->b_siftvo2.as<float2>(), c->descriptor);
       tm.end(ts);
    }
+};
+
+// ... and of the peaks order (hesaff_set_orientation_count K > 1): the multi form of the orientation kernel, and a rank's pass over its
+// own frames, window sides and flags - the bins and their counters are the one set, cleared for every pass
+struct PeaksDevice : GroupDevice {
+   OrientRanks mr;
+   PeaksDevice(hesaff_ctx *ctx, const Lists &s_, StageTimer &tm_, const std::vector<ImageGroup> &groups_, const PlaneTab &pt_, int H_, int W_, const OrientRanks &mr_)
+      : GroupDevice(ctx, s_, tm_, groups_, pt_, H_, W_), mr(mr_) {}
+   Lists rank_lists(int r) const
+   {
+      Lists sr = s;
+      sr.pw.A = mr.A_of(r); sr.pw.P0 = mr.P0_of(r); sr.pw.alive = mr.alive_of(r);
+      return sr;
+   }
+   void orientation(int g, int slot)
+   {
+      OrientIO oi;
+      memset(&oi, 0, sizeof oi);
+      oi.patches = c->b_patches2[slot].as<float>(); oi.h_lo = groups[g].lo; oi.h_hi = groups[g].hi;
+      oi.n_ptr = &s.counters->head.hess_total; oi.cap = s.hl.cap; oi.alive = s.pw.alive; oi.A = s.pw.A;
+      hipLaunchKernelGGL(k_orientation_peaks, dim3(orientation_grid(c, groups[g].hi - groups[g].lo)), dim3(64), 0, c->stream(), oi, c->tables.view, mr);
+   }
+   void rank_prepare(int g, int r)
+   {
+      hipStream_t st = c->stream();
+      t_patch = tm.begin(T_PATCH);
+      HIP_TRY(hipMemsetAsync(s.counters->bin_count, 0, CounterBlock::bins_bytes(), st));
+      hipLaunchKernelGGL(k_prepare_patch_second, dim3(1024), dim3(256), 0, st, s.hl, groups[g].lo, groups[g].hi, (const uint32_t *)&s.counters->head.hess_total, H, W,
+                         c->ct.consts, c->tables.view, rank_lists(r).pw);
+   }
+   void rank_patch_kernels(int g, int r, int slot, int n_side)
+   {
+      launch_patch_kernels(c, rank_lists(r), c->gray, c->b_patches2[slot].as<float>(), groups[g].lo, groups[g].large_rows, &pt, n_side);
+   }
+   void rank_descriptors(int g, int r, int slot, sched::Stream ss) { describe(g, slot, ss, mr.alive_of(r), mr.desc_of(r)); }
 };
 
 // Everything after the Hessian list of a batch is complete - by detection (run_batch) or from the caller's records (run_describe):
@@ -1189,6 +1244,7 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
    PlaneTab pt;
    memset(&pt, 0, sizeof pt);
    uint32_t n_hess_host = 0;   // Hessian keypoints of the batch
+   const int K = ori_count(c);
    for (size_t o = 0; o < c->oct.size(); o++)
       for (int l = 0; l < 3; l++) pt.L[o][l] = c->L[o * 3 + l];
    {
@@ -1200,20 +1256,36 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
       c->batch_max_p = (int)*hb.largest_window();   // largest huge window of the batch (0: none)
       // image groups [lo, hi) of keypoints; the T' rows of a group's huge windows fit the row buffer (form_groups, batch_plan.h)
       const GroupPlan gp = form_groups(hs, hb.large_rows(), B, c->trows_rows);
-      GroupDevice dev(c, s, tm, gp.groups, pt, H, W);
       if (gp.max_n) ensure_group_buffers(c, gp.max_n);
       const sched::ScheduleOptions so = {!c->no_overlap, c->sift_inside, with_affine, patch_side_streams(c, &pt)};
-      if (c->orientation == HESAFF_ORI_DOMINANT) sched::run_group_schedule_oriented(dev, (int)gp.groups.size(), so);
-      else sched::run_group_schedule(dev, (int)gp.groups.size(), so);
+      if (K > 1) {
+         ensure_rank_arrays(c, K);
+         PeaksDevice dev(c, s, tm, gp.groups, pt, H, W, rank_arrays(c, K));
+         sched::run_group_schedule_peaks(dev, (int)gp.groups.size(), K, so);
+      } else {
+         GroupDevice dev(c, s, tm, gp.groups, pt, H, W);
+         if (c->orientation == HESAFF_ORI_DOMINANT) sched::run_group_schedule_oriented(dev, (int)gp.groups.size(), so);
+         else sched::run_group_schedule(dev, (int)gp.groups.size(), so);
+      }
    }
    t = tm.begin(T_PACK);
    // final stable compaction (hesaff.cpp:87: keys.push_back in detection order): exclusive scan of the alive flags of the batch's
    // Hessian keypoints (alive[] is rewritten for h < n_hess each batch; the host knows n_hess since the round trip after detection -
    // the scan used to run over the whole capacity, 85 M flags for 31 M keypoints, behind a kernel that cleared the tail)
-   LoadFlagI32 lf; lf.p = s.pw.alive;
-   exclusive_scan(c, lf, (long long)n_hess_host, c->geo.b_rank.as<uint32_t>(), &cnt->head.desc_total);
-   hipLaunchKernelGGL(k_pack, dim3(HS_GRID_PACK), dim3(256), 0, st, s.hl, (const uint32_t *)&cnt->head.hess_total, s.pw, (const uint32_t *)c->geo.b_rank.p,
-                      (const uint8_t *)c->geo.b_desc.p, c->geo.b_out.as<KeyRec>());
+   if (K > 1) {
+      // an orientation count: a region owns as many adjacent rows as it has keys, so the scan runs over keys per region; the rows may
+      // outnumber the capacity b_out is sized for - k_pack_peaks clamps its writes, the host refuses the batch below
+      const OrientRanks mr = rank_arrays(c, K);
+      LoadKeyCount lk; lk.p = s.pw.alive; lk.ranks = mr.alive; lk.cap = mr.cap; lk.K = K;
+      exclusive_scan(c, lk, (long long)n_hess_host, c->geo.b_rank.as<uint32_t>(), &cnt->head.desc_total);
+      hipLaunchKernelGGL(k_pack_peaks, dim3(HS_GRID_PACK), dim3(256), 0, st, s.hl, (const uint32_t *)&cnt->head.hess_total, s.pw, mr, (const uint32_t *)c->geo.b_rank.p,
+                         (const uint8_t *)c->geo.b_desc.p, c->geo.b_out.as<KeyRec>(), c->cap);
+   } else {
+      LoadFlagI32 lf; lf.p = s.pw.alive;
+      exclusive_scan(c, lf, (long long)n_hess_host, c->geo.b_rank.as<uint32_t>(), &cnt->head.desc_total);
+      hipLaunchKernelGGL(k_pack, dim3(HS_GRID_PACK), dim3(256), 0, st, s.hl, (const uint32_t *)&cnt->head.hess_total, s.pw, (const uint32_t *)c->geo.b_rank.p,
+                         (const uint8_t *)c->geo.b_desc.p, c->geo.b_out.as<KeyRec>());
+   }
    const StartsBlock<int32_t> d_starts = starts_block(c->geo.b_starts.as<int32_t>(), B);
    hipLaunchKernelGGL(k_desc_starts, dim3((B + 1 + 63) / 64), dim3(64), 0, st, (const int32_t *)d_starts.hess(), B,
                       (const uint32_t *)c->geo.b_rank.p, (const uint32_t *)&cnt->head.hess_total, (const uint32_t *)&cnt->head.desc_total,
@@ -1235,6 +1307,8 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
    if (cn->overflow != 0 || cn->rec > c->cap)
       throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded; raise hesaff_params.max_kpts_per_mpx");
    if (cn->row_overflow != 0) throw HsError(HESAFF_ERR_NOMEM, "large-window row buffer exceeded (internal bound violated)");
+   if (K > 1 && cn->desc_total > c->cap)
+      throw HsError(HESAFF_ERR_CAPACITY, "the keys of the orientation count exceed the keypoint capacity; raise hesaff_params.max_kpts_per_mpx");
    const StartsBlock<const int32_t> h = starts_block((const int32_t *)h_starts, B);
    return {h.hess(), h.desc(), d_starts.desc()};
 }
@@ -1418,8 +1492,14 @@ void pack_regions(hesaff_ctx *c, uint32_t n_hess, int B, hesaff_region *d_region
    const Lists s = make_lists(c);
    RegionTab tab;
    for (int o = 0; o < HS_MAX_OCTAVES; o++) tab.pd[o] = c->ct.consts.pd0 * (float)(1 << o);   // pyramid.cpp:288, as run_detection hands it on
-   hipLaunchKernelGGL(k_pack_regions, dim3(std::min<uint32_t>((n_hess + 255) / 256, 4096u)), dim3(256), 0, c->stream(), s.hl, n_hess, s.ao, s.pw,
-                      (const uint32_t *)c->geo.b_rank.p, (const int32_t *)starts_block(c->geo.b_starts.as<int32_t>(), B).desc(), tab, (uint4 *)d_regions);
+   const dim3 grid(std::min<uint32_t>((n_hess + 255) / 256, 4096u));
+   const int32_t *desc_starts = starts_block(c->geo.b_starts.as<int32_t>(), B).desc();
+   if (ori_count(c) > 1)
+      hipLaunchKernelGGL(k_pack_regions_peaks, grid, dim3(256), 0, c->stream(), s.hl, n_hess, s.ao, s.pw, rank_arrays(c, ori_count(c)),
+                         (const uint32_t *)c->geo.b_rank.p, desc_starts, tab, (uint4 *)d_regions);
+   else
+      hipLaunchKernelGGL(k_pack_regions, grid, dim3(256), 0, c->stream(), s.hl, n_hess, s.ao, s.pw, (const uint32_t *)c->geo.b_rank.p, desc_starts, tab,
+                         (uint4 *)d_regions);
 }
 
 } // namespace

@@ -48,6 +48,8 @@ extern "C" {
  *    And for hesaff_set_orientation / hesaff_get_orientation / hesaff_stage_orientation (dominant-orientation mode): symbols only, version 8.
  *    And for the stage entry point hesaff_stage_detect_planes.
  *    And for hesaff_set_descriptor / hesaff_get_descriptor / hesaff_stage_sift_mode (RootSIFT descriptor mode): symbols only, version 8.
+ *    And for hesaff_set_orientation_count / hesaff_get_orientation_count / hesaff_stage_orientation_peaks (secondary orientation peaks):
+ *    symbols only, version 8.  With a count above 1, hesaff_region.reserved carries the number of a region's keys.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -440,8 +442,7 @@ int hesaff_get_keypoint_grid(const hesaff_ctx *ctx, int *rows, int *cols);
  * What follows:  a keypoint is described iff normalizeAffine accepts it in BOTH runs, otherwise its hesaff_region has outcome 1 and no
  * key.  hesaff_region is unchanged: U stays un-rectified and un-turned, x, y, s, response, type, iters as in mode 0.  The ellipse and
  * the text row are unchanged up to rounding (A' * A'^T = A * A^T); the file formats carry no orientation; theta is recoverable from
- * a key as atan2(-a12', a11'), because the rectified a12 is 0 and a11 > 0.  One orientation per keypoint: Lowe's secondary peaks,
- * which would make several keys of one region, are not produced.
+ * a key as atan2(-a12', a11'), because the rectified a12 is 0 and a11 > 0.  One orientation per keypoint, unless an orientation count is set (the next block).
  * The mode is context state, like the keypoint limit.  HESAFF_ORI_UP, the default, is today's behaviour bit for bit: nothing is
  * launched, allocated or copied for the mode.  HESAFF_ORI_DOMINANT applies to every detecting entry point (hesaff_detect_batch*,
  * hesaff_detect_regions*, hesaff_detect_batch_device*), to hesaff_process_files and to hesaff_describe_regions* in both `from` modes
@@ -454,6 +455,37 @@ int hesaff_get_keypoint_grid(const hesaff_ctx *ctx, int *rows, int *cols);
 #define HESAFF_ORI_DOMINANT 1
 int hesaff_set_orientation(hesaff_ctx *ctx, int mode);
 int hesaff_get_orientation(const hesaff_ctx *ctx, int *mode);
+
+/* ---- secondary orientation peaks: up to four keys per region ----
+ * Lowe's detector, OpenCV and VLFeat emit one descriptor per histogram peak within 80 % of the maximum; on a patch with two comparable
+ * gradient directions the highest peak flips between views, and a matcher that holds one of the two descriptors loses the region.  The
+ * context has an ORIENTATION COUNT K in 1..4, default 1, read only in HESAFF_ORI_DOMINANT; in HESAFF_ORI_UP it is inert, as a keypoint
+ * grid is with limit 0.  The arithmetic conventions are those of the block above.  For one keypoint, with h[0..35] after step 4 and m
+ * from step 5:
+ *  - flat histogram: h[m] == 0: one orientation, theta = 0, A' = A bit for bit, as with K = 1;
+ *  - candidates: otherwise every bin b != m with h[b] > h[b-1], h[b] > h[b+1] and h[b] >= 0.8f * h[m] - the neighbour comparisons strict
+ *    and circular, the product one binary32 multiplication, a comparison with a NaN false - ordered by h[b] descending, equal heights
+ *    lower bin first;
+ *  - ranks: rank 0 is bin m, rank j >= 1 the j-th candidate; n_ori = min(K, 1 + number of candidates);
+ *  - angle: theta_j is step 5's formula with (l, q, r) taken around bin b_j, its `den == 0 -> off = 0` clause included;
+ *  - frame: A'_j = A * R(theta_j) by step 6, each from the same up-is-up A - the frames are never cumulative;
+ *  - keys: for every rank j < n_ori, normalizeAffine(image, x, y, s, A'_j) runs; if it accepts, that patch goes to the descriptor (SIFT
+ *    or RootSIFT, as the context says) and makes one hesaff_keypoint that stores A'_j.
+ * A region has keys iff the first run of normalizeAffine (on A) accepted it, and its keys are those ranks whose own run accepted: rank 0
+ * may be rejected while a later rank is described.
+ * Output: the keys of one region are adjacent, in ascending rank, and regions stay in the reference's order.  In a hesaff_region, outcome
+ * is 2 iff the region has at least one key, `key` is the row of its first key and `reserved` the number of its keys (-1 and 0 without a
+ * key); every other field is unchanged.  count_desc MAY EXCEED count_hessian: a caller sizes for up to K keys per region.  Text and
+ * sidecar rows follow from the keys; the formats carry no rank.  The keys of a chunk must fit the keypoint capacity
+ * (hesaff_params.max_kpts_per_mpx) the result blocks are sized for: otherwise the call returns HESAFF_ERR_CAPACITY and the context stays
+ * usable.
+ * K = 1 is the dominant-orientation mode as it stands - every byte, `reserved` = 0 included, every kernel launched, nothing allocated.
+ * The first call with K > 1 allocates 152 bytes per keypoint of capacity and rank above 0 (HESAFF_ERR_NOMEM when the device cannot hold
+ * them), and a batch runs K patch passes and K descriptor chains per image group besides pass one; a pass with no live keypoint costs
+ * its launches.  Scope: that of the orientation mode.
+ * HESAFF_ERR_ARG, with nothing changed: ctx NULL, k outside 1..4 (hesaff_get_orientation_count: ctx or k NULL). */
+int hesaff_set_orientation_count(hesaff_ctx *ctx, int k);
+int hesaff_get_orientation_count(const hesaff_ctx *ctx, int *k);
 
 /* ---- descriptor mode: SIFT or RootSIFT bytes ----
  * Replaces nothing: the reference has the L2-normalised, clipped, 512-scaled SIFT byte vector only (siftdesc.cpp:98-113).  RootSIFT
@@ -680,6 +712,10 @@ int hesaff_stage_sift_mode(hesaff_ctx *ctx, int n, const float *patches, const i
 /* steps 1-6 of hesaff_set_orientation's definition (the production kernel, k_orientation) on n caller-supplied 41 x 41 patches:
  * theta[n]; optionally (NULL: not wanted) hist[n][36], the histogram after smoothing, and cs[n][2] = (cos theta, sin theta) */
 int hesaff_stage_orientation(hesaff_ctx *ctx, int n, const float *patches, float *theta, float *hist, float *cs);
+/* the peak rule of hesaff_set_orientation_count (the production kernel's multi form, k_orientation_peaks) on n caller-supplied 41 x 41
+ * patches with orientation count k in 1..4: n_ori[n], and for every rank j the bin bins[n][4] and the angle theta[n][4]; beyond n_ori the
+ * bin is -1 and the angle 0.  A flat histogram: n_ori 1, bin m (0), angle 0. */
+int hesaff_stage_orientation_peaks(hesaff_ctx *ctx, int n, const float *patches, int k, int32_t *n_ori, int32_t *bins, float *theta);
 /* exportKeypoints hesaff.cpp:107-130 on the device for n records in host memory (what hesaff_process_files runs per chunk):
  * format = HESAFF_OUT_TEXT: the bytes of the .hesaff.sift file, == hesaff_format_sift; HESAFF_OUT_BIN: the bytes of the sidecar,
  * == hesaff_write_bin's file.  *out is malloc'ed (hesaff_free). */

@@ -33,6 +33,14 @@ from ._binding import (  # noqa: F401
     write_bin,
     read_bin,
     BIN_ROW_DTYPE,
+    OUT_TEXT,
+    OUT_BIN,
+    OUT_WORDS,
+    WORDS_ROW_DTYPE,
+    read_vocabulary,
+    write_vocabulary,
+    read_words,
+    write_words,
     read_image,
     read_pnm,
     read_jpeg_coefficients,

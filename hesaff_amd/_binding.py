@@ -240,6 +240,17 @@ def load_library():
         L.hesaff_set_descriptor.argtypes = [vp, C.c_int]
         L.hesaff_get_descriptor.argtypes = [vp, C.POINTER(C.c_int)]
         L.hesaff_stage_sift_mode.argtypes = [vp, C.c_int, _f32p, C.c_void_p, C.c_int, _u8p]
+    if hasattr(L, "hesaff_set_vocabulary"):   # (likewise)
+        L.hesaff_set_vocabulary.argtypes = [vp, C.c_int, vp]
+        L.hesaff_get_vocabulary_size.argtypes = [vp, C.POINTER(C.c_int)]
+        L.hesaff_get_words.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_int)]
+        L.hesaff_get_words_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
+        L.hesaff_assign_words_device.argtypes = [vp, C.c_int64, vp, C.c_int64, C.c_int64, vp]
+        L.hesaff_stage_assign_words.argtypes = [vp, C.c_int, vp, vp]
+        L.hesaff_get_assign_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.hesaff_write_words.argtypes = [C.c_char_p, vp, vp, C.c_int, C.c_float, C.c_int]
+        L.hesaff_read_vocabulary.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int)]
+        L.hesaff_write_vocabulary.argtypes = [C.c_char_p, vp, C.c_int]
     L.hesaff_stage_math_sift_general.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math_sift.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]
@@ -281,7 +292,15 @@ ABI_SYMBOLS = [
     "hesaff_set_keypoint_grid", "hesaff_get_keypoint_grid", "hesaff_stage_detect_planes",
     "hesaff_set_descriptor", "hesaff_get_descriptor", "hesaff_stage_sift_mode",
     "hesaff_set_orientation_count", "hesaff_get_orientation_count", "hesaff_stage_orientation_peaks",
+    "hesaff_set_vocabulary", "hesaff_get_vocabulary_size", "hesaff_get_words", "hesaff_get_words_device",
+    "hesaff_assign_words_device", "hesaff_stage_assign_words", "hesaff_get_assign_ms", "hesaff_write_words",
+    "hesaff_read_vocabulary", "hesaff_write_vocabulary",
 ]
+
+# hesaff_set_output_format's bits
+OUT_TEXT = 1
+OUT_BIN = 2
+OUT_WORDS = 4   # <image>.hesaff.words (needs a vocabulary)
 
 # hesaff_set_descriptor's modes
 DESC_SIFT = 0       # the reference's SIFT bytes (default)
@@ -434,6 +453,66 @@ def read_bin(path):
     if len(rows) != n:
         raise HesaffError(-4, "%s is truncated" % path)
     return rows
+
+
+WORDS_ROW_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("a", "<f4"), ("b", "<f4"), ("c", "<f4"), ("word", "<u4")])
+
+
+def _vocabulary_array(words):
+    """uint8 [K, 128], C-contiguous, 1 <= K <= 2^20 - anything else is a ValueError"""
+    if not isinstance(words, np.ndarray) or words.dtype != np.uint8 or words.ndim != 2 or words.shape[1] != 128:
+        raise ValueError("a vocabulary is a uint8 array of shape [K, 128]")
+    if not words.flags["C_CONTIGUOUS"]:
+        raise ValueError("a vocabulary must be C-contiguous")
+    if not 1 <= words.shape[0] <= (1 << 20):
+        raise ValueError("a vocabulary has 1 .. 2^20 rows, not %d" % words.shape[0])
+    return words
+
+
+def write_vocabulary(path, words):
+    """hesaff_write_vocabulary: uint8 [K, 128] -> a vocabulary file ("HESAFFV1")."""
+    words = _vocabulary_array(words)
+    rc = load_library().hesaff_write_vocabulary(os.fsencode(path), words.ctypes.data, words.shape[0])
+    if rc != 0:
+        raise HesaffError(rc, "hesaff_write_vocabulary(%s)" % path)
+
+
+def read_vocabulary(path):
+    """hesaff_read_vocabulary: a vocabulary file -> uint8 [K, 128]."""
+    L = load_library()
+    data = C.c_void_p(); k = C.c_int()
+    rc = L.hesaff_read_vocabulary(os.fsencode(path), C.byref(data), C.byref(k))
+    if rc != 0:
+        raise HesaffError(rc, "hesaff_read_vocabulary(%s): not a readable, whole vocabulary file" % path)
+    try:
+        arr = np.frombuffer(C.string_at(data.value, k.value * 128), dtype=np.uint8).copy()
+    finally:
+        L.hesaff_free(data)
+    return arr.reshape(k.value, 128)
+
+
+def write_words(path, keys, words, mr_size, vocabulary_size):
+    """hesaff_write_words: keys[KEYPOINT_DTYPE] and their int32 [n, 2] (word, dist2) rows -> a words file ("HESAFFW1")."""
+    keys = np.ascontiguousarray(keys, dtype=KEYPOINT_DTYPE)
+    words = np.ascontiguousarray(words, dtype=np.int32).reshape(-1, 2)
+    if len(words) != len(keys):
+        raise ValueError("one (word, dist2) row per key")
+    rc = load_library().hesaff_write_words(os.fsencode(path), keys.ctypes.data, words.ctypes.data, len(keys), mr_size, int(vocabulary_size))
+    if rc != 0:
+        raise HesaffError(rc, "hesaff_write_words(%s)" % path)
+
+
+def read_words(path):
+    """.hesaff.words (hesaff_write_words) -> (vocabulary_size, structured array of WORDS_ROW_DTYPE)."""
+    with open(path, "rb") as f:
+        head = f.read(16)
+        if len(head) != 16 or head[:8] != b"HESAFFW1":
+            raise HesaffError(-4, "%s is not a .hesaff.words file" % path)
+        vocabulary_size, n = (int(v) for v in np.frombuffer(head[8:], "<u4"))
+        body = f.read()
+    if len(body) != n * WORDS_ROW_DTYPE.itemsize:
+        raise HesaffError(-4, "%s is truncated" % path)
+    return vocabulary_size, np.frombuffer(body, dtype=WORDS_ROW_DTYPE).copy()
 
 
 def read_image(path):
@@ -719,7 +798,8 @@ class HesaffContext:
         self._check(self.L.hesaff_detect_batch_cb(self.h, n, ptrs, ws, hs, st, chs, self._chunk_sink(sink), None))
 
     def set_output_format(self, fmt):
-        """1 = text (.hesaff.sift, default), 2 = binary sidecar (.hesaff.bin), 3 = both."""
+        """OUT_TEXT = 1 (.hesaff.sift, default), OUT_BIN = 2 (binary sidecar .hesaff.bin), OUT_WORDS = 4 (.hesaff.words, with a
+        vocabulary set), or-ed as wanted."""
         self._check(self.L.hesaff_set_output_format(self.h, fmt))
 
     def set_resume(self, on=True, strict=False):
@@ -827,6 +907,64 @@ class HesaffContext:
     @descriptor.setter
     def descriptor(self, mode):
         self.set_descriptor(mode)
+
+    # ---- visual words (hesaff_set_vocabulary, include/hesaff_amd.h) ----
+    def set_vocabulary(self, words):
+        """hesaff_set_vocabulary: words is a C-contiguous uint8 [K, 128] array (copied to the device) or None (no vocabulary, the
+        default).  With one set, every call that produces keys also assigns each key the lowest row of least squared distance to
+        its descriptor bytes; words(image) hands them out."""
+        if words is None:
+            self._check(self.L.hesaff_set_vocabulary(self.h, 0, None))
+            return
+        words = _vocabulary_array(words)
+        self._check(self.L.hesaff_set_vocabulary(self.h, words.shape[0], words.ctypes.data))
+
+    @property
+    def vocabulary_size(self):
+        k = C.c_int()
+        self._check(self.L.hesaff_get_vocabulary_size(self.h, C.byref(k)))
+        return k.value
+
+    def words(self, image):
+        """hesaff_get_words: int32 [count, 2] = (word, dist2), row for row the keys of image `image` of the last host call (a copy)."""
+        p = C.c_void_p(); n = C.c_int()
+        if self.L.hesaff_get_words(self.h, int(image), C.byref(p), C.byref(n)) != 0:
+            raise HesaffError(-1, "hesaff_get_words(%d): no vocabulary is set, or no such image in the last host call" % image)
+        if n.value == 0:
+            return np.zeros((0, 2), np.int32)
+        return np.frombuffer((C.c_char * (n.value * 8)).from_address(p.value), dtype=np.int32).copy().reshape(n.value, 2)
+
+    def assign_words(self, desc):
+        """hesaff_stage_assign_words: desc uint8 [n, 128] -> int32 [n, 2] = (word, dist2) against the context's vocabulary."""
+        desc = np.ascontiguousarray(desc, dtype=np.uint8)
+        if desc.ndim != 2 or desc.shape[1] != 128:
+            raise ValueError("descriptors are a uint8 array of shape [n, 128]")
+        out = np.zeros((desc.shape[0], 2), np.int32)
+        rc = self.L.hesaff_stage_assign_words(self.h, desc.shape[0], desc.ctypes.data if desc.shape[0] else None,
+                                              out.ctypes.data if desc.shape[0] else None)
+        if rc != 0 and desc.shape[0] == 0:
+            raise HesaffError(rc, "hesaff_stage_assign_words: no vocabulary is set")
+        self._check(rc)
+        return out
+
+    def assign_words_device(self, ptr, n, stride, offset, out_ptr):
+        """hesaff_assign_words_device: n descriptors in device memory, descriptor i at ptr + i * stride + offset (164 / 36: a key array;
+        128 / 0: a packed tensor) -> n x 2 int32 at out_ptr (raw device pointers)."""
+        self._check(self.L.hesaff_assign_words_device(self.h, int(n), C.c_void_p(ptr), int(stride), int(offset), C.c_void_p(out_ptr)))
+
+    def words_device(self):
+        """hesaff_get_words_device: (device pointer, rows) of the int32 [total, 2] array parallel to the keys of the last device-resident call."""
+        p = C.c_void_p(); tot = C.c_int64()
+        if self.L.hesaff_get_words_device(self.h, C.byref(p), C.byref(tot)) != 0:
+            raise HesaffError(-1, "hesaff_get_words_device: no vocabulary is set, or the last call was not device-resident")
+        return p.value, tot.value
+
+    @property
+    def assign_ms(self):
+        """HIP-event time of the last batch's word assignment (profiling level >= 1), in ms"""
+        ms = C.c_float()
+        self._check(self.L.hesaff_get_assign_ms(self.h, C.byref(ms)))
+        return ms.value
 
     def process_files(self, paths, out_paths=None, decode_threads=0, write_threads=0):
         """hesaff_process_files: image files -> <name>.hesaff.sift through the decode / device / write pipeline.

@@ -93,8 +93,11 @@ void detect_device(hesaff_ctx *c, int n, const SrcImages &src, int height, int w
    const SelMasks mk = device_masks(am, n, height, width);
    plan(c, c->par.max_batch, height, width);
    check_source();
+   c->word_spans.clear();
+   c->words_device_total = -1;
    const BatchResult r = run_batch(c, src, n, height, width, mk);
    const int32_t *hs = r.hessian_starts, *ds = r.desc_starts;
+   if (c->vocab.k) { finish_stream(c); c->words_device_total = ds[n]; }   // the words of the batch are in b_words when the call returns
    for (int b = 0; b < n; b++) {
       if (count_hessian) count_hessian[b] = hs[b + 1] - hs[b];
       if (count_desc) count_desc[b] = ds[b + 1] - ds[b];
@@ -508,6 +511,7 @@ struct ChunkDevice {
       size_t at = 0;
       auto place = [&at](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~(size_t)255; return o; };
       if (wants & WANT_KEYS) s.keys_at = place(n_rows * sizeof(hesaff_keypoint));
+      if (wants & WANT_WORDS) s.words_at = place(n_rows * 8);
       if (wants & WANT_REGIONS) s.regions_at = place(s.n_hess * sizeof(hesaff_region));
       if (times_export(s)) HIP_TRY(hipEventRecord(sl.ev_exp[0], c->stream()));
       if (wants & WANT_TEXT) {   // row lengths and offsets first: the host needs the byte count (a short wait on the main stream)
@@ -557,6 +561,8 @@ struct ChunkDevice {
          char *stg = (char *)sl.b_outstage.p;
          if ((wants & WANT_KEYS) && n_rows > 0)
             HIP_TRY(hipMemcpyAsync(stg + s.keys_at, c->geo.b_out.p, n_rows * sizeof(hesaff_keypoint), hipMemcpyDeviceToDevice, c->stream()));
+         if ((wants & WANT_WORDS) && n_rows > 0)   // (b_words: written by k_assign_words behind the pack stage, on this stream)
+            HIP_TRY(hipMemcpyAsync(stg + s.words_at, c->b_words.p, n_rows * 8, hipMemcpyDeviceToDevice, c->stream()));
          if (wants & WANT_REGIONS) pack_regions(c, (uint32_t)s.n_hess, B, (hesaff_region *)(stg + s.regions_at));
          if (times_export(s)) HIP_TRY(hipEventRecord(sl.ev_exp[2], c->stream()));
          if (wants & WANT_TEXT) export_text_write(c, d_keys, (uint32_t)n_rows, stg + s.text_at);
@@ -694,6 +700,12 @@ void detect_images(hesaff_ctx *c, int n, const void *images, bool f32, const int
    const MaskInput mi = host_masks(am, n, widths);
    ArrayIO io(&c->ring, c->par.max_batch, n, f32 ? planes.data() : (const uint8_t *const *)images, widths, heights, strides, channels, f32,
               di.regions, di.counts, di.from, mi);
+   c->words_device_total = -1;
+   c->word_spans.clear();
+   if (c->vocab.k) {   // the words travel beside the keys (WANT_WORDS); hesaff_get_words finds them by the caller's image index
+      c->word_spans.assign((size_t)n, WordSpan());
+      io.word_spans = &c->word_spans;
+   }
    set_consumer(io);
    run_chunks(c, io, ring);
    if (io.sink_rc.load() != 0) throw HsError(HESAFF_ERR_IO, "the result sink reported an error");
@@ -829,7 +841,7 @@ int hesaff_detect_batch_device_f32(hesaff_ctx *c, int n, const void *d_planes, i
 
 int hesaff_set_output_format(hesaff_ctx *c, int format)
 {
-   if (!c || (format & ~(HESAFF_OUT_TEXT | HESAFF_OUT_BIN)) != 0 || format == 0) return HESAFF_ERR_ARG;
+   if (!c || (format & ~(HESAFF_OUT_TEXT | HESAFF_OUT_BIN | HESAFF_OUT_WORDS)) != 0 || format == 0) return HESAFF_ERR_ARG;
    c->out_format = format;
    return HESAFF_OK;
 }
@@ -964,6 +976,9 @@ int hesaff_process_files(hesaff_ctx *c, int n, const char *const *paths, const c
    if (!c || n < 0 || (n > 0 && (!paths || !status))) return HESAFF_ERR_ARG;
    HS_API_BEGIN
    refuse_masks(am, "hesaff_process_files takes none: no masks travel with a file list");
+   if ((c->out_format & HESAFF_OUT_WORDS) && c->vocab.k == 0) throw HsError(HESAFF_ERR_ARG, "HESAFF_OUT_WORDS is selected but no vocabulary is set (hesaff_set_vocabulary)");
+   c->words_device_total = -1;
+   c->word_spans.clear();
    for (int i = 0; i < n; i++) { status[i].rc = HESAFF_ERR_IO; status[i].stage = HESAFF_FILE_PENDING; status[i].count_hessian = 0; status[i].count_desc = 0; }
    hesaff_host_plan hp;
    (void)hesaff_host_plan_for(1, &hp);   // "0 = auto": this context has the host to itself (callers that share it pass the counts of their own plan)
@@ -979,6 +994,7 @@ int hesaff_process_files(hesaff_ctx *c, int n, const char *const *paths, const c
    // the pool's threads step down (nice 10) only where they would otherwise crowd out the caller's thread: a CPU-starved plan
    const bool nice_pool = c->pool_priority == 1 || (c->pool_priority < 0 && hesaff_host_threads() <= dt + wt + 1);
    FileIO io(&c->ring, c->par.max_batch, c->par.mrSize, c->out_format, n, paths, out_paths, status, dt, wt, true, c->resume, device_jpeg, pin, nice_pool);
+   io.vocabulary_size = c->vocab.k;
    c->stage_threads = hesaff_stage_threads_for_pool(dt + wt);
    try {
       run_chunks(c, io, 3);
@@ -1546,6 +1562,130 @@ int hesaff_stage_math_sift_general(hesaff_ctx *c, int n, const float *gy, const 
    for (int q = 0; q < 3; q++) HIP_TRY(hipMemcpyAsync(outs[q], d + (2 + q) * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream()));
    finish_stream(c);
    HS_API_END(c)
+}
+
+// ---------------------------------- visual words (kernels_words.h) ----------------------------------
+} // extern "C"
+namespace {
+// The vocabulary as k_assign_words reads it: XORed with 0x80, padded to whole tiles of HS_WORD_TILE rows, in lane order - tile t, step
+// s, lane l: bytes [32 s + 16 (l >> 5), + 16) of row t * 32 + (l & 31) at ((t * 4 + s) * 64 + l) * 16 - and |w'|^2 per row (pad rows:
+// all zero, HS_WORD_PAD_NORM).
+void pack_vocabulary(const uint8_t *words, int k, std::vector<uint8_t> &tiles, std::vector<int32_t> &norms)
+{
+   const size_t n_tiles = ((size_t)k + HS_WORD_TILE - 1) / HS_WORD_TILE;
+   tiles.assign(n_tiles * HS_WORD_TILE_BYTES, 0);
+   norms.assign(n_tiles * HS_WORD_TILE, HS_WORD_PAD_NORM);
+   for (size_t row = 0; row < (size_t)k; row++) {
+      const uint8_t *w = words + row * 128;
+      const size_t t = row / HS_WORD_TILE, r = row % HS_WORD_TILE;
+      int32_t sq = 0;
+      for (int j = 0; j < 128; j++) {
+         const int v = (int)w[j] - 128;
+         sq += v * v;
+         const size_t s = (size_t)j / 32, h = ((size_t)j % 32) / 16, lane = r + 32 * h;
+         tiles[((t * 4 + s) * 64 + lane) * 16 + (size_t)j % 16] = (uint8_t)(w[j] ^ 0x80u);
+      }
+      norms[row] = sq;
+   }
+}
+
+void need_vocabulary(const hesaff_ctx *c)
+{
+   if (c->vocab.k == 0) throw HsError(HESAFF_ERR_ARG, "no vocabulary is set (hesaff_set_vocabulary)");
+}
+} // namespace
+extern "C" {
+
+int hesaff_set_vocabulary(hesaff_ctx *c, int k, const uint8_t *words)
+{
+   if (!c || k < 0 || k > (1 << 20) || (k > 0 && !words)) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   bind_device(c);
+   hesaff_ctx::Vocabulary v;
+   if (k > 0) {
+      std::vector<uint8_t> tiles;
+      std::vector<int32_t> norms;
+      pack_vocabulary(words, k, tiles, norms);
+      v.tiles.ensure(tiles.size());   // (throws HESAFF_ERR_NOMEM with the context's vocabulary untouched)
+      v.norms.ensure(norms.size() * 4);
+      HIP_TRY(hipMemcpy(v.tiles.p, tiles.data(), tiles.size(), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(v.norms.p, norms.data(), norms.size() * 4, hipMemcpyHostToDevice));
+      v.k = k;
+      v.n_tiles = (int)(norms.size() / HS_WORD_TILE);
+   }
+   HIP_TRY(hipStreamSynchronize(c->stream()));   // nothing still reads the vocabulary that goes
+   c->vocab = std::move(v);
+   if (k == 0) c->b_words.release();
+   c->word_spans.clear();
+   c->words_device_total = -1;
+   c->assign_timed = false;
+   HS_API_END(c)
+}
+
+int hesaff_get_vocabulary_size(const hesaff_ctx *c, int *k)
+{
+   if (!c || !k) return HESAFF_ERR_ARG;
+   *k = c->vocab.k;
+   return HESAFF_OK;
+}
+
+int hesaff_get_words(const hesaff_ctx *c, int image, const int32_t **words, int *count)
+{
+   if (!c || !words || !count || c->vocab.k == 0) return HESAFF_ERR_ARG;
+   if (image < 0 || (size_t)image >= c->word_spans.size() || c->word_spans[(size_t)image].n < 0) return HESAFF_ERR_ARG;
+   *words = c->word_spans[(size_t)image].p;
+   *count = c->word_spans[(size_t)image].n;
+   return HESAFF_OK;
+}
+
+int hesaff_get_words_device(const hesaff_ctx *c, const void **d_words, int64_t *total)
+{
+   if (!c || !d_words || !total || c->vocab.k == 0 || c->words_device_total < 0) return HESAFF_ERR_ARG;
+   *d_words = c->words_device_total > 0 ? c->b_words.p : nullptr;
+   *total = c->words_device_total;
+   return HESAFF_OK;
+}
+
+int hesaff_assign_words_device(hesaff_ctx *c, int64_t n, const void *d_desc, int64_t stride, int64_t offset, void *d_words_out)
+{
+   if (!c || n < 0 || (n > 0 && (!d_desc || !d_words_out))) return HESAFF_ERR_ARG;
+   if (stride < 128 || offset < 0 || offset + 128 > stride || stride % 4 != 0 || offset % 4 != 0) return HESAFF_ERR_ARG;
+   if ((uintptr_t)d_desc % 4 != 0 || (uintptr_t)d_words_out % 4 != 0 || n > ((int64_t)1 << 38)) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   need_vocabulary(c);
+   bind_device(c);
+   launch_assign_words(c, d_desc, (long long)n, (long long)stride, (long long)offset, d_words_out);
+   finish_stream(c);
+   HS_API_END(c)
+}
+
+int hesaff_stage_assign_words(hesaff_ctx *c, int n, const uint8_t *desc, int32_t *words_out)
+{
+   if (!c || n < 0 || (n > 0 && (!desc || !words_out))) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   need_vocabulary(c);
+   bind_device(c);
+   if (n == 0) return HESAFF_OK;
+   const size_t N = (size_t)n, off_out = (N * 128 + 255) & ~(size_t)255;
+   c->b_stage.ensure(off_out + N * 8);
+   char *base = (char *)c->b_stage.p;
+   HIP_TRY(hipMemcpyAsync(base, desc, N * 128, hipMemcpyHostToDevice, c->stream()));
+   launch_assign_words(c, base, n, 128, 0, base + off_out);
+   HIP_TRY(hipMemcpyAsync(words_out, base + off_out, N * 8, hipMemcpyDeviceToHost, c->stream()));
+   finish_stream(c);
+   HS_API_END(c)
+}
+
+int hesaff_get_assign_ms(const hesaff_ctx *c, float *ms)
+{
+   if (!c || !ms) return HESAFF_ERR_ARG;
+   *ms = 0.0f;
+   if (!c->assign_timed) return HESAFF_OK;
+   if (hipEventSynchronize(c->ev_assign[1]) != hipSuccess || hipEventElapsedTime(ms, c->ev_assign[0], c->ev_assign[1]) != hipSuccess) {
+      (void)hipGetLastError();
+      *ms = 0.0f;
+   }
+   return HESAFF_OK;
 }
 
 // ---------------------------------- host tables ----------------------------------

@@ -136,8 +136,12 @@ inline bool same_jpeg_layout(const hesaff_jpeg_layout &a, const hesaff_jpeg_layo
 enum { WANT_KEYS = 1,    // the hesaff_keypoint records (hesaff.cpp:41-48)
        WANT_TEXT = 2,    // the rows of the .hesaff.sift files, formatted on the device (kernels_export.h; hesaff.cpp:124-128)
        WANT_BIN = 4,     // the 148-byte rows of the binary sidecar
-       WANT_REGIONS = 8  // a hesaff_region per Hessian keypoint (hesaff_detect_regions; pyramid.h:43-47, affine.h:48-58)
+       WANT_REGIONS = 8, // a hesaff_region per Hessian keypoint (hesaff_detect_regions; pyramid.h:43-47, affine.h:48-58)
+       WANT_WORDS = 16   // two int32 (word, dist2) per record (hesaff_set_vocabulary), row for row the records
 };
+
+// hesaff_get_words: the rows of one image of the last host call inside the call's result blocks (n = -1: not, or no longer, there)
+struct WordSpan { const int32_t *p = nullptr; int n = -1; };
 
 struct ChunkDone {
    const HostChunk *chunk;
@@ -149,6 +153,7 @@ struct ChunkDone {
    const unsigned long long *text_off = nullptr;   //            image b owns text[text_off[b] .. text_off[b + 1])
    const char *bin = nullptr;                      // WANT_BIN: image b's rows start at bin + key_off[b] * 148
    const hesaff_region *regions = nullptr;         // WANT_REGIONS: image b's records start at its Hessian offset, the sum of count_hessian[0 .. b)
+   const int32_t *words = nullptr;                 // WANT_WORDS: image b's rows start at words + key_off[b] * 2
 };
 
 struct ChunkIO {
@@ -176,8 +181,8 @@ struct ChunkState {
    std::vector<unsigned long long> toff;   // WANT_TEXT: byte offset of every image's rows
    int total = 0;                          // records of the chunk
    size_t n_hess = 0;                      // Hessian keypoints of the chunk
-   // layout of the chunk's result block: [records][regions][text rows][sidecar rows], what the consumer wants of them, `bytes` in all
-   size_t keys_at = 0, regions_at = 0, text_at = 0, bin_at = 0, bytes = 0;
+   // layout of the chunk's result block: [records][words][regions][text rows][sidecar rows], what the consumer wants of them, `bytes` in all
+   size_t keys_at = 0, words_at = 0, regions_at = 0, text_at = 0, bin_at = 0, bytes = 0;
    int block = -1;                         // the result block the loop chose: one of the ring, or `no` without a ring
    uint32_t n_rec = 0;                     // hesaff_describe_regions: records of the chunk
    bool copied = false;                    // a copy out was enqueued
@@ -224,6 +229,7 @@ void run_chunk_loop(ChunkIO &io, BlockRing &ring, int ring_blocks, Device &dev)
       if (wants & WANT_TEXT) { d.text = blk + s.text_at; d.text_off = s.toff.data(); }
       if (wants & WANT_BIN) d.bin = blk + s.bin_at;
       if (wants & WANT_REGIONS) d.regions = (const hesaff_region *)(blk + s.regions_at);
+      if (wants & WANT_WORDS) d.words = (const int32_t *)(blk + s.words_at);
       io.done(d);
    };
 
@@ -300,6 +306,7 @@ struct ArrayIO : ChunkIO {
    hesaff_chunk_sink sink = nullptr;             // hesaff_detect_batch_cb
    void *user = nullptr;
    hesaff_region_result *region_results = nullptr;   // hesaff_detect_regions: filled in place (instead of results)
+   std::vector<WordSpan> *word_spans = nullptr;      // a vocabulary is set: every image's word rows are noted here, by the caller's index
    std::atomic<int> sink_rc{0};                 // written by done() on the caller's thread, read by next() on the staging thread
    ArrayIO(BlockRing *ring_, int max_batch, int n, const uint8_t *const *images, const int *widths, const int *heights, const int *strides,
            const int *channels, bool f32 = false, const hesaff_region *const *regions = nullptr, const int *counts = nullptr, int from = 0,
@@ -361,10 +368,20 @@ struct ArrayIO : ChunkIO {
       for (size_t i = pos; i < chunks.size() && chunks[i].W == q.W && chunks[i].H == q.H && chunks[i].ch == q.ch && chunks[i].f32 == q.f32; i++) m = std::max(m, chunks[i].data.size());
       return (int)m;
    }
-   int wants() const override { return region_results ? (WANT_KEYS | WANT_REGIONS) : WANT_KEYS; }
+   int wants() const override { return WANT_KEYS | (region_results ? WANT_REGIONS : 0) | (word_spans ? WANT_WORDS : 0); }
+   void note_words(const ChunkDone &d, bool valid)
+   {
+      if (!word_spans) return;
+      for (size_t b = 0; b < d.chunk->index.size(); b++) {
+         WordSpan &w = (*word_spans)[(size_t)d.chunk->index[b]];
+         w.n = valid ? d.count_desc[b] : -1;
+         w.p = valid && d.count_desc[b] > 0 ? d.words + d.key_off[b] * 2 : nullptr;
+      }
+   }
    void done(const ChunkDone &d) override
    {
       const size_t B = d.chunk->index.size();
+      note_words(d, true);
       if (region_results) {
          size_t h_off = 0;
          for (size_t b = 0; b < B; b++) {
@@ -385,6 +402,7 @@ struct ArrayIO : ChunkIO {
       std::vector<hesaff_result> tmp(B);
       for (size_t b = 0; b < B; b++) { tmp[b].count_hessian = d.count_hessian[b]; tmp[b].count_desc = d.count_desc[b]; tmp[b].keys = d.keys + d.key_off[b]; }
       if (sink_rc.load() == 0) sink_rc.store(sink(user, (int)B, d.chunk->index.data(), tmp.data()));
+      note_words(d, false);   // the block goes back to the ring: the rows were valid inside the sink
       ring->release(d.block);
    }
 };
@@ -401,6 +419,7 @@ struct FileIO : ChunkIO {
    hesaff_file_status *status;
    float mrSize;
    int fmt;
+   int vocabulary_size = 0;   // HESAFF_OUT_WORDS: the header field of the words files
    bool device_format;   // rows arrive formatted (ChunkDone::text / bin): the writers only write()
    int resume;           // hesaff_set_resume: an image whose complete output exists is not read (2: the rows of a text output are counted)
    bool nice_pool;       // the pool's threads run at nice 10 (hesaff_set_pool_priority: a CPU-starved plan)
@@ -416,7 +435,7 @@ struct FileIO : ChunkIO {
    std::condition_variable cv_work, cv_img, cv_done;   // workers: a job may be available; next(): an image changed state; wait_writers()
    int next_decode = 0, consumed = 0, window = 0, pos = 0, chunks_out = 0;
    bool stop = false;
-   struct Task { int index; const hesaff_keypoint *keys; int n; int chunk; const char *text; size_t text_len; const char *bin; };
+   struct Task { int index; const hesaff_keypoint *keys; int n; int chunk; const char *text; size_t text_len; const char *bin; const int32_t *words; };
    std::deque<Task> tasks;
    struct Open { int left; int block; };
    std::vector<Open> open_chunks;
@@ -494,6 +513,11 @@ struct FileIO : ChunkIO {
       if (!bin) return o ? std::string(o) : std::string(paths[i]) + ".hesaff.sift";   // hesaff.cpp:170-173
       return o ? (std::string(o) + ((fmt & HESAFF_OUT_TEXT) ? ".bin" : "")) : std::string(paths[i]) + ".hesaff.bin";
    }
+   std::string words_name(int i) const   // out_paths[i] itself when the words file is the only output, like the sidecar's
+   {
+      const char *o = out_paths ? out_paths[i] : nullptr;
+      return o ? (std::string(o) + (fmt != HESAFF_OUT_WORDS ? ".words" : "")) : std::string(paths[i]) + ".hesaff.words";
+   }
    // Pixel buffers and coefficient blobs come from the context's page-locked memory when it offers some (PinHooks): the reader then
    // fills the buffer the copy engine reads - no malloc'ed image, no staging copy (8 MB per UHD PGM file, 25-50 MB per UHD JPEG blob:
    // 1-4 ms of a host thread per image).  Buffers of images that have reached the device go to the next decoder instead of back to
@@ -541,15 +565,19 @@ struct FileIO : ChunkIO {
    void decode_one(int i)
    {
       if (resume && paths[i]) {
-         int n_text = 0, n_bin = 0;
-         if (fmt & HESAFF_OUT_TEXT) n_text = hesaff_output_is_complete(out_name(i, false).c_str(), HESAFF_OUT_TEXT | (resume == 2 ? HESAFF_OUT_STRICT : 0));
-         if (fmt & HESAFF_OUT_BIN) n_bin = hesaff_output_is_complete(out_name(i, true).c_str(), HESAFF_OUT_BIN);
-         if (n_text >= 0 && n_bin >= 0 && (fmt != (HESAFF_OUT_TEXT | HESAFF_OUT_BIN) || n_text == n_bin)) {
+         // every selected output is complete, and all hold the same number of rows
+         int rows = -2;
+         bool complete = true;
+         auto check = [&](int n_rows) { if (n_rows < 0 || (rows != -2 && rows != n_rows)) complete = false; else rows = n_rows; };
+         if (fmt & HESAFF_OUT_TEXT) check(hesaff_output_is_complete(out_name(i, false).c_str(), HESAFF_OUT_TEXT | (resume == 2 ? HESAFF_OUT_STRICT : 0)));
+         if (complete && (fmt & HESAFF_OUT_BIN)) check(hesaff_output_is_complete(out_name(i, true).c_str(), HESAFF_OUT_BIN));
+         if (complete && (fmt & HESAFF_OUT_WORDS)) check(hesaff_output_is_complete(words_name(i).c_str(), HESAFF_OUT_WORDS));
+         if (complete) {
             {
                std::lock_guard<std::mutex> lk(mu);
                imgs[(size_t)i].state = 2;
                status[i].rc = HESAFF_OK; status[i].stage = HESAFF_FILE_SKIPPED;
-               status[i].count_hessian = -1; status[i].count_desc = (fmt & HESAFF_OUT_TEXT) ? n_text : n_bin;
+               status[i].count_hessian = -1; status[i].count_desc = rows;
             }
             cv_img.notify_all();
             return;
@@ -651,7 +679,7 @@ struct FileIO : ChunkIO {
             status[i].count_hessian = d.count_hessian[b];
             status[i].count_desc = d.count_desc[b];
             status[i].stage = HESAFF_FILE_DETECTED;
-            Task t{i, d.keys ? d.keys + d.key_off[b] : nullptr, d.count_desc[b], id, nullptr, 0, nullptr};
+            Task t{i, d.keys ? d.keys + d.key_off[b] : nullptr, d.count_desc[b], id, nullptr, 0, nullptr, d.words ? d.words + d.key_off[b] * 2 : nullptr};
             if (d.text) { t.text = d.text + d.text_off[b]; t.text_len = (size_t)(d.text_off[b + 1] - d.text_off[b]); }
             if (d.bin) t.bin = d.bin + d.key_off[b] * (size_t)148;
             tasks.push_back(t);
@@ -662,8 +690,10 @@ struct FileIO : ChunkIO {
    }
    int wants() const override
    {
-      if (!device_format) return WANT_KEYS;
-      return ((fmt & HESAFF_OUT_TEXT) ? WANT_TEXT : 0) | ((fmt & HESAFF_OUT_BIN) ? WANT_BIN : 0);
+      // (a words row is composed on the host from the key's record and its word: both travel)
+      const int words = (fmt & HESAFF_OUT_WORDS) ? (WANT_KEYS | WANT_WORDS) : 0;
+      if (!device_format) return WANT_KEYS | words;
+      return ((fmt & HESAFF_OUT_TEXT) ? WANT_TEXT : 0) | ((fmt & HESAFF_OUT_BIN) ? WANT_BIN : 0) | words;
    }
    bool failed(const HostChunk &q, int rc) override
    {
@@ -684,6 +714,7 @@ struct FileIO : ChunkIO {
          if (device_format) rc = hesaff_write_bin_rows(name.c_str(), t.bin, t.n);
          else rc = hesaff_write_bin(name.c_str(), t.keys, t.n, mrSize);
       }
+      if ((fmt & HESAFF_OUT_WORDS) && rc == HESAFF_OK) rc = hesaff_write_words(words_name(t.index).c_str(), t.keys, t.words, t.n, mrSize, vocabulary_size);
       int blk = -1;
       {
          std::lock_guard<std::mutex> lk(mu);

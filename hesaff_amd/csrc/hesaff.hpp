@@ -149,6 +149,27 @@ struct AffineHessianDetector {
       if (hesaff_set_descriptor(ctx_, mode) != HESAFF_OK) throw std::invalid_argument("descriptor is HESAFF_DESC_SIFT or HESAFF_DESC_ROOTSIFT");
    }
 
+   // No counterpart in the reference (hesaff_set_vocabulary, include/hesaff_amd.h): a vocabulary of k rows of 128 bytes (copied; k = 0:
+   // none, the default).  With one set, every call that fills `keys` also assigns each key its visual word on the device - the LOWEST
+   // row of least squared distance to the key's descriptor bytes - and words() holds them; `keys` does not change by a bit.
+   void setVocabulary(const uint8_t *words, int k)
+   {
+      const int rc = hesaff_set_vocabulary(ctx_, k, words);
+      if (rc == HESAFF_ERR_ARG) throw std::invalid_argument("a vocabulary is k rows of 128 bytes, 0 <= k <= 2^20 (k = 0: none)");
+      if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+      words_.clear();
+   }
+   // (word, dist2) per key, two int32 each, parallel to `keys`: nullptr without a vocabulary or without keys
+   const int32_t *words() const { return words_.empty() ? nullptr : words_.data(); }
+   // <image>.hesaff.words of the current keys (hesaff_write_words): x, y, a, b, c as exportKeypoints prints them, and the word
+   void exportWords(const std::string &path) const
+   {
+      int k = 0;
+      if (hesaff_get_vocabulary_size(ctx_, &k) != HESAFF_OK || k == 0) throw std::runtime_error("exportWords: no vocabulary is set");
+      if (hesaff_write_words(path.c_str(), keys.data(), words(), (int)keys.size(), p_.mrSize, k) != HESAFF_OK)
+         throw std::runtime_error("cannot write '" + path + "'");
+   }
+
    // No counterpart in the reference (hesaff_set_next_masks, include/hesaff_amd.h; OpenCV's detect(image, keypoints, mask)): the NEXT
    // detectPyramidKeypoints keeps only the Hessian keypoints on a non-zero pixel of `mask` - height x width 8-bit pixels at the size of
    // the image as passed, rows strideBytes apart (0: tightly packed), pixel (row, col) = (clamp((int)(y + 0.5f)), clamp((int)(x +
@@ -269,6 +290,14 @@ struct AffineHessianDetector {
       g_numberOfPoints = count_hessian;
       g_numberOfAffinePoints += count_desc;   // the reference never resets this counter (hesaff.cpp:166)
       keys.assign(k, k + count_desc);
+      // the words of these keys, when a vocabulary is set (every call here has one image: index 0)
+      words_.clear();
+      int vk = 0, n = 0;
+      const int32_t *w = nullptr;
+      if (hesaff_get_vocabulary_size(ctx_, &vk) == HESAFF_OK && vk > 0) {
+         if (hesaff_get_words(ctx_, 0, &w, &n) != HESAFF_OK) throw std::runtime_error("hesaff_get_words failed");
+         if (n > 0) words_.assign(w, w + 2 * (size_t)n);
+      }
    }
    void taken(const hesaff_region_result &r, std::vector<hesaff_region> *described)
    {
@@ -313,6 +342,7 @@ struct AffineHessianDetector {
    hesaff_ctx *ctx_ = nullptr;
    HessianKeypointCallback *hessianKeypointCallback_ = nullptr;
    AffineShapeCallback *affineShapeCallback_ = nullptr;
+   std::vector<int32_t> words_;      // setVocabulary: (word, dist2) per key
    const uint8_t *mask_ = nullptr;   // setMask
    int maskStride_ = 0;
 };

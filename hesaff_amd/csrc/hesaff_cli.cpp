@@ -41,6 +41,11 @@
 //       --descriptor sift | rootsift  what the 128 bytes of a row hold (hesaff_set_descriptor): the reference's SIFT bytes (default), or RootSIFT -
 //                                     the vector L1-normalised and square-rooted on the device before it is quantised, for retrieval and matching
 //                                     under the Hellinger kernel.  The file formats are unchanged.  Batch form, and behind a single image.
+//   hesaff <image> --vocabulary <vocabulary file>
+//       a vocabulary of visual words (hesaff_read_vocabulary: "HESAFFV1", rows of 128 bytes): every key is assigned the lowest row of least
+//       squared distance to its descriptor on the device (hesaff_set_vocabulary), and <image>.hesaff.words (hesaff_write_words: x, y, a, b,
+//       c and the word per key) is written beside the .hesaff.sift.  With --batch the same for every image of the list; --words-only
+//       then writes the words files alone.  A vocabulary file that cannot be read ends the run before any image is read.
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -114,7 +119,8 @@ bool parse_devices(const char *spec, std::vector<int> &out)
 // hesaff --batch: the list is cut into contiguous shards, one per device context (hesaff_shard_range); every shard runs
 // through hesaff_process_files - decode threads -> device -> writer threads, bounded memory - on its own host thread.
 int run_batch_mode(const char *list_path, const char *devices_spec, int out_format, bool dynamic, int fast, int resume, int host_share, int runtime_nice,
-                   int max_keypoints, int orientation, int grid_rows, int grid_cols, int descriptor, int orientations)
+                   int max_keypoints, int orientation, int grid_rows, int grid_cols, int descriptor, int orientations,
+                   const uint8_t *vocabulary, int vocabulary_size)
 {
    std::ifstream lf(list_path);
    if (!lf) { fprintf(stderr, "hesaff: cannot read list '%s'\n", list_path); return 1; }
@@ -169,6 +175,11 @@ int run_batch_mode(const char *list_path, const char *devices_spec, int out_form
       hesaff_set_orientation(ctx, orientation);
       hesaff_set_orientation_count(ctx, orientations);
       hesaff_set_descriptor(ctx, descriptor);
+      if (vocabulary_size > 0 && hesaff_set_vocabulary(ctx, vocabulary_size, vocabulary) != HESAFF_OK) {
+         errs[(size_t)rank] = hesaff_last_error(ctx);
+         hesaff_destroy(ctx);
+         return;
+      }
       hesaff_host_plan hp;   // this device's share of the host: the library's one rule (include/hesaff_amd.h)
       hesaff_host_plan_for(world * host_share, &hp);
       const int wt = hp.write_threads, dt = hp.decode_threads;
@@ -247,14 +258,17 @@ int main(int argc, char **argv)
    if (batch) {
       const char *devices = nullptr, *list = nullptr;
       int out_format = HESAFF_OUT_TEXT, fast = 0, host_share = 1, runtime_nice = -1, max_keypoints = 0, orientation = HESAFF_ORI_UP, grid_rows = 1, grid_cols = 1, descriptor = HESAFF_DESC_SIFT, orientations = 1;
-      bool bad = false, grid = false, dynamic = false;
+      bool bad = false, grid = false, dynamic = false, words_only = false;
+      const char *vocabulary_path = nullptr;
       int resume = 0;
       for (int i = 1; i < argc && !bad; i += 2) {
          if (strcmp(argv[i], "--resume") == 0) { resume = 1; i--; continue; }
          if (strcmp(argv[i], "--resume=strict") == 0) { resume = 2; i--; continue; }   // also count the rows of existing text outputs
+         if (strcmp(argv[i], "--words-only") == 0) { words_only = true; i--; continue; }
          if (i + 1 >= argc) bad = true;
          else if (strcmp(argv[i], "--batch") == 0) list = argv[i + 1];
          else if (strcmp(argv[i], "--devices") == 0) devices = argv[i + 1];
+         else if (strcmp(argv[i], "--vocabulary") == 0) vocabulary_path = argv[i + 1];
          else if (strcmp(argv[i], "--host-share") == 0) { host_share = atoi(argv[i + 1]); bad = host_share < 1 || host_share > 1024; }
          else if (strcmp(argv[i], "--runtime-nice") == 0) { runtime_nice = atoi(argv[i + 1]); bad = runtime_nice < 0 || runtime_nice > 1; }
          else if (strcmp(argv[i], "--max-keypoints") == 0) {
@@ -298,10 +312,37 @@ int main(int argc, char **argv)
       }
       // a grid divides a budget: without --max-keypoints, or with more cells than keypoints, there is nothing to divide
       if (grid && (max_keypoints < 1 || grid_rows * grid_cols > max_keypoints)) bad = true;
-      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1] [--max-keypoints N] [--orientations 1..4] [--descriptor sift|rootsift] [--orientation up|dominant] [--grid RxC]\n"); return 1; }
-      return run_batch_mode(list, devices, out_format, dynamic, fast, resume, host_share, runtime_nice, max_keypoints, orientation, grid_rows, grid_cols, descriptor, orientations);
+      if (words_only && !vocabulary_path) bad = true;
+      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--vocabulary <vocabulary file> [--words-only]] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1] [--max-keypoints N] [--orientations 1..4] [--descriptor sift|rootsift] [--orientation up|dominant] [--grid RxC]\n"); return 1; }
+      uint8_t *vocabulary = nullptr;
+      int vocabulary_size = 0;
+      if (vocabulary_path) {   // before any image is read
+         if (hesaff_read_vocabulary(vocabulary_path, &vocabulary, &vocabulary_size) != HESAFF_OK) {
+            fprintf(stderr, "hesaff: cannot read vocabulary '%s' (a HESAFFV1 file with rows of 128 bytes expected)\n", vocabulary_path);
+            return 1;
+         }
+         out_format = words_only ? HESAFF_OUT_WORDS : (out_format | HESAFF_OUT_WORDS);
+      }
+      const int brc = run_batch_mode(list, devices, out_format, dynamic, fast, resume, host_share, runtime_nice, max_keypoints, orientation, grid_rows, grid_cols, descriptor,
+                                     orientations, vocabulary, vocabulary_size);
+      hesaff_free(vocabulary);
+      return brc;
    }
    if (argc > 1) {
+      // --vocabulary <file> behind the image (the last one counts): read first, so that a bad file ends the run before the image is read
+      uint8_t *vocabulary = nullptr;
+      int vocabulary_size = 0;
+      for (int i = 2; i < argc; i++) {
+         if (strcmp(argv[i], "--vocabulary") != 0) continue;
+         if (vocabulary) { hesaff_free(vocabulary); vocabulary = nullptr; }
+         if (i + 1 >= argc) { fprintf(stderr, "hesaff: --vocabulary needs a vocabulary file\n"); return 1; }
+         const char *vname = argv[++i];
+         if (hesaff_read_vocabulary(vname, &vocabulary, &vocabulary_size) != HESAFF_OK) {
+            fprintf(stderr, "hesaff: cannot read vocabulary '%s' (a HESAFFV1 file with rows of 128 bytes expected)\n", vname);
+            return 1;
+         }
+      }
+      struct FreeVocabulary { uint8_t *&p; ~FreeVocabulary() { hesaff_free(p); } } free_vocabulary{vocabulary};
       uint8_t *data = nullptr;
       int w = 0, h = 0, ch = 0;
       if (hesaff_read_image(argv[1], &data, &w, &h, &ch) != HESAFF_OK) {
@@ -364,7 +405,7 @@ int main(int argc, char **argv)
          if (strcmp(v, "sift") == 0) descriptor = HESAFF_DESC_SIFT;
          else if (strcmp(v, "rootsift") == 0) descriptor = HESAFF_DESC_ROOTSIFT;
          else {
-            fprintf(stderr, "hesaff: usage: hesaff <image> [--mask <mask file>] [--orientation up|dominant] [--orientations 1..4] [--descriptor sift|rootsift]\n");
+            fprintf(stderr, "hesaff: usage: hesaff <image> [--mask <mask file>] [--orientation up|dominant] [--orientations 1..4] [--descriptor sift|rootsift] [--vocabulary <vocabulary file>]\n");
             hesaff_free(data);
             if (mask) hesaff_free(mask);
             return 1;
@@ -377,6 +418,7 @@ int main(int argc, char **argv)
          detector.setOrientation(orientation);
          detector.setOrientationCount(orientations);
          detector.setDescriptor(descriptor);
+         if (vocabulary) detector.setVocabulary(vocabulary, vocabulary_size);
          const auto t1 = std::chrono::steady_clock::now();
          detector.detectPyramidKeypoints(data, w, h, ch);
          const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
@@ -386,6 +428,7 @@ int main(int argc, char **argv)
          std::ofstream out(name.c_str());
          if (!out) { fprintf(stderr, "hesaff: cannot write '%s'\n", name.c_str()); hesaff_free(data); if (mask) hesaff_free(mask); return 1; }
          detector.exportKeypoints(out);
+         if (vocabulary) detector.exportWords(std::string(argv[1]) + ".hesaff.words");
       } catch (const std::exception &e) {
          fprintf(stderr, "hesaff: %s\n", e.what());
          hesaff_free(data);

@@ -1095,6 +1095,12 @@ int hesaff_output_is_complete(const char *path, int format)
          memcpy(&dim, head + 8, 4); memcpy(&cnt, head + 12, 4);
          if (dim == 128 && cnt <= 0x7fffffffu && (unsigned long long)size == 16ull + 148ull * cnt) result = (int)cnt;
       }
+   } else if (format == HESAFF_OUT_WORDS) {   // words file: magic, size == 16 + 24 n
+      uint32_t cnt = 0;
+      if (got >= 16 && memcmp(head, "HESAFFW1", 8) == 0) {
+         memcpy(&cnt, head + 12, 4);
+         if (cnt <= 0x7fffffffu && (unsigned long long)size == 16ull + 24ull * cnt) result = (int)cnt;
+      }
    } else if (got >= 6 && memcmp(head, "128\n", 4) == 0) {
       long n = 0;
       int i = 4;
@@ -1138,6 +1144,96 @@ int hesaff_write_bin_rows(const char *path, const char *rows, int n)
    memcpy(head + 8, &dim, 4); memcpy(head + 12, &cnt, 4);
    return finish_part(fd, write_head_body(fd, head, 16, rows, (size_t)n * 148), part, path);
    HOSTIO_CATCH
+}
+
+// The words file of an image (hesaff_set_vocabulary): what a retrieval index keeps of a key.  Little-endian:
+//   char magic[8] = "HESAFFW1"; uint32 vocabulary_size; uint32 count; count x { float x, y, a, b, c; uint32 word }  (24 bytes each)
+// The five floats are those of hesaff_write_bin's row of the same key; words: (word, dist2) per key as hesaff_get_words hands them.
+int hesaff_write_words(const char *path, const hesaff_keypoint *keys, const int32_t *words, int n, float mrSize, int vocabulary_size)
+{
+   if (!path || n < 0 || vocabulary_size < 0 || (n > 0 && (!keys || !words))) return HESAFF_ERR_ARG;
+   HOSTIO_TRY
+   const size_t kRec = 24, kBlock = 8192;
+   static thread_local std::vector<char> tl_words;
+   tl_words.resize(16 + kBlock * kRec);
+   char *buf = tl_words.data();
+   std::string part;
+   const int fd = open_part(path, part);
+   if (fd < 0) return HESAFF_ERR_IO;
+   memcpy(buf, "HESAFFW1", 8);
+   const uint32_t vs = (uint32_t)vocabulary_size, cnt = (uint32_t)n;
+   memcpy(buf + 8, &vs, 4); memcpy(buf + 12, &cnt, 4);
+   size_t fill = 16;
+   bool ok = true;
+   for (int i0 = 0; ok; i0 += (int)kBlock) {
+      const int i1 = std::min(n, i0 + (int)kBlock);
+      char *p = buf + fill;
+      for (int i = i0; i < i1; i++) {
+         float v[5] = {keys[i].x, keys[i].y, 0, 0, 0};
+         hesaff_ellipse(&keys[i], mrSize, &v[2], &v[3], &v[4]);
+         const uint32_t w = (uint32_t)words[2 * (size_t)i];
+         memcpy(p, v, 20); memcpy(p + 20, &w, 4);
+         p += kRec;
+      }
+      ok = write_all(fd, buf, (size_t)(p - buf));
+      fill = 0;
+      if (i1 >= n) break;
+   }
+   return finish_part(fd, ok, part, path);
+   HOSTIO_CATCH
+}
+
+// Vocabulary file.  Little-endian:  char magic[8] = "HESAFFV1"; uint32 dim = 128; uint32 count; count x uint8[128]
+int hesaff_write_vocabulary(const char *path, const uint8_t *words, int k)
+{
+   if (!path || k < 1 || k > (1 << 20) || !words) return HESAFF_ERR_ARG;
+   HOSTIO_TRY
+   std::string part;
+   const int fd = open_part(path, part);
+   if (fd < 0) return HESAFF_ERR_IO;
+   char head[16];
+   memcpy(head, "HESAFFV1", 8);
+   const uint32_t dim = 128, cnt = (uint32_t)k;
+   memcpy(head + 8, &dim, 4); memcpy(head + 12, &cnt, 4);
+   return finish_part(fd, write_head_body(fd, head, 16, (const char *)words, (size_t)k * 128), part, path);
+   HOSTIO_CATCH
+}
+
+// -> the rows, malloc'ed (hesaff_free).  HESAFF_ERR_IO: the file cannot be read, or is not a whole vocabulary file (wrong magic, dim
+// other than 128, count outside 1 .. 2^20, a size other than 16 + 128 count).
+int hesaff_read_vocabulary(const char *path, uint8_t **words, int *k)
+{
+   if (!path || !words || !k) return HESAFF_ERR_ARG;
+   *words = nullptr; *k = 0;
+   const int fd = open(path, O_RDONLY | O_CLOEXEC);
+   if (fd < 0) return HESAFF_ERR_IO;
+   int rc = HESAFF_ERR_IO;
+   uint8_t *buf = nullptr;
+   const off_t size = lseek(fd, 0, SEEK_END);
+   char head[16];
+   uint32_t dim = 0, cnt = 0;
+   if (size >= 16 && pread(fd, head, 16, 0) == 16 && memcmp(head, "HESAFFV1", 8) == 0) {
+      memcpy(&dim, head + 8, 4); memcpy(&cnt, head + 12, 4);
+      if (dim == 128 && cnt >= 1 && cnt <= (1u << 20) && (unsigned long long)size == 16ull + 128ull * cnt) {
+         const size_t bytes = (size_t)cnt * 128;
+         buf = (uint8_t *)malloc(bytes);
+         if (!buf) rc = HESAFF_ERR_NOMEM;
+         else {
+            size_t done = 0;
+            while (done < bytes) {
+               const ssize_t r = pread(fd, buf + done, bytes - done, (off_t)(16 + done));
+               if (r < 0 && errno == EINTR) continue;
+               if (r <= 0) break;
+               done += (size_t)r;
+            }
+            if (done == bytes) rc = HESAFF_OK;
+         }
+      }
+   }
+   close(fd);
+   if (rc != HESAFF_OK) { free(buf); return rc; }
+   *words = buf; *k = (int)cnt;
+   return HESAFF_OK;
 }
 
 // One file per image of a batch (exportKeypoints once per image, hesaff.cpp:170-176), images

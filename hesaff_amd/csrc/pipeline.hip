@@ -40,6 +40,7 @@
 #include "kernels_pyramid.h"
 #include "kernels_export.h"
 #include "kernels_jpeg.h"
+#include "kernels_words.h"
 #include "chunk_engine.h"
 #include "batch_plan.h"
 #include "context_tables.h"
@@ -431,6 +432,14 @@ struct hesaff_ctx {
    int orientation = HESAFF_ORI_UP;    // hesaff_set_orientation: HESAFF_ORI_DOMINANT runs the oriented order of group_schedule.h (run_keypoint_stages)
    int orientation_count = 1;          // hesaff_set_orientation_count: keys per region at most (read in HESAFF_ORI_DOMINANT only: ori_count)
    DevBuf b_ori_ranks;                 // the rank arrays of an orientation count K > 1 (OrientRanks, kernels_orient.h): allocated by the first such call
+   // hesaff_set_vocabulary: the vocabulary as k_assign_words reads it (kernels_words.h: XORed, padded to whole tiles, in lane order,
+   // with |w'|^2 per row); k = 0: none, and nothing below is allocated, launched or copied
+   struct Vocabulary { DevBuf tiles, norms; int k = 0, n_tiles = 0; } vocab;
+   DevBuf b_words;                     // (word, dist2) per record of b_out, written behind the pack stage of every batch
+   int64_t words_device_total = -1;    // hesaff_get_words_device: the rows of b_words after a device-resident call (-1: no such call was the last)
+   std::vector<hesaff_engine::WordSpan> word_spans;   // hesaff_get_words: per image of the last host call, its rows in the call's result blocks
+   DevEvent ev_assign[2];              // profiling: brackets of the last k_assign_words launch
+   bool assign_timed = false;          // ev_assign holds a launch of the last batch
    ArmedMasks next_masks;              // hesaff_set_next_masks / _device: the masks of the next detecting call (taken, so cleared, by take_masks)
    int stage_threads = 4;              // host threads that copy a chunk's pixels into pinned memory (hesaff_process_files: within its thread budget)
    DevEvent ev_detect_done, ev_batch_done;   // blocking-sync events: the host sleeps instead of spinning
@@ -1231,6 +1240,31 @@ struct PeaksDevice : GroupDevice {
    void rank_descriptors(int g, int r, int slot, sched::Stream ss) { describe(g, slot, ss, mr.alive_of(r), mr.desc_of(r)); }
 };
 
+// k_assign_words (kernels_words.h) over n descriptors in device memory, on the main stream: (word, dist2) per key into d_out.
+// With profiling on, the launch is bracketed for hesaff_get_assign_ms.
+void launch_assign_words(hesaff_ctx *c, const void *d_desc, long long n, long long stride, long long offset, void *d_out)
+{
+   c->assign_timed = false;
+   if (n <= 0) return;
+   hipStream_t st = c->stream();
+   const bool timed = c->profiling >= 1;
+   if (timed && !c->ev_assign[0]) { c->ev_assign[0] = DevEvent(hipEventDefault); c->ev_assign[1] = DevEvent(hipEventDefault); }
+   if (timed) HIP_TRY(hipEventRecord(c->ev_assign[0], st));
+   const long long blocks = (n + HS_WORD_BLOCK_KEYS - 1) / HS_WORD_BLOCK_KEYS;
+   hipLaunchKernelGGL(k_assign_words, dim3((uint32_t)blocks), dim3(HS_WORD_BLOCK_WAVES * 64), 0, st, (const uint8_t *)d_desc, n, stride, offset,
+                      (const hs_v4i *)c->vocab.tiles.p, (const int32_t *)c->vocab.norms.p, c->vocab.n_tiles, (int32_t *)d_out);
+   if (timed) { HIP_TRY(hipEventRecord(c->ev_assign[1], st)); c->assign_timed = true; }
+}
+
+// the words of a batch's ordered records (b_out), behind the pack stage: b_words row for row
+void assign_batch_words(hesaff_ctx *c, long long total)
+{
+   c->assign_timed = false;
+   if (c->vocab.k == 0 || total <= 0) return;
+   c->b_words.ensure_grow((size_t)total * 8);
+   launch_assign_words(c, c->geo.b_out.p, total, (long long)sizeof(KeyRec), 36, c->b_words.p);
+}
+
 // Everything after the Hessian list of a batch is complete - by detection (run_batch) or from the caller's records (run_describe):
 // affine shape, patches and descriptors over image groups in the order of group_schedule.h, the stable compaction into KeyRec records,
 // the descriptor starts, and the wait for the end of the batch.  hs: fetch_hessian_starts' block.  with_affine = false: the affine
@@ -1310,6 +1344,7 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
    if (K > 1 && cn->desc_total > c->cap)
       throw HsError(HESAFF_ERR_CAPACITY, "the keys of the orientation count exceed the keypoint capacity; raise hesaff_params.max_kpts_per_mpx");
    const StartsBlock<const int32_t> h = starts_block((const int32_t *)h_starts, B);
+   assign_batch_words(c, (long long)h.desc()[B]);   // (nothing without a vocabulary)
    return {h.hess(), h.desc(), d_starts.desc()};
 }
 

@@ -50,6 +50,7 @@ extern "C" {
  *    And for hesaff_set_descriptor / hesaff_get_descriptor / hesaff_stage_sift_mode (RootSIFT descriptor mode): symbols only, version 8.
  *    And for hesaff_set_orientation_count / hesaff_get_orientation_count / hesaff_stage_orientation_peaks (secondary orientation peaks):
  *    symbols only, version 8.  With a count above 1, hesaff_region.reserved carries the number of a region's keys.
+ *    And for visual-word assignment (hesaff_set_vocabulary and the ten symbols declared with it, HESAFF_OUT_WORDS): symbols only, version 8.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -194,6 +195,8 @@ int hesaff_process_files(hesaff_ctx *ctx, int n, const char *const *paths, const
  * given, the binary file is out_paths[i] + ".bin" when both are written, out_paths[i] itself when only the binary one is. */
 #define HESAFF_OUT_TEXT 1
 #define HESAFF_OUT_BIN 2
+#define HESAFF_OUT_WORDS 4        /* <image>.hesaff.words (hesaff_write_words; needs a vocabulary, hesaff_set_vocabulary): alone or or-ed with the
+                                     other two.  With out_paths given: out_paths[i] + ".words" when combined, out_paths[i] itself when alone. */
 #define HESAFF_OUT_STRICT 0x100   /* hesaff_output_is_complete only: also count the rows of a text file (reads the whole file) */
 int hesaff_set_output_format(hesaff_ctx *ctx, int format);
 /* Resume a list that was interrupted (checkpoint / resume; no counterpart in the reference, which handles one
@@ -516,6 +519,51 @@ int hesaff_get_orientation_count(const hesaff_ctx *ctx, int *k);
 int hesaff_set_descriptor(hesaff_ctx *ctx, int mode);
 int hesaff_get_descriptor(const hesaff_ctx *ctx, int *mode);
 
+/* Visual-word assignment (no counterpart in the reference; the quantisation step of a retrieval pipeline): the nearest row of a
+ * vocabulary for every key, found on the device, so that a caller keeps (x, y, a, b, c, word) per region instead of 128 bytes.
+ * A vocabulary is K rows of 128 unsigned bytes, 1 <= K <= 2^20, in the byte space of the descriptors the context produces (SIFT or
+ * RootSIFT: the library does not check which).  For a key with descriptor bytes d[0..127]:
+ *     dist2(k) = sum_j (d[j] - w_k[j])^2        integers, at most 128 * 255^2 = 8 323 200
+ *     word     = the LOWEST k that minimises dist2(k)
+ *     dist2    = dist2(word)
+ * No floating point, no approximation, no dependence on launch geometry: exact, ties to the lowest row.  (On the device: with
+ * d' = d ^ 0x80 and w' = w ^ 0x80 read as signed bytes, dist2(k) = |d'|^2 + |w'_k|^2 - 2 d'.w'_k, every term within int32, the dot
+ * products on the i8 matrix instructions; kernels_words.h.)
+ * hesaff_set_vocabulary: words[k][128], copied to the device; k = 0 (words may be NULL): no vocabulary, the default.  The vocabulary
+ * is context state, like the descriptor mode.  With none set everything is bit for bit what it is without this feature: nothing is
+ * launched, allocated or copied.  With one set, every entry point that produces keys also assigns their words: hesaff_detect_batch*,
+ * hesaff_detect_regions*, hesaff_describe_regions*, hesaff_detect_batch_device* and hesaff_process_files; the keys do not change by a bit.
+ * HESAFF_ERR_NOMEM: the device cannot hold the vocabulary; the previous one stays set.
+ * hesaff_get_words: `image` is the caller's image index of the last host call; *words = int32_t[count][2] = (word, dist2), row for row
+ * that image's `keys` (count == count_desc: with an orientation count above 1 one row per key, not per region); *words is NULL when
+ * count is 0.  The pointer lives as long as the keys do; in the _cb forms it is valid inside the sink for the images of the chunk
+ * being delivered.
+ * hesaff_get_words_device: the device array parallel to d_keys_out of the last device-resident call.
+ * hesaff_assign_words_device: words for n caller-held descriptors in device memory; descriptor i is the 128 bytes at d_desc + i * stride
+ * + offset (stride = 164, offset = 36: a hesaff_keypoint array; stride = 128, offset = 0: a packed tensor); d_words_out receives n x 2
+ * int32.  hesaff_stage_assign_words: the same for desc[n][128] in host memory, words_out[n][2].
+ * hesaff_get_assign_ms: the HIP-event time of the last batch's assignment launch at profiling level >= 1 (0 otherwise).
+ * HESAFF_ERR_ARG, nothing changed, the context usable as before: ctx NULL; k < 0 or k > 2^20; words NULL with k > 0; a getter's out
+ * pointer NULL; hesaff_get_words*, hesaff_assign_words_device, hesaff_stage_assign_words, or HESAFF_OUT_WORDS in hesaff_process_files,
+ * with no vocabulary set; `image` outside the last host call's images; stride < 128, offset < 0, offset + 128 > stride, or stride,
+ * offset or a device pointer not a multiple of 4; n < 0. */
+int hesaff_set_vocabulary(hesaff_ctx *ctx, int k, const uint8_t *words);
+int hesaff_get_vocabulary_size(const hesaff_ctx *ctx, int *k);
+int hesaff_get_words(const hesaff_ctx *ctx, int image, const int32_t **words, int *count);
+int hesaff_get_words_device(const hesaff_ctx *ctx, const void **d_words, int64_t *total);
+int hesaff_assign_words_device(hesaff_ctx *ctx, int64_t n, const void *d_desc, int64_t stride, int64_t offset, void *d_words_out);
+int hesaff_stage_assign_words(hesaff_ctx *ctx, int n, const uint8_t *desc, int32_t *words_out);
+int hesaff_get_assign_ms(const hesaff_ctx *ctx, float *ms);
+/* The words file of an image, what a retrieval index keeps of its keys.  Little-endian:
+ *   char magic[8] = "HESAFFW1"; uint32 vocabulary_size; uint32 count; count x { float x, y, a, b, c; uint32 word }   (24 bytes per row)
+ * The five floats are those of hesaff_write_bin's row of the same key; words = (word, dist2) per key as hesaff_get_words hands them. */
+int hesaff_write_words(const char *path, const hesaff_keypoint *keys, const int32_t *words, int n, float mrSize, int vocabulary_size);
+/* Vocabulary file.  Little-endian:  char magic[8] = "HESAFFV1"; uint32 dim = 128; uint32 count; count x uint8[128]
+ * hesaff_read_vocabulary: *words is malloc'ed (hesaff_free); HESAFF_ERR_IO for a file that cannot be read or is not a whole vocabulary
+ * file (magic, dim, count outside 1 .. 2^20, size other than 16 + 128 count). */
+int hesaff_read_vocabulary(const char *path, uint8_t **words, int *k);
+int hesaff_write_vocabulary(const char *path, const uint8_t *words, int k);
+
 /* Same path with inputs already resident in device memory (bench / pipelines that decode
  * on the GPU): d_gray = n contiguous height x width 8-bit grey planes (device pointer).
  * Results stay on the device; per-image counts are copied to the two host arrays.
@@ -544,8 +592,8 @@ int hesaff_write_bin(const char *path, const hesaff_keypoint *keys, int n, float
  * n rows of 148 bytes; the header lines (hesaff.cpp:109-110) / the 16-byte sidecar header are added here. */
 int hesaff_write_sift_rows(const char *path, const char *rows, size_t len, int n);
 int hesaff_write_bin_rows(const char *path, const char *rows, int n);
-/* the row count of `path` when it is the complete output (format HESAFF_OUT_TEXT or HESAFF_OUT_BIN, optionally | HESAFF_OUT_STRICT)
- * of an earlier run, -1 otherwise: what hesaff_set_resume goes by (on = 1: as given; on = 2: with HESAFF_OUT_STRICT) */
+/* the row count of `path` when it is the complete output (format HESAFF_OUT_TEXT or HESAFF_OUT_BIN, optionally | HESAFF_OUT_STRICT, or
+ * HESAFF_OUT_WORDS: magic and size == 16 + 24 * count) of an earlier run, -1 otherwise: what hesaff_set_resume goes by (on = 1: as given; on = 2: with HESAFF_OUT_STRICT) */
 int hesaff_output_is_complete(const char *path, int format);
 /* formats into a malloc'ed buffer (*out, *len); caller frees with hesaff_free */
 int hesaff_format_sift(const hesaff_keypoint *keys, int n, float mrSize, char **out, size_t *len);

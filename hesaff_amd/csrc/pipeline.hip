@@ -1142,17 +1142,26 @@ struct BatchResult {
 
 // run_group_schedule's device (group_schedule.h): the launches of the keypoint stages of one batch, each with its timer bracket, on
 // the stream the schedule names.  The order, the waits and the slots are the schedule's; nothing here decides any of them.
+// Rank 0 lives in the base lists and b_desc; with an orientation count K > 1 a rank r >= 1 has its own frames, window sides, flags and
+// descriptor rows (mr) - the bins and their counters are the one set, cleared for every pass.
 struct GroupDevice : ScheduleDevice {
    const Lists &s;
    StageTimer &tm;
    const std::vector<ImageGroup> &groups;
    const PlaneTab &pt;
    int H, W;
+   OrientRanks mr;   // K > 1 only: nothing of it is read for rank 0
    int t_patch = -1;
-   GroupDevice(hesaff_ctx *ctx, const Lists &s_, StageTimer &tm_, const std::vector<ImageGroup> &groups_, const PlaneTab &pt_, int H_, int W_)
-      : ScheduleDevice{ctx}, s(s_), tm(tm_), groups(groups_), pt(pt_), H(H_), W(W_)
+   GroupDevice(hesaff_ctx *ctx, const Lists &s_, StageTimer &tm_, const std::vector<ImageGroup> &groups_, const PlaneTab &pt_, int H_, int W_, const OrientRanks &mr_)
+      : ScheduleDevice{ctx}, s(s_), tm(tm_), groups(groups_), pt(pt_), H(H_), W(W_), mr(mr_)
    {
       while (c->ev_aff.size() < groups.size()) c->ev_aff.emplace_back(hipEventDisableTiming);
+   }
+   Lists lists(int r) const
+   {
+      Lists sr = s;
+      if (r > 0) { sr.pw.A = mr.A_of(r); sr.pw.P0 = mr.P0_of(r); sr.pw.alive = mr.alive_of(r); }
+      return sr;
    }
    void affine(int g, sched::Stream as)
    {
@@ -1162,82 +1171,45 @@ struct GroupDevice : ScheduleDevice {
                          c->tables.view, c->ct.consts, s.ao);
       tm.end(ta);
    }
-   void patch_prepare(int g)
+   void pass_prepare(int g, int r, sched::Pass pass)
    {
       hipStream_t st = c->stream();
-      t_patch = tm.begin(T_PATCH);
+      if (pass == sched::PASS_UPRIGHT || r > 0) t_patch = tm.begin(T_PATCH);   // the unit's first pass; patch_done ends the bracket
       HIP_TRY(hipMemsetAsync(s.counters->bin_count, 0, CounterBlock::bins_bytes(), st));   // bin counts and work counters
       // (the group's end travels as a kernel argument: a 4-byte copy from pageable memory would make the host wait
       //  here until the stream has drained, once per group)
-      hipLaunchKernelGGL(k_prepare_patch, dim3(1024), dim3(256), 0, st, s.hl, groups[g].lo, groups[g].hi, (const uint32_t *)&s.counters->head.hess_total, s.ao, H, W,
-                         c->ct.consts, c->tables.view, s.pw);
+      if (pass == sched::PASS_UPRIGHT)
+         hipLaunchKernelGGL(k_prepare_patch, dim3(1024), dim3(256), 0, st, s.hl, groups[g].lo, groups[g].hi, (const uint32_t *)&s.counters->head.hess_total, s.ao, H, W,
+                            c->ct.consts, c->tables.view, s.pw);
+      else
+         hipLaunchKernelGGL(k_prepare_patch_second, dim3(1024), dim3(256), 0, st, s.hl, groups[g].lo, groups[g].hi, (const uint32_t *)&s.counters->head.hess_total, H, W,
+                            c->ct.consts, c->tables.view, lists(r).pw);
    }
-   void patch_kernels(int g, int slot, int n_side)
+   void patch_kernels(int g, int r, int slot, int n_side)
    {
-      launch_patch_kernels(c, s, c->gray, c->b_patches2[slot].as<float>(), groups[g].lo, groups[g].large_rows, &pt, n_side);
+      launch_patch_kernels(c, lists(r), c->gray, c->b_patches2[slot].as<float>(), groups[g].lo, groups[g].large_rows, &pt, n_side);
    }
-   // the oriented order only (hesaff_set_orientation): inside the patch stage's timer bracket, like the second pass behind them
+   // inside the patch stage's timer bracket, like the turned pass behind it; the multi form also writes the frames and flags of every rank >= 1
    void orientation(int g, int slot)
    {
       OrientIO oi;
       memset(&oi, 0, sizeof oi);
       oi.patches = c->b_patches2[slot].as<float>(); oi.h_lo = groups[g].lo; oi.h_hi = groups[g].hi;
       oi.n_ptr = &s.counters->head.hess_total; oi.cap = s.hl.cap; oi.alive = s.pw.alive; oi.A = s.pw.A;
-      hipLaunchKernelGGL(k_orientation, dim3(orientation_grid(c, groups[g].hi - groups[g].lo)), dim3(64), 0, c->stream(), oi, c->tables.view);
-   }
-   void patch_rebin(int g)
-   {
-      hipStream_t st = c->stream();
-      HIP_TRY(hipMemsetAsync(s.counters->bin_count, 0, CounterBlock::bins_bytes(), st));
-      hipLaunchKernelGGL(k_prepare_patch_second, dim3(1024), dim3(256), 0, st, s.hl, groups[g].lo, groups[g].hi, (const uint32_t *)&s.counters->head.hess_total, H, W,
-                         c->ct.consts, c->tables.view, s.pw);
+      const dim3 grid(orientation_grid(c, groups[g].hi - groups[g].lo));
+      if (mr.K > 1) hipLaunchKernelGGL(k_orientation_peaks, grid, dim3(64), 0, c->stream(), oi, c->tables.view, mr);
+      else hipLaunchKernelGGL(k_orientation, grid, dim3(64), 0, c->stream(), oi, c->tables.view);
    }
    void patch_done(int) { tm.end(t_patch); }
-   void descriptors(int g, int slot, sched::Stream ss) { describe(g, slot, ss, s.pw.alive, c->geo.b_desc.as<uint8_t>()); }
-   void describe(int g, int slot, sched::Stream ss, const int32_t *alive, uint8_t *desc)
+   void descriptors(int g, int r, int slot, sched::Stream ss)
    {
       SiftIO so;
-      so.patches = c->b_patches2[slot].as<float>(); so.alive = alive; so.meanvar = c->b_meanvar2.as<float>();
-      so.vec = nullptr; so.desc = desc; so.h_lo = groups[g].lo; so.h_hi = groups[g].hi;
+      so.patches = c->b_patches2[slot].as<float>(); so.alive = lists(r).pw.alive; so.meanvar = c->b_meanvar2.as<float>();
+      so.vec = nullptr; so.desc = r > 0 ? mr.desc_of(r) : c->geo.b_desc.as<uint8_t>(); so.h_lo = groups[g].lo; so.h_hi = groups[g].hi;
       const int ts = tm.begin(T_SIFT, 0, stream(ss));
       launch_sift(c, stream(ss), so, groups[g].hi - groups[g].lo, c->b_siftvo2.as<float2>(), c->descriptor);
       tm.end(ts);
    }
-};
-
-// ... and of the peaks order (hesaff_set_orientation_count K > 1): the multi form of the orientation kernel, and a rank's pass over its
-// own frames, window sides and flags - the bins and their counters are the one set, cleared for every pass
-struct PeaksDevice : GroupDevice {
-   OrientRanks mr;
-   PeaksDevice(hesaff_ctx *ctx, const Lists &s_, StageTimer &tm_, const std::vector<ImageGroup> &groups_, const PlaneTab &pt_, int H_, int W_, const OrientRanks &mr_)
-      : GroupDevice(ctx, s_, tm_, groups_, pt_, H_, W_), mr(mr_) {}
-   Lists rank_lists(int r) const
-   {
-      Lists sr = s;
-      sr.pw.A = mr.A_of(r); sr.pw.P0 = mr.P0_of(r); sr.pw.alive = mr.alive_of(r);
-      return sr;
-   }
-   void orientation(int g, int slot)
-   {
-      OrientIO oi;
-      memset(&oi, 0, sizeof oi);
-      oi.patches = c->b_patches2[slot].as<float>(); oi.h_lo = groups[g].lo; oi.h_hi = groups[g].hi;
-      oi.n_ptr = &s.counters->head.hess_total; oi.cap = s.hl.cap; oi.alive = s.pw.alive; oi.A = s.pw.A;
-      hipLaunchKernelGGL(k_orientation_peaks, dim3(orientation_grid(c, groups[g].hi - groups[g].lo)), dim3(64), 0, c->stream(), oi, c->tables.view, mr);
-   }
-   void rank_prepare(int g, int r)
-   {
-      hipStream_t st = c->stream();
-      t_patch = tm.begin(T_PATCH);
-      HIP_TRY(hipMemsetAsync(s.counters->bin_count, 0, CounterBlock::bins_bytes(), st));
-      hipLaunchKernelGGL(k_prepare_patch_second, dim3(1024), dim3(256), 0, st, s.hl, groups[g].lo, groups[g].hi, (const uint32_t *)&s.counters->head.hess_total, H, W,
-                         c->ct.consts, c->tables.view, rank_lists(r).pw);
-   }
-   void rank_patch_kernels(int g, int r, int slot, int n_side)
-   {
-      launch_patch_kernels(c, rank_lists(r), c->gray, c->b_patches2[slot].as<float>(), groups[g].lo, groups[g].large_rows, &pt, n_side);
-   }
-   void rank_descriptors(int g, int r, int slot, sched::Stream ss) { describe(g, slot, ss, mr.alive_of(r), mr.desc_of(r)); }
 };
 
 // k_assign_words (kernels_words.h) over n descriptors in device memory, on the main stream: (word, dist2) per key into d_out.
@@ -1291,16 +1263,10 @@ BatchResult run_keypoint_stages(hesaff_ctx *c, const Lists &s, StageTimer &tm, i
       // image groups [lo, hi) of keypoints; the T' rows of a group's huge windows fit the row buffer (form_groups, batch_plan.h)
       const GroupPlan gp = form_groups(hs, hb.large_rows(), B, c->trows_rows);
       if (gp.max_n) ensure_group_buffers(c, gp.max_n);
-      const sched::ScheduleOptions so = {!c->no_overlap, c->sift_inside, with_affine, patch_side_streams(c, &pt)};
-      if (K > 1) {
-         ensure_rank_arrays(c, K);
-         PeaksDevice dev(c, s, tm, gp.groups, pt, H, W, rank_arrays(c, K));
-         sched::run_group_schedule_peaks(dev, (int)gp.groups.size(), K, so);
-      } else {
-         GroupDevice dev(c, s, tm, gp.groups, pt, H, W);
-         if (c->orientation == HESAFF_ORI_DOMINANT) sched::run_group_schedule_oriented(dev, (int)gp.groups.size(), so);
-         else sched::run_group_schedule(dev, (int)gp.groups.size(), so);
-      }
+      const sched::ScheduleOptions so = {!c->no_overlap, c->sift_inside, with_affine, patch_side_streams(c, &pt), c->orientation == HESAFF_ORI_DOMINANT, K};
+      if (K > 1) ensure_rank_arrays(c, K);
+      GroupDevice dev(c, s, tm, gp.groups, pt, H, W, rank_arrays(c, K));   // (K = 1: no rank above 0, nothing allocated, nothing of it read)
+      sched::run_group_schedule(dev, (int)gp.groups.size(), so);
    }
    t = tm.begin(T_PACK);
    // final stable compaction (hesaff.cpp:87: keys.push_back in detection order): exclusive scan of the alive flags of the batch's

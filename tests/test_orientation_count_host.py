@@ -1,6 +1,6 @@
 """CPU suite of the orientation count (hesaff_set_orientation_count: secondary orientation peaks, up to four keys per region): the
 peak rule of hesaff_amd/csrc/orient_peaks.h on constructed histograms and the peaks stream / event order of group_schedule.h, each under a
-stand-alone checker built with AddressSanitizer + UBSan (tests/native/orient_peaks_check.cpp, schedule_peaks_check.cpp), and the C ABI
+stand-alone checker built with AddressSanitizer + UBSan (tests/native/orient_peaks_check.cpp, the peaks part of schedule_check.cpp), and the C ABI
 (three new symbols, their argument refusals, version and struct sizes as before).  No GPU."""
 import ctypes as C
 import os
@@ -11,6 +11,7 @@ import pytest
 
 import hesaff_amd
 from hesaff_amd import _binding
+from tests.schedule_native import run_schedule_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -36,9 +37,10 @@ def test_peak_rule_on_constructed_histograms(tmp_path):
 
 
 def test_peaks_schedule(tmp_path):
-    """run_group_schedule_peaks over a recording device: the hazards of the (group, rank) units at 0 .. 7 groups (HS_NSLOT and
-    HS_NSLOT + 2 among them) for K = 2, 3, 4 under every ScheduleOptions form; K = 1 is the oriented order; every wait and record is needed."""
-    _native(tmp_path, "schedule_peaks_check")
+    """run_group_schedule with an orientation count over a recording device: the hazards of the (group, rank) units at 0 .. 7 groups
+    (HS_NSLOT and HS_NSLOT + 2 among them) for K = 2, 3, 4 under every ScheduleOptions form; every wait and record is needed; the
+    sequences of the peaks form the header had (tests/golden/group_schedule_oriented_parent.txt)."""
+    run_schedule_check(tmp_path, "peaks")
 
 
 def test_orientation_count_abi():

@@ -1,10 +1,9 @@
 """CPU suite of the dominant-orientation mode (hesaff_set_orientation): hm_sincosf on a host build against this image's libm, the
 oriented stream / event order of group_schedule.h under a stand-alone checker built with AddressSanitizer + UBSan
-(tests/native/schedule_oriented_check.cpp), and the C ABI (three new symbols, version and struct sizes as before).  No GPU."""
+(the oriented part of tests/native/schedule_check.cpp), and the C ABI (three new symbols, version and struct sizes as before).  No GPU."""
 import ctypes as C
 import math
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 
 import hesaff_amd
 from hesaff_amd import _binding
+from tests.schedule_native import run_schedule_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -54,17 +54,7 @@ def test_hm_sincosf_equals_libm_rounded_once(sincos_host):
 
 
 def test_oriented_schedule(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("g++ not available")
-    exe = str(tmp_path / "schedule_oriented_check")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-o", exe, os.path.join(ROOT, "tests", "native", "schedule_oriented_check.cpp")]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, "schedule_oriented_check failed (rc %d)\n%s\n%s" % (r.returncode, r.stdout[-2000:], r.stderr[-6000:])
-    assert "schedule_oriented_check ok" in r.stdout, r.stdout
+    run_schedule_check(tmp_path, "oriented")
 
 
 def test_orientation_abi():

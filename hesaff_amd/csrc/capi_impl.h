@@ -1,4 +1,4 @@
-// capi_impl.h -- the extern "C" entry points of include/hesaff_amd.h.
+// capi_impl.h -- the extern "C" entry points of include/hesaff_amd.h, the stage operators apart (hesaff_stage_*: capi_stage.h).
 // Included at the end of pipeline.hip (same translation unit: needs hesaff_ctx and the
 // batch runner).  No exception crosses the ABI: everything is caught and turned into a
 // negative return code + hesaff_last_error().
@@ -643,25 +643,8 @@ std::vector<const uint8_t *> validate_f32_list(int n, const float *const *images
    return bytes;
 }
 
-// hesaff_detect_batch_device_f32's check (k_check_f32) of n planes in device memory, before any kernel reads them as an image: one flag
-// per image, read back once; a refused image is copied back to name its first pixel outside the domain
-void check_device_f32(hesaff_ctx *c, int n, const uint8_t *d, long long img_stride, int row_stride, int H, int W)
-{
-   c->b_stage.ensure((size_t)n * 4);
-   int32_t *flags = c->b_stage.as<int32_t>();
-   HIP_TRY(hipMemsetAsync(flags, 0, (size_t)n * 4, c->stream()));
-   const int gx = std::max(1, std::min(H, (8 * c->n_cu + n - 1) / n));   // about 8 blocks per CU in all
-   hipLaunchKernelGGL(k_check_f32, dim3(gx, 1, n), dim3(256), 0, c->stream(), d, img_stride, row_stride, H, W, flags);
-   std::vector<int32_t> h((size_t)n);
-   HIP_TRY(hipMemcpyAsync(h.data(), flags, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream()));
-   finish_stream(c);
-   for (int b = 0; b < n; b++) {
-      if (!h[(size_t)b]) continue;
-      std::vector<uint8_t> img((size_t)H * W * 4);
-      HIP_TRY(hipMemcpy2D(img.data(), (size_t)W * 4, d + (long long)b * img_stride, (size_t)row_stride, (size_t)W * 4, (size_t)H, hipMemcpyDeviceToHost));
-      throw_bad_f32(b, img.data(), H, W, (size_t)W * 4);
-   }
-}
+// hesaff_detect_batch_device_f32's check of n planes in device memory (capi_stage.h: its flags are an array of the stage buffer)
+void check_device_f32(hesaff_ctx *c, int n, const uint8_t *d, long long img_stride, int row_stride, int H, int W);
 
 // The body of the six host-image entry points: the list is validated, cut into chunks (ArrayIO), given its consumer - set_consumer
 // fills in `results`, `region_results` or `sink` + `user` - and run through the chunk engine with `ring` result blocks.
@@ -1009,561 +992,6 @@ int hesaff_process_files(hesaff_ctx *c, int n, const char *const *paths, const c
    HS_API_END(c)
 }
 
-// ---------------------------------- stage entry points ----------------------------------
-
-// The stage entry points run the PRODUCTION kernels wherever the batch path has one for the operator:
-//   gaussianBlur     -> k_blur_hess_march<K> (K = 9, 11, 13, 15: every blur of the default pyramid), else the generic two-pass kernels
-//   hessianResponse  -> the fused R0 epilogue of k_blur_hess_march<9, .., WRITE_R0> (pyramid.cpp:230 on the batch path)
-//   SIFT             -> k_sift_meanvar / _grad / _hist (histogram, then normalise / clip / quantise)
-//   normalizeAffine  -> k_prepare_patch + the five window-size bin kernels
-//   findAffineShape  -> hs_affine_groups (k_affine's body)
-// halfImage has no stand-alone production kernel (the decimation is an epilogue of the K = 13 blur launch, checked
-// plane by plane through hesaff_stage_pyramid); k_half serves the operator here.
-int hesaff_stage_gaussian_blur(hesaff_ctx *c, const float *in, int rows, int cols, float sigma, float *out)
-{
-   if (!c || !in || !out || rows < 1 || cols < 1 || !(sigma > 0.0f)) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   const int K = hesaff::gauss_ksize(sigma);
-   const int pitch = round_up(cols, 64);   // like the batch planes: rows stay 16-byte aligned for the float4 stores
-   const size_t n = (size_t)rows * pitch;
-   c->b_stage.ensure(n * 4 * 3 + (size_t)(K + 16) * 4);
-   float *d_in = c->b_stage.as<float>(), *d_tmp = d_in + n, *d_out = d_tmp + n, *d_taps = d_out + n;
-   std::vector<float> taps(K);
-   hesaff::blur_taps(K, sigma, taps.data());
-   HIP_TRY(hipMemcpy2DAsync(d_in, (size_t)pitch * 4, in, (size_t)cols * 4, (size_t)cols * 4, rows, hipMemcpyHostToDevice, c->stream()));
-   HIP_TRY(hipMemcpyAsync(d_taps, taps.data(), (size_t)K * 4, hipMemcpyHostToDevice, c->stream()));
-   DPlane pi = make_plane(d_in, rows, cols, pitch), pt = make_plane(d_tmp, rows, cols, pitch), po = make_plane(d_out, rows, cols, pitch);
-   const DPlane none = make_plane(nullptr, 0, 0, 0);
-   if (K == 1) {
-      HIP_TRY(hipMemcpyAsync(d_out, d_in, n * 4, hipMemcpyDeviceToDevice, c->stream()));
-   } else if (K == 9 || K == 11 || K == 13 || K == 15) {
-      launch_blur_hess<true, false, false>(c, pi, po, none, none, d_taps, K, 0.0f, 1);
-   } else {
-      const dim3 grid((cols + 255) / 256, rows, 1);
-      hipLaunchKernelGGL(k_blur_rows_generic, grid, dim3(256), 0, c->stream(), pi, pt, (const float *)d_taps, K);
-      hipLaunchKernelGGL(k_blur_cols_generic, grid, dim3(256), 0, c->stream(), pt, po, (const float *)d_taps, K);
-   }
-   HIP_TRY(hipMemcpy2DAsync(out, (size_t)cols * 4, d_out, (size_t)pitch * 4, (size_t)cols * 4, rows, hipMemcpyDeviceToHost, c->stream()));
-   finish_stream(c);
-   HS_API_END(c)
-}
-
-int hesaff_stage_hessian_response(hesaff_ctx *c, const float *in, int rows, int cols, float norm, float *out)
-{
-   if (!c || !in || !out || rows < 1 || cols < 1) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   const int pitch = round_up(cols, 64);
-   const size_t n = (size_t)rows * pitch;
-   c->b_stage.ensure(n * 4 * 4 + 64);
-   float *d_in = c->b_stage.as<float>(), *d_out = d_in + n, *d_l = d_out + n, *d_r = d_l + n, *d_taps = d_r + n;
-   HIP_TRY(hipMemcpy2DAsync(d_in, (size_t)pitch * 4, in, (size_t)cols * 4, (size_t)cols * 4, rows, hipMemcpyHostToDevice, c->stream()));
-   DPlane pi = make_plane(d_in, rows, cols, pitch), po = make_plane(d_out, rows, cols, pitch);
-   // the batch path computes R0 in the epilogue of the first blur launch of an octave (K = 9 at the default sigmas)
-   std::vector<float> taps(9);
-   hesaff::blur_taps(9, hesaff::make_schedule(1.6f, false).blur_sigma[1], taps.data());
-   HIP_TRY(hipMemcpyAsync(d_taps, taps.data(), 9 * 4, hipMemcpyHostToDevice, c->stream()));
-   launch_march<9, true, true, false, true>(c, pi, make_plane(d_l, rows, cols, pitch), make_plane(d_r, rows, cols, pitch), make_plane(nullptr, 0, 0, 0),
-                                            d_taps, 1.0f, 1, po, norm * norm);
-   HIP_TRY(hipMemcpy2DAsync(out, (size_t)cols * 4, d_out, (size_t)pitch * 4, (size_t)cols * 4, rows, hipMemcpyDeviceToHost, c->stream()));
-   finish_stream(c);
-   HS_API_END(c)
-}
-
-int hesaff_stage_half_image(hesaff_ctx *c, const float *in, int rows, int cols, float *out)
-{
-   if (!c || !in || !out || rows < 2 || cols < 2) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   const size_t n = (size_t)rows * cols;
-   const int r2 = rows / 2, c2 = cols / 2;
-   c->b_stage.ensure(n * 4 * 2);
-   float *d_in = c->b_stage.as<float>(), *d_out = d_in + n;
-   HIP_TRY(hipMemcpyAsync(d_in, in, n * 4, hipMemcpyHostToDevice, c->stream()));
-   DPlane pi = make_plane(d_in, rows, cols, cols), po = make_plane(d_out, r2, c2, c2);
-   hipLaunchKernelGGL(k_half, dim3((c2 + 255) / 256, r2, 1), dim3(256), 0, c->stream(), pi, po);
-   HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)r2 * c2 * 4, hipMemcpyDeviceToHost, c->stream()));
-   finish_stream(c);
-   HS_API_END(c)
-}
-
-// hesaff_stage_pyramid and its float twin: `image` is rows x cols pixels of 1 byte or, f32, of 4, tightly packed.  Out come all
-// planes of every octave, L0..L4 then R0..R4, without pitch padding: the builder's, with L4 kept in a scratch plane sized here
-static int stage_pyramid(hesaff_ctx *c, const void *image, bool f32, int rows, int cols, float *planes, int *n_octaves, size_t *n_floats)
-{
-   if (!c || rows < 1 || cols < 1) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   plan(c, 1, rows, cols);
-   size_t nf = 0;
-   for (const OctGeom &g : c->oct) nf += (size_t)10 * g.rows * g.cols;
-   if (n_octaves) *n_octaves = (int)c->oct.size();
-   if (n_floats) *n_floats = nf;
-   if (planes) {
-      if (!image) throw HsError(HESAFF_ERR_ARG, f32 ? "plane is NULL" : "gray is NULL");
-      const size_t row_bytes = (size_t)cols * (f32 ? 4 : 1), bytes = row_bytes * rows;
-      if (f32) {
-         if ((uintptr_t)image % 4 != 0) throw HsError(HESAFF_ERR_ARG, "float plane not 4-byte aligned");
-         int r = 0, col = 0;
-         float v = 0.0f;
-         if (first_bad_f32((const uint8_t *)image, rows, cols, row_bytes, &r, &col, &v))   // the value domain of the _f32 entry points
-            throw_bad_f32(0, (const uint8_t *)image, rows, cols, row_bytes);
-      }
-      c->b_input.ensure(bytes);
-      if (!c->oct.empty()) c->b_stage.ensure((size_t)c->oct[0].rows * c->oct[0].pitch * 4);   // L4 of the largest octave, the plan's first
-      HIP_TRY(hipMemcpyAsync(c->b_input.p, image, bytes, hipMemcpyHostToDevice, c->stream()));
-      c->ev_used = 0;
-      StageTimer tm(c);
-      const SrcImages src = f32 ? SrcImages::f32(c->b_input.p, (long long)bytes, (int)row_bytes) : SrcImages::u8(c->b_input.p, 1, (long long)bytes, (int)row_bytes);
-      build_first_level(c, src, 1, tm);
-      float *pout = planes;
-      for (size_t o = 0; o < c->oct.size(); o++) {
-         const OctGeom &g = c->oct[o];
-         OctavePlanes P = octave_planes(c, o, 1);
-         P.L[4] = make_plane(c->b_stage.as<float>(), g.rows, g.cols, g.pitch);
-         build_octave(c, o, 1, P, OctaveWant::DetectKeepL4, tm);
-         // (before the next octave overwrites L3 and the response planes: the copies are in stream order)
-         for (int l = 0; l < 10; l++, pout += (size_t)g.rows * g.cols)
-            HIP_TRY(hipMemcpy2DAsync(pout, (size_t)g.cols * 4, (l < 5 ? P.L[l] : P.R[l - 5]).p, (size_t)g.pitch * 4, (size_t)g.cols * 4, g.rows, hipMemcpyDeviceToHost,
-                                     c->stream()));
-      }
-      finish_stream(c);
-   }
-   HS_API_END(c)
-}
-
-int hesaff_stage_pyramid(hesaff_ctx *c, const uint8_t *gray, int rows, int cols, float *planes, int *n_octaves, size_t *n_floats)
-{
-   return stage_pyramid(c, gray, false, rows, cols, planes, n_octaves, n_floats);
-}
-
-int hesaff_stage_pyramid_f32(hesaff_ctx *c, const float *plane, int rows, int cols, float *planes, int *n_octaves, size_t *n_floats)
-{
-   return stage_pyramid(c, plane, true, rows, cols, planes, n_octaves, n_floats);
-}
-
-// the first m entries of the ordered Hessian list as the stage entry points return them (image: optional)
-static void fetch_hessian_list(hesaff_ctx *c, const Lists &s, int m, float *f, int32_t *iv, int32_t *image)
-{
-   std::vector<float> x(m), y(m), sc(m), resp(m);
-   std::vector<int32_t> meta(m), key(m);
-   HIP_TRY(hipMemcpy(x.data(), s.hl.x, (size_t)m * 4, hipMemcpyDeviceToHost));
-   HIP_TRY(hipMemcpy(y.data(), s.hl.y, (size_t)m * 4, hipMemcpyDeviceToHost));
-   HIP_TRY(hipMemcpy(sc.data(), s.hl.s, (size_t)m * 4, hipMemcpyDeviceToHost));
-   HIP_TRY(hipMemcpy(resp.data(), s.hl.response, (size_t)m * 4, hipMemcpyDeviceToHost));
-   HIP_TRY(hipMemcpy(meta.data(), s.hl.meta, (size_t)m * 4, hipMemcpyDeviceToHost));
-   HIP_TRY(hipMemcpy(key.data(), s.hl.r0c0, (size_t)m * 4, hipMemcpyDeviceToHost));
-   for (int i = 0; i < m; i++) {
-      const int octave = (meta[i] >> 4) & 15, level = (meta[i] >> 2) & 3, type = meta[i] & 3;
-      const OctGeom &g = c->oct[octave];
-      const uint32_t pix = (uint32_t)key[i] % (uint32_t)(g.rows * g.cols);
-      f[5 * i] = x[i]; f[5 * i + 1] = y[i]; f[5 * i + 2] = sc[i]; f[5 * i + 3] = c->ct.consts.pd0 * (float)(1 << octave); f[5 * i + 4] = resp[i];
-      iv[5 * i] = type; iv[5 * i + 1] = octave; iv[5 * i + 2] = level; iv[5 * i + 3] = (int32_t)(pix / g.cols); iv[5 * i + 4] = (int32_t)(pix % g.cols);
-      if (image) image[i] = meta[i] >> 8;
-   }
-}
-
-// the end of a stage operator that has enqueued detection: waits, refuses a list that did not fit, returns its length and first `cap` entries
-static void finish_hessian_list(hesaff_ctx *c, const Lists &s, int cap, float *f, int32_t *iv, int32_t *image, int *count)
-{
-   CounterHead cn;
-   HIP_TRY(hipMemcpyAsync(&cn, &s.counters->head, sizeof cn, hipMemcpyDeviceToHost, c->stream()));
-   finish_stream(c);
-   if (cn.overflow != 0 || cn.rec > c->cap) throw HsError(HESAFF_ERR_CAPACITY, "keypoint capacity exceeded");
-   *count = (int)cn.hess_total;
-   const int m = std::min(*count, cap);
-   if (m > 0 && f && iv) fetch_hessian_list(c, s, m, f, iv, image);
-}
-
-int hesaff_stage_hessian_keypoints(hesaff_ctx *c, const uint8_t *gray, int rows, int cols, int cap, float *f, int32_t *iv, int *count)
-{
-   if (!c || !gray || rows < 1 || cols < 1 || !count) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   plan(c, 1, rows, cols);
-   c->b_input.ensure((size_t)rows * cols);
-   HIP_TRY(hipMemcpyAsync(c->b_input.p, gray, (size_t)rows * cols, hipMemcpyHostToDevice, c->stream()));
-   c->ev_used = 0;
-   StageTimer tm(c);
-   Lists s = make_lists(c);
-   run_detection(c, SrcImages::u8(c->b_input.p, 1, (long long)rows * cols, cols), 1, s, tm);
-   finish_hessian_list(c, s, cap, f, iv, nullptr, count);
-   HS_API_END(c)
-}
-
-// The detection chain on the caller's planes: what run_detection does with an octave's planes once it has made them (begin_detection,
-// detect_octave, order_hessian_list: pipeline.hip), on octave 0 of a plan for n_images x rows x cols.
-int hesaff_stage_detect_planes(hesaff_ctx *c, int n_images, int rows, int cols, const float *L, const float *R, int band, int cap, float *f,
-                               int32_t *iv, int32_t *image, int *count)
-{
-   const int min_size = 2 * HS_BORDER + 2;   // pyramid.cpp:283: the smallest plane that is an octave
-   if (!c || !L || !R || !count || n_images < 1 || rows <= min_size || cols <= min_size) return HESAFF_ERR_ARG;
-   if (band != 0 && band != 32 && band != 64 && band != 128) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   if (c->ct.up) throw HsError(HESAFF_ERR_ARG, "hesaff_stage_detect_planes: the planes are the first pyramid level as given; not with upscaleInputImage");
-   plan(c, n_images, rows, cols);
-   const OctGeom &g = c->oct[0];
-   hipStream_t st = c->stream();
-   const size_t tight = (size_t)rows * cols;
-   const OctavePlanes P = octave_planes(c, 0, n_images);
-   // cols floats per row: the pitch padding behind them keeps what it held.  k_extrema_march's clamped 16-byte loads read it, as they do on
-   // the batch path (the blur kernels store cols floats too); it can only reach columns that are not scanned
-   for (int b = 0; b < n_images; b++)
-      for (int l = 0; l < 5; l++) {
-         const size_t off = ((size_t)b * 5 + l) * tight;
-         HIP_TRY(hipMemcpy2DAsync(P.R[l].img(b), (size_t)g.pitch * 4, R + off, (size_t)cols * 4, (size_t)cols * 4, rows, hipMemcpyHostToDevice, st));
-         if (l < 4) HIP_TRY(hipMemcpy2DAsync(P.L[l].img(b), (size_t)g.pitch * 4, L + off, (size_t)cols * 4, (size_t)cols * 4, rows, hipMemcpyHostToDevice, st));
-      }
-   c->ev_used = 0;
-   StageTimer tm(c);
-   Lists s = make_lists(c);
-   begin_detection(c, s, n_images);
-   detect_octave(c, s, tm, n_images, 0, P.L, P.R, band);
-   order_hessian_list(c, s, tm, n_images);
-   finish_hessian_list(c, s, cap, f, iv, image, count);
-   HS_API_END(c)
-}
-
-int hesaff_stage_find_affine_shape(hesaff_ctx *c, const float *blur, int rows, int cols, int n, const float *kp, int32_t *converged,
-                                   float *U, int32_t *iters)
-{
-   if (!c || !blur || !kp || rows < 2 || cols < 2 || n < 0) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   if (n == 0) return HESAFF_OK;
-   const size_t np = (size_t)rows * cols;
-   c->b_stage.ensure(np * 4 + (size_t)n * (4 + 6) * 4 + 64);
-   float *d_plane = c->b_stage.as<float>();
-   float *d_kp = d_plane + np;
-   int32_t *d_conv = (int32_t *)(d_kp + (size_t)4 * n), *d_iters = d_conv + n;
-   float *d_U = (float *)(d_iters + n);
-   HIP_TRY(hipMemcpyAsync(d_plane, blur, np * 4, hipMemcpyHostToDevice, c->stream()));
-   HIP_TRY(hipMemcpyAsync(d_kp, kp, (size_t)n * 16, hipMemcpyHostToDevice, c->stream()));
-   AffineOut ao; ao.converged = d_conv; ao.iters = d_iters; ao.U = d_U;
-   DPlane P = make_plane(d_plane, rows, cols, cols);
-   hipLaunchKernelGGL(k_affine_stage, dim3(std::min((n + HS_AFFP_G - 1) / HS_AFFP_G, 256 * 6)), dim3(64), 0, c->stream(), P, (const float *)d_kp, n, c->tables.view, c->ct.consts, ao);
-   if (converged) HIP_TRY(hipMemcpyAsync(converged, d_conv, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream()));
-   if (iters) HIP_TRY(hipMemcpyAsync(iters, d_iters, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream()));
-   if (U) HIP_TRY(hipMemcpyAsync(U, d_U, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream()));
-   finish_stream(c);
-   HS_API_END(c)
-}
-
-int hesaff_stage_rectify(hesaff_ctx *c, int n, float *A)
-{
-   if (!c || !A || n < 0) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   if (n == 0) return HESAFF_OK;
-   c->b_stage.ensure((size_t)n * 16);
-   HIP_TRY(hipMemcpyAsync(c->b_stage.p, A, (size_t)n * 16, hipMemcpyHostToDevice, c->stream()));
-   hipLaunchKernelGGL(k_rectify_stage, dim3((n + 255) / 256), dim3(256), 0, c->stream(), n, c->b_stage.as<float>());
-   HIP_TRY(hipMemcpyAsync(A, c->b_stage.p, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream()));
-   finish_stream(c);
-   HS_API_END(c)
-}
-
-// normalizeAffine for caller-supplied keypoints: reuses the batch kernels through a
-// one-image plan whose Hessian list is filled from the arguments.
-int hesaff_stage_normalize_affine(hesaff_ctx *c, const float *img, int rows, int cols, int n, const float *kp, const float *A,
-                                  int32_t *rejected, float *patches)
-{
-   if (!c || !img || !kp || !A || rows < 2 || cols < 2 || n < 0) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   if (n == 0) return HESAFF_OK;
-   plan(c, 1, rows, cols);
-   if ((uint32_t)n > c->cap) throw HsError(HESAFF_ERR_CAPACITY, "too many keypoints for this image size");
-   Lists s = make_lists(c);
-   hipStream_t st = c->stream();
-   HIP_TRY(hipMemcpy2DAsync(c->gray.p, (size_t)c->gray.pitch * 4, img, (size_t)cols * 4, (size_t)cols * 4, rows, hipMemcpyHostToDevice, st));
-   std::vector<float> x(n), y(n), sc(n);
-   std::vector<int32_t> meta(n, 0), P0(n), alive(n);
-   for (int i = 0; i < n; i++) { x[i] = kp[3 * i]; y[i] = kp[3 * i + 1]; sc[i] = kp[3 * i + 2]; }
-   HIP_TRY(hipMemcpyAsync(s.hl.x, x.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-   HIP_TRY(hipMemcpyAsync(s.hl.y, y.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-   HIP_TRY(hipMemcpyAsync(s.hl.s, sc.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-   HIP_TRY(hipMemcpyAsync(s.hl.meta, meta.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-   // feed A through the affine-output slot as an already rectified matrix: k_prepare_patch
-   // would rectify again, so do its arithmetic (mrScale, P0, border test) via a dedicated kernel
-   HIP_TRY(hipMemcpyAsync(s.pw.A, A, (size_t)n * 16, hipMemcpyHostToDevice, st));
-   HIP_TRY(hipMemsetAsync(s.counters, 0, sizeof(CounterBlock), st));
-   uint32_t nn = (uint32_t)n;
-   HIP_TRY(hipMemcpyAsync(&s.counters->head.hess_total, &nn, 4, hipMemcpyHostToDevice, st));
-   hipLaunchKernelGGL(k_prepare_patch_given_A, dim3((n + 255) / 256), dim3(256), 0, st, s.hl, (const uint32_t *)&s.counters->head.hess_total, rows, cols,
-                      c->ct.consts, c->tables.view, s.pw);
-   c->b_patches.ensure((size_t)n * HS_PATCH_PIX * 4);
-   HIP_TRY(hipMemsetAsync(c->b_patches.p, 0, (size_t)n * HS_PATCH_PIX * 4, st));
-   // T' rows of the huge windows: bounded by the sum of their sides
-   const LargeRows lr = host_large_rows(sc.data(), n, c->ct.consts.mrSize, c->tables.view.max_p0);
-   c->batch_max_p = lr.max_p;
-   run_patch_stage(c, s, c->gray, c->b_patches.as<float>(), 0, lr.rows);
-   uint32_t ovf = 0;
-   HIP_TRY(hipMemcpyAsync(&ovf, &s.counters->head.row_overflow, 4, hipMemcpyDeviceToHost, st));
-   HIP_TRY(hipMemcpyAsync(alive.data(), s.pw.alive, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-   if (patches) HIP_TRY(hipMemcpyAsync(patches, c->b_patches.p, (size_t)n * HS_PATCH_PIX * 4, hipMemcpyDeviceToHost, st));
-   finish_stream(c);
-   if (ovf) throw HsError(HESAFF_ERR_NOMEM, "large-window row buffer exceeded (internal bound violated)");
-   if (rejected) for (int i = 0; i < n; i++) rejected[i] = alive[i] ? 0 : 1;
-   HS_API_END(c)
-}
-
-// hesaff_stage_sift and hesaff_stage_sift_parts: the production descriptor kernels on caller-supplied patches; meanvar / hist
-// (either may be null) additionally receive what k_sift_meanvar left in the stage buffer and the histogram k_sift_hist writes out
-// when it is given a place for it (SiftIO::vec; the pipeline passes none)
-// alive (may be null: every keypoint alive): the pipeline's flags; desc then goes to the device first (dead keypoints' rows stay)
-// desc_mode: the operator's own (stage operators do not read the context's modes)
-static int stage_sift(hesaff_ctx *c, int n, const float *patches, float *meanvar, float *hist, uint8_t *desc, const int32_t *alive = nullptr,
-                      int desc_mode = HESAFF_DESC_SIFT)
-{
-   if (!c || !patches || !desc || n < 0) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   if (n == 0) return HESAFF_OK;
-   const size_t N = (size_t)n;
-   // patches | alive flags | mean,var | histogram | descriptor bytes | (mask*grad, o) pairs
-   const size_t off_alive = N * HS_PATCH_PIX * 4, off_mv = off_alive + N * 4, off_vec = off_mv + N * 8, off_desc = off_vec + N * 128 * 4;
-   const size_t off_vo = (off_desc + N * 128 + 63) & ~(size_t)63, total = off_vo + N * HS_VO_PITCH * 8 + 64;
-   c->b_stage.ensure(total);
-   char *base = (char *)c->b_stage.p;
-   std::vector<int32_t> ones(N, 1);
-   HIP_TRY(hipMemcpyAsync(base, patches, N * HS_PATCH_PIX * 4, hipMemcpyHostToDevice, c->stream()));
-   HIP_TRY(hipMemcpyAsync(base + off_alive, alive ? alive : ones.data(), N * 4, hipMemcpyHostToDevice, c->stream()));
-   if (alive) HIP_TRY(hipMemcpyAsync(base + off_desc, desc, N * 128, hipMemcpyHostToDevice, c->stream()));
-   HIP_TRY(hipMemsetAsync(base + off_vo, 0, N * HS_VO_PITCH * 8 + 64, c->stream()));   // pairs outside the circular mask stay (0, 0)
-   SiftIO so;
-   so.patches = (const float *)base; so.alive = (const int32_t *)(base + off_alive); so.meanvar = (float *)(base + off_mv);
-   so.vec = hist ? (float *)(base + off_vec) : nullptr; so.desc = (uint8_t *)(base + off_desc); so.h_lo = 0; so.h_hi = (uint32_t)n;
-   launch_sift(c, c->stream(), so, (uint32_t)n, (float2 *)(base + off_vo), desc_mode);
-   if (meanvar) HIP_TRY(hipMemcpyAsync(meanvar, base + off_mv, N * 8, hipMemcpyDeviceToHost, c->stream()));
-   if (hist) HIP_TRY(hipMemcpyAsync(hist, base + off_vec, N * 128 * 4, hipMemcpyDeviceToHost, c->stream()));
-   HIP_TRY(hipMemcpyAsync(desc, base + off_desc, N * 128, hipMemcpyDeviceToHost, c->stream()));
-   finish_stream(c);
-   HS_API_END(c)
-}
-
-int hesaff_stage_sift(hesaff_ctx *c, int n, const float *patches, uint8_t *desc) { return stage_sift(c, n, patches, nullptr, nullptr, desc); }
-
-int hesaff_stage_sift_parts(hesaff_ctx *c, int n, const float *patches, float *meanvar, float *hist, uint8_t *desc)
-{
-   if (!meanvar || !hist) return HESAFF_ERR_ARG;
-   return stage_sift(c, n, patches, meanvar, hist, desc);
-}
-
-int hesaff_stage_sift_alive(hesaff_ctx *c, int n, const float *patches, const int32_t *alive, uint8_t *desc)
-{
-   if (!alive) return HESAFF_ERR_ARG;
-   return stage_sift(c, n, patches, nullptr, nullptr, desc, alive);
-}
-
-int hesaff_stage_sift_mode(hesaff_ctx *c, int n, const float *patches, const int32_t *alive, int mode, uint8_t *desc)
-{
-   if (mode != HESAFF_DESC_SIFT && mode != HESAFF_DESC_ROOTSIFT) return HESAFF_ERR_ARG;
-   return stage_sift(c, n, patches, nullptr, nullptr, desc, alive, mode);
-}
-
-// k_orientation (kernels_orient.h) on caller-supplied patches: every keypoint alive, no affine frame to turn
-int hesaff_stage_orientation(hesaff_ctx *c, int n, const float *patches, float *theta, float *hist, float *cs)
-{
-   if (!c || !patches || !theta || n < 0) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   if (n == 0) return HESAFF_OK;
-   const size_t N = (size_t)n;
-   // patches | theta | hist | (cos, sin)
-   const size_t off_theta = N * HS_PATCH_PIX * 4, off_hist = off_theta + N * 4, off_cs = off_hist + N * HS_ORI_BINS * 4, total = off_cs + N * 8;
-   c->b_stage.ensure(total);
-   char *base = (char *)c->b_stage.p;
-   HIP_TRY(hipMemcpyAsync(base, patches, N * HS_PATCH_PIX * 4, hipMemcpyHostToDevice, c->stream()));
-   OrientIO oi;
-   memset(&oi, 0, sizeof oi);
-   oi.patches = (const float *)base; oi.h_lo = 0; oi.h_hi = (uint32_t)n;
-   oi.theta = (float *)(base + off_theta); oi.hist = (float *)(base + off_hist); oi.cs = (float *)(base + off_cs);
-   hipLaunchKernelGGL(k_orientation, dim3(orientation_grid(c, (uint32_t)n)), dim3(64), 0, c->stream(), oi, c->tables.view);
-   HIP_TRY(hipMemcpyAsync(theta, base + off_theta, N * 4, hipMemcpyDeviceToHost, c->stream()));
-   if (hist) HIP_TRY(hipMemcpyAsync(hist, base + off_hist, N * HS_ORI_BINS * 4, hipMemcpyDeviceToHost, c->stream()));
-   if (cs) HIP_TRY(hipMemcpyAsync(cs, base + off_cs, N * 8, hipMemcpyDeviceToHost, c->stream()));
-   finish_stream(c);
-   HS_API_END(c)
-}
-
-// k_orientation_peaks on caller-supplied patches: every keypoint alive, no frame to turn, no rank arrays
-int hesaff_stage_orientation_peaks(hesaff_ctx *c, int n, const float *patches, int k, int32_t *n_ori, int32_t *bins, float *theta)
-{
-   if (!c || !patches || !n_ori || !bins || !theta || n < 0 || k < 1 || k > HS_ORI_MAX_COUNT) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   if (n == 0) return HESAFF_OK;
-   const size_t N = (size_t)n;
-   // patches | n_ori | bins | theta
-   const size_t off_n = N * HS_PATCH_PIX * 4, off_bins = off_n + N * 4, off_theta = off_bins + N * HS_ORI_MAX_COUNT * 4, total = off_theta + N * HS_ORI_MAX_COUNT * 4;
-   c->b_stage.ensure(total);
-   char *base = (char *)c->b_stage.p;
-   HIP_TRY(hipMemcpyAsync(base, patches, N * HS_PATCH_PIX * 4, hipMemcpyHostToDevice, c->stream()));
-   HIP_TRY(hipMemsetAsync(base + off_n, 0, total - off_n, c->stream()));
-   OrientIO oi;
-   memset(&oi, 0, sizeof oi);
-   oi.patches = (const float *)base; oi.h_lo = 0; oi.h_hi = (uint32_t)n;
-   OrientRanks mr;
-   memset(&mr, 0, sizeof mr);
-   mr.K = k; mr.n_ori = (int32_t *)(base + off_n); mr.bins = (int32_t *)(base + off_bins); mr.thetas = (float *)(base + off_theta);
-   hipLaunchKernelGGL(k_orientation_peaks, dim3(orientation_grid(c, (uint32_t)n)), dim3(64), 0, c->stream(), oi, c->tables.view, mr);
-   // (an orientation count below 4 leaves the ranks beyond it to the host: bin -1, angle 0)
-   HIP_TRY(hipMemcpyAsync(n_ori, base + off_n, N * 4, hipMemcpyDeviceToHost, c->stream()));
-   HIP_TRY(hipMemcpyAsync(bins, base + off_bins, N * HS_ORI_MAX_COUNT * 4, hipMemcpyDeviceToHost, c->stream()));
-   HIP_TRY(hipMemcpyAsync(theta, base + off_theta, N * HS_ORI_MAX_COUNT * 4, hipMemcpyDeviceToHost, c->stream()));
-   finish_stream(c);
-   for (size_t i = 0; i < N; i++)
-      for (int j = k; j < HS_ORI_MAX_COUNT; j++) { bins[i * HS_ORI_MAX_COUNT + j] = -1; theta[i * HS_ORI_MAX_COUNT + j] = 0.0f; }
-   HS_API_END(c)
-}
-
-// exportKeypoints on the device for caller-supplied records: the kernels hesaff_process_files runs per chunk
-int hesaff_stage_export(hesaff_ctx *c, const hesaff_keypoint *keys, int n, float mrSize, int format, char **out, size_t *len)
-{
-   if (!c || n < 0 || (n > 0 && !keys) || !out || !len || (format != HESAFF_OUT_TEXT && format != HESAFF_OUT_BIN)) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   const float saved = c->par.mrSize;
-   c->par.mrSize = mrSize;
-   char *buf = nullptr;
-   try {
-      const size_t N = (size_t)n;
-      c->b_stage.ensure(std::max<size_t>(N * sizeof(KeyRec), 16));
-      if (n > 0) HIP_TRY(hipMemcpyAsync(c->b_stage.p, keys, N * sizeof(KeyRec), hipMemcpyHostToDevice, c->stream()));
-      const KeyRec *d_keys = c->b_stage.as<KeyRec>();
-      char head[64];
-      size_t hl, body;
-      if (format == HESAFF_OUT_TEXT) {
-         const int32_t starts[2] = {0, n};
-         c->b_ex_starts.ensure(16);
-         HIP_TRY(hipMemcpyAsync(c->b_ex_starts.p, starts, sizeof starts, hipMemcpyHostToDevice, c->stream()));
-         std::vector<unsigned long long> off;
-         body = (size_t)export_text_prepare(c, d_keys, (uint32_t)n, c->b_ex_starts.as<int32_t>(), 1, off);
-         hl = (size_t)snprintf(head, sizeof head, "%d\n%d\n", 128, n);
-      } else {
-         body = N * EX_BIN_ROW;
-         memcpy(head, "HESAFFB1", 8);
-         const uint32_t dim = 128, cnt = (uint32_t)n;
-         memcpy(head + 8, &dim, 4); memcpy(head + 12, &cnt, 4);
-         hl = 16;
-      }
-      buf = (char *)malloc(hl + body + 1);
-      if (!buf) throw HsError(HESAFF_ERR_NOMEM, "malloc failed");
-      memcpy(buf, head, hl);
-      if (body > 0) {
-         c->b_generic.ensure(body + 16);
-         if (format == HESAFF_OUT_TEXT) export_text_write(c, d_keys, (uint32_t)n, (char *)c->b_generic.p);
-         else export_bin_rows(c, d_keys, (uint32_t)n, (char *)c->b_generic.p);
-         HIP_TRY(hipMemcpyAsync(buf + hl, c->b_generic.p, body, hipMemcpyDeviceToHost, c->stream()));
-      }
-      finish_stream(c);
-      *out = buf;
-      *len = hl + body;
-   } catch (...) {
-      c->par.mrSize = saved;
-      free(buf);
-      throw;
-   }
-   c->par.mrSize = saved;
-   HS_API_END(c)
-}
-
-int hesaff_stage_fmt_g(hesaff_ctx *c, int n, const float *v, char *text, int32_t *lens)
-{
-   if (!c || n < 0 || (n > 0 && (!v || !text || !lens))) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   if (n == 0) return HESAFF_OK;
-   const size_t N = (size_t)n;
-   c->b_stage.ensure(N * (4 + 16 + 4));
-   float *d_v = c->b_stage.as<float>();
-   int32_t *d_len = (int32_t *)(d_v + N);
-   char *d_text = (char *)(d_len + N);
-   HIP_TRY(hipMemcpyAsync(d_v, v, N * 4, hipMemcpyHostToDevice, c->stream()));
-   HIP_TRY(hipMemsetAsync(d_text, 0, N * 16, c->stream()));
-   hipLaunchKernelGGL(k_fmt_g_test, dim3((n + 255) / 256), dim3(256), 0, c->stream(), n, (const float *)d_v, d_text, d_len);
-   HIP_TRY(hipMemcpyAsync(text, d_text, N * 16, hipMemcpyDeviceToHost, c->stream()));
-   HIP_TRY(hipMemcpyAsync(lens, d_len, N * 4, hipMemcpyDeviceToHost, c->stream()));
-   finish_stream(c);
-   HS_API_END(c)
-}
-
-int hesaff_stage_jpeg_pixels(hesaff_ctx *c, const hesaff_jpeg_layout *layout, int n, const uint8_t *blobs, size_t blob_bytes, uint8_t *pixels)
-{
-   if (!c || !layout || n < 0 || (n > 0 && (!blobs || !pixels))) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   if (n == 0) return HESAFF_OK;
-   const JpegGeom g = make_jpeg_geom(*layout);
-   if ((size_t)g.blob_bytes != blob_bytes) throw HsError(HESAFF_ERR_ARG, "blob size does not match the layout");
-   const size_t img = (size_t)g.W * g.H * g.nc;
-   DevBuf &b_jcoef = c->slot[0].b_jcoef;   // (no chunk is on its way during a stage call)
-   b_jcoef.ensure(blob_bytes * (size_t)n);
-   c->b_stage.ensure(img * (size_t)n);
-   HIP_TRY(hipMemcpyAsync(b_jcoef.p, blobs, blob_bytes * (size_t)n, hipMemcpyHostToDevice, c->stream()));
-   jpeg_pixels(c, b_jcoef.as<uint8_t>(), g, n, c->b_stage.as<uint8_t>(), img, c->stream());
-   HIP_TRY(hipMemcpyAsync(pixels, c->b_stage.p, img * (size_t)n, hipMemcpyDeviceToHost, c->stream()));
-   finish_stream(c);
-   HS_API_END(c)
-}
-
-int hesaff_stage_math(hesaff_ctx *c, int n, const float *a, const float *b, float *atan2_out, float *pow2_out)
-{
-   if (!c || !a || !b || n < 0) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   if (n == 0) return HESAFF_OK;
-   c->b_stage.ensure((size_t)n * 16);
-   float *d_a = c->b_stage.as<float>(), *d_b = d_a + n, *d_at = d_b + n, *d_pw = d_at + n;
-   HIP_TRY(hipMemcpyAsync(d_a, a, (size_t)n * 4, hipMemcpyHostToDevice, c->stream()));
-   HIP_TRY(hipMemcpyAsync(d_b, b, (size_t)n * 4, hipMemcpyHostToDevice, c->stream()));
-   hipLaunchKernelGGL(k_math, dim3((n + 255) / 256), dim3(256), 0, c->stream(), n, (const float *)d_a, (const float *)d_b, d_at, d_pw);
-   if (atan2_out) HIP_TRY(hipMemcpyAsync(atan2_out, d_at, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream()));
-   if (pow2_out) HIP_TRY(hipMemcpyAsync(pow2_out, d_pw, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream()));
-   finish_stream(c);
-   HS_API_END(c)
-}
-
-int hesaff_stage_math_sift(hesaff_ctx *c, int n, const float *gy, const float *gx, float *ori_general, float *ori_nd, float *grad_general,
-                           float *grad_nd)
-{
-   if (!c || !gy || !gx || !ori_general || !ori_nd || !grad_general || !grad_nd || n < 0) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   if (n == 0) return HESAFF_OK;
-   c->b_stage.ensure((size_t)n * 24);
-   float *d = c->b_stage.as<float>();
-   HIP_TRY(hipMemcpyAsync(d, gy, (size_t)n * 4, hipMemcpyHostToDevice, c->stream()));
-   HIP_TRY(hipMemcpyAsync(d + n, gx, (size_t)n * 4, hipMemcpyHostToDevice, c->stream()));
-   hipLaunchKernelGGL(k_math_sift, dim3(std::min(4096, (n + 255) / 256)), dim3(256), 0, c->stream(), n, (const float *)d, (const float *)(d + n),
-                      d + 2 * (size_t)n, d + 3 * (size_t)n, d + 4 * (size_t)n, d + 5 * (size_t)n);
-   float *outs[4] = {ori_general, ori_nd, grad_general, grad_nd};
-   for (int q = 0; q < 4; q++) HIP_TRY(hipMemcpyAsync(outs[q], d + (2 + q) * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream()));
-   finish_stream(c);
-   HS_API_END(c)
-}
-
-int hesaff_stage_math_sift_general(hesaff_ctx *c, int n, const float *gy, const float *gx, float *ori, float *grad, float *coord)
-{
-   if (!c || !gy || !gx || !ori || !grad || !coord || n < 0) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   if (n == 0) return HESAFF_OK;
-   c->b_stage.ensure((size_t)n * 20);
-   float *d = c->b_stage.as<float>();
-   HIP_TRY(hipMemcpyAsync(d, gy, (size_t)n * 4, hipMemcpyHostToDevice, c->stream()));
-   HIP_TRY(hipMemcpyAsync(d + n, gx, (size_t)n * 4, hipMemcpyHostToDevice, c->stream()));
-   hipLaunchKernelGGL(k_math_sift_general, dim3(std::min(4096, (n + 255) / 256)), dim3(256), 0, c->stream(), n, (const float *)d,
-                      (const float *)(d + n), d + 2 * (size_t)n, d + 3 * (size_t)n, d + 4 * (size_t)n);
-   float *outs[3] = {ori, grad, coord};
-   for (int q = 0; q < 3; q++) HIP_TRY(hipMemcpyAsync(outs[q], d + (2 + q) * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream()));
-   finish_stream(c);
-   HS_API_END(c)
-}
-
 // ---------------------------------- visual words (kernels_words.h) ----------------------------------
 } // extern "C"
 namespace {
@@ -1655,23 +1083,6 @@ int hesaff_assign_words_device(hesaff_ctx *c, int64_t n, const void *d_desc, int
    need_vocabulary(c);
    bind_device(c);
    launch_assign_words(c, d_desc, (long long)n, (long long)stride, (long long)offset, d_words_out);
-   finish_stream(c);
-   HS_API_END(c)
-}
-
-int hesaff_stage_assign_words(hesaff_ctx *c, int n, const uint8_t *desc, int32_t *words_out)
-{
-   if (!c || n < 0 || (n > 0 && (!desc || !words_out))) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   need_vocabulary(c);
-   bind_device(c);
-   if (n == 0) return HESAFF_OK;
-   const size_t N = (size_t)n, off_out = (N * 128 + 255) & ~(size_t)255;
-   c->b_stage.ensure(off_out + N * 8);
-   char *base = (char *)c->b_stage.p;
-   HIP_TRY(hipMemcpyAsync(base, desc, N * 128, hipMemcpyHostToDevice, c->stream()));
-   launch_assign_words(c, base, n, 128, 0, base + off_out);
-   HIP_TRY(hipMemcpyAsync(words_out, base + off_out, N * 8, hipMemcpyDeviceToHost, c->stream()));
    finish_stream(c);
    HS_API_END(c)
 }

@@ -45,11 +45,7 @@ struct KpTables {   // device tables built on the host once per context
 //  LDS; three lanes add the 361 terms of a,b,c in index order; one lane runs the
 //  double-precision invSqrt and the U update; result broadcast through LDS.
 // ---------------------------------------------------------------------------------------
-struct AffineOut {
-   int32_t *converged;   // 1 = onAffineShapeFound was called
-   float *U;             // [n][4] a11,a12,a21,a22
-   int32_t *iters;
-};
+// (AffineOut: device_lists.h)
 
 // ---------------------------------------------------------------------------------------
 // hs_affine_groups: the same iteration with FOUR keypoints per wavefront (16 lanes each).
@@ -318,15 +314,7 @@ __global__ __launch_bounds__(64) void k_affine_stage(DPlane P, const float *__re
 // (HS_NBINS bins with HS_BIN3_PMAX as the last bound: plan_consts.h)
 __host__ __device__ inline int hs_patch_bin(int P) { return P <= 41 ? 0 : (P <= 64 ? 1 : (P <= 128 ? 2 : (P <= HS_BIN3_PMAX ? 3 : 4))); }
 
-struct PatchWork {
-   float *A;            // [n][4] rectified a11,a12,a21,a22
-   int32_t *P0;         // 2*int(mrScale)+1 ; 0 = dead before the patch stage
-   int32_t *alive;      // 1 while the keypoint is still a candidate for output
-   uint32_t *bin_count; // [HS_NBINS]
-   uint32_t *bin_work;  // [HS_NBINS] next unclaimed item of each bin's list (dynamic scheduling of the patch kernels)
-   uint32_t *bin_items; // [HS_NBINS][cap]
-   uint32_t cap;
-};
+// (PatchWork: device_lists.h)
 
 // window side of normalizeAffine's smoothing branch from the scale alone (affine.cpp:106-109,120): 0 when P0 is out of range
 __device__ __forceinline__ int hs_window_p0(float s, float mrSize)
@@ -433,18 +421,13 @@ __global__ __launch_bounds__(256) void k_prepare_patch_given_A(HessList hl, cons
 // k_pack: stable compaction of the described keypoints into hesaff_keypoint records
 // (hesaff.cpp:87-91), rank from the exclusive scan of `alive`.
 // ---------------------------------------------------------------------------------------
-struct KeyRec {   // == hesaff_keypoint (include/hesaff_amd.h), 164 bytes
-   float x, y, s, a11, a12, a21, a22, response;
-   int32_t type;
-   uint8_t desc[128];
-};
+// (KeyRec and HS_PACK_DW, the dwords of a record: device_lists.h)
 
 // A block takes 64 consecutive Hessian keypoints: their head fields come in as coalesced runs of the nine arrays, their descriptors as one
 // 8 KB run, the records are assembled in LDS in rank order - the ranks of a run's survivors are consecutive (stable compaction) - and leave as
 // ONE contiguous run of dwords.  (Round 4's form - 32 lanes per keypoint, lane 0 fetching nine fields from nine lines and storing nine
 // dwords - ran at 2.2 TB/s: 4.6 ms per 256 UHD images; profiles/r05_notes.md.)
 #define HS_PACK_KP 64
-#define HS_PACK_DW 41   // dwords per record
 __global__ __launch_bounds__(256) void k_pack(HessList hl, const uint32_t *__restrict__ n_ptr, PatchWork pw,
                                               const uint32_t *__restrict__ rank, const uint8_t *__restrict__ desc, KeyRec *__restrict__ out)
 {

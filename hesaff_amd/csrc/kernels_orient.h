@@ -33,23 +33,7 @@ struct OrientIO {
    float *theta, *hist, *cs;   // the stage entry point's outputs by h - h_lo (each may be null): theta, hist[36] after smoothing, (cos, sin)
 };
 
-// What the ranks j >= 1 of an orientation count K own, rank-major over the keypoint capacity: array[(j - 1) * cap + h].  Rank 0 lives in
-// the PatchWork arrays and b_desc, as the one orientation does.
-struct OrientRanks {
-   int K;              // the orientation count, 2..HS_ORI_MAX_COUNT
-   uint32_t cap;
-   float *A;           // [K - 1][cap][4] the turned frames
-   int32_t *P0;        // [K - 1][cap]
-   int32_t *alive;     // [K - 1][cap] behind k_orientation_peaks: rank < n_ori; behind the rank's k_prepare_patch_second: the rank has a key
-   uint8_t *desc;      // [K - 1][cap][128]
-   // the stage entry point's outputs by h - h_lo (null in the pipeline): n_ori, and per rank the bin (-1 beyond n_ori) and theta (0 beyond it)
-   int32_t *n_ori, *bins;
-   float *thetas;
-   __host__ __device__ float *A_of(int j) const { return A + (size_t)(j - 1) * cap * 4; }
-   __host__ __device__ int32_t *P0_of(int j) const { return P0 + (size_t)(j - 1) * cap; }
-   __host__ __device__ int32_t *alive_of(int j) const { return alive + (size_t)(j - 1) * cap; }
-   __host__ __device__ uint8_t *desc_of(int j) const { return desc + (size_t)(j - 1) * cap * 128; }
-};
+// (OrientRanks, what the ranks j >= 1 of an orientation count K own: device_lists.h)
 
 // One wavefront per keypoint, blocks persistent over the list.  The patch comes into LDS as coalesced runs; lanes 0..38 each
 // march one row (41 floats apart: an odd stride over the banks) and add into their own 36 bins; lanes 0..35 add the 39 rows of one

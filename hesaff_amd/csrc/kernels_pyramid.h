@@ -3,6 +3,7 @@
 // Reference: pyramid.cpp, helpers.cpp:283-295,331-339, hesaff.cpp:138-148.
 #pragma once
 #include "device_common.h"
+#include "device_lists.h"   // CandList, RecList, HessList and the other pointer bundles of the kernel headers behind this one
 
 // ---------------------------------------------------------------------------------------
 // k_gray_plane: the float grey plane alone - wherever the initial blur does not make it on the way (upscaleInputImage, a
@@ -268,25 +269,8 @@ __device__ __forceinline__ float hs_from_lane_above(float v)
    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x130 /* wave_shl:1 */, 0xf, 0xf, false));
 }
 
-// Candidates of one octave: findLevelKeypoints pyramid.cpp:206-222 appends (img,level,r,c) for every pixel that
-// passes isMax / isMin (:39-61); unordered here, the order is restored by the bitmask ranks in k_scatter_ordered.
-// A candidate carries the 19 response values localizeKeypoint's first iteration reads (pyramid.cpp:132-150): k_extrema_march has
-// them in registers when it finds the extremum, and 89 % of the candidates converge in that iteration - so k_localize reads one
-// 96-byte record per candidate instead of nine scattered cache lines of three response planes (33 M candidates per 256 UHD
-// images: 3 GB written + 3 GB read instead of 19-38 GB of line fetches).
-struct CandRec {
-   uint32_t id0, id1;   // img<<2 | level, r<<16 | c;  id0 == HS_CAND_HOLE: an unused slot of a wavefront's block of 64
-   float v[19];         // cur 3x3 row-major (rows r-1..r+1, columns c-1..c+1) | low: centre, left, right, up, down | high: the same five
-   uint32_t pad[3];
-};
+// (CandRec, CandList: device_lists.h)
 #define HS_CAND_HOLE 0xffffffffu
-// (HS_CAND_BLOCK, the slots a wavefront reserves at a time: plan_consts.h)
-struct CandList {
-   uint32_t *count;   // device counter (slots handed out, holes included)
-   CandRec *items;
-   uint32_t cap;
-   uint32_t *overflow;   // set to 1 when a list ran out of capacity
-};
 
 // ---------------------------------------------------------------------------------------
 // k_localize: localizeKeypoint pyramid.cpp:122-204 (without the order-dependent octaveMap
@@ -312,17 +296,7 @@ struct OctaveCtx {
    int words_per_row;
 };
 
-struct RecList {   // surviving localisations of the whole batch (unordered)
-   uint32_t *count;
-   uint32_t cap;
-   float *x, *y, *s, *response;
-   int32_t *meta;       // img<<8 | octave<<4 | level<<2 | type
-   uint32_t *cell;      // final pixel index rf*cols+cf inside the octave plane (for the map)
-   uint32_t *key;       // level*N + r0*cols + c0
-   long long *word;     // bitmask word index of (img,octave,level,r0,c0>>6)
-   uint32_t *bit;       // c0 & 63
-};
-
+// (RecList: device_lists.h)
 __global__ __launch_bounds__(256) void k_localize(OctaveCtx oc, CandList cl, RecList rl, DConsts k)
 {
    const uint32_t n = min(*cl.count, cl.cap);
@@ -597,17 +571,7 @@ __global__ __launch_bounds__(256) void k_scan_down(LOAD load, long long n, const
 // at its position in the reference's detection order (image, octave, level, raster of the
 // initial extremum).
 // ---------------------------------------------------------------------------------------
-struct HessList {   // ordered Hessian keypoints of the batch = onHessianKeypointDetected calls
-   float *x, *y, *s, *response;
-   int32_t *meta;    // img<<8 | octave<<4 | level<<2 | type
-   int32_t *r0c0;    // r0<<16 | c0 (provenance, for the stage API)
-   uint32_t cap;
-};
-
-// Two launches: the record goes to its rank as ONE 32-byte item (the six fields side by side) and a second, streaming kernel deals the items out to
-// the six arrays of the Hessian list.  Scattering the six fields themselves (rounds 1-4) was six partial-line stores per record, 33 M records per
-// 256 UHD images: 2.7 ms; a 32-byte store is one whole sector, and the second pass is coalesced on both sides.
-struct __attribute__((aligned(32))) HessItem { float x, y, s, response; int32_t meta, r0c0; uint32_t pad0, pad1; };
+// (HessList, and HessItem - the record at its rank as ONE 32-byte item, dealt out to the six arrays by a second kernel: device_lists.h)
 __global__ __launch_bounds__(256) void k_scatter_ordered(RecList rl, const unsigned long long *__restrict__ bitmask,
                                                          const uint32_t *__restrict__ prefix, HessItem *__restrict__ items, uint32_t cap)
 {

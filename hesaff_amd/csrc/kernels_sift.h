@@ -23,14 +23,7 @@
 #pragma once
 #include "kernels_patch.h"
 
-struct SiftIO {
-   const float *patches;     // [n][1681] (index = h - h_lo)
-   const int32_t *alive;     // [n] flags, indexed by h
-   float *meanvar;           // [n][2]
-   float *vec;               // [n][128] un-normalised histogram: the stage API's test hook, null in the pipeline (not written)
-   uint8_t *desc;            // [n][128] (index = h, absolute)
-   uint32_t h_lo, h_hi;
-};
+// (SiftIO: device_lists.h)
 
 // (HS_VO_DIM and the layout of a keypoint's gradient pairs in HBM - HS_VO_ITEMS, HS_VO_ZERO, HS_VO_PITCH: plan_consts.h)
 #define HS_VO_TILE (HS_VO_DIM * HS_VO_DIM)    // float2 of k_sift_grad's LDS tile (row-major 40 x 40)

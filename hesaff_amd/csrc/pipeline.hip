@@ -43,6 +43,7 @@
 #include "kernels_words.h"
 #include "chunk_engine.h"
 #include "batch_plan.h"
+#include "buffer_layouts.h"
 #include "context_tables.h"
 #include "group_schedule.h"
 
@@ -148,6 +149,7 @@ struct DevBuf {
       bytes = 0;
    }
    template <class T> T *as() const { return (T *)p; }
+   template <class T> T *at(size_t off) const { return (T *)((char *)p + off); }   // an array of a layout (buffer_layouts.h)
 };
 
 // A page-locked host block that only grows, owned like a DevBuf.  The three ways to ask differ in what a block that has to be
@@ -431,7 +433,7 @@ struct hesaff_ctx {
    int descriptor = HESAFF_DESC_SIFT;  // hesaff_set_descriptor: which instantiation of k_sift_hist the pipeline's launch_sift takes
    int orientation = HESAFF_ORI_UP;    // hesaff_set_orientation: HESAFF_ORI_DOMINANT runs the oriented order of group_schedule.h (run_keypoint_stages)
    int orientation_count = 1;          // hesaff_set_orientation_count: keys per region at most (read in HESAFF_ORI_DOMINANT only: ori_count)
-   DevBuf b_ori_ranks;                 // the rank arrays of an orientation count K > 1 (OrientRanks, kernels_orient.h): allocated by the first such call
+   DevBuf b_ori_ranks;                 // the rank arrays of an orientation count K > 1 (OrientRanks, device_lists.h): allocated by the first such call
    // hesaff_set_vocabulary: the vocabulary as k_assign_words reads it (kernels_words.h: XORed, padded to whole tiles, in lane order,
    // with |w'|^2 per row); k = 0: none, and nothing below is allocated, launched or copied
    struct Vocabulary { DevBuf tiles, norms; int k = 0, n_tiles = 0; } vocab;
@@ -597,14 +599,18 @@ void plan_buffers(hesaff_ctx *c, int B, int H, int W)
    c->b_counters.ensure(sizeof(CounterBlock));
    c->cand_cap = candidate_capacity(c->cap, B, PH, PW);
    c->geo.b_cand.ensure((size_t)c->cand_cap * sizeof(CandRec));
-   c->geo.b_rec_f.ensure(cap * 4 * 4);
-   c->geo.b_rec_i.ensure(cap * 4 * 4);
-   c->geo.b_rec_w.ensure(cap * 8);
-   c->geo.b_hess_f.ensure(cap * 4 * 4);
-   c->geo.b_hess_i.ensure(cap * 2 * 4);
-   c->geo.b_aff.ensure(cap * 6 * 4);
-   c->geo.b_pw.ensure(cap * 6 * 4);
-   c->geo.b_bins.ensure(cap * HS_NBINS * 4);
+   // the lists: sized here, cut into their arrays by make_lists - both from the layouts of buffer_layouts.h
+   const RecLayout rec = rec_layout(cap);
+   c->geo.b_rec_f.ensure(rec.f_bytes);
+   c->geo.b_rec_i.ensure(rec.i_bytes);
+   c->geo.b_rec_w.ensure(rec.w_bytes);
+   const HessLayout hess = hess_layout(cap);
+   c->geo.b_hess_f.ensure(hess.f_bytes);
+   c->geo.b_hess_i.ensure(hess.i_bytes);
+   c->geo.b_aff.ensure(affine_layout(cap).bytes);
+   const PatchLayout patch = patch_layout(cap);
+   c->geo.b_pw.ensure(patch.pw_bytes);
+   c->geo.b_bins.ensure(patch.bins_bytes);
    c->geo.b_rank.ensure((cap + 1) * 4);
    c->geo.b_desc.ensure(cap * 128);
    c->geo.b_out.ensure(cap * sizeof(KeyRec));
@@ -727,24 +733,22 @@ Lists make_lists(hesaff_ctx *c)
 {
    Lists s;
    CounterBlock *cnt = c->b_counters.as<CounterBlock>();
-   const size_t cap = c->cap;
+   const hesaff_ctx::GeomBufs &g = c->geo;
    s.counters = cnt;
-   s.cl.count = &cnt->head.cand; s.cl.items = c->geo.b_cand.as<CandRec>(); s.cl.cap = c->cand_cap; s.cl.overflow = &cnt->head.overflow;
+   s.cl.count = &cnt->head.cand; s.cl.items = g.b_cand.as<CandRec>(); s.cl.cap = c->cand_cap; s.cl.overflow = &cnt->head.overflow;
+   const RecLayout rec = rec_layout(c->cap);
    s.rl.count = &cnt->head.rec; s.rl.cap = c->cap;
-   float *rf = c->geo.b_rec_f.as<float>();
-   s.rl.x = rf; s.rl.y = rf + cap; s.rl.s = rf + 2 * cap; s.rl.response = rf + 3 * cap;
-   uint32_t *ri = c->geo.b_rec_i.as<uint32_t>();
-   s.rl.meta = (int32_t *)ri; s.rl.cell = ri + cap; s.rl.key = ri + 2 * cap; s.rl.bit = ri + 3 * cap;
-   s.rl.word = c->geo.b_rec_w.as<long long>();
-   float *hf = c->geo.b_hess_f.as<float>();
-   s.hl.x = hf; s.hl.y = hf + cap; s.hl.s = hf + 2 * cap; s.hl.response = hf + 3 * cap;
-   int32_t *hi = c->geo.b_hess_i.as<int32_t>();
-   s.hl.meta = hi; s.hl.r0c0 = hi + cap; s.hl.cap = c->cap;
-   int32_t *ai = c->geo.b_aff.as<int32_t>();
-   s.ao.converged = ai; s.ao.iters = ai + cap; s.ao.U = (float *)(ai + 2 * cap);
-   int32_t *pi = c->geo.b_pw.as<int32_t>();
-   s.pw.P0 = pi; s.pw.alive = pi + cap; s.pw.A = (float *)(pi + 2 * cap);
-   s.pw.bin_count = cnt->bin_count; s.pw.bin_work = cnt->bin_work; s.pw.bin_items = c->geo.b_bins.as<uint32_t>(); s.pw.cap = c->cap;
+   s.rl.x = g.b_rec_f.at<float>(rec.x); s.rl.y = g.b_rec_f.at<float>(rec.y); s.rl.s = g.b_rec_f.at<float>(rec.s); s.rl.response = g.b_rec_f.at<float>(rec.response);
+   s.rl.meta = g.b_rec_i.at<int32_t>(rec.meta); s.rl.cell = g.b_rec_i.at<uint32_t>(rec.cell); s.rl.key = g.b_rec_i.at<uint32_t>(rec.key);
+   s.rl.bit = g.b_rec_i.at<uint32_t>(rec.bit); s.rl.word = g.b_rec_w.at<long long>(rec.word);
+   const HessLayout hess = hess_layout(c->cap);
+   s.hl.x = g.b_hess_f.at<float>(hess.x); s.hl.y = g.b_hess_f.at<float>(hess.y); s.hl.s = g.b_hess_f.at<float>(hess.s); s.hl.response = g.b_hess_f.at<float>(hess.response);
+   s.hl.meta = g.b_hess_i.at<int32_t>(hess.meta); s.hl.r0c0 = g.b_hess_i.at<int32_t>(hess.r0c0); s.hl.cap = c->cap;
+   const AffineLayout aff = affine_layout(c->cap);
+   s.ao.converged = g.b_aff.at<int32_t>(aff.converged); s.ao.iters = g.b_aff.at<int32_t>(aff.iters); s.ao.U = g.b_aff.at<float>(aff.U);
+   const PatchLayout patch = patch_layout(c->cap);
+   s.pw.P0 = g.b_pw.at<int32_t>(patch.P0); s.pw.alive = g.b_pw.at<int32_t>(patch.alive); s.pw.A = g.b_pw.at<float>(patch.A);
+   s.pw.bin_count = cnt->bin_count; s.pw.bin_work = cnt->bin_work; s.pw.bin_items = g.b_bins.at<uint32_t>(patch.bin_items); s.pw.cap = c->cap;
    return s;
 }
 
@@ -845,19 +849,19 @@ uint32_t orientation_grid(const hesaff_ctx *c, uint32_t n) { return std::max<uin
 // The orientation count in force: hesaff_set_orientation_count's K in HESAFF_ORI_DOMINANT, 1 - the feature inert - in HESAFF_ORI_UP.
 int ori_count(const hesaff_ctx *c) { return c->orientation == HESAFF_ORI_DOMINANT ? c->orientation_count : 1; }
 
-// The rank arrays of K > 1 over the current keypoint capacity: frames, window sides, flags and descriptor rows of the ranks 1 .. K - 1,
-// 152 bytes per keypoint and rank.  ensure_rank_arrays allocates them (HESAFF_ERR_NOMEM when the device cannot hold them).
+// The rank arrays of K > 1 over the current keypoint capacity: frames, window sides, flags and descriptor rows of the ranks 1 .. K - 1
+// (rank_layout, buffer_layouts.h).  ensure_rank_arrays allocates them (HESAFF_ERR_NOMEM when the device cannot hold them).
 OrientRanks rank_arrays(const hesaff_ctx *c, int K)
 {
    OrientRanks r;
    memset(&r, 0, sizeof r);
-   const size_t n = (size_t)(K - 1) * c->cap;
-   char *base = (char *)c->b_ori_ranks.p;
+   const RankLayout L = rank_layout(K, c->cap);
+   const DevBuf &b = c->b_ori_ranks;
    r.K = K; r.cap = c->cap;
-   r.A = (float *)base; r.P0 = (int32_t *)(base + n * 16); r.alive = (int32_t *)(base + n * 20); r.desc = (uint8_t *)(base + n * 24);
+   r.A = b.at<float>(L.A); r.P0 = b.at<int32_t>(L.P0); r.alive = b.at<int32_t>(L.alive); r.desc = b.at<uint8_t>(L.desc);
    return r;
 }
-void ensure_rank_arrays(hesaff_ctx *c, int K) { c->b_ori_ranks.ensure(std::max<size_t>((size_t)(K - 1) * c->cap * 152, 16)); }
+void ensure_rank_arrays(hesaff_ctx *c, int K) { c->b_ori_ranks.ensure(std::max<size_t>(rank_layout(K, c->cap).bytes, 16)); }
 
 // per image: upper bound of the T' rows its huge windows (P > 512) need, known from the scales alone
 void launch_image_large_rows(hesaff_ctx *c, const Lists &s, int B)
@@ -869,7 +873,7 @@ void launch_image_large_rows(hesaff_ctx *c, const Lists &s, int B)
 }
 
 // The three steps of detection that follow the response planes.  run_detection calls them on the planes it has just made,
-// hesaff_stage_detect_planes (capi_impl.h) on the planes of its caller: one set of launches for both.
+// hesaff_stage_detect_planes (capi_stage.h) on the planes of its caller: one set of launches for both.
 // begin_detection: the counters, the bitmask and the order-key map before the first octave of a batch
 void begin_detection(hesaff_ctx *c, const Lists &s, int B)
 {
@@ -1109,12 +1113,13 @@ void ensure_group_buffers(hesaff_ctx *c, uint32_t n)
    // The patch buffers rotate over HS_NSLOT slots (the patch stage fills one while the descriptor stage reads the others).  The
    // descriptor stage's own intermediates - gradient pairs (10.4 KB per keypoint), mean / variance - live and die on its
    // one stream (the main stream with HESAFF_OVERLAP=0), so one copy of them serves every group.
-   for (int slot = 0; slot < HS_NSLOT; slot++) c->b_patches2[slot].ensure_grow((size_t)n * HS_PATCH_PIX * 4);
-   c->b_meanvar2.ensure_grow((size_t)n * 2 * 4);
+   const GroupScratch gs = group_scratch(n);   // (buffer_layouts.h: hesaff_stage_sift sizes its arrays with it too)
+   for (int slot = 0; slot < HS_NSLOT; slot++) c->b_patches2[slot].ensure_grow(gs.patch_floats * sizeof(float));
+   c->b_meanvar2.ensure_grow(gs.meanvar_floats * sizeof(float));
    // the (mask*grad, o) pairs of pixels outside the circular mask stay (0, 0): zero-fill on (re)allocation
    const void *before = c->b_siftvo2.p;
    const size_t bytes_before = c->b_siftvo2.bytes;
-   c->b_siftvo2.ensure_grow((size_t)n * HS_VO_PITCH * 8 + 64);
+   c->b_siftvo2.ensure_grow(gs.vo_floats * sizeof(float));
    if (c->b_siftvo2.p != before || c->b_siftvo2.bytes != bytes_before) HIP_TRY(hipMemsetAsync(c->b_siftvo2.p, 0, c->b_siftvo2.bytes, c->stream()));
 }
 
@@ -1234,7 +1239,7 @@ void assign_batch_words(hesaff_ctx *c, long long total)
    c->assign_timed = false;
    if (c->vocab.k == 0 || total <= 0) return;
    c->b_words.ensure_grow((size_t)total * 8);
-   launch_assign_words(c, c->geo.b_out.p, total, (long long)sizeof(KeyRec), 36, c->b_words.p);
+   launch_assign_words(c, c->geo.b_out.p, total, (long long)sizeof(KeyRec), (long long)offsetof(KeyRec, desc), c->b_words.p);
 }
 
 // Everything after the Hessian list of a batch is complete - by detection (run_batch) or from the caller's records (run_describe):
@@ -1505,3 +1510,4 @@ void pack_regions(hesaff_ctx *c, uint32_t n_hess, int B, hesaff_region *d_region
 
 } // namespace
 #include "capi_impl.h"
+#include "capi_stage.h"

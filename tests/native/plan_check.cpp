@@ -1,4 +1,4 @@
-// CPU check of the batch plan's host arithmetic (hesaff_amd/csrc/batch_plan.h; built and run by tests/test_batch_plan.py with
+// CPU check of the batch plan's host arithmetic (hesaff_amd/csrc/batch_plan.h, and the device buffers' layouts of buffer_layouts.h; built and run by tests/test_batch_plan.py with
 // g++ -fsanitize=address,undefined).  Three kinds of checks: properties that pin the behaviour without reference to the code under test
 // (what the kernels read and write, taken from kernels_patch.h / kernels_keypoint.h and stated at each check), a few values worked
 // out by hand, and the blur steps of an octave against the loops the step table replaced.  Prints "plan_check ok"; the first failed check prints a message and ends the program with exit code 1.
@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <random>
 #include "../../hesaff_amd/csrc/batch_plan.h"
+#include "../../hesaff_amd/csrc/buffer_layouts.h"
 #include "../../hesaff_amd/csrc/host_tables.h"
 
 using namespace hesaff_plan;
@@ -62,6 +63,153 @@ static void check_capacity()
    CHECK(code == HESAFF_ERR_ARG, "a request above 2e9 keypoints: code %d", code);
 }
 
+// ---- buffer_layouts.h: the carver, the lists of a context, the rank arrays, the descriptor scratch, the stage arenas ----
+// One array of a buffer as the kernels index it: bytes [at, at + len).
+struct Extent { const char *name; size_t at, len; };
+// every array inside [0, bytes), at a multiple of `align`, and no two of one buffer overlapping
+static void check_extents(const char *what, size_t size, const std::vector<Extent> &e, size_t bytes, size_t align)
+{
+   for (size_t i = 0; i < e.size(); i++) {
+      CHECK(e[i].at <= bytes && e[i].len <= bytes - e[i].at, "%s (%zu): %s [%zu, +%zu) leaves the buffer's %zu bytes", what, size, e[i].name, e[i].at, e[i].len, bytes);
+      CHECK(e[i].at % align == 0, "%s (%zu): %s at %zu is not %zu-byte aligned", what, size, e[i].name, e[i].at, align);
+      for (size_t j = i + 1; j < e.size(); j++)
+         CHECK(e[i].at + e[i].len <= e[j].at || e[j].at + e[j].len <= e[i].at, "%s (%zu): %s and %s overlap", what, size, e[i].name, e[j].name);
+   }
+}
+
+static int carver_error(size_t end, size_t count, size_t align)
+{
+   Carver c;
+   c.end = end;
+   try { (void)c.take<float>(count, align); }
+   catch (const HsError &e) { return e.code; }
+   return 0;
+}
+static void check_carver()
+{
+   Carver c;
+   CHECK(c.bytes() == 0 && c.take<uint8_t>(3) == 0 && c.bytes() == 3, "the first array starts at 0 and ends the carver");
+   CHECK(c.take<float>(5) == 4 && c.bytes() == 24, "a float behind 3 bytes: at 4, its natural alignment");
+   CHECK(c.take<float>(5, 256) == 256 && c.bytes() == 276, "an alignment request is honoured, bytes() is the end of the last array");
+   CHECK(c.take<double>(0, 64) == 320 && c.bytes() == 276 && c.take<uint8_t>(0) == 276 && c.bytes() == 276, "a zero-count take occupies nothing");
+   CHECK(c.take<uint8_t>(1) == 276 && c.bytes() == 277, "the array behind an empty one");
+   // an end beyond SIZE_MAX: the count, the padding, or both
+   CHECK(carver_error(0, SIZE_MAX / 4 + 1, 4) == HESAFF_ERR_ARG, "count * sizeof(T) wraps");
+   CHECK(carver_error(SIZE_MAX - 10, 4, 4) == HESAFF_ERR_ARG, "end + bytes wraps");
+   CHECK(carver_error(SIZE_MAX - 10, 0, 256) == HESAFF_ERR_ARG, "the padding wraps");
+   CHECK(carver_error(SIZE_MAX - 19, 4, 4) == 0, "an array that ends at SIZE_MAX - 3 fits");
+}
+
+// The lists of a context over a keypoint capacity.  Extents: what the kernels index with h, slot, r < cap (cap itself is what the lists carry:
+// RecList::cap, HessList::cap, PatchWork::cap).  Parent: the sizes plan_buffers wrote and the offsets make_lists wrote as literals before
+// the layouts existed (pipeline.hip of commit 2c74b82, the lines named at each value) - equality with them is "nothing moved".
+static void check_list_layouts(size_t cap)
+{
+   CHECK(cap % 64 == 0, "cap %zu: keypoint_capacity makes multiples of 64", cap);
+   const RecLayout r = rec_layout(cap);
+   // k_localize: rl.x[slot] .. rl.bit[slot], rl.word[slot] (long long), slot < rl.cap (kernels_pyramid.h:405-413)
+   check_extents("b_rec_f", cap, {{"x", r.x, cap * 4}, {"y", r.y, cap * 4}, {"s", r.s, cap * 4}, {"response", r.response, cap * 4}}, r.f_bytes, 16);
+   check_extents("b_rec_i", cap, {{"meta", r.meta, cap * 4}, {"cell", r.cell, cap * 4}, {"key", r.key, cap * 4}, {"bit", r.bit, cap * 4}}, r.i_bytes, 16);
+   check_extents("b_rec_w", cap, {{"word", r.word, cap * 8}}, r.w_bytes, 16);
+   CHECK(r.f_bytes == cap * 16, "b_rec_f %zu bytes", r.f_bytes);                                                            // :600  cap * 4 * 4
+   CHECK(r.i_bytes == cap * 16, "b_rec_i %zu bytes", r.i_bytes);                                                            // :601  cap * 4 * 4
+   CHECK(r.w_bytes == cap * 8, "b_rec_w %zu bytes", r.w_bytes);                                                             // :602  cap * 8
+   CHECK(r.x == 0 && r.y == cap * 4 && r.s == cap * 8 && r.response == cap * 12, "RecList floats moved");                   // :735  rf, rf + cap, rf + 2 * cap, rf + 3 * cap
+   CHECK(r.meta == 0 && r.cell == cap * 4 && r.key == cap * 8 && r.bit == cap * 12 && r.word == 0, "RecList integers moved");   // :737-738  ri, ri + cap, ri + 2 * cap, ri + 3 * cap; word alone
+
+   const HessLayout h = hess_layout(cap);
+   // k_hess_deal: hl.x[r] .. hl.r0c0[r], r < hl.cap (kernels_pyramid.h:597-598)
+   check_extents("b_hess_f", cap, {{"x", h.x, cap * 4}, {"y", h.y, cap * 4}, {"s", h.s, cap * 4}, {"response", h.response, cap * 4}}, h.f_bytes, 16);
+   check_extents("b_hess_i", cap, {{"meta", h.meta, cap * 4}, {"r0c0", h.r0c0, cap * 4}}, h.i_bytes, 16);
+   CHECK(h.f_bytes == cap * 16, "b_hess_f %zu bytes", h.f_bytes);                                                           // :603  cap * 4 * 4
+   CHECK(h.i_bytes == cap * 8, "b_hess_i %zu bytes", h.i_bytes);                                                            // :604  cap * 2 * 4
+   CHECK(h.x == 0 && h.y == cap * 4 && h.s == cap * 8 && h.response == cap * 12, "HessList floats moved");                  // :740  hf, hf + cap, hf + 2 * cap, hf + 3 * cap
+   CHECK(h.meta == 0 && h.r0c0 == cap * 4, "HessList integers moved");                                                      // :742  hi, hi + cap
+
+   const AffineLayout a = affine_layout(cap);
+   // hs_affine_groups: out.converged[h], out.iters[h], out.U[4 * h + 3], h < cap (kernels_keypoint.h:124-125, 264-266)
+   check_extents("b_aff", cap, {{"converged", a.converged, cap * 4}, {"iters", a.iters, cap * 4}, {"U", a.U, cap * 16}}, a.bytes, 16);
+   CHECK(a.bytes == cap * 24, "b_aff %zu bytes", a.bytes);                                                                  // :605  cap * 6 * 4
+   CHECK(a.converged == 0 && a.iters == cap * 4 && a.U == cap * 8, "AffineOut moved");                                      // :744  ai, ai + cap, ai + 2 * cap
+
+   const PatchLayout p = patch_layout(cap);
+   // hs_prepare_patch_body: pw.A[4 * h + 3], pw.alive[h], pw.P0[h], h < cap (kernels_keypoint.h:352, 366-367); the bins' lists
+   // pw.bin_items[bq * cap + base + ..] below bin_items[(HS_NBINS - 1) * cap + cap - 1] (kernels_keypoint.h:385, kernels_patch.h:936)
+   check_extents("b_pw", cap, {{"P0", p.P0, cap * 4}, {"alive", p.alive, cap * 4}, {"A", p.A, cap * 16}}, p.pw_bytes, 16);
+   check_extents("b_bins", cap, {{"bin_items", p.bin_items, ((size_t)(HS_NBINS - 1) * cap + cap - 1 + 1) * 4}}, p.bins_bytes, 16);
+   CHECK(p.pw_bytes == cap * 24, "b_pw %zu bytes", p.pw_bytes);                                                             // :606  cap * 6 * 4
+   CHECK(p.bins_bytes == cap * HS_NBINS * 4, "b_bins %zu bytes", p.bins_bytes);                                             // :607  cap * HS_NBINS * 4
+   CHECK(p.P0 == 0 && p.alive == cap * 4 && p.A == cap * 8 && p.bin_items == 0, "PatchWork moved");                         // :746-747  pi, pi + cap, pi + 2 * cap; b_bins whole
+}
+
+// The rank arrays of an orientation count K: OrientRanks' accessors reach rank K - 1, (K - 2) * cap entries in, and the kernels index a rank
+// with h < cap - A_of(j) + 4 * h as one float4 (kernels_orient.h:197), alive_of(j)[h] (:188), P0_of(j) as PatchWork::P0 of the rank's pass
+// (pipeline.hip: GroupDevice::lists), desc_of(j) + 128 * h as 32 words (:252) - so desc_of(K - 1) + cap * 128 is the end of the buffer.
+static void check_rank_layout(int K, size_t cap)
+{
+   const RankLayout L = rank_layout(K, cap);
+   const size_t n = (size_t)(K - 1) * cap, last = (size_t)(K - 2) * cap;
+   check_extents("b_ori_ranks", cap, {{"A", L.A, (last + cap) * 16}, {"P0", L.P0, (last + cap) * 4}, {"alive", L.alive, (last + cap) * 4}, {"desc", L.desc, (last + cap) * 128}}, L.bytes, 16);
+   CHECK(L.bytes == n * 152, "K %d cap %zu: %zu bytes", K, cap, L.bytes);                                                   // :860  (K - 1) * cap * 152
+   CHECK(L.A == 0 && L.P0 == n * 16 && L.alive == n * 20 && L.desc == n * 24, "K %d cap %zu: the rank arrays moved", K, cap);   // :857  base, base + n * 16, + n * 20, + n * 24
+}
+
+// The descriptor stage's scratch for n keypoints: k_sift_meanvar reads io.patches + kp * HS_PATCH_PIX, HS_PATCH_PIX floats (kernels_sift.h:65),
+// and writes io.meanvar[2 * kp + 1] (:86), kp < n; k_sift_grad writes HS_VO_ITEMS float4 = HS_VO_PITCH float2 at vo + k * HS_VO_PITCH (:199).
+static void check_group_scratch(uint32_t n)
+{
+   const GroupScratch g = group_scratch(n);
+   const size_t N = n;
+   CHECK(g.patch_floats * 4 >= ((N - 1) * HS_PATCH_PIX + HS_PATCH_PIX) * 4, "n %u: patches", n);
+   CHECK(g.meanvar_floats * 4 >= (2 * (N - 1) + 2) * 4, "n %u: mean / variance", n);
+   CHECK(g.vo_floats * 4 >= ((N - 1) * HS_VO_PITCH + HS_VO_PITCH) * 8, "n %u: gradient pairs", n);
+   CHECK(g.patch_floats * 4 == N * HS_PATCH_PIX * 4, "n %u: patches %zu floats", n, g.patch_floats);        // :1112  n * HS_PATCH_PIX * 4
+   CHECK(g.meanvar_floats * 4 == N * 2 * 4, "n %u: mean / variance %zu floats", n, g.meanvar_floats);        // :1113  n * 2 * 4
+   CHECK(g.vo_floats * 4 == N * HS_VO_PITCH * 8 + 64, "n %u: gradient pairs %zu floats", n, g.vo_floats);    // :1117  n * HS_VO_PITCH * 8 + 64
+}
+
+// The stage arenas (capi_stage.h: StageArena over StagePlan): the arrays every converted operator declares, restated here as {element
+// size, count} from what its kernel indexes, against the bytes the operator asked of the stage buffer before the arena (capi_impl.h of
+// commit 2c74b82): disjoint, 256-byte aligned, and at most 256 bytes per array more.  The plane operators run on 13 x 13.
+struct ArenaArray { size_t elem, count; };
+static void check_arena(const char *what, size_t n, const std::vector<ArenaArray> &arrays, size_t parent_bytes)
+{
+   StagePlan plan;
+   std::vector<Extent> e;
+   for (const ArenaArray &a : arrays) {
+      const size_t at = a.elem == 1 ? plan.add<uint8_t>(a.count).off : plan.add<float>(a.count).off;
+      CHECK(a.elem == 1 || a.elem == 4, "%s: element size %zu", what, a.elem);
+      e.push_back({what, at, a.elem * a.count});
+      CHECK(plan.bytes() == at + a.elem * a.count, "%s (%zu): bytes() is not the end of the last array", what, n);
+   }
+   check_extents(what, n, e, plan.bytes(), 256);
+   CHECK(plan.bytes() <= parent_bytes + 256 * arrays.size(), "%s (%zu): %zu bytes, %zu before the arena", what, n, plan.bytes(), parent_bytes);
+}
+static void check_stage_arenas(size_t N)
+{
+   const size_t rows = 13, cols = 13, px = rows * 64 /* pitch: round_up(13, 64) */, np = rows * cols, K = 9;
+   const size_t PIX = HS_PATCH_PIX, VO = HS_VO_PITCH;
+   check_arena("gaussian_blur", N, {{4, px}, {4, px}, {4, px}, {4, K}}, px * 4 * 3 + (K + 16) * 4);           // in | tmp | out | taps
+   check_arena("hessian_response", N, {{4, px}, {4, px}, {4, px}, {4, px}, {4, 9}}, px * 4 * 4 + 64);         // in | R0 | L1 | R1 | taps
+   check_arena("half_image", N, {{4, np}, {4, (rows / 2) * (cols / 2)}}, np * 4 * 2);                         // in | out (k_half: rows / 2 x cols / 2)
+   // k_affine_stage: the plane rows x cols tight, kp[4 * i + 3], converged[i], iters[i], U[4 * i + 3], i < n
+   check_arena("find_affine_shape", N, {{4, np}, {4, 4 * N}, {4, N}, {4, N}, {4, 4 * N}}, np * 4 + N * (4 + 6) * 4 + 64);
+   check_arena("rectify", N, {{4, 4 * N}}, N * 16);
+   // launch_sift on n patches: group_scratch's three arrays, the flags, the histogram SiftIO::vec[128 * k + 127], the descriptors desc[128 * k + 127]
+   const GroupScratch g = group_scratch((uint32_t)N);
+   check_arena("sift", N, {{4, g.patch_floats}, {4, N}, {4, g.meanvar_floats}, {4, 128 * N}, {1, 128 * N}, {4, g.vo_floats}},
+               ((N * PIX * 4 + N * 4 + N * 8 + N * 128 * 4 + N * 128 + 63) & ~(size_t)63) + N * VO * 8 + 64);
+   // k_orientation: patches, theta[k], hist[36 * k + 35], cs[2 * k + 1]; k_orientation_peaks: patches, n_ori[k], bins[4 * k + 3], thetas[4 * k + 3]
+   check_arena("orientation", N, {{4, N * PIX}, {4, N}, {4, 36 * N}, {4, 2 * N}}, N * PIX * 4 + N * 4 + N * 36 * 4 + N * 8);
+   check_arena("orientation_peaks", N, {{4, N * PIX}, {4, N}, {4, 4 * N}, {4, 4 * N}}, N * PIX * 4 + N * 4 + N * 4 * 4 + N * 4 * 4);
+   check_arena("fmt_g", N, {{4, N}, {4, N}, {1, 16 * N}}, N * (4 + 16 + 4));                                   // values | lengths | 16 characters each
+   check_arena("math", N, {{4, N}, {4, N}, {4, N}, {4, N}}, N * 16);
+   check_arena("math_sift", N, {{4, N}, {4, N}, {4, N}, {4, N}, {4, N}, {4, N}}, N * 24);
+   check_arena("math_sift_general", N, {{4, N}, {4, N}, {4, N}, {4, N}, {4, N}}, N * 20);
+   check_arena("assign_words", N, {{1, 128 * N}, {4, 2 * N}}, ((N * 128 + 255) & ~(size_t)255) + N * 8);       // descriptors | (word, dist2) per key
+   check_arena("check_device_f32", N, {{4, N}}, N * 4);                                                        // one flag per image
+}
+
 static void check_layouts()
 {
    const int Bs[4] = {1, 2, 64, 256};
@@ -83,6 +231,16 @@ static void check_layouts()
    }
    // (the counter block's words are pinned by the static_asserts of batch_plan.h)
    CHECK(describe_records_offset(1) == 256 && describe_records_offset(63) == 256 && describe_records_offset(64) == 512, "describe_records_offset");
+   check_carver();
+   const size_t caps[3] = {64, 4096, keypoint_capacity(256, 2160, 3840, 40000.0)};
+   for (size_t cap : caps) {
+      check_list_layouts(cap);
+      check_rank_layout(2, cap);
+      check_rank_layout(4, cap);
+   }
+   const uint32_t ns[4] = {1, 3, 65, 1200000};
+   for (uint32_t n : ns) check_group_scratch(n);
+   for (size_t n : {(size_t)1, (size_t)3, (size_t)65}) check_stage_arenas(n);
 }
 
 // the properties of form_groups' result; they determine the greedy result

@@ -129,6 +129,19 @@ def test_dead_keypoints_write_nothing(ctx, dead):
 
 
 @gpu
+@pytest.mark.parametrize("n", [1, 3, 65])
+def test_dead_keypoints_write_nothing_at_odd_counts(ctx, n):
+    """The nine patches repeated to n keypoints, every third dead from the second on (n = 1: none): counts at which the operator's
+    arrays - patches, flags, descriptors, gradient pairs - are multiples of nothing.  The same reference, the same comparison."""
+    p, d, _ = nine()
+    idx = np.arange(n) % 9
+    alive = np.ones(n, np.int32); alive[1::3] = 0
+    got = ctx.sift_alive(p[idx], alive, fill=0xAB)
+    want = d[idx].copy(); want[alive == 0] = 0xAB
+    assert np.array_equal(got, want), np.flatnonzero((got != want).any(axis=1)).tolist()
+
+
+@gpu
 def test_clipped_next_to_unclipped_in_every_order(ctx):
     """A wavefront renormalises when any of its four keypoints clipped; the others must come out untouched by it.  All 16 patterns of
     clipped / unclipped over a group of four, and the all-zero vector at each position among clipped ones."""

@@ -166,11 +166,23 @@ def test_affine_shape_stage(ctx, oracle):
     sel = np.where((i[:, 1] == 0) & (i[:, 2] == 1))[0]
     assert len(sel) > 50
     blur = o.plane(0, 0, 1)
-    conv, Ug, it = ctx.find_affine_shape(blur, f[sel][:, :4])
-    assert np.array_equal(conv, ci[sel, 0])
-    ok = conv == 1
-    assert np.array_equal(it[ok], ci[sel, 1][ok])
-    assert_bit_equal(Ug[ok], U[sel][ok], "U")
+    # all of them, then 1, 3 and 65 from the first that converges on: the operator's arrays (plane, keypoints, flags, iterations, U) lie
+    # at sizes that are multiples of nothing
+    lo = int(np.flatnonzero(ci[sel, 0] == 1)[0])
+    for part in (sel, sel[lo:lo + 1], sel[lo:lo + 3], sel[lo:lo + 65]):
+        conv, Ug, it = ctx.find_affine_shape(blur, f[part][:, :4])
+        assert np.array_equal(conv, ci[part, 0]), len(part)
+        ok = conv == 1
+        assert ok.any()
+        assert np.array_equal(it[ok], ci[part, 1][ok]), len(part)
+        assert_bit_equal(Ug[ok], U[part][ok], "U of %d keypoints" % len(part))
+    # one keypoint on a 13 x 13 plane, the smallest an octave can be: five iterations to convergence in the reference
+    small = np.ascontiguousarray(blur[120:133, 40:53])
+    want_conv, want_U, want_it = oracle.OracleHandle().find_affine_shape(small, 6.3, 6.2, 0.4, 1.0)
+    assert want_conv == 1 and want_it == 5
+    conv, Ug, it = ctx.find_affine_shape(small, np.array([[6.3, 6.2, 0.4, 1.0]], np.float32))
+    assert conv.tolist() == [1] and it.tolist() == [want_it]
+    assert_bit_equal(Ug[0], want_U, "U on the 13 x 13 plane")
 
 
 def test_normalize_affine_and_sift_stage(ctx, oracle):

@@ -85,27 +85,29 @@ def oracle_patches(oracle, name, limit):
     return np.stack(out)
 
 
-def check_stage(ctx, oracle, patches, what):
-    theta, hist, cs = ctx.orientation_of(patches, parts=True)
-    assert np.array_equal(_u32(ctx.orientation_of(patches)), _u32(theta))
-    flats = []
-    for k in range(len(patches)):
-        t, h, (c, s), flat = R.estimate(oracle, patches[k])
-        assert np.array_equal(_u32(hist[k]), _u32(h)), "%s: histogram of patch %d" % (what, k)
-        assert _u32(theta[k:k + 1])[0] == _u32(np.array([t], np.float32))[0], "%s: theta of patch %d: %r, reference %r" % (what, k, theta[k], t)
-        assert _u32(cs[k])[0] == _u32(np.array([c], np.float32))[0] and _u32(cs[k])[1] == _u32(np.array([s], np.float32))[0], \
-            "%s: (cos, sin) of patch %d: %r, reference %r" % (what, k, cs[k], (c, s))
-        flats.append(flat)
-    return theta, hist, cs, np.array(flats)
+def check_stage(ctx, oracle, patches, what, counts=()):
+    """counts: the operator on the first n patches alone as well, for every n of it, against the same reference"""
+    want = [R.estimate(oracle, p) for p in patches]
+    for n in tuple(counts) + (len(patches),):
+        theta, hist, cs = ctx.orientation_of(patches[:n], parts=True)
+        assert np.array_equal(_u32(ctx.orientation_of(patches[:n])), _u32(theta))
+        for k in range(n):
+            t, h, (c, s), flat = want[k]
+            assert np.array_equal(_u32(hist[k]), _u32(h)), "%s, first %d: histogram of patch %d" % (what, n, k)
+            assert _u32(theta[k:k + 1])[0] == _u32(np.array([t], np.float32))[0], "%s, first %d: theta of patch %d: %r, reference %r" % (what, n, k, theta[k], t)
+            assert _u32(cs[k])[0] == _u32(np.array([c], np.float32))[0] and _u32(cs[k])[1] == _u32(np.array([s], np.float32))[0], \
+                "%s, first %d: (cos, sin) of patch %d: %r, reference %r" % (what, n, k, cs[k], (c, s))
+    return theta, hist, cs, np.array([w[3] for w in want])
 
 
 @pytest.mark.gpu
 def test_stage_on_oracle_patches(ctx, oracle):
     """hesaff_stage_orientation on 100 patches normalizeAffine made on band_160x120: theta, the smoothed histogram, cos and sin are
-    the reference's bits.  The property `orientation`, called, is the same operator."""
+    the reference's bits - and of the first 1, 3 and 65 of them alone, sizes at which the operator's arrays are multiples of nothing.
+    The property `orientation`, called, is the same operator."""
     patches = oracle_patches(oracle, "band_160x120", 100)
     assert len(patches) == 100
-    theta, _, _, flats = check_stage(ctx, oracle, patches, "oracle patches")
+    theta, _, _, flats = check_stage(ctx, oracle, patches, "oracle patches", counts=(1, 3, 65))
     assert not flats.any() and len(np.unique(theta)) > 90 and theta.min() < -2.0 and theta.max() > 2.0
     assert ctx.orientation == ORI_UP   # the operator neither needs nor changes the mode
     assert np.array_equal(_u32(ctx.orientation(patches[:3])), _u32(theta[:3]))

@@ -66,23 +66,26 @@ def key_ranks(ranks):
 
 # ---------------------------------------------------------------- the stage operator
 
-def check_stage(ctx, oracle, patches, K, what):
-    n_ori, bins, theta = ctx.orientation_peaks_of(patches, K)
+def check_stage(ctx, oracle, patches, K, what, counts=()):
+    """counts: the operator on the first n patches alone as well, for every n of it, against the same reference"""
     want = [P.peaks_of(oracle, p, K) for p in patches]
-    for k, (wn, wb, wt) in enumerate(want):
-        assert n_ori[k] == wn, "%s, K = %d: n_ori of patch %d: %d, reference %d" % (what, K, k, n_ori[k], wn)
-        assert bins[k].tolist() == wb.tolist(), "%s, K = %d: bins of patch %d: %s, reference %s" % (what, K, k, bins[k], wb)
-        assert np.array_equal(_u32(theta[k]), _u32(wt)), "%s, K = %d: thetas of patch %d: %s, reference %s" % (what, K, k, theta[k], wt)
+    for n in tuple(counts) + (len(patches),):
+        n_ori, bins, theta = ctx.orientation_peaks_of(patches[:n], K)
+        for k, (wn, wb, wt) in enumerate(want[:n]):
+            assert n_ori[k] == wn, "%s, K = %d, first %d: n_ori of patch %d: %d, reference %d" % (what, K, n, k, n_ori[k], wn)
+            assert bins[k].tolist() == wb.tolist(), "%s, K = %d, first %d: bins of patch %d: %s, reference %s" % (what, K, n, k, bins[k], wb)
+            assert np.array_equal(_u32(theta[k]), _u32(wt)), "%s, K = %d, first %d: thetas of patch %d: %s, reference %s" % (what, K, n, k, theta[k], wt)
     return np.array([w[0] for w in want]), np.stack([w[1] for w in want]), theta
 
 
 @pytest.mark.gpu
 def test_stage_on_oracle_patches(ctx, oracle):
     """hesaff_stage_orientation_peaks on 100 patches normalizeAffine made on band_160x120: n_ori, the bins and the angles of every
-    rank are the numpy rule's, for K = 4 and K = 2; rank 0's angle is hesaff_stage_orientation's.  The reference shows every n_ori."""
+    rank are the numpy rule's, for K = 4 and K = 2 - at K = 4 of the first 1, 3 and 65 patches alone too, sizes at which the operator's
+    arrays are multiples of nothing; rank 0's angle is hesaff_stage_orientation's.  The reference shows every n_ori."""
     patches = oracle_patches(oracle, "band_160x120", 100)
     assert len(patches) == 100
-    n_ori, bins, theta = check_stage(ctx, oracle, patches, 4, "oracle patches")
+    n_ori, bins, theta = check_stage(ctx, oracle, patches, 4, "oracle patches", counts=(1, 3, 65))
     census = collections.Counter(n_ori.tolist())
     print("n_ori over 100 oracle patches: %s" % sorted(census.items()))
     assert set(census) == {1, 2, 3, 4}, census

@@ -75,7 +75,7 @@ def e2e(vctx):
 @pytest.mark.gpu
 @pytest.mark.parametrize("family", V.FAMILIES)
 def test_stage_key_counts(vctx, family):
-    """n in {0, 1, 31, 32, 33, 64, 65, 257} against K in {33, 4099}: the tails of a key tile, of a wavefront's 64 keys and of a block's
+    """n in {0, 1, 3, 31, 32, 33, 64, 65, 257} against K in {33, 4099}: the tails of a key tile, of a wavefront's 64 keys and of a block's
     256, one word tile with a tail and 129 of them"""
     for K in (33, 4099):
         vocab = V.family(family, K, seed=100 + K)
@@ -83,7 +83,7 @@ def test_stage_key_counts(vctx, family):
         want = reference(desc, vocab, ("counts", family, K))
         vctx.set_vocabulary(vocab)
         assert vctx.vocabulary_size == K
-        for n in (0, 1, 31, 32, 33, 64, 65, 257):
+        for n in (0, 1, 3, 31, 32, 33, 64, 65, 257):
             _same_rows(vctx.assign_words(desc[:n]), want[:n], "%s, K = %d, n = %d" % (family, K, n))
 
 

@@ -251,6 +251,11 @@ def load_library():
         L.hesaff_write_words.argtypes = [C.c_char_p, vp, vp, C.c_int, C.c_float, C.c_int]
         L.hesaff_read_vocabulary.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int)]
         L.hesaff_write_vocabulary.argtypes = [C.c_char_p, vp, C.c_int]
+    if hasattr(L, "hesaff_train_vocabulary"):   # (likewise)
+        L.hesaff_train_vocabulary_device.argtypes = [vp, C.c_int64, vp, C.c_int64, C.c_int64, C.c_int, vp, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
+        L.hesaff_train_vocabulary.argtypes = [vp, C.c_int64, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
+        L.hesaff_stage_accumulate_words.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp]
+        L.hesaff_get_training_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.hesaff_stage_math_sift_general.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math_sift.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]
@@ -295,6 +300,7 @@ ABI_SYMBOLS = [
     "hesaff_set_vocabulary", "hesaff_get_vocabulary_size", "hesaff_get_words", "hesaff_get_words_device",
     "hesaff_assign_words_device", "hesaff_stage_assign_words", "hesaff_get_assign_ms", "hesaff_write_words",
     "hesaff_read_vocabulary", "hesaff_write_vocabulary",
+    "hesaff_train_vocabulary", "hesaff_train_vocabulary_device", "hesaff_stage_accumulate_words", "hesaff_get_training_ms",
 ]
 
 # hesaff_set_output_format's bits
@@ -965,6 +971,58 @@ class HesaffContext:
         ms = C.c_float()
         self._check(self.L.hesaff_get_assign_ms(self.h, C.byref(ms)))
         return ms.value
+
+    # ---- vocabulary training (hesaff_train_vocabulary, include/hesaff_amd.h) ----
+    def _train(self, call, k, iterations, init):
+        k, iterations = int(k), int(iterations)
+        if init is not None:
+            init = _vocabulary_array(init)
+            if init.shape[0] != k:
+                raise ValueError("init has %d rows, k is %d" % (init.shape[0], k))
+        words = np.zeros((max(k, 0), 128), np.uint8)
+        distortion = np.zeros(max(iterations, 0), np.int64)
+        empty = np.zeros(max(iterations, 0), np.int32)
+        done = C.c_int(0)
+        self._check(call(k, init.ctypes.data if init is not None else None, iterations, words.ctypes.data, distortion.ctypes.data,
+                         empty.ctypes.data, C.byref(done)))
+        return words, distortion[:done.value].copy(), empty[:done.value].copy()
+
+    def train_vocabulary(self, desc, k, iterations, init=None):
+        """hesaff_train_vocabulary: exact integer k-means over desc uint8 [n, 128] -> (words uint8 [k, 128], distortion int64 [done],
+        empty int32 [done]); done <= iterations is the number of iterations that ran (fewer: a fixed point was reached).  init: the
+        initial vocabulary uint8 [k, 128], or None for row r = desc[r * n // k].  The context's own vocabulary is not touched."""
+        if not isinstance(desc, np.ndarray) or desc.dtype != np.uint8 or desc.ndim != 2 or desc.shape[1] != 128:
+            raise ValueError("descriptors are a uint8 array of shape [n, 128]")
+        desc = np.ascontiguousarray(desc)
+        n = desc.shape[0]
+        return self._train(lambda *a: self.L.hesaff_train_vocabulary(self.h, n, desc.ctypes.data if n else None, *a), k, iterations, init)
+
+    def train_vocabulary_device(self, ptr, n, stride, offset, k, iterations, init=None):
+        """hesaff_train_vocabulary_device: the same on n descriptors in device memory, descriptor i at ptr + i * stride + offset
+        (164 / 36: a key array; 128 / 0: a packed tensor; a raw device pointer)."""
+        return self._train(lambda *a: self.L.hesaff_train_vocabulary_device(self.h, int(n), C.c_void_p(ptr), int(stride), int(offset), *a),
+                           k, iterations, init)
+
+    def accumulate_words(self, desc, words, k):
+        """hesaff_stage_accumulate_words: desc uint8 [n, 128], words int32 [n] in 0 .. k - 1 -> (sums uint32 [k, 128], counts uint32 [k])."""
+        desc = np.ascontiguousarray(desc, dtype=np.uint8)
+        words = np.ascontiguousarray(words, dtype=np.int32)
+        if desc.ndim != 2 or desc.shape[1] != 128 or words.shape != (desc.shape[0],):
+            raise ValueError("descriptors are uint8 [n, 128], words int32 [n]")
+        k = int(k)
+        sums = np.zeros((max(k, 0), 128), np.uint32)
+        counts = np.zeros(max(k, 0), np.uint32)
+        n = desc.shape[0]
+        self._check(self.L.hesaff_stage_accumulate_words(self.h, n, desc.ctypes.data if n else None, words.ctypes.data if n else None, k,
+                                                         sums.ctypes.data, counts.ctypes.data))
+        return sums, counts
+
+    @property
+    def training_ms(self):
+        """HIP-event times (assignment, accumulation, update) of the last training call, summed over its iterations (profiling >= 1), in ms"""
+        a, b, u = C.c_float(), C.c_float(), C.c_float()
+        self._check(self.L.hesaff_get_training_ms(self.h, C.byref(a), C.byref(b), C.byref(u)))
+        return a.value, b.value, u.value
 
     def process_files(self, paths, out_paths=None, decode_threads=0, write_threads=0):
         """hesaff_process_files: image files -> <name>.hesaff.sift through the decode / device / write pipeline.

@@ -170,6 +170,27 @@ struct AffineHessianDetector {
          throw std::runtime_error("cannot write '" + path + "'");
    }
 
+   // No counterpart in the reference (hesaff_train_vocabulary, include/hesaff_amd.h): exact integer k-means on the device over n
+   // descriptors of 128 bytes - the initial rows are desc[floor(r n / k)], at most `iterations` Lloyd iterations with the mean rounded
+   // half up, fewer when a fixed point is reached.  -> the k rows; distortion() and emptyWords() then hold one entry per iteration
+   // that ran.  The detector's own vocabulary does not change: install the result with setVocabulary.
+   std::vector<uint8_t> trainVocabulary(const uint8_t *desc, int n, int k, int iterations)
+   {
+      std::vector<uint8_t> rows((size_t)(k > 0 ? k : 0) * 128);
+      distortion_.assign((size_t)(iterations > 0 ? iterations : 0), 0);
+      empty_.assign(distortion_.size(), 0);
+      int done = 0;
+      const int rc = hesaff_train_vocabulary(ctx_, n, desc, k, nullptr, iterations, rows.data(), distortion_.data(), empty_.data(), &done);
+      if (rc != HESAFF_OK) { distortion_.clear(); empty_.clear(); }
+      if (rc == HESAFF_ERR_ARG) throw std::invalid_argument("training needs 1 <= k <= 2^20 rows, k <= n <= 2^24 descriptors and iterations >= 1");
+      if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+      distortion_.resize((size_t)done);
+      empty_.resize((size_t)done);
+      return rows;
+   }
+   const std::vector<int64_t> &distortion() const { return distortion_; }   // of the last trainVocabulary: distortion()[t] belongs to V_t
+   const std::vector<int32_t> &emptyWords() const { return empty_; }
+
    // No counterpart in the reference (hesaff_set_next_masks, include/hesaff_amd.h; OpenCV's detect(image, keypoints, mask)): the NEXT
    // detectPyramidKeypoints keeps only the Hessian keypoints on a non-zero pixel of `mask` - height x width 8-bit pixels at the size of
    // the image as passed, rows strideBytes apart (0: tightly packed), pixel (row, col) = (clamp((int)(y + 0.5f)), clamp((int)(x +
@@ -343,6 +364,8 @@ struct AffineHessianDetector {
    HessianKeypointCallback *hessianKeypointCallback_ = nullptr;
    AffineShapeCallback *affineShapeCallback_ = nullptr;
    std::vector<int32_t> words_;      // setVocabulary: (word, dist2) per key
+   std::vector<int64_t> distortion_; // trainVocabulary: per iteration that ran
+   std::vector<int32_t> empty_;
    const uint8_t *mask_ = nullptr;   // setMask
    int maskStride_ = 0;
 };

@@ -46,6 +46,12 @@
 //       squared distance to its descriptor on the device (hesaff_set_vocabulary), and <image>.hesaff.words (hesaff_write_words: x, y, a, b,
 //       c and the word per key) is written beside the .hesaff.sift.  With --batch the same for every image of the list; --words-only
 //       then writes the words files alone.  A vocabulary file that cannot be read ends the run before any image is read.
+//   hesaff --batch <list file> --train-vocabulary <vocabulary file> --words K [--iterations T]
+//       trains a vocabulary on the list's own descriptors (hesaff_train_vocabulary: exact integer k-means on the device, T = 10 iterations at
+//       most, fewer at a fixed point; the initial rows are keys spread evenly over the list's keys in list order).  Detection runs on one device
+//       with the run's other options (--descriptor, --orientation, --orientations, --max-keypoints, --grid, --fast); no per-image file is
+//       written, <vocabulary file> is, and one line per iteration is printed: the distortion and the number of empty words.  At most 2^24
+//       keys: a list that yields more stops with a message naming the count.
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -242,6 +248,107 @@ int run_batch_mode(const char *list_path, const char *devices_spec, int out_form
    return rc;
 }
 
+// hesaff --batch <list> --train-vocabulary <file> --words K: detect over the list on one device, keep every key's descriptor bytes in host
+// memory in list order (a hesaff_detect_batch_cb sink), train K words on them (hesaff_train_vocabulary) and write the vocabulary file.
+struct DescSink {
+   std::vector<std::vector<uint8_t>> *per_image;
+   int first;   // list index of the block's first image
+   static int take(void *user, int n_images, const int *image_index, const hesaff_result *results)
+   {
+      DescSink *s = (DescSink *)user;
+      for (int i = 0; i < n_images; i++) {
+         std::vector<uint8_t> &d = (*s->per_image)[(size_t)(s->first + image_index[i])];
+         d.resize((size_t)results[i].count_desc * 128);
+         for (int q = 0; q < results[i].count_desc; q++) memcpy(d.data() + (size_t)q * 128, results[i].keys[q].desc, 128);
+      }
+      return 0;
+   }
+};
+
+int run_train_mode(const char *list_path, const char *devices_spec, const char *out_path, int k, int iterations, int fast, int max_keypoints, int orientation,
+                   int grid_rows, int grid_cols, int descriptor, int orientations)
+{
+   std::ifstream lf(list_path);
+   if (!lf) { fprintf(stderr, "hesaff: cannot read list '%s'\n", list_path); return 1; }
+   std::vector<std::string> names;
+   for (std::string line; std::getline(lf, line);) {
+      while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+      if (!line.empty() && line[0] != '#') names.push_back(line);
+   }
+   std::vector<int> devices;
+   if (!parse_devices(devices_spec ? devices_spec : "0", devices)) {
+      fprintf(stderr, "hesaff: bad --devices '%s' (%d device(s) visible)\n", devices_spec ? devices_spec : "0", hesaff_device_count());
+      return 1;
+   }
+   const int n = (int)names.size(), kBlock = 64;
+   hesaff_params par;
+   hesaff_default_params(&par);
+   par.max_batch = std::max(1, std::min(n, kBlock));
+   par.fast = fast;
+   hesaff_ctx *ctx = nullptr;
+   if (hesaff_create(&ctx, &par, devices[0]) != HESAFF_OK) { fprintf(stderr, "hesaff: device %d: %s\n", devices[0], hesaff_last_error(nullptr)); return 1; }
+   struct Destroy { hesaff_ctx *c; ~Destroy() { hesaff_destroy(c); } } destroy{ctx};
+   hesaff_set_keypoint_limit(ctx, max_keypoints);
+   hesaff_set_keypoint_grid(ctx, grid_rows, grid_cols);
+   hesaff_set_orientation(ctx, orientation);
+   hesaff_set_orientation_count(ctx, orientations);
+   hesaff_set_descriptor(ctx, descriptor);
+   std::vector<std::vector<uint8_t>> per_image((size_t)n);
+   long long total = 0;
+   int rc = 0;
+   for (int lo = 0; lo < n; lo += kBlock) {
+      const int hi = std::min(n, lo + kBlock);
+      std::vector<uint8_t *> data;
+      std::vector<const uint8_t *> images;
+      std::vector<int> widths, heights, strides, channels, index;
+      for (int i = lo; i < hi; i++) {
+         uint8_t *px = nullptr;
+         int w = 0, h = 0, ch = 0;
+         if (hesaff_read_image(names[(size_t)i].c_str(), &px, &w, &h, &ch) != HESAFF_OK) {
+            fprintf(stderr, "hesaff: cannot read '%s' (PBM / PGM / PPM, PNG, JPEG, BMP or baseline TIFF expected): skipped\n", names[(size_t)i].c_str());
+            rc = 1;
+            continue;
+         }
+         data.push_back(px); images.push_back(px); widths.push_back(w); heights.push_back(h); strides.push_back(w * ch); channels.push_back(ch);
+         index.push_back(i);
+      }
+      // (the sink sees positions in this block's arrays: unreadable files leave gaps in the list, so the block's images are re-indexed)
+      std::vector<std::vector<uint8_t>> block(images.size());
+      DescSink sink{&block, 0};
+      const int drc = hesaff_detect_batch_cb(ctx, (int)images.size(), images.data(), widths.data(), heights.data(), strides.data(), channels.data(), DescSink::take, &sink);
+      for (uint8_t *px : data) hesaff_free(px);
+      if (drc != HESAFF_OK) { fprintf(stderr, "hesaff: %s\n", hesaff_last_error(ctx)); return 1; }
+      for (size_t j = 0; j < block.size(); j++) {
+         total += (long long)(block[j].size() / 128);
+         per_image[(size_t)index[j]] = std::move(block[j]);
+      }
+      if (total > (1ll << 24)) {
+         fprintf(stderr, "hesaff: the list yields more than 2^24 keys (%lld after %d of %d images): train on fewer images, or set --max-keypoints\n", total, hi, n);
+         return 1;
+      }
+   }
+   if (total < k) { fprintf(stderr, "hesaff: the list yields %lld keys, fewer than --words %d\n", total, k); return 1; }
+   std::vector<uint8_t> desc;
+   desc.reserve((size_t)total * 128);
+   for (std::vector<uint8_t> &d : per_image) {
+      desc.insert(desc.end(), d.begin(), d.end());
+      std::vector<uint8_t>().swap(d);
+   }
+   std::vector<uint8_t> rows((size_t)k * 128);
+   std::vector<int64_t> distortion((size_t)iterations);
+   std::vector<int32_t> empty((size_t)iterations);
+   int done = 0;
+   if (hesaff_train_vocabulary(ctx, total, desc.data(), k, nullptr, iterations, rows.data(), distortion.data(), empty.data(), &done) != HESAFF_OK) {
+      fprintf(stderr, "hesaff: training failed: %s\n", hesaff_last_error(ctx));
+      return 1;
+   }
+   if (hesaff_write_vocabulary(out_path, rows.data(), k) != HESAFF_OK) { fprintf(stderr, "hesaff: cannot write '%s'\n", out_path); return 1; }
+   for (int t = 0; t < done; t++) std::cout << "iteration " << t + 1 << ": distortion " << distortion[(size_t)t] << ", " << empty[(size_t)t] << " empty words" << std::endl;
+   std::cout << "Trained " << k << " words on " << total << " keys of " << n << " images in " << done << " iterations"
+             << (done < iterations ? " (fixed point)" : "") << std::endl;
+   return rc;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -259,8 +366,8 @@ int main(int argc, char **argv)
       const char *devices = nullptr, *list = nullptr;
       int out_format = HESAFF_OUT_TEXT, fast = 0, host_share = 1, runtime_nice = -1, max_keypoints = 0, orientation = HESAFF_ORI_UP, grid_rows = 1, grid_cols = 1, descriptor = HESAFF_DESC_SIFT, orientations = 1;
       bool bad = false, grid = false, dynamic = false, words_only = false;
-      const char *vocabulary_path = nullptr;
-      int resume = 0;
+      const char *vocabulary_path = nullptr, *train_path = nullptr;
+      int resume = 0, train_words = 0, train_iterations = 10;
       for (int i = 1; i < argc && !bad; i += 2) {
          if (strcmp(argv[i], "--resume") == 0) { resume = 1; i--; continue; }
          if (strcmp(argv[i], "--resume=strict") == 0) { resume = 2; i--; continue; }   // also count the rows of existing text outputs
@@ -269,6 +376,14 @@ int main(int argc, char **argv)
          else if (strcmp(argv[i], "--batch") == 0) list = argv[i + 1];
          else if (strcmp(argv[i], "--devices") == 0) devices = argv[i + 1];
          else if (strcmp(argv[i], "--vocabulary") == 0) vocabulary_path = argv[i + 1];
+         else if (strcmp(argv[i], "--train-vocabulary") == 0) train_path = argv[i + 1];
+         else if (strcmp(argv[i], "--words") == 0 || strcmp(argv[i], "--iterations") == 0) {
+            // digits only, at least 1: K up to 2^20 rows, T up to a million iterations
+            char *end = nullptr;
+            const long v = strtol(argv[i + 1], &end, 10);
+            if (argv[i + 1][0] < '0' || argv[i + 1][0] > '9' || *end != 0 || v < 1 || v > (1L << 20)) bad = true;
+            else (argv[i][2] == 'w' ? train_words : train_iterations) = (int)v;
+         }
          else if (strcmp(argv[i], "--host-share") == 0) { host_share = atoi(argv[i + 1]); bad = host_share < 1 || host_share > 1024; }
          else if (strcmp(argv[i], "--runtime-nice") == 0) { runtime_nice = atoi(argv[i + 1]); bad = runtime_nice < 0 || runtime_nice > 1; }
          else if (strcmp(argv[i], "--max-keypoints") == 0) {
@@ -313,7 +428,12 @@ int main(int argc, char **argv)
       // a grid divides a budget: without --max-keypoints, or with more cells than keypoints, there is nothing to divide
       if (grid && (max_keypoints < 1 || grid_rows * grid_cols > max_keypoints)) bad = true;
       if (words_only && !vocabulary_path) bad = true;
-      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--vocabulary <vocabulary file> [--words-only]] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1] [--max-keypoints N] [--orientations 1..4] [--descriptor sift|rootsift] [--orientation up|dominant] [--grid RxC]\n"); return 1; }
+      // training takes the list's keys and writes one vocabulary file: it needs --words, and nothing that is about per-image files
+      if (train_path && (train_words < 1 || vocabulary_path || words_only || resume || dynamic || out_format != HESAFF_OUT_TEXT)) bad = true;
+      if (!train_path && (train_words > 0 || train_iterations != 10)) bad = true;
+      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--vocabulary <vocabulary file> [--words-only]] [--train-vocabulary <vocabulary file> --words K [--iterations T]] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1] [--max-keypoints N] [--orientations 1..4] [--descriptor sift|rootsift] [--orientation up|dominant] [--grid RxC]\n"); return 1; }
+      if (train_path)
+         return run_train_mode(list, devices, train_path, train_words, train_iterations, fast, max_keypoints, orientation, grid_rows, grid_cols, descriptor, orientations);
       uint8_t *vocabulary = nullptr;
       int vocabulary_size = 0;
       if (vocabulary_path) {   // before any image is read

@@ -41,11 +41,13 @@
 #include "kernels_export.h"
 #include "kernels_jpeg.h"
 #include "kernels_words.h"
+#include "kernels_train.h"
 #include "chunk_engine.h"
 #include "batch_plan.h"
 #include "buffer_layouts.h"
 #include "context_tables.h"
 #include "group_schedule.h"
+#include "train_plan.h"
 
 static thread_local std::string g_create_error;
 
@@ -442,6 +444,7 @@ struct hesaff_ctx {
    std::vector<hesaff_engine::WordSpan> word_spans;   // hesaff_get_words: per image of the last host call, its rows in the call's result blocks
    DevEvent ev_assign[2];              // profiling: brackets of the last k_assign_words launch
    bool assign_timed = false;          // ev_assign holds a launch of the last batch
+   float train_ms[3] = {0.0f, 0.0f, 0.0f};   // hesaff_get_training_ms: assignment, accumulation, update of the last training call (profiling >= 1)
    ArmedMasks next_masks;              // hesaff_set_next_masks / _device: the masks of the next detecting call (taken, so cleared, by take_masks)
    int stage_threads = 4;              // host threads that copy a chunk's pixels into pinned memory (hesaff_process_files: within its thread budget)
    DevEvent ev_detect_done, ev_batch_done;   // blocking-sync events: the host sleeps instead of spinning
@@ -629,12 +632,12 @@ void plan_buffers(hesaff_ctx *c, int B, int H, int W)
    c->B = B; c->H = H; c->W = W;
 }
 
-template <class LOAD> void exclusive_scan(hesaff_ctx *c, LOAD load, long long n, uint32_t *out, uint32_t *total)
+template <class LOAD> void exclusive_scan(hesaff_ctx *c, LOAD load, long long n, uint32_t *out, uint32_t *total, uint32_t *block_sums = nullptr)
 {
-   // out[0..n) exclusive prefix, *total = sum (device pointers)
+   // out[0..n) exclusive prefix, *total = sum (device pointers); block_sums: one word per SCAN_BLOCK items (default: the plan's)
    if (n <= 0) { HIP_TRY(hipMemsetAsync(total, 0, 4, c->stream())); return; }
    const int nb = (int)((n + SCAN_BLOCK - 1) / SCAN_BLOCK);
-   uint32_t *bs = c->geo.b_blocksums.as<uint32_t>();
+   uint32_t *bs = block_sums ? block_sums : c->geo.b_blocksums.as<uint32_t>();
    hipLaunchKernelGGL(k_scan_reduce<LOAD>, dim3(nb), dim3(256), 0, c->stream(), load, n, bs);
    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, c->stream(), bs, nb, total);
    hipLaunchKernelGGL(k_scan_down<LOAD>, dim3(nb), dim3(256), 0, c->stream(), load, n, bs, out);
@@ -1217,6 +1220,15 @@ struct GroupDevice : ScheduleDevice {
    }
 };
 
+// k_assign_words against a packed vocabulary of n_tiles tiles (the context's, or the private one of a training call), n >= 1
+void launch_assign_kernel(hipStream_t st, const void *tiles, const void *norms, int n_tiles, const void *d_desc, long long n, long long stride, long long offset,
+                          void *d_out)
+{
+   const long long blocks = (n + HS_WORD_BLOCK_KEYS - 1) / HS_WORD_BLOCK_KEYS;
+   hipLaunchKernelGGL(k_assign_words, dim3((uint32_t)blocks), dim3(HS_WORD_BLOCK_WAVES * 64), 0, st, (const uint8_t *)d_desc, n, stride, offset,
+                      (const hs_v4i *)tiles, (const int32_t *)norms, n_tiles, (int32_t *)d_out);
+}
+
 // k_assign_words (kernels_words.h) over n descriptors in device memory, on the main stream: (word, dist2) per key into d_out.
 // With profiling on, the launch is bracketed for hesaff_get_assign_ms.
 void launch_assign_words(hesaff_ctx *c, const void *d_desc, long long n, long long stride, long long offset, void *d_out)
@@ -1227,9 +1239,7 @@ void launch_assign_words(hesaff_ctx *c, const void *d_desc, long long n, long lo
    const bool timed = c->profiling >= 1;
    if (timed && !c->ev_assign[0]) { c->ev_assign[0] = DevEvent(hipEventDefault); c->ev_assign[1] = DevEvent(hipEventDefault); }
    if (timed) HIP_TRY(hipEventRecord(c->ev_assign[0], st));
-   const long long blocks = (n + HS_WORD_BLOCK_KEYS - 1) / HS_WORD_BLOCK_KEYS;
-   hipLaunchKernelGGL(k_assign_words, dim3((uint32_t)blocks), dim3(HS_WORD_BLOCK_WAVES * 64), 0, st, (const uint8_t *)d_desc, n, stride, offset,
-                      (const hs_v4i *)c->vocab.tiles.p, (const int32_t *)c->vocab.norms.p, c->vocab.n_tiles, (int32_t *)d_out);
+   launch_assign_kernel(st, c->vocab.tiles.p, c->vocab.norms.p, c->vocab.n_tiles, d_desc, n, stride, offset, d_out);
    if (timed) { HIP_TRY(hipEventRecord(c->ev_assign[1], st)); c->assign_timed = true; }
 }
 
@@ -1511,3 +1521,4 @@ void pack_regions(hesaff_ctx *c, uint32_t n_hess, int B, hesaff_region *d_region
 } // namespace
 #include "capi_impl.h"
 #include "capi_stage.h"
+#include "capi_train.h"

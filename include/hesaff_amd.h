@@ -51,6 +51,8 @@ extern "C" {
  *    And for hesaff_set_orientation_count / hesaff_get_orientation_count / hesaff_stage_orientation_peaks (secondary orientation peaks):
  *    symbols only, version 8.  With a count above 1, hesaff_region.reserved carries the number of a region's keys.
  *    And for visual-word assignment (hesaff_set_vocabulary and the ten symbols declared with it, HESAFF_OUT_WORDS): symbols only, version 8.
+ *    And for vocabulary training (hesaff_train_vocabulary, hesaff_train_vocabulary_device, hesaff_stage_accumulate_words,
+ *    hesaff_get_training_ms): symbols only, version 8.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -563,6 +565,45 @@ int hesaff_write_words(const char *path, const hesaff_keypoint *keys, const int3
  * file (magic, dim, count outside 1 .. 2^20, size other than 16 + 128 count). */
 int hesaff_read_vocabulary(const char *path, uint8_t **words, int *k);
 int hesaff_write_vocabulary(const char *path, const uint8_t *words, int k);
+
+/* Vocabulary training (no counterpart in the reference): exact integer k-means on the device, which produces the vocabulary that
+ * hesaff_set_vocabulary consumes.  Inputs: n descriptors d_i of 128 unsigned bytes, 1 <= n <= 2^24; K rows, 1 <= K <= 2^20; T >= 1
+ * iterations; an initial vocabulary V_0 of K rows (`init`), or init == NULL: row k of V_0 is d_floor(k n / K), the product in 64 bits,
+ * which needs n >= K.  Iteration t = 1 .. T:
+ *     (word_i, dist2_i) = hesaff_set_vocabulary's assignment under V_{t-1}: the lowest row of least squared distance
+ *     count[k]          = #{i : word_i = k}
+ *     sum[k][j]         = sum of d_i[j] over the keys with word_i = k
+ *     distortion[t-1]   = sum_i dist2_i                                   (int64)
+ *     empty[t-1]        = #{k : count[k] = 0}
+ *     V_t[k][j]         = (2 sum[k][j] + count[k]) / (2 count[k])         integer division in 64 bits: the mean rounded half up
+ *     V_t[k]            = V_{t-1}[k] where count[k] = 0: an empty word keeps its row, nothing is reseeded
+ *     V_t == V_{t-1} byte for byte: stop, iterations_done = t.  Otherwise iterations_done = T.
+ * Output: V_{iterations_done}, and distortion[] / empty[] for the iterations that ran.  distortion[t-1] belongs to V_{t-1}; the
+ * distortion of the returned vocabulary itself is not computed.
+ * No floating point, no dependence on launch geometry or on the order of accumulation: every call with the same inputs returns the
+ * same bytes.  The rounded mean is the integer row that minimises a word's squared error over its keys, and the assignment minimises
+ * every key's distance over the rows, so distortion[t] <= distortion[t-1], always.
+ * n <= 2^24 so that a sum fits uint32 (2^24 * 255 < 2^32); a call beyond that is refused before anything is read.
+ * hesaff_train_vocabulary_device: descriptors in device memory, addressed as in hesaff_assign_words_device (stride 164, offset 36: a
+ * hesaff_keypoint array; stride 128, offset 0: a packed tensor).  init: K x 128 host bytes or NULL; words_out: K x 128 host bytes;
+ * distortion: int64_t[iterations], empty: int32_t[iterations], iterations_done: each may be NULL.
+ * hesaff_train_vocabulary: the same for desc[n][128] in host memory.
+ * Training neither reads nor changes the context's own vocabulary (it works on a private one, in device memory it allocates for the
+ * call and releases before it returns); a caller installs the result with hesaff_set_vocabulary.
+ * hesaff_stage_accumulate_words: the accumulation kernels alone - words[n] are the caller's words in 0 .. k - 1, sums_out is
+ * uint32_t[k][128], counts_out uint32_t[k].
+ * hesaff_get_training_ms: the HIP-event times of the last training call at profiling level >= 1, summed over its iterations:
+ * assignment, accumulation (grouping the keys by word and summing), update.  0 otherwise.
+ * HESAFF_ERR_ARG, nothing changed, the context usable as before: ctx NULL; the descriptors or words_out NULL; n < 1 or n > 2^24;
+ * k < 1 or k > 2^20; iterations < 1; init NULL with n < k; stride, offset or the device pointer outside the rules of
+ * hesaff_assign_words_device; in the stage operator a NULL array or a word outside 0 .. k - 1 (checked on the host); a getter's out
+ * pointer NULL.  HESAFF_ERR_NOMEM: the device cannot hold the working arrays (n = 2^24, K = 2^20: about 1 GB beside the descriptors). */
+int hesaff_train_vocabulary_device(hesaff_ctx *ctx, int64_t n, const void *d_desc, int64_t stride, int64_t offset, int k, const uint8_t *init,
+                                   int iterations, uint8_t *words_out, int64_t *distortion, int32_t *empty, int *iterations_done);
+int hesaff_train_vocabulary(hesaff_ctx *ctx, int64_t n, const uint8_t *desc, int k, const uint8_t *init, int iterations, uint8_t *words_out,
+                            int64_t *distortion, int32_t *empty, int *iterations_done);
+int hesaff_stage_accumulate_words(hesaff_ctx *ctx, int n, const uint8_t *desc, const int32_t *words, int k, uint32_t *sums_out, uint32_t *counts_out);
+int hesaff_get_training_ms(const hesaff_ctx *ctx, float *assign_ms, float *accumulate_ms, float *update_ms);
 
 /* Same path with inputs already resident in device memory (bench / pipelines that decode
  * on the GPU): d_gray = n contiguous height x width 8-bit grey planes (device pointer).

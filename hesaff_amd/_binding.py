@@ -256,6 +256,17 @@ def load_library():
         L.hesaff_train_vocabulary.argtypes = [vp, C.c_int64, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
         L.hesaff_stage_accumulate_words.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp]
         L.hesaff_get_training_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    if hasattr(L, "hesaff_index_build"):   # (likewise)
+        L.hesaff_index_build.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int]
+        L.hesaff_index_build_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int]
+        L.hesaff_index_query.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int)]
+        L.hesaff_index_query_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int)]
+        L.hesaff_index_get_scores.argtypes = [vp, vp, vp, vp]
+        L.hesaff_index_get_tables.argtypes = [vp, vp, vp, vp]
+        L.hesaff_index_get_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.hesaff_index_clear.argtypes = [vp]
+        L.hesaff_get_index_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.hesaff_read_words.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.hesaff_stage_math_sift_general.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math_sift.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]
@@ -301,6 +312,8 @@ ABI_SYMBOLS = [
     "hesaff_assign_words_device", "hesaff_stage_assign_words", "hesaff_get_assign_ms", "hesaff_write_words",
     "hesaff_read_vocabulary", "hesaff_write_vocabulary",
     "hesaff_train_vocabulary", "hesaff_train_vocabulary_device", "hesaff_stage_accumulate_words", "hesaff_get_training_ms",
+    "hesaff_index_build", "hesaff_index_build_device", "hesaff_index_query", "hesaff_index_query_device", "hesaff_index_get_scores",
+    "hesaff_index_get_tables", "hesaff_index_get_info", "hesaff_index_clear", "hesaff_get_index_ms", "hesaff_read_words",
 ]
 
 # hesaff_set_output_format's bits
@@ -519,6 +532,20 @@ def read_words(path):
     if len(body) != n * WORDS_ROW_DTYPE.itemsize:
         raise HesaffError(-4, "%s is truncated" % path)
     return vocabulary_size, np.frombuffer(body, dtype=WORDS_ROW_DTYPE).copy()
+
+
+def _index_words(w):
+    """an image's (or a query's) words for the index: int32 [n] or (word, dist2) rows [n, 2], C-contiguous"""
+    if not isinstance(w, np.ndarray) or w.dtype != np.int32 or not (w.ndim == 1 or (w.ndim == 2 and w.shape[1] == 2)):
+        raise ValueError("words are an int32 array of shape [n] or [n, 2]")
+    return np.ascontiguousarray(w)
+
+
+def _index_stride(arrays):
+    kinds = {a.ndim for a in arrays}
+    if len(kinds) > 1:
+        raise ValueError("the word arrays are all [n] or all [n, 2]")
+    return 2 if kinds == {2} else 1
 
 
 def read_image(path):
@@ -1023,6 +1050,78 @@ class HesaffContext:
         a, b, u = C.c_float(), C.c_float(), C.c_float()
         self._check(self.L.hesaff_get_training_ms(self.h, C.byref(a), C.byref(b), C.byref(u)))
         return a.value, b.value, u.value
+
+    # ---- image index (hesaff_index_build, include/hesaff_amd.h) ----
+    def build_index(self, images, vocabulary_size):
+        """hesaff_index_build: images is a list with, per image, an int32 array of words [n] or of (word, dist2) rows [n, 2] (what
+        words(i) returns), all of one kind; vocabulary_size is K.  Replaces the context's index."""
+        arrays = [_index_words(w) for w in images]
+        stride = _index_stride(arrays)
+        counts = np.array([len(a) for a in arrays], np.int32)
+        flat = np.ascontiguousarray(np.concatenate(arrays) if arrays else np.zeros((0,), np.int32))
+        self._check(self.L.hesaff_index_build(self.h, len(arrays), counts.ctypes.data, flat.ctypes.data if flat.size else None, stride, int(vocabulary_size)))
+
+    def build_index_device(self, ptr, counts, word_stride, vocabulary_size):
+        """hesaff_index_build_device: the words of all images one after the other in device memory (a raw pointer; key j's word is the
+        int32 at ptr + 4 j word_stride), counts the keys per image (host)."""
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        self._check(self.L.hesaff_index_build_device(self.h, len(counts), counts.ctypes.data, C.c_void_p(ptr), int(word_stride), int(vocabulary_size)))
+
+    def _query(self, call, top):
+        top = int(top)
+        images = np.zeros(max(min(top, 1024), 1), np.int32)
+        scores = np.zeros(len(images), np.float64)
+        n = C.c_int(0)
+        self._check(call(top, images.ctypes.data, scores.ctypes.data, C.byref(n)))
+        return images[:n.value].copy(), scores[:n.value].copy()
+
+    def query_index(self, words, top):
+        """hesaff_index_query: words int32 [n] or [n, 2] -> (images int32 [min(top, N)], scores float64), best first, ties by index."""
+        w = _index_words(words)
+        stride = _index_stride([w])
+        return self._query(lambda *a: self.L.hesaff_index_query(self.h, len(w), w.ctypes.data if len(w) else None, stride, *a), top)
+
+    def query_index_device(self, ptr, n, word_stride, top):
+        """hesaff_index_query_device: the same on n words in device memory (a raw pointer)."""
+        return self._query(lambda *a: self.L.hesaff_index_query_device(self.h, int(n), C.c_void_p(ptr), int(word_stride), *a), top)
+
+    @property
+    def index_info(self):
+        """hesaff_index_get_info: (n_images, vocabulary_size, n_keys, n_postings), or None when no index is built"""
+        n, k, t, p = C.c_int(), C.c_int(), C.c_int64(), C.c_int64()
+        if self.L.hesaff_index_get_info(self.h, C.byref(n), C.byref(k), C.byref(t), C.byref(p)) != 0:
+            return None
+        return n.value, k.value, t.value, p.value
+
+    def _need_index(self):
+        info = self.index_info
+        if info is None:
+            raise HesaffError(-2, "no index is built (build_index)")
+        return info
+
+    def index_scores(self):
+        """hesaff_index_get_scores: (dot uint64 [N], score float64 [N], nq2) of the last query, for every image"""
+        n = self._need_index()[0]
+        dot = np.zeros(n, np.uint64); score = np.zeros(n, np.float64); nq2 = C.c_uint64()
+        self._check(self.L.hesaff_index_get_scores(self.h, dot.ctypes.data, score.ctypes.data, C.addressof(nq2)))
+        return dot, score, nq2.value
+
+    def index_tables(self):
+        """hesaff_index_get_tables: (df uint32 [K], idf uint32 [K], norm2 uint64 [N])"""
+        n, k = self._need_index()[:2]
+        df = np.zeros(k, np.uint32); idf = np.zeros(k, np.uint32); norm2 = np.zeros(n, np.uint64)
+        self._check(self.L.hesaff_index_get_tables(self.h, df.ctypes.data, idf.ctypes.data, norm2.ctypes.data))
+        return df, idf, norm2
+
+    def clear_index(self):
+        self._check(self.L.hesaff_index_clear(self.h))
+
+    @property
+    def index_ms(self):
+        """HIP-event times (build, query) of the last build and the last query (profiling >= 1), in ms"""
+        b, q = C.c_float(), C.c_float()
+        self._check(self.L.hesaff_get_index_ms(self.h, C.byref(b), C.byref(q)))
+        return b.value, q.value
 
     def process_files(self, paths, out_paths=None, decode_threads=0, write_threads=0):
         """hesaff_process_files: image files -> <name>.hesaff.sift through the decode / device / write pipeline.

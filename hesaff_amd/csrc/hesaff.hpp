@@ -29,6 +29,7 @@
 #include <ostream>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/hesaff_amd.h"
@@ -190,6 +191,35 @@ struct AffineHessianDetector {
    }
    const std::vector<int64_t> &distortion() const { return distortion_; }   // of the last trainVocabulary: distortion()[t] belongs to V_t
    const std::vector<int32_t> &emptyWords() const { return empty_; }
+
+   // No counterpart in the reference (hesaff_index_build, include/hesaff_amd.h): an inverted file with integer tf-idf scoring over the
+   // words of a collection, built on the device.  words: the words of all images one after the other, counts[i] of them for image i,
+   // key j's word at words[j * wordStride] (1: packed; 2: the (word, dist2) rows words() holds); vocabularySize: K, every word in
+   // 0 .. K - 1.  A successful build replaces the detector's index; the detector's vocabulary plays no part.
+   void buildIndex(const std::vector<int32_t> &counts, const int32_t *words, int wordStride, int vocabularySize)
+   {
+      const int rc = hesaff_index_build(ctx_, (int)counts.size(), counts.data(), words, wordStride, vocabularySize);
+      if (rc == HESAFF_ERR_ARG)
+         throw std::invalid_argument("an index takes 1..2^20 images of at most 2^18 words each in 0 .. vocabularySize - 1, 2^28 in all, vocabularySize <= 2^20");
+      if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+   }
+   // the first min(top, images) images in the order (score descending, image ascending) for a query of n words; 1 <= top <= 1024
+   std::vector<std::pair<int32_t, double>> queryIndex(const int32_t *words, int n, int wordStride, int top)
+   {
+      std::vector<int32_t> images((size_t)(top > 0 && top <= 1024 ? top : 1));
+      std::vector<double> scores(images.size());
+      int count = 0;
+      const int rc = hesaff_index_query(ctx_, n, words, wordStride, top, images.data(), scores.data(), &count);
+      if (rc == HESAFF_ERR_ARG) throw std::invalid_argument("a query needs an index, at most 2^18 words inside its vocabulary and 1 <= top <= 1024");
+      if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+      std::vector<std::pair<int32_t, double>> out((size_t)count);
+      for (int i = 0; i < count; i++) out[(size_t)i] = {images[(size_t)i], scores[(size_t)i]};
+      return out;
+   }
+   void clearIndex()
+   {
+      if (hesaff_index_clear(ctx_) != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+   }
 
    // No counterpart in the reference (hesaff_set_next_masks, include/hesaff_amd.h; OpenCV's detect(image, keypoints, mask)): the NEXT
    // detectPyramidKeypoints keeps only the Hessian keypoints on a non-zero pixel of `mask` - height x width 8-bit pixels at the size of

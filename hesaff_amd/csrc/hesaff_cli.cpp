@@ -52,6 +52,11 @@
 //       with the run's other options (--descriptor, --orientation, --orientations, --max-keypoints, --grid, --fast); no per-image file is
 //       written, <vocabulary file> is, and one line per iteration is printed: the distortion and the number of empty words.  At most 2^24
 //       keys: a list that yields more stops with a message naming the count.
+//   hesaff --search <list of .hesaff.words files> --query <.hesaff.words file> [--top M] [--device D]
+//       builds an image index on device D (default 0) from the words files the list names, one per line (hesaff_index_build: an inverted
+//       file with integer tf-idf weights; every file must state the same vocabulary size), queries it with the words of the query file
+//       and prints the M best images (default 10, at most 1024), best first, equal scores in list order: rank<TAB>path<TAB>score, the
+//       score as %.17g.  Recognised before --batch and before the single-image form.
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -349,6 +354,59 @@ int run_train_mode(const char *list_path, const char *devices_spec, const char *
    return rc;
 }
 
+// hesaff --search <list> --query <file>: the word columns of the listed files (hesaff_read_words) into one index, one query, the
+// ranked list on stdout.
+int run_search_mode(const char *list_path, const char *query_path, int top, int device)
+{
+   std::ifstream lf(list_path);
+   if (!lf) { fprintf(stderr, "hesaff: cannot read list '%s'\n", list_path); return 1; }
+   std::vector<std::string> names;
+   for (std::string line; std::getline(lf, line);) {
+      while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+      if (!line.empty() && line[0] != '#') names.push_back(line);
+   }
+   if (names.empty()) { fprintf(stderr, "hesaff: list '%s' names no words file\n", list_path); return 1; }
+   std::vector<int32_t> counts, words;
+   int k = 0;
+   auto read = [&](const char *path, int &count) {
+      int32_t *w = nullptr;
+      int vs = 0;
+      if (hesaff_read_words(path, &w, &count, &vs) != HESAFF_OK) { fprintf(stderr, "hesaff: cannot read '%s' (a .hesaff.words file expected)\n", path); return false; }
+      words.insert(words.end(), w, w + count);
+      hesaff_free(w);
+      if (k == 0) k = vs;
+      if (vs != k || vs < 1) { fprintf(stderr, "hesaff: '%s' states vocabulary size %d, the files before it %d\n", path, vs, k); return false; }
+      return true;
+   };
+   for (const std::string &name : names) {
+      int count = 0;
+      if (!read(name.c_str(), count)) return 1;
+      counts.push_back(count);
+   }
+   const size_t indexed = words.size();
+   int n_query = 0;
+   if (!read(query_path, n_query)) return 1;
+   hesaff_params par;
+   hesaff_default_params(&par);
+   par.max_batch = 1;
+   hesaff_ctx *ctx = nullptr;
+   if (hesaff_create(&ctx, &par, device) != HESAFF_OK) { fprintf(stderr, "hesaff: device %d: %s\n", device, hesaff_last_error(nullptr)); return 1; }
+   struct Destroy { hesaff_ctx *c; ~Destroy() { hesaff_destroy(c); } } destroy{ctx};
+   if (hesaff_index_build(ctx, (int)counts.size(), counts.data(), words.data(), 1, k) != HESAFF_OK) {
+      fprintf(stderr, "hesaff: the index was not built: %s\n", hesaff_last_error(ctx));
+      return 1;
+   }
+   std::vector<int32_t> images((size_t)top);
+   std::vector<double> scores((size_t)top);
+   int count = 0;
+   if (hesaff_index_query(ctx, n_query, words.data() + indexed, 1, top, images.data(), scores.data(), &count) != HESAFF_OK) {
+      fprintf(stderr, "hesaff: the query failed: %s\n", hesaff_last_error(ctx));
+      return 1;
+   }
+   for (int r = 0; r < count; r++) printf("%d\t%s\t%.17g\n", r + 1, names[(size_t)images[(size_t)r]].c_str(), scores[(size_t)r]);
+   return 0;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -360,6 +418,27 @@ int main(int argc, char **argv)
    }
    // batch mode: "--batch <list>" and the other options in any order (the reference has no options: a first argument that does
    // not start with "--" is an image, as in hesaff.cpp:133-137)
+   bool search = false;
+   for (int i = 1; i < argc; i++) search = search || strcmp(argv[i], "--search") == 0;
+   if (search) {
+      const char *list = nullptr, *query = nullptr;
+      long top = 10, device = 0;
+      bool bad = false;
+      for (int i = 1; i < argc && !bad; i += 2) {
+         if (i + 1 >= argc) { bad = true; break; }
+         char *end = nullptr;
+         if (strcmp(argv[i], "--search") == 0 && !list) list = argv[i + 1];
+         else if (strcmp(argv[i], "--query") == 0 && !query) query = argv[i + 1];
+         else if (strcmp(argv[i], "--top") == 0) { top = strtol(argv[i + 1], &end, 10); bad = end == argv[i + 1] || *end || top < 1 || top > 1024; }
+         else if (strcmp(argv[i], "--device") == 0) { device = strtol(argv[i + 1], &end, 10); bad = end == argv[i + 1] || *end || device < 0 || device > 4095; }
+         else bad = true;
+      }
+      if (bad || !list || !query) {
+         fprintf(stderr, "hesaff: usage: hesaff --search <list of .hesaff.words files> --query <.hesaff.words file> [--top 1..1024] [--device D]\n");
+         return 1;
+      }
+      return run_search_mode(list, query, (int)top, (int)device);
+   }
    bool batch = false;
    for (int i = 1; i < argc; i++) batch = batch || strcmp(argv[i], "--batch") == 0;
    if (batch) {

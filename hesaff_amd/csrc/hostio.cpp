@@ -1236,6 +1236,49 @@ int hesaff_read_vocabulary(const char *path, uint8_t **words, int *k)
    return HESAFF_OK;
 }
 
+// The word column of a words file (hesaff_write_words) -> int32 words, malloc'ed (hesaff_free; NULL for a file of no rows).
+// HESAFF_ERR_IO: the file cannot be read, or is not a whole words file (wrong magic, a size other than 16 + 24 count).
+int hesaff_read_words(const char *path, int32_t **words, int *count, int *vocabulary_size)
+{
+   if (!path || !words || !count || !vocabulary_size) return HESAFF_ERR_ARG;
+   *words = nullptr; *count = 0; *vocabulary_size = 0;
+   const int fd = open(path, O_RDONLY | O_CLOEXEC);
+   if (fd < 0) return HESAFF_ERR_IO;
+   int rc = HESAFF_ERR_IO;
+   int32_t *out = nullptr;
+   const off_t size = lseek(fd, 0, SEEK_END);
+   char head[16];
+   uint32_t vs = 0, cnt = 0;
+   if (size >= 16 && pread(fd, head, 16, 0) == 16 && memcmp(head, "HESAFFW1", 8) == 0) {
+      memcpy(&vs, head + 8, 4); memcpy(&cnt, head + 12, 4);
+      if (cnt <= 0x7fffffffu && vs <= 0x7fffffffu && (unsigned long long)size == 16ull + 24ull * cnt) {
+         rc = HESAFF_OK;
+         if (cnt > 0) {
+            const size_t bytes = (size_t)cnt * 24;
+            char *rows = (char *)malloc(bytes);
+            out = (int32_t *)malloc((size_t)cnt * 4);
+            if (!rows || !out) rc = HESAFF_ERR_NOMEM;
+            else {
+               size_t done = 0;
+               while (done < bytes) {
+                  const ssize_t r = pread(fd, rows + done, bytes - done, (off_t)(16 + done));
+                  if (r < 0 && errno == EINTR) continue;
+                  if (r <= 0) break;
+                  done += (size_t)r;
+               }
+               if (done != bytes) rc = HESAFF_ERR_IO;
+               else for (size_t i = 0; i < cnt; i++) memcpy(&out[i], rows + i * 24 + 20, 4);
+            }
+            free(rows);
+         }
+      }
+   }
+   close(fd);
+   if (rc != HESAFF_OK) { free(out); return rc; }
+   *words = out; *count = (int)cnt; *vocabulary_size = (int)vs;
+   return HESAFF_OK;
+}
+
 // One file per image of a batch (exportKeypoints once per image, hesaff.cpp:170-176), images
 // taken by `threads` workers from a shared counter; every worker formats its image on its own.
 int hesaff_write_sift_batch(int n_images, const char *const *paths, const hesaff_result *results, float mrSize, int threads)

@@ -42,12 +42,14 @@
 #include "kernels_jpeg.h"
 #include "kernels_words.h"
 #include "kernels_train.h"
+#include "kernels_index.h"
 #include "chunk_engine.h"
 #include "batch_plan.h"
 #include "buffer_layouts.h"
 #include "context_tables.h"
 #include "group_schedule.h"
 #include "train_plan.h"
+#include "index_plan.h"
 
 static thread_local std::string g_create_error;
 
@@ -445,6 +447,17 @@ struct hesaff_ctx {
    DevEvent ev_assign[2];              // profiling: brackets of the last k_assign_words launch
    bool assign_timed = false;          // ev_assign holds a launch of the last batch
    float train_ms[3] = {0.0f, 0.0f, 0.0f};   // hesaff_get_training_ms: assignment, accumulation, update of the last training call (profiling >= 1)
+   // hesaff_index_build: the inverted file over visual words (index_plan.h: IndexArrays in `tables`, the posting lists in `lists`);
+   // not built: nothing here is allocated, launched or copied
+   struct Index {
+      DevBuf tables, lists, qwords;    // qwords: the staged words of a host query
+      IndexArrays a;
+      int n_images = 0, k = 0;
+      int64_t n_keys = 0, n_postings = 0;
+      bool built = false;
+      template <class T> T *ptr(const Span<T> &s) const { return tables.at<T>(s.off); }
+   } index;
+   float index_ms[3] = {0.0f, 0.0f, 0.0f};   // hesaff_get_index_ms: the last build's hash step and list steps, the last query (profiling >= 1)
    ArmedMasks next_masks;              // hesaff_set_next_masks / _device: the masks of the next detecting call (taken, so cleared, by take_masks)
    int stage_threads = 4;              // host threads that copy a chunk's pixels into pinned memory (hesaff_process_files: within its thread budget)
    DevEvent ev_detect_done, ev_batch_done;   // blocking-sync events: the host sleeps instead of spinning
@@ -1522,3 +1535,4 @@ void pack_regions(hesaff_ctx *c, uint32_t n_hess, int B, hesaff_region *d_region
 #include "capi_impl.h"
 #include "capi_stage.h"
 #include "capi_train.h"
+#include "capi_index.h"

@@ -53,6 +53,7 @@ extern "C" {
  *    And for visual-word assignment (hesaff_set_vocabulary and the ten symbols declared with it, HESAFF_OUT_WORDS): symbols only, version 8.
  *    And for vocabulary training (hesaff_train_vocabulary, hesaff_train_vocabulary_device, hesaff_stage_accumulate_words,
  *    hesaff_get_training_ms): symbols only, version 8.
+ *    And for the image index (hesaff_index_build and the nine symbols declared with it): symbols only, version 8.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -604,6 +605,58 @@ int hesaff_train_vocabulary(hesaff_ctx *ctx, int64_t n, const uint8_t *desc, int
                             int64_t *distortion, int32_t *empty, int *iterations_done);
 int hesaff_stage_accumulate_words(hesaff_ctx *ctx, int n, const uint8_t *desc, const int32_t *words, int k, uint32_t *sums_out, uint32_t *counts_out);
 int hesaff_get_training_ms(const hesaff_ctx *ctx, float *assign_ms, float *accumulate_ms, float *update_ms);
+
+/* Image index (no counterpart in the reference): an inverted file over visual words with tf-idf scoring, the consumer of the words
+ * that hesaff_set_vocabulary assigns.  Symbols only, version 8.
+ * An index is built in one call from N images, 1 <= N <= 2^20; image i has counts[i] words, 0 <= counts[i] <= 2^18, each in
+ * 0 .. K - 1, 1 <= K <= 2^20; the total number of keys is T <= 2^28.  K is an argument of the call, not the context's vocabulary:
+ * the words may come from files.  All integers:
+ *     tf(i, w)  = number of keys of image i with word w
+ *     df(w)     = #{i : tf(i, w) > 0}
+ *     idf(w)    = 0 where df(w) = 0, otherwise ilog2_q8 of N and df(w):
+ *                    q = (N << 31) / df                  uint64, floor;  2^31 <= q < 2^55
+ *                    e = (index of q's highest set bit) - 31;   m = q >> e        2^31 <= m < 2^32
+ *                    r = e
+ *                    8 times:  m = (m * m) >> 31;  r = 2 r;  if m >= 2^32 { r += 1; m >>= 1 }
+ *                    idf = r          (floor(256 log2(N / df)) but for the truncations; 0 when df = N; at most 6143)
+ *     norm2(i)  = sum_w (tf(i, w) * idf(w))^2            uint64
+ * The definition is this algorithm, not the logarithm.  A query is n words, 0 <= n <= 2^18, each in 0 .. K - 1, tfq(w) their counts:
+ *     nq2      = sum_w (tfq(w) * idf(w))^2                                  uint64
+ *     dot(i)   = sum_w tfq(w) * tf(i, w) * idf(w)^2                         uint64
+ *     score(i) = 0.0 where dot(i) = 0, otherwise
+ *                (double)dot(i) / sqrt((double)nq2 * (double)norm2(i))      conversions round to nearest even; *, sqrt, / are IEEE binary64
+ *     result   = the first min(top, N) images in the order (score descending, image index ascending), with their scores; 1 <= top <= 1024
+ * Every sum stays inside uint64: idf^2 < 2^26, sum_w tfq * tf <= 2^18 * 2^18 and sum_w tf^2 <= 2^36, so dot, nq2 and norm2 are each
+ * below 2^62.  The definition is total: images without keys, and images that share no weighted word with the query, score 0 and
+ * rank among themselves by index; an empty query returns images 0, 1, .. with score 0; equal images tie, the lower index first.
+ * Integer accumulation throughout: no result depends on launch geometry or on the order of atomics (kernels_index.h).
+ * The words of all images are concatenated, image after image; key j's word is words[j * word_stride], word_stride = 1 for a packed
+ * array, 2 for the (word, dist2) rows that hesaff_get_words and hesaff_get_words_device hand out.  counts is host memory in both
+ * forms.  The host forms check the words while staging them; the device forms run a read-only check kernel first.
+ * A successful build replaces the previous index.  The index is context state, like the vocabulary: it survives detecting calls,
+ * and without one nothing is launched, allocated or copied anywhere.  The build's scratch (a hash table of at least 2 T slots, 12
+ * bytes each) is released before the call returns.
+ * hesaff_index_get_scores: dot and score of EVERY image, and nq2, of the last query (zeros before the first); each may be NULL.
+ * hesaff_index_get_tables: df[K], idf[K], norm2[N]; each may be NULL.  hesaff_index_get_info: each may be NULL.
+ * hesaff_get_index_ms: HIP-event times of the last build and the last query at profiling level >= 1, 0 otherwise.
+ * hesaff_read_words: the word column of a words file ("HESAFFW1"); *words is malloc'ed (hesaff_free; NULL when count is 0);
+ * HESAFF_ERR_IO for a file that cannot be read or is not a whole words file (magic, a size other than 16 + 24 count).
+ * HESAFF_ERR_ARG, nothing changed, the context usable as before: ctx NULL; a required pointer NULL; a count outside the bounds above;
+ * word_stride not 1 or 2; a device pointer that is not 4-byte aligned; a word outside 0 .. K - 1; top outside 1..1024; a query, a
+ * getter or hesaff_index_get_info with no index built (hesaff_index_clear succeeds without one).
+ * HESAFF_ERR_NOMEM: the device cannot hold the index or the build's scratch; a previous index then stays. */
+int hesaff_index_build(hesaff_ctx *ctx, int n_images, const int32_t *counts, const int32_t *words, int word_stride, int vocabulary_size);
+int hesaff_index_build_device(hesaff_ctx *ctx, int n_images, const int32_t *counts, const void *d_words, int word_stride, int vocabulary_size);
+int hesaff_index_query(hesaff_ctx *ctx, int n, const int32_t *words, int word_stride, int top, int32_t *images_out, double *scores_out,
+                       int *count_out);
+int hesaff_index_query_device(hesaff_ctx *ctx, int n, const void *d_words, int word_stride, int top, int32_t *images_out, double *scores_out,
+                              int *count_out);
+int hesaff_index_get_scores(const hesaff_ctx *ctx, uint64_t *dots, double *scores, uint64_t *query_norm2);
+int hesaff_index_get_tables(const hesaff_ctx *ctx, uint32_t *df, uint32_t *idf, uint64_t *norm2);
+int hesaff_index_get_info(const hesaff_ctx *ctx, int *n_images, int *vocabulary_size, int64_t *n_keys, int64_t *n_postings);
+int hesaff_index_clear(hesaff_ctx *ctx);
+int hesaff_get_index_ms(const hesaff_ctx *ctx, float *build_ms, float *query_ms);
+int hesaff_read_words(const char *path, int32_t **words, int *count, int *vocabulary_size);
 
 /* Same path with inputs already resident in device memory (bench / pipelines that decode
  * on the GPU): d_gray = n contiguous height x width 8-bit grey planes (device pointer).

@@ -267,6 +267,14 @@ def load_library():
         L.hesaff_index_clear.argtypes = [vp]
         L.hesaff_get_index_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.hesaff_read_words.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(L, "hesaff_verify_matches"):   # (likewise)
+        L.hesaff_verify_matches.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]
+        L.hesaff_verify_matches_device.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp]
+        L.hesaff_verify_get_pairs.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_int)]
+        L.hesaff_verify_get_query_inert.argtypes = [vp, C.POINTER(C.c_int)]
+        L.hesaff_stage_verify_pairs.argtypes = [vp, C.c_int, vp, C.c_float, vp, C.POINTER(C.c_int32)]
+        L.hesaff_get_verify_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.hesaff_read_words_rows.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.hesaff_stage_math_sift_general.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math_sift.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]
@@ -314,6 +322,8 @@ ABI_SYMBOLS = [
     "hesaff_train_vocabulary", "hesaff_train_vocabulary_device", "hesaff_stage_accumulate_words", "hesaff_get_training_ms",
     "hesaff_index_build", "hesaff_index_build_device", "hesaff_index_query", "hesaff_index_query_device", "hesaff_index_get_scores",
     "hesaff_index_get_tables", "hesaff_index_get_info", "hesaff_index_clear", "hesaff_get_index_ms", "hesaff_read_words",
+    "hesaff_verify_matches", "hesaff_verify_matches_device", "hesaff_verify_get_pairs", "hesaff_verify_get_query_inert",
+    "hesaff_stage_verify_pairs", "hesaff_get_verify_ms", "hesaff_read_words_rows",
 ]
 
 # hesaff_set_output_format's bits
@@ -532,6 +542,13 @@ def read_words(path):
     if len(body) != n * WORDS_ROW_DTYPE.itemsize:
         raise HesaffError(-4, "%s is truncated" % path)
     return vocabulary_size, np.frombuffer(body, dtype=WORDS_ROW_DTYPE).copy()
+
+
+def _verify_rows(rows):
+    """the rows of an image (or of a query) for verification: a 1-d array of WORDS_ROW_DTYPE, C-contiguous"""
+    if not isinstance(rows, np.ndarray) or rows.dtype != WORDS_ROW_DTYPE or rows.ndim != 1:
+        raise ValueError("rows are a 1-d array of WORDS_ROW_DTYPE (what read_words returns)")
+    return np.ascontiguousarray(rows)
 
 
 def _index_words(w):
@@ -1122,6 +1139,62 @@ class HesaffContext:
         b, q = C.c_float(), C.c_float()
         self._check(self.L.hesaff_get_index_ms(self.h, C.byref(b), C.byref(q)))
         return b.value, q.value
+
+    # ---- spatial verification (hesaff_verify_matches, include/hesaff_amd.h) ----
+    def _verify(self, call, n_candidates):
+        out = np.zeros((n_candidates, 6), np.int32); hyp = np.zeros((n_candidates, 3), np.float32); order = np.zeros(n_candidates, np.int32)
+        self._check(call(out.ctypes.data, hyp.ctypes.data, order.ctypes.data))
+        return out, hyp, order
+
+    def verify_matches(self, query_rows, candidates, vocabulary_size, tolerance, max_pairs=1):
+        """hesaff_verify_matches: query_rows and every entry of the list `candidates` are arrays of WORDS_ROW_DTYPE (what read_words
+        returns) -> (out int32 [R, 6] = inliers, used, found, query_key, candidate_key, inert_keys; hyp float32 [R, 3] = L11, L21,
+        L22 of the best hypothesis; order int32 [R], the candidates by (inliers descending, position ascending))."""
+        q = _verify_rows(query_rows)
+        arrays = [_verify_rows(c) for c in candidates]
+        counts = np.array([len(a) for a in arrays], np.int32)
+        flat = np.ascontiguousarray(np.concatenate(arrays) if arrays else np.zeros(0, WORDS_ROW_DTYPE))
+        return self._verify(lambda *a: self.L.hesaff_verify_matches(self.h, len(q), q.ctypes.data if len(q) else None, len(arrays), counts.ctypes.data,
+                                                                     flat.ctypes.data if len(flat) else None, int(vocabulary_size), int(max_pairs),
+                                                                     float(tolerance), *a), len(arrays))
+
+    def verify_matches_device(self, query_ptr, nq, candidates_ptr, counts, vocabulary_size, tolerance, max_pairs=1):
+        """hesaff_verify_matches_device: the same on rows in device memory (raw pointers, 24 bytes per row, the candidates' rows one
+        image after the other), counts the rows per candidate (host)."""
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        return self._verify(lambda *a: self.L.hesaff_verify_matches_device(self.h, int(nq), C.c_void_p(query_ptr), len(counts), counts.ctypes.data,
+                                                                            C.c_void_p(candidates_ptr), int(vocabulary_size), int(max_pairs), float(tolerance),
+                                                                            *a), len(counts))
+
+    def verify_pairs(self, candidate):
+        """hesaff_verify_get_pairs: the used correspondences int32 [M, 2] = (query key, candidate key) of one candidate of the last call"""
+        p, n = C.c_void_p(), C.c_int()
+        self._check(self.L.hesaff_verify_get_pairs(self.h, int(candidate), C.byref(p), C.byref(n)))
+        if n.value == 0:
+            return np.zeros((0, 2), np.int32)
+        return np.frombuffer(C.string_at(p.value, n.value * 8), np.int32).reshape(-1, 2).copy()
+
+    @property
+    def verify_query_inert(self):
+        """hesaff_verify_get_query_inert: the inert keys of the last call's query"""
+        n = C.c_int()
+        self._check(self.L.hesaff_verify_get_query_inert(self.h, C.byref(n)))
+        return n.value
+
+    def stage_verify_pairs(self, pairs, tolerance):
+        """hesaff_stage_verify_pairs: pairs float32 [m, 10] -> (inl int32 [m], best h or -1)"""
+        c = np.ascontiguousarray(pairs, dtype=np.float32).reshape(-1, 10)
+        inl = np.zeros(len(c), np.int32); best = C.c_int32(-2)
+        self._check(self.L.hesaff_stage_verify_pairs(self.h, len(c), c.ctypes.data if len(c) else None, float(tolerance), inl.ctypes.data if len(c) else None,
+                                                     C.byref(best)))
+        return inl, best.value
+
+    @property
+    def verify_ms(self):
+        """HIP-event times (pairs, hypotheses) of the last verify call (profiling >= 1), in ms"""
+        a, b = C.c_float(), C.c_float()
+        self._check(self.L.hesaff_get_verify_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def process_files(self, paths, out_paths=None, decode_threads=0, write_threads=0):
         """hesaff_process_files: image files -> <name>.hesaff.sift through the decode / device / write pipeline.

@@ -221,6 +221,32 @@ struct AffineHessianDetector {
       if (hesaff_index_clear(ctx_) != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
    }
 
+   // No counterpart in the reference (hesaff_verify_matches, include/hesaff_amd.h): spatial verification of a shortlist.  queryRows
+   // and candidateRows are rows of words files (24 bytes: x, y, a, b, c, word), the candidates' one image after the other, counts[r]
+   // of them for candidate r; tolerance in pixels of the candidate image; maxPairs in 1..16.  Returns the candidates in the order
+   // (inliers descending, position ascending); `results`, where given, receives one record per candidate, in the candidates' order.
+   // Neither the detector's vocabulary nor its index plays a part.
+   struct Verified { int32_t inliers, used, found, queryKey, candidateKey, inertKeys; float L11, L21, L22; };
+   std::vector<int32_t> verifyMatches(const void *queryRows, int nq, const std::vector<int32_t> &counts, const void *candidateRows, int vocabularySize,
+                                      float tolerance, int maxPairs = 1, std::vector<Verified> *results = nullptr)
+   {
+      const size_t R = counts.size();
+      std::vector<int32_t> out(R * 6 + 1), order(R + 1);
+      std::vector<float> hyp(R * 3 + 1);
+      const int rc = hesaff_verify_matches(ctx_, nq, queryRows, (int)R, counts.data(), candidateRows, vocabularySize, maxPairs, tolerance, out.data(), hyp.data(),
+                                           order.data());
+      if (rc == HESAFF_ERR_ARG)
+         throw std::invalid_argument("verification takes 1..1024 candidates of at most 2^18 rows each with words in 0 .. vocabularySize - 1, 1 <= maxPairs <= 16 and 0 < tolerance <= 2^20");
+      if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+      order.resize(R);
+      if (results) {
+         results->resize(R);
+         for (size_t r = 0; r < R; r++)
+            (*results)[r] = {out[r * 6], out[r * 6 + 1], out[r * 6 + 2], out[r * 6 + 3], out[r * 6 + 4], out[r * 6 + 5], hyp[r * 3], hyp[r * 3 + 1], hyp[r * 3 + 2]};
+      }
+      return order;
+   }
+
    // No counterpart in the reference (hesaff_set_next_masks, include/hesaff_amd.h; OpenCV's detect(image, keypoints, mask)): the NEXT
    // detectPyramidKeypoints keeps only the Hessian keypoints on a non-zero pixel of `mask` - height x width 8-bit pixels at the size of
    // the image as passed, rows strideBytes apart (0: tightly packed), pixel (row, col) = (clamp((int)(y + 0.5f)), clamp((int)(x +

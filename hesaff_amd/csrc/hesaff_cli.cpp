@@ -355,8 +355,9 @@ int run_train_mode(const char *list_path, const char *devices_spec, const char *
 }
 
 // hesaff --search <list> --query <file>: the word columns of the listed files (hesaff_read_words) into one index, one query, the
-// ranked list on stdout.
-int run_search_mode(const char *list_path, const char *query_path, int top, int device)
+// ranked list on stdout.  With --verify the rows of the query and of the shortlisted files (hesaff_read_words_rows) go through
+// hesaff_verify_matches, and the shortlist is printed in verified order with its inlier counts.
+int run_search_mode(const char *list_path, const char *query_path, int top, int device, bool verify, float tolerance, int max_pairs)
 {
    std::ifstream lf(list_path);
    if (!lf) { fprintf(stderr, "hesaff: cannot read list '%s'\n", list_path); return 1; }
@@ -403,7 +404,36 @@ int run_search_mode(const char *list_path, const char *query_path, int top, int 
       fprintf(stderr, "hesaff: the query failed: %s\n", hesaff_last_error(ctx));
       return 1;
    }
-   for (int r = 0; r < count; r++) printf("%d\t%s\t%.17g\n", r + 1, names[(size_t)images[(size_t)r]].c_str(), scores[(size_t)r]);
+   if (!verify) {
+      for (int r = 0; r < count; r++) printf("%d\t%s\t%.17g\n", r + 1, names[(size_t)images[(size_t)r]].c_str(), scores[(size_t)r]);
+      return 0;
+   }
+   std::vector<char> rows, query_rows;
+   std::vector<int32_t> row_counts;
+   auto read_rows = [&](const char *path, std::vector<char> &to, int &n) {
+      void *p = nullptr;
+      int vs = 0;
+      if (hesaff_read_words_rows(path, &p, &n, &vs) != HESAFF_OK || vs != k) { fprintf(stderr, "hesaff: cannot read the rows of '%s'\n", path); hesaff_free(p); return false; }
+      to.insert(to.end(), (const char *)p, (const char *)p + (size_t)n * 24);
+      hesaff_free(p);
+      return true;
+   };
+   int nq_rows = 0;
+   if (!read_rows(query_path, query_rows, nq_rows)) return 1;
+   for (int r = 0; r < count; r++) {
+      int n = 0;
+      if (!read_rows(names[(size_t)images[(size_t)r]].c_str(), rows, n)) return 1;
+      row_counts.push_back(n);
+   }
+   std::vector<int32_t> out((size_t)count * 6), order((size_t)count);
+   if (hesaff_verify_matches(ctx, nq_rows, query_rows.data(), count, row_counts.data(), rows.data(), k, max_pairs, tolerance, out.data(), nullptr, order.data()) != HESAFF_OK) {
+      fprintf(stderr, "hesaff: the verification failed: %s\n", hesaff_last_error(ctx));
+      return 1;
+   }
+   for (int r = 0; r < count; r++) {
+      const size_t c = (size_t)order[(size_t)r];
+      printf("%d\t%s\t%.17g\t%d\n", r + 1, names[(size_t)images[c]].c_str(), scores[c], out[c * 6]);
+   }
    return 0;
 }
 
@@ -422,22 +452,31 @@ int main(int argc, char **argv)
    for (int i = 1; i < argc; i++) search = search || strcmp(argv[i], "--search") == 0;
    if (search) {
       const char *list = nullptr, *query = nullptr;
-      long top = 10, device = 0;
-      bool bad = false;
+      long top = 10, device = 0, pairs = 1;
+      float tolerance = 8.0f;
+      bool bad = false, verify = false, verify_options = false;
       for (int i = 1; i < argc && !bad; i += 2) {
+         if (strcmp(argv[i], "--verify") == 0 && !verify) { verify = true; i -= 1; continue; }   // (the one option without a value)
          if (i + 1 >= argc) { bad = true; break; }
          char *end = nullptr;
          if (strcmp(argv[i], "--search") == 0 && !list) list = argv[i + 1];
          else if (strcmp(argv[i], "--query") == 0 && !query) query = argv[i + 1];
          else if (strcmp(argv[i], "--top") == 0) { top = strtol(argv[i + 1], &end, 10); bad = end == argv[i + 1] || *end || top < 1 || top > 1024; }
          else if (strcmp(argv[i], "--device") == 0) { device = strtol(argv[i + 1], &end, 10); bad = end == argv[i + 1] || *end || device < 0 || device > 4095; }
+         else if (strcmp(argv[i], "--tolerance") == 0) {
+            tolerance = strtof(argv[i + 1], &end);
+            bad = end == argv[i + 1] || *end || !(tolerance > 0.0f && tolerance <= 1048576.0f);
+            verify_options = true;
+         }
+         else if (strcmp(argv[i], "--pairs") == 0) { pairs = strtol(argv[i + 1], &end, 10); bad = end == argv[i + 1] || *end || pairs < 1 || pairs > 16; verify_options = true; }
          else bad = true;
       }
-      if (bad || !list || !query) {
-         fprintf(stderr, "hesaff: usage: hesaff --search <list of .hesaff.words files> --query <.hesaff.words file> [--top 1..1024] [--device D]\n");
+      if (bad || !list || !query || (verify_options && !verify)) {
+         fprintf(stderr, "hesaff: usage: hesaff --search <list of .hesaff.words files> --query <.hesaff.words file> [--top 1..1024] [--device D] "
+                         "[--verify [--tolerance PX] [--pairs 1..16]]\n");
          return 1;
       }
-      return run_search_mode(list, query, (int)top, (int)device);
+      return run_search_mode(list, query, (int)top, (int)device, verify, tolerance, (int)pairs);
    }
    bool batch = false;
    for (int i = 1; i < argc; i++) batch = batch || strcmp(argv[i], "--batch") == 0;

@@ -1279,6 +1279,45 @@ int hesaff_read_words(const char *path, int32_t **words, int *count, int *vocabu
    return HESAFF_OK;
 }
 
+// The whole rows of a words file -> count x 24 bytes, malloc'ed (hesaff_free; NULL for a file of no rows).  HESAFF_ERR_IO as above.
+int hesaff_read_words_rows(const char *path, void **rows, int *count, int *vocabulary_size)
+{
+   if (!path || !rows || !count || !vocabulary_size) return HESAFF_ERR_ARG;
+   *rows = nullptr; *count = 0; *vocabulary_size = 0;
+   const int fd = open(path, O_RDONLY | O_CLOEXEC);
+   if (fd < 0) return HESAFF_ERR_IO;
+   int rc = HESAFF_ERR_IO;
+   char *out = nullptr;
+   const off_t size = lseek(fd, 0, SEEK_END);
+   char head[16];
+   uint32_t vs = 0, cnt = 0;
+   if (size >= 16 && pread(fd, head, 16, 0) == 16 && memcmp(head, "HESAFFW1", 8) == 0) {
+      memcpy(&vs, head + 8, 4); memcpy(&cnt, head + 12, 4);
+      if (cnt <= 0x7fffffffu && vs <= 0x7fffffffu && (unsigned long long)size == 16ull + 24ull * cnt) {
+         rc = HESAFF_OK;
+         if (cnt > 0) {
+            const size_t bytes = (size_t)cnt * 24;
+            out = (char *)malloc(bytes);
+            if (!out) rc = HESAFF_ERR_NOMEM;
+            else {
+               size_t done = 0;
+               while (done < bytes) {
+                  const ssize_t r = pread(fd, out + done, bytes - done, (off_t)(16 + done));
+                  if (r < 0 && errno == EINTR) continue;
+                  if (r <= 0) break;
+                  done += (size_t)r;
+               }
+               if (done != bytes) rc = HESAFF_ERR_IO;
+            }
+         }
+      }
+   }
+   close(fd);
+   if (rc != HESAFF_OK) { free(out); return rc; }
+   *rows = out; *count = (int)cnt; *vocabulary_size = (int)vs;
+   return HESAFF_OK;
+}
+
 // One file per image of a batch (exportKeypoints once per image, hesaff.cpp:170-176), images
 // taken by `threads` workers from a shared counter; every worker formats its image on its own.
 int hesaff_write_sift_batch(int n_images, const char *const *paths, const hesaff_result *results, float mrSize, int threads)

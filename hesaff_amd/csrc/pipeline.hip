@@ -43,6 +43,7 @@
 #include "kernels_words.h"
 #include "kernels_train.h"
 #include "kernels_index.h"
+#include "kernels_verify.h"
 #include "chunk_engine.h"
 #include "batch_plan.h"
 #include "buffer_layouts.h"
@@ -50,6 +51,7 @@
 #include "group_schedule.h"
 #include "train_plan.h"
 #include "index_plan.h"
+#include "verify_plan.h"
 
 static thread_local std::string g_create_error;
 
@@ -458,6 +460,19 @@ struct hesaff_ctx {
       template <class T> T *ptr(const Span<T> &s) const { return tables.at<T>(s.off); }
    } index;
    float index_ms[3] = {0.0f, 0.0f, 0.0f};   // hesaff_get_index_ms: the last build's hash step and list steps, the last query (profiling >= 1)
+   // hesaff_verify_matches: the result of the last call (verify_plan.h: VerifyResultArrays in `result`); no call: nothing here is
+   // allocated, launched or copied
+   struct Verify {
+      DevBuf result;
+      VerifyResultArrays a;
+      int n_candidates = 0;
+      uint32_t query_inert = 0;
+      bool done = false;
+      std::vector<uint32_t> used;      // M_r of the last call: hesaff_verify_get_pairs' counts
+      std::vector<int32_t> h_pairs;    // hesaff_verify_get_pairs: the pairs of the candidate asked for last
+      template <class T> T *ptr(const Span<T> &s) const { return result.at<T>(s.off); }
+   } verify;
+   float verify_ms[2] = {0.0f, 0.0f};        // hesaff_get_verify_ms: the pair steps and the hypothesis steps of the last call (profiling >= 1)
    ArmedMasks next_masks;              // hesaff_set_next_masks / _device: the masks of the next detecting call (taken, so cleared, by take_masks)
    int stage_threads = 4;              // host threads that copy a chunk's pixels into pinned memory (hesaff_process_files: within its thread budget)
    DevEvent ev_detect_done, ev_batch_done;   // blocking-sync events: the host sleeps instead of spinning
@@ -1536,3 +1551,4 @@ void pack_regions(hesaff_ctx *c, uint32_t n_hess, int B, hesaff_region *d_region
 #include "capi_stage.h"
 #include "capi_train.h"
 #include "capi_index.h"
+#include "capi_verify.h"

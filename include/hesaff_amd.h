@@ -54,6 +54,7 @@ extern "C" {
  *    And for vocabulary training (hesaff_train_vocabulary, hesaff_train_vocabulary_device, hesaff_stage_accumulate_words,
  *    hesaff_get_training_ms): symbols only, version 8.
  *    And for the image index (hesaff_index_build and the nine symbols declared with it): symbols only, version 8.
+ *    And for spatial verification (hesaff_verify_matches and the six symbols declared with it): symbols only, version 8.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -657,6 +658,68 @@ int hesaff_index_get_info(const hesaff_ctx *ctx, int *n_images, int *vocabulary_
 int hesaff_index_clear(hesaff_ctx *ctx);
 int hesaff_get_index_ms(const hesaff_ctx *ctx, float *build_ms, float *query_ms);
 int hesaff_read_words(const char *path, int32_t **words, int *count, int *vocabulary_size);
+
+/* Spatial verification (no counterpart in the reference): the shortlist of a tf-idf query re-ranked by how many tentative
+ * correspondences agree with the best single-correspondence affine hypothesis - the "fast spatial matching" of Philbin et al. 2007
+ * under the reference's own assumption that the vertical orientation is preserved (the frame of rectifyAffineTransformationUpIsUp,
+ * helpers.cpp:90-97).  It reads the x, y, a, b, c that every words file carries beside the word.  Symbols only, version 8.
+ * Everything is binary32 unless stated; no operation is contracted into an FMA; operations are evaluated left to right as written;
+ * / and sqrtf are the IEEE operations; a comparison with a NaN is false.
+ * Inputs: a query of nq rows and R candidate images of counts[r] rows each, concatenated; a row is the 24-byte row of a words file,
+ * { float x, y, a, b, c; uint32 word }.  1 <= R <= 1024 (hesaff_index_query's top); 0 <= nq <= 2^18, 0 <= counts[r] <= 2^18, their sum
+ * at most 2^28; K the vocabulary size, 1 <= K <= 2^20, every word < K; P = max_pairs in 1..16; tol = tolerance finite,
+ * 0 < tol <= 2^20, in pixels of the candidate image.
+ *  1. Frame of a key:  r = sqrtf(c);  q = b / r;  t = a - q * q;  p = sqrtf(t).  N = [[p, 0], [q, r]] satisfies N^T N = [[a, b], [b, c]]
+ *     and maps the vertical onto itself.  The key is LIVE iff c > 0, t > 0, 2^-20 <= p <= 2^20, 2^-20 <= r <= 2^20, a <= 2^40,
+ *     |x| <= 2^20 and |y| <= 2^20 (all false for a NaN, so a row with a NaN is not live).  Any other key is INERT: it takes part in
+ *     nothing and is counted per image.  (hesaff_ellipse can emit canonical NaNs for degenerate regions; such files must verify.)
+ *  2. Tentative correspondences of candidate r:  tfq(w) = the live query keys with word w, tf_r(w) = the live keys of candidate r with
+ *     word w.  All pairs (query key i, candidate key j), both live, of equal word w with tfq(w) * tf_r(w) <= P, listed in the order
+ *     (j ascending, then i ascending); j counts from the candidate's first row.  found_r is their number; the first
+ *     M_r = min(found_r, 4096) of the list are USED.
+ *  3. Hypothesis h = used correspondence h, query key (xq, yq, pq, qq, rq), candidate key (xd, yd, pd, qd, rd):
+ *        L11 = pq / pd;   L22 = rq / rd;   L21 = (qq - qd * L11) / rd          the map T(x) = N_d^-1 N_q (x - x_q) + x_d
+ *  4. Error of used correspondence k under h:
+ *        dx = xq_k - xq_h;  dy = yq_k - yq_h;  u = L11 * dx;  v = L21 * dx + L22 * dy
+ *        ex = (xd_h + u) - xd_k;  ey = (yd_h + v) - yd_k;  e2 = ex * ex + ey * ey
+ *     k is an inlier of h iff e2 <= tol2, tol2 = tol * tol; inl(h) = the inliers over k = 0 .. M_r - 1 (k = h among them: inl(h) >= 1).
+ *  5. inliers_r = max_h inl(h), the best hypothesis the lowest h that attains it.  M_r = 0: inliers_r = 0, no hypothesis, the key
+ *     indices are -1 and the matrix is zeros.
+ *  6. The candidates are ranked by (inliers_r descending, position r ascending).
+ * Range: for live keys q^2 < a <= 2^40, so |q| < 2^20; hence |L11|, |L22| <= 2^20 / 2^-20 = 2^40 and |L21| < (2^20 + 2^20 * 2^40) * 2^20
+ * < 2^81; |dx|, |dy| <= 2^21, so |u| <= 2^61, |v| < 2^103, and ex, ey are finite.  e2 is finite or +inf, never NaN, and +inf is simply
+ * not an inlier.  No value forms an address.
+ * All accumulations are integer counts: no result depends on launch geometry, on tiling or on the order of atomics; the same input
+ * gives the same bytes.
+ * hesaff_verify_matches: rows in host memory.  out[R][6] = (inliers, used, found, query_key, candidate_key, inert_keys), hyp[R][3] =
+ * (L11, L21, L22) of the best hypothesis, order[R] = the ranking; each may be NULL.  counts is host memory in both forms.
+ * hesaff_verify_matches_device: both row arrays in device memory, 4-byte aligned.  The host form checks the words while staging; the
+ * device form runs a read-only check kernel first.
+ * hesaff_verify_get_pairs: the used correspondences (i, j) of one candidate of the last call, pairs[count][2], in definition order; the
+ * memory is the library's, valid until the next hesaff_verify_* call.  hesaff_verify_get_query_inert: the query's inert keys.
+ * hesaff_stage_verify_pairs: the production hypothesis kernel alone on m <= 4096 correspondences of the caller's,
+ * pairs[m][10] = xq, yq, pq, qq, rq, xd, yd, pd, qd, rd (frames within the live bounds): inl_out[m] = inl(h), *best_out = the best
+ * h, -1 for m = 0; each may be NULL.
+ * hesaff_get_verify_ms: HIP-event times of the last call at profiling level >= 1 - grouping and pair construction, hypotheses and
+ * ranking - 0 otherwise.
+ * hesaff_read_words_rows: the whole rows of a words file ("HESAFFW1"), count x 24 bytes; *rows is malloc'ed (hesaff_free; NULL when
+ * count is 0); HESAFF_ERR_IO as for hesaff_read_words.
+ * Verification is no context state apart from the result of the last call: it neither reads nor changes the vocabulary or the
+ * index, its scratch (a hash table of at least 2 sum(counts) slots, 12 bytes each, and 160 KB per candidate) is released before the
+ * call returns, and without a call nothing is launched, allocated or copied anywhere.
+ * HESAFF_ERR_ARG, nothing changed, the context usable as before: ctx NULL; a required pointer NULL; a count or bound outside the
+ * ranges above; a word >= K; tol not finite or out of range; a device pointer that is not 4-byte aligned; a getter before any
+ * verify call, or `candidate` outside the last call's.  HESAFF_ERR_NOMEM: the device cannot hold the scratch. */
+int hesaff_verify_matches(hesaff_ctx *ctx, int nq, const void *query_rows, int n_candidates, const int32_t *counts, const void *candidate_rows,
+                          int vocabulary_size, int max_pairs, float tolerance, int32_t *out, float *hyp, int32_t *order);
+int hesaff_verify_matches_device(hesaff_ctx *ctx, int nq, const void *d_query_rows, int n_candidates, const int32_t *counts,
+                                 const void *d_candidate_rows, int vocabulary_size, int max_pairs, float tolerance, int32_t *out, float *hyp,
+                                 int32_t *order);
+int hesaff_verify_get_pairs(hesaff_ctx *ctx, int candidate, const int32_t **pairs, int *count);
+int hesaff_verify_get_query_inert(const hesaff_ctx *ctx, int *n);
+int hesaff_stage_verify_pairs(hesaff_ctx *ctx, int m, const float *pairs, float tolerance, int32_t *inl_out, int32_t *best_out);
+int hesaff_get_verify_ms(const hesaff_ctx *ctx, float *pairs_ms, float *hypotheses_ms);
+int hesaff_read_words_rows(const char *path, void **rows, int *count, int *vocabulary_size);
 
 /* Same path with inputs already resident in device memory (bench / pipelines that decode
  * on the GPU): d_gray = n contiguous height x width 8-bit grey planes (device pointer).

@@ -39,6 +39,8 @@ from ._binding import (  # noqa: F401
     WORDS_ROW_DTYPE,
     read_vocabulary,
     write_vocabulary,
+    read_vocabulary_cells,
+    write_vocabulary_cells,
     read_words,
     write_words,
     read_image,

@@ -256,6 +256,16 @@ def load_library():
         L.hesaff_train_vocabulary.argtypes = [vp, C.c_int64, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
         L.hesaff_stage_accumulate_words.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp]
         L.hesaff_get_training_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    if hasattr(L, "hesaff_set_vocabulary_cells"):   # (likewise)
+        L.hesaff_set_vocabulary_cells.argtypes = [vp, C.c_int, vp, vp]
+        L.hesaff_get_vocabulary_cells.argtypes = [vp, C.POINTER(C.c_int)]
+        L.hesaff_get_assign_cells_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.hesaff_build_vocabulary_cells.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(C.c_int)]
+        L.hesaff_train_vocabulary_cells_device.argtypes = [vp, C.c_int64, vp, C.c_int64, C.c_int64, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp,
+                                                           C.POINTER(C.c_int)]
+        L.hesaff_train_vocabulary_cells.argtypes = [vp, C.c_int64, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
+        L.hesaff_read_vocabulary_cells.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.hesaff_write_vocabulary_cells.argtypes = [C.c_char_p, C.c_int, vp, vp]
     if hasattr(L, "hesaff_index_build"):   # (likewise)
         L.hesaff_index_build.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int]
         L.hesaff_index_build_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int]
@@ -320,6 +330,8 @@ ABI_SYMBOLS = [
     "hesaff_assign_words_device", "hesaff_stage_assign_words", "hesaff_get_assign_ms", "hesaff_write_words",
     "hesaff_read_vocabulary", "hesaff_write_vocabulary",
     "hesaff_train_vocabulary", "hesaff_train_vocabulary_device", "hesaff_stage_accumulate_words", "hesaff_get_training_ms",
+    "hesaff_set_vocabulary_cells", "hesaff_get_vocabulary_cells", "hesaff_get_assign_cells_ms", "hesaff_build_vocabulary_cells",
+    "hesaff_train_vocabulary_cells", "hesaff_train_vocabulary_cells_device", "hesaff_read_vocabulary_cells", "hesaff_write_vocabulary_cells",
     "hesaff_index_build", "hesaff_index_build_device", "hesaff_index_query", "hesaff_index_query_device", "hesaff_index_get_scores",
     "hesaff_index_get_tables", "hesaff_index_get_info", "hesaff_index_clear", "hesaff_get_index_ms", "hesaff_read_words",
     "hesaff_verify_matches", "hesaff_verify_matches_device", "hesaff_verify_get_pairs", "hesaff_verify_get_query_inert",
@@ -518,6 +530,40 @@ def read_vocabulary(path):
     finally:
         L.hesaff_free(data)
     return arr.reshape(k.value, 128)
+
+
+def _cells_arrays(coarse, first):
+    """(coarse uint8 [C, 128], first uint32 [C + 1]), C-contiguous - anything else is a ValueError; the rules of `first` are the library's"""
+    coarse = _vocabulary_array(coarse)
+    first = np.ascontiguousarray(first)
+    if first.dtype.kind not in "iu" or first.shape != (coarse.shape[0] + 1,) or (first < 0).any() or (first > (1 << 20)).any():
+        raise ValueError("first is an integer array of C + 1 = %d row indices" % (coarse.shape[0] + 1))
+    return coarse, np.ascontiguousarray(first, dtype=np.uint32)
+
+
+def write_vocabulary_cells(path, coarse, first):
+    """hesaff_write_vocabulary_cells: coarse uint8 [C, 128], first [C + 1] -> a cells file ("HESAFFC1"), kept beside the vocabulary
+    file of the same first[C] rows."""
+    coarse, first = _cells_arrays(coarse, first)
+    rc = load_library().hesaff_write_vocabulary_cells(os.fsencode(path), coarse.shape[0], coarse.ctypes.data, first.ctypes.data)
+    if rc != 0:
+        raise HesaffError(rc, "hesaff_write_vocabulary_cells(%s)" % path)
+
+
+def read_vocabulary_cells(path):
+    """hesaff_read_vocabulary_cells: a cells file -> (coarse uint8 [C, 128], first uint32 [C + 1]); first[C] is the number of rows."""
+    L = load_library()
+    coarse = C.c_void_p(); first = C.c_void_p(); c = C.c_int(); k = C.c_int()
+    rc = L.hesaff_read_vocabulary_cells(os.fsencode(path), C.byref(coarse), C.byref(first), C.byref(c), C.byref(k))
+    if rc != 0:
+        raise HesaffError(rc, "hesaff_read_vocabulary_cells(%s): not a readable, whole cells file" % path)
+    try:
+        g = np.frombuffer(C.string_at(coarse.value, c.value * 128), dtype=np.uint8).copy()
+        f = np.frombuffer(C.string_at(first.value, (c.value + 1) * 4), dtype="<u4").astype(np.uint32)
+    finally:
+        L.hesaff_free(coarse)
+        L.hesaff_free(first)
+    return g.reshape(c.value, 128), f
 
 
 def write_words(path, keys, words, mr_size, vocabulary_size):
@@ -1067,6 +1113,80 @@ class HesaffContext:
         a, b, u = C.c_float(), C.c_float(), C.c_float()
         self._check(self.L.hesaff_get_training_ms(self.h, C.byref(a), C.byref(b), C.byref(u)))
         return a.value, b.value, u.value
+
+    # ---- vocabulary cells (hesaff_set_vocabulary_cells, include/hesaff_amd.h) ----
+    def set_vocabulary_cells(self, coarse, first=None):
+        """hesaff_set_vocabulary_cells: coarse uint8 [C, 128] and first [C + 1] (first[0] = 0, first[C] = K, strictly increasing: cell c
+        owns rows first[c] .. first[c + 1] - 1 of the vocabulary that is set), or None to remove the layer.  With a layer every
+        assignment takes the lowest nearest coarse row, then the lowest nearest row of that cell."""
+        if coarse is None:
+            self._check(self.L.hesaff_set_vocabulary_cells(self.h, 0, None, None))
+            return
+        coarse, first = _cells_arrays(coarse, first)
+        self._check(self.L.hesaff_set_vocabulary_cells(self.h, coarse.shape[0], coarse.ctypes.data, first.ctypes.data))
+
+    def vocabulary_cells(self):
+        """hesaff_get_vocabulary_cells: the number of cells of the layer that is set, 0 without one"""
+        c = C.c_int()
+        self._check(self.L.hesaff_get_vocabulary_cells(self.h, C.byref(c)))
+        return c.value
+
+    @property
+    def assign_cells_ms(self):
+        """HIP-event times (coarse assignment, grouping, assignment inside the cells) of the last assignment through a layer
+        (profiling level >= 1), in ms"""
+        a, b, f = C.c_float(), C.c_float(), C.c_float()
+        self._check(self.L.hesaff_get_assign_cells_ms(self.h, C.byref(a), C.byref(b), C.byref(f)))
+        return a.value, b.value, f.value
+
+    def build_vocabulary_cells(self, words, coarse):
+        """hesaff_build_vocabulary_cells: a layer for words uint8 [K, 128] given coarse uint8 [C, 128] -> (words in cell order uint8
+        [K, 128], order int32 [K] with order[new] = old row, coarse uint8 [C', 128], first uint32 [C' + 1]); C' <= C: coarse rows that
+        attract no row are dropped.  The context's own vocabulary is not touched."""
+        words = _vocabulary_array(words)
+        coarse = _vocabulary_array(coarse)
+        k, c = words.shape[0], coarse.shape[0]
+        words_out = np.zeros((k, 128), np.uint8); order = np.zeros(k, np.int32)
+        coarse_out = np.zeros((c, 128), np.uint8); first = np.zeros(c + 1, np.uint32)
+        kept = C.c_int(0)
+        self._check(self.L.hesaff_build_vocabulary_cells(self.h, k, words.ctypes.data, c, coarse.ctypes.data, words_out.ctypes.data, order.ctypes.data,
+                                                         coarse_out.ctypes.data, first.ctypes.data, C.byref(kept)))
+        return words_out, order, coarse_out[:kept.value].copy(), first[:kept.value + 1].copy()
+
+    def train_vocabulary_cells(self, desc, words, coarse, first, iterations):
+        """hesaff_train_vocabulary_cells: Lloyd iterations over desc uint8 [n, 128] on the rows `words` uint8 [K, 128] of a layer
+        (coarse, first), which stays fixed: every iteration assigns inside the cells -> (words, distortion, empty) as train_vocabulary."""
+        if not isinstance(desc, np.ndarray) or desc.dtype != np.uint8 or desc.ndim != 2 or desc.shape[1] != 128:
+            raise ValueError("descriptors are a uint8 array of shape [n, 128]")
+        desc = np.ascontiguousarray(desc)
+        coarse, first = _cells_arrays(coarse, first)
+        n, c = desc.shape[0], coarse.shape[0]
+        return self._train(lambda k, init, it, *a: self.L.hesaff_train_vocabulary_cells(self.h, n, desc.ctypes.data if n else None, k, init, c,
+                                                                                      coarse.ctypes.data, first.ctypes.data, it, *a),
+                           np.shape(words)[0], iterations, words)
+
+    def train_vocabulary_cells_device(self, ptr, n, stride, offset, words, coarse, first, iterations):
+        """hesaff_train_vocabulary_cells_device: the same on n descriptors in device memory, descriptor i at ptr + i * stride + offset"""
+        coarse, first = _cells_arrays(coarse, first)
+        c = coarse.shape[0]
+        return self._train(lambda k, init, it, *a: self.L.hesaff_train_vocabulary_cells_device(self.h, int(n), C.c_void_p(ptr), int(stride), int(offset), k,
+                                                                                             init, c, coarse.ctypes.data, first.ctypes.data, it, *a),
+                           np.shape(words)[0], iterations, words)
+
+    def train_cell_vocabulary(self, desc, k, cells, iterations, coarse_iterations):
+        """The composite: G = train_vocabulary(desc, cells, coarse_iterations); V0 = the rows desc[r * n // k]; build_vocabulary_cells(V0,
+        G); train_vocabulary_cells -> (words uint8 [k, 128], coarse uint8 [C', 128], first uint32 [C' + 1], distortion, empty).
+        Needs n >= k >= cells."""
+        if not isinstance(desc, np.ndarray) or desc.dtype != np.uint8 or desc.ndim != 2 or desc.shape[1] != 128:
+            raise ValueError("descriptors are a uint8 array of shape [n, 128]")
+        n, k, cells = desc.shape[0], int(k), int(cells)
+        if not n >= k >= cells >= 1:
+            raise ValueError("a cell vocabulary needs n >= k >= cells >= 1, not n = %d, k = %d, cells = %d" % (n, k, cells))
+        coarse = self.train_vocabulary(desc, cells, coarse_iterations)[0]
+        v0 = np.ascontiguousarray(desc[(np.arange(k, dtype=np.int64) * n) // k])
+        v0, _, coarse, first = self.build_vocabulary_cells(v0, coarse)
+        words, distortion, empty = self.train_vocabulary_cells(desc, v0, coarse, first, iterations)
+        return words, coarse, first, distortion, empty
 
     # ---- image index (hesaff_index_build, include/hesaff_amd.h) ----
     def build_index(self, images, vocabulary_size):

@@ -1043,6 +1043,7 @@ int hesaff_set_vocabulary(hesaff_ctx *c, int k, const uint8_t *words)
    }
    HIP_TRY(hipStreamSynchronize(c->stream()));   // nothing still reads the vocabulary that goes
    c->vocab = std::move(v);
+   c->cells.clear();   // (hesaff_set_vocabulary_cells: first[C] = K describes the vocabulary that went)
    if (k == 0) c->b_words.release();
    c->word_spans.clear();
    c->words_device_total = -1;

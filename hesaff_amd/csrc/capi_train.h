@@ -2,7 +2,8 @@
 // exact integer Lloyd iterations over k_assign_words (kernels_words.h) and the kernels of kernels_train.h.  Included at the end of
 // pipeline.hip, behind capi_stage.h (same translation unit).  A call works in a buffer of its own (TrainArrays, train_plan.h) that it
 // releases before it returns: the context's vocabulary, its words and its buffers are neither read nor written, and a context that
-// never trains allocates, launches and copies nothing here.
+// never trains allocates, launches and copies nothing here.  The same loop trains inside the fixed cells of a layer
+// (hesaff_train_vocabulary_cells*: capi_cells.h), whose arrays lie in the call's buffer as well.
 #pragma once
 
 namespace {
@@ -43,13 +44,25 @@ void update_words(hesaff_ctx *c, const TrainArena &m, const TrainArrays &t, int 
                       (const uint32_t *)m.ptr(t.acc.counts), k, rows_padded, m.ptr(t.rows), m.ptr(t.tiles), m.ptr(t.norms), m.ptr(t.acc.stats));
 }
 
-// the iterations of hesaff_train_vocabulary_device on n descriptors in device memory (arguments checked by the caller)
+// a fixed cell layer for the iterations (hesaff_train_vocabulary_cells: capi_cells.h): cells coarse rows and first[cells + 1], host memory
+struct TrainCells {
+   int cells;
+   const uint8_t *coarse;
+   const uint32_t *first;
+};
+
+// the iterations of hesaff_train_vocabulary_device on n descriptors in device memory (arguments checked by the caller).  With a layer
+// the assignment of every iteration is the cell-restricted one: the coarse step and the grouping once, before the first iteration (a
+// key's cell does not change while the coarse rows are fixed), k_assign_words_cells once per iteration.
 void train_on_device(hesaff_ctx *c, int n, const uint8_t *d_desc, long long stride, long long offset, int k, const uint8_t *init, int iterations,
-                     uint8_t *words_out, int64_t *distortion, int32_t *empty, int *iterations_done)
+                     uint8_t *words_out, int64_t *distortion, int32_t *empty, int *iterations_done, const TrainCells *layer = nullptr)
 {
    static_assert(HS_TRAIN_TILE == HS_WORD_TILE, "train_plan.h sizes the tiles k_assign_words reads");
    TrainArena m;
    const TrainArrays t = train_arrays(m, n, k);
+   CellLayerArrays la = {};
+   CellScratch ls = {};
+   if (layer) { la = cell_layer_arrays(m, layer->cells); ls = cell_scratch(m, n, layer->cells); }
    m.ensure();
    hipStream_t st = c->stream();
    const bool timed = c->profiling >= 1;
@@ -62,12 +75,26 @@ void train_on_device(hesaff_ctx *c, int n, const uint8_t *d_desc, long long stri
    if (init) HIP_TRY(hipMemcpyAsync(m.ptr(t.rows), init, (size_t)k * 128, hipMemcpyHostToDevice, st));
    else hipLaunchKernelGGL(k_sample_words, dim3((uint32_t)(((long long)k * 32 + 255) / 256)), dim3(256), 0, st, d_desc, stride, offset, n, k, m.ptr(t.rows));
    update_words(c, m, t, k);
+   CellsDevice cd = {};
+   if (layer) {
+      // the private packed copy of the coarse rows; the pageable copies return once the source has been read
+      std::vector<uint8_t> tiles;
+      std::vector<int32_t> norms;
+      pack_vocabulary(layer->coarse, layer->cells, tiles, norms);
+      HIP_TRY(hipMemcpyAsync(m.ptr(la.tiles), tiles.data(), tiles.size(), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(m.ptr(la.norms), norms.data(), norms.size() * 4, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(m.ptr(la.first), layer->first, la.first.bytes(), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      cd = cells_device(m.buf.p, la, layer->cells, m.buf.p, ls);
+      launch_cells_group(c, cd, d_desc, n, stride, offset, nullptr);
+   }
    TrainStats *h = (TrainStats *)c->h_small_end.ensure_small(sizeof(TrainStats));
    int done = iterations;
    for (int it = 1; it <= iterations; it++) {
       HIP_TRY(hipMemsetAsync(m.ptr(t.acc.stats), 0, sizeof(TrainStats), st));
       if (timed) HIP_TRY(hipEventRecord(ev[0], st));
-      launch_assign_kernel(st, m.ptr(t.tiles), m.ptr(t.norms), t.n_tiles, d_desc, n, stride, offset, m.ptr(t.assigned));
+      if (layer) launch_cells_fine(st, cd, m.ptr(t.tiles), m.ptr(t.norms), d_desc, n, stride, offset, m.ptr(t.assigned));
+      else launch_assign_kernel(st, m.ptr(t.tiles), m.ptr(t.norms), t.n_tiles, d_desc, n, stride, offset, m.ptr(t.assigned));
       if (timed) HIP_TRY(hipEventRecord(ev[1], st));
       accumulate_words(c, m, t.acc, d_desc, stride, offset, m.ptr(t.assigned), 2, n, k);
       if (timed) HIP_TRY(hipEventRecord(ev[2], st));

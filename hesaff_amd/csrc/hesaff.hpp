@@ -192,6 +192,61 @@ struct AffineHessianDetector {
    const std::vector<int64_t> &distortion() const { return distortion_; }   // of the last trainVocabulary: distortion()[t] belongs to V_t
    const std::vector<int32_t> &emptyWords() const { return empty_; }
 
+   // No counterpart in the reference (hesaff_set_vocabulary_cells, include/hesaff_amd.h): a cell layer over the vocabulary that is set -
+   // c coarse rows of 128 bytes and first[c + 1], cell j owning rows first[j] .. first[j + 1] - 1 (copied; c = 0: none).  With one set
+   // a key's word is the lowest nearest row of the cell of its lowest nearest coarse row.  setVocabulary removes the layer.
+   void setVocabularyCells(const uint8_t *coarse, const uint32_t *first, int c)
+   {
+      const int rc = hesaff_set_vocabulary_cells(ctx_, c, coarse, first);
+      if (rc == HESAFF_ERR_ARG)
+         throw std::invalid_argument("a cell layer needs a vocabulary of K rows, 0 <= c <= K coarse rows and first[0] = 0 < ... < first[c] = K");
+      if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+      words_.clear();
+   }
+   // A layer for k rows given c coarse rows (hesaff_build_vocabulary_cells): `rows` is put into cell order, order[new] = old row, the
+   // coarse rows that attract a row and their `first` are returned.  The detector's own vocabulary does not change.
+   struct VocabularyCells {
+      std::vector<uint8_t> coarse;
+      std::vector<uint32_t> first;
+      std::vector<int32_t> order;
+      int cells() const { return (int)first.size() - 1; }
+   };
+   VocabularyCells buildVocabularyCells(std::vector<uint8_t> &rows, const uint8_t *coarse, int c)
+   {
+      const int k = (int)(rows.size() / 128);
+      VocabularyCells v;
+      std::vector<uint8_t> sorted(rows.size());
+      v.coarse.resize((size_t)(c > 0 ? c : 0) * 128);
+      v.first.resize((size_t)(c > 0 ? c : 0) + 1);
+      v.order.resize((size_t)k);
+      int kept = 0;
+      const int rc = hesaff_build_vocabulary_cells(ctx_, k, rows.data(), c, coarse, sorted.data(), v.order.data(), v.coarse.data(), v.first.data(), &kept);
+      if (rc == HESAFF_ERR_ARG) throw std::invalid_argument("a cell layer is built for 1 <= k <= 2^20 rows from 1 <= c <= k coarse rows");
+      if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+      v.coarse.resize((size_t)kept * 128);
+      v.first.resize((size_t)kept + 1);
+      rows.swap(sorted);
+      return v;
+   }
+   // trainVocabulary on the rows of a layer, which stays fixed (hesaff_train_vocabulary_cells): `rows` are the initial k rows in the
+   // layer's order -> the k rows; distortion() and emptyWords() as for trainVocabulary.
+   std::vector<uint8_t> trainVocabularyCells(const uint8_t *desc, int n, const std::vector<uint8_t> &rows, const VocabularyCells &cells, int iterations)
+   {
+      const int k = (int)(rows.size() / 128);
+      std::vector<uint8_t> out(rows.size());
+      distortion_.assign((size_t)(iterations > 0 ? iterations : 0), 0);
+      empty_.assign(distortion_.size(), 0);
+      int done = 0;
+      const int rc = hesaff_train_vocabulary_cells(ctx_, n, desc, k, rows.data(), cells.cells(), cells.coarse.data(), cells.first.data(), iterations, out.data(),
+                                                   distortion_.data(), empty_.data(), &done);
+      if (rc != HESAFF_OK) { distortion_.clear(); empty_.clear(); }
+      if (rc == HESAFF_ERR_ARG) throw std::invalid_argument("cell training needs 1 <= n <= 2^24 descriptors, the k rows of the layer and iterations >= 1");
+      if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+      distortion_.resize((size_t)done);
+      empty_.resize((size_t)done);
+      return out;
+   }
+
    // No counterpart in the reference (hesaff_index_build, include/hesaff_amd.h): an inverted file with integer tf-idf scoring over the
    // words of a collection, built on the device.  words: the words of all images one after the other, counts[i] of them for image i,
    // key j's word at words[j * wordStride] (1: packed; 2: the (word, dist2) rows words() holds); vocabularySize: K, every word in

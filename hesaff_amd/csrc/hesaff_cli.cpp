@@ -52,6 +52,14 @@
 //       with the run's other options (--descriptor, --orientation, --orientations, --max-keypoints, --grid, --fast); no per-image file is
 //       written, <vocabulary file> is, and one line per iteration is printed: the distortion and the number of empty words.  At most 2^24
 //       keys: a list that yields more stops with a message naming the count.
+//   hesaff <image> --vocabulary <vocabulary file> --cells <cells file>      (and with --batch)
+//       a cell layer over the vocabulary (hesaff_read_vocabulary_cells: "HESAFFC1", coarse rows and each cell's first row; its row count must
+//       be the vocabulary's): a key is compared with the coarse rows and then only with the rows of its cell (hesaff_set_vocabulary_cells).
+//       The files written are the same; the vocabulary file stays an ordinary flat vocabulary of the same rows.
+//   hesaff --batch <list file> --train-vocabulary <vocabulary file> --words K --cells C [--iterations T] [--coarse-iterations Tc]
+//       trains C coarse rows (Tc = 10 iterations at most), spreads K initial rows over the list's keys, sorts them into the cells of their
+//       nearest coarse rows (hesaff_build_vocabulary_cells) and trains them inside the cells (hesaff_train_vocabulary_cells); writes
+//       <vocabulary file> and <vocabulary file>.cells.  Needs K >= C.
 //   hesaff --search <list of .hesaff.words files> --query <.hesaff.words file> [--top M] [--device D]
 //       builds an image index on device D (default 0) from the words files the list names, one per line (hesaff_index_build: an inverted
 //       file with integer tf-idf weights; every file must state the same vocabulary size), queries it with the words of the query file
@@ -131,7 +139,7 @@ bool parse_devices(const char *spec, std::vector<int> &out)
 // through hesaff_process_files - decode threads -> device -> writer threads, bounded memory - on its own host thread.
 int run_batch_mode(const char *list_path, const char *devices_spec, int out_format, bool dynamic, int fast, int resume, int host_share, int runtime_nice,
                    int max_keypoints, int orientation, int grid_rows, int grid_cols, int descriptor, int orientations,
-                   const uint8_t *vocabulary, int vocabulary_size)
+                   const uint8_t *vocabulary, int vocabulary_size, const uint8_t *cells_coarse, const uint32_t *cells_first, int cells)
 {
    std::ifstream lf(list_path);
    if (!lf) { fprintf(stderr, "hesaff: cannot read list '%s'\n", list_path); return 1; }
@@ -188,6 +196,11 @@ int run_batch_mode(const char *list_path, const char *devices_spec, int out_form
       hesaff_set_descriptor(ctx, descriptor);
       if (vocabulary_size > 0 && hesaff_set_vocabulary(ctx, vocabulary_size, vocabulary) != HESAFF_OK) {
          errs[(size_t)rank] = hesaff_last_error(ctx);
+         hesaff_destroy(ctx);
+         return;
+      }
+      if (cells > 0 && hesaff_set_vocabulary_cells(ctx, cells, cells_coarse, cells_first) != HESAFF_OK) {
+         errs[(size_t)rank] = "the cells file does not describe the vocabulary";
          hesaff_destroy(ctx);
          return;
       }
@@ -271,7 +284,7 @@ struct DescSink {
 };
 
 int run_train_mode(const char *list_path, const char *devices_spec, const char *out_path, int k, int iterations, int fast, int max_keypoints, int orientation,
-                   int grid_rows, int grid_cols, int descriptor, int orientations)
+                   int grid_rows, int grid_cols, int descriptor, int orientations, int cells, int coarse_iterations)
 {
    std::ifstream lf(list_path);
    if (!lf) { fprintf(stderr, "hesaff: cannot read list '%s'\n", list_path); return 1; }
@@ -343,7 +356,31 @@ int run_train_mode(const char *list_path, const char *devices_spec, const char *
    std::vector<int64_t> distortion((size_t)iterations);
    std::vector<int32_t> empty((size_t)iterations);
    int done = 0;
-   if (hesaff_train_vocabulary(ctx, total, desc.data(), k, nullptr, iterations, rows.data(), distortion.data(), empty.data(), &done) != HESAFF_OK) {
+   if (cells > 0) {
+      // the composite: C coarse rows, K initial rows spread over the keys, sorted into cells, trained inside them
+      std::vector<uint8_t> coarse((size_t)cells * 128), v0((size_t)k * 128), kept((size_t)cells * 128);
+      std::vector<uint32_t> first((size_t)cells + 1);
+      std::vector<int32_t> order((size_t)k);
+      int n_cells = 0;
+      if (hesaff_train_vocabulary(ctx, total, desc.data(), cells, nullptr, coarse_iterations, coarse.data(), nullptr, nullptr, nullptr) != HESAFF_OK) {
+         fprintf(stderr, "hesaff: training the coarse rows failed: %s\n", hesaff_last_error(ctx));
+         return 1;
+      }
+      for (long long r = 0; r < k; r++) memcpy(&v0[(size_t)r * 128], &desc[(size_t)(r * total / k) * 128], 128);
+      if (hesaff_build_vocabulary_cells(ctx, k, v0.data(), cells, coarse.data(), rows.data(), order.data(), kept.data(), first.data(), &n_cells) != HESAFF_OK ||
+          hesaff_train_vocabulary_cells(ctx, total, desc.data(), k, rows.data(), n_cells, kept.data(), first.data(), iterations, v0.data(), distortion.data(),
+                                        empty.data(), &done) != HESAFF_OK) {
+         fprintf(stderr, "hesaff: training failed: %s\n", hesaff_last_error(ctx));
+         return 1;
+      }
+      rows.swap(v0);
+      const std::string cells_path = std::string(out_path) + ".cells";
+      if (hesaff_write_vocabulary_cells(cells_path.c_str(), n_cells, kept.data(), first.data()) != HESAFF_OK) {
+         fprintf(stderr, "hesaff: cannot write '%s'\n", cells_path.c_str());
+         return 1;
+      }
+      std::cout << n_cells << " of " << cells << " cells hold rows" << std::endl;
+   } else if (hesaff_train_vocabulary(ctx, total, desc.data(), k, nullptr, iterations, rows.data(), distortion.data(), empty.data(), &done) != HESAFF_OK) {
       fprintf(stderr, "hesaff: training failed: %s\n", hesaff_last_error(ctx));
       return 1;
    }
@@ -484,8 +521,8 @@ int main(int argc, char **argv)
       const char *devices = nullptr, *list = nullptr;
       int out_format = HESAFF_OUT_TEXT, fast = 0, host_share = 1, runtime_nice = -1, max_keypoints = 0, orientation = HESAFF_ORI_UP, grid_rows = 1, grid_cols = 1, descriptor = HESAFF_DESC_SIFT, orientations = 1;
       bool bad = false, grid = false, dynamic = false, words_only = false;
-      const char *vocabulary_path = nullptr, *train_path = nullptr;
-      int resume = 0, train_words = 0, train_iterations = 10;
+      const char *vocabulary_path = nullptr, *train_path = nullptr, *cells_arg = nullptr;
+      int resume = 0, train_words = 0, train_iterations = 10, train_cells = 0, coarse_iterations = 10;
       for (int i = 1; i < argc && !bad; i += 2) {
          if (strcmp(argv[i], "--resume") == 0) { resume = 1; i--; continue; }
          if (strcmp(argv[i], "--resume=strict") == 0) { resume = 2; i--; continue; }   // also count the rows of existing text outputs
@@ -495,6 +532,13 @@ int main(int argc, char **argv)
          else if (strcmp(argv[i], "--devices") == 0) devices = argv[i + 1];
          else if (strcmp(argv[i], "--vocabulary") == 0) vocabulary_path = argv[i + 1];
          else if (strcmp(argv[i], "--train-vocabulary") == 0) train_path = argv[i + 1];
+         else if (strcmp(argv[i], "--cells") == 0) cells_arg = argv[i + 1];   // a cells file, or with --train-vocabulary the number of cells
+         else if (strcmp(argv[i], "--coarse-iterations") == 0) {
+            char *end = nullptr;
+            const long v = strtol(argv[i + 1], &end, 10);
+            if (argv[i + 1][0] < '0' || argv[i + 1][0] > '9' || *end != 0 || v < 1 || v > (1L << 20)) bad = true;
+            else coarse_iterations = (int)v;
+         }
          else if (strcmp(argv[i], "--words") == 0 || strcmp(argv[i], "--iterations") == 0) {
             // digits only, at least 1: K up to 2^20 rows, T up to a million iterations
             char *end = nullptr;
@@ -548,12 +592,22 @@ int main(int argc, char **argv)
       if (words_only && !vocabulary_path) bad = true;
       // training takes the list's keys and writes one vocabulary file: it needs --words, and nothing that is about per-image files
       if (train_path && (train_words < 1 || vocabulary_path || words_only || resume || dynamic || out_format != HESAFF_OUT_TEXT)) bad = true;
-      if (!train_path && (train_words > 0 || train_iterations != 10)) bad = true;
-      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--vocabulary <vocabulary file> [--words-only]] [--train-vocabulary <vocabulary file> --words K [--iterations T]] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1] [--max-keypoints N] [--orientations 1..4] [--descriptor sift|rootsift] [--orientation up|dominant] [--grid RxC]\n"); return 1; }
+      if (!train_path && (train_words > 0 || train_iterations != 10 || coarse_iterations != 10)) bad = true;
+      if (cells_arg && !train_path && !vocabulary_path) bad = true;
+      if (cells_arg && train_path) {   // digits only, 1 .. K
+         char *end = nullptr;
+         const long v = strtol(cells_arg, &end, 10);
+         if (cells_arg[0] < '0' || cells_arg[0] > '9' || *end != 0 || v < 1 || v > train_words) bad = true;
+         else train_cells = (int)v;
+      }
+      if (coarse_iterations != 10 && !train_cells) bad = true;
+      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--vocabulary <vocabulary file> [--words-only]] [--train-vocabulary <vocabulary file> --words K [--iterations T]] [--cells <cells file>|C [--coarse-iterations Tc]] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1] [--max-keypoints N] [--orientations 1..4] [--descriptor sift|rootsift] [--orientation up|dominant] [--grid RxC]\n"); return 1; }
       if (train_path)
-         return run_train_mode(list, devices, train_path, train_words, train_iterations, fast, max_keypoints, orientation, grid_rows, grid_cols, descriptor, orientations);
-      uint8_t *vocabulary = nullptr;
-      int vocabulary_size = 0;
+         return run_train_mode(list, devices, train_path, train_words, train_iterations, fast, max_keypoints, orientation, grid_rows, grid_cols, descriptor, orientations, train_cells,
+                               coarse_iterations);
+      uint8_t *vocabulary = nullptr, *cells_coarse = nullptr;
+      uint32_t *cells_first = nullptr;
+      int vocabulary_size = 0, cells = 0, cells_rows = 0;
       if (vocabulary_path) {   // before any image is read
          if (hesaff_read_vocabulary(vocabulary_path, &vocabulary, &vocabulary_size) != HESAFF_OK) {
             fprintf(stderr, "hesaff: cannot read vocabulary '%s' (a HESAFFV1 file with rows of 128 bytes expected)\n", vocabulary_path);
@@ -561,9 +615,16 @@ int main(int argc, char **argv)
          }
          out_format = words_only ? HESAFF_OUT_WORDS : (out_format | HESAFF_OUT_WORDS);
       }
+      if (cells_arg) {   // likewise
+         if (hesaff_read_vocabulary_cells(cells_arg, &cells_coarse, &cells_first, &cells, &cells_rows) != HESAFF_OK || cells_rows != vocabulary_size) {
+            fprintf(stderr, "hesaff: cannot read cells '%s' (a HESAFFC1 file over the %d rows of the vocabulary expected)\n", cells_arg, vocabulary_size);
+            hesaff_free(vocabulary); hesaff_free(cells_coarse); hesaff_free(cells_first);
+            return 1;
+         }
+      }
       const int brc = run_batch_mode(list, devices, out_format, dynamic, fast, resume, host_share, runtime_nice, max_keypoints, orientation, grid_rows, grid_cols, descriptor,
-                                     orientations, vocabulary, vocabulary_size);
-      hesaff_free(vocabulary);
+                                     orientations, vocabulary, vocabulary_size, cells_coarse, cells_first, cells);
+      hesaff_free(vocabulary); hesaff_free(cells_coarse); hesaff_free(cells_first);
       return brc;
    }
    if (argc > 1) {
@@ -581,6 +642,22 @@ int main(int argc, char **argv)
          }
       }
       struct FreeVocabulary { uint8_t *&p; ~FreeVocabulary() { hesaff_free(p); } } free_vocabulary{vocabulary};
+      // --cells <file> behind the image (the last one counts): a layer over that vocabulary, read before the image as well
+      uint8_t *cells_coarse = nullptr;
+      uint32_t *cells_first = nullptr;
+      int cells = 0;
+      struct FreeCells { uint8_t *&g; uint32_t *&f; ~FreeCells() { hesaff_free(g); hesaff_free(f); } } free_cells{cells_coarse, cells_first};
+      for (int i = 2; i < argc; i++) {
+         if (strcmp(argv[i], "--cells") != 0) continue;
+         hesaff_free(cells_coarse); hesaff_free(cells_first);
+         cells_coarse = nullptr; cells_first = nullptr;
+         int cells_rows = 0;
+         const char *cname = i + 1 < argc ? argv[++i] : "";
+         if (!vocabulary || hesaff_read_vocabulary_cells(cname, &cells_coarse, &cells_first, &cells, &cells_rows) != HESAFF_OK || cells_rows != vocabulary_size) {
+            fprintf(stderr, "hesaff: cannot read cells '%s' (--vocabulary and a HESAFFC1 file over its rows expected)\n", cname);
+            return 1;
+         }
+      }
       uint8_t *data = nullptr;
       int w = 0, h = 0, ch = 0;
       if (hesaff_read_image(argv[1], &data, &w, &h, &ch) != HESAFF_OK) {
@@ -657,6 +734,7 @@ int main(int argc, char **argv)
          detector.setOrientationCount(orientations);
          detector.setDescriptor(descriptor);
          if (vocabulary) detector.setVocabulary(vocabulary, vocabulary_size);
+         if (cells_coarse) detector.setVocabularyCells(cells_coarse, cells_first, cells);
          const auto t1 = std::chrono::steady_clock::now();
          detector.detectPyramidKeypoints(data, w, h, ch);
          const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();

@@ -27,6 +27,7 @@
 
 #include "../../include/hesaff_amd.h"
 #include "export_fmt.h"
+#include "cells_plan.h"   // cells_first_ok: the rule a cells file is read and written by
 
 namespace {
 
@@ -1233,6 +1234,73 @@ int hesaff_read_vocabulary(const char *path, uint8_t **words, int *k)
    close(fd);
    if (rc != HESAFF_OK) { free(buf); return rc; }
    *words = buf; *k = (int)cnt;
+   return HESAFF_OK;
+}
+
+// Cells file (hesaff_set_vocabulary_cells), kept beside the vocabulary file of the same rows.  Little-endian:
+//   char magic[8] = "HESAFFC1"; uint32 dim = 128; uint32 cells; uint32 rows; uint32 reserved = 0; cells x uint8[128]; (cells + 1) x uint32
+int hesaff_write_vocabulary_cells(const char *path, int cells, const uint8_t *coarse, const uint32_t *first)
+{
+   if (!path || !coarse || !first || cells < 1 || cells > (1 << 20)) return HESAFF_ERR_ARG;
+   if (!hesaff_plan::cells_first_ok(first, cells, (int64_t)first[cells])) return HESAFF_ERR_ARG;
+   HOSTIO_TRY
+   std::vector<char> body((size_t)cells * 128 + ((size_t)cells + 1) * 4);
+   memcpy(body.data(), coarse, (size_t)cells * 128);
+   memcpy(body.data() + (size_t)cells * 128, first, ((size_t)cells + 1) * 4);
+   std::string part;
+   const int fd = open_part(path, part);
+   if (fd < 0) return HESAFF_ERR_IO;
+   char head[24];
+   memcpy(head, "HESAFFC1", 8);
+   const uint32_t dim = 128, cnt = (uint32_t)cells, rows = first[cells], reserved = 0;
+   memcpy(head + 8, &dim, 4); memcpy(head + 12, &cnt, 4); memcpy(head + 16, &rows, 4); memcpy(head + 20, &reserved, 4);
+   return finish_part(fd, write_head_body(fd, head, 24, body.data(), body.size()), part, path);
+   HOSTIO_CATCH
+}
+
+// -> the coarse rows and first[cells + 1], malloc'ed (hesaff_free each).  HESAFF_ERR_IO: the file cannot be read, or is not a whole
+// cells file (wrong magic, dim other than 128, cells outside 1 .. rows, rows beyond 2^20, a reserved word other than 0, a size other
+// than 24 + 128 cells + 4 (cells + 1), or a `first` that is not 0 .. rows strictly increasing).
+int hesaff_read_vocabulary_cells(const char *path, uint8_t **coarse, uint32_t **first, int *cells, int *rows)
+{
+   if (!path || !coarse || !first || !cells || !rows) return HESAFF_ERR_ARG;
+   *coarse = nullptr; *first = nullptr; *cells = 0; *rows = 0;
+   const int fd = open(path, O_RDONLY | O_CLOEXEC);
+   if (fd < 0) return HESAFF_ERR_IO;
+   int rc = HESAFF_ERR_IO;
+   uint8_t *buf = nullptr;
+   uint32_t *fst = nullptr;
+   const off_t size = lseek(fd, 0, SEEK_END);
+   char head[24];
+   uint32_t dim = 0, cnt = 0, k = 0, reserved = 1;
+   if (size >= 24 && pread(fd, head, 24, 0) == 24 && memcmp(head, "HESAFFC1", 8) == 0) {
+      memcpy(&dim, head + 8, 4); memcpy(&cnt, head + 12, 4); memcpy(&k, head + 16, 4); memcpy(&reserved, head + 20, 4);
+      const size_t row_bytes = (size_t)cnt * 128, bytes = row_bytes + ((size_t)cnt + 1) * 4;
+      if (dim == 128 && reserved == 0 && cnt >= 1 && cnt <= k && k <= (1u << 20) && (unsigned long long)size == 24ull + bytes) {
+         std::vector<char> body;
+         try { body.resize(bytes); } catch (...) { close(fd); return HESAFF_ERR_NOMEM; }
+         size_t done = 0;
+         while (done < bytes) {
+            const ssize_t r = pread(fd, body.data() + done, bytes - done, (off_t)(24 + done));
+            if (r < 0 && errno == EINTR) continue;
+            if (r <= 0) break;
+            done += (size_t)r;
+         }
+         if (done == bytes) {
+            buf = (uint8_t *)malloc(row_bytes);
+            fst = (uint32_t *)malloc(((size_t)cnt + 1) * 4);
+            if (!buf || !fst) rc = HESAFF_ERR_NOMEM;
+            else {
+               memcpy(buf, body.data(), row_bytes);
+               memcpy(fst, body.data() + row_bytes, ((size_t)cnt + 1) * 4);
+               if (hesaff_plan::cells_first_ok(fst, cnt, k)) rc = HESAFF_OK;
+            }
+         }
+      }
+   }
+   close(fd);
+   if (rc != HESAFF_OK) { free(buf); free(fst); return rc; }
+   *coarse = buf; *first = fst; *cells = (int)cnt; *rows = (int)k;
    return HESAFF_OK;
 }
 

@@ -42,6 +42,7 @@
 #include "kernels_jpeg.h"
 #include "kernels_words.h"
 #include "kernels_train.h"
+#include "kernels_cells.h"
 #include "kernels_index.h"
 #include "kernels_verify.h"
 #include "chunk_engine.h"
@@ -50,6 +51,7 @@
 #include "context_tables.h"
 #include "group_schedule.h"
 #include "train_plan.h"
+#include "cells_plan.h"
 #include "index_plan.h"
 #include "verify_plan.h"
 
@@ -449,6 +451,18 @@ struct hesaff_ctx {
    DevEvent ev_assign[2];              // profiling: brackets of the last k_assign_words launch
    bool assign_timed = false;          // ev_assign holds a launch of the last batch
    float train_ms[3] = {0.0f, 0.0f, 0.0f};   // hesaff_get_training_ms: assignment, accumulation, update of the last training call (profiling >= 1)
+   // hesaff_set_vocabulary_cells: a cell layer over the vocabulary (cells_plan.h: CellLayerArrays in `layer`, CellScratch for `cap` keys
+   // in `scratch`, which is allocated by the first assignment through the layer and only grows); c = 0: none, nothing here is
+   // allocated, launched or copied and the assignment is k_assign_words over the whole vocabulary
+   struct Cells {
+      DevBuf layer, scratch;
+      CellLayerArrays a;
+      int c = 0;
+      int64_t cap = 0;                 // keys the scratch is laid out for
+      std::vector<DevEvent> ev;        // profiling: four per slice of the last assignment (start, coarse, grouped, fine)
+      int timed_slices = 0;            // slices of the last assignment that ev brackets
+      void clear() { layer.release(); scratch.release(); c = 0; cap = 0; timed_slices = 0; }
+   } cells;
    // hesaff_index_build: the inverted file over visual words (index_plan.h: IndexArrays in `tables`, the posting lists in `lists`);
    // not built: nothing here is allocated, launched or copied
    struct Index {
@@ -1257,17 +1271,103 @@ void launch_assign_kernel(hipStream_t st, const void *tiles, const void *norms, 
                       (const hs_v4i *)tiles, (const int32_t *)norms, n_tiles, (int32_t *)d_out);
 }
 
-// k_assign_words (kernels_words.h) over n descriptors in device memory, on the main stream: (word, dist2) per key into d_out.
-// With profiling on, the launch is bracketed for hesaff_get_assign_ms.
+// A cell layer and its working arrays as the kernels receive them (kernels_cells.h): the context's (launch_assign_cells) or the private
+// ones of a training call (capi_train.h)
+struct CellsDevice {
+   const void *tiles, *norms;   // the packed coarse rows
+   int n_tiles, c;
+   const uint32_t *first;       // [c + 1]
+   int32_t *coarse;
+   uint32_t *perm, *sub, *cursor, *item_first, *block_sums, *total;
+   size_t sub_bytes;
+   int slots;
+};
+CellsDevice cells_device(void *layer, const CellLayerArrays &a, int cells, void *scratch, const CellScratch &s)
+{
+   const auto at = [](void *base, size_t off) { return (void *)((char *)base + off); };
+   CellsDevice d;
+   d.tiles = at(layer, a.tiles.off); d.norms = at(layer, a.norms.off); d.first = (const uint32_t *)at(layer, a.first.off);
+   d.n_tiles = a.n_tiles; d.c = cells;
+   d.coarse = (int32_t *)at(scratch, s.coarse.off); d.perm = (uint32_t *)at(scratch, s.perm.off); d.sub = (uint32_t *)at(scratch, s.sub.off);
+   d.cursor = (uint32_t *)at(scratch, s.cursor.off); d.item_first = (uint32_t *)at(scratch, s.item_first.off);
+   d.block_sums = (uint32_t *)at(scratch, s.block_sums.off); d.total = (uint32_t *)at(scratch, s.total.off);
+   d.sub_bytes = s.sub.bytes(); d.slots = s.slots;
+   return d;
+}
+
+// the first two steps of an assignment through cells, for 1 <= n <= 2^24 keys: every key's coarse cell, then the keys grouped by cell
+// (perm, the cursor) and each cell's first work item (item_first).  ev: two events, recorded behind either step, or nullptr.
+void launch_cells_group(hesaff_ctx *c, const CellsDevice &d, const void *d_desc, int n, long long stride, long long offset, const DevEvent *ev)
+{
+   hipStream_t st = c->stream();
+   launch_assign_kernel(st, d.tiles, d.norms, d.n_tiles, d_desc, n, stride, offset, d.coarse);
+   if (ev) HIP_TRY(hipEventRecord(ev[0], st));
+   HIP_TRY(hipMemsetAsync(d.sub, 0, d.sub_bytes, st));
+   // (k_word_histogram and k_word_scatter: the same grid, so that a key's wave, and with it its slot, is the same in both)
+   const uint32_t key_blocks = (uint32_t)((n + 255) / 256);
+   hipLaunchKernelGGL(k_word_histogram, dim3(key_blocks), dim3(256), 0, st, (const int32_t *)d.coarse, 2, n, d.sub, d.slots, (unsigned long long *)nullptr);
+   LoadU32 load;
+   load.p = d.sub;
+   exclusive_scan(c, load, (long long)d.c * d.slots, d.cursor, d.total, d.block_sums);
+   hipLaunchKernelGGL(k_word_scatter, dim3(key_blocks), dim3(256), 0, st, (const int32_t *)d.coarse, 2, n, d.cursor, d.slots, d.perm);
+   LoadCellItems items;
+   items.p = d.cursor; items.slots = d.slots;
+   exclusive_scan(c, items, (long long)d.c, d.item_first, d.item_first + d.c, d.block_sums);
+   if (ev) HIP_TRY(hipEventRecord(ev[1], st));
+}
+
+// the third step: k_assign_words_cells over the grouped keys against a packed flat vocabulary, (word, dist2) per key into d_out
+void launch_cells_fine(hipStream_t st, const CellsDevice &d, const void *tiles, const void *norms, const void *d_desc, int n, long long stride, long long offset,
+                       void *d_out)
+{
+   const long long items = cells_item_bound(n, d.c);
+   const long long blocks = (items + HS_WORD_BLOCK_WAVES - 1) / HS_WORD_BLOCK_WAVES;
+   hipLaunchKernelGGL(k_assign_words_cells, dim3((uint32_t)blocks), dim3(HS_WORD_BLOCK_WAVES * 64), 0, st, (const uint8_t *)d_desc, stride, offset,
+                      (const uint32_t *)d.perm, (const uint32_t *)d.cursor, d.slots, (const uint32_t *)d.item_first, d.first, d.c, (const hs_v4i *)tiles,
+                      (const int32_t *)norms, (int32_t *)d_out);
+}
+
+// the context's assignment with a layer set: slices of at most 2^24 keys (what the scratch is ever sized for), each through the three
+// steps; the results are per key, so the cut is invisible.  With profiling on, four events per slice for hesaff_get_assign_cells_ms.
+void launch_assign_cells(hesaff_ctx *c, const void *d_desc, long long n, long long stride, long long offset, void *d_out)
+{
+   hesaff_ctx::Cells &cl = c->cells;
+   cl.timed_slices = 0;
+   cl.cap = std::max<int64_t>(cl.cap, std::min<int64_t>(n, HS_CELLS_SLICE_KEYS));
+   StagePlan p;
+   const CellScratch s = cell_scratch(p, cl.cap, cl.c);
+   cl.scratch.ensure(p.bytes());   // (grows with the keys and with the cells of a later layer; never shrinks)
+   const CellsDevice d = cells_device(cl.layer.p, cl.a, cl.c, cl.scratch.p, s);
+   const bool timed = c->profiling >= 1;
+   const int64_t slices = cells_slice_count(n, HS_CELLS_SLICE_KEYS);
+   if (timed) while ((int64_t)cl.ev.size() < 4 * slices) cl.ev.emplace_back(hipEventDefault);
+   hipStream_t st = c->stream();
+   for (int64_t i = 0; i < slices; i++) {
+      const int64_t begin = cells_slice_begin(i, HS_CELLS_SLICE_KEYS);
+      const int m = (int)cells_slice_keys(i, n, HS_CELLS_SLICE_KEYS);
+      const uint8_t *desc = (const uint8_t *)d_desc + begin * stride;
+      const DevEvent *ev = timed ? &cl.ev[(size_t)(4 * i)] : nullptr;
+      if (ev) HIP_TRY(hipEventRecord(ev[0], st));
+      launch_cells_group(c, d, desc, m, stride, offset, ev ? ev + 1 : nullptr);
+      launch_cells_fine(st, d, c->vocab.tiles.p, c->vocab.norms.p, desc, m, stride, offset, (int32_t *)d_out + 2 * begin);
+      if (ev) HIP_TRY(hipEventRecord(ev[3], st));
+   }
+   if (timed) cl.timed_slices = (int)slices;
+}
+
+// The assignment (kernels_words.h; through the cell layer where one is set: kernels_cells.h) over n descriptors in device memory, on the
+// main stream: (word, dist2) per key into d_out.  With profiling on, it is bracketed for hesaff_get_assign_ms.
 void launch_assign_words(hesaff_ctx *c, const void *d_desc, long long n, long long stride, long long offset, void *d_out)
 {
    c->assign_timed = false;
+   c->cells.timed_slices = 0;
    if (n <= 0) return;
    hipStream_t st = c->stream();
    const bool timed = c->profiling >= 1;
    if (timed && !c->ev_assign[0]) { c->ev_assign[0] = DevEvent(hipEventDefault); c->ev_assign[1] = DevEvent(hipEventDefault); }
    if (timed) HIP_TRY(hipEventRecord(c->ev_assign[0], st));
-   launch_assign_kernel(st, c->vocab.tiles.p, c->vocab.norms.p, c->vocab.n_tiles, d_desc, n, stride, offset, d_out);
+   if (c->cells.c > 0) launch_assign_cells(c, d_desc, n, stride, offset, d_out);
+   else launch_assign_kernel(st, c->vocab.tiles.p, c->vocab.norms.p, c->vocab.n_tiles, d_desc, n, stride, offset, d_out);
    if (timed) { HIP_TRY(hipEventRecord(c->ev_assign[1], st)); c->assign_timed = true; }
 }
 
@@ -1550,5 +1650,6 @@ void pack_regions(hesaff_ctx *c, uint32_t n_hess, int B, hesaff_region *d_region
 #include "capi_impl.h"
 #include "capi_stage.h"
 #include "capi_train.h"
+#include "capi_cells.h"
 #include "capi_index.h"
 #include "capi_verify.h"

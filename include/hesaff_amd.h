@@ -55,6 +55,7 @@ extern "C" {
  *    hesaff_get_training_ms): symbols only, version 8.
  *    And for the image index (hesaff_index_build and the nine symbols declared with it): symbols only, version 8.
  *    And for spatial verification (hesaff_verify_matches and the six symbols declared with it): symbols only, version 8.
+ *    And for vocabulary cells (hesaff_set_vocabulary_cells and the eight symbols declared with it): symbols only, version 8.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -606,6 +607,55 @@ int hesaff_train_vocabulary(hesaff_ctx *ctx, int64_t n, const uint8_t *desc, int
                             int64_t *distortion, int32_t *empty, int *iterations_done);
 int hesaff_stage_accumulate_words(hesaff_ctx *ctx, int n, const uint8_t *desc, const int32_t *words, int k, uint32_t *sums_out, uint32_t *counts_out);
 int hesaff_get_training_ms(const hesaff_ctx *ctx, float *assign_ms, float *accumulate_ms, float *update_ms);
+
+/* Vocabulary cells (no counterpart in the reference): a coarse layer over a set vocabulary, so that a key is compared with C coarse
+ * rows and then only with the rows of one cell - C + K / C exact distances instead of K.  Symbols only, version 8.
+ * A cell layer over a vocabulary of K rows is C coarse rows g_c of 128 bytes, 1 <= C <= K, and first[0 .. C] with first[0] = 0,
+ * first[C] = K, strictly increasing: cell c owns rows first[c] .. first[c + 1] - 1, and no cell is empty.  For a key with bytes d, dist2
+ * being hesaff_set_vocabulary's:
+ *     cell     = the LOWEST c of least dist2(d, g_c)
+ *     word     = the LOWEST k in [first[cell], first[cell + 1]) of least dist2(d, w_k)
+ *     dist2    = dist2(d, w_word)
+ * Integers, exact, ties decided, no dependence on launch geometry.  With C = 1 this is the flat assignment; a row outside the key's
+ * cell never wins, however near it is.
+ * hesaff_set_vocabulary_cells: coarse[c][128] and first[c + 1], copied to the device; a vocabulary must be set first; c = 0 (the arrays
+ * may be NULL) removes the layer, and so does every hesaff_set_vocabulary call (first[C] = K no longer describes the new rows).  With
+ * a layer set, every entry point that assigns words uses it - the detecting and describing calls, hesaff_assign_words_device,
+ * hesaff_stage_assign_words, hesaff_process_files - and the outputs keep their layout.  Without one nothing is launched, allocated or
+ * copied for it.  The working arrays (12 bytes per key of the largest call so far, at most 2^24 keys: longer sources run in slices;
+ * and arrays of size C) belong to the context, are allocated by the first assignment through a layer and only grow.
+ * hesaff_get_vocabulary_cells: *c = C, 0 without a layer.
+ * hesaff_get_assign_cells_ms: hesaff_get_assign_ms of the last assignment through a layer, split into the coarse assignment, the
+ * grouping of the keys by cell and the assignment inside the cells (profiling level >= 1; 0 otherwise).
+ * HESAFF_ERR_ARG, the previous layer stays set and the context usable as before: ctx NULL; no vocabulary set; c < 0 or c > K; an array
+ * NULL with c > 0; first[0] != 0, first[c] != K, or first not strictly increasing; a getter's out pointer NULL.
+ * hesaff_build_vocabulary_cells: a layer for any k rows (1 <= k <= 2^20) given c coarse rows (1 <= c <= k).  Every row is assigned to
+ * its nearest coarse row (the lowest of least dist2, on the device, against a private copy of `coarse`: the context's vocabulary is
+ * neither read nor changed), the rows are sorted by cell (stable, on the host), cells that received no row are dropped and their
+ * coarse rows compacted in order.  words_out[k][128]: the rows in the new order; order_out[new] = old row; coarse_out[c][128] and
+ * first_out[c + 1]: room for c cells, *c_out of them filled.  Deterministic.  HESAFF_ERR_ARG: a pointer NULL, k or c outside the bounds.
+ * hesaff_train_vocabulary_cells_device / hesaff_train_vocabulary_cells: hesaff_train_vocabulary[_device] on the K rows of a layer with
+ * the coarse rows and `first` fixed: the assignment of every iteration is the one above under V_{t-1}; the accumulation, the update, its
+ * rounding, the rule for empty words and the stop at a fixed point are training's.  `init` (the K rows, in the layer's order) is
+ * required.  A key's cell does not change during a call, so distortion[t] <= distortion[t - 1].  Bounds, outputs and errors are
+ * hesaff_train_vocabulary's, and HESAFF_ERR_ARG also answers init or coarse NULL and a `first` that is no layer over k rows.
+ * Cells file, kept beside the vocabulary file of the same rows (which stays an ordinary flat vocabulary).  Little-endian:
+ *   char magic[8] = "HESAFFC1"; uint32 dim = 128; uint32 cells; uint32 rows; uint32 reserved = 0; cells x uint8[128]; (cells + 1) x uint32
+ * hesaff_write_vocabulary_cells: rows = first[c]; HESAFF_ERR_ARG for a `first` that breaks the rules above.
+ * hesaff_read_vocabulary_cells: *coarse and *first are malloc'ed (hesaff_free each); HESAFF_ERR_IO for a file that cannot be read or is
+ * not a whole cells file (magic, dim, reserved, cells outside 1 .. rows, rows beyond 2^20, size, or a `first` that breaks the rules). */
+int hesaff_set_vocabulary_cells(hesaff_ctx *ctx, int c, const uint8_t *coarse, const uint32_t *first);
+int hesaff_get_vocabulary_cells(const hesaff_ctx *ctx, int *c);
+int hesaff_get_assign_cells_ms(const hesaff_ctx *ctx, float *coarse_ms, float *group_ms, float *fine_ms);
+int hesaff_build_vocabulary_cells(hesaff_ctx *ctx, int k, const uint8_t *words, int c, const uint8_t *coarse, uint8_t *words_out, int32_t *order_out,
+                                  uint8_t *coarse_out, uint32_t *first_out, int *c_out);
+int hesaff_train_vocabulary_cells_device(hesaff_ctx *ctx, int64_t n, const void *d_desc, int64_t stride, int64_t offset, int k, const uint8_t *init, int c,
+                                         const uint8_t *coarse, const uint32_t *first, int iterations, uint8_t *words_out, int64_t *distortion,
+                                         int32_t *empty, int *iterations_done);
+int hesaff_train_vocabulary_cells(hesaff_ctx *ctx, int64_t n, const uint8_t *desc, int k, const uint8_t *init, int c, const uint8_t *coarse,
+                                  const uint32_t *first, int iterations, uint8_t *words_out, int64_t *distortion, int32_t *empty, int *iterations_done);
+int hesaff_read_vocabulary_cells(const char *path, uint8_t **coarse, uint32_t **first, int *c, int *rows);
+int hesaff_write_vocabulary_cells(const char *path, int c, const uint8_t *coarse, const uint32_t *first);
 
 /* Image index (no counterpart in the reference): an inverted file over visual words with tf-idf scoring, the consumer of the words
  * that hesaff_set_vocabulary assigns.  Symbols only, version 8.

@@ -266,6 +266,10 @@ def load_library():
         L.hesaff_train_vocabulary_cells.argtypes = [vp, C.c_int64, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
         L.hesaff_read_vocabulary_cells.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.hesaff_write_vocabulary_cells.argtypes = [C.c_char_p, C.c_int, vp, vp]
+    if hasattr(L, "hesaff_set_vocabulary_probes"):   # (likewise)
+        L.hesaff_set_vocabulary_probes.argtypes = [vp, C.c_int]
+        L.hesaff_get_vocabulary_probes.argtypes = [vp, C.POINTER(C.c_int)]
+        L.hesaff_stage_probe_cells.argtypes = [vp, C.c_int, vp, vp, vp]
     if hasattr(L, "hesaff_index_build"):   # (likewise)
         L.hesaff_index_build.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int]
         L.hesaff_index_build_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int]
@@ -332,6 +336,7 @@ ABI_SYMBOLS = [
     "hesaff_train_vocabulary", "hesaff_train_vocabulary_device", "hesaff_stage_accumulate_words", "hesaff_get_training_ms",
     "hesaff_set_vocabulary_cells", "hesaff_get_vocabulary_cells", "hesaff_get_assign_cells_ms", "hesaff_build_vocabulary_cells",
     "hesaff_train_vocabulary_cells", "hesaff_train_vocabulary_cells_device", "hesaff_read_vocabulary_cells", "hesaff_write_vocabulary_cells",
+    "hesaff_set_vocabulary_probes", "hesaff_get_vocabulary_probes", "hesaff_stage_probe_cells",
     "hesaff_index_build", "hesaff_index_build_device", "hesaff_index_query", "hesaff_index_query_device", "hesaff_index_get_scores",
     "hesaff_index_get_tables", "hesaff_index_get_info", "hesaff_index_clear", "hesaff_get_index_ms", "hesaff_read_words",
     "hesaff_verify_matches", "hesaff_verify_matches_device", "hesaff_verify_get_pairs", "hesaff_verify_get_query_inert",
@@ -1130,6 +1135,33 @@ class HesaffContext:
         c = C.c_int()
         self._check(self.L.hesaff_get_vocabulary_cells(self.h, C.byref(c)))
         return c.value
+
+    def set_vocabulary_probes(self, probes):
+        """hesaff_set_vocabulary_probes: with a cell layer set, search a key's `probes` nearest cells (1..8, default 1 = its one cell;
+        at least as many as the layer has cells = the flat assignment).  A context setting: set_vocabulary and set_vocabulary_cells
+        keep it, and without a layer it has no effect."""
+        self._check(self.L.hesaff_set_vocabulary_probes(self.h, int(probes)))
+
+    def vocabulary_probes(self):
+        """hesaff_get_vocabulary_probes: the probe count that is set"""
+        p = C.c_int()
+        self._check(self.L.hesaff_get_vocabulary_probes(self.h, C.byref(p)))
+        return p.value
+
+    def probe_cells(self, desc):
+        """hesaff_stage_probe_cells: desc uint8 [n, 128] -> (cells int32 [n, P'], dist2 int32 [n, P']), the P' = min(probes, cells)
+        nearest cells of every key through the layer that is set, nearest first, equal distances in ascending cell."""
+        desc = np.ascontiguousarray(desc, dtype=np.uint8)
+        if desc.ndim != 2 or desc.shape[1] != 128:
+            raise ValueError("descriptors are a uint8 array of shape [n, 128]")
+        n, used = desc.shape[0], min(self.vocabulary_probes(), self.vocabulary_cells())
+        cells = np.zeros((n, used), np.int32)
+        dist2 = np.zeros((n, used), np.int32)
+        rc = self.L.hesaff_stage_probe_cells(self.h, n, desc.ctypes.data if n else None, cells.ctypes.data if n else None, dist2.ctypes.data if n else None)
+        if rc != 0 and used == 0:
+            raise HesaffError(rc, "hesaff_stage_probe_cells: no cell layer is set")
+        self._check(rc)
+        return cells, dist2
 
     @property
     def assign_cells_ms(self):

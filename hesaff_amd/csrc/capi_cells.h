@@ -1,5 +1,5 @@
-// capi_cells.h -- vocabulary cells (hesaff_set_vocabulary_cells, hesaff_build_vocabulary_cells, hesaff_train_vocabulary_cells* of
-// include/hesaff_amd.h): the entry points over the launchers beside launch_assign_words (pipeline.hip) and the training loop
+// capi_cells.h -- vocabulary cells and probes (hesaff_set_vocabulary_cells, hesaff_set_vocabulary_probes, hesaff_stage_probe_cells,
+// hesaff_build_vocabulary_cells, hesaff_train_vocabulary_cells* of include/hesaff_amd.h): the entry points over the launchers beside launch_assign_words (pipeline.hip) and the training loop
 // (capi_train.h).  Included at the end of pipeline.hip, behind capi_train.h (same translation unit).  A context without a layer
 // allocates, launches and copies nothing here.
 #pragma once
@@ -42,6 +42,46 @@ int hesaff_get_vocabulary_cells(const hesaff_ctx *c, int *cells)
    if (!c || !cells) return HESAFF_ERR_ARG;
    *cells = c->cells.c;
    return HESAFF_OK;
+}
+
+int hesaff_set_vocabulary_probes(hesaff_ctx *c, int probes)
+{
+   if (!c || !cells_probes_ok(probes)) return HESAFF_ERR_ARG;
+   c->cells.probes = probes;   // (read by the next assignment through a layer; nothing on the device depends on it until then)
+   return HESAFF_OK;
+}
+
+int hesaff_get_vocabulary_probes(const hesaff_ctx *c, int *probes)
+{
+   if (!c || !probes) return HESAFF_ERR_ARG;
+   *probes = c->cells.probes;
+   return HESAFF_OK;
+}
+
+// k_probe_cells alone on caller-supplied descriptors: the context's layer and probe count, P' = min(P, C) cells per key in probe order
+int hesaff_stage_probe_cells(hesaff_ctx *c, int n, const uint8_t *desc, int32_t *cells_out, int32_t *dist2_out)
+{
+   if (!c || n < 0 || (n > 0 && (!desc || !cells_out || !dist2_out)) || c->cells.c == 0) return HESAFF_ERR_ARG;
+   const int used = cells_probes_used(c->cells.probes, c->cells.c);
+   if (cells_probe_entries(n, used) > HS_CELLS_SLICE_KEYS) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   bind_device(c);
+   if (n == 0) return HESAFF_OK;
+   const size_t entries = (size_t)cells_probe_entries(n, used);
+   StageArena a(c);
+   const Span<uint8_t> a_desc = a.add<uint8_t>((size_t)n * 128);
+   const Span<int32_t> a_out = a.add<int32_t>(entries * 2);   // (cell, dist2) per entry
+   a.ensure();
+   a.upload(a_desc, desc);
+   CellsDevice d{};
+   d.tiles = c->cells.layer.at<uint8_t>(c->cells.a.tiles.off); d.norms = c->cells.layer.at<int32_t>(c->cells.a.norms.off);
+   d.n_tiles = c->cells.a.n_tiles; d.c = c->cells.c;
+   launch_probe_kernel(c->stream(), d, a.ptr(a_desc), n, 128, 0, used, a.ptr(a_out));
+   std::vector<int32_t> rows(entries * 2);
+   a.download(rows.data(), a_out);
+   finish_stream(c);
+   for (size_t e = 0; e < entries; e++) { cells_out[e] = rows[2 * e]; dist2_out[e] = rows[2 * e + 1]; }
+   HS_API_END(c)
 }
 
 int hesaff_get_assign_cells_ms(const hesaff_ctx *c, float *coarse_ms, float *group_ms, float *fine_ms)

@@ -1,8 +1,10 @@
 // cells_plan.h -- the host arithmetic of vocabulary cells (hesaff_set_vocabulary_cells, include/hesaff_amd.h): when a `first` array is
 // a cell layer over K rows, how many work items n keys in C cells make at most, which cell a work item belongs to, which rows of an
-// edge tile lie outside a cell, how a long source is cut into slices, and where the working arrays lie in the context's cells buffer.
+// edge tile lie outside a cell, how a long source is cut into slices, and where the working arrays lie in the context's cells buffer;
+// and the same numbers with probes (hesaff_set_vocabulary_probes): entries instead of keys.
 // Pure functions and plain structs, no HIP: capi_cells.h and kernels_cells.h obtain their numbers here, and
-// tests/native/cells_plan_check.cpp checks them on the CPU (tests/test_vocabulary_cells_host.py).
+// tests/native/cells_plan_check.cpp and probes_plan_check.cpp check them on the CPU (tests/test_vocabulary_cells_host.py,
+// tests/test_vocabulary_probes_host.py).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -103,6 +105,36 @@ inline CellScratch cell_scratch(StagePlan &p, int64_t cap, int64_t c)
    s.block_sums = p.add<uint32_t>((entries + 4095) / 4096 + 1);
    s.total = p.add<uint32_t>(1);
    return s;
+}
+
+// ---- vocabulary probes (hesaff_set_vocabulary_probes): a key is searched in its P' = min(P, C) nearest cells ----
+// The grouping and the search inside the cells then run over ENTRIES, e = key * P' + p for probe rank p, each with the cell of that
+// rank: n keys make n * P' entries, at most 2^24 of them in a slice - what the grouping is sized for - so a slice holds
+// floor(2^24 / P') keys, and the work items are bounded by the rule above over the entries, floor(n * P' / 64) + c.
+constexpr int HS_CELLS_MAX_PROBES = 8;
+inline bool cells_probes_ok(int64_t probes) { return probes >= 1 && probes <= HS_CELLS_MAX_PROBES; }
+inline int cells_probes_used(int64_t probes, int64_t c) { return (int)(probes < c ? probes : c); }
+inline int64_t cells_probe_slice_keys(int64_t used) { return HS_CELLS_SLICE_KEYS / used; }
+inline int64_t cells_probe_entries(int64_t n, int64_t used) { return n * used; }
+inline int64_t cells_probe_item_bound(int64_t n, int64_t used, int64_t c) { return cells_item_bound(cells_probe_entries(n, used), c); }
+HS_TRAIN_HD uint32_t cells_entry_key(uint32_t entry, uint32_t used) { return entry / used; }
+
+// The working arrays with probes, for `cap` keys of capacity: CellScratch over cap * P' entries - coarse holds (cell, dist2 to its
+// coarse row) per entry, perm the entries grouped by cell - and, with P' > 1, fine: (row, dist2) per entry, which the merge reduces
+// to the key's 8 bytes.  (8 + 4 + 8) P' bytes per key; with P' = 1 nothing is added and the layout is cell_scratch's byte for byte.
+struct ProbeScratch {
+   CellScratch s;
+   Span<int32_t> fine;          // [cap * P'][2]; P' = 1: empty, the fine search writes to the caller's array
+   int used;                    // P'
+};
+inline ProbeScratch probe_scratch(StagePlan &p, int64_t cap, int64_t c, int used)
+{
+   ProbeScratch q;
+   q.used = used;
+   q.s = cell_scratch(p, cells_probe_entries(cap, used), c);
+   q.fine.off = 0; q.fine.count = 0;
+   if (used > 1) q.fine = p.add<int32_t>((size_t)cells_probe_entries(cap, used) * 2);
+   return q;
 }
 
 // Sorting K rows by cell (hesaff_build_vocabulary_cells): cell[k] in 0 .. c - 1 -> order[new] = old row, stable; the cells that received

@@ -203,6 +203,21 @@ struct AffineHessianDetector {
       if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
       words_.clear();
    }
+   // No counterpart in the reference (hesaff_set_vocabulary_probes, include/hesaff_amd.h): with a cell layer set, a key is searched in
+   // its `probes` nearest cells, 1..8 (default 1: its one cell; at least the layer's cell count: the flat assignment).  A setting of the
+   // detector: setVocabulary and setVocabularyCells keep it, and without a layer it has no effect.
+   void setVocabularyProbes(int probes)
+   {
+      if (hesaff_set_vocabulary_probes(ctx_, probes) != HESAFF_OK) throw std::invalid_argument("vocabulary probes must be 1..8");
+      words_.clear();
+   }
+   int vocabularyProbes() const
+   {
+      int p = 1;
+      hesaff_get_vocabulary_probes(ctx_, &p);
+      return p;
+   }
+
    // A layer for k rows given c coarse rows (hesaff_build_vocabulary_cells): `rows` is put into cell order, order[new] = old row, the
    // coarse rows that attract a row and their `first` are returned.  The detector's own vocabulary does not change.
    struct VocabularyCells {

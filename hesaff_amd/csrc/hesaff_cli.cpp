@@ -56,6 +56,9 @@
 //       a cell layer over the vocabulary (hesaff_read_vocabulary_cells: "HESAFFC1", coarse rows and each cell's first row; its row count must
 //       be the vocabulary's): a key is compared with the coarse rows and then only with the rows of its cell (hesaff_set_vocabulary_cells).
 //       The files written are the same; the vocabulary file stays an ordinary flat vocabulary of the same rows.
+//   hesaff <image> --vocabulary <vocabulary file> --cells <cells file> --probes P      (and with --batch)
+//       P = 1..8: a key is searched in its P nearest cells (hesaff_set_vocabulary_probes; 1, the default, is its one cell, and from the
+//       layer's cell count on the result is the flat assignment).  Needs --cells <cells file>; refused with --train-vocabulary.
 //   hesaff --batch <list file> --train-vocabulary <vocabulary file> --words K --cells C [--iterations T] [--coarse-iterations Tc]
 //       trains C coarse rows (Tc = 10 iterations at most), spreads K initial rows over the list's keys, sorts them into the cells of their
 //       nearest coarse rows (hesaff_build_vocabulary_cells) and trains them inside the cells (hesaff_train_vocabulary_cells); writes
@@ -139,7 +142,7 @@ bool parse_devices(const char *spec, std::vector<int> &out)
 // through hesaff_process_files - decode threads -> device -> writer threads, bounded memory - on its own host thread.
 int run_batch_mode(const char *list_path, const char *devices_spec, int out_format, bool dynamic, int fast, int resume, int host_share, int runtime_nice,
                    int max_keypoints, int orientation, int grid_rows, int grid_cols, int descriptor, int orientations,
-                   const uint8_t *vocabulary, int vocabulary_size, const uint8_t *cells_coarse, const uint32_t *cells_first, int cells)
+                   const uint8_t *vocabulary, int vocabulary_size, const uint8_t *cells_coarse, const uint32_t *cells_first, int cells, int probes)
 {
    std::ifstream lf(list_path);
    if (!lf) { fprintf(stderr, "hesaff: cannot read list '%s'\n", list_path); return 1; }
@@ -204,6 +207,7 @@ int run_batch_mode(const char *list_path, const char *devices_spec, int out_form
          hesaff_destroy(ctx);
          return;
       }
+      hesaff_set_vocabulary_probes(ctx, probes);   // (main checked the range)
       hesaff_host_plan hp;   // this device's share of the host: the library's one rule (include/hesaff_amd.h)
       hesaff_host_plan_for(world * host_share, &hp);
       const int wt = hp.write_threads, dt = hp.decode_threads;
@@ -522,7 +526,8 @@ int main(int argc, char **argv)
       int out_format = HESAFF_OUT_TEXT, fast = 0, host_share = 1, runtime_nice = -1, max_keypoints = 0, orientation = HESAFF_ORI_UP, grid_rows = 1, grid_cols = 1, descriptor = HESAFF_DESC_SIFT, orientations = 1;
       bool bad = false, grid = false, dynamic = false, words_only = false;
       const char *vocabulary_path = nullptr, *train_path = nullptr, *cells_arg = nullptr;
-      int resume = 0, train_words = 0, train_iterations = 10, train_cells = 0, coarse_iterations = 10;
+      int resume = 0, train_words = 0, train_iterations = 10, train_cells = 0, coarse_iterations = 10, probes = 1;
+      bool probes_given = false;
       for (int i = 1; i < argc && !bad; i += 2) {
          if (strcmp(argv[i], "--resume") == 0) { resume = 1; i--; continue; }
          if (strcmp(argv[i], "--resume=strict") == 0) { resume = 2; i--; continue; }   // also count the rows of existing text outputs
@@ -533,6 +538,11 @@ int main(int argc, char **argv)
          else if (strcmp(argv[i], "--vocabulary") == 0) vocabulary_path = argv[i + 1];
          else if (strcmp(argv[i], "--train-vocabulary") == 0) train_path = argv[i + 1];
          else if (strcmp(argv[i], "--cells") == 0) cells_arg = argv[i + 1];   // a cells file, or with --train-vocabulary the number of cells
+         else if (strcmp(argv[i], "--probes") == 0) {
+            // one digit, 1..8 (hesaff_set_vocabulary_probes)
+            if (argv[i + 1][0] < '1' || argv[i + 1][0] > '8' || argv[i + 1][1] != 0) bad = true;
+            else { probes = argv[i + 1][0] - '0'; probes_given = true; }
+         }
          else if (strcmp(argv[i], "--coarse-iterations") == 0) {
             char *end = nullptr;
             const long v = strtol(argv[i + 1], &end, 10);
@@ -601,7 +611,8 @@ int main(int argc, char **argv)
          else train_cells = (int)v;
       }
       if (coarse_iterations != 10 && !train_cells) bad = true;
-      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--vocabulary <vocabulary file> [--words-only]] [--train-vocabulary <vocabulary file> --words K [--iterations T]] [--cells <cells file>|C [--coarse-iterations Tc]] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1] [--max-keypoints N] [--orientations 1..4] [--descriptor sift|rootsift] [--orientation up|dominant] [--grid RxC]\n"); return 1; }
+      if (probes_given && (!cells_arg || train_path)) bad = true;   // probes search a cells FILE's layer; training has one probe
+      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--vocabulary <vocabulary file> [--words-only]] [--train-vocabulary <vocabulary file> --words K [--iterations T]] [--cells <cells file>|C [--coarse-iterations Tc]] [--probes 1..8] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1] [--max-keypoints N] [--orientations 1..4] [--descriptor sift|rootsift] [--orientation up|dominant] [--grid RxC]\n"); return 1; }
       if (train_path)
          return run_train_mode(list, devices, train_path, train_words, train_iterations, fast, max_keypoints, orientation, grid_rows, grid_cols, descriptor, orientations, train_cells,
                                coarse_iterations);
@@ -623,7 +634,7 @@ int main(int argc, char **argv)
          }
       }
       const int brc = run_batch_mode(list, devices, out_format, dynamic, fast, resume, host_share, runtime_nice, max_keypoints, orientation, grid_rows, grid_cols, descriptor,
-                                     orientations, vocabulary, vocabulary_size, cells_coarse, cells_first, cells);
+                                     orientations, vocabulary, vocabulary_size, cells_coarse, cells_first, cells, probes);
       hesaff_free(vocabulary); hesaff_free(cells_coarse); hesaff_free(cells_first);
       return brc;
    }
@@ -655,6 +666,17 @@ int main(int argc, char **argv)
          const char *cname = i + 1 < argc ? argv[++i] : "";
          if (!vocabulary || hesaff_read_vocabulary_cells(cname, &cells_coarse, &cells_first, &cells, &cells_rows) != HESAFF_OK || cells_rows != vocabulary_size) {
             fprintf(stderr, "hesaff: cannot read cells '%s' (--vocabulary and a HESAFFC1 file over its rows expected)\n", cname);
+            return 1;
+         }
+      }
+      // --probes 1..8 behind the image (the last one counts): needs the layer of a --cells file
+      int probes = 1;
+      for (int i = 2; i < argc; i++) {
+         if (strcmp(argv[i], "--probes") != 0) continue;
+         const char *v = i + 1 < argc ? argv[++i] : "";
+         if (cells_coarse && v[0] >= '1' && v[0] <= '8' && v[1] == 0) probes = v[0] - '0';
+         else {
+            fprintf(stderr, "hesaff: --probes takes 1 .. 8 and needs --vocabulary with --cells <cells file>\n");
             return 1;
          }
       }
@@ -735,6 +757,7 @@ int main(int argc, char **argv)
          detector.setDescriptor(descriptor);
          if (vocabulary) detector.setVocabulary(vocabulary, vocabulary_size);
          if (cells_coarse) detector.setVocabularyCells(cells_coarse, cells_first, cells);
+         detector.setVocabularyProbes(probes);
          const auto t1 = std::chrono::steady_clock::now();
          detector.detectPyramidKeypoints(data, w, h, ch);
          const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();

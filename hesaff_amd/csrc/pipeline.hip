@@ -461,6 +461,7 @@ struct hesaff_ctx {
       int64_t cap = 0;                 // keys the scratch is laid out for
       std::vector<DevEvent> ev;        // profiling: four per slice of the last assignment (start, coarse, grouped, fine)
       int timed_slices = 0;            // slices of the last assignment that ev brackets
+      int probes = 1;                  // hesaff_set_vocabulary_probes: a context setting, kept by clear(); read with a layer set only
       void clear() { layer.release(); scratch.release(); c = 0; cap = 0; timed_slices = 0; }
    } cells;
    // hesaff_index_build: the inverted file over visual words (index_plan.h: IndexArrays in `tables`, the posting lists in `lists`);
@@ -1277,7 +1278,7 @@ struct CellsDevice {
    const void *tiles, *norms;   // the packed coarse rows
    int n_tiles, c;
    const uint32_t *first;       // [c + 1]
-   int32_t *coarse;
+   int32_t *coarse, *fine = nullptr;   // fine: with probes only (ProbeScratch), set by launch_assign_cells
    uint32_t *perm, *sub, *cursor, *item_first, *block_sums, *total;
    size_t sub_bytes;
    int slots;
@@ -1295,15 +1296,27 @@ CellsDevice cells_device(void *layer, const CellLayerArrays &a, int cells, void 
    return d;
 }
 
-// the first two steps of an assignment through cells, for 1 <= n <= 2^24 keys: every key's coarse cell, then the keys grouped by cell
-// (perm, the cursor) and each cell's first work item (item_first).  ev: two events, recorded behind either step, or nullptr.
-void launch_cells_group(hesaff_ctx *c, const CellsDevice &d, const void *d_desc, int n, long long stride, long long offset, const DevEvent *ev)
+// k_probe_cells: the `used` nearest cells of each of n >= 1 keys, 1 <= used <= the layer's cells, n * used <= 2^24: (cell, dist2) per
+// entry key * used + rank into d_out
+void launch_probe_kernel(hipStream_t st, const CellsDevice &d, const void *d_desc, long long n, long long stride, long long offset, int used, void *d_out)
+{
+   const long long blocks = (n + HS_WORD_BLOCK_KEYS - 1) / HS_WORD_BLOCK_KEYS;
+   hipLaunchKernelGGL(k_probe_cells, dim3((uint32_t)blocks), dim3(HS_WORD_BLOCK_WAVES * 64), 0, st, (const uint8_t *)d_desc, n, stride, offset,
+                      (const hs_v4i *)d.tiles, (const int32_t *)d.norms, d.n_tiles, used, (int32_t *)d_out);
+}
+
+// the first two steps of an assignment through cells, for 1 <= n * used <= 2^24 entries (used = 1: an entry is a key): every key's
+// coarse cell - with used > 1 its `used` nearest cells, an entry each - then the entries grouped by cell (perm, the cursor) and each
+// cell's first work item (item_first).  ev: two events, recorded behind either step, or nullptr.
+void launch_cells_group(hesaff_ctx *c, const CellsDevice &d, const void *d_desc, int n_keys, long long stride, long long offset, const DevEvent *ev, int used = 1)
 {
    hipStream_t st = c->stream();
-   launch_assign_kernel(st, d.tiles, d.norms, d.n_tiles, d_desc, n, stride, offset, d.coarse);
+   if (used > 1) launch_probe_kernel(st, d, d_desc, n_keys, stride, offset, used, d.coarse);
+   else launch_assign_kernel(st, d.tiles, d.norms, d.n_tiles, d_desc, n_keys, stride, offset, d.coarse);
    if (ev) HIP_TRY(hipEventRecord(ev[0], st));
    HIP_TRY(hipMemsetAsync(d.sub, 0, d.sub_bytes, st));
    // (k_word_histogram and k_word_scatter: the same grid, so that a key's wave, and with it its slot, is the same in both)
+   const int n = (int)cells_probe_entries(n_keys, used);
    const uint32_t key_blocks = (uint32_t)((n + 255) / 256);
    hipLaunchKernelGGL(k_word_histogram, dim3(key_blocks), dim3(256), 0, st, (const int32_t *)d.coarse, 2, n, d.sub, d.slots, (unsigned long long *)nullptr);
    LoadU32 load;
@@ -1316,40 +1329,53 @@ void launch_cells_group(hesaff_ctx *c, const CellsDevice &d, const void *d_desc,
    if (ev) HIP_TRY(hipEventRecord(ev[1], st));
 }
 
-// the third step: k_assign_words_cells over the grouped keys against a packed flat vocabulary, (word, dist2) per key into d_out
+// the third step: k_assign_words_cells over the grouped keys against a packed flat vocabulary, (word, dist2) per key into d_out.  With
+// used > 1 (d.fine is set): over the grouped entries into d.fine, then k_merge_probes, each key's least (dist2, row) into d_out.
 void launch_cells_fine(hipStream_t st, const CellsDevice &d, const void *tiles, const void *norms, const void *d_desc, int n, long long stride, long long offset,
-                       void *d_out)
+                       void *d_out, int used = 1)
 {
-   const long long items = cells_item_bound(n, d.c);
+   const long long items = cells_probe_item_bound(n, used, d.c);
    const long long blocks = (items + HS_WORD_BLOCK_WAVES - 1) / HS_WORD_BLOCK_WAVES;
-   hipLaunchKernelGGL(k_assign_words_cells, dim3((uint32_t)blocks), dim3(HS_WORD_BLOCK_WAVES * 64), 0, st, (const uint8_t *)d_desc, stride, offset,
+   if (used > 1) {
+      hipLaunchKernelGGL(k_assign_words_cells<true>, dim3((uint32_t)blocks), dim3(HS_WORD_BLOCK_WAVES * 64), 0, st, (const uint8_t *)d_desc, stride, offset,
+                         (const uint32_t *)d.perm, (const uint32_t *)d.cursor, d.slots, (const uint32_t *)d.item_first, d.first, d.c, (const hs_v4i *)tiles,
+                         (const int32_t *)norms, d.fine, used);
+      hipLaunchKernelGGL(k_merge_probes, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, (const int32_t *)d.fine, n, used, (int32_t *)d_out);
+      return;
+   }
+   hipLaunchKernelGGL(k_assign_words_cells<false>, dim3((uint32_t)blocks), dim3(HS_WORD_BLOCK_WAVES * 64), 0, st, (const uint8_t *)d_desc, stride, offset,
                       (const uint32_t *)d.perm, (const uint32_t *)d.cursor, d.slots, (const uint32_t *)d.item_first, d.first, d.c, (const hs_v4i *)tiles,
-                      (const int32_t *)norms, (int32_t *)d_out);
+                      (const int32_t *)norms, (int32_t *)d_out, 1);
 }
 
-// the context's assignment with a layer set: slices of at most 2^24 keys (what the scratch is ever sized for), each through the three
-// steps; the results are per key, so the cut is invisible.  With profiling on, four events per slice for hesaff_get_assign_cells_ms.
+// the context's assignment with a layer set: slices of at most 2^24 entries (what the scratch is ever sized for; P' = min(probes, C)
+// entries per key, so floor(2^24 / P') keys), each through the three steps; the results are per key, so the cut is invisible.  With
+// profiling on, four events per slice for hesaff_get_assign_cells_ms.  With P' = 1 the launches and the scratch are those of a
+// context that never heard of probes.
 void launch_assign_cells(hesaff_ctx *c, const void *d_desc, long long n, long long stride, long long offset, void *d_out)
 {
    hesaff_ctx::Cells &cl = c->cells;
    cl.timed_slices = 0;
-   cl.cap = std::max<int64_t>(cl.cap, std::min<int64_t>(n, HS_CELLS_SLICE_KEYS));
+   const int used = cells_probes_used(cl.probes, cl.c);
+   const int64_t slice = cells_probe_slice_keys(used);
+   cl.cap = std::max<int64_t>(cl.cap, std::min<int64_t>(n, slice));
    StagePlan p;
-   const CellScratch s = cell_scratch(p, cl.cap, cl.c);
-   cl.scratch.ensure(p.bytes());   // (grows with the keys and with the cells of a later layer; never shrinks)
-   const CellsDevice d = cells_device(cl.layer.p, cl.a, cl.c, cl.scratch.p, s);
+   const ProbeScratch s = probe_scratch(p, std::min<int64_t>(cl.cap, slice), cl.c, used);
+   cl.scratch.ensure(p.bytes());   // (grows with the keys, the probes and the cells of a later layer; never shrinks)
+   CellsDevice d = cells_device(cl.layer.p, cl.a, cl.c, cl.scratch.p, s.s);
+   d.fine = used > 1 ? cl.scratch.at<int32_t>(s.fine.off) : nullptr;
    const bool timed = c->profiling >= 1;
-   const int64_t slices = cells_slice_count(n, HS_CELLS_SLICE_KEYS);
+   const int64_t slices = cells_slice_count(n, slice);
    if (timed) while ((int64_t)cl.ev.size() < 4 * slices) cl.ev.emplace_back(hipEventDefault);
    hipStream_t st = c->stream();
    for (int64_t i = 0; i < slices; i++) {
-      const int64_t begin = cells_slice_begin(i, HS_CELLS_SLICE_KEYS);
-      const int m = (int)cells_slice_keys(i, n, HS_CELLS_SLICE_KEYS);
+      const int64_t begin = cells_slice_begin(i, slice);
+      const int m = (int)cells_slice_keys(i, n, slice);
       const uint8_t *desc = (const uint8_t *)d_desc + begin * stride;
       const DevEvent *ev = timed ? &cl.ev[(size_t)(4 * i)] : nullptr;
       if (ev) HIP_TRY(hipEventRecord(ev[0], st));
-      launch_cells_group(c, d, desc, m, stride, offset, ev ? ev + 1 : nullptr);
-      launch_cells_fine(st, d, c->vocab.tiles.p, c->vocab.norms.p, desc, m, stride, offset, (int32_t *)d_out + 2 * begin);
+      launch_cells_group(c, d, desc, m, stride, offset, ev ? ev + 1 : nullptr, used);
+      launch_cells_fine(st, d, c->vocab.tiles.p, c->vocab.norms.p, desc, m, stride, offset, (int32_t *)d_out + 2 * begin, used);
       if (ev) HIP_TRY(hipEventRecord(ev[3], st));
    }
    if (timed) cl.timed_slices = (int)slices;

@@ -56,6 +56,7 @@ extern "C" {
  *    And for the image index (hesaff_index_build and the nine symbols declared with it): symbols only, version 8.
  *    And for spatial verification (hesaff_verify_matches and the six symbols declared with it): symbols only, version 8.
  *    And for vocabulary cells (hesaff_set_vocabulary_cells and the eight symbols declared with it): symbols only, version 8.
+ *    And for vocabulary probes (hesaff_set_vocabulary_probes / hesaff_get_vocabulary_probes / hesaff_stage_probe_cells): symbols only, version 8.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -656,6 +657,34 @@ int hesaff_train_vocabulary_cells(hesaff_ctx *ctx, int64_t n, const uint8_t *des
                                   const uint32_t *first, int iterations, uint8_t *words_out, int64_t *distortion, int32_t *empty, int *iterations_done);
 int hesaff_read_vocabulary_cells(const char *path, uint8_t **coarse, uint32_t **first, int *c, int *rows);
 int hesaff_write_vocabulary_cells(const char *path, int c, const uint8_t *coarse, const uint32_t *first);
+
+/* Vocabulary probes (no counterpart in the reference; FAISS nprobe, FLANN checks): with a cell layer set, a key is searched in its P
+ * nearest cells, not in one - the dial between one cell and the flat search.  Symbols only, version 8.
+ * With the layer's C coarse rows g_c and first[0 .. C], a probe count P and P' = min(P, C), for a key with bytes d:
+ *     probe[0 .. P'-1] = the first P' cells in the order (dist2(d, g_c) ascending, c ascending)
+ *     word             = the k of least (dist2(d, w_k), k), lexicographically, over the rows k of the cells probe[0 .. P'-1]
+ *     dist2            = dist2(d, w_word)
+ * Integers, exact, ties decided, no dependence on launch geometry.  P = 1 is the definition of hesaff_set_vocabulary_cells; P' = C is
+ * the flat word and dist2 of hesaff_set_vocabulary exactly; a key's dist2 never increases with P; a row of a cell that is not probed
+ * never wins; a tie between rows of two probed cells goes to the lower row, whatever the ranks of their cells; equal coarse rows are
+ * probed in ascending c.
+ * hesaff_set_vocabulary_probes: 1 <= probes <= 8, default 1.  A setting of the context like the orientation count: it survives
+ * hesaff_set_vocabulary and hesaff_set_vocabulary_cells, and has no effect while no layer is set (the flat search is exact already).
+ * With a layer set and P > 1 every entry point that assigns words uses the probes - the detecting and describing calls,
+ * hesaff_assign_words_device, hesaff_stage_assign_words, hesaff_process_files - and the outputs keep their layout.  The working arrays
+ * grow to 20 P' bytes per key, a slice to floor(2^24 / P') keys.  With P' = 1 the kernels, their order and the 12 bytes per key are
+ * those of a context on which this was never called.  hesaff_get_assign_cells_ms then reports the search for the P' cells, the grouping
+ * of the n P' (key, rank) entries by cell, and the search inside the cells with the merge of a key's P' results.
+ * hesaff_build_vocabulary_cells and hesaff_train_vocabulary_cells[_device] do not read the setting: training assigns through its
+ * private layer with one probe.
+ * hesaff_get_vocabulary_probes: *probes = P.
+ * hesaff_stage_probe_cells: the first step alone, for desc[n][128] in host memory with the context's layer and probe count:
+ * cells_out[n][P'] and dist2_out[n][P'] (the distance to the coarse row), in probe order.
+ * HESAFF_ERR_ARG, with the setting as it was: ctx NULL, probes outside 1..8, a getter's out pointer NULL; hesaff_stage_probe_cells: a
+ * pointer NULL with n > 0, n < 0, n P' > 2^24, no layer set. */
+int hesaff_set_vocabulary_probes(hesaff_ctx *ctx, int probes);
+int hesaff_get_vocabulary_probes(const hesaff_ctx *ctx, int *probes);
+int hesaff_stage_probe_cells(hesaff_ctx *ctx, int n, const uint8_t *desc, int32_t *cells_out, int32_t *dist2_out);
 
 /* Image index (no counterpart in the reference): an inverted file over visual words with tf-idf scoring, the consumer of the words
  * that hesaff_set_vocabulary assigns.  Symbols only, version 8.

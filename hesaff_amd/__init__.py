@@ -43,6 +43,12 @@ from ._binding import (  # noqa: F401
     write_vocabulary_cells,
     read_words,
     write_words,
+    EMBED_BITS,
+    embedding_projection,
+    read_embedding,
+    write_embedding,
+    read_signatures,
+    write_signatures,
     read_image,
     read_pnm,
     read_jpeg_coefficients,

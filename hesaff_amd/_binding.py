@@ -289,6 +289,29 @@ def load_library():
         L.hesaff_stage_verify_pairs.argtypes = [vp, C.c_int, vp, C.c_float, vp, C.POINTER(C.c_int32)]
         L.hesaff_get_verify_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.hesaff_read_words_rows.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(L, "hesaff_set_embedding"):   # (likewise)
+        i64 = C.c_int64
+        L.hesaff_embedding_projection.argtypes = [C.c_uint64, vp]
+        L.hesaff_set_embedding.argtypes = [vp, vp, vp]
+        L.hesaff_get_embedding.argtypes = [vp, C.POINTER(C.c_int), vp, vp]
+        L.hesaff_get_signatures.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_int)]
+        L.hesaff_get_signatures_device.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
+        L.hesaff_embed_device.argtypes = [vp, i64, vp, i64, i64, vp, C.c_int, vp]
+        L.hesaff_stage_embed.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
+        L.hesaff_stage_project.argtypes = [vp, C.c_int, vp, vp, vp]
+        L.hesaff_train_embedding.argtypes = [vp, i64, vp, vp, C.c_int, C.c_int, vp, vp, vp]
+        L.hesaff_train_embedding_device.argtypes = [vp, i64, vp, i64, i64, vp, C.c_int, C.c_int, vp, vp, vp]
+        L.hesaff_get_embedding_ms.argtypes = [vp] + [C.POINTER(C.c_float)] * 4
+        L.hesaff_index_build_embedded.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int]
+        L.hesaff_index_build_embedded_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int]
+        L.hesaff_index_query_embedded.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int)]
+        L.hesaff_index_query_embedded_device.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int)]
+        L.hesaff_index_get_embedded.argtypes = [vp, C.POINTER(C.c_int), vp, vp, vp]
+        L.hesaff_write_embedding.argtypes = [C.c_char_p, C.c_int, vp, vp]
+        L.hesaff_read_embedding.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
+        L.hesaff_write_signatures.argtypes = [C.c_char_p, vp, C.c_int]
+        L.hesaff_read_signatures.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int)]
+        L.hesaff_signatures_is_complete.argtypes = [C.c_char_p]
     L.hesaff_stage_math_sift_general.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math_sift.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]
@@ -341,6 +364,11 @@ ABI_SYMBOLS = [
     "hesaff_index_get_tables", "hesaff_index_get_info", "hesaff_index_clear", "hesaff_get_index_ms", "hesaff_read_words",
     "hesaff_verify_matches", "hesaff_verify_matches_device", "hesaff_verify_get_pairs", "hesaff_verify_get_query_inert",
     "hesaff_stage_verify_pairs", "hesaff_get_verify_ms", "hesaff_read_words_rows",
+    "hesaff_embedding_projection", "hesaff_set_embedding", "hesaff_get_embedding", "hesaff_get_signatures", "hesaff_get_signatures_device",
+    "hesaff_embed_device", "hesaff_stage_embed", "hesaff_stage_project", "hesaff_train_embedding", "hesaff_train_embedding_device",
+    "hesaff_get_embedding_ms", "hesaff_index_build_embedded", "hesaff_index_build_embedded_device", "hesaff_index_query_embedded",
+    "hesaff_index_query_embedded_device", "hesaff_index_get_embedded", "hesaff_write_embedding", "hesaff_read_embedding",
+    "hesaff_write_signatures", "hesaff_read_signatures", "hesaff_signatures_is_complete",
 ]
 
 # hesaff_set_output_format's bits
@@ -593,6 +621,91 @@ def read_words(path):
     if len(body) != n * WORDS_ROW_DTYPE.itemsize:
         raise HesaffError(-4, "%s is truncated" % path)
     return vocabulary_size, np.frombuffer(body, dtype=WORDS_ROW_DTYPE).copy()
+
+
+EMBED_BITS = 64   # HESAFF_EMBED_BITS
+
+
+def embedding_projection(seed):
+    """The default projection of hesaff_embedding_projection in numpy: int8 [64, 128], entry e = i * 128 + j the e-th output of
+    splitmix64 from `seed`, its top byte less 128, with -128 raised to -127."""
+    with np.errstate(over="ignore"):
+        s = np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF) + np.arange(1, EMBED_BITS * 128 + 1, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+        x = (s ^ (s >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        x ^= x >> np.uint64(31)
+    v = (x >> np.uint64(56)).astype(np.int32) - 128
+    return np.maximum(v, -127).astype(np.int8).reshape(EMBED_BITS, 128)
+
+
+def _projection_array(P):
+    """int8 [64, 128], C-contiguous, no entry -128 - anything else is a ValueError"""
+    if not isinstance(P, np.ndarray) or P.dtype != np.int8 or P.shape != (EMBED_BITS, 128):
+        raise ValueError("a projection is an int8 array of shape [64, 128]")
+    if (P == -128).any():
+        raise ValueError("a projection has entries in -127 .. 127")
+    return np.ascontiguousarray(P)
+
+
+def _thresholds_array(tau, k=None):
+    """int32 [K, 64], C-contiguous"""
+    if not isinstance(tau, np.ndarray) or tau.dtype != np.int32 or tau.ndim != 2 or tau.shape[1] != EMBED_BITS or (k is not None and tau.shape[0] != k):
+        raise ValueError("thresholds are an int32 array of shape [K, 64]%s" % ("" if k is None else ", K = %d" % k))
+    return np.ascontiguousarray(tau)
+
+
+def _signature_array(sigs, n):
+    sigs = np.ascontiguousarray(sigs, dtype=np.uint64)
+    if sigs.shape != (n,):
+        raise ValueError("one uint64 signature per key: shape [%d], not %s" % (n, sigs.shape))
+    return sigs
+
+
+def write_embedding(path, P, tau):
+    """hesaff_write_embedding: P int8 [64, 128], tau int32 [K, 64] -> an embedding file ("HESAFFE1")."""
+    P = _projection_array(P)
+    tau = _thresholds_array(tau)
+    rc = load_library().hesaff_write_embedding(os.fsencode(path), tau.shape[0], P.ctypes.data, tau.ctypes.data)
+    if rc != 0:
+        raise HesaffError(rc, "hesaff_write_embedding(%s)" % path)
+
+
+def read_embedding(path):
+    """hesaff_read_embedding: an embedding file -> (P int8 [64, 128], tau int32 [K, 64])."""
+    L = load_library()
+    P = C.c_void_p(); tau = C.c_void_p(); k = C.c_int()
+    rc = L.hesaff_read_embedding(os.fsencode(path), C.byref(P), C.byref(tau), C.byref(k))
+    if rc != 0:
+        raise HesaffError(rc, "hesaff_read_embedding(%s): not a readable, whole embedding file" % path)
+    try:
+        p = np.frombuffer(C.string_at(P.value, EMBED_BITS * 128), dtype=np.int8).copy()
+        t = np.frombuffer(C.string_at(tau.value, k.value * EMBED_BITS * 4), dtype="<i4").astype(np.int32)
+    finally:
+        L.hesaff_free(P)
+        L.hesaff_free(tau)
+    return p.reshape(EMBED_BITS, 128), t.reshape(k.value, EMBED_BITS)
+
+
+def write_signatures(path, sigs):
+    """hesaff_write_signatures: uint64 [n] -> a signatures file ("HESAFFS1")."""
+    sigs = np.ascontiguousarray(sigs, dtype=np.uint64).reshape(-1)
+    rc = load_library().hesaff_write_signatures(os.fsencode(path), sigs.ctypes.data if len(sigs) else None, len(sigs))
+    if rc != 0:
+        raise HesaffError(rc, "hesaff_write_signatures(%s)" % path)
+
+
+def read_signatures(path):
+    """hesaff_read_signatures: a signatures file -> uint64 [n]."""
+    L = load_library()
+    p = C.c_void_p(); n = C.c_int()
+    rc = L.hesaff_read_signatures(os.fsencode(path), C.byref(p), C.byref(n))
+    if rc != 0:
+        raise HesaffError(rc, "hesaff_read_signatures(%s): not a readable, whole signatures file" % path)
+    try:
+        out = np.frombuffer(C.string_at(p.value, n.value * 8), dtype="<u8").astype(np.uint64) if n.value else np.zeros(0, np.uint64)
+    finally:
+        L.hesaff_free(p)
+    return out
 
 
 def _verify_rows(rows):
@@ -1220,15 +1333,147 @@ class HesaffContext:
         words, distortion, empty = self.train_vocabulary_cells(desc, v0, coarse, first, iterations)
         return words, coarse, first, distortion, empty
 
+    # ---- Hamming embedding (hesaff_set_embedding, include/hesaff_amd.h) ----
+    def set_embedding(self, projection, thresholds=None):
+        """hesaff_set_embedding: projection int8 [64, 128] (entries in -127 .. 127) and thresholds int32 [K, 64], K the rows of the
+        vocabulary that is set (both copied), or None to remove the embedding.  With one set, every call that assigns words also
+        makes a 64-bit signature per key; signatures(image) hands them out."""
+        if projection is None:
+            self._check(self.L.hesaff_set_embedding(self.h, None, None))
+            return
+        P = _projection_array(projection)
+        tau = _thresholds_array(thresholds, self.vocabulary_size)
+        self._check(self.L.hesaff_set_embedding(self.h, P.ctypes.data, tau.ctypes.data))
+
+    def embedding(self):
+        """hesaff_get_embedding: (P int8 [64, 128], tau int32 [K, 64]), or None when no embedding is set"""
+        k = C.c_int()
+        self._check(self.L.hesaff_get_embedding(self.h, C.byref(k), None, None))
+        if k.value == 0:
+            return None
+        P = np.zeros((EMBED_BITS, 128), np.int8); tau = np.zeros((k.value, EMBED_BITS), np.int32)
+        self._check(self.L.hesaff_get_embedding(self.h, C.byref(k), P.ctypes.data, tau.ctypes.data))
+        return P, tau
+
+    def signatures(self, image):
+        """hesaff_get_signatures: uint64 [count], row for row the keys (and words) of image `image` of the last host call (a copy)."""
+        p = C.c_void_p(); n = C.c_int()
+        if self.L.hesaff_get_signatures(self.h, int(image), C.byref(p), C.byref(n)) != 0:
+            raise HesaffError(-2, "hesaff_get_signatures(%d): no embedding is set, or no such image in the last host call" % image)
+        if n.value == 0:
+            return np.zeros(0, np.uint64)
+        return np.frombuffer((C.c_char * (n.value * 8)).from_address(p.value), dtype=np.uint64).copy()
+
+    def signatures_device(self):
+        """hesaff_get_signatures_device: (device pointer, rows) of the uint64 [total] array parallel to the keys of the last device-resident call."""
+        p = C.c_void_p(); tot = C.c_int64()
+        if self.L.hesaff_get_signatures_device(self.h, C.byref(p), C.byref(tot)) != 0:
+            raise HesaffError(-2, "hesaff_get_signatures_device: no embedding is set, or the last call was not device-resident")
+        return p.value, tot.value
+
+    @staticmethod
+    def _desc_words(desc, words):
+        desc = np.ascontiguousarray(desc, dtype=np.uint8)
+        words = _index_words(words)
+        if desc.ndim != 2 or desc.shape[1] != 128 or len(words) != desc.shape[0]:
+            raise ValueError("descriptors are uint8 [n, 128], words int32 [n] or [n, 2]")
+        return desc, words, words.ndim
+
+    def embed(self, desc, words):
+        """hesaff_stage_embed: desc uint8 [n, 128] and their words int32 [n] or (word, dist2) rows [n, 2] -> uint64 [n] signatures under
+        the context's embedding."""
+        desc, words, stride = self._desc_words(desc, words)
+        n = desc.shape[0]
+        out = np.zeros(n, np.uint64)
+        rc = self.L.hesaff_stage_embed(self.h, n, desc.ctypes.data if n else None, words.ctypes.data if n else None, stride, out.ctypes.data if n else None)
+        self._check(rc)
+        return out
+
+    def embed_device(self, ptr, n, stride, offset, words_ptr, word_stride, out_ptr):
+        """hesaff_embed_device: n descriptors in device memory (descriptor i at ptr + i * stride + offset), their words at words_ptr
+        (key i's the int32 at + 4 i word_stride) -> n uint64 at out_ptr (raw device pointers)."""
+        self._check(self.L.hesaff_embed_device(self.h, int(n), C.c_void_p(ptr), int(stride), int(offset), C.c_void_p(words_ptr), int(word_stride), C.c_void_p(out_ptr)))
+
+    def project(self, desc, projection):
+        """hesaff_stage_project: desc uint8 [n, 128] -> z int32 [n, 64] = projection . desc, by the kernel that makes the signatures."""
+        desc = np.ascontiguousarray(desc, dtype=np.uint8)
+        if desc.ndim != 2 or desc.shape[1] != 128:
+            raise ValueError("descriptors are a uint8 array of shape [n, 128]")
+        P = _projection_array(projection)
+        n = desc.shape[0]
+        z = np.zeros((n, EMBED_BITS), np.int32)
+        self._check(self.L.hesaff_stage_project(self.h, n, desc.ctypes.data if n else None, P.ctypes.data, z.ctypes.data if n else None))
+        return z
+
+    def train_embedding(self, desc, words, projection, k=None):
+        """hesaff_train_embedding: desc uint8 [n, 128], their words, projection int8 [64, 128] -> (tau int32 [k, 64], counts uint32 [k]):
+        per word and bit the lower median of the word's projections, 0 for a word without keys.  k defaults to the vocabulary that
+        is set.  The context's own embedding is not touched."""
+        desc, words, stride = self._desc_words(desc, words)
+        P = _projection_array(projection)
+        k = self.vocabulary_size if k is None else int(k)
+        n = desc.shape[0]
+        tau = np.zeros((max(k, 0), EMBED_BITS), np.int32); counts = np.zeros(max(k, 0), np.uint32)
+        self._check(self.L.hesaff_train_embedding(self.h, n, desc.ctypes.data if n else None, words.ctypes.data if n else None, stride, k, P.ctypes.data,
+                                                  tau.ctypes.data, counts.ctypes.data))
+        return tau, counts
+
+    def train_embedding_device(self, ptr, n, stride, offset, words_ptr, word_stride, k, projection):
+        """hesaff_train_embedding_device: the same on n descriptors and words in device memory (raw pointers)."""
+        P = _projection_array(projection)
+        k = int(k)
+        tau = np.zeros((max(k, 0), EMBED_BITS), np.int32); counts = np.zeros(max(k, 0), np.uint32)
+        self._check(self.L.hesaff_train_embedding_device(self.h, int(n), C.c_void_p(ptr), int(stride), int(offset), C.c_void_p(words_ptr), int(word_stride), k,
+                                                         P.ctypes.data, tau.ctypes.data, counts.ctypes.data))
+        return tau, counts
+
+    @property
+    def embedding_ms(self):
+        """HIP-event times (the last signature launch; projection, grouping, medians of the last threshold training) at profiling >= 1, in ms"""
+        v = [C.c_float() for _ in range(4)]
+        self._check(self.L.hesaff_get_embedding_ms(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
     # ---- image index (hesaff_index_build, include/hesaff_amd.h) ----
-    def build_index(self, images, vocabulary_size):
+    def build_index(self, images, vocabulary_size, signatures=None):
         """hesaff_index_build: images is a list with, per image, an int32 array of words [n] or of (word, dist2) rows [n, 2] (what
-        words(i) returns), all of one kind; vocabulary_size is K.  Replaces the context's index."""
+        words(i) returns), all of one kind; vocabulary_size is K.  Replaces the context's index.  signatures: per image a uint64
+        array [n] (what signatures(i) returns) - hesaff_index_build_embedded: the same index with key lists for query_index(hamming=)."""
         arrays = [_index_words(w) for w in images]
         stride = _index_stride(arrays)
         counts = np.array([len(a) for a in arrays], np.int32)
         flat = np.ascontiguousarray(np.concatenate(arrays) if arrays else np.zeros((0,), np.int32))
+        if signatures is not None:
+            if len(signatures) != len(arrays):
+                raise ValueError("one signature array per image")
+            sg = [_signature_array(g, len(a)) for g, a in zip(signatures, arrays)]
+            sflat = np.ascontiguousarray(np.concatenate(sg) if sg else np.zeros(0, np.uint64))
+            self._check(self.L.hesaff_index_build_embedded(self.h, len(arrays), counts.ctypes.data, flat.ctypes.data if flat.size else None, stride,
+                                                           sflat.ctypes.data if sflat.size else None, int(vocabulary_size)))
+            return
         self._check(self.L.hesaff_index_build(self.h, len(arrays), counts.ctypes.data, flat.ctypes.data if flat.size else None, stride, int(vocabulary_size)))
+
+    def build_embedded_index(self, images, signatures, vocabulary_size):
+        """hesaff_index_build_embedded: build_index with a signature per key"""
+        self.build_index(images, vocabulary_size, signatures=signatures)
+
+    def build_embedded_index_device(self, ptr, sigs_ptr, counts, word_stride, vocabulary_size):
+        """hesaff_index_build_embedded_device: words and signatures of all images one after the other in device memory (raw pointers)"""
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        self._check(self.L.hesaff_index_build_embedded_device(self.h, len(counts), counts.ctypes.data, C.c_void_p(ptr), int(word_stride), C.c_void_p(sigs_ptr),
+                                                              int(vocabulary_size)))
+
+    def index_embedded(self):
+        """hesaff_index_get_embedded: None for a plain index, otherwise (offsets uint32 [K + 1], images uint32 [T], sigs uint64 [T]): word
+        w's keys are entries offsets[w] .. offsets[w + 1] - 1, in no particular order"""
+        n, k, t, _ = self._need_index()
+        flag = C.c_int()
+        self._check(self.L.hesaff_index_get_embedded(self.h, C.byref(flag), None, None, None))
+        if not flag.value:
+            return None
+        offsets = np.zeros(k + 1, np.uint32); images = np.zeros(t, np.uint32); sigs = np.zeros(t, np.uint64)
+        self._check(self.L.hesaff_index_get_embedded(self.h, C.byref(flag), offsets.ctypes.data, images.ctypes.data if t else None, sigs.ctypes.data if t else None))
+        return offsets, images, sigs
 
     def build_index_device(self, ptr, counts, word_stride, vocabulary_size):
         """hesaff_index_build_device: the words of all images one after the other in device memory (a raw pointer; key j's word is the
@@ -1244,11 +1489,24 @@ class HesaffContext:
         self._check(call(top, images.ctypes.data, scores.ctypes.data, C.byref(n)))
         return images[:n.value].copy(), scores[:n.value].copy()
 
-    def query_index(self, words, top):
-        """hesaff_index_query: words int32 [n] or [n, 2] -> (images int32 [min(top, N)], scores float64), best first, ties by index."""
+    def query_index(self, words, top, signatures=None, hamming=None):
+        """hesaff_index_query: words int32 [n] or [n, 2] -> (images int32 [min(top, N)], scores float64), best first, ties by index.
+        With signatures uint64 [n] and hamming = T in 0 .. 64 - hesaff_index_query_embedded, on an index built with signatures: a
+        word match counts only where the two signatures differ in at most T bits."""
         w = _index_words(words)
         stride = _index_stride([w])
+        if (signatures is None) != (hamming is None):
+            raise ValueError("signatures and hamming go together")
+        if signatures is not None:
+            g = _signature_array(signatures, len(w))
+            return self._query(lambda *a: self.L.hesaff_index_query_embedded(self.h, len(w), w.ctypes.data if len(w) else None, stride,
+                                                                             g.ctypes.data if len(w) else None, int(hamming), *a), top)
         return self._query(lambda *a: self.L.hesaff_index_query(self.h, len(w), w.ctypes.data if len(w) else None, stride, *a), top)
+
+    def query_embedded_index_device(self, ptr, sigs_ptr, n, word_stride, hamming, top):
+        """hesaff_index_query_embedded_device: the same on n words and signatures in device memory (raw pointers)."""
+        return self._query(lambda *a: self.L.hesaff_index_query_embedded_device(self.h, int(n), C.c_void_p(ptr), int(word_stride), C.c_void_p(sigs_ptr),
+                                                                                int(hamming), *a), top)
 
     def query_index_device(self, ptr, n, word_stride, top):
         """hesaff_index_query_device: the same on n words in device memory (a raw pointer)."""

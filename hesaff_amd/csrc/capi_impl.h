@@ -94,10 +94,13 @@ void detect_device(hesaff_ctx *c, int n, const SrcImages &src, int height, int w
    plan(c, c->par.max_batch, height, width);
    check_source();
    c->word_spans.clear();
+   c->sig_spans.clear();
    c->words_device_total = -1;
+   c->sigs_device_total = -1;
    const BatchResult r = run_batch(c, src, n, height, width, mk);
    const int32_t *hs = r.hessian_starts, *ds = r.desc_starts;
    if (c->vocab.k) { finish_stream(c); c->words_device_total = ds[n]; }   // the words of the batch are in b_words when the call returns
+   if (c->embed.set) c->sigs_device_total = ds[n];                        // ... and the signatures in b_sigs
    for (int b = 0; b < n; b++) {
       if (count_hessian) count_hessian[b] = hs[b + 1] - hs[b];
       if (count_desc) count_desc[b] = ds[b + 1] - ds[b];
@@ -519,6 +522,7 @@ struct ChunkDevice {
          s.text_at = place((size_t)text_bytes);
       }
       if (wants & WANT_BIN) s.bin_at = place(n_rows * EX_BIN_ROW);
+      if (wants & WANT_SIGS) s.sigs_at = place(n_rows * 8);
       if (times_export(s)) HIP_TRY(hipEventRecord(sl.ev_exp[1], c->stream()));
       s.bytes = at;
       dbg_t3 = Clock::now();
@@ -563,6 +567,8 @@ struct ChunkDevice {
             HIP_TRY(hipMemcpyAsync(stg + s.keys_at, c->geo.b_out.p, n_rows * sizeof(hesaff_keypoint), hipMemcpyDeviceToDevice, c->stream()));
          if ((wants & WANT_WORDS) && n_rows > 0)   // (b_words: written by k_assign_words behind the pack stage, on this stream)
             HIP_TRY(hipMemcpyAsync(stg + s.words_at, c->b_words.p, n_rows * 8, hipMemcpyDeviceToDevice, c->stream()));
+         if ((wants & WANT_SIGS) && n_rows > 0)    // (b_sigs: written by k_embed_keys behind b_words, on this stream)
+            HIP_TRY(hipMemcpyAsync(stg + s.sigs_at, c->b_sigs.p, n_rows * 8, hipMemcpyDeviceToDevice, c->stream()));
          if (wants & WANT_REGIONS) pack_regions(c, (uint32_t)s.n_hess, B, (hesaff_region *)(stg + s.regions_at));
          if (times_export(s)) HIP_TRY(hipEventRecord(sl.ev_exp[2], c->stream()));
          if (wants & WANT_TEXT) export_text_write(c, d_keys, (uint32_t)n_rows, stg + s.text_at);
@@ -685,9 +691,15 @@ void detect_images(hesaff_ctx *c, int n, const void *images, bool f32, const int
               di.regions, di.counts, di.from, mi);
    c->words_device_total = -1;
    c->word_spans.clear();
+   c->sig_spans.clear();
+   c->sigs_device_total = -1;
    if (c->vocab.k) {   // the words travel beside the keys (WANT_WORDS); hesaff_get_words finds them by the caller's image index
       c->word_spans.assign((size_t)n, WordSpan());
       io.word_spans = &c->word_spans;
+      if (c->embed.set) {   // ... and so do the signatures (WANT_SIGS; hesaff_get_signatures)
+         c->sig_spans.assign((size_t)n, SigSpan());
+         io.sig_spans = &c->sig_spans;
+      }
    }
    set_consumer(io);
    run_chunks(c, io, ring);
@@ -962,6 +974,8 @@ int hesaff_process_files(hesaff_ctx *c, int n, const char *const *paths, const c
    if ((c->out_format & HESAFF_OUT_WORDS) && c->vocab.k == 0) throw HsError(HESAFF_ERR_ARG, "HESAFF_OUT_WORDS is selected but no vocabulary is set (hesaff_set_vocabulary)");
    c->words_device_total = -1;
    c->word_spans.clear();
+   c->sig_spans.clear();
+   c->sigs_device_total = -1;
    for (int i = 0; i < n; i++) { status[i].rc = HESAFF_ERR_IO; status[i].stage = HESAFF_FILE_PENDING; status[i].count_hessian = 0; status[i].count_desc = 0; }
    hesaff_host_plan hp;
    (void)hesaff_host_plan_for(1, &hp);   // "0 = auto": this context has the host to itself (callers that share it pass the counts of their own plan)
@@ -976,7 +990,7 @@ int hesaff_process_files(hesaff_ctx *c, int n, const char *const *paths, const c
    pin.user = c;
    // the pool's threads step down (nice 10) only where they would otherwise crowd out the caller's thread: a CPU-starved plan
    const bool nice_pool = c->pool_priority == 1 || (c->pool_priority < 0 && hesaff_host_threads() <= dt + wt + 1);
-   FileIO io(&c->ring, c->par.max_batch, c->par.mrSize, c->out_format, n, paths, out_paths, status, dt, wt, true, c->resume, device_jpeg, pin, nice_pool);
+   FileIO io(&c->ring, c->par.max_batch, c->par.mrSize, c->out_format, n, paths, out_paths, status, dt, wt, true, c->resume, device_jpeg, pin, nice_pool, c->embed.set);
    io.vocabulary_size = c->vocab.k;
    c->stage_threads = hesaff_stage_threads_for_pool(dt + wt);
    try {
@@ -1044,8 +1058,13 @@ int hesaff_set_vocabulary(hesaff_ctx *c, int k, const uint8_t *words)
    HIP_TRY(hipStreamSynchronize(c->stream()));   // nothing still reads the vocabulary that goes
    c->vocab = std::move(v);
    c->cells.clear();   // (hesaff_set_vocabulary_cells: first[C] = K describes the vocabulary that went)
+   c->embed.clear();   // (hesaff_set_embedding: tau has the rows of the vocabulary that went)
+   c->b_sigs.release();
    if (k == 0) c->b_words.release();
    c->word_spans.clear();
+   c->sig_spans.clear();
+   c->sigs_device_total = -1;
+   c->embed_timed = false;
    c->words_device_total = -1;
    c->assign_timed = false;
    HS_API_END(c)

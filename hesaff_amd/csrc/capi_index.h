@@ -36,8 +36,14 @@ bool stage_words(const int32_t *words, int word_stride, int64_t n, int k, std::v
    return true;
 }
 
-// the build over `total` checked words in device memory (arguments checked by the caller)
-void build_index_on_device(hesaff_ctx *c, int n_images, const int32_t *counts, const int32_t *d_words, int word_stride, int k, int64_t total)
+// the key lists of an embedded build (capi_embed.h), made in the new index before it becomes the context's
+void build_key_lists(hesaff_ctx *c, hesaff_ctx::Index &nx, int n_images, const int32_t *counts, const int32_t *d_words, int word_stride,
+                     const unsigned long long *d_sigs, int k, int64_t total);
+
+// the build over `total` checked words in device memory (arguments checked by the caller); embedded: with the key lists of
+// hesaff_index_build_embedded over the signatures at d_sigs, behind the plain build's steps, which are the same either way
+void build_index_on_device(hesaff_ctx *c, int n_images, const int32_t *counts, const int32_t *d_words, int word_stride, int k, int64_t total,
+                           const unsigned long long *d_sigs = nullptr, bool embedded = false)
 {
    hesaff_ctx::Index nx;
    StagePlan persistent;
@@ -87,6 +93,7 @@ void build_index_on_device(hesaff_ctx *c, int n_images, const int32_t *counts, c
       HIP_TRY(hipEventElapsedTime(&c->index_ms[1], ev[1], ev[2]));
    }
    nx.n_images = n_images; nx.k = k; nx.n_keys = total; nx.n_postings = n_postings; nx.built = true;
+   if (embedded) build_key_lists(c, nx, n_images, counts, d_words, word_stride, d_sigs, k, total);
    c->index = std::move(nx);
 }
 

@@ -137,11 +137,14 @@ enum { WANT_KEYS = 1,    // the hesaff_keypoint records (hesaff.cpp:41-48)
        WANT_TEXT = 2,    // the rows of the .hesaff.sift files, formatted on the device (kernels_export.h; hesaff.cpp:124-128)
        WANT_BIN = 4,     // the 148-byte rows of the binary sidecar
        WANT_REGIONS = 8, // a hesaff_region per Hessian keypoint (hesaff_detect_regions; pyramid.h:43-47, affine.h:48-58)
-       WANT_WORDS = 16   // two int32 (word, dist2) per record (hesaff_set_vocabulary), row for row the records
+       WANT_WORDS = 16,  // two int32 (word, dist2) per record (hesaff_set_vocabulary), row for row the records
+       WANT_SIGS = 32    // a uint64 signature per record (hesaff_set_embedding), row for row the records; only beside WANT_WORDS
 };
 
 // hesaff_get_words: the rows of one image of the last host call inside the call's result blocks (n = -1: not, or no longer, there)
 struct WordSpan { const int32_t *p = nullptr; int n = -1; };
+// hesaff_get_signatures: the same for the signatures
+struct SigSpan { const uint64_t *p = nullptr; int n = -1; };
 
 struct ChunkDone {
    const HostChunk *chunk;
@@ -154,6 +157,7 @@ struct ChunkDone {
    const char *bin = nullptr;                      // WANT_BIN: image b's rows start at bin + key_off[b] * 148
    const hesaff_region *regions = nullptr;         // WANT_REGIONS: image b's records start at its Hessian offset, the sum of count_hessian[0 .. b)
    const int32_t *words = nullptr;                 // WANT_WORDS: image b's rows start at words + key_off[b] * 2
+   const uint64_t *sigs = nullptr;                 // WANT_SIGS: image b's rows start at sigs + key_off[b]
 };
 
 struct ChunkIO {
@@ -181,8 +185,9 @@ struct ChunkState {
    std::vector<unsigned long long> toff;   // WANT_TEXT: byte offset of every image's rows
    int total = 0;                          // records of the chunk
    size_t n_hess = 0;                      // Hessian keypoints of the chunk
-   // layout of the chunk's result block: [records][words][regions][text rows][sidecar rows], what the consumer wants of them, `bytes` in all
-   size_t keys_at = 0, words_at = 0, regions_at = 0, text_at = 0, bin_at = 0, bytes = 0;
+   // layout of the chunk's result block: [records][words][regions][text rows][sidecar rows][signatures], what the consumer wants of
+   // them, `bytes` in all
+   size_t keys_at = 0, words_at = 0, regions_at = 0, text_at = 0, bin_at = 0, sigs_at = 0, bytes = 0;
    int block = -1;                         // the result block the loop chose: one of the ring, or `no` without a ring
    uint32_t n_rec = 0;                     // hesaff_describe_regions: records of the chunk
    bool copied = false;                    // a copy out was enqueued
@@ -230,6 +235,7 @@ void run_chunk_loop(ChunkIO &io, BlockRing &ring, int ring_blocks, Device &dev)
       if (wants & WANT_BIN) d.bin = blk + s.bin_at;
       if (wants & WANT_REGIONS) d.regions = (const hesaff_region *)(blk + s.regions_at);
       if (wants & WANT_WORDS) d.words = (const int32_t *)(blk + s.words_at);
+      if (wants & WANT_SIGS) d.sigs = (const uint64_t *)(blk + s.sigs_at);
       io.done(d);
    };
 
@@ -307,6 +313,7 @@ struct ArrayIO : ChunkIO {
    void *user = nullptr;
    hesaff_region_result *region_results = nullptr;   // hesaff_detect_regions: filled in place (instead of results)
    std::vector<WordSpan> *word_spans = nullptr;      // a vocabulary is set: every image's word rows are noted here, by the caller's index
+   std::vector<SigSpan> *sig_spans = nullptr;        // an embedding is set as well: the same for the signatures
    std::atomic<int> sink_rc{0};                 // written by done() on the caller's thread, read by next() on the staging thread
    ArrayIO(BlockRing *ring_, int max_batch, int n, const uint8_t *const *images, const int *widths, const int *heights, const int *strides,
            const int *channels, bool f32 = false, const hesaff_region *const *regions = nullptr, const int *counts = nullptr, int from = 0,
@@ -368,7 +375,7 @@ struct ArrayIO : ChunkIO {
       for (size_t i = pos; i < chunks.size() && chunks[i].W == q.W && chunks[i].H == q.H && chunks[i].ch == q.ch && chunks[i].f32 == q.f32; i++) m = std::max(m, chunks[i].data.size());
       return (int)m;
    }
-   int wants() const override { return WANT_KEYS | (region_results ? WANT_REGIONS : 0) | (word_spans ? WANT_WORDS : 0); }
+   int wants() const override { return WANT_KEYS | (region_results ? WANT_REGIONS : 0) | (word_spans ? WANT_WORDS : 0) | (sig_spans ? WANT_SIGS : 0); }
    void note_words(const ChunkDone &d, bool valid)
    {
       if (!word_spans) return;
@@ -376,6 +383,12 @@ struct ArrayIO : ChunkIO {
          WordSpan &w = (*word_spans)[(size_t)d.chunk->index[b]];
          w.n = valid ? d.count_desc[b] : -1;
          w.p = valid && d.count_desc[b] > 0 ? d.words + d.key_off[b] * 2 : nullptr;
+      }
+      if (!sig_spans) return;
+      for (size_t b = 0; b < d.chunk->index.size(); b++) {
+         SigSpan &g = (*sig_spans)[(size_t)d.chunk->index[b]];
+         g.n = valid ? d.count_desc[b] : -1;
+         g.p = valid && d.count_desc[b] > 0 ? d.sigs + d.key_off[b] : nullptr;
       }
    }
    void done(const ChunkDone &d) override
@@ -420,6 +433,8 @@ struct FileIO : ChunkIO {
    float mrSize;
    int fmt;
    int vocabulary_size = 0;   // HESAFF_OUT_WORDS: the header field of the words files
+   bool embedded;             // an embedding is set: HESAFF_OUT_WORDS also writes a signatures file beside every words file (read by the
+                              // pool's threads from their first image on, so it is the constructor's)
    bool device_format;   // rows arrive formatted (ChunkDone::text / bin): the writers only write()
    int resume;           // hesaff_set_resume: an image whose complete output exists is not read (2: the rows of a text output are counted)
    bool nice_pool;       // the pool's threads run at nice 10 (hesaff_set_pool_priority: a CPU-starved plan)
@@ -435,7 +450,7 @@ struct FileIO : ChunkIO {
    std::condition_variable cv_work, cv_img, cv_done;   // workers: a job may be available; next(): an image changed state; wait_writers()
    int next_decode = 0, consumed = 0, window = 0, pos = 0, chunks_out = 0;
    bool stop = false;
-   struct Task { int index; const hesaff_keypoint *keys; int n; int chunk; const char *text; size_t text_len; const char *bin; const int32_t *words; };
+   struct Task { int index; const hesaff_keypoint *keys; int n; int chunk; const char *text; size_t text_len; const char *bin; const int32_t *words; const uint64_t *sigs; };
    std::deque<Task> tasks;
    struct Open { int left; int block; };
    std::vector<Open> open_chunks;
@@ -444,8 +459,8 @@ struct FileIO : ChunkIO {
 
    FileIO(BlockRing *ring_, int max_batch_, float mrSize_, int fmt_, int n_, const char *const *p, const char *const *o, hesaff_file_status *st,
           int dec_threads, int wr_threads, bool device_format_ = false, int resume_ = 0, bool device_jpeg_ = false, PinHooks pin_ = PinHooks(),
-          bool nice_pool_ = false)
-      : ring(ring_), max_batch(max_batch_), n(n_), paths(p), out_paths(o), status(st), mrSize(mrSize_), fmt(fmt_), device_format(device_format_),
+          bool nice_pool_ = false, bool embedded_ = false)
+      : ring(ring_), max_batch(max_batch_), n(n_), paths(p), out_paths(o), status(st), mrSize(mrSize_), fmt(fmt_), embedded(embedded_), device_format(device_format_),
         resume(resume_), nice_pool(nice_pool_), device_jpeg(device_jpeg_), pin(pin_), imgs((size_t)n_)
    {
       window = 2 * max_batch + dec_threads;
@@ -518,6 +533,13 @@ struct FileIO : ChunkIO {
       const char *o = out_paths ? out_paths[i] : nullptr;
       return o ? (std::string(o) + (fmt != HESAFF_OUT_WORDS ? ".words" : "")) : std::string(paths[i]) + ".hesaff.words";
    }
+   // the signatures file beside a words file: its name with ".sigs" in the place of a final ".words", or appended where there is none
+   static std::string sigs_name_for(const std::string &words)
+   {
+      const size_t n = words.size();
+      return n >= 6 && words.compare(n - 6, 6, ".words") == 0 ? words.substr(0, n - 6) + ".sigs" : words + ".sigs";
+   }
+   bool writes_sigs() const { return embedded && (fmt & HESAFF_OUT_WORDS); }
    // Pixel buffers and coefficient blobs come from the context's page-locked memory when it offers some (PinHooks): the reader then
    // fills the buffer the copy engine reads - no malloc'ed image, no staging copy (8 MB per UHD PGM file, 25-50 MB per UHD JPEG blob:
    // 1-4 ms of a host thread per image).  Buffers of images that have reached the device go to the next decoder instead of back to
@@ -572,6 +594,7 @@ struct FileIO : ChunkIO {
          if (fmt & HESAFF_OUT_TEXT) check(hesaff_output_is_complete(out_name(i, false).c_str(), HESAFF_OUT_TEXT | (resume == 2 ? HESAFF_OUT_STRICT : 0)));
          if (complete && (fmt & HESAFF_OUT_BIN)) check(hesaff_output_is_complete(out_name(i, true).c_str(), HESAFF_OUT_BIN));
          if (complete && (fmt & HESAFF_OUT_WORDS)) check(hesaff_output_is_complete(words_name(i).c_str(), HESAFF_OUT_WORDS));
+         if (complete && writes_sigs()) check(hesaff_signatures_is_complete(sigs_name_for(words_name(i)).c_str()));
          if (complete) {
             {
                std::lock_guard<std::mutex> lk(mu);
@@ -679,7 +702,8 @@ struct FileIO : ChunkIO {
             status[i].count_hessian = d.count_hessian[b];
             status[i].count_desc = d.count_desc[b];
             status[i].stage = HESAFF_FILE_DETECTED;
-            Task t{i, d.keys ? d.keys + d.key_off[b] : nullptr, d.count_desc[b], id, nullptr, 0, nullptr, d.words ? d.words + d.key_off[b] * 2 : nullptr};
+            Task t{i, d.keys ? d.keys + d.key_off[b] : nullptr, d.count_desc[b], id, nullptr, 0, nullptr, d.words ? d.words + d.key_off[b] * 2 : nullptr,
+                   d.sigs ? d.sigs + d.key_off[b] : nullptr};
             if (d.text) { t.text = d.text + d.text_off[b]; t.text_len = (size_t)(d.text_off[b + 1] - d.text_off[b]); }
             if (d.bin) t.bin = d.bin + d.key_off[b] * (size_t)148;
             tasks.push_back(t);
@@ -691,7 +715,7 @@ struct FileIO : ChunkIO {
    int wants() const override
    {
       // (a words row is composed on the host from the key's record and its word: both travel)
-      const int words = (fmt & HESAFF_OUT_WORDS) ? (WANT_KEYS | WANT_WORDS) : 0;
+      const int words = (fmt & HESAFF_OUT_WORDS) ? (WANT_KEYS | WANT_WORDS | (embedded ? WANT_SIGS : 0)) : 0;
       if (!device_format) return WANT_KEYS | words;
       return ((fmt & HESAFF_OUT_TEXT) ? WANT_TEXT : 0) | ((fmt & HESAFF_OUT_BIN) ? WANT_BIN : 0) | words;
    }
@@ -715,6 +739,7 @@ struct FileIO : ChunkIO {
          else rc = hesaff_write_bin(name.c_str(), t.keys, t.n, mrSize);
       }
       if ((fmt & HESAFF_OUT_WORDS) && rc == HESAFF_OK) rc = hesaff_write_words(words_name(t.index).c_str(), t.keys, t.words, t.n, mrSize, vocabulary_size);
+      if (writes_sigs() && rc == HESAFF_OK) rc = hesaff_write_signatures(sigs_name_for(words_name(t.index)).c_str(), t.sigs, t.n);
       int blk = -1;
       {
          std::lock_guard<std::mutex> lk(mu);

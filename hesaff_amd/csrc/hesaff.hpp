@@ -159,6 +159,43 @@ struct AffineHessianDetector {
       if (rc == HESAFF_ERR_ARG) throw std::invalid_argument("a vocabulary is k rows of 128 bytes, 0 <= k <= 2^20 (k = 0: none)");
       if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
       words_.clear();
+      sigs_.clear();
+   }
+   // No counterpart in the reference (hesaff_set_embedding, include/hesaff_amd.h): a Hamming embedding over the vocabulary that is set -
+   // P is 64 x 128 signed bytes in -127 .. 127, tau 64 int32 thresholds per row of the vocabulary (both copied; nullptr, nullptr:
+   // none).  With one set every detection also gives each key a 64-bit signature: bit i is P[i] . desc > tau[word][i].
+   // setVocabulary removes the embedding.
+   void setEmbedding(const int8_t *P, const int32_t *tau)
+   {
+      const int rc = hesaff_set_embedding(ctx_, P, tau);
+      if (rc == HESAFF_ERR_ARG) throw std::invalid_argument("an embedding needs a vocabulary, a projection with entries in -127 .. 127 and its thresholds (or neither)");
+      if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+      sigs_.clear();
+   }
+   // a signature per key, parallel to `keys` and to words(): nullptr without an embedding or without keys
+   const uint64_t *signatures() const { return sigs_.empty() ? nullptr : sigs_.data(); }
+   // <image>.hesaff.sigs of the current keys (hesaff_write_signatures), row for row with exportWords' file
+   void exportSignatures(const std::string &path) const
+   {
+      if (hesaff_write_signatures(path.c_str(), sigs_.data(), (int)sigs_.size()) != HESAFF_OK) throw std::runtime_error("cannot write " + path);
+   }
+   // the default projection of a seed (hesaff_embedding_projection): 64 x 128 bytes
+   static std::vector<int8_t> embeddingProjection(uint64_t seed)
+   {
+      std::vector<int8_t> P((size_t)HESAFF_EMBED_BITS * 128);
+      hesaff_embedding_projection(seed, P.data());
+      return P;
+   }
+   // the thresholds of k words (hesaff_train_embedding): per word and bit the lower median of P . desc over the word's keys among n
+   // descriptors of 128 bytes with words[i * wordStride] in 0 .. k - 1 -> k x 64 int32.  The detector's own embedding does not
+   // change: install the result with setEmbedding.
+   std::vector<int32_t> trainEmbedding(const uint8_t *desc, const int32_t *words, int wordStride, int n, int k, const int8_t *P)
+   {
+      std::vector<int32_t> tau((size_t)(k > 0 ? k : 0) * HESAFF_EMBED_BITS);
+      const int rc = hesaff_train_embedding(ctx_, n, desc, words, wordStride, k, P, tau.data(), nullptr);
+      if (rc == HESAFF_ERR_ARG) throw std::invalid_argument("training an embedding needs 1 <= n <= 2^24 descriptors, their words in 0 .. k - 1, k <= 2^20, and a projection in -127 .. 127");
+      if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+      return tau;
    }
    // (word, dist2) per key, two int32 each, parallel to `keys`: nullptr without a vocabulary or without keys
    const int32_t *words() const { return words_.empty() ? nullptr : words_.data(); }
@@ -281,6 +318,27 @@ struct AffineHessianDetector {
       int count = 0;
       const int rc = hesaff_index_query(ctx_, n, words, wordStride, top, images.data(), scores.data(), &count);
       if (rc == HESAFF_ERR_ARG) throw std::invalid_argument("a query needs an index, at most 2^18 words inside its vocabulary and 1 <= top <= 1024");
+      if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+      std::vector<std::pair<int32_t, double>> out((size_t)count);
+      for (int i = 0; i < count; i++) out[(size_t)i] = {images[(size_t)i], scores[(size_t)i]};
+      return out;
+   }
+   // The same index with a signature per key (hesaff_index_build_embedded), for the queryIndex overload below
+   void buildIndex(const std::vector<int32_t> &counts, const int32_t *words, int wordStride, const uint64_t *signatures, int vocabularySize)
+   {
+      const int rc = hesaff_index_build_embedded(ctx_, (int)counts.size(), counts.data(), words, wordStride, signatures, vocabularySize);
+      if (rc == HESAFF_ERR_ARG)
+         throw std::invalid_argument("an embedded index takes 1..2^20 images of at most 2^18 words each in 0 .. vocabularySize - 1 with a signature per word, 2^28 in all");
+      if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+   }
+   // ... where a word match counts only if the two signatures differ in at most `hamming` bits, 0..64 (hesaff_index_query_embedded)
+   std::vector<std::pair<int32_t, double>> queryIndex(const int32_t *words, int n, int wordStride, const uint64_t *signatures, int hamming, int top)
+   {
+      std::vector<int32_t> images((size_t)(top > 0 && top <= 1024 ? top : 1));
+      std::vector<double> scores(images.size());
+      int count = 0;
+      const int rc = hesaff_index_query_embedded(ctx_, n, words, wordStride, signatures, hamming, top, images.data(), scores.data(), &count);
+      if (rc == HESAFF_ERR_ARG) throw std::invalid_argument("an embedded query needs an index built with signatures, words inside its vocabulary, 0 <= hamming <= 64 and 1 <= top <= 1024");
       if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
       std::vector<std::pair<int32_t, double>> out((size_t)count);
       for (int i = 0; i < count; i++) out[(size_t)i] = {images[(size_t)i], scores[(size_t)i]};
@@ -445,6 +503,14 @@ struct AffineHessianDetector {
          if (hesaff_get_words(ctx_, 0, &w, &n) != HESAFF_OK) throw std::runtime_error("hesaff_get_words failed");
          if (n > 0) words_.assign(w, w + 2 * (size_t)n);
       }
+      // ... and their signatures, when an embedding is set as well
+      sigs_.clear();
+      int ek = 0, m = 0;
+      const uint64_t *g = nullptr;
+      if (vk > 0 && hesaff_get_embedding(ctx_, &ek, nullptr, nullptr) == HESAFF_OK && ek > 0) {
+         if (hesaff_get_signatures(ctx_, 0, &g, &m) != HESAFF_OK) throw std::runtime_error("hesaff_get_signatures failed");
+         if (m > 0) sigs_.assign(g, g + (size_t)m);
+      }
    }
    void taken(const hesaff_region_result &r, std::vector<hesaff_region> *described)
    {
@@ -490,6 +556,7 @@ struct AffineHessianDetector {
    HessianKeypointCallback *hessianKeypointCallback_ = nullptr;
    AffineShapeCallback *affineShapeCallback_ = nullptr;
    std::vector<int32_t> words_;      // setVocabulary: (word, dist2) per key
+   std::vector<uint64_t> sigs_;      // setEmbedding: a signature per key
    std::vector<int64_t> distortion_; // trainVocabulary: per iteration that ran
    std::vector<int32_t> empty_;
    const uint8_t *mask_ = nullptr;   // setMask

@@ -46,6 +46,14 @@
 //       squared distance to its descriptor on the device (hesaff_set_vocabulary), and <image>.hesaff.words (hesaff_write_words: x, y, a, b,
 //       c and the word per key) is written beside the .hesaff.sift.  With --batch the same for every image of the list; --words-only
 //       then writes the words files alone.  A vocabulary file that cannot be read ends the run before any image is read.
+//   hesaff --batch <list file> --vocabulary <vocabulary file> --embedding <embedding file>
+//       a Hamming embedding over the vocabulary (hesaff_read_embedding: "HESAFFE1", a 64 x 128 projection and 64 thresholds per row; its
+//       row count must be the vocabulary's): every key also receives a 64-bit signature (hesaff_set_embedding), and <image>.hesaff.sigs
+//       (hesaff_write_signatures) is written beside every words file, row for row with it; --resume counts it as part of the output.
+//   hesaff --batch <list file> --vocabulary <vocabulary file> [--cells <cells file> [--probes P]] --train-embedding <embedding file> [--seed S]
+//       detects and describes every image of the list on one device, assigns every key its word, takes the default projection of seed S
+//       (hesaff_embedding_projection; 0 by default) and sets every word's 64 thresholds to the lower medians of its keys' projections
+//       (hesaff_train_embedding); writes <embedding file>.  No per-image file is written.  At most 2^24 keys, as --train-vocabulary.
 //   hesaff --batch <list file> --train-vocabulary <vocabulary file> --words K [--iterations T]
 //       trains a vocabulary on the list's own descriptors (hesaff_train_vocabulary: exact integer k-means on the device, T = 10 iterations at
 //       most, fewer at a fixed point; the initial rows are keys spread evenly over the list's keys in list order).  Detection runs on one device
@@ -63,11 +71,14 @@
 //       trains C coarse rows (Tc = 10 iterations at most), spreads K initial rows over the list's keys, sorts them into the cells of their
 //       nearest coarse rows (hesaff_build_vocabulary_cells) and trains them inside the cells (hesaff_train_vocabulary_cells); writes
 //       <vocabulary file> and <vocabulary file>.cells.  Needs K >= C.
-//   hesaff --search <list of .hesaff.words files> --query <.hesaff.words file> [--top M] [--device D]
+//   hesaff --search <list of .hesaff.words files> --query <.hesaff.words file> [--top M] [--device D] [--hamming T]
 //       builds an image index on device D (default 0) from the words files the list names, one per line (hesaff_index_build: an inverted
 //       file with integer tf-idf weights; every file must state the same vocabulary size), queries it with the words of the query file
 //       and prints the M best images (default 10, at most 1024), best first, equal scores in list order: rank<TAB>path<TAB>score, the
-//       score as %.17g.  Recognised before --batch and before the single-image form.
+//       score as %.17g.  Recognised before --batch and before the single-image form.  With --hamming T (0..64) the signatures file
+//       beside every words file (".sigs" in the place of the final ".words": what a context with an embedding writes) is read as well,
+//       and a word match counts only where the two 64-bit signatures differ in at most T bits (hesaff_index_query_embedded); a
+//       signatures file that is missing, or whose count differs from its words file's, ends the run with a message that names it.
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -142,7 +153,8 @@ bool parse_devices(const char *spec, std::vector<int> &out)
 // through hesaff_process_files - decode threads -> device -> writer threads, bounded memory - on its own host thread.
 int run_batch_mode(const char *list_path, const char *devices_spec, int out_format, bool dynamic, int fast, int resume, int host_share, int runtime_nice,
                    int max_keypoints, int orientation, int grid_rows, int grid_cols, int descriptor, int orientations,
-                   const uint8_t *vocabulary, int vocabulary_size, const uint8_t *cells_coarse, const uint32_t *cells_first, int cells, int probes)
+                   const uint8_t *vocabulary, int vocabulary_size, const uint8_t *cells_coarse, const uint32_t *cells_first, int cells, int probes,
+                   const int8_t *embed_P, const int32_t *embed_tau)
 {
    std::ifstream lf(list_path);
    if (!lf) { fprintf(stderr, "hesaff: cannot read list '%s'\n", list_path); return 1; }
@@ -208,6 +220,11 @@ int run_batch_mode(const char *list_path, const char *devices_spec, int out_form
          return;
       }
       hesaff_set_vocabulary_probes(ctx, probes);   // (main checked the range)
+      if (embed_P && hesaff_set_embedding(ctx, embed_P, embed_tau) != HESAFF_OK) {   // (main checked its rows against the vocabulary's)
+         errs[(size_t)rank] = hesaff_last_error(ctx);
+         hesaff_destroy(ctx);
+         return;
+      }
       hesaff_host_plan hp;   // this device's share of the host: the library's one rule (include/hesaff_amd.h)
       hesaff_host_plan_for(world * host_share, &hp);
       const int wt = hp.write_threads, dt = hp.decode_threads;
@@ -287,8 +304,17 @@ struct DescSink {
    }
 };
 
+// With `embed` (hesaff --batch <list> --vocabulary <file> --train-embedding <file>): the same collection of descriptors, then their
+// words under the vocabulary (and its cell layer and probes, where given), the default projection of `seed`, the thresholds of every
+// word (hesaff_train_embedding) and the embedding file.
+struct TrainEmbedding {
+   const uint8_t *vocabulary; int vocabulary_size;
+   const uint8_t *cells_coarse; const uint32_t *cells_first; int cells; int probes;
+   uint64_t seed;
+};
+
 int run_train_mode(const char *list_path, const char *devices_spec, const char *out_path, int k, int iterations, int fast, int max_keypoints, int orientation,
-                   int grid_rows, int grid_cols, int descriptor, int orientations, int cells, int coarse_iterations)
+                   int grid_rows, int grid_cols, int descriptor, int orientations, int cells, int coarse_iterations, const TrainEmbedding *embed = nullptr)
 {
    std::ifstream lf(list_path);
    if (!lf) { fprintf(stderr, "hesaff: cannot read list '%s'\n", list_path); return 1; }
@@ -349,12 +375,37 @@ int run_train_mode(const char *list_path, const char *devices_spec, const char *
          return 1;
       }
    }
-   if (total < k) { fprintf(stderr, "hesaff: the list yields %lld keys, fewer than --words %d\n", total, k); return 1; }
+   if (embed && total < 1) { fprintf(stderr, "hesaff: the list yields no key to train an embedding on\n"); return 1; }
+   if (!embed && total < k) { fprintf(stderr, "hesaff: the list yields %lld keys, fewer than --words %d\n", total, k); return 1; }
    std::vector<uint8_t> desc;
    desc.reserve((size_t)total * 128);
    for (std::vector<uint8_t> &d : per_image) {
       desc.insert(desc.end(), d.begin(), d.end());
       std::vector<uint8_t>().swap(d);
+   }
+   if (embed) {
+      const int K = embed->vocabulary_size;
+      if (hesaff_set_vocabulary(ctx, K, embed->vocabulary) != HESAFF_OK ||
+          (embed->cells > 0 && hesaff_set_vocabulary_cells(ctx, embed->cells, embed->cells_coarse, embed->cells_first) != HESAFF_OK) ||
+          hesaff_set_vocabulary_probes(ctx, embed->probes) != HESAFF_OK) {
+         fprintf(stderr, "hesaff: the vocabulary was not set: %s\n", hesaff_last_error(ctx));
+         return 1;
+      }
+      std::vector<int32_t> words((size_t)total * 2), tau((size_t)K * HESAFF_EMBED_BITS);
+      std::vector<uint32_t> counts((size_t)K);
+      std::vector<int8_t> P((size_t)HESAFF_EMBED_BITS * 128);
+      hesaff_embedding_projection(embed->seed, P.data());
+      if (hesaff_stage_assign_words(ctx, (int)total, desc.data(), words.data()) != HESAFF_OK ||
+          hesaff_train_embedding(ctx, total, desc.data(), words.data(), 2, K, P.data(), tau.data(), counts.data()) != HESAFF_OK) {
+         fprintf(stderr, "hesaff: training the embedding failed: %s\n", hesaff_last_error(ctx));
+         return 1;
+      }
+      if (hesaff_write_embedding(out_path, K, P.data(), tau.data()) != HESAFF_OK) { fprintf(stderr, "hesaff: cannot write '%s'\n", out_path); return 1; }
+      long long empty_words = 0;
+      for (uint32_t m : counts) empty_words += m == 0 ? 1 : 0;
+      std::cout << "Trained the thresholds of " << K << " words on " << total << " keys of " << n << " images (seed " << embed->seed << ", " << empty_words
+                << " words without keys)" << std::endl;
+      return rc;
    }
    std::vector<uint8_t> rows((size_t)k * 128);
    std::vector<int64_t> distortion((size_t)iterations);
@@ -397,8 +448,18 @@ int run_train_mode(const char *list_path, const char *devices_spec, const char *
 
 // hesaff --search <list> --query <file>: the word columns of the listed files (hesaff_read_words) into one index, one query, the
 // ranked list on stdout.  With --verify the rows of the query and of the shortlisted files (hesaff_read_words_rows) go through
-// hesaff_verify_matches, and the shortlist is printed in verified order with its inlier counts.
-int run_search_mode(const char *list_path, const char *query_path, int top, int device, bool verify, float tolerance, int max_pairs)
+// hesaff_verify_matches, and the shortlist is printed in verified order with its inlier counts.  With --hamming T (hamming >= 0) the
+// signatures file beside every words file is read as well (hesaff_read_signatures), the index is an embedded one and the query
+// counts a word match only within T bits (hesaff_index_query_embedded); verification keeps its pair rule.
+
+// the signatures file beside a words file: its name with ".sigs" in the place of a final ".words", or appended where there is none
+std::string sigs_name_for(const std::string &words)
+{
+   const size_t n = words.size();
+   return n >= 6 && words.compare(n - 6, 6, ".words") == 0 ? words.substr(0, n - 6) + ".sigs" : words + ".sigs";
+}
+
+int run_search_mode(const char *list_path, const char *query_path, int top, int device, bool verify, float tolerance, int max_pairs, int hamming)
 {
    std::ifstream lf(list_path);
    if (!lf) { fprintf(stderr, "hesaff: cannot read list '%s'\n", list_path); return 1; }
@@ -409,7 +470,25 @@ int run_search_mode(const char *list_path, const char *query_path, int top, int 
    }
    if (names.empty()) { fprintf(stderr, "hesaff: list '%s' names no words file\n", list_path); return 1; }
    std::vector<int32_t> counts, words;
+   std::vector<uint64_t> sigs;
    int k = 0;
+   auto read_sigs = [&](const char *words_path, int count) {
+      const std::string path = sigs_name_for(words_path);
+      uint64_t *g = nullptr;
+      int n = 0;
+      if (hesaff_read_signatures(path.c_str(), &g, &n) != HESAFF_OK) {
+         fprintf(stderr, "hesaff: --hamming needs the signatures file '%s' beside '%s', and it cannot be read (a .hesaff.sigs file expected)\n", path.c_str(), words_path);
+         return false;
+      }
+      if (n != count) {
+         fprintf(stderr, "hesaff: '%s' holds %d signatures, '%s' %d words\n", path.c_str(), n, words_path, count);
+         hesaff_free(g);
+         return false;
+      }
+      sigs.insert(sigs.end(), g, g + n);
+      hesaff_free(g);
+      return true;
+   };
    auto read = [&](const char *path, int &count) {
       int32_t *w = nullptr;
       int vs = 0;
@@ -418,7 +497,7 @@ int run_search_mode(const char *list_path, const char *query_path, int top, int 
       hesaff_free(w);
       if (k == 0) k = vs;
       if (vs != k || vs < 1) { fprintf(stderr, "hesaff: '%s' states vocabulary size %d, the files before it %d\n", path, vs, k); return false; }
-      return true;
+      return hamming < 0 || read_sigs(path, count);
    };
    for (const std::string &name : names) {
       int count = 0;
@@ -434,14 +513,19 @@ int run_search_mode(const char *list_path, const char *query_path, int top, int 
    hesaff_ctx *ctx = nullptr;
    if (hesaff_create(&ctx, &par, device) != HESAFF_OK) { fprintf(stderr, "hesaff: device %d: %s\n", device, hesaff_last_error(nullptr)); return 1; }
    struct Destroy { hesaff_ctx *c; ~Destroy() { hesaff_destroy(c); } } destroy{ctx};
-   if (hesaff_index_build(ctx, (int)counts.size(), counts.data(), words.data(), 1, k) != HESAFF_OK) {
+   const int built = hamming < 0 ? hesaff_index_build(ctx, (int)counts.size(), counts.data(), words.data(), 1, k)
+                                 : hesaff_index_build_embedded(ctx, (int)counts.size(), counts.data(), words.data(), 1, sigs.data(), k);
+   if (built != HESAFF_OK) {
       fprintf(stderr, "hesaff: the index was not built: %s\n", hesaff_last_error(ctx));
       return 1;
    }
    std::vector<int32_t> images((size_t)top);
    std::vector<double> scores((size_t)top);
    int count = 0;
-   if (hesaff_index_query(ctx, n_query, words.data() + indexed, 1, top, images.data(), scores.data(), &count) != HESAFF_OK) {
+   const int asked = hamming < 0 ? hesaff_index_query(ctx, n_query, words.data() + indexed, 1, top, images.data(), scores.data(), &count)
+                                 : hesaff_index_query_embedded(ctx, n_query, words.data() + indexed, 1, sigs.data() + indexed, hamming, top, images.data(),
+                                                               scores.data(), &count);
+   if (asked != HESAFF_OK) {
       fprintf(stderr, "hesaff: the query failed: %s\n", hesaff_last_error(ctx));
       return 1;
    }
@@ -493,7 +577,7 @@ int main(int argc, char **argv)
    for (int i = 1; i < argc; i++) search = search || strcmp(argv[i], "--search") == 0;
    if (search) {
       const char *list = nullptr, *query = nullptr;
-      long top = 10, device = 0, pairs = 1;
+      long top = 10, device = 0, pairs = 1, hamming = -1;
       float tolerance = 8.0f;
       bool bad = false, verify = false, verify_options = false;
       for (int i = 1; i < argc && !bad; i += 2) {
@@ -504,6 +588,7 @@ int main(int argc, char **argv)
          else if (strcmp(argv[i], "--query") == 0 && !query) query = argv[i + 1];
          else if (strcmp(argv[i], "--top") == 0) { top = strtol(argv[i + 1], &end, 10); bad = end == argv[i + 1] || *end || top < 1 || top > 1024; }
          else if (strcmp(argv[i], "--device") == 0) { device = strtol(argv[i + 1], &end, 10); bad = end == argv[i + 1] || *end || device < 0 || device > 4095; }
+         else if (strcmp(argv[i], "--hamming") == 0) { hamming = strtol(argv[i + 1], &end, 10); bad = end == argv[i + 1] || *end || hamming < 0 || hamming > HESAFF_EMBED_BITS; }
          else if (strcmp(argv[i], "--tolerance") == 0) {
             tolerance = strtof(argv[i + 1], &end);
             bad = end == argv[i + 1] || *end || !(tolerance > 0.0f && tolerance <= 1048576.0f);
@@ -513,11 +598,11 @@ int main(int argc, char **argv)
          else bad = true;
       }
       if (bad || !list || !query || (verify_options && !verify)) {
-         fprintf(stderr, "hesaff: usage: hesaff --search <list of .hesaff.words files> --query <.hesaff.words file> [--top 1..1024] [--device D] "
+         fprintf(stderr, "hesaff: usage: hesaff --search <list of .hesaff.words files> --query <.hesaff.words file> [--top 1..1024] [--device D] [--hamming 0..64] "
                          "[--verify [--tolerance PX] [--pairs 1..16]]\n");
          return 1;
       }
-      return run_search_mode(list, query, (int)top, (int)device, verify, tolerance, (int)pairs);
+      return run_search_mode(list, query, (int)top, (int)device, verify, tolerance, (int)pairs, (int)hamming);
    }
    bool batch = false;
    for (int i = 1; i < argc; i++) batch = batch || strcmp(argv[i], "--batch") == 0;
@@ -525,7 +610,9 @@ int main(int argc, char **argv)
       const char *devices = nullptr, *list = nullptr;
       int out_format = HESAFF_OUT_TEXT, fast = 0, host_share = 1, runtime_nice = -1, max_keypoints = 0, orientation = HESAFF_ORI_UP, grid_rows = 1, grid_cols = 1, descriptor = HESAFF_DESC_SIFT, orientations = 1;
       bool bad = false, grid = false, dynamic = false, words_only = false;
-      const char *vocabulary_path = nullptr, *train_path = nullptr, *cells_arg = nullptr;
+      const char *vocabulary_path = nullptr, *train_path = nullptr, *cells_arg = nullptr, *embedding_path = nullptr, *train_embedding_path = nullptr;
+      unsigned long long seed = 0;
+      bool seed_given = false;
       int resume = 0, train_words = 0, train_iterations = 10, train_cells = 0, coarse_iterations = 10, probes = 1;
       bool probes_given = false;
       for (int i = 1; i < argc && !bad; i += 2) {
@@ -536,6 +623,14 @@ int main(int argc, char **argv)
          else if (strcmp(argv[i], "--batch") == 0) list = argv[i + 1];
          else if (strcmp(argv[i], "--devices") == 0) devices = argv[i + 1];
          else if (strcmp(argv[i], "--vocabulary") == 0) vocabulary_path = argv[i + 1];
+         else if (strcmp(argv[i], "--embedding") == 0) embedding_path = argv[i + 1];
+         else if (strcmp(argv[i], "--train-embedding") == 0) train_embedding_path = argv[i + 1];
+         else if (strcmp(argv[i], "--seed") == 0) {
+            char *end = nullptr;
+            seed = strtoull(argv[i + 1], &end, 10);
+            if (argv[i + 1][0] < '0' || argv[i + 1][0] > '9' || *end != 0) bad = true;
+            seed_given = true;
+         }
          else if (strcmp(argv[i], "--train-vocabulary") == 0) train_path = argv[i + 1];
          else if (strcmp(argv[i], "--cells") == 0) cells_arg = argv[i + 1];   // a cells file, or with --train-vocabulary the number of cells
          else if (strcmp(argv[i], "--probes") == 0) {
@@ -604,6 +699,10 @@ int main(int argc, char **argv)
       if (train_path && (train_words < 1 || vocabulary_path || words_only || resume || dynamic || out_format != HESAFF_OUT_TEXT)) bad = true;
       if (!train_path && (train_words > 0 || train_iterations != 10 || coarse_iterations != 10)) bad = true;
       if (cells_arg && !train_path && !vocabulary_path) bad = true;
+      if (embedding_path && (!vocabulary_path || train_path)) bad = true;   // signatures go with words
+      // training an embedding takes the list's keys and a vocabulary and writes one embedding file: nothing that is about per-image files
+      if (train_embedding_path && (!vocabulary_path || train_path || embedding_path || words_only || resume || dynamic || out_format != HESAFF_OUT_TEXT)) bad = true;
+      if (seed_given && !train_embedding_path) bad = true;
       if (cells_arg && train_path) {   // digits only, 1 .. K
          char *end = nullptr;
          const long v = strtol(cells_arg, &end, 10);
@@ -612,7 +711,7 @@ int main(int argc, char **argv)
       }
       if (coarse_iterations != 10 && !train_cells) bad = true;
       if (probes_given && (!cells_arg || train_path)) bad = true;   // probes search a cells FILE's layer; training has one probe
-      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--vocabulary <vocabulary file> [--words-only]] [--train-vocabulary <vocabulary file> --words K [--iterations T]] [--cells <cells file>|C [--coarse-iterations Tc]] [--probes 1..8] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1] [--max-keypoints N] [--orientations 1..4] [--descriptor sift|rootsift] [--orientation up|dominant] [--grid RxC]\n"); return 1; }
+      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--vocabulary <vocabulary file> [--words-only] [--embedding <embedding file>] [--train-embedding <embedding file> [--seed S]]] [--train-vocabulary <vocabulary file> --words K [--iterations T]] [--cells <cells file>|C [--coarse-iterations Tc]] [--probes 1..8] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1] [--max-keypoints N] [--orientations 1..4] [--descriptor sift|rootsift] [--orientation up|dominant] [--grid RxC]\n"); return 1; }
       if (train_path)
          return run_train_mode(list, devices, train_path, train_words, train_iterations, fast, max_keypoints, orientation, grid_rows, grid_cols, descriptor, orientations, train_cells,
                                coarse_iterations);
@@ -633,9 +732,25 @@ int main(int argc, char **argv)
             return 1;
          }
       }
+      int8_t *embed_P = nullptr;
+      int32_t *embed_tau = nullptr;
+      if (embedding_path) {   // likewise
+         int embed_rows = 0;
+         if (hesaff_read_embedding(embedding_path, &embed_P, &embed_tau, &embed_rows) != HESAFF_OK || embed_rows != vocabulary_size) {
+            fprintf(stderr, "hesaff: cannot read embedding '%s' (a HESAFFE1 file over the %d rows of the vocabulary expected)\n", embedding_path, vocabulary_size);
+            hesaff_free(vocabulary); hesaff_free(cells_coarse); hesaff_free(cells_first); hesaff_free(embed_P); hesaff_free(embed_tau);
+            return 1;
+         }
+      }
+      if (train_embedding_path) {
+         const TrainEmbedding te = {vocabulary, vocabulary_size, cells_coarse, cells_first, cells, probes, (uint64_t)seed};
+         const int trc = run_train_mode(list, devices, train_embedding_path, 0, 1, fast, max_keypoints, orientation, grid_rows, grid_cols, descriptor, orientations, 0, 10, &te);
+         hesaff_free(vocabulary); hesaff_free(cells_coarse); hesaff_free(cells_first);
+         return trc;
+      }
       const int brc = run_batch_mode(list, devices, out_format, dynamic, fast, resume, host_share, runtime_nice, max_keypoints, orientation, grid_rows, grid_cols, descriptor,
-                                     orientations, vocabulary, vocabulary_size, cells_coarse, cells_first, cells, probes);
-      hesaff_free(vocabulary); hesaff_free(cells_coarse); hesaff_free(cells_first);
+                                     orientations, vocabulary, vocabulary_size, cells_coarse, cells_first, cells, probes, embed_P, embed_tau);
+      hesaff_free(vocabulary); hesaff_free(cells_coarse); hesaff_free(cells_first); hesaff_free(embed_P); hesaff_free(embed_tau);
       return brc;
    }
    if (argc > 1) {

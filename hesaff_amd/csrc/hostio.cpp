@@ -28,6 +28,7 @@
 #include "../../include/hesaff_amd.h"
 #include "export_fmt.h"
 #include "cells_plan.h"   // cells_first_ok: the rule a cells file is read and written by
+#include "embed_plan.h"   // the generator of the default projection and the heads of the embedding and signatures files
 
 namespace {
 
@@ -1384,6 +1385,128 @@ int hesaff_read_words_rows(const char *path, void **rows, int *count, int *vocab
    if (rc != HESAFF_OK) { free(out); return rc; }
    *rows = out; *count = (int)cnt; *vocabulary_size = (int)vs;
    return HESAFF_OK;
+}
+
+// ---- Hamming embedding (hesaff_set_embedding): the default projection and the two files; the rules are embed_plan.h's ----
+
+int hesaff_embedding_projection(uint64_t seed, int8_t *P)
+{
+   if (!P) return HESAFF_ERR_ARG;
+   hesaff_plan::embedding_projection(seed, P);
+   return HESAFF_OK;
+}
+
+// `bytes` bytes from offset `at` of fd into a malloc'ed block -> HESAFF_OK, HESAFF_ERR_NOMEM, or HESAFF_ERR_IO for a short file
+static int read_block(int fd, size_t at, size_t bytes, char **out)
+{
+   char *buf = (char *)malloc(bytes ? bytes : 1);
+   if (!buf) return HESAFF_ERR_NOMEM;
+   size_t done = 0;
+   while (done < bytes) {
+      const ssize_t r = pread(fd, buf + done, bytes - done, (off_t)(at + done));
+      if (r < 0 && errno == EINTR) continue;
+      if (r <= 0) break;
+      done += (size_t)r;
+   }
+   if (done != bytes) { free(buf); return HESAFF_ERR_IO; }
+   *out = buf;
+   return HESAFF_OK;
+}
+
+// Embedding file, kept beside the vocabulary file of the same k rows.  Little-endian:
+//   char magic[8] = "HESAFFE1"; uint32 bits = 64, dim = 128, k, reserved = 0; int8 P[64][128]; int32 tau[k][64]
+int hesaff_write_embedding(const char *path, int k, const int8_t *P, const int32_t *tau)
+{
+   if (!path || !tau || k < 1 || k > (1 << 20) || !hesaff_plan::embed_projection_ok(P)) return HESAFF_ERR_ARG;
+   HOSTIO_TRY
+   const size_t tau_bytes = (size_t)k * hesaff_plan::HS_EMBED_BITS * 4;
+   std::vector<char> body(hesaff_plan::HS_EMBED_P_BYTES + tau_bytes);
+   memcpy(body.data(), P, hesaff_plan::HS_EMBED_P_BYTES);
+   memcpy(body.data() + hesaff_plan::HS_EMBED_P_BYTES, tau, tau_bytes);
+   std::string part;
+   const int fd = open_part(path, part);
+   if (fd < 0) return HESAFF_ERR_IO;
+   char head[hesaff_plan::HS_EMBED_FILE_HEAD];
+   hesaff_plan::embed_file_head(head, (uint32_t)k);
+   return finish_part(fd, write_head_body(fd, head, sizeof head, body.data(), body.size()), part, path);
+   HOSTIO_CATCH
+}
+
+// -> P[64][128] and tau[k][64], malloc'ed (hesaff_free).  HESAFF_ERR_IO: the file cannot be read, or is not a whole embedding file
+// (wrong magic, bits other than 64, dim other than 128, k outside 1 .. 2^20, a reserved word other than 0, a size other than
+// 24 + 8192 + 256 k, an entry of P that is -128).
+int hesaff_read_embedding(const char *path, int8_t **P, int32_t **tau, int *k)
+{
+   if (!path || !P || !tau || !k) return HESAFF_ERR_ARG;
+   *P = nullptr; *tau = nullptr; *k = 0;
+   const int fd = open(path, O_RDONLY | O_CLOEXEC);
+   if (fd < 0) return HESAFF_ERR_IO;
+   int rc = HESAFF_ERR_IO;
+   char *p = nullptr, *t = nullptr;
+   const off_t size = lseek(fd, 0, SEEK_END);
+   char head[hesaff_plan::HS_EMBED_FILE_HEAD];
+   int64_t rows = -1;
+   if (size >= (off_t)sizeof head && pread(fd, head, sizeof head, 0) == (ssize_t)sizeof head) rows = hesaff_plan::embed_file_rows(head, (uint64_t)size);
+   if (rows >= 1) {
+      rc = read_block(fd, sizeof head, hesaff_plan::HS_EMBED_P_BYTES, &p);
+      if (rc == HESAFF_OK && !hesaff_plan::embed_projection_ok((const int8_t *)p)) rc = HESAFF_ERR_IO;
+      if (rc == HESAFF_OK) rc = read_block(fd, sizeof head + hesaff_plan::HS_EMBED_P_BYTES, (size_t)rows * hesaff_plan::HS_EMBED_BITS * 4, &t);
+   }
+   close(fd);
+   if (rc != HESAFF_OK) { free(p); free(t); return rc; }
+   *P = (int8_t *)p; *tau = (int32_t *)t; *k = (int)rows;
+   return HESAFF_OK;
+}
+
+// Signatures file of an image, beside its words file and row for row with it.  Little-endian:
+//   char magic[8] = "HESAFFS1"; uint32 bits = 64; uint32 count; count x uint64
+int hesaff_write_signatures(const char *path, const uint64_t *sigs, int n)
+{
+   if (!path || n < 0 || (n > 0 && !sigs)) return HESAFF_ERR_ARG;
+   HOSTIO_TRY
+   std::string part;
+   const int fd = open_part(path, part);
+   if (fd < 0) return HESAFF_ERR_IO;
+   char head[hesaff_plan::HS_SIGS_FILE_HEAD];
+   hesaff_plan::sigs_file_head(head, (uint32_t)n);
+   return finish_part(fd, write_head_body(fd, head, sizeof head, (const char *)sigs, (size_t)n * 8), part, path);
+   HOSTIO_CATCH
+}
+
+// -> the signatures, malloc'ed (hesaff_free; NULL for a file of no rows).  HESAFF_ERR_IO: the file cannot be read, or is not a whole
+// signatures file (wrong magic, bits other than 64, a size other than 16 + 8 count).
+int hesaff_read_signatures(const char *path, uint64_t **sigs, int *count)
+{
+   if (!path || !sigs || !count) return HESAFF_ERR_ARG;
+   *sigs = nullptr; *count = 0;
+   const int fd = open(path, O_RDONLY | O_CLOEXEC);
+   if (fd < 0) return HESAFF_ERR_IO;
+   int rc = HESAFF_ERR_IO;
+   char *out = nullptr;
+   const off_t size = lseek(fd, 0, SEEK_END);
+   char head[hesaff_plan::HS_SIGS_FILE_HEAD];
+   int64_t cnt = -1;
+   if (size >= (off_t)sizeof head && pread(fd, head, sizeof head, 0) == (ssize_t)sizeof head) cnt = hesaff_plan::sigs_file_count(head, (uint64_t)size);
+   if (cnt == 0) rc = HESAFF_OK;
+   else if (cnt > 0) rc = read_block(fd, sizeof head, (size_t)cnt * 8, &out);
+   close(fd);
+   if (rc != HESAFF_OK) return rc;
+   *sigs = (uint64_t *)out; *count = (int)cnt;
+   return HESAFF_OK;
+}
+
+// hesaff_output_is_complete's test for a signatures file: its number of rows, or -1 (an O(1) test: magic, bits, size)
+int hesaff_signatures_is_complete(const char *path)
+{
+   if (!path) return -1;
+   const int fd = open(path, O_RDONLY | O_CLOEXEC);
+   if (fd < 0) return -1;
+   const off_t size = lseek(fd, 0, SEEK_END);
+   char head[hesaff_plan::HS_SIGS_FILE_HEAD];
+   int64_t cnt = -1;
+   if (size >= (off_t)sizeof head && pread(fd, head, sizeof head, 0) == (ssize_t)sizeof head) cnt = hesaff_plan::sigs_file_count(head, (uint64_t)size);
+   close(fd);
+   return (int)cnt;
 }
 
 // One file per image of a batch (exportKeypoints once per image, hesaff.cpp:170-176), images

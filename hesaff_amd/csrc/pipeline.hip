@@ -45,6 +45,7 @@
 #include "kernels_cells.h"
 #include "kernels_index.h"
 #include "kernels_verify.h"
+#include "kernels_embed.h"
 #include "chunk_engine.h"
 #include "batch_plan.h"
 #include "buffer_layouts.h"
@@ -54,6 +55,7 @@
 #include "cells_plan.h"
 #include "index_plan.h"
 #include "verify_plan.h"
+#include "embed_plan.h"
 
 static thread_local std::string g_create_error;
 
@@ -469,11 +471,34 @@ struct hesaff_ctx {
    struct Index {
       DevBuf tables, lists, qwords;    // qwords: the staged words of a host query
       IndexArrays a;
+      // hesaff_index_build_embedded: word-major key lists of (image, signature) beside the postings (embed_plan.h: KeyListArrays in
+      // `keys`); a plain build leaves them empty
+      DevBuf keys, qsigs;              // qsigs: the staged signatures of a host query
+      KeyListArrays ka;
+      bool embedded = false;
+      template <class T> T *kptr(const Span<T> &s) const { return keys.at<T>(s.off); }
       int n_images = 0, k = 0;
       int64_t n_keys = 0, n_postings = 0;
       bool built = false;
       template <class T> T *ptr(const Span<T> &s) const { return tables.at<T>(s.off); }
    } index;
+   // hesaff_set_embedding: the projection as k_embed_keys reads it and the thresholds of every word (embed_plan.h: EmbedArrays in `buf`);
+   // not set: nothing here is allocated, launched or copied, and the assignment stops at the words
+   struct Embedding {
+      DevBuf buf;
+      EmbedArrays a;
+      int k = 0;                       // the rows of tau: the vocabulary's
+      bool set = false;
+      std::vector<int8_t> P;           // hesaff_get_embedding: P as the caller gave it
+      template <class T> T *ptr(const Span<T> &s) const { return buf.at<T>(s.off); }
+      void clear() { buf.release(); k = 0; set = false; P.clear(); P.shrink_to_fit(); }
+   } embed;
+   DevBuf b_sigs;                      // a signature per record of b_out, written behind b_words of every batch
+   int64_t sigs_device_total = -1;     // hesaff_get_signatures_device: the rows of b_sigs after a device-resident call (-1: as words_device_total)
+   std::vector<hesaff_engine::SigSpan> sig_spans;   // hesaff_get_signatures: per image of the last host call, its rows in the call's result blocks
+   DevEvent ev_embed[2];               // profiling: brackets of the last k_embed_keys launch
+   bool embed_timed = false;
+   float embed_train_ms[3] = {0.0f, 0.0f, 0.0f};   // hesaff_get_embedding_ms: projection, grouping, medians of the last threshold training
    float index_ms[3] = {0.0f, 0.0f, 0.0f};   // hesaff_get_index_ms: the last build's hash step and list steps, the last query (profiling >= 1)
    // hesaff_verify_matches: the result of the last call (verify_plan.h: VerifyResultArrays in `result`); no call: nothing here is
    // allocated, launched or copied
@@ -1397,13 +1422,43 @@ void launch_assign_words(hesaff_ctx *c, const void *d_desc, long long n, long lo
    if (timed) { HIP_TRY(hipEventRecord(c->ev_assign[1], st)); c->assign_timed = true; }
 }
 
-// the words of a batch's ordered records (b_out), behind the pack stage: b_words row for row
+// k_embed_keys against a packed projection (the context's, or the private one of a threshold training), n >= 1, on stream st
+template <bool RAW>
+void launch_embed_kernel(hipStream_t st, const void *tiles, const int32_t *bias, const int32_t *tau, const void *d_desc, long long n, long long stride,
+                         long long offset, const int32_t *d_words, int word_stride, void *d_out)
+{
+   const long long blocks = (n + HS_EMBED_BLOCK_WAVES * HS_EMBED_WAVE_KEYS - 1) / (HS_EMBED_BLOCK_WAVES * HS_EMBED_WAVE_KEYS);
+   hipLaunchKernelGGL(k_embed_keys<RAW>, dim3((uint32_t)blocks), dim3(HS_EMBED_BLOCK_WAVES * 64), 0, st, (const uint8_t *)d_desc, n, stride, offset, d_words,
+                      word_stride, (const hs_v4i *)tiles, bias, tau, d_out);
+}
+
+// The signatures (kernels_embed.h) of n descriptors in device memory whose words - by the flat assignment, through cells or through
+// probes: the word alone selects the thresholds - are at d_words, on the main stream: a uint64 per key into d_out.  With profiling
+// on, it is bracketed for hesaff_get_embedding_ms.
+void launch_embed_keys(hesaff_ctx *c, const void *d_desc, long long n, long long stride, long long offset, const int32_t *d_words, int word_stride, void *d_out)
+{
+   c->embed_timed = false;
+   if (n <= 0) return;
+   hipStream_t st = c->stream();
+   const bool timed = c->profiling >= 1;
+   if (timed && !c->ev_embed[0]) { c->ev_embed[0] = DevEvent(hipEventDefault); c->ev_embed[1] = DevEvent(hipEventDefault); }
+   if (timed) HIP_TRY(hipEventRecord(c->ev_embed[0], st));
+   launch_embed_kernel<false>(st, c->embed.ptr(c->embed.a.tiles), c->embed.ptr(c->embed.a.bias), c->embed.ptr(c->embed.a.tau), d_desc, n, stride, offset, d_words,
+                              word_stride, d_out);
+   if (timed) { HIP_TRY(hipEventRecord(c->ev_embed[1], st)); c->embed_timed = true; }
+}
+
+// the words of a batch's ordered records (b_out), behind the pack stage: b_words row for row; with an embedding set, b_sigs behind them
 void assign_batch_words(hesaff_ctx *c, long long total)
 {
    c->assign_timed = false;
+   c->embed_timed = false;
    if (c->vocab.k == 0 || total <= 0) return;
    c->b_words.ensure_grow((size_t)total * 8);
    launch_assign_words(c, c->geo.b_out.p, total, (long long)sizeof(KeyRec), (long long)offsetof(KeyRec, desc), c->b_words.p);
+   if (!c->embed.set) return;
+   c->b_sigs.ensure_grow((size_t)total * 8);
+   launch_embed_keys(c, c->geo.b_out.p, total, (long long)sizeof(KeyRec), (long long)offsetof(KeyRec, desc), c->b_words.as<int32_t>(), 2, c->b_sigs.p);
 }
 
 // Everything after the Hessian list of a batch is complete - by detection (run_batch) or from the caller's records (run_describe):
@@ -1679,3 +1734,4 @@ void pack_regions(hesaff_ctx *c, uint32_t n_hess, int B, hesaff_region *d_region
 #include "capi_cells.h"
 #include "capi_index.h"
 #include "capi_verify.h"
+#include "capi_embed.h"

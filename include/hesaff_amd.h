@@ -57,6 +57,7 @@ extern "C" {
  *    And for spatial verification (hesaff_verify_matches and the six symbols declared with it): symbols only, version 8.
  *    And for vocabulary cells (hesaff_set_vocabulary_cells and the eight symbols declared with it): symbols only, version 8.
  *    And for vocabulary probes (hesaff_set_vocabulary_probes / hesaff_get_vocabulary_probes / hesaff_stage_probe_cells): symbols only, version 8.
+ *    And for Hamming embedding (hesaff_set_embedding and the twenty symbols declared with it): symbols only, version 8.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -737,6 +738,94 @@ int hesaff_index_get_info(const hesaff_ctx *ctx, int *n_images, int *vocabulary_
 int hesaff_index_clear(hesaff_ctx *ctx);
 int hesaff_get_index_ms(const hesaff_ctx *ctx, float *build_ms, float *query_ms);
 int hesaff_read_words(const char *path, int32_t **words, int *count, int *vocabulary_size);
+
+/* Hamming embedding (no counterpart in the reference; Jegou, Douze, Schmid, ECCV 2008): a 64-bit signature per key places the key
+ * inside its word's cell, and a word match counts only where the two signatures are within a Hamming threshold.  Symbols only,
+ * version 8.  All arithmetic is integer, and every result is exact to the bit.
+ * Projection.  P[64][128] is signed bytes, every entry in -127 .. 127 (an entry of -128 is HESAFF_ERR_ARG).  For the descriptor bytes
+ * d[0..127] (unsigned) of a key:  z[i] = sum_j P[i][j] * d[j],  |z[i]| <= 128 * 127 * 255 = 4 145 280 < 2^22.
+ * hesaff_embedding_projection(seed, P): the default projection, pure host code.  Entry e = i * 128 + j, e = 0, 1, .., is the e-th
+ * output of splitmix64 from s = seed (uint64 arithmetic):
+ *     s += 0x9E3779B97F4A7C15;  x = s;  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;  x = (x ^ (x >> 27)) * 0x94D049BB133111EB;  x ^= x >> 31;
+ *     v = (int)(x >> 56) - 128, and -128 becomes -127.
+ * Signature of a key with word w: bit i (bit 0 the least significant) of a uint64 is  z[i] > tau[w][i],  strictly greater; tau is
+ * int32[K][64], any values, K the rows of the vocabulary that is set.
+ * hesaff_set_embedding(ctx, P, tau): needs a vocabulary; both are copied.  NULL, NULL removes the embedding.  hesaff_set_vocabulary
+ * removes it as it removes the cells; hesaff_set_vocabulary_cells and hesaff_set_vocabulary_probes leave it (the word alone selects
+ * the thresholds, however it was found).  With an embedding set, every call that assigns words also makes the signatures, behind
+ * the words: hesaff_get_signatures hands out those of one image of the last host call, row for row with hesaff_get_words and with
+ * its lifetime; hesaff_get_signatures_device those of the last device-resident call, parallel to hesaff_get_words_device (8-byte
+ * aligned device memory of the context, valid until its next call); hesaff_process_files with HESAFF_OUT_WORDS writes a signatures
+ * file beside every words file - its name with ".sigs" in the place of the final ".words", or appended where there is none - and
+ * hesaff_set_resume counts it as part of the output.  Without an embedding nothing is launched, allocated, copied or written, and
+ * keys, words and words files are those of a context that never had one.  hesaff_get_embedding: *k = the rows of tau (0: none set);
+ * P[64][128] and tau[k][64] are filled where not NULL.
+ * hesaff_embed_device: n descriptors in device memory (descriptor i at d_desc + i * stride + offset, hesaff_assign_words_device's
+ * rules), key i's word the int32 at d_words + 4 i word_stride (word_stride 1 or 2) -> n uint64 at d_sigs_out (8-byte aligned).
+ * hesaff_stage_embed: the same on host arrays.  hesaff_stage_project: z[n][64] = P . d of the caller's descriptors under the
+ * caller's P, by the kernel that makes the signatures; needs neither vocabulary nor embedding.
+ * Thresholds by training.  hesaff_train_embedding(ctx, n, desc, words, word_stride, k, P, tau_out, counts_out), 1 <= n <= 2^24,
+ * 1 <= k <= 2^20, every word in 0 .. k - 1: with m_w the number of keys of word w, tau_out[w][i] is the LOWER MEDIAN of that word's
+ * z[i] - element (m_w - 1) / 2 of the values sorted ascending - or 0 for every i where m_w = 0, and counts_out[w] = m_w (may be NULL).
+ * Nothing depends on the order of arrival or the launch geometry: two calls give the same bytes.  The context's own embedding and
+ * vocabulary are neither read nor written; the working set (256 bytes per key for z, 256 per word) is released before the call returns.
+ * hesaff_train_embedding_device: the same on descriptors and words in device memory.
+ * hesaff_get_embedding_ms: HIP-event times at profiling level >= 1, 0 otherwise: of the last signature launch (a batch's, or
+ * hesaff_embed_device's), and of the last training's projection, grouping and median steps.
+ * Embedded index.  hesaff_index_build_embedded takes a signature per key beside hesaff_index_build's words (sigs[j] belongs to key
+ * j; always packed).  It produces exactly the plain index's df, idf, offsets, postings and norm2, bit for bit, and word-major key
+ * lists of (image, signature); the order of the entries inside a list is unspecified, only sums over a list are output.  A plain
+ * hesaff_index_query on an embedded index answers as on a plain one.  hesaff_index_query_embedded with threshold T, 0 <= T <= 64:
+ *     dot_T(i) = sum over every query key q and every key j of image i with word_j = word_q and popcount(sig_q ^ sig_j) <= T
+ *                of idf(word_q)^2                                                          uint64
+ *     nq2 and norm2(i) are the plain index's; score(i) = 0.0 where dot_T(i) = 0, otherwise
+ *                (double)dot_T(i) / sqrt((double)nq2 * (double)norm2(i)), the plain query's three binary64 operations;
+ *     ranking and ties as the plain query.
+ * So T = 64 is the plain query bit for bit (dot, nq2, scores, ranking), and dot_T(i) never decreases with T.  The bounds are the plain
+ * index's: dot_T <= dot < 2^62.  hesaff_index_get_scores is valid after it.  hesaff_index_get_embedded: *embedded = 1 where the index
+ * that is built holds key lists; then offsets[K + 1], and per list entry its image and its signature (images[T], sigs[T]; each may
+ * be NULL; on a plain index all three must be NULL).
+ * Files, little-endian.  Embedding, kept beside the vocabulary file of the same k rows:
+ *     char magic[8] = "HESAFFE1"; uint32 bits = 64, dim = 128, k, reserved = 0; int8 P[64][128]; int32 tau[k][64]
+ * Signatures of an image, row for row with its words file:
+ *     char magic[8] = "HESAFFS1"; uint32 bits = 64; uint32 count; count x uint64
+ * The readers return malloc'ed arrays (hesaff_free; *sigs NULL where count is 0) and HESAFF_ERR_IO for anything that cannot be
+ * read or is not a whole file of the format (magic, bits, dim, k outside 1 .. 2^20, reserved, size against count, a P entry of -128).
+ * hesaff_signatures_is_complete: the O(1) test of hesaff_set_resume - the rows of a whole signatures file, or -1.
+ * HESAFF_ERR_ARG, nothing changed, the context usable as before: ctx or a required pointer NULL (P and tau not both NULL or both set);
+ * no vocabulary, or no embedding, where one is needed; a P entry of -128; T outside 0 .. 64; an embedded query on a plain index, or
+ * with no index; a word outside 0 .. K - 1; a count outside the bounds; word_stride not 1 or 2; a descriptor or word pointer in
+ * device memory that is not 4-byte aligned, a signature pointer that is not 8-byte aligned.
+ * HESAFF_ERR_NOMEM: the device cannot hold the arrays; the previous embedding, or the previous index, then stays. */
+#define HESAFF_EMBED_BITS 64
+int hesaff_embedding_projection(uint64_t seed, int8_t *P);
+int hesaff_set_embedding(hesaff_ctx *ctx, const int8_t *P, const int32_t *tau);
+int hesaff_get_embedding(const hesaff_ctx *ctx, int *k, int8_t *P, int32_t *tau);
+int hesaff_get_signatures(const hesaff_ctx *ctx, int image, const uint64_t **sigs, int *count);
+int hesaff_get_signatures_device(const hesaff_ctx *ctx, const void **d_sigs, int64_t *total);
+int hesaff_embed_device(hesaff_ctx *ctx, int64_t n, const void *d_desc, int64_t stride, int64_t offset, const void *d_words, int word_stride,
+                        void *d_sigs_out);
+int hesaff_stage_embed(hesaff_ctx *ctx, int n, const uint8_t *desc, const int32_t *words, int word_stride, uint64_t *sigs_out);
+int hesaff_stage_project(hesaff_ctx *ctx, int n, const uint8_t *desc, const int8_t *P, int32_t *z_out);
+int hesaff_train_embedding(hesaff_ctx *ctx, int64_t n, const uint8_t *desc, const int32_t *words, int word_stride, int k, const int8_t *P,
+                           int32_t *tau_out, uint32_t *counts_out);
+int hesaff_train_embedding_device(hesaff_ctx *ctx, int64_t n, const void *d_desc, int64_t stride, int64_t offset, const void *d_words,
+                                  int word_stride, int k, const int8_t *P, int32_t *tau_out, uint32_t *counts_out);
+int hesaff_get_embedding_ms(const hesaff_ctx *ctx, float *embed_ms, float *project_ms, float *group_ms, float *median_ms);
+int hesaff_index_build_embedded(hesaff_ctx *ctx, int n_images, const int32_t *counts, const int32_t *words, int word_stride,
+                                const uint64_t *sigs, int vocabulary_size);
+int hesaff_index_build_embedded_device(hesaff_ctx *ctx, int n_images, const int32_t *counts, const void *d_words, int word_stride,
+                                       const void *d_sigs, int vocabulary_size);
+int hesaff_index_query_embedded(hesaff_ctx *ctx, int n, const int32_t *words, int word_stride, const uint64_t *sigs, int hamming, int top,
+                                int32_t *images_out, double *scores_out, int *count_out);
+int hesaff_index_query_embedded_device(hesaff_ctx *ctx, int n, const void *d_words, int word_stride, const void *d_sigs, int hamming, int top,
+                                       int32_t *images_out, double *scores_out, int *count_out);
+int hesaff_index_get_embedded(const hesaff_ctx *ctx, int *embedded, uint32_t *offsets, uint32_t *images, uint64_t *sigs);
+int hesaff_write_embedding(const char *path, int k, const int8_t *P, const int32_t *tau);
+int hesaff_read_embedding(const char *path, int8_t **P, int32_t **tau, int *k);
+int hesaff_write_signatures(const char *path, const uint64_t *sigs, int n);
+int hesaff_read_signatures(const char *path, uint64_t **sigs, int *count);
+int hesaff_signatures_is_complete(const char *path);
 
 /* Spatial verification (no counterpart in the reference): the shortlist of a tf-idf query re-ranked by how many tentative
  * correspondences agree with the best single-correspondence affine hypothesis - the "fast spatial matching" of Philbin et al. 2007

@@ -49,6 +49,8 @@ from ._binding import (  # noqa: F401
     write_embedding,
     read_signatures,
     write_signatures,
+    read_index_file,
+    write_index_file,
     read_image,
     read_pnm,
     read_jpeg_coefficients,

@@ -312,6 +312,17 @@ def load_library():
         L.hesaff_write_signatures.argtypes = [C.c_char_p, vp, C.c_int]
         L.hesaff_read_signatures.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int)]
         L.hesaff_signatures_is_complete.argtypes = [C.c_char_p]
+    if hasattr(L, "hesaff_index_add"):   # (likewise)
+        L.hesaff_index_add.argtypes = [vp, C.c_int, vp, vp, C.c_int]
+        L.hesaff_index_add_device.argtypes = [vp, C.c_int, vp, vp, C.c_int]
+        L.hesaff_index_add_embedded.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
+        L.hesaff_index_add_embedded_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
+        L.hesaff_index_get_postings.argtypes = [vp, vp, vp, vp]
+        L.hesaff_index_save.argtypes = [vp, C.c_char_p]
+        L.hesaff_index_load.argtypes = [vp, C.c_char_p]
+        L.hesaff_get_index_growth_ms.argtypes = [vp] + [C.POINTER(C.c_float)] * 5
+        L.hesaff_write_index_file.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, i64, i64, vp, vp, vp, vp, vp]
+        L.hesaff_read_index_file.argtypes = [C.c_char_p] + [C.POINTER(C.c_int)] * 3 + [C.POINTER(i64)] * 2 + [C.POINTER(vp)] * 5
     L.hesaff_stage_math_sift_general.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math_sift.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]
@@ -369,6 +380,8 @@ ABI_SYMBOLS = [
     "hesaff_get_embedding_ms", "hesaff_index_build_embedded", "hesaff_index_build_embedded_device", "hesaff_index_query_embedded",
     "hesaff_index_query_embedded_device", "hesaff_index_get_embedded", "hesaff_write_embedding", "hesaff_read_embedding",
     "hesaff_write_signatures", "hesaff_read_signatures", "hesaff_signatures_is_complete",
+    "hesaff_index_add", "hesaff_index_add_device", "hesaff_index_add_embedded", "hesaff_index_add_embedded_device", "hesaff_index_get_postings",
+    "hesaff_index_save", "hesaff_index_load", "hesaff_get_index_growth_ms", "hesaff_write_index_file", "hesaff_read_index_file",
 ]
 
 # hesaff_set_output_format's bits
@@ -684,6 +697,49 @@ def read_embedding(path):
         L.hesaff_free(P)
         L.hesaff_free(tau)
     return p.reshape(EMBED_BITS, 128), t.reshape(k.value, EMBED_BITS)
+
+
+def write_index_file(path, n_images, n_keys, df, postings, key_count=None, key_image=None, key_sig=None):
+    """hesaff_write_index_file: an index file ("HESAFFI1") from host arrays - df uint32 [K], postings uint32 [n_postings, 2] = (image, tf)
+    word-major, and for an embedded index key_count uint32 [K], key_image uint32 [n_keys], key_sig uint64 [n_keys]."""
+    df = np.ascontiguousarray(df, dtype=np.uint32).reshape(-1)
+    postings = np.ascontiguousarray(postings, dtype=np.uint32).reshape(-1, 2)
+    embedded = key_count is not None
+    kc = ki = ks = None
+    if embedded:
+        kc = np.ascontiguousarray(key_count, dtype=np.uint32).reshape(-1)
+        ki = np.ascontiguousarray(key_image, dtype=np.uint32).reshape(-1)
+        ks = np.ascontiguousarray(key_sig, dtype=np.uint64).reshape(-1)
+        if len(kc) != len(df) or len(ki) != n_keys or len(ks) != n_keys:
+            raise ValueError("key_count has K entries, key_image and key_sig n_keys")
+    rc = load_library().hesaff_write_index_file(os.fsencode(path), int(embedded), len(df), int(n_images), int(n_keys), len(postings), df.ctypes.data,
+                                                postings.ctypes.data if len(postings) else None, kc.ctypes.data if embedded else None,
+                                                ki.ctypes.data if embedded and n_keys else None, ks.ctypes.data if embedded and n_keys else None)
+    if rc != 0:
+        raise HesaffError(rc, "hesaff_write_index_file(%s)" % path)
+
+
+def read_index_file(path):
+    """hesaff_read_index_file: an index file -> a dict of embedded, k, n_images, n_keys, n_postings, df, postings [n_postings, 2] and, for an
+    embedded index, key_count, key_image, key_sig (None otherwise)."""
+    L = load_library()
+    e, k, n = C.c_int(), C.c_int(), C.c_int()
+    t, p = C.c_int64(), C.c_int64()
+    ptr = [C.c_void_p() for _ in range(5)]
+    rc = L.hesaff_read_index_file(os.fsencode(path), C.byref(e), C.byref(k), C.byref(n), C.byref(t), C.byref(p), *[C.byref(q) for q in ptr])
+    if rc != 0:
+        raise HesaffError(rc, "hesaff_read_index_file(%s): not a readable, whole index file" % path)
+    try:
+        def take(q, count, dtype):
+            return np.frombuffer(C.string_at(q.value, count * np.dtype(dtype).itemsize), dtype=dtype).copy() if count else np.zeros(0, dtype)
+        out = dict(embedded=bool(e.value), k=k.value, n_images=n.value, n_keys=t.value, n_postings=p.value, df=take(ptr[0], k.value, np.uint32),
+                   postings=take(ptr[1], 2 * p.value, np.uint32).reshape(-1, 2), key_count=None, key_image=None, key_sig=None)
+        if e.value:
+            out.update(key_count=take(ptr[2], k.value, np.uint32), key_image=take(ptr[3], t.value, np.uint32), key_sig=take(ptr[4], t.value, np.uint64))
+    finally:
+        for q in ptr:
+            L.hesaff_free(q)
+    return out
 
 
 def write_signatures(path, sigs):
@@ -1474,6 +1530,56 @@ class HesaffContext:
         offsets = np.zeros(k + 1, np.uint32); images = np.zeros(t, np.uint32); sigs = np.zeros(t, np.uint64)
         self._check(self.L.hesaff_index_get_embedded(self.h, C.byref(flag), offsets.ctypes.data, images.ctypes.data if t else None, sigs.ctypes.data if t else None))
         return offsets, images, sigs
+
+    # ---- the growing, durable index (hesaff_index_add, hesaff_index_save, hesaff_index_load) ----
+    def add_to_index(self, images, signatures=None):
+        """hesaff_index_add: appends the images (as build_index takes them) to the context's index; they take the numbers N .. N + m - 1.
+        signatures: per image a uint64 array [n] - hesaff_index_add_embedded, on an index built with signatures."""
+        arrays = [_index_words(w) for w in images]
+        stride = _index_stride(arrays)
+        counts = np.array([len(a) for a in arrays], np.int32)
+        flat = np.ascontiguousarray(np.concatenate(arrays) if arrays else np.zeros((0,), np.int32))
+        if signatures is not None:
+            if len(signatures) != len(arrays):
+                raise ValueError("one signature array per image")
+            sg = [_signature_array(g, len(a)) for g, a in zip(signatures, arrays)]
+            sflat = np.ascontiguousarray(np.concatenate(sg) if sg else np.zeros(0, np.uint64))
+            self._check(self.L.hesaff_index_add_embedded(self.h, len(arrays), counts.ctypes.data, flat.ctypes.data if flat.size else None, stride,
+                                                         sflat.ctypes.data if sflat.size else None))
+            return
+        self._check(self.L.hesaff_index_add(self.h, len(arrays), counts.ctypes.data, flat.ctypes.data if flat.size else None, stride))
+
+    def add_to_index_device(self, ptr, counts, word_stride, sigs_ptr=None):
+        """hesaff_index_add_device: the words of the new images one after the other in device memory (a raw pointer), counts the keys per
+        image (host); with sigs_ptr hesaff_index_add_embedded_device."""
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        if sigs_ptr is not None:
+            self._check(self.L.hesaff_index_add_embedded_device(self.h, len(counts), counts.ctypes.data, C.c_void_p(ptr), int(word_stride), C.c_void_p(sigs_ptr)))
+            return
+        self._check(self.L.hesaff_index_add_device(self.h, len(counts), counts.ctypes.data, C.c_void_p(ptr), int(word_stride)))
+
+    def index_postings(self):
+        """hesaff_index_get_postings: (offsets uint32 [K + 1], images uint32 [n_postings], tf uint32 [n_postings]): word w's postings are
+        entries offsets[w] .. offsets[w + 1] - 1, in no particular order"""
+        n, k, t, p = self._need_index()
+        offsets = np.zeros(k + 1, np.uint32); images = np.zeros(p, np.uint32); tf = np.zeros(p, np.uint32)
+        self._check(self.L.hesaff_index_get_postings(self.h, offsets.ctypes.data, images.ctypes.data if p else None, tf.ctypes.data if p else None))
+        return offsets, images, tf
+
+    def save_index(self, path):
+        """hesaff_index_save: the context's index to an index file ("HESAFFI1")"""
+        self._check(self.L.hesaff_index_save(self.h, os.fsencode(path)))
+
+    def load_index(self, path):
+        """hesaff_index_load: replaces the context's index by an index file's; a file that is refused leaves the index as it was"""
+        self._check(self.L.hesaff_index_load(self.h, os.fsencode(path)))
+
+    @property
+    def index_growth_ms(self):
+        """HIP-event times (insert, tables, merge, scatter) of the last add and (load) of the last load's device pass (profiling >= 1), in ms"""
+        v = [C.c_float() for _ in range(5)]
+        self._check(self.L.hesaff_get_index_growth_ms(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     def build_index_device(self, ptr, counts, word_stride, vocabulary_size):
         """hesaff_index_build_device: the words of all images one after the other in device memory (a raw pointer; key j's word is the

@@ -344,6 +344,36 @@ struct AffineHessianDetector {
       for (int i = 0; i < count; i++) out[(size_t)i] = {images[(size_t)i], scores[(size_t)i]};
       return out;
    }
+   // Appends images to the detector's index (hesaff_index_add): counts[j] words of new image j, laid out as buildIndex's; the new
+   // images take the numbers behind the index's.  The index that results is the one buildIndex would make of all images together.
+   void addToIndex(const std::vector<int32_t> &counts, const int32_t *words, int wordStride)
+   {
+      const int rc = hesaff_index_add(ctx_, (int)counts.size(), counts.data(), words, wordStride);
+      if (rc == HESAFF_ERR_ARG)
+         throw std::invalid_argument("an add needs a plain index, at least one image, at most 2^20 images and 2^28 words with those of the index, every word inside its vocabulary");
+      if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+   }
+   // ... to an index built with signatures (hesaff_index_add_embedded)
+   void addToIndex(const std::vector<int32_t> &counts, const int32_t *words, int wordStride, const uint64_t *signatures)
+   {
+      const int rc = hesaff_index_add_embedded(ctx_, (int)counts.size(), counts.data(), words, wordStride, signatures);
+      if (rc == HESAFF_ERR_ARG)
+         throw std::invalid_argument("an embedded add needs an index built with signatures, at least one image, at most 2^20 images and 2^28 words with those of the index");
+      if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+   }
+   // The index to and from an index file (hesaff_index_save, hesaff_index_load: "HESAFFI1"); a file that is refused leaves the index as it was
+   void saveIndex(const char *path)
+   {
+      const int rc = hesaff_index_save(ctx_, path);
+      if (rc == HESAFF_ERR_ARG) throw std::invalid_argument("saveIndex needs an index and a path");
+      if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+   }
+   void loadIndex(const char *path)
+   {
+      const int rc = hesaff_index_load(ctx_, path);
+      if (rc == HESAFF_ERR_ARG) throw std::invalid_argument(path ? hesaff_last_error(ctx_) : "loadIndex needs a path");
+      if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+   }
    void clearIndex()
    {
       if (hesaff_index_clear(ctx_) != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));

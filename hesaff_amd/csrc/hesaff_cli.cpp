@@ -79,6 +79,16 @@
 //       beside every words file (".sigs" in the place of the final ".words": what a context with an embedding writes) is read as well,
 //       and a word match counts only where the two 64-bit signatures differ in at most T bits (hesaff_index_query_embedded); a
 //       signatures file that is missing, or whose count differs from its words file's, ends the run with a message that names it.
+//   hesaff --search <list of .hesaff.words files> --save-index <index file> [--device D] [--hamming T]
+//       builds the same index and, instead of asking a query, writes it to <index file> (hesaff_index_save: "HESAFFI1") and the list's
+//       paths, one per line, to <index file>.list.  With --hamming (any T) the signatures files are read and the index is an embedded one.
+//   hesaff --index <index file> --query <.hesaff.words file> [--top M] [--device D] [--hamming T] [--verify ...]
+//       as --search --query, but the index is loaded (hesaff_index_load), not built: no words file but the query's is read.  The paths
+//       printed, and the candidates' rows for --verify, are those of <index file>.list.  --hamming needs an embedded index.
+//   hesaff --index <index file> --add <list of .hesaff.words files> [--device D]
+//       loads the index, adds the listed files behind its images (hesaff_index_add; with their signatures files where the index is an
+//       embedded one) and rewrites <index file> and <index file>.list.  Both are written under temporary names and renamed when whole:
+//       a run that fails leaves the pair it found.
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -459,20 +469,27 @@ std::string sigs_name_for(const std::string &words)
    return n >= 6 && words.compare(n - 6, 6, ".words") == 0 ? words.substr(0, n - 6) + ".sigs" : words + ".sigs";
 }
 
-int run_search_mode(const char *list_path, const char *query_path, int top, int device, bool verify, float tolerance, int max_pairs, int hamming)
+// the lines of a list file: trailing blanks cut, empty lines and lines that begin with # skipped
+bool read_list(const char *list_path, std::vector<std::string> &names)
 {
    std::ifstream lf(list_path);
-   if (!lf) { fprintf(stderr, "hesaff: cannot read list '%s'\n", list_path); return 1; }
-   std::vector<std::string> names;
+   if (!lf) { fprintf(stderr, "hesaff: cannot read list '%s'\n", list_path); return false; }
    for (std::string line; std::getline(lf, line);) {
       while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
       if (!line.empty() && line[0] != '#') names.push_back(line);
    }
-   if (names.empty()) { fprintf(stderr, "hesaff: list '%s' names no words file\n", list_path); return 1; }
-   std::vector<int32_t> counts, words;
+   return true;
+}
+
+// the word columns (and with_sigs the signatures) of words files, one file after the other; k: the vocabulary size they all state
+// (0: the first file's)
+struct WordsReader {
+   std::vector<int32_t> words;
    std::vector<uint64_t> sigs;
    int k = 0;
-   auto read_sigs = [&](const char *words_path, int count) {
+   bool with_sigs = false;
+   bool read_sigs(const char *words_path, int count)
+   {
       const std::string path = sigs_name_for(words_path);
       uint64_t *g = nullptr;
       int n = 0;
@@ -488,8 +505,9 @@ int run_search_mode(const char *list_path, const char *query_path, int top, int 
       sigs.insert(sigs.end(), g, g + n);
       hesaff_free(g);
       return true;
-   };
-   auto read = [&](const char *path, int &count) {
+   }
+   bool read(const char *path, int &count)
+   {
       int32_t *w = nullptr;
       int vs = 0;
       if (hesaff_read_words(path, &w, &count, &vs) != HESAFF_OK) { fprintf(stderr, "hesaff: cannot read '%s' (a .hesaff.words file expected)\n", path); return false; }
@@ -497,34 +515,39 @@ int run_search_mode(const char *list_path, const char *query_path, int top, int 
       hesaff_free(w);
       if (k == 0) k = vs;
       if (vs != k || vs < 1) { fprintf(stderr, "hesaff: '%s' states vocabulary size %d, the files before it %d\n", path, vs, k); return false; }
-      return hamming < 0 || read_sigs(path, count);
-   };
-   for (const std::string &name : names) {
-      int count = 0;
-      if (!read(name.c_str(), count)) return 1;
-      counts.push_back(count);
+      return !with_sigs || read_sigs(path, count);
    }
-   const size_t indexed = words.size();
-   int n_query = 0;
-   if (!read(query_path, n_query)) return 1;
+   bool read_all(const std::vector<std::string> &names, std::vector<int32_t> &counts)
+   {
+      for (const std::string &name : names) {
+         int count = 0;
+         if (!read(name.c_str(), count)) return false;
+         counts.push_back(count);
+      }
+      return true;
+   }
+};
+
+hesaff_ctx *search_context(int device)
+{
    hesaff_params par;
    hesaff_default_params(&par);
    par.max_batch = 1;
    hesaff_ctx *ctx = nullptr;
-   if (hesaff_create(&ctx, &par, device) != HESAFF_OK) { fprintf(stderr, "hesaff: device %d: %s\n", device, hesaff_last_error(nullptr)); return 1; }
-   struct Destroy { hesaff_ctx *c; ~Destroy() { hesaff_destroy(c); } } destroy{ctx};
-   const int built = hamming < 0 ? hesaff_index_build(ctx, (int)counts.size(), counts.data(), words.data(), 1, k)
-                                 : hesaff_index_build_embedded(ctx, (int)counts.size(), counts.data(), words.data(), 1, sigs.data(), k);
-   if (built != HESAFF_OK) {
-      fprintf(stderr, "hesaff: the index was not built: %s\n", hesaff_last_error(ctx));
-      return 1;
-   }
+   if (hesaff_create(&ctx, &par, device) != HESAFF_OK) { fprintf(stderr, "hesaff: device %d: %s\n", device, hesaff_last_error(nullptr)); return nullptr; }
+   return ctx;
+}
+struct DestroyContext { hesaff_ctx *c; ~DestroyContext() { hesaff_destroy(c); } };
+
+// the query over the context's index, whose images are the files `names`; the ranked list (with verify: the verified list) on stdout
+int answer_query(hesaff_ctx *ctx, const std::vector<std::string> &names, int k, const char *query_path, const int32_t *qwords, int n_query, const uint64_t *qsigs,
+                 int top, bool verify, float tolerance, int max_pairs, int hamming)
+{
    std::vector<int32_t> images((size_t)top);
    std::vector<double> scores((size_t)top);
    int count = 0;
-   const int asked = hamming < 0 ? hesaff_index_query(ctx, n_query, words.data() + indexed, 1, top, images.data(), scores.data(), &count)
-                                 : hesaff_index_query_embedded(ctx, n_query, words.data() + indexed, 1, sigs.data() + indexed, hamming, top, images.data(),
-                                                               scores.data(), &count);
+   const int asked = hamming < 0 ? hesaff_index_query(ctx, n_query, qwords, 1, top, images.data(), scores.data(), &count)
+                                 : hesaff_index_query_embedded(ctx, n_query, qwords, 1, qsigs, hamming, top, images.data(), scores.data(), &count);
    if (asked != HESAFF_OK) {
       fprintf(stderr, "hesaff: the query failed: %s\n", hesaff_last_error(ctx));
       return 1;
@@ -562,6 +585,96 @@ int run_search_mode(const char *list_path, const char *query_path, int top, int 
    return 0;
 }
 
+// the pair of an index: <index> (hesaff_index_save) and <index>.list, the paths of its images one per line.  Both are written under
+// temporary names and renamed when both are whole, so that a run that fails leaves the pair it found.
+int write_index_pair(hesaff_ctx *ctx, const char *index_path, const std::vector<std::string> &names)
+{
+   const std::string list = std::string(index_path) + ".list", new_index = std::string(index_path) + ".new", new_list = list + ".new";
+   bool ok = hesaff_index_save(ctx, new_index.c_str()) == HESAFF_OK;
+   if (!ok) fprintf(stderr, "hesaff: cannot write '%s': %s\n", index_path, hesaff_last_error(ctx));
+   if (ok) {
+      std::ofstream lf(new_list.c_str(), std::ios::trunc);
+      for (const std::string &name : names) lf << name << '\n';
+      lf.close();
+      ok = !lf.fail();
+      if (!ok) fprintf(stderr, "hesaff: cannot write '%s'\n", list.c_str());
+   }
+   if (ok) {
+      ok = rename(new_index.c_str(), index_path) == 0 && rename(new_list.c_str(), list.c_str()) == 0;
+      if (!ok) fprintf(stderr, "hesaff: cannot rename the new index to '%s'\n", index_path);
+   }
+   if (!ok) { remove(new_index.c_str()); remove(new_list.c_str()); }
+   return ok ? 0 : 1;
+}
+
+// save_path == nullptr: hesaff --search <list> --query <file>, the index built for this one query.  Otherwise hesaff --search <list>
+// --save-index <index>: the index is built (an embedded one with --hamming) and written with its list; no query is asked.
+int run_search_mode(const char *list_path, const char *query_path, int top, int device, bool verify, float tolerance, int max_pairs, int hamming,
+                    const char *save_path = nullptr)
+{
+   std::vector<std::string> names;
+   if (!read_list(list_path, names)) return 1;
+   if (names.empty()) { fprintf(stderr, "hesaff: list '%s' names no words file\n", list_path); return 1; }
+   std::vector<int32_t> counts;
+   WordsReader in;
+   in.with_sigs = hamming >= 0;
+   if (!in.read_all(names, counts)) return 1;
+   const size_t indexed = in.words.size();
+   int n_query = 0;
+   if (query_path && !in.read(query_path, n_query)) return 1;
+   hesaff_ctx *ctx = search_context(device);
+   if (!ctx) return 1;
+   DestroyContext destroy{ctx};
+   const int built = hamming < 0 ? hesaff_index_build(ctx, (int)counts.size(), counts.data(), in.words.data(), 1, in.k)
+                                 : hesaff_index_build_embedded(ctx, (int)counts.size(), counts.data(), in.words.data(), 1, in.sigs.data(), in.k);
+   if (built != HESAFF_OK) {
+      fprintf(stderr, "hesaff: the index was not built: %s\n", hesaff_last_error(ctx));
+      return 1;
+   }
+   if (save_path) return write_index_pair(ctx, save_path, names);
+   return answer_query(ctx, names, in.k, query_path, in.words.data() + indexed, n_query, in.sigs.data() + indexed, top, verify, tolerance, max_pairs, hamming);
+}
+
+// hesaff --index <index> --query <file>: the index is loaded (hesaff_index_load), not built; the result paths, and the candidates'
+// rows for --verify, are those of <index>.list.  hesaff --index <index> --add <list>: the listed words files (and their signatures
+// files where the index is an embedded one) are added behind the index's images (hesaff_index_add) and the pair is rewritten.
+int run_index_mode(const char *index_path, const char *query_path, const char *add_path, int top, int device, bool verify, float tolerance, int max_pairs, int hamming)
+{
+   std::vector<std::string> names, more;
+   const std::string list = std::string(index_path) + ".list";
+   if (!read_list(list.c_str(), names)) return 1;
+   if (add_path && !read_list(add_path, more)) return 1;
+   if (add_path && more.empty()) { fprintf(stderr, "hesaff: list '%s' names no words file\n", add_path); return 1; }
+   hesaff_ctx *ctx = search_context(device);
+   if (!ctx) return 1;
+   DestroyContext destroy{ctx};
+   if (hesaff_index_load(ctx, index_path) != HESAFF_OK) { fprintf(stderr, "hesaff: the index was not loaded: %s\n", hesaff_last_error(ctx)); return 1; }
+   int n_images = 0, k = 0, embedded = 0;
+   hesaff_index_get_info(ctx, &n_images, &k, nullptr, nullptr);
+   hesaff_index_get_embedded(ctx, &embedded, nullptr, nullptr, nullptr);
+   if ((size_t)n_images != names.size()) { fprintf(stderr, "hesaff: '%s' holds %d images, '%s' names %zu\n", index_path, n_images, list.c_str(), names.size()); return 1; }
+   WordsReader in;
+   in.k = k;
+   if (add_path) {
+      std::vector<int32_t> counts;
+      in.with_sigs = embedded != 0;
+      if (!in.read_all(more, counts)) return 1;
+      const int added = embedded ? hesaff_index_add_embedded(ctx, (int)counts.size(), counts.data(), in.words.data(), 1, in.sigs.data())
+                                 : hesaff_index_add(ctx, (int)counts.size(), counts.data(), in.words.data(), 1);
+      if (added != HESAFF_OK) {
+         fprintf(stderr, "hesaff: the images were not added (an index holds at most 2^20 images and 2^28 keys): %s\n", hesaff_last_error(ctx));
+         return 1;
+      }
+      names.insert(names.end(), more.begin(), more.end());
+      return write_index_pair(ctx, index_path, names);
+   }
+   if (hamming >= 0 && !embedded) { fprintf(stderr, "hesaff: '%s' holds no signatures: --hamming needs an index saved with --hamming\n", index_path); return 1; }
+   in.with_sigs = hamming >= 0;
+   int n_query = 0;
+   if (!in.read(query_path, n_query)) return 1;
+   return answer_query(ctx, names, k, query_path, in.words.data(), n_query, in.sigs.data(), top, verify, tolerance, max_pairs, hamming);
+}
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -573,20 +686,24 @@ int main(int argc, char **argv)
    }
    // batch mode: "--batch <list>" and the other options in any order (the reference has no options: a first argument that does
    // not start with "--" is an image, as in hesaff.cpp:133-137)
-   bool search = false;
+   bool search = false, from_index = false;
    for (int i = 1; i < argc; i++) search = search || strcmp(argv[i], "--search") == 0;
-   if (search) {
-      const char *list = nullptr, *query = nullptr;
+   for (int i = 1; i < argc; i++) from_index = from_index || strcmp(argv[i], "--index") == 0;
+   if (search || from_index) {
+      const char *list = nullptr, *query = nullptr, *save = nullptr, *index = nullptr, *add = nullptr;
       long top = 10, device = 0, pairs = 1, hamming = -1;
       float tolerance = 8.0f;
-      bool bad = false, verify = false, verify_options = false;
+      bool bad = false, verify = false, verify_options = false, query_options = false;
       for (int i = 1; i < argc && !bad; i += 2) {
          if (strcmp(argv[i], "--verify") == 0 && !verify) { verify = true; i -= 1; continue; }   // (the one option without a value)
          if (i + 1 >= argc) { bad = true; break; }
          char *end = nullptr;
          if (strcmp(argv[i], "--search") == 0 && !list) list = argv[i + 1];
          else if (strcmp(argv[i], "--query") == 0 && !query) query = argv[i + 1];
-         else if (strcmp(argv[i], "--top") == 0) { top = strtol(argv[i + 1], &end, 10); bad = end == argv[i + 1] || *end || top < 1 || top > 1024; }
+         else if (strcmp(argv[i], "--save-index") == 0 && !save) save = argv[i + 1];
+         else if (strcmp(argv[i], "--index") == 0 && !index) index = argv[i + 1];
+         else if (strcmp(argv[i], "--add") == 0 && !add) add = argv[i + 1];
+         else if (strcmp(argv[i], "--top") == 0) { top = strtol(argv[i + 1], &end, 10); bad = end == argv[i + 1] || *end || top < 1 || top > 1024; query_options = true; }
          else if (strcmp(argv[i], "--device") == 0) { device = strtol(argv[i + 1], &end, 10); bad = end == argv[i + 1] || *end || device < 0 || device > 4095; }
          else if (strcmp(argv[i], "--hamming") == 0) { hamming = strtol(argv[i + 1], &end, 10); bad = end == argv[i + 1] || *end || hamming < 0 || hamming > HESAFF_EMBED_BITS; }
          else if (strcmp(argv[i], "--tolerance") == 0) {
@@ -597,12 +714,24 @@ int main(int argc, char **argv)
          else if (strcmp(argv[i], "--pairs") == 0) { pairs = strtol(argv[i + 1], &end, 10); bad = end == argv[i + 1] || *end || pairs < 1 || pairs > 16; verify_options = true; }
          else bad = true;
       }
-      if (bad || !list || !query || (verify_options && !verify)) {
-         fprintf(stderr, "hesaff: usage: hesaff --search <list of .hesaff.words files> --query <.hesaff.words file> [--top 1..1024] [--device D] [--hamming 0..64] "
-                         "[--verify [--tolerance PX] [--pairs 1..16]]\n");
+      bad = bad || (verify_options && !verify);
+      if (search) {
+         // one of --query and --save-index; --save-index asks no query, so it takes none of the query's options
+         bad = bad || !list || index || add || (query != nullptr) == (save != nullptr) || (save && (verify || query_options));
+         if (bad) {
+            fprintf(stderr, "hesaff: usage: hesaff --search <list of .hesaff.words files> --query <.hesaff.words file> [--top 1..1024] [--device D] [--hamming 0..64] "
+                            "[--verify [--tolerance PX] [--pairs 1..16]]   or   hesaff --search <list> --save-index <index file> [--device D] [--hamming 0..64]\n");
+            return 1;
+         }
+         return run_search_mode(list, query, (int)top, (int)device, verify, tolerance, (int)pairs, (int)hamming, save);
+      }
+      bad = bad || !index || save || (query != nullptr) == (add != nullptr) || (add && (verify || query_options || hamming >= 0));
+      if (bad) {
+         fprintf(stderr, "hesaff: usage: hesaff --index <index file> --query <.hesaff.words file> [--top 1..1024] [--device D] [--hamming 0..64] "
+                         "[--verify [--tolerance PX] [--pairs 1..16]]   or   hesaff --index <index file> --add <list of .hesaff.words files> [--device D]\n");
          return 1;
       }
-      return run_search_mode(list, query, (int)top, (int)device, verify, tolerance, (int)pairs, (int)hamming);
+      return run_index_mode(index, query, add, (int)top, (int)device, verify, tolerance, (int)pairs, (int)hamming);
    }
    bool batch = false;
    for (int i = 1; i < argc; i++) batch = batch || strcmp(argv[i], "--batch") == 0;

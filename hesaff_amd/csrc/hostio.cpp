@@ -28,6 +28,7 @@
 #include "../../include/hesaff_amd.h"
 #include "export_fmt.h"
 #include "cells_plan.h"   // cells_first_ok: the rule a cells file is read and written by
+#include "index_plan.h"   // the layout and the head of the index file
 #include "embed_plan.h"   // the generator of the default projection and the heads of the embedding and signatures files
 
 namespace {
@@ -1507,6 +1508,84 @@ int hesaff_signatures_is_complete(const char *path)
    if (size >= (off_t)sizeof head && pread(fd, head, sizeof head, 0) == (ssize_t)sizeof head) cnt = hesaff_plan::sigs_file_count(head, (uint64_t)size);
    close(fd);
    return (int)cnt;
+}
+
+// ---- the index file (hesaff_index_save / hesaff_index_load): layout and head rules are index_plan.h's ----
+
+// what the head cannot show: sum(df) == n_postings with every df <= n_images, and for an embedded index sum(key_count) == n_keys
+static bool index_file_sums_ok(const hesaff_plan::IndexFileHead &h, const uint32_t *df, const uint32_t *key_count)
+{
+   uint64_t postings = 0, keys = 0;
+   for (uint32_t w = 0; w < h.k; w++) {
+      if (df[w] > h.n_images) return false;
+      postings += df[w];
+      if (key_count) keys += key_count[w];
+   }
+   return postings == h.n_postings && (!key_count || keys == h.n_keys);
+}
+
+int hesaff_write_index_file(const char *path, int embedded, int vocabulary_size, int n_images, int64_t n_keys, int64_t n_postings, const uint32_t *df,
+                            const uint32_t *postings, const uint32_t *key_count, const uint32_t *key_image, const uint64_t *key_sig)
+{
+   using namespace hesaff_plan;
+   if (!path || !df || (embedded != 0 && embedded != 1) || !index_counts_ok(n_images, vocabulary_size)) return HESAFF_ERR_ARG;
+   if (n_keys < 0 || n_keys > HS_INDEX_MAX_KEYS || n_postings < 0 || n_postings > n_keys || (n_postings > 0 && !postings)) return HESAFF_ERR_ARG;
+   if (embedded ? (!key_count || (n_keys > 0 && (!key_image || !key_sig))) : (key_count || key_image || key_sig)) return HESAFF_ERR_ARG;
+   IndexFileHead h;
+   h.flags = embedded ? HS_INDEX_FILE_EMBEDDED : 0u; h.k = (uint32_t)vocabulary_size; h.n_images = (uint32_t)n_images;
+   h.n_keys = (uint64_t)n_keys; h.n_postings = (uint64_t)n_postings;
+   if (!index_file_sums_ok(h, df, key_count)) return HESAFF_ERR_ARG;
+   HOSTIO_TRY
+   const IndexFileLayout l = index_file_layout(h);
+   // the head, df and its pad in one block; the lists go out from the caller's arrays
+   std::vector<char> front(l.postings, 0), mid;
+   index_file_head(front.data(), h);
+   for (uint32_t w = 0; w < h.k; w++) index_file_put32(front.data() + l.df + (size_t)w * 4, df[w]);
+   std::string part;
+   const int fd = open_part(path, part);
+   if (fd < 0) return HESAFF_ERR_IO;
+   bool ok = write_head_body(fd, front.data(), front.size(), (const char *)postings, (size_t)n_postings * 8);
+   if (ok && embedded) {
+      mid.assign(l.key_image - l.key_count, 0);
+      for (uint32_t w = 0; w < h.k; w++) index_file_put32(mid.data() + (size_t)w * 4, key_count[w]);
+      const char pad[8] = {0};
+      ok = write_all(fd, mid.data(), mid.size()) && write_all(fd, (const char *)key_image, (size_t)n_keys * 4) &&
+           write_all(fd, pad, l.key_sig - l.key_image - (size_t)n_keys * 4) && write_all(fd, (const char *)key_sig, (size_t)n_keys * 8);
+   }
+   return finish_part(fd, ok, part, path);
+   HOSTIO_CATCH
+}
+
+int hesaff_read_index_file(const char *path, int *embedded, int *vocabulary_size, int *n_images, int64_t *n_keys, int64_t *n_postings, uint32_t **df,
+                           uint32_t **postings, uint32_t **key_count, uint32_t **key_image, uint64_t **key_sig)
+{
+   using namespace hesaff_plan;
+   if (!path || !embedded || !vocabulary_size || !n_images || !n_keys || !n_postings || !df || !postings || !key_count || !key_image || !key_sig) return HESAFF_ERR_ARG;
+   *embedded = 0; *vocabulary_size = 0; *n_images = 0; *n_keys = 0; *n_postings = 0;
+   *df = nullptr; *postings = nullptr; *key_count = nullptr; *key_image = nullptr; *key_sig = nullptr;
+   const int fd = open(path, O_RDONLY | O_CLOEXEC);
+   if (fd < 0) return HESAFF_ERR_IO;
+   int rc = HESAFF_ERR_IO;
+   char *b[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // df, postings, key_count, key_image, key_sig
+   const off_t size = lseek(fd, 0, SEEK_END);
+   char head[HS_INDEX_FILE_HEAD];
+   IndexFileHead h;
+   if (size >= (off_t)sizeof head && pread(fd, head, sizeof head, 0) == (ssize_t)sizeof head && index_file_parse_head(head, (uint64_t)size, &h)) {
+      const IndexFileLayout l = index_file_layout(h);
+      const bool emb = (h.flags & HS_INDEX_FILE_EMBEDDED) != 0u;
+      rc = read_block(fd, l.df, (size_t)h.k * 4, &b[0]);
+      if (rc == HESAFF_OK && h.n_postings) rc = read_block(fd, l.postings, (size_t)h.n_postings * 8, &b[1]);
+      if (rc == HESAFF_OK && emb) rc = read_block(fd, l.key_count, (size_t)h.k * 4, &b[2]);
+      if (rc == HESAFF_OK && emb && h.n_keys) rc = read_block(fd, l.key_image, (size_t)h.n_keys * 4, &b[3]);
+      if (rc == HESAFF_OK && emb && h.n_keys) rc = read_block(fd, l.key_sig, (size_t)h.n_keys * 8, &b[4]);
+      if (rc == HESAFF_OK && !index_file_sums_ok(h, (const uint32_t *)b[0], (const uint32_t *)b[2])) rc = HESAFF_ERR_IO;
+   }
+   close(fd);
+   if (rc != HESAFF_OK) { for (char *q : b) free(q); return rc; }
+   *embedded = (h.flags & HS_INDEX_FILE_EMBEDDED) ? 1 : 0; *vocabulary_size = (int)h.k; *n_images = (int)h.n_images;
+   *n_keys = (int64_t)h.n_keys; *n_postings = (int64_t)h.n_postings;
+   *df = (uint32_t *)b[0]; *postings = (uint32_t *)b[1]; *key_count = (uint32_t *)b[2]; *key_image = (uint32_t *)b[3]; *key_sig = (uint64_t *)b[4];
+   return HESAFF_OK;
 }
 
 // One file per image of a batch (exportKeypoints once per image, hesaff.cpp:170-176), images

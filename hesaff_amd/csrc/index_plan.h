@@ -142,4 +142,90 @@ inline size_t index_working_set_bytes(int64_t n_images, int64_t k, int64_t total
    return a.bytes() + b.bytes() + index_lists_bytes(total_keys);
 }
 
+// ---- growing an index (hesaff_index_add): n_old images of keys_old keys take m more of keys_new keys (each count already inside
+// index_image_keys_ok); the sums are the build's bounds ----
+inline bool index_add_ok(int64_t n_old, int64_t m, int64_t keys_old, int64_t keys_new)
+{
+   if (n_old < 1 || n_old > HS_INDEX_MAX_IMAGES || m < 1 || m > HS_INDEX_MAX_IMAGES || n_old + m > HS_INDEX_MAX_IMAGES) return false;
+   return index_total_ok(keys_old) && index_total_ok(keys_new) && keys_old + keys_new <= HS_INDEX_MAX_KEYS;
+}
+// the bytes an add holds at its peak beside the caller's words and the old index: the new tables, the new lists (at most one
+// posting per key of either) and a scratch whose hash table is sized for the NEW keys alone (n_old = 2^20 - 1, m = 1, k = 2^20,
+// keys_old = 2^28 - 2^18, keys_new = 2^18: 2.05 GiB, of which the lists are 2 and the hash table 6 MiB)
+inline size_t index_add_working_set_bytes(int64_t n_old, int64_t m, int64_t k, int64_t keys_old, int64_t keys_new)
+{
+   StagePlan a, b;
+   index_arrays(a, n_old + m, k);
+   index_build_arrays(b, m, k, keys_new);
+   return a.bytes() + b.bytes() + index_lists_bytes(keys_old + keys_new);
+}
+
+// ---- the index file (hesaff_index_save / hesaff_index_load).  Little-endian, every array on a multiple of 8 bytes:
+//   char magic[8] = "HESAFFI1"; uint32 flags (bit 0: embedded), k, n_images, reserved = 0; uint64 n_keys, n_postings;
+//   uint32 df[k] (+ 4 bytes of zero where k is odd); { uint32 image, tf } postings[n_postings], word-major;
+//   embedded only: uint32 key_count[k] (+ pad); uint32 key_image[n_keys] (+ pad); uint64 key_sig[n_keys]
+// idf, both offset tables and norm2 are derived on load. ----
+constexpr size_t HS_INDEX_FILE_HEAD = 40;
+constexpr uint32_t HS_INDEX_FILE_EMBEDDED = 1u;
+struct IndexFileHead { uint32_t flags, k, n_images; uint64_t n_keys, n_postings; };
+inline size_t index_file_pad8(size_t bytes) { return (bytes + 7) & ~(size_t)7; }
+struct IndexFileLayout { size_t df, postings, key_count, key_image, key_sig, size; };   // byte offsets; the last three == size for a plain file
+inline IndexFileLayout index_file_layout(const IndexFileHead &h)
+{
+   IndexFileLayout l;
+   l.df = HS_INDEX_FILE_HEAD;
+   l.postings = l.df + index_file_pad8((size_t)h.k * 4);
+   size_t at = l.postings + (size_t)h.n_postings * 8;
+   l.key_count = l.key_image = l.key_sig = at;
+   if (h.flags & HS_INDEX_FILE_EMBEDDED) {
+      l.key_image = l.key_count + index_file_pad8((size_t)h.k * 4);
+      l.key_sig = l.key_image + index_file_pad8((size_t)h.n_keys * 4);
+      at = l.key_sig + (size_t)h.n_keys * 8;
+   }
+   l.size = at;
+   return l;
+}
+inline void index_file_put32(char *p, uint32_t v) { for (int i = 0; i < 4; i++) p[i] = (char)(v >> (8 * i)); }
+inline void index_file_put64(char *p, uint64_t v) { for (int i = 0; i < 8; i++) p[i] = (char)(v >> (8 * i)); }
+inline uint32_t index_file_get32(const char *p) { uint32_t v = 0; for (int i = 0; i < 4; i++) v |= (uint32_t)(unsigned char)p[i] << (8 * i); return v; }
+inline uint64_t index_file_get64(const char *p) { uint64_t v = 0; for (int i = 0; i < 8; i++) v |= (uint64_t)(unsigned char)p[i] << (8 * i); return v; }
+inline void index_file_head(char *out, const IndexFileHead &h)
+{
+   const char magic[8] = {'H', 'E', 'S', 'A', 'F', 'F', 'I', '1'};
+   for (int i = 0; i < 8; i++) out[i] = magic[i];
+   index_file_put32(out + 8, h.flags); index_file_put32(out + 12, h.k); index_file_put32(out + 16, h.n_images); index_file_put32(out + 20, 0u);
+   index_file_put64(out + 24, h.n_keys); index_file_put64(out + 32, h.n_postings);
+}
+// the head of a file of `size` bytes -> true and *h where it is the head of a whole index file: magic, known flags, reserved 0,
+// 1 <= k, n_images <= 2^20, n_postings <= n_keys <= 2^28, and the size the fields imply
+inline bool index_file_parse_head(const char *in, uint64_t size, IndexFileHead *h)
+{
+   const char magic[8] = {'H', 'E', 'S', 'A', 'F', 'F', 'I', '1'};
+   for (int i = 0; i < 8; i++) if (in[i] != magic[i]) return false;
+   h->flags = index_file_get32(in + 8); h->k = index_file_get32(in + 12); h->n_images = index_file_get32(in + 16);
+   h->n_keys = index_file_get64(in + 24); h->n_postings = index_file_get64(in + 32);
+   if ((h->flags & ~HS_INDEX_FILE_EMBEDDED) != 0u || index_file_get32(in + 20) != 0u) return false;
+   if (!index_counts_ok((int64_t)h->n_images, (int64_t)h->k)) return false;
+   if (h->n_keys > (uint64_t)HS_INDEX_MAX_KEYS || h->n_postings > h->n_keys) return false;
+   return index_file_layout(*h).size == size;
+}
+
+// ---- the rules the device pass of a load checks, one bit each in its flag word; the lowest set bit is the rule reported ----
+constexpr uint32_t HS_LOAD_IMAGE = 1u;        // a posting's image >= n_images
+constexpr uint32_t HS_LOAD_TF = 2u;           // a posting's tf outside 1 .. 2^18
+constexpr uint32_t HS_LOAD_IMAGE_SUM = 4u;    // an image's tf sum above 2^18
+constexpr uint32_t HS_LOAD_TOTAL = 8u;        // the tf of all postings != n_keys
+constexpr uint32_t HS_LOAD_KEY_COUNT = 16u;   // embedded: a word's key count != the tf of its postings
+constexpr uint32_t HS_LOAD_KEY_IMAGE = 32u;   // embedded: a key's image >= n_images
+inline const char *index_load_rule(uint32_t flags)
+{
+   if (flags & HS_LOAD_IMAGE) return "a posting's image is not below n_images";
+   if (flags & HS_LOAD_TF) return "a posting's tf is outside 1 .. 2^18";
+   if (flags & HS_LOAD_IMAGE_SUM) return "an image's tf sum is above 2^18";
+   if (flags & HS_LOAD_TOTAL) return "the tf of all postings is not n_keys";
+   if (flags & HS_LOAD_KEY_COUNT) return "a word's key count is not the tf of its postings";
+   if (flags & HS_LOAD_KEY_IMAGE) return "a key's image is not below n_images";
+   return "";
+}
+
 } // namespace hesaff_plan

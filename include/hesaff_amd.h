@@ -58,6 +58,7 @@ extern "C" {
  *    And for vocabulary cells (hesaff_set_vocabulary_cells and the eight symbols declared with it): symbols only, version 8.
  *    And for vocabulary probes (hesaff_set_vocabulary_probes / hesaff_get_vocabulary_probes / hesaff_stage_probe_cells): symbols only, version 8.
  *    And for Hamming embedding (hesaff_set_embedding and the twenty symbols declared with it): symbols only, version 8.
+ *    And for the growing, durable index (hesaff_index_add and the nine symbols declared with it): symbols only, version 8.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -826,6 +827,59 @@ int hesaff_read_embedding(const char *path, int8_t **P, int32_t **tau, int *k);
 int hesaff_write_signatures(const char *path, const uint64_t *sigs, int n);
 int hesaff_read_signatures(const char *path, uint64_t **sigs, int *count);
 int hesaff_signatures_is_complete(const char *path);
+
+/* The index as a durable, growing object (no counterpart in the reference).  Symbols only, version 8.
+ * hesaff_index_add(ctx, m, counts, words, word_stride): appends m images, 1 <= m, to the context's index of N images over K words;
+ * image j of the call has counts[j] words, 0 <= counts[j] <= 2^18, each in 0 .. K - 1, laid out as hesaff_index_build's.  The new
+ * images take the numbers N .. N + m - 1 in the order given, and the index that results IS the index hesaff_index_build would make
+ * of the old images followed by the new ones: df, idf = ilog2_q8(N + m, df), the offsets and norm2 are equal bit for bit - the idf
+ * of every word changes with N, and with it the norm2 of every old image, which is summed again on the device - and every word's
+ * posting list is equal as a multiset (a build defines no order inside a list either).  Queries and hesaff_index_get_scores after
+ * an add are therefore bit for bit those of the rebuilt index; the last query's dot and score read zero after an add, as after a
+ * build.  hesaff_index_add_embedded takes a signature per key and extends an embedded index, whose key lists are likewise equal as
+ * multisets to the rebuilt index's, so embedded queries at every T are too.  The _device forms read words (and signatures) in
+ * device memory.  An add works on a new index and installs it when it is whole: its peak is the old index, the new one and a hash
+ * table sized for the NEW keys alone.
+ * HESAFF_ERR_ARG, with the context's index, vocabulary and embedding byte for byte what they were: no index is built; m < 1 or
+ * N + m > 2^20; a count outside 0 .. 2^18; the index's keys and the new ones together above 2^28; a word outside 0 .. K - 1 (found
+ * before anything is built); word_stride not 1 or 2; hesaff_index_add on an embedded index, or hesaff_index_add_embedded on a plain
+ * one; ctx or a required pointer NULL; a word pointer in device memory that is not 4-byte aligned, a signature pointer that is not
+ * 8-byte aligned.  HESAFF_ERR_NOMEM: the device cannot hold the new index beside the old; the old one stays.
+ * hesaff_index_get_postings: offsets[K + 1] and, per posting in word-major order, its image and its tf (images[n_postings],
+ * tf[n_postings]; each may be NULL; the order inside a list is unspecified) - the plain counterpart of hesaff_index_get_embedded.
+ * hesaff_index_save(ctx, path) writes the context's index, hesaff_index_load(ctx, path) replaces it by a file's.  The file, little-
+ * endian, every array on a multiple of 8 bytes (4 bytes of zero behind an array of an odd number of uint32):
+ *     char magic[8] = "HESAFFI1"; uint32 flags (bit 0: embedded), k, n_images, reserved = 0; uint64 n_keys, n_postings;
+ *     uint32 df[k]; { uint32 image, tf } postings[n_postings], word-major: df[0] of word 0, df[1] of word 1, ..;
+ *     an embedded index only: uint32 key_count[k]; uint32 key_image[n_keys]; uint64 key_sig[n_keys], word-major by key_count
+ * Only what cannot be derived is kept: idf, both offset tables and norm2 are made again on load.  The entries of a list are in the
+ * index's current order: two saves of equal indexes may differ as files and are equal as multisets.
+ * hesaff_write_index_file / hesaff_read_index_file are the writer and the reader over host arrays, pure host code; postings is
+ * uint32[n_postings][2] = (image, tf); the three key arrays are NULL for a plain index; the reader returns malloc'ed arrays
+ * (hesaff_free; NULL where an array has no entry or the file is plain).  The reader returns HESAFF_ERR_IO for anything that cannot
+ * be read or is not a whole file of the format: a short or long file, wrong magic, unknown flags, reserved not 0, k or n_images
+ * outside 1 .. 2^20, n_keys > 2^28, n_postings > n_keys, sum(df) != n_postings, a df > n_images, sum(key_count) != n_keys; the
+ * writer returns HESAFF_ERR_ARG for the same.  hesaff_index_load returns the reader's code for these, and then checks the lists
+ * on the device in the pass that sums norm2: every posting's image < n_images and 1 <= tf <= 2^18; every image's tf sum <= 2^18;
+ * the tf of all postings == n_keys; in an embedded file every word's key count == the tf of its postings and every key's
+ * image < n_images.  A file that fails one returns HESAFF_ERR_ARG, hesaff_last_error names the first rule violated in this order,
+ * and the context's index is untouched.  That an (image, word) pair occurs once per list is NOT checked: a file with a pair twice
+ * loads, and scores as if the image held the word's postings added up, but for norm2, which sums their squares one by one.
+ * A loaded index answers every query, embedded query and add bit for bit like the index that was saved.
+ * hesaff_get_index_growth_ms: HIP-event times at profiling level >= 1, 0 otherwise: of the last add its hash step, its tables (df,
+ * idf, offsets), the merge of the old postings and the scatter of the new ones; of the last load its device pass. */
+int hesaff_index_add(hesaff_ctx *ctx, int m_images, const int32_t *counts, const int32_t *words, int word_stride);
+int hesaff_index_add_device(hesaff_ctx *ctx, int m_images, const int32_t *counts, const void *d_words, int word_stride);
+int hesaff_index_add_embedded(hesaff_ctx *ctx, int m_images, const int32_t *counts, const int32_t *words, int word_stride, const uint64_t *sigs);
+int hesaff_index_add_embedded_device(hesaff_ctx *ctx, int m_images, const int32_t *counts, const void *d_words, int word_stride, const void *d_sigs);
+int hesaff_index_get_postings(const hesaff_ctx *ctx, uint32_t *offsets, uint32_t *images, uint32_t *tf);
+int hesaff_index_save(hesaff_ctx *ctx, const char *path);
+int hesaff_index_load(hesaff_ctx *ctx, const char *path);
+int hesaff_get_index_growth_ms(const hesaff_ctx *ctx, float *insert_ms, float *tables_ms, float *merge_ms, float *scatter_ms, float *load_ms);
+int hesaff_write_index_file(const char *path, int embedded, int vocabulary_size, int n_images, int64_t n_keys, int64_t n_postings, const uint32_t *df,
+                            const uint32_t *postings, const uint32_t *key_count, const uint32_t *key_image, const uint64_t *key_sig);
+int hesaff_read_index_file(const char *path, int *embedded, int *vocabulary_size, int *n_images, int64_t *n_keys, int64_t *n_postings, uint32_t **df,
+                           uint32_t **postings, uint32_t **key_count, uint32_t **key_image, uint64_t **key_sig);
 
 /* Spatial verification (no counterpart in the reference): the shortlist of a tf-idf query re-ranked by how many tentative
  * correspondences agree with the best single-correspondence affine hypothesis - the "fast spatial matching" of Philbin et al. 2007

@@ -146,8 +146,11 @@ const uint8_t kZigZag[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4
 
 inline uint8_t clamp8(int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
 
-// Two's-complement arithmetic that wraps: what libjpeg's INT32 does on every real target.  The IDCT of a legal stream
-// never leaves 32 bits; a damaged one can, and signed overflow would be undefined behaviour here.
+// Two's-complement arithmetic that wraps at 32 bits.  The IDCT of a legal stream never leaves 32 bits, so there the type does
+// not matter; a damaged stream (or 16-bit quantisers) can, and signed overflow would be undefined behaviour here.  libjpeg gives
+// no answer for such streams - its INT32 is a long, 64 bits on LP64 targets - so the wrap is this project's own definition of
+// them, shared with k_jpeg_idct and pinned by the wrapping reference of tests/jpeg_ref.py and a file with a 16-bit table
+// (tests/test_jpeg_constructed_host.py, tests/test_jpeg_constructed.py).
 struct W32 {
    uint32_t u;
    W32() = default;
@@ -466,6 +469,11 @@ int decode_jpeg(const std::vector<uint8_t> &f, uint8_t **data, int *width, int *
                c->pred = 0;
                memcpy(c->q, qt[c->tq], sizeof c->q);   // sequential: the table in force when the component's scan starts
                sc.push_back(c);
+            }
+            if (ns > 1) {   // an interleaved MCU holds at most 10 blocks (B.2.3; libjpeg: JERR_BAD_MCU_SIZE); a scan of one component is not bound
+               int mcu_blocks = 0;
+               for (Comp *c : sc) mcu_blocks += c->h * c->v;
+               if (mcu_blocks > 10) return HESAFF_ERR_IO;
             }
             BitReader br;
             br.p = &f[pos + len]; br.end = f.data() + n;

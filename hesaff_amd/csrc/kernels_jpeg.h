@@ -6,28 +6,22 @@
 // (jdsample.c "fancy" triangle filters) and the colour conversion (jdcolor.c).  On a host thread the three cost 60 % of
 // the decode time of a 4:2:0 photograph; here they run over all images of a chunk at once:
 //    k_jpeg_idct    one thread per 8 x 8 block of any component of any image (coefficients staged through LDS as whole cache
-//                   lines): dequantise, two 1-D passes in 32-bit integers (wrapping, like libjpeg's INT32), range limit, 8 rows of
+//                   lines): dequantise, two 1-D passes in 32-bit integers (wrapping, as jpeg_decode.cpp's W32 defines), range limit, 8 rows of
 //                   8 samples into the component plane
 //    k_jpeg_pixels  one thread per 4 output pixels: up-sample the components that are not at full resolution (edge
 //                   samples replicated), YCbCr -> RGB with jdcolor.c's fixed-point constants, bytes into the chunk's
 //                   input slot in the layout of a raw 1- or 3-channel image - the grey conversion (hesaff.cpp:138-148) and
 //                   everything after it then run exactly as for a PPM file.
 // Integer arithmetic only: the bytes equal hesaff_read_jpeg's (tests/test_gpu_parity.py), which equal libjpeg-turbo's
-// (tests/test_host_side.py).
+// (tests/test_host_side.py).  The edges of the domain - several images inside one wavefront, coefficients whose transform leaves
+// 32 bits or the 10-bit range-limit window, every sampling ratio and width, the Adobe RGB copy - are held by constructed
+// coefficients against a numpy statement of the whole stage: tests/test_jpeg_constructed.py with tests/jpeg_build.py and
+// tests/jpeg_ref.py, which tests/test_jpeg_constructed_host.py pins to hesaff_read_jpeg (and libjpeg-turbo) on the CPU first.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "device_common.h"
-
-struct JpegGeom {
-   int W, H, nc;
-   int bw[3], bh[3], cw[3], chgt[3], hx[3], vx[3], mode[3];
-   unsigned long long coef_off[3];    // bytes from the start of an image's blob
-   unsigned long long plane_off[3];   // bytes from the start of an image's planes
-   unsigned long long blob_bytes, plane_bytes;
-   unsigned int blocks[3], blocks_per_image;
-};
-enum { JPEG_UP_NONE = 0, JPEG_UP_H2V1 = 1, JPEG_UP_H2V2 = 2, JPEG_UP_H1V2 = 3, JPEG_UP_REPLICATE = 4 };
+#include "jpeg_plan.h"   // JpegGeom, JPEG_UP_*: the geometry and the layouts that are refused
 
 __device__ __forceinline__ int hs_jpeg_descale(int x, int n) { return (int)((unsigned)x + (1u << (n - 1))) >> n; }
 // range_limit[x & RANGE_MASK] of libjpeg: a 10-bit window around the level shift, clamped to 0..255

@@ -1666,28 +1666,7 @@ void export_text_write(hesaff_ctx *c, const KeyRec *keys, uint32_t n, char *d_te
 JpegGeom make_jpeg_geom(const hesaff_jpeg_layout &L)
 {
    JpegGeom g;
-   memset(&g, 0, sizeof g);
-   if (L.width < 1 || L.height < 1 || L.width > 65535 || L.height > 65535 || (L.channels != 1 && L.channels != 3))
-      throw HsError(HESAFF_ERR_ARG, "bad JPEG layout");
-   g.W = L.width; g.H = L.height; g.nc = L.channels;
-   unsigned long long coef = HESAFF_JPEG_BLOB_HEADER, plane = 0, blocks = 0;
-   for (int i = 0; i < g.nc; i++) {
-      const long long bw = L.bw[i], bh = L.bh[i], cw = L.cw[i], chgt = L.chgt[i], hx = L.hx[i], vx = L.vx[i];
-      if (bw < 1 || bh < 1 || bw > 8192 || bh > 8192 || cw < 1 || chgt < 1 || cw > bw * 8 || chgt > bh * 8 || hx < 1 || hx > 4 || vx < 1 || vx > 4 ||
-          cw * hx < L.width || chgt * vx < L.height || (g.nc == 1 && (hx != 1 || vx != 1)))
-         throw HsError(HESAFF_ERR_ARG, "bad JPEG layout");
-      g.bw[i] = (int)bw; g.bh[i] = (int)bh; g.cw[i] = (int)cw; g.chgt[i] = (int)chgt; g.hx[i] = (int)hx; g.vx[i] = (int)vx;
-      // jdsample.c's choice of method (jpeg_decode.cpp)
-      g.mode[i] = (hx == 1 && vx == 1) ? JPEG_UP_NONE : (hx == 2 && vx == 1 && cw > 2) ? JPEG_UP_H2V1 : (hx == 2 && vx == 2 && cw > 2) ? JPEG_UP_H2V2
-                  : (hx == 1 && vx == 2) ? JPEG_UP_H1V2 : JPEG_UP_REPLICATE;
-      g.blocks[i] = (unsigned int)(bw * bh);
-      g.coef_off[i] = coef; g.plane_off[i] = plane;
-      coef += (unsigned long long)(bw * bh) * 128;
-      plane += (unsigned long long)(bw * bh) * 64;
-      blocks += (unsigned long long)(bw * bh);
-   }
-   if (blocks > 0x7fffffffull) throw HsError(HESAFF_ERR_ARG, "bad JPEG layout");
-   g.blob_bytes = coef; g.plane_bytes = plane; g.blocks_per_image = (unsigned int)blocks;
+   if (!hesaff_plan::make_jpeg_geom(L, g)) throw HsError(HESAFF_ERR_ARG, "bad JPEG layout");   // jpeg_plan.h
    return g;
 }
 

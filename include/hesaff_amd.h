@@ -1029,7 +1029,9 @@ int hesaff_read_png(const char *path, uint8_t **data, int *width, int *height, i
 /* Huffman-coded 8-bit JPEG, sequential or progressive, grey or YCbCr: the integer algorithms of libjpeg at
  * cv::imread's settings (JDCT_ISLOW inverse DCT, "fancy" chroma up-sampling, JFIF colour conversion), pixel for pixel
  * the bytes libjpeg / libjpeg-turbo return for a complete file; channels = 1 for grey files, 3 (R,G,B order)
- * otherwise.  Arithmetic-coded, lossless, 12-bit and CMYK files: HESAFF_ERR_IO. */
+ * otherwise.  Arithmetic-coded, lossless, 12-bit and CMYK files: HESAFF_ERR_IO.  So is a file with an interleaved scan of more
+ * than 10 blocks per MCU (luma 3x3 or more beside two chroma blocks), which libjpeg refuses too (JERR_BAD_MCU_SIZE) - from this
+ * reader and from hesaff_read_jpeg_coefficients alike; scans of one component each are not bound by it. */
 int hesaff_read_jpeg(const char *path, uint8_t **data, int *width, int *height, int *channels);
 /* Windows bitmaps as OpenCV's BMP decoder delivers them at imread's default flag: 1 / 4 / 8 bits through the palette (uncompressed, RLE4, RLE8),
  * 16 bits (5-5-5, or 5-6-5 by bit fields; low bits left zero), 24 bits, 32 bits (fourth byte dropped), bottom-up or top-down, OS/2 core headers;

@@ -1115,7 +1115,10 @@ def test_device_jpeg_pixels_equal_the_host_reader(ctx, tmp_path):
     """The device half of the JPEG reader (kernels_jpeg.h: inverse DCT, fancy / replicating up-sampling, colour conversion, run by
     hesaff_process_files on the coefficients of every JPEG of its list) delivers the bytes of hesaff_read_jpeg - which
     tests/test_host_side.py pins to libjpeg-turbo's - for 4:4:4, 4:2:2, 4:2:0, 4:4:0 and grey files, odd sizes down to 1 x 1, restart
-    intervals, sequential and progressive, several images of one layout per call, the committed fixtures and the photographs."""
+    intervals, sequential and progressive, several images of one layout per call, the committed fixtures and the photographs.
+    These are the files an encoder writes.  The edges of the kernels' domain - many images inside one wavefront, transforms outside
+    32 bits or the range-limit window, every sampling ratio and width, Adobe RGB - are held by constructed coefficients against a
+    numpy reference in tests/test_jpeg_constructed.py (tests/jpeg_build.py, tests/jpeg_ref.py), without Pillow."""
     Image = pytest.importorskip("PIL.Image")
     import hesaff_amd
     rng = np.random.default_rng(3)

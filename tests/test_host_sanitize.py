@@ -216,6 +216,30 @@ def test_readers_refuse_damaged_files_without_memory_errors(driver, tmp_path):
     assert "read ok=" in out
 
 
+def test_constructed_jpeg_files_at_the_readers_edges(driver, tmp_path):
+    """Constructed files (tests/jpeg_build.py) that no encoder writes, through both readers: a chroma ratio of 3, a sub-sampled luma, a
+    16-bit quantisation table whose products leave 32 bits in the transform, Adobe RGB - and an interleaved scan of 11 blocks per MCU,
+    which is refused."""
+    import numpy as np
+    from tests import jpeg_build as JB
+    from tests.test_jpeg_constructed_host import _wrap_case
+    rng = np.random.default_rng(7)
+    paths = []
+
+    def add(name, W, H, samp, **kw):
+        L = JB.layout_for(W, H, samp)
+        data = JB.write_jpeg(W, H, samp, JB.legal_coefs(L, len(paths), rng), JB.legal_quants(L, rng), **kw)
+        p = str(tmp_path / name); open(p, "wb").write(data); paths.append(p)
+    add("ratio3.jpg", 19, 13, JB.SAMPLINGS["chroma_3x1"])
+    add("luma_sub.jpg", 19, 13, JB.SAMPLINGS["luma_2x1"])
+    L, coefs, quants = _wrap_case(rng)
+    p = str(tmp_path / "wrap16.jpg"); open(p, "wb").write(JB.write_jpeg(48, 48, [(1, 1)], coefs, quants, q16=True)); paths.append(p)
+    add("adobe_rgb.jpg", 19, 13, JB.SAMPLINGS["chroma_2x2"], adobe=0)
+    add("blocks11.jpg", 19, 13, JB.SAMPLINGS["chroma_3x3"])
+    out = _run(driver, ["read"] + paths)
+    assert "read ok=4 refused=1 coefficient blobs=4" in out, out
+
+
 def test_text_writer_on_arbitrary_bit_patterns(driver):
     for seed, n in [(1, 1), (2, 333), (3, 20000)]:
         out = _run(driver, ["format", str(seed), str(n)])

@@ -503,35 +503,7 @@ def test_jpeg_coefficients_for_the_device_pixel_stage(tmp_path):
             pass
 
 
-def _idct_islow_numpy(coef, quant):
-    """jidctint.c (JDCT_ISLOW) on an array of blocks [n, 8, 8] int16 with one quantisation table [8, 8]: int64 arithmetic (a legal
-    stream never leaves 32 bits), the same constants, shifts and range limit as idct_islow / k_jpeg_idct -> uint8 [n, 8, 8]."""
-    F = dict(f0298=2446, f0390=3196, f0541=4433, f0765=6270, f0899=7373, f1175=9633, f1501=12299, f1847=15137, f1961=16069, f2053=16819,
-             f2562=20995, f3072=25172)
-
-    def pass1d(d, shift):   # d: [..., 8] along the transformed axis (last)
-        z2, z3 = d[..., 2], d[..., 6]
-        z1 = (z2 + z3) * F["f0541"]
-        tmp2 = z1 + z3 * -F["f1847"]
-        tmp3 = z1 + z2 * F["f0765"]
-        tmp0 = (d[..., 0] + d[..., 4]) << 13
-        tmp1 = (d[..., 0] - d[..., 4]) << 13
-        tmp10, tmp13, tmp11, tmp12 = tmp0 + tmp3, tmp0 - tmp3, tmp1 + tmp2, tmp1 - tmp2
-        t0, t1, t2, t3 = d[..., 7], d[..., 5], d[..., 3], d[..., 1]
-        z1, z2, z3, z4 = t0 + t3, t1 + t2, t0 + t2, t1 + t3
-        z5 = (z3 + z4) * F["f1175"]
-        t0, t1, t2, t3 = t0 * F["f0298"], t1 * F["f2053"], t2 * F["f3072"], t3 * F["f1501"]
-        z1, z2, z3, z4 = z1 * -F["f0899"], z2 * -F["f2562"], z3 * -F["f1961"] + z5, z4 * -F["f0390"] + z5
-        t0, t1, t2, t3 = t0 + z1 + z3, t1 + z2 + z4, t2 + z2 + z3, t3 + z1 + z4
-        out = np.stack([tmp10 + t3, tmp11 + t2, tmp12 + t1, tmp13 + t0, tmp13 - t0, tmp12 - t1, tmp11 - t2, tmp10 - t3], -1)
-        return (out + (1 << (shift - 1))) >> shift
-    d = coef.astype(np.int64) * quant.astype(np.int64)[None]
-    ws = pass1d(np.swapaxes(d, 1, 2), 13 - 2)          # columns: transform along the row index
-    ws = np.swapaxes(ws, 1, 2)
-    o = pass1d(ws, 13 + 2 + 3)                          # rows
-    v = o & 1023
-    v = np.where(v >= 512, v - 1024, v) + 128
-    return np.clip(v, 0, 255).astype(np.uint8)
+from tests.jpeg_ref import _idct_islow_numpy   # noqa: E402  (jidctint.c in plain int64; the wrapping variant lives beside it)
 
 
 def test_jpeg_coefficient_blob_transforms_to_the_readers_pixels(tmp_path):

@@ -323,6 +323,15 @@ def load_library():
         L.hesaff_get_index_growth_ms.argtypes = [vp] + [C.POINTER(C.c_float)] * 5
         L.hesaff_write_index_file.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, i64, i64, vp, vp, vp, vp, vp]
         L.hesaff_read_index_file.argtypes = [C.c_char_p] + [C.POINTER(C.c_int)] * 3 + [C.POINTER(i64)] * 2 + [C.POINTER(vp)] * 5
+    if hasattr(L, "hesaff_index_query_batch"):   # (likewise)
+        L.hesaff_index_query_batch.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int)]
+        L.hesaff_index_query_batch_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int)]
+        L.hesaff_index_query_batch_embedded.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int)]
+        L.hesaff_index_query_batch_embedded_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int)]
+        L.hesaff_index_set_batch_budget.argtypes = [vp, C.c_size_t]
+        L.hesaff_index_get_batch_budget.argtypes = [vp, C.POINTER(C.c_size_t)]
+        L.hesaff_index_get_batch_chunks.argtypes = [vp, C.POINTER(C.c_int)]
+        L.hesaff_get_index_batch_ms.argtypes = [vp] + [C.POINTER(C.c_float)] * 3
     L.hesaff_stage_math_sift_general.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p]
     L.hesaff_stage_math_sift.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]
@@ -382,6 +391,8 @@ ABI_SYMBOLS = [
     "hesaff_write_signatures", "hesaff_read_signatures", "hesaff_signatures_is_complete",
     "hesaff_index_add", "hesaff_index_add_device", "hesaff_index_add_embedded", "hesaff_index_add_embedded_device", "hesaff_index_get_postings",
     "hesaff_index_save", "hesaff_index_load", "hesaff_get_index_growth_ms", "hesaff_write_index_file", "hesaff_read_index_file",
+    "hesaff_index_query_batch", "hesaff_index_query_batch_device", "hesaff_index_query_batch_embedded", "hesaff_index_query_batch_embedded_device",
+    "hesaff_index_set_batch_budget", "hesaff_index_get_batch_budget", "hesaff_index_get_batch_chunks", "hesaff_get_index_batch_ms",
 ]
 
 # hesaff_set_output_format's bits
@@ -1617,6 +1628,80 @@ class HesaffContext:
     def query_index_device(self, ptr, n, word_stride, top):
         """hesaff_index_query_device: the same on n words in device memory (a raw pointer)."""
         return self._query(lambda *a: self.L.hesaff_index_query_device(self.h, int(n), C.c_void_p(ptr), int(word_stride), *a), top)
+
+    # ---- batched index queries (hesaff_index_query_batch, include/hesaff_amd.h) ----
+    def _query_batch(self, call, n_queries, top):
+        top = int(top)
+        rows = max(min(top, 1024), 1)
+        images = np.zeros((max(n_queries, 1), rows), np.int32)
+        scores = np.zeros(images.shape, np.float64)
+        n = C.c_int(0)
+        self._check(call(top, images.ctypes.data, scores.ctypes.data, C.byref(n)))
+        return images[:n_queries, :n.value].copy(), scores[:n_queries, :n.value].copy()
+
+    def query_index_batch(self, queries, top, signatures=None, hamming=None):
+        """hesaff_index_query_batch: queries is a list with, per query, an int32 array of words [n] or [n, 2], all of one kind ->
+        (images int32 [Q, min(top, N)], scores float64 [Q, min(top, N)]); row q is what query_index returns for queries[q].  With
+        signatures (per query a uint64 array [n]) and hamming = T in 0 .. 64 - hesaff_index_query_batch_embedded."""
+        arrays = [_index_words(w) for w in queries]
+        stride = _index_stride(arrays)
+        if (signatures is None) != (hamming is None):
+            raise ValueError("signatures and hamming go together")
+        counts = np.array([len(a) for a in arrays], np.int32)
+        flat = np.ascontiguousarray(np.concatenate(arrays) if arrays else np.zeros((0,), np.int32))
+        if signatures is not None:
+            if len(signatures) != len(arrays):
+                raise ValueError("one signature array per query")
+            sg = [_signature_array(g, len(a)) for g, a in zip(signatures, arrays)]
+            sflat = np.ascontiguousarray(np.concatenate(sg) if sg else np.zeros(0, np.uint64))
+            return self._query_batch(lambda *a: self.L.hesaff_index_query_batch_embedded(self.h, len(arrays), counts.ctypes.data, flat.ctypes.data if flat.size else None,
+                                                                                         stride, sflat.ctypes.data if sflat.size else None, int(hamming), *a),
+                                     len(arrays), top)
+        return self._query_batch(lambda *a: self.L.hesaff_index_query_batch(self.h, len(arrays), counts.ctypes.data, flat.ctypes.data if flat.size else None, stride, *a),
+                                 len(arrays), top)
+
+    def query_index_batch_device(self, ptr, counts, word_stride, top, sigs_ptr=None, hamming=None):
+        """hesaff_index_query_batch_device: the words of all queries one after the other in device memory (a raw pointer), counts the
+        words per query (host); with sigs_ptr and hamming hesaff_index_query_batch_embedded_device."""
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        if counts.ndim != 1:
+            raise ValueError("counts is a 1-d array: the words per query")
+        if (sigs_ptr is None) != (hamming is None):
+            raise ValueError("sigs_ptr and hamming go together")
+        if sigs_ptr is not None:
+            return self._query_batch(lambda *a: self.L.hesaff_index_query_batch_embedded_device(self.h, len(counts), counts.ctypes.data, C.c_void_p(ptr), int(word_stride),
+                                                                                                C.c_void_p(sigs_ptr), int(hamming), *a), len(counts), top)
+        return self._query_batch(lambda *a: self.L.hesaff_index_query_batch_device(self.h, len(counts), counts.ctypes.data, C.c_void_p(ptr), int(word_stride), *a),
+                                 len(counts), top)
+
+    def set_index_batch_budget(self, nbytes):
+        """hesaff_index_set_batch_budget: the device scratch a chunk of a batch may hold, in bytes (0: the default); results do not
+        depend on it.  Releases what earlier batches allocated."""
+        nbytes = int(nbytes)
+        if nbytes < 0:
+            raise ValueError("a budget is a number of bytes, 0 for the default")
+        self._check(self.L.hesaff_index_set_batch_budget(self.h, C.c_size_t(nbytes)))
+
+    @property
+    def index_batch_budget(self):
+        """hesaff_index_get_batch_budget: the budget in force, in bytes"""
+        v = C.c_size_t(0)
+        self._check(self.L.hesaff_index_get_batch_budget(self.h, C.byref(v)))
+        return v.value
+
+    @property
+    def index_batch_chunks(self):
+        """hesaff_index_get_batch_chunks: the chunks the last batch ran in"""
+        v = C.c_int(0)
+        self._check(self.L.hesaff_index_get_batch_chunks(self.h, C.byref(v)))
+        return v.value
+
+    @property
+    def index_batch_ms(self):
+        """HIP-event times (group, score, select) summed over the chunks of the last batch (profiling >= 1), in ms"""
+        v = [C.c_float() for _ in range(3)]
+        self._check(self.L.hesaff_get_index_batch_ms(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     @property
     def index_info(self):

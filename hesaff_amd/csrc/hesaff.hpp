@@ -344,6 +344,33 @@ struct AffineHessianDetector {
       for (int i = 0; i < count; i++) out[(size_t)i] = {images[(size_t)i], scores[(size_t)i]};
       return out;
    }
+   // Many queries in one call (hesaff_index_query_batch): counts[q] words of query q, the words of all queries one after the other
+   // as buildIndex takes those of its images.  One ranked vector per query: what queryIndex returns for that query's words.
+   std::vector<std::vector<std::pair<int32_t, double>>> queryIndexBatch(const std::vector<int32_t> &counts, const int32_t *words, int wordStride, int top)
+   {
+      return queryBatch_(counts, top, [&](int32_t *images, double *scores, int *count) {
+         return hesaff_index_query_batch(ctx_, (int)counts.size(), counts.data(), words, wordStride, top, images, scores, count);
+      });
+   }
+   // ... with a signature per word and a Hamming threshold, 0..64 (hesaff_index_query_batch_embedded): per query the embedded queryIndex
+   std::vector<std::vector<std::pair<int32_t, double>>> queryIndexBatch(const std::vector<int32_t> &counts, const int32_t *words, int wordStride,
+                                                                        const uint64_t *signatures, int hamming, int top)
+   {
+      return queryBatch_(counts, top, [&](int32_t *images, double *scores, int *count) {
+         return hesaff_index_query_batch_embedded(ctx_, (int)counts.size(), counts.data(), words, wordStride, signatures, hamming, top, images, scores, count);
+      });
+   }
+   // The device scratch a chunk of a batch may hold, in bytes; 0: the default.  Results do not depend on it.
+   void setIndexBatchBudget(size_t bytes)
+   {
+      if (hesaff_index_set_batch_budget(ctx_, bytes) != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+   }
+   size_t indexBatchBudget() const
+   {
+      size_t bytes = 0;
+      hesaff_index_get_batch_budget(ctx_, &bytes);
+      return bytes;
+   }
    // Appends images to the detector's index (hesaff_index_add): counts[j] words of new image j, laid out as buildIndex's; the new
    // images take the numbers behind the index's.  The index that results is the one buildIndex would make of all images together.
    void addToIndex(const std::vector<int32_t> &counts, const int32_t *words, int wordStride)
@@ -579,6 +606,25 @@ struct AffineHessianDetector {
          if (affineShapeCallback_ && g.outcome >= 1)
             affineShapeCallback_->onAffineShapeFound(blur, g.x, g.y, g.s, g.pixelDistance, g.a11, g.a12, g.a21, g.a22, g.type, g.response, g.iters);
       }
+   }
+   // queryIndexBatch: the flat rows of a batch call as one ranked vector per query
+   template <class Call> std::vector<std::vector<std::pair<int32_t, double>>> queryBatch_(const std::vector<int32_t> &counts, int top, Call call)
+   {
+      const size_t row = (size_t)(top > 0 && top <= 1024 ? top : 1), nq = counts.empty() ? 1 : counts.size();
+      std::vector<int32_t> images(nq * row);
+      std::vector<double> scores(nq * row);
+      int count = 0;
+      const int rc = call(images.data(), scores.data(), &count);
+      if (rc == HESAFF_ERR_ARG)
+         throw std::invalid_argument("a batch needs an index (built with signatures for the embedded form), 1..2^16 queries of at most 2^18 words each inside its vocabulary, "
+                                     "2^28 in all, 0 <= hamming <= 64 and 1 <= top <= 1024");
+      if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+      std::vector<std::vector<std::pair<int32_t, double>>> out(counts.size());
+      for (size_t q = 0; q < counts.size(); q++) {
+         out[q].resize((size_t)count);
+         for (int i = 0; i < count; i++) out[q][(size_t)i] = {images[q * row + (size_t)i], scores[q * row + (size_t)i]};
+      }
+      return out;
    }
 
    hesaff_params p_;

@@ -85,6 +85,9 @@
 //   hesaff --index <index file> --query <.hesaff.words file> [--top M] [--device D] [--hamming T] [--verify ...]
 //       as --search --query, but the index is loaded (hesaff_index_load), not built: no words file but the query's is read.  The paths
 //       printed, and the candidates' rows for --verify, are those of <index file>.list.  --hamming needs an embedded index.
+//   hesaff --search <list> | --index <index file>  --queries <list of .hesaff.words files> [--top M] [--device D] [--hamming T] [--verify ...]
+//       in the place of --query: the listed files are ONE batch (hesaff_index_query_batch).  Per query, in list order, a line
+//       "# <query path>" and then exactly the lines --query prints for that file.  --query together with --queries is a usage error.
 //   hesaff --index <index file> --add <list of .hesaff.words files> [--device D]
 //       loads the index, adds the listed files behind its images (hesaff_index_add; with their signatures files where the index is an
 //       embedded one) and rewrites <index file> and <index file>.list.  Both are written under temporary names and renamed when whole:
@@ -539,19 +542,11 @@ hesaff_ctx *search_context(int device)
 }
 struct DestroyContext { hesaff_ctx *c; ~DestroyContext() { hesaff_destroy(c); } };
 
-// the query over the context's index, whose images are the files `names`; the ranked list (with verify: the verified list) on stdout
-int answer_query(hesaff_ctx *ctx, const std::vector<std::string> &names, int k, const char *query_path, const int32_t *qwords, int n_query, const uint64_t *qsigs,
-                 int top, bool verify, float tolerance, int max_pairs, int hamming)
+// the ranked list of one query - `count` images of the context's index, whose images are the files `names`, and their scores - on
+// stdout; with verify the verified list
+int print_ranked(hesaff_ctx *ctx, const std::vector<std::string> &names, int k, const char *query_path, const int32_t *images, const double *scores, int count,
+                 bool verify, float tolerance, int max_pairs)
 {
-   std::vector<int32_t> images((size_t)top);
-   std::vector<double> scores((size_t)top);
-   int count = 0;
-   const int asked = hamming < 0 ? hesaff_index_query(ctx, n_query, qwords, 1, top, images.data(), scores.data(), &count)
-                                 : hesaff_index_query_embedded(ctx, n_query, qwords, 1, qsigs, hamming, top, images.data(), scores.data(), &count);
-   if (asked != HESAFF_OK) {
-      fprintf(stderr, "hesaff: the query failed: %s\n", hesaff_last_error(ctx));
-      return 1;
-   }
    if (!verify) {
       for (int r = 0; r < count; r++) printf("%d\t%s\t%.17g\n", r + 1, names[(size_t)images[(size_t)r]].c_str(), scores[(size_t)r]);
       return 0;
@@ -585,6 +580,56 @@ int answer_query(hesaff_ctx *ctx, const std::vector<std::string> &names, int k, 
    return 0;
 }
 
+// the query over the context's index; the ranked list (with verify: the verified list) on stdout
+int answer_query(hesaff_ctx *ctx, const std::vector<std::string> &names, int k, const char *query_path, const int32_t *qwords, int n_query, const uint64_t *qsigs,
+                 int top, bool verify, float tolerance, int max_pairs, int hamming)
+{
+   std::vector<int32_t> images((size_t)top);
+   std::vector<double> scores((size_t)top);
+   int count = 0;
+   const int asked = hamming < 0 ? hesaff_index_query(ctx, n_query, qwords, 1, top, images.data(), scores.data(), &count)
+                                 : hesaff_index_query_embedded(ctx, n_query, qwords, 1, qsigs, hamming, top, images.data(), scores.data(), &count);
+   if (asked != HESAFF_OK) {
+      fprintf(stderr, "hesaff: the query failed: %s\n", hesaff_last_error(ctx));
+      return 1;
+   }
+   return print_ranked(ctx, names, k, query_path, images.data(), scores.data(), count, verify, tolerance, max_pairs);
+}
+
+// hesaff ... --queries <list>: the listed words files (and with --hamming their signatures files) as ONE batch over the context's
+// index (hesaff_index_query_batch); per query, in list order, a line "# <query path>" and then exactly what --query prints for that
+// file.  --verify runs per query on its own shortlist.
+int answer_queries(hesaff_ctx *ctx, const std::vector<std::string> &names, int k, const char *queries_path, int top, bool verify, float tolerance, int max_pairs,
+                   int hamming)
+{
+   std::vector<std::string> queries;
+   if (!read_list(queries_path, queries)) return 1;
+   if (queries.empty()) { fprintf(stderr, "hesaff: list '%s' names no words file\n", queries_path); return 1; }
+   if (queries.size() > 65536) { fprintf(stderr, "hesaff: list '%s' names %zu queries, a batch takes at most 65536\n", queries_path, queries.size()); return 1; }
+   std::vector<int32_t> counts;
+   WordsReader in;
+   in.k = k;
+   in.with_sigs = hamming >= 0;
+   if (!in.read_all(queries, counts)) return 1;
+   const size_t nq = queries.size();
+   std::vector<int32_t> images(nq * (size_t)top);
+   std::vector<double> scores(nq * (size_t)top);
+   int count = 0;
+   const int asked = hamming < 0 ? hesaff_index_query_batch(ctx, (int)nq, counts.data(), in.words.data(), 1, top, images.data(), scores.data(), &count)
+                                 : hesaff_index_query_batch_embedded(ctx, (int)nq, counts.data(), in.words.data(), 1, in.sigs.data(), hamming, top, images.data(),
+                                                                     scores.data(), &count);
+   if (asked != HESAFF_OK) {
+      fprintf(stderr, "hesaff: the queries failed: %s\n", hesaff_last_error(ctx));
+      return 1;
+   }
+   for (size_t q = 0; q < nq; q++) {
+      printf("# %s\n", queries[q].c_str());
+      const int rc = print_ranked(ctx, names, k, queries[q].c_str(), images.data() + q * (size_t)top, scores.data() + q * (size_t)top, count, verify, tolerance, max_pairs);
+      if (rc != 0) return rc;
+   }
+   return 0;
+}
+
 // the pair of an index: <index> (hesaff_index_save) and <index>.list, the paths of its images one per line.  Both are written under
 // temporary names and renamed when both are whole, so that a run that fails leaves the pair it found.
 int write_index_pair(hesaff_ctx *ctx, const char *index_path, const std::vector<std::string> &names)
@@ -610,7 +655,7 @@ int write_index_pair(hesaff_ctx *ctx, const char *index_path, const std::vector<
 // save_path == nullptr: hesaff --search <list> --query <file>, the index built for this one query.  Otherwise hesaff --search <list>
 // --save-index <index>: the index is built (an embedded one with --hamming) and written with its list; no query is asked.
 int run_search_mode(const char *list_path, const char *query_path, int top, int device, bool verify, float tolerance, int max_pairs, int hamming,
-                    const char *save_path = nullptr)
+                    const char *save_path = nullptr, const char *queries_path = nullptr)
 {
    std::vector<std::string> names;
    if (!read_list(list_path, names)) return 1;
@@ -632,13 +677,15 @@ int run_search_mode(const char *list_path, const char *query_path, int top, int 
       return 1;
    }
    if (save_path) return write_index_pair(ctx, save_path, names);
+   if (queries_path) return answer_queries(ctx, names, in.k, queries_path, top, verify, tolerance, max_pairs, hamming);
    return answer_query(ctx, names, in.k, query_path, in.words.data() + indexed, n_query, in.sigs.data() + indexed, top, verify, tolerance, max_pairs, hamming);
 }
 
 // hesaff --index <index> --query <file>: the index is loaded (hesaff_index_load), not built; the result paths, and the candidates'
 // rows for --verify, are those of <index>.list.  hesaff --index <index> --add <list>: the listed words files (and their signatures
 // files where the index is an embedded one) are added behind the index's images (hesaff_index_add) and the pair is rewritten.
-int run_index_mode(const char *index_path, const char *query_path, const char *add_path, int top, int device, bool verify, float tolerance, int max_pairs, int hamming)
+int run_index_mode(const char *index_path, const char *query_path, const char *add_path, int top, int device, bool verify, float tolerance, int max_pairs, int hamming,
+                   const char *queries_path = nullptr)
 {
    std::vector<std::string> names, more;
    const std::string list = std::string(index_path) + ".list";
@@ -669,6 +716,7 @@ int run_index_mode(const char *index_path, const char *query_path, const char *a
       return write_index_pair(ctx, index_path, names);
    }
    if (hamming >= 0 && !embedded) { fprintf(stderr, "hesaff: '%s' holds no signatures: --hamming needs an index saved with --hamming\n", index_path); return 1; }
+   if (queries_path) return answer_queries(ctx, names, k, queries_path, top, verify, tolerance, max_pairs, hamming);
    in.with_sigs = hamming >= 0;
    int n_query = 0;
    if (!in.read(query_path, n_query)) return 1;
@@ -689,8 +737,10 @@ int main(int argc, char **argv)
    bool search = false, from_index = false;
    for (int i = 1; i < argc; i++) search = search || strcmp(argv[i], "--search") == 0;
    for (int i = 1; i < argc; i++) from_index = from_index || strcmp(argv[i], "--index") == 0;
-   if (search || from_index) {
-      const char *list = nullptr, *query = nullptr, *save = nullptr, *index = nullptr, *add = nullptr;
+   bool batch_queries = false;   // --queries without --search or --index: the index form's usage error
+   for (int i = 1; i < argc; i++) batch_queries = batch_queries || strcmp(argv[i], "--queries") == 0;
+   if (search || from_index || batch_queries) {
+      const char *list = nullptr, *query = nullptr, *save = nullptr, *index = nullptr, *add = nullptr, *queries = nullptr;
       long top = 10, device = 0, pairs = 1, hamming = -1;
       float tolerance = 8.0f;
       bool bad = false, verify = false, verify_options = false, query_options = false;
@@ -700,6 +750,7 @@ int main(int argc, char **argv)
          char *end = nullptr;
          if (strcmp(argv[i], "--search") == 0 && !list) list = argv[i + 1];
          else if (strcmp(argv[i], "--query") == 0 && !query) query = argv[i + 1];
+         else if (strcmp(argv[i], "--queries") == 0 && !queries) queries = argv[i + 1];
          else if (strcmp(argv[i], "--save-index") == 0 && !save) save = argv[i + 1];
          else if (strcmp(argv[i], "--index") == 0 && !index) index = argv[i + 1];
          else if (strcmp(argv[i], "--add") == 0 && !add) add = argv[i + 1];
@@ -716,22 +767,22 @@ int main(int argc, char **argv)
       }
       bad = bad || (verify_options && !verify);
       if (search) {
-         // one of --query and --save-index; --save-index asks no query, so it takes none of the query's options
-         bad = bad || !list || index || add || (query != nullptr) == (save != nullptr) || (save && (verify || query_options));
+         // one of --query, --queries and --save-index; --save-index asks no query, so it takes none of the query's options
+         bad = bad || !list || index || add || (query != nullptr) + (queries != nullptr) + (save != nullptr) != 1 || (save && (verify || query_options));
          if (bad) {
-            fprintf(stderr, "hesaff: usage: hesaff --search <list of .hesaff.words files> --query <.hesaff.words file> [--top 1..1024] [--device D] [--hamming 0..64] "
+            fprintf(stderr, "hesaff: usage: hesaff --search <list of .hesaff.words files> --query <.hesaff.words file> | --queries <list of .hesaff.words files> [--top 1..1024] [--device D] [--hamming 0..64] "
                             "[--verify [--tolerance PX] [--pairs 1..16]]   or   hesaff --search <list> --save-index <index file> [--device D] [--hamming 0..64]\n");
             return 1;
          }
-         return run_search_mode(list, query, (int)top, (int)device, verify, tolerance, (int)pairs, (int)hamming, save);
+         return run_search_mode(list, query, (int)top, (int)device, verify, tolerance, (int)pairs, (int)hamming, save, queries);
       }
-      bad = bad || !index || save || (query != nullptr) == (add != nullptr) || (add && (verify || query_options || hamming >= 0));
+      bad = bad || !index || save || (query != nullptr) + (queries != nullptr) + (add != nullptr) != 1 || (add && (verify || query_options || hamming >= 0));
       if (bad) {
-         fprintf(stderr, "hesaff: usage: hesaff --index <index file> --query <.hesaff.words file> [--top 1..1024] [--device D] [--hamming 0..64] "
+         fprintf(stderr, "hesaff: usage: hesaff --index <index file> --query <.hesaff.words file> | --queries <list of .hesaff.words files> [--top 1..1024] [--device D] [--hamming 0..64] "
                          "[--verify [--tolerance PX] [--pairs 1..16]]   or   hesaff --index <index file> --add <list of .hesaff.words files> [--device D]\n");
          return 1;
       }
-      return run_index_mode(index, query, add, (int)top, (int)device, verify, tolerance, (int)pairs, (int)hamming);
+      return run_index_mode(index, query, add, (int)top, (int)device, verify, tolerance, (int)pairs, (int)hamming, queries);
    }
    bool batch = false;
    for (int i = 1; i < argc; i++) batch = batch || strcmp(argv[i], "--batch") == 0;

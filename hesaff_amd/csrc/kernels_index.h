@@ -137,6 +137,13 @@ __global__ __launch_bounds__(256) void k_query_score(const int32_t *__restrict__
    }
 }
 
+// the score of one image: the three binary64 operations of the definition (k_query_finish, and k_query_finish_batch of
+// kernels_index_batch.h)
+__device__ __forceinline__ double hs_index_score(unsigned long long d, unsigned long long nq2, unsigned long long n2)
+{
+   return d ? __ddiv_rn(__ull2double_rn(d), __dsqrt_rn(__dmul_rn(__ull2double_rn(nq2), __ull2double_rn(n2)))) : 0.0;
+}
+
 // score[i] = dot / sqrt(nq2 * norm2) in binary64 - the conversions, the product, the root and the quotient each rounded to nearest
 // even - or 0.0 where dot is 0.  Grid: ceil(n_images / 256).
 __global__ __launch_bounds__(256) void k_query_finish(const unsigned long long *__restrict__ dot, const unsigned long long *__restrict__ norm2,
@@ -144,10 +151,7 @@ __global__ __launch_bounds__(256) void k_query_finish(const unsigned long long *
 {
    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
    if (i >= n_images) return;
-   const unsigned long long d = dot[i];
-   double s = 0.0;
-   if (d) s = __ddiv_rn(__ull2double_rn(d), __dsqrt_rn(__dmul_rn(__ull2double_rn(head->nq2), __ull2double_rn(norm2[i]))));
-   score[i] = s;
+   score[i] = hs_index_score(dot[i], head->nq2, norm2[i]);
 }
 
 #define HS_ISEL_THREADS 1024
@@ -158,9 +162,11 @@ __device__ __forceinline__ uint32_t hs_isel_digit(unsigned long long hi, uint32_
    return pass < 8 ? (uint32_t)(hi >> (56 - 8 * pass)) & 255u : (lo >> (24 - 8 * (pass - 8))) & 255u;
 }
 
-// One block.  top_images / top_scores [min(top, n_images)]: the images in the order (score descending, image ascending); head->count.
-__global__ __launch_bounds__(HS_ISEL_THREADS) void k_index_select(const double *__restrict__ score, int n_images, int top, int32_t *__restrict__ top_images,
-                                                                  double *__restrict__ top_scores, IndexResultHead *__restrict__ head)
+// The selection of one block of HS_ISEL_THREADS threads over one row of scores (k_index_select, and one block per query in
+// k_index_select_batch of kernels_index_batch.h).  top_images / top_scores [min(top, n_images)]: the images in the order (score
+// descending, image ascending); head->count.
+__device__ __forceinline__ void hs_index_select_block(const double *__restrict__ score, int n_images, int top, int32_t *__restrict__ top_images,
+                                                      double *__restrict__ top_scores, IndexResultHead *__restrict__ head)
 {
    __shared__ uint32_t s_hist[256];
    __shared__ uint32_t s_wsum[4];
@@ -239,4 +245,11 @@ __global__ __launch_bounds__(HS_ISEL_THREADS) void k_index_select(const double *
       top_scores[rank] = __longlong_as_double((long long)hi);
    }
    if (tid == 0u) head->count = got;
+}
+
+// One block.
+__global__ __launch_bounds__(HS_ISEL_THREADS) void k_index_select(const double *__restrict__ score, int n_images, int top, int32_t *__restrict__ top_images,
+                                                                  double *__restrict__ top_scores, IndexResultHead *__restrict__ head)
+{
+   hs_index_select_block(score, n_images, top, top_images, top_scores, head);
 }

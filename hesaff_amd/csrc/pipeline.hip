@@ -47,6 +47,7 @@
 #include "kernels_verify.h"
 #include "kernels_embed.h"
 #include "kernels_index_grow.h"
+#include "kernels_index_batch.h"
 #include "chunk_engine.h"
 #include "batch_plan.h"
 #include "buffer_layouts.h"
@@ -482,7 +483,16 @@ struct hesaff_ctx {
       int64_t n_keys = 0, n_postings = 0;
       bool built = false;
       template <class T> T *ptr(const Span<T> &s) const { return tables.at<T>(s.off); }
+      // hesaff_index_query_batch*: the scratch of a chunk (index_batch_plan.h: IndexBatchArrays), the chunks' query starts, the staged
+      // words and signatures of a host batch, and the pinned block a chunk's ranked rows arrive in.  They grow to what the batches so
+      // far needed and go with the index; no batch call: nothing here is allocated, launched or copied
+      DevBuf batch_scratch, batch_starts, batch_words, batch_sigs;
+      PinBuf batch_ranked;
+      void release_batch() { batch_scratch.release(); batch_starts.release(); batch_words.release(); batch_sigs.release(); batch_ranked.release(); }
    } index;
+   size_t index_batch_budget = 0;      // hesaff_index_set_batch_budget: a context setting, kept by clear, build and load (0: the plan's default)
+   float index_batch_ms[3] = {0.0f, 0.0f, 0.0f};   // hesaff_get_index_batch_ms: grouping, scoring, finish and selection, summed over the last batch's chunks
+   int index_batch_chunks = 0;         // hesaff_index_get_batch_chunks: the chunks of the last batch
    // hesaff_set_embedding: the projection as k_embed_keys reads it and the thresholds of every word (embed_plan.h: EmbedArrays in `buf`);
    // not set: nothing here is allocated, launched or copied, and the assignment stops at the words
    struct Embedding {
@@ -1717,3 +1727,4 @@ void pack_regions(hesaff_ctx *c, uint32_t n_hess, int B, hesaff_region *d_region
 #include "capi_verify.h"
 #include "capi_embed.h"
 #include "capi_index_grow.h"
+#include "capi_index_batch.h"

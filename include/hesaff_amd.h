@@ -59,6 +59,7 @@ extern "C" {
  *    And for vocabulary probes (hesaff_set_vocabulary_probes / hesaff_get_vocabulary_probes / hesaff_stage_probe_cells): symbols only, version 8.
  *    And for Hamming embedding (hesaff_set_embedding and the twenty symbols declared with it): symbols only, version 8.
  *    And for the growing, durable index (hesaff_index_add and the nine symbols declared with it): symbols only, version 8.
+ *    And for batched index queries (hesaff_index_query_batch and the seven symbols declared with it): symbols only, version 8.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -880,6 +881,45 @@ int hesaff_write_index_file(const char *path, int embedded, int vocabulary_size,
                             const uint32_t *postings, const uint32_t *key_count, const uint32_t *key_image, const uint64_t *key_sig);
 int hesaff_read_index_file(const char *path, int *embedded, int *vocabulary_size, int *n_images, int64_t *n_keys, int64_t *n_postings, uint32_t **df,
                            uint32_t **postings, uint32_t **key_count, uint32_t **key_image, uint64_t **key_sig);
+
+/* Batched index queries: many queries per call, ranked on the device.  Symbols only, version 8.
+ * A batch is Q queries, 1 <= Q <= 2^16.  Query q has counts[q] words, 0 <= counts[q] <= 2^18, each in 0 .. K - 1; the total is at most
+ * 2^28 words; the words of all queries are concatenated in hesaff_index_build's layout (word_stride 1 or 2).  counts is host memory
+ * in both forms.  top applies to every query, 1 <= top <= 1024.
+ * THE RESULT OF QUERY q IS, BIT FOR BIT, WHAT hesaff_index_query RETURNS FOR THE SAME WORDS ON THE SAME INDEX (nq2, dot, the three
+ * binary64 operations, the order and the tie rules are unchanged): images_out[q * top + r] and scores_out[q * top + r] for
+ * r < *count_out = min(top, N); entries past the count are not written.  The embedded forms take a signature per word and answer per
+ * query as hesaff_index_query_embedded with the same threshold.
+ * The state a batch leaves is the state Q single calls in that order would leave: hesaff_index_get_scores gives the dot, score and
+ * nq2 of the batch's last query, and a later single query, add, save or detection behaves as if the batch had been single calls.
+ * hesaff_get_index_ms's query_ms reports the whole batch.
+ * A batch runs in chunks of consecutive queries: a chunk is the longest run whose device scratch - per query a row of dot and of
+ * score over the N images, a head and the ranked row, and the hash table of the chunk's words - fits the budget; one query is always
+ * a chunk, even above it.  hesaff_index_set_batch_budget sets the budget in bytes (0: the default, 1 GiB - a design choice, not a
+ * measured optimum) and releases what earlier batches allocated; hesaff_index_get_batch_budget reads the budget in force.  The
+ * result does not depend on the budget.  The scratch belongs to the context's index, grows to what the batches so far needed, and is
+ * released by hesaff_index_clear, by a build, load or add replacing the index, by hesaff_index_set_batch_budget and by destroy;
+ * without a batch call nothing is allocated, launched or copied.  The host forms also hold the batch's words (and signatures) in
+ * device memory for the call: 4 (12) bytes per word beside the scratch.
+ * HESAFF_ERR_ARG, with the index, the last query's scores and the context unchanged: a NULL context or a required pointer NULL; Q, a
+ * count, the total or top outside its bounds; word_stride not 1 or 2; a misaligned device pointer (words 4, signatures 8 bytes); a
+ * word outside 0 .. K - 1 in any query (the host forms check while staging, the device forms in one read-only pass over all words
+ * before any chunk runs); no index built; the embedded forms on a plain index, or hamming outside 0 .. 64.  HESAFF_ERR_NOMEM: what a
+ * batch needs is allocated before its first chunk runs, so a batch that cannot get it changes nothing either.
+ * hesaff_get_index_batch_ms: HIP-event times at profiling level >= 1, 0 otherwise, summed over the chunks of the last batch: grouping
+ * the words, scoring, and finish with selection.  hesaff_index_get_batch_chunks: the chunks the last batch ran in (0 before the first). */
+int hesaff_index_query_batch(hesaff_ctx *ctx, int n_queries, const int32_t *counts, const int32_t *words, int word_stride, int top,
+                             int32_t *images_out, double *scores_out, int *count_out);
+int hesaff_index_query_batch_device(hesaff_ctx *ctx, int n_queries, const int32_t *counts, const void *d_words, int word_stride, int top,
+                                    int32_t *images_out, double *scores_out, int *count_out);
+int hesaff_index_query_batch_embedded(hesaff_ctx *ctx, int n_queries, const int32_t *counts, const int32_t *words, int word_stride,
+                                      const uint64_t *sigs, int hamming, int top, int32_t *images_out, double *scores_out, int *count_out);
+int hesaff_index_query_batch_embedded_device(hesaff_ctx *ctx, int n_queries, const int32_t *counts, const void *d_words, int word_stride,
+                                             const void *d_sigs, int hamming, int top, int32_t *images_out, double *scores_out, int *count_out);
+int hesaff_index_set_batch_budget(hesaff_ctx *ctx, size_t bytes);
+int hesaff_index_get_batch_budget(const hesaff_ctx *ctx, size_t *bytes);
+int hesaff_index_get_batch_chunks(const hesaff_ctx *ctx, int *chunks);
+int hesaff_get_index_batch_ms(const hesaff_ctx *ctx, float *group_ms, float *score_ms, float *select_ms);
 
 /* Spatial verification (no counterpart in the reference): the shortlist of a tf-idf query re-ranked by how many tentative
  * correspondences agree with the best single-correspondence affine hypothesis - the "fast spatial matching" of Philbin et al. 2007

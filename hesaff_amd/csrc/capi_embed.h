@@ -1,8 +1,9 @@
 // capi_embed.h -- Hamming embedding (hesaff_set_embedding, hesaff_embed_device, hesaff_train_embedding*, hesaff_index_build_embedded*,
 // hesaff_index_query_embedded* and the getters declared with them in include/hesaff_amd.h): the entry points over the kernels of
 // kernels_embed.h, with every number from embed_plan.h.  Included at the end of pipeline.hip, behind capi_verify.h (same translation
-// unit).  The embedding is context state beside the vocabulary (hesaff_ctx::embed); a context without one allocates, launches and
-// copies nothing here, and its assignment, its index and its queries are those of a context that never had one.
+// unit).  The index forms are entry points alone: staging, build, key lists and the query driver are capi_index.h's, which the plain
+// forms share.  The embedding is context state beside the vocabulary (hesaff_ctx::embed); a context without one allocates, launches
+// and copies nothing here, and its assignment, its index and its queries are those of a context that never had one.
 #pragma once
 
 namespace {
@@ -58,73 +59,6 @@ void train_embedding_on_device(hesaff_ctx *c, int n, const uint8_t *d_desc, long
    finish_stream(c);
    if (timed)
       for (int q = 0; q < 3; q++) HIP_TRY(hipEventElapsedTime(&c->embed_train_ms[q], ev[q], ev[q + 1]));
-}
-
-// the key lists of a new index (not yet the context's) over `total` checked words and their signatures in device memory
-void build_key_lists(hesaff_ctx *c, hesaff_ctx::Index &nx, int n_images, const int32_t *counts, const int32_t *d_words, int word_stride,
-                     const unsigned long long *d_sigs, int k, int64_t total)
-{
-   StagePlan persistent;
-   nx.ka = key_list_arrays(persistent, k, total);
-   nx.keys.ensure(std::max<size_t>(persistent.bytes(), 256));   // (HESAFF_ERR_NOMEM: the context's index is untouched)
-   TrainArena m;
-   const KeyListBuildArrays b = key_list_build_arrays(m, k);
-   const Span<uint32_t> a_starts = m.add<uint32_t>((size_t)n_images + 1);
-   m.ensure();
-   hipStream_t st = c->stream();
-   std::vector<uint32_t> starts((size_t)n_images + 1);
-   starts[0] = 0;
-   for (int i = 0; i < n_images; i++) starts[(size_t)i + 1] = starts[(size_t)i] + (uint32_t)counts[i];
-   HIP_TRY(hipMemcpyAsync(m.ptr(a_starts), starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st));
-   HIP_TRY(hipMemsetAsync(m.ptr(b.counts), 0, b.counts.bytes(), st));
-   const uint32_t key_blocks = (uint32_t)((total + 255) / 256);
-   if (total > 0)
-      hipLaunchKernelGGL(k_word_histogram, dim3(key_blocks), dim3(256), 0, st, d_words, word_stride, (int)total, m.ptr(b.counts), 1, (unsigned long long *)nullptr);
-   LoadU32 load;
-   load.p = m.ptr(b.counts);
-   uint32_t *offsets = nx.kptr(nx.ka.offsets);
-   exclusive_scan(c, load, (long long)k, offsets, offsets + k, m.ptr(b.block_sums));
-   HIP_TRY(hipMemcpyAsync(m.ptr(b.counts), offsets, (size_t)k * 4, hipMemcpyDeviceToDevice, st));   // (the scan has read the counts: now the cursor)
-   if (total > 0)
-      hipLaunchKernelGGL(k_keylist_scatter, dim3(key_blocks), dim3(256), 0, st, d_words, word_stride, d_sigs, (const uint32_t *)m.ptr(a_starts), n_images,
-                         (uint32_t)total, m.ptr(b.counts), nx.kptr(nx.ka.sig), nx.kptr(nx.ka.image));
-   finish_stream(c);   // (the scratch and `starts` go with this frame)
-   nx.embedded = true;
-}
-
-// the embedded query over n checked words and their signatures in device memory; the ranked result goes to the caller's arrays
-void query_embedded_on_device(hesaff_ctx *c, int n, const int32_t *d_words, int word_stride, const unsigned long long *d_sigs, int threshold, int top,
-                              int32_t *images_out, double *scores_out, int *count_out)
-{
-   hesaff_ctx::Index &ix = c->index;
-   hipStream_t st = c->stream();
-   const bool timed = c->profiling >= 1;
-   DevEvent ev[2];
-   if (timed) for (DevEvent &e : ev) e = DevEvent(hipEventDefault);
-   IndexResultHead *head = ix.ptr(ix.a.head);
-   if (timed) HIP_TRY(hipEventRecord(ev[0], st));
-   HIP_TRY(hipMemsetAsync(ix.ptr(ix.a.dot), 0, ix.a.dot.bytes(), st));
-   HIP_TRY(hipMemsetAsync(head, 0, sizeof(IndexResultHead), st));
-   if (n > 0) {
-      hipLaunchKernelGGL(k_query_count, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, d_words, word_stride, n, ix.ptr(ix.a.tfq));
-      hipLaunchKernelGGL(k_query_score_embedded, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, st, d_words, word_stride, d_sigs, n, threshold, ix.ptr(ix.a.tfq),
-                         (const uint32_t *)ix.ptr(ix.a.idf), (const uint32_t *)ix.kptr(ix.ka.offsets), (const unsigned long long *)ix.kptr(ix.ka.sig),
-                         (const uint32_t *)ix.kptr(ix.ka.image), ix.ptr(ix.a.dot), head);
-   }
-   hipLaunchKernelGGL(k_query_finish, dim3((uint32_t)((ix.n_images + 255) / 256)), dim3(256), 0, st, (const unsigned long long *)ix.ptr(ix.a.dot),
-                      (const unsigned long long *)ix.ptr(ix.a.norm2), (const IndexResultHead *)head, ix.n_images, ix.ptr(ix.a.score));
-   hipLaunchKernelGGL(k_index_select, dim3(1), dim3(HS_ISEL_THREADS), 0, st, (const double *)ix.ptr(ix.a.score), ix.n_images, top, ix.ptr(ix.a.top_images), ix.ptr(ix.a.top_scores), head);
-   if (timed) HIP_TRY(hipEventRecord(ev[1], st));
-   const int count = std::min(top, ix.n_images);
-   char *h = (char *)c->h_small_end.ensure_small((size_t)HS_INDEX_MAX_TOP * 12);
-   HIP_TRY(hipMemcpyAsync(h, ix.ptr(ix.a.top_scores), (size_t)count * 8, hipMemcpyDeviceToHost, st));
-   HIP_TRY(hipMemcpyAsync(h + (size_t)HS_INDEX_MAX_TOP * 8, ix.ptr(ix.a.top_images), (size_t)count * 4, hipMemcpyDeviceToHost, st));
-   finish_stream(c);
-   c->index_ms[2] = 0.0f;
-   if (timed) HIP_TRY(hipEventElapsedTime(&c->index_ms[2], ev[0], ev[1]));
-   memcpy(scores_out, h, (size_t)count * 8);
-   memcpy(images_out, h + (size_t)HS_INDEX_MAX_TOP * 8, (size_t)count * 4);
-   *count_out = count;
 }
 
 bool embed_source_ok(int64_t n, const void *d_desc, int64_t stride, int64_t offset)
@@ -203,9 +137,9 @@ int hesaff_embed_device(hesaff_ctx *c, int64_t n, const void *d_desc, int64_t st
    HS_API_BEGIN
    need_vocabulary(c);
    need_embedding(c);
-   bind_device(c);
-   check_device_words(c, (const int32_t *)d_words, word_stride, (long long)n, c->embed.k, "hesaff_embed_device");
-   launch_embed_keys(c, d_desc, (long long)n, (long long)stride, (long long)offset, (const int32_t *)d_words, word_stride, d_sigs_out);
+   DevBuf none;
+   const DeviceWords w = stage_source(c, {"hesaff_embed_device", true, d_words, word_stride, n, nullptr, false}, c->embed.k, none);
+   launch_embed_keys(c, d_desc, (long long)n, (long long)stride, (long long)offset, w.d_words, w.word_stride, d_sigs_out);
    finish_stream(c);
    HS_API_END(c)
 }
@@ -216,8 +150,8 @@ int hesaff_stage_embed(hesaff_ctx *c, int n, const uint8_t *desc, const int32_t 
    HS_API_BEGIN
    need_vocabulary(c);
    need_embedding(c);
-   std::vector<int32_t> packed;
-   if (!stage_words(words, word_stride, n, c->embed.k, packed)) throw HsError(HESAFF_ERR_ARG, "hesaff_stage_embed: a word lies outside 0 .. vocabulary_size - 1");
+   std::vector<int32_t> packed;   // (into the stage arena with the descriptors, not into a buffer of their own: the check alone is shared)
+   pack_host_words({"hesaff_stage_embed", false, words, word_stride, n, nullptr, false}, c->embed.k, packed);
    bind_device(c);
    if (n == 0) return HESAFF_OK;
    const size_t N = (size_t)n;
@@ -264,9 +198,9 @@ int hesaff_train_embedding_device(hesaff_ctx *c, int64_t n, const void *d_desc, 
    if (!c || !d_desc || !d_words || !tau_out || !embed_train_counts_ok(n, k) || !embed_projection_ok(P)) return HESAFF_ERR_ARG;
    if (!word_source_ok(stride, offset) || !index_word_stride_ok(word_stride) || (uintptr_t)d_desc % 4 != 0 || (uintptr_t)d_words % 4 != 0) return HESAFF_ERR_ARG;
    HS_API_BEGIN
-   bind_device(c);
-   check_device_words(c, (const int32_t *)d_words, word_stride, (long long)n, k, "hesaff_train_embedding_device");
-   train_embedding_on_device(c, (int)n, (const uint8_t *)d_desc, (long long)stride, (long long)offset, (const int32_t *)d_words, word_stride, k, P, tau_out, counts_out);
+   DevBuf none;
+   const DeviceWords w = stage_source(c, {"hesaff_train_embedding_device", true, d_words, word_stride, n, nullptr, false}, k, none);
+   train_embedding_on_device(c, (int)n, (const uint8_t *)d_desc, (long long)stride, (long long)offset, w.d_words, w.word_stride, k, P, tau_out, counts_out);
    HS_API_END(c)
 }
 
@@ -275,15 +209,11 @@ int hesaff_train_embedding(hesaff_ctx *c, int64_t n, const uint8_t *desc, const 
 {
    if (!c || !desc || !words || !tau_out || !embed_train_counts_ok(n, k) || !embed_projection_ok(P) || !index_word_stride_ok(word_stride)) return HESAFF_ERR_ARG;
    HS_API_BEGIN
-   std::vector<int32_t> packed;
-   if (!stage_words(words, word_stride, n, k, packed)) throw HsError(HESAFF_ERR_ARG, "hesaff_train_embedding: a word lies outside 0 .. k - 1");
-   bind_device(c);
-   DevBuf d, w;
+   DevBuf d, g;
+   const DeviceWords w = stage_source(c, {"hesaff_train_embedding", false, words, word_stride, n, nullptr, false, "k"}, k, g);
    d.ensure((size_t)n * 128);
-   w.ensure(std::max<size_t>((size_t)n * 4, 256));
    HIP_TRY(hipMemcpyAsync(d.p, desc, (size_t)n * 128, hipMemcpyHostToDevice, c->stream()));
-   HIP_TRY(hipMemcpyAsync(w.p, packed.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream()));
-   train_embedding_on_device(c, (int)n, d.as<uint8_t>(), 128, 0, w.as<int32_t>(), 1, k, P, tau_out, counts_out);
+   train_embedding_on_device(c, (int)n, d.as<uint8_t>(), 128, 0, w.d_words, w.word_stride, k, P, tau_out, counts_out);
    HS_API_END(c)
 }
 
@@ -304,66 +234,25 @@ int hesaff_get_embedding_ms(const hesaff_ctx *c, float *embed_ms, float *project
 int hesaff_index_build_embedded_device(hesaff_ctx *c, int n_images, const int32_t *counts, const void *d_words, int word_stride, const void *d_sigs,
                                        int vocabulary_size)
 {
-   if (!c || !counts || !index_counts_ok(n_images, vocabulary_size) || !index_word_stride_ok(word_stride)) return HESAFF_ERR_ARG;
-   const int64_t total = index_total_keys(counts, n_images);
-   if (total < 0 || (total > 0 && (!d_words || !d_sigs)) || (uintptr_t)d_words % 4 != 0 || (uintptr_t)d_sigs % 8 != 0) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   check_device_words(c, (const int32_t *)d_words, word_stride, (long long)total, vocabulary_size, "hesaff_index_build_embedded_device");
-   build_index_on_device(c, n_images, counts, (const int32_t *)d_words, word_stride, vocabulary_size, total, (const unsigned long long *)d_sigs, true);
-   HS_API_END(c)
+   return build_from(c, n_images, counts, {"hesaff_index_build_embedded_device", true, d_words, word_stride, 0, d_sigs, true}, vocabulary_size);
 }
 
 int hesaff_index_build_embedded(hesaff_ctx *c, int n_images, const int32_t *counts, const int32_t *words, int word_stride, const uint64_t *sigs,
                                 int vocabulary_size)
 {
-   if (!c || !counts || !index_counts_ok(n_images, vocabulary_size) || !index_word_stride_ok(word_stride)) return HESAFF_ERR_ARG;
-   const int64_t total = index_total_keys(counts, n_images);
-   if (total < 0 || (total > 0 && (!words || !sigs))) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   std::vector<int32_t> packed;
-   if (!stage_words(words, word_stride, total, vocabulary_size, packed)) throw HsError(HESAFF_ERR_ARG, "hesaff_index_build_embedded: a word lies outside 0 .. vocabulary_size - 1");
-   bind_device(c);
-   DevBuf d, g;
-   d.ensure(std::max<size_t>((size_t)total * 4, 256));
-   g.ensure(std::max<size_t>((size_t)total * 8, 256));
-   if (total > 0) {
-      HIP_TRY(hipMemcpyAsync(d.p, packed.data(), (size_t)total * 4, hipMemcpyHostToDevice, c->stream()));
-      HIP_TRY(hipMemcpyAsync(g.p, sigs, (size_t)total * 8, hipMemcpyHostToDevice, c->stream()));
-   }
-   build_index_on_device(c, n_images, counts, d.as<int32_t>(), 1, vocabulary_size, total, g.as<unsigned long long>(), true);
-   HS_API_END(c)
+   return build_from(c, n_images, counts, {"hesaff_index_build_embedded", false, words, word_stride, 0, sigs, true}, vocabulary_size);
 }
 
 int hesaff_index_query_embedded_device(hesaff_ctx *c, int n, const void *d_words, int word_stride, const void *d_sigs, int hamming, int top,
                                        int32_t *images_out, double *scores_out, int *count_out)
 {
-   if (!c || !images_out || !scores_out || !count_out || !index_query_ok(n, top) || !index_word_stride_ok(word_stride) || !embed_threshold_ok(hamming)) return HESAFF_ERR_ARG;
-   if ((n > 0 && (!d_words || !d_sigs)) || (uintptr_t)d_words % 4 != 0 || (uintptr_t)d_sigs % 8 != 0 || !c->index.built || !c->index.embedded) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   check_device_words(c, (const int32_t *)d_words, word_stride, n, c->index.k, "hesaff_index_query_embedded_device");
-   query_embedded_on_device(c, n, (const int32_t *)d_words, word_stride, (const unsigned long long *)d_sigs, hamming, top, images_out, scores_out, count_out);
-   HS_API_END(c)
+   return query_from(c, {"hesaff_index_query_embedded_device", true, d_words, word_stride, n, d_sigs, true}, hamming, top, images_out, scores_out, count_out);
 }
 
 int hesaff_index_query_embedded(hesaff_ctx *c, int n, const int32_t *words, int word_stride, const uint64_t *sigs, int hamming, int top, int32_t *images_out,
                                 double *scores_out, int *count_out)
 {
-   if (!c || !images_out || !scores_out || !count_out || !index_query_ok(n, top) || !index_word_stride_ok(word_stride) || !embed_threshold_ok(hamming)) return HESAFF_ERR_ARG;
-   if ((n > 0 && (!words || !sigs)) || !c->index.built || !c->index.embedded) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   std::vector<int32_t> packed;
-   if (!stage_words(words, word_stride, n, c->index.k, packed)) throw HsError(HESAFF_ERR_ARG, "hesaff_index_query_embedded: a word lies outside 0 .. vocabulary_size - 1");
-   bind_device(c);
-   c->index.qwords.ensure(std::max<size_t>((size_t)n * 4, 256));
-   c->index.qsigs.ensure(std::max<size_t>((size_t)n * 8, 256));
-   if (n > 0) {
-      HIP_TRY(hipMemcpyAsync(c->index.qwords.p, packed.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream()));
-      HIP_TRY(hipMemcpyAsync(c->index.qsigs.p, sigs, (size_t)n * 8, hipMemcpyHostToDevice, c->stream()));
-   }
-   query_embedded_on_device(c, n, c->index.qwords.as<int32_t>(), 1, c->index.qsigs.as<unsigned long long>(), hamming, top, images_out, scores_out, count_out);
-   HS_API_END(c)
+   return query_from(c, {"hesaff_index_query_embedded", false, words, word_stride, n, sigs, true}, hamming, top, images_out, scores_out, count_out);
 }
 
 // *embedded: whether the index holds key lists; offsets[K + 1], and per entry of the lists its image and its signature (each may be

@@ -8,16 +8,8 @@
 
 namespace {
 
-struct BatchSource {
-   const int32_t *d_words;                // the batch's words in device memory, checked
-   int word_stride;
-   const unsigned long long *d_sigs;      // embedded: a signature per word
-   int threshold;
-   bool embedded;
-};
-
 // nq queries of counts[q] checked words each in device memory; the ranked rows go to the caller's arrays
-void query_batch_on_device(hesaff_ctx *c, int nq, const int32_t *counts, const BatchSource &src, int top, int32_t *images_out, double *scores_out, int *count_out)
+void query_batch_on_device(hesaff_ctx *c, int nq, const int32_t *counts, const QuerySource &src, int top, int32_t *images_out, double *scores_out, int *count_out)
 {
    hesaff_ctx::Index &ix = c->index;
    const int n_images = ix.n_images, keep = std::min(top, n_images);
@@ -29,9 +21,9 @@ void query_batch_on_device(hesaff_ctx *c, int nq, const int32_t *counts, const B
    size_t scratch_bytes = 0, ranked_bytes = 0;
    for (int64_t first = 0, word_first = 0; first < nq;) {
       const IndexBatchChunk ch = index_batch_next_chunk(counts, nq, first, word_first, n_images, keep, budget);
-      uint32_t at = 0;
-      for (int64_t q = 0; q < ch.count; q++) { starts.push_back(at); at += (uint32_t)counts[first + q]; }
-      starts.push_back(at);
+      const size_t at = starts.size();
+      starts.resize(at + (size_t)ch.count + 1);
+      index_starts(counts + first, ch.count, &starts[at]);
       scratch_bytes = std::max(scratch_bytes, ch.bytes);
       ranked_bytes = std::max(ranked_bytes, index_batch_ranked_bytes(ch.count, keep));
       chunks.push_back(ch);
@@ -65,25 +57,25 @@ void query_batch_on_device(hesaff_ctx *c, int nq, const int32_t *counts, const B
       double *score = (double *)(base + a.score.off), *ranked_scores = (double *)(base + a.ranked.off);
       int32_t *ranked_images = (int32_t *)(base + a.ranked_images_off);
       const uint32_t *d_starts = ix.batch_starts.as<uint32_t>() + ch.first + (int64_t)ci;
-      const int32_t *d_words = src.d_words + ch.word_first * src.word_stride;
+      const int32_t *d_words = src.w.d_words + ch.word_first * src.w.word_stride;
       const uint32_t words = (uint32_t)ch.words;
       // step 1: the distinct (query, word) pairs of the chunk and their counts
       if (timed) HIP_TRY(hipEventRecord(ev[0], st));
       HIP_TRY(hipMemsetAsync(base + a.zero_off, 0, a.zero_bytes, st));   // dot, the heads and the counts
       if (words > 0) {
          HIP_TRY(hipMemsetAsync(hash_keys, 0xFF, a.hash_keys.bytes(), st));
-         hipLaunchKernelGGL(k_index_insert, dim3((words + 255u) / 256u), dim3(256), 0, st, d_words, src.word_stride, d_starts, b, words, a.bits, hash_keys, hash_tf);
+         hipLaunchKernelGGL(k_index_insert, dim3((words + 255u) / 256u), dim3(256), 0, st, d_words, src.w.word_stride, d_starts, b, words, a.bits, hash_keys, hash_tf);
       }
       if (timed) HIP_TRY(hipEventRecord(ev[1], st));
       // step 2: a wavefront per key
       if (words > 0) {
          if (src.embedded)
-            hipLaunchKernelGGL(k_query_score_embedded_batch, dim3((words + 3u) / 4u), dim3(256), 0, st, d_words, src.word_stride, src.d_sigs + ch.word_first, d_starts, b,
+            hipLaunchKernelGGL(k_query_score_embedded_batch, dim3((words + 3u) / 4u), dim3(256), 0, st, d_words, src.w.word_stride, src.w.d_sigs + ch.word_first, d_starts, b,
                                words, src.threshold, a.bits, (const unsigned long long *)hash_keys, hash_tf, (const uint32_t *)ix.ptr(ix.a.idf),
                                (const uint32_t *)ix.kptr(ix.ka.offsets), (const unsigned long long *)ix.kptr(ix.ka.sig), (const uint32_t *)ix.kptr(ix.ka.image), n_images,
                                dot, heads);
          else
-            hipLaunchKernelGGL(k_query_score_batch, dim3((words + 3u) / 4u), dim3(256), 0, st, d_words, src.word_stride, d_starts, b, words, a.bits,
+            hipLaunchKernelGGL(k_query_score_batch, dim3((words + 3u) / 4u), dim3(256), 0, st, d_words, src.w.word_stride, d_starts, b, words, a.bits,
                                (const unsigned long long *)hash_keys, hash_tf, (const uint32_t *)ix.ptr(ix.a.idf), (const uint32_t *)ix.ptr(ix.a.offsets),
                                (const IndexPosting *)ix.lists.as<IndexPosting>(), n_images, dot, heads);
       }
@@ -124,13 +116,18 @@ void query_batch_on_device(hesaff_ctx *c, int nq, const int32_t *counts, const B
    *count_out = keep;
 }
 
-// what the four forms refuse before anything is staged: -> the words of the batch, or -1
-int64_t batch_arguments(const hesaff_ctx *c, int n_queries, const int32_t *counts, int word_stride, int top, const int32_t *images_out, const double *scores_out,
-                        const int *count_out)
+// the four batch forms: what they refuse before anything is staged, the staging - a host form's words and signatures in the index's
+// own batch buffers - and the batch (src.n: set here)
+int batch_from(hesaff_ctx *c, int n_queries, const int32_t *counts, WordSource src, int hamming, int top, int32_t *images_out, double *scores_out, int *count_out)
 {
-   if (!c || !counts || !images_out || !scores_out || !count_out || !index_batch_ok(n_queries, top) || !index_word_stride_ok(word_stride)) return -1;
-   if (!c->index.built) return -1;
-   return index_batch_total(counts, n_queries);
+   if (!c || !counts || !images_out || !scores_out || !count_out || !index_batch_ok(n_queries, top) || !index_word_stride_ok(src.word_stride)) return HESAFF_ERR_ARG;
+   if (!c->index.built || (src.with_sigs && (!embed_threshold_ok(hamming) || !c->index.embedded))) return HESAFF_ERR_ARG;
+   src.n = index_batch_total(counts, n_queries);
+   if (src.n < 0 || !source_ok(src)) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   const QuerySource q = {stage_source(c, src, c->index.k, c->index.batch_words, &c->index.batch_sigs), hamming, src.with_sigs};
+   query_batch_on_device(c, n_queries, counts, q, top, images_out, scores_out, count_out);
+   HS_API_END(c)
 }
 
 } // namespace
@@ -140,65 +137,26 @@ extern "C" {
 int hesaff_index_query_batch_device(hesaff_ctx *c, int n_queries, const int32_t *counts, const void *d_words, int word_stride, int top, int32_t *images_out,
                                     double *scores_out, int *count_out)
 {
-   const int64_t total = batch_arguments(c, n_queries, counts, word_stride, top, images_out, scores_out, count_out);
-   if (total < 0 || (total > 0 && !d_words) || (uintptr_t)d_words % 4 != 0) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   check_device_words(c, (const int32_t *)d_words, word_stride, (long long)total, c->index.k, "hesaff_index_query_batch_device");
-   const BatchSource src = {(const int32_t *)d_words, word_stride, nullptr, 0, false};
-   query_batch_on_device(c, n_queries, counts, src, top, images_out, scores_out, count_out);
-   HS_API_END(c)
+   return batch_from(c, n_queries, counts, {"hesaff_index_query_batch_device", true, d_words, word_stride, 0, nullptr, false}, 0, top, images_out, scores_out, count_out);
 }
 
 int hesaff_index_query_batch(hesaff_ctx *c, int n_queries, const int32_t *counts, const int32_t *words, int word_stride, int top, int32_t *images_out,
                              double *scores_out, int *count_out)
 {
-   const int64_t total = batch_arguments(c, n_queries, counts, word_stride, top, images_out, scores_out, count_out);
-   if (total < 0 || (total > 0 && !words)) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   std::vector<int32_t> packed;
-   if (!stage_words(words, word_stride, total, c->index.k, packed)) throw HsError(HESAFF_ERR_ARG, "hesaff_index_query_batch: a word lies outside 0 .. vocabulary_size - 1");
-   bind_device(c);
-   c->index.batch_words.ensure(std::max<size_t>((size_t)total * 4, 256));
-   if (total > 0) HIP_TRY(hipMemcpyAsync(c->index.batch_words.p, packed.data(), (size_t)total * 4, hipMemcpyHostToDevice, c->stream()));
-   const BatchSource src = {c->index.batch_words.as<int32_t>(), 1, nullptr, 0, false};
-   query_batch_on_device(c, n_queries, counts, src, top, images_out, scores_out, count_out);
-   HS_API_END(c)
+   return batch_from(c, n_queries, counts, {"hesaff_index_query_batch", false, words, word_stride, 0, nullptr, false}, 0, top, images_out, scores_out, count_out);
 }
 
 int hesaff_index_query_batch_embedded_device(hesaff_ctx *c, int n_queries, const int32_t *counts, const void *d_words, int word_stride, const void *d_sigs, int hamming,
                                              int top, int32_t *images_out, double *scores_out, int *count_out)
 {
-   const int64_t total = batch_arguments(c, n_queries, counts, word_stride, top, images_out, scores_out, count_out);
-   if (total < 0 || !embed_threshold_ok(hamming) || !c->index.embedded) return HESAFF_ERR_ARG;
-   if ((total > 0 && (!d_words || !d_sigs)) || (uintptr_t)d_words % 4 != 0 || (uintptr_t)d_sigs % 8 != 0) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   check_device_words(c, (const int32_t *)d_words, word_stride, (long long)total, c->index.k, "hesaff_index_query_batch_embedded_device");
-   const BatchSource src = {(const int32_t *)d_words, word_stride, (const unsigned long long *)d_sigs, hamming, true};
-   query_batch_on_device(c, n_queries, counts, src, top, images_out, scores_out, count_out);
-   HS_API_END(c)
+   return batch_from(c, n_queries, counts, {"hesaff_index_query_batch_embedded_device", true, d_words, word_stride, 0, d_sigs, true}, hamming, top, images_out, scores_out,
+                     count_out);
 }
 
 int hesaff_index_query_batch_embedded(hesaff_ctx *c, int n_queries, const int32_t *counts, const int32_t *words, int word_stride, const uint64_t *sigs, int hamming,
                                       int top, int32_t *images_out, double *scores_out, int *count_out)
 {
-   const int64_t total = batch_arguments(c, n_queries, counts, word_stride, top, images_out, scores_out, count_out);
-   if (total < 0 || !embed_threshold_ok(hamming) || !c->index.embedded || (total > 0 && (!words || !sigs))) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   std::vector<int32_t> packed;
-   if (!stage_words(words, word_stride, total, c->index.k, packed))
-      throw HsError(HESAFF_ERR_ARG, "hesaff_index_query_batch_embedded: a word lies outside 0 .. vocabulary_size - 1");
-   bind_device(c);
-   c->index.batch_words.ensure(std::max<size_t>((size_t)total * 4, 256));
-   c->index.batch_sigs.ensure(std::max<size_t>((size_t)total * 8, 256));
-   if (total > 0) {
-      HIP_TRY(hipMemcpyAsync(c->index.batch_words.p, packed.data(), (size_t)total * 4, hipMemcpyHostToDevice, c->stream()));
-      HIP_TRY(hipMemcpyAsync(c->index.batch_sigs.p, sigs, (size_t)total * 8, hipMemcpyHostToDevice, c->stream()));
-   }
-   const BatchSource src = {c->index.batch_words.as<int32_t>(), 1, c->index.batch_sigs.as<unsigned long long>(), hamming, true};
-   query_batch_on_device(c, n_queries, counts, src, top, images_out, scores_out, count_out);
-   HS_API_END(c)
+   return batch_from(c, n_queries, counts, {"hesaff_index_query_batch_embedded", false, words, word_stride, 0, sigs, true}, hamming, top, images_out, scores_out, count_out);
 }
 
 // the device scratch a chunk may hold (0: the plan's default); what the batches so far allocated is released

@@ -7,50 +7,21 @@
 
 namespace {
 
-uint32_t tile_grid(unsigned long long items) { return (uint32_t)std::max<unsigned long long>(1, (items + HS_GROW_TILE - 1) / HS_GROW_TILE); }
-
 // m images of `total` checked words (and, for an embedded index, their signatures) in device memory behind the context's index
-void add_to_index_on_device(hesaff_ctx *c, int m, const int32_t *counts, const int32_t *d_words, int word_stride, int64_t total, const unsigned long long *d_sigs)
+void add_to_index_on_device(hesaff_ctx *c, int m, const int32_t *counts, const DeviceWords &w, int64_t total)
 {
    const hesaff_ctx::Index &ox = c->index;
-   const int n_old = ox.n_images, n_new = n_old + m, k = ox.k;
+   const int k = ox.k;
    hesaff_ctx::Index nx;
-   StagePlan persistent;
-   nx.a = index_arrays(persistent, n_new, k);
-   nx.tables.ensure(std::max<size_t>(persistent.bytes(), 256));   // (HESAFF_ERR_NOMEM: the context's index is untouched)
+   nx.n_images = ox.n_images + m; nx.k = k; nx.n_keys = ox.n_keys + total;
    TrainArena s;   // the scratch of the call: its hash table is sized for the new keys alone
-   const IndexBuildArrays b = index_build_arrays(s, m, k, total);
-   s.ensure();
+   IndexBuildArrays b;
    hipStream_t st = c->stream();
    const bool timed = c->profiling >= 1;
    DevEvent ev[6];   // insert: 0 .. 1, tables: 1 .. 2, (the host reads the number of postings and allocates the lists) merge: 3 .. 4, scatter: 4 .. 5
    if (timed) for (DevEvent &e : ev) e = DevEvent(hipEventDefault);
-   std::vector<uint32_t> starts((size_t)m + 1);
-   starts[0] = 0;
-   for (int i = 0; i < m; i++) starts[(size_t)i + 1] = starts[(size_t)i] + (uint32_t)counts[i];
-   HIP_TRY(hipMemcpyAsync(s.ptr(b.starts), starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st));
-   HIP_TRY(hipMemsetAsync(nx.tables.p, 0, persistent.bytes(), st));
-   HIP_TRY(hipMemsetAsync(s.ptr(b.hash_keys), 0xFF, b.hash_keys.bytes(), st));
-   HIP_TRY(hipMemsetAsync(s.ptr(b.hash_tf), 0, b.hash_tf.bytes(), st));
-   // step 1: the distinct (image, word) pairs of the new images, numbered from 0 inside the table
-   if (timed) HIP_TRY(hipEventRecord(ev[0], st));
-   if (total > 0)
-      hipLaunchKernelGGL(k_index_insert, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, st, d_words, word_stride, (const uint32_t *)s.ptr(b.starts), m,
-                         (uint32_t)total, b.bits, s.ptr(b.hash_keys), s.ptr(b.hash_tf));
-   if (timed) HIP_TRY(hipEventRecord(ev[1], st));
-   // step 2: df = old + new, idf over N + m, the new offsets
-   const uint32_t slot_grid = grid_for(b.slots);
-   HIP_TRY(hipMemcpyAsync(nx.ptr(nx.a.df), ox.ptr(ox.a.df), (size_t)k * 4, hipMemcpyDeviceToDevice, st));
-   hipLaunchKernelGGL(k_index_df, dim3(slot_grid), dim3(256), 0, st, (const unsigned long long *)s.ptr(b.hash_keys), (unsigned long long)b.slots, nx.ptr(nx.a.df));
-   hipLaunchKernelGGL(k_index_idf, dim3((uint32_t)((k + 255) / 256)), dim3(256), 0, st, (const uint32_t *)nx.ptr(nx.a.df), k, n_new, nx.ptr(nx.a.idf));
-   LoadU32 load;
-   load.p = nx.ptr(nx.a.df);
-   exclusive_scan(c, load, (long long)k, nx.ptr(nx.a.offsets), nx.ptr(nx.a.offsets) + k, s.ptr(b.block_sums));
-   uint32_t *h_postings = (uint32_t *)c->h_small_end.ensure_small(4);
-   HIP_TRY(hipMemcpyAsync(h_postings, nx.ptr(nx.a.offsets) + k, 4, hipMemcpyDeviceToHost, st));
-   if (timed) HIP_TRY(hipEventRecord(ev[2], st));
-   finish_stream(c);
-   const int64_t n_postings = (int64_t)*h_postings;
+   // steps 1 and 2: the distinct (image, word) pairs of the new images; df = old + new, idf over N + m, the new offsets
+   const int64_t n_postings = index_tables_on_device(c, nx, &ox, s, b, counts, w, total, timed ? ev : nullptr);
    if (n_postings < ox.n_postings || n_postings > ox.n_postings + total) throw HsError(HESAFF_ERR_DEVICE, "hesaff_index_add: the postings do not add up");
    nx.lists.ensure(index_lists_bytes(n_postings));
    // step 3: the old postings to their new places, the old norms under the new idf, the cursors behind them
@@ -61,32 +32,11 @@ void add_to_index_on_device(hesaff_ctx *c, int m, const int32_t *counts, const i
                       s.ptr(b.cursor));
    if (timed) HIP_TRY(hipEventRecord(ev[4], st));
    // step 4: the new postings behind them
-   hipLaunchKernelGGL(k_index_postings_based, dim3(slot_grid), dim3(256), 0, st, (const unsigned long long *)s.ptr(b.hash_keys), (const uint32_t *)s.ptr(b.hash_tf),
-                      (unsigned long long)b.slots, (uint32_t)n_old, (const uint32_t *)nx.ptr(nx.a.idf), s.ptr(b.cursor), nx.lists.as<IndexPosting>(), nx.ptr(nx.a.norm2));
+   scatter_postings(c, nx, &ox, s, b);
    if (timed) HIP_TRY(hipEventRecord(ev[5], st));
-   nx.n_images = n_new; nx.k = k; nx.n_keys = ox.n_keys + total; nx.n_postings = n_postings; nx.built = true;
-   if (ox.embedded) {
-      // the key lists likewise: lengths = old + new, a scan, the move, the scatter
-      StagePlan kp;
-      nx.ka = key_list_arrays(kp, k, nx.n_keys);
-      nx.keys.ensure(std::max<size_t>(kp.bytes(), 256));
-      const uint32_t word_blocks = (uint32_t)((k + 255) / 256), key_blocks = (uint32_t)((total + 255) / 256);
-      uint32_t *cursor = s.ptr(b.cursor);   // (the posting scatter, earlier in the stream, is done with it)
-      uint32_t *offsets = nx.kptr(nx.ka.offsets);
-      hipLaunchKernelGGL(k_list_lengths, dim3(word_blocks), dim3(256), 0, st, (const uint32_t *)ox.kptr(ox.ka.offsets), k, cursor);
-      if (total > 0)
-         hipLaunchKernelGGL(k_word_histogram, dim3(key_blocks), dim3(256), 0, st, d_words, word_stride, (int)total, cursor, 1, (unsigned long long *)nullptr);
-      load.p = cursor;
-      exclusive_scan(c, load, (long long)k, offsets, offsets + k, s.ptr(b.block_sums));
-      hipLaunchKernelGGL(k_keylist_merge, dim3(tile_grid(std::max<unsigned long long>((unsigned long long)ox.n_keys, (unsigned long long)k))), dim3(256), 0, st,
-                         (const uint32_t *)ox.kptr(ox.ka.offsets), (const uint32_t *)offsets, k, (uint32_t)ox.n_keys, (const unsigned long long *)ox.kptr(ox.ka.sig),
-                         (const uint32_t *)ox.kptr(ox.ka.image), nx.kptr(nx.ka.sig), nx.kptr(nx.ka.image), cursor);
-      if (total > 0)
-         hipLaunchKernelGGL(k_keylist_scatter_based, dim3(key_blocks), dim3(256), 0, st, d_words, word_stride, d_sigs, (const uint32_t *)s.ptr(b.starts), m,
-                            (uint32_t)total, (uint32_t)n_old, cursor, nx.kptr(nx.ka.sig), nx.kptr(nx.ka.image));
-      nx.embedded = true;
-   }
-   finish_stream(c);   // (the scratch and `starts` go with this frame)
+   nx.n_postings = n_postings; nx.built = true;
+   if (ox.embedded) build_key_lists(c, nx, &ox, s, b, w, total);   // the key lists likewise: lengths = old + new, a scan, the move, the scatter
+   finish_stream(c);   // (the scratch goes with this frame)
    for (int q = 0; q < 4; q++) c->index_growth_ms[q] = 0.0f;
    if (timed) {
       const int from[4] = {0, 1, 3, 4};
@@ -95,14 +45,19 @@ void add_to_index_on_device(hesaff_ctx *c, int m, const int32_t *counts, const i
    c->index = std::move(nx);
 }
 
-// what the four add forms refuse before anything is staged: -> the new keys, or -1
-int64_t add_arguments(const hesaff_ctx *c, int m, const int32_t *counts, int word_stride, bool embedded)
+// the four add forms: what they refuse before anything is staged (an embedded index takes embedded adds alone, a plain one plain
+// adds), the staging, the add (src.n: set here)
+int add_from(hesaff_ctx *c, int m, const int32_t *counts, WordSource src)
 {
-   if (!c || !counts || !c->index.built || c->index.embedded != embedded || !index_word_stride_ok(word_stride)) return -1;
-   if (m < 1 || m > HS_INDEX_MAX_IMAGES) return -1;
-   const int64_t total = index_total_keys(counts, m);
-   if (total < 0 || !index_add_ok(c->index.n_images, m, c->index.n_keys, total)) return -1;
-   return total;
+   if (!c || !counts || !c->index.built || c->index.embedded != src.with_sigs || !index_word_stride_ok(src.word_stride)) return HESAFF_ERR_ARG;
+   if (m < 1 || m > HS_INDEX_MAX_IMAGES) return HESAFF_ERR_ARG;
+   src.n = index_total_keys(counts, m);
+   if (src.n < 0 || !index_add_ok(c->index.n_images, m, c->index.n_keys, src.n) || !source_ok(src)) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   DevBuf d, g;   // the staged words and signatures of a host form go with the call
+   const DeviceWords w = stage_source(c, src, c->index.k, d, &g);
+   add_to_index_on_device(c, m, counts, w, src.n);
+   HS_API_END(c)
 }
 
 // a host array of the index file's into a new device block
@@ -186,58 +141,22 @@ extern "C" {
 
 int hesaff_index_add_device(hesaff_ctx *c, int m_images, const int32_t *counts, const void *d_words, int word_stride)
 {
-   const int64_t total = add_arguments(c, m_images, counts, word_stride, false);
-   if (total < 0 || (total > 0 && !d_words) || (uintptr_t)d_words % 4 != 0) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   check_device_words(c, (const int32_t *)d_words, word_stride, (long long)total, c->index.k, "hesaff_index_add_device");
-   add_to_index_on_device(c, m_images, counts, (const int32_t *)d_words, word_stride, total, nullptr);
-   HS_API_END(c)
+   return add_from(c, m_images, counts, {"hesaff_index_add_device", true, d_words, word_stride, 0, nullptr, false});
 }
 
 int hesaff_index_add(hesaff_ctx *c, int m_images, const int32_t *counts, const int32_t *words, int word_stride)
 {
-   const int64_t total = add_arguments(c, m_images, counts, word_stride, false);
-   if (total < 0 || (total > 0 && !words)) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   std::vector<int32_t> packed;
-   if (!stage_words(words, word_stride, total, c->index.k, packed)) throw HsError(HESAFF_ERR_ARG, "hesaff_index_add: a word lies outside 0 .. vocabulary_size - 1");
-   bind_device(c);
-   DevBuf d;
-   d.ensure(std::max<size_t>((size_t)total * 4, 256));
-   if (total > 0) HIP_TRY(hipMemcpyAsync(d.p, packed.data(), (size_t)total * 4, hipMemcpyHostToDevice, c->stream()));
-   add_to_index_on_device(c, m_images, counts, d.as<int32_t>(), 1, total, nullptr);
-   HS_API_END(c)
+   return add_from(c, m_images, counts, {"hesaff_index_add", false, words, word_stride, 0, nullptr, false});
 }
 
 int hesaff_index_add_embedded_device(hesaff_ctx *c, int m_images, const int32_t *counts, const void *d_words, int word_stride, const void *d_sigs)
 {
-   const int64_t total = add_arguments(c, m_images, counts, word_stride, true);
-   if (total < 0 || (total > 0 && (!d_words || !d_sigs)) || (uintptr_t)d_words % 4 != 0 || (uintptr_t)d_sigs % 8 != 0) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   bind_device(c);
-   check_device_words(c, (const int32_t *)d_words, word_stride, (long long)total, c->index.k, "hesaff_index_add_embedded_device");
-   add_to_index_on_device(c, m_images, counts, (const int32_t *)d_words, word_stride, total, (const unsigned long long *)d_sigs);
-   HS_API_END(c)
+   return add_from(c, m_images, counts, {"hesaff_index_add_embedded_device", true, d_words, word_stride, 0, d_sigs, true});
 }
 
 int hesaff_index_add_embedded(hesaff_ctx *c, int m_images, const int32_t *counts, const int32_t *words, int word_stride, const uint64_t *sigs)
 {
-   const int64_t total = add_arguments(c, m_images, counts, word_stride, true);
-   if (total < 0 || (total > 0 && (!words || !sigs))) return HESAFF_ERR_ARG;
-   HS_API_BEGIN
-   std::vector<int32_t> packed;
-   if (!stage_words(words, word_stride, total, c->index.k, packed)) throw HsError(HESAFF_ERR_ARG, "hesaff_index_add_embedded: a word lies outside 0 .. vocabulary_size - 1");
-   bind_device(c);
-   DevBuf d, g;
-   d.ensure(std::max<size_t>((size_t)total * 4, 256));
-   g.ensure(std::max<size_t>((size_t)total * 8, 256));
-   if (total > 0) {
-      HIP_TRY(hipMemcpyAsync(d.p, packed.data(), (size_t)total * 4, hipMemcpyHostToDevice, c->stream()));
-      HIP_TRY(hipMemcpyAsync(g.p, sigs, (size_t)total * 8, hipMemcpyHostToDevice, c->stream()));
-   }
-   add_to_index_on_device(c, m_images, counts, d.as<int32_t>(), 1, total, g.as<unsigned long long>());
-   HS_API_END(c)
+   return add_from(c, m_images, counts, {"hesaff_index_add_embedded", false, words, word_stride, 0, sigs, true});
 }
 
 int hesaff_index_get_postings(const hesaff_ctx *c, uint32_t *offsets, uint32_t *images, uint32_t *tf)

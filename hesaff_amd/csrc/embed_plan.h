@@ -178,7 +178,8 @@ inline KeyListArrays key_list_arrays(StagePlan &p, int64_t k, int64_t total)
    a.image = p.add<uint32_t>((size_t)(total > 0 ? total : 1));
    return a;
 }
-// the scratch of the key lists' build
+// the scratch of a key lists' build on its own.  Inside an index build or add the lists are made in that call's scratch instead
+// (build_key_lists, capi_index.h): the cursor and the block sums of IndexBuildArrays, index_plan.h, which have these counts
 struct KeyListBuildArrays {
    Span<uint32_t> counts;       // [k]: keys per word, then (a copy of the offsets) each list's next free position
    Span<uint32_t> block_sums;   // the scan's

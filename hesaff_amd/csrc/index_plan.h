@@ -1,10 +1,11 @@
 // index_plan.h -- the host arithmetic of the image index (hesaff_index_build / hesaff_index_query, include/hesaff_amd.h): which calls
-// are refused, the integer logarithm behind idf, the key and the size of the build's hash table, and where the arrays of an index and
-// of a build lie in their buffers.  Pure functions and plain structs, no HIP: capi_index.h and kernels_index.h obtain their numbers
+// are refused, the packing of host words and the key starts of a call's images or queries, the integer logarithm behind idf, the key
+// and the size of the build's hash table, and where the arrays of an index and of a build lie in their buffers.  Pure functions and plain structs, no HIP: capi_index.h and kernels_index.h obtain their numbers
 // here, and tests/native/index_plan_check.cpp checks them on the CPU (tests/test_image_index_host.py).
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 #include "buffer_layouts.h"   // StagePlan, Span
 
@@ -40,6 +41,24 @@ inline int64_t index_total_keys(const int32_t *counts, int64_t n_images)
       total += counts[i];
    }
    return index_total_ok(total) ? total : -1;
+}
+// starts[n + 1]: image (or query) i's keys are words[starts[i] .. starts[i + 1]), an item without keys repeats a start.  The sums
+// are the caller's to bound (index_total_keys); they are made modulo 2^32
+inline void index_starts(const int32_t *counts, int64_t n, uint32_t *starts)
+{
+   starts[0] = 0;
+   for (int64_t i = 0; i < n; i++) starts[i + 1] = starts[i] + (uint32_t)counts[i];
+}
+// words in host memory, key j's at words[j * word_stride] -> packed, checked against 0 .. k - 1 on the way (false: one lies outside)
+inline bool index_stage_words(const int32_t *words, int64_t word_stride, int64_t n, int64_t k, std::vector<int32_t> &out)
+{
+   out.resize((size_t)n);
+   for (int64_t j = 0; j < n; j++) {
+      const int32_t w = words[j * word_stride];
+      if (w < 0 || w >= k) return false;
+      out[(size_t)j] = w;
+   }
+   return true;
 }
 
 // idf of a word in df of n images, 1 <= df <= n < 2^33: floor(256 log2(n / df)) but for the truncations below, which ARE the

@@ -150,11 +150,12 @@ __global__ __launch_bounds__(HS_EMBED_MEDIAN_WAVES * 64) void k_embed_medians(co
    if (wave == 0) tau[w * 64 + lane] = (int32_t)prefix - hesaff_plan::HS_EMBED_Z_BIAS;
 }
 
-// cursor[k]: each list's first position (a copy of the offsets) on entry, its end afterwards.  Key j (of image hs_index_image_of) goes
-// to its word's list.  Grid: ceil(total / 256) blocks of 256.
+// Key j (of image base + hs_index_image_of: a build numbers its images from 0, an add from the images of the index so far) goes to
+// its word's list.  cursor[k]: each list's next free position on entry - a copy of the offsets, or behind the old keys
+// (k_keylist_merge, kernels_index_grow.h) - its end afterwards.  Grid: ceil(total / 256) blocks of 256.
 __global__ __launch_bounds__(256) void k_keylist_scatter(const int32_t *__restrict__ words, int word_stride, const unsigned long long *__restrict__ sigs,
-                                                         const uint32_t *__restrict__ starts, int n_images, uint32_t total, uint32_t *__restrict__ cursor,
-                                                         unsigned long long *__restrict__ list_sig, uint32_t *__restrict__ list_image)
+                                                         const uint32_t *__restrict__ starts, int n_images, uint32_t total, uint32_t base,
+                                                         uint32_t *__restrict__ cursor, unsigned long long *__restrict__ list_sig, uint32_t *__restrict__ list_image)
 {
    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
    const bool live = j < total;
@@ -162,8 +163,18 @@ __global__ __launch_bounds__(256) void k_keylist_scatter(const int32_t *__restri
    const uint32_t pos = hs_claim_per_word(cursor, w, live);
    if (live) {
       list_sig[pos] = sigs[j];
-      list_image[pos] = hs_index_image_of(starts, n_images, j);
+      list_image[pos] = base + hs_index_image_of(starts, n_images, j);
    }
+}
+
+// A wave's walk of one word's keys, entries first .. end - 1 of the lists, its lanes striding them: every entry whose signature lies
+// within `threshold` bits of sig adds ff = idf^2 to row[image] (the dot of the query, or the query's row of a chunk's)
+__device__ __forceinline__ void hs_keylist_walk(int lane, uint32_t first, uint32_t end, const unsigned long long *__restrict__ list_sig,
+                                                const uint32_t *__restrict__ list_image, unsigned long long sig, int threshold, unsigned long long ff,
+                                                unsigned long long *__restrict__ row)
+{
+   for (uint32_t p = first + (uint32_t)lane; p < end; p += 64u)
+      if (__popcll(sig ^ list_sig[p]) <= threshold) atomicAdd(&row[list_image[p]], ff);
 }
 
 // One wavefront per query key; dot zeroed, head->nq2 zero on entry, tfq filled by k_query_count.  Grid: ceil(n / 4) blocks of 256.
@@ -181,10 +192,9 @@ __global__ __launch_bounds__(256) void k_query_score_embedded(const int32_t *__r
    uint32_t t = 0;
    if (lane == 0) t = atomicExch(&tfq[w], 0u);
    const unsigned long long f = idf[w];
-   if (lane == 0 && t != 0u) atomicAdd(&head->nq2, ((unsigned long long)t * f) * ((unsigned long long)t * f));   // (t idf)^2 < 2^62
+   if (lane == 0 && t != 0u) hs_query_norm_add(&head->nq2, t, f);
    if (f == 0ull) return;   // a word of every image weighs nothing: its list, one of the longest, is not walked
-   const unsigned long long sig = sigs[j], ff = f * f;   // < 2^26
+   const unsigned long long sig = sigs[j];
    const uint32_t end = offsets[w + 1];
-   for (uint32_t p = offsets[w] + (uint32_t)lane; p < end; p += 64u)
-      if (__popcll(sig ^ list_sig[p]) <= threshold) atomicAdd(&dot[list_image[p]], ff);
+   hs_keylist_walk(lane, offsets[w], end, list_sig, list_image, sig, threshold, f * f, dot);   // idf^2 < 2^26
 }

@@ -7,7 +7,7 @@
 // (image, word, tf) that results does not depend on the order of arrival; the slot layout does and is never output.  k_index_df adds
 // one to df[word] per occupied slot, k_index_idf turns df into idf (ilog2_q8), exclusive_scan (pipeline.hip) turns df into the list
 // offsets, and k_index_postings - the second pass over the table - writes every slot's (image, tf) to the next free place of its
-// word's list and adds (tf idf)^2 to norm2[image].  The order of the postings inside a list depends on which wave came first; only
+// word's list and adds (tf idf)^2 to norm2[image]; an add (kernels_index_grow.h) runs the same kernel behind the old postings.  The order of the postings inside a list depends on which wave came first; only
 // sums over a list are ever output.
 //
 // Query.  k_query_count adds the query's keys into tfq[word].  k_query_score runs one wavefront per query KEY: lane 0 exchanges
@@ -86,21 +86,30 @@ __global__ __launch_bounds__(256) void k_index_idf(const uint32_t *__restrict__ 
    if (w < k) idf[w] = hesaff_plan::index_idf((uint64_t)n_images, df[w]);
 }
 
-// cursor[k]: each list's first position (a copy of the offsets) on entry, its end afterwards.  norm2 zeroed by the caller.
+// (tf idf)^2 into norm2[image]: the one spelling of a posting's weight in its image's norm (the scatter below, and the merge and the
+// load of kernels_index_grow.h)
+__device__ __forceinline__ void hs_index_norm_add(unsigned long long *__restrict__ norm2, uint32_t image, uint32_t tf, uint32_t idf)
+{
+   const unsigned long long wt = (unsigned long long)tf * idf;   // < 2^31
+   if (wt) atomicAdd(&norm2[image], wt * wt);
+}
+
+// Every slot's (image, tf) to the next free place of its word's list, the table's images numbered from `base` (a build: 0, an add:
+// the images of the index so far).  cursor[k]: each list's next free position on entry - a copy of the offsets, or behind the old
+// postings (k_index_merge) - its end afterwards.  norm2 is added to.  Grid-stride over the slots.
 __global__ __launch_bounds__(256) void k_index_postings(const unsigned long long *__restrict__ hash_keys, const uint32_t *__restrict__ hash_tf,
-                                                        unsigned long long slots, const uint32_t *__restrict__ idf, uint32_t *__restrict__ cursor,
-                                                        IndexPosting *__restrict__ lists, unsigned long long *__restrict__ norm2)
+                                                        unsigned long long slots, uint32_t base, const uint32_t *__restrict__ idf,
+                                                        uint32_t *__restrict__ cursor, IndexPosting *__restrict__ lists, unsigned long long *__restrict__ norm2)
 {
    for (unsigned long long s = (unsigned long long)blockIdx.x * 256 + threadIdx.x; s < slots; s += (unsigned long long)gridDim.x * 256) {
       const unsigned long long key = hash_keys[s];
       if (key == hesaff_plan::HS_INDEX_EMPTY) continue;
-      const uint32_t word = hesaff_plan::index_key_word(key), image = hesaff_plan::index_key_image(key), tf = hash_tf[s];
+      const uint32_t word = hesaff_plan::index_key_word(key), image = base + hesaff_plan::index_key_image(key), tf = hash_tf[s];
       const uint32_t pos = atomicAdd(&cursor[word], 1u);
       IndexPosting p;
       p.image = image; p.tf = tf;
       lists[pos] = p;
-      const unsigned long long wt = (unsigned long long)tf * idf[word];   // < 2^31
-      if (wt) atomicAdd(&norm2[image], wt * wt);
+      hs_index_norm_add(norm2, image, tf, idf[word]);
    }
 }
 
@@ -109,6 +118,24 @@ __global__ __launch_bounds__(256) void k_query_count(const int32_t *__restrict__
 {
    const int j = (int)(blockIdx.x * 256u + threadIdx.x);
    if (j < n) atomicAdd(&tfq[words[(size_t)j * word_stride]], 1u);
+}
+
+// (t idf)^2 into a query's squared norm, by one lane of the one wave that holds the word's count t (k_query_score* here, in
+// kernels_embed.h and in kernels_index_batch.h)
+__device__ __forceinline__ void hs_query_norm_add(unsigned long long *__restrict__ nq2, uint32_t t, unsigned long long f)
+{
+   atomicAdd(nq2, ((unsigned long long)t * f) * ((unsigned long long)t * f));   // (t idf)^2 < 2^62
+}
+
+// A wave's walk of one word's postings lists[first .. end), its lanes striding them: tff tf = t tf idf^2 into row[image] (the dot
+// of the query, or the query's row of a chunk's)
+__device__ __forceinline__ void hs_posting_walk(int lane, uint32_t first, uint32_t end, const IndexPosting *__restrict__ lists, unsigned long long tff,
+                                                unsigned long long *__restrict__ row)
+{
+   for (uint32_t p = first + (uint32_t)lane; p < end; p += 64u) {
+      const IndexPosting e = lists[p];
+      atomicAdd(&row[e.image], tff * e.tf);   // < 2^62
+   }
 }
 
 // One wavefront per query key; dot zeroed, head->nq2 zero on entry.  Grid: ceil(n / 4) blocks of 256.
@@ -127,14 +154,10 @@ __global__ __launch_bounds__(256) void k_query_score(const int32_t *__restrict__
    t = (uint32_t)__shfl((int)t, 0, 64);
    if (t == 0u) return;
    const unsigned long long f = idf[w];
-   if (lane == 0) atomicAdd(&head->nq2, ((unsigned long long)t * f) * ((unsigned long long)t * f));   // (t idf)^2 < 2^62
+   if (lane == 0) hs_query_norm_add(&head->nq2, t, f);
    if (f == 0ull) return;   // a word of every image weighs nothing: its list, one of the longest, is not walked
-   const unsigned long long tff = (unsigned long long)t * f * f;   // < 2^44
    const uint32_t end = offsets[w + 1];
-   for (uint32_t p = offsets[w] + (uint32_t)lane; p < end; p += 64u) {
-      const IndexPosting e = lists[p];
-      atomicAdd(&dot[e.image], tff * e.tf);   // < 2^62
-   }
+   hs_posting_walk(lane, offsets[w], end, lists, (unsigned long long)t * f * f, dot);   // t idf^2 < 2^44
 }
 
 // the score of one image: the three binary64 operations of the definition (k_query_finish, and k_query_finish_batch of

@@ -20,7 +20,8 @@
 #include <stdint.h>
 
 #include "index_batch_plan.h"
-#include "kernels_index.h"
+#include "kernels_index.h"   // hs_index_image_of, hs_query_norm_add, hs_posting_walk, the score and the selection
+#include "kernels_embed.h"   // hs_keylist_walk
 
 // the slot of a key that the insert has put into the table, or `slots` where the probe meets an empty slot first (never, behind
 // k_index_insert over the same words; the walk ends either way)
@@ -59,15 +60,10 @@ __global__ __launch_bounds__(256) void k_query_score_batch(const int32_t *__rest
    t = (uint32_t)__shfl((int)t, 0, 64);
    if (t == 0u) return;
    const unsigned long long f = idf[w];
-   if (lane == 0) atomicAdd(&heads[q].nq2, ((unsigned long long)t * f) * ((unsigned long long)t * f));   // (t idf)^2 < 2^62
+   if (lane == 0) hs_query_norm_add(&heads[q].nq2, t, f);
    if (f == 0ull) return;   // a word of every image weighs nothing: its list is not walked
-   const unsigned long long tff = (unsigned long long)t * f * f;   // < 2^44
-   unsigned long long *__restrict__ row = dot + (size_t)q * (size_t)n_images;
    const uint32_t end = offsets[w + 1];
-   for (uint32_t p = offsets[w] + (uint32_t)lane; p < end; p += 64u) {
-      const IndexPosting e = lists[p];
-      atomicAdd(&row[e.image], tff * e.tf);   // < 2^62
-   }
+   hs_posting_walk(lane, offsets[w], end, lists, (unsigned long long)t * f * f, dot + (size_t)q * (size_t)n_images);   // t idf^2 < 2^44
 }
 
 // The same over the key lists of an embedded index: sigs[j] is key j's signature.  Grid: ceil(total / 4) blocks of 256.
@@ -88,14 +84,12 @@ __global__ __launch_bounds__(256) void k_query_score_embedded_batch(const int32_
       uint32_t t = 0;
       const unsigned long long slot = hs_batch_find_slot(hash_keys, bits, hesaff_plan::index_key(q, (uint32_t)w));
       if (slot < (1ull << bits)) t = atomicExch(&hash_tf[slot], 0u);
-      if (t != 0u) atomicAdd(&heads[q].nq2, ((unsigned long long)t * f) * ((unsigned long long)t * f));   // (t idf)^2 < 2^62
+      if (t != 0u) hs_query_norm_add(&heads[q].nq2, t, f);
    }
    if (f == 0ull) return;
-   const unsigned long long sig = sigs[j], ff = f * f;   // < 2^26
-   unsigned long long *__restrict__ row = dot + (size_t)q * (size_t)n_images;
+   const unsigned long long sig = sigs[j];
    const uint32_t end = offsets[w + 1];
-   for (uint32_t p = offsets[w] + (uint32_t)lane; p < end; p += 64u)
-      if (__popcll(sig ^ list_sig[p]) <= threshold) atomicAdd(&row[list_image[p]], ff);
+   hs_keylist_walk(lane, offsets[w], end, list_sig, list_image, sig, threshold, f * f, dot + (size_t)q * (size_t)n_images);   // idf^2 < 2^26
 }
 
 // score[q][i] over the b x n_images pairs of the chunk.  Grid-stride.

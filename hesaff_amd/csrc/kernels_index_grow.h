@@ -1,6 +1,7 @@
 // kernels_index_grow.h -- growing and reloading the image index (hesaff_index_add*, hesaff_index_load of include/hesaff_amd.h), beside
 // the build's kernels in kernels_index.h and kernels_embed.h, which run here unchanged wherever their contract fits: k_index_insert
-// and k_index_df over a hash table sized for the NEW keys alone, k_index_idf, exclusive_scan, k_word_histogram.
+// and k_index_df over a hash table sized for the NEW keys alone, k_index_idf, exclusive_scan, k_word_histogram, and the two scatters
+// with the old images as their base.  What is here is what only a grown or a loaded index needs: the merges, the lengths, the load.
 //
 // Add.  df_new = df_old + (one per new distinct (image, word)); idf and the offsets follow from df_new and N + m.  Every list keeps
 // its old entries in front: k_index_merge moves old posting r of word w from old_off[w] + r to new_off[w] + r.  The shift
@@ -12,13 +13,14 @@
 // was chosen over a wave per word because the list lengths are Zipf-distributed: most words hold fewer postings than a wave has
 // lanes, and the few that hold millions would each be one wave's work.  The same pass adds (tf idf_new)^2 to norm2[image] - every idf
 // changes with N, so every old norm is summed again, with the integer atomic of the build - and its first K threads leave
-// cursor[w] = new_off[w] + df_old[w].  k_index_postings_based then scatters the new table's slots behind the cursors, its images
-// numbered from the base N.  k_keylist_merge and k_keylist_scatter_based do the same for the (image, signature) lists of an embedded
-// index.  As everywhere in the index, sums are integers and the order inside a list is no part of any result.
+// cursor[w] = new_off[w] + df_old[w].  The build's k_index_postings (kernels_index.h) then scatters the new table's slots behind the
+// cursors, its images numbered from the base N.  k_keylist_merge and the build's k_keylist_scatter (kernels_embed.h) do the same for
+// the (image, signature) lists of an embedded index.  As everywhere in the index, sums are integers and the order inside a list is no
+// part of any result.
 //
 // Load.  k_index_load_postings is the one pass over the postings of an index file: it finds each position's word as the merge does,
-// checks the entry, and sums norm2 (hs_index_norm_add: the merge's arithmetic), tf per image and tf per word.  k_index_load_sums
-// then checks the sums.  A violated rule sets its bit in *flags (index_plan.h: HS_LOAD_*); nothing is written outside the arrays of
+// checks the entry, and sums norm2 (hs_index_norm_add of kernels_index.h: the build's arithmetic), tf per image and tf per word.
+// k_index_load_sums then checks the sums.  A violated rule sets its bit in *flags (index_plan.h: HS_LOAD_*); nothing is written outside the arrays of
 // the index under construction: an image or a key image outside 0 .. N - 1 is flagged and not used as an address.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -26,16 +28,8 @@
 
 #include "index_plan.h"
 #include "kernels_index.h"
-#include "kernels_train.h"   // hs_claim_per_word
 
 #define HS_GROW_TILE 1024   // positions per block of 256: four per thread
-
-// (tf idf)^2 into norm2[image]: the arithmetic of k_index_postings, shared by the merge and the load
-__device__ __forceinline__ void hs_index_norm_add(unsigned long long *__restrict__ norm2, uint32_t image, uint32_t tf, uint32_t idf)
-{
-   const unsigned long long wt = (unsigned long long)tf * idf;   // < 2^31
-   if (wt) atomicAdd(&norm2[image], wt * wt);
-}
 
 // the word w with off[w] <= p < off[w + 1], searched between lo and hi where off[lo] <= p < off[hi]
 __device__ __forceinline__ uint32_t hs_word_between(const uint32_t *__restrict__ off, uint32_t lo, uint32_t hi, uint32_t p)
@@ -89,39 +83,6 @@ __global__ __launch_bounds__(256) void k_keylist_merge(const uint32_t *__restric
       const uint32_t to = new_off[w] + (p - old_off[w]);
       new_sig[to] = old_sig[p];
       new_image[to] = old_image[p];
-   }
-}
-
-// k_index_postings with the table's images numbered from `base`: cursor[k] is each list's next free position on entry (k_index_merge),
-// its end afterwards; norm2 is added to.
-__global__ __launch_bounds__(256) void k_index_postings_based(const unsigned long long *__restrict__ hash_keys, const uint32_t *__restrict__ hash_tf,
-                                                              unsigned long long slots, uint32_t base, const uint32_t *__restrict__ idf,
-                                                              uint32_t *__restrict__ cursor, IndexPosting *__restrict__ lists, unsigned long long *__restrict__ norm2)
-{
-   for (unsigned long long s = (unsigned long long)blockIdx.x * 256 + threadIdx.x; s < slots; s += (unsigned long long)gridDim.x * 256) {
-      const unsigned long long key = hash_keys[s];
-      if (key == hesaff_plan::HS_INDEX_EMPTY) continue;
-      const uint32_t word = hesaff_plan::index_key_word(key), image = base + hesaff_plan::index_key_image(key), tf = hash_tf[s];
-      const uint32_t pos = atomicAdd(&cursor[word], 1u);
-      IndexPosting p;
-      p.image = image; p.tf = tf;
-      lists[pos] = p;
-      hs_index_norm_add(norm2, image, tf, idf[word]);
-   }
-}
-
-// k_keylist_scatter with the images numbered from `base`.  Grid: ceil(total / 256) blocks.
-__global__ __launch_bounds__(256) void k_keylist_scatter_based(const int32_t *__restrict__ words, int word_stride, const unsigned long long *__restrict__ sigs,
-                                                               const uint32_t *__restrict__ starts, int n_images, uint32_t total, uint32_t base,
-                                                               uint32_t *__restrict__ cursor, unsigned long long *__restrict__ list_sig, uint32_t *__restrict__ list_image)
-{
-   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
-   const bool live = j < total;
-   const int w = live ? words[(size_t)j * word_stride] : -1;
-   const uint32_t pos = hs_claim_per_word(cursor, w, live);
-   if (live) {
-      list_sig[pos] = sigs[j];
-      list_image[pos] = base + hs_index_image_of(starts, n_images, j);
    }
 }
 

@@ -1,6 +1,7 @@
 // index_plan_check.cpp -- the host arithmetic of the image index (hesaff_amd/csrc/index_plan.h) on the CPU: the bounds of a build and
 // of a query, the integer logarithm behind idf with its intermediate products checked in 128 bits, the worst-case sums, the size rule
-// of the hash table, and the layouts of the persistent arrays and of the build's scratch.
+// of the hash table, the packing of host words and the key starts of a build, an add and a batch's chunk, and the layouts of the
+// persistent arrays and of the build's scratch.
 // tests/test_image_index_host.py builds it with AddressSanitizer + UBSan and runs it.
 #include <cmath>
 #include <cstdio>
@@ -120,6 +121,60 @@ static void check_hash()
    }
 }
 
+// index_stage_words: the packing of host words at strides 1, 2 and 3, n = 0, k = 1, and the first and the last word out of range on
+// either side.  The source arrays are exactly as long as the walk (1 + (n - 1) stride words), so the sanitizer sees a read past it.
+static void check_stage_words()
+{
+   const int k = 7;
+   for (int stride : {1, 2, 3})
+      for (int n : {0, 1, 2, 5}) {
+         std::vector<int32_t> src(n ? (size_t)(1 + (n - 1) * stride) : 0, -99);   // (the gaps hold a word that would be refused)
+         std::vector<int32_t> want((size_t)n), out(3, 42);
+         for (int j = 0; j < n; j++) src[(size_t)(j * stride)] = want[(size_t)j] = (j * 3 + n) % k;
+         CHECK(index_stage_words(src.data(), stride, n, k, out) && out == want, "stride %d, n %d: the words packed in order", stride, n);
+         if (n == 0) continue;
+         for (int at : {0, n - 1})
+            for (int32_t bad : {-1, k, INT32_MIN, INT32_MAX}) {
+               std::vector<int32_t> s2 = src;
+               s2[(size_t)(at * stride)] = bad;
+               CHECK(!index_stage_words(s2.data(), stride, n, k, out), "stride %d, n %d: word %d = %d is refused", stride, n, at, bad);
+            }
+         std::vector<int32_t> edge = src;
+         edge[0] = 0;
+         edge[(size_t)((n - 1) * stride)] = k - 1;
+         CHECK(index_stage_words(edge.data(), stride, n, k, out) && out[0] == (n == 1 ? k - 1 : 0) && out[(size_t)n - 1] == k - 1, "stride %d, n %d: 0 and k - 1 pass", stride, n);
+      }
+   std::vector<int32_t> out;
+   const int32_t zeros[3] = {0, 0, 0}, one[3] = {0, 1, 0};
+   CHECK(index_stage_words(zeros, 1, 3, 1, out) && out == std::vector<int32_t>(3, 0), "k = 1: the word 0 alone");
+   CHECK(!index_stage_words(one, 1, 3, 1, out), "k = 1: the word 1 is refused");
+   CHECK(index_stage_words(nullptr, 2, 0, 1, out) && out.empty(), "n = 0 reads nothing");
+}
+
+// index_starts: the exclusive prefix sums with the total at the end; zero counts in front, inside and at the end repeat a start;
+// n = 0 is the single 0; a total of exactly UINT32_MAX is what it is (the function bounds nothing: index_total_keys does, far below)
+static void check_starts()
+{
+   const int32_t counts[8] = {0, 0, 3, 0, 4, 1, 0, 0};
+   std::vector<uint32_t> s(9, 77u);
+   index_starts(counts, 8, s.data());
+   CHECK(s == std::vector<uint32_t>({0, 0, 0, 3, 3, 7, 8, 8, 8}), "leading, inner and trailing zeros");
+   std::vector<uint32_t> one(1, 77u);
+   index_starts(nullptr, 0, one.data());
+   CHECK(one[0] == 0u, "n = 0: one start");
+   std::vector<uint32_t> part(4, 77u);   // (a window of the counts, as a chunk of a batch takes them)
+   index_starts(counts + 2, 3, part.data());
+   CHECK(part == std::vector<uint32_t>({0, 3, 3, 7}), "a window starts at 0 again");
+   const int32_t big[3] = {INT32_MAX, INT32_MAX, 1};   // 2 (2^31 - 1) + 1 = 2^32 - 1
+   std::vector<uint32_t> b(4);
+   index_starts(big, 3, b.data());
+   CHECK(b[1] == (uint32_t)INT32_MAX && b[2] == 0xfffffffeu && b[3] == UINT32_MAX, "a total of 2^32 - 1 is exact");
+   std::vector<int32_t> full(1024, (int32_t)1 << 18);   // the largest build: 2^28 keys
+   std::vector<uint32_t> f(1025);
+   index_starts(full.data(), 1024, f.data());
+   CHECK(f[1024] == ((uint32_t)1 << 28) && (int64_t)f[1024] == index_total_keys(full.data(), 1024), "the largest build's total");
+}
+
 struct Extent { const char *name; size_t off, bytes; };
 
 static void check_layout(const std::vector<Extent> &e, size_t total, const char *what)
@@ -160,6 +215,8 @@ int main()
    check_ilog2();
    check_sums();
    check_hash();
+   check_stage_words();
+   check_starts();
    for (int64_t n : {(int64_t)1, (int64_t)3, (int64_t)257, (int64_t)1 << 20})
       for (int64_t k : {(int64_t)1, (int64_t)33, (int64_t)4099, (int64_t)1 << 20})
          for (int64_t t : {(int64_t)0, (int64_t)1, (int64_t)513, (int64_t)1 << 28}) check_arrays(n, k, t);

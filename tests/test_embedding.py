@@ -416,6 +416,74 @@ def test_embedded_query_threshold_is_inclusive(ectx):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("stride", [1, 2])
+@pytest.mark.parametrize("device", [False, True])
+def test_embedded_build_and_query_forms_at_one_small_shape(ectx, device, stride):
+    """hesaff_index_build_embedded[_device] and hesaff_index_query_embedded[_device] at word_stride 1 and 2: 3 images over K = 5 with
+    the middle one empty, a query with repeats and a query of 0 words; a whole build of 0 words; and the first or the last word at
+    -1 or K, refused under the entry point's own name with the index left as it was.  Everything here is host plumbing and per-key
+    device code with no tile size in it, so the shape is small."""
+    import torch
+    K = 5
+    words = [np.array([0, 3, 3, 4, 1, 0, 3], np.int32), np.zeros(0, np.int32), np.array([4, 2], np.int32)]
+    sigs = [np.array([1, 2, 3, 0xFF, 5, 1, 7], np.uint64), np.zeros(0, np.uint64), np.array([0xF0, 9], np.uint64)]
+    rows = (lambda w: np.stack([w, np.full(len(w), -7, np.int32)], axis=1)) if stride == 2 else (lambda w: w)
+
+    def on_device(a):
+        t = torch.from_numpy(np.ascontiguousarray(a) if a.size else np.zeros(2, a.dtype)).cuda()
+        torch.cuda.synchronize()
+        return t
+
+    def build(ws, gs):
+        if device:
+            tw, ts = on_device(np.concatenate([rows(w) for w in ws])), on_device(np.concatenate(gs).view(np.int64))
+            ectx.build_embedded_index_device(tw.data_ptr(), ts.data_ptr(), [len(w) for w in ws], stride, K)
+        else:
+            ectx.build_embedded_index([rows(w) for w in ws], gs, K)
+
+    def query(qw, qs, T, top):
+        if device:
+            tw, ts = on_device(rows(qw)), on_device(qs.view(np.int64))
+            return ectx.query_embedded_index_device(tw.data_ptr(), ts.data_ptr(), len(qw), stride, T, top)
+        return ectx.query_index(rows(qw), top, signatures=qs, hamming=T)
+
+    def check(ws, gs, what):
+        ref = R.build(ws, K)
+        df, idf, norm2 = ectx.index_tables()
+        assert np.array_equal(df, ref[1]) and np.array_equal(idf, ref[2]) and np.array_equal(norm2, ref[3]), what
+        assert ectx.index_info == (3, K, sum(len(w) for w in ws), int(ref[1].sum())), what
+        offsets, images, lsigs = ectx.index_embedded()
+        assert np.array_equal(offsets, np.concatenate([[0], np.cumsum(np.bincount(np.concatenate(ws), minlength=K))])), what
+        for w in range(K):
+            got = sorted(zip(images[offsets[w]:offsets[w + 1]].tolist(), lsigs[offsets[w]:offsets[w + 1]].tolist()))
+            assert got == sorted((i, int(g)) for i, (a, b) in enumerate(zip(ws, gs)) for x, g in zip(a, b) if x == w), (what, w)
+        for qw, qs in ((np.array([3, 0, 3, 4], np.int32), np.array([3, 1, 6, 0xF1], np.uint64)), (np.zeros(0, np.int32), np.zeros(0, np.uint64))):
+            for T in (0, 1, 64):
+                want = E.query(ref, ws, gs, qw, qs, T, 3)
+                im, sc = query(qw, qs, T, 3)
+                dot, score, nq2 = ectx.index_scores()
+                assert nq2 == want[4] and np.array_equal(dot, want[2]) and np.array_equal(_bits(score), _bits(want[3])), (what, len(qw), T)
+                assert im.tolist() == want[0].tolist() and np.array_equal(_bits(sc), _bits(want[1])), (what, len(qw), T)
+
+    what = "device %s, stride %d" % (device, stride)
+    build([w[:0] for w in words], [g[:0] for g in sigs])
+    check([w[:0] for w in words], [g[:0] for g in sigs], what + ", no word at all")
+    build(words, sigs)
+    check(words, sigs, what)
+    suffix = "_device" if device else ""
+    for at, w in ((0, -1), (0, K), (-1, -1), (-1, K)):
+        bad = [a.copy() for a in words]
+        bad[0 if at == 0 else 2][at] = w
+        bad_query = np.array([3, 0, 4], np.int32)
+        bad_query[at] = w
+        with pytest.raises(hesaff_amd.HesaffError, match=r"hesaff_index_build_embedded%s: a word lies outside 0 \.\. vocabulary_size - 1$" % suffix):
+            build(bad, sigs)
+        with pytest.raises(hesaff_amd.HesaffError, match=r"hesaff_index_query_embedded%s: a word lies outside 0 \.\. vocabulary_size - 1$" % suffix):
+            query(bad_query, np.array([3, 1, 0xF1], np.uint64), 8, 2)
+    check(words, sigs, what + ", after the refusals")
+
+
+@pytest.mark.gpu
 def test_refusals_leave_the_index_the_vocabulary_and_the_embedding(ectx, collection):
     words, sigs, ref, base = collection
     L, h = ectx.L, ectx.h

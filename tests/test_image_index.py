@@ -132,6 +132,48 @@ def test_build_shapes(ictx, K):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("stride", [1, 2])
+@pytest.mark.parametrize("device", [False, True])
+def test_build_and_query_forms_at_one_small_shape(ictx, device, stride):
+    """hesaff_index_build[_device] and hesaff_index_query[_device] at word_stride 1 and 2: 3 images over K = 5 with the middle one
+    empty, a query with repeats and a query of 0 words; a whole build of 0 words; and the first or the last word at -1 or K, refused
+    under the entry point's own name with the index left as it was.  Everything here is host plumbing and per-key device code with
+    no tile size in it, so the shape is small."""
+    import torch
+    K = 5
+    images = [np.array([0, 3, 3, 4, 1, 0, 3], np.int32), np.zeros(0, np.int32), np.array([4, 2], np.int32)]
+    rows = (lambda w: np.stack([w, np.full(len(w), -7, np.int32)], axis=1)) if stride == 2 else (lambda w: w)
+    what = "device %s, stride %d" % (device, stride)
+    _check_build(ictx, [np.zeros(0, np.int32)] * 3, K, what + ", no word at all", device=device, stride=stride)
+    assert ictx.index_info == (3, K, 0, 0)
+    _check_query(ictx, R.build([[], [], []], K), rows(np.array([1, 1, 4], np.int32)), 2, what + ", against the empty index", device=device)
+    ref = _check_build(ictx, images, K, what, device=device, stride=stride)
+    for q, top in ((np.array([3, 0, 3, 4], np.int32), 3), (np.zeros(0, np.int32), 2)):
+        _check_query(ictx, ref, rows(q), top, what + ", query of %d words" % len(q), device=device)
+    suffix = "_device" if device else ""
+    for at, w in ((0, -1), (0, K), (-1, -1), (-1, K)):
+        bad_images = [a.copy() for a in images]
+        bad_images[0 if at == 0 else 2][at] = w
+        bad_query = np.array([3, 0, 4], np.int32)
+        bad_query[at] = w
+        with pytest.raises(hesaff_amd.HesaffError, match=r"hesaff_index_build%s: a word lies outside 0 \.\. vocabulary_size - 1$" % suffix):
+            if device:
+                t = torch.from_numpy(np.ascontiguousarray(np.concatenate([rows(a) for a in bad_images]))).cuda()
+                torch.cuda.synchronize()
+                ictx.build_index_device(t.data_ptr(), [len(a) for a in bad_images], stride, K)
+            else:
+                ictx.build_index([rows(a) for a in bad_images], K)
+        with pytest.raises(hesaff_amd.HesaffError, match=r"hesaff_index_query%s: a word lies outside 0 \.\. vocabulary_size - 1$" % suffix):
+            if device:
+                t = torch.from_numpy(np.ascontiguousarray(rows(bad_query))).cuda()
+                torch.cuda.synchronize()
+                ictx.query_index_device(t.data_ptr(), len(bad_query), stride, 2)
+            else:
+                ictx.query_index(rows(bad_query), 2)
+    _check_tables(ictx, ref, images, K, what + ", after the refusals")
+
+
+@pytest.mark.gpu
 def test_build_word_patterns(ictx):
     """all 4099 keys of an image in one word (one slot takes every atomic); every key a different word; a word in every image
     (idf 0) beside a word in exactly one; 257 images of one key each; a second build replacing the first"""

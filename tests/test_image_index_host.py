@@ -62,7 +62,9 @@ def test_reference_against_a_dense_computation():
 
 def test_index_plan_arithmetic(tmp_path):
     """tests/native/index_plan_check.cpp: every bound on both sides, ilog2_q8 with its products checked in 128 bits, the worst-case
-    sums, the hash size rule at T = 1, 511, 512, 513 and 2^28, the layouts disjoint and aligned, the working set of the largest case"""
+    sums, the hash size rule at T = 1, 511, 512, 513 and 2^28, the layouts disjoint and aligned, the working set of the largest case;
+    index_stage_words at strides 1 .. 3, n = 0, k = 1 and a first or last word of -1 or k; index_starts with zero counts in front,
+    inside and behind, n = 0, and a total of exactly 2^32 - 1"""
     if shutil.which("g++") is None:
         pytest.skip("g++ not available")
     exe = str(tmp_path / "index_plan_check")

@@ -206,6 +206,42 @@ def test_batch_shapes(bctx, K):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("stride", [1, 2])
+@pytest.mark.parametrize("device", [False, True])
+@pytest.mark.parametrize("embedded", [False, True])
+def test_batch_forms_at_one_small_shape(bctx, embedded, device, stride):
+    """hesaff_index_query_batch[_embedded][_device] at word_stride 1 and 2 over 3 images and K = 5: a batch of 3 queries with the
+    middle one empty, a batch of queries that hold no word at all, and the first or the last word at -1 or K, refused under the
+    entry point's own name with the last query's scores left as they were.  Everything here is host plumbing and per-key device
+    code with no tile size in it, so the shape is small."""
+    bctx.set_index_batch_budget(0)
+    K, T = 5, 24 if embedded else None
+    images = [np.array([0, 3, 3, 4, 1, 0, 3], np.int32), np.zeros(0, np.int32), np.array([4, 2], np.int32)]
+    isigs = [np.array([1, 2, 3, 0xFF, 5, 1, 7], np.uint64), np.zeros(0, np.uint64), np.array([0xF0, 9], np.uint64)]
+    queries = [np.array([3, 0, 3, 4], np.int32), np.zeros(0, np.int32), np.array([2, 4, 4], np.int32)]
+    qsigs = [np.array([3, 1, 6, 0xF1], np.uint64), np.zeros(0, np.uint64), np.array([9, 0xF0, 0xF0F0F0], np.uint64)]
+    bctx.build_index(images, K, signatures=isigs if embedded else None)
+    ref = R.build(images, K)
+    how = dict(device=device, stride=stride, sigs=qsigs if embedded else None, T=T)
+    what = "embedded %s, device %s, stride %d" % (embedded, device, stride)
+    refs = [E.query(ref, images, isigs, q, g, T, 3) if embedded else R.query(ref, q, 3) for q, g in zip(queries, qsigs)]
+    im, sc = _check_batch(bctx, queries, 2, what, refs=refs, n_images=3, **how)
+    assert im[1].tolist() == [0, 1] and (sc[1] == 0.0).all(), (what, "the query of 0 words")
+    none = dict(how, sigs=[g[:0] for g in qsigs] if embedded else None)
+    im, sc = _check_batch(bctx, [q[:0] for q in queries], 2, what + ", no word at all", **none)
+    assert im.tolist() == [[0, 1]] * 3 and (sc == 0.0).all(), (what, "a batch of 0 words")
+    state = bctx.index_scores()
+    name = "hesaff_index_query_batch%s%s" % ("_embedded" if embedded else "", "_device" if device else "")
+    for at, w in ((0, -1), (0, K), (-1, -1), (-1, K)):
+        bad = [q.copy() for q in queries]
+        bad[0 if at == 0 else 2][at] = w
+        with pytest.raises(hesaff_amd.HesaffError, match=name + r": a word lies outside 0 \.\. vocabulary_size - 1$"):
+            _run_batch(bctx, bad, 2, **how)
+    assert _same_scores(bctx.index_scores(), state), (what, "after the refusals")
+    _check_batch(bctx, queries, 2, what + ", after the refusals", refs=refs, n_images=3, **how)
+
+
+@pytest.mark.gpu
 def test_batch_word_patterns(bctx):
     """a word of every image (idf 0) beside a word of one image; words with df = 0; every query word distinct"""
     bctx.set_index_batch_budget(0)

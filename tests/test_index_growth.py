@@ -160,6 +160,78 @@ def test_add_against_rebuild(gctx, K):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("stride", [1, 2])
+@pytest.mark.parametrize("device", [False, True])
+@pytest.mark.parametrize("embedded", [False, True])
+def test_add_forms_at_one_small_shape(gctx, embedded, device, stride):
+    """hesaff_index_add[_embedded][_device] at word_stride 1 and 2 behind a build of 2 images over K = 5: an add of 3 images with
+    the middle one empty, an add of images that hold no word at all, and the first or the last word at -1 or K, refused under the
+    entry point's own name with the index left as it was.  Everything here is host plumbing and per-key device code with no tile
+    size in it, so the shape is small."""
+    import torch
+    K = 5
+    old = _i32([[1, 1, 4], [0]])
+    new = _i32([[0, 3, 3, 4, 1, 0, 3], [], [4, 2]])
+    rows = (lambda w: np.stack([w, np.full(len(w), -7, np.int32)], axis=1)) if stride == 2 else (lambda w: w)
+
+    def add(ws, gs):
+        if not device:
+            gctx.add_to_index([rows(w) for w in ws], signatures=gs)
+            return
+        flat = np.concatenate([rows(w) for w in ws])
+        tw = torch.from_numpy(np.ascontiguousarray(flat) if flat.size else np.zeros(2, np.int32)).cuda()
+        ts = None if gs is None else torch.from_numpy(np.concatenate(list(gs) + [np.zeros(1, np.uint64)]).view(np.int64)).cuda()
+        torch.cuda.synchronize()
+        gctx.add_to_index_device(tw.data_ptr(), [len(w) for w in ws], stride, sigs_ptr=None if ts is None else ts.data_ptr())
+
+    def sigs_of(ws, seed):
+        return [_sig_for(w, seed) for w in ws] if embedded else None
+    what = "embedded %s, device %s, stride %d" % (embedded, device, stride)
+    old_sigs, new_sigs = sigs_of(old, 1), sigs_of(new, 2)
+    gctx.build_index(old, K, signatures=old_sigs)
+    none = [w[:0] for w in new]
+    add(none, sigs_of(none, 3))
+    images, sigs = old + none, old_sigs + sigs_of(none, 3) if embedded else None
+    _check_index(gctx, images, K, what + ", an add of no word at all", sigs)
+    add(new, new_sigs)
+    images, sigs = images + new, sigs + new_sigs if embedded else None
+    ref = _check_index(gctx, images, K, what, sigs)
+    q = np.array([3, 0, 3, 4], np.int32)
+    _check_query(gctx, ref, images, q, 8, what)
+    if embedded:
+        _check_query(gctx, ref, images, q, 8, what + ", T = 24", sigs, _sig_for(q, 5), 24)
+    name = "hesaff_index_add%s%s" % ("_embedded" if embedded else "", "_device" if device else "")
+    for at, w in ((0, -1), (0, K), (-1, -1), (-1, K)):
+        bad = [a.copy() for a in new]
+        bad[0 if at == 0 else 2][at] = w
+        with pytest.raises(hesaff_amd.HesaffError, match=name + r": a word lies outside 0 \.\. vocabulary_size - 1$"):
+            add(bad, new_sigs)
+    _check_index(gctx, images, K, what + ", after the refusals", sigs, ref)
+
+
+@pytest.mark.gpu
+def test_embedded_add_equals_the_embedded_build_of_all_images(gctx):
+    """an embedded build of 4 images and an embedded add of 2 against ONE embedded build of the 6, both on the device: the key lists
+    (hesaff_index_get_embedded) and the postings (hesaff_index_get_postings) are equal as multisets per word, the offsets and the
+    tables as arrays.  K = 9; word 7 is in no old image, word 2 in no new one, word 8 in none."""
+    K = 9
+    old = _i32([[0, 1, 1, 2, 6], [2, 2, 3], [], [4, 5, 0, 0, 2, 6]])
+    new = _i32([[7, 7, 0, 1, 3], [4, 7, 5, 5, 6]])
+    assert 7 not in np.concatenate(old) and 2 not in np.concatenate(new) and 8 not in np.concatenate(old + new)
+    old_sigs, new_sigs = [_sig_for(w, 1) for w in old], [_sig_for(w, 2) for w in new]
+
+    def lists():
+        return [a.tobytes() for a in gctx.index_tables()] + [a.tobytes() for a in _sorted_lists(*gctx.index_postings())] + \
+               [a.tobytes() for a in _sorted_lists(*gctx.index_embedded())] + [gctx.index_postings()[0].tobytes(), gctx.index_embedded()[0].tobytes()]
+    gctx.build_index(old + new, K, signatures=old_sigs + new_sigs)
+    whole, info = lists(), gctx.index_info
+    gctx.build_index(old, K, signatures=old_sigs)
+    gctx.add_to_index(new, signatures=new_sigs)
+    assert lists() == whole and gctx.index_info == info
+    _check_index(gctx, old + new, K, "4 + 2 images", old_sigs + new_sigs)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("K,most", [(1, 3), (33, 40), (300, 40), (5000, 12)])
 def test_add_over_many_tiles(gctx, K, most):
     """2500 old images and 600 new ones: the merge runs over many tiles of 1024 positions - one list through all of them (K = 1), a few

@@ -282,7 +282,7 @@ int hesaff_stage_find_affine_shape(hesaff_ctx *c, const float *blur, int rows, i
    a.upload(a_kp, kp);
    AffineOut ao; ao.converged = a.ptr(a_conv); ao.iters = a.ptr(a_iters); ao.U = a.ptr(a_U);
    DPlane P = make_plane(a.ptr(a_plane), rows, cols, cols);
-   hipLaunchKernelGGL(k_affine_stage, dim3(std::min((n + HS_AFFP_G - 1) / HS_AFFP_G, 256 * 6)), dim3(64), 0, c->stream(), P, (const float *)a.ptr(a_kp), n, c->tables.view, c->ct.consts, ao);
+   hipLaunchKernelGGL(k_affine_stage, dim3(std::min((n + HS_AFF_SLOTS - 1) / HS_AFF_SLOTS, 256 * 6)), dim3(64), 0, c->stream(), P, (const float *)a.ptr(a_kp), n, c->tables.view, c->ct.consts, ao);
    if (converged) a.download(converged, a_conv);
    if (iters) a.download(iters, a_iters);
    if (U) a.download(U, a_U);

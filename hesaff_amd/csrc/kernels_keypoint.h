@@ -43,22 +43,10 @@ struct KpTables {   // device tables built on the host once per context
 // k_affine: AffineShape::findAffineShape affine.cpp:35-100.
 //  per iteration: 361 bilinear taps -> LDS img; gradients and the three products per pixel ->
 //  LDS; three lanes add the 361 terms of a,b,c in index order; one lane runs the
-//  double-precision invSqrt and the U update; result broadcast through LDS.
+//  double-precision invSqrt and the U update.
 // ---------------------------------------------------------------------------------------
 // (AffineOut: device_lists.h)
 
-// ---------------------------------------------------------------------------------------
-// hs_affine_groups: the same iteration with FOUR keypoints per wavefront (16 lanes each).
-// Per iteration a keypoint needs 361 parallel taps + products, then three 361-term sequential
-// sums and one double-precision invSqrt.  With one keypoint per wavefront the sums keep 3 lanes
-// busy and the invSqrt one lane; with four keypoints side by side those serial stretches are
-// shared by four (12 and 4 lanes busy) and the wavefront executes ~2.3x fewer instructions per
-// keypoint.  The 16-lane groups are persistent: a group whose keypoint converged (or was
-// rejected) takes the next keypoint at the end of the round, so keypoints with different
-// iteration counts do not wait for each other.
-// block = 64 threads (one wavefront), LDS 4 x 3 x 364 floats + mask (19 KB).
-// ---------------------------------------------------------------------------------------
-#define HS_AFF_G 4
 // interpolate()'s return flag ("some tap fell outside the image", helpers.cpp:209-244) for the P x P window of
 // normalizeAffine's smoothing branch (affine.cpp:126), without visiting the P^2 taps.  The tap coordinate
 //    w(j, i) = fl(fl(ofs + fl(j * a_row)) + fl(i * a_col))        j, i in [-half, half]
@@ -81,15 +69,40 @@ __device__ inline bool hs_window_outside(int imRows, int imCols, float ofsx, flo
    return outside;
 }
 
-#define HS_AFF_NT 23    // ceil(361 / 16)
-// the parity kernel's own grouping: four keypoints per wavefront, 16 lanes each (two keypoints of 32 lanes would halve the LDS per
-// wavefront and double the wavefronts per CU, but the serial sums and the double-precision tail would then serve two keypoints instead of four)
+// ---------------------------------------------------------------------------------------
+// hs_affine_groups: the same iteration with SIXTEEN persistent keypoint slots per wavefront.
+// Per iteration a keypoint needs 361 parallel taps + products, then three 361-term sequential
+// sums and one double-precision invSqrt.  A round of the wavefront serves every active slot once:
+//   * four batches q = 0..3.  In batch q the four 16-lane groups serve slots 4q .. 4q+3: corner test, taps (the untested
+//     variant when the windows of all the batch's active slots are inside), gradients and products, and the three sums in
+//     index order on 12 lanes, which leave a, b, c in s_abc[slot].  Every batch uses the same s_arr; a batch none of whose
+//     slots is active is skipped.
+//   * one tail: lane s < 16 owns slot s.  It runs invSqrt, the U update and the convergence logic on s_abc[s], so the
+//     double-precision stretch is executed once per round for sixteen keypoints.  The slot's iteration state (keypoint
+//     index, iteration count, U, both eigen ratios) lives in that lane's registers; a slot whose keypoint converged or was
+//     rejected stores the result and takes the block's next keypoint there, so keypoints with different iteration counts
+//     do not wait for each other.
+// What the sampling lanes need of a slot (plane, extent, position, ratio, U, active flag) is published by the tail lane in
+// the slot's LDS record and read by the slot's group at the start of its batch.  An inactive slot's record holds no valid
+// plane pointer: its group neither samples nor sums.
+// Every keypoint goes through the operations of the single-keypoint form on the same operands in the same order.
+// block = 64 threads (one wavefront), LDS 4 x 3 x 364 floats + mask + 16 records + s_abc (19.5 KB: eight blocks per CU).
+// ---------------------------------------------------------------------------------------
+#define HS_AFF_SLOTS 16   // keypoints a wavefront iterates on at a time; the launch sites size their grids by it
+// consecutive keypoints a block takes from the list at a time.  Alone on the device, per 32 UHD images: 16 -> 22.1 ms, 4 -> 19.2 ms,
+// 1 -> 18.2 ms (the four-group form: 21.1 ms).  All blocks of a launch are resident, so the launch lasts as long as its largest share.
+#define HS_AFF_ITEM 1
+// a batch: four keypoints side by side, 16 lanes each (two keypoints of 32 lanes would halve the LDS per wavefront and double
+// the wavefronts per CU, but the serial sums would then serve two keypoints instead of four)
 #define HS_AFFP_G 4
 #define HS_AFFP_L (64 / HS_AFFP_G)
 #define HS_AFFP_SH 4    // log2(HS_AFFP_L)
 #define HS_AFFP_NT ((HS_SMM_PIX + HS_AFFP_L - 1) / HS_AFFP_L)
 #define HS_AFF_BATCHES 2
 #define HS_AFF_ARR 364  // 361 rounded up to a multiple of 4 floats
+// a slot's record, 32-bit words
+enum { HS_AFR_PTR_LO, HS_AFR_PTR_HI, HS_AFR_PITCH, HS_AFR_WIDTH, HS_AFR_HEIGHT, HS_AFR_LX, HS_AFR_LY, HS_AFR_RATIO,
+       HS_AFR_U11, HS_AFR_U12, HS_AFR_U21, HS_AFR_U22, HS_AFR_ACTIVE, HS_AFR_WORDS };
 
 struct AffKp { const float *blur; int rows, cols, pitch; float x, y, s, pd; };
 
@@ -99,147 +112,178 @@ __device__ __forceinline__ void hs_affine_groups(uint32_t first, uint32_t n, con
 {
    __shared__ __attribute__((aligned(16))) float s_arr[HS_AFFP_G][3][HS_AFF_ARR];   // img, then a terms | b terms | c terms
    __shared__ float s_mask[HS_AFF_ARR];
-   __shared__ float s_bc[HS_AFFP_G][8];
+   __shared__ float s_abc[HS_AFF_SLOTS][3];
+   __shared__ uint32_t s_slot[HS_AFF_SLOTS][HS_AFR_WORDS];
    const int lane = threadIdx.x, grp = lane >> HS_AFFP_SH, li = lane & (HS_AFFP_L - 1);
+   const bool tail_lane = lane < HS_AFF_SLOTS;   // lane s owns slot s
    for (int i = lane; i < HS_SMM_PIX; i += 64) s_mask[i] = mask_g[i];
    float *s_img = s_arr[grp][0], *s_pa = s_arr[grp][0], *s_pb = s_arr[grp][1], *s_pc = s_arr[grp][2];   // the a terms replace the image
+   // A block walks the list in items of HS_AFF_ITEM consecutive keypoints at the block's stride.  Position p of its walk is
+   // keypoint p % HS_AFF_ITEM of its item p / HS_AFF_ITEM; the slots start on positions 0..15, and a slot that finishes takes
+   // the next position no slot has taken yet, so the slots of a block run dry together however unevenly the iteration
+   // counts fall.  (With a fixed stride per slot a block waits for its unluckiest slot with most batches a quarter full:
+   // 26.2 ms against the four-group form's 21.3 ms per 32 UHD images.)
    // XCD-aware order: block b runs on XCD b % 8 (observed dispatch order, a speed assumption only).  The keypoints are
    // ordered by image, octave, level and raster position, so neighbours in the list sample the same cache lines of the
    // same plane: each XCD takes one contiguous eighth of the list, its blocks stride inside that eighth, and those lines
    // are fetched into ONE private L2 instead of eight.  (Grids that are not a multiple of 8 blocks keep the plain stride.)
-   uint32_t hstep = gridDim.x * HS_AFFP_G, h_end = n;
-   uint32_t h = first + blockIdx.x * HS_AFFP_G + grp;
+   uint32_t hstep = gridDim.x * HS_AFF_ITEM, h_end = n;
+   uint32_t h0 = first + blockIdx.x * HS_AFF_ITEM;   // the block's first item
    if ((gridDim.x & 7u) == 0u && n > first) {
-      const uint32_t n_items = (n - first + HS_AFFP_G - 1) / HS_AFFP_G;   // groups of HS_AFFP_G keypoints
+      const uint32_t n_items = (n - first + HS_AFF_ITEM - 1) / HS_AFF_ITEM;
       const uint32_t xcd = blockIdx.x & 7u, rank = blockIdx.x >> 3, per_xcd = gridDim.x >> 3;
       const uint32_t it_lo = (uint32_t)(((unsigned long long)n_items * xcd) >> 3), it_hi = (uint32_t)(((unsigned long long)n_items * (xcd + 1)) >> 3);
-      hstep = per_xcd * HS_AFFP_G;
-      h_end = min(first + it_hi * HS_AFFP_G, n);
-      h = first + (it_lo + rank) * HS_AFFP_G + grp;
+      hstep = per_xcd * HS_AFF_ITEM;
+      h_end = min(first + it_hi * HS_AFF_ITEM, n);
+      h0 = first + (it_lo + rank) * HS_AFF_ITEM;
    }
-#define HS_AFF_END h_end
+   auto walk = [&](uint32_t p) { return h0 + (p / HS_AFF_ITEM) * hstep + (p % HS_AFF_ITEM); };
+   uint32_t h = walk((uint32_t)lane);
+   uint32_t next_p = HS_AFF_SLOTS;   // first position of the block's walk that no slot has taken (wave-uniform)
    if (k.maxIterations <= 0) {   // no iteration: U = identity, not converged
-      for (; h < HS_AFF_END; h += hstep)
-         if (li == 0) {
+      if (lane < HS_AFF_ITEM)
+         for (; h < h_end; h += hstep) {
             out.converged[h] = 0; out.iters[h] = 0;
             out.U[4 * h + 0] = 1.0f; out.U[4 * h + 1] = 0.0f; out.U[4 * h + 2] = 0.0f; out.U[4 * h + 3] = 1.0f;
          }
       return;
    }
-   // per-group state, replicated in the group's 16 lanes
-   const float *blur = nullptr;
-   int pitch = 0, width = 0, height = 0, l = 0;
-   float lx = 0, ly = 0, ratio = 0, u11 = 1.0f, u12 = 0.0f, u21 = 0.0f, u22 = 1.0f;
-   float eigen_ratio_act = 0.0f, eigen_ratio_bef = 0.0f;   // used by lane li == 0
-   bool active = h < HS_AFF_END;
+   // the slot's iteration state, in its tail lane (the other lanes stay inactive and hold nothing)
+   int l = 0;
+   float u11 = 1.0f, u12 = 0.0f, u21 = 0.0f, u22 = 1.0f;
+   float eigen_ratio_act = 0.0f, eigen_ratio_bef = 0.0f;
+   bool active = tail_lane && h < h_end;
+   // the slot takes keypoint h (or goes idle): the tail lane resets its state and publishes the record
    auto load_kp = [&]() {
+      uint32_t *rec = s_slot[lane];
+      rec[HS_AFR_ACTIVE] = active ? 1u : 0u;
       if (active) {
          const AffKp q = fetch(h);
-         blur = q.blur; pitch = q.pitch; width = q.cols - 1; height = q.rows - 1;
-         lx = q.x / q.pd; ly = q.y / q.pd;
-         ratio = q.s / (k.affInitialSigma * q.pd);
+         const unsigned long long pa = reinterpret_cast<unsigned long long>(q.blur);
+         rec[HS_AFR_PTR_LO] = (uint32_t)pa; rec[HS_AFR_PTR_HI] = (uint32_t)(pa >> 32);
+         rec[HS_AFR_PITCH] = (uint32_t)q.pitch; rec[HS_AFR_WIDTH] = (uint32_t)(q.cols - 1); rec[HS_AFR_HEIGHT] = (uint32_t)(q.rows - 1);
+         rec[HS_AFR_LX] = __float_as_uint(q.x / q.pd); rec[HS_AFR_LY] = __float_as_uint(q.y / q.pd);
+         rec[HS_AFR_RATIO] = __float_as_uint(q.s / (k.affInitialSigma * q.pd));
          u11 = 1.0f; u12 = 0.0f; u21 = 0.0f; u22 = 1.0f;
+         rec[HS_AFR_U11] = __float_as_uint(u11); rec[HS_AFR_U12] = __float_as_uint(u12);
+         rec[HS_AFR_U21] = __float_as_uint(u21); rec[HS_AFR_U22] = __float_as_uint(u22);
          eigen_ratio_act = 0.0f; eigen_ratio_bef = 0.0f;
          l = 0;
       }
    };
-   load_kp();
+   if (tail_lane) load_kp();
    HS_WAVE_LDS_SYNC();
    while (__ballot(active) != 0ull) {
-      bool win_in = true;
-      if (active) {
-         const float a11 = u11 * ratio, a12 = u12 * ratio, a21 = u21 * ratio, a22 = u22 * ratio;
-         // interpolate(), helpers.cpp:209-244 (return value ignored at affine.cpp:47): 23 taps per lane in two batches.
-         // The tap coordinates are monotone in i and in j (hs_window_outside): when the four corners of the 19 x 19 grid
-         // are inside the level, every tap is, and the taps need no bounds test, no selects and only 32-bit offsets;
-         // a window that touches the border (a few per cent) keeps the tested tap, which zeroes what lies outside.
-         win_in = !hs_window_outside(height + 1, width + 1, lx, ly, a11, a12, a21, a22, HS_SMM >> 1);
-      }
-      // one decision per wavefront (a branch per group would split the batches of gathers): the untested taps when the
-      // windows of all its active keypoints are inside, the tested ones for everybody otherwise
-      const bool all_in = __ballot(active && !win_in) == 0ull;
-      auto sample = [&](auto inside_c) {
-         constexpr bool INSIDE = decltype(inside_c)::value;
-         const float a11 = u11 * ratio, a12 = u12 * ratio, a21 = u21 * ratio, a22 = u22 * ratio;
+#pragma unroll 1
+      for (int q = 0; q < HS_AFF_SLOTS / HS_AFFP_G; q++) {
+         const int slot = q * HS_AFFP_G + grp;
+         const uint32_t *rec = s_slot[slot];
+         const bool act = rec[HS_AFR_ACTIVE] != 0u;   // this group's slot iterates in this round
+         if (__ballot(act) == 0ull) continue;
+         // the slot's record, replicated in the group's 16 lanes (an inactive slot's is stale: read, never used)
+         // (rebuilt as a pointer into global memory: from a bare integer the taps would become flat loads, which also wait on the LDS counter)
+         typedef const __attribute__((address_space(1))) float *hs_gptr;
+         const float *blur = (const float *)(hs_gptr)(((unsigned long long)rec[HS_AFR_PTR_HI] << 32) | rec[HS_AFR_PTR_LO]);
+         const int pitch = (int)rec[HS_AFR_PITCH], width = (int)rec[HS_AFR_WIDTH], height = (int)rec[HS_AFR_HEIGHT];
+         const float lx = __uint_as_float(rec[HS_AFR_LX]), ly = __uint_as_float(rec[HS_AFR_LY]), ratio = __uint_as_float(rec[HS_AFR_RATIO]);
+         const float su11 = __uint_as_float(rec[HS_AFR_U11]), su12 = __uint_as_float(rec[HS_AFR_U12]);
+         const float su21 = __uint_as_float(rec[HS_AFR_U21]), su22 = __uint_as_float(rec[HS_AFR_U22]);
+         bool win_in = true;
+         if (act) {
+            const float a11 = su11 * ratio, a12 = su12 * ratio, a21 = su21 * ratio, a22 = su22 * ratio;
+            // interpolate(), helpers.cpp:209-244 (return value ignored at affine.cpp:47): 23 taps per lane in two batches.
+            // The tap coordinates are monotone in i and in j (hs_window_outside): when the four corners of the 19 x 19 grid
+            // are inside the level, every tap is, and the taps need no bounds test, no selects and only 32-bit offsets;
+            // a window that touches the border (a few per cent) keeps the tested tap, which zeroes what lies outside.
+            win_in = !hs_window_outside(height + 1, width + 1, lx, ly, a11, a12, a21, a22, HS_SMM >> 1);
+         }
+         // one decision per batch (a branch per group would split the batches of gathers): the untested taps when the
+         // windows of all its active slots are inside, the tested ones for everybody otherwise
+         const bool all_in = __ballot(act && !win_in) == 0ull;
+         auto sample = [&](auto inside_c) {
+            constexpr bool INSIDE = decltype(inside_c)::value;
+            const float a11 = su11 * ratio, a12 = su12 * ratio, a21 = su21 * ratio, a22 = su22 * ratio;
 #pragma unroll
-         for (int half = 0; half < HS_AFF_BATCHES; half++) {
-            constexpr int NB = (HS_AFFP_NT + HS_AFF_BATCHES - 1) / HS_AFF_BATCHES;
-            float sv[NB];
+            for (int half = 0; half < HS_AFF_BATCHES; half++) {
+               constexpr int NB = (HS_AFFP_NT + HS_AFF_BATCHES - 1) / HS_AFF_BATCHES;
+               float sv[NB];
 #pragma unroll
-            for (int t = 0; t < NB; t++) {
-               const int idx = min(li + HS_AFFP_L * (half * NB + t), HS_SMM_PIX - 1);
-               const int jj = idx / HS_SMM, ii = idx - jj * HS_SMM;
-               const int j = jj - (HS_SMM >> 1), i = ii - (HS_SMM >> 1);
-               const float rx = lx + (float)j * a12;
-               const float ry = ly + (float)j * a22;
-               const float wx = rx + (float)i * a11;
-               const float wy = ry + (float)i * a21;
-               if (INSIDE) {
-                  sv[t] = hs_tap_inside_ptr(blur, pitch, wx, wy);
-               } else {
-                  bool outside = false;
-                  sv[t] = hs_bilinear(blur, pitch, width, height, wx, wy, outside);
+               for (int t = 0; t < NB; t++) {
+                  const int idx = min(li + HS_AFFP_L * (half * NB + t), HS_SMM_PIX - 1);
+                  const int jj = idx / HS_SMM, ii = idx - jj * HS_SMM;
+                  const int j = jj - (HS_SMM >> 1), i = ii - (HS_SMM >> 1);
+                  const float rx = lx + (float)j * a12;
+                  const float ry = ly + (float)j * a22;
+                  const float wx = rx + (float)i * a11;
+                  const float wy = ry + (float)i * a21;
+                  if (INSIDE) {
+                     sv[t] = hs_tap_inside_ptr(blur, pitch, wx, wy);
+                  } else {
+                     bool outside = false;
+                     sv[t] = hs_bilinear(blur, pitch, width, height, wx, wy, outside);
+                  }
+               }
+#pragma unroll
+               for (int t = 0; t < NB; t++) HS_KEEP(sv[t]);
+#pragma unroll
+               for (int t = 0; t < NB; t++) {
+                  const int idx = li + HS_AFFP_L * (half * NB + t);
+                  if (idx < HS_SMM_PIX) s_img[idx] = sv[t];
                }
             }
-#pragma unroll
-            for (int t = 0; t < NB; t++) HS_KEEP(sv[t]);
-#pragma unroll
-            for (int t = 0; t < NB; t++) {
-               const int idx = li + HS_AFFP_L * (half * NB + t);
-               if (idx < HS_SMM_PIX) s_img[idx] = sv[t];
-            }
+         };
+         if (act) {
+            if (all_in) sample(std::true_type{});
+            else sample(std::false_type{});
          }
-      };
-      if (active) {
-         if (all_in) sample(std::true_type{});
-         else sample(std::false_type{});
-      }
-      HS_WAVE_LDS_SYNC();
-      if (active) {
-         // computeGradient affine.cpp:14-33 + products affine.cpp:62-68.  The a terms take the place of
-         // the sampled image in LDS, so they wait in registers until every lane has read its neighbours.
-         float pa[HS_AFFP_NT];
+         HS_WAVE_LDS_SYNC();
+         if (act) {
+            // computeGradient affine.cpp:14-33 + products affine.cpp:62-68.  The a terms take the place of
+            // the sampled image in LDS, so they wait in registers until every lane has read its neighbours.
+            float pa[HS_AFFP_NT];
 #pragma unroll
-         for (int t = 0; t < HS_AFFP_NT; t++) {
-            const int idx = min(li + HS_AFFP_L * t, HS_SMM_PIX - 1);
-            const int r = idx / HS_SMM, c = idx - r * HS_SMM;
-            // hs_grad with clamped neighbour indices (one-sided differences at the tile border)
-            const float gxx = s_img[idx + (c < HS_SMM - 1 ? 1 : 0)] - s_img[idx - (c > 0 ? 1 : 0)];
-            const float gyy = s_img[idx + (r < HS_SMM - 1 ? HS_SMM : 0)] - s_img[idx - (r > 0 ? HS_SMM : 0)];
-            const float v = s_mask[idx];
-            const float gxy = gxx * gyy;
-            pa[t] = gxx * gxx * v;
-            if (li + HS_AFFP_L * t < HS_SMM_PIX) {
-               s_pb[idx] = gxy * v;
-               s_pc[idx] = gyy * gyy * v;
+            for (int t = 0; t < HS_AFFP_NT; t++) {
+               const int idx = min(li + HS_AFFP_L * t, HS_SMM_PIX - 1);
+               const int r = idx / HS_SMM, c = idx - r * HS_SMM;
+               // hs_grad with clamped neighbour indices (one-sided differences at the tile border)
+               const float gxx = s_img[idx + (c < HS_SMM - 1 ? 1 : 0)] - s_img[idx - (c > 0 ? 1 : 0)];
+               const float gyy = s_img[idx + (r < HS_SMM - 1 ? HS_SMM : 0)] - s_img[idx - (r > 0 ? HS_SMM : 0)];
+               const float v = s_mask[idx];
+               const float gxy = gxx * gyy;
+               pa[t] = gxx * gxx * v;
+               if (li + HS_AFFP_L * t < HS_SMM_PIX) {
+                  s_pb[idx] = gxy * v;
+                  s_pc[idx] = gyy * gyy * v;
+               }
+            }
+            HS_WAVE_LDS_SYNC();
+#pragma unroll
+            for (int t = 0; t < HS_AFFP_NT; t++) {
+               const int idx = li + HS_AFFP_L * t;
+               if (idx < HS_SMM_PIX) s_pa[idx] = pa[t];
             }
          }
          HS_WAVE_LDS_SYNC();
+         if (act && li < 3) {
+            // 361 terms in index order (affine.cpp:57-68); float4 LDS reads, the adds stay sequential
+            const float *pp = s_arr[grp][li];
+            const float4 *p4 = reinterpret_cast<const float4 *>(pp);
+            float acc = 0.0f;
+            for (int i0 = 0; i0 < HS_SMM_PIX / 4; i0 += 10) {   // 90 = 9 x 10 float4, ten reads in flight
+               float4 q4[10];
 #pragma unroll
-         for (int t = 0; t < HS_AFFP_NT; t++) {
-            const int idx = li + HS_AFFP_L * t;
-            if (idx < HS_SMM_PIX) s_pa[idx] = pa[t];
+               for (int u = 0; u < 10; u++) q4[u] = p4[i0 + u];
+#pragma unroll
+               for (int u = 0; u < 10; u++) { acc += q4[u].x; acc += q4[u].y; acc += q4[u].z; acc += q4[u].w; }
+            }
+            acc += pp[HS_SMM_PIX - 1];   // 361 = 4 * 90 + 1
+            s_abc[slot][li] = acc / (float)HS_SMM_PIX;
          }
+         HS_WAVE_LDS_SYNC();   // the next batch's taps overwrite the terms; the tail reads s_abc
       }
-      HS_WAVE_LDS_SYNC();
-      if (active && li < 3) {
-         // 361 terms in index order (affine.cpp:57-68); float4 LDS reads, the adds stay sequential
-         const float *pp = s_arr[grp][li];
-         const float4 *p4 = reinterpret_cast<const float4 *>(pp);
-         float acc = 0.0f;
-         for (int i0 = 0; i0 < HS_SMM_PIX / 4; i0 += 10) {   // 90 = 9 x 10 float4, ten reads in flight
-            float4 q[10];
-#pragma unroll
-            for (int u = 0; u < 10; u++) q[u] = p4[i0 + u];
-#pragma unroll
-            for (int u = 0; u < 10; u++) { acc += q[u].x; acc += q[u].y; acc += q[u].z; acc += q[u].w; }
-         }
-         acc += pp[HS_SMM_PIX - 1];   // 361 = 4 * 90 + 1
-         s_bc[grp][li] = acc / (float)HS_SMM_PIX;
-      }
-      HS_WAVE_LDS_SYNC();
-      if (active && li == 0) {
-         float a = s_bc[grp][0], b = s_bc[grp][1], c = s_bc[grp][2];
+      bool finished = false;
+      if (active) {   // the tail: one lane per active slot
+         float a = s_abc[lane][0], b = s_abc[lane][1], c = s_abc[lane][2];
          float l1, l2;
          hs_inv_sqrt(a, b, c, l1, l2);
          eigen_ratio_bef = eigen_ratio_act;
@@ -251,31 +295,32 @@ __device__ __forceinline__ void hs_affine_groups(uint32_t first, uint32_t n, con
          if (!hs_eigenvalues(n11, n12, n21, n22, l1, l2)) state = 1;
          else if ((l1 / l2 > 6) || (l2 / l1 > 6)) state = 1;
          else if (eigen_ratio_act < k.convergenceThreshold && eigen_ratio_bef < k.convergenceThreshold) state = 2;
-         s_bc[grp][3] = n11; s_bc[grp][4] = n12; s_bc[grp][5] = n21; s_bc[grp][6] = n22;
-         s_bc[grp][7] = __int_as_float(state);
-      }
-      HS_WAVE_LDS_SYNC();
-      if (active) {
-         u11 = s_bc[grp][3]; u12 = s_bc[grp][4]; u21 = s_bc[grp][5]; u22 = s_bc[grp][6];
-         const int state = __float_as_int(s_bc[grp][7]);
+         u11 = n11; u12 = n12; u21 = n21; u22 = n22;
          if (state != 0 || l + 1 >= k.maxIterations) {
             // affine.cpp:88-99: converged -> onAffineShapeFound(..., l); otherwise the keypoint is dropped
-            if (li == 0) {
-               out.converged[h] = (state == 2) ? 1 : 0;
-               out.iters[h] = (state == 2) ? l : 0;
-               out.U[4 * h + 0] = u11; out.U[4 * h + 1] = u12; out.U[4 * h + 2] = u21; out.U[4 * h + 3] = u22;
-            }
-            h += hstep;
-            active = h < HS_AFF_END;
-            load_kp();
+            out.converged[h] = (state == 2) ? 1 : 0;
+            out.iters[h] = (state == 2) ? l : 0;
+            out.U[4 * h + 0] = u11; out.U[4 * h + 1] = u12; out.U[4 * h + 2] = u21; out.U[4 * h + 3] = u22;
+            finished = true;
          } else {
+            uint32_t *rec = s_slot[lane];
+            rec[HS_AFR_U11] = __float_as_uint(u11); rec[HS_AFR_U12] = __float_as_uint(u12);
+            rec[HS_AFR_U21] = __float_as_uint(u21); rec[HS_AFR_U22] = __float_as_uint(u22);
             l++;
          }
       }
+      // the finished slots take the next positions of the block's walk, in slot order
+      const unsigned long long fin = __ballot(finished);
+      if (finished) {
+         const uint32_t p = next_p + (uint32_t)__popcll(fin & ((1ull << lane) - 1ull));
+         h = walk(p);
+         active = h < h_end;
+         load_kp();
+      }
+      next_p += (uint32_t)__popcll(fin);
       HS_WAVE_LDS_SYNC();
    }
 }
-
 
 __global__ __launch_bounds__(64) void k_affine(PlaneTab pt, HessList hl, uint32_t h_lo, uint32_t h_hi, const uint32_t *__restrict__ n_ptr,
                                                KpTables tb, DConsts k, AffineOut out)

@@ -1254,7 +1254,7 @@ struct GroupDevice : ScheduleDevice {
    void affine(int g, sched::Stream as)
    {
       const int ta = tm.begin(T_AFF, 0, stream(as));
-      const uint32_t agrid = std::min<uint32_t>((groups[g].hi - groups[g].lo + HS_AFFP_G - 1) / HS_AFFP_G, (uint32_t)c->n_cu * HS_AFF_BLOCKS_PER_CU);
+      const uint32_t agrid = std::min<uint32_t>((groups[g].hi - groups[g].lo + HS_AFF_SLOTS - 1) / HS_AFF_SLOTS, (uint32_t)c->n_cu * HS_AFF_BLOCKS_PER_CU);
       hipLaunchKernelGGL(k_affine, dim3(agrid), dim3(64), 0, stream(as), pt, s.hl, groups[g].lo, groups[g].hi, (const uint32_t *)&s.counters->head.hess_total,
                          c->tables.view, c->ct.consts, s.ao);
       tm.end(ta);

@@ -43,6 +43,7 @@ from ._binding import (  # noqa: F401
     write_vocabulary_cells,
     read_words,
     write_words,
+    expand_rows,
     EMBED_BITS,
     embedding_projection,
     read_embedding,

@@ -270,6 +270,13 @@ def load_library():
         L.hesaff_set_vocabulary_probes.argtypes = [vp, C.c_int]
         L.hesaff_get_vocabulary_probes.argtypes = [vp, C.POINTER(C.c_int)]
         L.hesaff_stage_probe_cells.argtypes = [vp, C.c_int, vp, vp, vp]
+    if hasattr(L, "hesaff_set_vocabulary_neighbours"):   # (likewise)
+        L.hesaff_set_vocabulary_neighbours.argtypes = [vp, C.c_int]
+        L.hesaff_get_vocabulary_neighbours.argtypes = [vp, C.POINTER(C.c_int)]
+        L.hesaff_get_neighbours.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.hesaff_get_neighbours_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+        L.hesaff_assign_neighbours_device.argtypes = [vp, C.c_int64, vp, C.c_int64, C.c_int64, vp]
+        L.hesaff_stage_assign_neighbours.argtypes = [vp, C.c_int, vp, vp]
     if hasattr(L, "hesaff_index_build"):   # (likewise)
         L.hesaff_index_build.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int]
         L.hesaff_index_build_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int]
@@ -393,6 +400,8 @@ ABI_SYMBOLS = [
     "hesaff_index_save", "hesaff_index_load", "hesaff_get_index_growth_ms", "hesaff_write_index_file", "hesaff_read_index_file",
     "hesaff_index_query_batch", "hesaff_index_query_batch_device", "hesaff_index_query_batch_embedded", "hesaff_index_query_batch_embedded_device",
     "hesaff_index_set_batch_budget", "hesaff_index_get_batch_budget", "hesaff_index_get_batch_chunks", "hesaff_get_index_batch_ms",
+    "hesaff_set_vocabulary_neighbours", "hesaff_get_vocabulary_neighbours", "hesaff_get_neighbours", "hesaff_get_neighbours_device",
+    "hesaff_assign_neighbours_device", "hesaff_stage_assign_neighbours",
 ]
 
 # hesaff_set_output_format's bits
@@ -645,6 +654,30 @@ def read_words(path):
     if len(body) != n * WORDS_ROW_DTYPE.itemsize:
         raise HesaffError(-4, "%s is truncated" % path)
     return vocabulary_size, np.frombuffer(body, dtype=WORDS_ROW_DTYPE).copy()
+
+
+def expand_rows(rows, neighbours, signatures=None):
+    """The rows a words file holds under a neighbour count R > 1 (hesaff_set_vocabulary_neighbours), built in numpy: for every key in
+    key order one row per present rank in ascending rank - the key's five floats, that rank's word; a rank with word -1 (fewer than R
+    rows in the vocabulary) gives no row.  rows: WORDS_ROW_DTYPE [n], one per key (their word column is not read); neighbours:
+    int32 [n, R, 2]; signatures: None, or uint64 [n, R], a signature per (key, rank).  -> the expanded rows, or (rows, signatures
+    row for row with them): what query_index and verify_matches take."""
+    rows = np.asarray(rows)
+    if rows.dtype != WORDS_ROW_DTYPE or rows.ndim != 1:
+        raise ValueError("rows are a 1-d array of WORDS_ROW_DTYPE (what read_words returns)")
+    neighbours = np.asarray(neighbours, dtype=np.int32)
+    if neighbours.ndim != 3 or neighbours.shape[0] != len(rows) or neighbours.shape[2] != 2:
+        raise ValueError("neighbours are an int32 array of shape [n, R, 2], a row per row of `rows`")
+    words = neighbours[:, :, 0]
+    key, rank = np.nonzero(words >= 0)   # (row-major: key order, ascending rank within a key)
+    out = rows[key].copy()
+    out["word"] = words[key, rank].astype(np.uint32)
+    if signatures is None:
+        return out
+    signatures = np.asarray(signatures, dtype=np.uint64)
+    if signatures.shape != words.shape:
+        raise ValueError("signatures are a uint64 array of shape [n, R], one per (key, rank)")
+    return out, np.ascontiguousarray(signatures[key, rank])
 
 
 EMBED_BITS = 64   # HESAFF_EMBED_BITS
@@ -1246,6 +1279,54 @@ class HesaffContext:
         ms = C.c_float()
         self._check(self.L.hesaff_get_assign_ms(self.h, C.byref(ms)))
         return ms.value
+
+    # ---- vocabulary neighbours (hesaff_set_vocabulary_neighbours, include/hesaff_amd.h) ----
+    def set_vocabulary_neighbours(self, neighbours):
+        """hesaff_set_vocabulary_neighbours: every key's R nearest rows of the vocabulary, not just the nearest (1..8, default 1).  With
+        R > 1 every call that assigns words also leaves neighbours(image), int32 [n, R, 2]; words(image) stays rank 0, byte for byte.
+        Does not combine with a cell layer."""
+        self._check(self.L.hesaff_set_vocabulary_neighbours(self.h, int(neighbours)))
+
+    def vocabulary_neighbours(self):
+        """hesaff_get_vocabulary_neighbours: the neighbour count that is set"""
+        r = C.c_int()
+        self._check(self.L.hesaff_get_vocabulary_neighbours(self.h, C.byref(r)))
+        return r.value
+
+    def neighbours(self, image):
+        """hesaff_get_neighbours: int32 [count, R, 2] = (word, dist2) per rank, row for row the keys of image `image` of the last host
+        call (a copy); a rank the vocabulary is too small for is (-1, 2^31 - 1)."""
+        p = C.c_void_p(); n = C.c_int(); r = C.c_int()
+        if self.L.hesaff_get_neighbours(self.h, int(image), C.byref(p), C.byref(n), C.byref(r)) != 0:
+            raise HesaffError(-1, "hesaff_get_neighbours(%d): no vocabulary is set, or no such image in the last host call" % image)
+        if n.value == 0:
+            return np.zeros((0, r.value, 2), np.int32)
+        return np.frombuffer((C.c_char * (n.value * r.value * 8)).from_address(p.value), dtype=np.int32).copy().reshape(n.value, r.value, 2)
+
+    def assign_neighbours(self, desc):
+        """hesaff_stage_assign_neighbours: desc uint8 [n, 128] -> int32 [n, R, 2] with the context's R (1 as well)."""
+        desc = np.ascontiguousarray(desc, dtype=np.uint8)
+        if desc.ndim != 2 or desc.shape[1] != 128:
+            raise ValueError("descriptors are a uint8 array of shape [n, 128]")
+        out = np.zeros((desc.shape[0], self.vocabulary_neighbours(), 2), np.int32)
+        rc = self.L.hesaff_stage_assign_neighbours(self.h, desc.shape[0], desc.ctypes.data if desc.shape[0] else None,
+                                                   out.ctypes.data if desc.shape[0] else None)
+        if rc != 0 and desc.shape[0] == 0:
+            raise HesaffError(rc, "hesaff_stage_assign_neighbours: no vocabulary is set")
+        self._check(rc)
+        return out
+
+    def assign_neighbours_device(self, ptr, n, stride, offset, out_ptr):
+        """hesaff_assign_neighbours_device: n descriptors in device memory, addressed as in assign_words_device -> n x R x 2 int32 at
+        out_ptr (raw device pointers)."""
+        self._check(self.L.hesaff_assign_neighbours_device(self.h, int(n), C.c_void_p(ptr), int(stride), int(offset), C.c_void_p(out_ptr)))
+
+    def neighbours_device(self):
+        """hesaff_get_neighbours_device: (device pointer, rows, R) of the int32 [total, R, 2] array the last assignment left."""
+        p = C.c_void_p(); tot = C.c_int64(); r = C.c_int()
+        if self.L.hesaff_get_neighbours_device(self.h, C.byref(p), C.byref(tot), C.byref(r)) != 0:
+            raise HesaffError(-1, "hesaff_get_neighbours_device: no vocabulary is set, or no assignment on the device was the last call")
+        return p.value, tot.value, r.value
 
     # ---- vocabulary training (hesaff_train_vocabulary, include/hesaff_amd.h) ----
     def _train(self, call, k, iterations, init):

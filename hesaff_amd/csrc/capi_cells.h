@@ -11,6 +11,8 @@ int hesaff_set_vocabulary_cells(hesaff_ctx *c, int cells, const uint8_t *coarse,
    if (!c || cells < 0 || c->vocab.k == 0 || cells > c->vocab.k) return HESAFF_ERR_ARG;
    if (cells > 0 && (!coarse || !cells_first_ok(first, cells, c->vocab.k))) return HESAFF_ERR_ARG;
    HS_API_BEGIN
+   if (cells > 0 && c->neighbours > 1)
+      throw HsError(HESAFF_ERR_ARG, "a cell layer and vocabulary neighbours (R > 1) do not combine: set hesaff_set_vocabulary_neighbours to 1 first; no layer is set");
    bind_device(c);
    hesaff_ctx::Cells &cl = c->cells;
    if (cells == 0) {

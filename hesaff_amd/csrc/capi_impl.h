@@ -97,9 +97,12 @@ void detect_device(hesaff_ctx *c, int n, const SrcImages &src, int height, int w
    c->sig_spans.clear();
    c->words_device_total = -1;
    c->sigs_device_total = -1;
+   c->neigh_spans.clear();
+   c->neigh_device_total = -1;
    const BatchResult r = run_batch(c, src, n, height, width, mk);
    const int32_t *hs = r.hessian_starts, *ds = r.desc_starts;
    if (c->vocab.k) { finish_stream(c); c->words_device_total = ds[n]; }   // the words of the batch are in b_words when the call returns
+   if (c->vocab.k && c->neighbours > 1) { c->neigh_device_total = ds[n]; c->neigh_device_r = c->neighbours; }   // ... the neighbours in b_neigh
    if (c->embed.set) c->sigs_device_total = ds[n];                        // ... and the signatures in b_sigs
    for (int b = 0; b < n; b++) {
       if (count_hessian) count_hessian[b] = hs[b + 1] - hs[b];
@@ -523,6 +526,11 @@ struct ChunkDevice {
       }
       if (wants & WANT_BIN) s.bin_at = place(n_rows * EX_BIN_ROW);
       if (wants & WANT_SIGS) s.sigs_at = place(n_rows * 8);
+      if (wants & WANT_NEIGH) s.neigh_at = place(n_rows * 8 * (size_t)c->neighbours);
+      if (wants & WANT_NSIGS) {   // the signatures of the ranks above 0 that every key has, a plane per rank (rank 0 is b_sigs)
+         s.nsigs_at = place(n_rows * 8 * (size_t)(c->neighbours - 1));
+         embed_batch_ranks(c, (long long)n_rows);
+      }
       if (times_export(s)) HIP_TRY(hipEventRecord(sl.ev_exp[1], c->stream()));
       s.bytes = at;
       dbg_t3 = Clock::now();
@@ -569,6 +577,10 @@ struct ChunkDevice {
             HIP_TRY(hipMemcpyAsync(stg + s.words_at, c->b_words.p, n_rows * 8, hipMemcpyDeviceToDevice, c->stream()));
          if ((wants & WANT_SIGS) && n_rows > 0)    // (b_sigs: written by k_embed_keys behind b_words, on this stream)
             HIP_TRY(hipMemcpyAsync(stg + s.sigs_at, c->b_sigs.p, n_rows * 8, hipMemcpyDeviceToDevice, c->stream()));
+         if ((wants & WANT_NEIGH) && n_rows > 0)   // (b_neigh: written by k_assign_neighbours with b_words, on this stream)
+            HIP_TRY(hipMemcpyAsync(stg + s.neigh_at, c->b_neigh.p, n_rows * 8 * (size_t)c->neighbours, hipMemcpyDeviceToDevice, c->stream()));
+         if ((wants & WANT_NSIGS) && n_rows > 0)   // (b_nsigs: written by embed_batch_ranks in compute(), on this stream)
+            HIP_TRY(hipMemcpyAsync(stg + s.nsigs_at, c->b_nsigs.p, n_rows * 8 * (size_t)(c->neighbours - 1), hipMemcpyDeviceToDevice, c->stream()));
          if (wants & WANT_REGIONS) pack_regions(c, (uint32_t)s.n_hess, B, (hesaff_region *)(stg + s.regions_at));
          if (times_export(s)) HIP_TRY(hipEventRecord(sl.ev_exp[2], c->stream()));
          if (wants & WANT_TEXT) export_text_write(c, d_keys, (uint32_t)n_rows, stg + s.text_at);
@@ -693,9 +705,17 @@ void detect_images(hesaff_ctx *c, int n, const void *images, bool f32, const int
    c->word_spans.clear();
    c->sig_spans.clear();
    c->sigs_device_total = -1;
+   c->neigh_spans.clear();
+   c->neigh_device_total = -1;
    if (c->vocab.k) {   // the words travel beside the keys (WANT_WORDS); hesaff_get_words finds them by the caller's image index
       c->word_spans.assign((size_t)n, WordSpan());
       io.word_spans = &c->word_spans;
+      if (c->neighbours > 1) {   // ... and so do the neighbours (WANT_NEIGH; hesaff_get_neighbours)
+         c->neigh_spans.assign((size_t)n, NeighSpan());
+         c->neigh_spans_r = c->neighbours;
+         io.neigh_spans = &c->neigh_spans;
+         io.neigh_r = c->neighbours;
+      }
       if (c->embed.set) {   // ... and so do the signatures (WANT_SIGS; hesaff_get_signatures)
          c->sig_spans.assign((size_t)n, SigSpan());
          io.sig_spans = &c->sig_spans;
@@ -703,6 +723,7 @@ void detect_images(hesaff_ctx *c, int n, const void *images, bool f32, const int
    }
    set_consumer(io);
    run_chunks(c, io, ring);
+   c->neigh_device_total = -1;   // (b_neigh holds the last chunk's rows only)
    if (io.sink_rc.load() != 0) throw HsError(HESAFF_ERR_IO, "the result sink reported an error");
 }
 
@@ -976,6 +997,8 @@ int hesaff_process_files(hesaff_ctx *c, int n, const char *const *paths, const c
    c->word_spans.clear();
    c->sig_spans.clear();
    c->sigs_device_total = -1;
+   c->neigh_spans.clear();
+   c->neigh_device_total = -1;
    for (int i = 0; i < n; i++) { status[i].rc = HESAFF_ERR_IO; status[i].stage = HESAFF_FILE_PENDING; status[i].count_hessian = 0; status[i].count_desc = 0; }
    hesaff_host_plan hp;
    (void)hesaff_host_plan_for(1, &hp);   // "0 = auto": this context has the host to itself (callers that share it pass the counts of their own plan)
@@ -992,6 +1015,7 @@ int hesaff_process_files(hesaff_ctx *c, int n, const char *const *paths, const c
    const bool nice_pool = c->pool_priority == 1 || (c->pool_priority < 0 && hesaff_host_threads() <= dt + wt + 1);
    FileIO io(&c->ring, c->par.max_batch, c->par.mrSize, c->out_format, n, paths, out_paths, status, dt, wt, true, c->resume, device_jpeg, pin, nice_pool, c->embed.set);
    io.vocabulary_size = c->vocab.k;
+   io.neighbours = c->vocab.k ? c->neighbours : 1;   // (R > 1: a row per key and present rank in the words and signatures files)
    c->stage_threads = hesaff_stage_threads_for_pool(dt + wt);
    try {
       run_chunks(c, io, 3);
@@ -1002,6 +1026,7 @@ int hesaff_process_files(hesaff_ctx *c, int n, const char *const *paths, const c
       throw;
    }
    io.shutdown();
+   c->neigh_device_total = -1;   // (b_neigh holds the last chunk's rows only)
    c->pin_read.trim(c->pin_read.keep_bytes);   // a long-lived context does not keep the peak of its largest list pinned
    HS_API_END(c)
 }
@@ -1067,6 +1092,9 @@ int hesaff_set_vocabulary(hesaff_ctx *c, int k, const uint8_t *words)
    c->embed_timed = false;
    c->words_device_total = -1;
    c->assign_timed = false;
+   if (k == 0) { c->b_neigh.release(); c->b_nsigs.release(); }
+   c->neigh_spans.clear();   // (the neighbour count itself is a setting and stays)
+   c->neigh_device_total = -1;
    HS_API_END(c)
 }
 
@@ -1103,6 +1131,75 @@ int hesaff_assign_words_device(hesaff_ctx *c, int64_t n, const void *d_desc, int
    need_vocabulary(c);
    bind_device(c);
    launch_assign_words(c, d_desc, (long long)n, (long long)stride, (long long)offset, d_words_out);
+   finish_stream(c);
+   HS_API_END(c)
+}
+
+// ---- vocabulary neighbours (kernels_neighbours.h) ----
+
+int hesaff_set_vocabulary_neighbours(hesaff_ctx *c, int neighbours)
+{
+   if (!c || neighbours < 1 || neighbours > HS_NEIGH_MAX) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   if (neighbours > 1 && c->cells.c > 0)
+      throw HsError(HESAFF_ERR_ARG, "vocabulary neighbours (R > 1) and a cell layer do not combine: remove the layer (hesaff_set_vocabulary_cells with 0 cells) first; the neighbour count is unchanged");
+   if (neighbours == c->neighbours) return HESAFF_OK;
+   bind_device(c);
+   HIP_TRY(hipStreamSynchronize(c->stream()));
+   c->neighbours = neighbours;
+   // the rows the former count left are not this count's: the getters serve the next call's (R = 1: the words, which stay)
+   c->neigh_spans.clear();
+   c->neigh_device_total = -1;
+   if (neighbours == 1) { c->b_neigh.release(); c->b_nsigs.release(); }
+   HS_API_END(c)
+}
+
+int hesaff_get_vocabulary_neighbours(const hesaff_ctx *c, int *neighbours)
+{
+   if (!c || !neighbours) return HESAFF_ERR_ARG;
+   *neighbours = c->neighbours;
+   return HESAFF_OK;
+}
+
+int hesaff_get_neighbours(const hesaff_ctx *c, int image, const int32_t **neighbours, int *count, int *r)
+{
+   if (!c || !neighbours || !count || !r || c->vocab.k == 0) return HESAFF_ERR_ARG;
+   if (c->neighbours == 1) {   // [n][1][2] is the (word, dist2) array itself
+      const int rc = hesaff_get_words(c, image, neighbours, count);
+      if (rc == HESAFF_OK) *r = 1;
+      return rc;
+   }
+   if (image < 0 || (size_t)image >= c->neigh_spans.size() || c->neigh_spans[(size_t)image].n < 0) return HESAFF_ERR_ARG;
+   *neighbours = c->neigh_spans[(size_t)image].p;
+   *count = c->neigh_spans[(size_t)image].n;
+   *r = c->neigh_spans_r;
+   return HESAFF_OK;
+}
+
+int hesaff_get_neighbours_device(const hesaff_ctx *c, const void **d_neighbours, int64_t *total, int *r)
+{
+   if (!c || !d_neighbours || !total || !r || c->vocab.k == 0) return HESAFF_ERR_ARG;
+   if (c->neighbours == 1) {
+      const int rc = hesaff_get_words_device(c, d_neighbours, total);
+      if (rc == HESAFF_OK) *r = 1;
+      return rc;
+   }
+   if (c->neigh_device_total < 0) return HESAFF_ERR_ARG;
+   *d_neighbours = c->neigh_device_total > 0 ? c->b_neigh.p : nullptr;
+   *total = c->neigh_device_total;
+   *r = c->neigh_device_r;
+   return HESAFF_OK;
+}
+
+int hesaff_assign_neighbours_device(hesaff_ctx *c, int64_t n, const void *d_desc, int64_t stride, int64_t offset, void *d_neighbours_out)
+{
+   if (!c || n < 0 || (n > 0 && (!d_desc || !d_neighbours_out))) return HESAFF_ERR_ARG;
+   if (stride < 128 || offset < 0 || offset + 128 > stride || stride % 4 != 0 || offset % 4 != 0) return HESAFF_ERR_ARG;
+   if ((uintptr_t)d_desc % 4 != 0 || (uintptr_t)d_neighbours_out % 4 != 0 || n > ((int64_t)1 << 38)) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   need_vocabulary(c);
+   bind_device(c);
+   launch_assign_neighbours(c, d_desc, (long long)n, (long long)stride, (long long)offset, d_neighbours_out);
    finish_stream(c);
    HS_API_END(c)
 }

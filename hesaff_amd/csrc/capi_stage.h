@@ -635,4 +635,24 @@ int hesaff_stage_assign_words(hesaff_ctx *c, int n, const uint8_t *desc, int32_t
    HS_API_END(c)
 }
 
+// k_assign_neighbours on caller-supplied descriptors (hesaff_set_vocabulary_neighbours: capi_impl.h): out[n][R][2], R the context's
+int hesaff_stage_assign_neighbours(hesaff_ctx *c, int n, const uint8_t *desc, int32_t *neighbours_out)
+{
+   if (!c || n < 0 || (n > 0 && (!desc || !neighbours_out))) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   need_vocabulary(c);
+   bind_device(c);
+   if (n == 0) return HESAFF_OK;
+   const size_t N = (size_t)n;
+   StageArena a(c);
+   const Span<uint8_t> a_desc = a.add<uint8_t>(N * 128);
+   const Span<int32_t> a_out = a.add<int32_t>(N * 2 * (size_t)c->neighbours);   // (word, dist2) per key and rank
+   a.ensure();
+   a.upload(a_desc, desc);
+   launch_assign_neighbours(c, a.ptr(a_desc), n, 128, 0, a.ptr(a_out));
+   a.download(neighbours_out, a_out);
+   finish_stream(c);
+   HS_API_END(c)
+}
+
 } // extern "C"

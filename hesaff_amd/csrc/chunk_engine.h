@@ -138,13 +138,17 @@ enum { WANT_KEYS = 1,    // the hesaff_keypoint records (hesaff.cpp:41-48)
        WANT_BIN = 4,     // the 148-byte rows of the binary sidecar
        WANT_REGIONS = 8, // a hesaff_region per Hessian keypoint (hesaff_detect_regions; pyramid.h:43-47, affine.h:48-58)
        WANT_WORDS = 16,  // two int32 (word, dist2) per record (hesaff_set_vocabulary), row for row the records
-       WANT_SIGS = 32    // a uint64 signature per record (hesaff_set_embedding), row for row the records; only beside WANT_WORDS
+       WANT_SIGS = 32,   // a uint64 signature per record (hesaff_set_embedding), row for row the records; only beside WANT_WORDS
+       WANT_NEIGH = 64,  // R x two int32 per record (hesaff_set_vocabulary_neighbours, R > 1), row for row the records; only beside WANT_WORDS
+       WANT_NSIGS = 128  // the signatures of the ranks 1 .. R - 1: R - 1 planes of a uint64 per record; only beside WANT_NEIGH and WANT_SIGS
 };
 
 // hesaff_get_words: the rows of one image of the last host call inside the call's result blocks (n = -1: not, or no longer, there)
 struct WordSpan { const int32_t *p = nullptr; int n = -1; };
 // hesaff_get_signatures: the same for the signatures
 struct SigSpan { const uint64_t *p = nullptr; int n = -1; };
+// hesaff_get_neighbours: the same for the neighbours, R x 2 int32 per row
+struct NeighSpan { const int32_t *p = nullptr; int n = -1; };
 
 struct ChunkDone {
    const HostChunk *chunk;
@@ -158,6 +162,9 @@ struct ChunkDone {
    const hesaff_region *regions = nullptr;         // WANT_REGIONS: image b's records start at its Hessian offset, the sum of count_hessian[0 .. b)
    const int32_t *words = nullptr;                 // WANT_WORDS: image b's rows start at words + key_off[b] * 2
    const uint64_t *sigs = nullptr;                 // WANT_SIGS: image b's rows start at sigs + key_off[b]
+   const int32_t *neigh = nullptr;                 // WANT_NEIGH: image b's rows start at neigh + key_off[b] * 2 R
+   const uint64_t *nsigs = nullptr;                // WANT_NSIGS: rank r's signature of record j at nsigs[(r - 1) * nsigs_plane + j]; ranks
+   size_t nsigs_plane = 0;                         //             that not every key has (r >= K) are not filled in
 };
 
 struct ChunkIO {
@@ -185,9 +192,9 @@ struct ChunkState {
    std::vector<unsigned long long> toff;   // WANT_TEXT: byte offset of every image's rows
    int total = 0;                          // records of the chunk
    size_t n_hess = 0;                      // Hessian keypoints of the chunk
-   // layout of the chunk's result block: [records][words][regions][text rows][sidecar rows][signatures], what the consumer wants of
-   // them, `bytes` in all
-   size_t keys_at = 0, words_at = 0, regions_at = 0, text_at = 0, bin_at = 0, sigs_at = 0, bytes = 0;
+   // layout of the chunk's result block: [records][words][regions][text rows][sidecar rows][signatures][neighbours], what the
+   // consumer wants of them, `bytes` in all
+   size_t keys_at = 0, words_at = 0, regions_at = 0, text_at = 0, bin_at = 0, sigs_at = 0, neigh_at = 0, nsigs_at = 0, bytes = 0;
    int block = -1;                         // the result block the loop chose: one of the ring, or `no` without a ring
    uint32_t n_rec = 0;                     // hesaff_describe_regions: records of the chunk
    bool copied = false;                    // a copy out was enqueued
@@ -236,6 +243,8 @@ void run_chunk_loop(ChunkIO &io, BlockRing &ring, int ring_blocks, Device &dev)
       if (wants & WANT_REGIONS) d.regions = (const hesaff_region *)(blk + s.regions_at);
       if (wants & WANT_WORDS) d.words = (const int32_t *)(blk + s.words_at);
       if (wants & WANT_SIGS) d.sigs = (const uint64_t *)(blk + s.sigs_at);
+      if (wants & WANT_NEIGH) d.neigh = (const int32_t *)(blk + s.neigh_at);
+      if (wants & WANT_NSIGS) { d.nsigs = (const uint64_t *)(blk + s.nsigs_at); d.nsigs_plane = (size_t)s.total; }
       io.done(d);
    };
 
@@ -314,6 +323,8 @@ struct ArrayIO : ChunkIO {
    hesaff_region_result *region_results = nullptr;   // hesaff_detect_regions: filled in place (instead of results)
    std::vector<WordSpan> *word_spans = nullptr;      // a vocabulary is set: every image's word rows are noted here, by the caller's index
    std::vector<SigSpan> *sig_spans = nullptr;        // an embedding is set as well: the same for the signatures
+   std::vector<NeighSpan> *neigh_spans = nullptr;    // a neighbour count R > 1 is set: the same for the neighbours, neigh_r = R
+   int neigh_r = 1;
    std::atomic<int> sink_rc{0};                 // written by done() on the caller's thread, read by next() on the staging thread
    ArrayIO(BlockRing *ring_, int max_batch, int n, const uint8_t *const *images, const int *widths, const int *heights, const int *strides,
            const int *channels, bool f32 = false, const hesaff_region *const *regions = nullptr, const int *counts = nullptr, int from = 0,
@@ -375,7 +386,7 @@ struct ArrayIO : ChunkIO {
       for (size_t i = pos; i < chunks.size() && chunks[i].W == q.W && chunks[i].H == q.H && chunks[i].ch == q.ch && chunks[i].f32 == q.f32; i++) m = std::max(m, chunks[i].data.size());
       return (int)m;
    }
-   int wants() const override { return WANT_KEYS | (region_results ? WANT_REGIONS : 0) | (word_spans ? WANT_WORDS : 0) | (sig_spans ? WANT_SIGS : 0); }
+   int wants() const override { return WANT_KEYS | (region_results ? WANT_REGIONS : 0) | (word_spans ? WANT_WORDS : 0) | (sig_spans ? WANT_SIGS : 0) | (neigh_spans ? WANT_NEIGH : 0); }
    void note_words(const ChunkDone &d, bool valid)
    {
       if (!word_spans) return;
@@ -384,6 +395,12 @@ struct ArrayIO : ChunkIO {
          w.n = valid ? d.count_desc[b] : -1;
          w.p = valid && d.count_desc[b] > 0 ? d.words + d.key_off[b] * 2 : nullptr;
       }
+      if (neigh_spans)
+         for (size_t b = 0; b < d.chunk->index.size(); b++) {
+            NeighSpan &g = (*neigh_spans)[(size_t)d.chunk->index[b]];
+            g.n = valid ? d.count_desc[b] : -1;
+            g.p = valid && d.count_desc[b] > 0 ? d.neigh + d.key_off[b] * 2 * (size_t)neigh_r : nullptr;
+         }
       if (!sig_spans) return;
       for (size_t b = 0; b < d.chunk->index.size(); b++) {
          SigSpan &g = (*sig_spans)[(size_t)d.chunk->index[b]];
@@ -450,7 +467,9 @@ struct FileIO : ChunkIO {
    std::condition_variable cv_work, cv_img, cv_done;   // workers: a job may be available; next(): an image changed state; wait_writers()
    int next_decode = 0, consumed = 0, window = 0, pos = 0, chunks_out = 0;
    bool stop = false;
-   struct Task { int index; const hesaff_keypoint *keys; int n; int chunk; const char *text; size_t text_len; const char *bin; const int32_t *words; const uint64_t *sigs; };
+   struct Task { int index; const hesaff_keypoint *keys; int n; int chunk; const char *text; size_t text_len; const char *bin; const int32_t *words; const uint64_t *sigs;
+                 const int32_t *neigh; const uint64_t *nsigs; size_t nsigs_plane; };
+   int neighbours = 1;   // hesaff_set_vocabulary_neighbours: R > 1 expands the words file (and the signatures file) to a row per key and present rank
    std::deque<Task> tasks;
    struct Open { int left; int block; };
    std::vector<Open> open_chunks;
@@ -703,7 +722,8 @@ struct FileIO : ChunkIO {
             status[i].count_desc = d.count_desc[b];
             status[i].stage = HESAFF_FILE_DETECTED;
             Task t{i, d.keys ? d.keys + d.key_off[b] : nullptr, d.count_desc[b], id, nullptr, 0, nullptr, d.words ? d.words + d.key_off[b] * 2 : nullptr,
-                   d.sigs ? d.sigs + d.key_off[b] : nullptr};
+                   d.sigs ? d.sigs + d.key_off[b] : nullptr, d.neigh ? d.neigh + d.key_off[b] * 2 * (size_t)neighbours : nullptr,
+                   d.nsigs ? d.nsigs + d.key_off[b] : nullptr, d.nsigs_plane};
             if (d.text) { t.text = d.text + d.text_off[b]; t.text_len = (size_t)(d.text_off[b + 1] - d.text_off[b]); }
             if (d.bin) t.bin = d.bin + d.key_off[b] * (size_t)148;
             tasks.push_back(t);
@@ -715,7 +735,8 @@ struct FileIO : ChunkIO {
    int wants() const override
    {
       // (a words row is composed on the host from the key's record and its word: both travel)
-      const int words = (fmt & HESAFF_OUT_WORDS) ? (WANT_KEYS | WANT_WORDS | (embedded ? WANT_SIGS : 0)) : 0;
+      const int ranks = neighbours > 1 ? (WANT_NEIGH | (embedded ? WANT_NSIGS : 0)) : 0;
+      const int words = (fmt & HESAFF_OUT_WORDS) ? (WANT_KEYS | WANT_WORDS | (embedded ? WANT_SIGS : 0) | ranks) : 0;
       if (!device_format) return WANT_KEYS | words;
       return ((fmt & HESAFF_OUT_TEXT) ? WANT_TEXT : 0) | ((fmt & HESAFF_OUT_BIN) ? WANT_BIN : 0) | words;
    }
@@ -738,8 +759,11 @@ struct FileIO : ChunkIO {
          if (device_format) rc = hesaff_write_bin_rows(name.c_str(), t.bin, t.n);
          else rc = hesaff_write_bin(name.c_str(), t.keys, t.n, mrSize);
       }
-      if ((fmt & HESAFF_OUT_WORDS) && rc == HESAFF_OK) rc = hesaff_write_words(words_name(t.index).c_str(), t.keys, t.words, t.n, mrSize, vocabulary_size);
-      if (writes_sigs() && rc == HESAFF_OK) rc = hesaff_write_signatures(sigs_name_for(words_name(t.index)).c_str(), t.sigs, t.n);
+      if ((fmt & HESAFF_OUT_WORDS) && neighbours > 1 && rc == HESAFF_OK) rc = write_ranks(t);
+      else {
+         if ((fmt & HESAFF_OUT_WORDS) && rc == HESAFF_OK) rc = hesaff_write_words(words_name(t.index).c_str(), t.keys, t.words, t.n, mrSize, vocabulary_size);
+         if (writes_sigs() && rc == HESAFF_OK) rc = hesaff_write_signatures(sigs_name_for(words_name(t.index)).c_str(), t.sigs, t.n);
+      }
       int blk = -1;
       {
          std::lock_guard<std::mutex> lk(mu);
@@ -750,6 +774,27 @@ struct FileIO : ChunkIO {
       }
       if (blk >= 0) ring->release(blk);
       cv_done.notify_all();
+   }
+   // the words file (and the signatures file) under a neighbour count R > 1: for every key in key order a row per present rank in
+   // ascending rank - the key's record with that rank's word, that rank's signature - composed here and written by the same writers
+   int write_ranks(const Task &t)
+   {
+      const size_t R = (size_t)neighbours;
+      std::vector<hesaff_keypoint> keys;
+      std::vector<int32_t> words;
+      std::vector<uint64_t> sigs;
+      for (size_t i = 0; i < (size_t)t.n; i++)
+         for (size_t r = 0; r < R; r++) {
+            const int32_t *nb = t.neigh + (i * R + r) * 2;
+            if (nb[0] < 0) continue;   // fewer than r + 1 rows in the vocabulary
+            keys.push_back(t.keys[i]);
+            words.push_back(nb[0]); words.push_back(nb[1]);
+            if (writes_sigs()) sigs.push_back(r == 0 ? t.sigs[i] : t.nsigs[(r - 1) * t.nsigs_plane + i]);
+         }
+      const int rows = (int)keys.size();
+      int rc = hesaff_write_words(words_name(t.index).c_str(), keys.data(), words.data(), rows, mrSize, vocabulary_size);
+      if (writes_sigs() && rc == HESAFF_OK) rc = hesaff_write_signatures(sigs_name_for(words_name(t.index)).c_str(), sigs.data(), rows);
+      return rc;
    }
    void wait_writers()
    {

@@ -26,6 +26,7 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <ostream>
 #include <stdexcept>
 #include <string>
@@ -175,9 +176,28 @@ struct AffineHessianDetector {
    // a signature per key, parallel to `keys` and to words(): nullptr without an embedding or without keys
    const uint64_t *signatures() const { return sigs_.empty() ? nullptr : sigs_.data(); }
    // <image>.hesaff.sigs of the current keys (hesaff_write_signatures), row for row with exportWords' file
+   // With a neighbour count R > 1 a row per key and present rank, like exportWords' file: rank 0 is signatures(), the ranks above are
+   // made here under that rank's word (hesaff_stage_embed on the keys' descriptors with the neighbours as a words array of stride 2 R)
    void exportSignatures(const std::string &path) const
    {
-      if (hesaff_write_signatures(path.c_str(), sigs_.data(), (int)sigs_.size()) != HESAFF_OK) throw std::runtime_error("cannot write " + path);
+      const size_t R = (size_t)neighboursR_, n = keys.size();
+      if (R <= 1 || neighbours_.empty() || sigs_.empty()) {
+         if (hesaff_write_signatures(path.c_str(), sigs_.data(), (int)sigs_.size()) != HESAFF_OK) throw std::runtime_error("cannot write " + path);
+         return;
+      }
+      std::vector<uint8_t> desc(n * 128);
+      for (size_t i = 0; i < n; i++) std::memcpy(&desc[i * 128], keys[i].desc, 128);
+      std::vector<uint64_t> plane(n), rows;
+      std::vector<std::vector<uint64_t>> by_rank(R);
+      by_rank[0] = sigs_;
+      for (size_t r = 1; r < R && neighbours_[2 * r] >= 0; r++) {   // (a rank is present for every key or for none: it is r < K)
+         if (hesaff_stage_embed(ctx_, (int)n, desc.data(), neighbours_.data() + 2 * r, (int)(2 * R), plane.data()) != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+         by_rank[r] = plane;
+      }
+      for (size_t i = 0; i < n; i++)
+         for (size_t r = 0; r < R; r++)
+            if (neighbours_[(i * R + r) * 2] >= 0) rows.push_back(by_rank[r][i]);
+      if (hesaff_write_signatures(path.c_str(), rows.data(), (int)rows.size()) != HESAFF_OK) throw std::runtime_error("cannot write " + path);
    }
    // the default projection of a seed (hesaff_embedding_projection): 64 x 128 bytes
    static std::vector<int8_t> embeddingProjection(uint64_t seed)
@@ -200,13 +220,50 @@ struct AffineHessianDetector {
    // (word, dist2) per key, two int32 each, parallel to `keys`: nullptr without a vocabulary or without keys
    const int32_t *words() const { return words_.empty() ? nullptr : words_.data(); }
    // <image>.hesaff.words of the current keys (hesaff_write_words): x, y, a, b, c as exportKeypoints prints them, and the word
+   // With a neighbour count R > 1: for every key in key order a row per present rank in ascending rank, the key's five floats with
+   // that rank's word - an ordinary words file with up to R rows per key.
    void exportWords(const std::string &path) const
    {
       int k = 0;
       if (hesaff_get_vocabulary_size(ctx_, &k) != HESAFF_OK || k == 0) throw std::runtime_error("exportWords: no vocabulary is set");
+      if (neighboursR_ > 1 && !neighbours_.empty()) {
+         const size_t R = (size_t)neighboursR_;
+         std::vector<hesaff_keypoint> rows;
+         std::vector<int32_t> row_words;
+         for (size_t i = 0; i < keys.size(); i++)
+            for (size_t r = 0; r < R; r++) {
+               const int32_t *nb = &neighbours_[(i * R + r) * 2];
+               if (nb[0] < 0) continue;
+               rows.push_back(keys[i]);
+               row_words.push_back(nb[0]); row_words.push_back(nb[1]);
+            }
+         if (hesaff_write_words(path.c_str(), rows.data(), row_words.data(), (int)rows.size(), p_.mrSize, k) != HESAFF_OK)
+            throw std::runtime_error("cannot write '" + path + "'");
+         return;
+      }
       if (hesaff_write_words(path.c_str(), keys.data(), words(), (int)keys.size(), p_.mrSize, k) != HESAFF_OK)
          throw std::runtime_error("cannot write '" + path + "'");
    }
+   // No counterpart in the reference (hesaff_set_vocabulary_neighbours, include/hesaff_amd.h): every key's R nearest rows of the
+   // vocabulary, 1..8 (default 1: the word alone).  A setting of the detector: setVocabulary keeps it.  With R > 1 every call also
+   // fills neighbours(); words() stays rank 0.  Does not combine with a cell layer: either setter then throws and changes nothing.
+   void setVocabularyNeighbours(int neighbours)
+   {
+      if (hesaff_set_vocabulary_neighbours(ctx_, neighbours) != HESAFF_OK)
+         throw std::invalid_argument(neighbours < 1 || neighbours > 8 ? "vocabulary neighbours must be 1..8" : hesaff_last_error(ctx_));
+      neighbours_.clear();
+      neighboursR_ = 1;
+   }
+   int vocabularyNeighbours() const
+   {
+      int r = 1;
+      hesaff_get_vocabulary_neighbours(ctx_, &r);
+      return r;
+   }
+   // (word, dist2) per key and rank of the last call, neighboursRanks() x two int32 per key, parallel to `keys`: nullptr with R = 1,
+   // without a vocabulary or without keys
+   const int32_t *neighbours() const { return neighbours_.empty() ? nullptr : neighbours_.data(); }
+   int neighboursRanks() const { return neighboursR_; }
 
    // No counterpart in the reference (hesaff_train_vocabulary, include/hesaff_amd.h): exact integer k-means on the device over n
    // descriptors of 128 bytes - the initial rows are desc[floor(r n / k)], at most `iterations` Lloyd iterations with the mean rounded
@@ -235,6 +292,7 @@ struct AffineHessianDetector {
    void setVocabularyCells(const uint8_t *coarse, const uint32_t *first, int c)
    {
       const int rc = hesaff_set_vocabulary_cells(ctx_, c, coarse, first);
+      if (rc == HESAFF_ERR_ARG && c > 0 && vocabularyNeighbours() > 1) throw std::invalid_argument(hesaff_last_error(ctx_));   // (the two do not combine)
       if (rc == HESAFF_ERR_ARG)
          throw std::invalid_argument("a cell layer needs a vocabulary of K rows, 0 <= c <= K coarse rows and first[0] = 0 < ... < first[c] = K");
       if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
@@ -560,6 +618,16 @@ struct AffineHessianDetector {
          if (hesaff_get_words(ctx_, 0, &w, &n) != HESAFF_OK) throw std::runtime_error("hesaff_get_words failed");
          if (n > 0) words_.assign(w, w + 2 * (size_t)n);
       }
+      // ... their neighbours, when a neighbour count above 1 is set
+      neighbours_.clear();
+      neighboursR_ = 1;
+      if (vk > 0 && vocabularyNeighbours() > 1) {
+         int m = 0, r = 1;
+         const int32_t *nb = nullptr;
+         if (hesaff_get_neighbours(ctx_, 0, &nb, &m, &r) != HESAFF_OK) throw std::runtime_error("hesaff_get_neighbours failed");
+         neighboursR_ = r;
+         if (m > 0) neighbours_.assign(nb, nb + 2 * (size_t)m * (size_t)r);
+      }
       // ... and their signatures, when an embedding is set as well
       sigs_.clear();
       int ek = 0, m = 0;
@@ -632,6 +700,8 @@ struct AffineHessianDetector {
    HessianKeypointCallback *hessianKeypointCallback_ = nullptr;
    AffineShapeCallback *affineShapeCallback_ = nullptr;
    std::vector<int32_t> words_;      // setVocabulary: (word, dist2) per key
+   std::vector<int32_t> neighbours_; // setVocabularyNeighbours above 1: (word, dist2) per key and rank
+   int neighboursR_ = 1;             // ... and the ranks per key they hold
    std::vector<uint64_t> sigs_;      // setEmbedding: a signature per key
    std::vector<int64_t> distortion_; // trainVocabulary: per iteration that ran
    std::vector<int32_t> empty_;

@@ -67,6 +67,11 @@
 //   hesaff <image> --vocabulary <vocabulary file> --cells <cells file> --probes P      (and with --batch)
 //       P = 1..8: a key is searched in its P nearest cells (hesaff_set_vocabulary_probes; 1, the default, is its one cell, and from the
 //       layer's cell count on the result is the flat assignment).  Needs --cells <cells file>; refused with --train-vocabulary.
+//   hesaff <image> --vocabulary <vocabulary file> --neighbours R      (and with --batch, also beside --embedding)
+//       R = 1..8: every key's R nearest rows of the vocabulary, not just the nearest (hesaff_set_vocabulary_neighbours; multiple assignment
+//       for QUERY images).  <image>.hesaff.words then holds, for every key in key order, a row per rank in ascending rank - the key's
+//       five floats, that rank's word - and <image>.hesaff.sigs is row for row with it: an ordinary words file with up to R rows per
+//       key, which --query, --queries, --hamming and --verify take unchanged.  Needs --vocabulary; R > 1 does not combine with --cells.
 //   hesaff --batch <list file> --train-vocabulary <vocabulary file> --words K --cells C [--iterations T] [--coarse-iterations Tc]
 //       trains C coarse rows (Tc = 10 iterations at most), spreads K initial rows over the list's keys, sorts them into the cells of their
 //       nearest coarse rows (hesaff_build_vocabulary_cells) and trains them inside the cells (hesaff_train_vocabulary_cells); writes
@@ -167,7 +172,7 @@ bool parse_devices(const char *spec, std::vector<int> &out)
 int run_batch_mode(const char *list_path, const char *devices_spec, int out_format, bool dynamic, int fast, int resume, int host_share, int runtime_nice,
                    int max_keypoints, int orientation, int grid_rows, int grid_cols, int descriptor, int orientations,
                    const uint8_t *vocabulary, int vocabulary_size, const uint8_t *cells_coarse, const uint32_t *cells_first, int cells, int probes,
-                   const int8_t *embed_P, const int32_t *embed_tau)
+                   const int8_t *embed_P, const int32_t *embed_tau, int neighbours)
 {
    std::ifstream lf(list_path);
    if (!lf) { fprintf(stderr, "hesaff: cannot read list '%s'\n", list_path); return 1; }
@@ -233,6 +238,7 @@ int run_batch_mode(const char *list_path, const char *devices_spec, int out_form
          return;
       }
       hesaff_set_vocabulary_probes(ctx, probes);   // (main checked the range)
+      hesaff_set_vocabulary_neighbours(ctx, neighbours);   // (likewise, and that no layer goes with a count above 1)
       if (embed_P && hesaff_set_embedding(ctx, embed_P, embed_tau) != HESAFF_OK) {   // (main checked its rows against the vocabulary's)
          errs[(size_t)rank] = hesaff_last_error(ctx);
          hesaff_destroy(ctx);
@@ -795,6 +801,8 @@ int main(int argc, char **argv)
       bool seed_given = false;
       int resume = 0, train_words = 0, train_iterations = 10, train_cells = 0, coarse_iterations = 10, probes = 1;
       bool probes_given = false;
+      int neighbours = 1;
+      bool neighbours_given = false;
       for (int i = 1; i < argc && !bad; i += 2) {
          if (strcmp(argv[i], "--resume") == 0) { resume = 1; i--; continue; }
          if (strcmp(argv[i], "--resume=strict") == 0) { resume = 2; i--; continue; }   // also count the rows of existing text outputs
@@ -817,6 +825,11 @@ int main(int argc, char **argv)
             // one digit, 1..8 (hesaff_set_vocabulary_probes)
             if (argv[i + 1][0] < '1' || argv[i + 1][0] > '8' || argv[i + 1][1] != 0) bad = true;
             else { probes = argv[i + 1][0] - '0'; probes_given = true; }
+         }
+         else if (strcmp(argv[i], "--neighbours") == 0) {
+            // one digit, 1..8 (hesaff_set_vocabulary_neighbours)
+            if (argv[i + 1][0] < '1' || argv[i + 1][0] > '8' || argv[i + 1][1] != 0) bad = true;
+            else { neighbours = argv[i + 1][0] - '0'; neighbours_given = true; }
          }
          else if (strcmp(argv[i], "--coarse-iterations") == 0) {
             char *end = nullptr;
@@ -891,7 +904,12 @@ int main(int argc, char **argv)
       }
       if (coarse_iterations != 10 && !train_cells) bad = true;
       if (probes_given && (!cells_arg || train_path)) bad = true;   // probes search a cells FILE's layer; training has one probe
-      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--vocabulary <vocabulary file> [--words-only] [--embedding <embedding file>] [--train-embedding <embedding file> [--seed S]]] [--train-vocabulary <vocabulary file> --words K [--iterations T]] [--cells <cells file>|C [--coarse-iterations Tc]] [--probes 1..8] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1] [--max-keypoints N] [--orientations 1..4] [--descriptor sift|rootsift] [--orientation up|dominant] [--grid RxC]\n"); return 1; }
+      if (neighbours_given && (!vocabulary_path || train_path || train_embedding_path)) bad = true;   // neighbours are rows of a vocabulary, for per-image files
+      if (bad || !list) { fprintf(stderr, "hesaff: usage: hesaff --batch <list file> [--devices 0-7|0,2|all] [--output text|bin|both] [--vocabulary <vocabulary file> [--words-only] [--embedding <embedding file>] [--train-embedding <embedding file> [--seed S]]] [--train-vocabulary <vocabulary file> --words K [--iterations T]] [--cells <cells file>|C [--coarse-iterations Tc]] [--probes 1..8] [--neighbours 1..8] [--schedule static|dynamic] [--fast 0|2] [--resume|--resume=strict] [--host-share K] [--runtime-nice 0|1] [--max-keypoints N] [--orientations 1..4] [--descriptor sift|rootsift] [--orientation up|dominant] [--grid RxC]\n"); return 1; }
+      if (neighbours > 1 && cells_arg) {   // (the library's refusal, before any file is read)
+         fprintf(stderr, "hesaff: --neighbours above 1 and --cells do not combine: the R nearest words are searched in the whole vocabulary\n");
+         return 1;
+      }
       if (train_path)
          return run_train_mode(list, devices, train_path, train_words, train_iterations, fast, max_keypoints, orientation, grid_rows, grid_cols, descriptor, orientations, train_cells,
                                coarse_iterations);
@@ -929,7 +947,7 @@ int main(int argc, char **argv)
          return trc;
       }
       const int brc = run_batch_mode(list, devices, out_format, dynamic, fast, resume, host_share, runtime_nice, max_keypoints, orientation, grid_rows, grid_cols, descriptor,
-                                     orientations, vocabulary, vocabulary_size, cells_coarse, cells_first, cells, probes, embed_P, embed_tau);
+                                     orientations, vocabulary, vocabulary_size, cells_coarse, cells_first, cells, probes, embed_P, embed_tau, neighbours);
       hesaff_free(vocabulary); hesaff_free(cells_coarse); hesaff_free(cells_first); hesaff_free(embed_P); hesaff_free(embed_tau);
       return brc;
    }
@@ -974,6 +992,21 @@ int main(int argc, char **argv)
             fprintf(stderr, "hesaff: --probes takes 1 .. 8 and needs --vocabulary with --cells <cells file>\n");
             return 1;
          }
+      }
+      // --neighbours 1..8 behind the image (the last one counts): needs --vocabulary, and above 1 no --cells
+      int neighbours = 1;
+      for (int i = 2; i < argc; i++) {
+         if (strcmp(argv[i], "--neighbours") != 0) continue;
+         const char *v = i + 1 < argc ? argv[++i] : "";
+         if (vocabulary && v[0] >= '1' && v[0] <= '8' && v[1] == 0) neighbours = v[0] - '0';
+         else {
+            fprintf(stderr, "hesaff: usage: hesaff <image> [--mask <mask file>] [--orientation up|dominant] [--orientations 1..4] [--descriptor sift|rootsift] [--vocabulary <vocabulary file> [--cells <cells file> [--probes 1..8]] [--neighbours 1..8]]\n");
+            return 1;
+         }
+      }
+      if (neighbours > 1 && cells_coarse) {
+         fprintf(stderr, "hesaff: --neighbours above 1 and --cells do not combine: the R nearest words are searched in the whole vocabulary\n");
+         return 1;
       }
       uint8_t *data = nullptr;
       int w = 0, h = 0, ch = 0;
@@ -1053,6 +1086,7 @@ int main(int argc, char **argv)
          if (vocabulary) detector.setVocabulary(vocabulary, vocabulary_size);
          if (cells_coarse) detector.setVocabularyCells(cells_coarse, cells_first, cells);
          detector.setVocabularyProbes(probes);
+         detector.setVocabularyNeighbours(neighbours);
          const auto t1 = std::chrono::steady_clock::now();
          detector.detectPyramidKeypoints(data, w, h, ch);
          const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();

@@ -41,6 +41,7 @@
 #include "kernels_export.h"
 #include "kernels_jpeg.h"
 #include "kernels_words.h"
+#include "kernels_neighbours.h"
 #include "kernels_train.h"
 #include "kernels_cells.h"
 #include "kernels_index.h"
@@ -452,7 +453,17 @@ struct hesaff_ctx {
    DevBuf b_words;                     // (word, dist2) per record of b_out, written behind the pack stage of every batch
    int64_t words_device_total = -1;    // hesaff_get_words_device: the rows of b_words after a device-resident call (-1: no such call was the last)
    std::vector<hesaff_engine::WordSpan> word_spans;   // hesaff_get_words: per image of the last host call, its rows in the call's result blocks
-   DevEvent ev_assign[2];              // profiling: brackets of the last k_assign_words launch
+   // hesaff_set_vocabulary_neighbours: R = 1 (the default) is the plain assignment, and nothing of the four below is allocated,
+   // launched or copied; R > 1: k_assign_neighbours (kernels_neighbours.h) takes k_assign_words' place and leaves int32[rows][R][2]
+   // in b_neigh beside the (word, dist2) array, which is its rank 0
+   int neighbours = 1;
+   DevBuf b_neigh;
+   DevBuf b_nsigs;                     // hesaff_process_files with an embedding and R > 1: the signatures of the ranks 1 .. R - 1 of a chunk, a plane per rank
+   int64_t neigh_device_total = -1;    // hesaff_get_neighbours_device: the rows of b_neigh the last assignment left (-1: none, or a host call since)
+   int neigh_device_r = 1;             // ... and the R they were written with
+   std::vector<hesaff_engine::NeighSpan> neigh_spans;   // hesaff_get_neighbours: per image of the last host call (R > 1), as word_spans
+   int neigh_spans_r = 1;
+   DevEvent ev_assign[2];              // profiling: brackets of the last k_assign_words (R > 1: k_assign_neighbours) launch
    bool assign_timed = false;          // ev_assign holds a launch of the last batch
    float train_ms[3] = {0.0f, 0.0f, 0.0f};   // hesaff_get_training_ms: assignment, accumulation, update of the last training call (profiling >= 1)
    // hesaff_set_vocabulary_cells: a cell layer over the vocabulary (cells_plan.h: CellLayerArrays in `layer`, CellScratch for `cap` keys
@@ -1309,6 +1320,21 @@ void launch_assign_kernel(hipStream_t st, const void *tiles, const void *norms, 
                       (const hs_v4i *)tiles, (const int32_t *)norms, n_tiles, (int32_t *)d_out);
 }
 
+// k_assign_neighbours against the same: the R least (dist2, row) per key into d_out [n][R][2], rank 0 into d_words [n][2] as well
+// where that is not nullptr; 1 <= R <= HS_NEIGH_MAX, n >= 1.  The list capacity is the least of 2, 4, 8 that holds R.
+void launch_neighbours_kernel(hipStream_t st, const void *tiles, const void *norms, int n_tiles, const void *d_desc, long long n, long long stride, long long offset,
+                              int R, void *d_out, void *d_words)
+{
+   const long long blocks = (n + HS_WORD_BLOCK_KEYS - 1) / HS_WORD_BLOCK_KEYS;
+   const auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(HS_WORD_BLOCK_WAVES * 64), 0, st, (const uint8_t *)d_desc, n, stride, offset, (const hs_v4i *)tiles,
+                         (const int32_t *)norms, n_tiles, R, (int32_t *)d_out, (int32_t *)d_words);
+   };
+   if (R <= 2) launch(k_assign_neighbours<2>);
+   else if (R <= 4) launch(k_assign_neighbours<4>);
+   else launch(k_assign_neighbours<8>);
+}
+
 // A cell layer and its working arrays as the kernels receive them (kernels_cells.h): the context's (launch_assign_cells) or the private
 // ones of a training call (capi_train.h)
 struct CellsDevice {
@@ -1430,7 +1456,28 @@ void launch_assign_words(hesaff_ctx *c, const void *d_desc, long long n, long lo
    if (timed && !c->ev_assign[0]) { c->ev_assign[0] = DevEvent(hipEventDefault); c->ev_assign[1] = DevEvent(hipEventDefault); }
    if (timed) HIP_TRY(hipEventRecord(c->ev_assign[0], st));
    if (c->cells.c > 0) launch_assign_cells(c, d_desc, n, stride, offset, d_out);
+   else if (c->neighbours > 1) {   // (never beside a layer: the setters refuse the pair)
+      c->b_neigh.ensure_grow((size_t)n * (size_t)c->neighbours * 8);
+      launch_neighbours_kernel(st, c->vocab.tiles.p, c->vocab.norms.p, c->vocab.n_tiles, d_desc, n, stride, offset, c->neighbours, c->b_neigh.p, d_out);
+      c->neigh_device_total = n;
+      c->neigh_device_r = c->neighbours;
+   }
    else launch_assign_kernel(st, c->vocab.tiles.p, c->vocab.norms.p, c->vocab.n_tiles, d_desc, n, stride, offset, d_out);
+   if (timed) { HIP_TRY(hipEventRecord(c->ev_assign[1], st)); c->assign_timed = true; }
+}
+
+// hesaff_assign_neighbours_device / hesaff_stage_assign_neighbours: the context's R least (dist2, row) of n descriptors in device
+// memory into the caller's d_out [n][R][2], on the main stream; R = 1 as well.  Bracketed for hesaff_get_assign_ms like the assignment.
+void launch_assign_neighbours(hesaff_ctx *c, const void *d_desc, long long n, long long stride, long long offset, void *d_out)
+{
+   c->assign_timed = false;
+   c->cells.timed_slices = 0;
+   if (n <= 0) return;
+   hipStream_t st = c->stream();
+   const bool timed = c->profiling >= 1;
+   if (timed && !c->ev_assign[0]) { c->ev_assign[0] = DevEvent(hipEventDefault); c->ev_assign[1] = DevEvent(hipEventDefault); }
+   if (timed) HIP_TRY(hipEventRecord(c->ev_assign[0], st));
+   launch_neighbours_kernel(st, c->vocab.tiles.p, c->vocab.norms.p, c->vocab.n_tiles, d_desc, n, stride, offset, c->neighbours, d_out, nullptr);
    if (timed) { HIP_TRY(hipEventRecord(c->ev_assign[1], st)); c->assign_timed = true; }
 }
 
@@ -1471,6 +1518,20 @@ void assign_batch_words(hesaff_ctx *c, long long total)
    if (!c->embed.set) return;
    c->b_sigs.ensure_grow((size_t)total * 8);
    launch_embed_keys(c, c->geo.b_out.p, total, (long long)sizeof(KeyRec), (long long)offsetof(KeyRec, desc), c->b_words.as<int32_t>(), 2, c->b_sigs.p);
+}
+
+// hesaff_process_files with an embedding and R > 1: behind assign_batch_words, the signature of every (key, rank) of the batch's `total`
+// records for the ranks 1 .. min(R, K) - 1 - the ranks every key has; rank 0 is b_sigs - into b_nsigs, plane r - 1 = rank r.  The
+// neighbours array is a words array of stride 2 R that starts at rank r (k_embed_keys reads the word alone).
+void embed_batch_ranks(hesaff_ctx *c, long long total)
+{
+   if (total <= 0 || !c->embed.set || c->neighbours < 2) return;
+   const int R = c->neighbours, ranks = std::min(R, c->vocab.k);
+   c->b_nsigs.ensure_grow((size_t)total * 8 * (size_t)(R - 1));
+   for (int r = 1; r < ranks; r++)
+      launch_embed_kernel<false>(c->stream(), c->embed.ptr(c->embed.a.tiles), c->embed.ptr(c->embed.a.bias), c->embed.ptr(c->embed.a.tau), c->geo.b_out.p, total,
+                                 (long long)sizeof(KeyRec), (long long)offsetof(KeyRec, desc), c->b_neigh.as<int32_t>() + 2 * r, 2 * R,
+                                 c->b_nsigs.at<uint64_t>((size_t)(r - 1) * (size_t)total * 8));
 }
 
 // Everything after the Hessian list of a batch is complete - by detection (run_batch) or from the caller's records (run_describe):

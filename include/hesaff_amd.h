@@ -60,6 +60,7 @@ extern "C" {
  *    And for Hamming embedding (hesaff_set_embedding and the twenty symbols declared with it): symbols only, version 8.
  *    And for the growing, durable index (hesaff_index_add and the nine symbols declared with it): symbols only, version 8.
  *    And for batched index queries (hesaff_index_query_batch and the seven symbols declared with it): symbols only, version 8.
+ *    And for vocabulary neighbours (hesaff_set_vocabulary_neighbours and the five symbols declared with it): symbols only, version 8.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -688,6 +689,47 @@ int hesaff_write_vocabulary_cells(const char *path, int c, const uint8_t *coarse
 int hesaff_set_vocabulary_probes(hesaff_ctx *ctx, int probes);
 int hesaff_get_vocabulary_probes(const hesaff_ctx *ctx, int *probes);
 int hesaff_stage_probe_cells(hesaff_ctx *ctx, int n, const uint8_t *desc, int32_t *cells_out, int32_t *dist2_out);
+
+/* Vocabulary neighbours (no counterpart in the reference; multiple assignment, Jegou, Douze and Schmid IJCV 2010; related to the soft
+ * assignment of Philbin et al. CVPR 2008): the R nearest rows of the vocabulary per key, not just the nearest, so that a QUERY key
+ * can be looked up under every word whose cell border it lies near.  The database and the index do not change.  Symbols only,
+ * version 8.
+ * With a vocabulary of K rows set, the neighbours of a key are the R lexicographically least pairs (dist2(k), k) over the rows
+ * k = 0 .. K - 1, in ascending order; dist2 as in hesaff_set_vocabulary.  Integers, exact, ties decided (a tie in dist2 goes to the
+ * lower row, also where it decides which row is the R-th), no dependence on launch geometry.  Rank 0 is hesaff_set_vocabulary's
+ * (word, dist2) of the key, bit for bit.  Where K < R, the ranks r >= K are (-1, 2^31 - 1).  All rows of a key's list are distinct.
+ * On the device one pass over the vocabulary keeps R candidates per key (k_assign_neighbours, kernels_neighbours.h).
+ * hesaff_set_vocabulary_neighbours: 1 <= R <= 8, default 1.  A setting of the context like the probe count: it survives
+ * hesaff_set_vocabulary.  With R > 1 every entry point that assigns words - the detecting and describing calls,
+ * hesaff_assign_words_device, hesaff_stage_assign_words, hesaff_process_files - also leaves int32[n][R][2] neighbours, (word, dist2)
+ * per rank, beside the words; the (word, dist2) arrays those entry points hand out keep their layout and their bytes: they are rank 0.
+ * With R = 1 the kernels, their order, the allocations and the copies are those of a context on which this was never called; the
+ * neighbours array costs 8 R bytes per key and exists only while R > 1.
+ * R > 1 and a cell layer do not combine: hesaff_set_vocabulary_cells (cells > 0) with R > 1 set, and this call with R > 1 while a
+ * layer is set, return HESAFF_ERR_ARG with a message that says so and leave the context as it was.
+ * hesaff_get_neighbours: as hesaff_get_words (the image index, the lifetime, the _cb forms); *neighbours = int32_t[count][*r][2], row
+ * for row that image's keys.  hesaff_get_neighbours_device: the device array the last assignment left - parallel to d_keys_out after
+ * a device-resident call, to the descriptors after hesaff_assign_words_device or hesaff_stage_assign_words; not after a host call
+ * (its rows are in host memory: hesaff_get_neighbours).  *r is the count the rows were written with.  With R = 1 both getters hand
+ * out the words themselves, which are [count][1][2].  Changing R leaves the words readable; the neighbours are the next call's.
+ * hesaff_assign_neighbours_device / hesaff_stage_assign_neighbours: the neighbours of n caller-held descriptors, addressed and aligned
+ * as in hesaff_assign_words_device / in host memory; the output receives n x R x 2 int32 with the context's R, R = 1 as well.  They
+ * search the whole vocabulary, whatever layer is set.  hesaff_get_assign_ms reports their launch, and with R > 1 that of the entry
+ * points above: the neighbours launch takes the assignment's place, it does not follow it.
+ * With an embedding set a (key, rank) pair has a signature of its own, bit i = z[i] > tau[word_r][i]: hesaff_embed_device with
+ * d_words = the neighbours + 2 r and word_stride = 2 R, for a rank that every key has (r < K).
+ * HESAFF_OUT_WORDS in hesaff_process_files with R > 1: <image>.hesaff.words holds, for every key in key order, one row per present
+ * rank in ascending rank - the five floats of the key, the word of the rank - and <image>.hesaff.sigs is row for row with it; ranks
+ * absent because K < R are not written.  Such a file is an ordinary words file with up to R rows per key.
+ * HESAFF_ERR_ARG, with the setting and the last results as they were: ctx NULL, R outside 1..8, a getter's out pointer NULL, no
+ * vocabulary set (getters and operators), `image` outside the last host call's images, the addressing rules of
+ * hesaff_assign_words_device, n < 0. */
+int hesaff_set_vocabulary_neighbours(hesaff_ctx *ctx, int neighbours);
+int hesaff_get_vocabulary_neighbours(const hesaff_ctx *ctx, int *neighbours);
+int hesaff_get_neighbours(const hesaff_ctx *ctx, int image, const int32_t **neighbours, int *count, int *r);
+int hesaff_get_neighbours_device(const hesaff_ctx *ctx, const void **d_neighbours, int64_t *total, int *r);
+int hesaff_assign_neighbours_device(hesaff_ctx *ctx, int64_t n, const void *d_desc, int64_t stride, int64_t offset, void *d_neighbours_out);
+int hesaff_stage_assign_neighbours(hesaff_ctx *ctx, int n, const uint8_t *desc, int32_t *neighbours_out);
 
 /* Image index (no counterpart in the reference): an inverted file over visual words with tf-idf scoring, the consumer of the words
  * that hesaff_set_vocabulary assigns.  Symbols only, version 8.

@@ -330,6 +330,9 @@ def load_library():
         L.hesaff_get_index_growth_ms.argtypes = [vp] + [C.POINTER(C.c_float)] * 5
         L.hesaff_write_index_file.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, i64, i64, vp, vp, vp, vp, vp]
         L.hesaff_read_index_file.argtypes = [C.c_char_p] + [C.POINTER(C.c_int)] * 3 + [C.POINTER(i64)] * 2 + [C.POINTER(vp)] * 5
+    if hasattr(L, "hesaff_index_remove"):   # (likewise)
+        L.hesaff_index_remove.argtypes = [vp, C.c_int, vp, vp]
+        L.hesaff_get_index_remove_ms.argtypes = [vp] + [C.POINTER(C.c_float)] * 4
     if hasattr(L, "hesaff_index_query_batch"):   # (likewise)
         L.hesaff_index_query_batch.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int)]
         L.hesaff_index_query_batch_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int)]
@@ -402,6 +405,7 @@ ABI_SYMBOLS = [
     "hesaff_index_set_batch_budget", "hesaff_index_get_batch_budget", "hesaff_index_get_batch_chunks", "hesaff_get_index_batch_ms",
     "hesaff_set_vocabulary_neighbours", "hesaff_get_vocabulary_neighbours", "hesaff_get_neighbours", "hesaff_get_neighbours_device",
     "hesaff_assign_neighbours_device", "hesaff_stage_assign_neighbours",
+    "hesaff_index_remove", "hesaff_get_index_remove_ms",
 ]
 
 # hesaff_set_output_format's bits
@@ -1671,6 +1675,23 @@ class HesaffContext:
         """HIP-event times (insert, tables, merge, scatter) of the last add and (load) of the last load's device pass (profiling >= 1), in ms"""
         v = [C.c_float() for _ in range(5)]
         self._check(self.L.hesaff_get_index_growth_ms(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    # ---- removal from the index (hesaff_index_remove) ----
+    def remove_from_index(self, images):
+        """hesaff_index_remove: removes the images with the given numbers (distinct, in any order, at least one and not all) from the
+        context's index; the images that stay keep their order and are renumbered densely.  -> remap int32 [N]: the new number of
+        every old image, -1 for a removed one."""
+        n = self._need_index()[0]
+        gone = np.ascontiguousarray(np.asarray(images).reshape(-1), dtype=np.int32)
+        remap = np.zeros(n, np.int32)
+        self._check(self.L.hesaff_index_remove(self.h, len(gone), gone.ctypes.data if gone.size else None, remap.ctypes.data))
+        return remap
+
+    def index_remove_ms(self):
+        """HIP-event times (count, tables, compact, keys) of the last removal (profiling >= 1), in ms"""
+        v = [C.c_float() for _ in range(4)]
+        self._check(self.L.hesaff_get_index_remove_ms(self.h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
     def build_index_device(self, ptr, counts, word_stride, vocabulary_size):

@@ -446,6 +446,21 @@ struct AffineHessianDetector {
          throw std::invalid_argument("an embedded add needs an index built with signatures, at least one image, at most 2^20 images and 2^28 words with those of the index");
       if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
    }
+   // Removes the images with the given numbers from the detector's index (hesaff_index_remove): distinct, in any order, at least one
+   // and not all.  The images that stay keep their order and are renumbered densely; the index that results is the one buildIndex
+   // would make of them.  Returns the new number of every old image, -1 for a removed one.
+   std::vector<int32_t> removeFromIndex(const std::vector<int> &images)
+   {
+      int n = 0;
+      std::vector<int32_t> gone(images.begin(), images.end());
+      if (hesaff_index_get_info(ctx_, &n, nullptr, nullptr, nullptr) != HESAFF_OK) throw std::invalid_argument("a removal needs an index");
+      std::vector<int32_t> remap((size_t)n);
+      const int rc = hesaff_index_remove(ctx_, (int)gone.size(), gone.data(), remap.data());
+      if (rc == HESAFF_ERR_ARG)
+         throw std::invalid_argument("a removal needs an index, at least one image and fewer than the index holds, every number inside the index and given once");
+      if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+      return remap;
+   }
    // The index to and from an index file (hesaff_index_save, hesaff_index_load: "HESAFFI1"); a file that is refused leaves the index as it was
    void saveIndex(const char *path)
    {

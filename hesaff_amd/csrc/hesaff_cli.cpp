@@ -97,6 +97,10 @@
 //       loads the index, adds the listed files behind its images (hesaff_index_add; with their signatures files where the index is an
 //       embedded one) and rewrites <index file> and <index file>.list.  Both are written under temporary names and renamed when whole:
 //       a run that fails leaves the pair it found.
+//   hesaff --index <index file> --remove <list of paths> [--device D]
+//       loads the index, removes every image whose line of <index file>.list equals a listed path (hesaff_index_remove; a path listed
+//       twice counts once) and rewrites the pair likewise; the images that stay keep their order.  A path the list does not hold, an
+//       empty list and a removal that would leave no image print one line, exit 1 and leave both files as they were.
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -690,14 +694,32 @@ int run_search_mode(const char *list_path, const char *query_path, int top, int 
 // hesaff --index <index> --query <file>: the index is loaded (hesaff_index_load), not built; the result paths, and the candidates'
 // rows for --verify, are those of <index>.list.  hesaff --index <index> --add <list>: the listed words files (and their signatures
 // files where the index is an embedded one) are added behind the index's images (hesaff_index_add) and the pair is rewritten.
+// hesaff --index <index> --remove <list>: every line of <index>.list equal to a listed path is removed (hesaff_index_remove; a path
+// listed twice counts once) and the pair is rewritten.  A path the list does not hold, an empty list and a removal that would leave
+// no image end the run before the index is read.
 int run_index_mode(const char *index_path, const char *query_path, const char *add_path, int top, int device, bool verify, float tolerance, int max_pairs, int hamming,
-                   const char *queries_path = nullptr)
+                   const char *queries_path = nullptr, const char *remove_path = nullptr)
 {
    std::vector<std::string> names, more;
    const std::string list = std::string(index_path) + ".list";
    if (!read_list(list.c_str(), names)) return 1;
    if (add_path && !read_list(add_path, more)) return 1;
    if (add_path && more.empty()) { fprintf(stderr, "hesaff: list '%s' names no words file\n", add_path); return 1; }
+   std::vector<int32_t> gone;   // --remove: the numbers of the images that go
+   std::vector<std::string> kept;
+   if (remove_path) {
+      if (!read_list(remove_path, more)) return 1;
+      if (more.empty()) { fprintf(stderr, "hesaff: list '%s' names no image\n", remove_path); return 1; }
+      const std::set<std::string> named(more.begin(), more.end());
+      std::set<std::string> found;
+      for (size_t i = 0; i < names.size(); i++) {
+         if (named.count(names[i])) { gone.push_back((int32_t)i); found.insert(names[i]); }
+         else kept.push_back(names[i]);
+      }
+      for (const std::string &name : more)
+         if (!found.count(name)) { fprintf(stderr, "hesaff: '%s' holds no image '%s'\n", list.c_str(), name.c_str()); return 1; }
+      if (kept.empty()) { fprintf(stderr, "hesaff: removing every image of '%s' would leave no index\n", index_path); return 1; }
+   }
    hesaff_ctx *ctx = search_context(device);
    if (!ctx) return 1;
    DestroyContext destroy{ctx};
@@ -720,6 +742,13 @@ int run_index_mode(const char *index_path, const char *query_path, const char *a
       }
       names.insert(names.end(), more.begin(), more.end());
       return write_index_pair(ctx, index_path, names);
+   }
+   if (remove_path) {
+      if (hesaff_index_remove(ctx, (int)gone.size(), gone.data(), nullptr) != HESAFF_OK) {
+         fprintf(stderr, "hesaff: the images were not removed: %s\n", hesaff_last_error(ctx));
+         return 1;
+      }
+      return write_index_pair(ctx, index_path, kept);
    }
    if (hamming >= 0 && !embedded) { fprintf(stderr, "hesaff: '%s' holds no signatures: --hamming needs an index saved with --hamming\n", index_path); return 1; }
    if (queries_path) return answer_queries(ctx, names, k, queries_path, top, verify, tolerance, max_pairs, hamming);
@@ -746,7 +775,7 @@ int main(int argc, char **argv)
    bool batch_queries = false;   // --queries without --search or --index: the index form's usage error
    for (int i = 1; i < argc; i++) batch_queries = batch_queries || strcmp(argv[i], "--queries") == 0;
    if (search || from_index || batch_queries) {
-      const char *list = nullptr, *query = nullptr, *save = nullptr, *index = nullptr, *add = nullptr, *queries = nullptr;
+      const char *list = nullptr, *query = nullptr, *save = nullptr, *index = nullptr, *add = nullptr, *queries = nullptr, *gone = nullptr;
       long top = 10, device = 0, pairs = 1, hamming = -1;
       float tolerance = 8.0f;
       bool bad = false, verify = false, verify_options = false, query_options = false;
@@ -760,6 +789,7 @@ int main(int argc, char **argv)
          else if (strcmp(argv[i], "--save-index") == 0 && !save) save = argv[i + 1];
          else if (strcmp(argv[i], "--index") == 0 && !index) index = argv[i + 1];
          else if (strcmp(argv[i], "--add") == 0 && !add) add = argv[i + 1];
+         else if (strcmp(argv[i], "--remove") == 0 && !gone) gone = argv[i + 1];
          else if (strcmp(argv[i], "--top") == 0) { top = strtol(argv[i + 1], &end, 10); bad = end == argv[i + 1] || *end || top < 1 || top > 1024; query_options = true; }
          else if (strcmp(argv[i], "--device") == 0) { device = strtol(argv[i + 1], &end, 10); bad = end == argv[i + 1] || *end || device < 0 || device > 4095; }
          else if (strcmp(argv[i], "--hamming") == 0) { hamming = strtol(argv[i + 1], &end, 10); bad = end == argv[i + 1] || *end || hamming < 0 || hamming > HESAFF_EMBED_BITS; }
@@ -774,7 +804,7 @@ int main(int argc, char **argv)
       bad = bad || (verify_options && !verify);
       if (search) {
          // one of --query, --queries and --save-index; --save-index asks no query, so it takes none of the query's options
-         bad = bad || !list || index || add || (query != nullptr) + (queries != nullptr) + (save != nullptr) != 1 || (save && (verify || query_options));
+         bad = bad || !list || index || add || gone || (query != nullptr) + (queries != nullptr) + (save != nullptr) != 1 || (save && (verify || query_options));
          if (bad) {
             fprintf(stderr, "hesaff: usage: hesaff --search <list of .hesaff.words files> --query <.hesaff.words file> | --queries <list of .hesaff.words files> [--top 1..1024] [--device D] [--hamming 0..64] "
                             "[--verify [--tolerance PX] [--pairs 1..16]]   or   hesaff --search <list> --save-index <index file> [--device D] [--hamming 0..64]\n");
@@ -782,13 +812,16 @@ int main(int argc, char **argv)
          }
          return run_search_mode(list, query, (int)top, (int)device, verify, tolerance, (int)pairs, (int)hamming, save, queries);
       }
-      bad = bad || !index || save || (query != nullptr) + (queries != nullptr) + (add != nullptr) != 1 || (add && (verify || query_options || hamming >= 0));
+      // one of --query, --queries, --add and --remove; the last two take none of the query's options
+      bad = bad || !index || save || (query != nullptr) + (queries != nullptr) + (add != nullptr) + (gone != nullptr) != 1 ||
+            ((add || gone) && (verify || query_options || hamming >= 0));
       if (bad) {
          fprintf(stderr, "hesaff: usage: hesaff --index <index file> --query <.hesaff.words file> | --queries <list of .hesaff.words files> [--top 1..1024] [--device D] [--hamming 0..64] "
-                         "[--verify [--tolerance PX] [--pairs 1..16]]   or   hesaff --index <index file> --add <list of .hesaff.words files> [--device D]\n");
+                         "[--verify [--tolerance PX] [--pairs 1..16]]   or   hesaff --index <index file> --add <list of .hesaff.words files> [--device D]"
+                         "   or   hesaff --index <index file> --remove <list of paths of <index file>.list> [--device D]\n");
          return 1;
       }
-      return run_index_mode(index, query, add, (int)top, (int)device, verify, tolerance, (int)pairs, (int)hamming, queries);
+      return run_index_mode(index, query, add, (int)top, (int)device, verify, tolerance, (int)pairs, (int)hamming, queries, gone);
    }
    bool batch = false;
    for (int i = 1; i < argc; i++) batch = batch || strcmp(argv[i], "--batch") == 0;

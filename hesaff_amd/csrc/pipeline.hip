@@ -48,6 +48,7 @@
 #include "kernels_verify.h"
 #include "kernels_embed.h"
 #include "kernels_index_grow.h"
+#include "kernels_index_remove.h"
 #include "kernels_index_batch.h"
 #include "chunk_engine.h"
 #include "batch_plan.h"
@@ -523,6 +524,7 @@ struct hesaff_ctx {
    float embed_train_ms[3] = {0.0f, 0.0f, 0.0f};   // hesaff_get_embedding_ms: projection, grouping, medians of the last threshold training
    float index_ms[3] = {0.0f, 0.0f, 0.0f};   // hesaff_get_index_ms: the last build's hash step and list steps, the last query (profiling >= 1)
    float index_growth_ms[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // hesaff_get_index_growth_ms: the last add's insert, tables, merge, scatter; the last load's device pass
+   float index_remove_ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // hesaff_get_index_remove_ms: the last removal's counting pass, tables, compaction, key lists
    // hesaff_verify_matches: the result of the last call (verify_plan.h: VerifyResultArrays in `result`); no call: nothing here is
    // allocated, launched or copied
    struct Verify {
@@ -1788,4 +1790,5 @@ void pack_regions(hesaff_ctx *c, uint32_t n_hess, int B, hesaff_region *d_region
 #include "capi_verify.h"
 #include "capi_embed.h"
 #include "capi_index_grow.h"
+#include "capi_index_remove.h"
 #include "capi_index_batch.h"

@@ -61,6 +61,7 @@ extern "C" {
  *    And for the growing, durable index (hesaff_index_add and the nine symbols declared with it): symbols only, version 8.
  *    And for batched index queries (hesaff_index_query_batch and the seven symbols declared with it): symbols only, version 8.
  *    And for vocabulary neighbours (hesaff_set_vocabulary_neighbours and the five symbols declared with it): symbols only, version 8.
+ *    And for removal from the index (hesaff_index_remove, hesaff_get_index_remove_ms): symbols only, version 8.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -923,6 +924,30 @@ int hesaff_write_index_file(const char *path, int embedded, int vocabulary_size,
                             const uint32_t *postings, const uint32_t *key_count, const uint32_t *key_image, const uint64_t *key_sig);
 int hesaff_read_index_file(const char *path, int *embedded, int *vocabulary_size, int *n_images, int64_t *n_keys, int64_t *n_postings, uint32_t **df,
                            uint32_t **postings, uint32_t **key_count, uint32_t **key_image, uint64_t **key_sig);
+
+/* Removal from the index (no counterpart in the reference).  Symbols only, version 8.
+ * hesaff_index_remove(ctx, m, images, remap_out): images[m] are m distinct image numbers, in any order, 1 <= m <= N - 1, of the
+ * context's index of N images over K words (host memory; an index always holds at least one image - emptying it is
+ * hesaff_index_clear).  The images that stay keep their order and are renumbered densely: old image i becomes i - #{removed numbers
+ * below i}.  remap_out, where not NULL, receives int32[N]: the new number of every old image, -1 for a removed one; it is written
+ * only on success.  The index that results IS the index hesaff_index_build (hesaff_index_build_embedded for an embedded index, with
+ * the signatures the keys had) would make of the remaining images in that order: df, idf = ilog2_q8(N - m, df), the offsets and
+ * norm2 are equal bit for bit - the idf of every word changes with N, and with it the norm2 of every image that stays, which is
+ * summed again on the device - n_keys and n_postings are the rebuild's, and every posting list, and every key list of an embedded
+ * index, is equal as a multiset (no order inside a list is defined).  So a word whose last posting goes gets df 0 and idf 0, a word
+ * every remaining image holds gets idf 0, and a removed image without keys only renumbers and changes N.  Every query, embedded
+ * query at every T, batched query, add, save and load afterwards is bit for bit the rebuilt index's; the last query's dot and score
+ * read zero after a removal, as after a build or an add, and the batch scratch is released, as by an add.  "Replace image i" is a
+ * removal followed by an add.  A removal works on a new index and installs it when it is whole: its peak is the old index, the new
+ * one and a scratch of O(N + K) words, no hash table (index_remove_working_set_bytes, index_remove_plan.h: beside the old index at
+ * most 2.05 GiB for a plain index of N = K = 2^20 and 2^28 postings, 5.07 GiB for an embedded one of 2^28 keys).
+ * HESAFF_ERR_ARG, with the context's index, vocabulary and embedding byte for byte what they were and remap_out untouched: no index
+ * is built; ctx or images NULL; m < 1 or m >= N; a number outside 0 .. N - 1; a number given twice (hesaff_last_error names the
+ * number).  HESAFF_ERR_NOMEM: the device cannot hold the new index beside the old; the old one stays.
+ * hesaff_get_index_remove_ms: HIP-event times of the last removal at profiling level >= 1, 0 otherwise: its counting pass, its
+ * tables (idf and the scans), the compaction of the postings, and the key lists (0 for a plain index). */
+int hesaff_index_remove(hesaff_ctx *ctx, int m_images, const int32_t *images, int32_t *remap_out);
+int hesaff_get_index_remove_ms(const hesaff_ctx *ctx, float *count_ms, float *tables_ms, float *compact_ms, float *keys_ms);
 
 /* Batched index queries: many queries per call, ranked on the device.  Symbols only, version 8.
  * A batch is Q queries, 1 <= Q <= 2^16.  Query q has counts[q] words, 0 <= counts[q] <= 2^18, each in 0 .. K - 1; the total is at most

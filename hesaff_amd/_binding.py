@@ -296,6 +296,10 @@ def load_library():
         L.hesaff_stage_verify_pairs.argtypes = [vp, C.c_int, vp, C.c_float, vp, C.POINTER(C.c_int32)]
         L.hesaff_get_verify_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.hesaff_read_words_rows.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(L, "hesaff_expand_query"):   # (likewise)
+        L.hesaff_expand_query.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(C.c_int), vp]
+        L.hesaff_expand_query_device.argtypes = L.hesaff_expand_query.argtypes
+        L.hesaff_get_expand_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     if hasattr(L, "hesaff_set_embedding"):   # (likewise)
         i64 = C.c_int64
         L.hesaff_embedding_projection.argtypes = [C.c_uint64, vp]
@@ -406,6 +410,7 @@ ABI_SYMBOLS = [
     "hesaff_set_vocabulary_neighbours", "hesaff_get_vocabulary_neighbours", "hesaff_get_neighbours", "hesaff_get_neighbours_device",
     "hesaff_assign_neighbours_device", "hesaff_stage_assign_neighbours",
     "hesaff_index_remove", "hesaff_get_index_remove_ms",
+    "hesaff_expand_query", "hesaff_expand_query_device", "hesaff_get_expand_ms",
 ]
 
 # hesaff_set_output_format's bits
@@ -817,6 +822,36 @@ def _verify_rows(rows):
     if not isinstance(rows, np.ndarray) or rows.dtype != WORDS_ROW_DTYPE or rows.ndim != 1:
         raise ValueError("rows are a 1-d array of WORDS_ROW_DTYPE (what read_words returns)")
     return np.ascontiguousarray(rows)
+
+
+def _live_rows(rows):
+    """the LIVE rule of hesaff_verify_matches (include/hesaff_amd.h, step 1) on an array of WORDS_ROW_DTYPE -> bool [n]"""
+    F = np.float32
+    x, y, a, b, c = (rows[f].astype(F) for f in "xyabc")
+    lo, hi = F(2.0 ** -20), F(2.0 ** 20)
+    with np.errstate(all="ignore"):
+        r = np.sqrt(c); q = b / r; t = a - q * q; p = np.sqrt(t)
+        return (c > 0) & (t > 0) & (p >= lo) & (p <= hi) & (r >= lo) & (r <= hi) & (a <= F(2.0 ** 40)) & (np.abs(x) <= hi) & (np.abs(y) <= hi)
+
+
+def _expand_roi(roi, rows):
+    """the region of an expansion as float32 [4] = x0, y0, x1, y1; None: the bounding box of the query's live keys (zeros without one)"""
+    if roi is None:
+        if rows is None:
+            raise ValueError("rows in device memory need a roi")
+        k = rows[_live_rows(rows)]
+        roi = (k["x"].min(), k["y"].min(), k["x"].max(), k["y"].max()) if len(k) else (0, 0, 0, 0)
+    roi = np.ascontiguousarray(roi, dtype=np.float32)
+    if roi.shape != (4,):
+        raise ValueError("roi is (x0, y0, x1, y1)")
+    return roi
+
+
+def _expand_hypotheses(out, hyp, n_candidates):
+    out = np.ascontiguousarray(out, dtype=np.int32); hyp = np.ascontiguousarray(hyp, dtype=np.float32)
+    if out.shape != (n_candidates, 6) or hyp.shape != (n_candidates, 3):
+        raise ValueError("out is int32 [R, 6] and hyp float32 [R, 3], as verify_matches returns them for the same candidates")
+    return out, hyp
 
 
 def _index_words(w):
@@ -1898,6 +1933,78 @@ class HesaffContext:
         a, b = C.c_float(), C.c_float()
         self._check(self.L.hesaff_get_verify_ms(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    # ---- query expansion (hesaff_expand_query, include/hesaff_amd.h) ----
+    def expand_query(self, query_rows, candidates, out, hyp, vocabulary_size, min_inliers, max_images=1024, roi=None, max_rows=2 ** 18,
+                     query_signatures=None, candidate_signatures=None):
+        """hesaff_expand_query: the query's rows followed by the keys of the selected candidates (out[r][0] >= min_inliers, the best
+        max_images of them), back-projected by hyp[r] and kept where they fall into roi = (x0, y0, x1, y1) - None: the bounding box
+        of the query's live keys.  out and hyp are what verify_matches returned for the same query and candidates.
+        -> (rows of WORDS_ROW_DTYPE [n_out], info int32 [R, 4] = rank or -1, live, kept, written keys) and, with query_signatures
+        uint64 [nq] and candidate_signatures (a uint64 array per candidate), the signatures uint64 [n_out] as a third entry."""
+        q = _verify_rows(query_rows)
+        arrays = [_verify_rows(c) for c in candidates]
+        counts = np.array([len(a) for a in arrays], np.int32)
+        flat = np.ascontiguousarray(np.concatenate(arrays) if arrays else np.zeros(0, WORDS_ROW_DTYPE))
+        out, hyp = _expand_hypotheses(out, hyp, len(arrays))
+        roi = _expand_roi(roi, q)
+        if (query_signatures is None) != (candidate_signatures is None):
+            raise ValueError("signatures of the query and of the candidates go together")
+        qs = cs = sigs = None
+        cap = max(min(int(max_rows), len(q) + len(flat)), 1)
+        if query_signatures is not None:
+            if len(candidate_signatures) != len(arrays):
+                raise ValueError("one signature array per candidate")
+            qs = _signature_array(query_signatures, len(q))
+            sg = [_signature_array(g, len(a)) for g, a in zip(candidate_signatures, arrays)]
+            cs = np.ascontiguousarray(np.concatenate(sg) if sg else np.zeros(0, np.uint64))
+            sigs = np.zeros(cap, np.uint64)
+        rows = np.zeros(cap, WORDS_ROW_DTYPE); words = np.zeros(cap, np.int32); info = np.zeros((len(arrays), 4), np.int32); n = C.c_int(0)
+        self._check(self.L.hesaff_expand_query(self.h, len(q), q.ctypes.data if len(q) else None, qs.ctypes.data if qs is not None and len(q) else None,
+                                               len(arrays), counts.ctypes.data, flat.ctypes.data if len(flat) else None,
+                                               cs.ctypes.data if cs is not None and len(flat) else None, out.ctypes.data, hyp.ctypes.data, int(min_inliers),
+                                               int(max_images), roi.ctypes.data, int(vocabulary_size), int(max_rows), rows.ctypes.data, words.ctypes.data,
+                                               sigs.ctypes.data if sigs is not None else None, C.byref(n), info.ctypes.data))
+        if sigs is not None:
+            return rows[:n.value].copy(), info, sigs[:n.value].copy()
+        return rows[:n.value].copy(), info
+
+    def expand_query_device(self, query_ptr, nq, candidates_ptr, counts, out, hyp, vocabulary_size, min_inliers, roi, rows_out_ptr, words_out_ptr,
+                            max_images=1024, max_rows=2 ** 18, query_sigs_ptr=None, candidate_sigs_ptr=None, sigs_out_ptr=None):
+        """hesaff_expand_query_device: the same on rows (24 bytes each), signatures and outputs in device memory (raw pointers; the
+        outputs hold min(max_rows, nq + sum(counts)) entries); counts, out, hyp and roi on the host -> (n_out, info int32 [R, 4])."""
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        out, hyp = _expand_hypotheses(out, hyp, len(counts))
+        roi = _expand_roi(roi, None)
+        info = np.zeros((len(counts), 4), np.int32); n = C.c_int(0)
+        opt = lambda p: None if p is None else C.c_void_p(p)
+        self._check(self.L.hesaff_expand_query_device(self.h, int(nq), opt(query_ptr), opt(query_sigs_ptr), len(counts), counts.ctypes.data, opt(candidates_ptr),
+                                                      opt(candidate_sigs_ptr), out.ctypes.data, hyp.ctypes.data, int(min_inliers), int(max_images), roi.ctypes.data,
+                                                      int(vocabulary_size), int(max_rows), opt(rows_out_ptr), opt(words_out_ptr), opt(sigs_out_ptr), C.byref(n),
+                                                      info.ctypes.data))
+        return n.value, info
+
+    @property
+    def expand_ms(self):
+        """HIP-event times (flags with its scan, scatter) of the last expand call (profiling >= 1), in ms"""
+        a, b = C.c_float(), C.c_float()
+        self._check(self.L.hesaff_get_expand_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def query_index_expanded(self, query_rows, image_rows, top, tolerance, min_inliers, max_images=1024, max_pairs=1, roi=None, max_rows=2 ** 18):
+        """query -> verify -> expand -> query in one call.  image_rows[i] are the rows of index image i: the index keeps no geometry,
+        so the caller supplies it.  -> ((images, scores, out, order) of the first query and its verification, (images, scores) of the
+        query with the expanded rows, the expanded rows, info)."""
+        q = _verify_rows(query_rows)
+        k = self._need_index()[1]
+        images, scores = self.query_index(np.ascontiguousarray(q["word"].astype(np.int32)), top)
+        cands = [image_rows[int(i)] for i in images]
+        if not cands:
+            return (images, scores, np.zeros((0, 6), np.int32), np.zeros(0, np.int32)), (images, scores), q.copy(), np.zeros((0, 4), np.int32)
+        out, hyp, order = self.verify_matches(q, cands, k, tolerance, max_pairs)
+        rows, info = self.expand_query(q, cands, out, hyp, k, min_inliers, max_images=max_images, roi=roi, max_rows=max_rows)
+        second = self.query_index(np.ascontiguousarray(rows["word"].astype(np.int32)), top)
+        return (images, scores, out, order), second, rows, info
 
     def process_files(self, paths, out_paths=None, decode_threads=0, write_threads=0):
         """hesaff_process_files: image files -> <name>.hesaff.sift through the decode / device / write pipeline.

@@ -24,6 +24,7 @@
 // detectPyramidKeypoints takes the reference's own input, a CV_32FC1 plane (pyramid.h:73), or
 // the 8-bit image main() converts to one (hesaff.cpp:138-148).
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -503,6 +504,73 @@ struct AffineHessianDetector {
             (*results)[r] = {out[r * 6], out[r * 6 + 1], out[r * 6 + 2], out[r * 6 + 3], out[r * 6 + 4], out[r * 6 + 5], hyp[r * 3], hyp[r * 3 + 1], hyp[r * 3 + 2]};
       }
       return order;
+   }
+
+   // No counterpart in the reference (hesaff_expand_query, include/hesaff_amd.h): query expansion.  The rows of the query followed by
+   // the keys of the verified candidates - results[r].inliers >= minInliers, the best maxImages of them - back-projected into the
+   // query's frame by their maps and kept where they fall into roi = (x0, y0, x1, y1); `results` is what verifyMatches filled for the
+   // same query and candidates.  Returns the expanded rows (24 bytes each; at most maxRows of them), which queryIndex - by their
+   // words, `words`, where given - and verifyMatches take as they are; `info`, where given, receives one record per candidate.
+   // With signatures (both arrays, and sigsOut) they travel with the rows.
+   struct Expanded { int32_t rank, liveKeys, keptKeys, writtenKeys; };
+   std::vector<char> expandQuery(const void *queryRows, int nq, const std::vector<int32_t> &counts, const void *candidateRows, const std::vector<Verified> &results,
+                                 int vocabularySize, int minInliers, const float roi[4], int maxImages = 1024, int maxRows = 1 << 18,
+                                 std::vector<int32_t> *words = nullptr, std::vector<Expanded> *info = nullptr, const uint64_t *querySigs = nullptr,
+                                 const uint64_t *candidateSigs = nullptr, std::vector<uint64_t> *sigsOut = nullptr)
+   {
+      const size_t R = counts.size();
+      if (results.size() != R) throw std::invalid_argument("expansion takes one verified record per candidate");
+      std::vector<int32_t> out(R * 6 + 1), inf(R * 4 + 1);
+      std::vector<float> hyp(R * 3 + 1);
+      size_t cap = (size_t)std::max(nq, 0);
+      for (size_t r = 0; r < R; r++) {
+         const Verified &v = results[r];
+         const int32_t o[6] = {v.inliers, v.used, v.found, v.queryKey, v.candidateKey, v.inertKeys};
+         std::copy(o, o + 6, out.begin() + (std::ptrdiff_t)(r * 6));
+         hyp[r * 3] = v.L11; hyp[r * 3 + 1] = v.L21; hyp[r * 3 + 2] = v.L22;
+         cap += (size_t)std::max(counts[r], 0);
+      }
+      cap = std::max<size_t>(std::min<size_t>(cap, (size_t)std::max(maxRows, 0)), 1);
+      std::vector<char> rows(cap * 24);
+      std::vector<int32_t> w(cap);
+      if (sigsOut) sigsOut->assign(cap, 0);
+      int n = 0;
+      const int rc = hesaff_expand_query(ctx_, nq, queryRows, querySigs, (int)R, counts.data(), candidateRows, candidateSigs, out.data(), hyp.data(), minInliers, maxImages,
+                                         roi, vocabularySize, maxRows, rows.data(), w.data(), sigsOut ? sigsOut->data() : nullptr, &n, inf.data());
+      if (rc == HESAFF_ERR_ARG)
+         throw std::invalid_argument("expansion takes the arguments and the results of verifyMatches, minInliers >= 1, 1 <= maxImages <= 1024, a finite region within 2^20, "
+                                     "nq <= maxRows <= 2^18, and signatures for both sides or for neither");
+      if (rc != HESAFF_OK) throw std::runtime_error(hesaff_last_error(ctx_));
+      rows.resize((size_t)n * 24);
+      w.resize((size_t)n);
+      if (sigsOut) sigsOut->resize((size_t)n);
+      if (words) *words = w;
+      if (info) {
+         info->resize(R);
+         for (size_t r = 0; r < R; r++) (*info)[r] = {inf[r * 4], inf[r * 4 + 1], inf[r * 4 + 2], inf[r * 4 + 3]};
+      }
+      return rows;
+   }
+   // the bounding box of the LIVE rows (step 1 of hesaff_verify_matches) of a words file's rows: the region of an expansion that is given
+   // none.  false, and zeros, where no row is live.
+   static bool liveBounds(const void *rows, int n, float roi[4])
+   {
+      bool any = false;
+      roi[0] = roi[1] = roi[2] = roi[3] = 0.0f;
+      for (int i = 0; i < n; i++) {
+         float k[5];
+         std::memcpy(k, (const char *)rows + (size_t)i * 24, 20);
+         const float r = std::sqrt(k[4]);
+         const float q = k[3] / r;
+         const float qq = q * q;
+         const float t = k[2] - qq;
+         const float p = std::sqrt(t);
+         const float lo = 9.5367431640625e-07f, hi = 1048576.0f;
+         if (!(k[4] > 0.0f && t > 0.0f && p >= lo && p <= hi && r >= lo && r <= hi && k[2] <= 1099511627776.0f && std::fabs(k[0]) <= hi && std::fabs(k[1]) <= hi)) continue;
+         if (!any) { roi[0] = roi[2] = k[0]; roi[1] = roi[3] = k[1]; any = true; }
+         roi[0] = std::min(roi[0], k[0]); roi[1] = std::min(roi[1], k[1]); roi[2] = std::max(roi[2], k[0]); roi[3] = std::max(roi[3], k[1]);
+      }
+      return any;
    }
 
    // No counterpart in the reference (hesaff_set_next_masks, include/hesaff_amd.h; OpenCV's detect(image, keypoints, mask)): the NEXT

@@ -93,6 +93,12 @@
 //   hesaff --search <list> | --index <index file>  --queries <list of .hesaff.words files> [--top M] [--device D] [--hamming T] [--verify ...]
 //       in the place of --query: the listed files are ONE batch (hesaff_index_query_batch).  Per query, in list order, a line
 //       "# <query path>" and then exactly the lines --query prints for that file.  --query together with --queries is a usage error.
+//   hesaff --search <list> | --index <index file>  --query <.hesaff.words file> --verify [...] --expand [--min-inliers N] [--expand-images E]
+//       query expansion (hesaff_expand_query): behind the verified list a line "# expanded: <rows> rows from <images> images", then
+//       the list of a second query in the same line format - the query's rows and, back-projected into its frame and cut to the
+//       bounding box of its live rows, those of the E best shortlisted files (default 10, at most 1024) with at least N inliers
+//       (default 4) - verified with the expanded rows.  The expanded query repeats the words of those files, so the second list's inlier
+//       counts need --pairs above 1.  Needs --verify; with --queries a usage error.
 //   hesaff --index <index file> --add <list of .hesaff.words files> [--device D]
 //       loads the index, adds the listed files behind its images (hesaff_index_add; with their signatures files where the index is an
 //       embedded one) and rewrites <index file> and <index file>.list.  Both are written under temporary names and renamed when whole:
@@ -552,47 +558,105 @@ hesaff_ctx *search_context(int device)
 }
 struct DestroyContext { hesaff_ctx *c; ~DestroyContext() { hesaff_destroy(c); } };
 
+// the rows of a words file that states vocabulary size k, appended to `to`
+bool read_rows(const char *path, int k, std::vector<char> &to, int &n)
+{
+   void *p = nullptr;
+   int vs = 0;
+   if (hesaff_read_words_rows(path, &p, &n, &vs) != HESAFF_OK || vs != k) { fprintf(stderr, "hesaff: cannot read the rows of '%s'\n", path); hesaff_free(p); return false; }
+   to.insert(to.end(), (const char *)p, (const char *)p + (size_t)n * 24);
+   hesaff_free(p);
+   return true;
+}
+
+// a shortlist with the rows of its files, verified against a query's rows
+struct Shortlist {
+   std::vector<char> rows;
+   std::vector<int32_t> row_counts, out, order;
+   std::vector<float> hyp;
+};
+// --expand: the verified shortlist's best `images` files with at least `min_inliers` inliers extend the query
+struct ExpandOptions { int min_inliers, images; };
+
+// the verified list of `count` images on stdout; s keeps what the verification read and returned
+int print_verified(hesaff_ctx *ctx, const std::vector<std::string> &names, int k, const std::vector<char> &query_rows, int nq_rows, const int32_t *images,
+                   const double *scores, int count, float tolerance, int max_pairs, Shortlist &s)
+{
+   for (int r = 0; r < count; r++) {
+      int n = 0;
+      if (!read_rows(names[(size_t)images[(size_t)r]].c_str(), k, s.rows, n)) return 1;
+      s.row_counts.push_back(n);
+   }
+   s.out.resize((size_t)count * 6); s.order.resize((size_t)count); s.hyp.resize((size_t)count * 3);
+   if (hesaff_verify_matches(ctx, nq_rows, query_rows.data(), count, s.row_counts.data(), s.rows.data(), k, max_pairs, tolerance, s.out.data(), s.hyp.data(),
+                             s.order.data()) != HESAFF_OK) {
+      fprintf(stderr, "hesaff: the verification failed: %s\n", hesaff_last_error(ctx));
+      return 1;
+   }
+   for (int r = 0; r < count; r++) {
+      const size_t c = (size_t)s.order[(size_t)r];
+      printf("%d\t%s\t%.17g\t%d\n", r + 1, names[(size_t)images[c]].c_str(), scores[c], s.out[c * 6]);
+   }
+   return 0;
+}
+
 // the ranked list of one query - `count` images of the context's index, whose images are the files `names`, and their scores - on
-// stdout; with verify the verified list
+// stdout; with verify the verified list.  With expand (hesaff_expand_query, the region the bounding box of the query's live rows) a
+// line "# expanded: <rows> rows from <images> images" follows, and then the list of the expanded query, verified with the expanded
+// rows; with hamming >= 0 the signatures travel with the rows and the second query is an embedded one as the first was.
 int print_ranked(hesaff_ctx *ctx, const std::vector<std::string> &names, int k, const char *query_path, const int32_t *images, const double *scores, int count,
-                 bool verify, float tolerance, int max_pairs)
+                 bool verify, float tolerance, int max_pairs, const ExpandOptions *expand = nullptr, int top = 0, int hamming = -1, const uint64_t *qsigs = nullptr)
 {
    if (!verify) {
       for (int r = 0; r < count; r++) printf("%d\t%s\t%.17g\n", r + 1, names[(size_t)images[(size_t)r]].c_str(), scores[(size_t)r]);
       return 0;
    }
-   std::vector<char> rows, query_rows;
-   std::vector<int32_t> row_counts;
-   auto read_rows = [&](const char *path, std::vector<char> &to, int &n) {
-      void *p = nullptr;
-      int vs = 0;
-      if (hesaff_read_words_rows(path, &p, &n, &vs) != HESAFF_OK || vs != k) { fprintf(stderr, "hesaff: cannot read the rows of '%s'\n", path); hesaff_free(p); return false; }
-      to.insert(to.end(), (const char *)p, (const char *)p + (size_t)n * 24);
-      hesaff_free(p);
-      return true;
-   };
+   std::vector<char> query_rows;
    int nq_rows = 0;
-   if (!read_rows(query_path, query_rows, nq_rows)) return 1;
-   for (int r = 0; r < count; r++) {
-      int n = 0;
-      if (!read_rows(names[(size_t)images[(size_t)r]].c_str(), rows, n)) return 1;
-      row_counts.push_back(n);
-   }
-   std::vector<int32_t> out((size_t)count * 6), order((size_t)count);
-   if (hesaff_verify_matches(ctx, nq_rows, query_rows.data(), count, row_counts.data(), rows.data(), k, max_pairs, tolerance, out.data(), nullptr, order.data()) != HESAFF_OK) {
-      fprintf(stderr, "hesaff: the verification failed: %s\n", hesaff_last_error(ctx));
+   if (!read_rows(query_path, k, query_rows, nq_rows)) return 1;
+   Shortlist first;
+   const int rc = print_verified(ctx, names, k, query_rows, nq_rows, images, scores, count, tolerance, max_pairs, first);
+   if (rc != 0 || !expand) return rc;
+   WordsReader sigs;   // (--hamming: the signatures of the shortlisted files)
+   if (hamming >= 0)
+      for (int r = 0; r < count; r++)
+         if (!sigs.read_sigs(names[(size_t)images[(size_t)r]].c_str(), first.row_counts[(size_t)r])) return 1;
+   float roi[4];
+   hesaff_amd::AffineHessianDetector::liveBounds(query_rows.data(), nq_rows, roi);
+   const int max_rows = 1 << 18;
+   size_t cap = (size_t)nq_rows;
+   for (int32_t n : first.row_counts) cap += (size_t)n;
+   cap = std::max<size_t>(std::min<size_t>(cap, (size_t)max_rows), 1);
+   std::vector<char> rows(cap * 24);
+   std::vector<int32_t> words(cap), info((size_t)count * 4);
+   std::vector<uint64_t> sigs_out(hamming >= 0 ? cap : 0);
+   int n_out = 0;
+   if (hesaff_expand_query(ctx, nq_rows, query_rows.data(), hamming >= 0 ? qsigs : nullptr, count, first.row_counts.data(), first.rows.data(),
+                           hamming >= 0 ? sigs.sigs.data() : nullptr, first.out.data(), first.hyp.data(), expand->min_inliers, expand->images, roi, k, max_rows, rows.data(),
+                           words.data(), hamming >= 0 ? sigs_out.data() : nullptr, &n_out, info.data()) != HESAFF_OK) {
+      fprintf(stderr, "hesaff: the expansion failed: %s\n", hesaff_last_error(ctx));
       return 1;
    }
-   for (int r = 0; r < count; r++) {
-      const size_t c = (size_t)order[(size_t)r];
-      printf("%d\t%s\t%.17g\t%d\n", r + 1, names[(size_t)images[c]].c_str(), scores[c], out[c * 6]);
+   int selected = 0;
+   for (int r = 0; r < count; r++) selected += info[(size_t)r * 4] >= 0 ? 1 : 0;
+   printf("# expanded: %d rows from %d images\n", n_out, selected);
+   std::vector<int32_t> images2((size_t)top);
+   std::vector<double> scores2((size_t)top);
+   int count2 = 0;
+   const int asked = hamming < 0 ? hesaff_index_query(ctx, n_out, words.data(), 1, top, images2.data(), scores2.data(), &count2)
+                                 : hesaff_index_query_embedded(ctx, n_out, words.data(), 1, sigs_out.data(), hamming, top, images2.data(), scores2.data(), &count2);
+   if (asked != HESAFF_OK) {
+      fprintf(stderr, "hesaff: the expanded query failed: %s\n", hesaff_last_error(ctx));
+      return 1;
    }
-   return 0;
+   rows.resize((size_t)n_out * 24);
+   Shortlist second;
+   return print_verified(ctx, names, k, rows, n_out, images2.data(), scores2.data(), count2, tolerance, max_pairs, second);
 }
 
-// the query over the context's index; the ranked list (with verify: the verified list) on stdout
+// the query over the context's index; the ranked list (with verify: the verified list, with expand the second one as well) on stdout
 int answer_query(hesaff_ctx *ctx, const std::vector<std::string> &names, int k, const char *query_path, const int32_t *qwords, int n_query, const uint64_t *qsigs,
-                 int top, bool verify, float tolerance, int max_pairs, int hamming)
+                 int top, bool verify, float tolerance, int max_pairs, int hamming, const ExpandOptions *expand = nullptr)
 {
    std::vector<int32_t> images((size_t)top);
    std::vector<double> scores((size_t)top);
@@ -603,7 +667,7 @@ int answer_query(hesaff_ctx *ctx, const std::vector<std::string> &names, int k, 
       fprintf(stderr, "hesaff: the query failed: %s\n", hesaff_last_error(ctx));
       return 1;
    }
-   return print_ranked(ctx, names, k, query_path, images.data(), scores.data(), count, verify, tolerance, max_pairs);
+   return print_ranked(ctx, names, k, query_path, images.data(), scores.data(), count, verify, tolerance, max_pairs, expand, top, hamming, qsigs);
 }
 
 // hesaff ... --queries <list>: the listed words files (and with --hamming their signatures files) as ONE batch over the context's
@@ -665,7 +729,7 @@ int write_index_pair(hesaff_ctx *ctx, const char *index_path, const std::vector<
 // save_path == nullptr: hesaff --search <list> --query <file>, the index built for this one query.  Otherwise hesaff --search <list>
 // --save-index <index>: the index is built (an embedded one with --hamming) and written with its list; no query is asked.
 int run_search_mode(const char *list_path, const char *query_path, int top, int device, bool verify, float tolerance, int max_pairs, int hamming,
-                    const char *save_path = nullptr, const char *queries_path = nullptr)
+                    const char *save_path = nullptr, const char *queries_path = nullptr, const ExpandOptions *expand = nullptr)
 {
    std::vector<std::string> names;
    if (!read_list(list_path, names)) return 1;
@@ -688,7 +752,7 @@ int run_search_mode(const char *list_path, const char *query_path, int top, int 
    }
    if (save_path) return write_index_pair(ctx, save_path, names);
    if (queries_path) return answer_queries(ctx, names, in.k, queries_path, top, verify, tolerance, max_pairs, hamming);
-   return answer_query(ctx, names, in.k, query_path, in.words.data() + indexed, n_query, in.sigs.data() + indexed, top, verify, tolerance, max_pairs, hamming);
+   return answer_query(ctx, names, in.k, query_path, in.words.data() + indexed, n_query, in.sigs.data() + indexed, top, verify, tolerance, max_pairs, hamming, expand);
 }
 
 // hesaff --index <index> --query <file>: the index is loaded (hesaff_index_load), not built; the result paths, and the candidates'
@@ -698,7 +762,7 @@ int run_search_mode(const char *list_path, const char *query_path, int top, int 
 // listed twice counts once) and the pair is rewritten.  A path the list does not hold, an empty list and a removal that would leave
 // no image end the run before the index is read.
 int run_index_mode(const char *index_path, const char *query_path, const char *add_path, int top, int device, bool verify, float tolerance, int max_pairs, int hamming,
-                   const char *queries_path = nullptr, const char *remove_path = nullptr)
+                   const char *queries_path = nullptr, const char *remove_path = nullptr, const ExpandOptions *expand = nullptr)
 {
    std::vector<std::string> names, more;
    const std::string list = std::string(index_path) + ".list";
@@ -755,7 +819,7 @@ int run_index_mode(const char *index_path, const char *query_path, const char *a
    in.with_sigs = hamming >= 0;
    int n_query = 0;
    if (!in.read(query_path, n_query)) return 1;
-   return answer_query(ctx, names, k, query_path, in.words.data(), n_query, in.sigs.data(), top, verify, tolerance, max_pairs, hamming);
+   return answer_query(ctx, names, k, query_path, in.words.data(), n_query, in.sigs.data(), top, verify, tolerance, max_pairs, hamming, expand);
 }
 
 } // namespace
@@ -776,11 +840,12 @@ int main(int argc, char **argv)
    for (int i = 1; i < argc; i++) batch_queries = batch_queries || strcmp(argv[i], "--queries") == 0;
    if (search || from_index || batch_queries) {
       const char *list = nullptr, *query = nullptr, *save = nullptr, *index = nullptr, *add = nullptr, *queries = nullptr, *gone = nullptr;
-      long top = 10, device = 0, pairs = 1, hamming = -1;
+      long top = 10, device = 0, pairs = 1, hamming = -1, min_inliers = 4, expand_images = 10;
       float tolerance = 8.0f;
-      bool bad = false, verify = false, verify_options = false, query_options = false;
+      bool bad = false, verify = false, verify_options = false, query_options = false, expand = false, expand_options = false;
       for (int i = 1; i < argc && !bad; i += 2) {
-         if (strcmp(argv[i], "--verify") == 0 && !verify) { verify = true; i -= 1; continue; }   // (the one option without a value)
+         if (strcmp(argv[i], "--verify") == 0 && !verify) { verify = true; i -= 1; continue; }   // (the two options without a value)
+         if (strcmp(argv[i], "--expand") == 0 && !expand) { expand = true; i -= 1; continue; }
          if (i + 1 >= argc) { bad = true; break; }
          char *end = nullptr;
          if (strcmp(argv[i], "--search") == 0 && !list) list = argv[i + 1];
@@ -798,30 +863,41 @@ int main(int argc, char **argv)
             bad = end == argv[i + 1] || *end || !(tolerance > 0.0f && tolerance <= 1048576.0f);
             verify_options = true;
          }
+         else if (strcmp(argv[i], "--min-inliers") == 0) {
+            min_inliers = strtol(argv[i + 1], &end, 10);
+            bad = end == argv[i + 1] || *end || min_inliers < 1 || min_inliers > 2147483647L;
+            expand_options = true;
+         }
+         else if (strcmp(argv[i], "--expand-images") == 0) {
+            expand_images = strtol(argv[i + 1], &end, 10);
+            bad = end == argv[i + 1] || *end || expand_images < 1 || expand_images > 1024;
+            expand_options = true;
+         }
          else if (strcmp(argv[i], "--pairs") == 0) { pairs = strtol(argv[i + 1], &end, 10); bad = end == argv[i + 1] || *end || pairs < 1 || pairs > 16; verify_options = true; }
          else bad = true;
       }
-      bad = bad || (verify_options && !verify);
+      bad = bad || (verify_options && !verify) || (expand_options && !expand) || (expand && (!verify || !query));
+      const ExpandOptions expand_with = {(int)min_inliers, (int)expand_images};
       if (search) {
          // one of --query, --queries and --save-index; --save-index asks no query, so it takes none of the query's options
          bad = bad || !list || index || add || gone || (query != nullptr) + (queries != nullptr) + (save != nullptr) != 1 || (save && (verify || query_options));
          if (bad) {
             fprintf(stderr, "hesaff: usage: hesaff --search <list of .hesaff.words files> --query <.hesaff.words file> | --queries <list of .hesaff.words files> [--top 1..1024] [--device D] [--hamming 0..64] "
-                            "[--verify [--tolerance PX] [--pairs 1..16]]   or   hesaff --search <list> --save-index <index file> [--device D] [--hamming 0..64]\n");
+                            "[--verify [--tolerance PX] [--pairs 1..16] [--expand [--min-inliers N] [--expand-images 1..1024]]]   or   hesaff --search <list> --save-index <index file> [--device D] [--hamming 0..64]\n");
             return 1;
          }
-         return run_search_mode(list, query, (int)top, (int)device, verify, tolerance, (int)pairs, (int)hamming, save, queries);
+         return run_search_mode(list, query, (int)top, (int)device, verify, tolerance, (int)pairs, (int)hamming, save, queries, expand ? &expand_with : nullptr);
       }
       // one of --query, --queries, --add and --remove; the last two take none of the query's options
       bad = bad || !index || save || (query != nullptr) + (queries != nullptr) + (add != nullptr) + (gone != nullptr) != 1 ||
             ((add || gone) && (verify || query_options || hamming >= 0));
       if (bad) {
          fprintf(stderr, "hesaff: usage: hesaff --index <index file> --query <.hesaff.words file> | --queries <list of .hesaff.words files> [--top 1..1024] [--device D] [--hamming 0..64] "
-                         "[--verify [--tolerance PX] [--pairs 1..16]]   or   hesaff --index <index file> --add <list of .hesaff.words files> [--device D]"
+                         "[--verify [--tolerance PX] [--pairs 1..16] [--expand [--min-inliers N] [--expand-images 1..1024]]]   or   hesaff --index <index file> --add <list of .hesaff.words files> [--device D]"
                          "   or   hesaff --index <index file> --remove <list of paths of <index file>.list> [--device D]\n");
          return 1;
       }
-      return run_index_mode(index, query, add, (int)top, (int)device, verify, tolerance, (int)pairs, (int)hamming, queries, gone);
+      return run_index_mode(index, query, add, (int)top, (int)device, verify, tolerance, (int)pairs, (int)hamming, queries, gone, expand ? &expand_with : nullptr);
    }
    bool batch = false;
    for (int i = 1; i < argc; i++) batch = batch || strcmp(argv[i], "--batch") == 0;

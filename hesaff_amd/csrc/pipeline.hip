@@ -46,6 +46,7 @@
 #include "kernels_cells.h"
 #include "kernels_index.h"
 #include "kernels_verify.h"
+#include "kernels_expand.h"
 #include "kernels_embed.h"
 #include "kernels_index_grow.h"
 #include "kernels_index_remove.h"
@@ -59,6 +60,7 @@
 #include "cells_plan.h"
 #include "index_plan.h"
 #include "verify_plan.h"
+#include "expand_plan.h"
 #include "embed_plan.h"
 
 static thread_local std::string g_create_error;
@@ -538,6 +540,7 @@ struct hesaff_ctx {
       template <class T> T *ptr(const Span<T> &s) const { return result.at<T>(s.off); }
    } verify;
    float verify_ms[2] = {0.0f, 0.0f};        // hesaff_get_verify_ms: the pair steps and the hypothesis steps of the last call (profiling >= 1)
+   float expand_ms[2] = {0.0f, 0.0f};        // hesaff_get_expand_ms: the flags pass with its scan, and the scatter, of the last call (profiling >= 1)
    ArmedMasks next_masks;              // hesaff_set_next_masks / _device: the masks of the next detecting call (taken, so cleared, by take_masks)
    int stage_threads = 4;              // host threads that copy a chunk's pixels into pinned memory (hesaff_process_files: within its thread budget)
    DevEvent ev_detect_done, ev_batch_done;   // blocking-sync events: the host sleeps instead of spinning
@@ -1788,6 +1791,7 @@ void pack_regions(hesaff_ctx *c, uint32_t n_hess, int B, hesaff_region *d_region
 #include "capi_cells.h"
 #include "capi_index.h"
 #include "capi_verify.h"
+#include "capi_expand.h"
 #include "capi_embed.h"
 #include "capi_index_grow.h"
 #include "capi_index_remove.h"

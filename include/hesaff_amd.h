@@ -62,6 +62,7 @@ extern "C" {
  *    And for batched index queries (hesaff_index_query_batch and the seven symbols declared with it): symbols only, version 8.
  *    And for vocabulary neighbours (hesaff_set_vocabulary_neighbours and the five symbols declared with it): symbols only, version 8.
  *    And for removal from the index (hesaff_index_remove, hesaff_get_index_remove_ms): symbols only, version 8.
+ *    And for query expansion (hesaff_expand_query, hesaff_expand_query_device, hesaff_get_expand_ms): symbols only, version 8.
  * Image sizes: a side of at most 65535 pixels at the first pyramid level, and sqrt(width x height) of at most about 27900 (the largest window
  * normalizeAffine could ask for, affine.cpp:114-124, must fit a compute unit's LDS as one row): HESAFF_ERR_ARG beyond. */
 #define HESAFF_ABI_VERSION 8
@@ -1049,6 +1050,74 @@ int hesaff_verify_get_query_inert(const hesaff_ctx *ctx, int *n);
 int hesaff_stage_verify_pairs(hesaff_ctx *ctx, int m, const float *pairs, float tolerance, int32_t *inl_out, int32_t *best_out);
 int hesaff_get_verify_ms(const hesaff_ctx *ctx, float *pairs_ms, float *hypotheses_ms);
 int hesaff_read_words_rows(const char *path, void **rows, int *count, int *vocabulary_size);
+
+/* Query expansion (no counterpart in the reference): the keys of the verified candidates of a shortlist, back-projected into the
+ * query's frame by each candidate's affinity, cut to the query's region and appended to the query - the average query expansion of
+ * Chum, Philbin, Sivic, Isard and Zisserman, "Total Recall" (ICCV 2007), over the 5-dof maps hesaff_verify_matches returns.  The
+ * result is an ordinary array of words-file rows, which the index and the verifier take unchanged.  Symbols only, version 8.
+ * The rules of the verification block hold: binary32, no FMA contraction, operations left to right, one per statement, / and sqrtf
+ * the IEEE operations, a comparison with a NaN false; frame, LIVE and the row are those of step 1 there.
+ * Inputs: a query of nq rows and R candidates of counts[r] rows, concatenated, within the bounds of hesaff_verify_matches; K =
+ * vocabulary_size, every word < K; a uint64 signature per query row and per candidate row, for both sides or for neither;
+ * verify_out[R][6] and hyp[R][3] exactly as hesaff_verify_matches returns them - arguments of the caller, no context state, so that
+ * constructed hypotheses can be expanded; min_inliers >= 1; max_images in 1..1024; roi[4] = (x0, y0, x1, y1) in the query's frame,
+ * finite, |v| <= 2^20, x0 <= x1, y0 <= y1; max_rows with nq <= max_rows <= 2^18, the query limit of the index and of the verifier.
+ *  1. Candidate r is ELIGIBLE iff verify_out[r][0] >= min_inliers.  The SELECTED candidates are the first min(max_images, eligible)
+ *     eligible ones in the order (inliers descending, r ascending); the position in that order is the rank s.  Of a candidate that
+ *     is not eligible nothing but the inlier count is read: its hyp may hold anything.  An eligible candidate - selected or cut by
+ *     max_images - must have 0 <= query_key < nq, 0 <= candidate_key < counts[r], both anchor rows live, 2^-40 <= L11 <= 2^40,
+ *     2^-40 <= L22 <= 2^40 and |L21| <= 2^81 (the range the verification block derives; false for a NaN): otherwise the call is
+ *     refused with HESAFF_ERR_ARG and hesaff_last_error names the lowest such r.
+ *  2. Back-projection of key j of a selected candidate, anchors (xq_h, yq_h) = query row query_key, (xd_h, yd_h) = candidate row
+ *     candidate_key:
+ *        dx = xd_j - xd_h;  dy = yd_j - yd_h;  u = dx / L11;  t = L21 * u;  s = dy - t;  v = s / L22;  x' = xq_h + u;  y' = yq_h + v
+ *     and, since x_d - x_dh = L (x_q - x_qh), the ellipse E' = L^T E L:
+ *        m0 = a * L11;  m1 = b * L21;  e00 = m0 + m1;  m2 = b * L11;  m3 = c * L21;  e10 = m2 + m3;  e01 = b * L22;  e11 = c * L22
+ *        n0 = L11 * e00;  n1 = L21 * e10;  a' = n0 + n1;  n2 = L11 * e01;  n3 = L21 * e11;  b' = n2 + n3;  c' = L22 * e11
+ *  3. Key j is KEPT iff it is live, x0 <= x' <= x1, y0 <= y' <= y1 and the frame of (x', y', a', b', c') is live: an expanded row
+ *     is always a row the verifier accepts.
+ *  4. The expanded query: the nq query rows byte for byte, inert ones included, then the kept rows { x', y', a', b', c', word } in
+ *     the order (rank s ascending, j ascending).  Exactly n_out = min(nq + kept_total, max_rows) rows are written: the cut falls on
+ *     the weakest selected candidates' highest keys.  The signatures, where given, travel row for row, and words_out[n_out] holds
+ *     the words alone (hesaff_index_query takes stride 1 or 2, not 6).
+ *  5. info[R][4] = (s or -1, live keys, kept keys, written keys) per candidate; zeros behind the -1 of a candidate that is not selected,
+ *     whose rows are not read.
+ * Range: for live keys |dx|, |dy| <= 2^21, and L11 >= 2^-40, so u is finite, |u| <= 2^61, and x' is finite.  |t| <= 2^81 * 2^61
+ * exceeds binary32: t, s, v and y' may be +-inf, but never NaN - no product has a zero beside an infinity (L21 and u are finite),
+ * no sum has two infinities (dy and yq_h are finite), and L22 is finite and positive.  An infinite y' fails the region test.  a' and
+ * b' can be NaN (inf - inf from a, b, c <= 2^40 times maps up to 2^81, squared); the frame of a NaN is not live, so the key is
+ * dropped.  No value forms an address.
+ * It follows that the anchor key itself maps to (xq_h, yq_h) exactly (dx = dy = 0 gives u = t = s = v = 0); that with L = (1, 0, 1)
+ * and coordinates that are small integers a shifted copy of the query back-projects to the query's own rows bit for bit; and that a
+ * call that selects nothing returns the query unchanged, n_out = nq.
+ * The only accumulations are integer counts, and the position of a row follows from counts alone: the same input gives the same
+ * bytes whatever the launch geometry.
+ * hesaff_expand_query: rows, signatures and the three outputs in host memory; rows_out, words_out (and sigs_out, with signatures)
+ * hold min(max_rows, nq + sum(counts)) entries.  sigs_out non-NULL says that signatures are given: then query_sigs (nq > 0) and
+ * candidate_sigs (sum(counts) > 0) are required, and without it both must be NULL.  info_out may be NULL.  The words are checked
+ * while staging; only the selected candidates' rows are copied to the device.
+ * hesaff_expand_query_device: rows, signatures and the three outputs in device memory (rows and words 4-byte, signatures 8-byte
+ * aligned), sized as above; counts, verify_out, hyp, roi, n_out and info_out in host memory.  A read-only kernel checks the words.
+ * Its outputs feed hesaff_index_query_device(words_out, n_out, 1, ...) and hesaff_verify_matches_device(rows_out, n_out, ...) as
+ * they are.
+ * hesaff_get_expand_ms: HIP-event times of the last call at profiling level >= 1 - the flags pass with its scan, the scatter - 0
+ * otherwise.
+ * Expansion is no context state: it reads and changes neither the vocabulary, nor the index, nor the result of the last verify
+ * call; its scratch (8 bytes per 64 rows of the selected candidates for the masks, 4 for the bases, 40 per selected candidate; in
+ * the host form the staged rows and outputs as well) is released before the call returns, and without a call nothing is launched,
+ * allocated or copied.
+ * HESAFF_ERR_ARG, nothing changed, the outputs untouched, the context usable as before: ctx NULL; a required pointer NULL; a count or
+ * bound outside the ranges above; a word >= K; signatures on one side only; a roi that is not finite, out of range or inverted; a
+ * misaligned device pointer; a broken eligible candidate.  HESAFF_ERR_NOMEM: the device cannot hold the scratch. */
+int hesaff_expand_query(hesaff_ctx *ctx, int nq, const void *query_rows, const uint64_t *query_sigs, int n_candidates, const int32_t *counts,
+                        const void *candidate_rows, const uint64_t *candidate_sigs, const int32_t *verify_out, const float *hyp, int min_inliers,
+                        int max_images, const float *roi, int vocabulary_size, int max_rows, void *rows_out, int32_t *words_out,
+                        uint64_t *sigs_out, int *n_out, int32_t *info_out);
+int hesaff_expand_query_device(hesaff_ctx *ctx, int nq, const void *d_query_rows, const void *d_query_sigs, int n_candidates, const int32_t *counts,
+                               const void *d_candidate_rows, const void *d_candidate_sigs, const int32_t *verify_out, const float *hyp,
+                               int min_inliers, int max_images, const float *roi, int vocabulary_size, int max_rows, void *d_rows_out,
+                               void *d_words_out, void *d_sigs_out, int *n_out, int32_t *info_out);
+int hesaff_get_expand_ms(const hesaff_ctx *ctx, float *flags_ms, float *scatter_ms);
 
 /* Same path with inputs already resident in device memory (bench / pipelines that decode
  * on the GPU): d_gray = n contiguous height x width 8-bit grey planes (device pointer).

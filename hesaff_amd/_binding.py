@@ -223,6 +223,8 @@ def load_library():
     L.hesaff_stage_detect_planes.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
     L.hesaff_stage_find_affine_shape.argtypes = [vp, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _f32p, _i32p]
     L.hesaff_stage_rectify.argtypes = [vp, C.c_int, _f32p]
+    if hasattr(L, "hesaff_stage_affine_tail"):   # (absent from an older build loaded through HESAFF_AMD_LIB for a comparison)
+        L.hesaff_stage_affine_tail.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _f32p, _i32p]
     L.hesaff_stage_normalize_affine.argtypes = [vp, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _i32p, _f32p]
     L.hesaff_stage_sift.argtypes = [vp, C.c_int, _f32p, _u8p]
     L.hesaff_stage_sift_parts.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, _u8p]
@@ -370,7 +372,7 @@ ABI_SYMBOLS = [
     "hesaff_detect_batch", "hesaff_detect_batch_device", "hesaff_set_profiling", "hesaff_get_timings", "hesaff_ellipse",
     "hesaff_write_sift", "hesaff_format_sift", "hesaff_free", "hesaff_read_pnm", "hesaff_stage_gaussian_blur",
     "hesaff_stage_hessian_response", "hesaff_stage_half_image", "hesaff_stage_pyramid", "hesaff_stage_hessian_keypoints",
-    "hesaff_stage_find_affine_shape", "hesaff_stage_rectify", "hesaff_stage_normalize_affine", "hesaff_stage_sift",
+    "hesaff_stage_find_affine_shape", "hesaff_stage_rectify", "hesaff_stage_affine_tail", "hesaff_stage_normalize_affine", "hesaff_stage_sift",
     "hesaff_stage_math", "hesaff_stage_math_sift", "hesaff_stage_sift_parts", "hesaff_stage_sift_alive", "hesaff_stage_math_sift_general", "hesaff_table_gauss_mask", "hesaff_table_circ_gauss_mask", "hesaff_table_sift_bins",
     "hesaff_table_gauss_kernel", "hesaff_format_sift_mt", "hesaff_write_sift_batch", "hesaff_test_fmt_g",
     "hesaff_read_png", "hesaff_read_image", "hesaff_device_count", "hesaff_shard_range", "hesaff_read_jpeg",
@@ -2122,6 +2124,18 @@ class HesaffContext:
         A = np.ascontiguousarray(A, np.float32).reshape(-1, 4).copy()
         self._check(self.L.hesaff_stage_rectify(self.h, len(A), A))
         return A
+
+    def affine_tail(self, abc, U, ratio_bef):
+        """One pass of findAffineShape's tail (affine.cpp:72-97) per row, with the context's convergenceThreshold.
+        -> abc'[n,3], U'[n,4], ratio[n], l[n,4] (l1, l2 of invSqrt, then of getEigenvalues), state[n] (0 continue, 1 break, 2 converged)"""
+        abc = np.ascontiguousarray(abc, np.float32).reshape(-1, 3).copy(); U = np.ascontiguousarray(U, np.float32).reshape(-1, 4).copy()
+        ratio = np.ascontiguousarray(ratio_bef, np.float32).reshape(-1).copy()
+        n = len(abc)
+        if len(U) != n or len(ratio) != n:
+            raise ValueError("affine_tail: abc, U and ratio_bef must have one row per operand set")
+        l = np.zeros((n, 4), np.float32); state = np.zeros(n, np.int32)
+        self._check(self.L.hesaff_stage_affine_tail(self.h, n, abc, U, ratio, l, state))
+        return abc, U, ratio, l, state
 
     def normalize_affine(self, img, kp, A):
         img = np.ascontiguousarray(img, np.float32); kp = np.ascontiguousarray(kp, np.float32).reshape(-1, 3)

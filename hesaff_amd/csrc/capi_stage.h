@@ -306,6 +306,32 @@ int hesaff_stage_rectify(hesaff_ctx *c, int n, float *A)
    HS_API_END(c)
 }
 
+// hs_affine_tail (k_affine's tail: kernels_keypoint.h) on caller-supplied operands, with the context's convergenceThreshold
+int hesaff_stage_affine_tail(hesaff_ctx *c, int n, float *abc, float *U, float *ratio, float *l, int32_t *state)
+{
+   if (!c || n < 0 || (n > 0 && (!abc || !U || !ratio || !l || !state))) return HESAFF_ERR_ARG;
+   HS_API_BEGIN
+   bind_device(c);
+   if (n == 0) return HESAFF_OK;
+   const size_t N = (size_t)n;
+   StageArena a(c);
+   const Span<float> a_abc = a.add<float>(3 * N), a_U = a.add<float>(4 * N), a_ratio = a.add<float>(N), a_l = a.add<float>(4 * N);
+   const Span<int32_t> a_state = a.add<int32_t>(N);
+   a.ensure();
+   a.upload(a_abc, (const float *)abc);
+   a.upload(a_U, (const float *)U);
+   a.upload(a_ratio, (const float *)ratio);
+   hipLaunchKernelGGL(k_affine_tail_stage, dim3((n + 255) / 256), dim3(256), 0, c->stream(), n, c->ct.consts.convergenceThreshold, a.ptr(a_abc), a.ptr(a_U),
+                      a.ptr(a_ratio), a.ptr(a_l), a.ptr(a_state));
+   a.download(abc, a_abc);
+   a.download(U, a_U);
+   a.download(ratio, a_ratio);
+   a.download(l, a_l);
+   a.download(state, a_state);
+   finish_stream(c);
+   HS_API_END(c)
+}
+
 // normalizeAffine for caller-supplied keypoints: reuses the batch kernels through a
 // one-image plan whose Hessian list is filled from the arguments.
 int hesaff_stage_normalize_affine(hesaff_ctx *c, const float *img, int rows, int cols, int n, const float *kp, const float *A,

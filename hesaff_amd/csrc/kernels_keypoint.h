@@ -88,6 +88,26 @@ __device__ inline bool hs_window_outside(int imRows, int imCols, float ofsx, flo
 // Every keypoint goes through the operations of the single-keypoint form on the same operands in the same order.
 // block = 64 threads (one wavefront), LDS 4 x 3 x 364 floats + mask + 16 records + s_abc (19.5 KB: eight blocks per CU).
 // ---------------------------------------------------------------------------------------
+// One pass of the iteration's tail, affine.cpp:72-97, on the three sums a, b, c of a keypoint: invSqrt, the eigen ratio, the U update
+// (n = [a b; b c] * u), getEigenvalues and the two decisions.  a, b, c leave as invSqrt's; l1, l2 as invSqrt's where getEigenvalues
+// refuses, else as getEigenvalues'.  Returns 0 continue, 1 break (rejected), 2 converged.
+__device__ __forceinline__ int hs_affine_tail(float &a, float &b, float &c, float u11, float u12, float u21, float u22, float &eigen_ratio_act,
+                                              float &eigen_ratio_bef, float convergenceThreshold, float &l1, float &l2, float &n11, float &n12,
+                                              float &n21, float &n22)
+{
+   hs_inv_sqrt(a, b, c, l1, l2);
+   eigen_ratio_bef = eigen_ratio_act;
+   eigen_ratio_act = 1 - l2 / l1;
+   const float u11t = u11, u12t = u12;
+   n11 = a * u11t + b * u21; n12 = a * u12t + b * u22;
+   n21 = b * u11t + c * u21; n22 = b * u12t + c * u22;
+   int state = 0;
+   if (!hs_eigenvalues(n11, n12, n21, n22, l1, l2)) state = 1;
+   else if ((l1 / l2 > 6) || (l2 / l1 > 6)) state = 1;
+   else if (eigen_ratio_act < convergenceThreshold && eigen_ratio_bef < convergenceThreshold) state = 2;
+   return state;
+}
+
 #define HS_AFF_SLOTS 16   // keypoints a wavefront iterates on at a time; the launch sites size their grids by it
 // consecutive keypoints a block takes from the list at a time.  Alone on the device, per 32 UHD images: 16 -> 22.1 ms, 4 -> 19.2 ms,
 // 1 -> 18.2 ms (the four-group form: 21.1 ms).  All blocks of a launch are resident, so the launch lasts as long as its largest share.
@@ -284,17 +304,8 @@ __device__ __forceinline__ void hs_affine_groups(uint32_t first, uint32_t n, con
       bool finished = false;
       if (active) {   // the tail: one lane per active slot
          float a = s_abc[lane][0], b = s_abc[lane][1], c = s_abc[lane][2];
-         float l1, l2;
-         hs_inv_sqrt(a, b, c, l1, l2);
-         eigen_ratio_bef = eigen_ratio_act;
-         eigen_ratio_act = 1 - l2 / l1;
-         const float u11t = u11, u12t = u12;
-         const float n11 = a * u11t + b * u21, n12 = a * u12t + b * u22;
-         const float n21 = b * u11t + c * u21, n22 = b * u12t + c * u22;
-         int state = 0;   // 0 continue, 1 break (rejected), 2 converged
-         if (!hs_eigenvalues(n11, n12, n21, n22, l1, l2)) state = 1;
-         else if ((l1 / l2 > 6) || (l2 / l1 > 6)) state = 1;
-         else if (eigen_ratio_act < k.convergenceThreshold && eigen_ratio_bef < k.convergenceThreshold) state = 2;
+         float l1, l2, n11, n12, n21, n22;
+         const int state = hs_affine_tail(a, b, c, u11, u12, u21, u22, eigen_ratio_act, eigen_ratio_bef, k.convergenceThreshold, l1, l2, n11, n12, n21, n22);
          u11 = n11; u12 = n12; u21 = n21; u22 = n22;
          if (state != 0 || l + 1 >= k.maxIterations) {
             // affine.cpp:88-99: converged -> onAffineShapeFound(..., l); otherwise the keypoint is dropped
@@ -348,6 +359,26 @@ __global__ __launch_bounds__(64) void k_affine_stage(DPlane P, const float *__re
       q.x = kp[4 * h]; q.y = kp[4 * h + 1]; q.s = kp[4 * h + 2]; q.pd = kp[4 * h + 3];
       return q;
    });
+}
+
+// hs_affine_tail on caller-supplied operands, thread per row: abc[n][3] and U[n][4] in and out, ratio[n] in (eigen_ratio_act of the
+// pass before) and out, l[n][4] = l1, l2 of invSqrt then l1, l2 as the tail leaves them, state[n] (0 continue, 1 rejected, 2 converged)
+__global__ void k_affine_tail_stage(int n, float convergenceThreshold, float *abc, float *U, float *ratio, float *l, int32_t *state)
+{
+   const int i = blockIdx.x * blockDim.x + threadIdx.x;
+   if (i >= n) return;
+   float a = abc[3 * i], b = abc[3 * i + 1], c = abc[3 * i + 2];
+   float eigen_ratio_act = ratio[i], eigen_ratio_bef = 0.0f;
+   float l1, l2, n11, n12, n21, n22;
+   // (invSqrt's l1, l2: the tail's first statement, once more, since the tail goes on to overwrite them)
+   { float a0 = a, b0 = b, c0 = c; hs_inv_sqrt(a0, b0, c0, l1, l2); l[4 * i] = l1; l[4 * i + 1] = l2; }
+   const int st = hs_affine_tail(a, b, c, U[4 * i], U[4 * i + 1], U[4 * i + 2], U[4 * i + 3], eigen_ratio_act, eigen_ratio_bef, convergenceThreshold,
+                                 l1, l2, n11, n12, n21, n22);
+   abc[3 * i] = a; abc[3 * i + 1] = b; abc[3 * i + 2] = c;
+   U[4 * i] = n11; U[4 * i + 1] = n12; U[4 * i + 2] = n21; U[4 * i + 3] = n22;
+   ratio[i] = eigen_ratio_act;
+   l[4 * i + 2] = l1; l[4 * i + 3] = l2;
+   state[i] = st;
 }
 
 // ---------------------------------------------------------------------------------------

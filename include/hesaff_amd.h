@@ -1292,6 +1292,12 @@ int hesaff_stage_find_affine_shape(hesaff_ctx *ctx, const float *blur, int rows,
                                    const float *kp, int32_t *converged, float *U, int32_t *iters);
 /* rectifyAffineTransformationUpIsUp helpers.cpp:90-97 for n matrices (in place, A[n][4]) */
 int hesaff_stage_rectify(hesaff_ctx *ctx, int n, float *A);
+/* One pass of findAffineShape's tail, affine.cpp:72-97 (invSqrt, the eigen ratio, the U update, getEigenvalues and the two decisions;
+ * the device function k_affine calls), for n rows of operands, with the context's convergenceThreshold.  In and out, in place:
+ * abc[n][3] (the three sums; out: as invSqrt leaves them), U[n][4], ratio[n] (in: eigen_ratio_act of the pass before; out: this pass's).
+ * Out: l[n][4] = l1, l2 of invSqrt, then l1, l2 of getEigenvalues (invSqrt's again where it returns false); state[n] = 0 continue,
+ * 1 break (no real eigenvalues, or l1 / l2 beyond 6), 2 converged.  Every float value is accepted. */
+int hesaff_stage_affine_tail(hesaff_ctx *ctx, int n, float *abc, float *U, float *ratio, float *l, int32_t *state);
 /* AffineShape::normalizeAffine affine.cpp:102-144 for n keypoints on one image.
  * kp[n][3] = x,y,s; A[n][4] rectified; out: rejected[n] (1 = reference returned true),
  * patches[n][41*41]. */

@@ -446,6 +446,15 @@ struct TraceRec {
 };
 inline uint32_t bitsOf(float v) { uint32_t u; memcpy(&u, &v, 4); return u; }
 
+// The ways findAffineShape leaves its loop (affine.cpp:81-97), and the states of one pass of its tail.  Test infrastructure
+// (tests/test_affine_edges.py), like the trace above.
+enum AffExit { AX_CONVERGED = 0, AX_NO_REAL_EIGEN = 1 /* getEigenvalues false */, AX_ANISOTROPY = 2 /* l1/l2 > 6 */, AX_MAX_ITER = 3 };
+enum AffTailState { AT_CONTINUE = 0, AT_NO_REAL_EIGEN = 1, AT_ANISOTROPY = 2, AT_CONVERGED = 3 };
+// words of one iteration's record: bits of a, b, c before invSqrt [0..2] and after it [3..5], its l1, l2 [6, 7], eigen_ratio_act [8],
+// U after the update [9..12], l1, l2 of getEigenvalues [13, 14], the largest finite |tap coordinate| [15]; then two integers: taps that
+// fell outside [16], AffTailState [17]
+enum { AFT_WORDS = 18 };
+
 struct AffRes {   // result of findAffineShape (affine.cpp:35-100)
    int converged;
    float a11, a12, a21, a22;
@@ -677,6 +686,91 @@ struct Oracle {
          }
       }
       return res;
+   }
+
+   // One pass of affine.cpp:72-97 on given operands (the part of the loop above between the three sums and the next interpolate):
+   // invSqrt, the eigen ratio, the U update, getEigenvalues and the two decisions.  Test infrastructure (tests/test_affine_edges.py).
+   // abc: in a, b, c; out a', b', c'.  U: in / out.  ratio: in eigen_ratio_act of the pass before, out this pass's.  thr: convergenceThreshold.
+   // l[4] = l1, l2 of invSqrt, then l1, l2 as getEigenvalues left them (unchanged where it returned false).
+   static int affineTail(float *abc, float *U, float *ratio, float thr, float *l)
+   {
+      float l1 = 1.0f, l2 = 1.0f;
+      invSqrt(abc[0], abc[1], abc[2], l1, l2);
+      l[0] = l1; l[1] = l2;
+      const float eigen_ratio_bef = *ratio;
+      const float eigen_ratio_act = 1 - l2 / l1;
+      *ratio = eigen_ratio_act;
+      const float a = abc[0], b = abc[1], c = abc[2];
+      const float u11t = U[0], u12t = U[1], u21t = U[2], u22t = U[3];
+      U[0] = a * u11t + b * u21t; U[1] = a * u12t + b * u22t;
+      U[2] = b * u11t + c * u21t; U[3] = b * u12t + c * u22t;
+      int state = AT_CONTINUE;
+      if (!getEigenvalues(U[0], U[1], U[2], U[3], l1, l2)) state = AT_NO_REAL_EIGEN;
+      else if ((l1 / l2 > 6) || (l2 / l1 > 6)) state = AT_ANISOTROPY;
+      else if (eigen_ratio_act < thr && eigen_ratio_bef < thr) state = AT_CONVERGED;
+      l[2] = l1; l[3] = l2;
+      return state;
+   }
+
+   // findAffineShape with a record of every iteration it enters (AFT_WORDS 32-bit words each, at most `cap` of them are stored) and of
+   // the way it leaves.  The same loop on the same functions: tests assert that it ends in findAffineShape's own result.
+   int affineTrace(const Plane &blur, float x, float y, float s, float pixelDistance, int cap, uint32_t *rec, int *nIter, float *Uexit)
+   {
+      float eigen_ratio_act = 0.0f;
+      float U[4] = {1.0f, 0.0f, 0.0f, 1.0f};
+      const float lx = x / pixelDistance, ly = y / pixelDistance;
+      const float ratio = s / (par.affInitialSigma * pixelDistance);
+      const int W = par.smmWindowSize, maskPixels = W * W, half = W >> 1;
+      std::vector<float> img(maskPixels);
+      int exitKind = AX_MAX_ITER;
+      int l = 0;
+      for (; l < par.maxIterations; l++) {
+         const float a11 = U[0] * ratio, a12 = U[1] * ratio, a21 = U[2] * ratio, a22 = U[3] * ratio;
+         interpolate(blur, lx, ly, a11, a12, a21, a22, img.data(), W, W);
+         // the tap coordinates once more (helpers.cpp:221-226), for the counts only
+         uint32_t nOutside = 0;
+         float maxCoord = 0.0f;
+         for (int j = -half; j <= half; ++j) {
+            const float rx = lx + j * a12;
+            const float ry = ly + j * a22;
+            for (int i = -half; i <= half; ++i) {
+               const float wx = rx + i * a11;
+               const float wy = ry + i * a21;
+               const int px = floorToInt(wx), py = floorToInt(wy);
+               if (!(px >= 0 && py >= 0 && px < blur.cols - 1 && py < blur.rows - 1)) nOutside++;
+               if (std::isfinite(wx) && fabsf(wx) > maxCoord) maxCoord = fabsf(wx);
+               if (std::isfinite(wy) && fabsf(wy) > maxCoord) maxCoord = fabsf(wy);
+            }
+         }
+         float abc[3] = {0, 0, 0};
+         for (int i = 0; i < maskPixels; ++i) {
+            float gxx, gyy;
+            gradAt(img.data(), W, i / W, i % W, gxx, gyy);
+            const float v = smmMask[i];
+            const float gxy = gxx * gyy;
+            abc[0] += gxx * gxx * v;
+            abc[1] += gxy * v;
+            abc[2] += gyy * gyy * v;
+         }
+         abc[0] /= maskPixels; abc[1] /= maskPixels; abc[2] /= maskPixels;
+         uint32_t *r = (l < cap) ? rec + (size_t)AFT_WORDS * l : nullptr;
+         if (r) for (int q = 0; q < 3; q++) r[q] = bitsOf(abc[q]);
+         float lam[4];
+         const int state = affineTail(abc, U, &eigen_ratio_act, par.convergenceThreshold, lam);
+         if (r) {
+            for (int q = 0; q < 3; q++) r[3 + q] = bitsOf(abc[q]);
+            r[6] = bitsOf(lam[0]); r[7] = bitsOf(lam[1]); r[8] = bitsOf(eigen_ratio_act);
+            for (int q = 0; q < 4; q++) r[9 + q] = bitsOf(U[q]);
+            r[13] = bitsOf(lam[2]); r[14] = bitsOf(lam[3]); r[15] = bitsOf(maxCoord);
+            r[16] = nOutside; r[17] = (uint32_t)state;
+         }
+         if (state == AT_NO_REAL_EIGEN) { exitKind = AX_NO_REAL_EIGEN; l++; break; }
+         if (state == AT_ANISOTROPY) { exitKind = AX_ANISOTROPY; l++; break; }
+         if (state == AT_CONVERGED) { exitKind = AX_CONVERGED; l++; break; }
+      }
+      *nIter = l;   // iterations entered
+      for (int q = 0; q < 4; q++) Uexit[q] = U[q];
+      return exitKind;
    }
 
    // affine.cpp:102-144 ; returns true when the keypoint is REJECTED (like the reference)
@@ -1051,6 +1145,21 @@ int ho_h_find_affine_shape(void *h, const float *blur, int rows, int cols, float
    const AffRes a = ((Oracle *)h)->findAffineShape(p, x, y, s, pd);
    A[0] = a.a11; A[1] = a.a12; A[2] = a.a21; A[3] = a.a22; *iters = a.iters;
    return a.converged;
+}
+// findAffineShape with its trace (Oracle::affineTrace): returns the exit kind (AffExit); rec[cap][AFT_WORDS] receives the first cap
+// iterations' records, *n_iter the iterations entered, U_exit[4] the matrix at the exit
+int ho_h_affine_trace(void *h, const float *blur, int rows, int cols, float x, float y, float s, float pd, int cap, unsigned *rec, int *n_iter,
+                      float *U_exit)
+{
+   Plane p(rows, cols);
+   memcpy(p.d.data(), blur, sizeof(float) * rows * cols);
+   return ((Oracle *)h)->affineTrace(p, x, y, s, pd, cap, rec, n_iter, U_exit);
+}
+// n passes of the tail (Oracle::affineTail) with convergenceThreshold thr: abc[n][3] and U[n][4] in and out, ratio[n] in
+// (eigen_ratio_act of the pass before) and out, l[n][4], state[n] (AffTailState)
+void ho_affine_tail(int n, float *abc, float *U, float *ratio, float thr, float *l, int *state)
+{
+   for (int i = 0; i < n; i++) state[i] = Oracle::affineTail(abc + 3 * (size_t)i, U + 4 * (size_t)i, ratio + i, thr, l + 4 * (size_t)i);
 }
 int ho_h_normalize_affine(void *h, const float *img, int rows, int cols, float x, float y, float s, const float *A, float *patch)
 {

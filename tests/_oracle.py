@@ -85,6 +85,9 @@ def lib():
     L.ho_num_trace.argtypes = [C.c_void_p]; L.ho_num_trace.restype = C.c_int
     L.ho_get_trace.argtypes = [C.c_void_p, i32p, u32p]
     L.ho_get_thresholds.argtypes = [C.c_void_p, f32p]
+    L.ho_h_affine_trace.argtypes = [C.c_void_p, f32p, C.c_int, C.c_int] + [C.c_float] * 4 + [C.c_int, u32p, i32p, f32p]
+    L.ho_h_affine_trace.restype = C.c_int
+    L.ho_affine_tail.argtypes = [C.c_int, f32p, f32p, f32p, C.c_float, f32p, i32p]
     _lib = L
     return L
 
@@ -129,6 +132,14 @@ class OracleHandle:
         conv = lib().ho_h_find_affine_shape(self.h, blur, blur.shape[0], blur.shape[1], float(x), float(y), float(s), float(pd), A, it)
         return conv, A, int(it[0])
 
+    def affine_trace(self, blur, x, y, s, pd, cap=64):
+        """findAffineShape with a record per iteration entered -> AffineTrace"""
+        blur = np.ascontiguousarray(blur, np.float32)
+        rec = np.zeros((cap, AFT_WORDS), np.uint32); n = np.zeros(1, np.int32); U = np.zeros(4, np.float32)
+        kind = lib().ho_h_affine_trace(self.h, blur, blur.shape[0], blur.shape[1], float(x), float(y), float(s), float(pd), cap,
+                                       rec.reshape(-1), n, U)
+        return AffineTrace(kind, int(n[0]), U, rec[:min(int(n[0]), cap)].copy())
+
     def sift(self, patch):
         p = np.ascontiguousarray(patch, np.float32).reshape(-1).copy()
         vec = np.zeros(128, np.float32)
@@ -141,6 +152,43 @@ class OracleHandle:
         mv = np.zeros(2, np.float32); hist = np.zeros(128, np.float32); vec = np.zeros(128, np.float32)
         lib().ho_h_sift_parts(self.h, p, mv, hist, vec)
         return mv, hist, vec.astype(np.uint8)
+
+
+# exits of findAffineShape (AffExit), the states of one pass of its tail (AffTailState) and an iteration's record (AFT_WORDS)
+AX_CONVERGED, AX_NO_REAL_EIGEN, AX_ANISOTROPY, AX_MAX_ITER = range(4)
+AX_NAMES = ["converged", "no-real-eigen", "anisotropy", "max-iter"]
+AT_CONTINUE, AT_NO_REAL_EIGEN, AT_ANISOTROPY, AT_CONVERGED = range(4)
+AFT_WORDS = 18
+
+
+class AffineTrace:
+    """kind (AX_*), n_iter (iterations entered), U (the matrix at the exit), and per iteration entered: abc_in[3], abc[3], l[2] (invSqrt's),
+    ratio (eigen_ratio_act), Us[4] (U after the update), ev[2] (getEigenvalues' l1, l2), max_coord (largest finite |tap coordinate|) as
+    float32 arrays over the bits the oracle had; outside (taps that fell outside) and state (AT_*) as integers."""
+
+    def __init__(self, kind, n_iter, U, rec):
+        f = rec.view(np.float32)
+        self.kind = kind; self.n_iter = n_iter; self.U = U
+        self.abc_in = f[:, 0:3]; self.abc = f[:, 3:6]; self.l = f[:, 6:8]; self.ratio = f[:, 8]; self.Us = f[:, 9:13]
+        self.ev = f[:, 13:15]; self.max_coord = f[:, 15]
+        self.outside = rec[:, 16].astype(np.int64); self.state = rec[:, 17].astype(np.int64)
+
+    def result(self):
+        """what findAffineShape returns for this trace: (converged, U, iters), zeros where it reports no shape"""
+        if self.kind == AX_CONVERGED:
+            return 1, self.U.copy(), self.n_iter - 1
+        return 0, np.zeros(4, np.float32), 0
+
+
+def affine_tail(abc, U, ratio_bef, thr):
+    """one pass of affine.cpp:72-97 per row -> abc'[n,3], U'[n,4], ratio[n], l[n,4], state[n] (AT_*)"""
+    abc = np.ascontiguousarray(abc, np.float32).reshape(-1, 3).copy(); U = np.ascontiguousarray(U, np.float32).reshape(-1, 4).copy()
+    ratio = np.ascontiguousarray(ratio_bef, np.float32).reshape(-1).copy()
+    n = len(abc)
+    assert len(U) == n and len(ratio) == n
+    l = np.zeros((n, 4), np.float32); state = np.zeros(n, np.int32)
+    lib().ho_affine_tail(n, abc.reshape(-1), U.reshape(-1), ratio, float(np.float32(thr)), l.reshape(-1), state)
+    return abc, U, ratio, l, state
 
 
 # exits of localizeKeypoint in a trace record (TraceExit, oracle/hesaff_oracle.cpp)

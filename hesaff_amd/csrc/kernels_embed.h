@@ -8,7 +8,7 @@
 // (r = l & 31, h = l >> 5) holds, for step s, bytes [32 s + 16 h, + 16) of key r, XORed with 0x80 (d' = d - 128 as signed bytes).  P
 // is packed once (embed_pack_projection, embed_plan.h) as two 32-row tiles in the same lane order, not XORed: it is signed already.
 // Eight v_mfma_i32_32x32x32_i8 per key tile give P.d' for the 64 rows and 32 keys; z = P.d' + bias[row], bias = 128 * rowsum(P), and
-// every term stays inside int32 (|P.d'|, |bias| < 2^21).  Accumulator element e of lane l is row (e & 3) + 8 (e >> 2) + 4 h of the
+// every term stays inside int32 (|P.d'|, |bias| < 2^21).  Accumulator element e of lane l is row hs_word_row(e, h) of the
 // tile and key r: a lane holds 16 rows per tile of its key, in four runs of four, so it reads its key's thresholds tau[word][..] - 256
 // contiguous bytes per key - as four 16-byte loads per tile, folds its compares into a 64-bit mask, ORs it with lane l ^ 32's (the
 // other 32 rows) and the lower lane writes the key's 8 bytes.  RAW: the test seam, z itself instead of the bits.
@@ -60,24 +60,20 @@ __global__ __launch_bounds__(HS_EMBED_BLOCK_WAVES * 64) void k_embed_keys(const 
    for (int t = 0; t < 2; t++)
 #pragma unroll
       for (int s = 0; s < 4; s++) a[t][s] = tiles[(size_t)(t * 4 + s) * 64 + lane];
-   // the bias of the lane's 16 rows of a tile: rows 8 g + 4 h .. + 3 for g = 0..3
+   // the bias of the lane's 16 rows of a tile: four runs of four
    hs_v4i bs[2][4];
 #pragma unroll
    for (int t = 0; t < 2; t++)
 #pragma unroll
-      for (int g = 0; g < 4; g++) bs[t][g] = *(const hs_v4i *)(bias + 32 * t + 8 * g + 4 * h);
+      for (int g = 0; g < 4; g++) bs[t][g] = *(const hs_v4i *)(bias + 32 * t + hs_word_row(4 * g, h));
 
 #pragma unroll
    for (int j = 0; j < 2; j++) {
       // a lane beyond the last key reads the last key again and stores nothing
       const long long key = key0 + 32 * j + r;
       const long long src = min(key, n - 1);
-      const uint32_t *p = (const uint32_t *)(desc + src * stride + offset + 16 * h);
       hs_v4i kf[4];
-#pragma unroll
-      for (int s = 0; s < 4; s++)
-#pragma unroll
-         for (int q = 0; q < 4; q++) kf[s][q] = (int)(p[8 * s + q] ^ 0x80808080u);
+      hs_key_load(desc, src, stride, offset, h, kf);
       const int32_t *th = RAW ? nullptr : tau + (size_t)words[(size_t)src * word_stride] * 64;
       unsigned long long bits = 0ull;
 #pragma unroll
@@ -87,7 +83,7 @@ __global__ __launch_bounds__(HS_EMBED_BLOCK_WAVES * 64) void k_embed_keys(const 
          for (int s = 0; s < 4; s++) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[t][s], kf[s], acc, 0, 0, 0);
 #pragma unroll
          for (int g = 0; g < 4; g++) {
-            const int row0 = 32 * t + 8 * g + 4 * h;   // the lane's rows row0 .. row0 + 3: accumulator elements 4 g .. 4 g + 3
+            const int row0 = 32 * t + hs_word_row(4 * g, h);   // the lane's rows row0 .. row0 + 3: accumulator elements 4 g .. 4 g + 3
             if (RAW) {
                if (key < n) {
                   hs_v4i z;

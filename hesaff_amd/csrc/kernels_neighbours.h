@@ -2,16 +2,13 @@
 // lexicographically least pairs (dist2(k), k) over the rows of the vocabulary, ascending, in ONE pass over the vocabulary.  Rank 0 is
 // what k_assign_words (kernels_words.h) gives, bit for bit: the same integers, the same order.
 //
-// k_assign_neighbours keeps k_assign_words' frame: a wavefront owns 64 keys (two 32-key column tiles) whose fragments stay in
-// registers, the packed vocabulary is streamed once in tiles of 32 rows loaded one tile ahead, four v_mfma_i32_32x32x32_i8 per key
-// tile and word tile, key = column of C (lane & 31), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5), score = |w'_k|^2 - 2 d'.w'_k.
+// k_assign_neighbours is the frame of kernels_words.h - keys and stream - with another memory.  k_assign_words keeps a running best
+// per accumulator ELEMENT (2 x 16 x 2 registers); R of them per element would be 64 R registers.  Here a lane keeps, per key tile, ONE
+// list of CAP >= R pairs (score, k) sorted ascending - 2 x 2 x CAP registers, 32 at CAP = 8 - over all the rows it sees: 16 of every
+// tile.  A key's rows are split between lanes l and l ^ 32, so its R least pairs lie in the union of the two lists' first R entries;
+// the last step merges them across the halves.
 //
-// What differs is what a lane remembers.  k_assign_words keeps a running best per accumulator ELEMENT (2 x 16 x 2 registers); R of
-// them per element would be 64 R registers.  Here a lane keeps, per key tile, ONE list of CAP >= R pairs (score, k) sorted ascending
-// - 2 x 2 x CAP registers, 32 at CAP = 8 - over all the rows it sees: 16 of every tile.  A key's rows are split between lanes l and
-// l ^ 32, so its R least pairs lie in the union of the two lists' first R entries; the last step merges them across the halves.
-//
-// The hot loop pays one compare per element, score <= the score of the list's last entry.  Only where it fires is the pair decided
+// The visit pays one compare per element, score <= the score of the list's last entry.  Only where it fires is the pair decided
 // exactly - rows do NOT reach a lane in ascending k (within a tile they come in element order, and the order of insertion is free
 // anyway), so a tie in score is decided by k, never by strict < - and inserted by CAP compare-and-shift steps with static indices.  A
 // list keeps CAP entries even where R < CAP: the surplus entries are candidates that cannot be wrong, and only the first R are written.
@@ -55,63 +52,24 @@ __global__ __launch_bounds__(HS_WORD_BLOCK_WAVES * 64) void k_assign_neighbours(
    const long long key0 = ((long long)blockIdx.x * HS_WORD_BLOCK_WAVES + wave) * HS_WORD_WAVE_KEYS;
    if (key0 >= n) return;   // (wave-uniform)
 
-   // the keys' fragments and the lane's half of |d'|^2, by k_assign_words' rule; a lane beyond the last key reads the last key again
+   // a lane beyond the last key reads the last key again and stores nothing
    hs_v4i kf[2][4];
    int knorm[2];
-#pragma unroll
-   for (int j = 0; j < 2; j++) {
-      const long long key = min(key0 + 32 * j + r, n - 1);
-      const uint32_t *p = (const uint32_t *)(desc + key * stride + offset + 16 * h);
-      int sq = 0;
-#pragma unroll
-      for (int s = 0; s < 4; s++)
-#pragma unroll
-         for (int q = 0; q < 4; q++) {
-            const uint32_t v = p[8 * s + q] ^ 0x80808080u;
-            kf[j][s][q] = (int)v;
-            sq += hs_sq4_i8(v);
-         }
-      knorm[j] = sq + __shfl_xor(sq, 32, 64);
-   }
-
    int ls[2][CAP], lk[2][CAP];
 #pragma unroll
-   for (int j = 0; j < 2; j++)
+   for (int j = 0; j < 2; j++) {
+      hs_key_load(desc, min(key0 + 32 * j + r, n - 1), stride, offset, h, kf[j]);
+      knorm[j] = hs_key_norm(kf[j]);
 #pragma unroll
       for (int i = 0; i < CAP; i++) { ls[j][i] = 0x7fffffff; lk[j][i] = 0x7fffffff; }
-
-   hs_v4i a[4], nr[4];
-#pragma unroll
-   for (int s = 0; s < 4; s++) a[s] = tiles[(size_t)s * 64 + lane];
-#pragma unroll
-   for (int g = 0; g < 4; g++) nr[g] = *(const hs_v4i *)(norms + 8 * g + 4 * h);
-   for (int t = 0; t < n_tiles; t++) {
-      hs_v4i a_next[4], nr_next[4];
-      const int tn = min(t + 1, n_tiles - 1);
-#pragma unroll
-      for (int s = 0; s < 4; s++) a_next[s] = tiles[((size_t)tn * 4 + s) * 64 + lane];
-#pragma unroll
-      for (int g = 0; g < 4; g++) nr_next[g] = *(const hs_v4i *)(norms + (size_t)tn * HS_WORD_TILE + 8 * g + 4 * h);
-      const int k_base = t * HS_WORD_TILE + 4 * h;
-#pragma unroll
-      for (int j = 0; j < 2; j++) {
-         hs_v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-         for (int s = 0; s < 4; s++) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], kf[j][s], acc, 0, 0, 0);
-#pragma unroll
-         for (int e = 0; e < 16; e++) {
-            const int score = nr[e >> 2][e & 3] - 2 * acc[e];
-            if (score <= ls[j][CAP - 1]) {   // rare once the list is warm; the exact decision, by (score, k), is the insertion's
-               const int k = k_base + (e & 3) + 8 * (e >> 2);
-               hs_neigh_insert<CAP>(ls[j], lk[j], score, k);
-            }
-         }
-      }
-#pragma unroll
-      for (int s = 0; s < 4; s++) a[s] = a_next[s];
-#pragma unroll
-      for (int g = 0; g < 4; g++) nr[g] = nr_next[g];
    }
+
+   hs_word_stream(tiles, norms, 0, n_tiles - 1, lane, kf, [&](int t, int j, int (&score)[16]) {
+#pragma unroll
+      for (int e = 0; e < 16; e++)
+         if (score[e] <= ls[j][CAP - 1])   // rare once the list is warm; the exact decision, by (score, k), is the insertion's
+            hs_neigh_insert<CAP>(ls[j], lk[j], score[e], t * HS_WORD_TILE + hs_word_row(e, h));
+   });
 
 #pragma unroll
    for (int j = 0; j < 2; j++) {

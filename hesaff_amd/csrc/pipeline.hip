@@ -1316,13 +1316,22 @@ struct GroupDevice : ScheduleDevice {
    }
 };
 
+// The launch of a kernel over the frame of kernels_words.h: one wavefront per work item, HS_WORD_BLOCK_WAVES to a block
+template <class Kernel, class... Args>
+void launch_word_kernel(Kernel kernel, hipStream_t st, long long waves, Args... args)
+{
+   const long long blocks = (waves + HS_WORD_BLOCK_WAVES - 1) / HS_WORD_BLOCK_WAVES;
+   hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(HS_WORD_BLOCK_WAVES * 64), 0, st, args...);
+}
+// the wavefronts of the flat kernels: HS_WORD_WAVE_KEYS keys each
+long long word_waves(long long n) { return (n + HS_WORD_WAVE_KEYS - 1) / HS_WORD_WAVE_KEYS; }
+
 // k_assign_words against a packed vocabulary of n_tiles tiles (the context's, or the private one of a training call), n >= 1
 void launch_assign_kernel(hipStream_t st, const void *tiles, const void *norms, int n_tiles, const void *d_desc, long long n, long long stride, long long offset,
                           void *d_out)
 {
-   const long long blocks = (n + HS_WORD_BLOCK_KEYS - 1) / HS_WORD_BLOCK_KEYS;
-   hipLaunchKernelGGL(k_assign_words, dim3((uint32_t)blocks), dim3(HS_WORD_BLOCK_WAVES * 64), 0, st, (const uint8_t *)d_desc, n, stride, offset,
-                      (const hs_v4i *)tiles, (const int32_t *)norms, n_tiles, (int32_t *)d_out);
+   launch_word_kernel(k_assign_words, st, word_waves(n), (const uint8_t *)d_desc, n, stride, offset, (const hs_v4i *)tiles, (const int32_t *)norms, n_tiles,
+                      (int32_t *)d_out);
 }
 
 // k_assign_neighbours against the same: the R least (dist2, row) per key into d_out [n][R][2], rank 0 into d_words [n][2] as well
@@ -1330,10 +1339,9 @@ void launch_assign_kernel(hipStream_t st, const void *tiles, const void *norms, 
 void launch_neighbours_kernel(hipStream_t st, const void *tiles, const void *norms, int n_tiles, const void *d_desc, long long n, long long stride, long long offset,
                               int R, void *d_out, void *d_words)
 {
-   const long long blocks = (n + HS_WORD_BLOCK_KEYS - 1) / HS_WORD_BLOCK_KEYS;
    const auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(HS_WORD_BLOCK_WAVES * 64), 0, st, (const uint8_t *)d_desc, n, stride, offset, (const hs_v4i *)tiles,
-                         (const int32_t *)norms, n_tiles, R, (int32_t *)d_out, (int32_t *)d_words);
+      launch_word_kernel(kernel, st, word_waves(n), (const uint8_t *)d_desc, n, stride, offset, (const hs_v4i *)tiles, (const int32_t *)norms, n_tiles, R,
+                         (int32_t *)d_out, (int32_t *)d_words);
    };
    if (R <= 2) launch(k_assign_neighbours<2>);
    else if (R <= 4) launch(k_assign_neighbours<4>);
@@ -1368,9 +1376,8 @@ CellsDevice cells_device(void *layer, const CellLayerArrays &a, int cells, void 
 // entry key * used + rank into d_out
 void launch_probe_kernel(hipStream_t st, const CellsDevice &d, const void *d_desc, long long n, long long stride, long long offset, int used, void *d_out)
 {
-   const long long blocks = (n + HS_WORD_BLOCK_KEYS - 1) / HS_WORD_BLOCK_KEYS;
-   hipLaunchKernelGGL(k_probe_cells, dim3((uint32_t)blocks), dim3(HS_WORD_BLOCK_WAVES * 64), 0, st, (const uint8_t *)d_desc, n, stride, offset,
-                      (const hs_v4i *)d.tiles, (const int32_t *)d.norms, d.n_tiles, used, (int32_t *)d_out);
+   launch_word_kernel(k_probe_cells, st, word_waves(n), (const uint8_t *)d_desc, n, stride, offset, (const hs_v4i *)d.tiles, (const int32_t *)d.norms, d.n_tiles,
+                      used, (int32_t *)d_out);
 }
 
 // the first two steps of an assignment through cells, for 1 <= n * used <= 2^24 entries (used = 1: an entry is a key): every key's
@@ -1403,17 +1410,16 @@ void launch_cells_fine(hipStream_t st, const CellsDevice &d, const void *tiles, 
                        void *d_out, int used = 1)
 {
    const long long items = cells_probe_item_bound(n, used, d.c);
-   const long long blocks = (items + HS_WORD_BLOCK_WAVES - 1) / HS_WORD_BLOCK_WAVES;
+   const auto launch = [&](auto kernel, int32_t *out) {
+      launch_word_kernel(kernel, st, items, (const uint8_t *)d_desc, stride, offset, (const uint32_t *)d.perm, (const uint32_t *)d.cursor, d.slots,
+                         (const uint32_t *)d.item_first, d.first, d.c, (const hs_v4i *)tiles, (const int32_t *)norms, out, used);
+   };
    if (used > 1) {
-      hipLaunchKernelGGL(k_assign_words_cells<true>, dim3((uint32_t)blocks), dim3(HS_WORD_BLOCK_WAVES * 64), 0, st, (const uint8_t *)d_desc, stride, offset,
-                         (const uint32_t *)d.perm, (const uint32_t *)d.cursor, d.slots, (const uint32_t *)d.item_first, d.first, d.c, (const hs_v4i *)tiles,
-                         (const int32_t *)norms, d.fine, used);
+      launch(k_assign_words_cells<true>, d.fine);
       hipLaunchKernelGGL(k_merge_probes, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, (const int32_t *)d.fine, n, used, (int32_t *)d_out);
       return;
    }
-   hipLaunchKernelGGL(k_assign_words_cells<false>, dim3((uint32_t)blocks), dim3(HS_WORD_BLOCK_WAVES * 64), 0, st, (const uint8_t *)d_desc, stride, offset,
-                      (const uint32_t *)d.perm, (const uint32_t *)d.cursor, d.slots, (const uint32_t *)d.item_first, d.first, d.c, (const hs_v4i *)tiles,
-                      (const int32_t *)norms, (int32_t *)d_out, 1);
+   launch(k_assign_words_cells<false>, (int32_t *)d_out);
 }
 
 // the context's assignment with a layer set: slices of at most 2^24 entries (what the scratch is ever sized for; P' = min(probes, C)
